@@ -12,10 +12,17 @@ per GPU); RCCL -- bound through the C-ABI (ci_comm_*), no PyTorch in this proces
 for the barrier / max-over-ranks timing and, after the timed region, to gather per-chain blocks
 from HBM and all-reduce the diagnostics' partial sums.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--sampler gibbs|hmc]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--sampler gibbs|hmc] [--dump-outputs DIR]
+                  [--full]
       N > 1 without a launcher: bench.py starts its own N ranks (one process per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
       (RANK / LOCAL_RANK / WORLD_SIZE from the environment; torch itself is never imported)
+
+A plain run sets up, warms up, times K steps and prints one JSON line (`value`, `ms_per_step`, the
+roofline of the timed kernels).  `--dump-outputs DIR` writes the result arrays of the last timed
+step to DIR/<name>.npy.  `--full` adds, after the timed region, everything the headline does not
+need: the kernel-only rate, split-R-hat / ESS over the gathered chains, roofline.traffic measured
+by rocprofv3 counter passes, the CPU baseline and the other BASELINE configs.
 """
 import argparse
 import json
@@ -40,6 +47,8 @@ CFG = dict(T=1000, covariates=10, has_slope=1, num_results=1000, num_warmup=112,
            chains_per_gpu=8, data_seed=2024, seed=(0, 20240927),
            hmc_warmup=500, hmc_leapfrog=15, chunk_draws=32)
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: all files together
+DUMP_SEED = 20241016            # the fixed sample of draws when the arrays exceed that
 
 
 def _cpu_chain(sampler, y, mask, X, spec, S, W, chain):
@@ -248,6 +257,10 @@ class _GibbsFit:
     res = self._into[1]
     return {k: res[k][0] for k in ("observation_noise_scale", "level_scale", "posterior_means")}
 
+  def outputs(self):
+    """Every result array the last run_and_fetch delivered (ci_outputs, [1, C, ...])."""
+    return dict(self._into[1])
+
   def note(self, C):
     return ("one persistent workgroup per chain: %d of 256 CUs busy; the fit is bound by the "
             "(W+S)-long sequential Gibbs dependency, not by HBM (DESIGN.md)" % C)
@@ -272,7 +285,8 @@ class _HmcFit:
     return {"kernel": hmc_ms, "latents": lat_ms}
 
   def fetch(self):
-    _, _, _, res = self.sess.hmc_fetch()
+    self._fetched = self.sess.hmc_fetch()
+    res = self._fetched[3]
     return {k: res[k][0] for k in ("observation_noise_scale", "level_scale", "posterior_means")}
 
   def run_and_fetch(self):
@@ -283,10 +297,38 @@ class _HmcFit:
   def last_small(self):
     return self._last
 
+  def outputs(self):
+    """Everything the last fetch delivered: the parameter draws, acceptance rates, step sizes and
+    the sample container ([1, C, ...])."""
+    draws, acc, eps, res = self._fetched
+    return dict(res, draws=draws, accept_rate=acc, step_size=eps)
+
   def note(self, C):
     return ("one persistent workgroup per chain (%d of 256 CUs) runs (W+S) x leapfrog dependent "
             "score evaluations; the latent / predictive pass (one workgroup per draw) fills the "
             "chip; `achieved` counts the fit's algorithmic bytes over BOTH kernels' time" % C)
+
+
+def _dump_outputs(arrays, out_dir, num_results):
+  """Writes the result arrays of one step to out_dir/<name>.npy, float32 / float64 as delivered.
+  When they exceed DUMP_LIMIT_BYTES in all, every array with a draw axis ([B, C, S, ...]) keeps the
+  same fixed, seeded, sorted sample of draws, sized so that the files take at most half of that."""
+  arrays = {k: np.asarray(a) for k, a in arrays.items() if np.size(a)}
+  total = sum(a.nbytes for a in arrays.values())
+  if total > DUMP_LIMIT_BYTES:
+    per_draw = [k for k, a in arrays.items() if a.ndim >= 4 and a.shape[2] == num_results]
+    rest = total - sum(arrays[k].nbytes for k in per_draw)
+    keep = int(num_results * (DUMP_LIMIT_BYTES // 2 - rest) / (total - rest))
+    if keep < 1:
+      raise SystemExit(f"--dump-outputs: {rest} bytes without a draw axis exceed the budget")
+    draws = np.sort(np.random.default_rng(DUMP_SEED).choice(num_results, keep, replace=False))
+    for k in per_draw:
+      arrays[k] = arrays[k][:, :, draws]
+  os.makedirs(out_dir, exist_ok=True)
+  for k, a in arrays.items():
+    if a.dtype not in (np.float32, np.float64):
+      a = a.astype(np.float64)
+    np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
 
 
 def _roof(nbytes, ms):
@@ -417,11 +459,17 @@ def main():
   ap.add_argument("--steps", type=int, default=None)
   ap.add_argument("--warmup", type=int, default=None)
   ap.add_argument("--sampler", choices=("gibbs", "hmc"), default="gibbs")
-  ap.add_argument("--no-cpu-baseline", action="store_true")
+  ap.add_argument("--full", action="store_true",
+                  help="after the timed region, also measure the kernel-only rate, split-R-hat / ESS, "
+                       "roofline.traffic, the CPU baseline and the other BASELINE configs")
+  ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
   ap.add_argument("--no-pmc", action="store_true",
-                  help="skip the two rocprofv3 counter passes that measure roofline.traffic")
+                  help="with --full: skip the two rocprofv3 counter passes that measure roofline.traffic")
   ap.add_argument("--no-other-configs", action="store_true",
-                  help="skip the short cfg3 / cfg4 / cfg5 measurements after the timed region")
+                  help="with --full: skip the short cfg3 / cfg4 / cfg5 measurements after the timed region")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write the result arrays of the last timed step (rank 0's chains) to "
+                       "DIR/<name>.npy; above 64 MB in all, a fixed seeded sample of the draws")
   ap.add_argument("--chains-per-gpu", type=int, default=CFG["chains_per_gpu"])
   ap.add_argument("--chunk-draws", type=int, default=CFG["chunk_draws"],
                   help="retained draws per device-to-host copy of the streamed fetch")
@@ -430,6 +478,8 @@ def main():
     args.steps = 20 if args.sampler == "gibbs" else 5
   if args.warmup is None:
     args.warmup = 3 if args.sampler == "gibbs" else 1
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be at least 1 and --warmup at least 0")
 
   # `python bench.py --gpus N` with no launcher around it: start the N ranks ourselves (one
   # process per GPU); rank 0 prints the JSON line.  Under torch.distributed.run (or any launcher
@@ -488,37 +538,41 @@ def main():
   dt = time.perf_counter() - t0
   if comm is not None:
     dt = float(comm.all_reduce([dt], _comm.MAX)[0])
+  if args.dump_outputs and rank == 0:
+    _dump_outputs(fit.outputs(), args.dump_outputs, CFG["num_results"])
 
-  # ---- after the timed region: kernel-only rate, chain gather + diagnostics
-  t1 = time.perf_counter()
-  n_k = 3
-  for _ in range(n_k):
-    fit.run()
-  dt_kernel = (time.perf_counter() - t1) / n_k
-  local = fit.last_small()
-  # chain gather + split-R-hat / ESS across ranks: all-gather of the blocks still resident in HBM
-  # (ncclAllGather on the sessions' device buffers) + ONE all-reduce of the partial sums
-  from causalimpact import _distributed  # pylint: disable=import-outside-toplevel
+  if args.full:
+    # ---- after the timed region: kernel-only rate, chain gather + diagnostics
+    t1 = time.perf_counter()
+    n_k = 3
+    for _ in range(n_k):
+      fit.run()
+    dt_kernel = (time.perf_counter() - t1) / n_k
+    local = fit.last_small()
+    # chain gather + split-R-hat / ESS across ranks: all-gather of the blocks still resident in HBM
+    # (ncclAllGather on the sessions' device buffers) + ONE all-reduce of the partial sums
+    from causalimpact import _distributed  # pylint: disable=import-outside-toplevel
 
-  def resident(key):
-    if comm is None:
-      return None
-    g = comm.session_all_gather(fit.sess, key)             # [world, 1, C, ...]
-    return g.reshape((world * C,) + g.shape[3:])
+    def resident(key):
+      if comm is None:
+        return None
+      g = comm.session_all_gather(fit.sess, key)             # [world, 1, C, ...]
+      return g.reshape((world * C,) + g.shape[3:])
 
-  comb = _distributed.fit_sharded(lambda first, count: local, world * C,
-                                  gather_keys=("posterior_means",), comm=comm, resident=resident)
-  rhat = comb["split_rhat"]
-  ess = {"bulk": comb["ess_bulk"], "tail": comb["ess_tail"]}
-  assert comb["posterior_means"].shape == (world * C, CFG["T"])
+    comb = _distributed.fit_sharded(lambda first, count: local, world * C,
+                                    gather_keys=("posterior_means",), comm=comm, resident=resident)
+    rhat = comb["split_rhat"]
+    ess = {"bulk": comb["ess_bulk"], "tail": comb["ess_tail"]}
+    assert comb["posterior_means"].shape == (world * C, CFG["T"])
 
   samples_per_step = world * C * CFG["num_results"]
   value = samples_per_step * args.steps / dt
   k_ms = float(np.mean([sum(k.values()) for k in kernel_ms]))
   alg_bytes = fit.sess.algorithmic_bytes()
   achieved = alg_bytes / (k_ms * 1e-3) / 1e9
-  traffic, traffic_src = None, None
-  if rank == 0 and world == 1 and not args.no_pmc and os.environ.get("CI_BENCH_INNER") != "1":
+  if not args.full:
+    traffic, traffic_src = None, "not measured in a plain run (--full measures it by rocprofv3 counter passes)"
+  elif rank == 0 and world == 1 and not args.no_pmc and os.environ.get("CI_BENCH_INNER") != "1":
     traffic, why = _measure_traffic(args.sampler)
     traffic_src = why
     if traffic is None:
@@ -554,21 +608,22 @@ def main():
                                  f"{comm.ranks_seen}" if comm is not None else "none"),
                  "ranks_seen": comm.ranks_seen if comm is not None else 1},
       "roofline": roof,
-      "kernel_only_value": C * CFG["num_results"] / dt_kernel,
-      "split_rhat": rhat, "ess": ess,
   }
-  if rank == 0 and world == 1 and not args.no_cpu_baseline:
-    out["cpu_baseline"] = _cpu_baseline(args.sampler, y, mask, X)
-  elif rank == 0:
-    # not `null` without comment (round-4 review): the object says why there is no value here
-    out["cpu_baseline"] = {"value": None, "unit": "posterior samples/sec", "cores": 0, "kind": "port",
-                           "sample": ("not measured in this run: the CPU leg is timed on rank 0 of the "
-                                      "N=1 run only (--no-cpu-baseline / N > 1); see the N=1 line")}
-    out["config"]["n_gt_1_note"] = ("cpu_baseline is timed at N=1 only; roofline.traffic on this "
-                                    "line is the committed single-GPU counter figure (per GPU), not "
-                                    "measured in this run")
-  if (rank == 0 and world == 1 and comm is None and args.sampler == "gibbs" and not args.no_other_configs
-      and os.environ.get("CI_BENCH_INNER") != "1"):
+  if args.full:
+    out["kernel_only_value"] = C * CFG["num_results"] / dt_kernel
+    out["split_rhat"], out["ess"] = rhat, ess
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+      out["cpu_baseline"] = _cpu_baseline(args.sampler, y, mask, X)
+    elif rank == 0:
+      # not `null` without comment (round-4 review): the object says why there is no value here
+      out["cpu_baseline"] = {"value": None, "unit": "posterior samples/sec", "cores": 0, "kind": "port",
+                             "sample": ("not measured in this run: the CPU leg is timed on rank 0 of the "
+                                        "N=1 run only (--no-cpu-baseline / N > 1); see the N=1 line")}
+      out["config"]["n_gt_1_note"] = ("cpu_baseline is timed at N=1 only; roofline.traffic on this "
+                                      "line is the committed single-GPU counter figure (per GPU), not "
+                                      "measured in this run")
+  if (args.full and rank == 0 and world == 1 and comm is None and args.sampler == "gibbs"
+      and not args.no_other_configs and os.environ.get("CI_BENCH_INNER") != "1"):
     # the other BASELINE configs, after the timed region (the headline value / config stay cfg2)
     fit.sess.close()
     fit.sess = None

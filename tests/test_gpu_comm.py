@@ -232,7 +232,7 @@ def test_bench_single_rank_through_the_rccl_path_matches_plain_bench():
   """bench.py with CI_BENCH_FORCE_DIST=1: the N > 1 code path (C-ABI communicator, barrier,
   max-reduce of the time, gather from HBM, diagnostics all-reduce) with one rank."""
   env = dict(os.environ, CI_BENCH_FORCE_DIST="1")
-  cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "3",
+  cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "3", "--full",
          "--no-cpu-baseline", "--no-pmc"]
   # the JSON line must be the LAST line of the output (librccl's banner is flushed before it)
   forced = json.loads(subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600,
@@ -256,7 +256,8 @@ def test_bench_gpus_2_starts_its_own_ranks_and_reports_the_whole_job():
   env = dict(os.environ, CI_COMM_TRANSPORT="host", CI_COMM_DEVICES="0,0")
   env.pop("WORLD_SIZE", None)
   env.pop("RANK", None)
-  cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+  cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+         "--full"]
   out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, check=True).stdout
   line = json.loads(out.strip().splitlines()[-1])
   assert line["n_gpus"] == 2 and line["scaling"] == "weak"
@@ -283,7 +284,7 @@ def test_bench_under_torch_distributed_run_the_drivers_command_line():
   env.update(CI_COMM_DEVICES="0,0", CI_COMM_INIT_TIMEOUT_S="60")
   cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-         "--gpus", "2", "--steps", "2", "--warmup", "1"]
+         "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
   r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
   assert r.returncode == 0, r.stderr[-3000:]
   lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
