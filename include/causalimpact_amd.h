@@ -115,6 +115,11 @@ typedef struct ci_problem {
  * design columns, which by default run on the quad-split kernel of csrc/ci_wide.h (the faster one
  * since round 6: profiles/).  Test / diagnostic knob. */
 #define CI_FLAG_CLUSTER_SEASONAL 64
+/* Seasonal models with a state of at most 64 components: run on the multi-wavefront build of the
+ * sequential kernel (csrc/ci_seasonal_mw.h), which every state of 65-256 components takes anyway.
+ * Same model, same random numbers; the sums differ from the one-wavefront kernel's only in float
+ * summation order.  Test / diagnostic knob. */
+#define CI_FLAG_MULTIWAVE_SEASONAL 128
 
 /* Caller-allocated result buffers (float32, chain-major so per-device shards
  * are contiguous).  == GibbsSamplerState stack + (means, trajectories) returned
@@ -159,6 +164,10 @@ int ci_host_free(void* ptr);
  *   X     [B,T,P]  float32 row-major design, intercept last; NULL when P == 0
  *   season_change [K,T] uint8, 1 where step t is the last step of a season of block k
  *   params[B]
+ * The seasonal state, 1 (+1 slope) + sum_k num_seasons[k] components, holds at most 256: states of
+ * 65-256 components (e.g. an hour-of-week block of 168 seasons) run on the multi-wavefront kernel
+ * (csrc/ci_seasonal_mw.h); wider ones are refused.  ci_fit_gibbs_f64 and the log-likelihood / HMC
+ * sessions hold at most 64.
  * Replaces _run_gibbs_sampler (causalimpact_lib.py:345-395). */
 int ci_fit_gibbs(const ci_problem* problem, const float* y, const uint8_t* mask, const float* X,
                  const uint8_t* season_change, const ci_series_params* params,

@@ -27,6 +27,7 @@
 #include "ci_wide_score.h"
 
 extern "C" void* ci_gibbs_seasonal_fn(int);
+extern "C" void* ci_gibbs_seasonal_mw_fn(int);
 extern "C" void* ci_gibbs_seasonal_tp_fn_nq2(void);
 extern "C" void* ci_gibbs_seasonal_tp_fn_nq3(void);
 extern "C" void* ci_gibbs_seasonal_tp_fn_nq4(void);
@@ -374,7 +375,9 @@ void* pick_wide_bigp_kernel(int has_slope, int num_seasons) {
 }
 bool wide_bigp_ok(const ci_problem* pb) {
   if (pb->P <= ci::MAXP || pb->T < 64) return false;
-  if (pb->flags & (CI_FLAG_SEQUENTIAL_SEASONAL | CI_FLAG_CLUSTER_SEASONAL | CI_FLAG_SEASONAL_WORKSPACE)) return false;
+  if (pb->flags & (CI_FLAG_SEQUENTIAL_SEASONAL | CI_FLAG_CLUSTER_SEASONAL | CI_FLAG_SEASONAL_WORKSPACE |
+                   CI_FLAG_MULTIWAVE_SEASONAL))
+    return false;
   if (!(pb->num_blocks == 0 || (pb->num_blocks == 1 && pb->num_seasons[0] >= 2 && pb->num_seasons[0] <= 7)))
     return false;
   const int d = (pb->has_slope ? 2 : 1) + (pb->num_blocks == 1 ? pb->num_seasons[0] - 1 : 1);
@@ -383,7 +386,7 @@ bool wide_bigp_ok(const ci_problem* pb) {
 bool use_wide(const ci_problem* pb) {
   if (pb->num_blocks == 1 && pb->P > ci::MAXP) return wide_bigp_ok(pb);
   return pb->num_blocks == 1 && pb->P <= ci::MAXP && !(pb->flags & CI_FLAG_SEQUENTIAL_SEASONAL) &&
-         !(pb->flags & CI_FLAG_CLUSTER_SEASONAL) &&
+         !(pb->flags & CI_FLAG_CLUSTER_SEASONAL) && !(pb->flags & CI_FLAG_MULTIWAVE_SEASONAL) &&
          pick_wide_kernel(pb->has_slope, pb->num_seasons[0]) != nullptr;
 }
 int wide_steps_per_thread(int T) {
@@ -476,6 +479,7 @@ struct ci_session {
   // time-parallel seasonal kernel
   bool wide = false;
   bool seasonal_gws = false;           // sequential seasonal kernel with its arrays over time in HBM
+  bool mw = false;                     // ... its multi-wavefront build (ci_seasonal_mw.h)
   size_t seasonal_ws_bytes = 0;
   int Lc = 0;
   DevBuf<float> ws;
@@ -608,7 +612,10 @@ static int validate(const ci_problem* pb) {
       if (wide_steps_per_thread(pb->T) > ci::WIDE_MAX_LC)
         return fail("T=%d exceeds the time-parallel seasonal path (max %d)", pb->T, ci::NT * ci::WIDE_MAX_LC);
     } else {
-      if (dfull > 64) return fail("seasonal state too wide for one wavefront: %d > 64", dfull);
+      // (65-256 components: the multi-wavefront build of the sequential kernel, ci_seasonal_mw.h)
+      if (dfull > ci::MW_MAXD)
+        return fail("seasonal state too wide: %d > %d components (the limit of the multi-wavefront "
+                    "seasonal kernel)", dfull, ci::MW_MAXD);
     }
   }
   if (pb->num_warmup < 0 || pb->num_results < 1) return fail("need num_warmup >= 0, num_results >= 1");
@@ -738,11 +745,15 @@ int ci_session_create(const ci_problem* pb, const float* y, const uint8_t* mask,
                               : pick_wide_kernel(pb->has_slope, pb->num_seasons[0]));
     } else {
       // arrays over time in LDS when the whole layout fits (fastest), else in a per-chain HBM
-      // workspace: no bound on the series length, and room in LDS for the P > 16 regression block
-      const ci::SLayout in_lds = ci::make_slayout(T, P, K, s->D_full, s->dred, pb->has_slope, 0);
+      // workspace: no bound on the series length, and room in LDS for the P > 16 regression block.
+      // States of more than 64 components (or CI_FLAG_MULTIWAVE_SEASONAL): the multi-wavefront
+      // build, a function of the model alone like every route
+      s->mw = s->D_full > 64 || (pb->flags & CI_FLAG_MULTIWAVE_SEASONAL) != 0;
+      const int nwv = s->mw ? ci::MW_NWV : 1;
+      const ci::SLayout in_lds = ci::make_slayout(T, P, K, s->D_full, s->dred, pb->has_slope, 0, nwv);
       s->seasonal_gws = in_lds.total > 150 * 1024 || (pb->flags & CI_FLAG_SEASONAL_WORKSPACE) != 0;
       const ci::SLayout lay = ci::make_slayout(T, P, K, s->D_full, s->dred, pb->has_slope,
-                                               s->seasonal_gws ? 1 : 0);
+                                               s->seasonal_gws ? 1 : 0, nwv);
       s->lds_bytes = lay.total;
       s->seasonal_ws_bytes = ((lay.t_total + 255) & ~(size_t)255) + (bigp ? ci::bigp_workspace_bytes(P) : 0);
     }
@@ -756,7 +767,7 @@ int ci_session_create(const ci_problem* pb, const float* y, const uint8_t* mask,
     // (measured, round 5: below ~110 steps the one-wavefront kernel is as fast or faster -- 158 us
     // against 171 us at T = 96 on the 4+7+6 model, 202 us against 174 us at T = 128)
     const int tp_min_t = P > ci::MAXP ? 64 : 112;
-    if (!s->wide && s->D_full <= ci::TP_MAXD && T >= tp_min_t && !(pb->flags & CI_FLAG_SEQUENTIAL_SEASONAL) &&
+    if (!s->wide && !s->mw && s->D_full <= ci::TP_MAXD && T >= tp_min_t && !(pb->flags & CI_FLAG_SEQUENTIAL_SEASONAL) &&
         !(pb->flags & CI_FLAG_SEASONAL_WORKSPACE)) {
       int num_cus = 256;
       (void)hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, pb->device);
@@ -788,11 +799,16 @@ int ci_session_create(const ci_problem* pb, const float* y, const uint8_t* mask,
       return fail("seasonal model needs %zu bytes of LDS per chain (max 163840): fewer covariates "
                   "or a narrower seasonal state", s->lds_bytes);
     }
-    if (!s->wide && !s->tp) s->fn = (KernelFn)ci_gibbs_seasonal_fn((s->seasonal_gws ? 1 : 0) | (bigp ? 2 : 0));
+    if (!s->wide && !s->tp) {
+      const int which = (s->seasonal_gws ? 1 : 0) | (bigp ? 2 : 0);
+      s->fn = (KernelFn)(s->mw ? ci_gibbs_seasonal_mw_fn(which) : ci_gibbs_seasonal_fn(which));
+    }
     char nm[96];
     if (s->tp) snprintf(nm, sizeof(nm), "ci::gibbs_seasonal_tp_kernel<%d> %d chunks x%d", ci::tp_nr(s->D_full) / 4,
                         s->Lc * ci::TP_NWV, s->cluster);
     else if (s->wide) snprintf(nm, sizeof(nm), bigp ? "ci::gibbs_wide_kernel<%d,%d,bigp>" : "ci::gibbs_wide_kernel<%d,%d>", D, pb->num_seasons[0]);
+    else if (s->mw) snprintf(nm, sizeof(nm), "ci::gibbs_seasonal_kernel<%s,%s,%d> (multi-wave)",
+                             s->seasonal_gws ? "true" : "false", bigp ? "true" : "false", ci::MW_NWV);
     else snprintf(nm, sizeof(nm), "ci::gibbs_seasonal_kernel<%s,%s>", s->seasonal_gws ? "true" : "false",
                   bigp ? "true" : "false");
     s->kernel_name = nm;
@@ -981,7 +997,8 @@ static int session_launch(ci_session* s) {
       HIP_TRY(hipMemsetAsync(s->csync.p, 0, s->csync.n * sizeof(int), s->stream));
       grid = (grid + 7) / 8 * 8 * s->cluster;       // (chain, role) <- workgroup id: see ci_wide.h
     }
-    hipLaunchKernelGGL((void (*)(ci::SArgs))s->fn, dim3(grid), dim3(s->tp ? ci::TP_NT : (s->wide ? ci::NT : 64)),
+    const int nthr = s->tp ? ci::TP_NT : (s->wide ? ci::NT : (s->mw ? 64 * ci::MW_NWV : 64));
+    hipLaunchKernelGGL((void (*)(ci::SArgs))s->fn, dim3(grid), dim3(nthr),
                        s->lds_bytes, s->stream, sa);
   } else {
     if (s->profile && s->eight_waves && s->fn_prof8) {
@@ -1359,7 +1376,9 @@ int ci_fit_gibbs_f64(const ci_problem* pb, const double* y, const uint8_t* mask,
   const int K = pb->num_blocks, has_slope = pb->has_slope ? 1 : 0;
   int dfull = has_slope ? 2 : 1, dred = dfull;
   for (int k = 0; k < K; ++k) { dfull += pb->num_seasons[k]; dred += pb->num_seasons[k] - 1; }
-  if (dfull > 64) return fail("seasonal state too wide for one wavefront: %d > 64", dfull);
+  if (dfull > 64)
+    return fail("seasonal state too wide for one wavefront: %d > 64 (dtype=float64 holds states of at "
+                "most 64 components; the float32 Gibbs sampler up to %d)", dfull, ci::MW_MAXD);
   HIP_TRY(hipSetDevice(pb->device));
   // LDS first: arrays over time AND the regression block (P <= 32) when both fit, then the arrays
   // over time alone; else the HBM workspace for the arrays (regression still in LDS if small)
@@ -1629,7 +1648,10 @@ int ci_ll_session_create2(const ci_problem* pb, const ci_series_params* params, 
                        wide_steps_per_thread(pb->T) <= ci::WIDE_MAX_LC &&
                        (pb->num_blocks == 0 ||
                         (pb->num_blocks == 1 && pb->num_seasons[0] >= 2 && pb->num_seasons[0] <= 7));
-  if (seq && !wide_ll && dfull > 64) return fail("seasonal state too wide for one wavefront: %d > 64", dfull);
+  if (seq && !wide_ll && dfull > 64)
+    return fail("seasonal state too wide for one wavefront: %d > 64 (the log-likelihood and "
+                "sampler=\"hmc\" paths hold states of at most 64 components; the Gibbs sampler up to %d)",
+                dfull, ci::MW_MAXD);
   HIP_TRY(hipSetDevice(pb->device));
   ci_ll_session* s = new ci_ll_session();
   LlSessionGuard guard{s};

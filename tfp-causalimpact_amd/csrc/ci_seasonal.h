@@ -25,6 +25,11 @@
 namespace ci {
 
 constexpr int SMAXK = 8;
+// The multi-wavefront build (ci_seasonal_mw.h): MW_NWV wavefronts per chain, states of up to
+// MW_MAXD components, MW_LDS_FLOATS floats of step vectors and scalars in LDS.
+constexpr int MW_NWV = 4;
+constexpr int MW_MAXD = 64 * MW_NWV;
+constexpr int MW_LDS_FLOATS = MW_MAXD + 96;
 
 // v_readlane on a float (the builtin is typed int: passing a float would convert by value)
 __device__ __forceinline__ float readlane_f(float v, int l) {
@@ -78,8 +83,10 @@ struct SLayout {
 // global_ws: the arrays over time live in a per-chain HBM workspace (offsets from its base,
 // t_total bytes) instead of LDS, which removes the LDS bound on the series length; the
 // LDS-resident one-wavefront regression block of P > 16 needs its buffers in LDS as well.
+// nwv > 1: the multi-wavefront build (ci_seasonal_mw.h): the covariance as a packed lower
+// triangle and the step vectors of up to MW_MAXD components in place of the one-wave mirror.
 __host__ __device__ inline SLayout make_slayout(int T, int P, int K, int D, int dred,
-                                                int has_slope, int global_ws = 0) {
+                                                int has_slope, int global_ws = 0, int nwv = 1) {
   SLayout l;
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 15) & ~(size_t)15; return r; };
@@ -99,10 +106,17 @@ __host__ __device__ inline SLayout make_slayout(int T, int P, int K, int D, int 
   l.nz = take(big ? sizeof(int) * Pp : 16);
   l.perm = take(big ? sizeof(int) * Pp : 16);
   l.idx = take(big ? sizeof(int) * Pp : 16);
-  // the covariance (mirror of the lanes' register rows): D rows of stride ((D + 7) & ~7) + 4 floats
-  l.Pa = take(sizeof(float) * D * ((((size_t)D + 7) & ~(size_t)7) + 4));
-  // P z [72], the blocks' shock vectors [SMAXK][72], the observed columns [16]
-  l.pzv = take(sizeof(float) * (72 + SMAXK * 72 + 16)); l.zi = take(sizeof(float) * (dred + 1));
+  // the covariance (one wave: mirror of the lanes' register rows, D rows of stride
+  // ((D + 7) & ~7) + 4 floats)
+  if (nwv > 1) {
+    l.Pa = take(sizeof(float) * ((size_t)D * (D + 1) / 2));
+    l.pzv = take(sizeof(float) * MW_LDS_FLOATS);
+  } else {
+    l.Pa = take(sizeof(float) * D * ((((size_t)D + 7) & ~(size_t)7) + 4));
+    // P z [72], the blocks' shock vectors [SMAXK][72], the observed columns [16]
+    l.pzv = take(sizeof(float) * (72 + SMAXK * 72 + 16));
+  }
+  l.zi = take(sizeof(float) * (dred + 1));
   l.x0r = take(sizeof(float) * (dred + 1));
   l.d2 = take(sizeof(float) * SMAXK);
   l.w = take(sizeof(float) * (Pp > 16 ? Pp : 16));
@@ -289,12 +303,24 @@ static __device__ __noinline__ void seasonal_filter_pass(const SeasFilterArgs& p
   }
 }
 
+}  // namespace ci
+#include "ci_seasonal_mw.h"
+namespace ci {
+
 // BIGP: the P > MAXP build (regression block in the HBM workspace, spike_slab_draw_big); its own
 // instantiation so that the call does not cost the P <= MAXP builds a stack frame.
-template <bool GWS, bool BIGP = false>
-__global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
+// NWV > 1: the multi-wavefront build (ci_seasonal_mw.h), states of up to 64 NWV components.  `lane`
+// is then the thread's component; wavefront 0 (w0) runs everything outside the four passes.
+template <bool GWS, bool BIGP = false, int NWV = 1>
+__global__ __launch_bounds__(64 * NWV) void gibbs_seasonal_kernel(SArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x;
+  constexpr int NT_ = 64 * NWV;
+  const bool w0 = NWV == 1 || lane < 64;
+  auto block_sync = []() {
+    if constexpr (NWV == 1) wave_sync();
+    else __syncthreads();
+  };
   const KArgs& g = a.k;
   const int T = g.T, P = g.P, K = a.K;
   const int series = blockIdx.x / g.C, chain = blockIdx.x % g.C;
@@ -311,7 +337,7 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
       if (k < K) { D += nsz[k]; rr += nsz[k] - 1; }
     }
   }
-  const SLayout L = make_slayout(T, P, K, D, a.dred, a.has_slope, GWS ? 1 : 0);
+  const SLayout L = make_slayout(T, P, K, D, a.dred, a.has_slope, GWS ? 1 : 0, NWV);
   // the arrays over time: LDS, or (GWS) this chain's slice of the HBM workspace -- every access
   // below is either one 16-byte row per 4 steps or lane-contiguous, and a chain only ever reads
   // what it wrote, so the slice stays in this XCD's L2
@@ -375,6 +401,8 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
   const int blk0 = blk >= 0 ? blk : 0;
 
   // ---- stage constants
+  double n_changes[SMAXK];
+  if (w0) {
   for (int t = lane; t < TS; t += 64) {
     const bool in = t < T;
     const bool m = in ? g.mask[(size_t)series * T + t] != 0 : true;
@@ -398,7 +426,6 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
     }
   for (int j = lane; j < (P > 16 ? P : 16); j += 64) R.w[j] = 0.f;
   wave_sync();
-  double n_changes[SMAXK];
 #pragma unroll
   for (int k = 0; k < SMAXK; ++k) {
     n_changes[k] = 0.0;
@@ -409,6 +436,7 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
     }
   }
 
+  }  // w0
   double obs_scale = sp.obs_scale0, level_scale = sp.level_scale0, slope_scale = sp.slope_scale0;
   double drift[SMAXK];
 #pragma unroll
@@ -433,10 +461,14 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
     obs_scale = lth[0]; level_scale = lth[1]; slope_scale = lth[2];
 #pragma unroll
     for (int k = 0; k < SMAXK; ++k) if (k < K) drift[k] = lth[3 + k];
-    for (int j = lane; j < P; j += 64) R.w[j] = (float)lth[3 + K + j];
+    if (w0) for (int j = lane; j < P; j += 64) R.w[j] = (float)lth[3 + K + j];
     wave_sync();
   }
+  CI_LDS float* mwv = (CI_LDS float*)pzv;      // NWV > 1: the step area of ci_seasonal_mw.h
+  (void)mwv;
   for (int it = 0; it <= n_iter; ++it) {
+    double emit_obs = obs_scale;
+    if (w0) {
     // ---- (1) X~'targets, y'y from the current latents
     if (!lat) {
       float yty = 0.f;
@@ -464,7 +496,7 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
     }
     prof.tick(20);
     // ---- (2) scale draws of iteration it-1, regression draw of iteration it
-    double emit_obs = obs_scale;
+    emit_obs = obs_scale;
     if (it > 0) {
       const uint32_t pit = (uint32_t)(it - 1) + itb;
       if (!lat) {
@@ -479,7 +511,9 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
 #pragma unroll
       for (int k = 0; k < SMAXK; ++k)
         if (k < K) {
-          const double v_d = (double)readlane_f(ssd, off[k]);
+          double v_d;
+          if constexpr (NWV == 1) v_d = (double)readlane_f(ssd, off[k]);
+          else v_d = (double)mwv[MW_DST + k];
           const double gk = gamma_wave(ss.drift_conc + 0.5 * n_changes[k], rng, pit,
                                        SITE_DRIFT_SCALE, (uint32_t)k, lane);
           const double sd = (double)__fsqrt_rn((float)((ss.drift_scale + 0.5 * v_d) * fast_rcp(gk)));
@@ -535,7 +569,9 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
         }
       }
     }
+    }  // w0
     if (it == n_iter) break;
+    if (w0) {
     if (P > 0 && !lat) {
       const double g_obs = gamma_wave(sp.obs_conc + 0.5 * sp.n_obs, rng, (uint32_t)it, SITE_OBSVAR, 0, lane);
       if (P <= 16)
@@ -571,26 +607,43 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
           *reinterpret_cast<float4*>(zk + k * TS + 4 * c) = make_float4(z4[0], z4[1], z4[2], z4[3]);
         }
     }
-    if (lane < a.dred) {
+    }  // w0
+    if (lane < a.dred) {     // (a.dred < 64 NWV)
       float z1[1];
       fill_normals<1>(rng, (uint32_t)it + itb, SITE_PRIOR_INIT, 0, (uint32_t)lane, z1);
       zi[lane] = z1[0];
     }
     float mydrift = 0.f;
+    if constexpr (NWV == 1) {
 #pragma unroll
-    for (int k = 0; k < SMAXK; ++k)
-      if (k < K) {
-        if (blk == k) mydrift = (float)drift[k];
-        if (lane == 0) d2[k] = (float)(drift[k] * drift[k]);
+      for (int k = 0; k < SMAXK; ++k)
+        if (k < K) {
+          if (blk == k) mydrift = (float)drift[k];
+          if (lane == 0) d2[k] = (float)(drift[k] * drift[k]);
+        }
+    } else {
+      // the other wavefronts learn this iteration's scales from wavefront 0
+#pragma unroll
+      for (int k = 0; k < SMAXK; ++k)
+        if (k < K && lane == 0) {
+          d2[k] = (float)(drift[k] * drift[k]);
+          mwv[MW_DSD + k] = (float)drift[k];
+        }
+      if (lane == 0) {
+        mwv[MW_SC] = (float)obs_scale; mwv[MW_SC + 1] = (float)level_scale; mwv[MW_SC + 2] = (float)slope_scale;
       }
-    wave_sync();
+    }
+    block_sync();
+    if constexpr (NWV > 1) {
+      if (blk >= 0) mydrift = mwv[MW_DSD + blk];
+    }
     // x+_0 = chol(P_1) z in the oracle's reduced coordinates, folded into the prior mean
     if (lane < a.dred) {
       float s = 0.f;
       for (int j = 0; j <= lane; ++j) s = fmaf(chol1[lane * a.dred + j], zi[j], s);
       x0r[lane] = s;
     }
-    wave_sync();
+    block_sync();
     float a1e = 0.f;
     if (lane == 0) a1e = (float)sp.init_level_loc + x0r[0];
     if (a.has_slope && lane == 1) a1e = x0r[1];
@@ -598,7 +651,8 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
       if (pos < nb - 1) a1e = x0r[rbase + pos];
       else { float s = 0.f; for (int q = 0; q < nb - 1; ++q) s += x0r[rbase + q]; a1e = -s; }
     }
-    const float so = (float)obs_scale, sl = (float)level_scale, ssc = (float)slope_scale;
+    float so = (float)obs_scale, sl = (float)level_scale, ssc = (float)slope_scale;
+    if constexpr (NWV > 1) { so = mwv[MW_SC]; sl = mwv[MW_SC + 1]; ssc = mwv[MW_SC + 2]; }
     const float H = so * so, ql = sl * sl, qs = ssc * ssc;
     const float* zkb = zk + blk0 * TS;
     prof.tick(22);
@@ -644,8 +698,13 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
         for (int q = 0; q < 4; ++q) {
           const int t = t4 + q;
           curw |= (uint32_t)mycur << (8 * q);
-          const float zx = zsum_slot(xp, mycur);
-          yt[q] = (at4(yv4, q) - at4(xw4, q)) - (zx + so * at4(zo4, q));
+          if constexpr (NWV == 1) {
+            const float zx = zsum_slot(xp, mycur);
+            yt[q] = (at4(yv4, q) - at4(xw4, q)) - (zx + so * at4(zo4, q));
+          } else {   // the observed components record x+; y~ is formed after the pass
+            yt[q] = xp;
+            if (blk >= 0 && pos == mycur) seas[blk * TS + t] = xp;
+          }
           if (t + 1 < T) {
             const unsigned cb = (cb4 >> (8 * q)) & 0xFFu;
             float r = xp;
@@ -663,13 +722,38 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
             xp = r;
           }
         }
-        if (lane == 0) *reinterpret_cast<float4*>(ytil + t4) = make_float4(yt[0], yt[1], yt[2], yt[3]);
+        if (lane == 0)
+          *reinterpret_cast<float4*>((NWV == 1 ? ytil : lev) + t4) = make_float4(yt[0], yt[1], yt[2], yt[3]);
         if (blk >= 0 && pos == 0) *reinterpret_cast<uint32_t*>(cidx + blk * TS + t4) = curw;
+      }
+      if constexpr (NWV > 1) {
+        // y~ = resid - Z x+ from the recorded components (lev: level, seas: each block's slot)
+        block_sync();
+        for (int t = lane; t < T; t += NT_) {
+          float zx = lev[t];
+#pragma unroll
+          for (int k = 0; k < SMAXK; ++k)
+            if (k < K) zx += seas[k * TS + t];
+          ytil[t] = (yv[t] - xw[t]) - (zx + so * zo[t]);
+        }
       }
     }
     prof.tick(23);
     // prior covariance of x_0 (c_k(0) = 0: slots are positions): sd^2 (I - 11'/n) per block
-    if (comp) {
+    if constexpr (NWV > 1) {
+      // packed column-major lower triangle (ci_seasonal_mw.h): the own row, j = 0..lane
+      if (comp) {
+        int ai = lane;
+        for (int j = 0; j <= lane; ++j) {
+          float v = 0.f;
+          if (lane == 0) v = p1l;
+          if (a.has_slope && lane == 1 && j == 1) v = p1s;
+          if (blk >= 0 && j >= boff) v = p1e * ((lane == j ? 1.f : 0.f) - rnb);
+          Pm[ai] = v;
+          ai += D - j - 1;
+        }
+      }
+    } else if (comp) {
       for (int j = D; j < DS; ++j) Prow[j] = 0.f;
       Prow[0] = lane == 0 ? p1l : 0.f;
       if (a.has_slope) Prow[1] = lane == 1 ? p1s : 0.f;
@@ -679,7 +763,7 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
           for (int q = 0; q < nsz[k]; ++q)
             Prow[off[k] + q] = (blk == k) ? p1e * ((pos == q ? 1.f : 0.f) - rnb) : 0.f;
     }
-    wave_sync();
+    block_sync();
     prof.tick(24);
     const uint8_t* cidb = cidx + blk0 * TS;      // c of this lane's block
 
@@ -692,17 +776,20 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
       fa.has_slope = a.has_slope;
       fa.a1e = a1e; fa.H = H; fa.ql = ql; fa.qs = qs; fa.myd2 = d2[blk0]; fa.rnb = rnb;
       fa.Pm = Pm; fa.pzv = pzv; fa.kf = kf; fa.vf = vf; fa.ytil = ytil; fa.cbv = cbv; fa.msk = msk; fa.cidb = cidb;
-      if (D <= 16) seasonal_filter_pass<GWS, 2>(fa);
+      if constexpr (NWV > 1) seasonal_filter_pass_mw<GWS, NWV>(fa, K);
+      else if (D <= 16) seasonal_filter_pass<GWS, 2>(fa);
       else if (D <= 24) seasonal_filter_pass<GWS, 3>(fa);
       else if (D <= 32) seasonal_filter_pass<GWS, 4>(fa);
       else seasonal_filter_pass<GWS, 8>(fa);
     }
-    wave_sync();
+    block_sync();
     prof.tick(25);
     // ---- (6) pass 2: backward recursion, rs[t] = r_{t-1}; then gd[k][t] = g . r_{t-1} per block
     // (the projection the forward reconstruction needs at season changes)
     {
       float r = 0.f;
+      int par = 0;       // NWV > 1: parity of the partial-sum slots
+      (void)par;
       for (int t4 = ((T - 1) & ~3); t4 >= 0; t4 -= 4) {
         const float4 vf4 = ld4(vf + t4);
         const uint32_t mk4 = ldb4(msk + t4), cw4 = ldb4(cidb + t4);
@@ -723,20 +810,28 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
           }
           if (((mk4 >> (8 * q)) & 0xFFu) == 0u) {
             const int mycur = (int)((cw4 >> (8 * q)) & 0xFFu);
-            const float kr = wave_sum_dpp(kfq[q] * r);
+            float kr = wave_sum_dpp(kfq[q] * r);
+            if constexpr (NWV > 1) {   // K' r over the wavefronts: partials by step parity, one barrier
+              if ((lane & 63) == 0) mwv[MW_RED + 8 * par + (lane >> 6)] = kr;
+              __syncthreads();
+              kr = mwv[MW_RED + 8 * par];
+#pragma unroll
+              for (int w = 1; w < NWV; ++w) kr += mwv[MW_RED + 8 * par + w];
+              par ^= 1;
+            }
             if (lane == 0 || (blk >= 0 && pos == mycur)) r += at4(vf4, q) - kr;
           }
           if (comp) rs[(size_t)t * D + lane] = r;
         }
       }
     }
-    wave_sync();
+    block_sync();
     // g . r_{t-1} per block, time-parallel: g = e_{slot observed at t-1} - 1/n
 #pragma unroll
     for (int k = 0; k < SMAXK; ++k)
       if (k < K) {
         const float rn = 1.0f / (float)nsz[k];
-        for (int t = lane; t < T; t += 64) {
+        for (int t = lane; t < T; t += NT_) {
           const float* rr = rs + (size_t)t * D + off[k];
           float sb = 0.f;
           for (int q = 0; q < nsz[k]; ++q) sb += rr[q];
@@ -744,7 +839,7 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
           gd[k * TS + t] = rr[cprev] - sb * rn;
         }
       }
-    wave_sync();
+    block_sync();
     prof.tick(26);
     // ---- (7) pass 3: reconstruct x^ forward, re-simulate x+, write the draw, gather statistics
     {
@@ -825,17 +920,29 @@ __global__ __launch_bounds__(64) void gibbs_seasonal_kernel(SArgs a) {
           *reinterpret_cast<float4*>(slp + t4) = make_float4(xo[0], xo[1], xo[2], xo[3]);
       }
       // the drift statistic of a block: every slot collected its own changes
+      if constexpr (NWV == 1) {
 #pragma unroll
-      for (int k = 0; k < SMAXK; ++k)
-        if (k < K) {
-          const float tot = wave_sum_dpp(blk == k ? ssd : 0.f);
-          if (lane == off[k]) ssd = tot;
-        }
+        for (int k = 0; k < SMAXK; ++k)
+          if (k < K) {
+            const float tot = wave_sum_dpp(blk == k ? ssd : 0.f);
+            if (lane == off[k]) ssd = tot;
+          }
+      } else {   // over the wavefronts: through LDS, summed in slot order by lane k of wavefront 0
+        if (comp) mwv[MW_PZ + lane] = blk >= 0 ? ssd : 0.f;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < SMAXK; ++k)
+          if (k < K && lane == k) {
+            float tot = 0.f;
+            for (int q = 0; q < nsz[k]; ++q) tot += mwv[MW_PZ + off[k] + q];
+            mwv[MW_DST + k] = tot;
+          }
+      }
     }
-    wave_sync();
+    block_sync();
     prof.tick(27);
   }
-  if (g.out_pred_mean) {
+  if (w0 && g.out_pred_mean) {
     const float inv = 1.0f / (float)(g.S > 0 ? g.S : 1);
     for (int t = lane; t < T; t += 64) g.out_pred_mean[chain_lin * T + t] *= inv;
   }
