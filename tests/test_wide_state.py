@@ -18,15 +18,17 @@ import wide_oracle
 MW = _native.FLAG_MULTIWAVE_SEASONAL
 
 
-def _inputs(T, p, has_slope, seasons, seed=7):
+def _inputs(T, p, has_slope, seasons, seed=7, edit=None):
   """The inputs of test_gpu_gibbs.py's seasonal per-draw parity: a weekly wave plus noise, and
-  masked pre-period steps."""
+  masked pre-period steps.  `edit` maps that mask (a copy) to the one used."""
   y, mask, X, _ = syn.make_sampler_inputs(T, p, seed)
   rng = np.random.default_rng(0)
   y = y + 0.8 * np.sin(2 * np.pi * np.arange(T) / 7.0) + 0.1 * rng.normal(size=T)
   if T >= 100:
     mask = mask.copy()
     mask[[2, 3, 40, T // 2]] = True
+  if edit is not None:
+    mask = np.asarray(edit(mask.copy()), bool)
   spec = orc.default_spec(y, mask, X, has_slope=bool(has_slope), seasons=seasons)
   return y, mask, X, spec
 
@@ -46,7 +48,32 @@ def _dfull(has_slope, seasons):
     (120, 4, 1, ((7, 1),)),
 ])
 def test_wide_oracle_reproduces_the_stock_oracle_bit_for_bit(T, p, has_slope, seasons):
-  y, mask, X, spec = _inputs(T, p, has_slope, seasons)
+  _wide_equals_stock(T, p, has_slope, seasons)
+
+
+def _gap(a, b):
+  """A mask edit: pre-period steps a..b-1 masked as well."""
+  def edit(m):
+    m[a:b] = True
+    return m
+  return edit
+
+
+@pytest.mark.parametrize("T,p,has_slope,seasons,edit", [
+    (200, 59, 1, ((7, 1), (12, 2)), None),                     # P = 60: the P > 52 regression block
+    (150, 52, 0, ((30, 1),), _gap(20, 70)),                    # P = 53 and a 50-step gap
+    (240, 0, 0, ((7, 3), (30, 2)), _gap(30, 75)),              # a 45-step gap over season changes
+    (240, 3, 1, ((60, 4),), _gap(41, 90)),                     # ... of a 4-step season, with a slope
+])
+def test_wide_oracle_reproduces_the_stock_oracle_with_many_columns_and_long_gaps(T, p, has_slope,
+                                                                                 seasons, edit):
+  """What the BIGP and long-gap GPU cases of test_wide_state_builds.py are compared against."""
+  _wide_equals_stock(T, p, has_slope, seasons, edit)
+
+
+def _wide_equals_stock(T, p, has_slope, seasons, edit=None):
+  assert _dfull(has_slope, seasons) <= 64
+  y, mask, X, spec = _inputs(T, p, has_slope, seasons, edit=edit)
   kw = dict(num_results=4, num_warmup=0, seed=(2, 6))
   want = orc.fit_gibbs(y, mask, X, spec, **kw)
   got = wide_oracle.fit_gibbs(y, mask, X, spec, **kw)
@@ -95,28 +122,48 @@ def _ragged(n):
   return (a, b)
 
 
-def _gpu_vs_oracle(T, p, has_slope, seasons, flags=0, oracle=None):
-  y, mask, X, spec = _inputs(T, p, has_slope, seasons)
+def _mw_name(gws, bigp):
+  """Session.kernel_name() of a build of the multi-wavefront kernel."""
+  return f"ci::gibbs_seasonal_kernel<{str(bool(gws)).lower()},{str(bool(bigp)).lower()},4> (multi-wave)"
+
+
+def _gpu_vs_oracle(T, p, has_slope, seasons, flags=0, oracle=None, kernel=None, edit=None):
+  """Four iterations of one chain on the device against the oracle, per draw; `kernel` is the
+  Session.kernel_name() the case must run on."""
+  y, mask, X, spec = _inputs(T, p, has_slope, seasons, edit=edit)
   counts, flg = _model.expand_seasons(seasons, T)
   S = 4
   pb = _native.make_problem(T=T, P=spec["P"], has_slope=has_slope, num_seasons=counts,
                             num_warmup=0, num_results=S, seed=(2, 6), flags=flags)
-  got = _native.fit_gibbs(pb, y[None], mask[None], None if X is None else X[None], flg,
-                          _native.make_params([spec]))
+  s = _native.Session(pb, y[None], mask[None], None if X is None else X[None], flg,
+                      _native.make_params([spec]))
+  try:
+    if kernel is not None:
+      assert s.kernel_name() == kernel
+    s.run()
+    got = s.fetch()
+  finally:
+    s.close()
   w = (oracle or wide_oracle.fit_gibbs)(y, mask, X, spec, num_results=S, num_warmup=0, seed=(2, 6))
-  # the tolerances of test_gpu_gibbs.py::test_seasonal_first_iterations_match_oracle_per_draw
-  np.testing.assert_allclose(got["level"][0, 0], w["level"], atol=5e-3)
-  np.testing.assert_allclose(got["seasonal_levels"][0, 0], w["seasonal"], atol=5e-3)
-  np.testing.assert_allclose(got["seasonal_drift_scales"][0, 0], w["drift_scales"], rtol=2e-2)
-  np.testing.assert_allclose(got["observation_noise_scale"][0, 0], w["obs_scale"], rtol=5e-3)
-  np.testing.assert_allclose(got["level_scale"][0, 0], w["level_scale"], rtol=5e-3)
-  if has_slope:
-    np.testing.assert_allclose(got["slope"][0, 0], w["slope"], atol=5e-3)
-  if spec["P"]:
-    np.testing.assert_allclose(got["weights"][0, 0], w["weights"], atol=5e-3)
-  np.testing.assert_allclose(got["posterior_trajectories"][0, 0], w["trajectories"], atol=1e-2)
-  np.testing.assert_allclose(got["posterior_means"][0, 0], w["pred_mean"], atol=5e-3)
+  _assert_draws_match(got, 0, 0, w, has_slope, spec["P"])
   assert got["seasonal_levels"].shape == (1, 1, S, T, len(seasons))
+  return got, w
+
+
+def _assert_draws_match(got, b, c, w, has_slope, P):
+  """Series b, chain c of a device fit against one oracle chain, per draw."""
+  # the tolerances of test_gpu_gibbs.py::test_seasonal_first_iterations_match_oracle_per_draw
+  np.testing.assert_allclose(got["level"][b, c], w["level"], atol=5e-3)
+  np.testing.assert_allclose(got["seasonal_levels"][b, c], w["seasonal"], atol=5e-3)
+  np.testing.assert_allclose(got["seasonal_drift_scales"][b, c], w["drift_scales"], rtol=2e-2)
+  np.testing.assert_allclose(got["observation_noise_scale"][b, c], w["obs_scale"], rtol=5e-3)
+  np.testing.assert_allclose(got["level_scale"][b, c], w["level_scale"], rtol=5e-3)
+  if has_slope:
+    np.testing.assert_allclose(got["slope"][b, c], w["slope"], atol=5e-3)
+  if P:
+    np.testing.assert_allclose(got["weights"][b, c], w["weights"], atol=5e-3)
+  np.testing.assert_allclose(got["posterior_trajectories"][b, c], w["trajectories"], atol=1e-2)
+  np.testing.assert_allclose(got["posterior_means"][b, c], w["pred_mean"], atol=5e-3)
 
 
 @pytest.mark.gpu
@@ -129,7 +176,8 @@ def _gpu_vs_oracle(T, p, has_slope, seasons, flags=0, oracle=None):
 ])
 def test_wide_state_first_iterations_match_the_widened_oracle_per_draw(T, p, has_slope, seasons):
   assert 64 < _dfull(has_slope, seasons) <= 256
-  _gpu_vs_oracle(T, p, has_slope, seasons)
+  # every one of these series is too long for LDS: the arrays over time live in the workspace
+  _gpu_vs_oracle(T, p, has_slope, seasons, kernel=_mw_name(True, False))
 
 
 @pytest.mark.gpu
@@ -232,3 +280,24 @@ def test_wide_state_limits_on_the_other_paths():
   with pytest.raises(Exception, match="257 > 256"):
     ci.fit_causalimpact(df, pre, post, model_options=ci.ModelOptions(seasons=[ci.Seasons(num_seasons=256)]),
                         inference_options=ci.InferenceOptions(num_results=10))
+
+
+@pytest.mark.gpu
+def test_float64_and_hmc_take_64_components_and_refuse_65():
+  """The one-wavefront limits of the float64 and HMC paths, at their edge."""
+  frames, pre, post, _ = _hourly_frames(1, weeks_pre=1, weeks_post=1)
+  df = frames[0]
+  at_64 = ci.ModelOptions(seasons=[ci.Seasons(num_seasons=63)])
+  at_65 = ci.ModelOptions(seasons=[ci.Seasons(num_seasons=64)])
+  f64 = ci.DataOptions(dtype=np.float64)
+  res = ci.fit_causalimpact(df, pre, post, model_options=at_64, data_options=f64,
+                            inference_options=ci.InferenceOptions(num_results=10))
+  assert np.isfinite(np.asarray(res.posterior_samples.seasonal_levels)).all()
+  with pytest.raises(Exception, match=r"65 > 64 \(dtype=float64"):
+    ci.fit_causalimpact(df, pre, post, model_options=at_65, data_options=f64,
+                        inference_options=ci.InferenceOptions(num_results=10))
+  hmc = ci.InferenceOptions(num_results=10, num_warmup_steps=10, sampler="hmc")
+  res = ci.fit_causalimpact(df, pre, post, model_options=at_64, inference_options=hmc)
+  assert np.isfinite(np.asarray(res.posterior_samples.seasonal_levels)).all()
+  with pytest.raises(Exception, match=r"65 > 64 \(the log-likelihood and sampler=\"hmc\""):
+    ci.fit_causalimpact(df, pre, post, model_options=at_65, inference_options=hmc)
