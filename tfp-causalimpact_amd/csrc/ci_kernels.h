@@ -171,43 +171,66 @@ template <int CTRL, int ROW_MASK, class E> __device__ __forceinline__ E dpp_move
                                                         CTRL, ROW_MASK, 0xF, false));
   return __builtin_bit_cast(E, a);
 }
+// The same move into fresh registers: lanes the control word gives no source (and rows outside
+// ROW_MASK) hold undefined values, so the move needs no copy of `e` to preserve them.  Every caller
+// selects those lanes out.
+template <int CTRL, int ROW_MASK, class E> __device__ __forceinline__ E dpp_take_e(const E& e) {
+  Arr<E> a = __builtin_bit_cast(Arr<E>, e);
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(E) / 4); ++i)
+    a.f[i] = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(a.f[i]), CTRL, ROW_MASK, 0xF, true));
+  return __builtin_bit_cast(E, a);
+}
+// c ? a : b, one v_cndmask per float (for a cheap side such as an identity element; a combine
+// stays behind an if: exec-masked code leaves the SIMD's issue slots of the lanes it skips to the
+// helper wave that shares it, which measured faster than selecting on every lane)
+template <class E> __device__ __forceinline__ E select_e(bool c, const E& a, const E& b) {
+  Arr<E> x = __builtin_bit_cast(Arr<E>, a);
+  const Arr<E> y = __builtin_bit_cast(Arr<E>, b);
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(E) / 4); ++i) x.f[i] = c ? x.f[i] : y.f[i];
+  return __builtin_bit_cast(E, x);
+}
 
 // Inclusive scan of one wavefront, earlier lanes first, for any associative op(earlier, later), on
 // the DPP crossbar (VALU moves, no LDS round trips): Kogge-Stone inside each row of 16 lanes
 // (row_shr 1, 2, 4, 8), then the last lane of row 0 / 2 joins rows 1 / 3 (row_bcast:15) and lane 31
-// joins rows 2 and 3 (row_bcast:31).
+// joins rows 2 and 3 (row_bcast:31).  The lanes without a source must not combine at all:
+// op(identity, x) is not x bit for bit (a -0 in x can come back +0).
 template <class E, class Op>
 __device__ __forceinline__ E wave_scan_incl_fwd(const E& v, Op op, int lane) {
   E incl = v;
   const int r = lane & 15;
-  { const E o = dpp_move_e<0x111, 0xF>(incl); if (r >= 1) incl = op(o, incl); }
-  { const E o = dpp_move_e<0x112, 0xF>(incl); if (r >= 2) incl = op(o, incl); }
-  { const E o = dpp_move_e<0x114, 0xF>(incl); if (r >= 4) incl = op(o, incl); }
-  { const E o = dpp_move_e<0x118, 0xF>(incl); if (r >= 8) incl = op(o, incl); }
-  { const E o = dpp_move_e<0x142, 0xA>(incl); if (lane & 16) incl = op(o, incl); }
-  { const E o = dpp_move_e<0x143, 0xC>(incl); if (lane & 32) incl = op(o, incl); }
+  { const E o = dpp_take_e<0x111, 0xF>(incl); if (r >= 1) incl = op(o, incl); }
+  { const E o = dpp_take_e<0x112, 0xF>(incl); if (r >= 2) incl = op(o, incl); }
+  { const E o = dpp_take_e<0x114, 0xF>(incl); if (r >= 4) incl = op(o, incl); }
+  { const E o = dpp_take_e<0x118, 0xF>(incl); if (r >= 8) incl = op(o, incl); }
+  { const E o = dpp_take_e<0x142, 0xA>(incl); if (lane & 16) incl = op(o, incl); }
+  { const E o = dpp_take_e<0x143, 0xC>(incl); if (lane & 32) incl = op(o, incl); }
   return incl;
 }
 // Inclusive SUFFIX scan: lane i gets v_i o v_{i+1} o ... o v_63 with op(outer, inner).  Inside the
-// rows the same DPP pattern mirrored (row_shl); there is no backward row broadcast, so the two
-// steps across rows read the first lane of the next row / of row 2 through v_readlane.
+// rows the same DPP pattern mirrored (row_shl).  There is no backward row broadcast: rows 0 and 2
+// take the first lane of the next row by row_newbcast:0 (every lane reads lane 0 of its own row)
+// and v_permlane16_swap (the odd rows of its first operand trade places with the even rows of its
+// second), all in VGPRs; rows 0 and 1 read lane 32 through v_readlane.
 template <class E, class Op>
 __device__ __forceinline__ E wave_scan_incl_bwd(const E& v, Op op, int lane) {
   E incl = v;
   const int r = lane & 15;
-  { const E o = dpp_move_e<0x101, 0xF>(incl); if (r < 15) incl = op(incl, o); }
-  { const E o = dpp_move_e<0x102, 0xF>(incl); if (r < 14) incl = op(incl, o); }
-  { const E o = dpp_move_e<0x104, 0xF>(incl); if (r < 12) incl = op(incl, o); }
-  { const E o = dpp_move_e<0x108, 0xF>(incl); if (r < 8) incl = op(incl, o); }
+  { const E o = dpp_take_e<0x101, 0xF>(incl); if (r < 15) incl = op(incl, o); }
+  { const E o = dpp_take_e<0x102, 0xF>(incl); if (r < 14) incl = op(incl, o); }
+  { const E o = dpp_take_e<0x104, 0xF>(incl); if (r < 12) incl = op(incl, o); }
+  { const E o = dpp_take_e<0x108, 0xF>(incl); if (r < 8) incl = op(incl, o); }
   {
-    // rows 0 and 2 take the suffix of row 1 / row 3, held by that row's first lane: two fixed
-    // source lanes, read through v_readlane (no LDS round trip)
-    Arr<E> a = __builtin_bit_cast(Arr<E>, incl);
+    // rows 0 and 2 take the suffix of row 1 / row 3, held by that row's first lane
+    const Arr<E> b = __builtin_bit_cast(Arr<E>, dpp_take_e<0x150, 0xF>(incl));     // row_newbcast:0
+    Arr<E> a;
 #pragma unroll
     for (int i = 0; i < (int)(sizeof(E) / 4); ++i) {
-      const int v16 = __builtin_amdgcn_readlane(__float_as_int(a.f[i]), 16);
-      const int v48 = __builtin_amdgcn_readlane(__float_as_int(a.f[i]), 48);
-      a.f[i] = __int_as_float(lane < 32 ? v16 : v48);
+      // vdst = the broadcast: its rows 1 / 3 land in rows 0 / 2 of the second result
+      const auto s = __builtin_amdgcn_permlane16_swap((unsigned)__float_as_int(b.f[i]), 0u, false, false);
+      a.f[i] = __int_as_float((int)s[1]);
     }
     const E o = __builtin_bit_cast(E, a);
     if ((lane & 16) == 0) incl = op(incl, o);
@@ -242,8 +265,7 @@ template <class E, class Op>
 __device__ __forceinline__ E block_scan_fwd_finish(const E& incl, Op op, const E& ident, const float* slots,
                                                    int lane, int wave) {
   constexpr int N = sizeof(E) / 4;
-  E ex = dpp_move_e<0x138, 0xF>(incl);        // wave_shr:1
-  if (lane == 0) ex = ident;
+  const E ex = select_e(lane == 0, ident, dpp_take_e<0x138, 0xF>(incl));        // wave_shr:1
   if (wave == 0) return ex;
   E wp = lds_load_e<E>(slots);
   for (int ww = 1; ww < wave; ++ww) wp = op(wp, lds_load_e<E>(slots + ww * N));
@@ -266,8 +288,7 @@ __device__ __forceinline__ E block_scan_excl_bwd(const E& tot, Op op, const E& i
   const E incl = wave_scan_incl_bwd(tot, op, lane);
   if (lane == 0) lds_store_e(slots + wave * N, incl);
   __syncthreads();
-  E ex = dpp_move_e<0x130, 0xF>(incl);        // wave_shl:1
-  if (lane == 63) ex = ident;
+  const E ex = select_e(lane == 63, ident, dpp_take_e<0x130, 0xF>(incl));       // wave_shl:1
   if (wave == NW - 1) return ex;
   E ws = lds_load_e<E>(slots + (wave + 1) * N);
   for (int ww = wave + 2; ww < NW; ++ww) ws = op(ws, lds_load_e<E>(slots + ww * N));
@@ -828,8 +849,7 @@ template <int D>
 __device__ __forceinline__ void dk_matrix_scan_finish(const FMElem<D>& incl, const float* slots_m,
                                                       int lane, int wave,
                                                       float (&Pin)[D * (D + 1) / 2]) {
-  FMElem<D> ex = dpp_move_e<0x138, 0xF>(incl);        // wave_shr:1
-  if (lane == 0) ex = fmelem_identity<D>();
+  const FMElem<D> ex = select_e(lane == 0, fmelem_identity<D>(), dpp_take_e<0x138, 0xF>(incl));  // wave_shr:1
   if (wave == 0) {
 #pragma unroll
     for (int i = 0; i < D * (D + 1) / 2; ++i) Pin[i] = ex.C[i];
@@ -858,8 +878,7 @@ __device__ __forceinline__ AElem<D> aff_fwd_begin(const AElem<D>& fe, float* slo
 template <int D>
 __device__ __forceinline__ Vec<D> aff_fwd_finish(const AElem<D>& incl, const float* slots_f, int lane,
                                                  int wave) {
-  AElem<D> ex = dpp_move_e<0x138, 0xF>(incl);
-  if (lane == 0) ex = aelem_identity<D>();
+  const AElem<D> ex = select_e(lane == 0, aelem_identity<D>(), dpp_take_e<0x138, 0xF>(incl));
   if (wave == 0) return ex.c;
   AElem<D> tot[NW - 1];
 #pragma unroll
@@ -882,8 +901,7 @@ __device__ __forceinline__ AElem<D> aff_bwd_begin(const AElem<D>& be, float* slo
 template <int D>
 __device__ __forceinline__ Vec<D> aff_bwd_finish(const AElem<D>& incl, const float* slots_b, int lane,
                                                  int wave) {
-  AElem<D> ex = dpp_move_e<0x130, 0xF>(incl);        // wave_shl:1
-  if (lane == 63) ex = aelem_identity<D>();
+  const AElem<D> ex = select_e(lane == 63, aelem_identity<D>(), dpp_take_e<0x130, 0xF>(incl));  // wave_shl:1
   if (wave == NW - 1) return ex.c;
   AElem<D> tot[NW];
 #pragma unroll
