@@ -335,6 +335,29 @@ int ci_ll_session_hmc_run(ci_ll_session* session, const ci_hmc_options* options,
  * fields ignored). */
 int ci_ll_session_hmc_fetch(ci_ll_session* session, double* draws, double* accept_rate,
                             double* step_size, ci_outputs* outputs);
+/* B series in one session, for a batched HMC fit: B x num_chains workgroups of the hmc_kernel in
+ * one launch (chain c of series b = workgroup b * num_chains + c).  Trend models only: no seasonal
+ * blocks, T <= 4096, P <= 128; everything is validated before the first device call.
+ *   params [B]; y, mask [B, T]; X [B, T, P] (row-major, NULL when P = 0).
+ * Honours problem->num_series = B, series_offset and CI_FLAG_SHARED_SERIES_STREAMS as ci_fit_gibbs
+ * does: series b draws from the Philox key ci_series_stream_key(seed, series_offset + b), or from
+ * seed itself with shared streams -- series b then equals a one-series session with that key, and a
+ * batch split into parts with matching series_offset equals the whole.
+ * On such a session ci_ll_session_hmc_run's num_chains is per series and init_theta is
+ * [B, num_chains, dim]; ci_ll_session_hmc_fetch returns draws [B, num_chains, num_results, 3 + P],
+ * accept_rate and step_size [B, num_chains] and the ci_fit_gibbs container with this B;
+ * horseshoe_scale applies to every series.  ci_ll_session_eval and ci_ll_session_draw_latents
+ * refuse sessions of more than one series.  A device allocation that fails returns an error. */
+int ci_ll_session_create_batch(const ci_problem* problem, const ci_series_params* params,
+                               const float* y, const uint8_t* mask, const float* X,
+                               int32_t max_evals, ci_ll_session** session);
+/* ci_session_summarize for the posterior-predictive trajectories of the last ci_ll_session_hmc_run
+ * (any session, B series): same arguments, same outputs, same kernels; the float32 [B, C, S, T]
+ * trajectories are read where they are, in HBM. */
+int ci_ll_session_hmc_summarize(ci_ll_session* session, const double* scale, const double* shift,
+                                const double* observed, const uint8_t* flags, int32_t num_ranks,
+                                const int32_t* ranks, double* value_order, double* cum_order,
+                                double* per_draw, double* per_draw_order);
 int ci_ll_session_kernel_name(const ci_ll_session* session, char* buf, int32_t buflen);
 /* Algorithmic bytes of the last configured HMC fit (DESIGN.md "Roofline", cfg3). */
 int ci_ll_session_algorithmic_bytes(const ci_ll_session* session, double* bytes);

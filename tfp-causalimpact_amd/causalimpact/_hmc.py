@@ -274,3 +274,64 @@ def fit_hmc_host(y, mask, X, spec: Dict, *, has_slope: bool, num_results: int, n
   out.update(hmc_accept_rate=accepted / max(S, 1), hmc_step_size=eps.copy(),
              hmc_target_calls=np.array(calls))
   return out
+
+
+# Device memory a batched fit holds per series and chain draw: level, slope, trajectory (float32,
+# [T] each), the summary's value and running-sum matrices (float64, [T] each) and the draw row.
+def hmc_batch_bytes_per_series(T: int, P: int, num_chains: int, num_results: int) -> int:
+  """HBM bytes one series of a one-launch HMC batch needs (outputs and summary scratch)."""
+  return int(num_chains) * int(num_results) * (int(T) * (3 * 4 + 2 * 8) + 8 * (3 + int(P)) + 4 * (3 + int(P)))
+
+
+# What one launch of `fit_hmc_batch` may hold in HBM; a shard of a batch that needs more is fitted
+# in several launches (`series_per_launch`).  The split does not change any result: series are
+# keyed by their global id (series_offset), chains by their index.
+HMC_BATCH_HBM_BYTES = 24 << 30
+
+
+def series_per_launch(T: int, P: int, num_chains: int, num_results: int,
+                      budget: Optional[int] = None) -> int:
+  """How many series one launch takes under the HBM budget (at least one; at most 65535, the grid
+  limit of the per-chain mean's series axis)."""
+  budget = HMC_BATCH_HBM_BYTES if budget is None else int(budget)
+  return min(65535, max(1, budget // max(1, hmc_batch_bytes_per_series(T, P, num_chains, num_results))))
+
+
+def fit_hmc_batch(y, mask, X, specs, *, has_slope: bool, num_results: int, num_warmup: int,
+                  num_chains: int, seed, device: int = 0, series_offset: int = 0,
+                  shared_streams: bool = False, num_leapfrog: int = 15, target_accept: float = 0.75,
+                  initial_step_size: float = 0.05, prior: str = "slab", horseshoe_scale: float = 0.1,
+                  summary: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+  """`fit_hmc` for B series of a trend model in ONE launch (ci_ll_session_create_batch: B x C
+  workgroups of the hmc_kernel, then B x C x S latent / predictive draws).  y, mask [B, T]; X
+  [B, T, P] or None; specs: B `_model.series_params` dicts.  Chains start at the Gibbs initial
+  state.  Series b draws from the Philox key of series id series_offset + b
+  (`_native.series_stream_key`), or with shared_streams=True from `seed` itself: it then equals
+  `fit_hmc` on that series alone, draw for draw.
+
+  Only small arrays leave the device: posterior_means [B, C, T], observation_noise_scale and
+  level_scale [B, C, S] (for the diagnostics), hmc_accept_rate and hmc_step_size [B, C],
+  hmc_kernel_ms.  summary (optional): dict(scale, shift, observed, flags, ranks) of
+  `_native.BatchLogLikSession.summarize` -- the order statistics of the [B, C, S, T] predictive
+  trajectories, computed where they are; returned as "summary"."""
+  y = np.asarray(y, np.float64)
+  B, T = y.shape
+  P = 0 if X is None else int(np.asarray(X).shape[2])
+  C, S, W = int(num_chains), int(num_results), int(num_warmup)
+  flags = _native.FLAG_SHARED_SERIES_STREAMS if shared_streams else 0
+  pb = _native.make_problem(T=T, P=P, has_slope=has_slope, num_warmup=0, num_results=1,
+                            num_series=B, seed=seed, device=device, series_offset=series_offset,
+                            flags=flags)
+  sess = _native.BatchLogLikSession(pb, _native.make_params(list(specs)), y, mask, X)
+  try:
+    ms = sess.hmc_run(num_chains=C, num_warmup=W, num_results=S, num_leapfrog=num_leapfrog,
+                      target_accept=target_accept, initial_step_size=initial_step_size, seed=seed,
+                      prior=prior, horseshoe_scale=horseshoe_scale)
+    _, acc, eps, out = sess.hmc_fetch(["posterior_means", "observation_noise_scale", "level_scale"],
+                                      with_draws=False)
+    if summary is not None:
+      out["summary"] = sess.summarize(**summary)
+  finally:
+    sess.close()
+  out.update(hmc_accept_rate=acc, hmc_step_size=eps, hmc_kernel_ms=np.asarray(ms))
+  return out

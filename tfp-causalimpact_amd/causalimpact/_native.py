@@ -121,6 +121,11 @@ def load():
   L.ci_ll_session_hmc_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(Outputs)]
   L.ci_ll_session_algorithmic_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+  L.ci_ll_session_create_batch.argtypes = [C.POINTER(Problem), C.POINTER(SeriesParams), C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+  L.ci_ll_session_hmc_summarize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
   L.ci_pool_trim.argtypes = []
   L.ci_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
   L.ci_host_free.argtypes = [C.c_void_p]
@@ -149,7 +154,8 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_summarize", "ci_summarize_draws", "ci_summarize_draws_f64",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
           "ci_ll_session_draw_latents", "ci_ll_session_hmc_run", "ci_ll_session_hmc_fetch",
-          "ci_ll_session_algorithmic_bytes", "ci_ll_session_destroy",
+          "ci_ll_session_algorithmic_bytes", "ci_ll_session_destroy", "ci_ll_session_create_batch",
+          "ci_ll_session_hmc_summarize",
           "ci_comm_unique_id", "ci_comm_create", "ci_comm_info", "ci_comm_set_timeout", "ci_comm_barrier",
           "ci_comm_all_reduce", "ci_comm_all_gather", "ci_comm_session_all_gather",
           "ci_comm_ll_session_all_gather", "ci_comm_destroy", "ci_test_rng",
@@ -470,8 +476,24 @@ def kalman_loglik(pb: Problem, params, y, mask, X, theta) -> np.ndarray:
   return out
 
 
+def _hmc_options(*, num_chains, chain_offset, num_warmup, num_results, num_leapfrog, target_accept,
+                 initial_step_size, seed, prior, horseshoe_scale) -> HmcOptions:
+  o = HmcOptions()
+  o.num_chains, o.chain_offset = int(num_chains), int(chain_offset)
+  o.num_warmup, o.num_results, o.num_leapfrog = int(num_warmup), int(num_results), int(num_leapfrog)
+  if prior not in HMC_PRIORS:
+    raise ValueError(f"prior must be one of {sorted(HMC_PRIORS)}, got {prior!r}")
+  o.prior = HMC_PRIORS[prior]
+  o.target_accept, o.initial_step_size = float(target_accept), float(initial_step_size)
+  o.horseshoe_scale = float(horseshoe_scale)
+  o.seed[0], o.seed[1] = seed_pair(seed)
+  return o
+
+
 class LogLikSession:
   """Device-resident log-likelihood / score evaluator and latent-path drawer for one series."""
+
+  B, batched = 1, False
 
   def __init__(self, pb: Problem, params, y, mask, X, max_evals: int, season_change=None):
     """season_change [K, T] uint8 for models with seasonal blocks (pb.num_blocks = K): those, and
@@ -515,20 +537,16 @@ class LogLikSession:
               horseshoe_scale=0.1):
     """The whole HMC fit on the device (ci_ll_session_hmc_run): chain, latent paths and
     predictive trajectories stay in HBM.  Returns (hmc_kernel_ms, latents_ms)."""
-    o = HmcOptions()
-    o.num_chains, o.chain_offset = int(num_chains), int(chain_offset)
-    o.num_warmup, o.num_results, o.num_leapfrog = int(num_warmup), int(num_results), int(num_leapfrog)
-    if prior not in HMC_PRIORS:
-      raise ValueError(f"prior must be one of {sorted(HMC_PRIORS)}, got {prior!r}")
-    o.prior = HMC_PRIORS[prior]
-    o.target_accept, o.initial_step_size = float(target_accept), float(initial_step_size)
-    o.horseshoe_scale = float(horseshoe_scale)
-    o.seed[0], o.seed[1] = seed_pair(seed)
+    o = _hmc_options(num_chains=num_chains, chain_offset=chain_offset, num_warmup=num_warmup,
+                     num_results=num_results, num_leapfrog=num_leapfrog, target_accept=target_accept,
+                     initial_step_size=initial_step_size, seed=seed, prior=prior,
+                     horseshoe_scale=horseshoe_scale)
     init = None if init_theta is None else np.ascontiguousarray(init_theta, dtype=np.float64)
     if init is not None:
       dim = (3 * self.P + 2 if prior == "horseshoe" else self.P) + self.D + 1 + self.K
-      if init.shape != (int(num_chains), dim):
-        raise ValueError(f"init_theta must be [{int(num_chains)}, {dim}], got {init.shape}")
+      want = (self.B, int(num_chains), dim) if self.batched else (int(num_chains), dim)
+      if init.shape != want:
+        raise ValueError(f"init_theta must be {list(want)}, got {list(init.shape)}")
     ms = (C.c_float * 2)()
     _check(self._lib.ci_ll_session_hmc_run(self._h, C.byref(o), _ptr(init), ms))
     self._hmc_shape = (int(num_chains), int(num_results))
@@ -583,6 +601,68 @@ class LogLikSession:
       self.close()
     except Exception:  # pylint: disable=broad-except
       pass
+
+
+class BatchLogLikSession(LogLikSession):
+  """B series in one session (ci_ll_session_create_batch): one launch fits B x num_chains HMC chains.
+  Trend models, T <= 4096, P <= 128.  pb.num_series = B, pb.series_offset and
+  FLAG_SHARED_SERIES_STREAMS in pb.flags key the series' random streams as in `fit_gibbs`.
+  Every result has a leading series axis: hmc_run's init_theta is [B, C, dim], hmc_fetch returns
+  draws [B, C, S, 3 + P], accept_rate and step_size [B, C] and the `fit_gibbs` container with this B.
+  `evaluate` and `draw_latents` need B = 1."""
+
+  batched = True
+
+  def __init__(self, pb: Problem, params, y, mask, X, max_evals: int = 1):   # pylint: disable=super-init-not-called
+    self._lib = load()
+    self.B, self.T, self.P, self.D, self.K = pb.num_series, pb.T, pb.P, 2 if pb.has_slope else 1, 0
+    self.num_seasons = []
+    self.max_evals = int(max_evals)
+    y32, mask8, X32, _ = _stage_inputs(pb, y, mask, X, None)
+    self._h = C.c_void_p()
+    _check(self._lib.ci_ll_session_create_batch(C.byref(pb), params, y32.ctypes.data, mask8.ctypes.data,
+                                                _ptr(X32), self.max_evals, C.byref(self._h)))
+
+  def hmc_fetch(self, want=None, with_draws=True):
+    """Host copies of the finished fit: draws [B, C, S, 3 + P] float64 (None unless with_draws),
+    accept_rate and step_size [B, C], and the float32 container of `fit_gibbs` for the fields in
+    `want` (default: all the trend model has)."""
+    Cn, S = self._hmc_shape
+    pb = make_problem(T=self.T, P=self.P, has_slope=self.D == 2, num_warmup=0, num_results=S,
+                      num_chains=Cn, num_series=self.B)
+    if want is None:
+      want = [f for f in _OUT_FIELDS if f not in ("seasonal_drift_scales", "seasonal_levels")]
+    out, arrs = _alloc_outputs(pb, want)
+    draws = np.zeros((self.B, Cn, S, 3 + self.P), np.float64) if with_draws else None
+    acc = np.zeros((self.B, Cn), np.float64)
+    eps = np.zeros((self.B, Cn), np.float64)
+    _check(self._lib.ci_ll_session_hmc_fetch(self._h, _ptr(draws), acc.ctypes.data,
+                                             eps.ctypes.data, C.byref(out)))
+    return draws, acc, eps, arrs
+
+  def hmc(self, **kw):
+    raise NotImplementedError("use hmc_run + hmc_fetch on a batched session")
+
+  def summarize(self, scale, shift, observed, flags, ranks) -> Dict[str, np.ndarray]:
+    """`Session.summarize` of the fit's resident predictive trajectories (ci_ll_session_hmc_summarize):
+    value_order [B,R,T], cum_order [B,R,T], per_draw [B,2,N], per_draw_order [B,2,R], N = C x S
+    (the series axis is kept for B = 1)."""
+    Cn, S = self._hmc_shape
+    B, T, N = self.B, self.T, Cn * S
+    sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (B,)))
+    sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.float64), (B,)))
+    obs = np.ascontiguousarray(np.broadcast_to(np.asarray(observed, np.float64), (B, T)))
+    fl = np.ascontiguousarray(np.broadcast_to(np.asarray(flags, np.uint8), (B, T)))
+    rk = np.ascontiguousarray(ranks, dtype=np.int32)
+    vo = np.empty((B, rk.size, T), np.float64)
+    co = np.empty((B, rk.size, T), np.float64)
+    pd_ = np.empty((B, 2, N), np.float64)
+    do = np.empty((B, 2, rk.size), np.float64)
+    _check(self._lib.ci_ll_session_hmc_summarize(self._h, sc.ctypes.data, sh.ctypes.data,
+                                                 obs.ctypes.data, fl.ctypes.data, int(rk.size),
+                                                 rk.ctypes.data, vo.ctypes.data, co.ctypes.data,
+                                                 pd_.ctypes.data, do.ctypes.data))
+    return dict(value_order=vo, cum_order=co, per_draw=pd_, per_draw_order=do)
 
 
 def test_rng(seed, chain, it, site, sub, n, alpha, device=0):

@@ -274,6 +274,25 @@ class PerSeriesBatchAnalysis(CausalImpactBatchAnalysis):
     return self._cache[range(len(self))[b]]
 
 
+# The one-launch HMC path (csrc/ci_hmc.h with a series axis, ci_ll_session_create_batch) covers
+# standardised float32 trend models of at most this many steps and design columns started at the
+# Gibbs initial state; every other HMC batch is fitted series by series.
+HMC_BATCH_MAX_T = 4096
+HMC_BATCH_MAX_P = 128
+
+
+def hmc_batch_route(*, float64: bool, standardize_data: bool, num_seasonal_blocks: int, T: int,
+                    P: int, hmc_init: str) -> str:
+  """Where `fit_causalimpact_batch(sampler="hmc")` fits a batch: "one_launch" (all series x chains
+  in one kernel launch per device and HBM budget) or "per_series" (`fit_causalimpact` on every
+  series in turn, with the series' key: seasonal blocks, T > 4096, P > 128, hmc_init="vi", float64,
+  standardize_data=False -- the refusals of the single-series path stay where they are)."""
+  if (float64 or not standardize_data or num_seasonal_blocks > 0 or T > HMC_BATCH_MAX_T
+      or P > HMC_BATCH_MAX_P or hmc_init != "gibbs"):
+    return "per_series"
+  return "one_launch"
+
+
 def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
                            pre_period, post_period, alpha: float = 0.05, seed=None,
                            data_options: Optional[lib.DataOptions] = None,
@@ -309,14 +328,25 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   conditioning), i.e. B sequential fits on one device -- B times the cost of one fit, and
   `inference_options.devices` is not used to shard them.  Their streams are keyed per series in
   the same way (series b on the key of series id b) unless `shared_streams=True`.
+
+  `InferenceOptions(sampler="hmc")`: standardised float32 batches of trend models with T <= 4096,
+  at most 128 design columns and `hmc_init="gibbs"` (either `hmc_prior`) run in one launch per
+  device: B x num_chains HMC chains (csrc/ci_hmc.h), then the latent paths, predictive
+  trajectories and their summary on the device.  A shard whose trajectories would exceed
+  `_hmc.HMC_BATCH_HBM_BYTES` is fitted in several launches; neither that split nor the one over
+  devices changes a result.  Every other HMC batch (seasonal blocks, longer series,
+  `hmc_init="vi"`, float64, `standardize_data=False`) is fitted series by series through
+  `fit_causalimpact`, keyed as above (`hmc_batch_route`).  With `shared_streams=True` series b
+  equals `fit_causalimpact(..., sampler="hmc")` on it alone on either route.
   """
   data_options = data_options or lib.DataOptions()
   model_options = model_options or lib.ModelOptions()
   inference_options = inference_options or lib.InferenceOptions()
   if not 0 < alpha < 1:
     raise ValueError("`alpha` must be between 0 and 1.")
-  if inference_options.sampler != "gibbs":
-    raise NotImplementedError("batched fits use the Gibbs sampler")
+  if inference_options.sampler not in ("gibbs", "hmc"):
+    raise ValueError(f"sampler must be 'gibbs' or 'hmc', got {inference_options.sampler!r}")
+  hmc = inference_options.sampler == "hmc"
   if isinstance(data, np.ndarray):
     values = np.asarray(data, np.float64)
     index = pd.RangeIndex(values.shape[1]) if index is None else pd.Index(index)
@@ -335,15 +365,27 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     index = first.index
   B = values.shape[0]
   names = list(range(B)) if names is None else list(names)
-  if (cid._as_numpy_dtype(data_options.dtype) == np.float64  # pylint: disable=protected-access
-      or not data_options.standardize_data):
+  float64 = cid._as_numpy_dtype(data_options.dtype) == np.float64  # pylint: disable=protected-access
+  prep = None
+  per_series = float64 or not data_options.standardize_data
+  if hmc and not per_series:
+    prep = prepare_batch(values, index, pre_period, post_period, data_options.standardize_data)
+    route = hmc_batch_route(float64=float64, standardize_data=data_options.standardize_data,
+                            num_seasonal_blocks=len(_model.expand_seasons(model_options.seasons,
+                                                                          prep.y.shape[1])[0]),
+                            T=prep.y.shape[1],
+                            P=0 if prep.design is None else prep.design.shape[2],
+                            hmc_init=inference_options.hmc_init)
+    per_series = route == "per_series"
+  if per_series:
     # float64 compute (csrc/ci_gibbs64.h) and raw-scale outcomes (their per-series internal
     # conditioning, causalimpact_lib._internal_conditioning) exist on the single-series path: the
     # batch is fitted series by series there -- same container, same summary table, every series
     # keyed like the one-launch path (series b on the Philox key of series id b,
     # ci_series_stream_key, so the Monte-Carlo errors of different series are independent; with
     # shared_streams=True every series equals `fit_causalimpact` on it alone with this seed).
-    # Not the one-launch path: B sequential fits on one device (see the docstring).
+    # Not the one-launch path: B sequential fits on one device (see the docstring).  The HMC
+    # batches the one-launch path does not take (hmc_batch_route) come here too.
     opts = dataclasses.replace(data_options, outcome_column=columns[0])
     analyses = []
     base_seed = lib._sanitize_seed(seed)   # pylint: disable=protected-access
@@ -354,7 +396,8 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
                                  model_options=model_options, inference_options=inference_options)
       analyses.append(dataclasses.replace(one, posterior_samples=None))   # (draws are not kept)
     return PerSeriesBatchAnalysis(names, alpha, analyses)
-  prep = prepare_batch(values, index, pre_period, post_period, data_options.standardize_data)
+  if prep is None:
+    prep = prepare_batch(values, index, pre_period, post_period, data_options.standardize_data)
   T = prep.y.shape[1]
   P = 0 if prep.design is None else prep.design.shape[2]
   num_seasons, season_change = _model.expand_seasons(model_options.seasons, T)
@@ -379,7 +422,31 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   devs = list(inference_options.devices) if inference_options.devices else [0]
   shards = [s for s in np.array_split(np.arange(B), len(devs)) if len(s)]
 
+  def run_hmc(dev, ids):
+    # one launch per part of the shard that fits the HBM budget; series keep their global ids
+    from causalimpact import _hmc  # pylint: disable=import-outside-toplevel
+    step = _hmc.series_per_launch(T, P, C, S)
+    outs, sums = [], []
+    for lo in range(0, len(ids), step):
+      part = ids[lo:lo + step]
+      res = _hmc.fit_hmc_batch(
+          y_model[part], prep.mask[part], None if prep.design is None else prep.design[part],
+          [params[b] for b in part], has_slope=model_options.local_linear_trend, num_results=S,
+          num_warmup=inference_options.num_warmup_steps, num_chains=C, seed=seed_pair, device=dev,
+          series_offset=int(part[0]), shared_streams=shared_streams,
+          prior=inference_options.hmc_prior,
+          summary=dict(scale=prep.outcome_sd[part] if prep.standardize_data else 1.0,
+                       shift=prep.outcome_mean[part] if prep.standardize_data else 0.0,
+                       observed=observed[part], flags=flags, ranks=ranks))
+      outs.append(res)
+      sums.append(res["summary"])
+    out = {k: np.concatenate([o[k] for o in outs], axis=0)
+           for k in ("posterior_means", "observation_noise_scale", "level_scale")}
+    return out, {k: np.concatenate([d[k] for d in sums], axis=0) for k in sums[0]}
+
   def run(dev, ids):
+    if hmc:
+      return run_hmc(dev, ids)
     pb = _native.make_problem(T=T, P=P, has_slope=model_options.local_linear_trend,
                               num_seasons=num_seasons, num_warmup=inference_options.num_warmup_steps,
                               num_results=S, num_chains=C, num_series=len(ids), seed=seed_pair,

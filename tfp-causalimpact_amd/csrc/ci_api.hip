@@ -69,6 +69,7 @@ CI_WIDE_DECL(2) CI_WIDE_DECL(3) CI_WIDE_DECL(4) CI_WIDE_DECL(5) CI_WIDE_DECL(6) 
   extern "C" void ci_launch_latents_d##D##_l##L(int, int, int, const float*, const uint8_t*,      \
                                                 const float*, const double*, float, float, float, \
                                                 uint32_t, uint32_t, uint32_t, uint32_t, int, int, \
+                                                int, int, const ci::HmcSeries*,                   \
                                                 float*, float*, float*, float*, float*,           \
                                                 hipStream_t);                                     \
   extern "C" void ci_launch_hmc_d##D##_l##L(const ci::HmcArgs*, hipStream_t);
@@ -137,21 +138,23 @@ static __global__ void test_rng_kernel(uint32_t k0, uint32_t k1, uint32_t chain,
 }
 
 // Per-chain mean over the S retained draws of the noise-free predictor (causalimpact_lib.py:627)
-// from the per-group sums the latents pass leaves: part [C, NG, T] -> pm [C, T].  One thread per
-// (chain, t), coalesced over t; the order of the sums is fixed, so chain c's mean does not depend
-// on how chains are split over launches.
+// from the per-group sums the latents pass leaves: part [B, C, NG, T] -> pm [B, C, T].  One thread
+// per (series, chain, t) -- grid (T / 256, C, B) --, coalesced over t; the order of the sums is
+// fixed, so chain c's mean does not depend on how chains or series are split over launches.
 static __global__ void hmc_mean_kernel(int C, int NG, int S, int T, const float* __restrict__ part,
                                        float* __restrict__ pm) {
-  // part [C, NG, T]: sums of the predictor over groups of consecutive draws (latents_kernel)
+  // part [B, C, NG, T]: sums of the predictor over groups of consecutive draws (latents_kernel)
   const int t = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
   if (t >= T || c >= C) return;
-  const float* p = part + (size_t)c * NG * T + t;
+  const size_t bc = (size_t)blockIdx.z * C + c;
+  const float* p = part + bc * NG * T + t;
   float acc = 0.f;
   for (int g = 0; g < NG; ++g) acc += p[(size_t)g * T];
-  pm[(size_t)c * T + t] = acc / (float)S;
+  pm[bc * T + t] = acc / (float)S;
 }
 
-// (sigma_obs, sigma_level, sigma_slope, beta) rows in float64 -> the float32 sample container.
+// (sigma_obs, sigma_level, sigma_slope, beta) rows in float64 -> the float32 sample container: N
+// rows [B, C, S] of a batched fit flattened.
 static __global__ void hmc_unpack_kernel(int N, int P, const double* __restrict__ draws,
                                          float* __restrict__ obs, float* __restrict__ lscale,
                                          float* __restrict__ sscale, float* __restrict__ w) {
@@ -456,6 +459,17 @@ ci::DevSeriesParams dev_series_params(const ci_series_params& q, double n_obs) {
 }
 }  // namespace
 
+// Scratch of the on-device summary (ci_summary.h) of a session's resident trajectories.
+struct SummScratch {
+  DevBuf<double> value, cum, obs, order, draw;
+  DevBuf<uint8_t> flags;
+  DevBuf<int> ranks;
+  void release() {
+    value.release(); cum.release(); obs.release(); flags.release();
+    ranks.release(); order.release(); draw.release();
+  }
+};
+
 struct ci_session {
   ci_problem pb;
   int L = 0, x_in_lds = 0;
@@ -490,10 +504,7 @@ struct ci_session {
   DevBuf<int> csync;
   DevBuf<float> cpart, cw;
   DevBuf<double> cv;
-  // on-device summarisation (ci_summary.h)
-  DevBuf<double> s_value, s_cum, s_obs, s_order, s_draw;
-  DevBuf<uint8_t> s_flags;
-  DevBuf<int> s_ranks;
+  SummScratch summ;          // on-device summarisation (ci_summary.h)
   bool ran = false;
   ci_problem kpb;          // what the kernel runs (== pb except for long trend-only series)
   bool inert_block = false;
@@ -1128,6 +1139,60 @@ static hipError_t launch_select(hipStream_t stream, int N, int T, int rows, int 
   return hipGetLastError();
 }
 
+// The summary of B series' [B, N, T] float32 trajectories resident in HBM (ci_session_summarize,
+// ci_ll_session_hmc_summarize): transpose with value = trajectory * scale + shift, running sums,
+// order statistics; the scratch is allocated on first use and kept.
+static int summarize_resident(hipStream_t stream, SummScratch& w, int B, int T, int N, const float* traj,
+                              const double* scale, const double* shift, const double* observed,
+                              const uint8_t* flags, int32_t num_ranks, const int32_t* ranks,
+                              double* value_order, double* cum_order, double* per_draw,
+                              double* per_draw_order) {
+  if (num_ranks < 1 || num_ranks > ci::SUMM_MAX_RANKS)
+    return fail("num_ranks must be in [1, %d], got %d", ci::SUMM_MAX_RANKS, num_ranks);
+  for (int r = 0; r < num_ranks; ++r)
+    if (ranks[r] < 0 || ranks[r] >= N) return fail("rank %d out of range [0, %d)", ranks[r], N);
+  const size_t BTN = (size_t)B * T * N;
+  if (!w.value.p) {
+    HIP_TRY(w.value.alloc(BTN));
+    HIP_TRY(w.cum.alloc(BTN));
+    HIP_TRY(w.obs.alloc((size_t)B * T + 2 * B));
+    HIP_TRY(w.flags.alloc((size_t)B * T));
+    HIP_TRY(w.ranks.alloc(ci::SUMM_MAX_RANKS));
+    HIP_TRY(w.order.alloc((size_t)2 * B * ci::SUMM_MAX_RANKS * T));
+    HIP_TRY(w.draw.alloc((size_t)B * 2 * N + (size_t)B * 2 * ci::SUMM_MAX_RANKS));
+  }
+  double* d_scale = w.obs.p + (size_t)B * T;
+  double* d_shift = d_scale + B;
+  HIP_TRY(hipMemcpyAsync(w.obs.p, observed, (size_t)B * T * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(w.flags.p, flags, (size_t)B * T, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, num_ranks * sizeof(int), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(ci::summ_transpose_kernel<float>, dim3((T + 63) / 64, (N + 63) / 64, B), dim3(64, 4), 0,
+                     stream, N, T, traj, d_scale, d_shift, w.value.p);
+  hipLaunchKernelGGL(ci::summ_cumsum_kernel, dim3((N + 63) / 64, B), dim3(64), 0, stream, N, T,
+                     w.value.p, w.obs.p, w.flags.p, w.cum.p, w.draw.p);
+  double* ord_value = w.order.p;
+  double* ord_cum = w.order.p + (size_t)B * ci::SUMM_MAX_RANKS * T;
+  HIP_TRY(launch_select(stream, N, T, B * T, num_ranks, w.ranks.p, w.value.p, w.cum.p,
+                        ord_value, ord_cum));
+  double* ord_draw = w.draw.p + (size_t)B * 2 * N;
+  if (per_draw_order)
+    HIP_TRY(launch_select(stream, N, 1, 2 * B, num_ranks, w.ranks.p, w.draw.p, nullptr,
+                          ord_draw, nullptr));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(stream));
+  const size_t ord_bytes = (size_t)B * num_ranks * T * sizeof(double);
+  if (value_order) HIP_TRY(hipMemcpy(value_order, ord_value, ord_bytes, hipMemcpyDeviceToHost));
+  if (cum_order) HIP_TRY(hipMemcpy(cum_order, ord_cum, ord_bytes, hipMemcpyDeviceToHost));
+  if (per_draw)
+    HIP_TRY(hipMemcpy(per_draw, w.draw.p, (size_t)B * 2 * N * sizeof(double), hipMemcpyDeviceToHost));
+  if (per_draw_order)
+    HIP_TRY(hipMemcpy(per_draw_order, ord_draw, (size_t)B * 2 * num_ranks * sizeof(double),
+                      hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int ci_session_summarize(ci_session* s, const double* scale, const double* shift,
                          const double* observed, const uint8_t* flags, int32_t num_ranks,
                          const int32_t* ranks, double* value_order, double* cum_order,
@@ -1135,52 +1200,10 @@ int ci_session_summarize(ci_session* s, const double* scale, const double* shift
   if (!s || !scale || !shift || !observed || !flags || !ranks) return fail("NULL argument");
   if (!s->ran) return fail("ci_session_summarize needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
-  if (num_ranks < 1 || num_ranks > ci::SUMM_MAX_RANKS)
-    return fail("num_ranks must be in [1, %d], got %d", ci::SUMM_MAX_RANKS, num_ranks);
-  const int T = pb.T, N = pb.num_chains * pb.num_results, B = pb.num_series;
-  for (int r = 0; r < num_ranks; ++r)
-    if (ranks[r] < 0 || ranks[r] >= N) return fail("rank %d out of range [0, %d)", ranks[r], N);
   HIP_TRY(hipSetDevice(pb.device));
-  const size_t BTN = (size_t)B * T * N;
-  if (!s->s_value.p) {
-    HIP_TRY(s->s_value.alloc(BTN));
-    HIP_TRY(s->s_cum.alloc(BTN));
-    HIP_TRY(s->s_obs.alloc((size_t)B * T + 2 * B));
-    HIP_TRY(s->s_flags.alloc((size_t)B * T));
-    HIP_TRY(s->s_ranks.alloc(ci::SUMM_MAX_RANKS));
-    HIP_TRY(s->s_order.alloc((size_t)2 * B * ci::SUMM_MAX_RANKS * T));
-    HIP_TRY(s->s_draw.alloc((size_t)B * 2 * N + (size_t)B * 2 * ci::SUMM_MAX_RANKS));
-  }
-  double* d_scale = s->s_obs.p + (size_t)B * T;
-  double* d_shift = d_scale + B;
-  HIP_TRY(hipMemcpyAsync(s->s_obs.p, observed, (size_t)B * T * sizeof(double), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(s->s_flags.p, flags, (size_t)B * T, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(s->s_ranks.p, ranks, num_ranks * sizeof(int), hipMemcpyHostToDevice, s->stream));
-  hipLaunchKernelGGL(ci::summ_transpose_kernel<float>, dim3((T + 63) / 64, (N + 63) / 64, B), dim3(64, 4), 0,
-                     s->stream, N, T, s->o_traj.p, d_scale, d_shift, s->s_value.p);
-  hipLaunchKernelGGL(ci::summ_cumsum_kernel, dim3((N + 63) / 64, B), dim3(64), 0, s->stream, N, T,
-                     s->s_value.p, s->s_obs.p, s->s_flags.p, s->s_cum.p, s->s_draw.p);
-  double* ord_value = s->s_order.p;
-  double* ord_cum = s->s_order.p + (size_t)B * ci::SUMM_MAX_RANKS * T;
-  HIP_TRY(launch_select(s->stream, N, T, B * T, num_ranks, s->s_ranks.p, s->s_value.p, s->s_cum.p,
-                        ord_value, ord_cum));
-  double* ord_draw = s->s_draw.p + (size_t)B * 2 * N;
-  if (per_draw_order)
-    HIP_TRY(launch_select(s->stream, N, 1, 2 * B, num_ranks, s->s_ranks.p, s->s_draw.p, nullptr,
-                          ord_draw, nullptr));
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  const size_t ord_bytes = (size_t)B * num_ranks * T * sizeof(double);
-  if (value_order) HIP_TRY(hipMemcpy(value_order, ord_value, ord_bytes, hipMemcpyDeviceToHost));
-  if (cum_order) HIP_TRY(hipMemcpy(cum_order, ord_cum, ord_bytes, hipMemcpyDeviceToHost));
-  if (per_draw)
-    HIP_TRY(hipMemcpy(per_draw, s->s_draw.p, (size_t)B * 2 * N * sizeof(double), hipMemcpyDeviceToHost));
-  if (per_draw_order)
-    HIP_TRY(hipMemcpy(per_draw_order, ord_draw, (size_t)B * 2 * num_ranks * sizeof(double),
-                      hipMemcpyDeviceToHost));
-  return 0;
+  return summarize_resident(s->stream, s->summ, pb.num_series, pb.T, pb.num_chains * pb.num_results,
+                            s->o_traj.p, scale, shift, observed, flags, num_ranks, ranks, value_order,
+                            cum_order, per_draw, per_draw_order);
 }
 
 extern "C++" {
@@ -1342,8 +1365,7 @@ int ci_session_destroy(ci_session* s) {
   s->o_traj.release(); s->mask.release(); s->xtx.release(); s->omega.release(); s->wps.release(); s->sp.release(); s->prof.release();
   s->season_change.release(); s->ssp.release(); s->p1_chol.release(); s->o_drift.release();
   s->o_seasonal.release(); s->ws.release(); s->csync.release(); s->cpart.release(); s->cw.release(); s->cv.release();
-  s->s_value.release(); s->s_cum.release(); s->s_obs.release(); s->s_flags.release();
-  s->s_ranks.release(); s->s_order.release(); s->s_draw.release();
+  s->summ.release();
   pool_event_put(s->ev0, s->pb.device);
   pool_event_put(s->ev1, s->pb.device);
   pool_stream_put(s->stream, s->pb.device);
@@ -1607,7 +1629,33 @@ struct ci_ll_session {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   ci_series_params prm;
+  // B series (ci_ll_session_create_batch; 1 otherwise): y, mask [B, T], xt [B, P, T], omega [B, P, P]
+  // and the fit's outputs with a leading series axis.  Series b draws from the Philox key of series
+  // id series_stream_base + b, or from the seed itself when series_stream_base < 0.
+  int B = 1, series_stream_base = -1;
+  std::vector<ci_series_params> prms;       // [B]
+  DevBuf<ci::HmcSeries> h_ser;              // [B]: what hmc_kernel / latents_kernel read per series
+  SummScratch summ;                         // ci_ll_session_hmc_summarize
 };
+
+extern "C++" {
+namespace {
+// Gaussian slab of the weights prior: Omega = 0.01 (X'X/2 + diag(X'X)/2) / T, all rows
+// (causalimpact_lib.py:451-453); X [T, P] row-major.
+std::vector<double> slab_omega(const float* X, int T, int P, double weights_prior_scale) {
+  std::vector<double> om((size_t)P * P, 0.0);
+  for (int t = 0; t < T; ++t)
+    for (int i = 0; i < P; ++i)
+      for (int j = 0; j < P; ++j)
+        om[(size_t)i * P + j] += (double)X[(size_t)t * P + i] * (double)X[(size_t)t * P + j];
+  for (int i = 0; i < P; ++i)
+    for (int j = 0; j < P; ++j)
+      om[(size_t)i * P + j] = 0.01 * (i == j ? om[(size_t)i * P + j] : 0.5 * om[(size_t)i * P + j]) / T *
+                              weights_prior_scale;
+  return om;
+}
+}  // namespace
+}  // extern "C++"
 
 int ci_ll_session_destroy(ci_ll_session* s);
 struct LlSessionGuard {
@@ -1712,24 +1760,87 @@ int ci_ll_session_create2(const ci_problem* pb, const ci_series_params* params, 
   HIP_TRY(hipMemcpy(s->y.p, yh.data(), T * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(s->mask.p, mask, T, hipMemcpyHostToDevice));
   s->prm = *params;
+  s->prms.assign(1, *params);
   if (P > 0) {
     std::vector<float> xt((size_t)P * T);
     for (int t = 0; t < T; ++t)
       for (int j = 0; j < P; ++j) xt[(size_t)j * T + t] = X[(size_t)t * P + j];
     HIP_TRY(hipMemcpy(s->xt.p, xt.data(), xt.size() * sizeof(float), hipMemcpyHostToDevice));
-    // Gaussian slab of the weights prior: Omega = 0.01 (X'X/2 + diag(X'X)/2) / T, all rows
-    // (causalimpact_lib.py:451-453)
-    std::vector<double> om((size_t)P * P, 0.0);
-    for (int t = 0; t < T; ++t)
-      for (int i = 0; i < P; ++i)
-        for (int j = 0; j < P; ++j)
-          om[(size_t)i * P + j] += (double)X[(size_t)t * P + i] * (double)X[(size_t)t * P + j];
-    for (int i = 0; i < P; ++i)
-      for (int j = 0; j < P; ++j)
-        om[(size_t)i * P + j] = 0.01 * (i == j ? om[(size_t)i * P + j] : 0.5 * om[(size_t)i * P + j]) / T *
-                                params->weights_prior_scale;
+    const std::vector<double> om = slab_omega(X, T, P, params->weights_prior_scale);
     HIP_TRY(s->omega.alloc((size_t)P * P));
     HIP_TRY(hipMemcpy(s->omega.p, om.data(), om.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  guard.s = nullptr;
+  *out = s;
+  return 0;
+}
+
+int ci_ll_session_create_batch(const ci_problem* pb, const ci_series_params* params, const float* y,
+                               const uint8_t* mask, const float* X, int32_t max_evals,
+                               ci_ll_session** out) {
+  // everything is checked before the first device call
+  if (!pb || !params || !y || !mask || !out)
+    return fail("ci_ll_session_create_batch: problem, params, y, mask and session must not be NULL");
+  const int B = pb->num_series, T = pb->T, P = pb->P;
+  if (B < 1) return fail("ci_ll_session_create_batch: num_series must be >= 1, got %d", B);
+  if (pb->num_blocks != 0)
+    return fail("ci_ll_session_create_batch: seasonal blocks are not supported (trend models only; "
+                "fit seasonal models one series at a time with ci_ll_session_create2)");
+  if (T > ci::NT * 16)
+    return fail("ci_ll_session_create_batch: T must be <= %d, got %d (longer series: one at a time "
+                "with ci_ll_session_create2)", ci::NT * 16, T);
+  if (P > ci::HMC_MAXP)
+    return fail("ci_ll_session_create_batch: P must be <= %d, got %d", ci::HMC_MAXP, P);
+  if (validate(pb)) return 1;
+  if (max_evals < 1) return fail("ci_ll_session_create_batch: max_evals must be >= 1, got %d", max_evals);
+  if (P > 0 && !X) return fail("ci_ll_session_create_batch: X is NULL but P=%d", P);
+  for (int b = 0; b < B; ++b)
+    if (!(params[b].weights_prior_scale > 0.0) || !std::isfinite(params[b].weights_prior_scale))
+      return fail("ci_ll_session_create_batch: params[%d].weights_prior_scale must be positive and "
+                  "finite, got %g", b, params[b].weights_prior_scale);
+  for (size_t i = 0; i < (size_t)B * T; ++i)
+    if (!mask[i] && !std::isfinite(y[i]))
+      return fail("ci_ll_session_create_batch: y[%d, %d] is not finite but unmasked", (int)(i / T),
+                  (int)(i % T));
+  HIP_TRY(hipSetDevice(pb->device));
+  ci_ll_session* s = new ci_ll_session();
+  LlSessionGuard guard{s};
+  s->T = T; s->P = P; s->D = pb->has_slope ? 2 : 1; s->L = steps_per_thread(T);
+  s->device = pb->device; s->max_evals = max_evals; s->D_full = s->D;
+  s->B = B;
+  s->series_stream_base = (pb->flags & CI_FLAG_SHARED_SERIES_STREAMS) ? -1 : pb->series_offset;
+  s->prm = params[0];
+  s->prms.assign(params, params + B);
+  s->a1 = (float)params[0].init_level_loc;
+  s->p10 = (float)(params[0].init_level_scale * params[0].init_level_scale);
+  s->p11 = (float)(params[0].init_slope_scale * params[0].init_slope_scale);
+  HIP_TRY(pool_stream_get(&s->stream));
+  HIP_TRY(pool_event_get(&s->ev0));
+  HIP_TRY(pool_event_get(&s->ev1));
+  HIP_TRY(pool_event_get(&s->ev2));
+  HIP_TRY(s->y.alloc((size_t)B * T));
+  HIP_TRY(s->mask.alloc((size_t)B * T));
+  HIP_TRY(s->xt.alloc((size_t)B * P * T));
+  HIP_TRY(s->omega.alloc((size_t)B * P * P));
+  HIP_TRY(s->theta.alloc((size_t)max_evals * (3 + P)));
+  HIP_TRY(s->ll.alloc(max_evals));
+  HIP_TRY(s->grad.alloc((size_t)max_evals * (3 + P)));
+  std::vector<float> yh((size_t)B * T);
+  for (size_t i = 0; i < yh.size(); ++i) yh[i] = mask[i] ? 0.f : y[i];
+  HIP_TRY(hipMemcpy(s->y.p, yh.data(), yh.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->mask.p, mask, (size_t)B * T, hipMemcpyHostToDevice));
+  if (P > 0) {
+    std::vector<float> xt((size_t)P * T);
+    for (int b = 0; b < B; ++b) {
+      const float* Xb = X + (size_t)b * T * P;
+      for (int t = 0; t < T; ++t)
+        for (int j = 0; j < P; ++j) xt[(size_t)j * T + t] = Xb[(size_t)t * P + j];
+      HIP_TRY(hipMemcpy(s->xt.p + (size_t)b * P * T, xt.data(), xt.size() * sizeof(float),
+                        hipMemcpyHostToDevice));
+      const std::vector<double> om = slab_omega(Xb, T, P, params[b].weights_prior_scale);
+      HIP_TRY(hipMemcpy(s->omega.p + (size_t)b * P * P, om.data(), om.size() * sizeof(double),
+                        hipMemcpyHostToDevice));
+    }
   }
   guard.s = nullptr;
   *out = s;
@@ -1848,14 +1959,16 @@ int ci_ll_session_hmc_run(ci_ll_session* s, const ci_hmc_options* o, const doubl
     return fail("prior must be CI_HMC_PRIOR_SLAB or CI_HMC_PRIOR_HORSESHOE, got %d", o->prior);
   if (o->prior == CI_HMC_PRIOR_HORSESHOE && !(o->horseshoe_scale > 0.0))
     return fail("horseshoe prior needs horseshoe_scale > 0");
+  if (o->num_chains > 65535) return fail("num_chains must be <= 65535, got %d", o->num_chains);
   HIP_TRY(hipSetDevice(s->device));
-  const int P = s->P, C = o->num_chains, S = o->num_results, T = s->T;
-  const size_t N = (size_t)C * S;
+  // num_chains is per series: B x C chains, every per-chain output with a leading series axis
+  const int P = s->P, C = o->num_chains, S = o->num_results, T = s->T, B = s->B;
+  const size_t BC = (size_t)B * C, N = BC * S;
   if (s->h_C != C || s->h_S != S) {
     s->h_draws.release(); s->h_acc.release(); s->h_eps.release();
     s->h_level.release(); s->h_slope.release(); s->h_part.release(); s->h_traj.release();
     s->h_pm.release(); s->h_obs.release(); s->h_lscale.release(); s->h_sscale.release();
-    s->h_w.release();
+    s->h_w.release(); s->summ.release();
     s->h_C = 0; s->h_S = 0;          // an allocation failing below must not leave a stale shape
     HIP_TRY(s->h_draws.alloc(N * (3 + s->K + P)));
     if (s->seq) {
@@ -1864,13 +1977,13 @@ int ci_ll_session_hmc_run(ci_ll_session* s, const ci_hmc_options* o, const doubl
       HIP_TRY(s->h_drift.alloc(N * s->K));
       HIP_TRY(s->h_loc.alloc(N * T));
     }
-    HIP_TRY(s->h_acc.alloc(C));
-    HIP_TRY(s->h_eps.alloc(C));
+    HIP_TRY(s->h_acc.alloc(BC));
+    HIP_TRY(s->h_eps.alloc(BC));
     HIP_TRY(s->h_level.alloc(N * T));
     HIP_TRY(s->h_slope.alloc(s->D == 2 ? N * T : 0));
-    HIP_TRY(s->h_part.alloc((size_t)C * ((S + HMC_LATENT_GROUP - 1) / HMC_LATENT_GROUP) * T));
+    HIP_TRY(s->h_part.alloc(BC * ((S + HMC_LATENT_GROUP - 1) / HMC_LATENT_GROUP) * T));
     HIP_TRY(s->h_traj.alloc(N * T));
-    HIP_TRY(s->h_pm.alloc((size_t)C * T));
+    HIP_TRY(s->h_pm.alloc(BC * T));
     HIP_TRY(s->h_obs.alloc(N));
     HIP_TRY(s->h_lscale.alloc(N));
     HIP_TRY(s->h_sscale.alloc(N));
@@ -1881,10 +1994,29 @@ int ci_ll_session_hmc_run(ci_ll_session* s, const ci_hmc_options* o, const doubl
   if (s->seq) return hmc_run_sequential(s, o, init_theta, kernel_ms);
   const int dim = ci::hmc_dim(P, s->D, o->prior);
   if (init_theta) {
-    if (s->h_init.n != (size_t)C * dim) { s->h_init.release(); HIP_TRY(s->h_init.alloc((size_t)C * dim)); }
-    HIP_TRY(hipMemcpyAsync(s->h_init.p, init_theta, (size_t)C * dim * sizeof(double),
+    if (s->h_init.n != BC * dim) { s->h_init.release(); HIP_TRY(s->h_init.alloc(BC * dim)); }
+    HIP_TRY(hipMemcpyAsync(s->h_init.p, init_theta, BC * dim * sizeof(double),
                            hipMemcpyHostToDevice, s->stream));
   }
+  // the per-series constants (hmc_kernel, latents_kernel)
+  std::vector<ci::HmcSeries> ser(B);
+  for (int b = 0; b < B; ++b) {
+    const ci_series_params& q = s->prms[b];
+    ci::HmcSeries& e = ser[b];
+    e.ig_a[0] = q.obs_conc; e.ig_b[0] = q.obs_scale;
+    e.ig_a[1] = q.level_conc; e.ig_b[1] = q.level_scale;
+    e.ig_a[2] = q.slope_conc; e.ig_b[2] = q.slope_scale;
+    e.init_log[0] = std::log(q.obs_scale0);
+    e.init_log[1] = std::log(std::max(q.level_scale0, 1e-4));
+    e.init_log[2] = std::log(std::max(q.slope_scale0, 1e-4));
+    e.hs_scale0 = o->horseshoe_scale;
+    e.a1 = (float)q.init_level_loc;
+    e.p10 = (float)(q.init_level_scale * q.init_level_scale);
+    e.p11 = (float)(q.init_slope_scale * q.init_slope_scale);
+    e.pad = 0.f;
+  }
+  if (s->h_ser.n != (size_t)B) { s->h_ser.release(); HIP_TRY(s->h_ser.alloc(B)); }
+  HIP_TRY(hipMemcpy(s->h_ser.p, ser.data(), B * sizeof(ci::HmcSeries), hipMemcpyHostToDevice));
   ci::HmcArgs a;
   a.init = init_theta ? s->h_init.p : nullptr;
   {
@@ -1901,18 +2033,11 @@ int ci_ll_session_hmc_run(ci_ll_session* s, const ci_hmc_options* o, const doubl
     HIP_TRY(hipMemsetAsync(hprof.p, 0, 32 * sizeof(long long), s->stream));
     a.prof = hprof.p;
   }
-  a.T = T; a.P = P; a.C = C; a.W = o->num_warmup; a.S = S; a.n_leap = o->num_leapfrog;
+  a.T = T; a.P = P; a.B = B; a.C = C; a.W = o->num_warmup; a.S = S; a.n_leap = o->num_leapfrog;
   a.chain_offset = o->chain_offset; a.seed0 = o->seed[0]; a.seed1 = o->seed[1];
-  a.prior_mode = o->prior; a.hs_scale0 = o->horseshoe_scale;
-  a.y = s->y.p; a.mask = s->mask.p; a.Xt = s->xt.p; a.omega = s->omega.p;
-  const ci_series_params& q = s->prm;
-  a.ig_a[0] = q.obs_conc; a.ig_b[0] = q.obs_scale;
-  a.ig_a[1] = q.level_conc; a.ig_b[1] = q.level_scale;
-  a.ig_a[2] = q.slope_conc; a.ig_b[2] = q.slope_scale;
-  a.init_log[0] = std::log(q.obs_scale0);
-  a.init_log[1] = std::log(std::max(q.level_scale0, 1e-4));
-  a.init_log[2] = std::log(std::max(q.slope_scale0, 1e-4));
-  a.a1 = s->a1; a.p10 = s->p10; a.p11 = s->p11;
+  a.series_stream_base = s->series_stream_base;
+  a.prior_mode = o->prior;
+  a.y = s->y.p; a.mask = s->mask.p; a.Xt = s->xt.p; a.omega = s->omega.p; a.ser = s->h_ser.p;
   a.target_accept = o->target_accept; a.eps0 = o->initial_step_size;
   a.draws = s->h_draws.p; a.accept_rate = s->h_acc.p; a.step_size = s->h_eps.p;
   const int D = s->D, L = s->L;
@@ -1929,13 +2054,13 @@ int ci_ll_session_hmc_run(ci_ll_session* s, const ci_hmc_options* o, const doubl
   if (D == DD && L == LL)                                                                         \
     ci_launch_latents_d##DD##_l##LL(T, P, (int)N, s->y.p, s->mask.p, s->xt.p, s->h_draws.p, s->a1, \
                                     s->p10, s->p11, o->seed[0], o->seed[1],                       \
-                                    (uint32_t)o->chain_offset, 0u, S, HMC_LATENT_GROUP,           \
-                                    s->h_level.p, s->h_slope.p, nullptr, s->h_traj.p,             \
-                                    s->h_part.p, s->stream);
+                                    (uint32_t)o->chain_offset, 0u, S, HMC_LATENT_GROUP, C,        \
+                                    s->series_stream_base, s->h_ser.p, s->h_level.p, s->h_slope.p, \
+                                    nullptr, s->h_traj.p, s->h_part.p, s->stream);
   CI_LAT_CASE(1, 1) CI_LAT_CASE(1, 2) CI_LAT_CASE(1, 4) CI_LAT_CASE(1, 8) CI_LAT_CASE(1, 16)
   CI_LAT_CASE(2, 1) CI_LAT_CASE(2, 2) CI_LAT_CASE(2, 4) CI_LAT_CASE(2, 8) CI_LAT_CASE(2, 16)
 #undef CI_LAT_CASE
-  hipLaunchKernelGGL(ci::hmc_mean_kernel, dim3((T + 255) / 256, C), dim3(256), 0, s->stream, C,
+  hipLaunchKernelGGL(ci::hmc_mean_kernel, dim3((T + 255) / 256, C, B), dim3(256), 0, s->stream, C,
                      (S + HMC_LATENT_GROUP - 1) / HMC_LATENT_GROUP, S, T, s->h_part.p, s->h_pm.p);
   hipLaunchKernelGGL(ci::hmc_unpack_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream,
                      (int)N, P, s->h_draws.p, s->h_obs.p, s->h_lscale.p, s->h_sscale.p, s->h_w.p);
@@ -1962,10 +2087,9 @@ int ci_ll_session_hmc_fetch(ci_ll_session* s, double* draws, double* accept_rate
   if (!s) return fail("session is NULL");
   if (!s->h_ran) return fail("ci_ll_session_hmc_fetch needs a finished ci_ll_session_hmc_run");
   HIP_TRY(hipSetDevice(s->device));
-  const int C = s->h_C;
   if (draws) HIP_TRY(hipMemcpy(draws, s->h_draws.p, s->h_draws.n * sizeof(double), hipMemcpyDeviceToHost));
-  if (accept_rate) HIP_TRY(hipMemcpy(accept_rate, s->h_acc.p, C * sizeof(double), hipMemcpyDeviceToHost));
-  if (step_size) HIP_TRY(hipMemcpy(step_size, s->h_eps.p, C * sizeof(double), hipMemcpyDeviceToHost));
+  if (accept_rate) HIP_TRY(hipMemcpy(accept_rate, s->h_acc.p, s->h_acc.n * sizeof(double), hipMemcpyDeviceToHost));
+  if (step_size) HIP_TRY(hipMemcpy(step_size, s->h_eps.p, s->h_eps.n * sizeof(double), hipMemcpyDeviceToHost));
   if (o) {
     auto get = [&](float* dst, const DevBuf<float>& src) -> hipError_t {
       if (!dst || src.n == 0) return hipSuccess;
@@ -1988,6 +2112,18 @@ int ci_ll_session_hmc_fetch(ci_ll_session* s, double* draws, double* accept_rate
   return 0;
 }
 
+int ci_ll_session_hmc_summarize(ci_ll_session* s, const double* scale, const double* shift,
+                                const double* observed, const uint8_t* flags, int32_t num_ranks,
+                                const int32_t* ranks, double* value_order, double* cum_order,
+                                double* per_draw, double* per_draw_order) {
+  if (!s || !scale || !shift || !observed || !flags || !ranks) return fail("NULL argument");
+  if (!s->h_ran) return fail("ci_ll_session_hmc_summarize needs a finished ci_ll_session_hmc_run");
+  HIP_TRY(hipSetDevice(s->device));
+  return summarize_resident(s->stream, s->summ, s->B, s->T, s->h_C * s->h_S, s->h_traj.p, scale, shift,
+                            observed, flags, num_ranks, ranks, value_order, cum_order, per_draw,
+                            per_draw_order);
+}
+
 int ci_ll_session_kernel_name(const ci_ll_session* s, char* buf, int32_t buflen) {
   if (!s) return fail("session is NULL");
   char nm[64];
@@ -2006,13 +2142,14 @@ int ci_ll_session_algorithmic_bytes(const ci_ll_session* s, double* bytes) {
   const double T = s->T, P = s->P, slope = s->D == 2 ? 1.0 : 0.0, K = s->K;
   const double per_draw = 4.0 * T * (1.0 + slope + K + 1.0) + 4.0 * (P + 2.0 + slope + K);
   const double per_chain = 4.0 * T * (P + 1.0) + T;
-  *bytes = (double)s->h_C * ((double)s->h_S * per_draw + per_chain);
+  *bytes = (double)s->B * s->h_C * ((double)s->h_S * per_draw + per_chain);
   return 0;
 }
 
 int ci_ll_session_eval(ci_ll_session* s, int32_t num_evals, const double* theta, double* loglik,
                        double* grad) {
   if (!s || !theta || !loglik) return fail("NULL argument");
+  if (s->B > 1) return fail("ci_ll_session_eval: one series per session only (this session holds %d)", s->B);
   if (num_evals < 1 || num_evals > s->max_evals) return fail("num_evals out of range");
   HIP_TRY(hipSetDevice(s->device));
   const int T = s->T, P = s->P, D = s->D, L = s->L, E = num_evals;
@@ -2061,6 +2198,8 @@ int ci_ll_session_draw_latents(ci_ll_session* s, int32_t num_draws, const double
                                float* level, float* slope, float* loc, float* traj) {
   if (!s || !theta || !seed || !level || !loc || !traj) return fail("NULL argument");
   if (s->seq) return fail("ci_ll_session_draw_latents: trend models with T <= 4096 only");
+  if (s->B > 1)
+    return fail("ci_ll_session_draw_latents: one series per session only (this session holds %d)", s->B);
   if (num_draws < 1 || num_draws > s->max_evals) return fail("num_draws out of range");
   HIP_TRY(hipSetDevice(s->device));
   const int T = s->T, P = s->P, D = s->D, L = s->L, E = num_draws;
@@ -2075,8 +2214,9 @@ int ci_ll_session_draw_latents(ci_ll_session* s, int32_t num_draws, const double
 #define CI_LAT_CASE(DD, LL)                                                                       \
   if (D == DD && L == LL)                                                                         \
     ci_launch_latents_d##DD##_l##LL(T, P, E, s->y.p, s->mask.p, s->xt.p, s->theta.p, s->a1,       \
-                                    s->p10, s->p11, seed[0], seed[1], rng_chain, iter0, 0, 1,     \
-                                    s->level.p, s->slope.p, s->loc.p, s->traj.p, nullptr, 0);
+                                    s->p10, s->p11, seed[0], seed[1], rng_chain, iter0, 0, 1, 0,  \
+                                    -1, nullptr, s->level.p, s->slope.p, s->loc.p, s->traj.p,     \
+                                    nullptr, 0);
   CI_LAT_CASE(1, 1) CI_LAT_CASE(1, 2) CI_LAT_CASE(1, 4) CI_LAT_CASE(1, 8) CI_LAT_CASE(1, 16)
   CI_LAT_CASE(2, 1) CI_LAT_CASE(2, 2) CI_LAT_CASE(2, 4) CI_LAT_CASE(2, 8) CI_LAT_CASE(2, 16)
 #undef CI_LAT_CASE
@@ -2099,7 +2239,7 @@ int ci_ll_session_destroy(ci_ll_session* s) {
   s->omega.release(); s->h_draws.release(); s->h_acc.release(); s->h_eps.release(); s->h_init.release();
   s->h_level.release(); s->h_slope.release(); s->h_part.release(); s->h_traj.release();
   s->h_pm.release(); s->h_obs.release(); s->h_lscale.release(); s->h_sscale.release();
-  s->h_w.release();
+  s->h_w.release(); s->h_ser.release(); s->summ.release();
   pool_event_put(s->ev0, s->device);
   pool_event_put(s->ev1, s->device);
   pool_event_put(s->ev2, s->device);

@@ -61,25 +61,27 @@ __host__ __device__ inline HmcWindows hmc_windows(int W) {
   return w;
 }
 
+// B series x C chains: workgroup g runs chain g % C of series g / C.  Per-series inputs sit at
+// base + series * stride (y, mask: T; Xt: P T; omega: P P) and in ser[series]; per-chain outputs are
+// [B, C, ...], i.e. indexed by the workgroup.  Series s draws from the Philox key
+// (stream_key0(seed0, series_stream_base, s), stream_key1(seed1, ...)), counter chain_offset + c: with
+// series_stream_base < 0 every series uses (seed0, seed1), the key of a single-series fit.
 struct HmcArgs {
-  int T, P, C, W, S, n_leap, chain_offset, x_in_lds, prior_mode;
+  int T, P, B, C, W, S, n_leap, chain_offset, x_in_lds, prior_mode, series_stream_base;
   uint32_t seed0, seed1;
-  const float* y;
-  const uint8_t* mask;
-  const float* Xt;
-  const double* omega;      // [P, P]
-  double ig_a[3], ig_b[3];  // inverse-gamma (concentration, scale) of sigma^2: obs, level, slope
-  double init_log[3];       // log of the initial scales (causalimpact_lib.py:566-572)
-  double hs_scale0;         // horseshoe: weights_prior_scale
-  float a1, p10, p11;
+  const float* y;           // [B, T]
+  const uint8_t* mask;      // [B, T]
+  const float* Xt;          // [B, P, T]
+  const double* omega;      // [B, P, P]
+  const HmcSeries* ser;     // [B]: prior constants, initial scales, initial state (ci_kernels.h)
   double target_accept, eps0;
-  const double* init;       // optional [C, dim] unconstrained starting points (e.g. draws of a
+  const double* init;       // optional [B, C, dim] unconstrained starting points (e.g. draws of a
                             // fitted surrogate posterior); NULL = the Gibbs sampler's initial state
   int legacy_driver;        // tests: 1 = the round 2-4 driver (five barriers around every score), whatever dim
   long long* prof;          // tools/exp_hmc_phases.py: 32 cycle counters of chain 0's thread 0, or NULL
-  double* draws;            // [C, S, 3 + P]  (sigma_obs, sigma_level, sigma_slope, beta)
-  double* accept_rate;      // [C]
-  double* step_size;        // [C]
+  double* draws;            // [B, C, S, 3 + P]  (sigma_obs, sigma_level, sigma_slope, beta)
+  double* accept_rate;      // [B, C]
+  double* step_size;        // [B, C]
 };
 
 __host__ __device__ inline int hmc_dim(int P, int D, int prior_mode) {
@@ -115,6 +117,15 @@ __global__ __launch_bounds__(NT) void hmc_kernel(HmcArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int P = a.P, T = a.T;
+  // workgroup = (series, chain); the series' inputs at base + series * stride
+  const int series = (int)blockIdx.x / a.C, chain = (int)blockIdx.x - series * a.C;
+  const float* y_s = a.y + (size_t)series * T;
+  const uint8_t* mask_s = a.mask + (size_t)series * T;
+  const float* Xt_s = a.Xt + (size_t)series * P * T;
+  const double* omega_s = a.omega + (size_t)series * P * P;
+  const HmcSeries& sp = a.ser[series];
+  const double hs_scale0 = sp.hs_scale0;
+  const float a1 = sp.a1, p10 = sp.p10, p11 = sp.p11;
   constexpr int NSC = (D == 2) ? 3 : 2;          // number of scales in the parameter vector
   const bool hs = a.prior_mode == 1;
   const int off_sc = hs ? 3 * P + 2 : P;         // where the log scales start
@@ -142,15 +153,15 @@ __global__ __launch_bounds__(NT) void hmc_kernel(HmcArgs a) {
   const bool x_in_lds = a.x_in_lds != 0;
   if (x_in_lds) {
     for (int j = 0; j < P; ++j)
-      for (int t = tid; t < TPAD; t += NT) Xs[j * TPAD + t] = t < T ? a.Xt[(size_t)j * T + t] : 0.f;
+      for (int t = tid; t < TPAD; t += NT) Xs[j * TPAD + t] = t < T ? Xt_s[(size_t)j * T + t] : 0.f;
   }
-  const int chain = blockIdx.x;
-  Rng rng{a.seed0, a.seed1, (uint32_t)(a.chain_offset + chain)};
+  Rng rng{stream_key0(a.seed0, a.series_stream_base, series), stream_key1(a.seed1, a.series_stream_base, series),
+          (uint32_t)(a.chain_offset + chain)};
 
   // d beta_j / d z_j of the horseshoe at the unconstrained point v
   auto hs_scale = [&](const double* v, int j) CI_HMC_INLINE {
     return exp(clamp30(v[P + j]) + 0.5 * clamp30(v[2 * P + j]) + clamp30(v[3 * P]) +
-               0.5 * clamp30(v[3 * P + 1])) * a.hs_scale0;
+               0.5 * clamp30(v[3 * P + 1])) * hs_scale0;
   };
 
   // The per-coordinate work of a leapfrog step -- momentum / position update, the device layout of
@@ -167,12 +178,12 @@ __global__ __launch_bounds__(NT) void hmc_kernel(HmcArgs a) {
   const bool om_regs = !hs && P <= 16 && L <= 4;      // (the L = 8, 16 builds have no registers to spare)
   double om[16];
 #pragma unroll
-  for (int k = 0; k < 16; ++k) om[k] = (om_regs && lane < P && k < P) ? a.omega[k * P + lane] : 0.0;
+  for (int k = 0; k < 16; ++k) om[k] = (om_regs && lane < P && k < P) ? omega_s[k * P + lane] : 0.0;
   double my_iga = 0.0, my_igb = 0.0;
   // (a select chain: a run-time index into the by-value arguments would move them to scratch)
-  const double iga0 = a.ig_a[0], iga1 = a.ig_a[1], iga2 = a.ig_a[2];
-  const double igb0 = a.ig_b[0], igb1 = a.ig_b[1], igb2 = a.ig_b[2];
-  const double il0 = a.init_log[0], il1 = a.init_log[1], il2 = a.init_log[2];
+  const double iga0 = sp.ig_a[0], iga1 = sp.ig_a[1], iga2 = sp.ig_a[2];
+  const double igb0 = sp.ig_b[0], igb1 = sp.ig_b[1], igb2 = sp.ig_b[2];
+  const double il0 = sp.init_log[0], il1 = sp.init_log[1], il2 = sp.init_log[2];
   auto pick3 = [](double v0, double v1, double v2, int k) { return k == 0 ? v0 : (k == 1 ? v1 : v2); };
   if (lane >= off_sc && lane < dim && dim <= 64) {
     my_iga = pick3(iga0, iga1, iga2, lane - off_sc);
@@ -205,14 +216,14 @@ __global__ __launch_bounds__(NT) void hmc_kernel(HmcArgs a) {
   // register limit already, reloads them per evaluation)
   float yv[L];
   uint32_t maskbits;
-  if constexpr (L <= 8) loglik_load_obs<L>(T, a.y, a.mask, tid, yv, maskbits);
+  if constexpr (L <= 8) loglik_load_obs<L>(T, y_s, mask_s, tid, yv, maskbits);
   auto score = [&]() CI_HMC_INLINE {
-    if constexpr (L > 8) loglik_load_obs<L>(T, a.y, a.mask, tid, yv, maskbits);
+    if constexpr (L > 8) loglik_load_obs<L>(T, y_s, mask_s, tid, yv, maskbits);
     if (x_in_lds)
-      loglik_grad_block_obs<D, L>(T, P, yv, maskbits, Xs, dev, a.a1, a.p10, a.p11, slots, part, &sc[0],
+      loglik_grad_block_obs<D, L>(T, P, yv, maskbits, Xs, dev, a1, p10, p11, slots, part, &sc[0],
                                   gdev, tid, lane, wave, TPAD, &hp);
     else
-      loglik_grad_block_obs<D, L>(T, P, yv, maskbits, a.Xt, dev, a.a1, a.p10, a.p11, slots, part, &sc[0],
+      loglik_grad_block_obs<D, L>(T, P, yv, maskbits, Xt_s, dev, a1, p10, p11, slots, part, &sc[0],
                                   gdev, tid, lane, wave, 0, &hp);
   };
   // Omega th for coordinate i (slab prior): the column from registers (P <= 16, i == lane) or L2
@@ -225,7 +236,7 @@ __global__ __launch_bounds__(NT) void hmc_kernel(HmcArgs a) {
 #pragma unroll
       for (int k = 0; k < 16; ++k) ob = k < P ? fma(tk[k], om[k], ob) : ob;
     } else {
-      for (int k = 0; k < P; ++k) ob = fma(th[k], a.omega[k * P + i], ob);
+      for (int k = 0; k < P; ++k) ob = fma(th[k], omega_s[k * P + i], ob);
     }
     return ob;
   };
@@ -330,7 +341,7 @@ __global__ __launch_bounds__(NT) void hmc_kernel(HmcArgs a) {
   if (tid < dim) {
     double v = 0.0;
     if (tid >= off_sc) v = pick3(il0, il1, il2, tid - off_sc);
-    if (a.init) th[tid] = a.init[(size_t)chain * dim + tid];
+    if (a.init) th[tid] = a.init[(size_t)blockIdx.x * dim + tid];
     else th[tid] = v + 0.01 * normal_d(rng, 0u, SITE_HMC_INIT, 0, (uint32_t)tid);
     imass[tid] = 1.0;
   }
@@ -392,6 +403,8 @@ __global__ __launch_bounds__(NT) void hmc_kernel(HmcArgs a) {
       }
       if (wave == 0) wave_sync();
     } else {
+      // wave 0 has read every momentum into h0 before waves 1 and 2 update theirs (dim > 64)
+      __syncthreads();
       for (int l = 0; l < a.n_leap; ++l) {
         if (tid < dim) {
           const double ph = mom[tid] + 0.5 * eps * g[tid];
@@ -460,7 +473,7 @@ __global__ __launch_bounds__(NT) void hmc_kernel(HmcArgs a) {
       if (it == a.W - 1 && t_da > 0.0) eps = exp(log_eps_bar);
     } else {
       accepted += take ? 1.0 : 0.0;
-      double* o = a.draws + ((size_t)chain * a.S + (it - a.W)) * (3 + P);
+      double* o = a.draws + ((size_t)blockIdx.x * a.S + (it - a.W)) * (3 + P);
       if (tid < P) o[3 + tid] = hs ? theta[tid] * hs_scale(theta, tid) : theta[tid];
       if (tid >= 64 && tid < 64 + NSC) o[tid - 64] = exp(clamp30(theta[off_sc + tid - 64]));
       if (D == 1 && tid == 128) o[2] = 0.0;
@@ -468,8 +481,8 @@ __global__ __launch_bounds__(NT) void hmc_kernel(HmcArgs a) {
     __syncthreads();
   }
   if (tid == 0) {
-    a.accept_rate[chain] = accepted / (double)(a.S > 0 ? a.S : 1);
-    a.step_size[chain] = eps;
+    a.accept_rate[blockIdx.x] = accepted / (double)(a.S > 0 ? a.S : 1);
+    a.step_size[blockIdx.x] = eps;
   }
 }
 

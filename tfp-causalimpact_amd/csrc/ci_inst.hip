@@ -105,16 +105,19 @@ void CI_CAT(ci_launch_latents_d, CI_D, _l, CI_L)(int T, int P, int E, const floa
                                                 const double* theta, float a1, float p10,
                                                 float p11, uint32_t k0, uint32_t k1,
                                                 uint32_t rng_chain, uint32_t iter0, int per_chain,
-                                                int group, float* level, float* slope, float* loc,
+                                                int group, int chains_per_series,
+                                                int series_stream_base, const ci::HmcSeries* ser,
+                                                float* level, float* slope, float* loc,
                                                 float* traj, float* loc_sum, hipStream_t stream) {
-  // E rows; per_chain > 0: chains x ceil(per_chain / group) workgroups (see latents_kernel)
+  // E rows; per_chain > 0: chains x ceil(per_chain / group) workgroups (see latents_kernel), the
+  // chains of all series of a batched fit (chains_per_series > 0) one after the other
   const int grid = per_chain > 0 ? (E / per_chain) * ((per_chain + group - 1) / group) : E;
   hipLaunchKernelGGL((ci::latents_kernel<CI_D, CI_L>), dim3(grid), dim3(ci::NT), 0, stream, T, P, y,
                      mask, Xt, theta, a1, p10, p11, k0, k1, rng_chain, iter0, per_chain, group, E,
-                     level, slope, loc, traj, loc_sum);
+                     chains_per_series, series_stream_base, ser, level, slope, loc, traj, loc_sum);
 }
 
-// Runs the on-device HMC fit: one workgroup per chain.
+// Runs the on-device HMC fit: one workgroup per (series, chain).
 void CI_CAT(ci_launch_hmc_d, CI_D, _l, CI_L)(const ci::HmcArgs* args, hipStream_t stream) {
   ci::HmcArgs a = *args;
   const size_t with_x = ci::hmc_lds_bytes(a.P, ci::NT * CI_L);
@@ -123,11 +126,11 @@ void CI_CAT(ci_launch_hmc_d, CI_D, _l, CI_L)(const ci::HmcArgs* args, hipStream_
   if (a.P > ci::MAXP) {
     (void)hipFuncSetAttribute((const void*)(&ci::hmc_kernel<CI_D, CI_L, true>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ci::hmc_kernel<CI_D, CI_L, true>), dim3(a.C), dim3(ci::NT), lds, stream, a);
+    hipLaunchKernelGGL((ci::hmc_kernel<CI_D, CI_L, true>), dim3(a.B * a.C), dim3(ci::NT), lds, stream, a);
   } else {
     (void)hipFuncSetAttribute((const void*)(&ci::hmc_kernel<CI_D, CI_L, false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ci::hmc_kernel<CI_D, CI_L, false>), dim3(a.C), dim3(ci::NT), lds, stream, a);
+    hipLaunchKernelGGL((ci::hmc_kernel<CI_D, CI_L, false>), dim3(a.B * a.C), dim3(ci::NT), lds, stream, a);
   }
 }
 

@@ -3692,11 +3692,25 @@ __global__ __launch_bounds__(NT) void loglik_grad_kernel(int T, int P, const flo
                           out_grad + (size_t)blockIdx.x * (3 + P), tid, lane, wave);
 }
 
+// Per-series scalars of a batched HMC fit (hmc_kernel, latents_kernel): one entry per series in
+// device memory, read once at the start of a workgroup.  The series' arrays (y, mask, Xt, Omega) are
+// found from the series index and T, P alone: base + series * stride.
+struct HmcSeries {
+  double ig_a[3], ig_b[3];  // inverse-gamma (concentration, scale) of sigma^2: obs, level, slope
+  double init_log[3];       // log of the initial scales (causalimpact_lib.py:566-572)
+  double hs_scale0;         // horseshoe: weights_prior_scale
+  float a1, p10, p11, pad;  // initial level mean, level / slope variances
+};
+
 // ------------------------------------------------------------------------------------
 // Latent path + posterior-predictive trajectory for GIVEN parameter draws (one workgroup per
 // draw): what one_step_predictive needs after an HMC fit, where the latents are not part of
 // the chain state.  theta[e] = (sigma_obs, sigma_level, sigma_slope, weights[P]); RNG stream:
-// chain = rng_chain, iteration = e.
+// chain = rng_chain, iteration = e.  Batched HMC fits (chains_per_series > 0): the rows are
+// [series][chain][draw]; series s reads its data at y + s T, mask + s T, Xt + s P T, its
+// (a1, p10, p11) from ser[s], and draws from the Philox key
+// (stream_key0(k0, series_stream_base, s), stream_key1(k1, ...)) -- with series_stream_base < 0
+// that is (k0, k1) for every series.
 // ------------------------------------------------------------------------------------
 template <int D, int L>
 __global__ __launch_bounds__(NT) void latents_kernel(int T, int P, const float* __restrict__ y,
@@ -3706,6 +3720,8 @@ __global__ __launch_bounds__(NT) void latents_kernel(int T, int P, const float* 
                                                      float p10, float p11, uint32_t k0, uint32_t k1,
                                                      uint32_t rng_chain, uint32_t iter0,
                                                      int per_chain, int group, int num_rows,
+                                                     int chains_per_series, int series_stream_base,
+                                                     const HmcSeries* __restrict__ ser,
                                                      float* __restrict__ out_level,
                                                      float* __restrict__ out_slope,
                                                      float* __restrict__ out_loc,
@@ -3733,6 +3749,16 @@ __global__ __launch_bounds__(NT) void latents_kernel(int T, int P, const float* 
     if (row1 > chain_end) row1 = chain_end;
   }
   if (row1 > num_rows) row1 = num_rows;
+  int series = 0;
+  uint32_t chain_in_series = row_chain;
+  if (chains_per_series > 0) {
+    series = (int)(row_chain / (uint32_t)chains_per_series);
+    chain_in_series = row_chain - (uint32_t)(series * chains_per_series);
+    y += (size_t)series * T;
+    mask += (size_t)series * T;
+    Xt += (size_t)series * P * T;
+    if (ser) { a1 = ser[series].a1; p10 = ser[series].p10; p11 = ser[series].p11; }
+  }
   uint32_t maskbits = 0;
   float yv[L], acc[L];
 #pragma unroll
@@ -3743,7 +3769,8 @@ __global__ __launch_bounds__(NT) void latents_kernel(int T, int P, const float* 
     yv[l] = m ? 0.f : y[t];
     acc[l] = 0.f;
   }
-  Rng g{k0, k1, rng_chain + row_chain};
+  Rng g{stream_key0(k0, series_stream_base, series), stream_key1(k1, series_stream_base, series),
+        rng_chain + chain_in_series};
   for (int row = row0; row < row1; ++row) {
     const double* th = theta + (size_t)row * (3 + P);
     float resid[L], xw[L];
