@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CI_ABI_VERSION 3
+#define CI_ABI_VERSION 4
 #define CI_MAX_BLOCKS 8
 
 /* Per-series priors and initial Gibbs state.  One per series because every
@@ -203,6 +203,28 @@ int ci_fit_gibbs_f64_kernel_ms(float* kernel_ms);
 int ci_session_create(const ci_problem* problem, const float* y, const uint8_t* mask,
                       const float* X, const uint8_t* season_change,
                       const ci_series_params* params, ci_session** session);
+/* A RAGGED session: B trend models (num_blocks = 0, P <= 52, float32) whose series have their own
+ * lengths, fitted in one launch.  problem->T is the ROW STRIDE of every array over time -- y and
+ * mask [B,T], X [B,T,P], every [.., T] member of ci_outputs, observed / flags of
+ * ci_session_summarize -- and must equal the longest series; series b has series_lengths[b] steps,
+ * 3 <= series_lengths[b] <= T, and all series must run the same number of steps per thread
+ * (the smallest L in {1, 2, 4, 8, 16} with 256 L >= length; hence T <= 4096).  Rows [length, T) of
+ * the inputs are padding and are never read; elements [length, T) of level, slope, posterior_means
+ * and posterior_trajectories read 0 after a run (the session clears those arrays when it is
+ * created; the kernel never writes them).  Series b then gets, bit for bit, the draws of a
+ * single-series session of its own length with the same seed and streams.
+ * series_ids (int32 [B], or NULL): the series id whose random streams series b draws from, in
+ * place of problem->series_offset + b -- the series of one launch need not be neighbours in their
+ * panel; ignored under CI_FLAG_SHARED_SERIES_STREAMS.
+ * Every argument is checked before any device call; the message names the offending series.
+ * ci_session_run, _fetch, _summarize (observed = NaN and flags = 0 in the padding; order
+ * statistics reported for padding steps carry no meaning), _algorithmic_bytes (counts real
+ * steps), _kernel_name ("ci::gibbs_kernel<D,L,PM,false,ragged>") and _destroy take such a session;
+ * ci_session_run_streamed and ci_session_profile refuse it.  It always runs the four-wavefront
+ * kernel (as under CI_FLAG_FOUR_WAVES: same bits as the eight-wavefront one). */
+int ci_session_create_ragged(const ci_problem* problem, const int32_t* series_lengths,
+                             const int32_t* series_ids, const float* y, const uint8_t* mask,
+                             const float* X, const ci_series_params* params, ci_session** session);
 /* Runs the fit on the session's stream and waits for it.  kernel_ms (optional)
  * receives the Gibbs kernel's duration measured with HIP events on that stream. */
 int ci_session_run(ci_session* session, float* kernel_ms);

@@ -17,6 +17,8 @@ from causalimpact.summary import summary
 from causalimpact.summary import summary_numbers
 from causalimpact.batch import CausalImpactBatchAnalysis
 from causalimpact.batch import fit_causalimpact_batch
+from causalimpact.batch import CausalImpactPanelAnalysis
+from causalimpact.batch import fit_causalimpact_panel
 
 
 from causalimpact.plot import plot

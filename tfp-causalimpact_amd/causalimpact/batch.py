@@ -93,6 +93,83 @@ def prepare_batch(values: np.ndarray, index: pd.Index, pre_period, post_period,
                        mask=mask, design=design, outcome_mean=o_mu, outcome_sd=o_sd)
 
 
+def summary_table(names, alpha, ranks, dsum, *, n_win, n_obs, obs_mean, obs_sum, avg_pred,
+                  cum_pred) -> pd.DataFrame:
+  """The (series, average|cumulative) x 15 summary table from the statistics of every series'
+  own post-period window: n_win (steps in the window; an int when all series share it, else [B]),
+  n_obs [B] (observed steps in it), obs_mean / obs_sum [B] (observed outcome over it), avg_pred /
+  cum_pred [B] (posterior mean over it), and the device summary `dsum` ("per_draw" [B, 2, N]
+  window totals of prediction and point effect per draw; optionally "per_draw_order" [B, 2, R],
+  their order statistics `ranks`).  The same numpy reductions as `_summary_rows`, along axis 1."""
+  B = len(names)
+  quantiles = (alpha / 2.0, 1.0 - alpha / 2.0)
+  n_obs = np.asarray(n_obs)
+  n_win_d = n_win if np.ndim(n_win) == 0 else np.asarray(n_win)[:, None]    # against [B, N]
+  pred_sum, point_sum = dsum["per_draw"][:, 0], dsum["per_draw"][:, 1]   # [B, N]
+  with np.errstate(invalid="ignore", divide="ignore"):
+    pred_mean = pred_sum / n_win_d
+    point_mean = np.where(n_obs[:, None] > 0, point_sum / np.maximum(n_obs, 1)[:, None], np.nan)
+    rel = obs_sum[:, None] / pred_sum - 1.0
+
+    # The bands interpolate order statistics of the per-draw totals; the device returned
+    # those (per_draw_order), and every banded quantity is a monotone map of the totals, so
+    # its order statistics are the mapped ones -- no [B, draws] sort on the host.
+    ranks = list(ranks)
+    N = pred_sum.shape[1]
+    order = dsum.get("per_draw_order")
+    if order is None:
+      order = np.sort(dsum["per_draw"], axis=2)[:, :, ranks]
+    (lo_a, hi_a, g_a), (lo_b, hi_b, g_b) = lib._quantile_ranks(N, quantiles)   # pylint: disable=protected-access
+    lerp = lib._lerp_order_stats                                               # pylint: disable=protected-access
+
+    def band_of(by_rank):
+      return np.stack([lerp(by_rank, lo_a, hi_a, g_a), lerp(by_rank, lo_b, hi_b, g_b)])
+
+    pred_o = {r: order[:, 0, i] for i, r in enumerate(ranks)}
+    point_o = {r: order[:, 1, i] for i, r in enumerate(ranks)}
+    need = (lo_a, hi_a, lo_b, hi_b)
+    band_pred_sum, band_point_sum = band_of(pred_o), band_of(point_o)
+    band_pred_mean = band_of({k: pred_o[k] / n_win for k in need})
+    band_point_mean = band_of({k: np.where(n_obs > 0, point_o[k] / np.maximum(n_obs, 1), np.nan)
+                               for k in need})
+    # rel = obs_sum / pred_sum - 1 is monotone in pred_sum on either side of zero: decreasing
+    # when obs_sum > 0 (its k-th smallest comes from the (N-1-k)-th smallest total), else
+    # increasing.  Series whose totals straddle zero take the sort.
+    down = obs_sum > 0
+    band_rel = band_of({k: np.where(down, obs_sum / pred_o[N - 1 - k], obs_sum / pred_o[k]) - 1.0
+                        for k in need})
+    straddle = ~((pred_sum.min(axis=1) > 0) | (pred_sum.max(axis=1) < 0))
+    if straddle.any():
+      band_rel[:, straddle] = np.quantile(rel[straddle], quantiles, axis=1)
+
+    def sd(x):
+      return np.std(x, axis=1, ddof=1)
+
+    cols = {
+        "actual": (obs_mean, obs_sum),
+        "predicted": (avg_pred, cum_pred),
+        "predicted_lower": (band_pred_mean[0], band_pred_sum[0]),
+        "predicted_upper": (band_pred_mean[1], band_pred_sum[1]),
+        "predicted_sd": (sd(pred_mean), sd(pred_sum)),
+        "abs_effect": (obs_mean - avg_pred, obs_sum - cum_pred),
+        "abs_effect_lower": (band_point_mean[0], band_point_sum[0]),
+        "abs_effect_upper": (band_point_mean[1], band_point_sum[1]),
+        "abs_effect_sd": (sd(point_mean), sd(point_sum)),
+        "rel_effect": (rel.mean(axis=1),) * 2,
+        "rel_effect_lower": (band_rel[0],) * 2,
+        "rel_effect_upper": (band_rel[1],) * 2,
+        "rel_effect_sd": (sd(rel),) * 2,
+    }
+  pool_le = ((obs_sum[:, None] <= pred_sum).sum(axis=1) + 1) / (pred_sum.shape[1] + 1)
+  pool_ge = ((obs_sum[:, None] >= pred_sum).sum(axis=1) + 1) / (pred_sum.shape[1] + 1)
+  p_value = np.minimum(pool_le, pool_ge)
+  data = {k: np.stack(v, axis=1).reshape(-1) for k, v in cols.items()}      # (b, avg|cum) order
+  data["p_value"] = np.repeat(p_value, 2)
+  data["alpha"] = np.full(2 * B, alpha)
+  index = pd.MultiIndex.from_product([list(names), ["average", "cumulative"]], names=["series", None])
+  return pd.DataFrame(data, index=index)
+
+
 class CausalImpactBatchAnalysis:
   """Results for B series.  `summary`: DataFrame indexed by (series, average|cumulative) with the
   reference's 15 summary columns; `analysis[b]` / iteration: per-series CausalImpactAnalysis
@@ -152,7 +229,6 @@ class CausalImpactBatchAnalysis:
     """The reference's 15 summary columns (causalimpact_lib.py:934-1093) for every series at
     once: the same numpy reductions as `_summary_rows`, along axis 1 of [B, draws] arrays."""
     p, B = self._prep, len(self)
-    quantiles = (self.alpha / 2.0, 1.0 - self.alpha / 2.0)
     rq = self._request(0)
     win = (rq["flags"] & 2) != 0
     n_win = int(win.sum())
@@ -164,72 +240,12 @@ class CausalImpactBatchAnalysis:
     scale = p.outcome_sd if p.standardize_data else np.ones(B)
     shift = p.outcome_mean if p.standardize_data else np.zeros(B)
     post_mean = (self._means.astype(np.float64) * scale[:, None] + shift[:, None])[:, win]
-    pred_sum, point_sum = self._dsum["per_draw"][:, 0], self._dsum["per_draw"][:, 1]   # [B, N]
     n_obs = np.sum(~np.isnan(obs_w), axis=1)
     with np.errstate(invalid="ignore", divide="ignore"):
       obs_mean, obs_sum = np.nanmean(obs_w, axis=1), np.nansum(obs_w, axis=1)
-      pred_mean = pred_sum / n_win
-      point_mean = np.where(n_obs[:, None] > 0, point_sum / np.maximum(n_obs, 1)[:, None], np.nan)
-      rel = obs_sum[:, None] / pred_sum - 1.0
-
-      # The bands interpolate order statistics of the per-draw totals; the device returned
-      # those (per_draw_order), and every banded quantity is a monotone map of the totals, so
-      # its order statistics are the mapped ones -- no [B, draws] sort on the host.
-      ranks = list(self._ranks)
-      N = pred_sum.shape[1]
-      order = self._dsum.get("per_draw_order")
-      if order is None:
-        order = np.sort(self._dsum["per_draw"], axis=2)[:, :, ranks]
-      (lo_a, hi_a, g_a), (lo_b, hi_b, g_b) = lib._quantile_ranks(N, quantiles)   # pylint: disable=protected-access
-      lerp = lib._lerp_order_stats                                               # pylint: disable=protected-access
-
-      def band_of(by_rank):
-        return np.stack([lerp(by_rank, lo_a, hi_a, g_a), lerp(by_rank, lo_b, hi_b, g_b)])
-
-      pred_o = {r: order[:, 0, i] for i, r in enumerate(ranks)}
-      point_o = {r: order[:, 1, i] for i, r in enumerate(ranks)}
-      need = (lo_a, hi_a, lo_b, hi_b)
-      band_pred_sum, band_point_sum = band_of(pred_o), band_of(point_o)
-      band_pred_mean = band_of({k: pred_o[k] / n_win for k in need})
-      band_point_mean = band_of({k: np.where(n_obs > 0, point_o[k] / np.maximum(n_obs, 1), np.nan)
-                                 for k in need})
-      # rel = obs_sum / pred_sum - 1 is monotone in pred_sum on either side of zero: decreasing
-      # when obs_sum > 0 (its k-th smallest comes from the (N-1-k)-th smallest total), else
-      # increasing.  Series whose totals straddle zero take the sort.
-      down = obs_sum > 0
-      band_rel = band_of({k: np.where(down, obs_sum / pred_o[N - 1 - k], obs_sum / pred_o[k]) - 1.0
-                          for k in need})
-      straddle = ~((pred_sum.min(axis=1) > 0) | (pred_sum.max(axis=1) < 0))
-      if straddle.any():
-        band_rel[:, straddle] = np.quantile(rel[straddle], quantiles, axis=1)
-
-      def sd(x):
-        return np.std(x, axis=1, ddof=1)
-
-      avg_pred, cum_pred = post_mean.mean(axis=1), post_mean.sum(axis=1)
-      cols = {
-          "actual": (obs_mean, obs_sum),
-          "predicted": (avg_pred, cum_pred),
-          "predicted_lower": (band_pred_mean[0], band_pred_sum[0]),
-          "predicted_upper": (band_pred_mean[1], band_pred_sum[1]),
-          "predicted_sd": (sd(pred_mean), sd(pred_sum)),
-          "abs_effect": (obs_mean - avg_pred, obs_sum - cum_pred),
-          "abs_effect_lower": (band_point_mean[0], band_point_sum[0]),
-          "abs_effect_upper": (band_point_mean[1], band_point_sum[1]),
-          "abs_effect_sd": (sd(point_mean), sd(point_sum)),
-          "rel_effect": (rel.mean(axis=1),) * 2,
-          "rel_effect_lower": (band_rel[0],) * 2,
-          "rel_effect_upper": (band_rel[1],) * 2,
-          "rel_effect_sd": (sd(rel),) * 2,
-      }
-    pool_le = ((obs_sum[:, None] <= pred_sum).sum(axis=1) + 1) / (pred_sum.shape[1] + 1)
-    pool_ge = ((obs_sum[:, None] >= pred_sum).sum(axis=1) + 1) / (pred_sum.shape[1] + 1)
-    p_value = np.minimum(pool_le, pool_ge)
-    data = {k: np.stack(v, axis=1).reshape(-1) for k, v in cols.items()}      # (b, avg|cum) order
-    data["p_value"] = np.repeat(p_value, 2)
-    data["alpha"] = np.full(2 * B, self.alpha)
-    index = pd.MultiIndex.from_product([self._names, ["average", "cumulative"]], names=["series", None])
-    return pd.DataFrame(data, index=index)
+    return summary_table(self._names, self.alpha, self._ranks, self._dsum, n_win=n_win, n_obs=n_obs,
+                         obs_mean=obs_mean, obs_sum=obs_sum, avg_pred=post_mean.mean(axis=1),
+                         cum_pred=post_mean.sum(axis=1))
 
   def __getitem__(self, b: int) -> lib.CausalImpactAnalysis:
     b = range(len(self))[b]
@@ -305,7 +321,8 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
 
   data: a sequence of DataFrames with identical index and column layout (outcome first, or
   `DataOptions.outcome_column`), or an array [B, T, 1 + covariates] (outcome first) with
-  `index` (default: 0..T-1).  Other arguments as `fit_causalimpact`.  Latent-state draws are not
+  `index` (default: 0..T-1).  Other arguments as `fit_causalimpact`.  Series that do NOT share
+  the index and the periods (own lengths, own intervention dates) go to `fit_causalimpact_panel`.  Latent-state draws are not
   downloaded (B x chains x draws x T values); the per-series frames and the summary table are.
 
   Random streams: series b draws from streams keyed by (its position b in the batch, chain), so
@@ -482,3 +499,417 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     keys = ("observation_noise_scale", "level_scale")
     diag_draws = {k: np.concatenate([r[0][k] for r in results], axis=0) for k in keys}   # [B, C, S]
   return CausalImpactBatchAnalysis(prep, names, alpha, means, dsum, ranks, columns, diag_draws)
+
+
+# ------------------------------------------------------------------------------------------
+# Panels: B series with the same columns, each with its own index, length and periods
+# ------------------------------------------------------------------------------------------
+# The ragged one-launch path (csrc/ci_kernels.h, the RAGGED build of the four-wavefront trend
+# kernel; ci_session_create_ragged) covers standardised float32 Gibbs trend models of at most this
+# many steps and design columns; all series of a launch run the same number of steps per thread.
+PANEL_RAGGED_MAX_T = 4096
+PANEL_RAGGED_MAX_P = 52
+
+
+def steps_class(T: int) -> int:
+  """Steps per thread of the register-resident trend kernels for a series of T steps: the
+  smallest L in (1, 2, 4, 8, 16) with 256 L >= T; 0 beyond 4096 steps."""
+  for L in (1, 2, 4, 8, 16):
+    if 256 * L >= T:
+      return L
+  return 0
+
+
+def panel_route(*, float64: bool, standardize_data: bool, sampler: str, num_seasonal_blocks: int,
+                P: int, lengths: Sequence[int]) -> Dict[str, Any]:
+  """Where `fit_causalimpact_panel` fits a panel whose series b has lengths[b] model steps.
+
+  {"route": ..., "groups": [(key, [series positions]), ...]}, groups in ascending key order, the
+  positions of a group ascending:
+    "ragged"        trend model, P <= 52, every length <= 4096, float32, standardised, Gibbs: series
+                    grouped by steps-per-thread class (key = L), one ragged launch per class (and
+                    device);
+    "equal_length"  any other float32 standardised Gibbs model (seasonal blocks, P > 52, a series
+                    longer than 4096): series grouped by equal length (key = T), one ordinary
+                    session per distinct length -- the existing kernels, per-series mask / flags;
+    "per_series"    float64, standardize_data=False, sampler="hmc": `fit_causalimpact` on every
+                    series in turn (one group per series, key = its position).
+  A series' random streams are keyed by its POSITION IN THE PANEL on every route (the positions
+  listed here are what the launches pass on), never by its place in a group."""
+  lengths = [int(t) for t in lengths]
+  if float64 or not standardize_data or sampler != "gibbs":
+    return dict(route="per_series", groups=[(b, [b]) for b in range(len(lengths))])
+  ragged = (num_seasonal_blocks == 0 and P <= PANEL_RAGGED_MAX_P and
+            all(t <= PANEL_RAGGED_MAX_T for t in lengths))
+  key_of = steps_class if ragged else (lambda t: t)
+  groups: Dict[int, List[int]] = {}
+  for b, t in enumerate(lengths):
+    groups.setdefault(key_of(t), []).append(b)
+  return dict(route="ragged" if ragged else "equal_length", groups=sorted(groups.items()))
+
+
+def panel_launches(route: Dict[str, Any], devices: Sequence[int], shared_streams: bool = False):
+  """[(device, key, [series positions])]: the launches of a routed panel.  Every group is sharded
+  over the devices as a batch is.  The ragged entry point takes the positions as `series_ids`, so
+  a shard is one launch whatever its positions are; an ordinary session keys series b of the launch
+  by series_offset + b, so on the "equal_length" route a shard is cut into runs of consecutive
+  positions (one launch each) -- unless the streams are shared, when no position enters a key."""
+  devs = list(devices) if devices else [0]
+  out = []
+  for key, ids in route["groups"]:
+    for dev, part in zip(devs, np.array_split(np.asarray(ids, dtype=np.int64), len(devs))):
+      part = [int(b) for b in part]
+      if not part:
+        continue
+      if route["route"] == "equal_length" and not shared_streams:
+        run = [part[0]]
+        for b in part[1:]:
+          if b != run[-1] + 1:
+            out.append((dev, key, run))
+            run = []
+          run.append(b)
+        out.append((dev, key, run))
+      else:
+        out.append((dev, key, part))
+  return out
+
+
+@dataclasses.dataclass
+class PreparedPanel:
+  """What the sampler consumes for a panel: `PreparedBatch` with a length per series.  Arrays over
+  time are padded to the longest series: y NaN, mask True, design 0, observed NaN, flags 0."""
+  raw: List[np.ndarray]         # per series [T_all_b, 1+p] raw data
+  indices: List[pd.Index]       # per series [T_all_b]
+  periods: List[Tuple[Tuple[Any, Any], Tuple[Any, Any]]]   # parsed (pre_period, post_period)
+  standardize_data: bool
+  model_rows: List[np.ndarray]  # per series: positions (into its index) of its model steps
+  lengths: np.ndarray           # [B] model steps T_b
+  num_pre: np.ndarray           # [B] steps of the own pre-period
+  y: np.ndarray                 # [B, T_max]
+  mask: np.ndarray              # [B, T_max] bool
+  design: Optional[np.ndarray]  # [B, T_max, P] or None
+  outcome_mean: np.ndarray      # [B]
+  outcome_sd: np.ndarray        # [B]
+  observed: np.ndarray          # [B, T_max] data-scale outcome, NaN in gap / tail / padding
+  flags: np.ndarray             # [B, T_max] uint8: bit 0 = t >= treatment start, bit 1 = in the window
+
+
+def prepare_panel(frames_or_values, periods, standardize_data: bool = True,
+                  indices_: Optional[Sequence[pd.Index]] = None, names=None) -> PreparedPanel:
+  """Vectorised `CausalImpactData.__init__` for a panel: a sequence of DataFrames (outcome first)
+  or of [T_b, 1 + p] arrays (with `indices_`, default 0..T_b-1), and one (pre_period, post_period)
+  per series.  Per series: the rows before its own pre-period are dropped, gap and tail kept, the
+  columns standardised by its own pre-period, y NaN from the end of that pre-period on.  The index
+  of every series is compared with its own periods (that cannot be shared); the numeric work runs
+  on the padded [B, T_max, 1 + p] block -- series with the same pre-period length are standardised
+  together, with the very operations of `prepare_batch`.  The reference's refusals are raised
+  with the series named."""
+  items = list(frames_or_values)
+  B = len(items)
+  if B == 0:
+    raise ValueError("`data` is empty")
+  periods = list(periods)
+  if len(periods) != B:
+    raise ValueError(f"`periods` must hold one (pre_period, post_period) per series: {B} series, "
+                     f"{len(periods)} periods")
+  names = list(range(B)) if names is None else list(names)
+  raw, idxs = [], []
+  for b, item in enumerate(items):
+    if isinstance(item, (pd.DataFrame, pd.Series)):
+      frame = pd.DataFrame(item)
+      raw.append(frame.to_numpy(dtype=np.float64))
+      idxs.append(frame.index)
+    else:
+      v = np.asarray(item, dtype=np.float64)
+      if v.ndim != 2:
+        raise ValueError(f"series {names[b]!r}: values must be [num_timesteps, 1 + num_covariates]")
+      raw.append(v)
+      idxs.append(pd.RangeIndex(v.shape[0]) if indices_ is None else pd.Index(indices_[b]))
+    if len(idxs[b]) != raw[b].shape[0]:
+      raise ValueError(f"series {names[b]!r}: the index must have one entry per timestep")
+  ncol = raw[0].shape[1]
+  for b in range(B):
+    if raw[b].shape[1] != ncol:
+      raise ValueError(f"series {names[b]!r} has {raw[b].shape[1]} columns, series {names[0]!r} has "
+                       f"{ncol}: all series of a panel must share the columns")
+  # ---- per series: its periods against its index (positions only; no numeric work)
+  parsed, rows_of, in_post_of, after_start_of = [], [], [], []
+  n_pre = np.zeros(B, np.int64)
+  for b in range(B):
+    idx = idxs[b]
+    try:
+      pre, post = indices.parse_and_validate_date_data(
+          data=pd.DataFrame({"y": np.zeros(len(idx))}, index=idx), pre_period=periods[b][0],
+          post_period=periods[b][1])
+    except ValueError as e:
+      raise ValueError(f"series {names[b]!r}: {e}") from e
+    parsed.append((pre, post))
+    in_pre = np.asarray((idx >= pre[0]) & (idx <= pre[1]))
+    rows = np.concatenate([np.flatnonzero(in_pre), np.flatnonzero(np.asarray(idx > pre[1]))])
+    n_pre[b] = int(in_pre.sum())
+    rows_of.append(rows)
+    midx = idx[rows]
+    in_post_of.append(np.asarray((midx >= post[0]) & (midx <= post[1])))
+    after_start_of.append(~np.asarray(midx < post[0]))
+  lengths = np.array([len(r) for r in rows_of], np.int64)
+  T_max, T_all = int(lengths.max()), max(v.shape[0] for v in raw)
+  # ---- the padded blocks
+  values = np.full((B, T_all, ncol), np.nan)
+  real = np.zeros((B, T_all), bool)
+  rows_pad = np.zeros((B, T_max), np.int64)
+  valid = np.arange(T_max)[None, :] < lengths[:, None]                   # [B, T_max]
+  in_post = np.zeros((B, T_max), bool)
+  after_start = np.zeros((B, T_max), bool)
+  for b in range(B):
+    values[b, :raw[b].shape[0]] = raw[b]
+    real[b, :raw[b].shape[0]] = True
+    rows_pad[b, :lengths[b]] = rows_of[b]
+    in_post[b, :lengths[b]] = in_post_of[b]
+    after_start[b, :lengths[b]] = after_start_of[b]
+  # ---- the reference's refusals (data.py:33-62), over every row of the frame as there
+  outcome = values[:, :, 0]
+  with np.errstate(invalid="ignore"):
+    seen = np.sum(~np.isnan(outcome), axis=1)
+    const = (seen > 0) & (np.nanstd(np.where(seen[:, None] > 0, outcome, 0.0), axis=1) == 0)
+  if const.any():
+    raise ValueError(f"series {names[int(np.flatnonzero(const)[0])]!r}: Input response cannot be constant.")
+  if (seen < 3).any():
+    raise ValueError(f"series {names[int(np.flatnonzero(seen < 3)[0])]!r}: Input data must have at "
+                     "least 3 observations.")
+  if ncol > 1:
+    bad = (np.isnan(values[:, :, 1:]).any(axis=2) & real).any(axis=1)
+    if bad.any():
+      raise ValueError(f"series {names[int(np.flatnonzero(bad)[0])]!r}: Input data cannot have any "
+                       "missing values.")
+  model = values[np.arange(B)[:, None], rows_pad]                          # [B, T_max, 1+p]
+  model[~valid] = np.nan
+  if standardize_data:
+    scaled = np.empty_like(model)
+    o_mu, o_sd = np.zeros(B), np.ones(B)
+    for n in np.unique(n_pre):                 # (one pass for a panel with one pre-period length)
+      sel = np.flatnonzero(n_pre == n)
+      sc, mu, sd = standardize.standardize_batch(model[sel], int(n))
+      scaled[sel], o_mu[sel], o_sd[sel] = sc, mu[:, 0], sd[:, 0]
+  else:
+    scaled = model
+    o_mu, o_sd = np.zeros(B), np.ones(B)
+  y = scaled[:, :, 0].copy()
+  y[np.arange(T_max)[None, :] >= n_pre[:, None]] = np.nan
+  design = None
+  if ncol > 1:
+    design = np.concatenate([scaled[:, :, 1:], np.ones((B, T_max, 1))], axis=2)
+    design[~valid] = 0.0
+  observed = model[:, :, 0].copy()
+  observed[(np.arange(T_max)[None, :] >= n_pre[:, None]) & ~in_post] = np.nan   # gap / tail: predictions only
+  flags = (after_start.astype(np.uint8) | (in_post.astype(np.uint8) << 1)) * valid.astype(np.uint8)
+  return PreparedPanel(raw=raw, indices=idxs, periods=parsed, standardize_data=standardize_data,
+                       model_rows=rows_of, lengths=lengths, num_pre=n_pre, y=y, mask=np.isnan(y),
+                       design=design, outcome_mean=o_mu, outcome_sd=o_sd, observed=observed,
+                       flags=flags)
+
+
+def panel_window_stats(observed: np.ndarray, flags: np.ndarray, post_mean: np.ndarray,
+                       lengths: Sequence[int]) -> Dict[str, np.ndarray]:
+  """The window statistics `summary_table` needs when every series has its own post-period window:
+  observed, flags, post_mean [B, T_max] (data scale; bit 1 of flags marks the window), lengths [B].
+  Per series the reductions of `_summary_rows` over ITS window: n_win, n_obs, obs_mean, obs_sum,
+  avg_pred, cum_pred, each [B].  Series that share length and window are reduced together with the
+  expressions of `CausalImpactBatchAnalysis._build_summary`: a panel with one shared period gets
+  that table, bit for bit."""
+  B = len(lengths)
+  out = {k: np.zeros(B) for k in ("obs_mean", "obs_sum", "avg_pred", "cum_pred")}
+  out["n_win"], out["n_obs"] = np.zeros(B, np.int64), np.zeros(B, np.int64)
+  groups: Dict[Any, List[int]] = {}
+  for b in range(B):
+    groups.setdefault((int(lengths[b]), (flags[b, :lengths[b]] & 2).tobytes()), []).append(b)
+  with np.errstate(invalid="ignore", divide="ignore"):
+    for (Tg, _), sel in groups.items():
+      win = (flags[sel[0], :Tg] & 2) != 0
+      obs_w = np.ascontiguousarray(observed[sel][:, :Tg])[:, win]            # [Bg, T_w]
+      pm_w = np.ascontiguousarray(post_mean[sel][:, :Tg])[:, win]
+      out["n_win"][sel], out["n_obs"][sel] = int(win.sum()), np.sum(~np.isnan(obs_w), axis=1)
+      out["obs_mean"][sel], out["obs_sum"][sel] = np.nanmean(obs_w, axis=1), np.nansum(obs_w, axis=1)
+      out["avg_pred"][sel], out["cum_pred"][sel] = pm_w.mean(axis=1), pm_w.sum(axis=1)
+  return out
+
+
+class CausalImpactPanelAnalysis(CausalImpactBatchAnalysis):
+  """`CausalImpactBatchAnalysis` for a panel: every series has its own index, length and periods,
+  hence its own post-period window in the summary table.  `posterior_means` [B, T_max] and the
+  device summary's arrays over time are padded to the longest series; series b owns [0, T_b)."""
+
+  def _request(self, b: int) -> Dict:
+    p, Tb = self._prep, int(self._prep.lengths[b])
+    return dict(scale=float(p.outcome_sd[b]), shift=float(p.outcome_mean[b]),
+                observed=p.observed[b, :Tb], flags=p.flags[b, :Tb], ranks=self._ranks,
+                quantiles=(self.alpha / 2.0, 1.0 - self.alpha / 2.0))
+
+  def _build_summary(self) -> pd.DataFrame:
+    p = self._prep
+    post_mean = (self._means.astype(np.float64) * p.outcome_sd[:, None] + p.outcome_mean[:, None])
+    stats = panel_window_stats(p.observed, p.flags, post_mean, p.lengths)
+    return summary_table(self._names, self.alpha, self._ranks, self._dsum, **stats)
+
+  def __getitem__(self, b: int) -> lib.CausalImpactAnalysis:
+    b = range(len(self))[b]
+    if b not in self._cache:
+      p = self._prep
+      Tb = int(p.lengths[b])
+      (pre, post) = p.periods[b]
+      df = pd.DataFrame(p.raw[b], index=p.indices[b], columns=self._columns)
+      ci_data = cid.CausalImpactData(df, pre, post, standardize_data=p.standardize_data)
+      dsum = {k: (v[b][..., :Tb] if k in ("value_order", "cum_order") else v[b])
+              for k, v in self._dsum.items()}
+      rq = lib._device_summary_request(ci_data, self.alpha)   # pylint: disable=protected-access
+      rq["ranks"] = self._ranks
+      series, summary = lib._compute_impact_device(            # pylint: disable=protected-access
+          self._means[b, :Tb], dsum, rq, ci_data, self.alpha)
+      self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b))
+    return self._cache[b]
+
+
+def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float = 0.05, seed=None,
+                           data_options: Optional[lib.DataOptions] = None,
+                           model_options: Optional[lib.ModelOptions] = None,
+                           inference_options: Optional[lib.InferenceOptions] = None,
+                           names: Optional[Sequence[Any]] = None,
+                           shared_streams: bool = False) -> CausalImpactBatchAnalysis:
+  """`fit_causalimpact` for a PANEL: B series with the same columns (outcome first, or
+  `DataOptions.outcome_column`; the same covariates), each with its own index, its own length and
+  its own (pre_period, post_period) -- staggered roll-outs, units that enter the data on different
+  days, placebo studies that cut one history at many dates.
+
+  data: a sequence of DataFrames; periods: one (pre_period, post_period) per series.  The result
+  has the interface of `fit_causalimpact_batch`'s: `summary` indexed by (series,
+  average|cumulative), `res[b]` the `CausalImpactAnalysis` of series b on its own index,
+  `diagnostics_of`, `len`, iteration.
+
+  Routes (`panel_route`): standardised float32 Gibbs trend models with at most 52 design columns
+  and 4096 steps are grouped by steps-per-thread class (<= 256, 512, 1024, 2048, 4096 steps) and
+  each class runs in ONE launch per device of the ragged build of the four-wavefront kernel, every
+  series on its own length.  Other float32 standardised Gibbs models (seasonal blocks, more
+  columns, longer series) are grouped by equal length, one ordinary session per length.  float64,
+  `standardize_data=False` and `sampler="hmc"` panels are fitted series by series.
+
+  Random streams as in `fit_causalimpact_batch`: series b draws from the streams of series id b,
+  its position in the PANEL, whatever group or device it lands in; `shared_streams=True` keys by
+  chain only, and series b then equals `fit_causalimpact` on its frame with its periods and this
+  seed (bit for bit in every array the session returns over its own steps); without it series 0
+  does, and series b equals the single fit seeded with `_native.series_stream_key(seed, b)`."""
+  data_options = data_options or lib.DataOptions()
+  model_options = model_options or lib.ModelOptions()
+  inference_options = inference_options or lib.InferenceOptions()
+  if not 0 < alpha < 1:
+    raise ValueError("`alpha` must be between 0 and 1.")
+  if inference_options.sampler not in ("gibbs", "hmc"):
+    raise ValueError(f"sampler must be 'gibbs' or 'hmc', got {inference_options.sampler!r}")
+  frames = [pd.DataFrame(d) for d in data]
+  if not frames:
+    raise ValueError("`data` is empty")
+  B = len(frames)
+  periods = list(periods)
+  if len(periods) != B:
+    raise ValueError(f"`periods` must hold one (pre_period, post_period) per series: {B} series, "
+                     f"{len(periods)} periods")
+  names = list(range(B)) if names is None else list(names)
+  first = frames[0]
+  oc = data_options.outcome_column if data_options.outcome_column is not None else first.columns[0]
+  columns = [oc] + [c for c in first.columns if c != oc]
+  for b, f in enumerate(frames):
+    if list(f.columns) != list(first.columns):
+      raise ValueError(f"series {names[b]!r}: all series of a panel must share the columns")
+  float64 = cid._as_numpy_dtype(data_options.dtype) == np.float64  # pylint: disable=protected-access
+  seed_pair = lib._sanitize_seed(seed)   # pylint: disable=protected-access
+  num_blocks = len(model_options.seasons)
+  # (which panels go series by series does not depend on the lengths: the frames' bound them here)
+  if panel_route(float64=float64, standardize_data=data_options.standardize_data,
+                 sampler=inference_options.sampler, num_seasonal_blocks=num_blocks,
+                 P=len(columns), lengths=[len(f) for f in frames])["route"] == "per_series":
+    opts = dataclasses.replace(data_options, outcome_column=oc)
+    analyses = []
+    for b, f in enumerate(frames):
+      seed_b = seed_pair if shared_streams else _native.series_stream_key(seed_pair, b)
+      one = lib.fit_causalimpact(f, periods[b][0], periods[b][1], alpha=alpha, seed=seed_b,
+                                 data_options=opts, model_options=model_options,
+                                 inference_options=inference_options)
+      analyses.append(dataclasses.replace(one, posterior_samples=None))   # (draws are not kept)
+    return PerSeriesBatchAnalysis(names, alpha, analyses)
+
+  prep = prepare_panel([f[columns] for f in frames], periods, data_options.standardize_data,
+                       names=names)
+  T_max = prep.y.shape[1]
+  P = 0 if prep.design is None else prep.design.shape[2]
+  route = panel_route(float64=float64, standardize_data=True, sampler="gibbs",
+                      num_seasonal_blocks=num_blocks, P=P, lengths=prep.lengths)
+  # the sampler sees the outcome in DataOptions.dtype (data.py:121-128), priors included
+  y_model = prep.y.astype(cid._as_numpy_dtype(data_options.dtype)).astype(np.float64)  # pylint: disable=protected-access
+  params = []
+  with np.errstate(invalid="ignore"):
+    for b in range(B):
+      Tb, nb = int(prep.lengths[b]), int(prep.num_pre[b])
+      params.append(_model.series_params(
+          y_model[b, :Tb], prep.mask[b, :Tb], None if prep.design is None else prep.design[b, :Tb],
+          prior_level_sd=model_options.prior_level_sd, num_seasonal_blocks=num_blocks,
+          has_slope=model_options.local_linear_trend,
+          outcome_sd=float(np.nanstd(y_model[b, :nb], ddof=1))))
+  C, S = inference_options.num_chains, inference_options.num_results
+  ranks = lib._summary_ranks(C * S, (alpha / 2.0, 1.0 - alpha / 2.0))   # pylint: disable=protected-access
+  kflags = (int(getattr(inference_options, "kernel_flags", 0)) |
+            (_native.FLAG_SHARED_SERIES_STREAMS if shared_streams else 0))
+  want = ["posterior_means", "observation_noise_scale", "level_scale"]
+
+  def run(dev, key, ids):
+    """One launch: the series `ids` (panel positions) on device `dev`; arrays back at stride T_max."""
+    ids = np.asarray(ids, dtype=np.int64)
+    T = int(prep.lengths[ids].max())                 # the stride of this launch
+    design = None if prep.design is None else prep.design[ids, :T]
+    common = dict(T=T, P=P, has_slope=model_options.local_linear_trend,
+                  num_warmup=inference_options.num_warmup_steps, num_results=S, num_chains=C,
+                  num_series=len(ids), seed=seed_pair, device=dev, flags=kflags)
+    par = _native.make_params([params[b] for b in ids])
+    if route["route"] == "ragged":
+      sess = _native.Session.ragged(_native.make_problem(**common), prep.lengths[ids],
+                                    y_model[ids, :T], prep.mask[ids, :T], design, par, series_ids=ids)
+    else:
+      num_seasons, season_change = _model.expand_seasons(model_options.seasons, T)
+      sess = _native.Session(_native.make_problem(num_seasons=num_seasons, series_offset=int(ids[0]),
+                                                  **common),
+                             y_model[ids, :T], prep.mask[ids, :T], design, season_change, par)
+    try:
+      sess.run()
+      out = sess.fetch(want)
+      dsum = sess.summarize(prep.outcome_sd[ids], prep.outcome_mean[ids], prep.observed[ids, :T],
+                            prep.flags[ids, :T], ranks)
+      if len(ids) == 1:
+        dsum = {k: v[None] for k, v in dsum.items()}
+    finally:
+      sess.close()
+    return ids, T, out, dsum
+
+  launches = panel_launches(route, inference_options.devices, shared_streams)
+  by_dev: Dict[int, list] = {}
+  for dev, key, ids in launches:
+    by_dev.setdefault(dev, []).append((dev, key, ids))
+  if len(by_dev) == 1:
+    results = [run(*a) for a in launches]
+  else:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=len(by_dev)) as pool:
+      per_dev = list(pool.map(lambda work: [run(*a) for a in work], by_dev.values()))
+    results = [r for part in per_dev for r in part]
+  R, N = len(ranks), C * S
+  means = np.zeros((B, T_max), np.float32)
+  dsum = dict(value_order=np.full((B, R, T_max), np.nan), cum_order=np.full((B, R, T_max), np.nan),
+              per_draw=np.zeros((B, 2, N)), per_draw_order=np.zeros((B, 2, R)))
+  diag_draws = None
+  if C > 1:
+    diag_draws = {k: np.zeros((B, C, S), np.float32) for k in ("observation_noise_scale", "level_scale")}
+  for ids, T, out, ds in results:
+    means[ids, :T] = out["posterior_means"].mean(axis=1)
+    dsum["value_order"][ids, :, :T] = ds["value_order"]
+    dsum["cum_order"][ids, :, :T] = ds["cum_order"]
+    dsum["per_draw"][ids] = ds["per_draw"]
+    dsum["per_draw_order"][ids] = ds["per_draw_order"]
+    if diag_draws is not None:
+      for k in diag_draws:
+        diag_draws[k][ids] = out[k]
+  return CausalImpactPanelAnalysis(prep, names, alpha, means, dsum, ranks, columns, diag_draws)

@@ -56,6 +56,7 @@ CI_WIDE_DECL(2) CI_WIDE_DECL(3) CI_WIDE_DECL(4) CI_WIDE_DECL(5) CI_WIDE_DECL(6) 
 // One object file per (D, L) instantiation (ci_inst.hip).
 #define CI_DECL(D, L)                                                                          \
   extern "C" void* ci_gibbs_fn_d##D##_l##L(int);                                              \
+  extern "C" void* ci_gibbs_ragged_fn_d##D##_l##L(int);                                       \
   extern "C" void* ci_gibbs8_fn_d##D##_l##L(int, int, size_t*);                               \
   extern "C" void ci_launch_dk_d##D##_l##L(int, const float*, const uint8_t*, float, float,    \
                                            float, float, float, float, uint32_t, uint32_t,     \
@@ -85,15 +86,18 @@ namespace ci {
 // feature-major copy).
 // ------------------------------------------------------------------------------------
 template <class XT>
-static __global__ void setup_regression_kernel(int T, int P, const XT* Xt, const uint8_t* mask,
+static __global__ void setup_regression_kernel(int TS, int P, const XT* Xt, const uint8_t* mask,
                                         const double* __restrict__ prior_scale, double* xtx,
-                                        double* omega) {
-  // one wavefront per (series, i, j): lanes stride over time (both rows coalesced), float64 sums
+                                        double* omega, const int* __restrict__ series_T = nullptr) {
+  // one wavefront per (series, i, j): lanes stride over time (both rows coalesced), float64 sums.
+  // TS is the row stride; a ragged session gives every series its own number of rows T <= TS
+  // (series_T) and rows [T, TS) are not read.
   const int e = blockIdx.x % (P * P), series = blockIdx.x / (P * P);
   const int i = e / P, j = e % P, lane = threadIdx.x;
-  const XT* xi = Xt + ((size_t)series * P + i) * T;
-  const XT* xj = Xt + ((size_t)series * P + j) * T;
-  const uint8_t* m = mask + (size_t)series * T;
+  const int T = series_T ? series_T[series] : TS;
+  const XT* xi = Xt + ((size_t)series * P + i) * TS;
+  const XT* xj = Xt + ((size_t)series * P + j) * TS;
+  const uint8_t* m = mask + (size_t)series * TS;
   double so = 0.0, sa = 0.0;
   for (int t = lane; t < T; t += 64) {
     const double v = (double)xi[t] * (double)xj[t];
@@ -181,6 +185,13 @@ KernelFn pick_kernel8(int D, int L, int profiled, int xg, size_t* lds_base) {
 }
 KernelFn pick_kernel(int D, int L, int pm) {
 #define CI_CASE(DD, LL) if (D == DD && L == LL) return (KernelFn)ci_gibbs_fn_d##DD##_l##LL(pm);
+  CI_CASE(1, 1) CI_CASE(1, 2) CI_CASE(1, 4) CI_CASE(1, 8) CI_CASE(1, 16)
+  CI_CASE(2, 1) CI_CASE(2, 2) CI_CASE(2, 4) CI_CASE(2, 8) CI_CASE(2, 16)
+#undef CI_CASE
+  return nullptr;
+}
+KernelFn pick_ragged_kernel(int D, int L, int pm) {
+#define CI_CASE(DD, LL) if (D == DD && L == LL) return (KernelFn)ci_gibbs_ragged_fn_d##DD##_l##LL(pm);
   CI_CASE(1, 1) CI_CASE(1, 2) CI_CASE(1, 4) CI_CASE(1, 8) CI_CASE(1, 16)
   CI_CASE(2, 1) CI_CASE(2, 2) CI_CASE(2, 4) CI_CASE(2, 8) CI_CASE(2, 16)
 #undef CI_CASE
@@ -485,6 +496,10 @@ struct ci_session {
   DevBuf<ci::DevSeriesParams> sp;
   DevBuf<long long> prof;
   bool profile = false;
+  // ragged sessions (ci_session_create_ragged): pb.T is the row stride, series b has lengths[b] steps
+  bool ragged = false;
+  std::vector<int> lengths;
+  DevBuf<int> series_T, series_ids;
   // seasonal models
   int D_full = 0, dred = 0;
   DevBuf<uint8_t> season_change;
@@ -647,10 +662,62 @@ struct SessionGuard {
   ~SessionGuard() { if (s) ci_session_destroy(s); }
 };
 
+// Everything ci_session_create_ragged checks, before any device call.
+static int validate_ragged(const ci_problem* pb, const int32_t* series_lengths) {
+  if (validate(pb)) return 1;
+  if (!series_lengths) return fail("series_lengths is NULL");
+  if (pb->num_blocks > 0)
+    return fail("ragged sessions hold trend models only: num_blocks must be 0, got %d", pb->num_blocks);
+  if (pb->P > ci::MAXP)
+    return fail("ragged sessions take at most %d design columns, got P=%d", ci::MAXP, pb->P);
+  const int L = steps_per_thread(pb->T);
+  if (L == 0)
+    return fail("ragged sessions take series of at most %d steps, got T=%d", ci::NT * 16, pb->T);
+  int longest = 0;
+  for (int b = 0; b < pb->num_series; ++b) {
+    const int tb = series_lengths[b];
+    if (tb < 3) return fail("series_lengths[%d] must be >= 3, got %d", b, tb);
+    if (tb > pb->T) return fail("series_lengths[%d] = %d exceeds the stride T=%d", b, tb, pb->T);
+    if (tb > longest) longest = tb;
+  }
+  if (longest != pb->T)
+    return fail("T must be the longest series of the session: max(series_lengths) = %d, T = %d",
+                longest, pb->T);
+  for (int b = 0; b < pb->num_series; ++b)
+    if (steps_per_thread(series_lengths[b]) != L)
+      return fail("series_lengths[%d] = %d runs %d steps per thread, the longest series (%d) runs %d: "
+                  "all series of a ragged session must share that class",
+                  b, series_lengths[b], steps_per_thread(series_lengths[b]), pb->T, L);
+  return 0;
+}
+
+static int session_create_impl(const ci_problem* pb, const int32_t* series_lengths,
+                               const int32_t* series_ids, const float* y, const uint8_t* mask,
+                               const float* X, const uint8_t* season_change,
+                               const ci_series_params* params, ci_session** out);
+
 int ci_session_create(const ci_problem* pb, const float* y, const uint8_t* mask, const float* X,
                       const uint8_t* season_change, const ci_series_params* params,
                       ci_session** out) {
   if (validate(pb)) return 1;
+  return session_create_impl(pb, nullptr, nullptr, y, mask, X, season_change, params, out);
+}
+
+int ci_session_create_ragged(const ci_problem* pb, const int32_t* series_lengths,
+                             const int32_t* series_ids, const float* y, const uint8_t* mask,
+                             const float* X, const ci_series_params* params, ci_session** out) {
+  if (validate_ragged(pb, series_lengths)) return 1;
+  if (series_ids)
+    for (int b = 0; b < pb->num_series; ++b)
+      if (series_ids[b] < 0) return fail("series_ids[%d] must be >= 0, got %d", b, series_ids[b]);
+  return session_create_impl(pb, series_lengths, series_ids, y, mask, X, nullptr, params, out);
+}
+
+static int session_create_impl(const ci_problem* pb, const int32_t* series_lengths,
+                               const int32_t* series_ids, const float* y, const uint8_t* mask,
+                               const float* X, const uint8_t* season_change,
+                               const ci_series_params* params, ci_session** out) {
+  const bool ragged = series_lengths != nullptr;
   if (!y || !mask || !params || !out) return fail("NULL argument");
   if (pb->num_blocks > 0 && !season_change) return fail("season_change is NULL but num_blocks > 0");
   if (pb->P > 0 && !X) return fail("X is NULL but P=%d", pb->P);
@@ -658,6 +725,8 @@ int ci_session_create(const ci_problem* pb, const float* y, const uint8_t* mask,
   ci_session* s = new ci_session();
   SessionGuard guard{s};
   s->pb = *pb;
+  s->ragged = ragged;
+  if (ragged) s->lengths.assign(series_lengths, series_lengths + pb->num_series);
   const ci_problem* caller_pb = pb;
   // Trend-only series longer than the register-resident kernel holds (T > 4096) run on the
   // time-parallel kernel (ci_wide.h) with one INERT seasonal block: 2 seasons, zero initial
@@ -692,11 +761,14 @@ int ci_session_create(const ci_problem* pb, const float* y, const uint8_t* mask,
     // P <= 16: the register-resident regression block, with the design in LDS or -- long series --
     // streamed from L2; beyond 16 columns the LDS block drawn by the whole workgroup
     const int pm = (P == 0) ? 0 : (P <= 16 ? (s->x_in_lds ? 1 : 3) : 2);
-    s->fn = pick_kernel(D, s->L, pm);
-    s->fn_prof = pick_kernel(D, s->L, pm + 8);       // instrumented variant (ci_session_profile)
-    if (!s->fn || !s->fn_prof) return fail("no kernel for L=%d", s->L);
+    // (x_in_lds and pm are functions of P and the steps-per-thread class alone: a ragged session
+    //  makes the choices of a single fit of any of its series)
+    s->fn = ragged ? pick_ragged_kernel(D, s->L, pm) : pick_kernel(D, s->L, pm);
+    s->fn_prof = ragged ? nullptr : pick_kernel(D, s->L, pm + 8);   // instrumented variant (ci_session_profile)
+    if (!s->fn || (!ragged && !s->fn_prof)) return fail("no kernel for L=%d", s->L);
     char nm[96];
-    snprintf(nm, sizeof(nm), "ci::gibbs_kernel<%d,%d,%d,false>", D, s->L, pm);
+    snprintf(nm, sizeof(nm), ragged ? "ci::gibbs_kernel<%d,%d,%d,false,ragged>" : "ci::gibbs_kernel<%d,%d,%d,false>",
+             D, s->L, pm);
     s->kernel_name = nm;
     // latency build (ci_kernels8.h): eight wavefronts per chain -- four time waves, a regression
     // wave that owns the serial section and sweeps the next iteration's matrix during the draw,
@@ -709,7 +781,8 @@ int ci_session_create(const ci_problem* pb, const float* y, const uint8_t* mask,
     int num_cus = 256;
     (void)hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, pb->device);
     const bool latency_regime = (long long)B * C <= (long long)num_cus;
-    if ((pm == 1 || pm == 3) && latency_regime && !(pb->flags & CI_FLAG_FOUR_WAVES)) {
+    // (ragged sessions always take the four-wave kernel: same bits, only the timing differs)
+    if ((pm == 1 || pm == 3) && latency_regime && !(pb->flags & CI_FLAG_FOUR_WAVES) && !ragged) {
       // the design in LDS when it fits beside the randomness buffers, else read from L2 (the
       // same sums in the same order: the same bits)
       size_t base8 = 0;
@@ -852,6 +925,20 @@ int ci_session_create(const ci_problem* pb, const float* y, const uint8_t* mask,
   HIP_TRY(s->o_slope.alloc(pb->has_slope ? BCS * T : 0));
   HIP_TRY(s->o_pm.alloc((size_t)B * C * T));
   HIP_TRY(s->o_traj.alloc(BCS * T));
+  if (ragged) {
+    // Elements [T_b, T) of the four per-step outputs are never written by the kernel: cleared here,
+    // once, so that they read 0 after every run.
+    HIP_TRY(hipMemset(s->o_level.p, 0, s->o_level.n * sizeof(float)));
+    if (s->o_slope.n) HIP_TRY(hipMemset(s->o_slope.p, 0, s->o_slope.n * sizeof(float)));
+    HIP_TRY(hipMemset(s->o_pm.p, 0, s->o_pm.n * sizeof(float)));
+    HIP_TRY(hipMemset(s->o_traj.p, 0, s->o_traj.n * sizeof(float)));
+    HIP_TRY(s->series_T.alloc(B));
+    HIP_TRY(hipMemcpy(s->series_T.p, series_lengths, B * sizeof(int), hipMemcpyHostToDevice));
+    if (series_ids) {
+      HIP_TRY(s->series_ids.alloc(B));
+      HIP_TRY(hipMemcpy(s->series_ids.p, series_ids, B * sizeof(int), hipMemcpyHostToDevice));
+    }
+  }
   if (K > 0 || bigp) {
     HIP_TRY(s->season_change.alloc((size_t)K * T));
     HIP_TRY(s->ssp.alloc(B));
@@ -919,11 +1006,12 @@ int ci_session_create(const ci_problem* pb, const float* y, const uint8_t* mask,
   }
 
   // host-side staging: zero masked outcomes, transpose X to feature-major, count observations
-  std::vector<float> yh(BT);
+  std::vector<float> yh(BT, 0.f);
   std::vector<ci::DevSeriesParams> sph(B);
   for (int b = 0; b < B; ++b) {
     double nobs = 0;
-    for (int t = 0; t < T; ++t) {
+    const int Tb = ragged ? series_lengths[b] : T;      // (rows [Tb, T) of a ragged series are padding)
+    for (int t = 0; t < Tb; ++t) {
       const size_t i = (size_t)b * T + t;
       const bool m = mask[i] != 0;
       yh[i] = m ? 0.f : y[i];
@@ -977,6 +1065,8 @@ static int session_launch(ci_session* s) {
   a.progress = s->progress_every > 0 ? s->progress : nullptr;
   a.progress_every = s->progress_every > 0 ? s->progress_every : 1;
   a.dbg = s->sched_word;
+  a.series_T = s->series_T.p;          // (null unless the session is ragged)
+  a.series_ids = s->series_ids.p;
   if (s->profile) {
     if (!s->prof.p) HIP_TRY(s->prof.alloc(32));
     HIP_TRY(hipMemsetAsync(s->prof.p, 0, 32 * sizeof(long long), s->stream));
@@ -984,7 +1074,8 @@ static int session_launch(ci_session* s) {
   }
   if (pb.P > 0) {
     hipLaunchKernelGGL(ci::setup_regression_kernel<float>, dim3(pb.num_series * pb.P * pb.P), dim3(64), 0,
-                       s->stream, pb.T, pb.P, s->Xt.p, s->mask.p, s->wps.p, s->xtx.p, s->omega.p);
+                       s->stream, pb.T, pb.P, s->Xt.p, s->mask.p, s->wps.p, s->xtx.p, s->omega.p,
+                       (const int*)s->series_T.p);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(s->ev0, s->stream));
@@ -1046,6 +1137,7 @@ struct BigPair { float* dst; const float* src; size_t row; };
 int ci_session_run_streamed(ci_session* s, ci_outputs* o, int32_t chunk_draws, float* kernel_ms) {
   if (!s || !o) return fail("NULL argument");
   if (chunk_draws < 1) return fail("chunk_draws must be >= 1, got %d", chunk_draws);
+  if (s->ragged) return fail("ci_session_run_streamed does not take ragged sessions: use ci_session_run and ci_session_fetch");
   const ci_problem& pb = s->pb;
   HIP_TRY(hipSetDevice(pb.device));
   const int S = pb.num_results, T = pb.T, K = pb.num_blocks;
@@ -1321,7 +1413,17 @@ int ci_session_fetch(ci_session* s, ci_outputs* o) {
 int ci_session_algorithmic_bytes(const ci_session* s, double* bytes) {
   if (!s || !bytes) return fail("NULL argument");
   const ci_problem& pb = s->pb;
-  const double T = pb.T, P = pb.P, S = pb.num_results;
+  const double P = pb.P, S = pb.num_results;
+  if (s->ragged) {
+    // the real steps of every series, not the padding up to the stride
+    double steps = 0.0;
+    for (int tb : s->lengths) steps += tb;
+    const double slope = pb.has_slope ? 1.0 : 0.0;
+    *bytes = pb.num_chains * (S * (4.0 * steps * (2.0 + slope) + pb.num_series * 4.0 * (P + 2.0 + slope)) +
+                              4.0 * steps * (P + 1.0) + steps);
+    return 0;
+  }
+  const double T = pb.T;
   const double chains = (double)pb.num_series * pb.num_chains;
   // per retained draw 4 T (d_out + 1) + 4 (P + 2 + slope + K), d_out = level
   // + slope + the seasonal latents the fit materialises (one per block: ci_outputs.seasonal_levels);
@@ -1349,6 +1451,7 @@ int ci_ll_session_kernel_name(const ci_ll_session* s, char* buf, int32_t buflen)
 
 int ci_session_profile(ci_session* s, int enable, int64_t* cycles16) {
   if (!s) return fail("session is NULL");
+  if (s->ragged && enable) return fail("ci_session_profile does not take ragged sessions (no instrumented ragged build)");
   s->profile = enable != 0;
   if (cycles16) {
     if (!s->prof.p) { memset(cycles16, 0, 32 * sizeof(int64_t)); return 0; }
@@ -1363,6 +1466,7 @@ int ci_session_destroy(ci_session* s) {
   s->y.release(); s->Xt.release(); s->o_obs.release(); s->o_lscale.release(); s->o_sscale.release();
   s->o_w.release(); s->o_level.release(); s->o_slope.release(); s->o_pm.release();
   s->o_traj.release(); s->mask.release(); s->xtx.release(); s->omega.release(); s->wps.release(); s->sp.release(); s->prof.release();
+  s->series_T.release(); s->series_ids.release();
   s->season_change.release(); s->ssp.release(); s->p1_chol.release(); s->o_drift.release();
   s->o_seasonal.release(); s->ws.release(); s->csync.release(); s->cpart.release(); s->cw.release(); s->cv.release();
   s->summ.release();

@@ -77,6 +77,13 @@ struct KArgs {
   int dbg;                 // $CI_SCHED_WORD: replaces the eight-wave kernel's helper-wave schedule word
                            // (ci_kernels8.h SCHED_DEFAULT) -- timing experiments and the
                            // timing-independence test; 0 in production
+  // Ragged sessions (ci_session_create_ragged; read by the RAGGED build of gibbs_kernel only, null
+  // everywhere else): series b runs series_T[b] steps, T above is then only the ROW STRIDE of the
+  // [B,T] / [B,P,T] / [B,C,S,T] arrays (the longest series of the launch); series_ids[b], when
+  // given, is the series id whose Philox streams series b draws from (instead of
+  // series_stream_base + b: the series of a launch need not be neighbours in their panel).
+  const int* series_T;     // [B] or null
+  const int* series_ids;   // [B] or null
 };
 
 // The random stream of (series, chain): Philox counter word 3 = the global chain id (all 32 bits),
@@ -417,7 +424,10 @@ constexpr int RED_INC = 20;        // then (ss_level, ss_slope) per time wave
 template <int L, int NF, bool XG = false, bool ROLL = false>
 __device__ __forceinline__ void xt_sums_wave(const float* tg, const float* Xs, int tpad, int P, int j0,
                                              bool with_yty, float* sums, int lane, int T = 0,
-                                             bool xwide = true) {
+                                             bool xwide = true, int row_stride = -1) {
+  // row_stride: distance between the rows of a streamed design when it is not their length T (ragged
+  // sessions); the default folds to T at compile time
+  const int TS = row_stride < 0 ? T : row_stride;
   float4 tq[L];
 #pragma unroll
   for (int c = 0; c < L; ++c) tq[c] = *reinterpret_cast<const float4*>(tg + 4 * (lane + 64 * c));
@@ -449,7 +459,7 @@ __device__ __forceinline__ void xt_sums_wave(const float* tg, const float* Xs, i
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
       const int j = j0 + f;
-      const float* row = Xs + (size_t)(j < P ? j : P - 1) * T;
+      const float* row = Xs + (size_t)(j < P ? j : P - 1) * TS;
       float4 xq[L];
 #pragma unroll
       for (int c = 0; c < L; ++c) {
@@ -463,7 +473,7 @@ __device__ __forceinline__ void xt_sums_wave(const float* tg, const float* Xs, i
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
       const int j = j0 + f;
-      const float* row = Xs + (size_t)(j < P ? j : P - 1) * T;
+      const float* row = Xs + (size_t)(j < P ? j : P - 1) * TS;
       if constexpr (ROLL) {
         // guarded scalar reads (T % 4 != 0), 4 L per feature: four quads of loads in flight at a time
         // in a ROLLED loop, the targets re-read from LDS -- unrolled, the 4 L loads of every feature
@@ -2652,7 +2662,7 @@ static __device__ __forceinline__ void serial_section(SerialCtx* cx, const RegLd
   wave_sync();
 }
 
-template <int D, int L, int PM, bool PROF = false>
+template <int D, int L, int PM, bool PROF = false, bool RAGGED = false>
 #ifndef CI_MIN_WAVES
 #define CI_MIN_WAVES 2
 #endif
@@ -2664,13 +2674,23 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
   // function holding both cost the 512-series batch 7 %)
   constexpr int RPM = (PM == 3) ? 1 : PM;
   constexpr bool STREAM = PM == 3;
+  // RAGGED: every series of the launch has its own number of steps (KArgs::series_T) -- its own
+  // instantiation, for the reason PM = 3 is one: the stock code objects stay what they are.  It
+  // differs from the stock build only in where T comes from: TS (= a.T) is the row stride of every
+  // array over time, T the series' own length, wave-uniform and read through readfirstlane so that
+  // it lives in a scalar register.  Steps [T, 256 L) of a lane are masked padding exactly as in a
+  // single fit of that length, which runs the same instantiation: the same bits.  Elements [T, TS)
+  // of out_level / out_slope / out_pred_mean / out_traj are never written by this kernel: the
+  // session clears those arrays once when it is created (ci_session_create_ragged).
   constexpr bool NEWRED = RPM == 1;       // xt_sums_wave's layout of `red` (shared with the eight-wave kernel)
   using PF = typename std::conditional<PROF, Prof, NoProf>::type;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int series = blockIdx.x / a.C, chain = blockIdx.x % a.C;
-  const int T = a.T, P = (RPM == 0) ? 0 : a.P;
+  const int TS = a.T, P = (RPM == 0) ? 0 : a.P;
+  int T = TS;
+  if constexpr (RAGGED) T = __builtin_amdgcn_readfirstlane(a.series_T[series]);
   constexpr int TPAD = NT * L;
   const LdsLayout lay = make_layout(P, D, TPAD, a.x_in_lds);
   SerialCtx* cx = (SerialCtx*)(smem + lay.off_ctx);
@@ -2688,16 +2708,26 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
   const int RS = (P > 16 ? P : 16) + 4;   // stride of the per-wave partial-sum rows
 
   Rng rng;
-  rng.k0 = stream_key0(a.seed0, a.series_stream_base, series);
-  rng.k1 = stream_key1(a.seed1, a.series_stream_base, series);
+  if constexpr (RAGGED) {
+    // the series id the streams are keyed by: base < 0 keeps "every series on the streams of series 0"
+    const int sid = a.series_ids != nullptr ? __builtin_amdgcn_readfirstlane(a.series_ids[series])
+                                            : a.series_stream_base + series;
+    rng.k0 = stream_key0(a.seed0, a.series_stream_base < 0 ? -1 : 0, sid);
+    rng.k1 = stream_key1(a.seed1, a.series_stream_base < 0 ? -1 : 0, sid);
+  } else {
+    rng.k0 = stream_key0(a.seed0, a.series_stream_base, series);
+    rng.k1 = stream_key1(a.seed1, a.series_stream_base, series);
+  }
   rng.chain = (uint32_t)(a.chain_offset + chain);
 
   // ---- stage the constants of this series
-  const float* yg = a.y + (size_t)series * T;
-  const uint8_t* mg = a.mask + (size_t)series * T;
-  const float* Xg = a.Xt + (size_t)series * P * T;
+  const float* yg = a.y + (size_t)series * TS;
+  const uint8_t* mg = a.mask + (size_t)series * TS;
+  const float* Xg = a.Xt + (size_t)series * P * TS;
   // rows of the streamed design can be read as float4: T % 4 == 0 keeps every row 16-byte aligned
-  const bool xwide = L % 4 == 0 && (T & 3) == 0 && (reinterpret_cast<uintptr_t>(Xg) & 15) == 0;
+  // (ragged: the stride aligns the rows, the length keeps a float4 from straddling the end)
+  const bool xwide = L % 4 == 0 && (T & 3) == 0 && (!RAGGED || (TS & 3) == 0) &&
+                     (reinterpret_cast<uintptr_t>(Xg) & 15) == 0;
   const int t0 = tid * L;
   RegLds R;
   {
@@ -2757,7 +2787,7 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
     if (a.x_in_lds) {
       float* xw_ = (float*)(smem + lay.off_x);
       for (int j = 0; j < P; ++j)
-        for (int t = tid; t < TPAD; t += NT) xw_[j * TPAD + t] = (t < T) ? Xg[(size_t)j * T + t] : 0.f;
+        for (int t = tid; t < TPAD; t += NT) xw_[j * TPAD + t] = (t < T) ? Xg[(size_t)j * TS + t] : 0.f;
     }
     if (tid < P) wls[tid] = 0.f;                   // weights = 0            :575-578
   }
@@ -2778,9 +2808,9 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
 #pragma unroll
   for (int l = 0; l < L; ++l) { lev[l] = 0.f; slp[l] = 0.f; xw[l] = 0.f; pm_acc[l] = 0.f; }  // :580-581
 
-  float* o_level = a.out_level ? a.out_level + chain_lin * a.S * T : nullptr;
-  float* o_slope = a.out_slope ? a.out_slope + chain_lin * a.S * T : nullptr;
-  float* o_traj = a.out_traj ? a.out_traj + chain_lin * a.S * T : nullptr;
+  float* o_level = a.out_level ? a.out_level + chain_lin * a.S * TS : nullptr;
+  float* o_slope = a.out_slope ? a.out_slope + chain_lin * a.S * TS : nullptr;
+  float* o_traj = a.out_traj ? a.out_traj + chain_lin * a.S * TS : nullptr;
 
   const int n_iter = a.W + a.S;
   PriorCarry pc;
@@ -2808,7 +2838,7 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
         // same sequence of float additions as the register copy: same bits)
         float xwp[L], acc[L];
         lds_row_load<L>(xwb + t0, xwp);
-        float* pmo = a.out_pred_mean ? a.out_pred_mean + chain_lin * T : nullptr;
+        float* pmo = a.out_pred_mean ? a.out_pred_mean + chain_lin * TS : nullptr;
 #pragma unroll
         for (int l = 0; l < L; ++l) acc[l] = (pmo != nullptr && s > 0 && t0 + l < T) ? pmo[t0 + l] : 0.f;
 #pragma unroll
@@ -2830,10 +2860,10 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
           tr[l] = fmaf(so, zp[l], loc);
         }
       }
-      const size_t row = (size_t)s * T;
+      const size_t row = (size_t)s * TS;
       bool vec_done = false;
       if constexpr (L % 4 == 0) {
-        if ((T & 3) == 0) {
+        if ((T & 3) == 0 && (!RAGGED || (TS & 3) == 0)) {
           vec_done = true;
 #pragma unroll
           for (int q = 0; q < L / 4; ++q) {
@@ -2945,9 +2975,9 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
           xt_rounds([&](int j, float (&xr)[L]) { lds_row_load<L>(Xs + j * TPAD + t0, xr); });
         } else if (xwide) {
           if constexpr (L % 4 == 0)
-            xt_rounds([&](int j, float (&xr)[L]) { global_row_load_wide<L>(Xg + (size_t)j * T, t0, T, xr); });
+            xt_rounds([&](int j, float (&xr)[L]) { global_row_load_wide<L>(Xg + (size_t)j * TS, t0, T, xr); });
         } else {
-          xt_rounds([&](int j, float (&xr)[L]) { global_row_load_scalar<L>(Xg + (size_t)j * T, t0, T, xr); });
+          xt_rounds([&](int j, float (&xr)[L]) { global_row_load_scalar<L>(Xg + (size_t)j * TS, t0, T, xr); });
         }
       }
       prof.tick(13);
@@ -2959,11 +2989,11 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
         if constexpr (STREAM && L >= 8) {
           // (two features at a time: the loads of four streamed rows of L float4 do not fit beside the
           //  rest -- same sums, each feature is summed on its own)
-          xt_sums_wave<L, 2, STREAM, true>(tgv, Xg, TPAD, P, 4 * wave, false, red, lane, T, xwide);
+          xt_sums_wave<L, 2, STREAM, true>(tgv, Xg, TPAD, P, 4 * wave, false, red, lane, T, xwide, TS);
           __builtin_amdgcn_sched_barrier(0);
-          xt_sums_wave<L, 2, STREAM, true>(tgv, Xg, TPAD, P, 4 * wave + 2, wave == NW - 1, red, lane, T, xwide);
+          xt_sums_wave<L, 2, STREAM, true>(tgv, Xg, TPAD, P, 4 * wave + 2, wave == NW - 1, red, lane, T, xwide, TS);
         } else {
-          xt_sums_wave<L, 4, STREAM>(tgv, STREAM ? Xg : Xs, TPAD, P, 4 * wave, wave == NW - 1, red, lane, T, xwide);
+          xt_sums_wave<L, 4, STREAM>(tgv, STREAM ? Xg : Xs, TPAD, P, 4 * wave, wave == NW - 1, red, lane, T, xwide, TS);
         }
       }
       float ssl = 0.f, sss = 0.f;
@@ -3141,9 +3171,9 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
         };
         if (xwide) {
           if constexpr (L % 4 == 0)
-            stream([&](int j, float (&xr)[L]) { global_row_load_wide<L>(Xg + (size_t)j * T, t0, T, xr); });
+            stream([&](int j, float (&xr)[L]) { global_row_load_wide<L>(Xg + (size_t)j * TS, t0, T, xr); });
         } else {
-          stream([&](int j, float (&xr)[L]) { global_row_load_scalar<L>(Xg + (size_t)j * T, t0, T, xr); });
+          stream([&](int j, float (&xr)[L]) { global_row_load_scalar<L>(Xg + (size_t)j * TS, t0, T, xr); });
         }
       }
     } else if constexpr (RPM == 2) {
@@ -3173,10 +3203,10 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
         xw_rounds([&](int j, float (&xr)[L]) { lds_row_load<L>(Xs + j * TPAD + t0, xr); }, std::false_type());
       } else if (xwide) {
         if constexpr (L % 4 == 0)
-          xw_rounds([&](int j, float (&xr)[L]) { global_row_load_wide<L>(Xg + (size_t)j * T, t0, T, xr); },
+          xw_rounds([&](int j, float (&xr)[L]) { global_row_load_wide<L>(Xg + (size_t)j * TS, t0, T, xr); },
                     std::true_type());
       } else {
-        xw_rounds([&](int j, float (&xr)[L]) { global_row_load_scalar<L>(Xg + (size_t)j * T, t0, T, xr); },
+        xw_rounds([&](int j, float (&xr)[L]) { global_row_load_scalar<L>(Xg + (size_t)j * TS, t0, T, xr); },
                   std::true_type());
       }
     }
@@ -3224,7 +3254,7 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
 
   if (a.out_pred_mean) {
     const float inv = 1.0f / (float)(a.S > 0 ? a.S : 1);
-    float* pm = a.out_pred_mean + chain_lin * T;
+    float* pm = a.out_pred_mean + chain_lin * TS;
 #pragma unroll
     for (int l = 0; l < L; ++l) {
       const int t = t0 + l;
