@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CI_ABI_VERSION 4
+#define CI_ABI_VERSION 5
 #define CI_MAX_BLOCKS 8
 
 /* Per-series priors and initial Gibbs state.  One per series because every
@@ -225,6 +225,26 @@ int ci_session_create(const ci_problem* problem, const float* y, const uint8_t* 
 int ci_session_create_ragged(const ci_problem* problem, const int32_t* series_lengths,
                              const int32_t* series_ids, const float* y, const uint8_t* mask,
                              const float* X, const ci_series_params* params, ci_session** session);
+/* A RAGGED SEASONAL session: B models of trend plus ONE seasonal block of 2..7 seasons
+ * (num_blocks = 1, P <= 52, float32) whose series have their own lengths, fitted in one launch of
+ * the ragged build of the time-parallel kernel.  problem->T is the ROW STRIDE of every array over
+ * time, as in ci_session_create_ragged, and of season_change [num_blocks, T] (one table for the
+ * launch: the flags are positional, series b reads its first series_lengths[b] entries); seasonal_levels
+ * is a [.., T] output too.  T must be a multiple of 4, at most 65536, and the longest series rounded
+ * up to that multiple (max(series_lengths) > T - 4); 3 <= series_lengths[b] <= T, and all series
+ * must share the chunk length of the draw's grid (4 steps up to 2048 steps, then ceil(length / 512)
+ * rounded up to a multiple of 4).  CI_FLAG_SEQUENTIAL_SEASONAL, CI_FLAG_CLUSTER_SEASONAL,
+ * CI_FLAG_MULTIWAVE_SEASONAL and CI_FLAG_SEASONAL_WORKSPACE are refused: a single fit would not run
+ * this kernel under them.  series_ids, the padding contract (elements [length, T) of level, slope,
+ * seasonal_levels, posterior_means and posterior_trajectories read 0), the checks before any device
+ * call and the entry points that take or refuse the session are those of ci_session_create_ragged;
+ * ci_session_kernel_name reports "ci::gibbs_wide_kernel<D,NS,ragged>".  Series b gets, bit for bit,
+ * the draws of a single-series session of its own length with the same seed and streams.  It always
+ * runs one workgroup per chain (the stock kernel gives the same bits for every cluster size). */
+int ci_session_create_ragged_seasonal(const ci_problem* problem, const int32_t* series_lengths,
+                                      const int32_t* series_ids, const float* y, const uint8_t* mask,
+                                      const float* X, const uint8_t* season_change,
+                                      const ci_series_params* params, ci_session** session);
 /* Runs the fit on the session's stream and waits for it.  kernel_ms (optional)
  * receives the Gibbs kernel's duration measured with HIP events on that stream. */
 int ci_session_run(ci_session* session, float* kernel_ms);

@@ -13,7 +13,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 MAX_BLOCKS = 8
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, "lib", "libcausalimpact_amd.so")
@@ -93,6 +93,9 @@ def load():
   L.ci_session_create_ragged.argtypes = [C.POINTER(Problem), C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.POINTER(SeriesParams),
                                          C.POINTER(C.c_void_p)]
+  L.ci_session_create_ragged_seasonal.argtypes = [C.POINTER(Problem), C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(SeriesParams), C.POINTER(C.c_void_p)]
   L.ci_session_run.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
   L.ci_session_fetch.argtypes = [C.c_void_p, C.POINTER(Outputs)]
   L.ci_session_algorithmic_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -151,7 +154,7 @@ def exported_symbols() -> Sequence[str]:
   """Every entry point include/causalimpact_amd.h declares."""
   return ("ci_last_error", "ci_abi_version", "ci_device_count", "ci_series_stream_key", "ci_device_synchronize", "ci_pool_trim", "ci_host_alloc",
           "ci_host_free", "ci_fit_gibbs", "ci_fit_gibbs_f64", "ci_fit_gibbs_f64_kernel_ms",
-          "ci_session_create", "ci_session_create_ragged", "ci_session_run", "ci_session_run_streamed", "ci_session_fetch",
+          "ci_session_create", "ci_session_create_ragged", "ci_session_create_ragged_seasonal", "ci_session_run", "ci_session_run_streamed", "ci_session_fetch",
           "ci_session_algorithmic_bytes", "ci_session_kernel_name", "ci_session_destroy",
           "ci_session_profile", "ci_ll_session_kernel_name",
           "ci_session_summarize", "ci_summarize_draws", "ci_summarize_draws_f64",
@@ -258,7 +261,7 @@ def _stage_inputs(pb: Problem, y, mask, X, season_change):
   if P > 0:
     X32 = np.ascontiguousarray(np.asarray(X, dtype=np.float32).reshape(B, T, P))
   sc = None
-  if K > 0:
+  if K > 0 and season_change is not None:
     sc = np.ascontiguousarray(np.asarray(season_change, dtype=np.uint8).reshape(K, T))
   return y32, mask8, X32, sc
 
@@ -389,11 +392,14 @@ class Session:
                                        params, C.byref(self._h)))
 
   @classmethod
-  def ragged(cls, pb: Problem, lengths, y, mask, X, params, series_ids=None) -> "Session":
+  def ragged(cls, pb: Problem, lengths, y, mask, X, params, series_ids=None,
+             season_change=None) -> "Session":
     """ci_session_create_ragged: B trend series with their own lengths in one launch.  pb.T is the
     row stride (= max(lengths)) of y, mask [B, T] and X [B, T, P]; rows beyond a series' length are
     padding (never read).  series_ids [B]: the series ids the random streams are keyed by (default
-    pb.series_offset + b).  fetch() returns [.., T] arrays that are 0 beyond each length."""
+    pb.series_offset + b).  fetch() returns [.., T] arrays that are 0 beyond each length.
+    With `season_change` [1, T]: ci_session_create_ragged_seasonal -- trend plus one block of 2-7
+    seasons; pb.T is then max(lengths) rounded up to a multiple of 4."""
     self = cls.__new__(cls)
     self._lib = load()
     self.pb = pb
@@ -405,8 +411,14 @@ class Session:
       ids = np.ascontiguousarray(series_ids, dtype=np.int32).reshape(-1)
       if ids.size != pb.num_series:
         raise ValueError(f"`series_ids` must have one entry per series ({pb.num_series}), got {ids.size}")
-    y32, mask8, X32, _ = _stage_inputs(pb, y, mask, X, None)
     self._h = C.c_void_p()
+    y32, mask8, X32, _ = _stage_inputs(pb, y, mask, X, None)
+    if season_change is not None:
+      sc = np.ascontiguousarray(np.asarray(season_change, dtype=np.uint8).reshape(-1, pb.T))
+      _check(self._lib.ci_session_create_ragged_seasonal(C.byref(pb), _ptr(self.lengths), _ptr(ids),
+                                                         _ptr(y32), _ptr(mask8), _ptr(X32), _ptr(sc),
+                                                         params, C.byref(self._h)))
+      return self
     _check(self._lib.ci_session_create_ragged(C.byref(pb), _ptr(self.lengths), _ptr(ids), _ptr(y32),
                                               _ptr(mask8), _ptr(X32), params, C.byref(self._h)))
     return self

@@ -520,8 +520,25 @@ def steps_class(T: int) -> int:
   return 0
 
 
+# The ragged seasonal one-launch path (csrc/ci_wide.h, the RAGGED build of the time-parallel kernel;
+# ci_session_create_ragged_seasonal) covers standardised float32 Gibbs models of trend plus ONE block
+# of 2..7 seasons with at most PANEL_RAGGED_MAX_P design columns and this many steps; all series of a
+# launch share the chunk length of the draw's grid.
+PANEL_SEASONAL_MAX_T = 65536
+PANEL_SEASONAL_MAX_SEASONS = 7
+
+
+def seasonal_steps_class(T: int) -> int:
+  """Steps per chunk of the time-parallel seasonal kernel's grid of 512 chunks for a series of T
+  steps (csrc/ci_wide.h: wide_quad_steps): 4 up to 2048 steps, then ceil(T / 512) rounded up to a
+  multiple of 4."""
+  lc = -(-int(T) // 512)
+  return 4 if lc < 4 else (lc + 3) & ~3
+
+
 def panel_route(*, float64: bool, standardize_data: bool, sampler: str, num_seasonal_blocks: int,
-                P: int, lengths: Sequence[int]) -> Dict[str, Any]:
+                P: int, lengths: Sequence[int],
+                num_seasons: Optional[Sequence[int]] = None) -> Dict[str, Any]:
   """Where `fit_causalimpact_panel` fits a panel whose series b has lengths[b] model steps.
 
   {"route": ..., "groups": [(key, [series positions]), ...]}, groups in ascending key order, the
@@ -529,9 +546,14 @@ def panel_route(*, float64: bool, standardize_data: bool, sampler: str, num_seas
     "ragged"        trend model, P <= 52, every length <= 4096, float32, standardised, Gibbs: series
                     grouped by steps-per-thread class (key = L), one ragged launch per class (and
                     device);
-    "equal_length"  any other float32 standardised Gibbs model (seasonal blocks, P > 52, a series
-                    longer than 4096): series grouped by equal length (key = T), one ordinary
-                    session per distinct length -- the existing kernels, per-series mask / flags;
+    "ragged_seasonal"  (only when `num_seasons`, the seasons of every block, is given) trend plus ONE
+                    block of 2..7 seasons, P <= 52, every length <= 65536, float32, standardised,
+                    Gibbs: series grouped by `seasonal_steps_class` (key = steps per chunk), one
+                    ragged launch of the time-parallel kernel per class (and device);
+    "equal_length"  any other float32 standardised Gibbs model (other seasonal blocks, P > 52, a
+                    trend series longer than 4096): series grouped by equal length (key = T), one
+                    ordinary session per distinct length -- the existing kernels, per-series mask /
+                    flags;
     "per_series"    float64, standardize_data=False, sampler="hmc": `fit_causalimpact` on every
                     series in turn (one group per series, key = its position).
   A series' random streams are keyed by its POSITION IN THE PANEL on every route (the positions
@@ -541,16 +563,20 @@ def panel_route(*, float64: bool, standardize_data: bool, sampler: str, num_seas
     return dict(route="per_series", groups=[(b, [b]) for b in range(len(lengths))])
   ragged = (num_seasonal_blocks == 0 and P <= PANEL_RAGGED_MAX_P and
             all(t <= PANEL_RAGGED_MAX_T for t in lengths))
-  key_of = steps_class if ragged else (lambda t: t)
+  seasonal = (num_seasons is not None and num_seasonal_blocks == 1 and len(num_seasons) == 1 and
+              2 <= int(num_seasons[0]) <= PANEL_SEASONAL_MAX_SEASONS and P <= PANEL_RAGGED_MAX_P and
+              all(t <= PANEL_SEASONAL_MAX_T for t in lengths))
+  key_of = steps_class if ragged else (seasonal_steps_class if seasonal else (lambda t: t))
   groups: Dict[int, List[int]] = {}
   for b, t in enumerate(lengths):
     groups.setdefault(key_of(t), []).append(b)
-  return dict(route="ragged" if ragged else "equal_length", groups=sorted(groups.items()))
+  name = "ragged" if ragged else ("ragged_seasonal" if seasonal else "equal_length")
+  return dict(route=name, groups=sorted(groups.items()))
 
 
 def panel_launches(route: Dict[str, Any], devices: Sequence[int], shared_streams: bool = False):
   """[(device, key, [series positions])]: the launches of a routed panel.  Every group is sharded
-  over the devices as a batch is.  The ragged entry point takes the positions as `series_ids`, so
+  over the devices as a batch is.  The ragged entry points take the positions as `series_ids`, so
   a shard is one launch whatever its positions are; an ordinary session keys series b of the launch
   by series_offset + b, so on the "equal_length" route a shard is cut into runs of consecutive
   positions (one launch each) -- unless the streams are shared, when no position enters a key."""
@@ -787,8 +813,11 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   Routes (`panel_route`): standardised float32 Gibbs trend models with at most 52 design columns
   and 4096 steps are grouped by steps-per-thread class (<= 256, 512, 1024, 2048, 4096 steps) and
   each class runs in ONE launch per device of the ragged build of the four-wavefront kernel, every
-  series on its own length.  Other float32 standardised Gibbs models (seasonal blocks, more
-  columns, longer series) are grouped by equal length, one ordinary session per length.  float64,
+  series on its own length.  Trend plus ONE block of 2..7 seasons (`Seasons(num_seasons=7)` on daily
+  data), at most 52 design columns and 65536 steps: grouped by `seasonal_steps_class` (one class up
+  to 2048 steps), ONE launch per class and device of the ragged build of the time-parallel kernel.
+  Other float32 standardised Gibbs models (other seasonal blocks, more columns, longer trend
+  series) are grouped by equal length, one ordinary session per length.  float64,
   `standardize_data=False` and `sampler="hmc"` panels are fitted series by series.
 
   Random streams as in `fit_causalimpact_batch`: series b draws from the streams of series id b,
@@ -840,7 +869,8 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   T_max = prep.y.shape[1]
   P = 0 if prep.design is None else prep.design.shape[2]
   route = panel_route(float64=float64, standardize_data=True, sampler="gibbs",
-                      num_seasonal_blocks=num_blocks, P=P, lengths=prep.lengths)
+                      num_seasonal_blocks=num_blocks, P=P, lengths=prep.lengths,
+                      num_seasons=_model.expand_seasons(model_options.seasons, 1)[0])
   # the sampler sees the outcome in DataOptions.dtype (data.py:121-128), priors included
   y_model = prep.y.astype(cid._as_numpy_dtype(data_options.dtype)).astype(np.float64)  # pylint: disable=protected-access
   params = []
@@ -867,9 +897,24 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
                   num_warmup=inference_options.num_warmup_steps, num_results=S, num_chains=C,
                   num_series=len(ids), seed=seed_pair, device=dev, flags=kflags)
     par = _native.make_params([params[b] for b in ids])
+    observed, flags = prep.observed[ids, :T], prep.flags[ids, :T]
     if route["route"] == "ragged":
       sess = _native.Session.ragged(_native.make_problem(**common), prep.lengths[ids],
                                     y_model[ids, :T], prep.mask[ids, :T], design, par, series_ids=ids)
+    elif route["route"] == "ragged_seasonal":
+      # the stride: the longest series rounded up to a multiple of 4 (every row 16-byte aligned);
+      # the padding as in PreparedPanel -- y NaN, mask True, design 0, observed NaN, flags 0 -- and
+      # one table of positional change flags for the launch (every series starts at its own step 0)
+      TS = (T + 3) & ~3
+      pad = lambda a, fill: np.concatenate(   # pylint: disable=unnecessary-lambda-assignment
+          [a[ids, :T], np.full((len(ids), TS - T) + a.shape[2:], fill, a.dtype)], axis=1)
+      num_seasons, season_change = _model.expand_seasons(model_options.seasons, TS)
+      common["T"] = TS
+      sess = _native.Session.ragged(_native.make_problem(num_seasons=num_seasons, **common),
+                                    prep.lengths[ids], pad(y_model, np.nan), pad(prep.mask, True),
+                                    None if design is None else pad(prep.design, 0.0), par,
+                                    series_ids=ids, season_change=season_change)
+      observed, flags = pad(prep.observed, np.nan), pad(prep.flags, 0)
     else:
       num_seasons, season_change = _model.expand_seasons(model_options.seasons, T)
       sess = _native.Session(_native.make_problem(num_seasons=num_seasons, series_offset=int(ids[0]),
@@ -878,12 +923,14 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
     try:
       sess.run()
       out = sess.fetch(want)
-      dsum = sess.summarize(prep.outcome_sd[ids], prep.outcome_mean[ids], prep.observed[ids, :T],
-                            prep.flags[ids, :T], ranks)
+      dsum = sess.summarize(prep.outcome_sd[ids], prep.outcome_mean[ids], observed, flags, ranks)
       if len(ids) == 1:
         dsum = {k: v[None] for k, v in dsum.items()}
     finally:
       sess.close()
+    if route["route"] == "ragged_seasonal":      # (back at the stride of the longest series)
+      out = {k: (v[..., :T] if k == "posterior_means" else v) for k, v in out.items()}
+      dsum = {k: (v[..., :T] if k in ("value_order", "cum_order") else v) for k, v in dsum.items()}
     return ids, T, out, dsum
 
   launches = panel_launches(route, inference_options.devices, shared_streams)

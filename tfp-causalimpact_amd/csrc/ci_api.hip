@@ -46,6 +46,8 @@ CI_WIDEBIG_DECL(2) CI_WIDEBIG_DECL(3) CI_WIDEBIG_DECL(4) CI_WIDEBIG_DECL(5) CI_W
 #define CI_WIDE_DECL(NS)                                  \
   extern "C" void* ci_gibbs_wide_fn_tr1_ns##NS(void);     \
   extern "C" void* ci_gibbs_wide_fn_tr2_ns##NS(void);     \
+  extern "C" void* ci_gibbs_wide_ragged_fn_tr1_ns##NS(void);     \
+  extern "C" void* ci_gibbs_wide_ragged_fn_tr2_ns##NS(void);     \
   extern "C" void ci_launch_wide_score_tr1_ns##NS(const ci::WideScoreArgs*, hipStream_t);  \
   extern "C" void ci_launch_wide_score_tr2_ns##NS(const ci::WideScoreArgs*, hipStream_t);  \
   extern "C" void ci_launch_hmc_wide_tr1_ns##NS(const ci::HmcWideArgs*, hipStream_t);      \
@@ -377,6 +379,14 @@ void* pick_wide_kernel(int has_slope, int num_seasons) {
 #undef CI_WIDE_CASE
   return nullptr;
 }
+// ... its RAGGED builds (ci_wide_ragged.hip: per-series lengths, <= 52 design columns)
+void* pick_wide_ragged_kernel(int has_slope, int num_seasons) {
+#define CI_WIDE_CASE(NS) \
+  if (num_seasons == NS) return has_slope ? ci_gibbs_wide_ragged_fn_tr2_ns##NS() : ci_gibbs_wide_ragged_fn_tr1_ns##NS();
+  CI_WIDE_CASE(2) CI_WIDE_CASE(3) CI_WIDE_CASE(4) CI_WIDE_CASE(5) CI_WIDE_CASE(6) CI_WIDE_CASE(7)
+#undef CI_WIDE_CASE
+  return nullptr;
+}
 // ... and its BIGP builds (53+ design columns): trend-only models (through the inert 2-season block)
 // and trend + one block of 2-7 seasons, while the packed regression matrix and its index table fit in LDS
 // (P <= ~150); wider designs, other block lists and very short series keep the general routes.
@@ -496,7 +506,8 @@ struct ci_session {
   DevBuf<ci::DevSeriesParams> sp;
   DevBuf<long long> prof;
   bool profile = false;
-  // ragged sessions (ci_session_create_ragged): pb.T is the row stride, series b has lengths[b] steps
+  // ragged sessions (ci_session_create_ragged, ci_session_create_ragged_seasonal): pb.T is the row
+  // stride, series b has lengths[b] steps
   bool ragged = false;
   std::vector<int> lengths;
   DevBuf<int> series_T, series_ids;
@@ -691,6 +702,54 @@ static int validate_ragged(const ci_problem* pb, const int32_t* series_lengths) 
   return 0;
 }
 
+// Everything ci_session_create_ragged_seasonal checks, before any device call.
+static int validate_ragged_seasonal(const ci_problem* pb, const int32_t* series_lengths,
+                                    const int32_t* series_ids, const uint8_t* season_change) {
+  if (validate(pb)) return 1;
+  if (!series_lengths) return fail("series_lengths is NULL");
+  if (!season_change) return fail("season_change is NULL");
+  if (pb->num_blocks != 1)
+    return fail("ragged seasonal sessions hold trend plus one seasonal block: num_blocks must be 1, got %d",
+                pb->num_blocks);
+  if (pb->num_seasons[0] < 2 || pb->num_seasons[0] > 7)
+    return fail("ragged seasonal sessions take a block of 2 to 7 seasons, got num_seasons[0]=%d",
+                pb->num_seasons[0]);
+  if (pb->P > ci::MAXP)
+    return fail("ragged seasonal sessions take at most %d design columns, got P=%d", ci::MAXP, pb->P);
+  if ((pb->T & 3) != 0)
+    return fail("the stride T of a ragged seasonal session must be a multiple of 4, got T=%d", pb->T);
+  // (T <= 65536: validate() has refused a longer series of this model already)
+  int longest = 0;
+  for (int b = 0; b < pb->num_series; ++b) {
+    const int tb = series_lengths[b];
+    if (tb < 3) return fail("series_lengths[%d] must be >= 3, got %d", b, tb);
+    if (tb > pb->T) return fail("series_lengths[%d] = %d exceeds the stride T=%d", b, tb, pb->T);
+    if (tb > longest) longest = tb;
+  }
+  if (longest <= pb->T - 4)
+    return fail("T must be the longest series of the session rounded up to a multiple of 4: "
+                "max(series_lengths) = %d, T = %d", longest, pb->T);
+  const int Lc = ci::wide_quad_steps(longest);
+  for (int b = 0; b < pb->num_series; ++b)
+    if (ci::wide_quad_steps(series_lengths[b]) != Lc)
+      return fail("series_lengths[%d] = %d runs chunks of %d steps, the longest series (%d) chunks of %d: "
+                  "all series of a ragged seasonal session must share that class",
+                  b, series_lengths[b], ci::wide_quad_steps(series_lengths[b]), longest, Lc);
+  if (series_ids)
+    for (int b = 0; b < pb->num_series; ++b)
+      if (series_ids[b] < 0) return fail("series_ids[%d] must be >= 0, got %d", b, series_ids[b]);
+  // (a single fit of the model would not run the time-parallel kernel under any of these)
+  if (pb->flags & CI_FLAG_SEQUENTIAL_SEASONAL)
+    return fail("ragged seasonal sessions do not take CI_FLAG_SEQUENTIAL_SEASONAL");
+  if (pb->flags & CI_FLAG_CLUSTER_SEASONAL)
+    return fail("ragged seasonal sessions do not take CI_FLAG_CLUSTER_SEASONAL");
+  if (pb->flags & CI_FLAG_MULTIWAVE_SEASONAL)
+    return fail("ragged seasonal sessions do not take CI_FLAG_MULTIWAVE_SEASONAL");
+  if (pb->flags & CI_FLAG_SEASONAL_WORKSPACE)
+    return fail("ragged seasonal sessions do not take CI_FLAG_SEASONAL_WORKSPACE");
+  return 0;
+}
+
 static int session_create_impl(const ci_problem* pb, const int32_t* series_lengths,
                                const int32_t* series_ids, const float* y, const uint8_t* mask,
                                const float* X, const uint8_t* season_change,
@@ -711,6 +770,14 @@ int ci_session_create_ragged(const ci_problem* pb, const int32_t* series_lengths
     for (int b = 0; b < pb->num_series; ++b)
       if (series_ids[b] < 0) return fail("series_ids[%d] must be >= 0, got %d", b, series_ids[b]);
   return session_create_impl(pb, series_lengths, series_ids, y, mask, X, nullptr, params, out);
+}
+
+int ci_session_create_ragged_seasonal(const ci_problem* pb, const int32_t* series_lengths,
+                                      const int32_t* series_ids, const float* y, const uint8_t* mask,
+                                      const float* X, const uint8_t* season_change,
+                                      const ci_series_params* params, ci_session** out) {
+  if (validate_ragged_seasonal(pb, series_lengths, series_ids, season_change)) return 1;
+  return session_create_impl(pb, series_lengths, series_ids, y, mask, X, season_change, params, out);
 }
 
 static int session_create_impl(const ci_problem* pb, const int32_t* series_lengths,
@@ -826,7 +893,8 @@ static int session_create_impl(const ci_problem* pb, const int32_t* series_lengt
       s->Lc = ci::wide_quad_steps(T);
       s->lds_bytes = ci::make_wlayout(P, s->dred).total;
       s->fn = (KernelFn)(bigp ? pick_wide_bigp_kernel(pb->has_slope, pb->num_seasons[0])
-                              : pick_wide_kernel(pb->has_slope, pb->num_seasons[0]));
+                              : ragged ? pick_wide_ragged_kernel(pb->has_slope, pb->num_seasons[0])
+                                       : pick_wide_kernel(pb->has_slope, pb->num_seasons[0]));
     } else {
       // arrays over time in LDS when the whole layout fits (fastest), else in a per-chain HBM
       // workspace: no bound on the series length, and room in LDS for the P > 16 regression block.
@@ -851,6 +919,8 @@ static int session_create_impl(const ci_problem* pb, const int32_t* series_lengt
     // (measured, round 5: below ~110 steps the one-wavefront kernel is as fast or faster -- 158 us
     // against 171 us at T = 96 on the 4+7+6 model, 202 us against 174 us at T = 128)
     const int tp_min_t = P > ci::MAXP ? 64 : 112;
+    if (ragged && !(s->wide && !bigp && s->fn))
+      return fail("ragged seasonal sessions run the time-parallel kernel only (one block of 2 to 7 seasons, P <= %d)", ci::MAXP);
     if (!s->wide && !s->mw && s->D_full <= ci::TP_MAXD && T >= tp_min_t && !(pb->flags & CI_FLAG_SEQUENTIAL_SEASONAL) &&
         !(pb->flags & CI_FLAG_SEASONAL_WORKSPACE)) {
       int num_cus = 256;
@@ -890,7 +960,7 @@ static int session_create_impl(const ci_problem* pb, const int32_t* series_lengt
     char nm[96];
     if (s->tp) snprintf(nm, sizeof(nm), "ci::gibbs_seasonal_tp_kernel<%d> %d chunks x%d", ci::tp_nr(s->D_full) / 4,
                         s->Lc * ci::TP_NWV, s->cluster);
-    else if (s->wide) snprintf(nm, sizeof(nm), bigp ? "ci::gibbs_wide_kernel<%d,%d,bigp>" : "ci::gibbs_wide_kernel<%d,%d>", D, pb->num_seasons[0]);
+    else if (s->wide) snprintf(nm, sizeof(nm), bigp ? "ci::gibbs_wide_kernel<%d,%d,bigp>" : ragged ? "ci::gibbs_wide_kernel<%d,%d,ragged>" : "ci::gibbs_wide_kernel<%d,%d>", D, pb->num_seasons[0]);
     else if (s->mw) snprintf(nm, sizeof(nm), "ci::gibbs_seasonal_kernel<%s,%s,%d> (multi-wave)",
                              s->seasonal_gws ? "true" : "false", bigp ? "true" : "false", ci::MW_NWV);
     else snprintf(nm, sizeof(nm), "ci::gibbs_seasonal_kernel<%s,%s>", s->seasonal_gws ? "true" : "false",
@@ -926,8 +996,8 @@ static int session_create_impl(const ci_problem* pb, const int32_t* series_lengt
   HIP_TRY(s->o_pm.alloc((size_t)B * C * T));
   HIP_TRY(s->o_traj.alloc(BCS * T));
   if (ragged) {
-    // Elements [T_b, T) of the four per-step outputs are never written by the kernel: cleared here,
-    // once, so that they read 0 after every run.
+    // Elements [T_b, T) of the per-step outputs are never written by the kernel: cleared here,
+    // once, so that they read 0 after every run (the seasonal latents: below).
     HIP_TRY(hipMemset(s->o_level.p, 0, s->o_level.n * sizeof(float)));
     if (s->o_slope.n) HIP_TRY(hipMemset(s->o_slope.p, 0, s->o_slope.n * sizeof(float)));
     HIP_TRY(hipMemset(s->o_pm.p, 0, s->o_pm.n * sizeof(float)));
@@ -947,6 +1017,7 @@ static int session_create_impl(const ci_problem* pb, const int32_t* series_lengt
     if (!long_trend) {
       HIP_TRY(s->o_drift.alloc(BCS * K));
       HIP_TRY(s->o_seasonal.alloc(BCS * T * K));
+      if (ragged) HIP_TRY(hipMemset(s->o_seasonal.p, 0, s->o_seasonal.n * sizeof(float)));
     }
     if (s->wide) {
       HIP_TRY(s->ws.alloc((size_t)B * C * ci::wide_workspace_floats(s->dred, s->Lc)));
@@ -956,7 +1027,9 @@ static int session_create_impl(const ci_problem* pb, const int32_t* series_lengt
       (void)hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, pb->device);
       const long long groups = ((long long)B * C + 7) / 8 * 8;
       s->cluster = 1;
-      if (!(pb->flags & CI_FLAG_NO_CLUSTER) && P > 0 && (T & 3) == 0) {
+      // (a ragged session: one workgroup per chain -- clusters need T_b % 4 == 0 of every series, and
+      //  every cluster size gives the same bits)
+      if (!(pb->flags & CI_FLAG_NO_CLUSTER) && P > 0 && (T & 3) == 0 && !ragged) {
         if (groups * 16 <= num_cus) s->cluster = 16;
         else if (groups * 8 <= num_cus) s->cluster = 8;
         else if (groups * 4 <= num_cus) s->cluster = 4;
@@ -1418,8 +1491,8 @@ int ci_session_algorithmic_bytes(const ci_session* s, double* bytes) {
     // the real steps of every series, not the padding up to the stride
     double steps = 0.0;
     for (int tb : s->lengths) steps += tb;
-    const double slope = pb.has_slope ? 1.0 : 0.0;
-    *bytes = pb.num_chains * (S * (4.0 * steps * (2.0 + slope) + pb.num_series * 4.0 * (P + 2.0 + slope)) +
+    const double slope = pb.has_slope ? 1.0 : 0.0, K = pb.num_blocks;
+    *bytes = pb.num_chains * (S * (4.0 * steps * (2.0 + slope + K) + pb.num_series * 4.0 * (P + 2.0 + slope + K)) +
                               4.0 * steps * (P + 1.0) + steps);
     return 0;
   }

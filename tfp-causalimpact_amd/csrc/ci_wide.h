@@ -548,7 +548,16 @@ __device__ __forceinline__ int cl_assemble(int* csync, int role, int G, int tid)
 // BIGP: the build for 53+ design columns (its own instantiation: the kernels for <= 52 columns are
 // what they were) -- X'X / Omega in global memory, the regression draw of ci_bigp.h by the main
 // workgroup, no sweeper, wider cluster message and partial-sum rows.
-template <int TR, int NS, bool BIGP = false>
+// RAGGED: every series of the launch has its own number of steps (KArgs::series_T;
+// ci_session_create_ragged_seasonal) -- its own instantiation (ci_wide_ragged.hip), so that the stock
+// code objects stay what they are.  It differs from the stock build only in where T comes from: TS
+// (= KArgs::T) is the row stride of every per-series and per-draw array over time, T the series' own
+// length, uniform over the workgroup and read through readfirstlane so that it lives in a scalar
+// register.  Lc -- hence TP, the workspace layout and the chunk grid -- is one value per launch: the
+// host only puts series of one wide_quad_steps class together, so every series runs the grid, the
+// summation path (vec4 = T % 4 == 0) and the random numbers of its single fit: the same bits.
+// Elements [T, TS) of the per-step outputs are never written: the session clears them once.
+template <int TR, int NS, bool BIGP = false, bool RAGGED = false>
 __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
   using W = WDim<TR, NS>;
   constexpr int D = W::D, O = W::O, N1 = W::N1;
@@ -556,7 +565,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const KArgs& g = a.k;
-  const int T = g.T, P = g.P, Lc = a.Lc;
+  const int TS = g.T, P = g.P, Lc = a.Lc;
   const int TP = DK_CH * Lc;
   // workgroup -> (chain, role): the workgroups of one chain share an XCD (ids equal mod 8)
   const int GL = a.cluster;                   // workgroups per chain in this launch
@@ -569,6 +578,8 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
   }
   const int series = chain_id / g.C, chain = chain_id % g.C;
   const size_t chain_lin = (size_t)series * g.C + chain;
+  int T = TS;
+  if constexpr (RAGGED) T = __builtin_amdgcn_readfirstlane(g.series_T[series]);
   typedef typename std::conditional<BIGP, WLayout, WLayoutS>::type Lay;
   Lay lay;
   if constexpr (BIGP) lay = make_wlayout(P, D); else lay = make_wlayout_small(P, D);
@@ -610,8 +621,15 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
   const DevSeriesParams& sp = g.sp[series];       // (by reference: a copy holds ~50 scalar registers through the whole kernel)
   const DevSeasonalParams& ss = a.ssp[series];
   Rng rng{stream_key0(g.seed0, g.series_stream_base, series), stream_key1(g.seed1, g.series_stream_base, series), (uint32_t)(g.chain_offset + chain)};
-  const float* yg = g.y + (size_t)series * T;
-  const float* Xg = g.Xt + (size_t)series * P * T;
+  if constexpr (RAGGED) {
+    // the series id the streams are keyed by: base < 0 keeps "every series on the streams of series 0"
+    const int sid = g.series_ids != nullptr ? __builtin_amdgcn_readfirstlane(g.series_ids[series])
+                                            : g.series_stream_base + series;
+    rng.k0 = stream_key0(g.seed0, g.series_stream_base < 0 ? -1 : 0, sid);
+    rng.k1 = stream_key1(g.seed1, g.series_stream_base < 0 ? -1 : 0, sid);
+  }
+  const float* yg = g.y + (size_t)series * TS;
+  const float* Xg = g.Xt + (size_t)series * P * TS;
   const float* chol1 = a.p1_chol + (size_t)series * D * D;
 
   // ---- phases shared by the workgroups of a cluster -------------------------------------------
@@ -624,7 +642,9 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
   if (cmode == 3 && role > 0) return;         // the cluster did not assemble: main runs alone
   const int G = cmode == 3 ? 1 : GL;          // workgroups actually sharing this chain
   const bool light = cmode == 2;
-  float* cpart = a.cpart + chain_lin * (size_t)nseg * NW * RS;
+  // (the partial-sum rows of a chain are a launch constant: sized by the stride)
+  const int nseg_s = RAGGED ? ((TS >> 2) + NT - 1) / NT : nseg;
+  float* cpart = a.cpart + chain_lin * (size_t)nseg_s * NW * RS;
   int GS = 64;                          // (constants in the <= 52-column builds)
   if constexpr (BIGP) GS = lay.gs;
   const int CW0 = BIGP ? wide_cw0(P) : 56;
@@ -694,7 +714,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
     if (jlo < jhi) {
 #pragma unroll
       for (int q = 0; q < XS; ++q)
-        xn[q] = *reinterpret_cast<const float4*>(Xg + (size_t)(jlo + q < jhi ? jlo + q : jhi - 1) * T + 4 * ca);
+        xn[q] = *reinterpret_cast<const float4*>(Xg + (size_t)(jlo + q < jhi ? jlo + q : jhi - 1) * TS + 4 * ca);
     }
     for (int j0 = jlo; j0 < jhi; j0 += XS) {
       float4 xv[XS];
@@ -704,7 +724,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
 #pragma unroll
         for (int q = 0; q < XS; ++q) {
           const int j = j0 + XS + q < jhi ? j0 + XS + q : jhi - 1;
-          xn[q] = *reinterpret_cast<const float4*>(Xg + (size_t)j * T + 4 * ca);
+          xn[q] = *reinterpret_cast<const float4*>(Xg + (size_t)j * TS + 4 * ca);
         }
       }
 #pragma unroll
@@ -747,7 +767,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
   auto emit_range = [&](int it, float so, int lo, int hi) {
     const int s = it - 1 - g.W;
     const size_t o = chain_lin * g.S + s;
-    const size_t row = o * T;
+    const size_t row = o * TS;
     // 4 steps per thread: whole 16-byte accesses when the rows are 16-byte aligned (T % 4 == 0;
     // the shared T-arrays are padded to a multiple of 4)
     const int cend = hi < (T + 3) / 4 ? hi : (T + 3) / 4;
@@ -776,7 +796,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
           put(g.out_traj + at, fmaf(so, zp[0], loc.x), fmaf(so, zp[1], loc.y), fmaf(so, zp[2], loc.z),
               fmaf(so, zp[3], loc.w));
         if (g.out_pred_mean) {
-          float4* pm = reinterpret_cast<float4*>(g.out_pred_mean + chain_lin * T + 4 * c);
+          float4* pm = reinterpret_cast<float4*>(g.out_pred_mean + chain_lin * TS + 4 * c);
           float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
           if (s != 0) acc = *pm;                 // running sum, scaled at the end
           *pm = make_float4(acc.x + loc.x, acc.y + loc.y, acc.z + loc.z, acc.w + loc.w);
@@ -794,7 +814,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
           if (a.out_seasonal) a.out_seasonal[row + t] = sv;
           if (g.out_traj) g.out_traj[row + t] = fmaf(so, zp[q], loc);
           if (g.out_pred_mean) {
-            float* pm = g.out_pred_mean + chain_lin * T + t;   // running sum, scaled at the end
+            float* pm = g.out_pred_mean + chain_lin * TS + t;   // running sum, scaled at the end
             *pm = (s == 0 ? 0.f : *pm) + loc;
           }
         }
@@ -818,7 +838,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
             const int j = have ? __ffsll((long long)todo) - 1 : 0;
             todo &= todo - 1ull;
             wj[q] = have ? R.w[j] : 0.f;
-            xv[q] = *reinterpret_cast<const float4*>(Xg + (size_t)j * T + 4 * c4);
+            xv[q] = *reinterpret_cast<const float4*>(Xg + (size_t)j * TS + 4 * c4);
           }
 #pragma unroll
           for (int q = 0; q < XR; ++q) {
@@ -863,7 +883,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
               const int j = have ? base + __ffsll((long long)todo) - 1 : 0;
               todo &= todo - 1ull;
               wj[q] = have ? R.w[j] : 0.f;
-              xv[q] = *reinterpret_cast<const float4*>(Xg + (size_t)j * T + 4 * c4);
+              xv[q] = *reinterpret_cast<const float4*>(Xg + (size_t)j * TS + 4 * c4);
             }
 #pragma unroll
             for (int q = 0; q < XR; ++q) {
@@ -953,7 +973,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
   float nch = 0.f;
   for (int t = tid; t < TP; t += NT) {
     const bool in = t < T;
-    mskp[t] = in ? (g.mask[(size_t)series * T + t] != 0 ? 1 : 0) : 1;
+    mskp[t] = in ? (g.mask[(size_t)series * TS + t] != 0 ? 1 : 0) : 1;
     const uint8_t c = in ? (a.season_change[t] != 0 ? 1 : 0) : 0;
     cbp[t] = c;
     if (t + 1 < T && c) nch += 1.f;
@@ -1027,7 +1047,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
 #pragma unroll
               for (int u = 0; u < 4; ++u) {
                 const int t = tb + u * NT;
-                xv[q][u] = Xg[(size_t)j * T + (t < T ? t : T - 1)];
+                xv[q][u] = Xg[(size_t)j * TS + (t < T ? t : T - 1)];
               }
             }
 #pragma unroll
@@ -1211,7 +1231,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
               const int t = tb + u * NT;
-              xv[q][u] = Xg[(size_t)j * T + (t < T ? t : T - 1)];
+              xv[q][u] = Xg[(size_t)j * TS + (t < T ? t : T - 1)];
             }
           }
 #pragma unroll
@@ -1282,7 +1302,7 @@ __global__ __launch_bounds__(NT) void gibbs_wide_kernel(SArgs a) {
   __syncthreads();     // the running sums were accumulated through the emission's thread mapping
   if (g.out_pred_mean) {
     const float inv = 1.0f / (float)(g.S > 0 ? g.S : 1);
-    for (int t = tid; t < T; t += NT) g.out_pred_mean[chain_lin * T + t] *= inv;
+    for (int t = tid; t < T; t += NT) g.out_pred_mean[chain_lin * TS + t] *= inv;
   }
 }
 
