@@ -289,6 +289,40 @@ int ci_session_summarize(ci_session* session, const double* scale, const double*
                          const double* observed, const uint8_t* flags, int32_t num_ranks,
                          const int32_t* ranks, double* value_order, double* cum_order,
                          double* per_draw, double* per_draw_order);
+/* On-device summary of the model's COMPONENTS over the pooled draws of a finished run, for all B
+ * series of the session at once.  Additive: no struct or signature changed and CI_ABI_VERSION stays 5;
+ * a caller that may meet an older library looks the symbol up (dlsym) before using it.  With (scale[b], shift[b]) exactly as handed to
+ * ci_session_summarize, n one of the N = C*S pooled draws (chain-major), all in float64:
+ *   trend[b, n, t]       = level[b, n, t] * scale[b] + shift[b]          (two roundings)
+ *   seasonal_k[b, n, t]  = seasonal_levels[b, n, t, k] * scale[b]        one per seasonal block k
+ *   regression[b, n, t]  = (sum over j = 0..P-1, ascending, of X[b, t, j] * weights[b, n, j]) * scale[b]
+ *                          (the products of two float32 values are exact; only the additions round)
+ * and, on the model's scale, the regression weights of every design column j (the intercept
+ * column included).  For every component and step, and for every column: the MEAN over the N draws
+ * and the ORDER STATISTICS at `ranks` (num_ranks <= 8, 0-based; the caller interpolates quantiles
+ * from them as numpy does); for every column also the share of draws with a non-zero weight.
+ * Outputs (host, caller-allocated, float64; each may be NULL and is then skipped):
+ *   trend_mean [B, T]            trend_order [B, num_ranks, T]
+ *   seasonal_mean [B, K, T]      seasonal_order [B, K, num_ranks, T]
+ *   regression_mean [B, T]       regression_order [B, num_ranks, T]
+ *   inclusion_prob [B, P]        weight_mean [B, P]        weight_order [B, num_ranks, P]
+ * With K = 0 the seasonal outputs, with P = 0 the regression and weight outputs are left untouched.
+ * Order statistics equal a sort of the same float64 values bit for bit, inclusion counts are
+ * exact, a mean is within N * 2^-52 * max|x| of any other float64 summation of its row.
+ * Ordinary and both kinds of ragged sessions are taken, on every kernel route.  In a ragged
+ * session T is the row stride of the outputs; beyond a series' own length every latent reads 0
+ * (the padding contract), so there trend = shift[b], the seasonal and regression terms are 0, and
+ * none of it carries meaning -- as for ci_session_summarize.  The components pass one after another
+ * through the scratch of ci_session_summarize (allocated by whichever of the two runs first): no
+ * device memory beyond it unless P > T.
+ * Checked before any device call: a finished ci_session_run, num_ranks in [1, 8], ranks in [0, N). */
+int ci_session_summarize_components(ci_session* session, const double* scale, const double* shift,
+                                    int32_t num_ranks, const int32_t* ranks,
+                                    double* trend_mean, double* trend_order,
+                                    double* seasonal_mean, double* seasonal_order,
+                                    double* regression_mean, double* regression_order,
+                                    double* inclusion_prob, double* weight_mean,
+                                    double* weight_order);
 /* The same summary for draws that are on the host (pooled from several devices / processes, or
  * produced by the HMC path): trajectories [num_draws, T] float32 are uploaded to `device`,
  * summarised there and the (one-series) results returned as above. */

@@ -15,6 +15,11 @@ import numpy as np
 
 ABI_VERSION = 5
 MAX_BLOCKS = 8
+MAX_SUMMARY_RANKS = 8   # == ci::SUMM_MAX_RANKS (csrc/ci_summary.h)
+# the output arrays of ci_session_summarize_components, in argument order
+COMPONENT_OUTPUTS = ("trend_mean", "trend_order", "seasonal_mean", "seasonal_order",
+                     "regression_mean", "regression_order", "inclusion_prob", "weight_mean",
+                     "weight_order")
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, "lib", "libcausalimpact_amd.so")
 
@@ -104,6 +109,8 @@ def load():
   L.ci_session_summarize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]
+  L.ci_session_summarize_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                C.c_void_p] + [C.c_void_p] * 9
   L.ci_summarize_draws.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double,
                                    C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -157,7 +164,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_create", "ci_session_create_ragged", "ci_session_create_ragged_seasonal", "ci_session_run", "ci_session_run_streamed", "ci_session_fetch",
           "ci_session_algorithmic_bytes", "ci_session_kernel_name", "ci_session_destroy",
           "ci_session_profile", "ci_ll_session_kernel_name",
-          "ci_session_summarize", "ci_summarize_draws", "ci_summarize_draws_f64",
+          "ci_session_summarize", "ci_session_summarize_components", "ci_summarize_draws", "ci_summarize_draws_f64",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
           "ci_ll_session_draw_latents", "ci_ll_session_hmc_run", "ci_ll_session_hmc_fetch",
           "ci_ll_session_algorithmic_bytes", "ci_ll_session_destroy", "ci_ll_session_create_batch",
@@ -486,6 +493,44 @@ class Session:
     if B == 1:
       vo, co, pd_, do = vo[0], co[0], pd_[0], do[0]
     return dict(value_order=vo, cum_order=co, per_draw=pd_, per_draw_order=do)
+
+  def summarize_components(self, scale, shift, ranks, want=None) -> Dict[str, np.ndarray]:
+    """On-device means and order statistics, over the pooled draws, of the trend, every seasonal
+    block, the regression term and the regression weights of every series
+    (ci_session_summarize_components).  scale, shift: scalars or [B], as for `summarize`; ranks: 1
+    to 8 order statistics.  Returns float64 arrays that keep the series axis: trend_mean [B,T],
+    trend_order [B,R,T]; with K seasonal blocks seasonal_mean [B,K,T], seasonal_order [B,K,R,T]; with
+    P design columns regression_mean [B,T], regression_order [B,R,T], inclusion_prob [B,P],
+    weight_mean [B,P], weight_order [B,R,P].  `want`: the names to compute (default: all that the
+    model has); the others are skipped on the device too."""
+    pb = self.pb
+    B, T, P, K = pb.num_series, pb.T, pb.P, pb.num_blocks
+    rk = np.ascontiguousarray(ranks, dtype=np.int32).reshape(-1)
+    if not 1 <= rk.size <= MAX_SUMMARY_RANKS:
+      raise ValueError(f"`ranks` must hold 1 to {MAX_SUMMARY_RANKS} order statistics, got {rk.size}")
+    sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
+    for name, a in (("scale", sc), ("shift", sh)):
+      if a.shape not in ((), (B,)):
+        raise ValueError(f"`{name}` must be a scalar or have one entry per series ({B}), got shape {a.shape}")
+    sc = np.ascontiguousarray(np.broadcast_to(sc, (B,)))
+    sh = np.ascontiguousarray(np.broadcast_to(sh, (B,)))
+    R = rk.size
+    shapes = dict(trend_mean=(B, T), trend_order=(B, R, T))
+    if K > 0:
+      shapes.update(seasonal_mean=(B, K, T), seasonal_order=(B, K, R, T))
+    if P > 0:
+      shapes.update(regression_mean=(B, T), regression_order=(B, R, T), inclusion_prob=(B, P),
+                    weight_mean=(B, P), weight_order=(B, R, P))
+    if want is not None:
+      unknown = [k for k in want if k not in COMPONENT_OUTPUTS]
+      if unknown:
+        raise ValueError(f"unknown component outputs {unknown}: choose from {list(COMPONENT_OUTPUTS)}")
+      shapes = {k: v for k, v in shapes.items() if k in want}
+    arrs = {k: np.empty(v, np.float64) for k, v in shapes.items()}
+    _check(self._lib.ci_session_summarize_components(
+        self._h, sc.ctypes.data, sh.ctypes.data, int(R), rk.ctypes.data,
+        *[_ptr(arrs.get(k)) for k in COMPONENT_OUTPUTS]))
+    return arrs
 
   def close(self):
     if self._h:

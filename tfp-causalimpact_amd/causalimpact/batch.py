@@ -170,6 +170,10 @@ def summary_table(names, alpha, ranks, dsum, *, n_win, n_obs, obs_mean, obs_sum,
   return pd.DataFrame(data, index=index)
 
 
+# the component-summary arrays whose last axis is the design columns, not time
+_PER_COLUMN = ("inclusion_prob", "weight_mean", "weight_order")
+
+
 class CausalImpactBatchAnalysis:
   """Results for B series.  `summary`: DataFrame indexed by (series, average|cumulative) with the
   reference's 15 summary columns; `analysis[b]` / iteration: per-series CausalImpactAnalysis
@@ -177,8 +181,10 @@ class CausalImpactBatchAnalysis:
   when more than one chain was run."""
 
   def __init__(self, prepared, names, alpha, posterior_means, device_summary, ranks, columns,
-               diagnostic_draws):
+               diagnostic_draws, component_summary=None):
     self._prep, self._names, self.alpha = prepared, list(names), alpha
+    # {name: [B, ...]} of ci_session_summarize_components (InferenceOptions.components), or None
+    self._csum = component_summary
     self._means, self._dsum, self._ranks, self._columns = posterior_means, device_summary, ranks, columns
     # {key: [B, chains, draws]} of the scalars the diagnostics rank, or None for one chain.  The
     # diagnostics themselves (three rank / FFT passes per key per series) are computed on access:
@@ -259,8 +265,21 @@ class CausalImpactBatchAnalysis:
       rq["ranks"] = self._ranks
       series, summary = lib._compute_impact_device(            # pylint: disable=protected-access
           self._means[b], dsum, rq, ci_data, self.alpha)
-      self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b))
+      self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b),
+                                                *self._component_frames(b, ci_data))
     return self._cache[b]
+
+  def _component_frames(self, b: int, ci_data, num_steps: Optional[int] = None):
+    """(components, coefficients) of series b (its first `num_steps` steps: a panel's arrays are
+    padded to the longest series), or (None, None) when they were not asked for."""
+    if self._csum is None:
+      return None, None
+    csum = {k: (v[b] if k in _PER_COLUMN or num_steps is None
+                else v[b][..., :num_steps]) for k, v in self._csum.items()}
+    return lib._component_frames(                               # pylint: disable=protected-access
+        csum, self._ranks, self._dsum["per_draw"].shape[-1], self.alpha,
+        lib.posterior_processing.model_index(ci_data), ci_data.data.index,
+        list(ci_data.feature_ts.columns) if ci_data.feature_ts is not None else None)
 
   def __iter__(self):
     return (self[b] for b in range(len(self)))
@@ -393,7 +412,9 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
                             T=prep.y.shape[1],
                             P=0 if prep.design is None else prep.design.shape[2],
                             hmc_init=inference_options.hmc_init)
-    per_series = route == "per_series"
+    # the one-launch HMC path keeps no latent draws and has no component summary: asked for
+    # components, an HMC batch takes the per-series route, where `fit_causalimpact` has the draws
+    per_series = route == "per_series" or inference_options.components
   if per_series:
     # float64 compute (csrc/ci_gibbs64.h) and raw-scale outcomes (their per-series internal
     # conditioning, causalimpact_lib._internal_conditioning) exist on the single-series path: the
@@ -481,6 +502,10 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
                             observed[ids], flags, ranks)
       if len(ids) == 1:
         dsum = {k: v[None] for k, v in dsum.items()}
+      if inference_options.components:
+        out["components"] = sess.summarize_components(
+            prep.outcome_sd[ids] if prep.standardize_data else 1.0,
+            prep.outcome_mean[ids] if prep.standardize_data else 0.0, ranks)
     finally:
       sess.close()
     return out, dsum
@@ -498,7 +523,11 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   if C > 1:
     keys = ("observation_noise_scale", "level_scale")
     diag_draws = {k: np.concatenate([r[0][k] for r in results], axis=0) for k in keys}   # [B, C, S]
-  return CausalImpactBatchAnalysis(prep, names, alpha, means, dsum, ranks, columns, diag_draws)
+  csum = None
+  if inference_options.components:
+    csum = {k: np.concatenate([r[0]["components"][k] for r in results], axis=0)
+            for k in results[0][0]["components"]}
+  return CausalImpactBatchAnalysis(prep, names, alpha, means, dsum, ranks, columns, diag_draws, csum)
 
 
 # ------------------------------------------------------------------------------------------
@@ -790,7 +819,8 @@ class CausalImpactPanelAnalysis(CausalImpactBatchAnalysis):
       rq["ranks"] = self._ranks
       series, summary = lib._compute_impact_device(            # pylint: disable=protected-access
           self._means[b, :Tb], dsum, rq, ci_data, self.alpha)
-      self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b))
+      self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b),
+                                                *self._component_frames(b, ci_data, Tb))
     return self._cache[b]
 
 
@@ -926,12 +956,17 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
       dsum = sess.summarize(prep.outcome_sd[ids], prep.outcome_mean[ids], observed, flags, ranks)
       if len(ids) == 1:
         dsum = {k: v[None] for k, v in dsum.items()}
+      csum = None
+      if inference_options.components:
+        csum = sess.summarize_components(prep.outcome_sd[ids], prep.outcome_mean[ids], ranks)
     finally:
       sess.close()
     if route["route"] == "ragged_seasonal":      # (back at the stride of the longest series)
       out = {k: (v[..., :T] if k == "posterior_means" else v) for k, v in out.items()}
       dsum = {k: (v[..., :T] if k in ("value_order", "cum_order") else v) for k, v in dsum.items()}
-    return ids, T, out, dsum
+      if csum is not None:
+        csum = {k: (v if k in _PER_COLUMN else v[..., :T]) for k, v in csum.items()}
+    return ids, T, out, dsum, csum
 
   launches = panel_launches(route, inference_options.devices, shared_streams)
   by_dev: Dict[int, list] = {}
@@ -950,7 +985,17 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   diag_draws = None
   if C > 1:
     diag_draws = {k: np.zeros((B, C, S), np.float32) for k in ("observation_noise_scale", "level_scale")}
-  for ids, T, out, ds in results:
+  csum = None
+  for ids, T, out, ds, cs in results:
+    if cs is not None:
+      if csum is None:      # over time padded to the longest series with NaN, like the order statistics
+        csum = {k: (np.zeros((B,) + v.shape[1:]) if k in _PER_COLUMN
+                    else np.full((B,) + v.shape[1:-1] + (T_max,), np.nan)) for k, v in cs.items()}
+      for k, v in cs.items():
+        if k in _PER_COLUMN:
+          csum[k][ids] = v
+        else:
+          csum[k][ids, ..., :T] = v
     means[ids, :T] = out["posterior_means"].mean(axis=1)
     dsum["value_order"][ids, :, :T] = ds["value_order"]
     dsum["cum_order"][ids, :, :T] = ds["cum_order"]
@@ -959,4 +1004,4 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
     if diag_draws is not None:
       for k in diag_draws:
         diag_draws[k][ids] = out[k]
-  return CausalImpactPanelAnalysis(prep, names, alpha, means, dsum, ranks, columns, diag_draws)
+  return CausalImpactPanelAnalysis(prep, names, alpha, means, dsum, ranks, columns, diag_draws, csum)

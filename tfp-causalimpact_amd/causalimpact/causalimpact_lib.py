@@ -97,6 +97,13 @@ class CausalImpactAnalysis:
   summary: pd.DataFrame
   posterior_samples: CausalImpactPosteriorSamples
   diagnostics: Optional[Dict[str, Any]] = None   # split-R-hat per scalar when num_chains > 1
+  # InferenceOptions(components=True) only.  `components`: indexed like `series`; posterior mean and
+  # alpha/2, 1 - alpha/2 quantiles of the trend, every seasonal block and the regression term on the
+  # data scale (trend, trend_lower, trend_upper, seasonal_<k>..., regression...).  `coefficients`:
+  # one row per design column (the intercept included) with inclusion_probability, mean, lower,
+  # upper of its weight on the model's scale; None for a model without covariates.
+  components: Optional[pd.DataFrame] = None
+  coefficients: Optional[pd.DataFrame] = None
 
 
 @dataclasses.dataclass
@@ -146,6 +153,11 @@ class InferenceOptions:
   # on a GPU shared with other jobs: the time-parallel seasonal kernel then runs one workgroup per
   # chain instead of spin-synchronised clusters of CUs (same draws, bit for bit).
   kernel_flags: int = 0
+  # Also summarise the trend, every seasonal block, the regression term and the regression weights
+  # over the draws (`CausalImpactAnalysis.components` / `.coefficients`): on the GPU that holds the
+  # draws wherever the predictive summary runs there (csrc/ci_components.h), also for batches and
+  # panels, which keep no draws; in numpy from the pooled draws on the other routes.
+  components: bool = False
 
   def __post_init__(self):
     if self.num_warmup_steps is None:
@@ -182,6 +194,10 @@ def fit_causalimpact(data: pd.DataFrame,
     raise ValueError("`alpha` must be between 0 and 1.")
   request = (_device_summary_request(ci_data, alpha) if inference_options.summarize_on_device
              else None)
+  comp_request = None
+  if inference_options.components:
+    base = request if request is not None else _device_summary_request(ci_data, alpha)
+    comp_request = dict(scale=base["scale"], shift=base["shift"], quantiles=base["quantiles"])
   samples, posterior_means, posterior_trajectories, device_summary = _run_sampler(
       ci_data=ci_data, prior_level_sd=model_options.prior_level_sd, seed=seed,
       num_results=inference_options.num_results,
@@ -190,7 +206,7 @@ def fit_causalimpact(data: pd.DataFrame,
       devices=inference_options.devices, local_linear_trend=model_options.local_linear_trend,
       sampler=inference_options.sampler, summary_request=request,
       hmc_init=inference_options.hmc_init, hmc_prior=inference_options.hmc_prior,
-      kernel_flags=inference_options.kernel_flags)
+      kernel_flags=inference_options.kernel_flags, component_request=comp_request)
   # (draws pooled on the host -- several devices, float64, HMC -- were summarised inside
   #  _run_sampler, in the sampler's internal units)
   if device_summary is not None:
@@ -212,7 +228,101 @@ def fit_causalimpact(data: pd.DataFrame,
       seasonal_levels=_tensor(samples["seasonal_levels"]),                           # :312-322
       slope_scale=_tensor(samples["slope_scale"]) if model_options.local_linear_trend else None,
       slope=_tensor(samples["slope"]) if model_options.local_linear_trend else None)
-  return CausalImpactAnalysis(series, summary, posterior, samples.get("diagnostics"))
+  components = coefficients = None
+  if comp_request is not None:
+    num_draws = samples["level"].shape[0]
+    csum = comp_request.get("summary")
+    if csum is None:
+      # the routes that pool the draws on the host: the same definitions in numpy.  X is the design
+      # as the sampler saw it (float64 for the float64 Gibbs kernels, float32 otherwise).
+      comp_request["ranks"] = _summary_ranks(num_draws, comp_request["quantiles"])
+      X = None
+      if has_weights:
+        f64 = (cid._as_numpy_dtype(data_options.dtype) == np.float64   # pylint: disable=protected-access
+               and inference_options.sampler == "gibbs")
+        X = np.asarray(ci_data.feature_ts.values, np.float64 if f64 else np.float32)
+      csum = _component_summary_host(samples["level"], samples["seasonal_levels"],
+                                     samples["weights"] if has_weights else None, X,
+                                     comp_request["scale"], comp_request["shift"],
+                                     comp_request["ranks"])
+    components, coefficients = _component_frames(
+        csum, comp_request["ranks"], num_draws, alpha, posterior_processing.model_index(ci_data),
+        ci_data.data.index,
+        list(ci_data.feature_ts.columns) if ci_data.feature_ts is not None else None)
+  return CausalImpactAnalysis(series, summary, posterior, samples.get("diagnostics"), components,
+                              coefficients)
+
+
+def _component_summary_host(level, seasonal_levels, weights, X, scale, shift, ranks) -> Dict:
+  """The component summary of one series in numpy, from pooled draws: level [N, T],
+  seasonal_levels [N, T, K], weights [N, P] (or None), X [T, P].  The definitions of
+  ci_session_summarize_components (include/causalimpact_amd.h), in float64:
+    trend = level * scale + shift; seasonal_k = seasonal_levels[..., k] * scale;
+    regression = (sum over j ascending of X[:, j] * weights[:, j]) * scale;
+  per component and step the mean over the draws and the order statistics `ranks`; per design
+  column the share of non-zero weights, their mean and their order statistics.  Arrays are laid out
+  as the device returns them for one series: *_mean [T], *_order [R, T], seasonal_mean [K, T],
+  seasonal_order [K, R, T], inclusion_prob / weight_mean [P], weight_order [R, P]."""
+  scale, shift = np.float64(scale), np.float64(shift)
+  ranks = list(ranks)
+
+  def stats(m):                       # [N, T] -> mean [T], order [R, T]
+    return m.mean(axis=0), np.sort(m, axis=0)[ranks]
+
+  out = {}
+  out["trend_mean"], out["trend_order"] = stats(np.asarray(level, np.float64) * scale + shift)
+  seasonal = np.asarray(seasonal_levels, np.float64)
+  if seasonal.ndim == 3 and seasonal.shape[-1] > 0:
+    per = [stats(seasonal[:, :, k] * scale) for k in range(seasonal.shape[-1])]
+    out["seasonal_mean"] = np.stack([m for m, _ in per])
+    out["seasonal_order"] = np.stack([o for _, o in per])
+  if weights is not None and np.shape(weights)[-1] > 0:
+    w, X = np.asarray(weights, np.float64), np.asarray(X, np.float64)
+    acc = np.zeros((w.shape[0], X.shape[0]))
+    for j in range(w.shape[1]):
+      acc += w[:, j, None] * X[None, :, j]
+    out["regression_mean"], out["regression_order"] = stats(acc * scale)
+    out["inclusion_prob"] = np.count_nonzero(w, axis=0) / w.shape[0]
+    out["weight_mean"], out["weight_order"] = stats(w)
+  return out
+
+
+def _component_frames(csum: Dict, ranks, num_draws: int, alpha: float, model_idx: pd.Index,
+                      full_idx: pd.Index, design_columns):
+  """(components, coefficients) frames from the component summary of one series (device or host:
+  the layout of `_component_summary_host`).  `components` is indexed like the `series` frame --
+  `full_idx`, NaN on the rows before the pre-period, which the model never sees; `coefficients`
+  by the design columns' names (None without covariates)."""
+  rank_pos = {r: i for i, r in enumerate(ranks)}
+  (lo_a, hi_a, g_a), (lo_b, hi_b, g_b) = _quantile_ranks(num_draws, (alpha / 2.0, 1.0 - alpha / 2.0))
+
+  def band(order):                    # [R, X] -> lower, upper
+    by_rank = {r: order[rank_pos[r]] for r in (lo_a, hi_a, lo_b, hi_b)}
+    return _lerp_order_stats(by_rank, lo_a, hi_a, g_a), _lerp_order_stats(by_rank, lo_b, hi_b, g_b)
+
+  cols = {}
+
+  def add(name, mean, order):
+    cols[name] = np.asarray(mean, np.float64)
+    cols[name + "_lower"], cols[name + "_upper"] = band(order)
+
+  add("trend", csum["trend_mean"], csum["trend_order"])
+  if "seasonal_mean" in csum:
+    for k in range(csum["seasonal_mean"].shape[0]):
+      add(f"seasonal_{k}", csum["seasonal_mean"][k], csum["seasonal_order"][k])
+  if "regression_mean" in csum:
+    add("regression", csum["regression_mean"], csum["regression_order"])
+  components = pd.DataFrame(cols, index=model_idx)
+  if not model_idx.equals(full_idx):
+    components = components.reindex(full_idx, fill_value=np.nan)
+  coefficients = None
+  if "weight_mean" in csum and design_columns is not None:
+    lower, upper = band(csum["weight_order"])
+    coefficients = pd.DataFrame(
+        {"inclusion_probability": np.asarray(csum["inclusion_prob"], np.float64),
+         "mean": np.asarray(csum["weight_mean"], np.float64), "lower": lower, "upper": upper},
+        index=pd.Index(list(design_columns)))
+  return components, coefficients
 
 
 def _sanitize_seed(seed: Optional[_SeedType]) -> Tuple[int, int]:
@@ -309,10 +419,12 @@ def _internal_conditioning(ci_data) -> Tuple[float, float]:
 def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps, model=None,
                  dtype=np.float32, seasons=(), num_chains=1, devices=None,
                  local_linear_trend=False, sampler="gibbs", summary_request=None,
-                 hmc_init="gibbs", hmc_prior="slab", kernel_flags=0):
+                 hmc_init="gibbs", hmc_prior="slab", kernel_flags=0, component_request=None):
   """_train_causalimpact_sts plus, when `summary_request` is given (single device, Gibbs), the
   on-device summary of the predictive draws; the [draws, T] trajectories then stay in HBM and
-  are returned as None."""
+  are returned as None.  `component_request` (scale, shift, quantiles): on that route the component
+  summary of the session (ci_session_summarize_components) is left in it under "summary", with the
+  "ranks" it was taken at; on every other route the dict comes back as it went in."""
   if model is not None:
     raise NotImplementedError("custom tfp.sts models are not supported by the HIP path")
   seed_pair = _sanitize_seed(seed)
@@ -392,6 +504,19 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
             shift=(np.asarray(summary_request["shift"], np.float64)
                    + cond_mu * np.asarray(summary_request["scale"], np.float64)),
             **{k: summary_request[k] for k in ("observed", "flags", "ranks")})
+        if component_request is not None:
+          component_request["ranks"] = _summary_ranks(len(chain_ids) * num_results,
+                                                      component_request["quantiles"])
+          csum = sess.summarize_components(
+              scale=np.float64(component_request["scale"]) * cond_s,
+              shift=np.float64(component_request["shift"]) + cond_mu * np.float64(component_request["scale"]),
+              ranks=component_request["ranks"])
+          csum = {k: v[0] for k, v in csum.items()}
+          if cond_s != 1.0:                 # the weights on the caller's model scale, as in `samples`
+            for k in ("weight_mean", "weight_order"):
+              if k in csum:
+                csum[k] = csum[k] * cond_s
+          component_request["summary"] = csum
       finally:
         sess.close()
       return part

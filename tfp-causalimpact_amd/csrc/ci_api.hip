@@ -1304,6 +1304,21 @@ static hipError_t launch_select(hipStream_t stream, int N, int T, int rows, int 
   return hipGetLastError();
 }
 
+// The scratch of a summary of B series of N draws over T steps: allocated on first use and kept
+// (ci_session_summarize and ci_session_summarize_components share it).
+static int summ_scratch_alloc(SummScratch& w, int B, int T, int N) {
+  if (w.value.p) return 0;
+  const size_t BTN = (size_t)B * T * N;
+  HIP_TRY(w.value.alloc(BTN));
+  HIP_TRY(w.cum.alloc(BTN));
+  HIP_TRY(w.obs.alloc((size_t)B * T + 2 * B));
+  HIP_TRY(w.flags.alloc((size_t)B * T));
+  HIP_TRY(w.ranks.alloc(ci::SUMM_MAX_RANKS));
+  HIP_TRY(w.order.alloc((size_t)2 * B * ci::SUMM_MAX_RANKS * T));
+  HIP_TRY(w.draw.alloc((size_t)B * 2 * N + (size_t)B * 2 * ci::SUMM_MAX_RANKS));
+  return 0;
+}
+
 // The summary of B series' [B, N, T] float32 trajectories resident in HBM (ci_session_summarize,
 // ci_ll_session_hmc_summarize): transpose with value = trajectory * scale + shift, running sums,
 // order statistics; the scratch is allocated on first use and kept.
@@ -1316,16 +1331,7 @@ static int summarize_resident(hipStream_t stream, SummScratch& w, int B, int T, 
     return fail("num_ranks must be in [1, %d], got %d", ci::SUMM_MAX_RANKS, num_ranks);
   for (int r = 0; r < num_ranks; ++r)
     if (ranks[r] < 0 || ranks[r] >= N) return fail("rank %d out of range [0, %d)", ranks[r], N);
-  const size_t BTN = (size_t)B * T * N;
-  if (!w.value.p) {
-    HIP_TRY(w.value.alloc(BTN));
-    HIP_TRY(w.cum.alloc(BTN));
-    HIP_TRY(w.obs.alloc((size_t)B * T + 2 * B));
-    HIP_TRY(w.flags.alloc((size_t)B * T));
-    HIP_TRY(w.ranks.alloc(ci::SUMM_MAX_RANKS));
-    HIP_TRY(w.order.alloc((size_t)2 * B * ci::SUMM_MAX_RANKS * T));
-    HIP_TRY(w.draw.alloc((size_t)B * 2 * N + (size_t)B * 2 * ci::SUMM_MAX_RANKS));
-  }
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
   double* d_scale = w.obs.p + (size_t)B * T;
   double* d_shift = d_scale + B;
   HIP_TRY(hipMemcpyAsync(w.obs.p, observed, (size_t)B * T * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -1369,6 +1375,114 @@ int ci_session_summarize(ci_session* s, const double* scale, const double* shift
   return summarize_resident(s->stream, s->summ, pb.num_series, pb.T, pb.num_chains * pb.num_results,
                             s->o_traj.p, scale, shift, observed, flags, num_ranks, ranks, value_order,
                             cum_order, per_draw, per_draw_order);
+}
+
+// The launches of ci_components.hip (kernels: ci_components.h).
+extern "C++" {
+namespace ci {
+hipError_t comp_launch_gather(hipStream_t stream, int B, int N, int T, int K, int k, const float* in,
+                              const double* scales, const double* shifts, double* out);
+hipError_t comp_launch_regression(hipStream_t stream, int B, int N, int T, int P, const float* Xt,
+                                  const float* w, const int* series_T, const double* scales,
+                                  double* out);
+hipError_t comp_launch_row_stats(hipStream_t stream, size_t rows, int N, const double* M,
+                                 double* mean, int* nonzero);
+}  // namespace ci
+}  // extern "C++"
+
+int ci_session_summarize_components(ci_session* s, const double* scale, const double* shift,
+                                    int32_t num_ranks, const int32_t* ranks, double* trend_mean,
+                                    double* trend_order, double* seasonal_mean, double* seasonal_order,
+                                    double* regression_mean, double* regression_order,
+                                    double* inclusion_prob, double* weight_mean, double* weight_order) {
+  if (!s || !scale || !shift || !ranks) return fail("NULL argument");
+  if (!s->ran) return fail("ci_session_summarize_components needs a finished ci_session_run");
+  const ci_problem& pb = s->pb;
+  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
+  const int K = s->o_seasonal.n ? pb.num_blocks : 0;
+  const int R = num_ranks;
+  if (R < 1 || R > ci::SUMM_MAX_RANKS)
+    return fail("num_ranks must be in [1, %d], got %d", ci::SUMM_MAX_RANKS, R);
+  for (int r = 0; r < R; ++r)
+    if (ranks[r] < 0 || ranks[r] >= N) return fail("rank %d out of range [0, %d)", ranks[r], N);
+  HIP_TRY(hipSetDevice(pb.device));
+  SummScratch& w = s->summ;
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  hipStream_t stream = s->stream;
+  double* d_scale = w.obs.p + (size_t)B * T;
+  double* d_shift = d_scale + B;
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
+  // One component at a time through the scratch: the [B*T, N] matrix in `value`, its row means in
+  // `obs` (the observations ci_session_summarize keeps there are uploaded by every call of it), its
+  // order statistics [B, R, T] in `order`.  `dst + off` of series b lies `pitch` doubles after
+  // that of series b - 1 (the seasonal outputs interleave the blocks).
+  auto reduce = [&](const double* M, double* d_mean, double* d_order, int Tc, double* mean_dst,
+                    size_t mean_pitch, double* order_dst, size_t order_pitch) -> int {
+    if (mean_dst) HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * Tc, N, M, d_mean, nullptr));
+    if (order_dst)
+      HIP_TRY(launch_select(stream, N, Tc, B * Tc, R, w.ranks.p, M, nullptr, d_order, nullptr));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (mean_dst)
+      HIP_TRY(hipMemcpy2D(mean_dst, mean_pitch * sizeof(double), d_mean, (size_t)Tc * sizeof(double),
+                          (size_t)Tc * sizeof(double), B, hipMemcpyDeviceToHost));
+    if (order_dst)
+      HIP_TRY(hipMemcpy2D(order_dst, order_pitch * sizeof(double), d_order,
+                          (size_t)R * Tc * sizeof(double), (size_t)R * Tc * sizeof(double), B,
+                          hipMemcpyDeviceToHost));
+    return 0;
+  };
+  if (trend_mean || trend_order) {
+    HIP_TRY(ci::comp_launch_gather(stream, B, N, T, 1, 0, s->o_level.p, d_scale, d_shift, w.value.p));
+    if (reduce(w.value.p, w.obs.p, w.order.p, T, trend_mean, T, trend_order, (size_t)R * T)) return 1;
+  }
+  for (int k = 0; k < K && (seasonal_mean || seasonal_order); ++k) {
+    HIP_TRY(ci::comp_launch_gather(stream, B, N, T, K, k, s->o_seasonal.p, d_scale, nullptr, w.value.p));
+    if (reduce(w.value.p, w.obs.p, w.order.p, T, seasonal_mean ? seasonal_mean + (size_t)k * T : nullptr,
+               (size_t)K * T, seasonal_order ? seasonal_order + (size_t)k * R * T : nullptr,
+               (size_t)K * R * T))
+      return 1;
+  }
+  if (P > 0 && (regression_mean || regression_order)) {
+    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p,
+                                       s->ragged ? s->series_T.p : nullptr, d_scale, w.value.p));
+    if (reduce(w.value.p, w.obs.p, w.order.p, T, regression_mean, T, regression_order, (size_t)R * T))
+      return 1;
+  }
+  if (P > 0 && (inclusion_prob || weight_mean || weight_order)) {
+    // the weights: the design columns take the place of the steps.  More columns than steps do not
+    // fit the scratch: such a call takes a buffer of its own and gives it back.
+    const size_t BP = (size_t)B * P;
+    DevBuf<double> big;
+    double *M = w.value.p, *d_mean = w.obs.p, *d_order = w.order.p;
+    int* d_count = reinterpret_cast<int*>(w.cum.p);
+    if (P > T) {
+      hipError_t e = big.alloc(BP * N + BP * R + 2 * BP);
+      if (e != hipSuccess) return fail("allocating the weight summary failed: %s", hipGetErrorString(e));
+      M = big.p; d_order = M + BP * N; d_mean = d_order + BP * R;
+      d_count = reinterpret_cast<int*>(d_mean + BP);
+    }
+    std::vector<int> count(BP);
+    auto body = [&]() -> int {
+      HIP_TRY(ci::comp_launch_gather(stream, B, N, P, 1, 0, s->o_w.p, nullptr, nullptr, M));
+      HIP_TRY(ci::comp_launch_row_stats(stream, BP, N, M, d_mean, d_count));
+      if (weight_order)
+        HIP_TRY(launch_select(stream, N, P, B * P, R, w.ranks.p, M, nullptr, d_order, nullptr));
+      HIP_TRY(hipStreamSynchronize(stream));
+      HIP_TRY(hipMemcpy(count.data(), d_count, BP * sizeof(int), hipMemcpyDeviceToHost));
+      if (weight_mean) HIP_TRY(hipMemcpy(weight_mean, d_mean, BP * sizeof(double), hipMemcpyDeviceToHost));
+      if (weight_order)
+        HIP_TRY(hipMemcpy(weight_order, d_order, BP * R * sizeof(double), hipMemcpyDeviceToHost));
+      return 0;
+    };
+    const int rc = body();
+    big.release();
+    if (rc) return rc;
+    if (inclusion_prob)
+      for (size_t e = 0; e < BP; ++e) inclusion_prob[e] = (double)count[e] / (double)N;
+  }
+  return 0;
 }
 
 extern "C++" {
