@@ -94,6 +94,17 @@ def test_argument_validation_happens_before_any_device_call():
   rc = _native.load().ci_session_create(C.byref(pb), y.ctypes.data, m.ctypes.data, None, None, prm,
                                         C.byref(h))
   assert rc != 0 and b"X is NULL" in _native.load().ci_last_error()
+  # ... and so are the checks of the staged inputs: an unmasked NaN, a non-positive prior multiplier
+  pb = _native.make_problem(T=T, P=0, has_slope=0, num_warmup=1, num_results=2)
+  ynan = y.copy()
+  ynan[0, 7] = np.nan
+  rc = _native.load().ci_session_create(C.byref(pb), ynan.ctypes.data, m.ctypes.data, None, None, prm,
+                                        C.byref(h))
+  assert rc != 0 and b"is not finite but unmasked" in _native.load().ci_last_error()
+  bad = _native.make_params([dict(spec, weights_prior_scale=0.0)])
+  rc = _native.load().ci_session_create(C.byref(pb), y.ctypes.data, m.ctypes.data, None, None, bad,
+                                        C.byref(h))
+  assert rc != 0 and b"weights_prior_scale" in _native.load().ci_last_error()
 
 
 def test_round_3_entry_points_validate_before_any_device_call():
@@ -147,6 +158,16 @@ def test_round_3_entry_points_validate_before_any_device_call():
   assert L.ci_ll_session_create2(C.byref(pb), bad, y32.ctypes.data, m.ctypes.data, None, None, 4,
                                  C.byref(h)) != 0
   assert b"weights_prior_scale" in L.ci_last_error()
+  # ci_fit_gibbs_f64 checks its staged inputs before any device call too
+  T = 20
+  y64 = np.zeros((1, T), np.float64)
+  m = np.zeros((1, T), np.uint8)
+  pb = _native.make_problem(T=T, P=0, has_slope=0, num_warmup=1, num_results=2)
+  assert L.ci_fit_gibbs_f64(C.byref(pb), y64.ctypes.data, m.ctypes.data, None, None, bad, C.byref(out)) != 0
+  assert b"weights_prior_scale" in L.ci_last_error()
+  y64[0, 7] = np.nan
+  assert L.ci_fit_gibbs_f64(C.byref(pb), y64.ctypes.data, m.ctypes.data, None, None, prm, C.byref(out)) != 0
+  assert b"is not finite but unmasked" in L.ci_last_error()
 
 
 def test_make_params_fills_every_member_by_name():

@@ -1,6 +1,5 @@
-// ci_comm.h -- chain gather / diagnostics collectives behind the C-ABI (ci_comm_*), no PyTorch.
+// ci_comm.hip -- chain gather / diagnostics collectives behind the C-ABI (ci_comm_*), no PyTorch.
 //
-// Included at the end of ci_api.hip (it needs ci_session / ci_ll_session, fail(), DevBuf).
 // The reference has no communication at all (one chain, one process); chains
 // are independent, so the fit itself never communicates.  After the fit:
 //   * all-gather of per-chain result blocks that are still RESIDENT IN HBM (pooled summaries),
@@ -11,7 +10,6 @@
 //   CI_COMM_HOST  a POSIX shared-memory segment on one node: for ranks that SHARE a device (RCCL
 //                 refuses two ranks on one GPU: "Duplicate GPU detected") and for GPU-less tests of
 //                 the launcher; device-resident blocks are staged through the host.
-#pragma once
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <sched.h>
@@ -20,7 +18,17 @@
 #include <time.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cerrno>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "ci_session.h"
 
 namespace {
 
@@ -310,8 +318,8 @@ int host_all_reduce(ci_comm* c, double* v, size_t n, int op) {
 }
 
 int comm_scratch(ci_comm* c, size_t send_bytes, size_t recv_bytes) {
-  if (c->send.n < send_bytes) { c->send.release(); HIP_TRY(c->send.alloc(send_bytes)); }
-  if (c->recv.n < recv_bytes) { c->recv.release(); HIP_TRY(c->recv.alloc(recv_bytes)); }
+  if (c->send.n < send_bytes) HIP_TRY(c->send.alloc(send_bytes));
+  if (c->recv.n < recv_bytes) HIP_TRY(c->recv.alloc(recv_bytes));
   return 0;
 }
 
@@ -358,8 +366,6 @@ int ci_comm_unique_id(int32_t transport, uint8_t* id) {
   close(fd);
   return 0;
 }
-
-int ci_comm_destroy(ci_comm* c);
 
 int ci_comm_create(int32_t transport, const uint8_t* id, int32_t rank, int32_t world, int32_t device,
                    ci_comm** out) {
@@ -453,43 +459,36 @@ int ci_comm_all_gather(ci_comm* c, const void* send, void* recv, int64_t bytes) 
   return 0;
 }
 
+// The resident array a CI_FIELD_* names (null: no such field).
+static const DevBuf<float>* field_of(const OutBufs<float>& o, int32_t field) {
+  switch (field) {
+    case CI_FIELD_OBSERVATION_NOISE_SCALE: return &o.obs;
+    case CI_FIELD_LEVEL_SCALE: return &o.lscale;
+    case CI_FIELD_SLOPE_SCALE: return &o.sscale;
+    case CI_FIELD_SEASONAL_DRIFT_SCALES: return &o.drift;
+    case CI_FIELD_WEIGHTS: return &o.w;
+    case CI_FIELD_LEVEL: return &o.level;
+    case CI_FIELD_SLOPE: return &o.slope;
+    case CI_FIELD_SEASONAL_LEVELS: return &o.seasonal;
+    case CI_FIELD_POSTERIOR_MEANS: return &o.pm;
+    case CI_FIELD_POSTERIOR_TRAJECTORIES: return &o.traj;
+    default: return nullptr;
+  }
+}
+
 int ci_comm_session_all_gather(ci_comm* c, ci_session* s, int32_t field, float* recv) {
   if (!c || !s) return fail("NULL argument");
   if (!s->ran) return fail("ci_comm_session_all_gather needs a finished ci_session_run");
-  const DevBuf<float>* b = nullptr;
-  switch (field) {
-    case CI_FIELD_OBSERVATION_NOISE_SCALE: b = &s->o_obs; break;
-    case CI_FIELD_LEVEL_SCALE: b = &s->o_lscale; break;
-    case CI_FIELD_SLOPE_SCALE: b = &s->o_sscale; break;
-    case CI_FIELD_SEASONAL_DRIFT_SCALES: b = &s->o_drift; break;
-    case CI_FIELD_WEIGHTS: b = &s->o_w; break;
-    case CI_FIELD_LEVEL: b = &s->o_level; break;
-    case CI_FIELD_SLOPE: b = &s->o_slope; break;
-    case CI_FIELD_SEASONAL_LEVELS: b = &s->o_seasonal; break;
-    case CI_FIELD_POSTERIOR_MEANS: b = &s->o_pm; break;
-    case CI_FIELD_POSTERIOR_TRAJECTORIES: b = &s->o_traj; break;
-    default: return fail("unknown field %d", field);
-  }
+  const DevBuf<float>* b = field_of(s->outputs(), field);
+  if (!b) return fail("unknown field %d", field);
   return gather_device_floats(c, b->p, b->n, recv, s->pb.device);
 }
 
 int ci_comm_ll_session_all_gather(ci_comm* c, ci_ll_session* s, int32_t field, float* recv) {
   if (!c || !s) return fail("NULL argument");
   if (!s->h_ran) return fail("ci_comm_ll_session_all_gather needs a finished ci_ll_session_hmc_run");
-  const DevBuf<float>* b = nullptr;
-  switch (field) {
-    case CI_FIELD_OBSERVATION_NOISE_SCALE: b = &s->h_obs; break;
-    case CI_FIELD_LEVEL_SCALE: b = &s->h_lscale; break;
-    case CI_FIELD_SLOPE_SCALE: b = &s->h_sscale; break;
-    case CI_FIELD_SEASONAL_DRIFT_SCALES: b = &s->h_drift; break;
-    case CI_FIELD_SEASONAL_LEVELS: b = &s->h_seasonal; break;
-    case CI_FIELD_WEIGHTS: b = &s->h_w; break;
-    case CI_FIELD_LEVEL: b = &s->h_level; break;
-    case CI_FIELD_SLOPE: b = &s->h_slope; break;
-    case CI_FIELD_POSTERIOR_MEANS: b = &s->h_pm; break;
-    case CI_FIELD_POSTERIOR_TRAJECTORIES: b = &s->h_traj; break;
-    default: return fail("field %d is not part of an HMC fit", field);
-  }
+  const DevBuf<float>* b = field_of(s->outputs(), field);
+  if (!b) return fail("field %d is not part of an HMC fit", field);
   return gather_device_floats(c, b->p, b->n, recv, s->device);
 }
 
@@ -504,9 +503,10 @@ int ci_comm_destroy(ci_comm* c) {
     const bool wedged = c->dead && c->nc != nullptr;
     if (!wedged) {
       if (c->nc && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c->nc);
-      c->send.release();
-      c->recv.release();
       if (c->stream) (void)hipStreamDestroy(c->stream);
+    } else {
+      c->send.p = nullptr;       // (the leak: `delete c` below must not hand them to the pool)
+      c->recv.p = nullptr;
     }
   } else if (c->hdr) {
     munmap((void*)c->hdr, c->map_bytes);

@@ -1,5 +1,5 @@
 // Instantiation unit of the component-summary kernels (ci_components.h) and their launches;
-// ci_session_summarize_components (ci_api.hip) calls these.
+// ci_session_summarize_components (ci_summary.hip) calls these.
 #include "ci_components.h"
 
 namespace ci {

@@ -6,6 +6,7 @@
 #include "ci_kernels.h"
 #include "ci_kernels8.h"
 #include "ci_hmc.h"
+#include "ci_inst.h"
 
 #ifndef CI_D
 #error "define CI_D"
@@ -17,11 +18,11 @@
 #define CI_CAT_(a, b, c, d) a##b##c##d
 #define CI_CAT(a, b, c, d) CI_CAT_(a, b, c, d)
 
-extern "C" {
+namespace {
 
 // Returns the device-function handle of gibbs_kernel<CI_D, CI_L, pm[, profiled]>: pm + 8 selects the
 // variant instrumented with per-phase cycle counters (ci_session_profile).
-void* CI_CAT(ci_gibbs_fn_d, CI_D, _l, CI_L)(int pm) {
+void* gibbs_fn(int pm) {
   if (pm == 0) return (void*)(&ci::gibbs_kernel<CI_D, CI_L, 0, false>);
   if (pm == 1) return (void*)(&ci::gibbs_kernel<CI_D, CI_L, 1, false>);
   if (pm == 2) return (void*)(&ci::gibbs_kernel<CI_D, CI_L, 2, false>);
@@ -40,7 +41,7 @@ void* CI_CAT(ci_gibbs_fn_d, CI_D, _l, CI_L)(int pm) {
 // The eight-wavefront latency build of the register-resident kernels (ci_kernels8.h).  xg = 0: the
 // design copied to LDS (*lds_base = its LDS bytes without the design, + P * 256 * L * 4 for it);
 // xg = 1: the design read from L2 (*lds_base = everything).
-void* CI_CAT(ci_gibbs8_fn_d, CI_D, _l, CI_L)(int profiled, int xg, size_t* lds_base) {
+void* gibbs8_fn(int profiled, int xg, size_t* lds_base) {
   if (lds_base) *lds_base = ci::Lay8<CI_D, CI_L>::off_x;
   if (xg) {
 #if CI_L >= 8
@@ -61,7 +62,7 @@ void* CI_CAT(ci_gibbs8_fn_d, CI_D, _l, CI_L)(int profiled, int xg, size_t* lds_b
 }
 
 // Launches the one-draw Durbin-Koopman test kernel on the default stream.
-void CI_CAT(ci_launch_dk_d, CI_D, _l, CI_L)(int T, const float* resid, const uint8_t* mask, float H,
+void launch_dk(int T, const float* resid, const uint8_t* mask, float H,
                                            float sig0, float sig1, float a1, float p10, float p11,
                                            uint32_t k0, uint32_t k1, uint32_t chain, uint32_t iter,
                                            float* out) {
@@ -82,7 +83,7 @@ void CI_CAT(ci_launch_dk_d, CI_D, _l, CI_L)(int T, const float* resid, const uin
 }
 
 // Launches the log-likelihood kernel for E parameter sets on `stream`.
-void CI_CAT(ci_launch_loglik_d, CI_D, _l, CI_L)(int T, int P, int E, const float* y,
+void launch_loglik(int T, int P, int E, const float* y,
                                                const uint8_t* mask, const float* Xt,
                                                const double* theta, float a1, float p10,
                                                float p11, double* out, hipStream_t stream) {
@@ -90,7 +91,7 @@ void CI_CAT(ci_launch_loglik_d, CI_D, _l, CI_L)(int T, int P, int E, const float
                      mask, Xt, theta, a1, p10, p11, out);
 }
 
-void CI_CAT(ci_launch_llgrad_d, CI_D, _l, CI_L)(int T, int P, int E, const float* y,
+void launch_llgrad(int T, int P, int E, const float* y,
                                                const uint8_t* mask, const float* Xt,
                                                const double* theta, float a1, float p10,
                                                float p11, double* out_ll, double* out_grad,
@@ -100,7 +101,7 @@ void CI_CAT(ci_launch_llgrad_d, CI_D, _l, CI_L)(int T, int P, int E, const float
                      y, mask, Xt, theta, a1, p10, p11, out_ll, out_grad);
 }
 
-void CI_CAT(ci_launch_latents_d, CI_D, _l, CI_L)(int T, int P, int E, const float* y,
+void launch_latents(int T, int P, int E, const float* y,
                                                 const uint8_t* mask, const float* Xt,
                                                 const double* theta, float a1, float p10,
                                                 float p11, uint32_t k0, uint32_t k1,
@@ -118,7 +119,7 @@ void CI_CAT(ci_launch_latents_d, CI_D, _l, CI_L)(int T, int P, int E, const floa
 }
 
 // Runs the on-device HMC fit: one workgroup per (series, chain).
-void CI_CAT(ci_launch_hmc_d, CI_D, _l, CI_L)(const ci::HmcArgs* args, hipStream_t stream) {
+void launch_hmc(const ci::HmcArgs* args, hipStream_t stream) {
   ci::HmcArgs a = *args;
   const size_t with_x = ci::hmc_lds_bytes(a.P, ci::NT * CI_L);
   a.x_in_lds = (a.P > 0 && with_x <= 150 * 1024) ? 1 : 0;
@@ -134,4 +135,10 @@ void CI_CAT(ci_launch_hmc_d, CI_D, _l, CI_L)(const ci::HmcArgs* args, hipStream_
   }
 }
 
-}  // extern "C"
+}  // namespace
+
+extern "C" const CiInst* CI_CAT(ci_inst_d, CI_D, _l, CI_L)(void) {
+  static const CiInst inst = {gibbs_fn,      gibbs8_fn,      launch_dk, launch_loglik,
+                              launch_llgrad, launch_latents, launch_hmc};
+  return &inst;
+}

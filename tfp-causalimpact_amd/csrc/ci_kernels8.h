@@ -3,7 +3,7 @@
 // X resident in LDS).  Same sampler, same random stream, the same arithmetic in the same order as
 // gibbs_kernel<D, L, 1> (ci_kernels.h) -- both call the same functions for everything that
 // rounds, and the library is built with -ffp-contract=on -- so every draw of the two kernels is
-// bit-identical (tests/test_gpu_gibbs.py) and the dispatch by launch size in ci_api.hip never
+// bit-identical (tests/test_gpu_gibbs.py) and the dispatch by launch size in ci_gibbs.hip never
 // changes a result.  What changes is WHO computes WHAT WHEN.
 //
 //   waves 0-3  TIME waves: thread i owns the L consecutive steps [iL, (i+1)L) -- targets, the

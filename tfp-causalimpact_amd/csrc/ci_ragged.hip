@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ci_kernels.h"
+#include "ci_inst.h"
 
 #ifndef CI_D
 #error "define CI_D"
@@ -16,11 +17,11 @@
 #define CI_CAT_(a, b, c, d) a##b##c##d
 #define CI_CAT(a, b, c, d) CI_CAT_(a, b, c, d)
 
-extern "C" {
+namespace {
 
 // The device-function handle of gibbs_kernel<CI_D, CI_L, pm, false, true> (pm as in ci_inst.hip;
 // there is no instrumented ragged build).
-void* CI_CAT(ci_gibbs_ragged_fn_d, CI_D, _l, CI_L)(int pm) {
+void* gibbs_fn(int pm) {
   if (pm == 0) return (void*)(&ci::gibbs_kernel<CI_D, CI_L, 0, false, true>);
   if (pm == 1) return (void*)(&ci::gibbs_kernel<CI_D, CI_L, 1, false, true>);
   if (pm == 2) return (void*)(&ci::gibbs_kernel<CI_D, CI_L, 2, false, true>);
@@ -30,4 +31,9 @@ void* CI_CAT(ci_gibbs_ragged_fn_d, CI_D, _l, CI_L)(int pm) {
   return nullptr;
 }
 
-}  // extern "C"
+}  // namespace
+
+extern "C" const CiRaggedInst* CI_CAT(ci_ragged_inst_d, CI_D, _l, CI_L)(void) {
+  static const CiRaggedInst inst = {gibbs_fn};
+  return &inst;
+}

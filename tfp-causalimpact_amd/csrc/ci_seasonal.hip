@@ -6,6 +6,7 @@
 #include "ci_seasonal.h"
 #include "ci_score_seq.h"
 #include "ci_gibbs64.h"
+#include "ci_inst.h"
 
 extern "C" void* ci_gibbs_seasonal_fn(int which) {
   switch (which) {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ci_seasonal.h"
+#include "ci_inst.h"
 
 extern "C" void* ci_gibbs_seasonal_mw_fn(int which) {
   switch (which) {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ci_seasonal_tp.h"
+#include "ci_inst.h"
 
 #ifndef CI_TP_NQ
 #error "compile with -DCI_TP_NQ=2..8"
@@ -12,6 +13,7 @@
 #define CI_TP_CAT2(a, b) a##b
 #define CI_TP_CAT(a, b) CI_TP_CAT2(a, b)
 
-extern "C" void* CI_TP_CAT(ci_gibbs_seasonal_tp_fn_nq, CI_TP_NQ)(void) {
-  return (void*)&ci::gibbs_seasonal_tp_kernel<CI_TP_NQ>;
+extern "C" const CiKernelInst* CI_TP_CAT(ci_seasonal_tp_inst_nq, CI_TP_NQ)(void) {
+  static const CiKernelInst inst = {(void*)&ci::gibbs_seasonal_tp_kernel<CI_TP_NQ>};
+  return &inst;
 }

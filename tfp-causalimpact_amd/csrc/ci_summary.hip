@@ -1,0 +1,262 @@
+// ci_summary.hip -- the on-device summaries behind the C-ABI (kernels: ci_summary.h,
+// ci_components.h): ci_session_summarize, ci_session_summarize_components,
+// ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] on
+// draws the caller hands in.
+#include <vector>
+
+#include "ci_session.h"
+#include "ci_summary.h"
+
+static int check_ranks(int32_t num_ranks, const int32_t* ranks, int N) {
+  if (num_ranks < 1 || num_ranks > ci::SUMM_MAX_RANKS)
+    return fail("num_ranks must be in [1, %d], got %d", ci::SUMM_MAX_RANKS, num_ranks);
+  for (int r = 0; r < num_ranks; ++r)
+    if (ranks[r] < 0 || ranks[r] >= N) return fail("rank %d out of range [0, %d)", ranks[r], N);
+  return 0;
+}
+
+// Order statistics of the rows of two [rows, N] matrices in one launch (M1 may be NULL: one
+// matrix); out[(row / T) * R + r][row % T].  Rows of up to 16384 values (every fit_causalimpact
+// shape: N = chains x draws) are selected from registers; longer rows by the L2 digit sweeps of
+// summ_select_kernel.
+#ifndef CI_SEL_NT
+#define CI_SEL_NT 256
+#endif
+static hipError_t launch_select(hipStream_t stream, int N, int T, int rows, int R, const int* d_ranks,
+                                const double* M0, const double* M1, double* out0, double* out1) {
+  const int grid = M1 ? 2 * rows : rows;
+  if (N <= 8192) {
+    hipLaunchKernelGGL((ci::summ_select_reg_kernel<CI_SEL_NT, 8192 / CI_SEL_NT>), dim3(grid),
+                       dim3(CI_SEL_NT), 0, stream, N, T, R, rows, d_ranks, M0, M1, out0, out1);
+  } else if (N <= 16384) {
+    hipLaunchKernelGGL((ci::summ_select_reg_kernel<512, 32>), dim3(grid), dim3(512), 0, stream,
+                       N, T, R, rows, d_ranks, M0, M1, out0, out1);
+  } else {
+    hipLaunchKernelGGL(ci::summ_select_kernel, dim3(rows), dim3(256), 0, stream, N, T, R, d_ranks,
+                       M0, out0);
+    if (M1)
+      hipLaunchKernelGGL(ci::summ_select_kernel, dim3(rows), dim3(256), 0, stream, N, T, R, d_ranks,
+                         M1, out1);
+  }
+  return hipGetLastError();
+}
+
+// The scratch of a summary of B series of N draws over T steps: allocated on first use and kept
+// (ci_session_summarize and ci_session_summarize_components share it).
+static int summ_scratch_alloc(SummScratch& w, int B, int T, int N) {
+  if (w.value.p) return 0;
+  const size_t BTN = (size_t)B * T * N;
+  HIP_TRY(w.value.alloc(BTN));
+  HIP_TRY(w.cum.alloc(BTN));
+  HIP_TRY(w.obs.alloc((size_t)B * T + 2 * B));
+  HIP_TRY(w.flags.alloc((size_t)B * T));
+  HIP_TRY(w.ranks.alloc(ci::SUMM_MAX_RANKS));
+  HIP_TRY(w.order.alloc((size_t)2 * B * ci::SUMM_MAX_RANKS * T));
+  HIP_TRY(w.draw.alloc((size_t)B * 2 * N + (size_t)B * 2 * ci::SUMM_MAX_RANKS));
+  return 0;
+}
+
+// The summary of B series' [B, N, T] trajectories resident in HBM (ci_session_summarize,
+// ci_ll_session_hmc_summarize; ci_summarize_draws after its upload): transpose with value = trajectory * scale + shift, running sums,
+// order statistics; the scratch is allocated on first use and kept.
+template <class TIn>
+static int summarize_resident(hipStream_t stream, SummScratch& w, int B, int T, int N, const TIn* traj,
+                              const double* scale, const double* shift, const double* observed,
+                              const uint8_t* flags, int32_t num_ranks, const int32_t* ranks,
+                              double* value_order, double* cum_order, double* per_draw,
+                              double* per_draw_order) {
+  if (check_ranks(num_ranks, ranks, N)) return 1;
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  double* d_scale = w.obs.p + (size_t)B * T;
+  double* d_shift = d_scale + B;
+  HIP_TRY(hipMemcpyAsync(w.obs.p, observed, (size_t)B * T * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(w.flags.p, flags, (size_t)B * T, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, num_ranks * sizeof(int), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(ci::summ_transpose_kernel<TIn>, dim3((T + 63) / 64, (N + 63) / 64, B), dim3(64, 4), 0,
+                     stream, N, T, traj, d_scale, d_shift, w.value.p);
+  hipLaunchKernelGGL(ci::summ_cumsum_kernel, dim3((N + 63) / 64, B), dim3(64), 0, stream, N, T,
+                     w.value.p, w.obs.p, w.flags.p, w.cum.p, w.draw.p);
+  double* ord_value = w.order.p;
+  double* ord_cum = w.order.p + (size_t)B * ci::SUMM_MAX_RANKS * T;
+  HIP_TRY(launch_select(stream, N, T, B * T, num_ranks, w.ranks.p, w.value.p, w.cum.p,
+                        ord_value, ord_cum));
+  double* ord_draw = w.draw.p + (size_t)B * 2 * N;
+  if (per_draw_order)
+    HIP_TRY(launch_select(stream, N, 1, 2 * B, num_ranks, w.ranks.p, w.draw.p, nullptr,
+                          ord_draw, nullptr));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(stream));
+  const size_t ord_bytes = (size_t)B * num_ranks * T * sizeof(double);
+  if (value_order) HIP_TRY(hipMemcpy(value_order, ord_value, ord_bytes, hipMemcpyDeviceToHost));
+  if (cum_order) HIP_TRY(hipMemcpy(cum_order, ord_cum, ord_bytes, hipMemcpyDeviceToHost));
+  if (per_draw)
+    HIP_TRY(hipMemcpy(per_draw, w.draw.p, (size_t)B * 2 * N * sizeof(double), hipMemcpyDeviceToHost));
+  if (per_draw_order)
+    HIP_TRY(hipMemcpy(per_draw_order, ord_draw, (size_t)B * 2 * num_ranks * sizeof(double),
+                      hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The launches of ci_components.hip (kernels: ci_components.h).
+namespace ci {
+hipError_t comp_launch_gather(hipStream_t stream, int B, int N, int T, int K, int k, const float* in,
+                              const double* scales, const double* shifts, double* out);
+hipError_t comp_launch_regression(hipStream_t stream, int B, int N, int T, int P, const float* Xt,
+                                  const float* w, const int* series_T, const double* scales,
+                                  double* out);
+hipError_t comp_launch_row_stats(hipStream_t stream, size_t rows, int N, const double* M,
+                                 double* mean, int* nonzero);
+}  // namespace ci
+
+// ci_summarize_draws / ci_summarize_draws_f64: one series of draws from the host, uploaded into a
+// scratch of its own, summarised on the null stream and given back.
+template <class TIn>
+static int summarize_draws_impl(int32_t device, int32_t num_draws, int32_t T, const TIn* trajectories,
+                                double scale, double shift, const double* observed, const uint8_t* flags,
+                                int32_t num_ranks, const int32_t* ranks, double* value_order,
+                                double* cum_order, double* per_draw, double* per_draw_order) {
+  if (!trajectories || !observed || !flags || !ranks) return fail("NULL argument");
+  if (num_draws < 1 || T < 1) return fail("need num_draws >= 1 and T >= 1");
+  if (check_ranks(num_ranks, ranks, num_draws)) return 1;
+  HIP_TRY(hipSetDevice(device));
+  const size_t TN = (size_t)T * num_draws;
+  DevBuf<TIn> d_traj;
+  SummScratch w;
+  HIP_TRY(d_traj.alloc(TN));
+  HIP_TRY(hipMemcpy(d_traj.p, trajectories, TN * sizeof(TIn), hipMemcpyHostToDevice));
+  return summarize_resident<TIn>(nullptr, w, 1, T, num_draws, d_traj.p, &scale, &shift, observed, flags,
+                                 num_ranks, ranks, value_order, cum_order, per_draw, per_draw_order);
+}
+
+extern "C" {
+
+int ci_session_summarize(ci_session* s, const double* scale, const double* shift,
+                         const double* observed, const uint8_t* flags, int32_t num_ranks,
+                         const int32_t* ranks, double* value_order, double* cum_order,
+                         double* per_draw, double* per_draw_order) {
+  if (!s || !scale || !shift || !observed || !flags || !ranks) return fail("NULL argument");
+  if (!s->ran) return fail("ci_session_summarize needs a finished ci_session_run");
+  const ci_problem& pb = s->pb;
+  HIP_TRY(hipSetDevice(pb.device));
+  return summarize_resident(s->stream, s->summ, pb.num_series, pb.T, pb.num_chains * pb.num_results,
+                            s->o_traj.p, scale, shift, observed, flags, num_ranks, ranks, value_order,
+                            cum_order, per_draw, per_draw_order);
+}
+
+int ci_session_summarize_components(ci_session* s, const double* scale, const double* shift,
+                                    int32_t num_ranks, const int32_t* ranks, double* trend_mean,
+                                    double* trend_order, double* seasonal_mean, double* seasonal_order,
+                                    double* regression_mean, double* regression_order,
+                                    double* inclusion_prob, double* weight_mean, double* weight_order) {
+  if (!s || !scale || !shift || !ranks) return fail("NULL argument");
+  if (!s->ran) return fail("ci_session_summarize_components needs a finished ci_session_run");
+  const ci_problem& pb = s->pb;
+  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
+  const int K = s->o_seasonal.n ? pb.num_blocks : 0;
+  const int R = num_ranks;
+  if (check_ranks(R, ranks, N)) return 1;
+  HIP_TRY(hipSetDevice(pb.device));
+  SummScratch& w = s->summ;
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  hipStream_t stream = s->stream;
+  double* d_scale = w.obs.p + (size_t)B * T;
+  double* d_shift = d_scale + B;
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
+  // One component at a time through the scratch: the [B*T, N] matrix in `value`, its row means in
+  // `obs` (the observations ci_session_summarize keeps there are uploaded by every call of it), its
+  // order statistics [B, R, T] in `order`.  `dst + off` of series b lies `pitch` doubles after
+  // that of series b - 1 (the seasonal outputs interleave the blocks).
+  auto reduce = [&](const double* M, double* d_mean, double* d_order, int Tc, double* mean_dst,
+                    size_t mean_pitch, double* order_dst, size_t order_pitch) -> int {
+    if (mean_dst) HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * Tc, N, M, d_mean, nullptr));
+    if (order_dst)
+      HIP_TRY(launch_select(stream, N, Tc, B * Tc, R, w.ranks.p, M, nullptr, d_order, nullptr));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (mean_dst)
+      HIP_TRY(hipMemcpy2D(mean_dst, mean_pitch * sizeof(double), d_mean, (size_t)Tc * sizeof(double),
+                          (size_t)Tc * sizeof(double), B, hipMemcpyDeviceToHost));
+    if (order_dst)
+      HIP_TRY(hipMemcpy2D(order_dst, order_pitch * sizeof(double), d_order,
+                          (size_t)R * Tc * sizeof(double), (size_t)R * Tc * sizeof(double), B,
+                          hipMemcpyDeviceToHost));
+    return 0;
+  };
+  if (trend_mean || trend_order) {
+    HIP_TRY(ci::comp_launch_gather(stream, B, N, T, 1, 0, s->o_level.p, d_scale, d_shift, w.value.p));
+    if (reduce(w.value.p, w.obs.p, w.order.p, T, trend_mean, T, trend_order, (size_t)R * T)) return 1;
+  }
+  for (int k = 0; k < K && (seasonal_mean || seasonal_order); ++k) {
+    HIP_TRY(ci::comp_launch_gather(stream, B, N, T, K, k, s->o_seasonal.p, d_scale, nullptr, w.value.p));
+    if (reduce(w.value.p, w.obs.p, w.order.p, T, seasonal_mean ? seasonal_mean + (size_t)k * T : nullptr,
+               (size_t)K * T, seasonal_order ? seasonal_order + (size_t)k * R * T : nullptr,
+               (size_t)K * R * T))
+      return 1;
+  }
+  if (P > 0 && (regression_mean || regression_order)) {
+    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p,
+                                       s->ragged ? s->series_T.p : nullptr, d_scale, w.value.p));
+    if (reduce(w.value.p, w.obs.p, w.order.p, T, regression_mean, T, regression_order, (size_t)R * T))
+      return 1;
+  }
+  if (P > 0 && (inclusion_prob || weight_mean || weight_order)) {
+    // the weights: the design columns take the place of the steps.  More columns than steps do not
+    // fit the scratch: such a call takes a buffer of its own and gives it back.
+    const size_t BP = (size_t)B * P;
+    DevBuf<double> big;
+    double *M = w.value.p, *d_mean = w.obs.p, *d_order = w.order.p;
+    int* d_count = reinterpret_cast<int*>(w.cum.p);
+    if (P > T) {
+      hipError_t e = big.alloc(BP * N + BP * R + 2 * BP);
+      if (e != hipSuccess) return fail("allocating the weight summary failed: %s", hipGetErrorString(e));
+      M = big.p; d_order = M + BP * N; d_mean = d_order + BP * R;
+      d_count = reinterpret_cast<int*>(d_mean + BP);
+    }
+    std::vector<int> count(BP);
+    HIP_TRY(ci::comp_launch_gather(stream, B, N, P, 1, 0, s->o_w.p, nullptr, nullptr, M));
+    HIP_TRY(ci::comp_launch_row_stats(stream, BP, N, M, d_mean, d_count));
+    if (weight_order)
+      HIP_TRY(launch_select(stream, N, P, B * P, R, w.ranks.p, M, nullptr, d_order, nullptr));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy(count.data(), d_count, BP * sizeof(int), hipMemcpyDeviceToHost));
+    if (weight_mean) HIP_TRY(hipMemcpy(weight_mean, d_mean, BP * sizeof(double), hipMemcpyDeviceToHost));
+    if (weight_order)
+      HIP_TRY(hipMemcpy(weight_order, d_order, BP * R * sizeof(double), hipMemcpyDeviceToHost));
+    if (inclusion_prob)
+      for (size_t e = 0; e < BP; ++e) inclusion_prob[e] = (double)count[e] / (double)N;
+  }
+  return 0;
+}
+
+int ci_summarize_draws(int32_t device, int32_t num_draws, int32_t T, const float* trajectories,
+                       double scale, double shift, const double* observed, const uint8_t* flags,
+                       int32_t num_ranks, const int32_t* ranks, double* value_order,
+                       double* cum_order, double* per_draw, double* per_draw_order) {
+  return summarize_draws_impl<float>(device, num_draws, T, trajectories, scale, shift, observed, flags,
+                                     num_ranks, ranks, value_order, cum_order, per_draw, per_draw_order);
+}
+
+int ci_summarize_draws_f64(int32_t device, int32_t num_draws, int32_t T, const double* trajectories,
+                           double scale, double shift, const double* observed, const uint8_t* flags,
+                           int32_t num_ranks, const int32_t* ranks, double* value_order,
+                           double* cum_order, double* per_draw, double* per_draw_order) {
+  return summarize_draws_impl<double>(device, num_draws, T, trajectories, scale, shift, observed, flags,
+                                      num_ranks, ranks, value_order, cum_order, per_draw, per_draw_order);
+}
+
+int ci_ll_session_hmc_summarize(ci_ll_session* s, const double* scale, const double* shift,
+                                const double* observed, const uint8_t* flags, int32_t num_ranks,
+                                const int32_t* ranks, double* value_order, double* cum_order,
+                                double* per_draw, double* per_draw_order) {
+  if (!s || !scale || !shift || !observed || !flags || !ranks) return fail("NULL argument");
+  if (!s->h_ran) return fail("ci_ll_session_hmc_summarize needs a finished ci_ll_session_hmc_run");
+  HIP_TRY(hipSetDevice(s->device));
+  return summarize_resident(s->stream, s->summ, s->B, s->T, s->h_C * s->h_S, s->h_traj.p, scale, shift,
+                            observed, flags, num_ranks, ranks, value_order, cum_order, per_draw,
+                            per_draw_order);
+}
+
+}  // extern "C"

@@ -5,10 +5,12 @@
 
 #define CI_SEASONAL_DECL_ONLY
 #include "ci_wide.h"
+#include "ci_inst.h"
 
 #define CI_CAT_(a, b, c, d) a##b##c##d
 #define CI_CAT(a, b, c, d) CI_CAT_(a, b, c, d)
 
-extern "C" void* CI_CAT(ci_gibbs_wide_bigp_fn_tr, CI_TR, _ns, CI_NS)(void) {
-  return (void*)(&ci::gibbs_wide_kernel<CI_TR, CI_NS, true>);
+extern "C" const CiKernelInst* CI_CAT(ci_wide_bigp_inst_tr, CI_TR, _ns, CI_NS)(void) {
+  static const CiKernelInst inst = {(void*)(&ci::gibbs_wide_kernel<CI_TR, CI_NS, true>)};
+  return &inst;
 }

@@ -7,11 +7,13 @@
 
 #define CI_SEASONAL_DECL_ONLY
 #include "ci_wide.h"
+#include "ci_inst.h"
 
 #define CI_CAT_(a, b, c, d) a##b##c##d
 #define CI_CAT(a, b, c, d) CI_CAT_(a, b, c, d)
 
 // The device-function handle of gibbs_wide_kernel<CI_TR, CI_NS, false, true> (<= 52 design columns).
-extern "C" void* CI_CAT(ci_gibbs_wide_ragged_fn_tr, CI_TR, _ns, CI_NS)(void) {
-  return (void*)(&ci::gibbs_wide_kernel<CI_TR, CI_NS, false, true>);
+extern "C" const CiKernelInst* CI_CAT(ci_wide_ragged_inst_tr, CI_TR, _ns, CI_NS)(void) {
+  static const CiKernelInst inst = {(void*)(&ci::gibbs_wide_kernel<CI_TR, CI_NS, false, true>)};
+  return &inst;
 }
