@@ -48,6 +48,25 @@ def test_prepare_batch_equals_causal_impact_data(standardize):
   assert list(idx[prep.model_rows]) == list(idx[5:])
 
 
+def test_prepared_batch_observed_and_flags_are_the_single_series_request():
+  """What the device summary of a batch is asked for -- the data-scale outcome with the gap and
+  the tail as NaN, and the window flags the series share -- is `_device_summary_request` of every
+  series: a gap between the periods, a tail after the post-period, a missing post-period outcome."""
+  B, T, alpha = 3, 30, 0.05
+  frames = _frames(B, T, 1, seed=2)
+  frames[2].iloc[24, 0] = np.nan                          # missing in the post-period
+  idx = frames[0].index
+  pre, post = (idx[0], idx[17]), (idx[21], idx[26])       # gap: rows 18-20; tail: rows 27-29
+  prep = batch.prepare_batch(np.stack([f.to_numpy(float) for f in frames]), idx, pre, post)
+  assert prep.observed.shape == (B, T) and prep.flags.shape == (T,) and prep.flags.dtype == np.uint8
+  for b, f in enumerate(frames):
+    rq = lib._device_summary_request(cid.CausalImpactData(f, pre, post), alpha)   # pylint: disable=protected-access
+    np.testing.assert_array_equal(prep.observed[b], rq["observed"])
+    np.testing.assert_array_equal(prep.flags, rq["flags"])
+  assert np.isnan(prep.observed[:, 18:21]).all() and np.isnan(prep.observed[:, 27:]).all()
+  assert np.isnan(prep.observed[2, 24]) and not np.isnan(prep.observed[:2, 21:27]).any()
+
+
 def test_prepare_batch_rejects_what_the_reference_rejects():
   T = 40
   v = np.random.default_rng(0).normal(size=(2, T, 2))
@@ -101,6 +120,27 @@ def test_batch_fit_equals_separate_fits(p, dates):
                                     inference_options=opts)
   assert not np.allclose(twins.summary.loc[0].to_numpy(float), twins.summary.loc[1].to_numpy(float),
                          rtol=1e-6)
+
+
+@pytest.mark.gpu
+def test_gibbs_batch_sharded_over_devices_equals_one_launch():
+  """Series are keyed by their position in the batch, so cutting the batch into launches (here:
+  device 0 twice, shards of 3 and 2) changes nothing, bit for bit."""
+  T, B = 40, 5
+  frames = _frames(B, T, 1, seed=20)
+  idx = frames[0].index
+  pre, post = (idx[0], idx[27]), (idx[30], idx[39])
+  kw = dict(num_chains=2, num_results=60, num_warmup_steps=30, components=True)
+  one = ci.fit_causalimpact_batch(frames, pre, post, seed=4,
+                                  inference_options=ci.InferenceOptions(devices=[0], **kw))
+  two = ci.fit_causalimpact_batch(frames, pre, post, seed=4,
+                                  inference_options=ci.InferenceOptions(devices=[0, 0], **kw))
+  pd.testing.assert_frame_equal(two.summary, one.summary, check_exact=True)
+  for b in (0, 2, 4):
+    pd.testing.assert_frame_equal(two[b].series, one[b].series, check_exact=True)
+    pd.testing.assert_frame_equal(two[b].components, one[b].components, check_exact=True)
+    pd.testing.assert_frame_equal(two[b].coefficients, one[b].coefficients, check_exact=True)
+  assert two.diagnostics_of(3) == one.diagnostics_of(3)
 
 
 @pytest.mark.gpu

@@ -293,3 +293,119 @@ def test_panel_refuses_bad_arguments_before_fitting():
     ci.fit_causalimpact_panel([frames[0], frames[1].rename(columns={"x0": "z"})], periods)
   with pytest.raises(ValueError, match="alpha"):
     ci.fit_causalimpact_panel(frames, periods, alpha=1.5)
+
+
+# ---- the assembler (`batch._assemble`) over a fake launch function: no device, no library ----
+
+_C, _S, _R, _P = 2, 5, 3, 1          # chains, draws per chain, order statistics, design columns
+
+
+def _fake_launch(lengths, calls):
+  """A launch function that returns what a session would, as a function of the panel position b
+  and the step t alone: base(b, t) = 1000 b + t over a series' own steps, arrays at the stride of
+  the longest series of the launch, and beyond a series' length what the device leaves there
+  (posterior_means 0, order statistics and components NaN)."""
+  lengths = np.asarray(lengths)
+
+  def run(launch):
+    calls.append(launch)
+    ids = np.asarray(launch[2])
+    T = int(lengths[ids].max())
+    t = np.arange(T)
+    own = t[None, :] < lengths[ids][:, None]                                  # [n, T]
+    base = np.where(own, 1000.0 * ids[:, None] + t[None, :], np.nan)
+    ranks, chains = np.arange(_R)[None, :, None], np.arange(_C)[None, :, None]
+    per_b = ids.astype(np.float64)
+    out = dict(posterior_means=np.nan_to_num(base[:, None, :] + 0.25 * chains).astype(np.float32),
+               observation_noise_scale=(per_b[:, None, None] + chains + 0.5 * np.arange(_S)).astype(np.float32),
+               level_scale=(per_b[:, None, None] - chains - 0.5 * np.arange(_S)).astype(np.float32))
+    dsum = dict(value_order=base[:, None, :] + 0.5 * ranks, cum_order=-base[:, None, :] - 0.5 * ranks,
+                per_draw=per_b[:, None, None] + np.arange(2 * _C * _S).reshape(1, 2, _C * _S),
+                per_draw_order=per_b[:, None, None] + np.arange(2 * _R).reshape(1, 2, _R))
+    csum = dict(trend_mean=base + 0.125, trend_order=base[:, None, :] + 2.0 * ranks,
+                regression_mean=base - 0.125, regression_order=base[:, None, :] - 2.0 * ranks,
+                inclusion_prob=per_b[:, None] + np.zeros((1, _P)),
+                weight_mean=-per_b[:, None] + np.zeros((1, _P)),
+                weight_order=per_b[:, None, None] + np.arange(_R * _P).reshape(1, _R, _P))
+    return out, dsum, csum
+
+  return run
+
+
+def _assert_assembled(got, lengths):
+  """Every series' row holds its own values over [0, T_b) and the padding beyond."""
+  means, dsum, diag, csum = got
+  B, T_max = len(lengths), max(lengths)
+  assert means.shape == (B, T_max) and means.dtype == np.float32
+  assert set(diag) == {"observation_noise_scale", "level_scale"}
+  assert all(v.shape == (B, _C, _S) for v in diag.values())
+  assert dsum["value_order"].shape == dsum["cum_order"].shape == (B, _R, T_max)
+  assert csum["trend_order"].shape == csum["regression_order"].shape == (B, _R, T_max)
+  assert csum["inclusion_prob"].shape == csum["weight_mean"].shape == (B, _P)
+  assert csum["weight_order"].shape == (B, _R, _P)
+  ranks = np.arange(_R)[:, None]
+  for b, Tb in enumerate(lengths):
+    base = 1000.0 * b + np.arange(Tb)
+    np.testing.assert_array_equal(means[b, :Tb], base + 0.125)          # the mean of two chains
+    assert (means[b, Tb:] == 0).all()
+    np.testing.assert_array_equal(dsum["value_order"][b, :, :Tb], base + 0.5 * ranks)
+    np.testing.assert_array_equal(dsum["cum_order"][b, :, :Tb], -base - 0.5 * ranks)
+    np.testing.assert_array_equal(csum["trend_mean"][b, :Tb], base + 0.125)
+    np.testing.assert_array_equal(csum["trend_order"][b, :, :Tb], base + 2.0 * ranks)
+    np.testing.assert_array_equal(csum["regression_mean"][b, :Tb], base - 0.125)
+    np.testing.assert_array_equal(csum["regression_order"][b, :, :Tb], base - 2.0 * ranks)
+    for over_time in (dsum["value_order"], dsum["cum_order"], csum["trend_mean"], csum["trend_order"],
+                      csum["regression_mean"], csum["regression_order"]):
+      assert np.isnan(over_time[b, ..., Tb:]).all()
+    np.testing.assert_array_equal(dsum["per_draw"][b], b + np.arange(2 * _C * _S).reshape(2, _C * _S))
+    np.testing.assert_array_equal(dsum["per_draw_order"][b], b + np.arange(2 * _R).reshape(2, _R))
+    np.testing.assert_array_equal(csum["inclusion_prob"][b], np.full(_P, float(b)))
+    np.testing.assert_array_equal(csum["weight_mean"][b], np.full(_P, -float(b)))
+    np.testing.assert_array_equal(csum["weight_order"][b], b + np.arange(_R * _P).reshape(_R, _P))
+    np.testing.assert_array_equal(diag["observation_noise_scale"][b],
+                                  b + np.arange(_C)[:, None] + 0.5 * np.arange(_S))
+    np.testing.assert_array_equal(diag["level_scale"][b], b - np.arange(_C)[:, None] - 0.5 * np.arange(_S))
+
+
+@pytest.mark.parametrize("devices", [[0], [0, 1]])
+@pytest.mark.parametrize("blocks,route_name,num_groups", [(0, "ragged", 1), (2, "equal_length", 3)])
+def test_assembler_puts_every_series_of_a_panel_in_its_row(blocks, route_name, num_groups, devices):
+  lengths = (7, 12, 7, 9, 12)
+  route = batch.panel_route(float64=False, standardize_data=True, sampler="gibbs",
+                            num_seasonal_blocks=blocks, P=_P, lengths=lengths)
+  assert route["route"] == route_name and len(route["groups"]) == num_groups
+  launches = batch.panel_launches(route, devices)
+  if blocks:
+    assert [ids for _, _, ids in batch.panel_launches(route, [0])] == [[0], [2], [3], [1], [4]]
+  calls = []
+  got = batch._assemble(launches, _fake_launch(lengths, calls), len(lengths), max(lengths))   # pylint: disable=protected-access
+  assert sorted(calls) == sorted(launches) and len(calls) == len(launches)
+  _assert_assembled(got, lengths)
+
+
+def test_assembler_takes_a_batch_as_one_group_and_does_not_copy_a_whole_launch():
+  B, T = 5, 6
+  route = dict(route="equal_length", groups=[(T, list(range(B)))])      # what a batch is to the assembler
+  results = {}
+
+  def run(launch, inner=_fake_launch([T] * B, [])):
+    results[tuple(launch[2])] = inner(launch)
+    return results[tuple(launch[2])]
+
+  two = batch.panel_launches(route, [0, 0])
+  assert [ids for _, _, ids in two] == [[0, 1, 2], [3, 4]]
+  split = batch._assemble(two, run, B, T)                               # pylint: disable=protected-access
+  _assert_assembled(split, [T] * B)
+  one = batch._assemble(batch.panel_launches(route, [0]), run, B, T)    # pylint: disable=protected-access
+  _assert_assembled(one, [T] * B)
+  for a, b in zip(split[1:], one[1:]):
+    assert list(a) == list(b)
+    for k in a:
+      assert a[k].dtype == b[k].dtype
+      np.testing.assert_array_equal(a[k], b[k])
+  np.testing.assert_array_equal(split[0], one[0])
+  # one launch with all B series in order at full stride: its arrays, not copies of them
+  out, dsum, csum = results[tuple(range(B))]
+  assert all(one[1][k] is dsum[k] for k in dsum) and all(one[3][k] is csum[k] for k in csum)
+  assert all(one[2][k] is out[k] for k in one[2])
+  assert not any(np.shares_memory(split[1][k], dsum[k]) for k in dsum)

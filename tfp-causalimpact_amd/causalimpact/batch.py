@@ -14,10 +14,22 @@ index and the pre/post periods (the same calendar for many geos / products):
 Random streams are keyed by (series position in the batch, chain): Monte-Carlo errors are
 independent across series; `shared_streams=True` keys them by chain only, which makes series b
 of a batch equal `fit_causalimpact` on series b alone with the same seed, draw for draw.
+
+`fit_causalimpact_panel` is the same for series with their own index, length and periods.
+
+Both fit functions are one pipeline over different preparations (`prepare_batch`, one shared
+calendar; `prepare_panel`, padded to the longest series):
+  * `_options` / `_frames_outcome_first`: defaults, argument checks, outcome-first columns;
+  * `_fit_per_series`: the routes without a one-launch kernel (float64, raw scale, most HMC);
+  * `panel_route` + `panel_launches`: which series share a launch on which device -- a batch is
+    the panel of ONE group of equal lengths, cut into consecutive positions per device;
+  * `_run_launch` (Gibbs: ordinary, ragged or ragged seasonal session) or `_run_hmc_launch`: one
+    session from creation to close, arrays back with the series axis at the launch's stride;
+  * `_assemble`: the launches of a device in turn, the devices side by side
+    (`causalimpact_lib.map_by_device`), then the [B, ..., T_max] blocks of the containers.
 """
 from __future__ import annotations
 
-import concurrent.futures
 import dataclasses
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -47,6 +59,8 @@ class PreparedBatch:
   design: Optional[np.ndarray]   # [B, T, P] standardised covariates + intercept, or None
   outcome_mean: np.ndarray    # [B] pre-period mean of the outcome (0 if not standardised)
   outcome_sd: np.ndarray      # [B] pre-period sd (ddof=1)     (1 if not standardised)
+  observed: np.ndarray        # [B, T] data-scale outcome, NaN in gap / tail (predictions only)
+  flags: np.ndarray           # [T] uint8: bit 0 = t >= treatment start, bit 1 = in the window
 
 
 def prepare_batch(values: np.ndarray, index: pd.Index, pre_period, post_period,
@@ -88,9 +102,15 @@ def prepare_batch(values: np.ndarray, index: pd.Index, pre_period, post_period,
   design = None
   if ncol > 1:
     design = np.concatenate([scaled[:, :, 1:], np.ones((B, len(rows), 1))], axis=2)
+  idx = index[rows]
+  in_post = np.asarray((idx >= post[0]) & (idx <= post[1]))
+  flags = (~np.asarray(idx < post[0])).astype(np.uint8) | (in_post.astype(np.uint8) << 1)
+  observed = values[:, rows, 0].copy()
+  observed[:, n_pre:][:, ~in_post[n_pre:]] = np.nan        # gap / tail: predictions only
   return PreparedBatch(values=values, index=index, pre_period=pre, post_period=post,
                        standardize_data=standardize_data, model_rows=rows, num_pre=n_pre, y=y,
-                       mask=mask, design=design, outcome_mean=o_mu, outcome_sd=o_sd)
+                       mask=mask, design=design, outcome_mean=o_mu, outcome_sd=o_sd,
+                       observed=observed, flags=flags)
 
 
 def summary_table(names, alpha, ranks, dsum, *, n_win, n_obs, obs_mean, obs_sum, avg_pred,
@@ -170,8 +190,17 @@ def summary_table(names, alpha, ranks, dsum, *, n_win, n_obs, obs_mean, obs_sum,
   return pd.DataFrame(data, index=index)
 
 
-# the component-summary arrays whose last axis is the design columns, not time
+# What a launch returns has the series axis first and, with these exceptions, time last: the
+# fetched draws of the scalars the diagnostics rank [B, chains, draws], the device summary's window
+# totals per draw, and the component-summary arrays whose last axis is the design columns.
+_DRAW_SCALARS = ("observation_noise_scale", "level_scale")
+_PER_DRAW = ("per_draw", "per_draw_order")
 _PER_COLUMN = ("inclusion_prob", "weight_mean", "weight_order")
+
+
+def _cut(arrays: Dict[str, np.ndarray], num_steps: int, whole=()) -> Dict[str, np.ndarray]:
+  """`arrays` with the time (last) axis cut to `num_steps`, but for the names in `whole`."""
+  return {k: (v if k in whole else v[..., :num_steps]) for k, v in arrays.items()}
 
 
 class CausalImpactBatchAnalysis:
@@ -219,63 +248,48 @@ class CausalImpactBatchAnalysis:
   def __len__(self):
     return len(self._names)
 
-  def _request(self, b: int) -> Dict:
-    p = self._prep
-    idx = p.index[p.model_rows]
-    in_post = np.asarray((idx >= p.post_period[0]) & (idx <= p.post_period[1]))
-    obs = p.values[b, p.model_rows, 0].copy()
-    obs[p.num_pre:][~in_post[p.num_pre:]] = np.nan        # gap / tail: predictions only
-    flags = (~np.asarray(idx < p.post_period[0])).astype(np.uint8) | (in_post.astype(np.uint8) << 1)
-    return dict(scale=float(p.outcome_sd[b]) if p.standardize_data else 1.0,
-                shift=float(p.outcome_mean[b]) if p.standardize_data else 0.0,
-                observed=obs, flags=flags, ranks=self._ranks,
-                quantiles=(self.alpha / 2.0, 1.0 - self.alpha / 2.0))
-
   def _build_summary(self) -> pd.DataFrame:
     """The reference's 15 summary columns (causalimpact_lib.py:934-1093) for every series at
     once: the same numpy reductions as `_summary_rows`, along axis 1 of [B, draws] arrays."""
-    p, B = self._prep, len(self)
-    rq = self._request(0)
-    win = (rq["flags"] & 2) != 0
-    n_win = int(win.sum())
-    idx = p.index[p.model_rows]
-    in_post = np.asarray((idx >= p.post_period[0]) & (idx <= p.post_period[1]))
-    obs = p.values[:, p.model_rows, 0].copy()
-    obs[:, p.num_pre:][:, ~in_post[p.num_pre:]] = np.nan
-    obs_w = obs[:, win]                                                    # [B, T_w]
-    scale = p.outcome_sd if p.standardize_data else np.ones(B)
-    shift = p.outcome_mean if p.standardize_data else np.zeros(B)
-    post_mean = (self._means.astype(np.float64) * scale[:, None] + shift[:, None])[:, win]
+    p = self._prep
+    win = (p.flags & 2) != 0
+    obs_w = p.observed[:, win]                                             # [B, T_w]
+    post_mean = (self._means.astype(np.float64) * p.outcome_sd[:, None]
+                 + p.outcome_mean[:, None])[:, win]
     n_obs = np.sum(~np.isnan(obs_w), axis=1)
     with np.errstate(invalid="ignore", divide="ignore"):
       obs_mean, obs_sum = np.nanmean(obs_w, axis=1), np.nansum(obs_w, axis=1)
-    return summary_table(self._names, self.alpha, self._ranks, self._dsum, n_win=n_win, n_obs=n_obs,
-                         obs_mean=obs_mean, obs_sum=obs_sum, avg_pred=post_mean.mean(axis=1),
-                         cum_pred=post_mean.sum(axis=1))
+    return summary_table(self._names, self.alpha, self._ranks, self._dsum, n_win=int(win.sum()),
+                         n_obs=n_obs, obs_mean=obs_mean, obs_sum=obs_sum,
+                         avg_pred=post_mean.mean(axis=1), cum_pred=post_mean.sum(axis=1))
+
+  def _series_view(self, b: int):
+    """(frame, pre_period, post_period, model steps) of series b."""
+    p = self._prep
+    return (pd.DataFrame(p.values[b], index=p.index, columns=self._columns), p.pre_period,
+            p.post_period, len(p.model_rows))
 
   def __getitem__(self, b: int) -> lib.CausalImpactAnalysis:
     b = range(len(self))[b]
     if b not in self._cache:
-      p = self._prep
-      df = pd.DataFrame(p.values[b], index=p.index, columns=self._columns)
-      ci_data = cid.CausalImpactData(df, p.pre_period, p.post_period,
-                                     standardize_data=p.standardize_data)
-      dsum = {k: v[b] for k, v in self._dsum.items()}
+      # (arrays over time are padded to the longest series of a panel: series b owns [0, Tb))
+      df, pre, post, Tb = self._series_view(b)
+      ci_data = cid.CausalImpactData(df, pre, post, standardize_data=self._prep.standardize_data)
+      dsum = _cut({k: v[b] for k, v in self._dsum.items()}, Tb, _PER_DRAW)
       rq = lib._device_summary_request(ci_data, self.alpha)   # pylint: disable=protected-access
       rq["ranks"] = self._ranks
       series, summary = lib._compute_impact_device(            # pylint: disable=protected-access
-          self._means[b], dsum, rq, ci_data, self.alpha)
+          self._means[b, :Tb], dsum, rq, ci_data, self.alpha)
       self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b),
-                                                *self._component_frames(b, ci_data))
+                                                *self._component_frames(b, ci_data, Tb))
     return self._cache[b]
 
-  def _component_frames(self, b: int, ci_data, num_steps: Optional[int] = None):
-    """(components, coefficients) of series b (its first `num_steps` steps: a panel's arrays are
-    padded to the longest series), or (None, None) when they were not asked for."""
+  def _component_frames(self, b: int, ci_data, num_steps: int):
+    """(components, coefficients) of series b over its `num_steps` steps, or (None, None) when they
+    were not asked for."""
     if self._csum is None:
       return None, None
-    csum = {k: (v[b] if k in _PER_COLUMN or num_steps is None
-                else v[b][..., :num_steps]) for k, v in self._csum.items()}
+    csum = _cut({k: v[b] for k, v in self._csum.items()}, num_steps, _PER_COLUMN)
     return lib._component_frames(                               # pylint: disable=protected-access
         csum, self._ranks, self._dsum["per_draw"].shape[-1], self.alpha,
         lib.posterior_processing.model_index(ci_data), ci_data.data.index,
@@ -326,208 +340,6 @@ def hmc_batch_route(*, float64: bool, standardize_data: bool, num_seasonal_block
       or P > HMC_BATCH_MAX_P or hmc_init != "gibbs"):
     return "per_series"
   return "one_launch"
-
-
-def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
-                           pre_period, post_period, alpha: float = 0.05, seed=None,
-                           data_options: Optional[lib.DataOptions] = None,
-                           model_options: Optional[lib.ModelOptions] = None,
-                           inference_options: Optional[lib.InferenceOptions] = None,
-                           index: Optional[pd.Index] = None,
-                           names: Optional[Sequence[Any]] = None,
-                           shared_streams: bool = False) -> CausalImpactBatchAnalysis:
-  """`fit_causalimpact` for B series at once.
-
-  data: a sequence of DataFrames with identical index and column layout (outcome first, or
-  `DataOptions.outcome_column`), or an array [B, T, 1 + covariates] (outcome first) with
-  `index` (default: 0..T-1).  Other arguments as `fit_causalimpact`.  Series that do NOT share
-  the index and the periods (own lengths, own intervention dates) go to `fit_causalimpact_panel`.  Latent-state draws are not
-  downloaded (B x chains x draws x T values); the per-series frames and the summary table are.
-
-  Random streams: series b draws from streams keyed by (its position b in the batch, chain), so
-  the Monte-Carlo errors of different series are independent (pooling effects over geos averages
-  them out) and the result does not depend on how the batch is split over devices.  Series 0 of
-  a batch equals `fit_causalimpact` on that series alone with the same seed.
-  `shared_streams=True` keys the streams by chain only: EVERY series then reproduces its
-  single-series fit draw for draw, at the price of perfectly correlated Monte-Carlo errors.
-  "Equals" is bit for bit on every route: the kernel a series runs on is a function of its model
-  and length alone (trend models, trend + one block of 2-7 seasons, and the general seasonal /
-  more-than-52-covariate routes alike), never of the batch size or the device's CU count; the
-  launch size only decides how many workgroups share one chain's work, which does not change the
-  arithmetic (tests/test_gpu_gibbs.py, including a seasonal batch with more chains than CUs).
-  `InferenceOptions.kernel_flags` (e.g. `_native.FLAG_SEQUENTIAL_SEASONAL`: 1.5-1.7x the throughput
-  for batches of hundreds of short multi-block series) applies to the batch as to a single fit: give
-  it to both when comparing them.
-
-  `DataOptions.dtype=float64` and `standardize_data=False` batches are NOT one launch: they are
-  fitted series by series on the single-series routes (float64 kernels / exact internal
-  conditioning), i.e. B sequential fits on one device -- B times the cost of one fit, and
-  `inference_options.devices` is not used to shard them.  Their streams are keyed per series in
-  the same way (series b on the key of series id b) unless `shared_streams=True`.
-
-  `InferenceOptions(sampler="hmc")`: standardised float32 batches of trend models with T <= 4096,
-  at most 128 design columns and `hmc_init="gibbs"` (either `hmc_prior`) run in one launch per
-  device: B x num_chains HMC chains (csrc/ci_hmc.h), then the latent paths, predictive
-  trajectories and their summary on the device.  A shard whose trajectories would exceed
-  `_hmc.HMC_BATCH_HBM_BYTES` is fitted in several launches; neither that split nor the one over
-  devices changes a result.  Every other HMC batch (seasonal blocks, longer series,
-  `hmc_init="vi"`, float64, `standardize_data=False`) is fitted series by series through
-  `fit_causalimpact`, keyed as above (`hmc_batch_route`).  With `shared_streams=True` series b
-  equals `fit_causalimpact(..., sampler="hmc")` on it alone on either route.
-  """
-  data_options = data_options or lib.DataOptions()
-  model_options = model_options or lib.ModelOptions()
-  inference_options = inference_options or lib.InferenceOptions()
-  if not 0 < alpha < 1:
-    raise ValueError("`alpha` must be between 0 and 1.")
-  if inference_options.sampler not in ("gibbs", "hmc"):
-    raise ValueError(f"sampler must be 'gibbs' or 'hmc', got {inference_options.sampler!r}")
-  hmc = inference_options.sampler == "hmc"
-  if isinstance(data, np.ndarray):
-    values = np.asarray(data, np.float64)
-    index = pd.RangeIndex(values.shape[1]) if index is None else pd.Index(index)
-    columns = ["y"] + [f"x{j}" for j in range(values.shape[2] - 1)]
-  else:
-    frames = [pd.DataFrame(d) for d in data]
-    if not frames:
-      raise ValueError("`data` is empty")
-    first = frames[0]
-    oc = data_options.outcome_column if data_options.outcome_column is not None else first.columns[0]
-    columns = [oc] + [c for c in first.columns if c != oc]
-    for f in frames:
-      if not f.index.equals(first.index) or list(f.columns) != list(first.columns):
-        raise ValueError("all series of a batch must share the index and the columns")
-    values = np.stack([f[columns].to_numpy(dtype=np.float64) for f in frames])
-    index = first.index
-  B = values.shape[0]
-  names = list(range(B)) if names is None else list(names)
-  float64 = cid._as_numpy_dtype(data_options.dtype) == np.float64  # pylint: disable=protected-access
-  prep = None
-  per_series = float64 or not data_options.standardize_data
-  if hmc and not per_series:
-    prep = prepare_batch(values, index, pre_period, post_period, data_options.standardize_data)
-    route = hmc_batch_route(float64=float64, standardize_data=data_options.standardize_data,
-                            num_seasonal_blocks=len(_model.expand_seasons(model_options.seasons,
-                                                                          prep.y.shape[1])[0]),
-                            T=prep.y.shape[1],
-                            P=0 if prep.design is None else prep.design.shape[2],
-                            hmc_init=inference_options.hmc_init)
-    # the one-launch HMC path keeps no latent draws and has no component summary: asked for
-    # components, an HMC batch takes the per-series route, where `fit_causalimpact` has the draws
-    per_series = route == "per_series" or inference_options.components
-  if per_series:
-    # float64 compute (csrc/ci_gibbs64.h) and raw-scale outcomes (their per-series internal
-    # conditioning, causalimpact_lib._internal_conditioning) exist on the single-series path: the
-    # batch is fitted series by series there -- same container, same summary table, every series
-    # keyed like the one-launch path (series b on the Philox key of series id b,
-    # ci_series_stream_key, so the Monte-Carlo errors of different series are independent; with
-    # shared_streams=True every series equals `fit_causalimpact` on it alone with this seed).
-    # Not the one-launch path: B sequential fits on one device (see the docstring).  The HMC
-    # batches the one-launch path does not take (hmc_batch_route) come here too.
-    opts = dataclasses.replace(data_options, outcome_column=columns[0])
-    analyses = []
-    base_seed = lib._sanitize_seed(seed)   # pylint: disable=protected-access
-    for b in range(B):
-      seed_b = base_seed if shared_streams else _native.series_stream_key(base_seed, b)
-      one = lib.fit_causalimpact(pd.DataFrame(values[b], index=index, columns=columns), pre_period,
-                                 post_period, alpha=alpha, seed=seed_b, data_options=opts,
-                                 model_options=model_options, inference_options=inference_options)
-      analyses.append(dataclasses.replace(one, posterior_samples=None))   # (draws are not kept)
-    return PerSeriesBatchAnalysis(names, alpha, analyses)
-  if prep is None:
-    prep = prepare_batch(values, index, pre_period, post_period, data_options.standardize_data)
-  T = prep.y.shape[1]
-  P = 0 if prep.design is None else prep.design.shape[2]
-  num_seasons, season_change = _model.expand_seasons(model_options.seasons, T)
-  # the sampler sees the outcome in DataOptions.dtype (data.py:121-128), priors included
-  y_model = prep.y.astype(cid._as_numpy_dtype(data_options.dtype)).astype(np.float64)  # pylint: disable=protected-access
-  with np.errstate(invalid="ignore"):
-    pre_sd = np.nanstd(y_model[:, :prep.num_pre], axis=1, ddof=1)
-  params = [_model.series_params(y_model[b], prep.mask[b],
-                                 None if prep.design is None else prep.design[b],
-                                 prior_level_sd=model_options.prior_level_sd,
-                                 num_seasonal_blocks=len(num_seasons),
-                                 has_slope=model_options.local_linear_trend,
-                                 outcome_sd=float(pre_sd[b])) for b in range(B)]
-  seed_pair = lib._sanitize_seed(seed)   # pylint: disable=protected-access
-  C, S = inference_options.num_chains, inference_options.num_results
-  ranks = lib._summary_ranks(C * S, (alpha / 2.0, 1.0 - alpha / 2.0))   # pylint: disable=protected-access
-  idx = index[prep.model_rows]
-  in_post = np.asarray((idx >= prep.post_period[0]) & (idx <= prep.post_period[1]))
-  flags = (~np.asarray(idx < prep.post_period[0])).astype(np.uint8) | (in_post.astype(np.uint8) << 1)
-  observed = values[:, prep.model_rows, 0].copy()
-  observed[:, prep.num_pre:][:, ~in_post[prep.num_pre:]] = np.nan
-  devs = list(inference_options.devices) if inference_options.devices else [0]
-  shards = [s for s in np.array_split(np.arange(B), len(devs)) if len(s)]
-
-  def run_hmc(dev, ids):
-    # one launch per part of the shard that fits the HBM budget; series keep their global ids
-    from causalimpact import _hmc  # pylint: disable=import-outside-toplevel
-    step = _hmc.series_per_launch(T, P, C, S)
-    outs, sums = [], []
-    for lo in range(0, len(ids), step):
-      part = ids[lo:lo + step]
-      res = _hmc.fit_hmc_batch(
-          y_model[part], prep.mask[part], None if prep.design is None else prep.design[part],
-          [params[b] for b in part], has_slope=model_options.local_linear_trend, num_results=S,
-          num_warmup=inference_options.num_warmup_steps, num_chains=C, seed=seed_pair, device=dev,
-          series_offset=int(part[0]), shared_streams=shared_streams,
-          prior=inference_options.hmc_prior,
-          summary=dict(scale=prep.outcome_sd[part] if prep.standardize_data else 1.0,
-                       shift=prep.outcome_mean[part] if prep.standardize_data else 0.0,
-                       observed=observed[part], flags=flags, ranks=ranks))
-      outs.append(res)
-      sums.append(res["summary"])
-    out = {k: np.concatenate([o[k] for o in outs], axis=0)
-           for k in ("posterior_means", "observation_noise_scale", "level_scale")}
-    return out, {k: np.concatenate([d[k] for d in sums], axis=0) for k in sums[0]}
-
-  def run(dev, ids):
-    if hmc:
-      return run_hmc(dev, ids)
-    pb = _native.make_problem(T=T, P=P, has_slope=model_options.local_linear_trend,
-                              num_seasons=num_seasons, num_warmup=inference_options.num_warmup_steps,
-                              num_results=S, num_chains=C, num_series=len(ids), seed=seed_pair,
-                              device=dev, series_offset=int(ids[0]),
-                              flags=int(getattr(inference_options, "kernel_flags", 0)) |
-                              (_native.FLAG_SHARED_SERIES_STREAMS if shared_streams else 0))
-    sess = _native.Session(pb, y_model[ids], prep.mask[ids],
-                           None if prep.design is None else prep.design[ids], season_change,
-                           _native.make_params([params[b] for b in ids]))
-    try:
-      sess.run()
-      out = sess.fetch(["posterior_means", "observation_noise_scale", "level_scale"])
-      dsum = sess.summarize(prep.outcome_sd[ids] if prep.standardize_data else 1.0,
-                            prep.outcome_mean[ids] if prep.standardize_data else 0.0,
-                            observed[ids], flags, ranks)
-      if len(ids) == 1:
-        dsum = {k: v[None] for k, v in dsum.items()}
-      if inference_options.components:
-        out["components"] = sess.summarize_components(
-            prep.outcome_sd[ids] if prep.standardize_data else 1.0,
-            prep.outcome_mean[ids] if prep.standardize_data else 0.0, ranks)
-    finally:
-      sess.close()
-    return out, dsum
-
-  if len(shards) == 1:
-    # one device: no worker thread (a fresh host thread pays the runtime's per-thread set-up,
-    # ~30 ms, more than the fit of 512 series takes)
-    results = [run(devs[0], shards[0])]
-  else:
-    with concurrent.futures.ThreadPoolExecutor(max_workers=len(shards)) as pool:
-      results = list(pool.map(lambda a: run(*a), zip(devs, shards)))
-  means = np.concatenate([r[0]["posterior_means"].mean(axis=1) for r in results], axis=0)   # [B, T]
-  dsum = {k: np.concatenate([r[1][k] for r in results], axis=0) for k in results[0][1]}
-  diag_draws = None
-  if C > 1:
-    keys = ("observation_noise_scale", "level_scale")
-    diag_draws = {k: np.concatenate([r[0][k] for r in results], axis=0) for k in keys}   # [B, C, S]
-  csum = None
-  if inference_options.components:
-    csum = {k: np.concatenate([r[0]["components"][k] for r in results], axis=0)
-            for k in results[0][0]["components"]}
-  return CausalImpactBatchAnalysis(prep, names, alpha, means, dsum, ranks, columns, diag_draws, csum)
 
 
 # ------------------------------------------------------------------------------------------
@@ -793,35 +605,334 @@ class CausalImpactPanelAnalysis(CausalImpactBatchAnalysis):
   hence its own post-period window in the summary table.  `posterior_means` [B, T_max] and the
   device summary's arrays over time are padded to the longest series; series b owns [0, T_b)."""
 
-  def _request(self, b: int) -> Dict:
-    p, Tb = self._prep, int(self._prep.lengths[b])
-    return dict(scale=float(p.outcome_sd[b]), shift=float(p.outcome_mean[b]),
-                observed=p.observed[b, :Tb], flags=p.flags[b, :Tb], ranks=self._ranks,
-                quantiles=(self.alpha / 2.0, 1.0 - self.alpha / 2.0))
-
   def _build_summary(self) -> pd.DataFrame:
     p = self._prep
     post_mean = (self._means.astype(np.float64) * p.outcome_sd[:, None] + p.outcome_mean[:, None])
     stats = panel_window_stats(p.observed, p.flags, post_mean, p.lengths)
     return summary_table(self._names, self.alpha, self._ranks, self._dsum, **stats)
 
-  def __getitem__(self, b: int) -> lib.CausalImpactAnalysis:
-    b = range(len(self))[b]
-    if b not in self._cache:
-      p = self._prep
-      Tb = int(p.lengths[b])
-      (pre, post) = p.periods[b]
-      df = pd.DataFrame(p.raw[b], index=p.indices[b], columns=self._columns)
-      ci_data = cid.CausalImpactData(df, pre, post, standardize_data=p.standardize_data)
-      dsum = {k: (v[b][..., :Tb] if k in ("value_order", "cum_order") else v[b])
-              for k, v in self._dsum.items()}
-      rq = lib._device_summary_request(ci_data, self.alpha)   # pylint: disable=protected-access
-      rq["ranks"] = self._ranks
-      series, summary = lib._compute_impact_device(            # pylint: disable=protected-access
-          self._means[b, :Tb], dsum, rq, ci_data, self.alpha)
-      self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b),
-                                                *self._component_frames(b, ci_data, Tb))
-    return self._cache[b]
+  def _series_view(self, b: int):
+    p = self._prep
+    return (pd.DataFrame(p.raw[b], index=p.indices[b], columns=self._columns), *p.periods[b],
+            int(p.lengths[b]))
+
+
+# ------------------------------------------------------------------------------------------
+# The one launch-and-assemble path of batches and panels
+# ------------------------------------------------------------------------------------------
+def _options(alpha, data_options, model_options, inference_options):
+  """The options of a fit function with their defaults filled in, after its argument checks."""
+  data_options = data_options or lib.DataOptions()
+  model_options = model_options or lib.ModelOptions()
+  inference_options = inference_options or lib.InferenceOptions()
+  if not 0 < alpha < 1:
+    raise ValueError("`alpha` must be between 0 and 1.")
+  if inference_options.sampler not in ("gibbs", "hmc"):
+    raise ValueError(f"sampler must be 'gibbs' or 'hmc', got {inference_options.sampler!r}")
+  return data_options, model_options, inference_options
+
+
+def _frames_outcome_first(data, data_options):
+  """(`data` as a list of DataFrames, the columns of the first with the outcome in front)."""
+  frames = [pd.DataFrame(d) for d in data]
+  if not frames:
+    raise ValueError("`data` is empty")
+  first = frames[0]
+  oc = data_options.outcome_column if data_options.outcome_column is not None else first.columns[0]
+  return frames, [oc] + [c for c in first.columns if c != oc]
+
+
+def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_options, model_options,
+                    inference_options, shared_streams) -> PerSeriesBatchAnalysis:
+  """`fit_causalimpact` on every series in turn: the routes the one-launch path does not have.
+  float64 compute (csrc/ci_gibbs64.h) and raw-scale outcomes (their per-series internal
+  conditioning, causalimpact_lib._internal_conditioning) exist on the single-series path, and so do
+  the HMC fits that `hmc_batch_route` / `panel_route` send here.  Same container, same summary
+  table, every series keyed like the one-launch path: series b on the Philox key of series id b
+  (ci_series_stream_key), so the Monte-Carlo errors of different series are independent; with
+  shared_streams=True every series equals `fit_causalimpact` on it alone with this seed.  B
+  sequential fits on one device (see the docstrings of the fit functions)."""
+  opts = dataclasses.replace(data_options, outcome_column=outcome_column)
+  base_seed = lib._sanitize_seed(seed)   # pylint: disable=protected-access
+  analyses = []
+  for b, frame in enumerate(frames):
+    seed_b = base_seed if shared_streams else _native.series_stream_key(base_seed, b)
+    one = lib.fit_causalimpact(frame, periods[b][0], periods[b][1], alpha=alpha, seed=seed_b,
+                               data_options=opts, model_options=model_options,
+                               inference_options=inference_options)
+    analyses.append(dataclasses.replace(one, posterior_samples=None))   # (draws are not kept)
+  return PerSeriesBatchAnalysis(names, alpha, analyses)
+
+
+@dataclasses.dataclass
+class _Fit:
+  """What the launches of one fit read: the prepared arrays, series first and time padded to the
+  longest series as in `PreparedPanel`, and the fit options."""
+  y: np.ndarray                 # [B, T_max] standardised outcome as the sampler sees it
+  mask: np.ndarray              # [B, T_max] bool
+  design: Optional[np.ndarray]  # [B, T_max, P] or None
+  lengths: np.ndarray           # [B] model steps of every series
+  scale: np.ndarray             # [B] the outcomes' sd: value = trajectory * scale + shift
+  shift: np.ndarray             # [B] the outcomes' mean
+  observed: np.ndarray          # [B, T_max] data-scale outcome, NaN in gap / tail / padding
+  flags: np.ndarray             # window flags: [T_max] when the series share them, else [B, T_max]
+  params: List[Dict]            # per series: `_model.series_params`
+  ranks: Sequence[int]          # the order statistics the summaries return
+  seed: Tuple[int, int]
+  shared_streams: bool
+  model_options: lib.ModelOptions
+  inference_options: lib.InferenceOptions
+
+
+def _sampler_outcome(prep, data_options) -> np.ndarray:
+  """prep.y as the sampler sees it: in DataOptions.dtype (data.py:121-128), priors included."""
+  return prep.y.astype(cid._as_numpy_dtype(data_options.dtype)).astype(np.float64)  # pylint: disable=protected-access
+
+
+def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_options,
+             shared_streams) -> _Fit:
+  """The `_Fit` of a prepared batch or panel: y = `_sampler_outcome(prep)`, lengths [B], pre_sd [B]
+  the sd of every series' own pre-period outcome."""
+  with np.errstate(invalid="ignore"):
+    params = [_model.series_params(
+        y[b, :Tb], prep.mask[b, :Tb], None if prep.design is None else prep.design[b, :Tb],
+        prior_level_sd=model_options.prior_level_sd, num_seasonal_blocks=len(model_options.seasons),
+        has_slope=model_options.local_linear_trend, outcome_sd=float(pre_sd[b]))
+              for b, Tb in enumerate(int(t) for t in lengths)]
+  num_draws = inference_options.num_chains * inference_options.num_results
+  return _Fit(y=y, mask=prep.mask, design=prep.design, lengths=np.asarray(lengths),
+              scale=prep.outcome_sd, shift=prep.outcome_mean, observed=prep.observed,
+              flags=prep.flags, params=params,
+              ranks=lib._summary_ranks(num_draws, (alpha / 2.0, 1.0 - alpha / 2.0)),   # pylint: disable=protected-access
+              seed=lib._sanitize_seed(seed), shared_streams=shared_streams,   # pylint: disable=protected-access
+              model_options=model_options, inference_options=inference_options)
+
+
+def _run_launch(launch, kind: str, fit: _Fit):
+  """One launch of the Gibbs sampler and its summaries on the device.  launch: (device, key,
+  positions) as `panel_launches` lists them; kind: the session the positions run in --
+    "ordinary"         `_native.Session`: series b of the launch is keyed by positions[0] + b, hence
+                       runs of consecutive positions (or shared streams), all of one length;
+    "ragged"           `_native.Session.ragged`: every series on its own length and keyed by its
+                       position (`series_ids`), the stride the longest series of the launch;
+    "ragged_seasonal"  the same with the table of positional change flags of the launch (every
+                       series starts at its own step 0) and the stride rounded up to a multiple of 4
+                       (every row 16-byte aligned), the padding as in `PreparedPanel`: y NaN, mask
+                       True, design 0, observed NaN, flags 0.
+  Returns (out, dsum, csum): `fetch` of posterior_means [n, C, T] and `_DRAW_SCALARS` [n, C, S],
+  `summarize`, and `summarize_components` (None unless InferenceOptions.components).  Every array
+  keeps the series axis, and T is the longest series of the launch on every route."""
+  dev, _, ids = launch
+  ids = np.asarray(ids, dtype=np.int64)
+  mo, io = fit.model_options, fit.inference_options
+  T = int(fit.lengths[ids].max())
+  stride = (T + 3) & ~3 if kind == "ragged_seasonal" else T
+
+  def rows(a, fill):
+    a = a[ids, :T]
+    if stride == T:
+      return a
+    return np.concatenate([a, np.full((len(ids), stride - T) + a.shape[2:], fill, a.dtype)], axis=1)
+
+  y, mask = rows(fit.y, np.nan), rows(fit.mask, True)
+  design = None if fit.design is None else rows(fit.design, 0.0)
+  observed = rows(fit.observed, np.nan)
+  flags = fit.flags[:T] if fit.flags.ndim == 1 else rows(fit.flags, 0)
+  scale, shift = fit.scale[ids], fit.shift[ids]
+  num_seasons, season_change = _model.expand_seasons(mo.seasons, stride)
+  problem = dict(T=stride, P=0 if design is None else design.shape[2], has_slope=mo.local_linear_trend,
+                 num_seasons=num_seasons, num_warmup=io.num_warmup_steps, num_results=io.num_results,
+                 num_chains=io.num_chains, num_series=len(ids), seed=fit.seed, device=dev,
+                 flags=int(getattr(io, "kernel_flags", 0)) |
+                 (_native.FLAG_SHARED_SERIES_STREAMS if fit.shared_streams else 0))
+  par = _native.make_params([fit.params[b] for b in ids])
+  if kind == "ordinary":
+    sess = _native.Session(_native.make_problem(series_offset=int(ids[0]), **problem), y, mask,
+                           design, season_change, par)
+  else:
+    sess = _native.Session.ragged(
+        _native.make_problem(**problem), fit.lengths[ids], y, mask, design, par, series_ids=ids,
+        season_change=season_change if kind == "ragged_seasonal" else None)
+  try:
+    sess.run()
+    out = sess.fetch(["posterior_means", *_DRAW_SCALARS])
+    dsum = sess.summarize(scale, shift, observed, flags, fit.ranks)
+    if len(ids) == 1:        # (`summarize` drops the series axis of a session of one series)
+      dsum = {k: v[None] for k, v in dsum.items()}
+    csum = sess.summarize_components(scale, shift, fit.ranks) if io.components else None
+  finally:
+    sess.close()
+  if stride != T:            # (back at the stride of the longest series)
+    out, dsum = _cut(out, T, _DRAW_SCALARS), _cut(dsum, T, _PER_DRAW)
+    csum = None if csum is None else _cut(csum, T, _PER_COLUMN)
+  return out, dsum, csum
+
+
+def _run_hmc_launch(launch, fit: _Fit):
+  """`_run_launch` for the one-launch HMC path (`_hmc.fit_hmc_batch`: B x chains HMC chains, then
+  the latent paths, the predictive trajectories and their summary on the device): consecutive
+  positions of a batch, series b keyed by positions[0] + b.  It keeps no latent draws, hence no
+  component summary."""
+  from causalimpact import _hmc  # pylint: disable=import-outside-toplevel
+  dev, _, ids = launch
+  ids = np.asarray(ids, dtype=np.int64)
+  mo, io = fit.model_options, fit.inference_options
+  res = _hmc.fit_hmc_batch(
+      fit.y[ids], fit.mask[ids], None if fit.design is None else fit.design[ids],
+      [fit.params[b] for b in ids], has_slope=mo.local_linear_trend, num_results=io.num_results,
+      num_warmup=io.num_warmup_steps, num_chains=io.num_chains, seed=fit.seed, device=dev,
+      series_offset=int(ids[0]), shared_streams=fit.shared_streams, prior=io.hmc_prior,
+      summary=dict(scale=fit.scale[ids], shift=fit.shift[ids], observed=fit.observed[ids],
+                   flags=fit.flags, ranks=fit.ranks))
+  return {k: res[k] for k in ("posterior_means", *_DRAW_SCALARS)}, res["summary"], None
+
+
+def _scatter(parts, num_series: int, num_steps: int, whole, fill) -> Dict[str, np.ndarray]:
+  """{name: [num_series, ...]} of parts = [(positions, {name: [len(positions), ...]})].  The names
+  in `whole` have no time axis; the others are arrays over time (last axis), padded from a launch's
+  stride to `num_steps` with `fill`."""
+  out = {k: (np.zeros((num_series,) + v.shape[1:], v.dtype) if k in whole else
+             np.full((num_series,) + v.shape[1:-1] + (num_steps,), fill, v.dtype))
+         for k, v in parts[0][1].items()}
+  for ids, arrays in parts:
+    for k, v in arrays.items():
+      if k in whole:
+        out[k][ids] = v
+      else:
+        out[k][ids, ..., :v.shape[-1]] = v
+  return out
+
+
+def _assemble(launches, run, num_series: int, num_steps: int):
+  """Runs `launches` [(device, key, positions)] through `run(launch) -> (out, dsum, csum)`
+  (`_run_launch`; the launches of a device in turn, the devices side by side) and puts the series
+  axis back together.  Returns what the containers take:
+    means [B, T_max]  the chain mean of posterior_means, 0 beyond a series' length;
+    dsum              the device summary {name: [B, ...]}: the order statistics over time NaN beyond
+                      a series' length;
+    diag_draws        {name: [B, C, S]} of `_DRAW_SCALARS`, or None for one chain;
+    csum              the component summary {name: [B, ...]}, NaN beyond a series' length (the
+                      `_PER_COLUMN` arrays have no time axis), or None when `run` returns none.
+  One launch that holds all B series in order at full stride is the result as it stands: its blocks
+  (512 series: 24 MB of summary in pinned memory) are not copied a second time."""
+  results = lib.map_by_device(run, launches)
+  # per launch: the chain mean with the scalar draws, the device summary, the component summary
+  groups = [(dict({k: out[k] for k in _DRAW_SCALARS}, means=out["posterior_means"].mean(axis=1)),
+             dsum, csum) for out, dsum, csum in results]
+  fetched, dsum, csum = groups[0]
+  if not (len(launches) == 1 and list(launches[0][2]) == list(range(num_series))
+          and fetched["means"].shape[-1] == num_steps):
+    def gather(i, whole, fill):
+      parts = [(list(launch[2]), group[i]) for launch, group in zip(launches, groups)]
+      return _scatter(parts, num_series, num_steps, whole, fill)
+    fetched, dsum = gather(0, _DRAW_SCALARS, 0), gather(1, _PER_DRAW, np.nan)
+    csum = None if csum is None else gather(2, _PER_COLUMN, np.nan)
+  means = fetched.pop("means")
+  diag_draws = fetched if fetched[_DRAW_SCALARS[0]].shape[1] > 1 else None
+  return means, dsum, diag_draws, csum
+
+
+def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
+                           pre_period, post_period, alpha: float = 0.05, seed=None,
+                           data_options: Optional[lib.DataOptions] = None,
+                           model_options: Optional[lib.ModelOptions] = None,
+                           inference_options: Optional[lib.InferenceOptions] = None,
+                           index: Optional[pd.Index] = None,
+                           names: Optional[Sequence[Any]] = None,
+                           shared_streams: bool = False) -> CausalImpactBatchAnalysis:
+  """`fit_causalimpact` for B series at once.
+
+  data: a sequence of DataFrames with identical index and column layout (outcome first, or
+  `DataOptions.outcome_column`), or an array [B, T, 1 + covariates] (outcome first) with
+  `index` (default: 0..T-1).  Other arguments as `fit_causalimpact`.  Series that do NOT share
+  the index and the periods (own lengths, own intervention dates) go to `fit_causalimpact_panel`.  Latent-state draws are not
+  downloaded (B x chains x draws x T values); the per-series frames and the summary table are.
+
+  Random streams: series b draws from streams keyed by (its position b in the batch, chain), so
+  the Monte-Carlo errors of different series are independent (pooling effects over geos averages
+  them out) and the result does not depend on how the batch is split over devices.  Series 0 of
+  a batch equals `fit_causalimpact` on that series alone with the same seed.
+  `shared_streams=True` keys the streams by chain only: EVERY series then reproduces its
+  single-series fit draw for draw, at the price of perfectly correlated Monte-Carlo errors.
+  "Equals" is bit for bit on every route: the kernel a series runs on is a function of its model
+  and length alone (trend models, trend + one block of 2-7 seasons, and the general seasonal /
+  more-than-52-covariate routes alike), never of the batch size or the device's CU count; the
+  launch size only decides how many workgroups share one chain's work, which does not change the
+  arithmetic (tests/test_gpu_gibbs.py, including a seasonal batch with more chains than CUs).
+  `InferenceOptions.kernel_flags` (e.g. `_native.FLAG_SEQUENTIAL_SEASONAL`: 1.5-1.7x the throughput
+  for batches of hundreds of short multi-block series) applies to the batch as to a single fit: give
+  it to both when comparing them.
+
+  `DataOptions.dtype=float64` and `standardize_data=False` batches are NOT one launch: they are
+  fitted series by series on the single-series routes (float64 kernels / exact internal
+  conditioning), i.e. B sequential fits on one device -- B times the cost of one fit, and
+  `inference_options.devices` is not used to shard them.  Their streams are keyed per series in
+  the same way (series b on the key of series id b) unless `shared_streams=True`.
+
+  `InferenceOptions(sampler="hmc")`: standardised float32 batches of trend models with T <= 4096,
+  at most 128 design columns and `hmc_init="gibbs"` (either `hmc_prior`) run in one launch per
+  device: B x num_chains HMC chains (csrc/ci_hmc.h), then the latent paths, predictive
+  trajectories and their summary on the device.  A shard whose trajectories would exceed
+  `_hmc.HMC_BATCH_HBM_BYTES` is fitted in several launches; neither that split nor the one over
+  devices changes a result.  Every other HMC batch (seasonal blocks, longer series,
+  `hmc_init="vi"`, float64, `standardize_data=False`) is fitted series by series through
+  `fit_causalimpact`, keyed as above (`hmc_batch_route`).  With `shared_streams=True` series b
+  equals `fit_causalimpact(..., sampler="hmc")` on it alone on either route.
+  """
+  data_options, model_options, inference_options = _options(alpha, data_options, model_options,
+                                                             inference_options)
+  if isinstance(data, np.ndarray):
+    values = np.asarray(data, np.float64)
+    index = pd.RangeIndex(values.shape[1]) if index is None else pd.Index(index)
+    columns = ["y"] + [f"x{j}" for j in range(values.shape[2] - 1)]
+  else:
+    frames, columns = _frames_outcome_first(data, data_options)
+    first = frames[0]
+    for f in frames:
+      if not f.index.equals(first.index) or list(f.columns) != list(first.columns):
+        raise ValueError("all series of a batch must share the index and the columns")
+    values = np.stack([f[columns].to_numpy(dtype=np.float64) for f in frames])
+    index = first.index
+  B = values.shape[0]
+  names = list(range(B)) if names is None else list(names)
+  hmc = inference_options.sampler == "hmc"
+  # float64 and raw-scale batches go series by series; every other batch is standardised float32
+  per_series = (cid._as_numpy_dtype(data_options.dtype) == np.float64   # pylint: disable=protected-access
+                or not data_options.standardize_data)
+  if not per_series:
+    prep = prepare_batch(values, index, pre_period, post_period)
+    T = prep.y.shape[1]
+    # the one-launch HMC path keeps no latent draws and has no component summary: asked for
+    # components, an HMC batch takes the per-series route, where `fit_causalimpact` has the draws
+    per_series = hmc and (inference_options.components or hmc_batch_route(
+        float64=False, standardize_data=True, num_seasonal_blocks=len(model_options.seasons), T=T,
+        P=0 if prep.design is None else prep.design.shape[2],
+        hmc_init=inference_options.hmc_init) == "per_series")
+  if per_series:
+    return _fit_per_series((pd.DataFrame(values[b], index=index, columns=columns) for b in range(B)),
+                           [(pre_period, post_period)] * B, names, columns[0], alpha, seed,
+                           data_options, model_options, inference_options, shared_streams)
+  y = _sampler_outcome(prep, data_options)
+  with np.errstate(invalid="ignore"):
+    pre_sd = np.nanstd(y[:, :prep.num_pre], axis=1, ddof=1)
+  fit = _new_fit(prep, y, np.full(B, T), pre_sd, alpha, seed, model_options, inference_options,
+                 shared_streams)
+  # a batch is the panel of one group of equal lengths: consecutive positions on every device
+  launches = panel_launches(dict(route="equal_length", groups=[(T, list(range(B)))]),
+                            inference_options.devices, shared_streams)
+  if hmc:
+    from causalimpact import _hmc  # pylint: disable=import-outside-toplevel
+    # one launch per part of a device's share that fits the HBM budget
+    step = _hmc.series_per_launch(T, 0 if prep.design is None else prep.design.shape[2],
+                                  inference_options.num_chains, inference_options.num_results)
+    launches = [(dev, key, ids[lo:lo + step]) for dev, key, ids in launches
+                for lo in range(0, len(ids), step)]
+    run = lambda launch: _run_hmc_launch(launch, fit)          # pylint: disable=unnecessary-lambda-assignment
+  else:
+    run = lambda launch: _run_launch(launch, "ordinary", fit)   # pylint: disable=unnecessary-lambda-assignment
+  means, dsum, diag_draws, csum = _assemble(launches, run, B, T)
+  return CausalImpactBatchAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
+                                   csum)
 
 
 def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float = 0.05, seed=None,
@@ -855,153 +966,39 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   chain only, and series b then equals `fit_causalimpact` on its frame with its periods and this
   seed (bit for bit in every array the session returns over its own steps); without it series 0
   does, and series b equals the single fit seeded with `_native.series_stream_key(seed, b)`."""
-  data_options = data_options or lib.DataOptions()
-  model_options = model_options or lib.ModelOptions()
-  inference_options = inference_options or lib.InferenceOptions()
-  if not 0 < alpha < 1:
-    raise ValueError("`alpha` must be between 0 and 1.")
-  if inference_options.sampler not in ("gibbs", "hmc"):
-    raise ValueError(f"sampler must be 'gibbs' or 'hmc', got {inference_options.sampler!r}")
-  frames = [pd.DataFrame(d) for d in data]
-  if not frames:
-    raise ValueError("`data` is empty")
+  data_options, model_options, inference_options = _options(alpha, data_options, model_options,
+                                                             inference_options)
+  frames, columns = _frames_outcome_first(data, data_options)
   B = len(frames)
   periods = list(periods)
   if len(periods) != B:
     raise ValueError(f"`periods` must hold one (pre_period, post_period) per series: {B} series, "
                      f"{len(periods)} periods")
   names = list(range(B)) if names is None else list(names)
-  first = frames[0]
-  oc = data_options.outcome_column if data_options.outcome_column is not None else first.columns[0]
-  columns = [oc] + [c for c in first.columns if c != oc]
   for b, f in enumerate(frames):
-    if list(f.columns) != list(first.columns):
+    if list(f.columns) != list(frames[0].columns):
       raise ValueError(f"series {names[b]!r}: all series of a panel must share the columns")
   float64 = cid._as_numpy_dtype(data_options.dtype) == np.float64  # pylint: disable=protected-access
-  seed_pair = lib._sanitize_seed(seed)   # pylint: disable=protected-access
   num_blocks = len(model_options.seasons)
   # (which panels go series by series does not depend on the lengths: the frames' bound them here)
   if panel_route(float64=float64, standardize_data=data_options.standardize_data,
                  sampler=inference_options.sampler, num_seasonal_blocks=num_blocks,
                  P=len(columns), lengths=[len(f) for f in frames])["route"] == "per_series":
-    opts = dataclasses.replace(data_options, outcome_column=oc)
-    analyses = []
-    for b, f in enumerate(frames):
-      seed_b = seed_pair if shared_streams else _native.series_stream_key(seed_pair, b)
-      one = lib.fit_causalimpact(f, periods[b][0], periods[b][1], alpha=alpha, seed=seed_b,
-                                 data_options=opts, model_options=model_options,
-                                 inference_options=inference_options)
-      analyses.append(dataclasses.replace(one, posterior_samples=None))   # (draws are not kept)
-    return PerSeriesBatchAnalysis(names, alpha, analyses)
-
-  prep = prepare_panel([f[columns] for f in frames], periods, data_options.standardize_data,
-                       names=names)
-  T_max = prep.y.shape[1]
-  P = 0 if prep.design is None else prep.design.shape[2]
-  route = panel_route(float64=float64, standardize_data=True, sampler="gibbs",
-                      num_seasonal_blocks=num_blocks, P=P, lengths=prep.lengths,
+    return _fit_per_series(frames, periods, names, columns[0], alpha, seed, data_options,
+                           model_options, inference_options, shared_streams)
+  prep = prepare_panel([f[columns] for f in frames], periods, names=names)
+  route = panel_route(float64=False, standardize_data=True, sampler="gibbs",
+                      num_seasonal_blocks=num_blocks,
+                      P=0 if prep.design is None else prep.design.shape[2], lengths=prep.lengths,
                       num_seasons=_model.expand_seasons(model_options.seasons, 1)[0])
-  # the sampler sees the outcome in DataOptions.dtype (data.py:121-128), priors included
-  y_model = prep.y.astype(cid._as_numpy_dtype(data_options.dtype)).astype(np.float64)  # pylint: disable=protected-access
-  params = []
+  y = _sampler_outcome(prep, data_options)
   with np.errstate(invalid="ignore"):
-    for b in range(B):
-      Tb, nb = int(prep.lengths[b]), int(prep.num_pre[b])
-      params.append(_model.series_params(
-          y_model[b, :Tb], prep.mask[b, :Tb], None if prep.design is None else prep.design[b, :Tb],
-          prior_level_sd=model_options.prior_level_sd, num_seasonal_blocks=num_blocks,
-          has_slope=model_options.local_linear_trend,
-          outcome_sd=float(np.nanstd(y_model[b, :nb], ddof=1))))
-  C, S = inference_options.num_chains, inference_options.num_results
-  ranks = lib._summary_ranks(C * S, (alpha / 2.0, 1.0 - alpha / 2.0))   # pylint: disable=protected-access
-  kflags = (int(getattr(inference_options, "kernel_flags", 0)) |
-            (_native.FLAG_SHARED_SERIES_STREAMS if shared_streams else 0))
-  want = ["posterior_means", "observation_noise_scale", "level_scale"]
-
-  def run(dev, key, ids):
-    """One launch: the series `ids` (panel positions) on device `dev`; arrays back at stride T_max."""
-    ids = np.asarray(ids, dtype=np.int64)
-    T = int(prep.lengths[ids].max())                 # the stride of this launch
-    design = None if prep.design is None else prep.design[ids, :T]
-    common = dict(T=T, P=P, has_slope=model_options.local_linear_trend,
-                  num_warmup=inference_options.num_warmup_steps, num_results=S, num_chains=C,
-                  num_series=len(ids), seed=seed_pair, device=dev, flags=kflags)
-    par = _native.make_params([params[b] for b in ids])
-    observed, flags = prep.observed[ids, :T], prep.flags[ids, :T]
-    if route["route"] == "ragged":
-      sess = _native.Session.ragged(_native.make_problem(**common), prep.lengths[ids],
-                                    y_model[ids, :T], prep.mask[ids, :T], design, par, series_ids=ids)
-    elif route["route"] == "ragged_seasonal":
-      # the stride: the longest series rounded up to a multiple of 4 (every row 16-byte aligned);
-      # the padding as in PreparedPanel -- y NaN, mask True, design 0, observed NaN, flags 0 -- and
-      # one table of positional change flags for the launch (every series starts at its own step 0)
-      TS = (T + 3) & ~3
-      pad = lambda a, fill: np.concatenate(   # pylint: disable=unnecessary-lambda-assignment
-          [a[ids, :T], np.full((len(ids), TS - T) + a.shape[2:], fill, a.dtype)], axis=1)
-      num_seasons, season_change = _model.expand_seasons(model_options.seasons, TS)
-      common["T"] = TS
-      sess = _native.Session.ragged(_native.make_problem(num_seasons=num_seasons, **common),
-                                    prep.lengths[ids], pad(y_model, np.nan), pad(prep.mask, True),
-                                    None if design is None else pad(prep.design, 0.0), par,
-                                    series_ids=ids, season_change=season_change)
-      observed, flags = pad(prep.observed, np.nan), pad(prep.flags, 0)
-    else:
-      num_seasons, season_change = _model.expand_seasons(model_options.seasons, T)
-      sess = _native.Session(_native.make_problem(num_seasons=num_seasons, series_offset=int(ids[0]),
-                                                  **common),
-                             y_model[ids, :T], prep.mask[ids, :T], design, season_change, par)
-    try:
-      sess.run()
-      out = sess.fetch(want)
-      dsum = sess.summarize(prep.outcome_sd[ids], prep.outcome_mean[ids], observed, flags, ranks)
-      if len(ids) == 1:
-        dsum = {k: v[None] for k, v in dsum.items()}
-      csum = None
-      if inference_options.components:
-        csum = sess.summarize_components(prep.outcome_sd[ids], prep.outcome_mean[ids], ranks)
-    finally:
-      sess.close()
-    if route["route"] == "ragged_seasonal":      # (back at the stride of the longest series)
-      out = {k: (v[..., :T] if k == "posterior_means" else v) for k, v in out.items()}
-      dsum = {k: (v[..., :T] if k in ("value_order", "cum_order") else v) for k, v in dsum.items()}
-      if csum is not None:
-        csum = {k: (v if k in _PER_COLUMN else v[..., :T]) for k, v in csum.items()}
-    return ids, T, out, dsum, csum
-
-  launches = panel_launches(route, inference_options.devices, shared_streams)
-  by_dev: Dict[int, list] = {}
-  for dev, key, ids in launches:
-    by_dev.setdefault(dev, []).append((dev, key, ids))
-  if len(by_dev) == 1:
-    results = [run(*a) for a in launches]
-  else:
-    with concurrent.futures.ThreadPoolExecutor(max_workers=len(by_dev)) as pool:
-      per_dev = list(pool.map(lambda work: [run(*a) for a in work], by_dev.values()))
-    results = [r for part in per_dev for r in part]
-  R, N = len(ranks), C * S
-  means = np.zeros((B, T_max), np.float32)
-  dsum = dict(value_order=np.full((B, R, T_max), np.nan), cum_order=np.full((B, R, T_max), np.nan),
-              per_draw=np.zeros((B, 2, N)), per_draw_order=np.zeros((B, 2, R)))
-  diag_draws = None
-  if C > 1:
-    diag_draws = {k: np.zeros((B, C, S), np.float32) for k in ("observation_noise_scale", "level_scale")}
-  csum = None
-  for ids, T, out, ds, cs in results:
-    if cs is not None:
-      if csum is None:      # over time padded to the longest series with NaN, like the order statistics
-        csum = {k: (np.zeros((B,) + v.shape[1:]) if k in _PER_COLUMN
-                    else np.full((B,) + v.shape[1:-1] + (T_max,), np.nan)) for k, v in cs.items()}
-      for k, v in cs.items():
-        if k in _PER_COLUMN:
-          csum[k][ids] = v
-        else:
-          csum[k][ids, ..., :T] = v
-    means[ids, :T] = out["posterior_means"].mean(axis=1)
-    dsum["value_order"][ids, :, :T] = ds["value_order"]
-    dsum["cum_order"][ids, :, :T] = ds["cum_order"]
-    dsum["per_draw"][ids] = ds["per_draw"]
-    dsum["per_draw_order"][ids] = ds["per_draw_order"]
-    if diag_draws is not None:
-      for k in diag_draws:
-        diag_draws[k][ids] = out[k]
-  return CausalImpactPanelAnalysis(prep, names, alpha, means, dsum, ranks, columns, diag_draws, csum)
+    pre_sd = [np.nanstd(y[b, :nb], ddof=1) for b, nb in enumerate(prep.num_pre)]
+  fit = _new_fit(prep, y, prep.lengths, pre_sd, alpha, seed, model_options, inference_options,
+                 shared_streams)
+  kind = "ordinary" if route["route"] == "equal_length" else route["route"]
+  means, dsum, diag_draws, csum = _assemble(
+      panel_launches(route, inference_options.devices, shared_streams),
+      lambda launch: _run_launch(launch, kind, fit), B, prep.y.shape[1])
+  return CausalImpactPanelAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
+                                   csum)

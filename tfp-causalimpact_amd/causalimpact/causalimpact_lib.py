@@ -416,6 +416,29 @@ def _internal_conditioning(ci_data) -> Tuple[float, float]:
   return mu, sd
 
 
+def map_by_device(fn, work):
+  """[fn(w) for w in work], every `w` a tuple that starts with its device: the items of one device
+  run in their order, the devices side by side, each on a host thread of its own -- the library
+  calls are synchronous and release the GIL, and there is no collective (chains and series are
+  independent).  One device: no worker thread (a fresh host thread pays the runtime's per-thread
+  set-up, ~30 ms, more than the fit of 512 series takes)."""
+  by_dev: Dict[Any, List[int]] = {}
+  for i, w in enumerate(work):
+    by_dev.setdefault(w[0], []).append(i)
+  if len(by_dev) <= 1:
+    return [fn(w) for w in work]
+  out = [None] * len(work)
+
+  def run(positions):
+    for i in positions:
+      out[i] = fn(work[i])
+
+  import concurrent.futures  # pylint: disable=import-outside-toplevel
+  with concurrent.futures.ThreadPoolExecutor(max_workers=len(by_dev)) as pool_:
+    list(pool_.map(run, by_dev.values()))     # (list: a worker's exception is raised here)
+  return out
+
+
 def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps, model=None,
                  dtype=np.float32, seasons=(), num_chains=1, devices=None,
                  local_linear_trend=False, sampler="gibbs", summary_request=None,
@@ -464,7 +487,6 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
     raise ValueError(f"sampler must be 'gibbs' or 'hmc', got {sampler!r}")
   devs = list(devices) if devices else [0]
   shares = np.array_split(np.arange(num_chains), len(devs))
-  parts = []
   device_summary = None
   def run_on(dev, chain_ids):
     """One device's share of the chains (chain ids keep their global RNG streams)."""
@@ -523,15 +545,8 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
     return _native.fit_gibbs(pb, y[None], mask[None], None if design is None else design[None],
                              season_change, _native.make_params([params]))
 
-  work = [(dev, ids) for dev, ids in zip(devs, shares) if len(ids)]
-  if len(work) == 1:
-    parts = [run_on(*work[0])]
-  else:
-    # the library calls are synchronous and release the GIL: one host thread per device runs
-    # the shares concurrently (no collective: chains are independent)
-    import concurrent.futures  # pylint: disable=import-outside-toplevel
-    with concurrent.futures.ThreadPoolExecutor(max_workers=len(work)) as pool_:
-      parts = list(pool_.map(lambda a: run_on(*a), work))
+  parts = map_by_device(lambda a: run_on(*a),
+                        [(dev, ids) for dev, ids in zip(devs, shares) if len(ids)])
   out = ({k: v[0] for k, v in parts[0].items()} if len(parts) == 1 else              # [C, ...]
          {k: np.concatenate([p[k][0] for p in parts], axis=0) for k in parts[0]})
 
