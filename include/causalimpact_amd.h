@@ -323,6 +323,30 @@ int ci_session_summarize_components(ci_session* session, const double* scale, co
                                     double* regression_mean, double* regression_order,
                                     double* inclusion_prob, double* weight_mean,
                                     double* weight_order);
+/* Weighted sums over GROUPS of series of the predictive trajectories of a finished run, draw by
+ * draw: the draws of a pooled effect (all units, a region), whose quantiles are not sums of the
+ * per-series quantiles.  Additive: CI_ABI_VERSION stays 5; look the symbol up (dlsym) where an older
+ * library may be met.  The [B, N, T] float32 trajectories (N = C*S pooled draws, chain-major; T the
+ * session's stride) are read where they are, in HBM.  The num_groups groups are the rows of a sparse
+ * weight table in CSR form: group g has the members[offsets[g] .. offsets[g + 1]) (positions of
+ * series in the session, strictly ascending) with the weights at the same places; members of zero
+ * weight are left out, a group may be empty.  For every group, draw n and step t, all in float64:
+ *   acc = init[g, n, t]                          (0.0 when init is NULL)
+ *   for the members b of g, ascending:
+ *     v   = trajectory[b, n, t] * scale[b] + shift[b]     (two roundings: the value of ci_session_summarize)
+ *     acc = acc + weights[g, b] * v                         (two roundings, no fused multiply-add)
+ *   out[g, n, t] = acc
+ * which a plain loop on the host reproduces bit for bit.  init and out are host arrays
+ * [num_groups, N, T] float64 (init may be NULL, and may be out itself).  A batch cut into several
+ * sessions continues ONE running sum in series order by handing the `out` of a part to the next as
+ * `init`: the result is bit-identical however the batch is cut.  The groups pass through the scratch
+ * of ci_session_summarize (allocated by whichever call comes first), min(num_groups, B) at a time.
+ * Checked before any device call: no NULL argument but init, a finished run, num_groups >= 1,
+ * offsets[0] = 0 and offsets non-decreasing, members strictly ascending within a group and in
+ * [0, B), weights finite. */
+int ci_session_pool_trajectories(ci_session* session, const double* scale, const double* shift,
+                                 int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                 const double* weights, const double* init, double* out);
 /* The same summary for draws that are on the host (pooled from several devices / processes, or
  * produced by the HMC path): trajectories [num_draws, T] float32 are uploaded to `device`,
  * summarised there and the (one-series) results returned as above. */
@@ -434,6 +458,12 @@ int ci_ll_session_hmc_summarize(ci_ll_session* session, const double* scale, con
                                 const double* observed, const uint8_t* flags, int32_t num_ranks,
                                 const int32_t* ranks, double* value_order, double* cum_order,
                                 double* per_draw, double* per_draw_order);
+/* ci_session_pool_trajectories for the trajectories of the last ci_ll_session_hmc_run (any session,
+ * B series, N = num_chains x num_results): same arguments, same arithmetic, same kernel. */
+int ci_ll_session_pool_trajectories(ci_ll_session* session, const double* scale, const double* shift,
+                                    int32_t num_groups, const int32_t* offsets,
+                                    const int32_t* members, const double* weights, const double* init,
+                                    double* out);
 int ci_ll_session_kernel_name(const ci_ll_session* session, char* buf, int32_t buflen);
 /* Algorithmic bytes of the last configured HMC fit (DESIGN.md "Roofline", cfg3). */
 int ci_ll_session_algorithmic_bytes(const ci_ll_session* session, double* bytes);

@@ -111,6 +111,9 @@ def load():
                                      C.c_void_p]
   L.ci_session_summarize_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                 C.c_void_p] + [C.c_void_p] * 9
+  for pool_fn in (L.ci_session_pool_trajectories, L.ci_ll_session_pool_trajectories):
+    pool_fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                        C.c_void_p, C.c_void_p, C.c_void_p]
   L.ci_summarize_draws.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double,
                                    C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -165,6 +168,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_algorithmic_bytes", "ci_session_kernel_name", "ci_session_destroy",
           "ci_session_profile", "ci_ll_session_kernel_name",
           "ci_session_summarize", "ci_session_summarize_components", "ci_summarize_draws", "ci_summarize_draws_f64",
+          "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
           "ci_ll_session_draw_latents", "ci_ll_session_hmc_run", "ci_ll_session_hmc_fetch",
           "ci_ll_session_algorithmic_bytes", "ci_ll_session_destroy", "ci_ll_session_create_batch",
@@ -292,6 +296,67 @@ def summarize_draws(trajectories, scale, shift, observed, flags, ranks, device=0
             obs.ctypes.data, fl.ctypes.data, int(rk.size), rk.ctypes.data,
             vo.ctypes.data, co.ctypes.data, pd_.ctypes.data, do.ctypes.data))
   return dict(value_order=vo, cum_order=co, per_draw=pd_, per_draw_order=do)
+
+
+def groups_csr(groups, num_series: int):
+  """The sparse weight table of `pool_trajectories` in CSR form: (offsets [G + 1] int32, members
+  int32, weights float64).  groups: a sequence with one entry per group, each a mapping {position
+  of a series in the session: weight} or a sequence of positions (weight 1).  Members are sorted
+  by position and those of zero weight left out; a group may be empty.  ValueError for a position
+  outside [0, num_series), a repeated member or a weight that is not finite."""
+  offsets, members, weights = [0], [], []
+  for g, group in enumerate(groups):
+    items = group.items() if hasattr(group, "items") else [(b, 1.0) for b in group]
+    items = sorted((int(b), float(w)) for b, w in items)
+    for i, (b, w) in enumerate(items):
+      if not 0 <= b < num_series:
+        raise ValueError(f"group {g}: member {b} is outside [0, {num_series})")
+      if i and b == items[i - 1][0]:
+        raise ValueError(f"group {g}: member {b} is listed twice")
+      if not np.isfinite(w):
+        raise ValueError(f"group {g}: the weight of member {b} is not finite")
+      if w != 0.0:
+        members.append(b)
+        weights.append(w)
+    offsets.append(len(members))
+  return (np.asarray(offsets, np.int32), np.asarray(members, np.int32),
+          np.asarray(weights, np.float64))
+
+
+def pool_host(trajectories, scale, shift, groups, init=None) -> np.ndarray:
+  """What `pool_trajectories` computes, in numpy: trajectories [B, N, T] (any float type), scale,
+  shift [B], groups as for `groups_csr`; returns [G, N, T] float64.  One rounding per operation,
+  members in ascending order -- the loop of include/causalimpact_amd.h -- so it is the definition the
+  device is compared with, and the accumulator of the batch routes that fit series by series."""
+  tr = np.asarray(trajectories)
+  B = tr.shape[0]
+  offsets, members, weights = groups_csr(groups, B)
+  sc = np.broadcast_to(np.asarray(scale, np.float64), (B,))
+  sh = np.broadcast_to(np.asarray(shift, np.float64), (B,))
+  out = (np.zeros((len(offsets) - 1,) + tr.shape[1:], np.float64) if init is None
+         else np.array(init, np.float64).reshape((len(offsets) - 1,) + tr.shape[1:]))
+  for g in range(len(offsets) - 1):
+    for k in range(offsets[g], offsets[g + 1]):
+      b = members[k]
+      out[g] = out[g] + weights[k] * (tr[b].astype(np.float64) * sc[b] + sh[b])
+  return out
+
+
+def _pool_call(fn, handle, B: int, N: int, T: int, scale, shift, groups, init) -> np.ndarray:
+  """The call both sessions' `pool_trajectories` make."""
+  sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (B,)))
+  sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.float64), (B,)))
+  offsets, members, weights = groups_csr(groups, B)
+  G = offsets.size - 1
+  if init is not None:
+    init = np.ascontiguousarray(init, dtype=np.float64)
+    if init.shape != (G, N, T):
+      raise ValueError(f"`init` must be {[G, N, T]}, got {list(init.shape)}")
+  big = G * N * T * 8 > (1 << 20)
+  out = pinned_empty((G, N, T), np.float64) if big else np.empty((G, N, T), np.float64)
+  _check(fn(handle, sc.ctypes.data, sh.ctypes.data, G, offsets.ctypes.data, members.ctypes.data,
+            weights.ctypes.data, _ptr(init), out.ctypes.data))
+  return out
 
 
 class _PinnedBlock:
@@ -532,6 +597,18 @@ class Session:
         *[_ptr(arrs.get(k)) for k in COMPONENT_OUTPUTS]))
     return arrs
 
+  def pool_trajectories(self, scale, shift, groups, init=None) -> np.ndarray:
+    """Weighted sums over groups of series of the resident predictive trajectories, draw by draw
+    (ci_session_pool_trajectories): out[g] = init[g] + sum over the members b of group g, ascending,
+    of w[g, b] * (trajectory[b] * scale[b] + shift[b]), float64, one rounding per operation
+    (`pool_host` is the same loop in numpy).  scale, shift: scalars or [B]; groups: one entry per
+    group, a mapping {position in the session: weight} or a sequence of positions (`groups_csr`);
+    init: [G, N, T] float64 -- the result of the part of a batch in front of this session -- or
+    None.  Returns [G, N, T] float64, N = chains x draws (chain-major)."""
+    pb = self.pb
+    return _pool_call(self._lib.ci_session_pool_trajectories, self._h, pb.num_series,
+                      pb.num_chains * pb.num_results, pb.T, scale, shift, groups, init)
+
   def close(self):
     if self._h:
       self._lib.ci_session_destroy(self._h)
@@ -663,6 +740,13 @@ class LogLikSession:
     _check(self._lib.ci_ll_session_hmc_fetch(self._h, draws.ctypes.data, acc.ctypes.data,
                                              eps.ctypes.data, None))
     return draws, acc, eps
+
+  def pool_trajectories(self, scale, shift, groups, init=None) -> np.ndarray:
+    """`Session.pool_trajectories` of the fit's resident predictive trajectories
+    (ci_ll_session_pool_trajectories): [G, N, T] float64, N = chains x draws of the last `hmc_run`."""
+    Cn, S = self._hmc_shape
+    return _pool_call(self._lib.ci_ll_session_pool_trajectories, self._h, self.B, Cn * S, self.T,
+                      scale, shift, groups, init)
 
   def algorithmic_bytes(self) -> float:
     b = C.c_double(0)

@@ -15,6 +15,11 @@ Random streams are keyed by (series position in the batch, chain): Monte-Carlo e
 independent across series; `shared_streams=True` keys them by chain only, which makes series b
 of a batch equal `fit_causalimpact` on series b alone with the same seed, draw for draw.
 
+`fit_causalimpact_batch(..., aggregates={name: members})` also returns the POOLED effect of groups of
+series (all geos, a region) with its credible bands: the weighted sum of the members' predictive
+trajectories draw by draw, formed on the device that holds them (csrc/ci_pool.h) and chained from
+launch to launch in series order, then summarised like any single series.
+
 `fit_causalimpact_panel` is the same for series with their own index, length and periods.
 
 Both fit functions are one pipeline over different preparations (`prepare_batch`, one shared
@@ -25,11 +30,14 @@ calendar; `prepare_panel`, padded to the longest series):
     the panel of ONE group of equal lengths, cut into consecutive positions per device;
   * `_run_launch` (Gibbs: ordinary, ragged or ragged seasonal session) or `_run_hmc_launch`: one
     session from creation to close, arrays back with the series axis at the launch's stride;
+  * `aggregate_groups`, `_PoolChain`, `_aggregate_analyses`: the aggregates of a batch -- the group
+    table, the running sums handed from launch to launch, the frames of every group;
   * `_assemble`: the launches of a device in turn, the devices side by side
     (`causalimpact_lib.map_by_device`), then the [B, ..., T_max] blocks of the containers.
 """
 from __future__ import annotations
 
+import concurrent.futures
 import dataclasses
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -222,6 +230,10 @@ class CausalImpactBatchAnalysis:
     self._diag: Dict[int, Dict] = {}
     self._cache: Dict[int, lib.CausalImpactAnalysis] = {}
     self.summary = self._build_summary()
+    # `fit_causalimpact_batch(aggregates=...)`: {aggregate name: CausalImpactAnalysis of the pooled
+    # outcome} and the 15-column table indexed by (aggregate, average|cumulative); None otherwise
+    self.aggregates: Optional[Dict[Any, lib.CausalImpactAnalysis]] = None
+    self.aggregate_summary: Optional[pd.DataFrame] = None
 
   def diagnostics_of(self, b: int):
     """{"split_rhat" | "ess_bulk" | "ess_tail": {key: value}} of series b (None for one chain)."""
@@ -308,6 +320,8 @@ class PerSeriesBatchAnalysis(CausalImpactBatchAnalysis):
     self._cache = dict(enumerate(analyses))
     self._diag_draws = None
     self.summary = pd.concat([a.summary for a in analyses], keys=self._names, names=["series", None])
+    self.aggregates = None
+    self.aggregate_summary = None
 
   def diagnostics_of(self, b: int):
     return self._cache[range(len(self))[b]].diagnostics
@@ -618,6 +632,223 @@ class CausalImpactPanelAnalysis(CausalImpactBatchAnalysis):
 
 
 # ------------------------------------------------------------------------------------------
+# Aggregates: the pooled effect of groups of series of a batch
+# ------------------------------------------------------------------------------------------
+def aggregate_groups(aggregates, names: Sequence[Any]):
+  """The group table of `fit_causalimpact_batch(aggregates=...)`: (aggregate names, (offsets,
+  members, weights)), the groups in CSR form over the POSITIONS of the series in the batch
+  (`_native.groups_csr`: members ascending, those of zero weight left out).
+
+  aggregates: a mapping {aggregate name: members}; members are a sequence of series names (weight 1),
+  a mapping {series name: weight}, or the string "all" (every series, weight 1).  ValueError for a
+  series name the batch does not have, a member listed twice, a weight that is not finite and a
+  group without a member of non-zero weight."""
+  if not hasattr(aggregates, "items"):
+    raise ValueError("`aggregates` must be a mapping {aggregate name: members}")
+  if len(aggregates) == 0:
+    raise ValueError("`aggregates` is empty")
+  names = list(names)
+  position = {}
+  for b, name in enumerate(names):
+    if name in position:
+      raise ValueError(f"aggregates need unique series names: {name!r} names series {position[name]} and {b}")
+    position[name] = b
+  groups = []
+  for agg, spec in aggregates.items():
+    if isinstance(spec, str):
+      if spec != "all":
+        raise ValueError(f"aggregate {agg!r}: members are a sequence or a mapping of series names, or "
+                         f"the string 'all'; got {spec!r}")
+      items = [(name, 1.0) for name in names]
+    elif hasattr(spec, "items"):
+      items = list(spec.items())
+    else:
+      items = [(name, 1.0) for name in spec]
+    group = {}
+    for name, w in items:
+      if name not in position:
+        raise ValueError(f"aggregate {agg!r}: unknown series {name!r}")
+      if position[name] in group:
+        raise ValueError(f"aggregate {agg!r}: series {name!r} is listed twice")
+      w = float(w)
+      if not np.isfinite(w):
+        raise ValueError(f"aggregate {agg!r}: the weight of series {name!r} is not finite")
+      group[position[name]] = w
+    if not any(w != 0.0 for w in group.values()):
+      raise ValueError(f"aggregate {agg!r} is empty: it has no member of non-zero weight")
+    groups.append(group)
+  return list(aggregates.keys()), _native.groups_csr(groups, len(names))
+
+
+def _check_aggregates(aggregates, names, shared_streams: bool):
+  """`aggregate_groups` after the refusal of common random numbers."""
+  if shared_streams:
+    raise ValueError(
+        "`aggregates` cannot be combined with shared_streams=True: with common random numbers the "
+        "Monte-Carlo errors of all series are perfectly correlated, and pairing draw n of every "
+        "series is then not a draw from the joint posterior of independent series -- the pooled "
+        "bands would be wrong.  Fit with the default per-series streams.")
+  return aggregate_groups(aggregates, names)
+
+
+def _groups_within(csr, ids: np.ndarray) -> List[Dict[int, float]]:
+  """The groups of `csr` cut to the consecutive ascending positions `ids` of one launch: per group
+  {position within the launch: weight} (empty for a group without a member there)."""
+  offsets, members, weights = csr
+  lo, hi = int(ids[0]), int(ids[-1])
+  out = []
+  for g in range(len(offsets) - 1):
+    m, w = members[offsets[g]:offsets[g + 1]], weights[offsets[g]:offsets[g + 1]]
+    keep = (m >= lo) & (m <= hi)
+    out.append({int(b) - lo: float(x) for b, x in zip(m[keep], w[keep])})
+  return out
+
+
+def pool_weighted(rows: np.ndarray, csr, init: Optional[np.ndarray] = None) -> np.ndarray:
+  """out[g] = init[g] + the sum over the members b of group g, ascending, of w[g, b] * rows[b], in
+  float64 with one rounding per operation (NaN wherever a member is NaN): rows [B, ...] -> [G, ...].
+  The accumulation of `csrc/ci_pool.h` for values already on the data scale: the pooled outcome, the
+  pooled posterior mean, and the running sums of the routes that fit series by series."""
+  offsets, members, weights = csr
+  rows = np.asarray(rows, np.float64)
+  G = len(offsets) - 1
+  out = np.zeros((G,) + rows.shape[1:]) if init is None else np.array(init, np.float64)
+  for g in range(G):
+    for k in range(offsets[g], offsets[g + 1]):
+      out[g] = out[g] + weights[k] * rows[members[k]]
+  return out
+
+
+class HostPool:
+  """The running sums of csrc/ci_pool.h in numpy, for batches that are fitted series by series: the
+  series are added in order, `add(b, ...)` for b = 0, 1, ..., each from its fit's trajectories
+  [N, T] (any float type) with value = trajectory * scale + shift in float64, two roundings, and
+  pooled[g] = pooled[g] + w[g, b] * value for every group that has b, two roundings.  `pooled`
+  [G, N, T] float64; `means`: every series' posterior mean [T] on the data scale."""
+
+  def __init__(self, csr):
+    self.csr = csr
+    self.pooled: Optional[np.ndarray] = None
+    self.means: List[np.ndarray] = []
+
+  def add(self, b: int, posterior_means, trajectories, scale, shift):
+    offsets, members, weights = self.csr
+    scale, shift = np.float64(scale), np.float64(shift)
+    value = np.asarray(trajectories).astype(np.float64) * scale + shift
+    self.means.append(np.asarray(posterior_means).astype(np.float64) * scale + shift)
+    if self.pooled is None:
+      self.pooled = np.zeros((len(offsets) - 1,) + value.shape)
+    for g in range(len(offsets) - 1):
+      k = offsets[g] + int(np.searchsorted(members[offsets[g]:offsets[g + 1]], b))
+      if k < offsets[g + 1] and members[k] == b:
+        self.pooled[g] = self.pooled[g] + weights[k] * value
+
+
+class _PoolChain:
+  """The running sums [G, N, T] of a batch's aggregates over its launches.  The launches are chained
+  in list order, which is ascending positions: launch k waits for the accumulator of launch k - 1,
+  passes it on as `init` and hands its own result to launch k + 1, so the sum runs over the series
+  in order however the batch is cut into launches and devices.  The fits still run side by side;
+  only these steps serialise.  Futures carry the accumulators: the exception of a launch reaches
+  the launch that waits for it.  A launch that fails also fails every launch behind it in the chain
+  that is not done: a device stops at its first failure, so the launches it had left never run, and
+  whoever waits for one of them on another device must not wait for ever."""
+
+  def __init__(self, launches, csr):
+    self.csr = csr
+    self._index = {int(launch[2][0]): k for k, launch in enumerate(launches)}
+    self._futures = [concurrent.futures.Future() for _ in launches]
+
+  def step(self, launch, pool):
+    """The pool step of `launch`, its session still open: pool(groups, init) is the session's
+    `pool_trajectories` with its scale and shift.  Only the groups with a member in the launch go to
+    the device; the others pass their accumulator through untouched."""
+    k = self._index[int(launch[2][0])]
+    try:
+      acc = self._futures[k - 1].result() if k else None
+      groups = _groups_within(self.csr, np.asarray(launch[2]))
+      active = [g for g, group in enumerate(groups) if group]
+      if active:
+        part = pool([groups[g] for g in active], None if acc is None else acc[active])
+        if len(active) == len(groups):
+          acc = part
+        else:
+          if acc is None:
+            acc = np.zeros((len(groups),) + part.shape[1:])
+          else:
+            acc = acc.copy()
+          acc[active] = part
+      if self._futures[k].done():            # failed meanwhile by a launch in front that ended in an error
+        self._futures[k].result()
+      self._futures[k].set_result(acc)
+    except BaseException as e:
+      self.fail(launch, e)
+      raise
+
+  def fail(self, launch, error: BaseException):
+    """A launch that ends in `error` before its pool step is done: whoever waits for it, or for a
+    launch behind it (none of those can complete a sum that lacks this part), gets the error."""
+    for future in self._futures[self._index[int(launch[2][0])]:]:
+      try:
+        future.set_exception(error)
+      except concurrent.futures.InvalidStateError:     # done already
+        pass
+
+  def guarded(self, run):
+    """`run(launch)` with its failure handed down the chain."""
+    def call(launch):
+      try:
+        return run(launch)
+      except BaseException as e:
+        self.fail(launch, e)
+        raise
+    return call
+
+  def result(self) -> np.ndarray:
+    return self._futures[-1].result()
+
+
+def scaler_stats(outcome_pre: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+  """(mean [B], sd [B]) of every series' pre-period outcome [B, n_pre] as `standardize.Scaler` fits
+  them on that series alone (`CausalImpactData.outcome_scaler`): the statistics a series' own
+  `series` frame puts its posterior mean on the data scale with.  (`standardize_batch` reduces the
+  whole block along a strided axis and may differ from them in the last bit.)"""
+  rows = [np.ascontiguousarray(r) for r in np.asarray(outcome_pre, np.float64)]
+  with np.errstate(invalid="ignore"):
+    return (np.array([np.nanmean(r, axis=0) for r in rows]),
+            np.array([np.nanstd(r, axis=0, ddof=1) for r in rows]))
+
+
+def _aggregate_analyses(agg_names, csr, pooled: np.ndarray, means: np.ndarray, prep: PreparedBatch,
+                        outcome_name, alpha: float, ranks, device: int = 0):
+  """(`aggregates`, `aggregate_summary`) of a batch from the pooled draws [G, N, T] (float64, data
+  scale) and the series' posterior means [B, T] on the data scale.  Per group: the observed outcome
+  and the posterior mean are pooled with the same weights (`pool_weighted`; the outcome is NaN
+  wherever a member is), the order statistics and per-draw totals of the pooled draws come from
+  `_native.summarize_draws` (ci_summarize_draws_f64: scale 1, shift 0, the batch's window flags), and
+  the reference's frames are built by `_compute_impact_device` over a `CausalImpactData` of the
+  pooled outcome, which is on the data scale already (standardize_data=False)."""
+  outcome = pool_weighted(prep.values[:, :, 0], csr)            # [G, T_all]: the raw pooled outcome
+  observed = pool_weighted(prep.observed, csr)                  # [G, T]: NaN in gap / tail
+  mean = pool_weighted(means, csr)                              # [G, T]
+  analyses = {}
+  for g, name in enumerate(agg_names):
+    try:
+      ci_data = cid.CausalImpactData(pd.DataFrame({outcome_name: outcome[g]}, index=prep.index),
+                                     prep.pre_period, prep.post_period, standardize_data=False)
+    except ValueError as e:
+      raise ValueError(f"aggregate {name!r}: {e}") from e
+    dsum = _native.summarize_draws(pooled[g], 1.0, 0.0, observed[g], prep.flags, ranks, device=device)
+    rq = lib._device_summary_request(ci_data, alpha)             # pylint: disable=protected-access
+    rq.update(observed=observed[g], flags=prep.flags, ranks=ranks)
+    series, summary = lib._compute_impact_device(mean[g], dsum, rq, ci_data, alpha)   # pylint: disable=protected-access
+    analyses[name] = lib.CausalImpactAnalysis(series, summary, None)
+  table = pd.concat([a.summary for a in analyses.values()], keys=list(analyses),
+                    names=["aggregate", None])
+  return analyses, table
+
+
+# ------------------------------------------------------------------------------------------
 # The one launch-and-assemble path of batches and panels
 # ------------------------------------------------------------------------------------------
 def _options(alpha, data_options, model_options, inference_options):
@@ -643,7 +874,7 @@ def _frames_outcome_first(data, data_options):
 
 
 def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_options, model_options,
-                    inference_options, shared_streams) -> PerSeriesBatchAnalysis:
+                    inference_options, shared_streams, aggregates=None) -> PerSeriesBatchAnalysis:
   """`fit_causalimpact` on every series in turn: the routes the one-launch path does not have.
   float64 compute (csrc/ci_gibbs64.h) and raw-scale outcomes (their per-series internal
   conditioning, causalimpact_lib._internal_conditioning) exist on the single-series path, and so do
@@ -651,17 +882,35 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
   table, every series keyed like the one-launch path: series b on the Philox key of series id b
   (ci_series_stream_key), so the Monte-Carlo errors of different series are independent; with
   shared_streams=True every series equals `fit_causalimpact` on it alone with this seed.  B
-  sequential fits on one device (see the docstrings of the fit functions)."""
+  sequential fits on one device (see the docstrings of the fit functions).
+
+  aggregates (batches only): (aggregate names, csr, prep) -- the group table of `aggregate_groups`
+  and the `PreparedBatch` of the shared calendar.  The running sums of csrc/ci_pool.h are then
+  accumulated in numpy, series by series in order, from every fit's data-scale trajectories in
+  float64 (same order, same formula), before its draws are dropped."""
   opts = dataclasses.replace(data_options, outcome_column=outcome_column)
   base_seed = lib._sanitize_seed(seed)   # pylint: disable=protected-access
   analyses = []
+  host_pool, extra = None, {}
+  if aggregates is not None:
+    agg_names, csr, prep = aggregates
+    host_pool = HostPool(csr)
   for b, frame in enumerate(frames):
     seed_b = base_seed if shared_streams else _native.series_stream_key(base_seed, b)
+    if host_pool is not None:
+      extra = dict(_trajectory_sink=lambda *a, b=b: host_pool.add(b, *a))
     one = lib.fit_causalimpact(frame, periods[b][0], periods[b][1], alpha=alpha, seed=seed_b,
                                data_options=opts, model_options=model_options,
-                               inference_options=inference_options)
+                               inference_options=inference_options, **extra)
     analyses.append(dataclasses.replace(one, posterior_samples=None))   # (draws are not kept)
-  return PerSeriesBatchAnalysis(names, alpha, analyses)
+  res = PerSeriesBatchAnalysis(names, alpha, analyses)
+  if host_pool is not None:
+    ranks = lib._summary_ranks(host_pool.pooled.shape[1], (alpha / 2.0, 1.0 - alpha / 2.0))   # pylint: disable=protected-access
+    devs = list(inference_options.devices) if inference_options.devices else [0]
+    res.aggregates, res.aggregate_summary = _aggregate_analyses(
+        agg_names, csr, host_pool.pooled, np.stack(host_pool.means), prep, outcome_column, alpha,
+        ranks, devs[0])
+  return res
 
 
 @dataclasses.dataclass
@@ -708,7 +957,7 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
               model_options=model_options, inference_options=inference_options)
 
 
-def _run_launch(launch, kind: str, fit: _Fit):
+def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None):
   """One launch of the Gibbs sampler and its summaries on the device.  launch: (device, key,
   positions) as `panel_launches` lists them; kind: the session the positions run in --
     "ordinary"         `_native.Session`: series b of the launch is keyed by positions[0] + b, hence
@@ -721,7 +970,9 @@ def _run_launch(launch, kind: str, fit: _Fit):
                        True, design 0, observed NaN, flags 0.
   Returns (out, dsum, csum): `fetch` of posterior_means [n, C, T] and `_DRAW_SCALARS` [n, C, S],
   `summarize`, and `summarize_components` (None unless InferenceOptions.components).  Every array
-  keeps the series axis, and T is the longest series of the launch on every route."""
+  keeps the series axis, and T is the longest series of the launch on every route.
+  chain (batches with aggregates): the launch's pool step runs after `summarize`, the session still
+  open."""
   dev, _, ids = launch
   ids = np.asarray(ids, dtype=np.int64)
   mo, io = fit.model_options, fit.inference_options
@@ -760,6 +1011,8 @@ def _run_launch(launch, kind: str, fit: _Fit):
     if len(ids) == 1:        # (`summarize` drops the series axis of a session of one series)
       dsum = {k: v[None] for k, v in dsum.items()}
     csum = sess.summarize_components(scale, shift, fit.ranks) if io.components else None
+    if chain is not None:
+      chain.step(launch, lambda groups, init: sess.pool_trajectories(scale, shift, groups, init))
   finally:
     sess.close()
   if stride != T:            # (back at the stride of the longest series)
@@ -768,7 +1021,7 @@ def _run_launch(launch, kind: str, fit: _Fit):
   return out, dsum, csum
 
 
-def _run_hmc_launch(launch, fit: _Fit):
+def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None):
   """`_run_launch` for the one-launch HMC path (`_hmc.fit_hmc_batch`: B x chains HMC chains, then
   the latent paths, the predictive trajectories and their summary on the device): consecutive
   positions of a batch, series b keyed by positions[0] + b.  It keeps no latent draws, hence no
@@ -777,13 +1030,18 @@ def _run_hmc_launch(launch, fit: _Fit):
   dev, _, ids = launch
   ids = np.asarray(ids, dtype=np.int64)
   mo, io = fit.model_options, fit.inference_options
+  scale, shift = fit.scale[ids], fit.shift[ids]
+  pool = None
+  if chain is not None:
+    pool = lambda sess: chain.step(   # pylint: disable=unnecessary-lambda-assignment
+        launch, lambda groups, init: sess.pool_trajectories(scale, shift, groups, init))
   res = _hmc.fit_hmc_batch(
       fit.y[ids], fit.mask[ids], None if fit.design is None else fit.design[ids],
       [fit.params[b] for b in ids], has_slope=mo.local_linear_trend, num_results=io.num_results,
       num_warmup=io.num_warmup_steps, num_chains=io.num_chains, seed=fit.seed, device=dev,
       series_offset=int(ids[0]), shared_streams=fit.shared_streams, prior=io.hmc_prior,
-      summary=dict(scale=fit.scale[ids], shift=fit.shift[ids], observed=fit.observed[ids],
-                   flags=fit.flags, ranks=fit.ranks))
+      summary=dict(scale=scale, shift=shift, observed=fit.observed[ids],
+                   flags=fit.flags, ranks=fit.ranks), after_summary=pool)
   return {k: res[k] for k in ("posterior_means", *_DRAW_SCALARS)}, res["summary"], None
 
 
@@ -839,7 +1097,8 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
                            inference_options: Optional[lib.InferenceOptions] = None,
                            index: Optional[pd.Index] = None,
                            names: Optional[Sequence[Any]] = None,
-                           shared_streams: bool = False) -> CausalImpactBatchAnalysis:
+                           shared_streams: bool = False,
+                           aggregates=None) -> CausalImpactBatchAnalysis:
   """`fit_causalimpact` for B series at once.
 
   data: a sequence of DataFrames with identical index and column layout (outcome first, or
@@ -878,6 +1137,27 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   `hmc_init="vi"`, float64, `standardize_data=False`) is fitted series by series through
   `fit_causalimpact`, keyed as above (`hmc_batch_route`).  With `shared_streams=True` series b
   equals `fit_causalimpact(..., sampler="hmc")` on it alone on either route.
+
+  aggregates: the POOLED effect of groups of series -- the total over all geos, per region -- with
+  its credible bands.  A mapping {aggregate name: members}; members are a sequence of series names
+  (entries of `names`; weight 1), a mapping {series name: weight}, or the string "all".  The effect
+  of a group is that of its pooled outcome y_g = sum_b w_b y_b: interval ends do not add (a sum of
+  2.5 % quantiles is not the 2.5 % quantile of the sum), so the members' predictive trajectories are
+  added draw by draw -- draw n of the group is sum_b w_b * (draw n of series b on the data scale),
+  over b ascending in float64 -- on the device that holds them (csrc/ci_pool.h; the [B, draws, T]
+  trajectories are never downloaded), and the [draws, T] sums are summarised like a single series'.
+  The sum is handed from launch to launch in series order, so the result does not depend on how the
+  batch is cut into launches and devices, bit for bit.  Series are independent given their own
+  data, and so are their default random streams: draw n of every series pairs up to a draw of the
+  joint posterior.  `shared_streams=True` is refused with aggregates: common random numbers make the
+  Monte-Carlo errors of all series move together.  The result then has `aggregates` ({name:
+  CausalImpactAnalysis} with the reference's `series` and `summary` frames of the pooled outcome;
+  `plot` takes it as any other; no `posterior_samples`) and `aggregate_summary` (the 15 summary
+  columns indexed by (aggregate, average|cumulative)); both are None without the argument, and
+  nothing else changes with it.  The pooled outcome is NaN wherever a member's is.  ValueError for an
+  unknown series name, a member listed twice, a weight that is not finite or a group without a
+  member of non-zero weight.  Batches fitted series by series (float64, raw scale, most HMC) add up
+  the same sum in numpy from every fit's trajectories.
   """
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
@@ -895,6 +1175,7 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     index = first.index
   B = values.shape[0]
   names = list(range(B)) if names is None else list(names)
+  agg = None if aggregates is None else _check_aggregates(aggregates, names, shared_streams)
   hmc = inference_options.sampler == "hmc"
   # float64 and raw-scale batches go series by series; every other batch is standardised float32
   per_series = (cid._as_numpy_dtype(data_options.dtype) == np.float64   # pylint: disable=protected-access
@@ -909,9 +1190,11 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
         P=0 if prep.design is None else prep.design.shape[2],
         hmc_init=inference_options.hmc_init) == "per_series")
   if per_series:
+    if agg is not None:   # (the shared calendar: pooled outcome, window flags)
+      agg = (*agg, prepare_batch(values, index, pre_period, post_period, data_options.standardize_data))
     return _fit_per_series((pd.DataFrame(values[b], index=index, columns=columns) for b in range(B)),
                            [(pre_period, post_period)] * B, names, columns[0], alpha, seed,
-                           data_options, model_options, inference_options, shared_streams)
+                           data_options, model_options, inference_options, shared_streams, agg)
   y = _sampler_outcome(prep, data_options)
   with np.errstate(invalid="ignore"):
     pre_sd = np.nanstd(y[:, :prep.num_pre], axis=1, ddof=1)
@@ -927,12 +1210,22 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
                                   inference_options.num_chains, inference_options.num_results)
     launches = [(dev, key, ids[lo:lo + step]) for dev, key, ids in launches
                 for lo in range(0, len(ids), step)]
-    run = lambda launch: _run_hmc_launch(launch, fit)          # pylint: disable=unnecessary-lambda-assignment
+  chain = None if agg is None else _PoolChain(launches, agg[1])
+  if hmc:
+    run = lambda launch: _run_hmc_launch(launch, fit, chain)          # pylint: disable=unnecessary-lambda-assignment
   else:
-    run = lambda launch: _run_launch(launch, "ordinary", fit)   # pylint: disable=unnecessary-lambda-assignment
-  means, dsum, diag_draws, csum = _assemble(launches, run, B, T)
-  return CausalImpactBatchAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
-                                   csum)
+    run = lambda launch: _run_launch(launch, "ordinary", fit, chain)   # pylint: disable=unnecessary-lambda-assignment
+  means, dsum, diag_draws, csum = _assemble(launches, run if chain is None else chain.guarded(run),
+                                            B, T)
+  res = CausalImpactBatchAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
+                                  csum)
+  if chain is not None:
+    # the posterior means on the data scale with the statistics every series' own frame uses
+    mu, sd = scaler_stats(prep.values[:, prep.model_rows[:prep.num_pre], 0])
+    res.aggregates, res.aggregate_summary = _aggregate_analyses(
+        agg[0], agg[1], chain.result(), means.astype(np.float64) * sd[:, None] + mu[:, None], prep,
+        columns[0], alpha, fit.ranks, launches[0][0])
+  return res
 
 
 def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float = 0.05, seed=None,
@@ -965,7 +1258,11 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   its position in the PANEL, whatever group or device it lands in; `shared_streams=True` keys by
   chain only, and series b then equals `fit_causalimpact` on its frame with its periods and this
   seed (bit for bit in every array the session returns over its own steps); without it series 0
-  does, and series b equals the single fit seeded with `_native.series_stream_key(seed, b)`."""
+  does, and series b equals the single fit seeded with `_native.series_stream_key(seed, b)`.
+
+  There is no `aggregates` argument here: series with their own calendars share no time axis to add
+  their trajectories on (`fit_causalimpact_batch(aggregates=...)` pools series of ONE calendar).  A
+  pooled effect of a panel in event time is not provided."""
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
   frames, columns = _frames_outcome_first(data, data_options)

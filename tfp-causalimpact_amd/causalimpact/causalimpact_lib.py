@@ -179,6 +179,10 @@ def fit_causalimpact(data: pd.DataFrame,
   inference_options = inference_options if inference_options is not None else InferenceOptions()
   experimental_model = kwargs.pop("experimental_model", None)
   kwargs.pop("experimental_tf_function_cache_key_addition", 0)   # no graph cache to key
+  # (internal, batch.py: the running sums of a batch's aggregates on the routes that fit series by
+  #  series) called with (posterior_means [T], posterior_trajectories [draws, T], scale, shift):
+  #  data-scale value = array * scale + shift
+  trajectory_sink = kwargs.pop("_trajectory_sink", None)
   if kwargs:
     raise TypeError(f"Received unknown {kwargs=}")
   if experimental_model is not None:
@@ -206,7 +210,11 @@ def fit_causalimpact(data: pd.DataFrame,
       devices=inference_options.devices, local_linear_trend=model_options.local_linear_trend,
       sampler=inference_options.sampler, summary_request=request,
       hmc_init=inference_options.hmc_init, hmc_prior=inference_options.hmc_prior,
-      kernel_flags=inference_options.kernel_flags, component_request=comp_request)
+      kernel_flags=inference_options.kernel_flags, component_request=comp_request,
+      keep_trajectories=trajectory_sink is not None)
+  if trajectory_sink is not None:
+    base = request if request is not None else _device_summary_request(ci_data, alpha)
+    trajectory_sink(posterior_means, posterior_trajectories, base["scale"], base["shift"])
   # (draws pooled on the host -- several devices, float64, HMC -- were summarised inside
   #  _run_sampler, in the sampler's internal units)
   if device_summary is not None:
@@ -442,12 +450,15 @@ def map_by_device(fn, work):
 def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps, model=None,
                  dtype=np.float32, seasons=(), num_chains=1, devices=None,
                  local_linear_trend=False, sampler="gibbs", summary_request=None,
-                 hmc_init="gibbs", hmc_prior="slab", kernel_flags=0, component_request=None):
+                 hmc_init="gibbs", hmc_prior="slab", kernel_flags=0, component_request=None,
+                 keep_trajectories=False):
   """_train_causalimpact_sts plus, when `summary_request` is given (single device, Gibbs), the
   on-device summary of the predictive draws; the [draws, T] trajectories then stay in HBM and
   are returned as None.  `component_request` (scale, shift, quantiles): on that route the component
   summary of the session (ci_session_summarize_components) is left in it under "summary", with the
-  "ranks" it was taken at; on every other route the dict comes back as it went in."""
+  "ranks" it was taken at; on every other route the dict comes back as it went in.
+  `keep_trajectories`: the trajectories are wanted on the host; the fit then takes the route of
+  draws pooled on the host, whose summary runs the same kernels on the same values."""
   if model is not None:
     raise NotImplementedError("custom tfp.sts models are not supported by the HIP path")
   seed_pair = _sanitize_seed(seed)
@@ -508,7 +519,7 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
       # float64 compute (csrc/ci_gibbs64.h): the sequential kernel, every buffer float64
       return _native.fit_gibbs_f64(pb, y[None], mask[None], None if design is None else design[None],
                                    season_change, _native.make_params([params]))
-    if summary_request is not None and len(devs) == 1:
+    if summary_request is not None and len(devs) == 1 and not keep_trajectories:
       sess = _native.Session(pb, y[None], mask[None], None if design is None else design[None],
                              season_change, _native.make_params([params]))
       try:

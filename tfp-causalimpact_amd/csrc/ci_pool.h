@@ -1,0 +1,143 @@
+// ci_pool.h -- weighted sums over groups of series of a session's resident predictive trajectories
+// (ci_session_pool_trajectories, ci_ll_session_pool_trajectories): the draws of a POOLED effect.
+// A sum of per-series quantiles is not a quantile of the sum; the band of "all geos" or "region
+// north" needs the sum over series draw by draw, and a batch keeps its [B, N, T] float32 draws in
+// HBM only.  One streaming pass reads them where they are.
+//
+// Arithmetic is float64 and ordered like the numpy loop it stands for:
+//   acc = init (or 0.0);  for the members b of the group, ascending:
+//     v = traj[b] * scale[b] + shift[b]      the value ci_session_summarize forms (two roundings)
+//     acc = acc + w * v                      (two roundings)
+// so the result does not depend on the launch geometry, and a batch cut into several sessions
+// continues one running sum through `init`, bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ci {
+
+constexpr int POOL_NT = 256;       // threads per workgroup, four consecutive elements each
+constexpr int POOL_AHEAD = 8;      // members whose loads are in flight ahead of the dependent adds
+
+// One (group, member) entry of the sparse weight table.
+struct PoolEntry {
+  long long start;                 // first element of the member's [N*T] block in the trajectories
+  double w, scale, shift;
+};
+
+// float4 loads want 16-byte alignment; series b starts at element b * N*T, which is not a multiple
+// of 4 for odd b when N*T is not.  A misaligned member is read as the two aligned float4 that
+// cover the thread's four elements (the second is its neighbour's first: an L1 hit), and the four
+// are picked by the member's offset m = 1..3, which is the same for every thread.
+__device__ __forceinline__ void pool_pick(const float4 a, const float4 b, unsigned m, float v[4]) {
+  const float c[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = m == 0u ? c[j] : (m == 1u ? c[j + 1] : (m == 2u ? c[j + 2] : c[j + 3]));
+}
+
+// CNT consecutive members of a group added to a thread's four accumulators, in order: the CNT (or
+// 2 CNT) vector loads first, then the dependent float64 operations.  `en`: the members' entries;
+// e: the thread's first element; base_m: the offset of `traj` from the 16-byte grid, in floats.
+template <bool ALIGNED, int CNT>
+__device__ __forceinline__ void pool_chunk(const float* __restrict__ traj,
+                                           const PoolEntry* __restrict__ en, long long e,
+                                           unsigned base_m, double acc[4]) {
+  float4 lo[CNT], hi[CNT];
+#pragma unroll
+  for (int u = 0; u < CNT; ++u) {
+    const long long at = en[u].start + e;
+    if (ALIGNED) {
+      lo[u] = *reinterpret_cast<const float4*>(traj + at);
+    } else {
+      const long long a = at - (long long)((base_m + (unsigned)at) & 3u);
+      lo[u] = *reinterpret_cast<const float4*>(traj + a);
+      hi[u] = *reinterpret_cast<const float4*>(traj + a + 4);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < CNT; ++u) {
+    const PoolEntry m = en[u];
+    float v[4];
+    if (ALIGNED) {
+      v[0] = lo[u].x; v[1] = lo[u].y; v[2] = lo[u].z; v[3] = lo[u].w;
+    } else {
+      pool_pick(lo[u], hi[u], (base_m + (unsigned)m.start) & 3u, v);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const double x = __dadd_rn(__dmul_rn((double)v[j], m.scale), m.shift);
+      acc[j] = __dadd_rn(acc[j], __dmul_rn(m.w, x));
+    }
+  }
+}
+
+// grid (ceil(NT / (4 POOL_NT)), groups of this launch): one group and a contiguous slice of the
+// flattened N*T axis per workgroup.  traj: the [N*T] blocks of all series of the session; entries
+// offsets[g] .. offsets[g + 1] are the members of group g; pooled [groups, NT] float64 holds the
+// initial accumulator when has_init, and the result afterwards.
+// ALIGNED: every member block starts 16-byte aligned (N*T a multiple of 4 on an aligned base):
+// one float4 per member and thread.
+template <bool ALIGNED>
+__global__ __launch_bounds__(POOL_NT) void pool_kernel(long long NT,
+                                                       const float* __restrict__ traj,
+                                                       const int* __restrict__ offsets,
+                                                       const PoolEntry* __restrict__ entries,
+                                                       int has_init, double* __restrict__ pooled) {
+  const long long e = ((long long)blockIdx.x * POOL_NT + threadIdx.x) * 4;
+  if (e >= NT) return;
+  const int g = blockIdx.y;
+  const int k0 = offsets[g], k1 = offsets[g + 1];
+  double* out = pooled + (size_t)g * NT + e;
+  const int left = NT - e < 4 ? (int)(NT - e) : 4;          // elements of this thread
+  const bool out16 = left == 4 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0u;
+  const unsigned base_m = (unsigned)(reinterpret_cast<uintptr_t>(traj) >> 2) & 3u;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  if (has_init) {
+    if (out16) {
+      const double2 i0 = *reinterpret_cast<const double2*>(out);
+      const double2 i1 = *reinterpret_cast<const double2*>(out + 2);
+      acc[0] = i0.x; acc[1] = i0.y; acc[2] = i1.x; acc[3] = i1.y;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < left) acc[j] = out[j];
+    }
+  }
+  // The vector path reads [a, a + 4) (ALIGNED) or [a, a + 8) with a = the member's first element
+  // rounded down to a multiple of 4: inside the member's block but for up to 3 elements before it
+  // (the end of the series in front; none in front of series 0 on an aligned base) and up to 4 after
+  // the thread's own, which stay inside the block while e + 8 <= NT.
+  const bool vec = ALIGNED ? left == 4 : (e + 8 <= NT && (e >= 4 || base_m == 0u));
+  if (vec) {
+    // whole chunks of POOL_AHEAD members, then the rest in chunks of 4, 2 and 1: every load is of a
+    // member of the group, and the loads of a chunk are issued together, without a branch between
+    int k = k0;
+    for (; k + POOL_AHEAD <= k1; k += POOL_AHEAD) pool_chunk<ALIGNED, POOL_AHEAD>(traj, entries + k, e, base_m, acc);
+    if (k + 4 <= k1) { pool_chunk<ALIGNED, 4>(traj, entries + k, e, base_m, acc); k += 4; }
+    if (k + 2 <= k1) { pool_chunk<ALIGNED, 2>(traj, entries + k, e, base_m, acc); k += 2; }
+    if (k < k1) pool_chunk<ALIGNED, 1>(traj, entries + k, e, base_m, acc);
+  } else {
+    // the last elements of the slice (and the first four on a misaligned base): element by element
+    for (int k = k0; k < k1; ++k) {
+      const PoolEntry en = entries[k];
+      const float* p = traj + en.start + e;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j < left) {
+          const double x = __dadd_rn(__dmul_rn((double)p[j], en.scale), en.shift);
+          acc[j] = __dadd_rn(acc[j], __dmul_rn(en.w, x));
+        }
+      }
+    }
+  }
+  if (out16) {
+    *reinterpret_cast<double2*>(out) = make_double2(acc[0], acc[1]);
+    *reinterpret_cast<double2*>(out + 2) = make_double2(acc[2], acc[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < left) out[j] = acc[j];
+  }
+}
+
+}  // namespace ci

@@ -1,9 +1,12 @@
 // ci_summary.hip -- the on-device summaries behind the C-ABI (kernels: ci_summary.h,
 // ci_components.h): ci_session_summarize, ci_session_summarize_components,
 // ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] on
-// draws the caller hands in.
+// draws the caller hands in; ci_session_pool_trajectories and ci_ll_session_pool_trajectories
+// (kernel: ci_pool.h) on the trajectories a session holds.
+#include <cmath>
 #include <vector>
 
+#include "ci_pool.h"
 #include "ci_session.h"
 #include "ci_summary.h"
 
@@ -130,7 +133,87 @@ static int summarize_draws_impl(int32_t device, int32_t num_draws, int32_t T, co
                                  num_ranks, ranks, value_order, cum_order, per_draw, per_draw_order);
 }
 
+// ci_session_pool_trajectories / ci_ll_session_pool_trajectories: weighted sums over groups of
+// series of the [B, N, T] float32 trajectories resident in HBM.  Everything is checked before the
+// first device call.  The groups pass through the summary's `value` matrix (B * N*T doubles,
+// allocated on first use and kept), as many at a time as fit it: no device memory beyond the
+// scratch but the weight table.
+static int pool_resident(int device, hipStream_t stream, SummScratch& w, int B, int T, int N,
+                         const float* traj, const double* scale, const double* shift, int32_t G,
+                         const int32_t* offsets, const int32_t* members, const double* weights,
+                         const double* init, double* out) {
+  if (G < 1) return fail("num_groups must be >= 1, got %d", G);
+  if (offsets[0] != 0) return fail("offsets[0] must be 0, got %d", offsets[0]);
+  for (int g = 0; g < G; ++g) {
+    if (offsets[g + 1] < offsets[g])
+      return fail("offsets must not decrease: offsets[%d] = %d after %d", g + 1, offsets[g + 1], offsets[g]);
+    if (offsets[g + 1] - offsets[g] > B)
+      return fail("group %d has %d members, the session %d series", g, offsets[g + 1] - offsets[g], B);
+    for (int k = offsets[g]; k < offsets[g + 1]; ++k) {
+      if (members[k] < 0 || members[k] >= B)
+        return fail("group %d: member %d out of range [0, %d)", g, members[k], B);
+      if (k > offsets[g] && members[k] <= members[k - 1])
+        return fail("group %d: members must be strictly ascending (%d after %d)", g, members[k], members[k - 1]);
+      if (!std::isfinite(weights[k])) return fail("group %d: the weight of member %d is not finite", g, members[k]);
+    }
+  }
+  const long long NT = (long long)N * T;
+  std::vector<ci::PoolEntry> entries((size_t)offsets[G]);
+  for (int k = 0; k < offsets[G]; ++k) {
+    const int b = members[k];
+    entries[k] = ci::PoolEntry{(long long)b * NT, weights[k], scale[b], shift[b]};
+  }
+  HIP_TRY(hipSetDevice(device));
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  const int per_pass = G < B ? G : (B < 65535 ? B : 65535);       // groups that fit `value` (grid.y)
+  DevBuf<ci::PoolEntry> d_entries;
+  DevBuf<int> d_offsets;
+  HIP_TRY(d_entries.alloc(entries.size() ? entries.size() : 1));
+  HIP_TRY(d_offsets.alloc((size_t)G + 1));
+  if (!entries.empty())
+    HIP_TRY(hipMemcpyAsync(d_entries.p, entries.data(), entries.size() * sizeof(ci::PoolEntry),
+                           hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_offsets.p, offsets, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+  const bool aligned = NT % 4 == 0 && (reinterpret_cast<uintptr_t>(traj) & 15u) == 0u;
+  const unsigned slices = (unsigned)((NT + 4 * ci::POOL_NT - 1) / (4 * ci::POOL_NT));
+  for (int g0 = 0; g0 < G; g0 += per_pass) {
+    const int ng = G - g0 < per_pass ? G - g0 : per_pass;
+    const size_t bytes = (size_t)ng * NT * sizeof(double);
+    if (init)
+      HIP_TRY(hipMemcpyAsync(w.value.p, init + (size_t)g0 * NT, bytes, hipMemcpyHostToDevice, stream));
+    if (aligned)
+      hipLaunchKernelGGL(ci::pool_kernel<true>, dim3(slices, ng), dim3(ci::POOL_NT), 0, stream, NT, traj,
+                         d_offsets.p + g0, d_entries.p, init ? 1 : 0, w.value.p);
+    else
+      hipLaunchKernelGGL(ci::pool_kernel<false>, dim3(slices, ng), dim3(ci::POOL_NT), 0, stream, NT, traj,
+                         d_offsets.p + g0, d_entries.p, init ? 1 : 0, w.value.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out + (size_t)g0 * NT, w.value.p, bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+  return 0;
+}
+
 extern "C" {
+
+int ci_session_pool_trajectories(ci_session* s, const double* scale, const double* shift,
+                                 int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                 const double* weights, const double* init, double* out) {
+  if (!s || !scale || !shift || !offsets || !members || !weights || !out) return fail("NULL argument");
+  if (!s->ran) return fail("ci_session_pool_trajectories needs a finished ci_session_run");
+  const ci_problem& pb = s->pb;
+  return pool_resident(pb.device, s->stream, s->summ, pb.num_series, pb.T, pb.num_chains * pb.num_results,
+                       s->o_traj.p, scale, shift, num_groups, offsets, members, weights, init, out);
+}
+
+int ci_ll_session_pool_trajectories(ci_ll_session* s, const double* scale, const double* shift,
+                                    int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                    const double* weights, const double* init, double* out) {
+  if (!s || !scale || !shift || !offsets || !members || !weights || !out) return fail("NULL argument");
+  if (!s->h_ran) return fail("ci_ll_session_pool_trajectories needs a finished ci_ll_session_hmc_run");
+  return pool_resident(s->device, s->stream, s->summ, s->B, s->T, s->h_C * s->h_S, s->h_traj.p, scale,
+                       shift, num_groups, offsets, members, weights, init, out);
+}
 
 int ci_session_summarize(ci_session* s, const double* scale, const double* shift,
                          const double* observed, const uint8_t* flags, int32_t num_ranks,
