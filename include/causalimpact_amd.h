@@ -347,6 +347,32 @@ int ci_session_summarize_components(ci_session* session, const double* scale, co
 int ci_session_pool_trajectories(ci_session* session, const double* scale, const double* shift,
                                  int32_t num_groups, const int32_t* offsets, const int32_t* members,
                                  const double* weights, const double* init, double* out);
+/* ci_session_pool_trajectories over WINDOWS of the members' trajectories, every member shifted to a
+ * start of its own: the draws of a pooled effect in EVENT TIME, for series with their own calendars
+ * (a panel) aligned on each one's treatment start.  Additive: CI_ABI_VERSION stays 5; look the
+ * symbol up (dlsym) where an older library may be met.  Groups, members and weights as above;
+ * first[k] (per entry, parallel to members) is the step of member k that lands in column 0 of its
+ * group, width[g] the number of columns of group g, out_stride the row length of init and out
+ * (>= every width).  For every group g, draw n and column c < width[g], all in float64:
+ *   acc = init[g, n, c]                          (0.0 when init is NULL)
+ *   for the members k of g, ascending, b = members[k]:
+ *     v   = trajectory[b, n, first[k] + c] * scale[b] + shift[b]     (two roundings)
+ *     acc = acc + weights[k] * v                                     (two roundings, no fused multiply-add)
+ *   out[g, n, c] = acc
+ * which a plain loop on the host reproduces bit for bit.  Columns c >= width[g] are written as 0.0
+ * and their values in init do not matter.  init and out are host arrays [num_groups, N, out_stride]
+ * float64 (init may be NULL, and may be out itself); several sessions continue one running sum
+ * through them as above, in the order of the calls.  With first = 0 and width = out_stride = T
+ * everywhere the result is that of ci_session_pool_trajectories, bit for bit.  Ordinary and both
+ * kinds of ragged sessions are taken; T is the session's stride.  The groups pass through the
+ * scratch of ci_session_summarize, min(num_groups, B) at a time: no device memory beyond it but the
+ * tables.  No load touches memory outside the trajectories.
+ * Checked before any device call: everything ci_session_pool_trajectories checks, no NULL argument
+ * but init, width[g] in [1, out_stride] and <= T, first[k] >= 0, first[k] + width[g] <= T. */
+int ci_session_pool_event_trajectories(ci_session* session, const double* scale, const double* shift,
+                                       int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                       const double* weights, const int32_t* first, const int32_t* width,
+                                       int32_t out_stride, const double* init, double* out);
 /* The same summary for draws that are on the host (pooled from several devices / processes, or
  * produced by the HMC path): trajectories [num_draws, T] float32 are uploaded to `device`,
  * summarised there and the (one-series) results returned as above. */

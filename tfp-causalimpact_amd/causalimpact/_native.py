@@ -114,6 +114,10 @@ def load():
   for pool_fn in (L.ci_session_pool_trajectories, L.ci_ll_session_pool_trajectories):
     pool_fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p, C.c_void_p]
+  if hasattr(L, "ci_session_pool_event_trajectories"):   # (additive: a library built before it lacks it)
+    L.ci_session_pool_event_trajectories.argtypes = [
+        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
   L.ci_summarize_draws.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double,
                                    C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -169,6 +173,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_profile", "ci_ll_session_kernel_name",
           "ci_session_summarize", "ci_session_summarize_components", "ci_summarize_draws", "ci_summarize_draws_f64",
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
+          "ci_session_pool_event_trajectories",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
           "ci_ll_session_draw_latents", "ci_ll_session_hmc_run", "ci_ll_session_hmc_fetch",
           "ci_ll_session_algorithmic_bytes", "ci_ll_session_destroy", "ci_ll_session_create_batch",
@@ -356,6 +361,54 @@ def _pool_call(fn, handle, B: int, N: int, T: int, scale, shift, groups, init) -
   out = pinned_empty((G, N, T), np.float64) if big else np.empty((G, N, T), np.float64)
   _check(fn(handle, sc.ctypes.data, sh.ctypes.data, G, offsets.ctypes.data, members.ctypes.data,
             weights.ctypes.data, _ptr(init), out.ctypes.data))
+  return out
+
+
+def event_groups_csr(groups, num_series: int):
+  """The tables of `pool_event_trajectories`: (offsets [G + 1], members, weights, first, width).
+  groups: one (members, width) pair per group, members a mapping {position of a series in the
+  session: (weight, first)} -- `first` the step of that series that lands in column 0 of the group --
+  and width the number of columns of the group.  The first three arrays are `groups_csr`'s (members
+  ascending, those of zero weight left out, the same refusals); first int32 is parallel to members,
+  width int32 [G]."""
+  groups = [(dict(members), int(width)) for members, width in groups]
+  offsets, members, weights = groups_csr(
+      [{b: w for b, (w, _) in group.items()} for group, _ in groups], num_series)
+  first = [int(groups[g][0][int(b)][1]) for g in range(len(groups))
+           for b in members[offsets[g]:offsets[g + 1]]]
+  return (offsets, members, weights, np.asarray(first, np.int32),
+          np.asarray([width for _, width in groups], np.int32))
+
+
+def _event_stride(width, out_stride) -> int:
+  stride = int(width.max()) if out_stride is None else int(out_stride)
+  if width.size and (width.min() < 1 or width.max() > stride):
+    raise ValueError(f"every width must be in [1, out_stride = {stride}], got {width.tolist()}")
+  return stride
+
+
+def pool_event_host(trajectories, scale, shift, groups, init=None, out_stride=None) -> np.ndarray:
+  """What `pool_event_trajectories` computes, in numpy: trajectories [B, N, T] (any float type),
+  scale, shift [B], groups as for `event_groups_csr`; returns [G, N, out_stride] float64 (out_stride:
+  the widest group by default).  out[g][:, :width] = init[g][:, :width] + the sum over the members,
+  ascending, of weight * (trajectory[:, first : first + width] * scale + shift), one rounding per
+  operation; the columns beyond a group's width are 0.0.  The definition the device is compared
+  with."""
+  tr = np.asarray(trajectories)
+  B = tr.shape[0]
+  offsets, members, weights, first, width = event_groups_csr(groups, B)
+  stride = _event_stride(width, out_stride)
+  sc = np.broadcast_to(np.asarray(scale, np.float64), (B,))
+  sh = np.broadcast_to(np.asarray(shift, np.float64), (B,))
+  out = np.zeros((width.size, tr.shape[1], stride), np.float64)
+  for g, W in enumerate(width):
+    if init is not None:
+      out[g, :, :W] = np.asarray(init, np.float64)[g, :, :W]
+    for k in range(offsets[g], offsets[g + 1]):
+      b, f = members[k], first[k]
+      if f < 0 or f + W > tr.shape[2]:
+        raise ValueError(f"group {g}: member {b} from step {f} over {W} columns leaves [0, {tr.shape[2]})")
+      out[g, :, :W] = out[g, :, :W] + weights[k] * (tr[b, :, f:f + W].astype(np.float64) * sc[b] + sh[b])
   return out
 
 
@@ -608,6 +661,35 @@ class Session:
     pb = self.pb
     return _pool_call(self._lib.ci_session_pool_trajectories, self._h, pb.num_series,
                       pb.num_chains * pb.num_results, pb.T, scale, shift, groups, init)
+
+  def pool_event_trajectories(self, scale, shift, groups, init=None, out_stride=None) -> np.ndarray:
+    """`pool_trajectories` over windows of the members' trajectories, every member from a step of its
+    own (ci_session_pool_event_trajectories): the draws of a pooled effect in event time.  groups:
+    one (members, width) pair per group, members a mapping {position in the session: (weight,
+    first)} (`event_groups_csr`).  out[g, n, c] = init[g, n, c] + the sum over the members b of group
+    g, ascending, of weight * (trajectory[b, n, first + c] * scale[b] + shift[b]) for c < width,
+    float64, one rounding per operation (`pool_event_host` is the same loop in numpy); the columns
+    from a group's width to out_stride (default: the widest group) are 0.0.  init: [G, N, out_stride]
+    float64 or None.  Returns [G, N, out_stride] float64."""
+    fn = getattr(self._lib, "ci_session_pool_event_trajectories", None)
+    if fn is None:
+      raise NativeError("the loaded library has no ci_session_pool_event_trajectories: rebuild it")
+    pb = self.pb
+    B, N = pb.num_series, pb.num_chains * pb.num_results
+    sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (B,)))
+    sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.float64), (B,)))
+    offsets, members, weights, first, width = event_groups_csr(groups, B)
+    G, stride = width.size, _event_stride(width, out_stride)
+    if init is not None:
+      init = np.ascontiguousarray(init, dtype=np.float64)
+      if init.shape != (G, N, stride):
+        raise ValueError(f"`init` must be {[G, N, stride]}, got {list(init.shape)}")
+    big = G * N * stride * 8 > (1 << 20)
+    out = pinned_empty((G, N, stride), np.float64) if big else np.empty((G, N, stride), np.float64)
+    _check(fn(self._h, sc.ctypes.data, sh.ctypes.data, G, offsets.ctypes.data, members.ctypes.data,
+              weights.ctypes.data, first.ctypes.data, width.ctypes.data, stride, _ptr(init),
+              out.ctypes.data))
+    return out
 
   def close(self):
     if self._h:

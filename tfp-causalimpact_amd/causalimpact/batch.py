@@ -20,7 +20,9 @@ series (all geos, a region) with its credible bands: the weighted sum of the mem
 trajectories draw by draw, formed on the device that holds them (csrc/ci_pool.h) and chained from
 launch to launch in series order, then summarised like any single series.
 
-`fit_causalimpact_panel` is the same for series with their own index, length and periods.
+`fit_causalimpact_panel` is the same for series with their own index, length and periods;
+`fit_causalimpact_panel(..., event_aggregates={name: members})` pools groups of them in EVENT TIME,
+every series aligned on its own treatment start (csrc/ci_pool_event.h, `_PanelPoolChain`).
 
 Both fit functions are one pipeline over different preparations (`prepare_batch`, one shared
 calendar; `prepare_panel`, padded to the longest series):
@@ -32,6 +34,9 @@ calendar; `prepare_panel`, padded to the longest series):
     session from creation to close, arrays back with the series axis at the launch's stride;
   * `aggregate_groups`, `_PoolChain`, `_aggregate_analyses`: the aggregates of a batch -- the group
     table, the running sums handed from launch to launch, the frames of every group;
+  * `event_axes` / `event_plan`, `_PanelPoolChain`, `_event_aggregate_analyses`: their twins for
+    the event-time aggregates of a panel -- every group's axis around its members' own treatment
+    starts, the running sums over launches whose positions interleave, the frames on `event_time`;
   * `_assemble`: the launches of a device in turn, the devices side by side
     (`causalimpact_lib.map_by_device`), then the [B, ..., T_max] blocks of the containers.
 """
@@ -849,6 +854,235 @@ def _aggregate_analyses(agg_names, csr, pooled: np.ndarray, means: np.ndarray, p
 
 
 # ------------------------------------------------------------------------------------------
+# Event-time aggregates: the pooled effect of groups of series of a panel
+# ------------------------------------------------------------------------------------------
+# The series of a panel have their own calendars; what they share is EVENT TIME, the number of rows
+# since each one's own treatment start.  These are the twins of the batch's helpers above for sums
+# over shifted windows of the members' steps (csrc/ci_pool_event.h).
+@dataclasses.dataclass
+class EventAxis:
+  """The event-time axis of one group: tau = -L .. H - 1, column c of the group is step
+  first[k] + c of its k-th member (members as the group table lists them: ascending positions,
+  those of zero weight left out)."""
+  L: int              # steps before the treatment start that every member has
+  gap: int            # the longest gap between a member's pre-period and its treatment start
+  Hwin: int           # the shortest post-period window
+  H: int              # steps from the treatment start on that every member has
+  first: np.ndarray   # int32, per member: its step at column 0 (tau = -L)
+
+  @property
+  def width(self) -> int:
+    return self.L + self.H
+
+  @property
+  def index(self) -> pd.Index:
+    return pd.Index(np.arange(-self.L, self.H, dtype=np.int64), name="event_time")
+
+  @property
+  def flags(self) -> np.ndarray:
+    """The window flags of the pooled series: bit 0 = tau >= 0, bit 1 = 0 <= tau < Hwin."""
+    tau = np.arange(-self.L, self.H)
+    return (tau >= 0).astype(np.uint8) | (((tau >= 0) & (tau < self.Hwin)).astype(np.uint8) << 1)
+
+
+def event_axes(prep: PreparedPanel, csr) -> List[EventAxis]:
+  """The event-time axis of every group of the table `csr` (`aggregate_groups`), from the prepared
+  panel alone.  Series b of T_b model steps starts its treatment at e_b, its first step with bit 0
+  of `flags` set (its pre-period plus gap_b = e_b - num_pre[b] steps), and has a window of win_b
+  steps (bit 1), contiguous from e_b.  Over the members of a group (zero weights are not members):
+  L = min e_b, gap = max gap_b, Hwin = min win_b, H = min (T_b - e_b); member b contributes its
+  steps first_b .. first_b + L + H - 1 with first_b = e_b - L, all inside [0, T_b).  Event time
+  counts the ROWS of a series, not calendar units."""
+  offsets, members, _ = csr
+  B = len(prep.lengths)
+  start = np.zeros(B, np.int64)
+  for b in range(B):
+    after = np.flatnonzero(prep.flags[b, :prep.lengths[b]] & 1)
+    if after.size == 0:
+      raise ValueError(f"series at position {b} has no step from its treatment start on")
+    start[b] = after[0]
+  gaps = start - np.asarray(prep.num_pre, np.int64)
+  windows = np.sum((prep.flags & 2) != 0, axis=1)
+  tails = np.asarray(prep.lengths, np.int64) - start
+  axes = []
+  for g in range(len(offsets) - 1):
+    m = np.asarray(members[offsets[g]:offsets[g + 1]], np.int64)
+    L = int(start[m].min())
+    axes.append(EventAxis(L=L, gap=int(gaps[m].max()), Hwin=int(windows[m].min()),
+                          H=int(tails[m].min()), first=(start[m] - L).astype(np.int32)))
+  return axes
+
+
+def pool_event_weighted(rows: Sequence[np.ndarray], csr, axes: Sequence[EventAxis]) -> List[np.ndarray]:
+  """`pool_weighted` over shifted windows: per group g the [width_g] sum over its members b,
+  ascending, of w[g, b] * rows[b][first_b : first_b + width_g], in float64 with one rounding per
+  operation (NaN wherever a member is NaN).  rows: per series an array over its model steps."""
+  offsets, members, weights = csr
+  out = []
+  for g, axis in enumerate(axes):
+    acc = np.zeros(axis.width)
+    for k, f in zip(range(offsets[g], offsets[g + 1]), axis.first):
+      acc = acc + weights[k] * np.asarray(rows[members[k]], np.float64)[f:f + axis.width]
+    out.append(acc)
+  return out
+
+
+@dataclasses.dataclass
+class EventPlan:
+  """What `fit_causalimpact_panel(event_aggregates=...)` knows before any fit: the group table, the
+  axes, and per group the pooled observed outcome [width] (NaN wherever a member is: gap, tail,
+  missing value) and the `CausalImpactData` of the pooled raw outcome on its `event_time` index."""
+  names: List[Any]
+  csr: Tuple[np.ndarray, np.ndarray, np.ndarray]
+  axes: List[EventAxis]
+  observed: List[np.ndarray]
+  data: List[cid.CausalImpactData]
+
+  @property
+  def stride(self) -> int:
+    """The row length of the accumulators [G, N, stride]: the widest group."""
+    return max(axis.width for axis in self.axes)
+
+
+def event_plan(agg_names, csr, prep: PreparedPanel, outcome_name) -> EventPlan:
+  """The `EventPlan` of a prepared panel.  ValueError, with the aggregate named, when the common
+  axis of a group leaves fewer than 3 pre-period steps (L - gap), and for whatever else
+  `CausalImpactData` refuses about the pooled outcome."""
+  axes = event_axes(prep, csr)
+  model_outcome = [prep.raw[b][prep.model_rows[b], 0] for b in range(len(prep.lengths))]
+  outcome = pool_event_weighted(model_outcome, csr, axes)
+  observed = pool_event_weighted([prep.observed[b, :Tb] for b, Tb in enumerate(prep.lengths)], csr, axes)
+  data = []
+  for name, axis, y in zip(agg_names, axes, outcome):
+    num_pre = axis.L - axis.gap
+    if num_pre < 3:
+      raise ValueError(f"aggregate {name!r}: pre_period must span at least 3 time points on the event "
+                       f"axis its members share. Got {max(num_pre, 0)}")
+    try:
+      # (integer periods are POSITIONS into the index: tau = -L .. -1 - gap and 0 .. Hwin - 1)
+      data.append(cid.CausalImpactData(pd.DataFrame({outcome_name: y}, index=axis.index),
+                                       (0, num_pre - 1), (axis.L, axis.L + axis.Hwin - 1),
+                                       standardize_data=False))
+    except ValueError as e:
+      raise ValueError(f"aggregate {name!r}: {e}") from e
+  return EventPlan(list(agg_names), csr, axes, observed, data)
+
+
+def _check_event_aggregates(event_aggregates, names, shared_streams: bool):
+  """`aggregate_groups` for `event_aggregates`, after the refusal of common random numbers."""
+  if shared_streams:
+    raise ValueError(
+        "`event_aggregates` cannot be combined with shared_streams=True: with common random numbers "
+        "the Monte-Carlo errors of all series are perfectly correlated, and pairing draw n of every "
+        "series is then not a draw from the joint posterior of independent series -- the pooled "
+        "bands would be wrong.  Fit with the default per-series streams.")
+  return aggregate_groups(event_aggregates, names)
+
+
+class EventHostPool:
+  """`HostPool` in event time, for panels that are fitted series by series: `add(b, ...)` for
+  b = 0, 1, ... adds w[g, b] * (trajectories[:, first_b : first_b + width_g] * scale + shift) to
+  pooled[g][:, :width_g] for every group that has b, float64, one rounding per operation.  `pooled`
+  [G, N, stride] float64, 0.0 beyond a group's width; `means`: every series' posterior mean over its
+  own steps on the data scale."""
+
+  def __init__(self, csr, axes: Sequence[EventAxis]):
+    self.csr, self.axes = csr, list(axes)
+    self.stride = max(axis.width for axis in self.axes)
+    self.pooled: Optional[np.ndarray] = None
+    self.means: List[np.ndarray] = []
+
+  def add(self, b: int, posterior_means, trajectories, scale, shift):
+    offsets, members, weights = self.csr
+    scale, shift = np.float64(scale), np.float64(shift)
+    value = np.asarray(trajectories).astype(np.float64) * scale + shift
+    self.means.append(np.asarray(posterior_means).astype(np.float64) * scale + shift)
+    if self.pooled is None:
+      self.pooled = np.zeros((len(self.axes), value.shape[0], self.stride))
+    for g, axis in enumerate(self.axes):
+      k = offsets[g] + int(np.searchsorted(members[offsets[g]:offsets[g + 1]], b))
+      if k < offsets[g + 1] and members[k] == b:
+        f, W = int(axis.first[k - offsets[g]]), axis.width
+        self.pooled[g, :, :W] = self.pooled[g, :, :W] + weights[k] * value[:, f:f + W]
+
+
+class _PanelPoolChain(_PoolChain):
+  """`_PoolChain` for the launches of a panel: the running sums [G, N, stride] of its event-time
+  aggregates.  A class of a panel holds whatever positions fall in it, so the launches do not cut the
+  positions into consecutive runs; they are chained in the order `panel_launches` lists them -- class
+  key ascending, ascending positions within a class, which its split over devices keeps -- and a
+  session adds its members in ascending position.  A group is therefore summed in (class key,
+  position) order: a function of the model and the series alone, the same on any number of devices,
+  and not plain position order when its members fall in different classes.  Every launch waits for
+  an earlier one of the list and every device runs its launches in list order
+  (`causalimpact_lib.map_by_device`), so no wait is circular; a failed launch fails every launch
+  behind it, as in `_PoolChain`."""
+
+  def __init__(self, launches, csr, axes: Sequence[EventAxis]):
+    super().__init__(launches, csr)
+    self.axes = list(axes)
+    self.stride = max(axis.width for axis in self.axes)
+
+  def groups_of(self, ids: Sequence[int]):
+    """The groups cut to the positions `ids` of one launch, whatever they are: per group (members,
+    width) with members {place within the launch: (weight, first)}, empty without a member there."""
+    offsets, members, weights = self.csr
+    place = {int(b): i for i, b in enumerate(ids)}
+    out = []
+    for g, axis in enumerate(self.axes):
+      rows = zip(members[offsets[g]:offsets[g + 1]], weights[offsets[g]:offsets[g + 1]], axis.first)
+      out.append(({place[int(b)]: (float(w), int(f)) for b, w, f in rows if int(b) in place},
+                  axis.width))
+    return out
+
+  def step(self, launch, pool):
+    """The pool step of `launch`, its session still open: pool(groups, init) is the session's
+    `pool_event_trajectories` with its scale and shift and out_stride = `stride`.  Only the groups
+    with a member in the launch go to the device; the others pass their accumulator through."""
+    k = self._index[int(launch[2][0])]
+    try:
+      acc = self._futures[k - 1].result() if k else None
+      groups = self.groups_of(launch[2])
+      active = [g for g, (group, _) in enumerate(groups) if group]
+      if active:
+        part = pool([groups[g] for g in active], None if acc is None else acc[active])
+        if len(active) == len(groups):
+          acc = part
+        else:
+          acc = np.zeros((len(groups),) + part.shape[1:]) if acc is None else acc.copy()
+          acc[active] = part
+      if self._futures[k].done():            # failed meanwhile by a launch in front that ended in an error
+        self._futures[k].result()
+      self._futures[k].set_result(acc)
+    except BaseException as e:
+      self.fail(launch, e)
+      raise
+
+
+def _event_aggregate_analyses(plan: EventPlan, pooled: np.ndarray, means: Sequence[np.ndarray],
+                              alpha: float, ranks, device: int = 0):
+  """`_aggregate_analyses` in event time: (`aggregates`, `aggregate_summary`) of a panel from the
+  pooled draws [G, N, stride] (float64, data scale; group g owns its first width_g columns) and the
+  series' posterior means over their own steps on the data scale.  Per group the posterior mean is
+  pooled over the members' windows like the outcome (`pool_event_weighted`, the member order of the
+  draws), the pooled draws are summarised by `_native.summarize_draws` with the pooled flags, and the
+  frames are built by `_compute_impact_device` on the group's `event_time` index."""
+  mean = pool_event_weighted(means, plan.csr, plan.axes)
+  analyses = {}
+  for g, (name, axis) in enumerate(zip(plan.names, plan.axes)):
+    ci_data, observed, flags = plan.data[g], plan.observed[g], axis.flags
+    dsum = _native.summarize_draws(pooled[g][:, :axis.width], 1.0, 0.0, observed, flags, ranks,
+                                   device=device)
+    rq = lib._device_summary_request(ci_data, alpha)             # pylint: disable=protected-access
+    rq.update(observed=observed, flags=flags, ranks=ranks)
+    series, summary = lib._compute_impact_device(mean[g], dsum, rq, ci_data, alpha)   # pylint: disable=protected-access
+    analyses[name] = lib.CausalImpactAnalysis(series, summary, None)
+  table = pd.concat([a.summary for a in analyses.values()], keys=list(analyses),
+                    names=["aggregate", None])
+  return analyses, table
+
+
+# ------------------------------------------------------------------------------------------
 # The one launch-and-assemble path of batches and panels
 # ------------------------------------------------------------------------------------------
 def _options(alpha, data_options, model_options, inference_options):
@@ -874,7 +1108,8 @@ def _frames_outcome_first(data, data_options):
 
 
 def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_options, model_options,
-                    inference_options, shared_streams, aggregates=None) -> PerSeriesBatchAnalysis:
+                    inference_options, shared_streams, aggregates=None,
+                    event_aggregates: Optional[EventPlan] = None) -> PerSeriesBatchAnalysis:
   """`fit_causalimpact` on every series in turn: the routes the one-launch path does not have.
   float64 compute (csrc/ci_gibbs64.h) and raw-scale outcomes (their per-series internal
   conditioning, causalimpact_lib._internal_conditioning) exist on the single-series path, and so do
@@ -887,7 +1122,10 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
   aggregates (batches only): (aggregate names, csr, prep) -- the group table of `aggregate_groups`
   and the `PreparedBatch` of the shared calendar.  The running sums of csrc/ci_pool.h are then
   accumulated in numpy, series by series in order, from every fit's data-scale trajectories in
-  float64 (same order, same formula), before its draws are dropped."""
+  float64 (same order, same formula), before its draws are dropped.
+
+  event_aggregates (panels only): the `EventPlan`.  The same in event time (`EventHostPool`): every
+  series is a class of its own on this route, so (class key, position) order is position order."""
   opts = dataclasses.replace(data_options, outcome_column=outcome_column)
   base_seed = lib._sanitize_seed(seed)   # pylint: disable=protected-access
   analyses = []
@@ -895,6 +1133,8 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
   if aggregates is not None:
     agg_names, csr, prep = aggregates
     host_pool = HostPool(csr)
+  elif event_aggregates is not None:
+    host_pool = EventHostPool(event_aggregates.csr, event_aggregates.axes)
   for b, frame in enumerate(frames):
     seed_b = base_seed if shared_streams else _native.series_stream_key(base_seed, b)
     if host_pool is not None:
@@ -907,9 +1147,13 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
   if host_pool is not None:
     ranks = lib._summary_ranks(host_pool.pooled.shape[1], (alpha / 2.0, 1.0 - alpha / 2.0))   # pylint: disable=protected-access
     devs = list(inference_options.devices) if inference_options.devices else [0]
-    res.aggregates, res.aggregate_summary = _aggregate_analyses(
-        agg_names, csr, host_pool.pooled, np.stack(host_pool.means), prep, outcome_column, alpha,
-        ranks, devs[0])
+    if event_aggregates is not None:
+      res.aggregates, res.aggregate_summary = _event_aggregate_analyses(
+          event_aggregates, host_pool.pooled, host_pool.means, alpha, ranks, devs[0])
+    else:
+      res.aggregates, res.aggregate_summary = _aggregate_analyses(
+          agg_names, csr, host_pool.pooled, np.stack(host_pool.means), prep, outcome_column, alpha,
+          ranks, devs[0])
   return res
 
 
@@ -957,7 +1201,8 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
               model_options=model_options, inference_options=inference_options)
 
 
-def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None):
+def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None,
+                event_chain: Optional[_PanelPoolChain] = None):
   """One launch of the Gibbs sampler and its summaries on the device.  launch: (device, key,
   positions) as `panel_launches` lists them; kind: the session the positions run in --
     "ordinary"         `_native.Session`: series b of the launch is keyed by positions[0] + b, hence
@@ -972,7 +1217,9 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
   `summarize`, and `summarize_components` (None unless InferenceOptions.components).  Every array
   keeps the series axis, and T is the longest series of the launch on every route.
   chain (batches with aggregates): the launch's pool step runs after `summarize`, the session still
-  open."""
+  open.  event_chain (panels with event-time aggregates): the same with the windows of
+  `pool_event_trajectories`; first + width stays within every member's own length, hence within
+  the stride of any kind of session."""
   dev, _, ids = launch
   ids = np.asarray(ids, dtype=np.int64)
   mo, io = fit.model_options, fit.inference_options
@@ -1013,6 +1260,9 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
     csum = sess.summarize_components(scale, shift, fit.ranks) if io.components else None
     if chain is not None:
       chain.step(launch, lambda groups, init: sess.pool_trajectories(scale, shift, groups, init))
+    if event_chain is not None:
+      event_chain.step(launch, lambda groups, init: sess.pool_event_trajectories(
+          scale, shift, groups, init, event_chain.stride))
   finally:
     sess.close()
   if stride != T:            # (back at the stride of the longest series)
@@ -1233,7 +1483,8 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
                            model_options: Optional[lib.ModelOptions] = None,
                            inference_options: Optional[lib.InferenceOptions] = None,
                            names: Optional[Sequence[Any]] = None,
-                           shared_streams: bool = False) -> CausalImpactBatchAnalysis:
+                           shared_streams: bool = False,
+                           event_aggregates=None) -> CausalImpactBatchAnalysis:
   """`fit_causalimpact` for a PANEL: B series with the same columns (outcome first, or
   `DataOptions.outcome_column`; the same covariates), each with its own index, its own length and
   its own (pre_period, post_period) -- staggered roll-outs, units that enter the data on different
@@ -1260,9 +1511,36 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   seed (bit for bit in every array the session returns over its own steps); without it series 0
   does, and series b equals the single fit seeded with `_native.series_stream_key(seed, b)`.
 
-  There is no `aggregates` argument here: series with their own calendars share no time axis to add
-  their trajectories on (`fit_causalimpact_batch(aggregates=...)` pools series of ONE calendar).  A
-  pooled effect of a panel in event time is not provided."""
+  event_aggregates: the POOLED effect of groups of series in EVENT TIME -- the roll-out as a whole,
+  every unit aligned on its own treatment start -- with its credible bands.  (There is no
+  `aggregates` argument here: series with their own calendars share no calendar axis to add their
+  trajectories on; `fit_causalimpact_batch(aggregates=...)` pools series of ONE calendar.)  A mapping
+  {aggregate name: members} with the member syntax of `fit_causalimpact_batch(aggregates=...)`: a
+  sequence of series names (weight 1), a mapping {series name: weight}, or the string "all".
+  Event time tau counts the ROWS of a series from its treatment start (tau = 0 is the first step of
+  its post-period), not calendar units: the series of a panel are expected to share a sampling
+  interval.  The axis of a group is what all its members of non-zero weight have (`event_axes`):
+  tau = -L .. H - 1 with L the fewest steps a member has before its start and H the fewest from it
+  on; its pre-period ends before the longest gap any member leaves between pre-period and start, its
+  post-period is the shortest window, 0 .. Hwin - 1.  Draw n of the group at tau is the sum over its
+  members b of w_b * (draw n of series b at its own step start_b + tau, on the data scale), in
+  float64, added on the device that holds the trajectories (csrc/ci_pool_event.h; they are never
+  downloaded) and handed from launch to launch.  The order of addition is (length class of the
+  route, position in the panel) -- the order `panel_launches` lists the launches in, ascending
+  positions within a launch -- which is a function of the model and the series alone: the result is
+  the same on any number of devices, bit for bit, but the order is not plain position order when
+  the members fall in different length classes.  Panels fitted series by series (float64, raw
+  scale, HMC) add the same windows in numpy in position order (every series is its own class
+  there).  The pooled outcome and the pooled posterior mean are the same weighted sums; the pooled
+  outcome is NaN wherever a member's is (gap, tail, missing value).  The result then has
+  `aggregates` ({name: CausalImpactAnalysis}: the reference's `series` frame on an integer index
+  named `event_time`, and `summary`; `plot` takes it as any other; no `posterior_samples`) and
+  `aggregate_summary` (the 15 summary columns indexed by (aggregate, average|cumulative)); both are
+  None without the argument, and nothing else changes with it.  `shared_streams=True` is refused
+  with it (common random numbers make the Monte-Carlo errors of all series move together).
+  ValueError, before any fit, for an unknown series name, a member listed twice, a weight that is not
+  finite, a group without a member of non-zero weight, and a group whose common axis keeps fewer
+  than 3 pre-period steps."""
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
   frames, columns = _frames_outcome_first(data, data_options)
@@ -1272,6 +1550,8 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
     raise ValueError(f"`periods` must hold one (pre_period, post_period) per series: {B} series, "
                      f"{len(periods)} periods")
   names = list(range(B)) if names is None else list(names)
+  agg = (None if event_aggregates is None else
+         _check_event_aggregates(event_aggregates, names, shared_streams))
   for b, f in enumerate(frames):
     if list(f.columns) != list(frames[0].columns):
       raise ValueError(f"series {names[b]!r}: all series of a panel must share the columns")
@@ -1281,9 +1561,14 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   if panel_route(float64=float64, standardize_data=data_options.standardize_data,
                  sampler=inference_options.sampler, num_seasonal_blocks=num_blocks,
                  P=len(columns), lengths=[len(f) for f in frames])["route"] == "per_series":
+    plan = None
+    if agg is not None:   # (the event axes come from the prepared panel; the fits prepare their own data)
+      plan = event_plan(*agg, prepare_panel([f[columns] for f in frames], periods,
+                                            data_options.standardize_data, names=names), columns[0])
     return _fit_per_series(frames, periods, names, columns[0], alpha, seed, data_options,
-                           model_options, inference_options, shared_streams)
+                           model_options, inference_options, shared_streams, event_aggregates=plan)
   prep = prepare_panel([f[columns] for f in frames], periods, names=names)
+  plan = None if agg is None else event_plan(*agg, prep, columns[0])
   route = panel_route(float64=False, standardize_data=True, sampler="gibbs",
                       num_seasonal_blocks=num_blocks,
                       P=0 if prep.design is None else prep.design.shape[2], lengths=prep.lengths,
@@ -1294,8 +1579,19 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   fit = _new_fit(prep, y, prep.lengths, pre_sd, alpha, seed, model_options, inference_options,
                  shared_streams)
   kind = "ordinary" if route["route"] == "equal_length" else route["route"]
-  means, dsum, diag_draws, csum = _assemble(
-      panel_launches(route, inference_options.devices, shared_streams),
-      lambda launch: _run_launch(launch, kind, fit), B, prep.y.shape[1])
-  return CausalImpactPanelAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
-                                   csum)
+  launches = panel_launches(route, inference_options.devices, shared_streams)
+  chain = None if plan is None else _PanelPoolChain(launches, plan.csr, plan.axes)
+  run = lambda launch: _run_launch(launch, kind, fit, event_chain=chain)   # pylint: disable=unnecessary-lambda-assignment
+  means, dsum, diag_draws, csum = _assemble(launches, run if chain is None else chain.guarded(run),
+                                            B, prep.y.shape[1])
+  res = CausalImpactPanelAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
+                                  csum)
+  if chain is not None:
+    # the posterior means on the data scale with the statistics every series' own frame uses
+    data_means = []
+    for b, (Tb, nb) in enumerate(zip(prep.lengths, prep.num_pre)):
+      mu, sd = scaler_stats(prep.raw[b][prep.model_rows[b][:nb], 0][None])
+      data_means.append(means[b, :Tb].astype(np.float64) * sd[0] + mu[0])
+    res.aggregates, res.aggregate_summary = _event_aggregate_analyses(
+        plan, chain.result(), data_means, alpha, fit.ranks, launches[0][0])
+  return res

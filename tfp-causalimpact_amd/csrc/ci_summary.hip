@@ -2,11 +2,13 @@
 // ci_components.h): ci_session_summarize, ci_session_summarize_components,
 // ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] on
 // draws the caller hands in; ci_session_pool_trajectories and ci_ll_session_pool_trajectories
-// (kernel: ci_pool.h) on the trajectories a session holds.
+// (kernel: ci_pool.h) and ci_session_pool_event_trajectories (kernel: ci_pool_event.h) on the
+// trajectories a session holds.
 #include <cmath>
 #include <vector>
 
 #include "ci_pool.h"
+#include "ci_pool_event.h"
 #include "ci_session.h"
 #include "ci_summary.h"
 
@@ -133,15 +135,9 @@ static int summarize_draws_impl(int32_t device, int32_t num_draws, int32_t T, co
                                  num_ranks, ranks, value_order, cum_order, per_draw, per_draw_order);
 }
 
-// ci_session_pool_trajectories / ci_ll_session_pool_trajectories: weighted sums over groups of
-// series of the [B, N, T] float32 trajectories resident in HBM.  Everything is checked before the
-// first device call.  The groups pass through the summary's `value` matrix (B * N*T doubles,
-// allocated on first use and kept), as many at a time as fit it: no device memory beyond the
-// scratch but the weight table.
-static int pool_resident(int device, hipStream_t stream, SummScratch& w, int B, int T, int N,
-                         const float* traj, const double* scale, const double* shift, int32_t G,
-                         const int32_t* offsets, const int32_t* members, const double* weights,
-                         const double* init, double* out) {
+// The group table of the pool entry points (CSR over the positions of the session's B series).
+static int check_groups(int B, int32_t G, const int32_t* offsets, const int32_t* members,
+                        const double* weights) {
   if (G < 1) return fail("num_groups must be >= 1, got %d", G);
   if (offsets[0] != 0) return fail("offsets[0] must be 0, got %d", offsets[0]);
   for (int g = 0; g < G; ++g) {
@@ -157,6 +153,19 @@ static int pool_resident(int device, hipStream_t stream, SummScratch& w, int B, 
       if (!std::isfinite(weights[k])) return fail("group %d: the weight of member %d is not finite", g, members[k]);
     }
   }
+  return 0;
+}
+
+// ci_session_pool_trajectories / ci_ll_session_pool_trajectories: weighted sums over groups of
+// series of the [B, N, T] float32 trajectories resident in HBM.  Everything is checked before the
+// first device call.  The groups pass through the summary's `value` matrix (B * N*T doubles,
+// allocated on first use and kept), as many at a time as fit it: no device memory beyond the
+// scratch but the weight table.
+static int pool_resident(int device, hipStream_t stream, SummScratch& w, int B, int T, int N,
+                         const float* traj, const double* scale, const double* shift, int32_t G,
+                         const int32_t* offsets, const int32_t* members, const double* weights,
+                         const double* init, double* out) {
+  if (check_groups(B, G, offsets, members, weights)) return 1;
   const long long NT = (long long)N * T;
   std::vector<ci::PoolEntry> entries((size_t)offsets[G]);
   for (int k = 0; k < offsets[G]; ++k) {
@@ -194,7 +203,101 @@ static int pool_resident(int device, hipStream_t stream, SummScratch& w, int B, 
   return 0;
 }
 
+// ci_session_pool_event_trajectories: pool_resident over windows of the members' rows, member k
+// from its step first[k] on, width[g] columns per group, in accumulators of out_stride columns.
+// The accumulators pass through `value` with rows of min(out_stride, T) columns -- no width exceeds
+// T, so min(num_groups, B) groups fit it at a time as in pool_resident -- and the columns of a wider
+// host row are zeroed on the host.
+static int pool_event_resident(int device, hipStream_t stream, SummScratch& w, int B, int T, int N,
+                               const float* traj, const double* scale, const double* shift, int32_t G,
+                               const int32_t* offsets, const int32_t* members, const double* weights,
+                               const int32_t* first, const int32_t* width, int32_t S,
+                               const double* init, double* out) {
+  if (check_groups(B, G, offsets, members, weights)) return 1;
+  if (S < 1) return fail("out_stride must be >= 1, got %d", S);
+  for (int g = 0; g < G; ++g) {
+    if (width[g] < 1 || width[g] > S)
+      return fail("group %d: width %d outside [1, out_stride = %d]", g, width[g], S);
+    if (width[g] > T)        // (a group without a member too: no row on the device is longer)
+      return fail("group %d: width %d exceeds the session's %d steps", g, width[g], T);
+    for (int k = offsets[g]; k < offsets[g + 1]; ++k) {
+      if (first[k] < 0) return fail("group %d: the first step of member %d is negative (%d)", g, members[k], first[k]);
+      if ((long long)first[k] + width[g] > T)
+        return fail("group %d: member %d from step %d over %d columns ends beyond the session's %d steps",
+                    g, members[k], first[k], width[g], T);
+    }
+  }
+  const long long NT = (long long)N * T;
+  const int Sd = S < T ? S : T;                                     // row length on the device
+  bool aligned = T % 4 == 0 && (reinterpret_cast<uintptr_t>(traj) & 15u) == 0u;
+  std::vector<ci::PoolEntry> entries((size_t)offsets[G]);
+  for (int k = 0; k < offsets[G]; ++k) {
+    const int b = members[k];
+    entries[k] = ci::PoolEntry{(long long)b * NT + first[k], weights[k], scale[b], shift[b]};
+    aligned = aligned && first[k] % 4 == 0;
+  }
+  HIP_TRY(hipSetDevice(device));
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  const int per_pass = G < B ? G : (B < 65535 ? B : 65535);       // groups that fit `value` (grid.y)
+  DevBuf<ci::PoolEntry> d_entries;
+  DevBuf<int> d_tables;                                             // offsets [G + 1], widths [G]
+  HIP_TRY(d_entries.alloc(entries.size() ? entries.size() : 1));
+  HIP_TRY(d_tables.alloc((size_t)2 * G + 1));
+  if (!entries.empty())
+    HIP_TRY(hipMemcpyAsync(d_entries.p, entries.data(), entries.size() * sizeof(ci::PoolEntry),
+                           hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_tables.p, offsets, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_tables.p + G + 1, width, (size_t)G * sizeof(int), hipMemcpyHostToDevice, stream));
+  const long long quads = (long long)N * ((Sd + 3) / 4);
+  const unsigned blocks = (unsigned)((quads + ci::POOL_NT - 1) / ci::POOL_NT);
+  const size_t host_pitch = (size_t)S * sizeof(double), dev_pitch = (size_t)Sd * sizeof(double);
+  for (int g0 = 0; g0 < G; g0 += per_pass) {
+    const int ng = G - g0 < per_pass ? G - g0 : per_pass;
+    const size_t rows = (size_t)ng * N;
+    if (init) {
+      const double* src = init + (size_t)g0 * N * S;
+      if (Sd == S)
+        HIP_TRY(hipMemcpyAsync(w.value.p, src, rows * dev_pitch, hipMemcpyHostToDevice, stream));
+      else
+        HIP_TRY(hipMemcpy2DAsync(w.value.p, dev_pitch, src, host_pitch, dev_pitch, rows,
+                                 hipMemcpyHostToDevice, stream));
+    }
+    const int* d_off = d_tables.p + g0;
+    const int* d_width = d_tables.p + G + 1 + g0;
+    if (aligned)
+      hipLaunchKernelGGL(ci::pool_event_kernel<true>, dim3(blocks, ng), dim3(ci::POOL_NT), 0, stream, N, T,
+                         (long long)B * NT, traj, d_off, d_entries.p, d_width, Sd, init ? 1 : 0, w.value.p);
+    else
+      hipLaunchKernelGGL(ci::pool_event_kernel<false>, dim3(blocks, ng), dim3(ci::POOL_NT), 0, stream, N, T,
+                         (long long)B * NT, traj, d_off, d_entries.p, d_width, Sd, init ? 1 : 0, w.value.p);
+    HIP_TRY(hipGetLastError());
+    double* dst = out + (size_t)g0 * N * S;
+    if (Sd == S)
+      HIP_TRY(hipMemcpyAsync(dst, w.value.p, rows * dev_pitch, hipMemcpyDeviceToHost, stream));
+    else
+      HIP_TRY(hipMemcpy2DAsync(dst, host_pitch, w.value.p, dev_pitch, dev_pitch, rows,
+                               hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (size_t row = 0; Sd < S && row < rows; ++row)                // no width reaches these columns
+      for (int c = Sd; c < S; ++c) dst[row * S + c] = 0.0;
+  }
+  return 0;
+}
+
 extern "C" {
+
+int ci_session_pool_event_trajectories(ci_session* s, const double* scale, const double* shift,
+                                       int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                       const double* weights, const int32_t* first, const int32_t* width,
+                                       int32_t out_stride, const double* init, double* out) {
+  if (!s || !scale || !shift || !offsets || !members || !weights || !first || !width || !out)
+    return fail("NULL argument");
+  if (!s->ran) return fail("ci_session_pool_event_trajectories needs a finished ci_session_run");
+  const ci_problem& pb = s->pb;
+  return pool_event_resident(pb.device, s->stream, s->summ, pb.num_series, pb.T,
+                             pb.num_chains * pb.num_results, s->o_traj.p, scale, shift, num_groups, offsets,
+                             members, weights, first, width, out_stride, init, out);
+}
 
 int ci_session_pool_trajectories(ci_session* s, const double* scale, const double* shift,
                                  int32_t num_groups, const int32_t* offsets, const int32_t* members,
