@@ -82,8 +82,8 @@ def test_fit_refuses_bad_aggregates_before_any_device_work():
 def test_groups_are_cut_to_the_positions_of_a_launch():
   _, csr = batch.aggregate_groups({"total": "all", "mix": {"north": 0.5, "west": -2.0}, "one": ["east"]},
                                   NAMES)
-  assert batch._groups_within(csr, np.array([0, 1, 2])) == [{0: 1.0, 1: 1.0, 2: 1.0}, {0: 0.5}, {2: 1.0}]
-  assert batch._groups_within(csr, np.array([3, 4])) == [{0: 1.0, 1: 1.0}, {0: -2.0}, {}]
+  assert batch._PoolChain([], csr).groups_of(np.array([0, 1, 2])) == [{0: 1.0, 1: 1.0, 2: 1.0}, {0: 0.5}, {2: 1.0}]
+  assert batch._PoolChain([], csr).groups_of(np.array([3, 4])) == [{0: 1.0, 1: 1.0}, {0: -2.0}, {}]
 
 
 # ---- pooled observed and posterior mean ----------------------------------------------------------
@@ -260,6 +260,42 @@ def test_pool_chain_hands_the_accumulator_from_launch_to_launch():
   lib.map_by_device(chain.guarded(lambda launch: chain.step(
       launch, _fake_launch_pool(traj, scale, shift, np.asarray(launch[2])))), launches)
   np.testing.assert_array_equal(chain.result(), want)
+
+
+def test_chain_with_full_width_axes_from_step_zero_is_the_chain_without_axes():
+  """A calendar aggregate is the event-time aggregate whose members all start at step 0 with the width
+  T: one chain built without axes and one built with such axes, driven by the same fake session, end
+  in the same accumulator."""
+  rng = np.random.default_rng(6)
+  B, N, T = 5, 3, 4
+  traj = (rng.normal(size=(B, N, T)) * 10.0 ** rng.integers(-3, 4, size=(B, 1, 1))).astype(np.float32)
+  scale, shift = rng.uniform(1, 2, B), rng.normal(size=B)
+  _, csr = batch.aggregate_groups({"total": "all", "mix": {"north": 0.5, "west": -2.0}, "one": ["east"]},
+                                  NAMES)
+  offsets = csr[0]
+  axes = [batch.EventAxis(L=1, gap=0, Hwin=1, H=T - 1, first=np.zeros(offsets[g + 1] - offsets[g], np.int32))
+          for g in range(3)]
+  seen = []
+
+  def fake_pool(ids):
+    def pool(groups, init):
+      seen.append(type(groups[0]))
+      if isinstance(groups[0], tuple):
+        return _native.pool_event_host(traj[ids], scale[ids], shift[ids], groups, init)
+      return _native.pool_host(traj[ids], scale[ids], shift[ids], groups, init)
+    return pool
+
+  # (positions that interleave: what a batch never has and a panel does)
+  for cut in ([[0, 1, 2, 3, 4]], [[0, 1, 2], [3, 4]], [[0, 2, 4], [1, 3]]):
+    launches = [(0, T, ids) for ids in cut]
+    plain, event = batch._PoolChain(launches, csr), batch._PoolChain(launches, csr, axes)
+    assert plain.stride is None and event.stride == T
+    for launch in launches:
+      plain.step(launch, fake_pool(np.asarray(launch[2])))
+      event.step(launch, fake_pool(np.asarray(launch[2])))
+    assert plain.result().shape == (3, N, T)
+    np.testing.assert_array_equal(event.result(), plain.result())
+  assert set(seen) == {dict, tuple}
 
 
 def test_pool_chain_passes_a_failure_on_instead_of_blocking():

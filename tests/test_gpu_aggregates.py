@@ -145,12 +145,12 @@ def test_running_sum_chained_over_two_sessions_equals_one_session(fitted, whole)
   try:
     sess.run()
     first = sess.pool_trajectories(f.scale[first_ids], f.shift[first_ids],
-                                   batch._groups_within(csr, first_ids))
+                                   batch._PoolChain([], csr).groups_of(first_ids))
   finally:
     sess.close()
   sess = fitted.session(second_ids)
   try:
-    groups = batch._groups_within(csr, second_ids)
+    groups = batch._PoolChain([], csr).groups_of(second_ids)
     assert groups[2] == {}
     with pytest.raises(_native.NativeError, match="needs a finished ci_session_run"):
       sess.pool_trajectories(f.scale[second_ids], f.shift[second_ids], groups, first)
@@ -185,6 +185,56 @@ def test_running_sum_chained_over_two_sessions_equals_one_session(fitted, whole)
   finally:
     sess.close()
   np.testing.assert_array_equal(second, plain)
+
+
+# ---- groups of more members than one chunk of loads ---------------------------------------------------
+# 15 series, 17 steps, 3 chains x 3 draws: N*T = 153 is odd again.  The kernel adds the members of a
+# group in chunks of 8, 4, 2 and 1: 15 = 8 + 4 + 2 + 1, 8, 9 = 8 + 1, 7 = 4 + 2 + 1, and 1.
+MANY_B, MANY_T, MANY_DRAWS = 15, 17, 3
+MANY_N = CHAINS * MANY_DRAWS
+MANY_GROUPS = [{b: (-1.0) ** b * (0.25 + 0.5 * b) for b in range(15)},
+               {b: 1.0 for b in range(0, 15, 2)},
+               {b: 3.0 - b for b in (1, 2, 4, 5, 6, 7, 8, 9, 10)},
+               {b: 0.125 * b for b in range(1, 15, 2)},
+               {14: -2.5}]
+
+
+@pytest.fixture(scope="module")
+def many():
+  """(trajectories [15, 9, 17] float32, scale, shift, pooled without init, pooled with init, init) of
+  one ordinary session of 15 series."""
+  rng = np.random.default_rng(3)
+  x = rng.normal(size=(MANY_B, MANY_T, 1))
+  y = 1.5 * x[:, :, 0] + 10.0 + 3.0 * np.arange(MANY_B)[:, None] + 0.3 * rng.normal(size=(MANY_B, MANY_T))
+  prep = batch.prepare_batch(np.concatenate([y[:, :, None], x], axis=2), pd.RangeIndex(MANY_T), (0, 10), (11, 16))
+  ys = batch._sampler_outcome(prep, ci.DataOptions())
+  options = ci.InferenceOptions(num_results=MANY_DRAWS, num_chains=CHAINS, num_warmup_steps=5)
+  f = batch._new_fit(prep, ys, np.full(MANY_B, MANY_T), np.nanstd(ys[:, :prep.num_pre], axis=1, ddof=1),
+                     ALPHA, SEED, ci.ModelOptions(), options, False)
+  pb = _native.make_problem(T=MANY_T, P=f.design.shape[2], has_slope=False, num_warmup=5,
+                            num_results=MANY_DRAWS, num_chains=CHAINS, num_series=MANY_B, seed=f.seed, device=0)
+  sess = _native.Session(pb, f.y, f.mask, f.design, None, _native.make_params(f.params))
+  try:
+    sess.run()
+    traj = sess.fetch(["posterior_trajectories"])["posterior_trajectories"].reshape(MANY_B, MANY_N, MANY_T)
+    init = np.random.default_rng(9).normal(size=(len(MANY_GROUPS), MANY_N, MANY_T)) * 50.0
+    plain = sess.pool_trajectories(f.scale, f.shift, MANY_GROUPS)
+    continued = sess.pool_trajectories(f.scale, f.shift, MANY_GROUPS, init)
+  finally:
+    sess.close()
+  return traj, f.scale, f.shift, plain, continued, init
+
+
+@pytest.mark.parametrize("with_init", [False, True])
+def test_groups_of_up_to_15_members_equal_the_numpy_loop(many, with_init):
+  traj, scale, shift, plain, continued, init = many
+  assert [len(g) for g in MANY_GROUPS] == [15, 8, 9, 7, 1]
+  assert any(w < 0 for w in MANY_GROUPS[0].values()) and (MANY_N * MANY_T) % 2 == 1
+  assert np.isfinite(traj).all() and traj.std() > 0
+  if with_init:
+    np.testing.assert_array_equal(continued, _pool_loop(traj, scale, shift, MANY_GROUPS, init))
+  else:
+    np.testing.assert_array_equal(plain, _pool_loop(traj, scale, shift, MANY_GROUPS))
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """Event-time aggregates of a panel on the device: ci_session_pool_event_trajectories
-(csrc/ci_pool_event.h) against the numpy loop of its definition on ragged trend sessions (stride 47,
+(csrc/ci_pool.h) against the numpy loop of its definition on ragged trend sessions (stride 47,
 N*T odd: the offset of a row from the 16-byte grid changes with the draw) and ragged seasonal
 sessions (stride a multiple of 4), the running sum chained over sessions, the argument checks that
 need a session, and `fit_causalimpact_panel(event_aggregates=...)` on every route against the host
@@ -234,6 +234,64 @@ def test_event_pool_equals_the_numpy_loop_on_aligned_rows(weekly):
   assert all(first % 4 == 0 for g, _ in ALIGNED_GROUPS for _, first in g.values())
   np.testing.assert_array_equal(got["aligned"], _loop(traj, f.scale, f.shift, ALIGNED_GROUPS, 12))
   np.testing.assert_array_equal(got["full"], got["whole"])
+
+
+# ---- groups of more members than one chunk of loads ---------------------------------------------------
+# 15 series of 17 steps in one ragged trend session (stride 17, N*T odd).  The kernel adds the members
+# of a group in chunks of 8, 4, 2 and 1: 15 = 8 + 4 + 2 + 1 and 9 = 8 + 1.  The first steps cover all
+# residues mod 4; the group of 15 starts at the first float of the buffer (series 0 from step 0) and
+# ends at the last one (series 14 up to step 17): the quads that go element by element.  Widths 9 and
+# 6 in rows of 14 columns.
+MANY_GROUPS = [({b: ((-1.0) ** b * (0.25 + 0.5 * b), f)
+                 for b, f in enumerate([0, 1, 2, 3, 4, 5, 6, 7, 8, 0, 1, 2, 3, 5, 8])}, 9),
+               ({b: (3.0 - b, f) for b, f in zip((0, 2, 3, 5, 6, 8, 9, 11, 12), (3, 0, 1, 2, 7, 6, 5, 4, 11))}, 6)]
+# ... and 15 series of 20 steps, every first step and the width a multiple of 4: the aligned build
+MANY_ALIGNED_GROUPS = [({b: (0.5 * b - 3.0, 4 * (b % 4)) for b in range(15)}, 8)]
+
+
+@pytest.fixture(scope="module")
+def many():
+  """Per session (trajectories, scale, shift, {name: pooled}): 15 series of 17 steps, 15 of 20."""
+  out = []
+  for T, groups, stride in ((17, MANY_GROUPS, 14), (20, MANY_ALIGNED_GROUPS, None)):
+    panel = _panel_of([T] * 15)
+    f = panel.fit
+    sess, session_stride = panel.session(range(15), "ragged")
+    assert session_stride == T
+    try:
+      sess.run()
+      traj = _trajectories(sess)
+      init = np.random.default_rng(9).normal(size=(len(groups), N, stride or groups[0][1])) * 50.0
+      for g, (_, width) in enumerate(groups):               # beyond the width init is never looked at
+        init[g, :, width:] = np.nan
+      got = dict(plain=sess.pool_event_trajectories(f.scale, f.shift, groups, out_stride=stride),
+                 continued=sess.pool_event_trajectories(f.scale, f.shift, groups, init, out_stride=stride),
+                 init=init)
+    finally:
+      sess.close()
+    out.append((traj, f.scale, f.shift, got))
+  return out
+
+
+@pytest.mark.parametrize("with_init", [False, True])
+def test_event_groups_of_15_and_9_members_equal_the_numpy_loop(many, with_init):
+  traj, scale, shift, got = many[0]
+  assert [len(g) for g, _ in MANY_GROUPS] == [15, 9] and traj.shape == (15, N, 17)
+  for group, width in MANY_GROUPS:
+    assert {first % 4 for _, first in group.values()} == {0, 1, 2, 3} and width % 4 != 0
+  assert MANY_GROUPS[0][0][0][1] == 0 and MANY_GROUPS[0][0][14][1] + MANY_GROUPS[0][1] == 17
+  want = _loop(traj, scale, shift, MANY_GROUPS, 14, got["init"] if with_init else None)
+  np.testing.assert_array_equal(got["continued" if with_init else "plain"], want)
+
+
+@pytest.mark.parametrize("with_init", [False, True])
+def test_event_group_of_15_members_equals_the_numpy_loop_on_aligned_rows(many, with_init):
+  traj, scale, shift, got = many[1]
+  group, width = MANY_ALIGNED_GROUPS[0]
+  assert len(group) == 15 and traj.shape[2] % 4 == 0 and width % 4 == 0
+  assert all(first % 4 == 0 for _, first in group.values())
+  want = _loop(traj, scale, shift, MANY_ALIGNED_GROUPS, 8, got["init"] if with_init else None)
+  np.testing.assert_array_equal(got["continued" if with_init else "plain"], want)
 
 
 def _cut_groups(groups, ids):

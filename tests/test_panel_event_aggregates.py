@@ -119,7 +119,7 @@ def test_event_host_pool_equals_an_explicit_loop_bit_for_bit(dtype):
   csr = _native.groups_csr([{b: w for b, (w, _) in g.items()} for g, _ in groups], 4)
   axes = [batch.EventAxis(L=1, gap=0, Hwin=1, H=width - 1,
                           first=np.array([g[b][1] for b in sorted(g)], np.int32)) for g, width in groups]
-  pool = batch.EventHostPool(csr, axes)
+  pool = batch.HostPool(csr, axes)
   assert pool.stride == 9
   for b in range(4):
     pool.add(b, pm[b], traj[b], scale[b], shift[b])
@@ -207,7 +207,7 @@ def test_panel_chain_adds_in_class_then_position_order():
   cuts = [([(0, 1, [0, 2, 4]), (0, 2, [1, 3])], ((0, 2, 4), [[0, 1, 2], [0], [1]])),
           ([(0, 1, [0, 2]), (1, 1, [4]), (0, 2, [1]), (1, 2, [3])], ((0, 2), [[0, 1], [0], [1]]))]
   for launches, first_step in cuts:
-    chain = batch._PanelPoolChain(launches, panel.csr, panel.axes)
+    chain = batch._PoolChain(launches, panel.csr, panel.axes)
     assert chain.stride == 20
     seen = []
     for launch in launches:
@@ -216,7 +216,7 @@ def test_panel_chain_adds_in_class_then_position_order():
     # only the groups with a member in a launch went to its pool step, by place within the launch
     assert seen[0] == first_step
     # side by side on two devices, every device its launches in list order
-    chain = batch._PanelPoolChain(launches, panel.csr, panel.axes)
+    chain = batch._PoolChain(launches, panel.csr, panel.axes)
     lib.map_by_device(chain.guarded(lambda launch: chain.step(launch, panel.pool_of(launch))), launches)
     np.testing.assert_array_equal(chain.result(), want)
 
@@ -224,7 +224,7 @@ def test_panel_chain_adds_in_class_then_position_order():
 def test_panel_chain_passes_a_group_without_a_member_through():
   panel = _FakePanel()
   launches = [(0, 1, [0, 2, 4]), (0, 2, [1, 3])]
-  chain = batch._PanelPoolChain(launches, panel.csr, panel.axes)
+  chain = batch._PoolChain(launches, panel.csr, panel.axes)
   assert chain.groups_of([1, 3]) == [({0: (1.0, 9), 1: (1.0, 4)}, 10), ({1: (-2.0, 8)}, 12), ({}, 6),
                                      ({0: (1.0, 0), 1: (0.25, 0)}, 20)]
   chain.step(launches[0], panel.pool_of(launches[0]))
@@ -238,7 +238,7 @@ def test_panel_chain_passes_a_group_without_a_member_through():
 def test_panel_chain_failure_fails_every_later_launch():
   panel = _FakePanel()
   launches = [(0, 1, [0, 2]), (1, 1, [4]), (0, 2, [1]), (1, 2, [3])]
-  chain = batch._PanelPoolChain(launches, panel.csr, panel.axes)
+  chain = batch._PoolChain(launches, panel.csr, panel.axes)
 
   def run(launch):
     if launch[2] == [0, 2]:
@@ -253,7 +253,7 @@ def test_panel_chain_failure_fails_every_later_launch():
   with pytest.raises(RuntimeError, match="first launch failed"):
     chain.result()
   # a pool step that fails does the same
-  chain = batch._PanelPoolChain(launches, panel.csr, panel.axes)
+  chain = batch._PoolChain(launches, panel.csr, panel.axes)
   chain.step(launches[0], panel.pool_of(launches[0]))
 
   def broken(groups, init):

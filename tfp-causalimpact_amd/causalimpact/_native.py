@@ -347,20 +347,22 @@ def pool_host(trajectories, scale, shift, groups, init=None) -> np.ndarray:
   return out
 
 
-def _pool_call(fn, handle, B: int, N: int, T: int, scale, shift, groups, init) -> np.ndarray:
-  """The call both sessions' `pool_trajectories` make."""
+def _pool_call(fn, handle, B: int, N: int, T: int, scale, shift, groups, init, event=False,
+               out_stride=None) -> np.ndarray:
+  """The call every session's `pool_trajectories` and `pool_event_trajectories` (event=True: the
+  tables of `event_groups_csr` and rows of out_stride columns) make."""
   sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (B,)))
   sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.float64), (B,)))
-  offsets, members, weights = groups_csr(groups, B)
-  G = offsets.size - 1
+  csr = (event_groups_csr if event else groups_csr)(groups, B)
+  G, stride = csr[0].size - 1, _event_stride(csr[4], out_stride) if event else T
+  tables = [a.ctypes.data for a in csr] + ([stride] if event else [])
   if init is not None:
     init = np.ascontiguousarray(init, dtype=np.float64)
-    if init.shape != (G, N, T):
-      raise ValueError(f"`init` must be {[G, N, T]}, got {list(init.shape)}")
-  big = G * N * T * 8 > (1 << 20)
-  out = pinned_empty((G, N, T), np.float64) if big else np.empty((G, N, T), np.float64)
-  _check(fn(handle, sc.ctypes.data, sh.ctypes.data, G, offsets.ctypes.data, members.ctypes.data,
-            weights.ctypes.data, _ptr(init), out.ctypes.data))
+    if init.shape != (G, N, stride):
+      raise ValueError(f"`init` must be {[G, N, stride]}, got {list(init.shape)}")
+  big = G * N * stride * 8 > (1 << 20)
+  out = pinned_empty((G, N, stride), np.float64) if big else np.empty((G, N, stride), np.float64)
+  _check(fn(handle, sc.ctypes.data, sh.ctypes.data, G, *tables, _ptr(init), out.ctypes.data))
   return out
 
 
@@ -675,21 +677,8 @@ class Session:
     if fn is None:
       raise NativeError("the loaded library has no ci_session_pool_event_trajectories: rebuild it")
     pb = self.pb
-    B, N = pb.num_series, pb.num_chains * pb.num_results
-    sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (B,)))
-    sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.float64), (B,)))
-    offsets, members, weights, first, width = event_groups_csr(groups, B)
-    G, stride = width.size, _event_stride(width, out_stride)
-    if init is not None:
-      init = np.ascontiguousarray(init, dtype=np.float64)
-      if init.shape != (G, N, stride):
-        raise ValueError(f"`init` must be {[G, N, stride]}, got {list(init.shape)}")
-    big = G * N * stride * 8 > (1 << 20)
-    out = pinned_empty((G, N, stride), np.float64) if big else np.empty((G, N, stride), np.float64)
-    _check(fn(self._h, sc.ctypes.data, sh.ctypes.data, G, offsets.ctypes.data, members.ctypes.data,
-              weights.ctypes.data, first.ctypes.data, width.ctypes.data, stride, _ptr(init),
-              out.ctypes.data))
-    return out
+    return _pool_call(fn, self._h, pb.num_series, pb.num_chains * pb.num_results, pb.T, scale, shift,
+                      groups, init, True, out_stride)
 
   def close(self):
     if self._h:

@@ -22,7 +22,7 @@ launch to launch in series order, then summarised like any single series.
 
 `fit_causalimpact_panel` is the same for series with their own index, length and periods;
 `fit_causalimpact_panel(..., event_aggregates={name: members})` pools groups of them in EVENT TIME,
-every series aligned on its own treatment start (csrc/ci_pool_event.h, `_PanelPoolChain`).
+every series aligned on its own treatment start (the same header and chain, over windows).
 
 Both fit functions are one pipeline over different preparations (`prepare_batch`, one shared
 calendar; `prepare_panel`, padded to the longest series):
@@ -32,11 +32,14 @@ calendar; `prepare_panel`, padded to the longest series):
     the panel of ONE group of equal lengths, cut into consecutive positions per device;
   * `_run_launch` (Gibbs: ordinary, ragged or ragged seasonal session) or `_run_hmc_launch`: one
     session from creation to close, arrays back with the series axis at the launch's stride;
-  * `aggregate_groups`, `_PoolChain`, `_aggregate_analyses`: the aggregates of a batch -- the group
-    table, the running sums handed from launch to launch, the frames of every group;
-  * `event_axes` / `event_plan`, `_PanelPoolChain`, `_event_aggregate_analyses`: their twins for
-    the event-time aggregates of a panel -- every group's axis around its members' own treatment
-    starts, the running sums over launches whose positions interleave, the frames on `event_time`;
+  * `aggregate_groups`, `_PoolChain` (`HostPool` on the per-series routes), `_frame_analyses`: the
+    aggregates of both -- the group table, the running sums handed from launch to launch, the frames
+    of every group.  A calendar aggregate is an event-time aggregate whose members all start at step
+    0 with the width T, so one chain and one host pool serve both, given the axes or not;
+  * `pool_weighted` + `_aggregate_analyses` (a batch) and `event_axes` / `event_plan`,
+    `pool_event_weighted` + `_event_aggregate_analyses` (a panel): what differs -- every group's axis
+    around its members' own treatment starts, the pooled outcome and posterior mean, the rows of
+    `_frame_analyses`;
   * `_assemble`: the launches of a device in turn, the devices side by side
     (`causalimpact_lib.map_by_device`), then the [B, ..., T_max] blocks of the containers.
 """
@@ -685,28 +688,16 @@ def aggregate_groups(aggregates, names: Sequence[Any]):
   return list(aggregates.keys()), _native.groups_csr(groups, len(names))
 
 
-def _check_aggregates(aggregates, names, shared_streams: bool):
-  """`aggregate_groups` after the refusal of common random numbers."""
+def _check_aggregates(aggregates, names, shared_streams: bool, argument: str = "aggregates"):
+  """`aggregate_groups` for the argument `aggregates` or `event_aggregates`, after the refusal of
+  common random numbers."""
   if shared_streams:
     raise ValueError(
-        "`aggregates` cannot be combined with shared_streams=True: with common random numbers the "
+        f"`{argument}` cannot be combined with shared_streams=True: with common random numbers the "
         "Monte-Carlo errors of all series are perfectly correlated, and pairing draw n of every "
         "series is then not a draw from the joint posterior of independent series -- the pooled "
         "bands would be wrong.  Fit with the default per-series streams.")
   return aggregate_groups(aggregates, names)
-
-
-def _groups_within(csr, ids: np.ndarray) -> List[Dict[int, float]]:
-  """The groups of `csr` cut to the consecutive ascending positions `ids` of one launch: per group
-  {position within the launch: weight} (empty for a group without a member there)."""
-  offsets, members, weights = csr
-  lo, hi = int(ids[0]), int(ids[-1])
-  out = []
-  for g in range(len(offsets) - 1):
-    m, w = members[offsets[g]:offsets[g + 1]], weights[offsets[g]:offsets[g + 1]]
-    keep = (m >= lo) & (m <= hi)
-    out.append({int(b) - lo: float(x) for b, x in zip(m[keep], w[keep])})
-  return out
 
 
 def pool_weighted(rows: np.ndarray, csr, init: Optional[np.ndarray] = None) -> np.ndarray:
@@ -725,14 +716,19 @@ def pool_weighted(rows: np.ndarray, csr, init: Optional[np.ndarray] = None) -> n
 
 
 class HostPool:
-  """The running sums of csrc/ci_pool.h in numpy, for batches that are fitted series by series: the
-  series are added in order, `add(b, ...)` for b = 0, 1, ..., each from its fit's trajectories
-  [N, T] (any float type) with value = trajectory * scale + shift in float64, two roundings, and
-  pooled[g] = pooled[g] + w[g, b] * value for every group that has b, two roundings.  `pooled`
-  [G, N, T] float64; `means`: every series' posterior mean [T] on the data scale."""
+  """The running sums of csrc/ci_pool.h in numpy, for batches and panels that are fitted series by
+  series: the series are added in order, `add(b, ...)` for b = 0, 1, ..., each from its fit's
+  trajectories [N, T] (any float type) with value = trajectory * scale + shift in float64, two
+  roundings, and pooled[g] = pooled[g] + w[g, b] * value for every group that has b, two roundings.
+  Without `axes` (calendar time) `pooled` is [G, N, T] float64.  With the `EventAxis` of every group
+  (event time) the window value[:, first_b : first_b + width_g] is added to pooled[g][:, :width_g];
+  `pooled` is [G, N, stride] float64, stride the widest group, 0.0 beyond a group's width.  `means`:
+  every series' posterior mean over its own steps on the data scale."""
 
-  def __init__(self, csr):
+  def __init__(self, csr, axes: Optional[Sequence[EventAxis]] = None):
     self.csr = csr
+    self.axes = None if axes is None else list(axes)
+    self.stride = None if axes is None else max(axis.width for axis in self.axes)
     self.pooled: Optional[np.ndarray] = None
     self.means: List[np.ndarray] = []
 
@@ -742,46 +738,85 @@ class HostPool:
     value = np.asarray(trajectories).astype(np.float64) * scale + shift
     self.means.append(np.asarray(posterior_means).astype(np.float64) * scale + shift)
     if self.pooled is None:
-      self.pooled = np.zeros((len(offsets) - 1,) + value.shape)
+      self.pooled = np.zeros((len(offsets) - 1,) + value.shape[:-1] + (self.stride or value.shape[-1],))
     for g in range(len(offsets) - 1):
       k = offsets[g] + int(np.searchsorted(members[offsets[g]:offsets[g + 1]], b))
       if k < offsets[g + 1] and members[k] == b:
-        self.pooled[g] = self.pooled[g] + weights[k] * value
+        f, W = 0, value.shape[-1]
+        if self.axes is not None:
+          f, W = int(self.axes[g].first[k - offsets[g]]), self.axes[g].width
+        self.pooled[g, ..., :W] = self.pooled[g, ..., :W] + weights[k] * value[..., f:f + W]
 
 
 class _PoolChain:
-  """The running sums [G, N, T] of a batch's aggregates over its launches.  The launches are chained
-  in list order, which is ascending positions: launch k waits for the accumulator of launch k - 1,
-  passes it on as `init` and hands its own result to launch k + 1, so the sum runs over the series
-  in order however the batch is cut into launches and devices.  The fits still run side by side;
-  only these steps serialise.  Futures carry the accumulators: the exception of a launch reaches
-  the launch that waits for it.  A launch that fails also fails every launch behind it in the chain
-  that is not done: a device stops at its first failure, so the launches it had left never run, and
-  whoever waits for one of them on another device must not wait for ever."""
+  """The running sums of a fit's aggregates over its launches: [G, N, T] for a batch (calendar time),
+  [G, N, stride] with the `EventAxis` of every group for a panel (event time; `stride` the widest
+  group).  The launches are chained in list order: launch k waits for the accumulator of launch
+  k - 1, passes it on as `init` and hands its own result to launch k + 1.  The fits still run side by
+  side; only these steps serialise.
 
-  def __init__(self, launches, csr):
+  A batch lists its launches in ascending positions, so the sum runs over the series in order
+  however the batch is cut into launches and devices.  A class of a panel holds whatever positions
+  fall in it, so the launches do not cut the positions into consecutive runs; they are chained in the
+  order `panel_launches` lists them -- class key ascending, ascending positions within a class, which
+  its split over devices keeps -- and a session adds its members in ascending position.  A group is
+  therefore summed in (class key, position) order: a function of the model and the series alone, the
+  same on any number of devices, and not plain position order when its members fall in different
+  classes.
+
+  Every launch waits for an earlier one of the list and every device runs its launches in list order
+  (`causalimpact_lib.map_by_device`), so no wait is circular.  Futures carry the accumulators: the
+  exception of a launch reaches the launch that waits for it.  A launch that fails also fails every
+  launch behind it in the chain that is not done: a device stops at its first failure, so the
+  launches it had left never run, and whoever waits for one of them on another device must not wait
+  for ever."""
+
+  def __init__(self, launches, csr, axes: Optional[Sequence[EventAxis]] = None):
     self.csr = csr
+    self.axes = None if axes is None else list(axes)
+    self.stride = None if axes is None else max(axis.width for axis in self.axes)
     self._index = {int(launch[2][0]): k for k, launch in enumerate(launches)}
     self._futures = [concurrent.futures.Future() for _ in launches]
 
+  def groups_of(self, ids: Sequence[int]):
+    """The groups cut to the positions `ids` of one launch, whatever they are, as the session's pool
+    method takes them: per group {place within the launch: weight}, or with axes ({place: (weight,
+    first)}, width); the mapping is empty for a group without a member there."""
+    offsets, members, weights = self.csr
+    place = {int(b): i for i, b in enumerate(ids)}
+    out = []
+    for g in range(len(offsets) - 1):
+      m, w = members[offsets[g]:offsets[g + 1]], weights[offsets[g]:offsets[g + 1]]
+      if self.axes is None:
+        out.append({place[int(b)]: float(x) for b, x in zip(m, w) if int(b) in place})
+      else:
+        out.append(({place[int(b)]: (float(x), int(f)) for b, x, f in zip(m, w, self.axes[g].first)
+                     if int(b) in place}, self.axes[g].width))
+    return out
+
+  def session_pool(self, sess, scale, shift):
+    """pool(groups, init) of the open session `sess` for `step`: its `pool_trajectories`, or with axes
+    its `pool_event_trajectories` with out_stride = `stride` (first + width stays within every
+    member's own length, hence within the stride of any kind of session)."""
+    if self.axes is None:
+      return lambda groups, init: sess.pool_trajectories(scale, shift, groups, init)
+    return lambda groups, init: sess.pool_event_trajectories(scale, shift, groups, init, self.stride)
+
   def step(self, launch, pool):
-    """The pool step of `launch`, its session still open: pool(groups, init) is the session's
-    `pool_trajectories` with its scale and shift.  Only the groups with a member in the launch go to
-    the device; the others pass their accumulator through untouched."""
+    """The pool step of `launch`, its session still open: pool(groups, init) as `session_pool` makes
+    it.  Only the groups with a member in the launch go to the device; the others pass their
+    accumulator through untouched."""
     k = self._index[int(launch[2][0])]
     try:
       acc = self._futures[k - 1].result() if k else None
-      groups = _groups_within(self.csr, np.asarray(launch[2]))
-      active = [g for g, group in enumerate(groups) if group]
+      groups = self.groups_of(launch[2])
+      active = [g for g, group in enumerate(groups) if (group if self.axes is None else group[0])]
       if active:
         part = pool([groups[g] for g in active], None if acc is None else acc[active])
         if len(active) == len(groups):
           acc = part
         else:
-          if acc is None:
-            acc = np.zeros((len(groups),) + part.shape[1:])
-          else:
-            acc = acc.copy()
+          acc = np.zeros((len(groups),) + part.shape[1:]) if acc is None else acc.copy()
           acc[active] = part
       if self._futures[k].done():            # failed meanwhile by a launch in front that ended in an error
         self._futures[k].result()
@@ -824,41 +859,52 @@ def scaler_stats(outcome_pre: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
             np.array([np.nanstd(r, axis=0, ddof=1) for r in rows]))
 
 
-def _aggregate_analyses(agg_names, csr, pooled: np.ndarray, means: np.ndarray, prep: PreparedBatch,
-                        outcome_name, alpha: float, ranks, device: int = 0):
-  """(`aggregates`, `aggregate_summary`) of a batch from the pooled draws [G, N, T] (float64, data
-  scale) and the series' posterior means [B, T] on the data scale.  Per group: the observed outcome
-  and the posterior mean are pooled with the same weights (`pool_weighted`; the outcome is NaN
-  wherever a member is), the order statistics and per-draw totals of the pooled draws come from
-  `_native.summarize_draws` (ci_summarize_draws_f64: scale 1, shift 0, the batch's window flags), and
-  the reference's frames are built by `_compute_impact_device` over a `CausalImpactData` of the
-  pooled outcome, which is on the data scale already (standardize_data=False)."""
-  outcome = pool_weighted(prep.values[:, :, 0], csr)            # [G, T_all]: the raw pooled outcome
-  observed = pool_weighted(prep.observed, csr)                  # [G, T]: NaN in gap / tail
-  mean = pool_weighted(means, csr)                              # [G, T]
+def _frame_analyses(rows, alpha: float, ranks, device: int = 0):
+  """(`aggregates`, `aggregate_summary`) from one row per group: (name, the `CausalImpactData` of the
+  pooled outcome -- on the data scale already: standardize_data=False -- the pooled observed outcome
+  and the window flags over the model steps, the pooled posterior mean, the pooled draws [N, steps]
+  float64).  The order statistics and per-draw totals of the pooled draws come from
+  `_native.summarize_draws` (ci_summarize_draws_f64: scale 1, shift 0), and the reference's frames are
+  built by `_compute_impact_device`."""
   analyses = {}
-  for g, name in enumerate(agg_names):
-    try:
-      ci_data = cid.CausalImpactData(pd.DataFrame({outcome_name: outcome[g]}, index=prep.index),
-                                     prep.pre_period, prep.post_period, standardize_data=False)
-    except ValueError as e:
-      raise ValueError(f"aggregate {name!r}: {e}") from e
-    dsum = _native.summarize_draws(pooled[g], 1.0, 0.0, observed[g], prep.flags, ranks, device=device)
+  for name, ci_data, observed, flags, mean, draws in rows:
+    dsum = _native.summarize_draws(draws, 1.0, 0.0, observed, flags, ranks, device=device)
     rq = lib._device_summary_request(ci_data, alpha)             # pylint: disable=protected-access
-    rq.update(observed=observed[g], flags=prep.flags, ranks=ranks)
-    series, summary = lib._compute_impact_device(mean[g], dsum, rq, ci_data, alpha)   # pylint: disable=protected-access
+    rq.update(observed=observed, flags=flags, ranks=ranks)
+    series, summary = lib._compute_impact_device(mean, dsum, rq, ci_data, alpha)   # pylint: disable=protected-access
     analyses[name] = lib.CausalImpactAnalysis(series, summary, None)
   table = pd.concat([a.summary for a in analyses.values()], keys=list(analyses),
                     names=["aggregate", None])
   return analyses, table
 
 
+def _aggregate_analyses(agg_names, csr, pooled: np.ndarray, means: np.ndarray, prep: PreparedBatch,
+                        outcome_name, alpha: float, ranks, device: int = 0):
+  """(`aggregates`, `aggregate_summary`) of a batch from the pooled draws [G, N, T] (float64, data
+  scale) and the series' posterior means [B, T] on the data scale.  Per group: the observed outcome
+  and the posterior mean are pooled with the same weights (`pool_weighted`; the outcome is NaN
+  wherever a member is), the flags are the batch's, and the frames are built by `_frame_analyses` over
+  a `CausalImpactData` of the pooled outcome."""
+  outcome = pool_weighted(prep.values[:, :, 0], csr)            # [G, T_all]: the raw pooled outcome
+  observed = pool_weighted(prep.observed, csr)                  # [G, T]: NaN in gap / tail
+  mean = pool_weighted(means, csr)                              # [G, T]
+  rows = []
+  for g, name in enumerate(agg_names):
+    try:
+      ci_data = cid.CausalImpactData(pd.DataFrame({outcome_name: outcome[g]}, index=prep.index),
+                                     prep.pre_period, prep.post_period, standardize_data=False)
+    except ValueError as e:
+      raise ValueError(f"aggregate {name!r}: {e}") from e
+    rows.append((name, ci_data, observed[g], prep.flags, mean[g], pooled[g]))
+  return _frame_analyses(rows, alpha, ranks, device)
+
+
 # ------------------------------------------------------------------------------------------
 # Event-time aggregates: the pooled effect of groups of series of a panel
 # ------------------------------------------------------------------------------------------
 # The series of a panel have their own calendars; what they share is EVENT TIME, the number of rows
-# since each one's own treatment start.  These are the twins of the batch's helpers above for sums
-# over shifted windows of the members' steps (csrc/ci_pool_event.h).
+# since each one's own treatment start.  What differs from a batch is here: the axis of every group
+# and the sums over shifted windows of the members' steps; `HostPool` and `_PoolChain` take the axes.
 @dataclasses.dataclass
 class EventAxis:
   """The event-time axis of one group: tau = -L .. H - 1, column c of the group is step
@@ -968,118 +1014,17 @@ def event_plan(agg_names, csr, prep: PreparedPanel, outcome_name) -> EventPlan:
   return EventPlan(list(agg_names), csr, axes, observed, data)
 
 
-def _check_event_aggregates(event_aggregates, names, shared_streams: bool):
-  """`aggregate_groups` for `event_aggregates`, after the refusal of common random numbers."""
-  if shared_streams:
-    raise ValueError(
-        "`event_aggregates` cannot be combined with shared_streams=True: with common random numbers "
-        "the Monte-Carlo errors of all series are perfectly correlated, and pairing draw n of every "
-        "series is then not a draw from the joint posterior of independent series -- the pooled "
-        "bands would be wrong.  Fit with the default per-series streams.")
-  return aggregate_groups(event_aggregates, names)
-
-
-class EventHostPool:
-  """`HostPool` in event time, for panels that are fitted series by series: `add(b, ...)` for
-  b = 0, 1, ... adds w[g, b] * (trajectories[:, first_b : first_b + width_g] * scale + shift) to
-  pooled[g][:, :width_g] for every group that has b, float64, one rounding per operation.  `pooled`
-  [G, N, stride] float64, 0.0 beyond a group's width; `means`: every series' posterior mean over its
-  own steps on the data scale."""
-
-  def __init__(self, csr, axes: Sequence[EventAxis]):
-    self.csr, self.axes = csr, list(axes)
-    self.stride = max(axis.width for axis in self.axes)
-    self.pooled: Optional[np.ndarray] = None
-    self.means: List[np.ndarray] = []
-
-  def add(self, b: int, posterior_means, trajectories, scale, shift):
-    offsets, members, weights = self.csr
-    scale, shift = np.float64(scale), np.float64(shift)
-    value = np.asarray(trajectories).astype(np.float64) * scale + shift
-    self.means.append(np.asarray(posterior_means).astype(np.float64) * scale + shift)
-    if self.pooled is None:
-      self.pooled = np.zeros((len(self.axes), value.shape[0], self.stride))
-    for g, axis in enumerate(self.axes):
-      k = offsets[g] + int(np.searchsorted(members[offsets[g]:offsets[g + 1]], b))
-      if k < offsets[g + 1] and members[k] == b:
-        f, W = int(axis.first[k - offsets[g]]), axis.width
-        self.pooled[g, :, :W] = self.pooled[g, :, :W] + weights[k] * value[:, f:f + W]
-
-
-class _PanelPoolChain(_PoolChain):
-  """`_PoolChain` for the launches of a panel: the running sums [G, N, stride] of its event-time
-  aggregates.  A class of a panel holds whatever positions fall in it, so the launches do not cut the
-  positions into consecutive runs; they are chained in the order `panel_launches` lists them -- class
-  key ascending, ascending positions within a class, which its split over devices keeps -- and a
-  session adds its members in ascending position.  A group is therefore summed in (class key,
-  position) order: a function of the model and the series alone, the same on any number of devices,
-  and not plain position order when its members fall in different classes.  Every launch waits for
-  an earlier one of the list and every device runs its launches in list order
-  (`causalimpact_lib.map_by_device`), so no wait is circular; a failed launch fails every launch
-  behind it, as in `_PoolChain`."""
-
-  def __init__(self, launches, csr, axes: Sequence[EventAxis]):
-    super().__init__(launches, csr)
-    self.axes = list(axes)
-    self.stride = max(axis.width for axis in self.axes)
-
-  def groups_of(self, ids: Sequence[int]):
-    """The groups cut to the positions `ids` of one launch, whatever they are: per group (members,
-    width) with members {place within the launch: (weight, first)}, empty without a member there."""
-    offsets, members, weights = self.csr
-    place = {int(b): i for i, b in enumerate(ids)}
-    out = []
-    for g, axis in enumerate(self.axes):
-      rows = zip(members[offsets[g]:offsets[g + 1]], weights[offsets[g]:offsets[g + 1]], axis.first)
-      out.append(({place[int(b)]: (float(w), int(f)) for b, w, f in rows if int(b) in place},
-                  axis.width))
-    return out
-
-  def step(self, launch, pool):
-    """The pool step of `launch`, its session still open: pool(groups, init) is the session's
-    `pool_event_trajectories` with its scale and shift and out_stride = `stride`.  Only the groups
-    with a member in the launch go to the device; the others pass their accumulator through."""
-    k = self._index[int(launch[2][0])]
-    try:
-      acc = self._futures[k - 1].result() if k else None
-      groups = self.groups_of(launch[2])
-      active = [g for g, (group, _) in enumerate(groups) if group]
-      if active:
-        part = pool([groups[g] for g in active], None if acc is None else acc[active])
-        if len(active) == len(groups):
-          acc = part
-        else:
-          acc = np.zeros((len(groups),) + part.shape[1:]) if acc is None else acc.copy()
-          acc[active] = part
-      if self._futures[k].done():            # failed meanwhile by a launch in front that ended in an error
-        self._futures[k].result()
-      self._futures[k].set_result(acc)
-    except BaseException as e:
-      self.fail(launch, e)
-      raise
-
-
 def _event_aggregate_analyses(plan: EventPlan, pooled: np.ndarray, means: Sequence[np.ndarray],
                               alpha: float, ranks, device: int = 0):
-  """`_aggregate_analyses` in event time: (`aggregates`, `aggregate_summary`) of a panel from the
-  pooled draws [G, N, stride] (float64, data scale; group g owns its first width_g columns) and the
-  series' posterior means over their own steps on the data scale.  Per group the posterior mean is
-  pooled over the members' windows like the outcome (`pool_event_weighted`, the member order of the
-  draws), the pooled draws are summarised by `_native.summarize_draws` with the pooled flags, and the
-  frames are built by `_compute_impact_device` on the group's `event_time` index."""
+  """(`aggregates`, `aggregate_summary`) of a panel from the pooled draws [G, N, stride] (float64,
+  data scale; group g owns its first width_g columns) and the series' posterior means over their own
+  steps on the data scale.  Per group the posterior mean is pooled over the members' windows like the
+  outcome (`pool_event_weighted`, the member order of the draws), the flags are the axis', and the
+  frames are built by `_frame_analyses` on the group's `event_time` index."""
   mean = pool_event_weighted(means, plan.csr, plan.axes)
-  analyses = {}
-  for g, (name, axis) in enumerate(zip(plan.names, plan.axes)):
-    ci_data, observed, flags = plan.data[g], plan.observed[g], axis.flags
-    dsum = _native.summarize_draws(pooled[g][:, :axis.width], 1.0, 0.0, observed, flags, ranks,
-                                   device=device)
-    rq = lib._device_summary_request(ci_data, alpha)             # pylint: disable=protected-access
-    rq.update(observed=observed, flags=flags, ranks=ranks)
-    series, summary = lib._compute_impact_device(mean[g], dsum, rq, ci_data, alpha)   # pylint: disable=protected-access
-    analyses[name] = lib.CausalImpactAnalysis(series, summary, None)
-  table = pd.concat([a.summary for a in analyses.values()], keys=list(analyses),
-                    names=["aggregate", None])
-  return analyses, table
+  return _frame_analyses(
+      [(name, plan.data[g], plan.observed[g], axis.flags, mean[g], pooled[g][:, :axis.width])
+       for g, (name, axis) in enumerate(zip(plan.names, plan.axes))], alpha, ranks, device)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1124,8 +1069,9 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
   accumulated in numpy, series by series in order, from every fit's data-scale trajectories in
   float64 (same order, same formula), before its draws are dropped.
 
-  event_aggregates (panels only): the `EventPlan`.  The same in event time (`EventHostPool`): every
-  series is a class of its own on this route, so (class key, position) order is position order."""
+  event_aggregates (panels only): the `EventPlan`.  The same in event time (`HostPool` with the
+  axes): every series is a class of its own on this route, so (class key, position) order is position
+  order."""
   opts = dataclasses.replace(data_options, outcome_column=outcome_column)
   base_seed = lib._sanitize_seed(seed)   # pylint: disable=protected-access
   analyses = []
@@ -1134,7 +1080,7 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
     agg_names, csr, prep = aggregates
     host_pool = HostPool(csr)
   elif event_aggregates is not None:
-    host_pool = EventHostPool(event_aggregates.csr, event_aggregates.axes)
+    host_pool = HostPool(event_aggregates.csr, event_aggregates.axes)
   for b, frame in enumerate(frames):
     seed_b = base_seed if shared_streams else _native.series_stream_key(base_seed, b)
     if host_pool is not None:
@@ -1201,8 +1147,7 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
               model_options=model_options, inference_options=inference_options)
 
 
-def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None,
-                event_chain: Optional[_PanelPoolChain] = None):
+def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None):
   """One launch of the Gibbs sampler and its summaries on the device.  launch: (device, key,
   positions) as `panel_launches` lists them; kind: the session the positions run in --
     "ordinary"         `_native.Session`: series b of the launch is keyed by positions[0] + b, hence
@@ -1216,10 +1161,8 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
   Returns (out, dsum, csum): `fetch` of posterior_means [n, C, T] and `_DRAW_SCALARS` [n, C, S],
   `summarize`, and `summarize_components` (None unless InferenceOptions.components).  Every array
   keeps the series axis, and T is the longest series of the launch on every route.
-  chain (batches with aggregates): the launch's pool step runs after `summarize`, the session still
-  open.  event_chain (panels with event-time aggregates): the same with the windows of
-  `pool_event_trajectories`; first + width stays within every member's own length, hence within
-  the stride of any kind of session."""
+  chain (aggregates of a batch, event-time aggregates of a panel): the launch's pool step runs after
+  `summarize`, the session still open."""
   dev, _, ids = launch
   ids = np.asarray(ids, dtype=np.int64)
   mo, io = fit.model_options, fit.inference_options
@@ -1259,10 +1202,7 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
       dsum = {k: v[None] for k, v in dsum.items()}
     csum = sess.summarize_components(scale, shift, fit.ranks) if io.components else None
     if chain is not None:
-      chain.step(launch, lambda groups, init: sess.pool_trajectories(scale, shift, groups, init))
-    if event_chain is not None:
-      event_chain.step(launch, lambda groups, init: sess.pool_event_trajectories(
-          scale, shift, groups, init, event_chain.stride))
+      chain.step(launch, chain.session_pool(sess, scale, shift))
   finally:
     sess.close()
   if stride != T:            # (back at the stride of the longest series)
@@ -1283,8 +1223,7 @@ def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None):
   scale, shift = fit.scale[ids], fit.shift[ids]
   pool = None
   if chain is not None:
-    pool = lambda sess: chain.step(   # pylint: disable=unnecessary-lambda-assignment
-        launch, lambda groups, init: sess.pool_trajectories(scale, shift, groups, init))
+    pool = lambda sess: chain.step(launch, chain.session_pool(sess, scale, shift))   # pylint: disable=unnecessary-lambda-assignment
   res = _hmc.fit_hmc_batch(
       fit.y[ids], fit.mask[ids], None if fit.design is None else fit.design[ids],
       [fit.params[b] for b in ids], has_slope=mo.local_linear_trend, num_results=io.num_results,
@@ -1524,7 +1463,7 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   on; its pre-period ends before the longest gap any member leaves between pre-period and start, its
   post-period is the shortest window, 0 .. Hwin - 1.  Draw n of the group at tau is the sum over its
   members b of w_b * (draw n of series b at its own step start_b + tau, on the data scale), in
-  float64, added on the device that holds the trajectories (csrc/ci_pool_event.h; they are never
+  float64, added on the device that holds the trajectories (csrc/ci_pool.h; they are never
   downloaded) and handed from launch to launch.  The order of addition is (length class of the
   route, position in the panel) -- the order `panel_launches` lists the launches in, ascending
   positions within a launch -- which is a function of the model and the series alone: the result is
@@ -1551,7 +1490,7 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
                      f"{len(periods)} periods")
   names = list(range(B)) if names is None else list(names)
   agg = (None if event_aggregates is None else
-         _check_event_aggregates(event_aggregates, names, shared_streams))
+         _check_aggregates(event_aggregates, names, shared_streams, "event_aggregates"))
   for b, f in enumerate(frames):
     if list(f.columns) != list(frames[0].columns):
       raise ValueError(f"series {names[b]!r}: all series of a panel must share the columns")
@@ -1580,8 +1519,8 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
                  shared_streams)
   kind = "ordinary" if route["route"] == "equal_length" else route["route"]
   launches = panel_launches(route, inference_options.devices, shared_streams)
-  chain = None if plan is None else _PanelPoolChain(launches, plan.csr, plan.axes)
-  run = lambda launch: _run_launch(launch, kind, fit, event_chain=chain)   # pylint: disable=unnecessary-lambda-assignment
+  chain = None if plan is None else _PoolChain(launches, plan.csr, plan.axes)
+  run = lambda launch: _run_launch(launch, kind, fit, chain)   # pylint: disable=unnecessary-lambda-assignment
   means, dsum, diag_draws, csum = _assemble(launches, run if chain is None else chain.guarded(run),
                                             B, prep.y.shape[1])
   res = CausalImpactPanelAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,

@@ -1,14 +1,12 @@
 // ci_summary.hip -- the on-device summaries behind the C-ABI (kernels: ci_summary.h,
 // ci_components.h): ci_session_summarize, ci_session_summarize_components,
 // ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] on
-// draws the caller hands in; ci_session_pool_trajectories and ci_ll_session_pool_trajectories
-// (kernel: ci_pool.h) and ci_session_pool_event_trajectories (kernel: ci_pool_event.h) on the
-// trajectories a session holds.
+// draws the caller hands in; ci_session_pool_trajectories, ci_ll_session_pool_trajectories and
+// ci_session_pool_event_trajectories (kernels: ci_pool.h) on the trajectories a session holds.
 #include <cmath>
 #include <vector>
 
 #include "ci_pool.h"
-#include "ci_pool_event.h"
 #include "ci_session.h"
 #include "ci_summary.h"
 
@@ -156,64 +154,10 @@ static int check_groups(int B, int32_t G, const int32_t* offsets, const int32_t*
   return 0;
 }
 
-// ci_session_pool_trajectories / ci_ll_session_pool_trajectories: weighted sums over groups of
-// series of the [B, N, T] float32 trajectories resident in HBM.  Everything is checked before the
-// first device call.  The groups pass through the summary's `value` matrix (B * N*T doubles,
-// allocated on first use and kept), as many at a time as fit it: no device memory beyond the
-// scratch but the weight table.
-static int pool_resident(int device, hipStream_t stream, SummScratch& w, int B, int T, int N,
-                         const float* traj, const double* scale, const double* shift, int32_t G,
-                         const int32_t* offsets, const int32_t* members, const double* weights,
-                         const double* init, double* out) {
-  if (check_groups(B, G, offsets, members, weights)) return 1;
-  const long long NT = (long long)N * T;
-  std::vector<ci::PoolEntry> entries((size_t)offsets[G]);
-  for (int k = 0; k < offsets[G]; ++k) {
-    const int b = members[k];
-    entries[k] = ci::PoolEntry{(long long)b * NT, weights[k], scale[b], shift[b]};
-  }
-  HIP_TRY(hipSetDevice(device));
-  if (summ_scratch_alloc(w, B, T, N)) return 1;
-  const int per_pass = G < B ? G : (B < 65535 ? B : 65535);       // groups that fit `value` (grid.y)
-  DevBuf<ci::PoolEntry> d_entries;
-  DevBuf<int> d_offsets;
-  HIP_TRY(d_entries.alloc(entries.size() ? entries.size() : 1));
-  HIP_TRY(d_offsets.alloc((size_t)G + 1));
-  if (!entries.empty())
-    HIP_TRY(hipMemcpyAsync(d_entries.p, entries.data(), entries.size() * sizeof(ci::PoolEntry),
-                           hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_offsets.p, offsets, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-  const bool aligned = NT % 4 == 0 && (reinterpret_cast<uintptr_t>(traj) & 15u) == 0u;
-  const unsigned slices = (unsigned)((NT + 4 * ci::POOL_NT - 1) / (4 * ci::POOL_NT));
-  for (int g0 = 0; g0 < G; g0 += per_pass) {
-    const int ng = G - g0 < per_pass ? G - g0 : per_pass;
-    const size_t bytes = (size_t)ng * NT * sizeof(double);
-    if (init)
-      HIP_TRY(hipMemcpyAsync(w.value.p, init + (size_t)g0 * NT, bytes, hipMemcpyHostToDevice, stream));
-    if (aligned)
-      hipLaunchKernelGGL(ci::pool_kernel<true>, dim3(slices, ng), dim3(ci::POOL_NT), 0, stream, NT, traj,
-                         d_offsets.p + g0, d_entries.p, init ? 1 : 0, w.value.p);
-    else
-      hipLaunchKernelGGL(ci::pool_kernel<false>, dim3(slices, ng), dim3(ci::POOL_NT), 0, stream, NT, traj,
-                         d_offsets.p + g0, d_entries.p, init ? 1 : 0, w.value.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out + (size_t)g0 * NT, w.value.p, bytes, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
-  return 0;
-}
-
-// ci_session_pool_event_trajectories: pool_resident over windows of the members' rows, member k
-// from its step first[k] on, width[g] columns per group, in accumulators of out_stride columns.
-// The accumulators pass through `value` with rows of min(out_stride, T) columns -- no width exceeds
-// T, so min(num_groups, B) groups fit it at a time as in pool_resident -- and the columns of a wider
-// host row are zeroed on the host.
-static int pool_event_resident(int device, hipStream_t stream, SummScratch& w, int B, int T, int N,
-                               const float* traj, const double* scale, const double* shift, int32_t G,
-                               const int32_t* offsets, const int32_t* members, const double* weights,
-                               const int32_t* first, const int32_t* width, int32_t S,
-                               const double* init, double* out) {
-  if (check_groups(B, G, offsets, members, weights)) return 1;
+// The windows of ci_session_pool_event_trajectories: member k of a group from its step first[k] on,
+// width[g] columns per group, in accumulators of S = out_stride columns.
+static int check_windows(int T, int32_t G, const int32_t* offsets, const int32_t* members,
+                         const int32_t* first, const int32_t* width, int32_t S) {
   if (S < 1) return fail("out_stride must be >= 1, got %d", S);
   for (int g = 0; g < G; ++g) {
     if (width[g] < 1 || width[g] > S)
@@ -227,14 +171,34 @@ static int pool_event_resident(int device, hipStream_t stream, SummScratch& w, i
                     g, members[k], first[k], width[g], T);
     }
   }
+  return 0;
+}
+
+// The pool entry points: weighted sums over groups of series of the [B, N, T] float32 trajectories
+// resident in HBM.  Everything is checked before the first device call.  The groups pass through the
+// summary's `value` matrix (B * N*T doubles, allocated on first use and kept), as many at a time as
+// fit it: no device memory beyond the scratch but the tables.
+// first == NULL (ci_session_pool_trajectories / ci_ll_session_pool_trajectories): calendar time, a
+// group is ONE row of N*T doubles on the device and on the host.
+// Otherwise (ci_session_pool_event_trajectories): a group is N rows of S = out_stride doubles on the
+// host and of min(S, T) on the device -- no width exceeds T, so min(num_groups, B) groups fit `value`
+// at a time either way -- and the columns of a wider host row are zeroed on the host.
+static int pool_resident(int device, hipStream_t stream, SummScratch& w, int B, int T, int N,
+                         const float* traj, const double* scale, const double* shift, int32_t G,
+                         const int32_t* offsets, const int32_t* members, const double* weights,
+                         const int32_t* first, const int32_t* width, int32_t S,
+                         const double* init, double* out) {
+  if (check_groups(B, G, offsets, members, weights)) return 1;
+  if (first && check_windows(T, G, offsets, members, first, width, S)) return 1;
   const long long NT = (long long)N * T;
-  const int Sd = S < T ? S : T;                                     // row length on the device
-  bool aligned = T % 4 == 0 && (reinterpret_cast<uintptr_t>(traj) & 15u) == 0u;
+  const size_t group_rows = first ? N : 1;                          // rows per group
+  const long long Sh = first ? S : NT, Sd = first && T < S ? T : Sh;  // row length: host, device
+  bool aligned = (first ? T : NT) % 4 == 0 && (reinterpret_cast<uintptr_t>(traj) & 15u) == 0u;
   std::vector<ci::PoolEntry> entries((size_t)offsets[G]);
   for (int k = 0; k < offsets[G]; ++k) {
-    const int b = members[k];
-    entries[k] = ci::PoolEntry{(long long)b * NT + first[k], weights[k], scale[b], shift[b]};
-    aligned = aligned && first[k] % 4 == 0;
+    const int b = members[k], f = first ? first[k] : 0;
+    entries[k] = ci::PoolEntry{(long long)b * NT + f, weights[k], scale[b], shift[b]};
+    aligned = aligned && f % 4 == 0;
   }
   HIP_TRY(hipSetDevice(device));
   if (summ_scratch_alloc(w, B, T, N)) return 1;
@@ -247,39 +211,43 @@ static int pool_event_resident(int device, hipStream_t stream, SummScratch& w, i
     HIP_TRY(hipMemcpyAsync(d_entries.p, entries.data(), entries.size() * sizeof(ci::PoolEntry),
                            hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(d_tables.p, offsets, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_tables.p + G + 1, width, (size_t)G * sizeof(int), hipMemcpyHostToDevice, stream));
-  const long long quads = (long long)N * ((Sd + 3) / 4);
+  if (first)
+    HIP_TRY(hipMemcpyAsync(d_tables.p + G + 1, width, (size_t)G * sizeof(int), hipMemcpyHostToDevice, stream));
+  const long long quads = (long long)group_rows * ((Sd + 3) / 4);   // four elements per thread
   const unsigned blocks = (unsigned)((quads + ci::POOL_NT - 1) / ci::POOL_NT);
-  const size_t host_pitch = (size_t)S * sizeof(double), dev_pitch = (size_t)Sd * sizeof(double);
+  const size_t host_pitch = (size_t)Sh * sizeof(double), dev_pitch = (size_t)Sd * sizeof(double);
+  // `rows` rows between the host (pitch host_pitch) and `value`: one block when the pitches agree
+  auto copy = [&](void* dst, const void* src, size_t rows, bool to_device) {
+    const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    if (Sd == Sh) return hipMemcpyAsync(dst, src, rows * dev_pitch, kind, stream);
+    return hipMemcpy2DAsync(dst, to_device ? dev_pitch : host_pitch, src, to_device ? host_pitch : dev_pitch,
+                            dev_pitch, rows, kind, stream);
+  };
   for (int g0 = 0; g0 < G; g0 += per_pass) {
     const int ng = G - g0 < per_pass ? G - g0 : per_pass;
-    const size_t rows = (size_t)ng * N;
-    if (init) {
-      const double* src = init + (size_t)g0 * N * S;
-      if (Sd == S)
-        HIP_TRY(hipMemcpyAsync(w.value.p, src, rows * dev_pitch, hipMemcpyHostToDevice, stream));
-      else
-        HIP_TRY(hipMemcpy2DAsync(w.value.p, dev_pitch, src, host_pitch, dev_pitch, rows,
-                                 hipMemcpyHostToDevice, stream));
-    }
+    const size_t rows = (size_t)ng * group_rows, at = (size_t)g0 * group_rows * Sh;
+    if (init) HIP_TRY(copy(w.value.p, init + at, rows, true));
+    const dim3 grid(blocks, ng), block(ci::POOL_NT);
     const int* d_off = d_tables.p + g0;
     const int* d_width = d_tables.p + G + 1 + g0;
-    if (aligned)
-      hipLaunchKernelGGL(ci::pool_event_kernel<true>, dim3(blocks, ng), dim3(ci::POOL_NT), 0, stream, N, T,
-                         (long long)B * NT, traj, d_off, d_entries.p, d_width, Sd, init ? 1 : 0, w.value.p);
+    const int has_init = init ? 1 : 0;
+    if (!first && aligned)
+      hipLaunchKernelGGL(ci::pool_kernel<true>, grid, block, 0, stream, NT, traj, d_off, d_entries.p,
+                         has_init, w.value.p);
+    else if (!first)
+      hipLaunchKernelGGL(ci::pool_kernel<false>, grid, block, 0, stream, NT, traj, d_off, d_entries.p,
+                         has_init, w.value.p);
+    else if (aligned)
+      hipLaunchKernelGGL(ci::pool_event_kernel<true>, grid, block, 0, stream, N, T, (long long)B * NT, traj,
+                         d_off, d_entries.p, d_width, (int)Sd, has_init, w.value.p);
     else
-      hipLaunchKernelGGL(ci::pool_event_kernel<false>, dim3(blocks, ng), dim3(ci::POOL_NT), 0, stream, N, T,
-                         (long long)B * NT, traj, d_off, d_entries.p, d_width, Sd, init ? 1 : 0, w.value.p);
+      hipLaunchKernelGGL(ci::pool_event_kernel<false>, grid, block, 0, stream, N, T, (long long)B * NT, traj,
+                         d_off, d_entries.p, d_width, (int)Sd, has_init, w.value.p);
     HIP_TRY(hipGetLastError());
-    double* dst = out + (size_t)g0 * N * S;
-    if (Sd == S)
-      HIP_TRY(hipMemcpyAsync(dst, w.value.p, rows * dev_pitch, hipMemcpyDeviceToHost, stream));
-    else
-      HIP_TRY(hipMemcpy2DAsync(dst, host_pitch, w.value.p, dev_pitch, dev_pitch, rows,
-                               hipMemcpyDeviceToHost, stream));
+    HIP_TRY(copy(out + at, w.value.p, rows, false));
     HIP_TRY(hipStreamSynchronize(stream));
-    for (size_t row = 0; Sd < S && row < rows; ++row)                // no width reaches these columns
-      for (int c = Sd; c < S; ++c) dst[row * S + c] = 0.0;
+    for (size_t row = 0; Sd < Sh && row < rows; ++row)               // no width reaches these columns
+      for (long long c = Sd; c < Sh; ++c) out[at + row * Sh + c] = 0.0;
   }
   return 0;
 }
@@ -294,9 +262,9 @@ int ci_session_pool_event_trajectories(ci_session* s, const double* scale, const
     return fail("NULL argument");
   if (!s->ran) return fail("ci_session_pool_event_trajectories needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
-  return pool_event_resident(pb.device, s->stream, s->summ, pb.num_series, pb.T,
-                             pb.num_chains * pb.num_results, s->o_traj.p, scale, shift, num_groups, offsets,
-                             members, weights, first, width, out_stride, init, out);
+  return pool_resident(pb.device, s->stream, s->summ, pb.num_series, pb.T, pb.num_chains * pb.num_results,
+                       s->o_traj.p, scale, shift, num_groups, offsets, members, weights, first, width,
+                       out_stride, init, out);
 }
 
 int ci_session_pool_trajectories(ci_session* s, const double* scale, const double* shift,
@@ -306,7 +274,8 @@ int ci_session_pool_trajectories(ci_session* s, const double* scale, const doubl
   if (!s->ran) return fail("ci_session_pool_trajectories needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
   return pool_resident(pb.device, s->stream, s->summ, pb.num_series, pb.T, pb.num_chains * pb.num_results,
-                       s->o_traj.p, scale, shift, num_groups, offsets, members, weights, init, out);
+                       s->o_traj.p, scale, shift, num_groups, offsets, members, weights, nullptr, nullptr, 0,
+                       init, out);
 }
 
 int ci_ll_session_pool_trajectories(ci_ll_session* s, const double* scale, const double* shift,
@@ -315,7 +284,7 @@ int ci_ll_session_pool_trajectories(ci_ll_session* s, const double* scale, const
   if (!s || !scale || !shift || !offsets || !members || !weights || !out) return fail("NULL argument");
   if (!s->h_ran) return fail("ci_ll_session_pool_trajectories needs a finished ci_ll_session_hmc_run");
   return pool_resident(s->device, s->stream, s->summ, s->B, s->T, s->h_C * s->h_S, s->h_traj.p, scale,
-                       shift, num_groups, offsets, members, weights, init, out);
+                       shift, num_groups, offsets, members, weights, nullptr, nullptr, 0, init, out);
 }
 
 int ci_session_summarize(ci_session* s, const double* scale, const double* shift,

@@ -2,7 +2,7 @@
 tools/exp_panel.py (512 series, 5 covariates, lengths uniform in 257..512 -- one steps-per-thread
 class --, own periods, 1 chain x 1000 draws): the call with the argument off and with one group of
 all series, in interleaved runs after one warm-up of each; the pool step alone on a ragged session
-that holds the panel (csrc/ci_pool_event.h), one group of all series against one group of one
+that holds the panel (csrc/ci_pool.h), one group of all series against one group of one
 series; and the alternative the feature replaces -- the trajectories of a share of the panel (64
 series) downloaded and their shifted windows added up in numpy, scaled to the panel by the series
 count.
