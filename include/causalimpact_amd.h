@@ -323,6 +323,50 @@ int ci_session_summarize_components(ci_session* session, const double* scale, co
                                     double* regression_mean, double* regression_order,
                                     double* inclusion_prob, double* weight_mean,
                                     double* weight_order);
+/* One-step-ahead PREDICTION ERRORS of every fit of a finished run, for all B series of the session
+ * at once: for every pooled draw n (N = C*S, chain-major) the Kalman filter of that draw's model over
+ * the observed series, all in float64.  Additive: CI_ABI_VERSION stays 5; look the symbol up (dlsym)
+ * where an older library may be met.  The model of series b and draw n, with d = 1 + has_slope +
+ * (ns - 1) state components (level, [slope], ns - 1 seasonal effects):
+ *   sigma_obs, sigma_level, sigma_slope, sigma_drift: the float32 draws of ci_outputs widened to
+ *     double; H = sigma_obs^2, the process variances sigma_level^2, sigma_slope^2 (separately
+ *     rounded squares);
+ *   a = (init_level_loc, 0, ..), P = 0 but P[0][0] = init_level_scale^2, P[1][1] =
+ *     init_slope_scale^2 (with a slope) and, over the effects i, j, init_seasonal_scale^2 *
+ *     ((i == j) - 1 / ns) -- the members of the ci_series_params the session was created with;
+ *   transition T_t: level += slope; at a step t whose season_change[t] is set the effects x become
+ *     (x_1, .., x_{ns-2}, -sum x); Q_t: sigma_level^2 on P[0][0], sigma_slope^2 on P[1][1], and at
+ *     such a step (sigma_drift / ns)^2 on EVERY entry of the effects' block;
+ *   Z picks the level and the first effect;
+ *   reg[n, t] = sum over j = 0..P-1, ascending from 0.0, of (double)X[b, t, j] * (double)weights[b, n, j].
+ * For t = 0 .. T_b - 1 (T_b = T, or the series' own length in a ragged session):
+ *   m = Z a;   F = Z P Z' + H;   f = m + reg[n, t]
+ *   forecast[n, t] = f * scale[b] + shift[b]                (two roundings, as ci_session_summarize)
+ *   variance[n, t] = (F * scale[b]) * scale[b]
+ *   if mask[b, t] == 0:  v = (double)y[b, t] - f
+ *                        pit[n, t] = 0.5 * erfc(-v / sqrt(2 F))
+ *                        loglik[n] += -0.5 * (log(2 pi) + log(F) + v * v / F)
+ *                        a += (P Z' / F) v;   P -= (P Z') (P Z')' / F
+ *   else:                pit[n, t] = 0.0                    (no observation to score)
+ *   if t + 1 < T_b:      a = T_t a;   P = T_t P T_t' + Q_t
+ * so forecast and variance at a masked step are those of the several-steps-ahead forecast from the
+ * last observation.  Beyond T_b (padding of a ragged session) f = 0: the forecast reads shift[b],
+ * variance and pit 0; none of it carries meaning there.
+ * scale, shift [B] as handed to ci_session_summarize; ranks: num_ranks (1..8) 0-based order
+ * statistics over the N draws.  Outputs (host, caller-allocated, float64; each may be NULL: it is
+ * then skipped and its matrix is not built):
+ *   forecast_mean [B, T]   forecast_order [B, num_ranks, T]   variance_mean [B, T]   pit_mean [B, T]
+ *   loglik [B, N]          (per draw, on the model's scale)
+ * Means and order statistics over the draws are those of ci_session_summarize_components.
+ * Ordinary and both kinds of ragged sessions are taken, on every kernel route; the models: a trend
+ * with or without slope, alone or with ONE block of 2 to 7 seasons.  The matrices pass one after
+ * another through the scratch of ci_session_summarize: no device memory beyond it but five doubles
+ * per series.  Checked before any device call: the arguments but the outputs are not NULL, the block
+ * list is one of the above, a finished ci_session_run, num_ranks in [1, 8], ranks in [0, N). */
+int ci_session_summarize_predictions(ci_session* session, const double* scale, const double* shift,
+                                     int32_t num_ranks, const int32_t* ranks,
+                                     double* forecast_mean, double* forecast_order,
+                                     double* variance_mean, double* pit_mean, double* loglik);
 /* Weighted sums over GROUPS of series of the predictive trajectories of a finished run, draw by
  * draw: the draws of a pooled effect (all units, a region), whose quantiles are not sums of the
  * per-series quantiles.  Additive: CI_ABI_VERSION stays 5; look the symbol up (dlsym) where an older

@@ -20,6 +20,8 @@ MAX_SUMMARY_RANKS = 8   # == ci::SUMM_MAX_RANKS (csrc/ci_summary.h)
 COMPONENT_OUTPUTS = ("trend_mean", "trend_order", "seasonal_mean", "seasonal_order",
                      "regression_mean", "regression_order", "inclusion_prob", "weight_mean",
                      "weight_order")
+# the output arrays of ci_session_summarize_predictions, in argument order
+PREDICTION_OUTPUTS = ("forecast_mean", "forecast_order", "variance_mean", "pit_mean", "loglik")
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, "lib", "libcausalimpact_amd.so")
 
@@ -111,6 +113,9 @@ def load():
                                      C.c_void_p]
   L.ci_session_summarize_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                 C.c_void_p] + [C.c_void_p] * 9
+  if hasattr(L, "ci_session_summarize_predictions"):   # (additive: a library built before it lacks it)
+    L.ci_session_summarize_predictions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                   C.c_void_p] + [C.c_void_p] * 5
   for pool_fn in (L.ci_session_pool_trajectories, L.ci_ll_session_pool_trajectories):
     pool_fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p, C.c_void_p]
@@ -171,7 +176,8 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_create", "ci_session_create_ragged", "ci_session_create_ragged_seasonal", "ci_session_run", "ci_session_run_streamed", "ci_session_fetch",
           "ci_session_algorithmic_bytes", "ci_session_kernel_name", "ci_session_destroy",
           "ci_session_profile", "ci_ll_session_kernel_name",
-          "ci_session_summarize", "ci_session_summarize_components", "ci_summarize_draws", "ci_summarize_draws_f64",
+          "ci_session_summarize", "ci_session_summarize_components",
+          "ci_session_summarize_predictions", "ci_summarize_draws", "ci_summarize_draws_f64",
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
           "ci_session_pool_event_trajectories",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
@@ -650,6 +656,38 @@ class Session:
     _check(self._lib.ci_session_summarize_components(
         self._h, sc.ctypes.data, sh.ctypes.data, int(R), rk.ctypes.data,
         *[_ptr(arrs.get(k)) for k in COMPONENT_OUTPUTS]))
+    return arrs
+
+  def summarize_predictions(self, scale, shift, ranks, want=None) -> Dict[str, np.ndarray]:
+    """On-device one-step-ahead prediction errors of every fit (ci_session_summarize_predictions):
+    for every pooled draw the Kalman filter of that draw's model over the observed series, in
+    float64 (`causalimpact_lib._prediction_summary_host` is the same definition in numpy).  scale,
+    shift: scalars or [B], as for `summarize`; ranks: 1 to 8 order statistics.  Returns float64 arrays
+    that keep the series axis: forecast_mean [B,T], forecast_order [B,R,T], variance_mean [B,T],
+    pit_mean [B,T] (0 at the masked steps), loglik [B,N].  `want`: the names to compute (default:
+    all); the others are skipped on the device too."""
+    fn = getattr(self._lib, "ci_session_summarize_predictions", None)
+    if fn is None:
+      raise NativeError("the loaded library has no ci_session_summarize_predictions: rebuild it")
+    pb = self.pb
+    B, T, N = pb.num_series, pb.T, pb.num_chains * pb.num_results
+    rk = np.ascontiguousarray(ranks, dtype=np.int32).reshape(-1)
+    sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
+    for name, a in (("scale", sc), ("shift", sh)):
+      if a.shape not in ((), (B,)):
+        raise ValueError(f"`{name}` must be a scalar or have one entry per series ({B}), got shape {a.shape}")
+    sc = np.ascontiguousarray(np.broadcast_to(sc, (B,)))
+    sh = np.ascontiguousarray(np.broadcast_to(sh, (B,)))
+    shapes = dict(forecast_mean=(B, T), forecast_order=(B, rk.size, T), variance_mean=(B, T),
+                  pit_mean=(B, T), loglik=(B, N))
+    if want is not None:
+      unknown = [k for k in want if k not in PREDICTION_OUTPUTS]
+      if unknown:
+        raise ValueError(f"unknown prediction outputs {unknown}: choose from {list(PREDICTION_OUTPUTS)}")
+      shapes = {k: v for k, v in shapes.items() if k in want}
+    arrs = {k: np.empty(v, np.float64) for k, v in shapes.items()}
+    _check(fn(self._h, sc.ctypes.data, sh.ctypes.data, int(rk.size), rk.ctypes.data,
+              *[_ptr(arrs.get(k)) for k in PREDICTION_OUTPUTS]))
     return arrs
 
   def pool_trajectories(self, scale, shift, groups, init=None) -> np.ndarray:

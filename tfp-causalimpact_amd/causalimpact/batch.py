@@ -212,6 +212,10 @@ def summary_table(names, alpha, ranks, dsum, *, n_win, n_obs, obs_mean, obs_sum,
 _DRAW_SCALARS = ("observation_noise_scale", "level_scale")
 _PER_DRAW = ("per_draw", "per_draw_order")
 _PER_COLUMN = ("inclusion_prob", "weight_mean", "weight_order")
+_PER_DRAW_LOGLIK = ("loglik",)       # of the prediction summary: [B, draws]
+# the parameter draws the prediction errors are filtered from (`lib._prediction_summary_host`)
+_PARAMETER_DRAWS = ("observation_noise_scale", "level_scale", "slope_scale", "seasonal_drift_scales",
+                    "weights")
 
 
 def _cut(arrays: Dict[str, np.ndarray], num_steps: int, whole=()) -> Dict[str, np.ndarray]:
@@ -226,10 +230,14 @@ class CausalImpactBatchAnalysis:
   when more than one chain was run."""
 
   def __init__(self, prepared, names, alpha, posterior_means, device_summary, ranks, columns,
-               diagnostic_draws, component_summary=None):
+               diagnostic_draws, component_summary=None, prediction_summary=None, state_dim=0):
     self._prep, self._names, self.alpha = prepared, list(names), alpha
     # {name: [B, ...]} of ci_session_summarize_components (InferenceOptions.components), or None
     self._csum = component_summary
+    # {name: [B, ...]} of ci_session_summarize_predictions (InferenceOptions.prediction_errors), or
+    # None, and the state dimension of the model (the first step `fit_quality` scores)
+    self._psum, self._state_dim = prediction_summary, state_dim
+    self._quality: Optional[pd.DataFrame] = None
     self._means, self._dsum, self._ranks, self._columns = posterior_means, device_summary, ranks, columns
     # {key: [B, chains, draws]} of the scalars the diagnostics rank, or None for one chain.  The
     # diagnostics themselves (three rank / FFT passes per key per series) are computed on access:
@@ -301,8 +309,39 @@ class CausalImpactBatchAnalysis:
       series, summary = lib._compute_impact_device(            # pylint: disable=protected-access
           self._means[b, :Tb], dsum, rq, ci_data, self.alpha)
       self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b),
-                                                *self._component_frames(b, ci_data, Tb))
+                                                *self._component_frames(b, ci_data, Tb),
+                                                *self._prediction_frames(b, ci_data, Tb))
     return self._cache[b]
+
+  def _prediction_inputs(self, b: int, num_steps: int):
+    """(summary, observed, conditioned) of series b over its `num_steps` steps."""
+    p = self._prep
+    psum = _cut({k: v[b] for k, v in self._psum.items()}, num_steps, _PER_DRAW_LOGLIK)
+    return psum, p.observed[b, :num_steps], ~p.mask[b, :num_steps]
+
+  def _prediction_frames(self, b: int, ci_data, num_steps: int):
+    """(prediction_errors, fit_quality) of series b, or (None, None) when they were not asked for."""
+    if self._psum is None:
+      return None, None
+    psum, observed, conditioned = self._prediction_inputs(b, num_steps)
+    return lib._prediction_frames(                              # pylint: disable=protected-access
+        psum, self._ranks, self.alpha, observed, conditioned, self._state_dim,
+        lib.posterior_processing.model_index(ci_data), ci_data.data.index)
+
+  @property
+  def fit_quality(self) -> Optional[pd.DataFrame]:
+    """One row per series with the entries of `CausalImpactAnalysis.fit_quality` (None unless
+    InferenceOptions.prediction_errors): which fits of the batch to trust."""
+    if self._psum is None:
+      return None
+    if self._quality is None:
+      rows = []
+      for b in range(len(self)):
+        psum, observed, conditioned = self._prediction_inputs(b, self._series_view(b)[3])
+        cols = lib._prediction_columns(psum, self._ranks, self.alpha, observed, conditioned)   # pylint: disable=protected-access
+        rows.append(lib._fit_quality(cols, psum["loglik"], self.alpha, observed, self._state_dim))   # pylint: disable=protected-access
+      self._quality = pd.DataFrame(rows, index=pd.Index(self._names, name="series"))
+    return self._quality
 
   def _component_frames(self, b: int, ci_data, num_steps: int):
     """(components, coefficients) of series b over its `num_steps` steps, or (None, None) when they
@@ -330,6 +369,13 @@ class PerSeriesBatchAnalysis(CausalImpactBatchAnalysis):
     self.summary = pd.concat([a.summary for a in analyses], keys=self._names, names=["series", None])
     self.aggregates = None
     self.aggregate_summary = None
+
+  @property
+  def fit_quality(self) -> Optional[pd.DataFrame]:
+    if any(a.fit_quality is None for a in self._cache.values()):
+      return None
+    return pd.DataFrame([self._cache[b].fit_quality for b in range(len(self))],
+                        index=pd.Index(self._names, name="series"))
 
   def diagnostics_of(self, b: int):
     return self._cache[range(len(self))[b]].diagnostics
@@ -1039,7 +1085,16 @@ def _options(alpha, data_options, model_options, inference_options):
     raise ValueError("`alpha` must be between 0 and 1.")
   if inference_options.sampler not in ("gibbs", "hmc"):
     raise ValueError(f"sampler must be 'gibbs' or 'hmc', got {inference_options.sampler!r}")
+  if inference_options.prediction_errors:     # (a state too wide for the filter: refused before any fit)
+    lib.check_prediction_state(model_options.local_linear_trend, model_options.seasons)
   return data_options, model_options, inference_options
+
+
+def _state_dim(model_options, inference_options) -> int:
+  """The state dimension `fit_quality` scores from; 0 (unused, unchecked) without the option."""
+  if not inference_options.prediction_errors:
+    return 0
+  return lib.check_prediction_state(model_options.local_linear_trend, model_options.seasons)
 
 
 def _frames_outcome_first(data, data_options):
@@ -1121,6 +1176,12 @@ class _Fit:
   shared_streams: bool
   model_options: lib.ModelOptions
   inference_options: lib.InferenceOptions
+  # InferenceOptions.prediction_errors only: (sd [B], mean [B]) of every series' pre-period outcome
+  # as its OWN scaler fits them (`scaler_stats`) -- the prediction summary is put on the data scale
+  # with these, so that a series' frames equal its single fit's bit for bit (`scale` and `shift`
+  # come from the vectorised pass and may differ from them in the last bit)
+  own_scale: Optional[np.ndarray] = None
+  own_shift: Optional[np.ndarray] = None
 
 
 def _sampler_outcome(prep, data_options) -> np.ndarray:
@@ -1132,6 +1193,14 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
              shared_streams) -> _Fit:
   """The `_Fit` of a prepared batch or panel: y = `_sampler_outcome(prep)`, lengths [B], pre_sd [B]
   the sd of every series' own pre-period outcome."""
+  own_shift = own_scale = None
+  if inference_options.prediction_errors:
+    if isinstance(prep, PreparedPanel):
+      stats = [scaler_stats(prep.raw[b][prep.model_rows[b][:nb], 0][None])
+               for b, nb in enumerate(prep.num_pre)]
+      own_shift, own_scale = (np.array([st[i][0] for st in stats]) for i in (0, 1))
+    else:
+      own_shift, own_scale = scaler_stats(prep.values[:, prep.model_rows[:prep.num_pre], 0])
   with np.errstate(invalid="ignore"):
     params = [_model.series_params(
         y[b, :Tb], prep.mask[b, :Tb], None if prep.design is None else prep.design[b, :Tb],
@@ -1144,7 +1213,8 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
               flags=prep.flags, params=params,
               ranks=lib._summary_ranks(num_draws, (alpha / 2.0, 1.0 - alpha / 2.0)),   # pylint: disable=protected-access
               seed=lib._sanitize_seed(seed), shared_streams=shared_streams,   # pylint: disable=protected-access
-              model_options=model_options, inference_options=inference_options)
+              model_options=model_options, inference_options=inference_options,
+              own_scale=own_scale, own_shift=own_shift)
 
 
 def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None):
@@ -1158,9 +1228,11 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
                        series starts at its own step 0) and the stride rounded up to a multiple of 4
                        (every row 16-byte aligned), the padding as in `PreparedPanel`: y NaN, mask
                        True, design 0, observed NaN, flags 0.
-  Returns (out, dsum, csum): `fetch` of posterior_means [n, C, T] and `_DRAW_SCALARS` [n, C, S],
-  `summarize`, and `summarize_components` (None unless InferenceOptions.components).  Every array
-  keeps the series axis, and T is the longest series of the launch on every route.
+  Returns (out, dsum, csum, psum): `fetch` of posterior_means [n, C, T] and `_DRAW_SCALARS` [n, C, S],
+  `summarize`, `summarize_components` (None unless InferenceOptions.components) and the prediction
+  summary (None unless InferenceOptions.prediction_errors): `summarize_predictions` for the block
+  lists the device takes, `_host_predictions` from the fetched parameter draws for the others.  Every
+  array keeps the series axis, and T is the longest series of the launch on every route.
   chain (aggregates of a batch, event-time aggregates of a panel): the launch's pool step runs after
   `summarize`, the session still open."""
   dev, _, ids = launch
@@ -1201,6 +1273,11 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
     if len(ids) == 1:        # (`summarize` drops the series axis of a session of one series)
       dsum = {k: v[None] for k, v in dsum.items()}
     csum = sess.summarize_components(scale, shift, fit.ranks) if io.components else None
+    psum = None
+    if io.prediction_errors and lib.device_predictions_supported(num_seasons):
+      psum = sess.summarize_predictions(fit.own_scale[ids], fit.own_shift[ids], fit.ranks)
+    elif io.prediction_errors:
+      psum = _host_predictions(fit, ids, T, sess.fetch(list(_PARAMETER_DRAWS)), season_change)
     if chain is not None:
       chain.step(launch, chain.session_pool(sess, scale, shift))
   finally:
@@ -1208,14 +1285,45 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
   if stride != T:            # (back at the stride of the longest series)
     out, dsum = _cut(out, T, _DRAW_SCALARS), _cut(dsum, T, _PER_DRAW)
     csum = None if csum is None else _cut(csum, T, _PER_COLUMN)
-  return out, dsum, csum
+    psum = None if psum is None else _cut(psum, T, _PER_DRAW_LOGLIK)
+  return out, dsum, csum, psum
+
+
+def _host_predictions(fit: _Fit, ids, num_steps: int, draws: Dict[str, np.ndarray],
+                      season_change) -> Dict[str, np.ndarray]:
+  """The prediction summary of the series `ids` of a launch in numpy (`lib._prediction_summary_host`),
+  from the launch's parameter draws {name: [n, C, S, ...]} (a name the model lacks may be missing):
+  the routes whose models the device filter does not take.  Arrays [n, ...] over `num_steps` steps,
+  with the padding convention of the device beyond a series' length."""
+  mo = fit.model_options
+  num_seasons = _model.expand_seasons(mo.seasons, 1)[0]
+  n, R = len(ids), len(fit.ranks)
+  out = None
+  for i, b in enumerate(int(b) for b in ids):
+    Tb = int(fit.lengths[b])
+    pooled = {k: v[i].reshape((v.shape[1] * v.shape[2],) + v.shape[3:]) for k, v in draws.items()}
+    one = lib._prediction_summary_host(                         # pylint: disable=protected-access
+        np.where(fit.mask[b, :Tb], 0.0, fit.y[b, :Tb]).astype(np.float32), fit.mask[b, :Tb],
+        None if fit.design is None else fit.design[b, :Tb].astype(np.float32),
+        np.asarray(season_change)[:, :Tb], num_seasons, mo.local_linear_trend, fit.params[b], pooled,
+        fit.own_scale[b], fit.own_shift[b], fit.ranks)
+    if out is None:
+      N = one["loglik"].shape[0]
+      out = dict(forecast_mean=np.zeros((n, num_steps)), forecast_order=np.zeros((n, R, num_steps)),
+                 variance_mean=np.zeros((n, num_steps)), pit_mean=np.zeros((n, num_steps)),
+                 loglik=np.zeros((n, N)))
+    out["forecast_mean"][i], out["forecast_order"][i] = fit.own_shift[b], fit.own_shift[b]
+    for k, v in one.items():
+      out[k][i, ..., :v.shape[-1]] = v
+  return out
 
 
 def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None):
   """`_run_launch` for the one-launch HMC path (`_hmc.fit_hmc_batch`: B x chains HMC chains, then
   the latent paths, the predictive trajectories and their summary on the device): consecutive
   positions of a batch, series b keyed by positions[0] + b.  It keeps no latent draws, hence no
-  component summary."""
+  component summary; the prediction summary is `_host_predictions` from the parameter draws, which
+  it fetches for that."""
   from causalimpact import _hmc  # pylint: disable=import-outside-toplevel
   dev, _, ids = launch
   ids = np.asarray(ids, dtype=np.int64)
@@ -1230,8 +1338,13 @@ def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None):
       num_warmup=io.num_warmup_steps, num_chains=io.num_chains, seed=fit.seed, device=dev,
       series_offset=int(ids[0]), shared_streams=fit.shared_streams, prior=io.hmc_prior,
       summary=dict(scale=scale, shift=shift, observed=fit.observed[ids],
-                   flags=fit.flags, ranks=fit.ranks), after_summary=pool)
-  return {k: res[k] for k in ("posterior_means", *_DRAW_SCALARS)}, res["summary"], None
+                   flags=fit.flags, ranks=fit.ranks), after_summary=pool,
+      also_fetch=("slope_scale", "weights") if io.prediction_errors else ())
+  psum = None
+  if io.prediction_errors:
+    draws = {k: res[k] for k in _PARAMETER_DRAWS if k in res}
+    psum = _host_predictions(fit, ids, fit.y.shape[1], draws, np.zeros((0, fit.y.shape[1]), np.uint8))
+  return {k: res[k] for k in ("posterior_means", *_DRAW_SCALARS)}, res["summary"], None, psum
 
 
 def _scatter(parts, num_series: int, num_steps: int, whole, fill) -> Dict[str, np.ndarray]:
@@ -1251,7 +1364,7 @@ def _scatter(parts, num_series: int, num_steps: int, whole, fill) -> Dict[str, n
 
 
 def _assemble(launches, run, num_series: int, num_steps: int):
-  """Runs `launches` [(device, key, positions)] through `run(launch) -> (out, dsum, csum)`
+  """Runs `launches` [(device, key, positions)] through `run(launch) -> (out, dsum, csum[, psum])`
   (`_run_launch`; the launches of a device in turn, the devices side by side) and puts the series
   axis back together.  Returns what the containers take:
     means [B, T_max]  the chain mean of posterior_means, 0 beyond a series' length;
@@ -1259,24 +1372,27 @@ def _assemble(launches, run, num_series: int, num_steps: int):
                       a series' length;
     diag_draws        {name: [B, C, S]} of `_DRAW_SCALARS`, or None for one chain;
     csum              the component summary {name: [B, ...]}, NaN beyond a series' length (the
-                      `_PER_COLUMN` arrays have no time axis), or None when `run` returns none.
+                      `_PER_COLUMN` arrays have no time axis), or None when `run` returns none;
+    psum              (only when `run` returns four values) the prediction summary {name: [B, ...]}
+                      likewise (loglik has no time axis), or None.
   One launch that holds all B series in order at full stride is the result as it stands: its blocks
   (512 series: 24 MB of summary in pinned memory) are not copied a second time."""
   results = lib.map_by_device(run, launches)
   # per launch: the chain mean with the scalar draws, the device summary, the component summary
   groups = [(dict({k: out[k] for k in _DRAW_SCALARS}, means=out["posterior_means"].mean(axis=1)),
-             dsum, csum) for out, dsum, csum in results]
-  fetched, dsum, csum = groups[0]
+             *summaries) for out, *summaries in results]
+  fetched, dsum, *optional = groups[0]
   if not (len(launches) == 1 and list(launches[0][2]) == list(range(num_series))
           and fetched["means"].shape[-1] == num_steps):
     def gather(i, whole, fill):
       parts = [(list(launch[2]), group[i]) for launch, group in zip(launches, groups)]
       return _scatter(parts, num_series, num_steps, whole, fill)
     fetched, dsum = gather(0, _DRAW_SCALARS, 0), gather(1, _PER_DRAW, np.nan)
-    csum = None if csum is None else gather(2, _PER_COLUMN, np.nan)
+    optional = [None if one is None else gather(2 + i, whole, np.nan)
+                for i, (one, whole) in enumerate(zip(optional, (_PER_COLUMN, _PER_DRAW_LOGLIK)))]
   means = fetched.pop("means")
   diag_draws = fetched if fetched[_DRAW_SCALARS[0]].shape[1] > 1 else None
-  return means, dsum, diag_draws, csum
+  return (means, dsum, diag_draws, *optional)
 
 
 def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
@@ -1404,10 +1520,10 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     run = lambda launch: _run_hmc_launch(launch, fit, chain)          # pylint: disable=unnecessary-lambda-assignment
   else:
     run = lambda launch: _run_launch(launch, "ordinary", fit, chain)   # pylint: disable=unnecessary-lambda-assignment
-  means, dsum, diag_draws, csum = _assemble(launches, run if chain is None else chain.guarded(run),
-                                            B, T)
+  means, dsum, diag_draws, csum, psum = _assemble(
+      launches, run if chain is None else chain.guarded(run), B, T)
   res = CausalImpactBatchAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
-                                  csum)
+                                  csum, psum, _state_dim(model_options, inference_options))
   if chain is not None:
     # the posterior means on the data scale with the statistics every series' own frame uses
     mu, sd = scaler_stats(prep.values[:, prep.model_rows[:prep.num_pre], 0])
@@ -1521,10 +1637,10 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   launches = panel_launches(route, inference_options.devices, shared_streams)
   chain = None if plan is None else _PoolChain(launches, plan.csr, plan.axes)
   run = lambda launch: _run_launch(launch, kind, fit, chain)   # pylint: disable=unnecessary-lambda-assignment
-  means, dsum, diag_draws, csum = _assemble(launches, run if chain is None else chain.guarded(run),
-                                            B, prep.y.shape[1])
+  means, dsum, diag_draws, csum, psum = _assemble(
+      launches, run if chain is None else chain.guarded(run), B, prep.y.shape[1])
   res = CausalImpactPanelAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
-                                  csum)
+                                  csum, psum, _state_dim(model_options, inference_options))
   if chain is not None:
     # the posterior means on the data scale with the statistics every series' own frame uses
     data_means = []

@@ -104,6 +104,24 @@ class CausalImpactAnalysis:
   # upper of its weight on the model's scale; None for a model without covariates.
   components: Optional[pd.DataFrame] = None
   coefficients: Optional[pd.DataFrame] = None
+  # InferenceOptions(prediction_errors=True) only.  `prediction_errors`: indexed like `series`, NaN on
+  # the rows the model never sees; per step the one-step-ahead forecast of the Kalman filter run with
+  # every draw's scales and weights (forecast: mean over the draws; forecast_lower / forecast_upper:
+  # alpha/2 and 1 - alpha/2 quantiles over the draws; forecast_sd: root of the mean predictive
+  # variance), error = observed - forecast, standardized_error = error / forecast_sd and pit, the
+  # mean over the draws of Phi(v / sqrt F) -- the mixture-predictive CDF at the observation.  The last
+  # three are NaN where the model does not condition on the observation (post-period, missing
+  # values); `forecast` is the several-steps-ahead forecast from the last observation there.
+  # `fit_quality`: n_scored, rmse, mae, mase (below 1: the model beats a random walk), coverage
+  # (share of scored steps with alpha/2 <= pit <= 1 - alpha/2; nominal 1 - alpha), loglik_mean,
+  # loglik_sd (over the draws, in the sampler's units) over the observed pre-period steps t >= the
+  # state dimension.  (Init-only pseudo-fields kept as plain attributes: `dataclasses.fields` and
+  # `asdict` of this class stay what they were.)
+  prediction_errors: dataclasses.InitVar[Optional[pd.DataFrame]] = None
+  fit_quality: dataclasses.InitVar[Optional[pd.Series]] = None
+
+  def __post_init__(self, prediction_errors, fit_quality):
+    self.prediction_errors, self.fit_quality = prediction_errors, fit_quality
 
 
 @dataclasses.dataclass
@@ -158,8 +176,16 @@ class InferenceOptions:
   # draws wherever the predictive summary runs there (csrc/ci_components.h), also for batches and
   # panels, which keep no draws; in numpy from the pooled draws on the other routes.
   components: bool = False
+  # Also score the model: one-step-ahead prediction errors of the Kalman filter run with every
+  # draw's parameters (`CausalImpactAnalysis.prediction_errors` / `.fit_quality`, the check `bsts`
+  # users know as bsts.prediction.errors).  On the GPU that holds the draws wherever the predictive
+  # summary runs there (csrc/ci_predict.h), also for batches and panels; in numpy from the parameter
+  # draws on the other routes.  (An init-only pseudo-field kept as a plain attribute: the fields,
+  # `asdict` and equality of the options stay what they were.)
+  prediction_errors: dataclasses.InitVar[bool] = False
 
-  def __post_init__(self):
+  def __post_init__(self, prediction_errors=False):
+    self.prediction_errors = bool(prediction_errors)
     if self.num_warmup_steps is None:
       self.num_warmup_steps = math.ceil(self.num_results / 9)
 
@@ -202,6 +228,12 @@ def fit_causalimpact(data: pd.DataFrame,
   if inference_options.components:
     base = request if request is not None else _device_summary_request(ci_data, alpha)
     comp_request = dict(scale=base["scale"], shift=base["shift"], quantiles=base["quantiles"])
+  pred_request = None
+  if inference_options.prediction_errors:
+    state_dim = check_prediction_state(model_options.local_linear_trend, model_options.seasons)
+    base = request if request is not None else _device_summary_request(ci_data, alpha)
+    pred_request = dict(scale=base["scale"], shift=base["shift"], quantiles=base["quantiles"],
+                        observed=base["observed"])
   samples, posterior_means, posterior_trajectories, device_summary = _run_sampler(
       ci_data=ci_data, prior_level_sd=model_options.prior_level_sd, seed=seed,
       num_results=inference_options.num_results,
@@ -211,7 +243,7 @@ def fit_causalimpact(data: pd.DataFrame,
       sampler=inference_options.sampler, summary_request=request,
       hmc_init=inference_options.hmc_init, hmc_prior=inference_options.hmc_prior,
       kernel_flags=inference_options.kernel_flags, component_request=comp_request,
-      keep_trajectories=trajectory_sink is not None)
+      keep_trajectories=trajectory_sink is not None, prediction_request=pred_request)
   if trajectory_sink is not None:
     base = request if request is not None else _device_summary_request(ci_data, alpha)
     trajectory_sink(posterior_means, posterior_trajectories, base["scale"], base["shift"])
@@ -257,8 +289,14 @@ def fit_causalimpact(data: pd.DataFrame,
         csum, comp_request["ranks"], num_draws, alpha, posterior_processing.model_index(ci_data),
         ci_data.data.index,
         list(ci_data.feature_ts.columns) if ci_data.feature_ts is not None else None)
+  prediction_errors = fit_quality = None
+  if pred_request is not None:
+    prediction_errors, fit_quality = _prediction_frames(
+        pred_request["summary"], pred_request["ranks"], alpha, pred_request["observed"],
+        pred_request["conditioned"], state_dim, posterior_processing.model_index(ci_data),
+        ci_data.data.index)
   return CausalImpactAnalysis(series, summary, posterior, samples.get("diagnostics"), components,
-                              coefficients)
+                              coefficients, prediction_errors, fit_quality)
 
 
 def _component_summary_host(level, seasonal_levels, weights, X, scale, shift, ranks) -> Dict:
@@ -331,6 +369,184 @@ def _component_frames(csum: Dict, ranks, num_draws: int, alpha: float, model_idx
          "mean": np.asarray(csum["weight_mean"], np.float64), "lower": lower, "upper": upper},
         index=pd.Index(list(design_columns)))
   return components, coefficients
+
+
+# the most state components the prediction-error filter takes (== CI_MAX_D of the oracle)
+PREDICTION_MAX_STATE = 64
+_erfc = np.vectorize(math.erfc, otypes=[np.float64])
+
+
+def prediction_state_dim(has_slope: bool, num_seasons: Sequence[int]) -> int:
+  """State components of the model: level, [slope], n - 1 effects per seasonal block."""
+  return 1 + int(bool(has_slope)) + sum(int(n) - 1 for n in num_seasons)
+
+
+def check_prediction_state(local_linear_trend: bool, seasons: Sequence) -> int:
+  """The state dimension of ModelOptions(local_linear_trend, seasons); ValueError when it is more
+  than the prediction-error filter takes (raised before anything is fitted)."""
+  d = prediction_state_dim(local_linear_trend, [
+      int(getattr(s, "num_seasons", s[0] if isinstance(s, (tuple, list)) else s)) for s in seasons])
+  if d > PREDICTION_MAX_STATE:
+    raise ValueError(f"InferenceOptions(prediction_errors=True) takes a state of at most "
+                     f"{PREDICTION_MAX_STATE} components, this model has {d}")
+  return d
+
+
+def device_predictions_supported(num_seasons: Sequence[int]) -> bool:
+  """The block lists ci_session_summarize_predictions takes: none, or one block of 2 to 7 seasons."""
+  return len(num_seasons) == 0 or (len(num_seasons) == 1 and 2 <= int(num_seasons[0]) <= 7)
+
+
+def _prediction_summary_host(y, mask, X, season_change, num_seasons, has_slope, params, draws,
+                             scale, shift, ranks) -> Dict:
+  """The prediction-error summary of one series in numpy, from the pooled PARAMETER draws alone:
+  for every draw the Kalman filter of that draw's model over the observed series -- the definitions
+  of ci_session_summarize_predictions (include/causalimpact_amd.h) in float64, for any block list.
+  Vectorised over the draws, a loop over time, a dense d x d recursion.
+    y, mask [T]: the outcome the sampler saw and its missing flags (y is not read where masked);
+    X [T, P] or None; season_change [K, T]; num_seasons [K]; params: the series' parameter dict
+    (`_model.series_params`: init_level_loc, init_level_scale, init_slope_scale, init_seasonal_scale);
+    draws: observation_noise_scale, level_scale, slope_scale [N], seasonal_drift_scales [N, K],
+    weights [N, P], all in the sampler's units; scale, shift: the map to the data scale.
+  Returns forecast_mean [T], forecast_order [R, T], variance_mean [T], pit_mean [T] (0 where
+  masked) and loglik [N], as the device returns them for one series."""
+  y = np.asarray(y, np.float64)
+  mask = np.asarray(mask, bool)
+  T = y.shape[0]
+  scale, shift = np.float64(scale), np.float64(shift)
+  num_seasons = [int(n) for n in num_seasons]
+  K, hs = len(num_seasons), int(bool(has_slope))
+  d = prediction_state_dim(hs, num_seasons)
+  if d > PREDICTION_MAX_STATE:
+    raise ValueError(f"prediction errors take a state of at most {PREDICTION_MAX_STATE} components, "
+                     f"this model has {d}")
+  sc = np.asarray(season_change, np.uint8).reshape(K, T) if K else np.zeros((0, T), np.uint8)
+  so = np.asarray(draws["observation_noise_scale"], np.float64).reshape(-1)
+  N = so.shape[0]
+  H = so * so
+  sl = np.asarray(draws["level_scale"], np.float64).reshape(N)
+  ss = np.asarray(draws["slope_scale"], np.float64).reshape(N) if hs else None
+  sd = np.asarray(draws["seasonal_drift_scales"], np.float64).reshape(N, -1) if K else None
+  reg = np.zeros((N, T))
+  w = draws.get("weights")
+  if X is not None and w is not None and np.shape(w)[-1] > 0:
+    w, X = np.asarray(w, np.float64).reshape(N, -1), np.asarray(X, np.float64)
+    for j in range(w.shape[1]):
+      reg += w[:, j, None] * X[None, :, j]
+  offsets = np.cumsum([1 + hs] + [n - 1 for n in num_seasons])[:-1] if K else []
+  Z = np.zeros(d)
+  Z[0] = 1.0
+  for o in offsets:
+    Z[o] = 1.0
+  a = np.zeros((N, d))
+  a[:, 0] = float(params["init_level_loc"])
+  P = np.zeros((N, d, d))
+  P[:, 0, 0] = float(params["init_level_scale"]) ** 2
+  if hs:
+    P[:, 1, 1] = float(params["init_slope_scale"]) ** 2
+  for o, n in zip(offsets, num_seasons):
+    P[:, o:o + n - 1, o:o + n - 1] = float(params["init_seasonal_scale"]) ** 2 * (np.eye(n - 1) - 1.0 / n)
+  forecast, variance, pit = np.zeros((N, T)), np.zeros((N, T)), np.zeros((N, T))
+  loglik = np.zeros(N)
+  for t in range(T):
+    pz = P @ Z                                      # [N, d]
+    F = pz @ Z + H
+    f = a @ Z + reg[:, t]
+    forecast[:, t] = f * scale + shift
+    variance[:, t] = (F * scale) * scale
+    if not mask[t]:
+      v = y[t] - f
+      pit[:, t] = 0.5 * _erfc(-v / np.sqrt(2.0 * F))
+      loglik += -0.5 * (math.log(2.0 * math.pi) + np.log(F) + v * v / F)
+      a = a + (pz / F[:, None]) * v[:, None]
+      P = P - pz[:, :, None] * pz[:, None, :] / F[:, None, None]
+    if t + 1 < T:
+      Tm = np.eye(d)
+      if hs:
+        Tm[0, 1] = 1.0
+      Q = np.zeros((N, d, d))
+      Q[:, 0, 0] = sl * sl
+      if hs:
+        Q[:, 1, 1] = ss * ss
+      for k, (o, n) in enumerate(zip(offsets, num_seasons)):
+        if sc[k, t]:
+          blk = np.zeros((n - 1, n - 1))
+          blk[:-1, 1:] = np.eye(n - 2)
+          blk[-1, :] = -1.0
+          Tm[o:o + n - 1, o:o + n - 1] = blk
+          q = sd[:, k] / n
+          Q[:, o:o + n - 1, o:o + n - 1] = (q * q)[:, None, None]
+      a = a @ Tm.T
+      P = Tm @ P @ Tm.T + Q
+  ranks = list(ranks)
+  return dict(forecast_mean=forecast.mean(axis=0), forecast_order=np.sort(forecast, axis=0)[ranks],
+              variance_mean=variance.mean(axis=0), pit_mean=pit.mean(axis=0), loglik=loglik)
+
+
+PREDICTION_COLUMNS = ("forecast", "forecast_lower", "forecast_upper", "forecast_sd", "error",
+                      "standardized_error", "pit")
+FIT_QUALITY_ENTRIES = ("n_scored", "rmse", "mae", "mase", "coverage", "loglik_mean", "loglik_sd")
+
+
+def _prediction_columns(psum: Dict, ranks, alpha: float, observed, conditioned) -> Dict[str, np.ndarray]:
+  """The `PREDICTION_COLUMNS` over the model's steps from the prediction summary of one series
+  (device or host: the layout of `_prediction_summary_host`).  observed [T]: the outcome on the data
+  scale (NaN: none); conditioned [T] bool: the steps whose observation the model conditions on.
+  error, standardized_error and pit are NaN on every other step."""
+  num_draws = np.shape(psum["loglik"])[-1]
+  rank_pos = {r: i for i, r in enumerate(ranks)}
+  (lo_a, hi_a, g_a), (lo_b, hi_b, g_b) = _quantile_ranks(num_draws, (alpha / 2.0, 1.0 - alpha / 2.0))
+  order = np.asarray(psum["forecast_order"], np.float64)
+  by_rank = {r: order[rank_pos[r]] for r in (lo_a, hi_a, lo_b, hi_b)}
+  observed = np.asarray(observed, np.float64)
+  conditioned = np.asarray(conditioned, bool) & ~np.isnan(observed)
+  forecast = np.asarray(psum["forecast_mean"], np.float64)
+  with np.errstate(invalid="ignore", divide="ignore"):
+    sd = np.sqrt(np.asarray(psum["variance_mean"], np.float64))
+    error = np.where(conditioned, observed - forecast, np.nan)
+    return {
+        "forecast": forecast,
+        "forecast_lower": _lerp_order_stats(by_rank, lo_a, hi_a, g_a),
+        "forecast_upper": _lerp_order_stats(by_rank, lo_b, hi_b, g_b),
+        "forecast_sd": sd,
+        "error": error,
+        "standardized_error": error / sd,
+        "pit": np.where(conditioned, np.asarray(psum["pit_mean"], np.float64), np.nan)}
+
+
+def _fit_quality(cols: Dict[str, np.ndarray], loglik, alpha: float, observed, state_dim: int) -> pd.Series:
+  """The `FIT_QUALITY_ENTRIES` of one series from its `_prediction_columns`, the per-draw
+  log-likelihoods and the data-scale outcome: over the SCORED steps, those the model conditions on
+  (error is not NaN) from step `state_dim` on -- the earlier ones only measure the initial prior."""
+  observed = np.asarray(observed, np.float64)
+  scored = ~np.isnan(cols["error"])
+  scored[:state_dim] = False
+  e, pit = cols["error"][scored], cols["pit"][scored]
+  # the random walk's error at the scored steps whose predecessor is observed
+  prev_ok = np.concatenate([[False], ~np.isnan(observed[:-1])])
+  naive = np.abs(np.diff(observed, prepend=np.nan))[scored & prev_ok]
+  ll = np.asarray(loglik, np.float64)
+  with np.errstate(invalid="ignore", divide="ignore"):
+    mae = np.mean(np.abs(e)) if e.size else np.nan
+    return pd.Series({
+        "n_scored": float(e.size),
+        "rmse": np.sqrt(np.mean(e * e)) if e.size else np.nan,
+        "mae": mae,
+        "mase": mae / np.mean(naive) if naive.size else np.nan,
+        "coverage": np.mean((pit >= alpha / 2.0) & (pit <= 1.0 - alpha / 2.0)) if e.size else np.nan,
+        "loglik_mean": np.mean(ll),
+        "loglik_sd": np.std(ll, ddof=1) if ll.size > 1 else np.nan}, name="fit_quality")
+
+
+def _prediction_frames(psum: Dict, ranks, alpha: float, observed, conditioned, state_dim: int,
+                       model_idx: pd.Index, full_idx: pd.Index):
+  """(prediction_errors, fit_quality) of one series: `_prediction_columns` indexed like the `series`
+  frame -- `full_idx`, NaN on the rows the model never sees -- and `_fit_quality`."""
+  cols = _prediction_columns(psum, ranks, alpha, observed, conditioned)
+  frame = pd.DataFrame(cols, index=model_idx)
+  if not model_idx.equals(full_idx):
+    frame = frame.reindex(full_idx, fill_value=np.nan)
+  return frame, _fit_quality(cols, psum["loglik"], alpha, observed, state_dim)
 
 
 def _sanitize_seed(seed: Optional[_SeedType]) -> Tuple[int, int]:
@@ -451,12 +667,16 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
                  dtype=np.float32, seasons=(), num_chains=1, devices=None,
                  local_linear_trend=False, sampler="gibbs", summary_request=None,
                  hmc_init="gibbs", hmc_prior="slab", kernel_flags=0, component_request=None,
-                 keep_trajectories=False):
+                 keep_trajectories=False, prediction_request=None):
   """_train_causalimpact_sts plus, when `summary_request` is given (single device, Gibbs), the
   on-device summary of the predictive draws; the [draws, T] trajectories then stay in HBM and
   are returned as None.  `component_request` (scale, shift, quantiles): on that route the component
   summary of the session (ci_session_summarize_components) is left in it under "summary", with the
   "ranks" it was taken at; on every other route the dict comes back as it went in.
+  `prediction_request` (scale, shift, quantiles): the prediction-error summary is left in it under
+  "summary" with its "ranks" and "conditioned" (the steps the model conditions on) -- taken on the
+  device on that route (ci_session_summarize_predictions; a trend with at most one block of 2-7
+  seasons), by `_prediction_summary_host` from the parameter draws on every other.
   `keep_trajectories`: the trajectories are wanted on the host; the fit then takes the route of
   draws pooled on the host, whose summary runs the same kernels on the same values."""
   if model is not None:
@@ -550,6 +770,14 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
               if k in csum:
                 csum[k] = csum[k] * cond_s
           component_request["summary"] = csum
+        if prediction_request is not None and device_predictions_supported(num_seasons):
+          prediction_request["ranks"] = _summary_ranks(len(chain_ids) * num_results,
+                                                       prediction_request["quantiles"])
+          psum = sess.summarize_predictions(
+              scale=np.float64(prediction_request["scale"]) * cond_s,
+              shift=np.float64(prediction_request["shift"]) + cond_mu * np.float64(prediction_request["scale"]),
+              ranks=prediction_request["ranks"])
+          prediction_request["summary"] = {k: v[0] for k, v in psum.items()}
       finally:
         sess.close()
       return part
@@ -576,6 +804,24 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
         float(summary_request["shift"]) + cond_mu * float(summary_request["scale"]),
         summary_request["observed"], summary_request["flags"], summary_request["ranks"],
         device=devs[0])
+  if prediction_request is not None:
+    prediction_request["conditioned"] = ~mask
+    if "summary" not in prediction_request:
+      # the routes without a session: the same definitions in numpy, from the parameter draws in the
+      # sampler's units, on the outcome and design as the sampler saw them (float64 for the float64
+      # Gibbs kernels, float32 otherwise)
+      f64 = np_dtype == np.float64 and sampler == "gibbs"
+      seen = np.float64 if f64 else np.float32
+      fields = ("observation_noise_scale", "level_scale", "slope_scale", "seasonal_drift_scales", "weights")
+      draws = {k: out[k].reshape((out[k].shape[0] * out[k].shape[1],) + out[k].shape[2:]) for k in fields}
+      prediction_request["ranks"] = _summary_ranks(draws["level_scale"].shape[0],
+                                                   prediction_request["quantiles"])
+      prediction_request["summary"] = _prediction_summary_host(
+          np.where(mask, 0.0, y).astype(seen), mask, None if design is None else design.astype(seen),
+          season_change, num_seasons, local_linear_trend, params, draws,
+          np.float64(prediction_request["scale"]) * cond_s,
+          np.float64(prediction_request["shift"]) + cond_mu * np.float64(prediction_request["scale"]),
+          prediction_request["ranks"])
   if (cond_mu, cond_s) != (0.0, 1.0):
     # back to the caller's scale, in float64: locations get the offset, everything else the scale
     out = {k: np.asarray(v, np.float64) * cond_s for k, v in out.items()}

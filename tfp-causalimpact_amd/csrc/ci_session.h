@@ -65,6 +65,10 @@ struct ci_session {
   DevBuf<float> cpart, cw;
   DevBuf<double> cv;
   SummScratch summ;          // on-device summarisation (ci_summary.h)
+  // ci_session_summarize_predictions: the B parameter blocks the session was created with, and on
+  // the device (first call) [B, 4] initial moments followed by [B] ones (ci_predict.h)
+  std::vector<ci_series_params> params;
+  DevBuf<double> pred_init;
   bool ran = false;
   ci_problem kpb;          // what the kernel runs (== pb except for long trend-only series)
   bool inert_block = false;

@@ -1,5 +1,6 @@
 // ci_summary.hip -- the on-device summaries behind the C-ABI (kernels: ci_summary.h,
-// ci_components.h): ci_session_summarize, ci_session_summarize_components,
+// ci_components.h, ci_predict.h): ci_session_summarize, ci_session_summarize_components,
+// ci_session_summarize_predictions,
 // ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] on
 // draws the caller hands in; ci_session_pool_trajectories, ci_ll_session_pool_trajectories and
 // ci_session_pool_event_trajectories (kernels: ci_pool.h) on the trajectories a session holds.
@@ -7,6 +8,7 @@
 #include <vector>
 
 #include "ci_pool.h"
+#include "ci_predict.h"
 #include "ci_session.h"
 #include "ci_summary.h"
 
@@ -111,6 +113,9 @@ hipError_t comp_launch_regression(hipStream_t stream, int B, int N, int T, int P
                                   double* out);
 hipError_t comp_launch_row_stats(hipStream_t stream, size_t rows, int N, const double* M,
                                  double* mean, int* nonzero);
+// The launch of ci_predict.hip (kernels: ci_predict.h).
+hipError_t predict_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
+                          const PredArgs& args);
 }  // namespace ci
 
 // ci_summarize_draws / ci_summarize_draws_f64: one series of draws from the host, uploaded into a
@@ -383,6 +388,81 @@ int ci_session_summarize_components(ci_session* s, const double* scale, const do
     if (inclusion_prob)
       for (size_t e = 0; e < BP; ++e) inclusion_prob[e] = (double)count[e] / (double)N;
   }
+  return 0;
+}
+
+int ci_session_summarize_predictions(ci_session* s, const double* scale, const double* shift,
+                                     int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
+                                     double* forecast_order, double* variance_mean, double* pit_mean,
+                                     double* loglik) {
+  if (!s || !scale || !shift || !ranks) return fail("NULL argument");
+  const ci_problem& pb = s->pb;          // (not kpb: the inert block of a long trend-only series is no part of the model)
+  if (pb.num_blocks > 1 || (pb.num_blocks == 1 && (pb.num_seasons[0] < 2 || pb.num_seasons[0] > 7))) {
+    std::string blocks;
+    for (int k = 0; k < pb.num_blocks; ++k) blocks += (k ? ", " : "") + std::to_string(pb.num_seasons[k]);
+    return fail("ci_session_summarize_predictions takes a trend with at most one block of 2 to 7 seasons, "
+                "this session has the blocks (%s)", blocks.c_str());
+  }
+  if (!s->ran) return fail("ci_session_summarize_predictions needs a finished ci_session_run");
+  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
+  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, R = num_ranks;
+  if (check_ranks(R, ranks, N)) return 1;
+  HIP_TRY(hipSetDevice(pb.device));
+  SummScratch& w = s->summ;
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  hipStream_t stream = s->stream;
+  double* d_scale = w.obs.p + (size_t)B * T;
+  double* d_shift = d_scale + B;
+  if (!s->pred_init.p) {
+    // per series: the initial moments of its ci_series_params, and the 1.0 the regression term is scaled by
+    std::vector<double> init((size_t)5 * B, 1.0);
+    for (int b = 0; b < B; ++b) {
+      const ci_series_params& q = s->params[b];
+      init[4 * b + 0] = q.init_level_loc;
+      init[4 * b + 1] = q.init_level_scale * q.init_level_scale;
+      init[4 * b + 2] = q.init_slope_scale * q.init_slope_scale;
+      init[4 * b + 3] = q.init_seasonal_scale * q.init_seasonal_scale;
+    }
+    HIP_TRY(s->pred_init.alloc(init.size()));
+    HIP_TRY(hipMemcpy(s->pred_init.p, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
+  // The regression term of every draw and step in `cum`, once; then one filter pass per requested
+  // matrix through `value`, its row means in `obs`, its order statistics in `order`, the per-draw
+  // log-likelihoods (with the first pass) in `draw`.
+  const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
+  if (P > 0)
+    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
+                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
+  ci::PredArgs a;
+  a.N = N; a.T = T;
+  a.y = s->y.p; a.mask = s->mask.p; a.season_change = s->season_change.p; a.series_T = d_series_T;
+  a.obs = s->o_obs.p; a.lscale = s->o_lscale.p; a.sscale = s->o_sscale.p; a.drift = s->o_drift.p;
+  a.init = s->pred_init.p; a.scales = d_scale; a.shifts = d_shift;
+  a.reg = P > 0 ? w.cum.p : nullptr;
+  a.out = w.value.p;
+  bool ll_pending = loglik != nullptr;
+  auto pass = [&](int which, double* mean_dst, double* order_dst) -> int {
+    a.ll = ll_pending ? w.draw.p : nullptr;
+    HIP_TRY(ci::predict_launch(stream, B, pb.has_slope, NS, which, a));
+    if (mean_dst) HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * T, N, w.value.p, w.obs.p, nullptr));
+    if (order_dst)
+      HIP_TRY(launch_select(stream, N, T, B * T, R, w.ranks.p, w.value.p, nullptr, w.order.p, nullptr));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (mean_dst)
+      HIP_TRY(hipMemcpy(mean_dst, w.obs.p, (size_t)B * T * sizeof(double), hipMemcpyDeviceToHost));
+    if (order_dst)
+      HIP_TRY(hipMemcpy(order_dst, w.order.p, (size_t)B * R * T * sizeof(double), hipMemcpyDeviceToHost));
+    if (ll_pending)
+      HIP_TRY(hipMemcpy(loglik, w.draw.p, (size_t)B * N * sizeof(double), hipMemcpyDeviceToHost));
+    ll_pending = false;
+    return 0;
+  };
+  if ((forecast_mean || forecast_order) && pass(ci::PRED_FORECAST, forecast_mean, forecast_order)) return 1;
+  if (variance_mean && pass(ci::PRED_VARIANCE, variance_mean, nullptr)) return 1;
+  if ((pit_mean || ll_pending) && pass(ci::PRED_PIT, pit_mean, nullptr)) return 1;
   return 0;
 }
 
