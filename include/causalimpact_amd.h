@@ -367,6 +367,42 @@ int ci_session_summarize_predictions(ci_session* session, const double* scale, c
                                      int32_t num_ranks, const int32_t* ranks,
                                      double* forecast_mean, double* forecast_order,
                                      double* variance_mean, double* pit_mean, double* loglik);
+/* Per-draw totals over SUB-WINDOWS of the session's steps, for all B series at once: how an effect
+ * unfolds inside the post-period (week 1 against week 4, a promotion's second phase), whose bands,
+ * relative effect and tail-area probability need every draw's total over the window and are not
+ * combinations of the per-step bands.  Additive: CI_ABI_VERSION stays 5; look the symbol up (dlsym)
+ * where an older library may be met.  The [B, N, T] float32 trajectories (N = C*S pooled draws,
+ * chain-major; T the session's stride) are read where they are, in HBM, and only the columns of the
+ * 64-step tiles a window intersects; no [B, T, N] matrix is built.  Series b has the num_windows
+ * windows first[b, w], count[b, w] (steps of the session; windows may overlap, count may be 0).  For
+ * every series b, window w and draw n, all in float64:
+ *   pred_sum = 0.0; point_sum = 0.0
+ *   for t = first[b, w] .. first[b, w] + count[b, w] - 1, ascending:
+ *     v        = trajectory[b, n, t] * scale[b] + shift[b]     (two roundings, no fused multiply-add)
+ *     pred_sum = pred_sum + v
+ *     point    = -(v - observed[b, t])
+ *     if point == point: point_sum = point_sum + point        (NaN, no observation: skipped)
+ *   per_draw[b, w, 0, n] = pred_sum;   per_draw[b, w, 1, n] = point_sum
+ * which a plain loop on the host reproduces bit for bit, and which for a window equal to the steps
+ * whose flag bit 1 is set are ci_session_summarize's per_draw and per_draw_order, bit for bit.
+ * per_draw_order[b, w, k, r] is the ranks[r]-th smallest of per_draw[b, w, k, :]; count = 0 gives
+ * totals 0.0 and order statistics 0.0.  scale, shift [B] and observed [B, T] as handed to
+ * ci_session_summarize; first, count [B, num_windows]; ranks: num_ranks 0-based order statistics
+ * over the N draws.  Outputs (host, caller-allocated, float64; each may be NULL):
+ *   per_draw [B, num_windows, 2, N]       per_draw_order [B, num_windows, 2, num_ranks]
+ * Ordinary and both kinds of ragged sessions are taken, on every kernel route; in a ragged session
+ * every series passes windows of its own.  The scratch of ci_session_summarize is neither built nor
+ * touched: the device memory of a call is the tables (observed, scale, shift, first, count, ranks)
+ * plus 2 * (N + 8) doubles per (series, window), given back when it returns.  No load touches
+ * memory outside the trajectories, observed and the tables.
+ * Checked before any device call, the error text naming the offending window: a finished run, no
+ * NULL argument but the two outputs, num_windows in [1, 1024], first >= 0, count >= 0, first +
+ * count <= T, num_ranks in [1, 8], ranks in [0, N). */
+int ci_session_summarize_windows(ci_session* session, const double* scale, const double* shift,
+                                 const double* observed, int32_t num_windows,
+                                 const int32_t* first, const int32_t* count,
+                                 int32_t num_ranks, const int32_t* ranks,
+                                 double* per_draw, double* per_draw_order);
 /* Weighted sums over GROUPS of series of the predictive trajectories of a finished run, draw by
  * draw: the draws of a pooled effect (all units, a region), whose quantiles are not sums of the
  * per-series quantiles.  Additive: CI_ABI_VERSION stays 5; look the symbol up (dlsym) where an older
@@ -534,6 +570,14 @@ int ci_ll_session_pool_trajectories(ci_ll_session* session, const double* scale,
                                     int32_t num_groups, const int32_t* offsets,
                                     const int32_t* members, const double* weights, const double* init,
                                     double* out);
+/* ci_session_summarize_windows for the trajectories of the last ci_ll_session_hmc_run (any session,
+ * B series, N = num_chains x num_results): same arguments, same checks, same arithmetic, same
+ * kernel; T is the session's T. */
+int ci_ll_session_summarize_windows(ci_ll_session* session, const double* scale, const double* shift,
+                                    const double* observed, int32_t num_windows,
+                                    const int32_t* first, const int32_t* count,
+                                    int32_t num_ranks, const int32_t* ranks,
+                                    double* per_draw, double* per_draw_order);
 int ci_ll_session_kernel_name(const ci_ll_session* session, char* buf, int32_t buflen);
 /* Algorithmic bytes of the last configured HMC fit (DESIGN.md "Roofline", cfg3). */
 int ci_ll_session_algorithmic_bytes(const ci_ll_session* session, double* bytes);

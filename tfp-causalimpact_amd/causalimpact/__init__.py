@@ -19,6 +19,8 @@ from causalimpact.batch import CausalImpactBatchAnalysis
 from causalimpact.batch import fit_causalimpact_batch
 from causalimpact.batch import CausalImpactPanelAnalysis
 from causalimpact.batch import fit_causalimpact_panel
+from causalimpact.batch import calendar_windows
+from causalimpact.batch import event_windows
 
 
 from causalimpact.plot import plot

@@ -116,6 +116,11 @@ def load():
   if hasattr(L, "ci_session_summarize_predictions"):   # (additive: a library built before it lacks it)
     L.ci_session_summarize_predictions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                    C.c_void_p] + [C.c_void_p] * 5
+  for name in ("ci_session_summarize_windows", "ci_ll_session_summarize_windows"):
+    if hasattr(L, name):                               # (additive: a library built before it lacks it)
+      getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]
   for pool_fn in (L.ci_session_pool_trajectories, L.ci_ll_session_pool_trajectories):
     pool_fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p, C.c_void_p]
@@ -178,6 +183,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_profile", "ci_ll_session_kernel_name",
           "ci_session_summarize", "ci_session_summarize_components",
           "ci_session_summarize_predictions", "ci_summarize_draws", "ci_summarize_draws_f64",
+          "ci_session_summarize_windows", "ci_ll_session_summarize_windows",
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
           "ci_session_pool_event_trajectories",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
@@ -417,6 +423,67 @@ def pool_event_host(trajectories, scale, shift, groups, init=None, out_stride=No
       if f < 0 or f + W > tr.shape[2]:
         raise ValueError(f"group {g}: member {b} from step {f} over {W} columns leaves [0, {tr.shape[2]})")
       out[g, :, :W] = out[g, :, :W] + weights[k] * (tr[b, :, f:f + W].astype(np.float64) * sc[b] + sh[b])
+  return out
+
+
+def window_totals_host(trajectories, scale, shift, observed, first, count) -> np.ndarray:
+  """What `summarize_windows` computes, as a plain loop: trajectories [B, N, T] (float32 or float64),
+  scale, shift scalars or [B], observed [T] or [B, T] (NaN = no observation), first, count [W] or
+  [B, W] in steps.  Returns per_draw [B, W, 2, N] float64: for every series, window and draw the sum
+  over the window's steps, ascending, of value = trajectory * scale + shift (two roundings) and of
+  -(value - observed) with the NaN steps skipped; count = 0 gives 0.0.  One rounding per operation,
+  in the order of include/causalimpact_amd.h -- so it is the definition the device is compared with,
+  and the route of the fits whose draws are pooled on the host."""
+  tr = np.asarray(trajectories)
+  if tr.ndim != 3:
+    raise ValueError(f"`trajectories` must be [B, N, T], got shape {tr.shape}")
+  B, N, T = tr.shape
+  sc = np.broadcast_to(np.asarray(scale, np.float64), (B,))
+  sh = np.broadcast_to(np.asarray(shift, np.float64), (B,))
+  obs = np.broadcast_to(np.asarray(observed, np.float64), (B, T))
+  fi = np.asarray(first, np.int64)
+  fi = np.broadcast_to(fi, (B,) + fi.shape[-1:])
+  co = np.broadcast_to(np.asarray(count, np.int64), fi.shape)
+  W = fi.shape[1]
+  out = np.zeros((B, W, 2, N), np.float64)
+  for b in range(B):
+    for w in range(W):
+      f, c = int(fi[b, w]), int(co[b, w])
+      if f < 0 or c < 0 or f + c > T:
+        raise ValueError(f"window {w} of series {b}: steps {f} .. {f + c - 1} leave [0, {T})")
+      pred_sum, point_sum = np.zeros(N, np.float64), np.zeros(N, np.float64)
+      for t in range(f, f + c):
+        v = tr[b, :, t].astype(np.float64) * sc[b] + sh[b]
+        pred_sum = pred_sum + v
+        point = -(v - obs[b, t])
+        point_sum = np.where(point == point, point_sum + point, point_sum)
+      out[b, w, 0], out[b, w, 1] = pred_sum, point_sum
+  return out
+
+
+def _windows_call(fn, handle, B: int, N: int, T: int, scale, shift, observed, first, count, ranks,
+                  want_draws: bool) -> Dict[str, np.ndarray]:
+  """The call every session's `summarize_windows` makes."""
+  sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (B,)))
+  sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.float64), (B,)))
+  obs = np.ascontiguousarray(np.broadcast_to(np.asarray(observed, np.float64), (B, T)))
+  fi = np.asarray(first, np.int32)
+  if fi.ndim not in (1, 2) or (fi.ndim == 2 and fi.shape[0] != B):
+    raise ValueError(f"`first` must be [W] or [{B}, W], got shape {fi.shape}")
+  fi = np.ascontiguousarray(np.broadcast_to(fi, (B, fi.shape[-1])))
+  co = np.asarray(count, np.int32)
+  if co.shape not in (fi.shape, fi.shape[1:]):
+    raise ValueError(f"`count` must have the shape of `first`, got {co.shape}")
+  co = np.ascontiguousarray(np.broadcast_to(co, fi.shape))
+  rk = np.ascontiguousarray(ranks, dtype=np.int32).reshape(-1)
+  W = fi.shape[1]
+  pd_ = np.empty((B, W, 2, N), np.float64) if want_draws else None
+  do = np.empty((B, W, 2, rk.size), np.float64)
+  _check(fn(handle, sc.ctypes.data, sh.ctypes.data, obs.ctypes.data, W, fi.ctypes.data, co.ctypes.data,
+            int(rk.size), rk.ctypes.data, _ptr(pd_), do.ctypes.data))
+  out = dict(per_draw_order=do)
+  if want_draws:
+    out["per_draw"] = pd_
   return out
 
 
@@ -690,6 +757,23 @@ class Session:
               *[_ptr(arrs.get(k)) for k in PREDICTION_OUTPUTS]))
     return arrs
 
+  def summarize_windows(self, scale, shift, observed, first, count, ranks,
+                        want_draws=True) -> Dict[str, np.ndarray]:
+    """On-device per-draw totals over sub-windows of the steps, and their order statistics
+    (ci_session_summarize_windows): one streaming pass over the windows' own columns of the resident
+    float32 trajectories.  scale, shift: scalars or [B]; observed: [T] or [B, T]; first, count: [W]
+    (the same windows for every series) or [B, W], in steps of the session; ranks: 1 to 8 order
+    statistics.  Returns per_draw [B, W, 2, N] (the window's sum of the predicted values, and of the
+    point effects with the unobserved steps skipped; left out unless want_draws) and per_draw_order
+    [B, W, 2, R]; the series axis is kept.  `window_totals_host` is the same loop on the host; a
+    window equal to the post-period gives `summarize`'s per_draw and per_draw_order bit for bit."""
+    fn = getattr(self._lib, "ci_session_summarize_windows", None)
+    if fn is None:
+      raise NativeError("the loaded library has no ci_session_summarize_windows: rebuild it")
+    pb = self.pb
+    return _windows_call(fn, self._h, pb.num_series, pb.num_chains * pb.num_results, pb.T, scale, shift,
+                         observed, first, count, ranks, want_draws)
+
   def pool_trajectories(self, scale, shift, groups, init=None) -> np.ndarray:
     """Weighted sums over groups of series of the resident predictive trajectories, draw by draw
     (ci_session_pool_trajectories): out[g] = init[g] + sum over the members b of group g, ascending,
@@ -939,6 +1023,17 @@ class BatchLogLikSession(LogLikSession):
                                                  rk.ctypes.data, vo.ctypes.data, co.ctypes.data,
                                                  pd_.ctypes.data, do.ctypes.data))
     return dict(value_order=vo, cum_order=co, per_draw=pd_, per_draw_order=do)
+
+  def summarize_windows(self, scale, shift, observed, first, count, ranks,
+                        want_draws=True) -> Dict[str, np.ndarray]:
+    """`Session.summarize_windows` of the fit's resident predictive trajectories
+    (ci_ll_session_summarize_windows): per_draw [B, W, 2, N], per_draw_order [B, W, 2, R], N = C x S."""
+    fn = getattr(self._lib, "ci_ll_session_summarize_windows", None)
+    if fn is None:
+      raise NativeError("the loaded library has no ci_ll_session_summarize_windows: rebuild it")
+    Cn, S = self._hmc_shape
+    return _windows_call(fn, self._h, self.B, Cn * S, self.T, scale, shift, observed, first, count,
+                         ranks, want_draws)
 
 
 def test_rng(seed, chain, it, site, sub, n, alpha, device=0):

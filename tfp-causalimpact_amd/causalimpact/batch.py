@@ -206,6 +206,133 @@ def summary_table(names, alpha, ranks, dsum, *, n_win, n_obs, obs_mean, obs_sum,
   return pd.DataFrame(data, index=index)
 
 
+# ------------------------------------------------------------------------------------------
+# Effect windows: the summary over sub-windows of the post-period
+# ------------------------------------------------------------------------------------------
+def calendar_windows(index: pd.DatetimeIndex, post_period, freq) -> Dict[str, Tuple[Any, Any]]:
+  """`effect_windows` of a fit on a DatetimeIndex: one window per pandas period of `freq` ("W", "M",
+  ...) that holds a row of the post-period, clipped to the post-period and named by the period's
+  label.  post_period as the fit takes it (labels, aligned to the index)."""
+  index = pd.DatetimeIndex(index)
+  start, end = indices._align(                                  # pylint: disable=protected-access
+      tuple(indices._to_index_value(v, index) for v in post_period), index)   # pylint: disable=protected-access
+  out = {}
+  for period in pd.period_range(start, end, freq=freq):
+    rows = index[(index >= max(period.start_time, start)) & (index <= min(period.end_time, end))]
+    if len(rows):
+      out[str(period)] = (rows[0], rows[-1])
+  return out
+
+
+def event_windows(width: int, num: int) -> Dict[str, Tuple[int, int]]:
+  """`effect_windows` of a panel: `num` consecutive windows of `width` rows in event time, named
+  "0..6", "7..13", ... (both ends inclusive)."""
+  width, num = int(width), int(num)
+  if width < 1 or num < 1:
+    raise ValueError(f"`width` and `num` must be >= 1, got {width} and {num}")
+  return {f"{k * width}..{(k + 1) * width - 1}": (k * width, (k + 1) * width - 1) for k in range(num)}
+
+
+@dataclasses.dataclass
+class WindowPlan:
+  """The resolved `effect_windows` of a batch or panel: the window names and, per series and
+  window, the model steps first .. first + count - 1 (count 0: the series does not cover it)."""
+  names: List[Any]
+  first: np.ndarray           # [B, W] int32
+  count: np.ndarray           # [B, W] int32
+  # batches: the `lib.EffectWindow`s every series shares; panels: the (tau_first, tau_last) pairs
+  windows: List[Any]
+
+
+def batch_windows(effect_windows, prep: PreparedBatch) -> WindowPlan:
+  """The `WindowPlan` of a prepared batch: labels on the shared index, as `fit_causalimpact` reads
+  them (`lib.resolve_windows`), the same steps for every series."""
+  wins = lib.resolve_windows(effect_windows, prep.index, prep.index[prep.model_rows], prep.post_period)
+  B = prep.y.shape[0]
+  return WindowPlan([w.name for w in wins],
+                    np.tile(np.array([w.first for w in wins], np.int32), (B, 1)),
+                    np.tile(np.array([w.count for w in wins], np.int32), (B, 1)), wins)
+
+
+def _tau_windows(effect_windows):
+  """[(name, tau_first, tau_last)] of a panel's `effect_windows`; ValueError with the window named."""
+  out = []
+  for name, bounds in lib._window_items(effect_windows):       # pylint: disable=protected-access
+    if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in bounds):
+      raise ValueError(f"effect window {name!r}: the bounds of a panel's window are integers in event "
+                       f"time, got {tuple(bounds)!r}")
+    lo, hi = int(bounds[0]), int(bounds[1])
+    if not 0 <= lo <= hi:
+      raise ValueError(f"effect window {name!r}: need 0 <= tau_first <= tau_last, got ({lo}, {hi})")
+    out.append((name, lo, hi))
+  return out
+
+
+def panel_windows(effect_windows, prep: PreparedPanel) -> WindowPlan:
+  """The `WindowPlan` of a prepared panel: windows (tau_first, tau_last) in event time, the model
+  rows since a series' own treatment start (`event_axes`).  Series b covers a window that ends inside
+  its post-period window; it then owns the steps start_b + tau_first .. start_b + tau_last, else
+  count 0.  ValueError naming the window that no series covers."""
+  taus = _tau_windows(effect_windows)
+  B = len(prep.lengths)
+  first, count = np.zeros((B, len(taus)), np.int32), np.zeros((B, len(taus)), np.int32)
+  for b in range(B):
+    after = np.flatnonzero(prep.flags[b, :prep.lengths[b]] & 1)
+    width = int(np.sum((prep.flags[b] & 2) != 0))
+    for w, (_, lo, hi) in enumerate(taus):
+      if after.size and hi < width:
+        first[b, w], count[b, w] = after[0] + lo, hi - lo + 1
+  for w, (name, lo, hi) in enumerate(taus):
+    if not count[:, w].any():
+      raise ValueError(f"effect window {name!r}: no series has a post-period of {hi + 1} rows to cover "
+                       f"({lo}, {hi})")
+  return WindowPlan([t[0] for t in taus], first, count, [(lo, hi) for _, lo, hi in taus])
+
+
+def window_table(names, alpha, ranks, plan: WindowPlan, wsum: Dict[str, np.ndarray],
+                 observed: np.ndarray, post_mean: np.ndarray, classes=None) -> pd.DataFrame:
+  """`window_summary` of B series: `summary_table` fed with every (series, window)'s own statistics
+  -- n_win, n_obs, obs_mean, obs_sum from observed [B, T], avg_pred and cum_pred from post_mean [B, T]
+  (data scale), and the window totals wsum ("per_draw" [B, W, 2, N], optionally "per_draw_order"
+  [B, W, 2, R]).  Indexed by (series, window, average|cumulative); NaN rows where count is 0.
+  classes: [(steps, positions)], the series whose `summary` rows are reduced together over arrays of
+  `steps` columns (default: all B over T; a panel: `panel_window_stats`' groups).  Within a class the
+  series that share a window's steps are reduced together with the very expressions of
+  `_build_summary` -- numpy's summation order depends on the shape of what it reduces -- so that a
+  window equal to the post-period gets the `summary` rows bit for bit."""
+  B, W = plan.first.shape
+  if classes is None:
+    classes = [(observed.shape[1], list(range(B)))]
+  stats = {k: np.zeros((B, W)) for k in ("obs_mean", "obs_sum", "avg_pred", "cum_pred")}
+  stats["n_obs"] = np.zeros((B, W), np.int64)
+  with np.errstate(invalid="ignore", divide="ignore"):
+    for Tg, members in classes:
+      for w in range(W):
+        groups: Dict[Any, List[int]] = {}
+        for b in members:
+          if plan.count[b, w] > 0:
+            groups.setdefault((int(plan.first[b, w]), int(plan.count[b, w])), []).append(b)
+        for (f, c), sel in groups.items():
+          win = np.zeros(Tg, bool)
+          win[f:f + c] = True
+          obs_w = np.ascontiguousarray(observed[sel][:, :Tg])[:, win]
+          pm_w = np.ascontiguousarray(post_mean[sel][:, :Tg])[:, win]
+          stats["n_obs"][sel, w] = np.sum(~np.isnan(obs_w), axis=1)
+          stats["obs_mean"][sel, w], stats["obs_sum"][sel, w] = np.nanmean(obs_w, axis=1), np.nansum(obs_w, axis=1)
+          stats["avg_pred"][sel, w], stats["cum_pred"][sel, w] = pm_w.mean(axis=1), pm_w.sum(axis=1)
+  covered = np.flatnonzero(plan.count.reshape(-1) > 0)
+  pick = (lambda a: a) if covered.size == B * W else (lambda a: a[covered])   # (a batch: views, no copy)
+  flat = {k: pick(v.reshape((B * W,) + v.shape[2:])) for k, v in wsum.items()}
+  table = summary_table(covered, alpha, ranks, flat, n_win=pick(plan.count.reshape(-1)).astype(np.int64),
+                        **{k: pick(v.reshape(-1)) for k, v in stats.items()})
+  rows = (2 * covered[:, None] + np.arange(2)[None, :]).reshape(-1)
+  full = np.full((2 * B * W, table.shape[1]), np.nan)
+  full[rows] = table.to_numpy(dtype=np.float64)
+  index = pd.MultiIndex.from_product([list(names), list(plan.names), ["average", "cumulative"]],
+                                     names=["series", "window", None])
+  return pd.DataFrame(full, index=index, columns=table.columns)
+
+
 # What a launch returns has the series axis first and, with these exceptions, time last: the
 # fetched draws of the scalars the diagnostics rank [B, chains, draws], the device summary's window
 # totals per draw, and the component-summary arrays whose last axis is the design columns.
@@ -250,6 +377,18 @@ class CausalImpactBatchAnalysis:
     # outcome} and the 15-column table indexed by (aggregate, average|cumulative); None otherwise
     self.aggregates: Optional[Dict[Any, lib.CausalImpactAnalysis]] = None
     self.aggregate_summary: Optional[pd.DataFrame] = None
+    # `effect_windows=`: the 15 summary columns of every sub-window of the post-period, indexed by
+    # (series, window, average|cumulative) -- `analysis[b].window_summary` is the slice of series b --
+    # and, with aggregates, the same for every pooled group (aggregate, window, average|cumulative)
+    self.window_summary: Optional[pd.DataFrame] = None
+    self.aggregate_window_summary: Optional[pd.DataFrame] = None
+
+  def _window_slice(self, b: int) -> Optional[pd.DataFrame]:
+    """The rows of series b of `window_summary`, indexed by (window, average|cumulative)."""
+    if self.window_summary is None:
+      return None
+    per = len(self.window_summary) // len(self)
+    return self.window_summary.iloc[b * per:(b + 1) * per].droplevel("series")
 
   def diagnostics_of(self, b: int):
     """{"split_rhat" | "ess_bulk" | "ess_tail": {key: value}} of series b (None for one chain)."""
@@ -310,7 +449,8 @@ class CausalImpactBatchAnalysis:
           self._means[b, :Tb], dsum, rq, ci_data, self.alpha)
       self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b),
                                                 *self._component_frames(b, ci_data, Tb),
-                                                *self._prediction_frames(b, ci_data, Tb))
+                                                *self._prediction_frames(b, ci_data, Tb),
+                                                self._window_slice(b))
     return self._cache[b]
 
   def _prediction_inputs(self, b: int, num_steps: int):
@@ -369,6 +509,8 @@ class PerSeriesBatchAnalysis(CausalImpactBatchAnalysis):
     self.summary = pd.concat([a.summary for a in analyses], keys=self._names, names=["series", None])
     self.aggregates = None
     self.aggregate_summary = None
+    self.window_summary = None
+    self.aggregate_window_summary = None
 
   @property
   def fit_quality(self) -> Optional[pd.DataFrame]:
@@ -905,28 +1047,44 @@ def scaler_stats(outcome_pre: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
             np.array([np.nanstd(r, axis=0, ddof=1) for r in rows]))
 
 
-def _frame_analyses(rows, alpha: float, ranks, device: int = 0):
-  """(`aggregates`, `aggregate_summary`) from one row per group: (name, the `CausalImpactData` of the
+def _frame_analyses(rows, alpha: float, ranks, device: int = 0, windows=None):
+  """(`aggregates`, `aggregate_summary`, `aggregate_window_summary`) from one row per group: (name, the `CausalImpactData` of the
   pooled outcome -- on the data scale already: standardize_data=False -- the pooled observed outcome
   and the window flags over the model steps, the pooled posterior mean, the pooled draws [N, steps]
   float64).  The order statistics and per-draw totals of the pooled draws come from
   `_native.summarize_draws` (ci_summarize_draws_f64: scale 1, shift 0), and the reference's frames are
-  built by `_compute_impact_device`."""
+  built by `_compute_impact_device`.  windows (`effect_windows`): (window names, per group the
+  `lib.EffectWindow`s its axis covers); their totals come from `_native.window_totals_host` on the
+  same pooled draws (scale 1, shift 0), and the table has NaN rows for a window a group does not
+  cover.  The third result is None without them."""
   analyses = {}
-  for name, ci_data, observed, flags, mean, draws in rows:
+  for g, (name, ci_data, observed, flags, mean, draws) in enumerate(rows):
     dsum = _native.summarize_draws(draws, 1.0, 0.0, observed, flags, ranks, device=device)
     rq = lib._device_summary_request(ci_data, alpha)             # pylint: disable=protected-access
     rq.update(observed=observed, flags=flags, ranks=ranks)
-    series, summary = lib._compute_impact_device(mean, dsum, rq, ci_data, alpha)   # pylint: disable=protected-access
-    analyses[name] = lib.CausalImpactAnalysis(series, summary, None)
+    wins = () if windows is None else windows[1][g]
+    if wins:
+      rq["window_totals"] = _native.window_totals_host(
+          draws[None], 1.0, 0.0, observed, [w.first for w in wins], [w.count for w in wins])[0]
+    series, summary, window_summary = lib._compute_impact_device(   # pylint: disable=protected-access
+        mean, dsum, rq, ci_data, alpha, windows=wins)
+    analyses[name] = lib.CausalImpactAnalysis(series, summary, None, window_summary=window_summary)
   table = pd.concat([a.summary for a in analyses.values()], keys=list(analyses),
                     names=["aggregate", None])
-  return analyses, table
+  window_table_ = None
+  if windows is not None:
+    full = pd.MultiIndex.from_product([list(windows[0]), ["average", "cumulative"]], names=["window", None])
+    blank = pd.DataFrame(np.nan, index=full, columns=table.columns)
+    window_table_ = pd.concat(
+        [blank if a.window_summary is None else a.window_summary.reindex(full) for a in analyses.values()],
+        keys=list(analyses), names=["aggregate", "window", None])
+  return analyses, table, window_table_
 
 
 def _aggregate_analyses(agg_names, csr, pooled: np.ndarray, means: np.ndarray, prep: PreparedBatch,
-                        outcome_name, alpha: float, ranks, device: int = 0):
-  """(`aggregates`, `aggregate_summary`) of a batch from the pooled draws [G, N, T] (float64, data
+                        outcome_name, alpha: float, ranks, device: int = 0,
+                        windows: Optional[WindowPlan] = None):
+  """(`aggregates`, `aggregate_summary`, `aggregate_window_summary`) of a batch from the pooled draws [G, N, T] (float64, data
   scale) and the series' posterior means [B, T] on the data scale.  Per group: the observed outcome
   and the posterior mean are pooled with the same weights (`pool_weighted`; the outcome is NaN
   wherever a member is), the flags are the batch's, and the frames are built by `_frame_analyses` over
@@ -942,7 +1100,9 @@ def _aggregate_analyses(agg_names, csr, pooled: np.ndarray, means: np.ndarray, p
     except ValueError as e:
       raise ValueError(f"aggregate {name!r}: {e}") from e
     rows.append((name, ci_data, observed[g], prep.flags, mean[g], pooled[g]))
-  return _frame_analyses(rows, alpha, ranks, device)
+  # (the groups share the batch's calendar, hence its windows)
+  return _frame_analyses(rows, alpha, ranks, device,
+                         None if windows is None else (windows.names, [windows.windows] * len(rows)))
 
 
 # ------------------------------------------------------------------------------------------
@@ -1061,16 +1221,25 @@ def event_plan(agg_names, csr, prep: PreparedPanel, outcome_name) -> EventPlan:
 
 
 def _event_aggregate_analyses(plan: EventPlan, pooled: np.ndarray, means: Sequence[np.ndarray],
-                              alpha: float, ranks, device: int = 0):
-  """(`aggregates`, `aggregate_summary`) of a panel from the pooled draws [G, N, stride] (float64,
+                              alpha: float, ranks, device: int = 0,
+                              windows: Optional[WindowPlan] = None):
+  """(`aggregates`, `aggregate_summary`, `aggregate_window_summary`) of a panel from the pooled draws [G, N, stride] (float64,
   data scale; group g owns its first width_g columns) and the series' posterior means over their own
   steps on the data scale.  Per group the posterior mean is pooled over the members' windows like the
   outcome (`pool_event_weighted`, the member order of the draws), the flags are the axis', and the
   frames are built by `_frame_analyses` on the group's `event_time` index."""
   mean = pool_event_weighted(means, plan.csr, plan.axes)
+  wins = None
+  if windows is not None:
+    # on the group's own axis: tau is a value of its `event_time` index, step L + tau; a window the
+    # axis' post-period (0 .. Hwin - 1) does not cover is left out (NaN rows)
+    wins = (windows.names,
+            [[lib.EffectWindow(name, lo, hi, axis.L + lo, hi - lo + 1)
+              for name, (lo, hi) in zip(windows.names, windows.windows) if hi < axis.Hwin]
+             for axis in plan.axes])
   return _frame_analyses(
       [(name, plan.data[g], plan.observed[g], axis.flags, mean[g], pooled[g][:, :axis.width])
-       for g, (name, axis) in enumerate(zip(plan.names, plan.axes))], alpha, ranks, device)
+       for g, (name, axis) in enumerate(zip(plan.names, plan.axes))], alpha, ranks, device, wins)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1109,7 +1278,8 @@ def _frames_outcome_first(data, data_options):
 
 def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_options, model_options,
                     inference_options, shared_streams, aggregates=None,
-                    event_aggregates: Optional[EventPlan] = None) -> PerSeriesBatchAnalysis:
+                    event_aggregates: Optional[EventPlan] = None,
+                    windows: Optional[WindowPlan] = None, series_windows=None) -> PerSeriesBatchAnalysis:
   """`fit_causalimpact` on every series in turn: the routes the one-launch path does not have.
   float64 compute (csrc/ci_gibbs64.h) and raw-scale outcomes (their per-series internal
   conditioning, causalimpact_lib._internal_conditioning) exist on the single-series path, and so do
@@ -1126,7 +1296,12 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
 
   event_aggregates (panels only): the `EventPlan`.  The same in event time (`HostPool` with the
   axes): every series is a class of its own on this route, so (class key, position) order is position
-  order."""
+  order.
+
+  windows, series_windows (`effect_windows`): the `WindowPlan` and, per series, the `effect_windows`
+  its own `fit_causalimpact` takes (a panel: the windows it covers, as positions into its index; None
+  for a series that covers none).  `window_summary` stacks the fits' own tables, NaN rows for the
+  windows a series does not cover."""
   opts = dataclasses.replace(data_options, outcome_column=outcome_column)
   base_seed = lib._sanitize_seed(seed)   # pylint: disable=protected-access
   analyses = []
@@ -1142,19 +1317,29 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
       extra = dict(_trajectory_sink=lambda *a, b=b: host_pool.add(b, *a))
     one = lib.fit_causalimpact(frame, periods[b][0], periods[b][1], alpha=alpha, seed=seed_b,
                                data_options=opts, model_options=model_options,
-                               inference_options=inference_options, **extra)
-    analyses.append(dataclasses.replace(one, posterior_samples=None))   # (draws are not kept)
+                               inference_options=inference_options,
+                               effect_windows=None if series_windows is None else series_windows[b],
+                               **extra)
+    analyses.append(dataclasses.replace(one, posterior_samples=None,   # (draws are not kept)
+                                        window_summary=one.window_summary))
   res = PerSeriesBatchAnalysis(names, alpha, analyses)
+  if windows is not None:
+    full = pd.MultiIndex.from_product([windows.names, ["average", "cumulative"]], names=["window", None])
+    blank = pd.DataFrame(np.nan, index=full, columns=analyses[0].summary.columns)
+    for a in analyses:
+      a.window_summary = blank if a.window_summary is None else a.window_summary.reindex(full)
+    res.window_summary = pd.concat([a.window_summary for a in analyses], keys=list(names),
+                                   names=["series", "window", None])
   if host_pool is not None:
     ranks = lib._summary_ranks(host_pool.pooled.shape[1], (alpha / 2.0, 1.0 - alpha / 2.0))   # pylint: disable=protected-access
     devs = list(inference_options.devices) if inference_options.devices else [0]
     if event_aggregates is not None:
-      res.aggregates, res.aggregate_summary = _event_aggregate_analyses(
-          event_aggregates, host_pool.pooled, host_pool.means, alpha, ranks, devs[0])
+      res.aggregates, res.aggregate_summary, res.aggregate_window_summary = _event_aggregate_analyses(
+          event_aggregates, host_pool.pooled, host_pool.means, alpha, ranks, devs[0], windows)
     else:
-      res.aggregates, res.aggregate_summary = _aggregate_analyses(
+      res.aggregates, res.aggregate_summary, res.aggregate_window_summary = _aggregate_analyses(
           agg_names, csr, host_pool.pooled, np.stack(host_pool.means), prep, outcome_column, alpha,
-          ranks, devs[0])
+          ranks, devs[0], windows)
   return res
 
 
@@ -1182,6 +1367,8 @@ class _Fit:
   # come from the vectorised pass and may differ from them in the last bit)
   own_scale: Optional[np.ndarray] = None
   own_shift: Optional[np.ndarray] = None
+  # `effect_windows=` only: the resolved windows, every series' own first / count [B, W]
+  windows: Optional[WindowPlan] = None
 
 
 def _sampler_outcome(prep, data_options) -> np.ndarray:
@@ -1190,7 +1377,7 @@ def _sampler_outcome(prep, data_options) -> np.ndarray:
 
 
 def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_options,
-             shared_streams) -> _Fit:
+             shared_streams, windows: Optional[WindowPlan] = None) -> _Fit:
   """The `_Fit` of a prepared batch or panel: y = `_sampler_outcome(prep)`, lengths [B], pre_sd [B]
   the sd of every series' own pre-period outcome."""
   own_shift = own_scale = None
@@ -1214,7 +1401,7 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
               ranks=lib._summary_ranks(num_draws, (alpha / 2.0, 1.0 - alpha / 2.0)),   # pylint: disable=protected-access
               seed=lib._sanitize_seed(seed), shared_streams=shared_streams,   # pylint: disable=protected-access
               model_options=model_options, inference_options=inference_options,
-              own_scale=own_scale, own_shift=own_shift)
+              own_scale=own_scale, own_shift=own_shift, windows=windows)
 
 
 def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None):
@@ -1228,10 +1415,11 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
                        series starts at its own step 0) and the stride rounded up to a multiple of 4
                        (every row 16-byte aligned), the padding as in `PreparedPanel`: y NaN, mask
                        True, design 0, observed NaN, flags 0.
-  Returns (out, dsum, csum, psum): `fetch` of posterior_means [n, C, T] and `_DRAW_SCALARS` [n, C, S],
+  Returns (out, dsum, csum, psum, wsum): `fetch` of posterior_means [n, C, T] and `_DRAW_SCALARS` [n, C, S],
   `summarize`, `summarize_components` (None unless InferenceOptions.components) and the prediction
   summary (None unless InferenceOptions.prediction_errors): `summarize_predictions` for the block
-  lists the device takes, `_host_predictions` from the fetched parameter draws for the others.  Every
+  lists the device takes, `_host_predictions` from the fetched parameter draws for the others;
+  wsum `summarize_windows` with every series' own windows (None unless `effect_windows`).  Every
   array keeps the series axis, and T is the longest series of the launch on every route.
   chain (aggregates of a batch, event-time aggregates of a panel): the launch's pool step runs after
   `summarize`, the session still open."""
@@ -1278,6 +1466,10 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
       psum = sess.summarize_predictions(fit.own_scale[ids], fit.own_shift[ids], fit.ranks)
     elif io.prediction_errors:
       psum = _host_predictions(fit, ids, T, sess.fetch(list(_PARAMETER_DRAWS)), season_change)
+    wsum = None
+    if fit.windows is not None:
+      wsum = sess.summarize_windows(scale, shift, observed, fit.windows.first[ids],
+                                    fit.windows.count[ids], fit.ranks)
     if chain is not None:
       chain.step(launch, chain.session_pool(sess, scale, shift))
   finally:
@@ -1286,7 +1478,7 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
     out, dsum = _cut(out, T, _DRAW_SCALARS), _cut(dsum, T, _PER_DRAW)
     csum = None if csum is None else _cut(csum, T, _PER_COLUMN)
     psum = None if psum is None else _cut(psum, T, _PER_DRAW_LOGLIK)
-  return out, dsum, csum, psum
+  return out, dsum, csum, psum, wsum
 
 
 def _host_predictions(fit: _Fit, ids, num_steps: int, draws: Dict[str, np.ndarray],
@@ -1323,28 +1515,36 @@ def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None):
   the latent paths, the predictive trajectories and their summary on the device): consecutive
   positions of a batch, series b keyed by positions[0] + b.  It keeps no latent draws, hence no
   component summary; the prediction summary is `_host_predictions` from the parameter draws, which
-  it fetches for that."""
+  it fetches for that; the window totals are `BatchLogLikSession.summarize_windows`, taken while the
+  fit is resident."""
   from causalimpact import _hmc  # pylint: disable=import-outside-toplevel
   dev, _, ids = launch
   ids = np.asarray(ids, dtype=np.int64)
   mo, io = fit.model_options, fit.inference_options
   scale, shift = fit.scale[ids], fit.shift[ids]
-  pool = None
-  if chain is not None:
-    pool = lambda sess: chain.step(launch, chain.session_pool(sess, scale, shift))   # pylint: disable=unnecessary-lambda-assignment
+  wsum = {}
+
+  def after_summary(sess):       # (the session still open: the window totals, then the pool step)
+    if fit.windows is not None:
+      wsum.update(sess.summarize_windows(scale, shift, fit.observed[ids], fit.windows.first[ids],
+                                         fit.windows.count[ids], fit.ranks))
+    if chain is not None:
+      chain.step(launch, chain.session_pool(sess, scale, shift))
+
   res = _hmc.fit_hmc_batch(
       fit.y[ids], fit.mask[ids], None if fit.design is None else fit.design[ids],
       [fit.params[b] for b in ids], has_slope=mo.local_linear_trend, num_results=io.num_results,
       num_warmup=io.num_warmup_steps, num_chains=io.num_chains, seed=fit.seed, device=dev,
       series_offset=int(ids[0]), shared_streams=fit.shared_streams, prior=io.hmc_prior,
       summary=dict(scale=scale, shift=shift, observed=fit.observed[ids],
-                   flags=fit.flags, ranks=fit.ranks), after_summary=pool,
+                   flags=fit.flags, ranks=fit.ranks),
+      after_summary=after_summary if chain is not None or fit.windows is not None else None,
       also_fetch=("slope_scale", "weights") if io.prediction_errors else ())
   psum = None
   if io.prediction_errors:
     draws = {k: res[k] for k in _PARAMETER_DRAWS if k in res}
     psum = _host_predictions(fit, ids, fit.y.shape[1], draws, np.zeros((0, fit.y.shape[1]), np.uint8))
-  return {k: res[k] for k in ("posterior_means", *_DRAW_SCALARS)}, res["summary"], None, psum
+  return {k: res[k] for k in ("posterior_means", *_DRAW_SCALARS)}, res["summary"], None, psum, wsum or None
 
 
 def _scatter(parts, num_series: int, num_steps: int, whole, fill) -> Dict[str, np.ndarray]:
@@ -1374,7 +1574,9 @@ def _assemble(launches, run, num_series: int, num_steps: int):
     csum              the component summary {name: [B, ...]}, NaN beyond a series' length (the
                       `_PER_COLUMN` arrays have no time axis), or None when `run` returns none;
     psum              (only when `run` returns four values) the prediction summary {name: [B, ...]}
-                      likewise (loglik has no time axis), or None.
+                      likewise (loglik has no time axis), or None;
+    wsum              (only when `run` returns five values) the window totals {name: [B, W, ...]} (no
+                      time axis), or None.
   One launch that holds all B series in order at full stride is the result as it stands: its blocks
   (512 series: 24 MB of summary in pinned memory) are not copied a second time."""
   results = lib.map_by_device(run, launches)
@@ -1389,7 +1591,7 @@ def _assemble(launches, run, num_series: int, num_steps: int):
       return _scatter(parts, num_series, num_steps, whole, fill)
     fetched, dsum = gather(0, _DRAW_SCALARS, 0), gather(1, _PER_DRAW, np.nan)
     optional = [None if one is None else gather(2 + i, whole, np.nan)
-                for i, (one, whole) in enumerate(zip(optional, (_PER_COLUMN, _PER_DRAW_LOGLIK)))]
+                for i, (one, whole) in enumerate(zip(optional, (_PER_COLUMN, _PER_DRAW_LOGLIK, _PER_DRAW)))]
   means = fetched.pop("means")
   diag_draws = fetched if fetched[_DRAW_SCALARS[0]].shape[1] > 1 else None
   return (means, dsum, diag_draws, *optional)
@@ -1403,7 +1605,7 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
                            index: Optional[pd.Index] = None,
                            names: Optional[Sequence[Any]] = None,
                            shared_streams: bool = False,
-                           aggregates=None) -> CausalImpactBatchAnalysis:
+                           aggregates=None, effect_windows=None) -> CausalImpactBatchAnalysis:
   """`fit_causalimpact` for B series at once.
 
   data: a sequence of DataFrames with identical index and column layout (outcome first, or
@@ -1463,6 +1665,16 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   unknown series name, a member listed twice, a weight that is not finite or a group without a
   member of non-zero weight.  Batches fitted series by series (float64, raw scale, most HMC) add up
   the same sum in numpy from every fit's trajectories.
+
+  effect_windows: {name: (start, end)}, sub-windows of the post-period as labels on the shared index
+  (both ends inclusive, read as `post_period` is): how the effect unfolds.  The result then has
+  `window_summary`, the 15 summary columns indexed by (series, window, average|cumulative) --
+  `result[b].window_summary` is the slice of series b -- from every draw's totals over every window,
+  summed where the trajectories lie (csrc/ci_windows.h: one pass over the windows' own columns, no
+  draws downloaded; `_native.window_totals_host` on the routes fitted series by series), and with
+  `aggregates` also `aggregate_window_summary` (aggregate, window, average|cumulative) from the
+  pooled draws.  ValueError before any fit, naming the window, for one that leaves the post-period or
+  holds no row.  None: both attributes are None and nothing runs.
   """
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
@@ -1495,16 +1707,22 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
         P=0 if prep.design is None else prep.design.shape[2],
         hmc_init=inference_options.hmc_init) == "per_series")
   if per_series:
-    if agg is not None:   # (the shared calendar: pooled outcome, window flags)
-      agg = (*agg, prepare_batch(values, index, pre_period, post_period, data_options.standardize_data))
+    shared = None
+    if agg is not None or effect_windows is not None:   # (the shared calendar: pooled outcome, window flags)
+      shared = prepare_batch(values, index, pre_period, post_period, data_options.standardize_data)
+    if agg is not None:
+      agg = (*agg, shared)
+    plan = None if effect_windows is None else batch_windows(effect_windows, shared)
     return _fit_per_series((pd.DataFrame(values[b], index=index, columns=columns) for b in range(B)),
                            [(pre_period, post_period)] * B, names, columns[0], alpha, seed,
-                           data_options, model_options, inference_options, shared_streams, agg)
+                           data_options, model_options, inference_options, shared_streams, agg,
+                           windows=plan, series_windows=None if plan is None else [effect_windows] * B)
+  plan = None if effect_windows is None else batch_windows(effect_windows, prep)
   y = _sampler_outcome(prep, data_options)
   with np.errstate(invalid="ignore"):
     pre_sd = np.nanstd(y[:, :prep.num_pre], axis=1, ddof=1)
   fit = _new_fit(prep, y, np.full(B, T), pre_sd, alpha, seed, model_options, inference_options,
-                 shared_streams)
+                 shared_streams, plan)
   # a batch is the panel of one group of equal lengths: consecutive positions on every device
   launches = panel_launches(dict(route="equal_length", groups=[(T, list(range(B)))]),
                             inference_options.devices, shared_streams)
@@ -1520,17 +1738,34 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     run = lambda launch: _run_hmc_launch(launch, fit, chain)          # pylint: disable=unnecessary-lambda-assignment
   else:
     run = lambda launch: _run_launch(launch, "ordinary", fit, chain)   # pylint: disable=unnecessary-lambda-assignment
-  means, dsum, diag_draws, csum, psum = _assemble(
+  means, dsum, diag_draws, csum, psum, wsum = _assemble(
       launches, run if chain is None else chain.guarded(run), B, T)
   res = CausalImpactBatchAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
                                   csum, psum, _state_dim(model_options, inference_options))
+  if plan is not None:
+    res.window_summary = _window_summary(res, plan, wsum)
   if chain is not None:
     # the posterior means on the data scale with the statistics every series' own frame uses
     mu, sd = scaler_stats(prep.values[:, prep.model_rows[:prep.num_pre], 0])
-    res.aggregates, res.aggregate_summary = _aggregate_analyses(
+    res.aggregates, res.aggregate_summary, res.aggregate_window_summary = _aggregate_analyses(
         agg[0], agg[1], chain.result(), means.astype(np.float64) * sd[:, None] + mu[:, None], prep,
-        columns[0], alpha, fit.ranks, launches[0][0])
+        columns[0], alpha, fit.ranks, launches[0][0], plan)
   return res
+
+
+def _window_summary(res: CausalImpactBatchAnalysis, plan: WindowPlan, wsum) -> pd.DataFrame:
+  """`window_summary` of a one-launch batch or panel from the assembled window totals: the
+  observations and the data-scale posterior mean of `_build_summary`, every window's own steps."""
+  p = res._prep                                                  # pylint: disable=protected-access
+  post_mean = (res._means.astype(np.float64) * p.outcome_sd[:, None]   # pylint: disable=protected-access
+               + p.outcome_mean[:, None])
+  classes = None
+  if isinstance(p, PreparedPanel):       # (the groups `panel_window_stats` reduces together)
+    groups: Dict[Any, List[int]] = {}
+    for b, Tb in enumerate(p.lengths):
+      groups.setdefault((int(Tb), (p.flags[b, :Tb] & 2).tobytes()), []).append(b)
+    classes = [(Tg, sel) for (Tg, _), sel in groups.items()]
+  return window_table(res._names, res.alpha, res._ranks, plan, wsum, p.observed, post_mean, classes)   # pylint: disable=protected-access
 
 
 def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float = 0.05, seed=None,
@@ -1539,7 +1774,7 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
                            inference_options: Optional[lib.InferenceOptions] = None,
                            names: Optional[Sequence[Any]] = None,
                            shared_streams: bool = False,
-                           event_aggregates=None) -> CausalImpactBatchAnalysis:
+                           event_aggregates=None, effect_windows=None) -> CausalImpactBatchAnalysis:
   """`fit_causalimpact` for a PANEL: B series with the same columns (outcome first, or
   `DataOptions.outcome_column`; the same covariates), each with its own index, its own length and
   its own (pre_period, post_period) -- staggered roll-outs, units that enter the data on different
@@ -1595,7 +1830,16 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   with it (common random numbers make the Monte-Carlo errors of all series move together).
   ValueError, before any fit, for an unknown series name, a member listed twice, a weight that is not
   finite, a group without a member of non-zero weight, and a group whose common axis keeps fewer
-  than 3 pre-period steps."""
+  than 3 pre-period steps.
+
+  effect_windows: {name: (tau_first, tau_last)}, windows in EVENT TIME as above (integers, both ends
+  inclusive, 0 <= tau_first <= tau_last; `event_windows(7, 4)` gives four weeks of daily rows): the
+  rows tau_first .. tau_last since every series' own treatment start.  The result then has
+  `window_summary`, the 15 summary columns indexed by (series, window, average|cumulative), as in
+  `fit_causalimpact_batch`; a series whose post-period does not reach tau_last has NaN rows for that
+  window, and a window that no series covers is a ValueError before any fit.  With
+  `event_aggregates` also `aggregate_window_summary`, the windows taken on every group's own axis
+  (NaN rows where its post-period, the shortest of its members', does not cover them)."""
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
   frames, columns = _frames_outcome_first(data, data_options)
@@ -1616,14 +1860,24 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   if panel_route(float64=float64, standardize_data=data_options.standardize_data,
                  sampler=inference_options.sampler, num_seasonal_blocks=num_blocks,
                  P=len(columns), lengths=[len(f) for f in frames])["route"] == "per_series":
-    plan = None
-    if agg is not None:   # (the event axes come from the prepared panel; the fits prepare their own data)
-      plan = event_plan(*agg, prepare_panel([f[columns] for f in frames], periods,
-                                            data_options.standardize_data, names=names), columns[0])
+    plan = wplan = own = None
+    if agg is not None or effect_windows is not None:
+      # (the event axes and the windows come from the prepared panel; the fits prepare their own data)
+      shared = prepare_panel([f[columns] for f in frames], periods, data_options.standardize_data,
+                             names=names)
+      plan = None if agg is None else event_plan(*agg, shared, columns[0])
+    if effect_windows is not None:
+      wplan = panel_windows(effect_windows, shared)
+      # every fit reads integers as POSITIONS into its own index: the rows of its covered windows
+      own = [{name: (int(shared.model_rows[b][f]), int(shared.model_rows[b][f + c - 1]))
+              for name, f, c in zip(wplan.names, wplan.first[b], wplan.count[b]) if c > 0} or None
+             for b in range(B)]
     return _fit_per_series(frames, periods, names, columns[0], alpha, seed, data_options,
-                           model_options, inference_options, shared_streams, event_aggregates=plan)
+                           model_options, inference_options, shared_streams, event_aggregates=plan,
+                           windows=wplan, series_windows=own)
   prep = prepare_panel([f[columns] for f in frames], periods, names=names)
   plan = None if agg is None else event_plan(*agg, prep, columns[0])
+  wplan = None if effect_windows is None else panel_windows(effect_windows, prep)
   route = panel_route(float64=False, standardize_data=True, sampler="gibbs",
                       num_seasonal_blocks=num_blocks,
                       P=0 if prep.design is None else prep.design.shape[2], lengths=prep.lengths,
@@ -1632,21 +1886,23 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   with np.errstate(invalid="ignore"):
     pre_sd = [np.nanstd(y[b, :nb], ddof=1) for b, nb in enumerate(prep.num_pre)]
   fit = _new_fit(prep, y, prep.lengths, pre_sd, alpha, seed, model_options, inference_options,
-                 shared_streams)
+                 shared_streams, wplan)
   kind = "ordinary" if route["route"] == "equal_length" else route["route"]
   launches = panel_launches(route, inference_options.devices, shared_streams)
   chain = None if plan is None else _PoolChain(launches, plan.csr, plan.axes)
   run = lambda launch: _run_launch(launch, kind, fit, chain)   # pylint: disable=unnecessary-lambda-assignment
-  means, dsum, diag_draws, csum, psum = _assemble(
+  means, dsum, diag_draws, csum, psum, wsum = _assemble(
       launches, run if chain is None else chain.guarded(run), B, prep.y.shape[1])
   res = CausalImpactPanelAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
                                   csum, psum, _state_dim(model_options, inference_options))
+  if wplan is not None:
+    res.window_summary = _window_summary(res, wplan, wsum)
   if chain is not None:
     # the posterior means on the data scale with the statistics every series' own frame uses
     data_means = []
     for b, (Tb, nb) in enumerate(zip(prep.lengths, prep.num_pre)):
       mu, sd = scaler_stats(prep.raw[b][prep.model_rows[b][:nb], 0][None])
       data_means.append(means[b, :Tb].astype(np.float64) * sd[0] + mu[0])
-    res.aggregates, res.aggregate_summary = _event_aggregate_analyses(
-        plan, chain.result(), data_means, alpha, fit.ranks, launches[0][0])
+    res.aggregates, res.aggregate_summary, res.aggregate_window_summary = _event_aggregate_analyses(
+        plan, chain.result(), data_means, alpha, fit.ranks, launches[0][0], wplan)
   return res

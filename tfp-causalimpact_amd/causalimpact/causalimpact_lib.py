@@ -26,6 +26,7 @@ from causalimpact import _diagnostics
 from causalimpact import _model
 from causalimpact import _native
 from causalimpact import data as cid
+from causalimpact import indices
 from causalimpact import posterior_processing
 from causalimpact.indices import InputDateType
 from causalimpact.indices import OutputDateType
@@ -119,9 +120,13 @@ class CausalImpactAnalysis:
   # `asdict` of this class stay what they were.)
   prediction_errors: dataclasses.InitVar[Optional[pd.DataFrame]] = None
   fit_quality: dataclasses.InitVar[Optional[pd.Series]] = None
+  # `effect_windows=` only: the 15 columns of `summary` for every sub-window of the post-period,
+  # indexed by (window, average|cumulative).  (Init-only and kept as a plain attribute, as the two above.)
+  window_summary: dataclasses.InitVar[Optional[pd.DataFrame]] = None
 
-  def __post_init__(self, prediction_errors, fit_quality):
+  def __post_init__(self, prediction_errors, fit_quality, window_summary=None):
     self.prediction_errors, self.fit_quality = prediction_errors, fit_quality
+    self.window_summary = window_summary
 
 
 @dataclasses.dataclass
@@ -198,8 +203,19 @@ def fit_causalimpact(data: pd.DataFrame,
                      data_options: Optional[DataOptions] = None,
                      model_options: Optional[ModelOptions] = None,
                      inference_options: Optional[InferenceOptions] = None,
+                     effect_windows=None,
                      **kwargs) -> CausalImpactAnalysis:
-  """Fits the CausalImpact model and summarises the effect (reference :223-339)."""
+  """Fits the CausalImpact model and summarises the effect (reference :223-339).
+
+  effect_windows (extension): {name: (start, end)}, sub-windows of the post-period given as labels
+  on the index, both ends inclusive, parsed and aligned exactly as `post_period` is.  The result then
+  has `window_summary`: the 15 columns of `summary` for every window, indexed by (window,
+  average|cumulative) -- how the effect unfolds (week 1 against week 4, a promotion's second phase).
+  The bands, the relative effect and `p_value` of a window come from every draw's total over that
+  window (csrc/ci_windows.h on the GPU that holds the draws; `_native.window_totals_host` on the
+  routes that pool them on the host).  ValueError, before any fit and with the window named, for a
+  window that leaves the post-period or contains no model row.  None (the default): `window_summary`
+  is None and nothing runs."""
   data_options = data_options if data_options is not None else DataOptions()
   model_options = model_options if model_options is not None else ModelOptions()
   inference_options = inference_options if inference_options is not None else InferenceOptions()
@@ -224,6 +240,12 @@ def fit_causalimpact(data: pd.DataFrame,
     raise ValueError("`alpha` must be between 0 and 1.")
   request = (_device_summary_request(ci_data, alpha) if inference_options.summarize_on_device
              else None)
+  windows = None
+  if effect_windows is not None:
+    windows = resolve_windows(effect_windows, ci_data.data.index,
+                              posterior_processing.model_index(ci_data), ci_data.post_period)
+    if request is not None:
+      request["windows"] = windows
   comp_request = None
   if inference_options.components:
     base = request if request is not None else _device_summary_request(ci_data, alpha)
@@ -250,12 +272,12 @@ def fit_causalimpact(data: pd.DataFrame,
   # (draws pooled on the host -- several devices, float64, HMC -- were summarised inside
   #  _run_sampler, in the sampler's internal units)
   if device_summary is not None:
-    series, summary = _compute_impact_device(posterior_means, device_summary, request, ci_data,
-                                             alpha)
+    series, summary, window_summary = _compute_impact_device(
+        posterior_means, device_summary, request, ci_data, alpha, windows=windows or ())
   else:
-    series, summary = _compute_impact(posterior_means=posterior_means,
-                                      posterior_trajectories=posterior_trajectories,
-                                      ci_data=ci_data, alpha=alpha)
+    series, summary, window_summary = _compute_impact(
+        posterior_means=posterior_means, posterior_trajectories=posterior_trajectories,
+        ci_data=ci_data, alpha=alpha, windows=windows or ())
   has_weights = samples["weights"].shape[-1] > 0
   has_seasons = samples["seasonal_drift_scales"].shape[-1] > 0
   posterior = CausalImpactPosteriorSamples(
@@ -296,7 +318,63 @@ def fit_causalimpact(data: pd.DataFrame,
         pred_request["conditioned"], state_dim, posterior_processing.model_index(ci_data),
         ci_data.data.index)
   return CausalImpactAnalysis(series, summary, posterior, samples.get("diagnostics"), components,
-                              coefficients, prediction_errors, fit_quality)
+                              coefficients, prediction_errors, fit_quality, window_summary)
+
+
+@dataclasses.dataclass(frozen=True)
+class EffectWindow:
+  """One resolved entry of `effect_windows`: its bounds as values of the index (aligned like
+  `post_period`) and its model steps first .. first + count - 1."""
+  name: Any
+  start: Any
+  end: Any
+  first: int
+  count: int
+
+
+def _window_items(effect_windows):
+  """[(name, (lower, upper))] of an `effect_windows` argument; ValueError with the window named."""
+  if not hasattr(effect_windows, "items"):
+    raise ValueError("`effect_windows` must be a mapping {name: (start, end)}")
+  items = list(effect_windows.items())
+  if not items:
+    raise ValueError("`effect_windows` is empty")
+  for name, bounds in items:
+    if isinstance(bounds, str) or not hasattr(bounds, "__len__") or len(bounds) != 2:
+      raise ValueError(f"effect window {name!r}: expected (start, end), got {bounds!r}")
+  return items
+
+
+def resolve_windows(effect_windows, index: pd.Index, model_idx: pd.Index, post_period) -> List[EffectWindow]:
+  """The `effect_windows` of a fit on `index` as `EffectWindow`s over the model steps `model_idx`
+  (`posterior_processing.model_index`).  The bounds are converted and aligned exactly as `post_period`
+  is (`indices`: a string is a date, an integer a POSITION into the index, a bound between two index
+  values shrinks the window).  ValueError naming the window for bounds that cannot be read, a window
+  that leaves the (aligned) post-period, or one without a model row.  The post-period is a contiguous
+  run of model steps, hence so is every window."""
+  out = []
+  for name, bounds in _window_items(effect_windows):
+    try:
+      start, end = indices._align(                               # pylint: disable=protected-access
+          tuple(indices._to_index_value(v, index) for v in bounds), index)   # pylint: disable=protected-access
+    except (ValueError, IndexError, TypeError) as e:
+      raise ValueError(f"effect window {name!r}: {e}") from e
+    if start < post_period[0] or end > post_period[1]:
+      raise ValueError(f"effect window {name!r}: ({start}, {end}) leaves the post-period "
+                       f"({post_period[0]}, {post_period[1]})")
+    steps = np.flatnonzero(np.asarray((model_idx >= start) & (model_idx <= end)))
+    if steps.size == 0:
+      raise ValueError(f"effect window {name!r}: ({start}, {end}) contains no row of the data")
+    out.append(EffectWindow(name, start, end, int(steps[0]), int(steps.size)))
+  return out
+
+
+def _window_tables(windows: Sequence[EffectWindow], table_of) -> Optional[pd.DataFrame]:
+  """`window_summary` of one fit: table_of(position, window) -> the 2 x 15 frame of that window."""
+  if not windows:
+    return None
+  return pd.concat([table_of(w, win) for w, win in enumerate(windows)],
+                   keys=[win.name for win in windows], names=["window", None])
 
 
 def _component_summary_host(level, seasonal_levels, weights, X, scale, shift, ranks) -> Dict:
@@ -757,6 +835,16 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
             shift=(np.asarray(summary_request["shift"], np.float64)
                    + cond_mu * np.asarray(summary_request["scale"], np.float64)),
             **{k: summary_request[k] for k in ("observed", "flags", "ranks")})
+        if summary_request.get("windows"):
+          # the same conditioned (scale, shift): every draw's totals over the windows' own columns
+          summary_request["window_totals"] = sess.summarize_windows(
+              scale=np.asarray(summary_request["scale"], np.float64) * cond_s,
+              shift=(np.asarray(summary_request["shift"], np.float64)
+                     + cond_mu * np.asarray(summary_request["scale"], np.float64)),
+              observed=summary_request["observed"],
+              first=[w.first for w in summary_request["windows"]],
+              count=[w.count for w in summary_request["windows"]],
+              ranks=summary_request["ranks"])["per_draw"][0]
         if component_request is not None:
           component_request["ranks"] = _summary_ranks(len(chain_ids) * num_results,
                                                       component_request["quantiles"])
@@ -804,6 +892,14 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
         float(summary_request["shift"]) + cond_mu * float(summary_request["scale"]),
         summary_request["observed"], summary_request["flags"], summary_request["ranks"],
         device=devs[0])
+    if summary_request.get("windows"):
+      # ... and the window totals from exactly these trajectories and this (scale, shift)
+      summary_request["window_totals"] = _native.window_totals_host(
+          tr.reshape((1, tr.shape[0] * tr.shape[1]) + tr.shape[2:]),
+          float(summary_request["scale"]) * cond_s,
+          float(summary_request["shift"]) + cond_mu * float(summary_request["scale"]),
+          summary_request["observed"], [w.first for w in summary_request["windows"]],
+          [w.count for w in summary_request["windows"]])[0]
   if prediction_request is not None:
     prediction_request["conditioned"] = ~mask
     if "summary" not in prediction_request:
@@ -860,8 +956,9 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
 # impact post-processing (reference :635-1093) -- numpy inside, the reference's frames outside
 # --------------------------------------------------------------------------------------
 def _compute_impact(posterior_means, posterior_trajectories, ci_data: cid.CausalImpactData,
-                    alpha: float = 0.05) -> Tuple[pd.DataFrame, pd.DataFrame]:
-  """(series, summary) from the sampler's predictive draws (reference :635-705)."""
+                    alpha: float = 0.05, windows: Optional[Sequence[EffectWindow]] = None):
+  """(series, summary) from the sampler's predictive draws (reference :635-705); with `windows`
+  (series, summary, window_summary), the summary of every `EffectWindow` over its own rows."""
   if not 0 < alpha < 1:
     raise ValueError("`alpha` must be between 0 and 1.")
   observed_pre = ci_data.pre_data[ci_data.outcome_column]
@@ -883,7 +980,13 @@ def _compute_impact(posterior_means, posterior_trajectories, ci_data: cid.Causal
   summary = _compute_summary(posterior_trajectory_summary=trajectory_summary,
                              trajectory_dict=trajectory_dict, observed_ts_post=observed_post,
                              post_period=ci_data.post_period, quantiles=quantiles, alpha=alpha)
-  return series, summary
+  if windows is None:
+    return series, summary
+  window_summary = _window_tables(windows, lambda _, win: _compute_summary(
+      posterior_trajectory_summary=trajectory_summary, trajectory_dict=trajectory_dict,
+      observed_ts_post=observed_post, post_period=(win.start, win.end), quantiles=quantiles,
+      alpha=alpha))
+  return series, summary, window_summary
 
 
 def _observed_series(ci_data: cid.CausalImpactData):
@@ -945,10 +1048,23 @@ def _lerp_order_stats(order: Dict[int, np.ndarray], lo: int, hi: int, gamma) -> 
     return np.quantile(pair, gamma, axis=0)
 
 
+def _per_draw_means(pred_sum, point_sum, num_steps: int, num_observed: int) -> Dict[str, np.ndarray]:
+  """The per-draw window means and totals `_compute_summary` takes, from the totals over a window of
+  `num_steps` steps of which `num_observed` have an observation."""
+  with np.errstate(invalid="ignore", divide="ignore"):
+    return dict(pred_mean=pred_sum / num_steps, pred_sum=pred_sum,
+                point_mean_t=point_sum / num_observed if num_observed else
+                np.full_like(point_sum, np.nan),
+                point_sum_t=point_sum)
+
+
 def _compute_impact_device(posterior_means, device_summary: Dict, request: Dict,
-                           ci_data: cid.CausalImpactData, alpha: float):
+                           ci_data: cid.CausalImpactData, alpha: float,
+                           windows: Optional[Sequence[EffectWindow]] = None):
   """(series, summary) from the on-device summary (csrc/ci_summary.h) -- same frames as
-  _compute_impact, which stays the host reference of this arithmetic."""
+  _compute_impact, which stays the host reference of this arithmetic.  With `windows` (series,
+  summary, window_summary): the summary of every `EffectWindow` from request["window_totals"]
+  [W, 2, N], every draw's totals over it (csrc/ci_windows.h)."""
   quantiles = (alpha / 2.0, 1.0 - alpha / 2.0)
   observed_post, observed_full = _observed_series(ci_data)
   idx = posterior_processing.model_index(ci_data)
@@ -983,16 +1099,24 @@ def _compute_impact_device(posterior_means, device_summary: Dict, request: Dict,
   window = (request["flags"] & 2) != 0
   n_obs_window = int(np.sum(~np.isnan(obs[window])))
   pred_sum, point_sum = device_summary["per_draw"]
-  with np.errstate(invalid="ignore", divide="ignore"):
-    per_draw = dict(pred_mean=pred_sum / int(window.sum()), pred_sum=pred_sum,
-                    point_mean_t=point_sum / n_obs_window if n_obs_window else
-                    np.full_like(point_sum, np.nan),
-                    point_sum_t=point_sum)
+  per_draw = _per_draw_means(pred_sum, point_sum, int(window.sum()), n_obs_window)
   summary = _compute_summary(posterior_trajectory_summary=trajectory_summary,
                              trajectory_dict=None, observed_ts_post=observed_post,
                              post_period=ci_data.post_period, quantiles=quantiles, alpha=alpha,
                              per_draw=per_draw)
-  return series, summary
+  if windows is None:
+    return series, summary
+
+  def table_of(w, win):
+    steps = slice(win.first, win.first + win.count)
+    totals = request["window_totals"][w]
+    return _compute_summary(
+        posterior_trajectory_summary=trajectory_summary, trajectory_dict=None,
+        observed_ts_post=observed_post, post_period=(win.start, win.end), quantiles=quantiles,
+        alpha=alpha, per_draw=_per_draw_means(totals[0], totals[1], win.count,
+                                              int(np.sum(~np.isnan(obs[steps])))))
+
+  return series, summary, _window_tables(windows, table_of)
 
 
 def _sample_posterior_predictive(posterior_means, posterior_trajectories,
@@ -1171,15 +1295,16 @@ def _compute_summary(posterior_trajectory_summary: pd.DataFrame,
                      trajectory_dict: Dict[str, pd.DataFrame], observed_ts_post: pd.Series,
                      post_period: OutputPeriodType, quantiles: Tuple[float, float],
                      alpha: float, per_draw: Optional[Dict[str, np.ndarray]] = None) -> pd.DataFrame:
-  """The 2 x 15 `summary` frame over the post-period (reference :934-1093).  `per_draw`:
-  precomputed per-draw window means / totals (on-device summary)."""
+  """The 2 x 15 `summary` frame over the post-period (reference :934-1093), or over any window
+  inside it handed in as `post_period` (`effect_windows`: observed_ts_post is cut to it like the
+  other frames).  `per_draw`: precomputed per-draw window means / totals (on-device summary)."""
 
   def window(frame):
     keep = (frame.index >= post_period[0]) & (frame.index <= post_period[1])
     return frame.loc[keep]
 
   post_mean = window(posterior_trajectory_summary)["posterior_mean"].to_numpy(dtype=np.float64)
-  obs = observed_ts_post.to_numpy(dtype=np.float64)
+  obs = window(observed_ts_post).to_numpy(dtype=np.float64)
   if per_draw is None:
     pred = window(trajectory_dict["predictions"]).to_numpy(dtype=np.float64)      # [T_post, draws]
     point = window(trajectory_dict["point_effects"]).to_numpy(dtype=np.float64)

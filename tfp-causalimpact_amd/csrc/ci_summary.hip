@@ -1,6 +1,7 @@
 // ci_summary.hip -- the on-device summaries behind the C-ABI (kernels: ci_summary.h,
 // ci_components.h, ci_predict.h): ci_session_summarize, ci_session_summarize_components,
-// ci_session_summarize_predictions,
+// ci_session_summarize_predictions, ci_session_summarize_windows, ci_ll_session_summarize_windows
+// (kernel: ci_windows.h),
 // ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] on
 // draws the caller hands in; ci_session_pool_trajectories, ci_ll_session_pool_trajectories and
 // ci_session_pool_event_trajectories (kernels: ci_pool.h) on the trajectories a session holds.
@@ -116,7 +117,66 @@ hipError_t comp_launch_row_stats(hipStream_t stream, size_t rows, int N, const d
 // The launch of ci_predict.hip (kernels: ci_predict.h).
 hipError_t predict_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
                           const PredArgs& args);
+// The launch of ci_windows.hip (kernel: ci_windows.h).
+hipError_t windows_launch(hipStream_t stream, int B, int N, int T, int W, const float* traj,
+                          const double* obs, const double* scales, const double* shifts,
+                          const int* first, const int* count, double* out);
 }  // namespace ci
+
+// The window totals of B series' [B, N, T] float32 trajectories resident in HBM
+// (ci_session_summarize_windows, ci_ll_session_summarize_windows): everything is checked before the
+// first device call; one streaming pass over the windows' own columns, then the order statistics of
+// the 2 * B * W rows of totals.  The call's device memory -- the tables and 2 * (N + 8) doubles per
+// (series, window) -- is its own and goes back on every return path; the summary's scratch is
+// neither built nor touched.
+static int windows_resident(const char* what, int device, hipStream_t stream, int B, int T, int N,
+                            const float* traj, const double* scale, const double* shift,
+                            const double* observed, int32_t W, const int32_t* first,
+                            const int32_t* count, int32_t num_ranks, const int32_t* ranks,
+                            double* per_draw, double* per_draw_order) {
+  if (W < 1 || W > 1024) return fail("%s: num_windows must be in [1, 1024], got %d", what, W);
+  for (int b = 0; b < B; ++b)
+    for (int w = 0; w < W; ++w) {
+      const int f = first[(size_t)b * W + w], c = count[(size_t)b * W + w];
+      if (f < 0) return fail("%s: window %d of series %d: first step %d is negative", what, w, b, f);
+      if (c < 0) return fail("%s: window %d of series %d: count %d is negative", what, w, b, c);
+      if ((long long)f + c > T)
+        return fail("%s: window %d of series %d: steps %d .. %lld end beyond the session's %d steps",
+                    what, w, b, f, (long long)f + c - 1, T);
+    }
+  if (check_ranks(num_ranks, ranks, N)) return 1;
+  HIP_TRY(hipSetDevice(device));
+  const int R = ci::SUMM_MAX_RANKS;
+  const size_t BW = (size_t)B * W, BT = (size_t)B * T;
+  DevBuf<double> d_f64;       // observed [B, T], scale [B], shift [B], totals [B, W, 2, N], order [B, W, 2, 8]
+  DevBuf<int> d_i32;          // first [B, W], count [B, W], ranks [8]
+  HIP_TRY(d_f64.alloc(BT + 2 * (size_t)B + 2 * BW * ((size_t)N + R)));
+  HIP_TRY(d_i32.alloc(2 * BW + R));
+  double* d_scale = d_f64.p + BT;
+  double* d_shift = d_scale + B;
+  double* d_draw = d_shift + B;
+  double* d_order = d_draw + 2 * BW * N;
+  int* d_count = d_i32.p + BW;
+  int* d_ranks = d_count + BW;
+  HIP_TRY(hipMemcpyAsync(d_f64.p, observed, BT * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_i32.p, first, BW * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_count, count, BW * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_ranks, ranks, num_ranks * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(ci::windows_launch(stream, B, N, T, W, traj, d_f64.p, d_scale, d_shift, d_i32.p, d_count,
+                             d_draw));
+  if (per_draw_order)
+    HIP_TRY(launch_select(stream, N, 1, (int)(2 * BW), num_ranks, d_ranks, d_draw, nullptr, d_order,
+                          nullptr));
+  if (per_draw)
+    HIP_TRY(hipMemcpyAsync(per_draw, d_draw, 2 * BW * N * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (per_draw_order)
+    HIP_TRY(hipMemcpyAsync(per_draw_order, d_order, 2 * BW * num_ranks * sizeof(double),
+                           hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
 
 // ci_summarize_draws / ci_summarize_draws_f64: one series of draws from the host, uploaded into a
 // scratch of its own, summarised on the null stream and given back.
@@ -303,6 +363,29 @@ int ci_session_summarize(ci_session* s, const double* scale, const double* shift
   return summarize_resident(s->stream, s->summ, pb.num_series, pb.T, pb.num_chains * pb.num_results,
                             s->o_traj.p, scale, shift, observed, flags, num_ranks, ranks, value_order,
                             cum_order, per_draw, per_draw_order);
+}
+
+int ci_session_summarize_windows(ci_session* s, const double* scale, const double* shift,
+                                 const double* observed, int32_t num_windows, const int32_t* first,
+                                 const int32_t* count, int32_t num_ranks, const int32_t* ranks,
+                                 double* per_draw, double* per_draw_order) {
+  if (!s || !scale || !shift || !observed || !first || !count || !ranks) return fail("NULL argument");
+  if (!s->ran) return fail("ci_session_summarize_windows needs a finished ci_session_run");
+  const ci_problem& pb = s->pb;
+  return windows_resident("ci_session_summarize_windows", pb.device, s->stream, pb.num_series, pb.T,
+                          pb.num_chains * pb.num_results, s->o_traj.p, scale, shift, observed,
+                          num_windows, first, count, num_ranks, ranks, per_draw, per_draw_order);
+}
+
+int ci_ll_session_summarize_windows(ci_ll_session* s, const double* scale, const double* shift,
+                                    const double* observed, int32_t num_windows, const int32_t* first,
+                                    const int32_t* count, int32_t num_ranks, const int32_t* ranks,
+                                    double* per_draw, double* per_draw_order) {
+  if (!s || !scale || !shift || !observed || !first || !count || !ranks) return fail("NULL argument");
+  if (!s->h_ran) return fail("ci_ll_session_summarize_windows needs a finished ci_ll_session_hmc_run");
+  return windows_resident("ci_ll_session_summarize_windows", s->device, s->stream, s->B, s->T,
+                          s->h_C * s->h_S, s->h_traj.p, scale, shift, observed, num_windows, first,
+                          count, num_ranks, ranks, per_draw, per_draw_order);
 }
 
 int ci_session_summarize_components(ci_session* s, const double* scale, const double* shift,
