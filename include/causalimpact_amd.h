@@ -198,6 +198,15 @@ int ci_fit_gibbs_f64(const ci_problem* problem, const double* y, const uint8_t* 
 /* Duration (HIP events) of the sampling kernel of the calling thread's last successful
  * ci_fit_gibbs_f64 -- the call itself also allocates, uploads and downloads. */
 int ci_fit_gibbs_f64_kernel_ms(float* kernel_ms);
+/* The route ci_fit_gibbs_f64 takes for `problem`, decided on the host from its shape alone (no
+ * device call; the same validation and the same errors as the fit: state wider than 64, LDS limit).
+ *   global_ws    1: the arrays over time in the per-chain HBM workspace, 0: in LDS
+ *   reg_lds      1: the regression block's O(P^2) arrays in LDS, 0: in the workspace
+ *   trend_kernel 1: the eight-wavefront trend kernel (num_blocks = 0), 0: the sequential kernel
+ *   lds_bytes    the dynamic LDS of the launch
+ * The tests use it to prove which kernel build and memory layout a shape reaches. */
+int ci_fit_gibbs_f64_route(const ci_problem* problem, int32_t* global_ws, int32_t* reg_lds,
+                           int32_t* trend_kernel, int64_t* lds_bytes);
 
 /* Device-resident variant (what bench.py times: inputs already in HBM). */
 int ci_session_create(const ci_problem* problem, const float* y, const uint8_t* mask,

@@ -132,6 +132,15 @@ def test_round_3_entry_points_validate_before_any_device_call():
   assert L.ci_fit_gibbs_f64(C.byref(pb), y64.ctypes.data, m.ctypes.data, None, sc.ctypes.data, prm,
                             C.byref(out)) != 0
   assert b"too wide" in L.ci_last_error()
+  # ... and ci_fit_gibbs_f64_route answers the same without any data (tests/test_float64_route_table.py)
+  g, r, k, lds = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int64(-1)
+  assert L.ci_fit_gibbs_f64_route(C.byref(pb), C.byref(g), C.byref(r), C.byref(k), C.byref(lds)) != 0
+  assert b"too wide" in L.ci_last_error()
+  assert (g.value, r.value, k.value, lds.value) == (-1, -1, -1, -1)      # nothing written on an error
+  pb = _native.make_problem(T=T, P=2, has_slope=0, num_warmup=1, num_results=2)
+  assert L.ci_fit_gibbs_f64_route(C.byref(pb), C.byref(g), C.byref(r), C.byref(k), C.byref(lds)) == 0
+  assert (g.value, r.value, k.value) == (0, 1, 1) and 0 < lds.value <= 160 * 1024
+  assert _native.fit_gibbs_f64_route(pb) == dict(global_ws=0, reg_lds=1, trend_kernel=1, lds_bytes=lds.value)
   # log-likelihood sessions: blocks need create2's season_change; P is capped at 128 there (round 5: was 52)
   h = C.c_void_p()
   pb = _native.make_problem(T=T, P=0, has_slope=0, num_seasons=(7,), num_warmup=0, num_results=1)

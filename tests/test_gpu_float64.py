@@ -2,7 +2,9 @@
 against the float64 oracle: same algorithm, same random numbers, float64 on both sides, so the two
 agree DRAW FOR DRAW over whole fits up to summation order -- 1e-8, not the 5e-3 of the float32
 kernels.  This is the tightest pin of the device algorithm in the suite: inclusion patterns,
-every scale, every weight, every latent path and predictive trajectory of every iteration."""
+every scale, every weight, every latent path and predictive trajectory of every iteration.
+The cases here are single series on the common routes; tests/test_gpu_float64_routes.py pins every
+route of `ci_fit_gibbs_f64` (LDS / workspace, both kernels), batches of series and the gap patterns."""
 import numpy as np
 import pandas as pd
 import pytest

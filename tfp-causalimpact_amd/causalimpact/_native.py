@@ -95,6 +95,8 @@ def load():
   L.ci_fit_gibbs_f64.argtypes = [C.POINTER(Problem), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.POINTER(SeriesParams), C.POINTER(Outputs)]
   L.ci_fit_gibbs_f64_kernel_ms.argtypes = [C.POINTER(C.c_float)]
+  L.ci_fit_gibbs_f64_route.argtypes = [C.POINTER(Problem), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
   L.ci_session_create.argtypes = [C.POINTER(Problem), C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.POINTER(SeriesParams), C.POINTER(C.c_void_p)]
   L.ci_session_create_ragged.argtypes = [C.POINTER(Problem), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -178,6 +180,7 @@ def exported_symbols() -> Sequence[str]:
   """Every entry point include/causalimpact_amd.h declares."""
   return ("ci_last_error", "ci_abi_version", "ci_device_count", "ci_series_stream_key", "ci_device_synchronize", "ci_pool_trim", "ci_host_alloc",
           "ci_host_free", "ci_fit_gibbs", "ci_fit_gibbs_f64", "ci_fit_gibbs_f64_kernel_ms",
+          "ci_fit_gibbs_f64_route",
           "ci_session_create", "ci_session_create_ragged", "ci_session_create_ragged_seasonal", "ci_session_run", "ci_session_run_streamed", "ci_session_fetch",
           "ci_session_algorithmic_bytes", "ci_session_kernel_name", "ci_session_destroy",
           "ci_session_profile", "ci_ll_session_kernel_name",
@@ -578,6 +581,17 @@ def fit_gibbs_f64_kernel_ms() -> float:
   ms = C.c_float()
   _check(load().ci_fit_gibbs_f64_kernel_ms(C.byref(ms)))
   return float(ms.value)
+
+
+def fit_gibbs_f64_route(pb: Problem) -> Dict[str, int]:
+  """The route fit_gibbs_f64 takes for `pb` (ci_fit_gibbs_f64_route; host arithmetic, no device):
+  global_ws / reg_lds -- arrays over time / regression block in the HBM workspace or in LDS,
+  trend_kernel -- eight-wavefront trend kernel or the sequential one, lds_bytes of the launch.
+  Raises what the fit would raise for a shape it refuses."""
+  gws, reg, trend, lds = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+  _check(load().ci_fit_gibbs_f64_route(C.byref(pb), C.byref(gws), C.byref(reg), C.byref(trend),
+                                       C.byref(lds)))
+  return dict(global_ws=gws.value, reg_lds=reg.value, trend_kernel=trend.value, lds_bytes=lds.value)
 
 
 class Session:

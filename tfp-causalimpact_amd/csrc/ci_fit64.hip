@@ -11,7 +11,49 @@
 
 static thread_local float g_f64_kernel_ms = 0.f;   // duration of the last ci_fit_gibbs_f64 kernel on this thread
 
+// The route of a float64 fit of a validated problem: where its arrays live and which kernel runs.
+struct F64Route {
+  int dfull, dred, gws, reg_lds;
+  ci::Layout64 lay;
+};
+// LDS first: arrays over time AND the regression block (P <= 32) when both fit, then the arrays
+// over time alone; else the HBM workspace for the arrays (regression still in LDS if small).
+// Host arithmetic only (ci_fit_gibbs_f64_route answers without a device).
+static int f64_route(const ci_problem* pb, F64Route* r) {
+  const int T = pb->T, P = pb->P, K = pb->num_blocks, has_slope = pb->has_slope ? 1 : 0;
+  int dfull = has_slope ? 2 : 1, dred = dfull;
+  for (int k = 0; k < K; ++k) { dfull += pb->num_seasons[k]; dred += pb->num_seasons[k] - 1; }
+  if (dfull > 64)
+    return fail("seasonal state too wide for one wavefront: %d > 64 (dtype=float64 holds states of at "
+                "most 64 components; the float32 Gibbs sampler up to %d)", dfull, ci::MW_MAXD);
+  int gws = 0, reg_lds = P <= 32 ? 1 : 0;
+  if (ci::make_layout64(T, P, K, dfull, dred, has_slope, 0, reg_lds).total > 150 * 1024) {
+    reg_lds = 0;
+    if (ci::make_layout64(T, P, K, dfull, dred, has_slope, 0, 0).total > 150 * 1024) {
+      gws = 1;
+      reg_lds = P <= 32 ? 1 : 0;
+    }
+  }
+  r->dfull = dfull; r->dred = dred; r->gws = gws; r->reg_lds = reg_lds;
+  r->lay = ci::make_layout64(T, P, K, dfull, dred, has_slope, gws, reg_lds);
+  if (r->lay.total > 160 * 1024) return fail("float64 fit needs %zu bytes of LDS (max 163840)", r->lay.total);
+  return 0;
+}
+
 extern "C" {
+
+int ci_fit_gibbs_f64_route(const ci_problem* pb, int32_t* global_ws, int32_t* reg_lds,
+                           int32_t* trend_kernel, int64_t* lds_bytes) {
+  if (validate(pb)) return 1;
+  if (!global_ws || !reg_lds || !trend_kernel || !lds_bytes) return fail("NULL argument");
+  F64Route r;
+  if (f64_route(pb, &r)) return 1;
+  *global_ws = r.gws;
+  *reg_lds = r.reg_lds;
+  *trend_kernel = pb->num_blocks == 0 ? 1 : 0;   // (ci_launch_gibbs64: gibbs64_trend_kernel without blocks)
+  *lds_bytes = (int64_t)r.lay.total;
+  return 0;
+}
 
 int ci_fit_gibbs_f64(const ci_problem* pb, const double* y, const uint8_t* mask, const double* X,
                      const uint8_t* season_change, const ci_series_params* params,
@@ -22,23 +64,10 @@ int ci_fit_gibbs_f64(const ci_problem* pb, const double* y, const uint8_t* mask,
   if (pb->P > 0 && !X) return fail("X is NULL but P=%d", pb->P);
   const int T = pb->T, P = pb->P, B = pb->num_series, C = pb->num_chains, S = pb->num_results;
   const int K = pb->num_blocks, has_slope = pb->has_slope ? 1 : 0;
-  int dfull = has_slope ? 2 : 1, dred = dfull;
-  for (int k = 0; k < K; ++k) { dfull += pb->num_seasons[k]; dred += pb->num_seasons[k] - 1; }
-  if (dfull > 64)
-    return fail("seasonal state too wide for one wavefront: %d > 64 (dtype=float64 holds states of at "
-                "most 64 components; the float32 Gibbs sampler up to %d)", dfull, ci::MW_MAXD);
-  // LDS first: arrays over time AND the regression block (P <= 32) when both fit, then the arrays
-  // over time alone; else the HBM workspace for the arrays (regression still in LDS if small)
-  int gws = 0, reg_lds = P <= 32 ? 1 : 0;
-  if (ci::make_layout64(T, P, K, dfull, dred, has_slope, 0, reg_lds).total > 150 * 1024) {
-    reg_lds = 0;
-    if (ci::make_layout64(T, P, K, dfull, dred, has_slope, 0, 0).total > 150 * 1024) {
-      gws = 1;
-      reg_lds = P <= 32 ? 1 : 0;
-    }
-  }
-  const ci::Layout64 lay = ci::make_layout64(T, P, K, dfull, dred, has_slope, gws, reg_lds);
-  if (lay.total > 160 * 1024) return fail("float64 fit needs %zu bytes of LDS (max 163840)", lay.total);
+  F64Route route;
+  if (f64_route(pb, &route)) return 1;
+  const int dfull = route.dfull, dred = route.dred, gws = route.gws, reg_lds = route.reg_lds;
+  const ci::Layout64& lay = route.lay;
   const size_t ws_stride = ci::gibbs64_ws_bytes(T, P, K, dfull, dred, has_slope, gws, reg_lds);
   const size_t BT = (size_t)B * T, BCS = (size_t)B * C * S;
   // staged and checked on the host before the first device call

@@ -12,7 +12,9 @@
 //   * the regression draw of spike_slab_draw_big (dense float64 sweeps) for every P.
 // Consequence: the device and the float64 oracle (oracle/ci_oracle.c) run the same arithmetic up
 // to summation order, so they agree draw for draw to ~1e-9 over whole fits
-// (tests/test_gpu_float64.py) -- a far tighter pin of the device algorithm than the float32
+// (tests/test_gpu_float64.py; every route of ci_fit_gibbs_f64 -- LDS or workspace, regression block
+// in or out of LDS, both kernels -- batches of series and the missing-data patterns are pinned in
+// tests/test_gpu_float64_routes.py) -- a far tighter pin of the device algorithm than the float32
 // kernels' 5e-3.  It is the precision option, not the fast one: sequential in time for models
 // with seasonal blocks; trend-only models (the reference's default) are time-parallel over the
 // 64 lanes of the chain's wavefront (Drift2 / Kf2 / Aff2 below).
