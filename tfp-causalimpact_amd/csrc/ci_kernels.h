@@ -132,6 +132,9 @@ struct Prof {
       t = n;
     }
   }
+  __device__ __forceinline__ void mark() {      // start an interval that the next tick() closes
+    if (p) t = clock64();
+  }
 };
 
 // The same interface compiled to nothing: the production instantiations of the Gibbs kernel carry
@@ -140,6 +143,7 @@ struct Prof {
 struct NoProf {
   __device__ __forceinline__ void start(long long*, bool) {}
   __device__ __forceinline__ void tick(int) {}
+  __device__ __forceinline__ void mark() {}
 };
 
 template <class E> struct Arr { float f[sizeof(E) / 4]; };

@@ -62,7 +62,9 @@ constexpr int PRE_MAXS = 16;          // recorded sweeps / un-sweeps (P <= 16)
 // LDS tables written by the regression wave's precompute, read by its next serial section.
 struct PreTables {
   double* tsw;      // [PRE_MAXS][16]  sweep s: t_j = A[k_s][j] / pivot of feature j (1 at the pivot)
-  double* V;        // [16][16]        the posterior block swept on S, row-major (V[k][j])
+  double* V;        // [16][16]        the posterior block swept on S for its one reader, the right-hand-
+                    //                 side product: row-major (V[k][j]), or, where that product is split
+                    //                 by chain (rhs_split), V[k][j] at [k & 1][k >> 2][j][(k >> 1) & 1]
   double* rdk;      // [16]            1 / pivot of the sweep of feature j (j in S)
   double* hand;     // [20]            serial section -> weights wave: posterior mean of the weights
                     //                 [16], sigma_obs, then (as ints) S lo, S hi, flag "draw them"
@@ -110,6 +112,23 @@ __device__ __forceinline__ double row_sum16_d(double v) {
   v = dpp_ror_add_d<0x121>(v);   // row_ror:1
   return readlane_d(v, 0);
 }
+// Lanes 0-31 and lanes 32-63 hold one value each per lane pair (l, l + 32): both to both lanes
+// (v_permlane32_swap: the upper half of its first operand changes places with the lower half of
+// its second).
+__device__ __forceinline__ void halves_d(double v, double& of_lower, double& of_upper) {
+  const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+  const auto sl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+  const auto sh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  of_lower = __hiloint2double((int)sh[0], (int)sl[0]);
+  of_upper = __hiloint2double((int)sh[1], (int)sl[1]);
+}
+
+// The right-hand-side product of the serial section is split over the halves of the regression
+// wave (spike_slab_draw_pre) where that was measured to pay: the builds with registers to spare
+// (L <= 4; at L >= 8 the kernel is at 256 VGPRs with scratch, the time waves' window sets the pace
+// and every build keeps the replicated product) and more than two groups of four columns (up to
+// P = 8 the replicated product has 8 loads per lane and no exchange: measured faster at P = 6).
+template <int L> __device__ __forceinline__ bool rhs_split(int P) { return L <= 4 && P > 8; }
 
 // sweep_q_kr<KR, false> that also returns its multipliers (t of this lane, 1 / pivot).
 template <int KR>
@@ -144,10 +163,10 @@ __device__ __forceinline__ void sweep_rec(QCols& m, int k, int lane, double& t_o
 // S (ascending), recording per sweep the multipliers t_j = A[k][j] / pivot.  Those ARE the Cholesky
 // factor of the included block M_S = L L' (L_jk / L_kk = t_j of sweep k for j > k in S,
 // L_kk^2 = pivot_k), which is all the weights draw u = L^-T z needs (back substitution, see
-// weights_backsub) -- no second pass of un-sweeps.  The swept block itself goes to LDS row-major
-// for the right-hand-side product.  Written as a RESUMABLE sequence of steps (build, one sweep per
-// member of S, store): the caller runs each step in whatever interval between two workgroup
-// barriers its schedule gives it.
+// weights_backsub) -- no second pass of un-sweeps.  The swept block itself goes to LDS laid out
+// by chain for the right-hand-side product (PreTables::V).  Written as a RESUMABLE sequence of
+// steps (build, one sweep per member of S, store): the caller runs each step in whatever interval
+// between two workgroup barriers its schedule gives it.
 struct PreRun {
   QCols m;
   double rdk;
@@ -163,7 +182,7 @@ __device__ __forceinline__ void pre_begin(PreRun& st, unsigned long long S) {
 }
 __device__ __forceinline__ void pre_step(PreRun& st, const RegLds& R, int P, double var_next,
                                          unsigned long long S, int lane, const PreTables& tb,
-                                         PreState& ps) {
+                                         PreState& ps, bool split) {
   const int j = lane & 15, q = lane >> 4;
   const bool live = j < P;
   const int col = live ? j : 0;
@@ -192,8 +211,17 @@ __device__ __forceinline__ void pre_step(PreRun& st, const RegLds& R, int P, dou
     st.pending &= st.pending - 1ull;
     if (st.pending == 0ull) st.phase = 2;
   } else {
+    // (split:) rows 4q, 4q + 2 are a pair of the even chain of the right-hand-side product, rows 4q + 1,
+    // 4q + 3 one of the odd chain: two 16-byte stores; the 16 columns of a pair are neighbours, so
+    // the 16 lanes of a read group cover one 256-byte row of banks
+    if (split) {
+      double2* V2 = reinterpret_cast<double2*>(tb.V);
+      V2[q * 16 + j] = make_double2(st.m.c[0], st.m.c[2]);
+      V2[(4 + q) * 16 + j] = make_double2(st.m.c[1], st.m.c[3]);
+    } else {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) tb.V[(4 * q + r) * 16 + j] = st.m.c[r];
+      for (int r = 0; r < 4; ++r) tb.V[(4 * q + r) * 16 + j] = st.m.c[r];
+    }
     if (q == 0) tb.rdk[j] = st.rdk;
     ps.n_sw = st.n;
 #pragma unroll
@@ -249,13 +277,17 @@ __device__ __forceinline__ void weights_backsub(const PreTables& tb, const doubl
 // `publish(new_scale, mean, S, clean)` is called as soon as sigma_obs is drawn; when it returns true
 // the weights are drawn by somebody else (weights_backsub on another wave) and this function ends.
 // `publish(new_scale)` is called as soon as sigma_obs is drawn -- before the weights.
-template <class PF, class Pub>
+template <bool HOIST, class PF, class Pub>
 __device__ __forceinline__ double spike_slab_draw_pre(const RegLds& R, int P,
                                                       const DevSeriesParams& sp,
                                                       double prev_obs_scale, double g_obs,
-                                                      int lane, PriorCarry& pc, const double* pre,
-                                                      const PreTables& tb, const PreState& ps,
-                                                      const float* red, PF& prof, Pub publish) {
+                                                      double rg_obs_early, double logit_pi_early,
+                                                      bool split, int lane, PriorCarry& pc,
+                                                      const double* pre, const PreTables& tb,
+                                                      const PreState& ps, const float* red, PF& prof,
+                                                      Pub publish) {
+  // (HOIST: fast_rcp(g_obs) and logit_pi come from the caller, which forms them where nobody
+  //  waits for this wave; the expressions are those of spike_slab_draw_regs either way)
   const double prev_var = prev_obs_scale * prev_obs_scale;
   const double a_post = sp.obs_conc + 0.5 * sp.n_obs;
   const bool all_in = sp.nonzero_prob >= 1.0;
@@ -274,31 +306,68 @@ __device__ __forceinline__ double spike_slab_draw_pre(const RegLds& R, int P,
   unsigned long long S = ps.S;
   // ---- right-hand side: with V the matrix swept on S (precompute) and b = X~'targets,
   //   b~_j = (j in S ? 0 : b_j) - sum_{k in S} V_kj b_k ,   corner = y'y - sum_{k in S} b_k b~_k
-  // (what carrying b through the recorded sweeps gives): every lane forms the product for its
-  // own column j from the row-major copy in LDS -- 16 independent loads, no cross-lane traffic;
-  // the four rows of 16 lanes compute replicas
+  // (what carrying b through the recorded sweeps gives).  The sum runs as two chains, the even k
+  // ascending and the odd k ascending, added at the end.  Rows 0-1 of 16 lanes run the even chain
+  // for their column j, rows 2-3 the odd one; one exchange of the two halves of the wave then
+  // gives every lane both: each chain is the same sequence of fma on the same operands whoever
+  // runs it.  Per lane four 16-byte loads of V (two members of its chain each: the layout of
+  // pre_step's store) and four broadcast loads of b, no cross-lane traffic before the exchange.
   {
-    // (rows in groups of four, groups beyond P skipped: the branch is uniform and sits around a
-    //  whole group of independent loads)
-    double v[16], bk[16];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      if (4 * g < P) {
-#pragma unroll
-        for (int k = 4 * g; k < 4 * g + 4; ++k) {
-          v[k] = tb.V[k * 16 + j];
-          bk[k] = (double)red[k];        // (red[P .. 15] hold nothing: masked by S below)
-        }
-      } else {
-#pragma unroll
-        for (int k = 4 * g; k < 4 * g + 4; ++k) { v[k] = 0.0; bk[k] = 0.0; }
-      }
-    }
     double acc0 = 0.0, acc1 = 0.0;
+    if (split) {
+      // (in groups of four k, groups beyond P skipped: the branch is uniform and sits around a
+      //  whole group of independent loads)
+      const int h = q >> 1;
+      const double2* V2 = reinterpret_cast<const double2*>(tb.V) + h * 64 + j;
+      const float4* b4 = reinterpret_cast<const float4*>(red);
+      double2 v[4];
+      float4 f[4];
 #pragma unroll
-    for (int k = 0; k < 16; k += 2) {
-      acc0 = ((S >> k) & 1ull) ? fma(v[k], bk[k], acc0) : acc0;
-      acc1 = ((S >> (k + 1)) & 1ull) ? fma(v[k + 1], bk[k + 1], acc1) : acc1;
+      for (int g = 0; g < 4; ++g) {
+        if (4 * g < P) {
+          v[g] = V2[g * 16];                 // V[4g + h][j], V[4g + 2 + h][j]
+          f[g] = b4[g];                      // (red[P .. 15] hold nothing: masked by S below)
+        } else {
+          v[g] = make_double2(0.0, 0.0);
+          f[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+      double ba[4], bb[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        ba[g] = (double)(h ? f[g].y : f[g].x);
+        bb[g] = (double)(h ? f[g].w : f[g].z);
+      }
+      const unsigned Sh = (unsigned)(S & 0xFFFFull) >> h;      // bit 2i: member 2i + h of S
+      double acc = 0.0;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        acc = ((Sh >> (4 * g)) & 1u) ? fma(v[g].x, ba[g], acc) : acc;
+        acc = ((Sh >> (4 * g + 2)) & 1u) ? fma(v[g].y, bb[g], acc) : acc;
+      }
+      halves_d(acc, acc0, acc1);
+    } else {
+      // every lane runs both chains for its own column j from the row-major copy: 16 independent
+      // loads, no cross-lane traffic; the four rows of 16 lanes compute replicas
+      double v[16], bk[16];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        if (4 * g < P) {
+#pragma unroll
+          for (int k = 4 * g; k < 4 * g + 4; ++k) {
+            v[k] = tb.V[k * 16 + j];
+            bk[k] = (double)red[k];        // (red[P .. 15] hold nothing: masked by S below)
+          }
+        } else {
+#pragma unroll
+          for (int k = 4 * g; k < 4 * g + 4; ++k) { v[k] = 0.0; bk[k] = 0.0; }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 16; k += 2) {
+        acc0 = ((S >> k) & 1ull) ? fma(v[k], bk[k], acc0) : acc0;
+        acc1 = ((S >> (k + 1)) & 1ull) ? fma(v[k + 1], bk[k + 1], acc1) : acc1;
+      }
     }
     const bool inj = ((S >> j) & 1ull) != 0ull;
     const double bj = m.cb;
@@ -310,8 +379,9 @@ __device__ __forceinline__ double spike_slab_draw_pre(const RegLds& R, int P,
   if (!all_in) {
     const int rank = reinterpret_cast<const int*>(pre + 16)[j];
     const double uflip = pre[j];
-    const double logit_pi =
-        (double)(__logf((float)sp.nonzero_prob) - __logf((float)(1.0 - sp.nonzero_prob)));
+    double logit_pi = logit_pi_early;
+    if constexpr (!HOIST)
+      logit_pi = (double)(__logf((float)sp.nonzero_prob) - __logf((float)(1.0 - sp.nonzero_prob)));
     int s_cur = 0;
     const double inv_prev_var = fast_rcp(prev_var);
     for (;;) {
@@ -347,7 +417,7 @@ __device__ __forceinline__ double spike_slab_draw_pre(const RegLds& R, int P,
   pc.S = S;
   pc.valid = 1;
   const double beta_post = sp.obs_scale + 0.5 * m.corner;
-  double var = beta_post * fast_rcp(g_obs);
+  double var = beta_post * (HOIST ? rg_obs_early : fast_rcp(g_obs));
   if (var > sp.obs_ub) var = sp.obs_ub;
   const double new_scale = (double)__fsqrt_rn((float)var);
   const double mean = m.cb;
@@ -430,6 +500,9 @@ enum Scal8 { SC8_INIT_LOC = 8, SC8_INIT_VAR = 9, SC8_INIT_SVAR = 10, SC8_ZINIT =
 //                       18 = wait at (Bs)   23 = weights + scale draws   17 = wait at (B3)
 //                       19 = precompute steps (pure)   29 = its waits at (B4) (B5)
 //   randomness wave 5:  30 = work   31 = waits at barriers
+//   arrival at (Bs), cycles since the wave left (B2), lane 0 of: 8, 9, 10 = time waves 1, 2, 3
+//                       11, 12, 13 = randomness waves 5, 6, 7 (time wave 0: slot 2; the regression
+//                       wave: 20 + 21 + 22) -- who is last there
 // XG: the design stays in global memory (L2) -- series too long for a copy in LDS beside the
 // randomness buffers (T > ~1500 with a dozen columns, every T > 2048).
 template <int D, int L, bool PROF = false, bool XG = false>
@@ -531,6 +604,8 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
     const int n_my = k_hi - k_lo;
     PF eprof;
     eprof.start(a.prof, a.prof != nullptr && blockIdx.x == 0 && wave == NW + 1 && lane == 0);
+    PF aprof;                                            // arrival at (Bs), every randomness wave
+    aprof.start(a.prof, a.prof != nullptr && blockIdx.x == 0 && lane == 0);
     auto normals_round = [&](int k, uint32_t it_for) __attribute__((always_inline)) {
       // the disturbances of the draw of iteration it_for; task-major: all chunks of a kind, then
       // the next kind
@@ -579,8 +654,16 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
       eprof.tick(30);
       __syncthreads();                                   // (B2)
       eprof.tick(31);
+      aprof.mark();
+      // With a short window (L <= 4) the time waves reach (Bs) long before the regression wave,
+      // and the gammas / flip randoms, issued behind a time wave on the same SIMD, arrive last:
+      // there they go first (the arrival stamps of the instrumented build).
+      // Longer windows are the critical path themselves and keep their priority.
+      if constexpr (L <= 4) __builtin_amdgcn_s_setprio(2);
       role_work(it + 1);
+      if constexpr (L <= 4) __builtin_amdgcn_s_setprio(0);
       eprof.tick(30);
+      aprof.tick(11 + e);
       __syncthreads();                                   // (Bs)
       eprof.tick(31);
       if (e == 2 && it < n_iter) {
@@ -637,19 +720,38 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
     float* o_w = a.out_weights;
     const int sched = (a.dbg & 0xFFFF) ? (a.dbg & 0xFFFF) : SCHED_DEFAULT;
     const int mode = sched & 3;
+    // What the serial section needs and the targets do not feed is formed outside it in the builds
+    // with registers to spare; the builds at 256 VGPRs (L >= 8), where the time waves' window and
+    // not this wave sets the pace, keep everything where it was.
+    constexpr bool HOIST = L <= 4;
+    const bool split = rhs_split<L>(P);
+    // constant of the series in the flip proposals (spike_slab_draw_regs' expression)
+    double logit_pi = 0.0;
+    if constexpr (HOIST)
+      logit_pi = (double)(__logf((float)sp.nonzero_prob) - __logf((float)(1.0 - sp.nonzero_prob)));
     for (int it = 0; it <= n_iter; ++it) {
       __syncthreads();                                   // (B1) targets in LDS
       // from here to sigma^2_obs this wave is the critical path of the iteration and shares its
       // SIMD with time wave 0, which has slack until (Bs): win the issue arbitration while it lasts
       __builtin_amdgcn_s_setprio(3);
       xt_sums_wave<L, 2, XG>(tgv, Xs, TPAD, P, 2 * wave, false, red, lane, T, xwide);
+      // this iteration's gamma variates are a whole iteration old (complete before (Bs) of the
+      // previous one, before the first (B1) for iteration 0): the reciprocal sigma^2_obs ends with
+      // is formed here, where this wave is ahead of the time waves' longer stretch to (B2)
+      const double* gm = gam + 4 * (it & 1);
+      double g_level, g_slope, g_obs, rg_obs = 0.0;
+      if constexpr (HOIST) {
+        g_level = gm[0]; g_slope = gm[1]; g_obs = gm[2];
+        rg_obs = fast_rcp(g_obs);
+        asm volatile("" : "+v"(rg_obs));                 // (here, not sunk to its use behind (B2))
+      }
       __syncthreads();                                   // (B2) all sums complete
       rprof.tick(16);
       const PreTables tb = pre_tables_at(pre_base, it);
-      if (lane < P + 1) R.bvec[lane] = (double)red[lane < P ? lane : RED_YTY];
+      if constexpr (!HOIST)
+        if (lane < P + 1) R.bvec[lane] = (double)red[lane < P ? lane : RED_YTY];
       const float wprev = lane < P ? wls[lane] : 0.f;    // the previous draw's weights (stored below)
-      const double* gm = gam + 4 * (it & 1);
-      const double g_level = gm[0], g_slope = gm[1], g_obs = gm[2];
+      if constexpr (!HOIST) { g_level = gm[0]; g_slope = gm[1]; g_obs = gm[2]; }
       const double emit_obs = obs_scale;
       rprof.tick(20);
       // sigma_obs(it) to the time waves -- and, on the replay route with no flip accepted in this
@@ -674,11 +776,14 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
       auto publish1 = [&](double ns) __attribute__((always_inline)) { (void)publish4(ns, 0.0, 0ull, false); };
       if (it < n_iter) {
         if (ps.valid && ps.S == pc.S) {
-          obs_scale = spike_slab_draw_pre(R, P, sp, obs_scale, g_obs, lane, pc, gam + 8 + 32 * (it & 1), tb,
-                                          ps, red, rprof, publish4);
+          obs_scale = spike_slab_draw_pre<HOIST>(R, P, sp, obs_scale, g_obs, rg_obs, logit_pi, split, lane,
+                                                 pc, gam + 8 + 32 * (it & 1), tb, ps, red, rprof, publish4);
         } else {
+          // only this route reads X~'targets and y'y from R.bvec (HOIST: written here)
           NoProf np;
-          wave_sync();                                   // R.bvec written above
+          if constexpr (HOIST)
+            if (lane < P + 1) R.bvec[lane] = (double)red[lane < P ? lane : RED_YTY];
+          wave_sync();
           obs_scale = spike_slab_draw_regs(R, P, sp, obs_scale, g_obs, rng, (uint32_t)it, lane, np, pc,
                                            gam + 8 + 32 * (it & 1), publish1);
         }
@@ -737,20 +842,20 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
       const int s_4 = mode == 1 ? n_sw + 2 : (mode == 2 ? 0 : (s_3 + p_4 < 1 + n_sw ? s_3 + p_4 : 1 + n_sw));
       const int s_5 = mode == 1 ? n_sw + 2 : (mode == 2 ? 0 : (1 + n_sw - p_a > s_4 ? 1 + n_sw - p_a : s_4));
       int step = 0;
-      for (; st.phase != 3 && step < s_3; ++step) pre_step(st, R, P, var_next, pc.S, lane, tbn, ps);
+      for (; st.phase != 3 && step < s_3; ++step) pre_step(st, R, P, var_next, pc.S, lane, tbn, ps, split);
       rprof.tick(19);
       __syncthreads();                                   // (B3) weights(it) published
       rprof.tick(17);
       after_b3();
-      for (; st.phase != 3 && step < s_4; ++step) pre_step(st, R, P, var_next, pc.S, lane, tbn, ps);
+      for (; st.phase != 3 && step < s_4; ++step) pre_step(st, R, P, var_next, pc.S, lane, tbn, ps, split);
       rprof.tick(19);
       __syncthreads();                                   // (B4)
       rprof.tick(29);
-      for (; st.phase != 3 && step < s_5; ++step) pre_step(st, R, P, var_next, pc.S, lane, tbn, ps);
+      for (; st.phase != 3 && step < s_5; ++step) pre_step(st, R, P, var_next, pc.S, lane, tbn, ps, split);
       rprof.tick(19);
       __syncthreads();                                   // (B5)
       rprof.tick(29);
-      for (; st.phase != 3; ++step) pre_step(st, R, P, var_next, pc.S, lane, tbn, ps);
+      for (; st.phase != 3; ++step) pre_step(st, R, P, var_next, pc.S, lane, tbn, ps, split);
       rprof.tick(19);
     }
     return;
@@ -785,6 +890,8 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
   float* o_traj = a.out_traj ? a.out_traj + chain_lin * a.S * T : nullptr;
   PF prof;
   prof.start(a.prof, a.prof != nullptr && blockIdx.x == 0 && tid == 0);
+  PF aprof;                                              // arrival at (Bs), time waves 1-3
+  aprof.start(a.prof, a.prof != nullptr && blockIdx.x == 0 && wave > 0 && lane == 0);
   for (int it = 0; it <= n_iter; ++it) {
     // ---- targets (they use the CURRENT level) to LDS; the last owned state for the neighbour
     {
@@ -837,6 +944,7 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
     const float so_prev = scal[SC_OBS_DK];
     __syncthreads();                                       // (B2)
     prof.tick(0);
+    aprof.mark();
 
     // ---- window: the normals of this iteration from LDS, emission of draw it-1, this iteration's
     // disturbance scales, first half of the prior-simulation scan
@@ -963,6 +1071,7 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
                          ((it - a.W) % a.progress_every == 0 || it - a.W == a.S);
     if (publish) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows are in L2
     prof.tick(2);
+    aprof.tick(7 + wave);
     __syncthreads();                                       // (Bs) sigma^2_obs(it) in LDS
     prof.tick(1);
     if (publish) {

@@ -44,7 +44,10 @@ def main():
         f"{plain * 1e3 / n_it:.2f} us/iteration")
   print(f"  kernel: {sess.kernel_name()}")
   top = cyc[:8].sum() + cyc[24:29].sum()
+  eight = "kernel8" in sess.kernel_name()
   for i, name in enumerate(SLOTS):
+    if eight and 8 <= i <= 13:
+      continue        # the eight-wave kernel keeps arrival times at (Bs) there: listed below
     print(f"  [{i:2d}] {name:34s} {cyc[i] / n_it:9.0f} cyc/iter  {100.0 * cyc[i] / top:5.1f} %")
   for i, name in ((24, "dk: matrix chunk (A, C, J)"), (25, "dk: matrix scan"), (26, "dk: matrix local pass"),
                   (27, "dk: forward chunk of the means"), (28, "dk: backward scan")):
@@ -77,6 +80,13 @@ def main():
     print("  randomness wave 5 (lane 0):")
     for i, name in ((30, "work"), (31, "waits at barriers")):
       print(f"  [{i:2d}] {name:52s} {cyc[i] / n_it:9.0f} cyc/iter")
+    print("  arrival at (Bs), cycles after leaving (B2) (lane 0 of each wave; the last one sets the pace):")
+    arrivals = [("[ 2] time wave 0", cyc[2]), ("[ 8] time wave 1", cyc[8]), ("[ 9] time wave 2", cyc[9]),
+                ("[10] time wave 3", cyc[10]), ("[20] + [21] + [22] regression wave", cyc[20] + cyc[21] + cyc[22]),
+                ("[11] randomness wave 5 (gammas)", cyc[11]), ("[12] randomness wave 6 (flip randoms)", cyc[12]),
+                ("[13] randomness wave 7 (x_0 normals)", cyc[13])]
+    for name, c in arrivals:
+      print(f"       {name:52s} {c / n_it:9.0f} cyc/iter")
 
 
 if __name__ == "__main__":
