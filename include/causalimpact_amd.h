@@ -376,6 +376,46 @@ int ci_session_summarize_predictions(ci_session* session, const double* scale, c
                                      int32_t num_ranks, const int32_t* ranks,
                                      double* forecast_mean, double* forecast_order,
                                      double* variance_mean, double* pit_mean, double* loglik);
+/* PLACEBO FORECASTS of every fit of a finished run, for all B series of the session at once: the
+ * treatment is pretended to begin at ORIGINS inside the observed series, and for every pooled draw n
+ * the sum of the next H_b observations is forecast without any update -- how a cumulative band of
+ * that length behaves where no effect exists.  Additive: CI_ABI_VERSION stays 5; look the symbol up
+ * (dlsym) where an older library may be met.  This is the FIXED-PARAMETER placebo: every draw's
+ * scales and weights are those of the one fit the session ran; nothing is refitted.
+ * The model, the state space, Z, T_t, Q_t, reg[n, t] and the initial moments of series b and draw n
+ * are those of ci_session_summarize_predictions above.  For an origin o and the horizon H_b >= 1 of
+ * the series, o + H_b <= T_b:
+ *   run that filter over t = 0 .. o - 1: (a, P) are the predicted moments of x_o given y[0 .. o - 1]
+ *   r = 0 (d components), V = 0, C = 0, A = 0, cnt = 0
+ *   for h = 0 .. H_b - 1, with t = o + h:
+ *     pz = P Z';   m = Z a
+ *     if mask[b, t] == 0 (sums ascending in h, from 0.0):
+ *       C += m + reg[n, t];   A += (double)y[b, t];   cnt += 1
+ *       V += (2 (Z r) + Z pz) + sigma_obs^2;   r += pz
+ *     if h + 1 < H_b:   a = T_t a;   r = T_t r;   P = T_t P T_t' + Q_t
+ * (r is Cov(S, x) of the running sum S: it transforms like a mean.)  C is the conditional mean of
+ * the sum of the counted observations, V its exact predictive variance for that draw, observation
+ * noise included.  Per (b, origin slot i, n):
+ *   SUM    = C * scale[b] + cnt * shift[b]                  (separate roundings)
+ *   SPREAD = ((V + (A - C)^2) * scale[b]) * scale[b]
+ *   PIT    = 0.5 * erfc(-(A - C) / sqrt(2 V))
+ * and 0 in all three where cnt == 0 or the slot is unused.
+ * scale, shift [B] as handed to ci_session_summarize; max_origins: O, the slots per series, in
+ * [1, T]; origins [B, O]: steps, strictly ascending, -1 = unused, the unused slots at the end of the
+ * row; horizon [B].  Outputs (host, caller-allocated, float64, each [B, O]; each may be NULL: it is
+ * then skipped and its matrix is not built -- what the others return does not change):
+ *   predicted_mean, spread_mean, pit_mean: the means over the N draws of SUM, SPREAD and PIT, as
+ *   ci_session_summarize_components takes its means.
+ * The predictive variance of the sum over the draws' mixture is spread_mean - e^2 with e the
+ * observed sum on the data scale minus predicted_mean.
+ * Sessions and models as ci_session_summarize_predictions; a ragged session uses each series' own
+ * length T_b.  The matrices [B * O, N] pass one after another through the scratch of
+ * ci_session_summarize.  Checked before any device call: the arguments but the outputs are not NULL,
+ * the block list, a finished ci_session_run, max_origins in [1, T], horizon >= 1, the origins
+ * ascending with -1 only at the end, o + H_b <= T_b. */
+int ci_session_summarize_placebo(ci_session* session, const double* scale, const double* shift,
+                                 int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                 double* predicted_mean, double* spread_mean, double* pit_mean);
 /* Per-draw totals over SUB-WINDOWS of the session's steps, for all B series at once: how an effect
  * unfolds inside the post-period (week 1 against week 4, a promotion's second phase), whose bands,
  * relative effect and tail-area probability need every draw's total over the window and are not

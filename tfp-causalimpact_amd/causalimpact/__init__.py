@@ -11,6 +11,7 @@ from causalimpact.causalimpact_lib import DataOptions
 from causalimpact.causalimpact_lib import fit_causalimpact
 from causalimpact.causalimpact_lib import InferenceOptions
 from causalimpact.causalimpact_lib import ModelOptions
+from causalimpact.causalimpact_lib import Placebo
 from causalimpact.causalimpact_lib import Seasons
 from causalimpact.indices import InputDateType
 from causalimpact.summary import summary

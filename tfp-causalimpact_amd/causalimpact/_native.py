@@ -22,6 +22,8 @@ COMPONENT_OUTPUTS = ("trend_mean", "trend_order", "seasonal_mean", "seasonal_ord
                      "weight_order")
 # the output arrays of ci_session_summarize_predictions, in argument order
 PREDICTION_OUTPUTS = ("forecast_mean", "forecast_order", "variance_mean", "pit_mean", "loglik")
+# the output arrays of ci_session_summarize_placebo, in argument order
+PLACEBO_OUTPUTS = ("predicted_mean", "spread_mean", "pit_mean")
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, "lib", "libcausalimpact_amd.so")
 
@@ -118,6 +120,9 @@ def load():
   if hasattr(L, "ci_session_summarize_predictions"):   # (additive: a library built before it lacks it)
     L.ci_session_summarize_predictions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                    C.c_void_p] + [C.c_void_p] * 5
+  if hasattr(L, "ci_session_summarize_placebo"):       # (additive, likewise)
+    L.ci_session_summarize_placebo.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                               C.c_void_p, C.c_void_p] + [C.c_void_p] * 3
   for name in ("ci_session_summarize_windows", "ci_ll_session_summarize_windows"):
     if hasattr(L, name):                               # (additive: a library built before it lacks it)
       getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
@@ -185,7 +190,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_algorithmic_bytes", "ci_session_kernel_name", "ci_session_destroy",
           "ci_session_profile", "ci_ll_session_kernel_name",
           "ci_session_summarize", "ci_session_summarize_components",
-          "ci_session_summarize_predictions", "ci_summarize_draws", "ci_summarize_draws_f64",
+          "ci_session_summarize_predictions", "ci_session_summarize_placebo", "ci_summarize_draws", "ci_summarize_draws_f64",
           "ci_session_summarize_windows", "ci_ll_session_summarize_windows",
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
           "ci_session_pool_event_trajectories",
@@ -769,6 +774,46 @@ class Session:
     arrs = {k: np.empty(v, np.float64) for k, v in shapes.items()}
     _check(fn(self._h, sc.ctypes.data, sh.ctypes.data, int(rk.size), rk.ctypes.data,
               *[_ptr(arrs.get(k)) for k in PREDICTION_OUTPUTS]))
+    return arrs
+
+  def summarize_placebo(self, scale, shift, origins, horizon, want=None) -> Dict[str, np.ndarray]:
+    """On-device placebo forecasts of every fit (ci_session_summarize_placebo): for every pooled draw
+    the filter of `summarize_predictions` up to each origin, then the forecast of the sum of the next
+    `horizon` observations without any update, in float64 (`causalimpact_lib._placebo_summary_host`
+    is the same definition in numpy).  scale, shift: scalars or [B], as for `summarize`; origins
+    [B, O] (or [O] for one series) int: steps, strictly ascending, -1 = unused, at the end of the
+    row; horizon: scalar or [B].  Returns float64 arrays [B, O]: predicted_mean, spread_mean,
+    pit_mean (0 in the unused slots and where the window counts no observation).  `want`: the names
+    to compute (default: all); the others are skipped on the device too."""
+    fn = getattr(self._lib, "ci_session_summarize_placebo", None)
+    if fn is None:
+      raise NativeError("the loaded library has no ci_session_summarize_placebo: rebuild it")
+    B = self.pb.num_series
+    org = np.asarray(origins)
+    if org.ndim == 1 and B == 1:
+      org = org[None]
+    if org.ndim != 2 or org.shape[0] != B:
+      raise ValueError(f"`origins` must be [{B}, O], got shape {org.shape}")
+    org = np.ascontiguousarray(org, dtype=np.int32)
+    hz = np.asarray(horizon)
+    if hz.shape not in ((), (B,)):
+      raise ValueError(f"`horizon` must be a scalar or have one entry per series ({B}), got shape {hz.shape}")
+    hz = np.ascontiguousarray(np.broadcast_to(hz, (B,)), dtype=np.int32)
+    sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
+    for name, a in (("scale", sc), ("shift", sh)):
+      if a.shape not in ((), (B,)):
+        raise ValueError(f"`{name}` must be a scalar or have one entry per series ({B}), got shape {a.shape}")
+    sc = np.ascontiguousarray(np.broadcast_to(sc, (B,)))
+    sh = np.ascontiguousarray(np.broadcast_to(sh, (B,)))
+    names = PLACEBO_OUTPUTS
+    if want is not None:
+      unknown = [k for k in want if k not in PLACEBO_OUTPUTS]
+      if unknown:
+        raise ValueError(f"unknown placebo outputs {unknown}: choose from {list(PLACEBO_OUTPUTS)}")
+      names = [k for k in PLACEBO_OUTPUTS if k in want]
+    arrs = {k: np.empty(org.shape, np.float64) for k in names}
+    _check(fn(self._h, sc.ctypes.data, sh.ctypes.data, int(org.shape[1]), org.ctypes.data,
+              hz.ctypes.data, *[_ptr(arrs.get(k)) for k in PLACEBO_OUTPUTS]))
     return arrs
 
   def summarize_windows(self, scale, shift, observed, first, count, ranks,

@@ -340,6 +340,8 @@ _DRAW_SCALARS = ("observation_noise_scale", "level_scale")
 _PER_DRAW = ("per_draw", "per_draw_order")
 _PER_COLUMN = ("inclusion_prob", "weight_mean", "weight_order")
 _PER_DRAW_LOGLIK = ("loglik",)       # of the prediction summary: [B, draws]
+# the placebo summary: [B, O] each, none over time (`lib._placebo_summary_host`, `lib._placebo_seen`)
+_PLACEBO = ("predicted_mean", "spread_mean", "pit_mean", "n_counted", "seen_sum")
 # the parameter draws the prediction errors are filtered from (`lib._prediction_summary_host`)
 _PARAMETER_DRAWS = ("observation_noise_scale", "level_scale", "slope_scale", "seasonal_drift_scales",
                     "weights")
@@ -357,8 +359,13 @@ class CausalImpactBatchAnalysis:
   when more than one chain was run."""
 
   def __init__(self, prepared, names, alpha, posterior_means, device_summary, ranks, columns,
-               diagnostic_draws, component_summary=None, prediction_summary=None, state_dim=0):
+               diagnostic_draws, component_summary=None, prediction_summary=None, state_dim=0,
+               placebo_summary=None):
     self._prep, self._names, self.alpha = prepared, list(names), alpha
+    # `placebo=`: dict(summary {name: [B, O]} of `_PLACEBO`, origins [B, O] (-1: unused), horizon [B],
+    # n_post [B]), or None
+    self._placebo = placebo_summary
+    self._placebo_quality: Optional[pd.DataFrame] = None
     # {name: [B, ...]} of ci_session_summarize_components (InferenceOptions.components), or None
     self._csum = component_summary
     # {name: [B, ...]} of ci_session_summarize_predictions (InferenceOptions.prediction_errors), or
@@ -450,8 +457,39 @@ class CausalImpactBatchAnalysis:
       self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b),
                                                 *self._component_frames(b, ci_data, Tb),
                                                 *self._prediction_frames(b, ci_data, Tb),
-                                                self._window_slice(b))
+                                                self._window_slice(b),
+                                                *self._placebo_frames(b, ci_data, Tb, summary))
     return self._cache[b]
+
+  def _placebo_frames(self, b: int, ci_data, num_steps: int, summary: pd.DataFrame):
+    """(placebo, placebo_quality) of series b, or (None, None) when they were not asked for."""
+    if self._placebo is None:
+      return None, None
+    pl = self._placebo
+    return lib._placebo_frames(                                 # pylint: disable=protected-access
+        {k: v[b] for k, v in pl["summary"].items()}, pl["origins"][b], int(pl["horizon"][b]), self.alpha,
+        self._prep.observed[b, :num_steps], lib.posterior_processing.model_index(ci_data),
+        int(pl["n_post"][b]), summary.loc["cumulative", "rel_effect"])
+
+  @property
+  def placebo_quality(self) -> Optional[pd.DataFrame]:
+    """One row per series with the entries of `CausalImpactAnalysis.placebo_quality` (None without
+    `placebo=`): which cumulative bands of the batch to trust at the post-period's horizon.  A
+    series of a panel whose pre-period has no room for an origin has n_origins 0 and NaN."""
+    if self._placebo is None:
+      return None
+    if self._placebo_quality is None:
+      pl, rows = self._placebo, []
+      rel = self.summary["rel_effect"].to_numpy()[1::2]          # (the cumulative rows)
+      for b in range(len(self)):
+        H, cols = int(pl["horizon"][b]), None
+        if np.any(pl["origins"][b] >= 0):
+          cols = lib._placebo_columns(                          # pylint: disable=protected-access
+              {k: v[b] for k, v in pl["summary"].items()}, pl["origins"][b], H, self.alpha,
+              self._prep.observed[b, :self._series_view(b)[3]])
+        rows.append(lib._placebo_quality(cols, H, self.alpha, int(pl["n_post"][b]), rel[b]))   # pylint: disable=protected-access
+      self._placebo_quality = pd.DataFrame(rows, index=pd.Index(self._names, name="series"))
+    return self._placebo_quality
 
   def _prediction_inputs(self, b: int, num_steps: int):
     """(summary, observed, conditioned) of series b over its `num_steps` steps."""
@@ -517,6 +555,13 @@ class PerSeriesBatchAnalysis(CausalImpactBatchAnalysis):
     if any(a.fit_quality is None for a in self._cache.values()):
       return None
     return pd.DataFrame([self._cache[b].fit_quality for b in range(len(self))],
+                        index=pd.Index(self._names, name="series"))
+
+  @property
+  def placebo_quality(self) -> Optional[pd.DataFrame]:
+    if any(a.placebo_quality is None for a in self._cache.values()):
+      return None
+    return pd.DataFrame([self._cache[b].placebo_quality for b in range(len(self))],
                         index=pd.Index(self._names, name="series"))
 
   def diagnostics_of(self, b: int):
@@ -1279,7 +1324,8 @@ def _frames_outcome_first(data, data_options):
 def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_options, model_options,
                     inference_options, shared_streams, aggregates=None,
                     event_aggregates: Optional[EventPlan] = None,
-                    windows: Optional[WindowPlan] = None, series_windows=None) -> PerSeriesBatchAnalysis:
+                    windows: Optional[WindowPlan] = None, series_windows=None,
+                    placebo=None, placebo_lenient: bool = False) -> PerSeriesBatchAnalysis:
   """`fit_causalimpact` on every series in turn: the routes the one-launch path does not have.
   float64 compute (csrc/ci_gibbs64.h) and raw-scale outcomes (their per-series internal
   conditioning, causalimpact_lib._internal_conditioning) exist on the single-series path, and so do
@@ -1301,7 +1347,10 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
   windows, series_windows (`effect_windows`): the `WindowPlan` and, per series, the `effect_windows`
   its own `fit_causalimpact` takes (a panel: the windows it covers, as positions into its index; None
   for a series that covers none).  `window_summary` stacks the fits' own tables, NaN rows for the
-  windows a series does not cover."""
+  windows a series does not cover.
+
+  placebo: the `placebo=` every fit takes; placebo_lenient (panels): a series whose pre-period has
+  no room for an origin gets an empty `placebo` frame and a NaN quality row instead of a ValueError."""
   opts = dataclasses.replace(data_options, outcome_column=outcome_column)
   base_seed = lib._sanitize_seed(seed)   # pylint: disable=protected-access
   analyses = []
@@ -1315,13 +1364,16 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
     seed_b = base_seed if shared_streams else _native.series_stream_key(base_seed, b)
     if host_pool is not None:
       extra = dict(_trajectory_sink=lambda *a, b=b: host_pool.add(b, *a))
+    if placebo is not None:
+      extra = dict(extra, placebo=placebo, _placebo_lenient=placebo_lenient)
     one = lib.fit_causalimpact(frame, periods[b][0], periods[b][1], alpha=alpha, seed=seed_b,
                                data_options=opts, model_options=model_options,
                                inference_options=inference_options,
                                effect_windows=None if series_windows is None else series_windows[b],
                                **extra)
     analyses.append(dataclasses.replace(one, posterior_samples=None,   # (draws are not kept)
-                                        window_summary=one.window_summary))
+                                        window_summary=one.window_summary, placebo=one.placebo,
+                                        placebo_quality=one.placebo_quality))
   res = PerSeriesBatchAnalysis(names, alpha, analyses)
   if windows is not None:
     full = pd.MultiIndex.from_product([windows.names, ["average", "cumulative"]], names=["window", None])
@@ -1369,6 +1421,10 @@ class _Fit:
   own_shift: Optional[np.ndarray] = None
   # `effect_windows=` only: the resolved windows, every series' own first / count [B, W]
   windows: Optional[WindowPlan] = None
+  # `placebo=` only: every series' origins [B, O] (model steps ascending, -1: unused, at the end)
+  # and horizon [B] (`placebo_plans`); the summary is put on the data scale with own_scale / own_shift
+  placebo_origins: Optional[np.ndarray] = None
+  placebo_horizon: Optional[np.ndarray] = None
 
 
 def _sampler_outcome(prep, data_options) -> np.ndarray:
@@ -1377,11 +1433,11 @@ def _sampler_outcome(prep, data_options) -> np.ndarray:
 
 
 def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_options,
-             shared_streams, windows: Optional[WindowPlan] = None) -> _Fit:
+             shared_streams, windows: Optional[WindowPlan] = None, placebo=None) -> _Fit:
   """The `_Fit` of a prepared batch or panel: y = `_sampler_outcome(prep)`, lengths [B], pre_sd [B]
-  the sd of every series' own pre-period outcome."""
+  the sd of every series' own pre-period outcome; placebo: (origins [B, O], horizon [B]) or None."""
   own_shift = own_scale = None
-  if inference_options.prediction_errors:
+  if inference_options.prediction_errors or placebo is not None:
     if isinstance(prep, PreparedPanel):
       stats = [scaler_stats(prep.raw[b][prep.model_rows[b][:nb], 0][None])
                for b, nb in enumerate(prep.num_pre)]
@@ -1401,7 +1457,64 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
               ranks=lib._summary_ranks(num_draws, (alpha / 2.0, 1.0 - alpha / 2.0)),   # pylint: disable=protected-access
               seed=lib._sanitize_seed(seed), shared_streams=shared_streams,   # pylint: disable=protected-access
               model_options=model_options, inference_options=inference_options,
-              own_scale=own_scale, own_shift=own_shift, windows=windows)
+              own_scale=own_scale, own_shift=own_shift, windows=windows,
+              placebo_origins=None if placebo is None else placebo[0],
+              placebo_horizon=None if placebo is None else placebo[1])
+
+
+def placebo_plans(placebo: lib.Placebo, num_pre, num_post, state_dim: int):
+  """(origins [B, O] int32 -- -1: unused, at the end of a row; O at least 1 --, horizon [B] int32) of
+  B series from their pre- and post-period step counts: `lib.placebo_plan` of every series.  A
+  series whose pre-period has no room for an origin has a row of -1."""
+  plans = [lib.placebo_plan(placebo, int(a), int(b), state_dim) for a, b in zip(num_pre, num_post)]
+  width = max(1, max(len(o) for _, o in plans))
+  origins = np.full((len(plans), width), -1, np.int32)
+  for b, (_, o) in enumerate(plans):
+    origins[b, :len(o)] = o
+  return origins, np.array([h for h, _ in plans], np.int32)
+
+
+def _placebo_seen_rows(fit: _Fit, ids, plsum: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+  """`plsum` {name: [n, O]} of the series `ids` with `lib._placebo_seen`'s n_counted and seen_sum."""
+  seen = [lib._placebo_seen(                                    # pylint: disable=protected-access
+      np.where(fit.mask[b], 0.0, fit.y[b]).astype(np.float32), fit.mask[b], fit.placebo_origins[b],
+      fit.placebo_horizon[b], fit.own_scale[b], fit.own_shift[b]) for b in (int(b) for b in ids)]
+  return dict(plsum, n_counted=np.stack([c for c, _ in seen]), seen_sum=np.stack([a for _, a in seen]))
+
+
+def _device_placebo(sess, fit: _Fit, ids) -> Dict[str, np.ndarray]:
+  """The placebo summary {name: [n, O]} of the series `ids` from their open session
+  (`summarize_placebo`): the launch's own origin slots (never more than its steps), the horizon of a
+  series without origin raised to the 1 the entry asks for."""
+  org = fit.placebo_origins[ids]
+  width = max(1, int((org >= 0).sum(axis=1).max()))
+  got = sess.summarize_placebo(fit.own_scale[ids], fit.own_shift[ids], org[:, :width],
+                               np.maximum(fit.placebo_horizon[ids], 1))
+  out = {k: np.zeros(org.shape) for k in got}
+  for k, v in got.items():
+    out[k][:, :width] = v
+  return _placebo_seen_rows(fit, ids, out)
+
+
+def _host_placebo(fit: _Fit, ids, draws: Dict[str, np.ndarray], season_change) -> Dict[str, np.ndarray]:
+  """The same in numpy (`lib._placebo_summary_host`) from the launch's parameter draws
+  {name: [n, C, S, ...]}: the routes whose models the device filter does not take."""
+  mo = fit.model_options
+  num_seasons = _model.expand_seasons(mo.seasons, 1)[0]
+  out = {k: np.zeros((len(ids), fit.placebo_origins.shape[1])) for k in _PLACEBO[:3]}
+  for i, b in enumerate(int(b) for b in ids):
+    if not np.any(fit.placebo_origins[b] >= 0):
+      continue
+    Tb = int(fit.lengths[b])
+    pooled = {k: v[i].reshape((v.shape[1] * v.shape[2],) + v.shape[3:]) for k, v in draws.items()}
+    one = lib._placebo_summary_host(                            # pylint: disable=protected-access
+        np.where(fit.mask[b, :Tb], 0.0, fit.y[b, :Tb]).astype(np.float32), fit.mask[b, :Tb],
+        None if fit.design is None else fit.design[b, :Tb].astype(np.float32),
+        np.asarray(season_change)[:, :Tb], num_seasons, mo.local_linear_trend, fit.params[b], pooled,
+        fit.own_scale[b], fit.own_shift[b], fit.placebo_origins[b], fit.placebo_horizon[b])
+    for k, v in one.items():
+      out[k][i] = v
+  return _placebo_seen_rows(fit, ids, out)
 
 
 def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None):
@@ -1415,11 +1528,13 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
                        series starts at its own step 0) and the stride rounded up to a multiple of 4
                        (every row 16-byte aligned), the padding as in `PreparedPanel`: y NaN, mask
                        True, design 0, observed NaN, flags 0.
-  Returns (out, dsum, csum, psum, wsum): `fetch` of posterior_means [n, C, T] and `_DRAW_SCALARS` [n, C, S],
+  Returns (out, dsum, csum, psum, wsum, plsum): `fetch` of posterior_means [n, C, T] and `_DRAW_SCALARS` [n, C, S],
   `summarize`, `summarize_components` (None unless InferenceOptions.components) and the prediction
   summary (None unless InferenceOptions.prediction_errors): `summarize_predictions` for the block
   lists the device takes, `_host_predictions` from the fetched parameter draws for the others;
-  wsum `summarize_windows` with every series' own windows (None unless `effect_windows`).  Every
+  wsum `summarize_windows` with every series' own windows (None unless `effect_windows`); plsum
+  the placebo summary (None unless `placebo=`), routed like the prediction summary:
+  `_device_placebo` or `_host_placebo`.  Every
   array keeps the series axis, and T is the longest series of the launch on every route.
   chain (aggregates of a batch, event-time aggregates of a panel): the launch's pool step runs after
   `summarize`, the session still open."""
@@ -1470,6 +1585,11 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
     if fit.windows is not None:
       wsum = sess.summarize_windows(scale, shift, observed, fit.windows.first[ids],
                                     fit.windows.count[ids], fit.ranks)
+    plsum = None
+    if fit.placebo_origins is not None and lib.device_predictions_supported(num_seasons):
+      plsum = _device_placebo(sess, fit, ids)
+    elif fit.placebo_origins is not None:
+      plsum = _host_placebo(fit, ids, sess.fetch(list(_PARAMETER_DRAWS)), season_change)
     if chain is not None:
       chain.step(launch, chain.session_pool(sess, scale, shift))
   finally:
@@ -1478,7 +1598,7 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
     out, dsum = _cut(out, T, _DRAW_SCALARS), _cut(dsum, T, _PER_DRAW)
     csum = None if csum is None else _cut(csum, T, _PER_COLUMN)
     psum = None if psum is None else _cut(psum, T, _PER_DRAW_LOGLIK)
-  return out, dsum, csum, psum, wsum
+  return out, dsum, csum, psum, wsum, plsum
 
 
 def _host_predictions(fit: _Fit, ids, num_steps: int, draws: Dict[str, np.ndarray],
@@ -1514,8 +1634,8 @@ def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None):
   """`_run_launch` for the one-launch HMC path (`_hmc.fit_hmc_batch`: B x chains HMC chains, then
   the latent paths, the predictive trajectories and their summary on the device): consecutive
   positions of a batch, series b keyed by positions[0] + b.  It keeps no latent draws, hence no
-  component summary; the prediction summary is `_host_predictions` from the parameter draws, which
-  it fetches for that; the window totals are `BatchLogLikSession.summarize_windows`, taken while the
+  component summary; the prediction summary is `_host_predictions` and the placebo summary
+  `_host_placebo` from the parameter draws, which it fetches for them; the window totals are `BatchLogLikSession.summarize_windows`, taken while the
   fit is resident."""
   from causalimpact import _hmc  # pylint: disable=import-outside-toplevel
   dev, _, ids = launch
@@ -1539,12 +1659,18 @@ def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None):
       summary=dict(scale=scale, shift=shift, observed=fit.observed[ids],
                    flags=fit.flags, ranks=fit.ranks),
       after_summary=after_summary if chain is not None or fit.windows is not None else None,
-      also_fetch=("slope_scale", "weights") if io.prediction_errors else ())
+      also_fetch=("slope_scale", "weights")
+      if io.prediction_errors or fit.placebo_origins is not None else ())
   psum = None
   if io.prediction_errors:
     draws = {k: res[k] for k in _PARAMETER_DRAWS if k in res}
     psum = _host_predictions(fit, ids, fit.y.shape[1], draws, np.zeros((0, fit.y.shape[1]), np.uint8))
-  return {k: res[k] for k in ("posterior_means", *_DRAW_SCALARS)}, res["summary"], None, psum, wsum or None
+  plsum = None
+  if fit.placebo_origins is not None:
+    draws = {k: res[k] for k in _PARAMETER_DRAWS if k in res}
+    plsum = _host_placebo(fit, ids, draws, np.zeros((0, fit.y.shape[1]), np.uint8))
+  return ({k: res[k] for k in ("posterior_means", *_DRAW_SCALARS)}, res["summary"], None, psum,
+          wsum or None, plsum)
 
 
 def _scatter(parts, num_series: int, num_steps: int, whole, fill) -> Dict[str, np.ndarray]:
@@ -1576,6 +1702,8 @@ def _assemble(launches, run, num_series: int, num_steps: int):
     psum              (only when `run` returns four values) the prediction summary {name: [B, ...]}
                       likewise (loglik has no time axis), or None;
     wsum              (only when `run` returns five values) the window totals {name: [B, W, ...]} (no
+                      time axis), or None;
+    plsum             (only when `run` returns six values) the placebo summary {name: [B, O]} (no
                       time axis), or None.
   One launch that holds all B series in order at full stride is the result as it stands: its blocks
   (512 series: 24 MB of summary in pinned memory) are not copied a second time."""
@@ -1591,7 +1719,7 @@ def _assemble(launches, run, num_series: int, num_steps: int):
       return _scatter(parts, num_series, num_steps, whole, fill)
     fetched, dsum = gather(0, _DRAW_SCALARS, 0), gather(1, _PER_DRAW, np.nan)
     optional = [None if one is None else gather(2 + i, whole, np.nan)
-                for i, (one, whole) in enumerate(zip(optional, (_PER_COLUMN, _PER_DRAW_LOGLIK, _PER_DRAW)))]
+                for i, (one, whole) in enumerate(zip(optional, (_PER_COLUMN, _PER_DRAW_LOGLIK, _PER_DRAW, _PLACEBO)))]
   means = fetched.pop("means")
   diag_draws = fetched if fetched[_DRAW_SCALARS[0]].shape[1] > 1 else None
   return (means, dsum, diag_draws, *optional)
@@ -1605,7 +1733,8 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
                            index: Optional[pd.Index] = None,
                            names: Optional[Sequence[Any]] = None,
                            shared_streams: bool = False,
-                           aggregates=None, effect_windows=None) -> CausalImpactBatchAnalysis:
+                           aggregates=None, effect_windows=None,
+                           placebo=None) -> CausalImpactBatchAnalysis:
   """`fit_causalimpact` for B series at once.
 
   data: a sequence of DataFrames with identical index and column layout (outcome first, or
@@ -1675,9 +1804,19 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   `aggregates` also `aggregate_window_summary` (aggregate, window, average|cumulative) from the
   pooled draws.  ValueError before any fit, naming the window, for one that leaves the post-period or
   holds no row.  None: both attributes are None and nothing runs.
+
+  placebo: None (the default: nothing runs, no result differs), True or a `lib.Placebo` -- the
+  fixed-parameter placebo check of `fit_causalimpact` for every series: `result[b].placebo`,
+  `result[b].placebo_quality`, and `result.placebo_quality` as one table with a row per series, the
+  companion of `fit_quality` at the horizon of the post-period.  Forecast on the device that holds
+  the draws (csrc/ci_placebo.h) inside every launch; in numpy on the routes `prediction_errors`
+  takes in numpy.  ValueError before any fit when the pre-period has no room for an origin.
   """
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
+  placebo = lib.resolve_placebo(placebo)
+  pl_dim = None if placebo is None else lib.placebo_state_dim(model_options.local_linear_trend,
+                                                              model_options.seasons)
   if isinstance(data, np.ndarray):
     values = np.asarray(data, np.float64)
     index = pd.RangeIndex(values.shape[1]) if index is None else pd.Index(index)
@@ -1716,13 +1855,21 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     return _fit_per_series((pd.DataFrame(values[b], index=index, columns=columns) for b in range(B)),
                            [(pre_period, post_period)] * B, names, columns[0], alpha, seed,
                            data_options, model_options, inference_options, shared_streams, agg,
-                           windows=plan, series_windows=None if plan is None else [effect_windows] * B)
+                           windows=plan, series_windows=None if plan is None else [effect_windows] * B,
+                           placebo=placebo)
   plan = None if effect_windows is None else batch_windows(effect_windows, prep)
+  pl_plan = pl_post = None
+  if placebo is not None:
+    pl_post = np.full(B, int(np.count_nonzero(prep.flags & 2)))
+    pl_plan = placebo_plans(placebo, [prep.num_pre] * B, pl_post, pl_dim)
+    if not np.any(pl_plan[0] >= 0):
+      raise ValueError(f"placebo: a pre-period of {prep.num_pre} steps has no room for an origin with "
+                       f"horizon {int(pl_plan[1][0])} and the history it needs")
   y = _sampler_outcome(prep, data_options)
   with np.errstate(invalid="ignore"):
     pre_sd = np.nanstd(y[:, :prep.num_pre], axis=1, ddof=1)
   fit = _new_fit(prep, y, np.full(B, T), pre_sd, alpha, seed, model_options, inference_options,
-                 shared_streams, plan)
+                 shared_streams, plan, pl_plan)
   # a batch is the panel of one group of equal lengths: consecutive positions on every device
   launches = panel_launches(dict(route="equal_length", groups=[(T, list(range(B)))]),
                             inference_options.devices, shared_streams)
@@ -1738,10 +1885,13 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     run = lambda launch: _run_hmc_launch(launch, fit, chain)          # pylint: disable=unnecessary-lambda-assignment
   else:
     run = lambda launch: _run_launch(launch, "ordinary", fit, chain)   # pylint: disable=unnecessary-lambda-assignment
-  means, dsum, diag_draws, csum, psum, wsum = _assemble(
+  means, dsum, diag_draws, csum, psum, wsum, plsum = _assemble(
       launches, run if chain is None else chain.guarded(run), B, T)
-  res = CausalImpactBatchAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
-                                  csum, psum, _state_dim(model_options, inference_options))
+  res = CausalImpactBatchAnalysis(
+      prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws, csum, psum,
+      _state_dim(model_options, inference_options),
+      None if placebo is None else dict(summary=plsum, origins=pl_plan[0], horizon=pl_plan[1],
+                                        n_post=pl_post))
   if plan is not None:
     res.window_summary = _window_summary(res, plan, wsum)
   if chain is not None:
@@ -1774,7 +1924,8 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
                            inference_options: Optional[lib.InferenceOptions] = None,
                            names: Optional[Sequence[Any]] = None,
                            shared_streams: bool = False,
-                           event_aggregates=None, effect_windows=None) -> CausalImpactBatchAnalysis:
+                           event_aggregates=None, effect_windows=None,
+                           placebo=None) -> CausalImpactBatchAnalysis:
   """`fit_causalimpact` for a PANEL: B series with the same columns (outcome first, or
   `DataOptions.outcome_column`; the same covariates), each with its own index, its own length and
   its own (pre_period, post_period) -- staggered roll-outs, units that enter the data on different
@@ -1839,9 +1990,16 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   `fit_causalimpact_batch`; a series whose post-period does not reach tau_last has NaN rows for that
   window, and a window that no series covers is a ValueError before any fit.  With
   `event_aggregates` also `aggregate_window_summary`, the windows taken on every group's own axis
-  (NaN rows where its post-period, the shortest of its members', does not cover them)."""
+  (NaN rows where its post-period, the shortest of its members', does not cover them).
+
+  placebo: as in `fit_causalimpact_batch`, every series with the horizon and the origins of its OWN
+  pre- and post-period.  A series whose pre-period has no room for an origin has an empty
+  `placebo` frame and a NaN row (n_origins 0) in `placebo_quality` -- no error."""
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
+  placebo = lib.resolve_placebo(placebo)
+  pl_dim = None if placebo is None else lib.placebo_state_dim(model_options.local_linear_trend,
+                                                              model_options.seasons)
   frames, columns = _frames_outcome_first(data, data_options)
   B = len(frames)
   periods = list(periods)
@@ -1874,8 +2032,12 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
              for b in range(B)]
     return _fit_per_series(frames, periods, names, columns[0], alpha, seed, data_options,
                            model_options, inference_options, shared_streams, event_aggregates=plan,
-                           windows=wplan, series_windows=own)
+                           windows=wplan, series_windows=own, placebo=placebo, placebo_lenient=True)
   prep = prepare_panel([f[columns] for f in frames], periods, names=names)
+  pl_plan = pl_post = None
+  if placebo is not None:
+    pl_post = np.array([np.count_nonzero(prep.flags[b, :Tb] & 2) for b, Tb in enumerate(prep.lengths)])
+    pl_plan = placebo_plans(placebo, prep.num_pre, pl_post, pl_dim)
   plan = None if agg is None else event_plan(*agg, prep, columns[0])
   wplan = None if effect_windows is None else panel_windows(effect_windows, prep)
   route = panel_route(float64=False, standardize_data=True, sampler="gibbs",
@@ -1886,15 +2048,18 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   with np.errstate(invalid="ignore"):
     pre_sd = [np.nanstd(y[b, :nb], ddof=1) for b, nb in enumerate(prep.num_pre)]
   fit = _new_fit(prep, y, prep.lengths, pre_sd, alpha, seed, model_options, inference_options,
-                 shared_streams, wplan)
+                 shared_streams, wplan, pl_plan)
   kind = "ordinary" if route["route"] == "equal_length" else route["route"]
   launches = panel_launches(route, inference_options.devices, shared_streams)
   chain = None if plan is None else _PoolChain(launches, plan.csr, plan.axes)
   run = lambda launch: _run_launch(launch, kind, fit, chain)   # pylint: disable=unnecessary-lambda-assignment
-  means, dsum, diag_draws, csum, psum, wsum = _assemble(
+  means, dsum, diag_draws, csum, psum, wsum, plsum = _assemble(
       launches, run if chain is None else chain.guarded(run), B, prep.y.shape[1])
-  res = CausalImpactPanelAnalysis(prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws,
-                                  csum, psum, _state_dim(model_options, inference_options))
+  res = CausalImpactPanelAnalysis(
+      prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws, csum, psum,
+      _state_dim(model_options, inference_options),
+      None if placebo is None else dict(summary=plsum, origins=pl_plan[0], horizon=pl_plan[1],
+                                        n_post=pl_post))
   if wplan is not None:
     res.window_summary = _window_summary(res, wplan, wsum)
   if chain is not None:

@@ -123,10 +123,26 @@ class CausalImpactAnalysis:
   # `effect_windows=` only: the 15 columns of `summary` for every sub-window of the post-period,
   # indexed by (window, average|cumulative).  (Init-only and kept as a plain attribute, as the two above.)
   window_summary: dataclasses.InitVar[Optional[pd.DataFrame]] = None
+  # `placebo=` only (see `Placebo`).  `placebo`: one row per placebo origin, indexed by the origin's
+  # label on the series' index, with the `PLACEBO_COLUMNS`: horizon_end (the label of the window's
+  # last step), n_counted (observed steps of the window), actual (the sum of the data over them),
+  # predicted (the forecast of that sum from the origin without any update, mean over the draws),
+  # predicted_sd (root of the mixture's predictive variance, observation noise included), effect,
+  # relative_effect, pit (the mixture-predictive CDF at the actual sum), p = 2 min(pit, 1 - pit) and
+  # significant (pit outside [alpha/2, 1 - alpha/2]).  `placebo_quality`: the `PLACEBO_QUALITY_ENTRIES`
+  # n_origins, horizon, false_positive_rate (nominal alpha), mean_relative_effect, mde_relative (the
+  # 1 - alpha quantile of |relative_effect|: the smallest relative effect the data could tell from
+  # noise at this horizon) and empirical_p (the rank of the fit's cumulative relative effect among
+  # the placebo ones; NaN unless the horizon is the post-period's).  The windows OVERLAP: the
+  # origins are not independent trials.  (Init-only and kept as plain attributes, as those above.)
+  placebo: dataclasses.InitVar[Optional[pd.DataFrame]] = None
+  placebo_quality: dataclasses.InitVar[Optional[pd.Series]] = None
 
-  def __post_init__(self, prediction_errors, fit_quality, window_summary=None):
+  def __post_init__(self, prediction_errors, fit_quality, window_summary=None, placebo=None,
+                    placebo_quality=None):
     self.prediction_errors, self.fit_quality = prediction_errors, fit_quality
     self.window_summary = window_summary
+    self.placebo, self.placebo_quality = placebo, placebo_quality
 
 
 @dataclasses.dataclass
@@ -204,6 +220,7 @@ def fit_causalimpact(data: pd.DataFrame,
                      model_options: Optional[ModelOptions] = None,
                      inference_options: Optional[InferenceOptions] = None,
                      effect_windows=None,
+                     placebo=None,
                      **kwargs) -> CausalImpactAnalysis:
   """Fits the CausalImpact model and summarises the effect (reference :223-339).
 
@@ -215,7 +232,20 @@ def fit_causalimpact(data: pd.DataFrame,
   window (csrc/ci_windows.h on the GPU that holds the draws; `_native.window_totals_host` on the
   routes that pool them on the host).  ValueError, before any fit and with the window named, for a
   window that leaves the post-period or contains no model row.  None (the default): `window_summary`
-  is None and nothing runs."""
+  is None and nothing runs.
+
+  placebo (extension): None (the default: nothing runs, no result differs), True or a `Placebo`.
+  The treatment is pretended to begin at several earlier dates inside the pre-period and the model
+  forecasts a post-period's length from each without updating: the result then has `placebo` (one row
+  per origin) and `placebo_quality` (false-positive rate, the minimal detectable relative effect, the
+  empirical p-value of the fit's cumulative effect) -- whether a cumulative band of that length can
+  be trusted.  This is the FIXED-PARAMETER placebo: every draw's scales and weights come from the one
+  fit of the whole pre-period, nothing is refitted, which makes the check cheap and somewhat
+  optimistic; the windows overlap, so the origins are not independent trials.  On the GPU that holds
+  the draws wherever the predictive summary runs there (csrc/ci_placebo.h), in numpy from the
+  parameter draws on the other routes, exactly as `InferenceOptions.prediction_errors`.  ValueError
+  before any fit when the pre-period has no room for one origin, or the state has more than
+  `PREDICTION_MAX_STATE` components."""
   data_options = data_options if data_options is not None else DataOptions()
   model_options = model_options if model_options is not None else ModelOptions()
   inference_options = inference_options if inference_options is not None else InferenceOptions()
@@ -225,6 +255,8 @@ def fit_causalimpact(data: pd.DataFrame,
   #  series) called with (posterior_means [T], posterior_trajectories [draws, T], scale, shift):
   #  data-scale value = array * scale + shift
   trajectory_sink = kwargs.pop("_trajectory_sink", None)
+  # (internal, batch.py: a panel's series without room for a placebo origin gets the NaN row)
+  placebo_lenient = kwargs.pop("_placebo_lenient", False)
   if kwargs:
     raise TypeError(f"Received unknown {kwargs=}")
   if experimental_model is not None:
@@ -256,6 +288,19 @@ def fit_causalimpact(data: pd.DataFrame,
     base = request if request is not None else _device_summary_request(ci_data, alpha)
     pred_request = dict(scale=base["scale"], shift=base["shift"], quantiles=base["quantiles"],
                         observed=base["observed"])
+  placebo_request = None
+  placebo = resolve_placebo(placebo)
+  if placebo is not None:
+    base = request if request is not None else _device_summary_request(ci_data, alpha)
+    n_post = int(np.count_nonzero(base["flags"] & 2))
+    n_pre = base["flags"].shape[0] - ci_data.model_after_pre_data.shape[0]
+    horizon, origins = placebo_plan(
+        placebo, n_pre, n_post, placebo_state_dim(model_options.local_linear_trend, model_options.seasons))
+    if origins.size == 0 and not placebo_lenient:
+      raise ValueError(f"placebo: a pre-period of {n_pre} steps has no room for an origin with "
+                       f"horizon {horizon} and the history it needs")
+    if origins.size:
+      placebo_request = dict(scale=base["scale"], shift=base["shift"], origins=origins, horizon=horizon)
   samples, posterior_means, posterior_trajectories, device_summary = _run_sampler(
       ci_data=ci_data, prior_level_sd=model_options.prior_level_sd, seed=seed,
       num_results=inference_options.num_results,
@@ -265,7 +310,8 @@ def fit_causalimpact(data: pd.DataFrame,
       sampler=inference_options.sampler, summary_request=request,
       hmc_init=inference_options.hmc_init, hmc_prior=inference_options.hmc_prior,
       kernel_flags=inference_options.kernel_flags, component_request=comp_request,
-      keep_trajectories=trajectory_sink is not None, prediction_request=pred_request)
+      keep_trajectories=trajectory_sink is not None, prediction_request=pred_request,
+      placebo_request=placebo_request)
   if trajectory_sink is not None:
     base = request if request is not None else _device_summary_request(ci_data, alpha)
     trajectory_sink(posterior_means, posterior_trajectories, base["scale"], base["shift"])
@@ -317,8 +363,15 @@ def fit_causalimpact(data: pd.DataFrame,
         pred_request["summary"], pred_request["ranks"], alpha, pred_request["observed"],
         pred_request["conditioned"], state_dim, posterior_processing.model_index(ci_data),
         ci_data.data.index)
+  placebo_frame = placebo_quality = None
+  if placebo is not None:
+    placebo_frame, placebo_quality = _placebo_frames(
+        None if placebo_request is None else placebo_request["summary"], origins, horizon, alpha,
+        base["observed"],
+        posterior_processing.model_index(ci_data), n_post, summary.loc["cumulative", "rel_effect"])
   return CausalImpactAnalysis(series, summary, posterior, samples.get("diagnostics"), components,
-                              coefficients, prediction_errors, fit_quality, window_summary)
+                              coefficients, prediction_errors, fit_quality, window_summary,
+                              placebo_frame, placebo_quality)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -627,6 +680,301 @@ def _prediction_frames(psum: Dict, ranks, alpha: float, observed, conditioned, s
   return frame, _fit_quality(cols, psum["loglik"], alpha, observed, state_dim)
 
 
+@dataclasses.dataclass(frozen=True)
+class Placebo:
+  """Options of the placebo (A/A) check, `placebo=` of the three fit functions.
+    horizon      steps every placebo window forecasts; None: min(n_post, n_pre // 3) of the series
+                 (the post-period's own length wherever the pre-period is three times as long);
+    max_origins  the most origins per series, spread evenly over the admissible ones;
+    min_history  the first admissible origin (steps of history before it); None: max(horizon,
+                 state dimension + 1).
+  Fixed-parameter: every draw's scales and weights are those of the one fit of the whole pre-period,
+  so the check is cheap and somewhat optimistic; the windows overlap, so the origins are not
+  independent trials."""
+  horizon: Optional[int] = None
+  max_origins: int = 32
+  min_history: Optional[int] = None
+
+  def __post_init__(self):
+    if self.horizon is not None and int(self.horizon) < 1:
+      raise ValueError(f"Placebo.horizon must be at least 1, got {self.horizon}")
+    if int(self.max_origins) < 1:
+      raise ValueError(f"Placebo.max_origins must be at least 1, got {self.max_origins}")
+    if self.min_history is not None and int(self.min_history) < 0:
+      raise ValueError(f"Placebo.min_history must not be negative, got {self.min_history}")
+
+
+def resolve_placebo(placebo) -> Optional[Placebo]:
+  """`placebo=` as given -> None (off), or the `Placebo` to run (True: the defaults)."""
+  if placebo is None or placebo is False:
+    return None
+  if placebo is True:
+    return Placebo()
+  if isinstance(placebo, Placebo):
+    return placebo
+  raise TypeError(f"`placebo` must be None, True or a Placebo, got {placebo!r}")
+
+
+def placebo_horizon(placebo: Placebo, n_pre: int, n_post: int) -> int:
+  """Steps every placebo window of a series forecasts: the option, else min(n_post, n_pre // 3)."""
+  return int(placebo.horizon) if placebo.horizon is not None else min(int(n_post), int(n_pre) // 3)
+
+
+def placebo_min_history(placebo: Placebo, horizon: int, state_dim: int) -> int:
+  """The first admissible origin: the option, else max(horizon, state_dim + 1)."""
+  return int(placebo.min_history) if placebo.min_history is not None else max(int(horizon), int(state_dim) + 1)
+
+
+def placebo_origins(n_pre: int, horizon: int, min_history: int, max_origins: int) -> np.ndarray:
+  """The origins (model steps, strictly ascending) of a series with `n_pre` pre-period steps:
+  lo = min_history, hi = n_pre - horizon, m = min(max_origins, hi - lo + 1) of them at
+  lo + ((hi - lo) i) // (m - 1); the single origin of m = 1 is hi; none (an empty array) when
+  hi < lo or the horizon is below 1."""
+  lo, hi = int(min_history), int(n_pre) - int(horizon)
+  if hi < lo or horizon < 1:
+    return np.zeros(0, np.int32)
+  m = min(int(max_origins), hi - lo + 1)
+  if m == 1:
+    return np.array([hi], np.int32)
+  return np.array([lo + ((hi - lo) * i) // (m - 1) for i in range(m)], np.int32)
+
+
+def placebo_plan(placebo: Placebo, n_pre: int, n_post: int, state_dim: int):
+  """(horizon, origins) of one series: `placebo_horizon`, `placebo_min_history`, `placebo_origins`."""
+  horizon = placebo_horizon(placebo, n_pre, n_post)
+  return horizon, placebo_origins(n_pre, horizon, placebo_min_history(placebo, horizon, state_dim),
+                                  placebo.max_origins)
+
+
+def placebo_state_dim(local_linear_trend: bool, seasons: Sequence) -> int:
+  """The state dimension of ModelOptions(local_linear_trend, seasons); ValueError when it is more than
+  the placebo filter takes (raised before anything is fitted)."""
+  d = prediction_state_dim(local_linear_trend, [
+      int(getattr(s, "num_seasons", s[0] if isinstance(s, (tuple, list)) else s)) for s in seasons])
+  if d > PREDICTION_MAX_STATE:
+    raise ValueError(f"placebo forecasts take a state of at most {PREDICTION_MAX_STATE} components, "
+                     f"this model has {d}")
+  return d
+
+
+def _placebo_summary_host(y, mask, X, season_change, num_seasons, has_slope, params, draws,
+                          scale, shift, origins, horizon, per_draw: bool = False) -> Dict:
+  """The placebo summary of one series in numpy, from the pooled PARAMETER draws alone: the
+  definitions of ci_session_summarize_placebo (include/causalimpact_amd.h) in float64, for any block
+  list of up to `PREDICTION_MAX_STATE` state components.  The arguments but the last three are those
+  of `_prediction_summary_host`, whose filter this runs; origins [O]: steps, strictly ascending
+  (-1: an unused slot, at the end); horizon: steps per window, origin + horizon <= T.
+  Returns predicted_mean, spread_mean, pit_mean [O] (0 in an unused slot and where the window counts
+  no observation), as the device returns them for one series; with `per_draw` also C, V [O, N] (the
+  conditional mean and predictive variance of the counted sum, in the sampler's units), A and cnt [O]."""
+  y = np.asarray(y, np.float64)
+  mask = np.asarray(mask, bool)
+  T = y.shape[0]
+  scale, shift = np.float64(scale), np.float64(shift)
+  origins = [int(o) for o in np.asarray(origins).reshape(-1)]
+  Hn = int(horizon)
+  used = [o for o in origins if o >= 0]
+  if Hn < 1:
+    raise ValueError(f"the placebo horizon must be at least 1, got {Hn}")
+  if any(o < -1 for o in origins) or used != origins[:len(used)] or any(b <= a for a, b in zip(used, used[1:])):
+    raise ValueError("placebo origins must be strictly ascending steps with the unused slots (-1) at the end")
+  if used and used[-1] + Hn > T:
+    raise ValueError(f"placebo origin {used[-1]} with horizon {Hn} reaches beyond the series' {T} steps")
+  num_seasons = [int(n) for n in num_seasons]
+  K, hs = len(num_seasons), int(bool(has_slope))
+  d = prediction_state_dim(hs, num_seasons)
+  if d > PREDICTION_MAX_STATE:
+    raise ValueError(f"placebo forecasts take a state of at most {PREDICTION_MAX_STATE} components, "
+                     f"this model has {d}")
+  sc = np.asarray(season_change, np.uint8).reshape(K, -1)[:, :T] if K else np.zeros((0, T), np.uint8)
+  so = np.asarray(draws["observation_noise_scale"], np.float64).reshape(-1)
+  N = so.shape[0]
+  H = so * so
+  sl = np.asarray(draws["level_scale"], np.float64).reshape(N)
+  ss = np.asarray(draws["slope_scale"], np.float64).reshape(N) if hs else None
+  sd = np.asarray(draws["seasonal_drift_scales"], np.float64).reshape(N, -1) if K else None
+  reg = np.zeros((N, T))
+  w = draws.get("weights")
+  if X is not None and w is not None and np.shape(w)[-1] > 0:
+    w, X = np.asarray(w, np.float64).reshape(N, -1), np.asarray(X, np.float64)
+    for j in range(w.shape[1]):
+      reg += w[:, j, None] * X[None, :, j]
+  offsets = np.cumsum([1 + hs] + [n - 1 for n in num_seasons])[:-1] if K else []
+  Z = np.zeros(d)
+  Z[0] = 1.0
+  for o in offsets:
+    Z[o] = 1.0
+  a = np.zeros((N, d))
+  a[:, 0] = float(params["init_level_loc"])
+  P = np.zeros((N, d, d))
+  P[:, 0, 0] = float(params["init_level_scale"]) ** 2
+  if hs:
+    P[:, 1, 1] = float(params["init_slope_scale"]) ** 2
+  for o, n in zip(offsets, num_seasons):
+    P[:, o:o + n - 1, o:o + n - 1] = float(params["init_seasonal_scale"]) ** 2 * (np.eye(n - 1) - 1.0 / n)
+
+  def transition(t):                  # (T_t [d, d], Q_t [N, d, d]) of step t -> t + 1
+    Tm = np.eye(d)
+    if hs:
+      Tm[0, 1] = 1.0
+    Q = np.zeros((N, d, d))
+    Q[:, 0, 0] = sl * sl
+    if hs:
+      Q[:, 1, 1] = ss * ss
+    for k, (o, n) in enumerate(zip(offsets, num_seasons)):
+      if sc[k, t]:
+        blk = np.zeros((n - 1, n - 1))
+        blk[:-1, 1:] = np.eye(n - 2)
+        blk[-1, :] = -1.0
+        Tm[o:o + n - 1, o:o + n - 1] = blk
+        q = sd[:, k] / n
+        Q[:, o:o + n - 1, o:o + n - 1] = (q * q)[:, None, None]
+    return Tm, Q
+
+  O = len(origins)
+  Cs, Vs, As, cnts = np.zeros((N, O)), np.zeros((N, O)), np.zeros(O), np.zeros(O)
+  sums, spreads, pits = np.zeros((N, O)), np.zeros((N, O)), np.zeros((N, O))
+  slot = 0
+  for t in range(T):
+    if slot >= len(used):
+      break
+    if t == used[slot]:
+      fa, fP, r = a, P, np.zeros((N, d))
+      V, C, A, cnt = np.zeros(N), np.zeros(N), np.float64(0.0), 0
+      for h in range(Hn):
+        u = t + h
+        pz = fP @ Z
+        if not mask[u]:
+          C = C + (fa @ Z + reg[:, u])
+          A = A + y[u]
+          cnt += 1
+          V = V + ((2.0 * (r @ Z) + pz @ Z) + H)
+          r = r + pz
+        if h + 1 < Hn:
+          Tm, Q = transition(u)
+          fa, r = fa @ Tm.T, r @ Tm.T
+          fP = Tm @ fP @ Tm.T + Q
+      Cs[:, slot], Vs[:, slot], As[slot], cnts[slot] = C, V, A, cnt
+      if cnt:
+        e = A - C
+        sums[:, slot] = C * scale + np.float64(cnt) * shift
+        spreads[:, slot] = ((V + e * e) * scale) * scale
+        pits[:, slot] = 0.5 * _erfc(-e / np.sqrt(2.0 * V))
+      slot += 1
+      if slot >= len(used):
+        break
+    pz = P @ Z
+    if not mask[t]:
+      F = pz @ Z + H
+      v = y[t] - (a @ Z + reg[:, t])
+      a = a + (pz / F[:, None]) * v[:, None]
+      P = P - pz[:, :, None] * pz[:, None, :] / F[:, None, None]
+    if t + 1 < T:
+      Tm, Q = transition(t)
+      a = a @ Tm.T
+      P = Tm @ P @ Tm.T + Q
+  out = dict(predicted_mean=sums.mean(axis=0), spread_mean=spreads.mean(axis=0), pit_mean=pits.mean(axis=0))
+  if per_draw:
+    out.update(C=Cs.T.copy(), V=Vs.T.copy(), A=As, cnt=cnts)
+  return out
+
+
+def _placebo_seen(y_seen, mask, origins, horizon: int, scale, shift):
+  """(n_counted [O], seen_sum [O]) of a series' placebo windows: the observed steps of every window
+  and the sum over them of the outcome AS THE SAMPLER SAW IT (y_seen, in its number format and
+  units), accumulated ascending in float64 and mapped to the data scale: A * scale + cnt * shift --
+  the value every route's pit and spread are taken at.  0 and NaN for an unused slot (-1)."""
+  y_seen = np.asarray(y_seen, np.float64)
+  mask = np.asarray(mask, bool)
+  origins = np.asarray(origins).reshape(-1)
+  n_counted, seen_sum = np.zeros(origins.size), np.full(origins.size, np.nan)
+  used = origins >= 0
+  if used.any():
+    steps = origins[used].astype(np.int64)[:, None] + np.arange(int(horizon))[None, :]     # [O, H]
+    seen = ~mask[steps]
+    # (a masked step adds 0.0; cumsum adds left to right: the ascending sum)
+    A = np.cumsum(np.where(seen, y_seen[steps], 0.0), axis=1)[:, -1]
+    cnt = seen.sum(axis=1).astype(np.float64)
+    n_counted[used], seen_sum[used] = cnt, A * np.float64(scale) + cnt * np.float64(shift)
+  return n_counted, seen_sum
+
+
+PLACEBO_COLUMNS = ("horizon_end", "n_counted", "actual", "predicted", "predicted_sd", "effect",
+                   "relative_effect", "pit", "p", "significant")
+PLACEBO_QUALITY_ENTRIES = ("n_origins", "horizon", "false_positive_rate", "mean_relative_effect",
+                           "mde_relative", "empirical_p")
+
+
+def _placebo_quality(cols: Optional[Dict[str, np.ndarray]], horizon: int, alpha: float, n_post: int,
+                     fit_relative_effect) -> pd.Series:
+  """The `PLACEBO_QUALITY_ENTRIES` of one series from its placebo columns (None: a series without
+  room for an origin -- NaN but n_origins 0 and the horizon), over the origins whose window counts
+  an observation.  empirical_p = (1 + #{|placebo relative effect| >= |the fit's cumulative relative
+  effect|}) / (1 + n_origins), NaN unless horizon == n_post."""
+  nan = np.float64(np.nan)
+  row = dict(n_origins=0.0, horizon=float(horizon), false_positive_rate=nan, mean_relative_effect=nan,
+             mde_relative=nan, empirical_p=nan)
+  if cols is not None:
+    ok = np.asarray(cols["n_counted"]) > 0
+    rel = np.asarray(cols["relative_effect"], np.float64)[ok]
+    row["n_origins"] = float(rel.size)
+    if rel.size:
+      row["false_positive_rate"] = float(np.mean(np.asarray(cols["significant"], bool)[ok]))
+      row["mean_relative_effect"] = float(np.mean(rel))
+      row["mde_relative"] = float(np.quantile(np.abs(rel), 1.0 - alpha))
+      fit_rel = np.float64(fit_relative_effect)
+      if int(horizon) == int(n_post) and not np.isnan(fit_rel):
+        row["empirical_p"] = float((1 + np.count_nonzero(np.abs(rel) >= abs(fit_rel))) / (1 + rel.size))
+  return pd.Series(row, name="placebo_quality")
+
+
+def _placebo_columns(psum: Dict, origins, horizon: int, alpha: float, observed) -> Dict[str, np.ndarray]:
+  """The `PLACEBO_COLUMNS` but horizon_end (as the step horizon_end_step) over the USED origins of one
+  series, from its placebo summary (device or host: predicted_mean, spread_mean, pit_mean, and
+  n_counted, seen_sum of `_placebo_seen`, each [O]).  observed [T]: the outcome on the data scale.
+  effect = seen_sum - predicted: the actual sum as the sampler saw it minus the forecast, the e of
+  predicted_sd = sqrt(max(spread - e^2, 0)), so that the device and the host route agree."""
+  origins = np.asarray(origins).reshape(-1)
+  used = origins >= 0
+  org = origins[used].astype(np.int64)
+  observed = np.asarray(observed, np.float64)
+  n_counted = np.asarray(psum["n_counted"], np.float64)[used]
+  some = n_counted > 0
+  nan = np.where(some, 0.0, np.nan)                  # NaN on the rows whose window counts nothing
+  actual = np.array([np.nansum(observed[o:o + int(horizon)]) for o in org], np.float64) + nan
+  predicted = np.asarray(psum["predicted_mean"], np.float64)[used] + nan
+  effect = np.asarray(psum["seen_sum"], np.float64)[used] - predicted
+  pit = np.asarray(psum["pit_mean"], np.float64)[used] + nan
+  with np.errstate(invalid="ignore", divide="ignore"):
+    sd = np.sqrt(np.maximum(np.asarray(psum["spread_mean"], np.float64)[used] - effect * effect, 0.0)) + nan
+    return {
+        "horizon_end_step": org + int(horizon) - 1,
+        "n_counted": n_counted,
+        "actual": actual,
+        "predicted": predicted,
+        "predicted_sd": sd,
+        "effect": effect,
+        "relative_effect": effect / predicted,
+        "pit": pit,
+        "p": 2.0 * np.minimum(pit, 1.0 - pit),
+        "significant": some & ((pit < alpha / 2.0) | (pit > 1.0 - alpha / 2.0))}
+
+
+def _placebo_frames(psum: Optional[Dict], origins, horizon: int, alpha: float, observed,
+                    model_idx: pd.Index, n_post: int, fit_relative_effect):
+  """(placebo, placebo_quality) of one series: `_placebo_columns` indexed by the origins' labels on
+  the model's index, and `_placebo_quality`.  psum None or no origin: an empty frame and the NaN row."""
+  origins = np.asarray(origins).reshape(-1)
+  if psum is None or not np.any(origins >= 0):
+    frame = pd.DataFrame({k: np.zeros(0) for k in PLACEBO_COLUMNS}, index=model_idx[:0])
+    return frame, _placebo_quality(None, horizon, alpha, n_post, fit_relative_effect)
+  cols = _placebo_columns(psum, origins, horizon, alpha, observed)
+  end = cols.pop("horizon_end_step")
+  frame = pd.DataFrame({"horizon_end": model_idx[end], **cols}, index=model_idx[origins[origins >= 0]])
+  frame.index.name = "origin"
+  return frame[list(PLACEBO_COLUMNS)], _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
+
+
 def _sanitize_seed(seed: Optional[_SeedType]) -> Tuple[int, int]:
   """int s -> (0, s); pair -> pair; None -> fresh entropy (reference :535-543)."""
   if seed is None:
@@ -745,7 +1093,7 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
                  dtype=np.float32, seasons=(), num_chains=1, devices=None,
                  local_linear_trend=False, sampler="gibbs", summary_request=None,
                  hmc_init="gibbs", hmc_prior="slab", kernel_flags=0, component_request=None,
-                 keep_trajectories=False, prediction_request=None):
+                 keep_trajectories=False, prediction_request=None, placebo_request=None):
   """_train_causalimpact_sts plus, when `summary_request` is given (single device, Gibbs), the
   on-device summary of the predictive draws; the [draws, T] trajectories then stay in HBM and
   are returned as None.  `component_request` (scale, shift, quantiles): on that route the component
@@ -755,6 +1103,9 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
   "summary" with its "ranks" and "conditioned" (the steps the model conditions on) -- taken on the
   device on that route (ci_session_summarize_predictions; a trend with at most one block of 2-7
   seasons), by `_prediction_summary_host` from the parameter draws on every other.
+  `placebo_request` (scale, shift, origins, horizon): the placebo summary is left in it under
+  "summary" (predicted_mean, spread_mean, pit_mean and `_placebo_seen`'s n_counted, seen_sum, each
+  [O]) -- ci_session_summarize_placebo or `_placebo_summary_host`, routed like the prediction errors.
   `keep_trajectories`: the trajectories are wanted on the host; the fit then takes the route of
   draws pooled on the host, whose summary runs the same kernels on the same values."""
   if model is not None:
@@ -866,6 +1217,12 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
               shift=np.float64(prediction_request["shift"]) + cond_mu * np.float64(prediction_request["scale"]),
               ranks=prediction_request["ranks"])
           prediction_request["summary"] = {k: v[0] for k, v in psum.items()}
+        if placebo_request is not None and device_predictions_supported(num_seasons):
+          plsum = sess.summarize_placebo(
+              scale=np.float64(placebo_request["scale"]) * cond_s,
+              shift=np.float64(placebo_request["shift"]) + cond_mu * np.float64(placebo_request["scale"]),
+              origins=placebo_request["origins"], horizon=placebo_request["horizon"])
+          placebo_request["summary"] = {k: v[0] for k, v in plsum.items()}
       finally:
         sess.close()
       return part
@@ -918,6 +1275,22 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
           np.float64(prediction_request["scale"]) * cond_s,
           np.float64(prediction_request["shift"]) + cond_mu * np.float64(prediction_request["scale"]),
           prediction_request["ranks"])
+  if placebo_request is not None:
+    # (the outcome and design as the sampler saw them: float64 for the float64 Gibbs kernels)
+    seen = np.float64 if np_dtype == np.float64 and sampler == "gibbs" else np.float32
+    y_seen = np.where(mask, 0.0, y).astype(seen)
+    pl_scale = np.float64(placebo_request["scale"]) * cond_s
+    pl_shift = np.float64(placebo_request["shift"]) + cond_mu * np.float64(placebo_request["scale"])
+    if "summary" not in placebo_request:
+      fields = ("observation_noise_scale", "level_scale", "slope_scale", "seasonal_drift_scales", "weights")
+      draws = {k: out[k].reshape((out[k].shape[0] * out[k].shape[1],) + out[k].shape[2:]) for k in fields}
+      placebo_request["summary"] = _placebo_summary_host(
+          y_seen, mask, None if design is None else design.astype(seen), season_change, num_seasons,
+          local_linear_trend, params, draws, pl_scale, pl_shift, placebo_request["origins"],
+          placebo_request["horizon"])
+    n_counted, seen_sum = _placebo_seen(y_seen, mask, placebo_request["origins"],
+                                        placebo_request["horizon"], pl_scale, pl_shift)
+    placebo_request["summary"].update(n_counted=n_counted, seen_sum=seen_sum)
   if (cond_mu, cond_s) != (0.0, 1.0):
     # back to the caller's scale, in float64: locations get the offset, everything else the scale
     out = {k: np.asarray(v, np.float64) * cond_s for k, v in out.items()}

@@ -1,0 +1,187 @@
+// ci_placebo.h -- placebo forecasts of every fit of a finished session: for every series b, pooled
+// draw n and ORIGIN o inside the observed series the H_b-step forecast of the window's sum without
+// any update, in float64 (ci_session_summarize_placebo; DESIGN.md "Placebo forecasts").
+//
+// The model, the state space, Z, T_t, Q_t, reg[n, t] and the initial moments are those at the top of
+// ci_predict.h, and so is the layout: one lane per (series, draw), a wavefront holds 64 consecutive
+// draws of one series, templated on <HAS_SLOPE, NS, OUT> so that every array is a fully unrolled
+// register array.  The lane runs the filter of ci_predict.h over t = 0, 1, ..; when t reaches the
+// series' next origin -- uniform over the wavefront: the origins belong to the series -- it copies
+// the predicted moments (a, P) of x_o given y[0 .. o - 1] and forecasts from the copy:
+//   r = 0 (D components: Cov(S, x) of the running sum S), V = C = A = 0, cnt = 0
+//   for h = 0 .. H_b - 1, t = o + h:
+//     pz = P Z';  m = Z a
+//     mask[t] == 0:  C += m + reg[n, t];  A += double(y[t]);  cnt += 1
+//                    V += (2 (Z r) + Z pz) + sigma_obs^2;  r += pz
+//     h + 1 < H_b:   a <- T_t a;  r <- T_t r;  P <- T_t P T_t' + Q_t
+// C is the conditional mean of the sum of the counted observations, V its exact predictive variance
+// for that draw (observation noise included).  Per (b, origin i, n), selected by OUT:
+//   SUM    = C * scale[b] + cnt * shift[b]          (separate roundings)
+//   SPREAD = ((V + (A - C)^2) * scale[b]) * scale[b]
+//   PIT    = 0.5 erfc(-(A - C) / sqrt(2 V))
+// An origin whose window counts no step, and a slot without origin (-1, at the end of the row),
+// read 0 in all three.  The filter then goes on from the untouched (a, P) and stops after the
+// series' last origin.  The result is the [B * O, N] matrix `out`, draws contiguous: what the
+// row-statistics kernel reads.  The host checks o + H_b <= T_b for every origin before the launch:
+// no step beyond the series is read.
+#pragma once
+#include "ci_predict.h"
+
+namespace ci {
+
+enum PlaceboOut { PLACEBO_SUM = 0, PLACEBO_SPREAD = 1, PLACEBO_PIT = 2 };
+
+struct PlaceboArgs {
+  PredArgs p;                      // the filter's inputs; p.out [B, O, N], p.ll unused
+  int O;                           // origin slots per series
+  const int* origins;              // [B, O] strictly ascending, -1: unused (at the end)
+  const int* horizon;              // [B]
+};
+
+// a <- T a, P <- T P T' + Q of step t -> t + 1 (the lines of predict_kernel): the trend's part, then
+// the block's where `change` is set.
+template <int HAS_SLOPE, int NS, int D>
+__device__ __forceinline__ void placebo_propagate(double (&a)[D], double (&P)[D * (D + 1) / 2], bool change,
+                                                  double q_level, double q_slope, double q_drift) {
+#define PM(i, j) P[pred_sym<D>(i, j)]
+  constexpr int N1 = NS ? NS - 1 : 0, O = 1 + HAS_SLOPE;
+  if (HAS_SLOPE) {
+    a[0] += a[1];
+    const double p01 = PM(0, 1) + PM(1, 1);
+    PM(0, 0) = (PM(0, 0) + PM(0, 1)) + p01;
+    PM(0, 1) = p01;
+#pragma unroll
+    for (int j = 2; j < D; ++j) PM(0, j) += PM(1, j);
+  }
+  if constexpr (NS > 0) {
+    if (change) pred_season_step<O, N1, D>(a, P, q_drift);
+  }
+  PM(0, 0) += q_level;
+  if (HAS_SLOPE) PM(1, 1) += q_slope;
+#undef PM
+}
+
+// grid (ceil(N / 64), B), block 64.
+template <int HAS_SLOPE, int NS, int OUT>
+__global__ __launch_bounds__(64) void placebo_kernel(PlaceboArgs k) {
+  constexpr int N1 = NS ? NS - 1 : 0, O = 1 + HAS_SLOPE, D = O + N1, NP = D * (D + 1) / 2;
+  constexpr int ZS = O < D ? O : 0;              // the block's first effect (NS > 0)
+  const int n = blockIdx.x * 64 + threadIdx.x, N = k.p.N, T = k.p.T, NO = k.O;
+  const size_t b = blockIdx.y;
+  if (n >= N) return;
+  const int Tb = k.p.series_T ? k.p.series_T[b] : T;
+  const size_t bn = b * N + n;
+  const double so = (double)k.p.obs[bn], H = so * so;
+  const double sl = (double)k.p.lscale[bn], q_level = sl * sl;
+  double q_slope = 0.0, q_drift = 0.0;
+  if (HAS_SLOPE) {
+    const double ss = (double)k.p.sscale[bn];
+    q_slope = ss * ss;
+  }
+  if (NS) {
+    const double q = (double)k.p.drift[bn] / (double)NS;
+    q_drift = q * q;
+  }
+  const double scale = k.p.scales[b], shift = k.p.shifts[b];
+  const double* init = k.p.init + 4 * b;
+  const float* y = k.p.y + b * T;
+  const uint8_t* mask = k.p.mask + b * T;
+  const double* reg = k.p.reg ? k.p.reg + b * T * N + n : nullptr;
+  double* out = k.p.out + b * NO * N + n;
+  const int* org = k.origins + b * NO;
+  const int Hb = k.horizon[b];
+
+  double a[D], P[NP];
+#define PM(i, j) P[pred_sym<D>(i, j)]
+#define FM(i, j) fP[pred_sym<D>(i, j)]
+#pragma unroll
+  for (int i = 0; i < D; ++i) a[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) P[i] = 0.0;
+  a[0] = init[0];
+  PM(0, 0) = init[1];
+  if (HAS_SLOPE) PM(1, 1) = init[2];
+  if (NS) {
+    const double v = init[3];
+#pragma unroll
+    for (int i = 0; i < N1; ++i)
+#pragma unroll
+      for (int j = i; j < N1; ++j) PM(O + i, O + j) = v * ((i == j ? 1.0 : 0.0) - 1.0 / (double)NS);
+  }
+
+  int slot = 0;
+  int next = org[0];                             // uniform over the wavefront, as everything of the origins
+  for (int t = 0; t < Tb && next >= 0; ++t) {
+    if (t == next) {
+      // the forecast branch, from a copy of the predicted moments
+      double fa[D], fP[NP], r[D];
+#pragma unroll
+      for (int i = 0; i < D; ++i) fa[i] = a[i], r[i] = 0.0;
+#pragma unroll
+      for (int i = 0; i < NP; ++i) fP[i] = P[i];
+      double V = 0.0, C = 0.0, A = 0.0;
+      int cnt = 0;
+      for (int h = 0; h < Hb; ++h) {
+        const int u = t + h;
+        double pz[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) pz[i] = NS ? FM(i, 0) + FM(i, ZS) : FM(i, 0);
+        if (mask[u] == 0) {
+          const double m = NS ? fa[0] + fa[ZS] : fa[0];
+          const double zr = NS ? r[0] + r[ZS] : r[0];
+          const double zpz = NS ? pz[0] + pz[ZS] : pz[0];
+          C += m + (reg ? reg[(size_t)u * N] : 0.0);
+          A += (double)y[u];
+          cnt += 1;
+          V += (2.0 * zr + zpz) + H;
+#pragma unroll
+          for (int i = 0; i < D; ++i) r[i] += pz[i];
+        }
+        if (h + 1 >= Hb) break;
+        if (HAS_SLOPE) r[0] += r[1];
+        bool change = false;
+        if constexpr (NS > 0) {
+          change = k.p.season_change[u] != 0;
+          if (change) pred_season_rotate<O, N1, D>(r);
+        }
+        placebo_propagate<HAS_SLOPE, NS, D>(fa, fP, change, q_level, q_slope, q_drift);
+      }
+      double res = 0.0;
+      if (cnt > 0) {
+        const double e = A - C;
+        if (OUT == PLACEBO_SUM) res = __dadd_rn(__dmul_rn(C, scale), __dmul_rn((double)cnt, shift));
+        else if (OUT == PLACEBO_SPREAD) res = __dmul_rn(__dmul_rn(__dadd_rn(V, __dmul_rn(e, e)), scale), scale);
+        else res = 0.5 * erfc(-e / sqrt(2.0 * V));
+      }
+      out[(size_t)slot * N] = res;
+      ++slot;
+      next = slot < NO ? org[slot] : -1;
+      if (next < 0) break;
+    }
+    // the filter's step t (predict_kernel)
+    double pz[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) pz[i] = NS ? PM(i, 0) + PM(i, ZS) : PM(i, 0);
+    if (mask[t] == 0) {
+      const double m = NS ? a[0] + a[ZS] : a[0];
+      const double F = (NS ? pz[0] + pz[ZS] : pz[0]) + H;
+      const double f = m + (reg ? reg[(size_t)t * N] : 0.0);
+      const double v = (double)y[t] - f;
+#pragma unroll
+      for (int i = 0; i < D; ++i) a[i] += (pz[i] / F) * v;
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) PM(i, j) -= pz[i] * pz[j] / F;
+    }
+    if (t + 1 >= Tb) break;
+    bool change = false;
+    if constexpr (NS > 0) change = k.p.season_change[t] != 0;
+    placebo_propagate<HAS_SLOPE, NS, D>(a, P, change, q_level, q_slope, q_drift);
+  }
+#undef PM
+#undef FM
+  for (; slot < NO; ++slot) out[(size_t)slot * N] = 0.0;
+}
+
+}  // namespace ci

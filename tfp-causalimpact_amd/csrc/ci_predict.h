@@ -60,12 +60,11 @@ template <int D> __host__ __device__ constexpr int pred_sym(int i, int j) {
   return i <= j ? i * D - i * (i - 1) / 2 + (j - i) : j * D - j * (j - 1) / 2 + (i - j);
 }
 
-// The block's step at a season change, on the mean and the upper triangle of the covariance: the
-// companion rotation x' = (x_1, .., x_{N1-1}, -sum x) of the N1 effects at offset O, then q on every
-// entry of the block.  Sums run ascending from 0.0.
+// The block's companion rotation x' = (x_1, .., x_{N1-1}, -sum x) of the N1 effects at offset O on a
+// vector that transforms like the state mean (the mean itself; the covariance of the state with a
+// running sum, ci_placebo.h).  The sum runs ascending from 0.0.
 template <int O, int N1, int D>
-__device__ __forceinline__ void pred_season_step(double (&a)[D], double (&P)[D * (D + 1) / 2], double q_drift) {
-#define PM(i, j) P[pred_sym<D>(i, j)]
+__device__ __forceinline__ void pred_season_rotate(double (&a)[D]) {
   constexpr int L = N1 - 1;                  // the block's last effect
   double s = 0.0;
 #pragma unroll
@@ -73,6 +72,16 @@ __device__ __forceinline__ void pred_season_step(double (&a)[D], double (&P)[D *
 #pragma unroll
   for (int i = 0; i < L; ++i) a[O + i] = a[O + i + 1];
   a[O + L] = -s;
+}
+
+// The block's step at a season change, on the mean and the upper triangle of the covariance: the
+// companion rotation x' = (x_1, .., x_{N1-1}, -sum x) of the N1 effects at offset O, then q on every
+// entry of the block.  Sums run ascending from 0.0.
+template <int O, int N1, int D>
+__device__ __forceinline__ void pred_season_step(double (&a)[D], double (&P)[D * (D + 1) / 2], double q_drift) {
+#define PM(i, j) P[pred_sym<D>(i, j)]
+  constexpr int L = N1 - 1;                  // the block's last effect
+  pred_season_rotate<O, N1, D>(a);
 #pragma unroll
   for (int c = 0; c < O; ++c) {              // the trend's rows of the block's columns
     double sc = 0.0;

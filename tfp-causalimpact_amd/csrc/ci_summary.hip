@@ -1,6 +1,7 @@
 // ci_summary.hip -- the on-device summaries behind the C-ABI (kernels: ci_summary.h,
 // ci_components.h, ci_predict.h): ci_session_summarize, ci_session_summarize_components,
-// ci_session_summarize_predictions, ci_session_summarize_windows, ci_ll_session_summarize_windows
+// ci_session_summarize_predictions, ci_session_summarize_placebo (kernels: ci_placebo.h),
+// ci_session_summarize_windows, ci_ll_session_summarize_windows
 // (kernel: ci_windows.h),
 // ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] on
 // draws the caller hands in; ci_session_pool_trajectories, ci_ll_session_pool_trajectories and
@@ -8,6 +9,7 @@
 #include <cmath>
 #include <vector>
 
+#include "ci_placebo.h"
 #include "ci_pool.h"
 #include "ci_predict.h"
 #include "ci_session.h"
@@ -117,6 +119,9 @@ hipError_t comp_launch_row_stats(hipStream_t stream, size_t rows, int N, const d
 // The launch of ci_predict.hip (kernels: ci_predict.h).
 hipError_t predict_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
                           const PredArgs& args);
+// The launch of ci_placebo.hip (kernels: ci_placebo.h).
+hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
+                          const PlaceboArgs& args);
 // The launch of ci_windows.hip (kernel: ci_windows.h).
 hipError_t windows_launch(hipStream_t stream, int B, int N, int T, int W, const float* traj,
                           const double* obs, const double* scales, const double* shifts,
@@ -474,19 +479,45 @@ int ci_session_summarize_components(ci_session* s, const double* scale, const do
   return 0;
 }
 
+// What ci_session_summarize_predictions and ci_session_summarize_placebo ask of a session: a trend
+// with at most one block of 2 to 7 seasons, and a finished run.
+static int pred_check_session(const ci_session* s, const char* who) {
+  const ci_problem& pb = s->pb;
+  if (pb.num_blocks > 1 || (pb.num_blocks == 1 && (pb.num_seasons[0] < 2 || pb.num_seasons[0] > 7))) {
+    std::string blocks;
+    for (int k = 0; k < pb.num_blocks; ++k) blocks += (k ? ", " : "") + std::to_string(pb.num_seasons[k]);
+    return fail("%s takes a trend with at most one block of 2 to 7 seasons, "
+                "this session has the blocks (%s)", who, blocks.c_str());
+  }
+  if (!s->ran) return fail("%s needs a finished ci_session_run", who);
+  return 0;
+}
+
+// On the device, once per session: per series the initial moments of its ci_series_params [B, 4],
+// then [B] times the 1.0 the regression term is scaled by.
+static int pred_init_upload(ci_session* s) {
+  if (s->pred_init.p) return 0;
+  const int B = s->pb.num_series;
+  std::vector<double> init((size_t)5 * B, 1.0);
+  for (int b = 0; b < B; ++b) {
+    const ci_series_params& q = s->params[b];
+    init[4 * b + 0] = q.init_level_loc;
+    init[4 * b + 1] = q.init_level_scale * q.init_level_scale;
+    init[4 * b + 2] = q.init_slope_scale * q.init_slope_scale;
+    init[4 * b + 3] = q.init_seasonal_scale * q.init_seasonal_scale;
+  }
+  HIP_TRY(s->pred_init.alloc(init.size()));
+  HIP_TRY(hipMemcpy(s->pred_init.p, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
 int ci_session_summarize_predictions(ci_session* s, const double* scale, const double* shift,
                                      int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
                                      double* forecast_order, double* variance_mean, double* pit_mean,
                                      double* loglik) {
   if (!s || !scale || !shift || !ranks) return fail("NULL argument");
   const ci_problem& pb = s->pb;          // (not kpb: the inert block of a long trend-only series is no part of the model)
-  if (pb.num_blocks > 1 || (pb.num_blocks == 1 && (pb.num_seasons[0] < 2 || pb.num_seasons[0] > 7))) {
-    std::string blocks;
-    for (int k = 0; k < pb.num_blocks; ++k) blocks += (k ? ", " : "") + std::to_string(pb.num_seasons[k]);
-    return fail("ci_session_summarize_predictions takes a trend with at most one block of 2 to 7 seasons, "
-                "this session has the blocks (%s)", blocks.c_str());
-  }
-  if (!s->ran) return fail("ci_session_summarize_predictions needs a finished ci_session_run");
+  if (pred_check_session(s, "ci_session_summarize_predictions")) return 1;
   const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
   const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, R = num_ranks;
   if (check_ranks(R, ranks, N)) return 1;
@@ -496,19 +527,7 @@ int ci_session_summarize_predictions(ci_session* s, const double* scale, const d
   hipStream_t stream = s->stream;
   double* d_scale = w.obs.p + (size_t)B * T;
   double* d_shift = d_scale + B;
-  if (!s->pred_init.p) {
-    // per series: the initial moments of its ci_series_params, and the 1.0 the regression term is scaled by
-    std::vector<double> init((size_t)5 * B, 1.0);
-    for (int b = 0; b < B; ++b) {
-      const ci_series_params& q = s->params[b];
-      init[4 * b + 0] = q.init_level_loc;
-      init[4 * b + 1] = q.init_level_scale * q.init_level_scale;
-      init[4 * b + 2] = q.init_slope_scale * q.init_slope_scale;
-      init[4 * b + 3] = q.init_seasonal_scale * q.init_seasonal_scale;
-    }
-    HIP_TRY(s->pred_init.alloc(init.size()));
-    HIP_TRY(hipMemcpy(s->pred_init.p, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
+  if (pred_init_upload(s)) return 1;
   HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
@@ -546,6 +565,72 @@ int ci_session_summarize_predictions(ci_session* s, const double* scale, const d
   if ((forecast_mean || forecast_order) && pass(ci::PRED_FORECAST, forecast_mean, forecast_order)) return 1;
   if (variance_mean && pass(ci::PRED_VARIANCE, variance_mean, nullptr)) return 1;
   if ((pit_mean || ll_pending) && pass(ci::PRED_PIT, pit_mean, nullptr)) return 1;
+  return 0;
+}
+
+int ci_session_summarize_placebo(ci_session* s, const double* scale, const double* shift,
+                                 int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                 double* predicted_mean, double* spread_mean, double* pit_mean) {
+  if (!s || !scale || !shift || !origins || !horizon) return fail("NULL argument");
+  const ci_problem& pb = s->pb;          // (not kpb: the inert block of a long trend-only series is no part of the model)
+  if (pred_check_session(s, "ci_session_summarize_placebo")) return 1;
+  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
+  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins;
+  if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
+  for (int b = 0; b < B; ++b) {
+    const int Tb = s->ragged ? s->lengths[b] : T, Hb = horizon[b];
+    if (Hb < 1) return fail("horizon[%d] must be at least 1, got %d", b, Hb);
+    const int32_t* row = origins + (size_t)b * O;
+    bool ended = false;
+    for (int i = 0; i < O; ++i) {
+      const int o = row[i];
+      if (o == -1) { ended = true; continue; }
+      if (o < 0) return fail("origins[%d, %d] must be a step or -1 (unused), got %d", b, i, o);
+      if (ended || (i > 0 && o <= row[i - 1]))
+        return fail("origins[%d] must be strictly ascending with the unused slots (-1) at the end "
+                    "(slot %d holds %d)", b, i, o);
+      if ((long long)o + Hb > Tb)
+        return fail("origins[%d, %d] = %d with horizon %d reaches beyond the series' %d steps", b, i, o, Hb, Tb);
+    }
+  }
+  HIP_TRY(hipSetDevice(pb.device));
+  SummScratch& w = s->summ;
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  hipStream_t stream = s->stream;
+  double* d_scale = w.obs.p + (size_t)B * T;
+  double* d_shift = d_scale + B;
+  if (pred_init_upload(s)) return 1;
+  DevBuf<int> d_plan;                    // origins [B, O], then horizon [B]
+  HIP_TRY(d_plan.alloc((size_t)B * O + B));
+  HIP_TRY(hipMemcpyAsync(d_plan.p, origins, (size_t)B * O * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_plan.p + (size_t)B * O, horizon, B * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  // The regression term of every draw and step in `cum`, once; then one pass per requested matrix
+  // [B * O, N] through `value` (O <= T: it fits), its row means in `obs`.
+  const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
+  if (P > 0)
+    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
+                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
+  ci::PlaceboArgs a;
+  a.p.N = N; a.p.T = T;
+  a.p.y = s->y.p; a.p.mask = s->mask.p; a.p.season_change = s->season_change.p; a.p.series_T = d_series_T;
+  a.p.obs = s->o_obs.p; a.p.lscale = s->o_lscale.p; a.p.sscale = s->o_sscale.p; a.p.drift = s->o_drift.p;
+  a.p.init = s->pred_init.p; a.p.scales = d_scale; a.p.shifts = d_shift;
+  a.p.reg = P > 0 ? w.cum.p : nullptr;
+  a.p.out = w.value.p; a.p.ll = nullptr;
+  a.O = O; a.origins = d_plan.p; a.horizon = d_plan.p + (size_t)B * O;
+  auto pass = [&](int which, double* mean_dst) -> int {
+    HIP_TRY(ci::placebo_launch(stream, B, pb.has_slope, NS, which, a));
+    HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * O, N, w.value.p, w.obs.p, nullptr));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy(mean_dst, w.obs.p, (size_t)B * O * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+  };
+  if (predicted_mean && pass(ci::PLACEBO_SUM, predicted_mean)) return 1;
+  if (spread_mean && pass(ci::PLACEBO_SPREAD, spread_mean)) return 1;
+  if (pit_mean && pass(ci::PLACEBO_PIT, pit_mean)) return 1;
+  HIP_TRY(hipStreamSynchronize(stream));   // (the uploads of a call that asks for nothing)
   return 0;
 }
 
