@@ -435,7 +435,7 @@ __device__ __forceinline__ void xt_sums_wave(const float* tg, const float* Xs, i
   float4 tq[L];
 #pragma unroll
   for (int c = 0; c < L; ++c) tq[c] = *reinterpret_cast<const float4*>(tg + 4 * (lane + 64 * c));
-  float acc[NF];
+  float acc[NF > 0 ? NF : 1];             // (NF = 0: y'y alone)
   auto dot = [&](const float4 (&xq)[L]) {
     float sv = 0.f;
 #pragma unroll

@@ -22,10 +22,12 @@
 //   time waves                         regression wave                 randomness waves
 //   targets -> LDS                     .                               .
 //   (B1) ------------------------------------------------------------------------------------
-//   X~'targets: 2 features per wave over the WHOLE series (xt_sums_wave; all 8 waves), no
-//   cross-wave reduction; time waves also sum the level / slope increments
+//   level / slope increments,        X~'targets over the WHOLE series (xt_sums_wave, no cross-wave
+//   this iteration's normals         reduction): floor(P / 4) features | ceil-ish shares of the rest,
+//   from LDS                         rows held in registers, y'y with wave 7
+//   (helpers_sum builds; the others: 2 feature slots per wave on all 8 waves, increments besides)
 //   (B2) ------------------------------------------------------------------------------------
-//   normals from LDS, emission of    right-hand side replay, flips,   gammas / permutation /
+//   [normals from LDS,] emission of  right-hand side replay, flips,   gammas / permutation /
 //   draw it-1, disturbance scales,   sigma^2_obs(it) -> LDS           x_0 normals of it+1
 //   prior-simulation scan (1st half)
 //   (Bs) sigma^2_obs published --------------------------------------------------------------
@@ -449,6 +451,82 @@ __device__ __forceinline__ double spike_slab_draw_pre(const RegLds& R, int P,
   return new_scale;
 }
 
+// ---- X~'targets between (B1) and (B2).  Where helpers_sum<D, L>() says so the four helper waves
+// -- the regression wave and the three randomness waves, which reach (B1) with nothing pending --
+// sum all P features, up to four each, and the time waves, which used to arrive last at (B2), sum
+// only their level / slope increments.  The split is a function of P alone, contiguous, and no
+// slot beyond P is summed: the regression wave, the critical path from (B2) on, takes
+// floor(P / 4) features, the randomness waves 5, 6, 7 one more each while the remainder lasts;
+// y'y stays with wave 7.  xt_sums_wave's sum of a feature does not depend on who forms it, so the
+// bits are those of any other split.  Chosen per build by measurement: the
+// builds at 256 VGPRs (L >= 8) keep two slots per wave over all eight waves, as does <2, 2>, which
+// was 0.6-0.9 % slower with the helpers' split; <1, 1> and <1, 4> were not measured and stay too.
+// With one step per thread the sums are short and the split pays up to 8 columns only (P = 13:
+// 0.35 % slower): helpers_on adds that condition at run time (a constant in every other build).
+template <int D, int L> constexpr bool helpers_sum() {
+  return (D == 2 && (L == 4 || L == 1)) || (D == 1 && L == 2);
+}
+template <int D, int L> __device__ __forceinline__ bool helpers_on(int P) {
+  return helpers_sum<D, L>() && (L > 1 || P <= 8);
+}
+// h = 0 the regression wave, 1 .. 3 the randomness waves
+__device__ __forceinline__ void xt_share8(int P, int h, int& j0, int& n) {
+  const int base = P >> 2, rem = P & 3;
+  n = base + ((h >= 1 && h <= rem) ? 1 : 0);
+  j0 = h * base + (h == 0 ? 0 : (h - 1 < rem ? h - 1 : rem));
+}
+// xt_sums_wave over a share of n <= 4 features (n wave-uniform: one instantiation runs)
+template <int L, bool XG>
+__device__ __forceinline__ void xt_sums_share(const float* tg, const float* Xs, int tpad, int P, int j0, int n,
+                                              bool with_yty, float* sums, int lane, int T, bool xwide) {
+  switch (n) {
+    case 4: xt_sums_wave<L, 4, XG>(tg, Xs, tpad, P, j0, with_yty, sums, lane, T, xwide); break;
+    case 3: xt_sums_wave<L, 3, XG>(tg, Xs, tpad, P, j0, with_yty, sums, lane, T, xwide); break;
+    case 2: xt_sums_wave<L, 2, XG>(tg, Xs, tpad, P, j0, with_yty, sums, lane, T, xwide); break;
+    case 1: xt_sums_wave<L, 1, XG>(tg, Xs, tpad, P, j0, with_yty, sums, lane, T, xwide); break;
+    default: xt_sums_wave<L, 0, XG>(tg, Xs, tpad, P, j0, with_yty, sums, lane, T, xwide); break;   // y'y alone
+  }
+}
+// The same sums with the share's design rows HELD in registers (a randomness wave reads them once,
+// before the first iteration: the design does not change): per iteration only the targets are
+// read.  Per feature the chain of xt_sums_wave -- the lane's float4 chunks in order, four fused
+// multiply-adds per chunk, then wave_prefix_dpp -- so the bits are the same.
+template <int L>
+__device__ __forceinline__ void xt_rows_hold(const float* Xs, int tpad, int P, int j0, int n, int lane,
+                                             float4 (&xh)[4][L]) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    const int j = j0 + f;
+    const float* row = Xs + (size_t)(j < P ? j : P - 1) * tpad;
+#pragma unroll
+    for (int c = 0; c < L; ++c)
+      xh[f][c] = f < n ? *reinterpret_cast<const float4*>(row + 4 * (lane + 64 * c)) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+template <int L>
+__device__ __forceinline__ void xt_sums_held(const float* tg, const float4 (&xh)[4][L], int tpad, int P, int j0,
+                                             int n, bool with_yty, float* sums, int lane) {
+  float4 tq[L];
+#pragma unroll
+  for (int c = 0; c < L; ++c) tq[c] = *reinterpret_cast<const float4*>(tg + 4 * (lane + 64 * c));
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    if (f < n) {
+      float sv = 0.f;
+#pragma unroll
+      for (int c = 0; c < L; ++c) {
+        sv = fmaf(xh[f][c].x, tq[c].x, sv);
+        sv = fmaf(xh[f][c].y, tq[c].y, sv);
+        sv = fmaf(xh[f][c].z, tq[c].z, sv);
+        sv = fmaf(xh[f][c].w, tq[c].w, sv);
+      }
+      sv = wave_prefix_dpp(sv);
+      if (lane == 63) sums[j0 + f] = sv;
+    }
+  }
+  if (with_yty) xt_sums_wave<L, 0>(tg, nullptr, tpad, P, j0, true, sums, lane);   // y'y alone
+}
+
 // ---- scheduling of the helper waves.  Workgroup barriers are all-or-nothing: a helper (the
 // regression wave outside its serial section, a randomness wave) that is still inside a chunk of
 // background work -- a Philox round (~2k cycles next to a busy time wave), a sweep (~1k) -- when the
@@ -492,7 +570,8 @@ template <int D, int L> struct Lay8 {
 enum Scal8 { SC8_INIT_LOC = 8, SC8_INIT_VAR = 9, SC8_INIT_SVAR = 10, SC8_ZINIT = 12 };
 
 // Profile slots of the instrumented build (ci_session_profile; 32 int64):
-//   time thread 0:      0 = targets .. (B2)   2 = window work   1 = wait at (Bs)   24 = matrix chunk +
+//   time thread 0:      4 = fix-up end .. leaves (B1)   14 = (B1) .. arrival at (B2)   0 = wait at (B2)
+//                       2 = window work   1 = wait at (Bs)   24 = matrix chunk +
 //                       in-wave scan   25 = wait (B3) + cross-wave + local   3 = X w + prior path
 //                       27 = forward chunk + in-wave scan   5 = (B4) + finish   6 = local means +
 //                       adjoint in-wave scan   28 = (B5) + finish   7 = fix-up
@@ -503,6 +582,8 @@ enum Scal8 { SC8_INIT_LOC = 8, SC8_INIT_VAR = 9, SC8_INIT_SVAR = 10, SC8_ZINIT =
 //   arrival at (Bs), cycles since the wave left (B2), lane 0 of: 8, 9, 10 = time waves 1, 2, 3
 //                       11, 12, 13 = randomness waves 5, 6, 7 (time wave 0: slot 2; the regression
 //                       wave: 20 + 21 + 22) -- who is last there
+//   arrival at (B2), cycles since the wave left (B1), lane 0 of: 14 = time wave 0   15 = the
+//                       regression wave   26 = randomness wave 7 (the one with y'y)
 // XG: the design stays in global memory (L2) -- series too long for a copy in LDS beside the
 // randomness buffers (T > ~1500 with a dozen columns, every T > 2048).
 template <int D, int L, bool PROF = false, bool XG = false>
@@ -647,11 +728,26 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
     const int r_3 = mode == 1 ? n_my : (mode == 2 ? 0 : (c_3 < n_my ? c_3 : n_my));
     const int r_4 = mode == 1 ? n_my : (mode == 2 ? 0 : (r_3 + c_4 < n_my ? r_3 + c_4 : n_my));
     const int r_5 = mode == 2 ? 0 : (n_my - c_a > r_4 ? n_my - c_a : r_4);
+    int xj0, xn;
+    xt_share8(P, e + 1, xj0, xn);
+    constexpr bool HOLD = helpers_sum<D, L>() && !XG;    // (its share's rows of the LDS copy, in registers)
+    float4 xh[4][HOLD ? L : 1];
+    if constexpr (HOLD) xt_rows_hold<L>(Xs, TPAD, P, xj0, helpers_on<D, L>(P) ? xn : 0, lane, xh);
     for (int it = 0; it <= n_iter; ++it) {
       __syncthreads();                                   // (B1)
       eprof.tick(31);
-      xt_sums_wave<L, 2, XG>(tgv, Xs, TPAD, P, 2 * wave, wave == NW8 - 1, red, lane, T, xwide);
+      aprof.mark();
+      if (helpers_on<D, L>(P)) {
+        if constexpr (HOLD) {
+          xt_sums_held<L>(tgv, xh, TPAD, P, xj0, xn, wave == NW8 - 1, red, lane);
+        } else {
+          xt_sums_share<L, XG>(tgv, Xs, TPAD, P, xj0, xn, wave == NW8 - 1, red, lane, T, xwide);
+        }
+      } else {
+        xt_sums_wave<L, 2, XG>(tgv, Xs, TPAD, P, 2 * wave, wave == NW8 - 1, red, lane, T, xwide);
+      }
       eprof.tick(30);
+      if (e == 2) aprof.tick(26);
       __syncthreads();                                   // (B2)
       eprof.tick(31);
       aprof.mark();
@@ -712,6 +808,8 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
     for (int r = 0; r < 4; ++r) ps.c[r] = 0.0;
     PF rprof;
     rprof.start(a.prof, a.prof != nullptr && blockIdx.x == 0 && lane == 0);
+    PF bprof;                                            // arrival at (B2)
+    bprof.start(a.prof, a.prof != nullptr && blockIdx.x == 0 && lane == 0);
     double obs_scale = cx->sp.obs_scale0, level_scale = cx->sp.level_scale0, slope_scale = cx->sp.slope_scale0;
     const DevSeriesParams sp = cx->sp;
     float* o_obs = a.out_obs;
@@ -729,12 +827,19 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
     double logit_pi = 0.0;
     if constexpr (HOIST)
       logit_pi = (double)(__logf((float)sp.nonzero_prob) - __logf((float)(1.0 - sp.nonzero_prob)));
+    int xj0, xn;
+    xt_share8(P, 0, xj0, xn);
     for (int it = 0; it <= n_iter; ++it) {
       __syncthreads();                                   // (B1) targets in LDS
+      bprof.mark();
       // from here to sigma^2_obs this wave is the critical path of the iteration and shares its
       // SIMD with time wave 0, which has slack until (Bs): win the issue arbitration while it lasts
       __builtin_amdgcn_s_setprio(3);
-      xt_sums_wave<L, 2, XG>(tgv, Xs, TPAD, P, 2 * wave, false, red, lane, T, xwide);
+      if (helpers_on<D, L>(P)) {
+        xt_sums_share<L, XG>(tgv, Xs, TPAD, P, xj0, xn, false, red, lane, T, xwide);
+      } else {
+        xt_sums_wave<L, 2, XG>(tgv, Xs, TPAD, P, 2 * wave, false, red, lane, T, xwide);
+      }
       // this iteration's gamma variates are a whole iteration old (complete before (Bs) of the
       // previous one, before the first (B1) for iteration 0): the reciprocal sigma^2_obs ends with
       // is formed here, where this wave is ahead of the time waves' longer stretch to (B2)
@@ -745,6 +850,7 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
         rg_obs = fast_rcp(g_obs);
         asm volatile("" : "+v"(rg_obs));                 // (here, not sunk to its use behind (B2))
       }
+      bprof.tick(15);
       __syncthreads();                                   // (B2) all sums complete
       rprof.tick(16);
       const PreTables tb = pre_tables_at(pre_base, it);
@@ -912,7 +1018,9 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
       if constexpr (D == 2) xlast[tid * D + 1] = slp[L - 1];
     }
     __syncthreads();                                       // (B1)
-    xt_sums_wave<L, 2, XG>(tgv, Xs, TPAD, P, 2 * wave, false, red, lane, T, xwide);
+    prof.tick(4);
+    if (!helpers_on<D, L>(P))
+      xt_sums_wave<L, 2, XG>(tgv, Xs, TPAD, P, 2 * wave, false, red, lane, T, xwide);
     {
       float ssl = 0.f, sss = 0.f;
       float pl = (tid > 0) ? xlast[(tid - 1) * D] : 0.f;
@@ -942,22 +1050,31 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
     // sigma_obs of iteration it-1's regression draw: the noise scale of its predictive trajectory
     // (read before the regression wave publishes this iteration's, which happens after (B2))
     const float so_prev = scal[SC_OBS_DK];
+    // This iteration's normals (in LDS since before (B1)) are what the window after (B2) starts
+    // with: where the sums are the helper waves' they are fetched here, where the time waves
+    // would only wait.
+    const bool early_z = helpers_on<D, L>(P);
+    float zl[L], zs[L], zo[L];
+    const float* zit = zb + t0;
+    auto load_normals = [&]() __attribute__((always_inline)) {
+      lds_row_load<L>(zit, zl);
+      if constexpr (D == 2) {
+        lds_row_load<L>(zit + TPAD, zs);
+      } else {
+#pragma unroll
+        for (int l = 0; l < L; ++l) zs[l] = 0.f;
+      }
+      lds_row_load<L>(zit + 2 * TPAD, zo);
+    };
+    if (early_z) load_normals();
+    prof.tick(14);
     __syncthreads();                                       // (B2)
     prof.tick(0);
     aprof.mark();
 
     // ---- window: the normals of this iteration from LDS, emission of draw it-1, this iteration's
     // disturbance scales, first half of the prior-simulation scan
-    float zl[L], zs[L], zo[L];
-    const float* zit = zb + t0;
-    lds_row_load<L>(zit, zl);
-    if constexpr (D == 2) {
-      lds_row_load<L>(zit + TPAD, zs);
-    } else {
-#pragma unroll
-      for (int l = 0; l < L; ++l) zs[l] = 0.f;
-    }
-    lds_row_load<L>(zit + 2 * TPAD, zo);
+    if (!early_z) load_normals();
     if (it > a.W) {
       const int s = it - 1 - a.W;
       float zp[L];

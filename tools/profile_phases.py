@@ -62,24 +62,28 @@ def main():
           f"{cyc[31] / n_it:.2f}")
   if "kernel8" in sess.kernel_name():
     print("  eight-wave kernel, time thread 0:")
-    for i, name in ((0, "targets .. (B2)"), (2, "window: normals from LDS, emission (+ its normals), scales, prior scan"),
+    for i, name in ((4, "fix-up end .. leaves (B1): targets to LDS, wait"),
+                    (14, "(B1) .. arrival at (B2): its sums"), (0, "wait at (B2)"), (2, "window: normals from LDS, emission (+ its normals), scales, prior scan"),
                     (1, "wait at (Bs) for sigma^2_obs"), (24, "matrix chunk + in-wave scan"),
                     (25, "(B3) + cross-wave + local covariance pass"), (3, "X w, residual, prior path"),
                     (27, "forward chunk + in-wave scan"), (5, "(B4) + cross-wave"),
                     (6, "local means + adjoint chunk + in-wave scan"), (28, "(B5) + cross-wave"),
                     (7, "fix-up")):
       print(f"  [{i:2d}] {name:52s} {cyc[i] / n_it:9.0f} cyc/iter")
-    t_sum = sum(cyc[i] for i in (0, 2, 1, 24, 25, 3, 27, 5, 6, 28, 7))
+    t_sum = sum(cyc[i] for i in (4, 14, 0, 2, 1, 24, 25, 3, 27, 5, 6, 28, 7))
     print(f"       time thread 0 total                                  {t_sum / n_it:9.0f} cyc/iter")
     print("  regression wave (lane 0):")
     for i, name in ((16, "(B1) + its two features + (B2)"), (20, "gather"), (21, "right-hand-side replay"),
                     (22, "flips + sigma^2_obs"), (18, "wait at (Bs)"), (23, "weights replay + scale draws + outputs"),
                     (19, "precompute steps (pure, from (Bs) on)"), (17, "its wait at (B3)"), (29, "its waits at (B4) (B5)")):
       print(f"  [{i:2d}] {name:52s} {cyc[i] / n_it:9.0f} cyc/iter")
-    print(f"       iterations on the replay route: {cyc[14]} of {n_it}")
     print("  randomness wave 5 (lane 0):")
     for i, name in ((30, "work"), (31, "waits at barriers")):
       print(f"  [{i:2d}] {name:52s} {cyc[i] / n_it:9.0f} cyc/iter")
+    print("  arrival at (B2), cycles after leaving (B1) (lane 0 of each role; the last one sets the pace):")
+    for name, c in (("[14] time wave 0", cyc[14]), ("[15] regression wave", cyc[15]),
+                    ("[26] randomness wave 7 (with y'y)", cyc[26])):
+      print(f"       {name:52s} {c / n_it:9.0f} cyc/iter")
     print("  arrival at (Bs), cycles after leaving (B2) (lane 0 of each wave; the last one sets the pace):")
     arrivals = [("[ 2] time wave 0", cyc[2]), ("[ 8] time wave 1", cyc[8]), ("[ 9] time wave 2", cyc[9]),
                 ("[10] time wave 3", cyc[10]), ("[20] + [21] + [22] regression wave", cyc[20] + cyc[21] + cyc[22]),
