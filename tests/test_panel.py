@@ -298,13 +298,16 @@ def test_panel_refuses_bad_arguments_before_fitting():
 # ---- the assembler (`batch._assemble`) over a fake launch function: no device, no library ----
 
 _C, _S, _R, _P = 2, 5, 3, 1          # chains, draws per chain, order statistics, design columns
+_W, _O = 2, 3                        # windows, placebo origin slots
 
 
 def _fake_launch(lengths, calls):
   """A launch function that returns what a session would, as a function of the panel position b
   and the step t alone: base(b, t) = 1000 b + t over a series' own steps, arrays at the stride of
   the longest series of the launch, and beyond a series' length what the device leaves there
-  (posterior_means 0, order statistics and components NaN)."""
+  (posterior_means 0, order statistics and components NaN).  All five kinds of the record but the
+  predictions (None: a kind the fit did not ask for); the window totals and the placebo summary have
+  no time axis."""
   lengths = np.asarray(lengths)
 
   def run(launch):
@@ -327,15 +330,24 @@ def _fake_launch(lengths, calls):
                 inclusion_prob=per_b[:, None] + np.zeros((1, _P)),
                 weight_mean=-per_b[:, None] + np.zeros((1, _P)),
                 weight_order=per_b[:, None, None] + np.arange(_R * _P).reshape(1, _R, _P))
-    return out, dsum, csum
+    wsum = dict(per_draw=per_b[:, None, None, None] + np.arange(_W * 2 * _C * _S).reshape(1, _W, 2, _C * _S),
+                per_draw_order=per_b[:, None, None, None] - np.arange(_W * 2 * _R).reshape(1, _W, 2, _R))
+    plsum = {k: (i + 1) * per_b[:, None] + np.arange(_O)[None, :]
+             for i, k in enumerate(lib.SUMMARY_KINDS["placebo"].whole)}
+    return out, lib.SummaryRecord(effect=dsum, components=csum, windows=wsum, placebo=plsum)
 
   return run
 
 
 def _assert_assembled(got, lengths):
   """Every series' row holds its own values over [0, T_b) and the padding beyond."""
-  means, dsum, diag, csum = got
+  means, record, diag = got
+  dsum, csum, wsum, plsum = record.effect, record.components, record.windows, record.placebo
+  assert record.predictions is None
   B, T_max = len(lengths), max(lengths)
+  assert wsum["per_draw"].shape == (B, _W, 2, _C * _S) and wsum["per_draw_order"].shape == (B, _W, 2, _R)
+  assert set(plsum) == set(lib.SUMMARY_KINDS["placebo"].whole)
+  assert all(v.shape == (B, _O) for v in plsum.values())
   assert means.shape == (B, T_max) and means.dtype == np.float32
   assert set(diag) == {"observation_noise_scale", "level_scale"}
   assert all(v.shape == (B, _C, _S) for v in diag.values())
@@ -362,6 +374,11 @@ def _assert_assembled(got, lengths):
     np.testing.assert_array_equal(csum["inclusion_prob"][b], np.full(_P, float(b)))
     np.testing.assert_array_equal(csum["weight_mean"][b], np.full(_P, -float(b)))
     np.testing.assert_array_equal(csum["weight_order"][b], b + np.arange(_R * _P).reshape(_R, _P))
+    np.testing.assert_array_equal(wsum["per_draw"][b],
+                                  b + np.arange(_W * 2 * _C * _S).reshape(_W, 2, _C * _S))
+    np.testing.assert_array_equal(wsum["per_draw_order"][b], b - np.arange(_W * 2 * _R).reshape(_W, 2, _R))
+    for i, k in enumerate(lib.SUMMARY_KINDS["placebo"].whole):
+      np.testing.assert_array_equal(plsum[k][b], (i + 1) * b + np.arange(_O))
     np.testing.assert_array_equal(diag["observation_noise_scale"][b],
                                   b + np.arange(_C)[:, None] + 0.5 * np.arange(_S))
     np.testing.assert_array_equal(diag["level_scale"][b], b - np.arange(_C)[:, None] - 0.5 * np.arange(_S))
@@ -398,14 +415,18 @@ def test_assembler_takes_a_batch_as_one_group_and_does_not_copy_a_whole_launch()
   _assert_assembled(split, [T] * B)
   one = batch._assemble(batch.panel_launches(route, [0]), run, B, T)    # pylint: disable=protected-access
   _assert_assembled(one, [T] * B)
-  for a, b in zip(split[1:], one[1:]):
+  for (kind, a), (_, b) in zip([*split[1].kinds(), ("diag", split[2])], [*one[1].kinds(), ("diag", one[2])]):
+    if kind == "predictions":
+      assert a is None and b is None
+      continue
     assert list(a) == list(b)
     for k in a:
       assert a[k].dtype == b[k].dtype
       np.testing.assert_array_equal(a[k], b[k])
   np.testing.assert_array_equal(split[0], one[0])
   # one launch with all B series in order at full stride: its arrays, not copies of them
-  out, dsum, csum = results[tuple(range(B))]
-  assert all(one[1][k] is dsum[k] for k in dsum) and all(one[3][k] is csum[k] for k in csum)
+  out, whole = results[tuple(range(B))]
+  for kind, arrays in whole.kinds():
+    assert arrays is None or all(getattr(one[1], kind)[k] is arrays[k] for k in arrays)
   assert all(one[2][k] is out[k] for k in one[2])
-  assert not any(np.shares_memory(split[1][k], dsum[k]) for k in dsum)
+  assert not any(np.shares_memory(split[1].effect[k], whole.effect[k]) for k in whole.effect)

@@ -301,8 +301,7 @@ def fit_hmc_batch(y, mask, X, specs, *, has_slope: bool, num_results: int, num_w
                   num_chains: int, seed, device: int = 0, series_offset: int = 0,
                   shared_streams: bool = False, num_leapfrog: int = 15, target_accept: float = 0.75,
                   initial_step_size: float = 0.05, prior: str = "slab", horseshoe_scale: float = 0.1,
-                  summary: Optional[Dict] = None, after_summary=None,
-                  also_fetch: Sequence[str] = ()) -> Dict[str, np.ndarray]:
+                  resident=None) -> Dict[str, np.ndarray]:
   """`fit_hmc` for B series of a trend model in ONE launch (ci_ll_session_create_batch: B x C
   workgroups of the hmc_kernel, then B x C x S latent / predictive draws).  y, mask [B, T]; X
   [B, T, P] or None; specs: B `_model.series_params` dicts.  Chains start at the Gibbs initial
@@ -311,13 +310,10 @@ def fit_hmc_batch(y, mask, X, specs, *, has_slope: bool, num_results: int, num_w
   `fit_hmc` on that series alone, draw for draw.
 
   Only small arrays leave the device: posterior_means [B, C, T], observation_noise_scale and
-  level_scale [B, C, S] (for the diagnostics), hmc_accept_rate and hmc_step_size [B, C],
-  hmc_kernel_ms, and the fields of the sample container named in `also_fetch` (the parameter draws
-  the prediction errors are filtered from: slope_scale [B, C, S], weights [B, C, S, P]).  summary (optional): dict(scale, shift, observed, flags, ranks) of
-  `_native.BatchLogLikSession.summarize` -- the order statistics of the [B, C, S, T] predictive
-  trajectories, computed where they are; returned as "summary".  after_summary (optional): called
-  with the session while the fit is still resident, after the summary (the pool step of a batch's
-  aggregates: `_native.BatchLogLikSession.pool_trajectories`)."""
+  level_scale [B, C, S] (for the diagnostics), hmc_accept_rate and hmc_step_size [B, C] and
+  hmc_kernel_ms.  resident (optional): called with the `_native.BatchLogLikSession` while the fit is
+  still resident -- the summaries of the [B, C, S, T] predictive trajectories, computed where they
+  are, the pool step of a batch's aggregates --; what it returns comes back as "resident"."""
   y = np.asarray(y, np.float64)
   B, T = y.shape
   P = 0 if X is None else int(np.asarray(X).shape[2])
@@ -331,12 +327,10 @@ def fit_hmc_batch(y, mask, X, specs, *, has_slope: bool, num_results: int, num_w
     ms = sess.hmc_run(num_chains=C, num_warmup=W, num_results=S, num_leapfrog=num_leapfrog,
                       target_accept=target_accept, initial_step_size=initial_step_size, seed=seed,
                       prior=prior, horseshoe_scale=horseshoe_scale)
-    _, acc, eps, out = sess.hmc_fetch(["posterior_means", "observation_noise_scale", "level_scale",
-                                       *also_fetch], with_draws=False)
-    if summary is not None:
-      out["summary"] = sess.summarize(**summary)
-    if after_summary is not None:
-      after_summary(sess)
+    _, acc, eps, out = sess.hmc_fetch(["posterior_means", "observation_noise_scale", "level_scale"],
+                                      with_draws=False)
+    if resident is not None:
+      out["resident"] = resident(sess)
   finally:
     sess.close()
   out.update(hmc_accept_rate=acc, hmc_step_size=eps, hmc_kernel_ms=np.asarray(ms))

@@ -602,6 +602,9 @@ def fit_gibbs_f64_route(pb: Problem) -> Dict[str, int]:
 class Session:
   """Device-resident fit (inputs and outputs live in HBM between run() calls)."""
 
+  # the kinds of `causalimpact_lib.SummaryRecord` this session takes on the device
+  summaries = ("effect", "components", "predictions", "windows", "placebo")
+
   def __init__(self, pb: Problem, y, mask, X, season_change, params):
     self._lib = load()
     self.pb = pb
@@ -1031,6 +1034,9 @@ class BatchLogLikSession(LogLikSession):
   `evaluate` and `draw_latents` need B = 1."""
 
   batched = True
+  # the kinds of `causalimpact_lib.SummaryRecord` this session takes on the device (it keeps no
+  # latent draws and has no filter entries)
+  summaries = ("effect", "windows")
 
   def __init__(self, pb: Problem, params, y, mask, X, max_evals: int = 1):   # pylint: disable=super-init-not-called
     self._lib = load()
@@ -1061,6 +1067,11 @@ class BatchLogLikSession(LogLikSession):
 
   def hmc(self, **kw):
     raise NotImplementedError("use hmc_run + hmc_fetch on a batched session")
+
+  def fetch(self, want) -> Dict[str, np.ndarray]:
+    """`Session.fetch` of the finished fit: the fields of `want` that the trend model has."""
+    return self.hmc_fetch([k for k in want if k not in ("seasonal_drift_scales", "seasonal_levels")],
+                          with_draws=False)[3]
 
   def summarize(self, scale, shift, observed, flags, ranks) -> Dict[str, np.ndarray]:
     """`Session.summarize` of the fit's resident predictive trajectories (ci_ll_session_hmc_summarize):

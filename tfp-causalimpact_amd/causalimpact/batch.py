@@ -31,7 +31,9 @@ calendar; `prepare_panel`, padded to the longest series):
   * `panel_route` + `panel_launches`: which series share a launch on which device -- a batch is
     the panel of ONE group of equal lengths, cut into consecutive positions per device;
   * `_run_launch` (Gibbs: ordinary, ragged or ragged seasonal session) or `_run_hmc_launch`: one
-    session from creation to close, arrays back with the series axis at the launch's stride;
+    session from creation to close, arrays back with the series axis at the launch's stride -- what
+    it fetches and the `causalimpact_lib.SummaryRecord` that `causalimpact_lib.take_summaries` fills
+    from the open session (one kind per summary; `_KINDS` says how each is laid out);
   * `aggregate_groups`, `_PoolChain` (`HostPool` on the per-series routes), `_frame_analyses`: the
     aggregates of both -- the group table, the running sums handed from launch to launch, the frames
     of every group.  A calendar aggregate is an event-time aggregate whose members all start at step
@@ -333,23 +335,16 @@ def window_table(names, alpha, ranks, plan: WindowPlan, wsum: Dict[str, np.ndarr
   return pd.DataFrame(full, index=index, columns=table.columns)
 
 
-# What a launch returns has the series axis first and, with these exceptions, time last: the
-# fetched draws of the scalars the diagnostics rank [B, chains, draws], the device summary's window
-# totals per draw, and the component-summary arrays whose last axis is the design columns.
+# What a launch returns has the series axis first and, but for the names a kind lists as whole, time
+# last: the kinds of `lib.SummaryRecord` and what a launch fetches -- posterior_means over time and
+# the draws of the scalars the diagnostics rank [B, chains, draws], 0 beyond a series' length.
 _DRAW_SCALARS = ("observation_noise_scale", "level_scale")
-_PER_DRAW = ("per_draw", "per_draw_order")
-_PER_COLUMN = ("inclusion_prob", "weight_mean", "weight_order")
-_PER_DRAW_LOGLIK = ("loglik",)       # of the prediction summary: [B, draws]
-# the placebo summary: [B, O] each, none over time (`lib._placebo_summary_host`, `lib._placebo_seen`)
-_PLACEBO = ("predicted_mean", "spread_mean", "pit_mean", "n_counted", "seen_sum")
-# the parameter draws the prediction errors are filtered from (`lib._prediction_summary_host`)
-_PARAMETER_DRAWS = ("observation_noise_scale", "level_scale", "slope_scale", "seasonal_drift_scales",
-                    "weights")
+_KINDS = dict(lib.SUMMARY_KINDS, fetched=lib.SummaryKind(_DRAW_SCALARS, 0))
 
 
-def _cut(arrays: Dict[str, np.ndarray], num_steps: int, whole=()) -> Dict[str, np.ndarray]:
-  """`arrays` with the time (last) axis cut to `num_steps`, but for the names in `whole`."""
-  return {k: (v if k in whole else v[..., :num_steps]) for k, v in arrays.items()}
+def _cut(arrays: Dict[str, np.ndarray], num_steps: int, kind: str) -> Dict[str, np.ndarray]:
+  """`arrays` of `kind` with the time (last) axis cut to `num_steps`."""
+  return {k: (v if k in _KINDS[kind].whole else v[..., :num_steps]) for k, v in arrays.items()}
 
 
 class CausalImpactBatchAnalysis:
@@ -359,18 +354,19 @@ class CausalImpactBatchAnalysis:
   when more than one chain was run."""
 
   def __init__(self, prepared, names, alpha, posterior_means, device_summary, ranks, columns,
-               diagnostic_draws, component_summary=None, prediction_summary=None, state_dim=0,
-               placebo_summary=None):
+               diagnostic_draws, record: Optional[lib.SummaryRecord] = None, state_dim=0,
+               placebo_plan=None):
     self._prep, self._names, self.alpha = prepared, list(names), alpha
-    # `placebo=`: dict(summary {name: [B, O]} of `_PLACEBO`, origins [B, O] (-1: unused), horizon [B],
-    # n_post [B]), or None
-    self._placebo = placebo_summary
+    record = record if record is not None else lib.SummaryRecord()
+    # `placebo=`: placebo_plan dict(origins [B, O] (-1: unused), horizon [B], n_post [B]) with the
+    # record's placebo summary {name: [B, O]} as "summary", or None
+    self._placebo = None if placebo_plan is None else dict(placebo_plan, summary=record.placebo)
     self._placebo_quality: Optional[pd.DataFrame] = None
     # {name: [B, ...]} of ci_session_summarize_components (InferenceOptions.components), or None
-    self._csum = component_summary
+    self._csum = record.components
     # {name: [B, ...]} of ci_session_summarize_predictions (InferenceOptions.prediction_errors), or
     # None, and the state dimension of the model (the first step `fit_quality` scores)
-    self._psum, self._state_dim = prediction_summary, state_dim
+    self._psum, self._state_dim = record.predictions, state_dim
     self._quality: Optional[pd.DataFrame] = None
     self._means, self._dsum, self._ranks, self._columns = posterior_means, device_summary, ranks, columns
     # {key: [B, chains, draws]} of the scalars the diagnostics rank, or None for one chain.  The
@@ -449,11 +445,10 @@ class CausalImpactBatchAnalysis:
       # (arrays over time are padded to the longest series of a panel: series b owns [0, Tb))
       df, pre, post, Tb = self._series_view(b)
       ci_data = cid.CausalImpactData(df, pre, post, standardize_data=self._prep.standardize_data)
-      dsum = _cut({k: v[b] for k, v in self._dsum.items()}, Tb, _PER_DRAW)
+      dsum = _cut({k: v[b] for k, v in self._dsum.items()}, Tb, "effect")
       rq = lib._device_summary_request(ci_data, self.alpha)   # pylint: disable=protected-access
-      rq["ranks"] = self._ranks
       series, summary = lib._compute_impact_device(            # pylint: disable=protected-access
-          self._means[b, :Tb], dsum, rq, ci_data, self.alpha)
+          self._means[b, :Tb], dsum, rq["observed"], rq["flags"], self._ranks, ci_data, self.alpha)
       self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b),
                                                 *self._component_frames(b, ci_data, Tb),
                                                 *self._prediction_frames(b, ci_data, Tb),
@@ -494,7 +489,7 @@ class CausalImpactBatchAnalysis:
   def _prediction_inputs(self, b: int, num_steps: int):
     """(summary, observed, conditioned) of series b over its `num_steps` steps."""
     p = self._prep
-    psum = _cut({k: v[b] for k, v in self._psum.items()}, num_steps, _PER_DRAW_LOGLIK)
+    psum = _cut({k: v[b] for k, v in self._psum.items()}, num_steps, "predictions")
     return psum, p.observed[b, :num_steps], ~p.mask[b, :num_steps]
 
   def _prediction_frames(self, b: int, ci_data, num_steps: int):
@@ -526,7 +521,7 @@ class CausalImpactBatchAnalysis:
     were not asked for."""
     if self._csum is None:
       return None, None
-    csum = _cut({k: v[b] for k, v in self._csum.items()}, num_steps, _PER_COLUMN)
+    csum = _cut({k: v[b] for k, v in self._csum.items()}, num_steps, "components")
     return lib._component_frames(                               # pylint: disable=protected-access
         csum, self._ranks, self._dsum["per_draw"].shape[-1], self.alpha,
         lib.posterior_processing.model_index(ci_data), ci_data.data.index,
@@ -1105,14 +1100,12 @@ def _frame_analyses(rows, alpha: float, ranks, device: int = 0, windows=None):
   analyses = {}
   for g, (name, ci_data, observed, flags, mean, draws) in enumerate(rows):
     dsum = _native.summarize_draws(draws, 1.0, 0.0, observed, flags, ranks, device=device)
-    rq = lib._device_summary_request(ci_data, alpha)             # pylint: disable=protected-access
-    rq.update(observed=observed, flags=flags, ranks=ranks)
-    wins = () if windows is None else windows[1][g]
+    wins, totals = (() if windows is None else windows[1][g]), None
     if wins:
-      rq["window_totals"] = _native.window_totals_host(
+      totals = _native.window_totals_host(
           draws[None], 1.0, 0.0, observed, [w.first for w in wins], [w.count for w in wins])[0]
     series, summary, window_summary = lib._compute_impact_device(   # pylint: disable=protected-access
-        mean, dsum, rq, ci_data, alpha, windows=wins)
+        mean, dsum, observed, flags, ranks, ci_data, alpha, windows=wins, window_totals=totals)
     analyses[name] = lib.CausalImpactAnalysis(series, summary, None, window_summary=window_summary)
   table = pd.concat([a.summary for a in analyses.values()], keys=list(analyses),
                     names=["aggregate", None])
@@ -1474,49 +1467,6 @@ def placebo_plans(placebo: lib.Placebo, num_pre, num_post, state_dim: int):
   return origins, np.array([h for h, _ in plans], np.int32)
 
 
-def _placebo_seen_rows(fit: _Fit, ids, plsum: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
-  """`plsum` {name: [n, O]} of the series `ids` with `lib._placebo_seen`'s n_counted and seen_sum."""
-  seen = [lib._placebo_seen(                                    # pylint: disable=protected-access
-      np.where(fit.mask[b], 0.0, fit.y[b]).astype(np.float32), fit.mask[b], fit.placebo_origins[b],
-      fit.placebo_horizon[b], fit.own_scale[b], fit.own_shift[b]) for b in (int(b) for b in ids)]
-  return dict(plsum, n_counted=np.stack([c for c, _ in seen]), seen_sum=np.stack([a for _, a in seen]))
-
-
-def _device_placebo(sess, fit: _Fit, ids) -> Dict[str, np.ndarray]:
-  """The placebo summary {name: [n, O]} of the series `ids` from their open session
-  (`summarize_placebo`): the launch's own origin slots (never more than its steps), the horizon of a
-  series without origin raised to the 1 the entry asks for."""
-  org = fit.placebo_origins[ids]
-  width = max(1, int((org >= 0).sum(axis=1).max()))
-  got = sess.summarize_placebo(fit.own_scale[ids], fit.own_shift[ids], org[:, :width],
-                               np.maximum(fit.placebo_horizon[ids], 1))
-  out = {k: np.zeros(org.shape) for k in got}
-  for k, v in got.items():
-    out[k][:, :width] = v
-  return _placebo_seen_rows(fit, ids, out)
-
-
-def _host_placebo(fit: _Fit, ids, draws: Dict[str, np.ndarray], season_change) -> Dict[str, np.ndarray]:
-  """The same in numpy (`lib._placebo_summary_host`) from the launch's parameter draws
-  {name: [n, C, S, ...]}: the routes whose models the device filter does not take."""
-  mo = fit.model_options
-  num_seasons = _model.expand_seasons(mo.seasons, 1)[0]
-  out = {k: np.zeros((len(ids), fit.placebo_origins.shape[1])) for k in _PLACEBO[:3]}
-  for i, b in enumerate(int(b) for b in ids):
-    if not np.any(fit.placebo_origins[b] >= 0):
-      continue
-    Tb = int(fit.lengths[b])
-    pooled = {k: v[i].reshape((v.shape[1] * v.shape[2],) + v.shape[3:]) for k, v in draws.items()}
-    one = lib._placebo_summary_host(                            # pylint: disable=protected-access
-        np.where(fit.mask[b, :Tb], 0.0, fit.y[b, :Tb]).astype(np.float32), fit.mask[b, :Tb],
-        None if fit.design is None else fit.design[b, :Tb].astype(np.float32),
-        np.asarray(season_change)[:, :Tb], num_seasons, mo.local_linear_trend, fit.params[b], pooled,
-        fit.own_scale[b], fit.own_shift[b], fit.placebo_origins[b], fit.placebo_horizon[b])
-    for k, v in one.items():
-      out[k][i] = v
-  return _placebo_seen_rows(fit, ids, out)
-
-
 def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None):
   """One launch of the Gibbs sampler and its summaries on the device.  launch: (device, key,
   positions) as `panel_launches` lists them; kind: the session the positions run in --
@@ -1528,16 +1478,11 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
                        series starts at its own step 0) and the stride rounded up to a multiple of 4
                        (every row 16-byte aligned), the padding as in `PreparedPanel`: y NaN, mask
                        True, design 0, observed NaN, flags 0.
-  Returns (out, dsum, csum, psum, wsum, plsum): `fetch` of posterior_means [n, C, T] and `_DRAW_SCALARS` [n, C, S],
-  `summarize`, `summarize_components` (None unless InferenceOptions.components) and the prediction
-  summary (None unless InferenceOptions.prediction_errors): `summarize_predictions` for the block
-  lists the device takes, `_host_predictions` from the fetched parameter draws for the others;
-  wsum `summarize_windows` with every series' own windows (None unless `effect_windows`); plsum
-  the placebo summary (None unless `placebo=`), routed like the prediction summary:
-  `_device_placebo` or `_host_placebo`.  Every
-  array keeps the series axis, and T is the longest series of the launch on every route.
+  Returns (out, record): `fetch` of posterior_means [n, C, T] and `_DRAW_SCALARS` [n, C, S], and the
+  `lib.SummaryRecord` of `_launch_request` (`lib.take_summaries`).  Every array keeps the series axis,
+  and T is the longest series of the launch on every route.
   chain (aggregates of a batch, event-time aggregates of a panel): the launch's pool step runs after
-  `summarize`, the session still open."""
+  the summaries, the session still open."""
   dev, _, ids = launch
   ids = np.asarray(ids, dtype=np.int64)
   mo, io = fit.model_options, fit.inference_options
@@ -1572,111 +1517,74 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
   try:
     sess.run()
     out = sess.fetch(["posterior_means", *_DRAW_SCALARS])
-    dsum = sess.summarize(scale, shift, observed, flags, fit.ranks)
-    if len(ids) == 1:        # (`summarize` drops the series axis of a session of one series)
-      dsum = {k: v[None] for k, v in dsum.items()}
-    csum = sess.summarize_components(scale, shift, fit.ranks) if io.components else None
-    psum = None
-    if io.prediction_errors and lib.device_predictions_supported(num_seasons):
-      psum = sess.summarize_predictions(fit.own_scale[ids], fit.own_shift[ids], fit.ranks)
-    elif io.prediction_errors:
-      psum = _host_predictions(fit, ids, T, sess.fetch(list(_PARAMETER_DRAWS)), season_change)
-    wsum = None
-    if fit.windows is not None:
-      wsum = sess.summarize_windows(scale, shift, observed, fit.windows.first[ids],
-                                    fit.windows.count[ids], fit.ranks)
-    plsum = None
-    if fit.placebo_origins is not None and lib.device_predictions_supported(num_seasons):
-      plsum = _device_placebo(sess, fit, ids)
-    elif fit.placebo_origins is not None:
-      plsum = _host_placebo(fit, ids, sess.fetch(list(_PARAMETER_DRAWS)), season_change)
+    record = lib.take_summaries(sess, _launch_request(fit, ids, observed, flags),
+                                _series_inputs(fit, ids, season_change, num_seasons))
     if chain is not None:
       chain.step(launch, chain.session_pool(sess, scale, shift))
   finally:
     sess.close()
   if stride != T:            # (back at the stride of the longest series)
-    out, dsum = _cut(out, T, _DRAW_SCALARS), _cut(dsum, T, _PER_DRAW)
-    csum = None if csum is None else _cut(csum, T, _PER_COLUMN)
-    psum = None if psum is None else _cut(psum, T, _PER_DRAW_LOGLIK)
-  return out, dsum, csum, psum, wsum, plsum
+    out, record = _cut(out, T, "fetched"), record.map(lambda kind, arrays: _cut(arrays, T, kind))
+  return out, record
 
 
-def _host_predictions(fit: _Fit, ids, num_steps: int, draws: Dict[str, np.ndarray],
-                      season_change) -> Dict[str, np.ndarray]:
-  """The prediction summary of the series `ids` of a launch in numpy (`lib._prediction_summary_host`),
-  from the launch's parameter draws {name: [n, C, S, ...]} (a name the model lacks may be missing):
-  the routes whose models the device filter does not take.  Arrays [n, ...] over `num_steps` steps,
-  with the padding convention of the device beyond a series' length."""
-  mo = fit.model_options
-  num_seasons = _model.expand_seasons(mo.seasons, 1)[0]
-  n, R = len(ids), len(fit.ranks)
-  out = None
-  for i, b in enumerate(int(b) for b in ids):
-    Tb = int(fit.lengths[b])
-    pooled = {k: v[i].reshape((v.shape[1] * v.shape[2],) + v.shape[3:]) for k, v in draws.items()}
-    one = lib._prediction_summary_host(                         # pylint: disable=protected-access
-        np.where(fit.mask[b, :Tb], 0.0, fit.y[b, :Tb]).astype(np.float32), fit.mask[b, :Tb],
-        None if fit.design is None else fit.design[b, :Tb].astype(np.float32),
-        np.asarray(season_change)[:, :Tb], num_seasons, mo.local_linear_trend, fit.params[b], pooled,
-        fit.own_scale[b], fit.own_shift[b], fit.ranks)
-    if out is None:
-      N = one["loglik"].shape[0]
-      out = dict(forecast_mean=np.zeros((n, num_steps)), forecast_order=np.zeros((n, R, num_steps)),
-                 variance_mean=np.zeros((n, num_steps)), pit_mean=np.zeros((n, num_steps)),
-                 loglik=np.zeros((n, N)))
-    out["forecast_mean"][i], out["forecast_order"][i] = fit.own_shift[b], fit.own_shift[b]
-    for k, v in one.items():
-      out[k][i, ..., :v.shape[-1]] = v
-  return out
+def _launch_request(fit: _Fit, ids, observed, flags) -> lib.SummaryRequest:
+  """What the fit wants of the launch of the series `ids`; observed, flags: theirs at its stride."""
+  io, own = fit.inference_options, None
+  if fit.own_scale is not None:
+    own = lib.Affine(fit.own_scale[ids], fit.own_shift[ids])
+  return lib.SummaryRequest(
+      scale=fit.scale[ids], shift=fit.shift[ids], observed=observed, flags=flags, ranks=fit.ranks,
+      components=io.components, predictions=own if io.prediction_errors else None,
+      windows=None if fit.windows is None else lib.Windows(fit.windows.first[ids], fit.windows.count[ids]),
+      placebo=None if fit.placebo_origins is None else lib.PlaceboPart(
+          *own, fit.placebo_origins[ids], fit.placebo_horizon[ids]))
+
+
+def _series_inputs(fit: _Fit, ids, season_change, num_seasons) -> Optional[List[lib.SeriesInputs]]:
+  """The series `ids` as their sampler saw them, each over its own steps, for the summaries taken in
+  numpy (None when the fit asks for none of them)."""
+  if fit.own_scale is None:
+    return None
+  season_change = np.asarray(season_change)
+  return [lib.SeriesInputs(fit.y[b, :Tb], fit.mask[b, :Tb], None if fit.design is None else fit.design[b, :Tb],
+                           season_change[:, :Tb], num_seasons, fit.model_options.local_linear_trend,
+                           fit.params[b]) for b, Tb in ((int(b), int(fit.lengths[b])) for b in ids)]
 
 
 def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None):
   """`_run_launch` for the one-launch HMC path (`_hmc.fit_hmc_batch`: B x chains HMC chains, then
-  the latent paths, the predictive trajectories and their summary on the device): consecutive
-  positions of a batch, series b keyed by positions[0] + b.  It keeps no latent draws, hence no
-  component summary; the prediction summary is `_host_predictions` and the placebo summary
-  `_host_placebo` from the parameter draws, which it fetches for them; the window totals are `BatchLogLikSession.summarize_windows`, taken while the
-  fit is resident."""
+  the latent paths and the predictive trajectories on the device): consecutive positions of a batch,
+  series b keyed by positions[0] + b.  Its session (`_native.BatchLogLikSession`) has the effect
+  summary and the window totals; it keeps no latent draws, hence no component summary, and prediction
+  errors and placebo forecasts are filtered in numpy from the parameter draws."""
   from causalimpact import _hmc  # pylint: disable=import-outside-toplevel
   dev, _, ids = launch
   ids = np.asarray(ids, dtype=np.int64)
   mo, io = fit.model_options, fit.inference_options
-  scale, shift = fit.scale[ids], fit.shift[ids]
-  wsum = {}
 
-  def after_summary(sess):       # (the session still open: the window totals, then the pool step)
-    if fit.windows is not None:
-      wsum.update(sess.summarize_windows(scale, shift, fit.observed[ids], fit.windows.first[ids],
-                                         fit.windows.count[ids], fit.ranks))
+  def resident(sess):            # (the session still open: the summaries, then the pool step)
+    record = lib.take_summaries(
+        sess, _launch_request(fit, ids, fit.observed[ids], fit.flags),
+        _series_inputs(fit, ids, np.zeros((0, fit.y.shape[1]), np.uint8), ()))
     if chain is not None:
-      chain.step(launch, chain.session_pool(sess, scale, shift))
+      chain.step(launch, chain.session_pool(sess, fit.scale[ids], fit.shift[ids]))
+    return record
 
   res = _hmc.fit_hmc_batch(
       fit.y[ids], fit.mask[ids], None if fit.design is None else fit.design[ids],
       [fit.params[b] for b in ids], has_slope=mo.local_linear_trend, num_results=io.num_results,
       num_warmup=io.num_warmup_steps, num_chains=io.num_chains, seed=fit.seed, device=dev,
       series_offset=int(ids[0]), shared_streams=fit.shared_streams, prior=io.hmc_prior,
-      summary=dict(scale=scale, shift=shift, observed=fit.observed[ids],
-                   flags=fit.flags, ranks=fit.ranks),
-      after_summary=after_summary if chain is not None or fit.windows is not None else None,
-      also_fetch=("slope_scale", "weights")
-      if io.prediction_errors or fit.placebo_origins is not None else ())
-  psum = None
-  if io.prediction_errors:
-    draws = {k: res[k] for k in _PARAMETER_DRAWS if k in res}
-    psum = _host_predictions(fit, ids, fit.y.shape[1], draws, np.zeros((0, fit.y.shape[1]), np.uint8))
-  plsum = None
-  if fit.placebo_origins is not None:
-    draws = {k: res[k] for k in _PARAMETER_DRAWS if k in res}
-    plsum = _host_placebo(fit, ids, draws, np.zeros((0, fit.y.shape[1]), np.uint8))
-  return ({k: res[k] for k in ("posterior_means", *_DRAW_SCALARS)}, res["summary"], None, psum,
-          wsum or None, plsum)
+      resident=resident)
+  return {k: res[k] for k in ("posterior_means", *_DRAW_SCALARS)}, res["resident"]
 
 
-def _scatter(parts, num_series: int, num_steps: int, whole, fill) -> Dict[str, np.ndarray]:
-  """{name: [num_series, ...]} of parts = [(positions, {name: [len(positions), ...]})].  The names
-  in `whole` have no time axis; the others are arrays over time (last axis), padded from a launch's
-  stride to `num_steps` with `fill`."""
+def _scatter(parts, num_series: int, num_steps: int, kind: str) -> Dict[str, np.ndarray]:
+  """{name: [num_series, ...]} of parts = [(positions, {name: [len(positions), ...]})], arrays of
+  `kind`: those over time (last axis) are padded from a launch's stride to `num_steps` with the
+  kind's fill."""
+  whole, fill = _KINDS[kind]
   out = {k: (np.zeros((num_series,) + v.shape[1:], v.dtype) if k in whole else
              np.full((num_series,) + v.shape[1:-1] + (num_steps,), fill, v.dtype))
          for k, v in parts[0][1].items()}
@@ -1690,39 +1598,31 @@ def _scatter(parts, num_series: int, num_steps: int, whole, fill) -> Dict[str, n
 
 
 def _assemble(launches, run, num_series: int, num_steps: int):
-  """Runs `launches` [(device, key, positions)] through `run(launch) -> (out, dsum, csum[, psum])`
+  """Runs `launches` [(device, key, positions)] through `run(launch) -> (out, record)`
   (`_run_launch`; the launches of a device in turn, the devices side by side) and puts the series
   axis back together.  Returns what the containers take:
     means [B, T_max]  the chain mean of posterior_means, 0 beyond a series' length;
-    dsum              the device summary {name: [B, ...]}: the order statistics over time NaN beyond
-                      a series' length;
-    diag_draws        {name: [B, C, S]} of `_DRAW_SCALARS`, or None for one chain;
-    csum              the component summary {name: [B, ...]}, NaN beyond a series' length (the
-                      `_PER_COLUMN` arrays have no time axis), or None when `run` returns none;
-    psum              (only when `run` returns four values) the prediction summary {name: [B, ...]}
-                      likewise (loglik has no time axis), or None;
-    wsum              (only when `run` returns five values) the window totals {name: [B, W, ...]} (no
-                      time axis), or None;
-    plsum             (only when `run` returns six values) the placebo summary {name: [B, O]} (no
-                      time axis), or None.
+    record            the `lib.SummaryRecord` {name: [B, ...]} per kind (None: a kind the launches
+                      did not take); arrays over time are NaN beyond a series' length;
+    diag_draws        {name: [B, C, S]} of `_DRAW_SCALARS`, or None for one chain.
   One launch that holds all B series in order at full stride is the result as it stands: its blocks
   (512 series: 24 MB of summary in pinned memory) are not copied a second time."""
   results = lib.map_by_device(run, launches)
-  # per launch: the chain mean with the scalar draws, the device summary, the component summary
-  groups = [(dict({k: out[k] for k in _DRAW_SCALARS}, means=out["posterior_means"].mean(axis=1)),
-             *summaries) for out, *summaries in results]
-  fetched, dsum, *optional = groups[0]
-  if not (len(launches) == 1 and list(launches[0][2]) == list(range(num_series))
-          and fetched["means"].shape[-1] == num_steps):
-    def gather(i, whole, fill):
-      parts = [(list(launch[2]), group[i]) for launch, group in zip(launches, groups)]
-      return _scatter(parts, num_series, num_steps, whole, fill)
-    fetched, dsum = gather(0, _DRAW_SCALARS, 0), gather(1, _PER_DRAW, np.nan)
-    optional = [None if one is None else gather(2 + i, whole, np.nan)
-                for i, (one, whole) in enumerate(zip(optional, (_PER_COLUMN, _PER_DRAW_LOGLIK, _PER_DRAW, _PLACEBO)))]
+  # per launch: the chain mean with the scalar draws
+  fetched = [dict({k: out[k] for k in _DRAW_SCALARS}, means=out["posterior_means"].mean(axis=1))
+             for out, _ in results]
+  if (len(launches) == 1 and list(launches[0][2]) == list(range(num_series))
+      and fetched[0]["means"].shape[-1] == num_steps):
+    fetched, record = fetched[0], results[0][1]
+  else:
+    def gather(kind, per_launch):
+      return _scatter([(list(launch[2]), arrays) for launch, arrays in zip(launches, per_launch)],
+                      num_series, num_steps, kind)
+    fetched = gather("fetched", fetched)
+    record = results[0][1].map(lambda kind, _: gather(kind, [getattr(rec, kind) for _, rec in results]))
   means = fetched.pop("means")
   diag_draws = fetched if fetched[_DRAW_SCALARS[0]].shape[1] > 1 else None
-  return (means, dsum, diag_draws, *optional)
+  return means, record, diag_draws
 
 
 def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
@@ -1885,15 +1785,13 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     run = lambda launch: _run_hmc_launch(launch, fit, chain)          # pylint: disable=unnecessary-lambda-assignment
   else:
     run = lambda launch: _run_launch(launch, "ordinary", fit, chain)   # pylint: disable=unnecessary-lambda-assignment
-  means, dsum, diag_draws, csum, psum, wsum, plsum = _assemble(
-      launches, run if chain is None else chain.guarded(run), B, T)
+  means, record, diag_draws = _assemble(launches, run if chain is None else chain.guarded(run), B, T)
   res = CausalImpactBatchAnalysis(
-      prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws, csum, psum,
+      prep, names, alpha, means, record.effect, fit.ranks, columns, diag_draws, record,
       _state_dim(model_options, inference_options),
-      None if placebo is None else dict(summary=plsum, origins=pl_plan[0], horizon=pl_plan[1],
-                                        n_post=pl_post))
+      None if placebo is None else dict(origins=pl_plan[0], horizon=pl_plan[1], n_post=pl_post))
   if plan is not None:
-    res.window_summary = _window_summary(res, plan, wsum)
+    res.window_summary = _window_summary(res, plan, record.windows)
   if chain is not None:
     # the posterior means on the data scale with the statistics every series' own frame uses
     mu, sd = scaler_stats(prep.values[:, prep.model_rows[:prep.num_pre], 0])
@@ -2053,15 +1951,14 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   launches = panel_launches(route, inference_options.devices, shared_streams)
   chain = None if plan is None else _PoolChain(launches, plan.csr, plan.axes)
   run = lambda launch: _run_launch(launch, kind, fit, chain)   # pylint: disable=unnecessary-lambda-assignment
-  means, dsum, diag_draws, csum, psum, wsum, plsum = _assemble(
-      launches, run if chain is None else chain.guarded(run), B, prep.y.shape[1])
+  means, record, diag_draws = _assemble(launches, run if chain is None else chain.guarded(run), B,
+                                        prep.y.shape[1])
   res = CausalImpactPanelAnalysis(
-      prep, names, alpha, means, dsum, fit.ranks, columns, diag_draws, csum, psum,
+      prep, names, alpha, means, record.effect, fit.ranks, columns, diag_draws, record,
       _state_dim(model_options, inference_options),
-      None if placebo is None else dict(summary=plsum, origins=pl_plan[0], horizon=pl_plan[1],
-                                        n_post=pl_post))
+      None if placebo is None else dict(origins=pl_plan[0], horizon=pl_plan[1], n_post=pl_post))
   if wplan is not None:
-    res.window_summary = _window_summary(res, wplan, wsum)
+    res.window_summary = _window_summary(res, wplan, record.windows)
   if chain is not None:
     # the posterior means on the data scale with the statistics every series' own frame uses
     data_means = []

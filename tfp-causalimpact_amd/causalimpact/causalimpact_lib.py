@@ -17,7 +17,7 @@ against the reference's own output by tests/test_golden_postprocessing.py.
 import collections.abc
 import dataclasses
 import math
-from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import pandas as pd
@@ -270,28 +270,16 @@ def fit_causalimpact(data: pd.DataFrame,
       standardize_data=data_options.standardize_data, dtype=data_options.dtype)
   if not 0 < alpha < 1:
     raise ValueError("`alpha` must be between 0 and 1.")
-  request = (_device_summary_request(ci_data, alpha) if inference_options.summarize_on_device
-             else None)
+  base = _device_summary_request(ci_data, alpha)
   windows = None
   if effect_windows is not None:
     windows = resolve_windows(effect_windows, ci_data.data.index,
                               posterior_processing.model_index(ci_data), ci_data.post_period)
-    if request is not None:
-      request["windows"] = windows
-  comp_request = None
-  if inference_options.components:
-    base = request if request is not None else _device_summary_request(ci_data, alpha)
-    comp_request = dict(scale=base["scale"], shift=base["shift"], quantiles=base["quantiles"])
-  pred_request = None
   if inference_options.prediction_errors:
     state_dim = check_prediction_state(model_options.local_linear_trend, model_options.seasons)
-    base = request if request is not None else _device_summary_request(ci_data, alpha)
-    pred_request = dict(scale=base["scale"], shift=base["shift"], quantiles=base["quantiles"],
-                        observed=base["observed"])
-  placebo_request = None
+  placebo_part = None
   placebo = resolve_placebo(placebo)
   if placebo is not None:
-    base = request if request is not None else _device_summary_request(ci_data, alpha)
     n_post = int(np.count_nonzero(base["flags"] & 2))
     n_pre = base["flags"].shape[0] - ci_data.model_after_pre_data.shape[0]
     horizon, origins = placebo_plan(
@@ -300,26 +288,33 @@ def fit_causalimpact(data: pd.DataFrame,
       raise ValueError(f"placebo: a pre-period of {n_pre} steps has no room for an origin with "
                        f"horizon {horizon} and the history it needs")
     if origins.size:
-      placebo_request = dict(scale=base["scale"], shift=base["shift"], origins=origins, horizon=horizon)
-  samples, posterior_means, posterior_trajectories, device_summary = _run_sampler(
+      placebo_part = PlaceboPart(base["scale"], base["shift"], origins, horizon)
+  ranks = _summary_ranks(inference_options.num_chains * inference_options.num_results, base["quantiles"])
+  request = SummaryRequest(
+      scale=base["scale"], shift=base["shift"], observed=base["observed"], flags=base["flags"],
+      ranks=ranks, components=inference_options.components,
+      predictions=Affine(base["scale"], base["shift"]) if inference_options.prediction_errors else None,
+      windows=Windows([w.first for w in windows], [w.count for w in windows]) if windows else None,
+      placebo=placebo_part, on_device=inference_options.summarize_on_device,
+      keep_trajectories=trajectory_sink is not None)
+  samples, posterior_means, posterior_trajectories, record = _run_sampler(
       ci_data=ci_data, prior_level_sd=model_options.prior_level_sd, seed=seed,
       num_results=inference_options.num_results,
       num_warmup_steps=inference_options.num_warmup_steps, dtype=data_options.dtype,
       seasons=model_options.seasons, num_chains=inference_options.num_chains,
       devices=inference_options.devices, local_linear_trend=model_options.local_linear_trend,
-      sampler=inference_options.sampler, summary_request=request,
+      sampler=inference_options.sampler, request=request,
       hmc_init=inference_options.hmc_init, hmc_prior=inference_options.hmc_prior,
-      kernel_flags=inference_options.kernel_flags, component_request=comp_request,
-      keep_trajectories=trajectory_sink is not None, prediction_request=pred_request,
-      placebo_request=placebo_request)
+      kernel_flags=inference_options.kernel_flags)
   if trajectory_sink is not None:
-    base = request if request is not None else _device_summary_request(ci_data, alpha)
     trajectory_sink(posterior_means, posterior_trajectories, base["scale"], base["shift"])
   # (draws pooled on the host -- several devices, float64, HMC -- were summarised inside
   #  _run_sampler, in the sampler's internal units)
-  if device_summary is not None:
+  if record.effect is not None:
     series, summary, window_summary = _compute_impact_device(
-        posterior_means, device_summary, request, ci_data, alpha, windows=windows or ())
+        posterior_means, record.effect, base["observed"], base["flags"], ranks, ci_data, alpha,
+        windows=windows or (),
+        window_totals=None if record.windows is None else record.windows["per_draw"])
   else:
     series, summary, window_summary = _compute_impact(
         posterior_means=posterior_means, posterior_trajectories=posterior_trajectories,
@@ -337,13 +332,11 @@ def fit_causalimpact(data: pd.DataFrame,
       slope_scale=_tensor(samples["slope_scale"]) if model_options.local_linear_trend else None,
       slope=_tensor(samples["slope"]) if model_options.local_linear_trend else None)
   components = coefficients = None
-  if comp_request is not None:
-    num_draws = samples["level"].shape[0]
-    csum = comp_request.get("summary")
+  if inference_options.components:
+    csum = record.components
     if csum is None:
       # the routes that pool the draws on the host: the same definitions in numpy.  X is the design
       # as the sampler saw it (float64 for the float64 Gibbs kernels, float32 otherwise).
-      comp_request["ranks"] = _summary_ranks(num_draws, comp_request["quantiles"])
       X = None
       if has_weights:
         f64 = (cid._as_numpy_dtype(data_options.dtype) == np.float64   # pylint: disable=protected-access
@@ -351,23 +344,20 @@ def fit_causalimpact(data: pd.DataFrame,
         X = np.asarray(ci_data.feature_ts.values, np.float64 if f64 else np.float32)
       csum = _component_summary_host(samples["level"], samples["seasonal_levels"],
                                      samples["weights"] if has_weights else None, X,
-                                     comp_request["scale"], comp_request["shift"],
-                                     comp_request["ranks"])
+                                     base["scale"], base["shift"], ranks)
     components, coefficients = _component_frames(
-        csum, comp_request["ranks"], num_draws, alpha, posterior_processing.model_index(ci_data),
+        csum, ranks, samples["level"].shape[0], alpha, posterior_processing.model_index(ci_data),
         ci_data.data.index,
         list(ci_data.feature_ts.columns) if ci_data.feature_ts is not None else None)
   prediction_errors = fit_quality = None
-  if pred_request is not None:
+  if record.predictions is not None:
     prediction_errors, fit_quality = _prediction_frames(
-        pred_request["summary"], pred_request["ranks"], alpha, pred_request["observed"],
-        pred_request["conditioned"], state_dim, posterior_processing.model_index(ci_data),
-        ci_data.data.index)
+        record.predictions, ranks, alpha, base["observed"], ~_model_mask(ci_data), state_dim,
+        posterior_processing.model_index(ci_data), ci_data.data.index)
   placebo_frame = placebo_quality = None
   if placebo is not None:
     placebo_frame, placebo_quality = _placebo_frames(
-        None if placebo_request is None else placebo_request["summary"], origins, horizon, alpha,
-        base["observed"],
+        record.placebo, origins, horizon, alpha, base["observed"],
         posterior_processing.model_index(ci_data), n_post, summary.loc["cumulative", "rel_effect"])
   return CausalImpactAnalysis(series, summary, posterior, samples.get("diagnostics"), components,
                               coefficients, prediction_errors, fit_quality, window_summary,
@@ -1089,25 +1079,250 @@ def map_by_device(fn, work):
   return out
 
 
+# --------------------------------------------------------------------------------------
+# What a fit wants summarised where its draws lie, and what it got
+# --------------------------------------------------------------------------------------
+class Affine(NamedTuple):
+  """value = internal * scale + shift: scalars, or [B] for the series of a launch."""
+  scale: Any
+  shift: Any
+
+
+class Windows(NamedTuple):
+  """Sub-windows of the steps: first, count [W], or [B, W] for the series of a launch."""
+  first: Any
+  count: Any
+
+
+class PlaceboPart(NamedTuple):
+  """The placebo forecasts' own (scale, shift), origins [O] or [B, O] (-1: unused, at the end of a
+  row) and horizon (scalar or [B])."""
+  scale: Any
+  shift: Any
+  origins: Any
+  horizon: Any
+
+
+@dataclasses.dataclass(frozen=True)
+class SummaryRequest:
+  """What one fit -- a single series, or the series of one launch -- wants summarised over its
+  draws.  Whoever fills it in (`take_summaries`, `_run_sampler`) does not modify it; the answers come
+  back in a `SummaryRecord`."""
+  scale: Any                    # the effect summary (`_native.Session.summarize`): scalars or [B]
+  shift: Any
+  observed: np.ndarray          # [T] or [B, T] data-scale outcome, NaN: none
+  flags: np.ndarray             # [T] or [B, T] window flags
+  ranks: Sequence[int]          # the order statistics every kind returns (`_summary_ranks`)
+  components: bool = False
+  predictions: Optional[Affine] = None
+  windows: Optional[Windows] = None
+  placebo: Optional[PlaceboPart] = None
+  # (single fits) False: the effect and its windows are left to the host arithmetic of
+  # `_compute_impact`; keep_trajectories: the predictive draws are wanted on the host as well
+  on_device: bool = True
+  keep_trajectories: bool = False
+
+
+@dataclasses.dataclass(frozen=True)
+class SummaryRecord:
+  """What a fit got: per kind {name: [B, ...]} (`of_series`: one series' own), or None for a kind that
+  was not asked for or that this route leaves to the host."""
+  effect: Optional[Dict[str, np.ndarray]] = None
+  components: Optional[Dict[str, np.ndarray]] = None
+  predictions: Optional[Dict[str, np.ndarray]] = None
+  windows: Optional[Dict[str, np.ndarray]] = None
+  placebo: Optional[Dict[str, np.ndarray]] = None
+
+  def kinds(self):
+    return [(f.name, getattr(self, f.name)) for f in dataclasses.fields(self)]
+
+  def map(self, fn) -> "SummaryRecord":
+    """The record of fn(kind, arrays) for every kind that is there."""
+    return SummaryRecord(**{kind: None if arrays is None else fn(kind, arrays) for kind, arrays in self.kinds()})
+
+  def of_series(self, b: int) -> "SummaryRecord":
+    return self.map(lambda _, arrays: {k: v[b] for k, v in arrays.items()})
+
+
+class SummaryKind(NamedTuple):
+  """How the arrays of one kind are laid out: series first and, but for the names in `whole`, time
+  last -- cut to a series' length, and padded with `fill` beyond it when launches are put together."""
+  whole: Tuple[str, ...]
+  fill: float
+
+
+SUMMARY_KINDS = {
+    "effect": SummaryKind(("per_draw", "per_draw_order"), np.nan),            # [B, 2, draws | R]
+    "components": SummaryKind(("inclusion_prob", "weight_mean", "weight_order"), np.nan),   # [B, ..., P]
+    "predictions": SummaryKind(("loglik",), np.nan),                          # [B, draws]
+    "windows": SummaryKind(("per_draw", "per_draw_order"), np.nan),           # [B, W, 2, draws | R]
+    "placebo": SummaryKind(("predicted_mean", "spread_mean", "pit_mean", "n_counted", "seen_sum"),
+                           np.nan)}                                           # [B, O]
+# the parameter draws the prediction errors and the placebo forecasts are filtered from on the host
+_PARAMETER_DRAWS = ("observation_noise_scale", "level_scale", "slope_scale", "seasonal_drift_scales",
+                    "weights")
+
+
+def _to_internal_units(scale, shift, cond_mu, cond_s) -> Affine:
+  """The caller's (scale, shift) as the map from the sampler's internal units
+  (`_internal_conditioning`: internal = (value - cond_mu) / cond_s) to the data scale, in float64."""
+  scale = np.asarray(scale, np.float64)
+  return Affine(scale * cond_s, np.asarray(shift, np.float64) + cond_mu * scale)
+
+
+def _request_in_internal_units(request: SummaryRequest, cond_mu, cond_s) -> SummaryRequest:
+  """`request` with every part's own (scale, shift) mapped by `_to_internal_units`."""
+  own = lambda part: _to_internal_units(part.scale, part.shift, cond_mu, cond_s)   # pylint: disable=unnecessary-lambda-assignment
+  return dataclasses.replace(
+      request, **own(request)._asdict(),
+      predictions=None if request.predictions is None else own(request.predictions),
+      placebo=None if request.placebo is None else request.placebo._replace(**own(request.placebo)._asdict()))
+
+
+@dataclasses.dataclass(frozen=True)
+class SeriesInputs:
+  """One series as its sampler saw it, for the summaries taken in numpy: y, mask [T], design [T, P]
+  or None (`seen`: the number format the sampler read them in), season_change [K, T], the model and
+  the parameter block (`_model.series_params`)."""
+  y: np.ndarray
+  mask: np.ndarray
+  design: Optional[np.ndarray]
+  season_change: np.ndarray
+  num_seasons: Sequence[int]
+  has_slope: bool
+  params: Dict
+  seen: Any = np.float32
+
+  def outcome(self) -> np.ndarray:
+    return np.where(self.mask, 0.0, self.y).astype(self.seen)
+
+  def filter_inputs(self):
+    """(y, mask, X, season_change, num_seasons, has_slope, params) of the host filters."""
+    return (self.outcome(), self.mask, None if self.design is None else self.design.astype(self.seen),
+            self.season_change, self.num_seasons, self.has_slope, self.params)
+
+
+def _pooled_draws(draws: Dict[str, np.ndarray], i: int) -> Dict[str, np.ndarray]:
+  """{name: [C * S, ...]} of series i of {name: [n, C, S, ...]}, chain-major."""
+  return {k: v[i].reshape((v.shape[1] * v.shape[2],) + v.shape[3:]) for k, v in draws.items()}
+
+
+def _host_prediction_summaries(inputs: Sequence[SeriesInputs], draws, own: Affine, ranks):
+  """The prediction summary {name: [n, ...]} of n series in numpy (`_prediction_summary_host`) from
+  their parameter draws {name: [n, C, S, ...]} (a name the model lacks may be missing): the routes
+  whose models the device filter does not take.  Over the steps of the longest series, with the
+  padding convention of the device beyond a series' length."""
+  n, R, num_steps = len(inputs), len(ranks), max(i.y.shape[0] for i in inputs)
+  scale, shift = (np.broadcast_to(np.asarray(a, np.float64), (n,)) for a in own)
+  out = None
+  for i, one in enumerate(inputs):
+    got = _prediction_summary_host(*one.filter_inputs(), _pooled_draws(draws, i), scale[i], shift[i], ranks)
+    if out is None:
+      out = dict(forecast_mean=np.zeros((n, num_steps)), forecast_order=np.zeros((n, R, num_steps)),
+                 variance_mean=np.zeros((n, num_steps)), pit_mean=np.zeros((n, num_steps)),
+                 loglik=np.zeros((n, got["loglik"].shape[0])))
+    out["forecast_mean"][i], out["forecast_order"][i] = shift[i], shift[i]
+    for k, v in got.items():
+      out[k][i, ..., :v.shape[-1]] = v
+  return out
+
+
+def _host_placebo_summaries(inputs: Sequence[SeriesInputs], draws, part: PlaceboPart):
+  """The same for the placebo summary (`_placebo_summary_host`; `part` per series: `_per_series`); a
+  series without an origin stays at zero."""
+  out = {k: np.zeros(part.origins.shape) for k in SUMMARY_KINDS["placebo"].whole[:3]}
+  for i, one in enumerate(inputs):
+    if np.any(part.origins[i] >= 0):
+      got = _placebo_summary_host(*one.filter_inputs(), _pooled_draws(draws, i), part.scale[i],
+                                  part.shift[i], part.origins[i], part.horizon[i])
+      for k, v in got.items():
+        out[k][i] = v
+  return out
+
+
+def _device_placebo_summaries(sess, part: PlaceboPart):
+  """The placebo summary {name: [n, O]} of an open session (`summarize_placebo`): the launch's own
+  origin slots (never more than its steps), the horizon of a series without origin raised to the 1
+  the entry asks for."""
+  width = max(1, int((part.origins >= 0).sum(axis=1).max()))
+  got = sess.summarize_placebo(part.scale, part.shift, part.origins[:, :width], np.maximum(part.horizon, 1))
+  out = {k: np.zeros(part.origins.shape) for k in got}
+  for k, v in got.items():
+    out[k][:, :width] = v
+  return out
+
+
+def _per_series(part: PlaceboPart, n: int) -> PlaceboPart:
+  """`part` with one row per series: scale, shift, horizon [n], origins [n, O]."""
+  origins = np.asarray(part.origins)
+  return PlaceboPart(np.broadcast_to(np.asarray(part.scale, np.float64), (n,)),
+                     np.broadcast_to(np.asarray(part.shift, np.float64), (n,)),
+                     np.broadcast_to(origins, (n, origins.shape[-1])),
+                     np.broadcast_to(np.asarray(part.horizon), (n,)))
+
+
+def _with_placebo_seen(inputs: Sequence[SeriesInputs], part: PlaceboPart, plsum):
+  """`plsum` {name: [n, O]} with `_placebo_seen`'s n_counted and seen_sum of every series."""
+  seen = [_placebo_seen(one.outcome(), one.mask, part.origins[i], part.horizon[i],
+                        part.scale[i], part.shift[i]) for i, one in enumerate(inputs)]
+  return dict(plsum, n_counted=np.stack([c for c, _ in seen]), seen_sum=np.stack([a for _, a in seen]))
+
+
+def take_summaries(sess, request: SummaryRequest,
+                   series_inputs: Optional[Sequence[SeriesInputs]] = None) -> SummaryRecord:
+  """Fills the record of `request` from the finished, still open session `sess`: `summarize`,
+  `summarize_components`, `summarize_predictions`, `summarize_windows`, `summarize_placebo`, in this
+  order for every caller -- every entry uploads its own arguments and leaves nothing behind for the
+  next (tests/test_gpu_summaries_together.py).  `sess.summaries` names the kinds a session has.
+  Prediction errors and placebo forecasts are filtered on the device where the session has the
+  entries and `device_predictions_supported` takes the model; else in numpy from the parameter draws,
+  fetched once for both, over `series_inputs` (one per series of the session; read for these two
+  kinds only).  Components a session lacks stay None: the caller's business.  The scales and shifts
+  map the SESSION's units to the data scale (`_request_in_internal_units`)."""
+  effect = sess.summarize(request.scale, request.shift, request.observed, request.flags, request.ranks)
+  if effect["value_order"].ndim == 2:      # (`Session.summarize` drops the series axis of one series)
+    effect = {k: v[None] for k, v in effect.items()}
+  components = predictions = windows = placebo = draws = None
+  if request.components and "components" in sess.summaries:
+    components = sess.summarize_components(request.scale, request.shift, request.ranks)
+  on_host = (request.predictions is not None or request.placebo is not None) and not (
+      {"predictions", "placebo"} <= set(sess.summaries)
+      and device_predictions_supported(series_inputs[0].num_seasons))
+  if on_host:
+    draws = sess.fetch(list(_PARAMETER_DRAWS))
+  if request.predictions is not None:
+    predictions = (_host_prediction_summaries(series_inputs, draws, request.predictions, request.ranks)
+                   if on_host else sess.summarize_predictions(*request.predictions, request.ranks))
+  if request.windows is not None:
+    windows = sess.summarize_windows(request.scale, request.shift, request.observed, *request.windows,
+                                     request.ranks)
+  if request.placebo is not None:
+    part = _per_series(request.placebo, len(series_inputs))
+    placebo = _with_placebo_seen(series_inputs, part, _host_placebo_summaries(series_inputs, draws, part)
+                                 if on_host else _device_placebo_summaries(sess, part))
+  return SummaryRecord(effect=effect, components=components, predictions=predictions, windows=windows,
+                       placebo=placebo)
+
+
+def _model_mask(ci_data) -> np.ndarray:
+  """[T] bool: the steps the model does not condition on -- the missing pre-period values and, as
+  missing observations, everything after the pre-period (forecasting == sampling, :548-562)."""
+  return np.concatenate([np.asarray(ci_data.outcome_ts.is_missing, bool),
+                         np.ones(ci_data.model_after_pre_data.shape[0], bool)])
+
+
 def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps, model=None,
                  dtype=np.float32, seasons=(), num_chains=1, devices=None,
-                 local_linear_trend=False, sampler="gibbs", summary_request=None,
-                 hmc_init="gibbs", hmc_prior="slab", kernel_flags=0, component_request=None,
-                 keep_trajectories=False, prediction_request=None, placebo_request=None):
-  """_train_causalimpact_sts plus, when `summary_request` is given (single device, Gibbs), the
-  on-device summary of the predictive draws; the [draws, T] trajectories then stay in HBM and
-  are returned as None.  `component_request` (scale, shift, quantiles): on that route the component
-  summary of the session (ci_session_summarize_components) is left in it under "summary", with the
-  "ranks" it was taken at; on every other route the dict comes back as it went in.
-  `prediction_request` (scale, shift, quantiles): the prediction-error summary is left in it under
-  "summary" with its "ranks" and "conditioned" (the steps the model conditions on) -- taken on the
-  device on that route (ci_session_summarize_predictions; a trend with at most one block of 2-7
-  seasons), by `_prediction_summary_host` from the parameter draws on every other.
-  `placebo_request` (scale, shift, origins, horizon): the placebo summary is left in it under
-  "summary" (predicted_mean, spread_mean, pit_mean and `_placebo_seen`'s n_counted, seen_sum, each
-  [O]) -- ci_session_summarize_placebo or `_placebo_summary_host`, routed like the prediction errors.
-  `keep_trajectories`: the trajectories are wanted on the host; the fit then takes the route of
-  draws pooled on the host, whose summary runs the same kernels on the same values."""
+                 local_linear_trend=False, sampler="gibbs", request: Optional[SummaryRequest] = None,
+                 hmc_init="gibbs", hmc_prior="slab", kernel_flags=0):
+  """_train_causalimpact_sts plus the `SummaryRecord` of `request` (on the caller's scale; None: an
+  empty record), the record of ONE series (`SummaryRecord.of_series`).  On one device, with the
+  float32 Gibbs sampler and unless `request.on_device` is off or it wants the trajectories kept, the
+  fit stays in a session for `take_summaries`; the [draws, T] trajectories then stay in HBM and are
+  returned as None.  On every other route the draws are pooled on the host: the effect and its
+  windows run the same kernels on the same values (`_native.summarize_draws`,
+  `_native.window_totals_host`; left out with `request.on_device` off), prediction errors and placebo
+  forecasts are filtered in numpy, and the components stay None for the caller's pooled draws."""
   if model is not None:
     raise NotImplementedError("custom tfp.sts models are not supported by the HIP path")
   seed_pair = _sanitize_seed(seed)
@@ -1124,8 +1339,7 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
   # Post-period handled as missing observations: forecasting == sampling (:548-562).
   n_after = ci_data.model_after_pre_data.shape[0]
   y = np.concatenate([_outcome_float64(ci_data), np.full(n_after, np.nan)])
-  mask = np.concatenate([np.asarray(ci_data.outcome_ts.is_missing, bool),
-                         np.ones(n_after, bool)])
+  mask = _model_mask(ci_data)
   T = y.shape[0]
   cond_mu, cond_s = _internal_conditioning(ci_data)
   if (cond_mu, cond_s) != (0.0, 1.0):
@@ -1147,10 +1361,14 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
     raise ValueError(f"sampler must be 'gibbs' or 'hmc', got {sampler!r}")
   devs = list(devices) if devices else [0]
   shares = np.array_split(np.arange(num_chains), len(devs))
-  device_summary = None
+  # the float64 Gibbs kernels read the outcome and the design in float64, every other sampler in float32
+  inputs = [SeriesInputs(y, mask, design, season_change, num_seasons, local_linear_trend, params,
+                         np.float64 if np_dtype == np.float64 and sampler == "gibbs" else np.float32)]
+  internal = None if request is None else _request_in_internal_units(request, cond_mu, cond_s)
+  record = SummaryRecord()
   def run_on(dev, chain_ids):
     """One device's share of the chains (chain ids keep their global RNG streams)."""
-    nonlocal device_summary
+    nonlocal record
     if sampler == "hmc":
       from causalimpact import _hmc  # pylint: disable=import-outside-toplevel
       res = _hmc.fit_hmc(y, mask, design, params, has_slope=local_linear_trend,
@@ -1168,7 +1386,7 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
       # float64 compute (csrc/ci_gibbs64.h): the sequential kernel, every buffer float64
       return _native.fit_gibbs_f64(pb, y[None], mask[None], None if design is None else design[None],
                                    season_change, _native.make_params([params]))
-    if summary_request is not None and len(devs) == 1 and not keep_trajectories:
+    if internal is not None and internal.on_device and len(devs) == 1 and not internal.keep_trajectories:
       sess = _native.Session(pb, y[None], mask[None], None if design is None else design[None],
                              season_change, _native.make_params([params]))
       try:
@@ -1178,51 +1396,7 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
             want=[k for k in _native._OUT_FIELDS  # pylint: disable=protected-access
                   if k != "posterior_trajectories" and (k != "slope" or local_linear_trend)],
             chunk_draws=32)
-        summary_request["ranks"] = _summary_ranks(len(chain_ids) * num_results,
-                                                  summary_request["quantiles"])
-        # value = trajectory * scale + shift, the trajectory being in the internal units
-        device_summary = sess.summarize(
-            scale=np.asarray(summary_request["scale"], np.float64) * cond_s,
-            shift=(np.asarray(summary_request["shift"], np.float64)
-                   + cond_mu * np.asarray(summary_request["scale"], np.float64)),
-            **{k: summary_request[k] for k in ("observed", "flags", "ranks")})
-        if summary_request.get("windows"):
-          # the same conditioned (scale, shift): every draw's totals over the windows' own columns
-          summary_request["window_totals"] = sess.summarize_windows(
-              scale=np.asarray(summary_request["scale"], np.float64) * cond_s,
-              shift=(np.asarray(summary_request["shift"], np.float64)
-                     + cond_mu * np.asarray(summary_request["scale"], np.float64)),
-              observed=summary_request["observed"],
-              first=[w.first for w in summary_request["windows"]],
-              count=[w.count for w in summary_request["windows"]],
-              ranks=summary_request["ranks"])["per_draw"][0]
-        if component_request is not None:
-          component_request["ranks"] = _summary_ranks(len(chain_ids) * num_results,
-                                                      component_request["quantiles"])
-          csum = sess.summarize_components(
-              scale=np.float64(component_request["scale"]) * cond_s,
-              shift=np.float64(component_request["shift"]) + cond_mu * np.float64(component_request["scale"]),
-              ranks=component_request["ranks"])
-          csum = {k: v[0] for k, v in csum.items()}
-          if cond_s != 1.0:                 # the weights on the caller's model scale, as in `samples`
-            for k in ("weight_mean", "weight_order"):
-              if k in csum:
-                csum[k] = csum[k] * cond_s
-          component_request["summary"] = csum
-        if prediction_request is not None and device_predictions_supported(num_seasons):
-          prediction_request["ranks"] = _summary_ranks(len(chain_ids) * num_results,
-                                                       prediction_request["quantiles"])
-          psum = sess.summarize_predictions(
-              scale=np.float64(prediction_request["scale"]) * cond_s,
-              shift=np.float64(prediction_request["shift"]) + cond_mu * np.float64(prediction_request["scale"]),
-              ranks=prediction_request["ranks"])
-          prediction_request["summary"] = {k: v[0] for k, v in psum.items()}
-        if placebo_request is not None and device_predictions_supported(num_seasons):
-          plsum = sess.summarize_placebo(
-              scale=np.float64(placebo_request["scale"]) * cond_s,
-              shift=np.float64(placebo_request["shift"]) + cond_mu * np.float64(placebo_request["scale"]),
-              origins=placebo_request["origins"], horizon=placebo_request["horizon"])
-          placebo_request["summary"] = {k: v[0] for k, v in plsum.items()}
+        record = take_summaries(sess, internal, inputs)
       finally:
         sess.close()
       return part
@@ -1234,63 +1408,35 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
   out = ({k: v[0] for k, v in parts[0].items()} if len(parts) == 1 else              # [C, ...]
          {k: np.concatenate([p[k][0] for p in parts], axis=0) for k in parts[0]})
 
-  if (summary_request is not None and device_summary is None
-      and "posterior_trajectories" in out):
+  if internal is not None and record.effect is None:
     # draws pooled on the host (several devices, the float64 kernels, the HMC path): the summary
     # kernels read float32 trajectories, so they get them in the INTERNAL (conditioned) units --
     # O(1) values -- with the map to the caller's scale folded into (scale, shift) in float64, as
     # on the single-device path.  Summarising the rescaled draws would round the offset back in
     # (8e-6 steps at y ~ 100).
-    tr = out["posterior_trajectories"]
-    summary_request["ranks"] = _summary_ranks(tr.shape[0] * tr.shape[1], summary_request["quantiles"])
-    device_summary = _native.summarize_draws(
-        tr.reshape((tr.shape[0] * tr.shape[1],) + tr.shape[2:]),
-        float(summary_request["scale"]) * cond_s,
-        float(summary_request["shift"]) + cond_mu * float(summary_request["scale"]),
-        summary_request["observed"], summary_request["flags"], summary_request["ranks"],
-        device=devs[0])
-    if summary_request.get("windows"):
-      # ... and the window totals from exactly these trajectories and this (scale, shift)
-      summary_request["window_totals"] = _native.window_totals_host(
-          tr.reshape((1, tr.shape[0] * tr.shape[1]) + tr.shape[2:]),
-          float(summary_request["scale"]) * cond_s,
-          float(summary_request["shift"]) + cond_mu * float(summary_request["scale"]),
-          summary_request["observed"], [w.first for w in summary_request["windows"]],
-          [w.count for w in summary_request["windows"]])[0]
-  if prediction_request is not None:
-    prediction_request["conditioned"] = ~mask
-    if "summary" not in prediction_request:
-      # the routes without a session: the same definitions in numpy, from the parameter draws in the
-      # sampler's units, on the outcome and design as the sampler saw them (float64 for the float64
-      # Gibbs kernels, float32 otherwise)
-      f64 = np_dtype == np.float64 and sampler == "gibbs"
-      seen = np.float64 if f64 else np.float32
-      fields = ("observation_noise_scale", "level_scale", "slope_scale", "seasonal_drift_scales", "weights")
-      draws = {k: out[k].reshape((out[k].shape[0] * out[k].shape[1],) + out[k].shape[2:]) for k in fields}
-      prediction_request["ranks"] = _summary_ranks(draws["level_scale"].shape[0],
-                                                   prediction_request["quantiles"])
-      prediction_request["summary"] = _prediction_summary_host(
-          np.where(mask, 0.0, y).astype(seen), mask, None if design is None else design.astype(seen),
-          season_change, num_seasons, local_linear_trend, params, draws,
-          np.float64(prediction_request["scale"]) * cond_s,
-          np.float64(prediction_request["shift"]) + cond_mu * np.float64(prediction_request["scale"]),
-          prediction_request["ranks"])
-  if placebo_request is not None:
-    # (the outcome and design as the sampler saw them: float64 for the float64 Gibbs kernels)
-    seen = np.float64 if np_dtype == np.float64 and sampler == "gibbs" else np.float32
-    y_seen = np.where(mask, 0.0, y).astype(seen)
-    pl_scale = np.float64(placebo_request["scale"]) * cond_s
-    pl_shift = np.float64(placebo_request["shift"]) + cond_mu * np.float64(placebo_request["scale"])
-    if "summary" not in placebo_request:
-      fields = ("observation_noise_scale", "level_scale", "slope_scale", "seasonal_drift_scales", "weights")
-      draws = {k: out[k].reshape((out[k].shape[0] * out[k].shape[1],) + out[k].shape[2:]) for k in fields}
-      placebo_request["summary"] = _placebo_summary_host(
-          y_seen, mask, None if design is None else design.astype(seen), season_change, num_seasons,
-          local_linear_trend, params, draws, pl_scale, pl_shift, placebo_request["origins"],
-          placebo_request["horizon"])
-    n_counted, seen_sum = _placebo_seen(y_seen, mask, placebo_request["origins"],
-                                        placebo_request["horizon"], pl_scale, pl_shift)
-    placebo_request["summary"].update(n_counted=n_counted, seen_sum=seen_sum)
+    effect = windows = predictions = placebo = None
+    if internal.on_device:
+      tr = out["posterior_trajectories"]
+      tr = tr.reshape((1, tr.shape[0] * tr.shape[1]) + tr.shape[2:])
+      effect = {k: v[None] for k, v in _native.summarize_draws(
+          tr[0], internal.scale, internal.shift, internal.observed, internal.flags, internal.ranks,
+          device=devs[0]).items()}
+      if internal.windows is not None:
+        # ... and the window totals from exactly these trajectories and this (scale, shift)
+        windows = dict(per_draw=_native.window_totals_host(
+            tr, internal.scale, internal.shift, internal.observed, *internal.windows))
+    # the same definitions in numpy, from the parameter draws in the sampler's units
+    draws = {k: out[k][None] for k in _PARAMETER_DRAWS}
+    if internal.predictions is not None:
+      predictions = _host_prediction_summaries(inputs, draws, internal.predictions, internal.ranks)
+    if internal.placebo is not None:
+      part = _per_series(internal.placebo, 1)
+      placebo = _with_placebo_seen(inputs, part, _host_placebo_summaries(inputs, draws, part))
+    record = SummaryRecord(effect=effect, predictions=predictions, windows=windows, placebo=placebo)
+  if record.components is not None and cond_s != 1.0:
+    # the weights on the caller's model scale, as in `samples`
+    record = dataclasses.replace(record, components={
+        k: v * cond_s if k in ("weight_mean", "weight_order") else v for k, v in record.components.items()})
   if (cond_mu, cond_s) != (0.0, 1.0):
     # back to the caller's scale, in float64: locations get the offset, everything else the scale
     out = {k: np.asarray(v, np.float64) * cond_s for k, v in out.items()}
@@ -1322,7 +1468,7 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
     tr = out["posterior_trajectories"]
     posterior_trajectories = tr.reshape((tr.shape[0] * tr.shape[1],) + tr.shape[2:]).astype(
         pred_dtype, copy=False)
-  return samples, posterior_means, posterior_trajectories, device_summary
+  return samples, posterior_means, posterior_trajectories, record.of_series(0)
 
 
 # --------------------------------------------------------------------------------------
@@ -1409,8 +1555,7 @@ def _device_summary_request(ci_data: cid.CausalImpactData, alpha: float) -> Dict
     scale, shift = 1.0, 0.0
   return dict(scale=scale, shift=shift, observed=obs,
               flags=after_start.astype(np.uint8) | (window.astype(np.uint8) << 1),
-              quantiles=(alpha / 2.0, 1.0 - alpha / 2.0),
-              ranks=None)   # filled in by _run_sampler once the number of draws is known
+              quantiles=(alpha / 2.0, 1.0 - alpha / 2.0))
 
 
 def _lerp_order_stats(order: Dict[int, np.ndarray], lo: int, hi: int, gamma) -> np.ndarray:
@@ -1431,18 +1576,17 @@ def _per_draw_means(pred_sum, point_sum, num_steps: int, num_observed: int) -> D
                 point_sum_t=point_sum)
 
 
-def _compute_impact_device(posterior_means, device_summary: Dict, request: Dict,
-                           ci_data: cid.CausalImpactData, alpha: float,
-                           windows: Optional[Sequence[EffectWindow]] = None):
+def _compute_impact_device(posterior_means, device_summary: Dict, obs: np.ndarray, flags: np.ndarray,
+                           ranks: Sequence[int], ci_data: cid.CausalImpactData, alpha: float,
+                           windows: Optional[Sequence[EffectWindow]] = None, window_totals=None):
   """(series, summary) from the on-device summary (csrc/ci_summary.h) -- same frames as
-  _compute_impact, which stays the host reference of this arithmetic.  With `windows` (series,
-  summary, window_summary): the summary of every `EffectWindow` from request["window_totals"]
-  [W, 2, N], every draw's totals over it (csrc/ci_windows.h)."""
+  _compute_impact, which stays the host reference of this arithmetic.  obs, flags [T] and ranks: what
+  the summary was taken with.  With `windows` (series, summary, window_summary): the summary of every
+  `EffectWindow` from `window_totals` [W, 2, N], every draw's totals over it (csrc/ci_windows.h)."""
   quantiles = (alpha / 2.0, 1.0 - alpha / 2.0)
   observed_post, observed_full = _observed_series(ci_data)
   idx = posterior_processing.model_index(ci_data)
-  obs = request["observed"]
-  ranks = list(request["ranks"])
+  ranks = list(ranks)
   num_draws = device_summary["per_draw"].shape[1]
   value_order = {r: device_summary["value_order"][i] for i, r in enumerate(ranks)}
   cum_order = {r: device_summary["cum_order"][i] for i, r in enumerate(ranks)}
@@ -1469,7 +1613,7 @@ def _compute_impact_device(posterior_means, device_summary: Dict, request: Dict,
   series = _compute_impact_estimates(posterior_trajectory_summary=trajectory_summary,
                                      trajectory_dict=None, observed_ts_full=observed_full,
                                      ci_data=ci_data, quantiles=quantiles, bands=bands)
-  window = (request["flags"] & 2) != 0
+  window = (flags & 2) != 0
   n_obs_window = int(np.sum(~np.isnan(obs[window])))
   pred_sum, point_sum = device_summary["per_draw"]
   per_draw = _per_draw_means(pred_sum, point_sum, int(window.sum()), n_obs_window)
@@ -1482,7 +1626,7 @@ def _compute_impact_device(posterior_means, device_summary: Dict, request: Dict,
 
   def table_of(w, win):
     steps = slice(win.first, win.first + win.count)
-    totals = request["window_totals"][w]
+    totals = window_totals[w]
     return _compute_summary(
         posterior_trajectory_summary=trajectory_summary, trajectory_dict=None,
         observed_ts_post=observed_post, post_period=(win.start, win.end), quantiles=quantiles,
