@@ -452,6 +452,68 @@ int ci_session_summarize_windows(ci_session* session, const double* scale, const
                                  const int32_t* first, const int32_t* count,
                                  int32_t num_ranks, const int32_t* ranks,
                                  double* per_draw, double* per_draw_order);
+/* Simultaneous bands and a whole-path test of the effect: for every draw the largest standardised
+ * excursion of its WHOLE path over a window, for the prediction and for the cumulative effect.  A
+ * pointwise band is no statement about a path, and the total of a window misses an effect that rises
+ * and then reverses; the 1 - alpha quantile c of the excursions gives the band center -+ c * spread
+ * that holds the whole path with probability 1 - alpha, and the share of draws whose excursion
+ * reaches the observed one a p-value for "the observed path is unlike every predictive path".
+ * Additive: CI_ABI_VERSION stays 5; look the symbol up (dlsym) where an older library may be met.
+ * The [B, N, T] float32 trajectories (N = C*S pooled draws, chain-major; T the session's stride) are
+ * read where they are, in HBM, and only the columns of the 64-step tiles a window intersects; no
+ * [B, T, N] matrix of a whole series is built.  Series b has the num_windows windows first[b, w],
+ * count[b, w] (steps of the session; windows may overlap, count may be 0).  For every series b,
+ * window w = (first, count) and draw n, all in float64, with
+ *   v[n, t] = trajectory[b, n, t] * scale[b] + shift[b]        (two roundings, no fused multiply-add)
+ * the two paths over t = first .. first + count - 1 are
+ *   path 0 (prediction)         x0[n, t] = v[n, t];                        target_0[t] = observed[b, t]
+ *   path 1 (cumulative effect)  x1[n, t] = the running sum over s = first .. t, ascending, of
+ *                               point = -(v[n, s] - observed[b, s]), NaN points skipped;   target_1[t] = 0.0
+ * (the expressions of ci_session_summarize_windows: x1 at the window's last step is its point_sum,
+ * bit for bit), and for k = 0, 1
+ *   center_k[t] = (sum over n of x_k[n, t]) / N
+ *   spread_k[t] = sqrt((sum over n of (x_k[n, t] - center_k[t])^2) / (N - 1))
+ *   counted steps of path k: the window's steps with an observation and spread_k[t] > 0
+ *   z_k[n, t]      = |x_k[n, t] - center_k[t]| / spread_k[t]   (subtract, abs, divide: one rounding each)
+ *   excursion_k[n] = max over the counted t of z_k[n, t];  0.0 when no step is counted
+ *   observed_excursion_k = max over the counted t of |target_k[t] - center_k[t]| / spread_k[t];  NaN
+ *                          when no step is counted;  at_k = the first t that attains it, else -1
+ *   exceed_k       = #{n : excursion_k[n] >= observed_excursion_k}
+ *   excursion_order_k[r] = the ranks[r]-th smallest of excursion_k[:]
+ * ORDER OF THE ADDITIONS OVER n (both sums; a function of N alone): 256 partial sums, the i-th over
+ * n = i, i + 256, i + 512, ... ascending from 0.0; each run of 64 consecutive partial sums is added
+ * pairwise at distances 32, 16, 8, 4, 2, 1 (element l takes l + l', the element above); the four
+ * results are added in ascending order.  A host loop in another order agrees with center to N * 2^-53
+ * of the largest |x| and with spread to N * 2^-53 relative; GIVEN the returned center and spread, a
+ * plain loop on the host reproduces excursion, excursion_order, observed_excursion, at and exceed bit
+ * for bit.  count = 0: excursions and order statistics 0.0, observed_excursion NaN, at -1, exceed 0.
+ * scale, shift [B] and observed [B, T] as handed to ci_session_summarize; first, count
+ * [B, num_windows]; ranks: num_ranks 0-based order statistics over the N draws.  Outputs (host,
+ * caller-allocated; each may be NULL):
+ *   center, spread [B, num_windows, 2, T] float64: NaN outside the window and, for path 1, at the
+ *     steps without an observation (as ci_session_summarize reports `cum`)
+ *   excursion [B, num_windows, 2, N]      excursion_order [B, num_windows, 2, num_ranks]   float64
+ *   observed_excursion [B, num_windows, 2] float64     at, exceed [B, num_windows, 2] int32
+ * Ordinary and both kinds of ragged sessions are taken, on every kernel route; in a ragged session
+ * every series passes windows of its own.  DEVICE MEMORY: the scratch of ci_session_summarize is
+ * neither built nor touched.  A call takes at most CI_PATHS_MAX_BYTES (1 GiB) of its own, given back
+ * when it returns: the tables (observed, scale, shift, first, count, ranks and one int64 per window)
+ * and, per (series, window) of `count` steps, count * (2 N + 4) + 2 N + 20 doubles -- both paths of
+ * the window's own steps, their moments and the results.  Every (series, window) is computed alone,
+ * so the windows are taken in as many chunks as the limit asks for and no result depends on the
+ * chunking; a window that does not fit the limit beside the tables is refused by name, a failed
+ * allocation is an error.  No load touches memory outside the trajectories, observed and the tables.
+ * Checked before any device call, the error text naming the offending window: a finished run, no
+ * NULL argument but the outputs, num_windows in [1, 64], first >= 0, count >= 0, first + count <= T,
+ * num_ranks in [1, 8], ranks in [0, N). */
+#define CI_PATHS_MAX_BYTES (1ll << 30)
+int ci_session_summarize_paths(ci_session* session, const double* scale, const double* shift,
+                               const double* observed, int32_t num_windows,
+                               const int32_t* first, const int32_t* count,
+                               int32_t num_ranks, const int32_t* ranks,
+                               double* center, double* spread, double* excursion,
+                               double* excursion_order, double* observed_excursion,
+                               int32_t* at, int32_t* exceed);
 /* Weighted sums over GROUPS of series of the predictive trajectories of a finished run, draw by
  * draw: the draws of a pooled effect (all units, a region), whose quantiles are not sums of the
  * per-series quantiles.  Additive: CI_ABI_VERSION stays 5; look the symbol up (dlsym) where an older
@@ -627,6 +689,16 @@ int ci_ll_session_summarize_windows(ci_ll_session* session, const double* scale,
                                     const int32_t* first, const int32_t* count,
                                     int32_t num_ranks, const int32_t* ranks,
                                     double* per_draw, double* per_draw_order);
+/* ci_session_summarize_paths for the trajectories of the last ci_ll_session_hmc_run (any session,
+ * B series, N = num_chains x num_results): same arguments, same checks, same arithmetic, same
+ * kernels; T is the session's T. */
+int ci_ll_session_summarize_paths(ci_ll_session* session, const double* scale, const double* shift,
+                                  const double* observed, int32_t num_windows,
+                                  const int32_t* first, const int32_t* count,
+                                  int32_t num_ranks, const int32_t* ranks,
+                                  double* center, double* spread, double* excursion,
+                                  double* excursion_order, double* observed_excursion,
+                                  int32_t* at, int32_t* exceed);
 int ci_ll_session_kernel_name(const ci_ll_session* session, char* buf, int32_t buflen);
 /* Algorithmic bytes of the last configured HMC fit (DESIGN.md "Roofline", cfg3). */
 int ci_ll_session_algorithmic_bytes(const ci_ll_session* session, double* bytes);
@@ -692,6 +764,17 @@ int ci_test_dk_draw(const ci_problem* problem, const ci_series_params* params,
                     const float* resid, const uint8_t* mask, const uint8_t* season_change,
                     double obs_scale, double level_scale, double slope_scale,
                     const double* drift_scales, uint32_t iter, float* out_latents);
+/* ci_session_summarize_paths with the limit of its device memory handed in (max_bytes in place of
+ * CI_PATHS_MAX_BYTES) and the number of chunks it took written to num_chunks (may be NULL): a test
+ * can force several chunks and compare them with one. */
+int ci_test_session_summarize_paths(ci_session* session, const double* scale, const double* shift,
+                                    const double* observed, int32_t num_windows,
+                                    const int32_t* first, const int32_t* count,
+                                    int32_t num_ranks, const int32_t* ranks,
+                                    double* center, double* spread, double* excursion,
+                                    double* excursion_order, double* observed_excursion,
+                                    int32_t* at, int32_t* exceed, int64_t max_bytes,
+                                    int32_t* num_chunks);
 
 #ifdef __cplusplus
 }

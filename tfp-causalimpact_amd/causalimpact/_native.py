@@ -128,6 +128,12 @@ def load():
       getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                    C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p]
+  for name in ("ci_session_summarize_paths", "ci_ll_session_summarize_paths",
+               "ci_test_session_summarize_paths"):
+    if hasattr(L, name):                               # (additive, likewise)
+      getattr(L, name).argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p] + [C.c_void_p] * 7 +
+                                   ([C.c_int64, C.c_void_p] if name.startswith("ci_test_") else []))
   for pool_fn in (L.ci_session_pool_trajectories, L.ci_ll_session_pool_trajectories):
     pool_fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p, C.c_void_p]
@@ -192,6 +198,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_summarize", "ci_session_summarize_components",
           "ci_session_summarize_predictions", "ci_session_summarize_placebo", "ci_summarize_draws", "ci_summarize_draws_f64",
           "ci_session_summarize_windows", "ci_ll_session_summarize_windows",
+          "ci_session_summarize_paths", "ci_ll_session_summarize_paths",
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
           "ci_session_pool_event_trajectories",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
@@ -201,7 +208,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_comm_unique_id", "ci_comm_create", "ci_comm_info", "ci_comm_set_timeout", "ci_comm_barrier",
           "ci_comm_all_reduce", "ci_comm_all_gather", "ci_comm_session_all_gather",
           "ci_comm_ll_session_all_gather", "ci_comm_destroy", "ci_test_rng",
-          "ci_test_dk_draw")
+          "ci_test_dk_draw", "ci_test_session_summarize_paths")
 
 
 def _check(rc: int):
@@ -495,6 +502,113 @@ def _windows_call(fn, handle, B: int, N: int, T: int, scale, shift, observed, fi
   return out
 
 
+PATH_OUTPUTS = ("center", "spread", "excursion", "excursion_order", "observed_excursion", "at", "exceed")
+
+
+def path_excursions_host(trajectories, scale, shift, observed, first, count, ranks=None, center=None,
+                         spread=None) -> Dict[str, np.ndarray]:
+  """What `summarize_paths` computes, as a plain loop (the definitions of ci_session_summarize_paths,
+  include/causalimpact_amd.h): trajectories [B, N, T] (float32 or float64), scale, shift scalars or
+  [B], observed [T] or [B, T] (NaN = no observation), first, count [W] or [B, W] in steps.  For every
+  series, window and path k (0: the prediction against the observations; 1: the running sum of the
+  point effects against 0.0) the moments over the draws center, spread [B, W, 2, T] (NaN outside the
+  window and, for path 1, at the steps without an observation), every draw's largest standardised
+  excursion over the counted steps -- those with an observation and spread > 0 -- excursion
+  [B, W, 2, N], observed_excursion [B, W, 2] (NaN: no counted step), at [B, W, 2] (its first step, -1:
+  none), exceed [B, W, 2] = #{n: excursion >= observed_excursion}, excursion_order [B, W, 2, R] with
+  `ranks`, and x [B, W, 2, N, T], the paths themselves (NaN outside the window).  center=, spread=
+  [B, W, 2, T]: the second stage from these moments instead of its own -- given the device's, every
+  other array is the device's bit for bit; its own moments add the draws in numpy's order.  It is the
+  definition the device is compared with, and the route of the fits whose draws are pooled on the
+  host."""
+  tr = np.asarray(trajectories)
+  if tr.ndim != 3:
+    raise ValueError(f"`trajectories` must be [B, N, T], got shape {tr.shape}")
+  B, N, T = tr.shape
+  sc = np.broadcast_to(np.asarray(scale, np.float64), (B,))
+  sh = np.broadcast_to(np.asarray(shift, np.float64), (B,))
+  obs = np.broadcast_to(np.asarray(observed, np.float64), (B, T))
+  fi = np.asarray(first, np.int64)
+  fi = np.broadcast_to(fi, (B,) + fi.shape[-1:])
+  co = np.broadcast_to(np.asarray(count, np.int64), fi.shape)
+  W = fi.shape[1]
+  given = center is not None
+  if given != (spread is not None):
+    raise ValueError("`center` and `spread` go together")
+  out = dict(center=np.full((B, W, 2, T), np.nan), spread=np.full((B, W, 2, T), np.nan),
+             excursion=np.zeros((B, W, 2, N)), observed_excursion=np.full((B, W, 2), np.nan),
+             at=np.full((B, W, 2), -1, np.int32), exceed=np.zeros((B, W, 2), np.int32),
+             x=np.full((B, W, 2, N, T), np.nan))
+  with np.errstate(invalid="ignore", divide="ignore"):
+    for b in range(B):
+      for w in range(W):
+        f, c = int(fi[b, w]), int(co[b, w])
+        if f < 0 or c < 0 or f + c > T:
+          raise ValueError(f"window {w} of series {b}: steps {f} .. {f + c - 1} leave [0, {T})")
+        point_sum = np.zeros(N, np.float64)
+        for t in range(f, f + c):
+          v = tr[b, :, t].astype(np.float64) * sc[b] + sh[b]
+          point = -(v - obs[b, t])
+          point_sum = np.where(point == point, point_sum + point, point_sum)
+          out["x"][b, w, 0, :, t], out["x"][b, w, 1, :, t] = v, point_sum
+        for k in range(2):
+          x, best, seen, where = out["x"][b, w, k], np.zeros(N, np.float64), np.nan, -1
+          for t in range(f, f + c):
+            has_obs = obs[b, t] == obs[b, t]
+            if given:
+              ce, sp = np.float64(center[b, w, k, t]), np.float64(spread[b, w, k, t])
+            else:
+              ce = x[:, t].sum() / N
+              dev = x[:, t] - ce
+              sp = np.sqrt((dev * dev).sum() / np.float64(N - 1)) if N > 1 else np.float64(np.nan)
+              if k == 0 or has_obs:
+                out["center"][b, w, k, t], out["spread"][b, w, k, t] = ce, sp
+            if not has_obs or not sp > 0.0:
+              continue
+            z = np.abs(x[:, t] - ce) / sp
+            best = np.where(z > best, z, best)
+            zo = np.abs((0.0 if k else obs[b, t]) - ce) / sp
+            if where < 0 or zo > seen:
+              seen, where = zo, t
+          if given:
+            out["center"][b, w, k], out["spread"][b, w, k] = center[b, w, k], spread[b, w, k]
+          out["excursion"][b, w, k], out["observed_excursion"][b, w, k] = best, seen
+          out["at"][b, w, k], out["exceed"][b, w, k] = where, np.count_nonzero(best >= seen)
+  if ranks is not None:
+    rk = np.asarray(ranks, np.int64).reshape(-1)
+    out["excursion_order"] = np.sort(out["excursion"], axis=-1)[..., rk]
+  return out
+
+
+def _paths_call(fn, handle, B: int, N: int, T: int, scale, shift, observed, first, count, ranks,
+                want, extra=()) -> Dict[str, np.ndarray]:
+  """The call every session's `summarize_paths` makes; want: the `PATH_OUTPUTS` to return."""
+  sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (B,)))
+  sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.float64), (B,)))
+  obs = np.ascontiguousarray(np.broadcast_to(np.asarray(observed, np.float64), (B, T)))
+  fi = np.asarray(first, np.int32)
+  if fi.ndim not in (1, 2) or (fi.ndim == 2 and fi.shape[0] != B):
+    raise ValueError(f"`first` must be [W] or [{B}, W], got shape {fi.shape}")
+  fi = np.ascontiguousarray(np.broadcast_to(fi, (B, fi.shape[-1])))
+  co = np.asarray(count, np.int32)
+  if co.shape not in (fi.shape, fi.shape[1:]):
+    raise ValueError(f"`count` must have the shape of `first`, got {co.shape}")
+  co = np.ascontiguousarray(np.broadcast_to(co, fi.shape))
+  rk = np.ascontiguousarray(ranks, dtype=np.int32).reshape(-1)
+  W = fi.shape[1]
+  unknown = set(want) - set(PATH_OUTPUTS)
+  if unknown:
+    raise ValueError(f"unknown path outputs {sorted(unknown)}")
+  shapes = dict(center=(B, W, 2, T), spread=(B, W, 2, T), excursion=(B, W, 2, N),
+                excursion_order=(B, W, 2, rk.size), observed_excursion=(B, W, 2), at=(B, W, 2),
+                exceed=(B, W, 2))
+  arrs = {k: np.empty(shapes[k], np.int32 if k in ("at", "exceed") else np.float64)
+          for k in PATH_OUTPUTS if k in want}
+  _check(fn(handle, sc.ctypes.data, sh.ctypes.data, obs.ctypes.data, W, fi.ctypes.data, co.ctypes.data,
+            int(rk.size), rk.ctypes.data, *[_ptr(arrs.get(k)) for k in PATH_OUTPUTS], *extra))
+  return arrs
+
+
 class _PinnedBlock:
   """Owner of one ci_host_alloc buffer: returned to the library's pool when the last numpy view
   of it is collected."""
@@ -603,7 +717,7 @@ class Session:
   """Device-resident fit (inputs and outputs live in HBM between run() calls)."""
 
   # the kinds of `causalimpact_lib.SummaryRecord` this session takes on the device
-  summaries = ("effect", "components", "predictions", "windows", "placebo")
+  summaries = ("effect", "components", "predictions", "windows", "placebo", "paths")
 
   def __init__(self, pb: Problem, y, mask, X, season_change, params):
     self._lib = load()
@@ -836,6 +950,28 @@ class Session:
     return _windows_call(fn, self._h, pb.num_series, pb.num_chains * pb.num_results, pb.T, scale, shift,
                          observed, first, count, ranks, want_draws)
 
+  def summarize_paths(self, scale, shift, observed, first, count, ranks, want=PATH_OUTPUTS,
+                      max_bytes=None) -> Dict[str, np.ndarray]:
+    """On-device moments of the prediction's and the cumulative effect's paths over sub-windows of
+    the steps, and every draw's largest standardised excursion from them (ci_session_summarize_paths;
+    kernels: csrc/ci_paths.h): what a simultaneous band and a whole-path test are made of.  Arguments
+    as for `summarize_windows`; want: the `PATH_OUTPUTS` to return -- center, spread [B, W, 2, T],
+    excursion [B, W, 2, N], excursion_order [B, W, 2, R], observed_excursion [B, W, 2], at, exceed
+    [B, W, 2] int32; the series axis is kept.  `path_excursions_host` is the same in numpy.
+    max_bytes (tests): the limit of the call's device memory in place of the library's
+    (ci_test_session_summarize_paths); the result then has "num_chunks" too."""
+    name = "ci_session_summarize_paths" if max_bytes is None else "ci_test_session_summarize_paths"
+    fn = getattr(self._lib, name, None)
+    if fn is None:
+      raise NativeError(f"the loaded library has no {name}: rebuild it")
+    pb, chunks = self.pb, C.c_int32(0)
+    out = _paths_call(fn, self._h, pb.num_series, pb.num_chains * pb.num_results, pb.T, scale, shift,
+                      observed, first, count, ranks, want,
+                      () if max_bytes is None else (int(max_bytes), C.addressof(chunks)))
+    if max_bytes is not None:
+      out["num_chunks"] = chunks.value
+    return out
+
   def pool_trajectories(self, scale, shift, groups, init=None) -> np.ndarray:
     """Weighted sums over groups of series of the resident predictive trajectories, draw by draw
     (ci_session_pool_trajectories): out[g] = init[g] + sum over the members b of group g, ascending,
@@ -1036,7 +1172,7 @@ class BatchLogLikSession(LogLikSession):
   batched = True
   # the kinds of `causalimpact_lib.SummaryRecord` this session takes on the device (it keeps no
   # latent draws and has no filter entries)
-  summaries = ("effect", "windows")
+  summaries = ("effect", "windows", "paths")
 
   def __init__(self, pb: Problem, params, y, mask, X, max_evals: int = 1):   # pylint: disable=super-init-not-called
     self._lib = load()
@@ -1104,6 +1240,17 @@ class BatchLogLikSession(LogLikSession):
     Cn, S = self._hmc_shape
     return _windows_call(fn, self._h, self.B, Cn * S, self.T, scale, shift, observed, first, count,
                          ranks, want_draws)
+
+  def summarize_paths(self, scale, shift, observed, first, count, ranks,
+                      want=PATH_OUTPUTS) -> Dict[str, np.ndarray]:
+    """`Session.summarize_paths` of the fit's resident predictive trajectories
+    (ci_ll_session_summarize_paths), N = C x S."""
+    fn = getattr(self._lib, "ci_ll_session_summarize_paths", None)
+    if fn is None:
+      raise NativeError("the loaded library has no ci_ll_session_summarize_paths: rebuild it")
+    Cn, S = getattr(self, "_hmc_shape", (0, 0))           # (before a run: the entry refuses the call)
+    return _paths_call(fn, self._h, self.B, Cn * S, self.T, scale, shift, observed, first, count, ranks,
+                       want)
 
 
 def test_rng(seed, chain, it, site, sub, n, alpha, device=0):

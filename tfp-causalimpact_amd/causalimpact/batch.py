@@ -385,6 +385,50 @@ class CausalImpactBatchAnalysis:
     # and, with aggregates, the same for every pooled group (aggregate, window, average|cumulative)
     self.window_summary: Optional[pd.DataFrame] = None
     self.aggregate_window_summary: Optional[pd.DataFrame] = None
+    # `joint_bands=True` (`set_joint`): `joint_summary`, the `lib.JOINT_SUMMARY_COLUMNS` indexed by
+    # (series, pointwise|cumulative), and with `effect_windows` `window_joint_summary`, indexed by
+    # (series, window, pointwise|cumulative), NaN where a series does not cover a window;
+    # `analysis[b]` carries its own slices and its `joint_bands` frame
+    self._joint: Optional[Dict[str, Any]] = None
+    self.joint_summary: Optional[pd.DataFrame] = None
+    self.window_joint_summary: Optional[pd.DataFrame] = None
+
+  def _model_labels(self, b: int) -> pd.Index:
+    """The labels of the model steps of series b."""
+    return self._prep.index[self._prep.model_rows]
+
+  def set_joint(self, wsum: Dict[str, np.ndarray], path_ranks, window_names=None):
+    """Takes the path arrays of the record's `windows` kind ({path_*: [B, 1 + W, 2, ...]}, window 0
+    every series' post-period) and builds `joint_summary` and `window_joint_summary`."""
+    self._joint = dict(psum={k: v for k, v in wsum.items() if k.startswith("path_")},
+                       ranks=list(path_ranks), names=list(window_names) if window_names else None)
+    num_draws = self._dsum["per_draw"].shape[-1]
+    critical = lib._joint_critical(self._joint["psum"], path_ranks, num_draws, self.alpha)   # pylint: disable=protected-access
+    rows = []                                                   # [series][window]: the two rows
+    for b in range(len(self)):
+      Tb, labels = self._series_view(b)[3], self._model_labels(b)
+      psum = _cut({k: v[b] for k, v in self._joint["psum"].items()}, Tb, "windows")
+      rows.append([lib._joint_rows(psum, w, critical[b], num_draws, self._prep.observed[b, :Tb],   # pylint: disable=protected-access
+                                   lambda step, labels=labels: labels[step])
+                   for w in range(critical.shape[1])])
+    paths = list(lib.JOINT_PATHS)
+    self.joint_summary = lib.joint_table_frame(
+        [r for per in rows for r in per[0]],
+        pd.MultiIndex.from_product([self._names, paths], names=["series", None]))
+    if window_names:
+      self.window_joint_summary = lib.joint_table_frame(
+          [r for per in rows for two in per[1:] for r in two],
+          pd.MultiIndex.from_product([self._names, list(window_names), paths], names=["series", "window", None]))
+
+  def _joint_frames(self, b: int, ci_data, num_steps: int):
+    """(joint_bands, joint_summary, window_joint_summary) of series b, or Nones."""
+    if self._joint is None:
+      return None, None, None
+    psum = _cut({k: v[b] for k, v in self._joint["psum"].items()}, num_steps, "windows")
+    rq = lib._device_summary_request(ci_data, self.alpha)       # pylint: disable=protected-access
+    return lib._joint_frames(                                   # pylint: disable=protected-access
+        psum, self._joint["ranks"], self._dsum["per_draw"].shape[-1], self.alpha, rq["observed"],
+        lib.posterior_processing.model_index(ci_data), ci_data.data.index, self._joint["names"])
 
   def _window_slice(self, b: int) -> Optional[pd.DataFrame]:
     """The rows of series b of `window_summary`, indexed by (window, average|cumulative)."""
@@ -453,7 +497,8 @@ class CausalImpactBatchAnalysis:
                                                 *self._component_frames(b, ci_data, Tb),
                                                 *self._prediction_frames(b, ci_data, Tb),
                                                 self._window_slice(b),
-                                                *self._placebo_frames(b, ci_data, Tb, summary))
+                                                *self._placebo_frames(b, ci_data, Tb, summary),
+                                                *self._joint_frames(b, ci_data, Tb))
     return self._cache[b]
 
   def _placebo_frames(self, b: int, ci_data, num_steps: int, summary: pd.DataFrame):
@@ -544,6 +589,12 @@ class PerSeriesBatchAnalysis(CausalImpactBatchAnalysis):
     self.aggregate_summary = None
     self.window_summary = None
     self.aggregate_window_summary = None
+    self._joint = None
+    self.joint_summary = None
+    self.window_joint_summary = None
+    if all(a.joint_summary is not None for a in analyses):
+      self.joint_summary = pd.concat([a.joint_summary for a in analyses], keys=self._names,
+                                     names=["series", None])
 
   @property
   def fit_quality(self) -> Optional[pd.DataFrame]:
@@ -865,6 +916,9 @@ class CausalImpactPanelAnalysis(CausalImpactBatchAnalysis):
     p = self._prep
     return (pd.DataFrame(p.raw[b], index=p.indices[b], columns=self._columns), *p.periods[b],
             int(p.lengths[b]))
+
+  def _model_labels(self, b: int) -> pd.Index:
+    return self._prep.indices[b][self._prep.model_rows[b]]
 
 
 # ------------------------------------------------------------------------------------------
@@ -1318,7 +1372,8 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
                     inference_options, shared_streams, aggregates=None,
                     event_aggregates: Optional[EventPlan] = None,
                     windows: Optional[WindowPlan] = None, series_windows=None,
-                    placebo=None, placebo_lenient: bool = False) -> PerSeriesBatchAnalysis:
+                    placebo=None, placebo_lenient: bool = False,
+                    joint_bands: bool = False) -> PerSeriesBatchAnalysis:
   """`fit_causalimpact` on every series in turn: the routes the one-launch path does not have.
   float64 compute (csrc/ci_gibbs64.h) and raw-scale outcomes (their per-series internal
   conditioning, causalimpact_lib._internal_conditioning) exist on the single-series path, and so do
@@ -1359,6 +1414,8 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
       extra = dict(_trajectory_sink=lambda *a, b=b: host_pool.add(b, *a))
     if placebo is not None:
       extra = dict(extra, placebo=placebo, _placebo_lenient=placebo_lenient)
+    if joint_bands:
+      extra = dict(extra, joint_bands=True)
     one = lib.fit_causalimpact(frame, periods[b][0], periods[b][1], alpha=alpha, seed=seed_b,
                                data_options=opts, model_options=model_options,
                                inference_options=inference_options,
@@ -1366,7 +1423,9 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
                                **extra)
     analyses.append(dataclasses.replace(one, posterior_samples=None,   # (draws are not kept)
                                         window_summary=one.window_summary, placebo=one.placebo,
-                                        placebo_quality=one.placebo_quality))
+                                        placebo_quality=one.placebo_quality, joint_bands=one.joint_bands,
+                                        joint_summary=one.joint_summary,
+                                        window_joint_summary=one.window_joint_summary))
   res = PerSeriesBatchAnalysis(names, alpha, analyses)
   if windows is not None:
     full = pd.MultiIndex.from_product([windows.names, ["average", "cumulative"]], names=["window", None])
@@ -1375,6 +1434,14 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
       a.window_summary = blank if a.window_summary is None else a.window_summary.reindex(full)
     res.window_summary = pd.concat([a.window_summary for a in analyses], keys=list(names),
                                    names=["series", "window", None])
+    if joint_bands:
+      full = pd.MultiIndex.from_product([windows.names, list(lib.JOINT_PATHS)], names=["window", None])
+      blank = lib.joint_table_frame([None] * len(full), full)
+      for a in analyses:
+        a.window_joint_summary = (blank if a.window_joint_summary is None
+                                  else a.window_joint_summary.reindex(full))
+      res.window_joint_summary = pd.concat([a.window_joint_summary for a in analyses], keys=list(names),
+                                           names=["series", "window", None])
   if host_pool is not None:
     ranks = lib._summary_ranks(host_pool.pooled.shape[1], (alpha / 2.0, 1.0 - alpha / 2.0))   # pylint: disable=protected-access
     devs = list(inference_options.devices) if inference_options.devices else [0]
@@ -1418,6 +1485,10 @@ class _Fit:
   # and horizon [B] (`placebo_plans`); the summary is put on the data scale with own_scale / own_shift
   placebo_origins: Optional[np.ndarray] = None
   placebo_horizon: Optional[np.ndarray] = None
+  # `joint_bands=True` only: every series' windows of `summarize_paths` [B, 1 + W] (`lib.joint_windows`:
+  # window 0 its post-period) and the order statistics of the excursions
+  paths: Optional[lib.Windows] = None
+  path_ranks: Sequence[int] = ()
 
 
 def _sampler_outcome(prep, data_options) -> np.ndarray:
@@ -1426,7 +1497,8 @@ def _sampler_outcome(prep, data_options) -> np.ndarray:
 
 
 def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_options,
-             shared_streams, windows: Optional[WindowPlan] = None, placebo=None) -> _Fit:
+             shared_streams, windows: Optional[WindowPlan] = None, placebo=None,
+             joint_bands: bool = False) -> _Fit:
   """The `_Fit` of a prepared batch or panel: y = `_sampler_outcome(prep)`, lengths [B], pre_sd [B]
   the sd of every series' own pre-period outcome; placebo: (origins [B, O], horizon [B]) or None."""
   own_shift = own_scale = None
@@ -1444,6 +1516,10 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
         has_slope=model_options.local_linear_trend, outcome_sd=float(pre_sd[b]))
               for b, Tb in enumerate(int(t) for t in lengths)]
   num_draws = inference_options.num_chains * inference_options.num_results
+  paths = None
+  if joint_bands:
+    flags = np.broadcast_to(prep.flags, prep.observed.shape)
+    paths = lib.joint_windows(flags, None if windows is None else lib.Windows(windows.first, windows.count))
   return _Fit(y=y, mask=prep.mask, design=prep.design, lengths=np.asarray(lengths),
               scale=prep.outcome_sd, shift=prep.outcome_mean, observed=prep.observed,
               flags=prep.flags, params=params,
@@ -1452,7 +1528,8 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
               model_options=model_options, inference_options=inference_options,
               own_scale=own_scale, own_shift=own_shift, windows=windows,
               placebo_origins=None if placebo is None else placebo[0],
-              placebo_horizon=None if placebo is None else placebo[1])
+              placebo_horizon=None if placebo is None else placebo[1], paths=paths,
+              path_ranks=lib._path_ranks(num_draws, alpha) if joint_bands else ())   # pylint: disable=protected-access
 
 
 def placebo_plans(placebo: lib.Placebo, num_pre, num_post, state_dim: int):
@@ -1538,7 +1615,9 @@ def _launch_request(fit: _Fit, ids, observed, flags) -> lib.SummaryRequest:
       components=io.components, predictions=own if io.prediction_errors else None,
       windows=None if fit.windows is None else lib.Windows(fit.windows.first[ids], fit.windows.count[ids]),
       placebo=None if fit.placebo_origins is None else lib.PlaceboPart(
-          *own, fit.placebo_origins[ids], fit.placebo_horizon[ids]))
+          *own, fit.placebo_origins[ids], fit.placebo_horizon[ids]),
+      paths=None if fit.paths is None else lib.Windows(fit.paths.first[ids], fit.paths.count[ids]),
+      path_ranks=fit.path_ranks)
 
 
 def _series_inputs(fit: _Fit, ids, season_change, num_seasons) -> Optional[List[lib.SeriesInputs]]:
@@ -1634,7 +1713,7 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
                            names: Optional[Sequence[Any]] = None,
                            shared_streams: bool = False,
                            aggregates=None, effect_windows=None,
-                           placebo=None) -> CausalImpactBatchAnalysis:
+                           placebo=None, joint_bands: bool = False) -> CausalImpactBatchAnalysis:
   """`fit_causalimpact` for B series at once.
 
   data: a sequence of DataFrames with identical index and column layout (outcome first, or
@@ -1711,6 +1790,14 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   companion of `fit_quality` at the horizon of the post-period.  Forecast on the device that holds
   the draws (csrc/ci_placebo.h) inside every launch; in numpy on the routes `prediction_errors`
   takes in numpy.  ValueError before any fit when the pre-period has no room for an origin.
+
+  joint_bands: False (the default: nothing runs, no result differs) or True -- the simultaneous bands
+  and the whole-path test of `fit_causalimpact` for every series: `result[b].joint_bands`,
+  `result[b].joint_summary`, `result.joint_summary` as one table indexed by (series,
+  pointwise|cumulative) and, with `effect_windows`, `window_joint_summary` indexed by (series, window,
+  pointwise|cumulative).  Every draw's largest standardised excursion is taken where the trajectories
+  lie (csrc/ci_paths.h; no draws downloaded), in numpy on the routes fitted series by series.  The
+  pooled `aggregates` get no joint bands.
   """
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
@@ -1756,7 +1843,7 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
                            [(pre_period, post_period)] * B, names, columns[0], alpha, seed,
                            data_options, model_options, inference_options, shared_streams, agg,
                            windows=plan, series_windows=None if plan is None else [effect_windows] * B,
-                           placebo=placebo)
+                           placebo=placebo, joint_bands=joint_bands)
   plan = None if effect_windows is None else batch_windows(effect_windows, prep)
   pl_plan = pl_post = None
   if placebo is not None:
@@ -1769,7 +1856,7 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   with np.errstate(invalid="ignore"):
     pre_sd = np.nanstd(y[:, :prep.num_pre], axis=1, ddof=1)
   fit = _new_fit(prep, y, np.full(B, T), pre_sd, alpha, seed, model_options, inference_options,
-                 shared_streams, plan, pl_plan)
+                 shared_streams, plan, pl_plan, joint_bands)
   # a batch is the panel of one group of equal lengths: consecutive positions on every device
   launches = panel_launches(dict(route="equal_length", groups=[(T, list(range(B)))]),
                             inference_options.devices, shared_streams)
@@ -1792,6 +1879,8 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
       None if placebo is None else dict(origins=pl_plan[0], horizon=pl_plan[1], n_post=pl_post))
   if plan is not None:
     res.window_summary = _window_summary(res, plan, record.windows)
+  if joint_bands:
+    res.set_joint(record.windows, fit.path_ranks, None if plan is None else plan.names)
   if chain is not None:
     # the posterior means on the data scale with the statistics every series' own frame uses
     mu, sd = scaler_stats(prep.values[:, prep.model_rows[:prep.num_pre], 0])
@@ -1813,7 +1902,8 @@ def _window_summary(res: CausalImpactBatchAnalysis, plan: WindowPlan, wsum) -> p
     for b, Tb in enumerate(p.lengths):
       groups.setdefault((int(Tb), (p.flags[b, :Tb] & 2).tobytes()), []).append(b)
     classes = [(Tg, sel) for (Tg, _), sel in groups.items()]
-  return window_table(res._names, res.alpha, res._ranks, plan, wsum, p.observed, post_mean, classes)   # pylint: disable=protected-access
+  totals = {k: v for k, v in wsum.items() if not k.startswith("path_")}     # (`joint_bands` travels with them)
+  return window_table(res._names, res.alpha, res._ranks, plan, totals, p.observed, post_mean, classes)   # pylint: disable=protected-access
 
 
 def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float = 0.05, seed=None,
@@ -1823,7 +1913,7 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
                            names: Optional[Sequence[Any]] = None,
                            shared_streams: bool = False,
                            event_aggregates=None, effect_windows=None,
-                           placebo=None) -> CausalImpactBatchAnalysis:
+                           placebo=None, joint_bands: bool = False) -> CausalImpactBatchAnalysis:
   """`fit_causalimpact` for a PANEL: B series with the same columns (outcome first, or
   `DataOptions.outcome_column`; the same covariates), each with its own index, its own length and
   its own (pre_period, post_period) -- staggered roll-outs, units that enter the data on different
@@ -1892,7 +1982,11 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
 
   placebo: as in `fit_causalimpact_batch`, every series with the horizon and the origins of its OWN
   pre- and post-period.  A series whose pre-period has no room for an origin has an empty
-  `placebo` frame and a NaN row (n_origins 0) in `placebo_quality` -- no error."""
+  `placebo` frame and a NaN row (n_origins 0) in `placebo_quality` -- no error.
+
+  joint_bands: as in `fit_causalimpact_batch`, every series over its OWN post-period and the
+  `effect_windows` in event time; `window_joint_summary` has NaN rows where a series' post-period does
+  not reach a window.  The pooled `event_aggregates` get no joint bands."""
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
   placebo = lib.resolve_placebo(placebo)
@@ -1930,7 +2024,8 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
              for b in range(B)]
     return _fit_per_series(frames, periods, names, columns[0], alpha, seed, data_options,
                            model_options, inference_options, shared_streams, event_aggregates=plan,
-                           windows=wplan, series_windows=own, placebo=placebo, placebo_lenient=True)
+                           windows=wplan, series_windows=own, placebo=placebo, placebo_lenient=True,
+                           joint_bands=joint_bands)
   prep = prepare_panel([f[columns] for f in frames], periods, names=names)
   pl_plan = pl_post = None
   if placebo is not None:
@@ -1946,7 +2041,7 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   with np.errstate(invalid="ignore"):
     pre_sd = [np.nanstd(y[b, :nb], ddof=1) for b, nb in enumerate(prep.num_pre)]
   fit = _new_fit(prep, y, prep.lengths, pre_sd, alpha, seed, model_options, inference_options,
-                 shared_streams, wplan, pl_plan)
+                 shared_streams, wplan, pl_plan, joint_bands)
   kind = "ordinary" if route["route"] == "equal_length" else route["route"]
   launches = panel_launches(route, inference_options.devices, shared_streams)
   chain = None if plan is None else _PoolChain(launches, plan.csr, plan.axes)
@@ -1959,6 +2054,8 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
       None if placebo is None else dict(origins=pl_plan[0], horizon=pl_plan[1], n_post=pl_post))
   if wplan is not None:
     res.window_summary = _window_summary(res, wplan, record.windows)
+  if joint_bands:
+    res.set_joint(record.windows, fit.path_ranks, None if wplan is None else wplan.names)
   if chain is not None:
     # the posterior means on the data scale with the statistics every series' own frame uses
     data_means = []

@@ -137,12 +137,31 @@ class CausalImpactAnalysis:
   # origins are not independent trials.  (Init-only and kept as plain attributes, as those above.)
   placebo: dataclasses.InitVar[Optional[pd.DataFrame]] = None
   placebo_quality: dataclasses.InitVar[Optional[pd.Series]] = None
+  # `joint_bands=True` only.  `joint_bands`: indexed like `series`, NaN outside the post-period; the
+  # `JOINT_BAND_COLUMNS` -- SIMULTANEOUS bands: the counterfactual path lies inside posterior_lower ..
+  # posterior_upper at every step at once with probability 1 - alpha (center -+ c * spread of the
+  # draws, c the 1 - alpha quantile of every draw's largest standardised excursion), the same for the
+  # point effects (observed minus that band) and, with its own c, for the cumulative effect; `outside`:
+  # the observation lies outside the posterior band at that step.  `joint_summary`: one row for
+  # `pointwise` (the observed path against the predictive paths) and one for `cumulative` (the
+  # cumulative effect against 0) with the `JOINT_SUMMARY_COLUMNS`: critical_value (c), max_excursion
+  # (the observed path's largest standardised excursion), at (its label), n_outside, first_outside,
+  # p = (1 + #{draws whose excursion reaches it}) / (1 + draws) and significant = max_excursion >
+  # critical_value = some step is outside.  An effect that rises and reverses shows here and not in
+  # `summary`.  `window_joint_summary` (with `effect_windows=`): the same table per window, indexed by
+  # (window, pointwise|cumulative), critical value and test taken over the window's steps alone.
+  # (Init-only and kept as plain attributes, as those above.)
+  joint_bands: dataclasses.InitVar[Optional[pd.DataFrame]] = None
+  joint_summary: dataclasses.InitVar[Optional[pd.DataFrame]] = None
+  window_joint_summary: dataclasses.InitVar[Optional[pd.DataFrame]] = None
 
   def __post_init__(self, prediction_errors, fit_quality, window_summary=None, placebo=None,
-                    placebo_quality=None):
+                    placebo_quality=None, joint_bands=None, joint_summary=None, window_joint_summary=None):
     self.prediction_errors, self.fit_quality = prediction_errors, fit_quality
     self.window_summary = window_summary
     self.placebo, self.placebo_quality = placebo, placebo_quality
+    self.joint_bands, self.joint_summary = joint_bands, joint_summary
+    self.window_joint_summary = window_joint_summary
 
 
 @dataclasses.dataclass
@@ -221,6 +240,7 @@ def fit_causalimpact(data: pd.DataFrame,
                      inference_options: Optional[InferenceOptions] = None,
                      effect_windows=None,
                      placebo=None,
+                     joint_bands=False,
                      **kwargs) -> CausalImpactAnalysis:
   """Fits the CausalImpact model and summarises the effect (reference :223-339).
 
@@ -245,7 +265,18 @@ def fit_causalimpact(data: pd.DataFrame,
   the draws wherever the predictive summary runs there (csrc/ci_placebo.h), in numpy from the
   parameter draws on the other routes, exactly as `InferenceOptions.prediction_errors`.  ValueError
   before any fit when the pre-period has no room for one origin, or the state has more than
-  `PREDICTION_MAX_STATE` components."""
+  `PREDICTION_MAX_STATE` components.
+
+  joint_bands (extension): False (the default: nothing runs, no result differs) or True.  The bands
+  of `series` are pointwise: over a long post-period the observed series leaves them at several steps
+  by chance alone, and the total of `summary` misses an effect that rises and then reverses.  The
+  result then has `joint_bands` (simultaneous bands: the whole counterfactual path lies inside with
+  probability 1 - alpha), `joint_summary` (one p-value for "the observed path is unlike every
+  predictive path", for the prediction and for the cumulative effect) and, with `effect_windows`,
+  `window_joint_summary` -- see `CausalImpactAnalysis`.  They need every draw's largest standardised
+  excursion over its whole path: computed where the draws lie (csrc/ci_paths.h on the GPU that holds
+  them; `_native.path_excursions_host` on the routes that pool them on the host).  The bands are of
+  the posterior predictive; nothing is refitted."""
   data_options = data_options if data_options is not None else DataOptions()
   model_options = model_options if model_options is not None else ModelOptions()
   inference_options = inference_options if inference_options is not None else InferenceOptions()
@@ -289,14 +320,20 @@ def fit_causalimpact(data: pd.DataFrame,
                        f"horizon {horizon} and the history it needs")
     if origins.size:
       placebo_part = PlaceboPart(base["scale"], base["shift"], origins, horizon)
-  ranks = _summary_ranks(inference_options.num_chains * inference_options.num_results, base["quantiles"])
+  num_draws = inference_options.num_chains * inference_options.num_results
+  ranks = _summary_ranks(num_draws, base["quantiles"])
+  path_windows = None
+  if joint_bands:
+    path_windows = joint_windows(base["flags"], None if not windows else
+                                 Windows([w.first for w in windows], [w.count for w in windows]))
   request = SummaryRequest(
       scale=base["scale"], shift=base["shift"], observed=base["observed"], flags=base["flags"],
       ranks=ranks, components=inference_options.components,
       predictions=Affine(base["scale"], base["shift"]) if inference_options.prediction_errors else None,
       windows=Windows([w.first for w in windows], [w.count for w in windows]) if windows else None,
       placebo=placebo_part, on_device=inference_options.summarize_on_device,
-      keep_trajectories=trajectory_sink is not None)
+      keep_trajectories=trajectory_sink is not None,
+      paths=path_windows, path_ranks=_path_ranks(num_draws, alpha) if joint_bands else ())
   samples, posterior_means, posterior_trajectories, record = _run_sampler(
       ci_data=ci_data, prior_level_sd=model_options.prior_level_sd, seed=seed,
       num_results=inference_options.num_results,
@@ -314,7 +351,7 @@ def fit_causalimpact(data: pd.DataFrame,
     series, summary, window_summary = _compute_impact_device(
         posterior_means, record.effect, base["observed"], base["flags"], ranks, ci_data, alpha,
         windows=windows or (),
-        window_totals=None if record.windows is None else record.windows["per_draw"])
+        window_totals=None if record.windows is None else record.windows.get("per_draw"))
   else:
     series, summary, window_summary = _compute_impact(
         posterior_means=posterior_means, posterior_trajectories=posterior_trajectories,
@@ -359,9 +396,14 @@ def fit_causalimpact(data: pd.DataFrame,
     placebo_frame, placebo_quality = _placebo_frames(
         record.placebo, origins, horizon, alpha, base["observed"],
         posterior_processing.model_index(ci_data), n_post, summary.loc["cumulative", "rel_effect"])
+  joint = (None, None, None)
+  if joint_bands:
+    joint = _joint_frames(record.windows, request.path_ranks, num_draws, alpha, base["observed"],
+                          posterior_processing.model_index(ci_data), ci_data.data.index,
+                          [w.name for w in windows] if windows else None)
   return CausalImpactAnalysis(series, summary, posterior, samples.get("diagnostics"), components,
                               coefficients, prediction_errors, fit_quality, window_summary,
-                              placebo_frame, placebo_quality)
+                              placebo_frame, placebo_quality, *joint)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -965,6 +1007,122 @@ def _placebo_frames(psum: Optional[Dict], origins, horizon: int, alpha: float, o
   return frame[list(PLACEBO_COLUMNS)], _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
 
 
+# --------------------------------------------------------------------------------------
+# Simultaneous bands and the whole-path test (`joint_bands=True`)
+# --------------------------------------------------------------------------------------
+JOINT_BAND_COLUMNS = ("posterior_lower", "posterior_upper", "point_effects_lower", "point_effects_upper",
+                      "cumulative_effects_lower", "cumulative_effects_upper", "outside")
+JOINT_SUMMARY_COLUMNS = ("critical_value", "max_excursion", "at", "n_outside", "first_outside", "p",
+                         "significant")
+JOINT_PATHS = ("pointwise", "cumulative")
+# (nullable integer and boolean: a window a series does not cover has missing values in every column)
+_JOINT_DTYPES = dict(critical_value="float64", max_excursion="float64", at=object, n_outside="Int64",
+                     first_outside=object, p="float64", significant="boolean")
+
+
+def joint_table_frame(rows, index) -> pd.DataFrame:
+  """The `JOINT_SUMMARY_COLUMNS` frame of `rows` (dicts; None: a row of missing values) on `index`."""
+  blank = dict(critical_value=np.nan, max_excursion=np.nan, at=None, n_outside=pd.NA, first_outside=None,
+               p=np.nan, significant=pd.NA)
+  # (labels stay objects whatever they are: a column of dates alone would else become datetime64)
+  cols = {c: pd.Series([(blank if r is None else r)[c] for r in rows], index=index, dtype=_JOINT_DTYPES[c])
+          for c in JOINT_SUMMARY_COLUMNS}
+  return pd.DataFrame(cols, index=index, columns=list(JOINT_SUMMARY_COLUMNS))
+# what a `SummaryRecord` keeps of `summarize_paths` (inside its `windows` kind, `path_` in front)
+_PATH_RECORD = ("center", "spread", "excursion_order", "observed_excursion", "at", "exceed")
+
+
+def _path_ranks(num_draws: int, alpha: float) -> List[int]:
+  """The order statistics the 1 - alpha quantile of the excursions needs (`_quantile_ranks`)."""
+  (lo, hi, _), = _quantile_ranks(num_draws, (1.0 - alpha,))
+  return sorted({lo, hi})
+
+
+def joint_windows(flags, windows: Optional["Windows"] = None) -> "Windows":
+  """The windows `summarize_paths` takes for a fit: window 0 is the post-period (the steps whose flag
+  bit 1 is set: a contiguous run), followed by the effect windows if any.  flags [T] or [B, T];
+  windows: first, count [W] or [B, W]."""
+  win = (np.asarray(flags) & 2) != 0
+  count = win.sum(axis=-1)
+  first = np.where(count > 0, win.argmax(axis=-1), 0)
+  first, count = first[..., None], count[..., None]
+  if windows is not None:
+    more_first, more_count = (np.asarray(a) for a in windows)
+    lead = np.broadcast_shapes(first.shape[:-1], more_first.shape[:-1])
+    first = np.concatenate([np.broadcast_to(first, lead + (1,)), np.broadcast_to(more_first, lead + more_first.shape[-1:])], axis=-1)
+    count = np.concatenate([np.broadcast_to(count, lead + (1,)), np.broadcast_to(more_count, lead + more_count.shape[-1:])], axis=-1)
+  return Windows(first.astype(np.int32), count.astype(np.int32))
+
+
+def _joint_critical(psum: Dict, ranks, num_draws: int, alpha: float) -> np.ndarray:
+  """c [..., W, 2]: the 1 - alpha quantile of the excursions, interpolated from the two order
+  statistics of path_excursion_order [..., W, 2, R] as numpy's linear method does."""
+  order = {r: psum["path_excursion_order"][..., i] for i, r in enumerate(ranks)}
+  (lo, hi, gamma), = _quantile_ranks(num_draws, (1.0 - alpha,))
+  return _lerp_order_stats(order, lo, hi, gamma)
+
+
+def _joint_rows(psum: Dict, w: int, critical, num_draws: int, observed, label_of) -> List[Optional[Dict]]:
+  """The two rows (`JOINT_PATHS`) of window w of one series for `joint_table_frame`: psum {path_*:
+  [W, 2, ...]}, critical [W, 2], observed [T]; label_of(step) -> the label of a model step.  None
+  where the window counts no step."""
+  rows = []
+  for k in range(2):
+    center, spread = psum["path_center"][w, k], psum["path_spread"][w, k]
+    c, seen, at = critical[w, k], psum["path_observed_excursion"][w, k], int(psum["path_at"][w, k])
+    if at < 0:
+      rows.append(None)
+      continue
+    outside = _joint_outside(center, spread, observed if k == 0 else np.where(np.isnan(observed), np.nan, 0.0), c)
+    steps = np.flatnonzero(outside)
+    rows.append(dict(critical_value=c, max_excursion=seen, at=label_of(at), n_outside=int(steps.size),
+                     first_outside=label_of(int(steps[0])) if steps.size else None,
+                     p=(1.0 + int(psum["path_exceed"][w, k])) / (1.0 + num_draws),
+                     significant=bool(seen > c)))
+  return rows
+
+
+def _joint_outside(center, spread, target, critical) -> np.ndarray:
+  """[T] bool: the counted steps (a target, spread > 0) at which the target's standardised excursion
+  exceeds `critical` -- the expression of observed_excursion, so `significant` is `outside.any()`."""
+  with np.errstate(invalid="ignore", divide="ignore"):
+    z = np.abs(target - center) / spread
+    return ~np.isnan(target) & (spread > 0.0) & (z > critical)
+
+
+def _joint_frames(psum: Optional[Dict], ranks, num_draws: int, alpha: float, observed, model_idx: pd.Index,
+                  full_index: pd.Index, window_names=None):
+  """(joint_bands, joint_summary, window_joint_summary) of one series from the path arrays of its
+  record (`psum` {path_*: [W, 2, ...]}, window 0 the post-period, then the effect windows in the
+  order of `window_names`; a window the series does not cover has count 0, hence NaN rows).  observed
+  [T]: the outcome on the data scale over the model steps `model_idx`."""
+  critical = _joint_critical(psum, ranks, num_draws, alpha)
+  center, spread = psum["path_center"][0], psum["path_spread"][0]
+  with np.errstate(invalid="ignore"):
+    lower = [center[k] - critical[0, k] * spread[k] for k in range(2)]
+    upper = [center[k] + critical[0, k] * spread[k] for k in range(2)]
+    cols = {"posterior_lower": lower[0], "posterior_upper": upper[0],
+            "point_effects_lower": observed - upper[0], "point_effects_upper": observed - lower[0],
+            "cumulative_effects_lower": lower[1], "cumulative_effects_upper": upper[1],
+            "outside": _joint_outside(center[0], spread[0], observed, critical[0, 0])}
+  bands = pd.DataFrame(cols, index=model_idx, columns=list(JOINT_BAND_COLUMNS)).reindex(full_index)
+  bands["outside"] = bands["outside"].eq(True)                     # (the rows the model never sees: not outside)
+  label_of = lambda step: model_idx[step]   # pylint: disable=unnecessary-lambda-assignment
+  rows = [_joint_rows(psum, w, critical, num_draws, observed, label_of) for w in range(critical.shape[0])]
+  summary = joint_table_frame(rows[0], list(JOINT_PATHS))
+  by_window = None
+  if window_names:
+    by_window = joint_table_frame(
+        [r for two in rows[1:] for r in two],
+        pd.MultiIndex.from_product([list(window_names), list(JOINT_PATHS)], names=["window", None]))
+  return bands, summary, by_window
+
+
+def _paths_record(got: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+  """What `summarize_paths` / `path_excursions_host` returned as the record keeps it."""
+  return {"path_" + k: got[k] for k in _PATH_RECORD}
+
+
 def _sanitize_seed(seed: Optional[_SeedType]) -> Tuple[int, int]:
   """int s -> (0, s); pair -> pair; None -> fresh entropy (reference :535-543)."""
   if seed is None:
@@ -1117,6 +1275,11 @@ class SummaryRequest:
   predictions: Optional[Affine] = None
   windows: Optional[Windows] = None
   placebo: Optional[PlaceboPart] = None
+  # `joint_bands`: the windows `summarize_paths` takes (`joint_windows`: window 0 the post-period) and
+  # the order statistics of the excursions (`_path_ranks`).  The answers travel in the record's
+  # `windows` kind under `path_` names: they are per-window arrays.
+  paths: Optional[Windows] = None
+  path_ranks: Sequence[int] = ()
   # (single fits) False: the effect and its windows are left to the host arithmetic of
   # `_compute_impact`; keep_trajectories: the predictive draws are wanted on the host as well
   on_device: bool = True
@@ -1155,7 +1318,9 @@ SUMMARY_KINDS = {
     "effect": SummaryKind(("per_draw", "per_draw_order"), np.nan),            # [B, 2, draws | R]
     "components": SummaryKind(("inclusion_prob", "weight_mean", "weight_order"), np.nan),   # [B, ..., P]
     "predictions": SummaryKind(("loglik",), np.nan),                          # [B, draws]
-    "windows": SummaryKind(("per_draw", "per_draw_order"), np.nan),           # [B, W, 2, draws | R]
+    # [B, W, 2, draws | R]; `joint_bands`: path_center, path_spread [B, 1 + W, 2, T] over time, the rest whole
+    "windows": SummaryKind(("per_draw", "per_draw_order", "path_excursion_order", "path_observed_excursion",
+                            "path_at", "path_exceed"), np.nan),
     "placebo": SummaryKind(("predicted_mean", "spread_mean", "pit_mean", "n_counted", "seen_sum"),
                            np.nan)}                                           # [B, O]
 # the parameter draws the prediction errors and the placebo forecasts are filtered from on the host
@@ -1271,8 +1436,8 @@ def _with_placebo_seen(inputs: Sequence[SeriesInputs], part: PlaceboPart, plsum)
 def take_summaries(sess, request: SummaryRequest,
                    series_inputs: Optional[Sequence[SeriesInputs]] = None) -> SummaryRecord:
   """Fills the record of `request` from the finished, still open session `sess`: `summarize`,
-  `summarize_components`, `summarize_predictions`, `summarize_windows`, `summarize_placebo`, in this
-  order for every caller -- every entry uploads its own arguments and leaves nothing behind for the
+  `summarize_components`, `summarize_predictions`, `summarize_windows` (`summarize_paths` directly
+  after it), `summarize_placebo`, in this order for every caller -- every entry uploads its own arguments and leaves nothing behind for the
   next (tests/test_gpu_summaries_together.py).  `sess.summaries` names the kinds a session has.
   Prediction errors and placebo forecasts are filtered on the device where the session has the
   entries and `device_predictions_supported` takes the model; else in numpy from the parameter draws,
@@ -1296,6 +1461,9 @@ def take_summaries(sess, request: SummaryRequest,
   if request.windows is not None:
     windows = sess.summarize_windows(request.scale, request.shift, request.observed, *request.windows,
                                      request.ranks)
+  if request.paths is not None:
+    windows = dict(windows or {}, **_paths_record(sess.summarize_paths(
+        request.scale, request.shift, request.observed, *request.paths, request.path_ranks, want=_PATH_RECORD)))
   if request.placebo is not None:
     part = _per_series(request.placebo, len(series_inputs))
     placebo = _with_placebo_seen(series_inputs, part, _host_placebo_summaries(series_inputs, draws, part)
@@ -1425,6 +1593,12 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
         # ... and the window totals from exactly these trajectories and this (scale, shift)
         windows = dict(per_draw=_native.window_totals_host(
             tr, internal.scale, internal.shift, internal.observed, *internal.windows))
+    if internal.paths is not None:
+      # ... and the path excursions, also where the effect is left to `_compute_impact`
+      tr = out["posterior_trajectories"]
+      windows = dict(windows or {}, **_paths_record(_native.path_excursions_host(
+          tr.reshape((1, tr.shape[0] * tr.shape[1]) + tr.shape[2:]), internal.scale, internal.shift,
+          internal.observed, *internal.paths, ranks=internal.path_ranks)))
     # the same definitions in numpy, from the parameter draws in the sampler's units
     draws = {k: out[k][None] for k in _PARAMETER_DRAWS}
     if internal.predictions is not None:

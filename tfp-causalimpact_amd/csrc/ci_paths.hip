@@ -1,0 +1,35 @@
+// Instantiation unit of the path excursions (ci_paths.h) and their launch;
+// ci_session_summarize_paths and ci_ll_session_summarize_paths (ci_summary.hip) call it.
+#include "ci_paths.h"
+
+namespace ci {
+
+// One chunk: the `pairs` (series, window) pairs from p0 on (in the order [B, W]), the longest of
+// `max_count` steps: traj [B, N, T] float32, obs [B, T], scales, shifts [B], first, count [B, W],
+// steps_before [B * W + 1] (the running total of count); X [steps of the chunk, 2, N], mom [steps of the chunk, 4], observed_excursion, at, exceed
+// [pairs, 2], excursion [pairs, 2, N]; all device pointers.  The windows were checked by the caller
+// (0 <= first, 0 <= count, first + count <= T), and 1 <= pairs <= 65535.
+hipError_t paths_launch(hipStream_t stream, int N, int T, int W, int p0, int pairs, int max_count,
+                        const float* traj, const double* obs, const double* scales, const double* shifts,
+                        const int* first, const int* count, const long long* steps_before, double* X,
+                        double* mom, double* observed_excursion, int* at, double* excursion, int* exceed) {
+  const PathsChunk c{N, T, W, p0, first, count, steps_before, obs, scales, shifts};
+  const bool aligned = c.T % 4 == 0 && (reinterpret_cast<uintptr_t>(traj) & 15u) == 0u;
+  hipError_t e = hipMemsetAsync(exceed, 0, (size_t)2 * pairs * sizeof(int), stream);
+  if (e != hipSuccess) return e;
+  if (max_count > 0) {
+    const dim3 grid((c.N + PATHS_TILE - 1) / PATHS_TILE, pairs);
+    if (aligned)
+      hipLaunchKernelGGL(path_values_kernel<true>, grid, dim3(PATHS_TILE), 0, stream, c, traj, X);
+    else
+      hipLaunchKernelGGL(path_values_kernel<false>, grid, dim3(PATHS_TILE), 0, stream, c, traj, X);
+    hipLaunchKernelGGL(path_moments_kernel, dim3(2 * max_count, pairs), dim3(PATHS_NT), 0, stream, c, X, mom);
+  }
+  hipLaunchKernelGGL(path_observed_kernel, dim3((2 * pairs + 63) / 64), dim3(64), 0, stream, c, pairs, mom,
+                     observed_excursion, at);
+  hipLaunchKernelGGL(path_excursion_kernel, dim3(2 * ((c.N + PATHS_NT - 1) / PATHS_NT), pairs),
+                     dim3(PATHS_NT), 0, stream, c, X, mom, observed_excursion, excursion, exceed);
+  return hipGetLastError();
+}
+
+}  // namespace ci

@@ -2,7 +2,7 @@
 // ci_components.h, ci_predict.h): ci_session_summarize, ci_session_summarize_components,
 // ci_session_summarize_predictions, ci_session_summarize_placebo (kernels: ci_placebo.h),
 // ci_session_summarize_windows, ci_ll_session_summarize_windows
-// (kernel: ci_windows.h),
+// (kernel: ci_windows.h), ci_session_summarize_paths, ci_ll_session_summarize_paths (kernels: ci_paths.h),
 // ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] on
 // draws the caller hands in; ci_session_pool_trajectories, ci_ll_session_pool_trajectories and
 // ci_session_pool_event_trajectories (kernels: ci_pool.h) on the trajectories a session holds.
@@ -126,7 +126,30 @@ hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seas
 hipError_t windows_launch(hipStream_t stream, int B, int N, int T, int W, const float* traj,
                           const double* obs, const double* scales, const double* shifts,
                           const int* first, const int* count, double* out);
+// The launch of ci_paths.hip (kernels: ci_paths.h).
+hipError_t paths_launch(hipStream_t stream, int N, int T, int W, int p0, int pairs, int max_count,
+                        const float* traj, const double* obs, const double* scales, const double* shifts,
+                        const int* first, const int* count, const long long* steps_before, double* X,
+                        double* mom, double* observed_excursion, int* at, double* excursion, int* exceed);
 }  // namespace ci
+
+// The window tables of ci_session_summarize_windows and ci_session_summarize_paths: first, count
+// [B, W] inside the session's T steps, the error naming the offending window.
+static int check_window_table(const char* what, int B, int T, int32_t W, int max_windows,
+                              const int32_t* first, const int32_t* count) {
+  if (W < 1 || W > max_windows)
+    return fail("%s: num_windows must be in [1, %d], got %d", what, max_windows, W);
+  for (int b = 0; b < B; ++b)
+    for (int w = 0; w < W; ++w) {
+      const int f = first[(size_t)b * W + w], c = count[(size_t)b * W + w];
+      if (f < 0) return fail("%s: window %d of series %d: first step %d is negative", what, w, b, f);
+      if (c < 0) return fail("%s: window %d of series %d: count %d is negative", what, w, b, c);
+      if ((long long)f + c > T)
+        return fail("%s: window %d of series %d: steps %d .. %lld end beyond the session's %d steps",
+                    what, w, b, f, (long long)f + c - 1, T);
+    }
+  return 0;
+}
 
 // The window totals of B series' [B, N, T] float32 trajectories resident in HBM
 // (ci_session_summarize_windows, ci_ll_session_summarize_windows): everything is checked before the
@@ -139,16 +162,7 @@ static int windows_resident(const char* what, int device, hipStream_t stream, in
                             const double* observed, int32_t W, const int32_t* first,
                             const int32_t* count, int32_t num_ranks, const int32_t* ranks,
                             double* per_draw, double* per_draw_order) {
-  if (W < 1 || W > 1024) return fail("%s: num_windows must be in [1, 1024], got %d", what, W);
-  for (int b = 0; b < B; ++b)
-    for (int w = 0; w < W; ++w) {
-      const int f = first[(size_t)b * W + w], c = count[(size_t)b * W + w];
-      if (f < 0) return fail("%s: window %d of series %d: first step %d is negative", what, w, b, f);
-      if (c < 0) return fail("%s: window %d of series %d: count %d is negative", what, w, b, c);
-      if ((long long)f + c > T)
-        return fail("%s: window %d of series %d: steps %d .. %lld end beyond the session's %d steps",
-                    what, w, b, f, (long long)f + c - 1, T);
-    }
+  if (check_window_table(what, B, T, W, 1024, first, count)) return 1;
   if (check_ranks(num_ranks, ranks, N)) return 1;
   HIP_TRY(hipSetDevice(device));
   const int R = ci::SUMM_MAX_RANKS;
@@ -180,6 +194,128 @@ static int windows_resident(const char* what, int device, hipStream_t stream, in
     HIP_TRY(hipMemcpyAsync(per_draw_order, d_order, 2 * BW * num_ranks * sizeof(double),
                            hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
+
+// The path excursions of B series' [B, N, T] float32 trajectories resident in HBM
+// (ci_session_summarize_paths, ci_ll_session_summarize_paths; kernels: ci_paths.h): everything is
+// checked before the first device call.  The (series, window) pairs are computed alone, so they are
+// taken in chunks of consecutive pairs whose device memory -- the tables, and per pair of `count`
+// steps the doubles paths_pair_doubles counts -- stays within max_bytes; the results cannot depend on
+// the chunking.  All of it is the call's own and goes back on every return path; the summary's
+// scratch is neither built nor touched.  num_chunks (may be NULL): how many chunks it took.
+static size_t paths_pair_doubles(int N, int count) {
+  // X [count, 2, N], moments [count, 4], excursion [2, N], order [2, 8], observed_excursion [2],
+  // at and exceed [2] int32 each
+  return (size_t)count * (2 * (size_t)N + 4) + 2 * (size_t)N + 2 * ci::SUMM_MAX_RANKS + 2 + 2;
+}
+
+static int paths_resident(const char* what, int device, hipStream_t stream, int B, int T, int N,
+                          const float* traj, const double* scale, const double* shift,
+                          const double* observed, int32_t W, const int32_t* first, const int32_t* count,
+                          int32_t num_ranks, const int32_t* ranks, double* center, double* spread,
+                          double* excursion, double* excursion_order, double* observed_excursion,
+                          int32_t* at, int32_t* exceed, int64_t max_bytes, int32_t* num_chunks) {
+  if (check_window_table(what, B, T, W, 64, first, count)) return 1;
+  if (check_ranks(num_ranks, ranks, N)) return 1;
+  const int R = ci::SUMM_MAX_RANKS;
+  const size_t BW = (size_t)B * W, BT = (size_t)B * T;
+  const size_t table_bytes = (BT + 2 * (size_t)B) * sizeof(double) + 2 * BW * sizeof(int) +
+                             (BW + 1) * sizeof(long long) + R * sizeof(int);
+  if (max_bytes < 0 || (size_t)max_bytes < table_bytes)
+    return fail("%s: the tables alone take %zu bytes of device memory, the limit is %lld", what,
+                table_bytes, (long long)max_bytes);
+  const size_t budget = ((size_t)max_bytes - table_bytes) / sizeof(double);
+  // chunks of consecutive pairs: [starts[i], starts[i + 1])
+  std::vector<long long> steps_before(BW + 1, 0);
+  std::vector<size_t> starts(1, 0);
+  size_t used = 0, most_steps = 0, most_pairs = 0;
+  for (size_t p = 0; p < BW; ++p) {
+    steps_before[p + 1] = steps_before[p] + count[p];
+    const size_t need = paths_pair_doubles(N, count[p]);
+    if (need > budget)
+      return fail("%s: window %d of series %d: its %d steps of %d draws take %zu bytes of device memory "
+                  "beside %zu of tables, the limit is %lld", what, (int)(p % W), (int)(p / W), count[p], N,
+                  need * sizeof(double), table_bytes, (long long)max_bytes);
+    if (used + need > budget || p - starts.back() == 65535) {
+      starts.push_back(p);
+      used = 0;
+    }
+    used += need;
+    const size_t steps = (size_t)(steps_before[p + 1] - steps_before[starts.back()]);
+    most_steps = steps > most_steps ? steps : most_steps;
+    most_pairs = p + 1 - starts.back() > most_pairs ? p + 1 - starts.back() : most_pairs;
+  }
+  starts.push_back(BW);
+  if (num_chunks) *num_chunks = (int32_t)(starts.size() - 1);
+  HIP_TRY(hipSetDevice(device));
+  DevBuf<double> d_f64, d_X;  // observed [B, T], scale, shift [B]; per chunk: moments, excursion, order, observed_excursion
+  DevBuf<int> d_i32;          // first, count [B, W], ranks [8]; per chunk: at, exceed [pairs, 2]
+  DevBuf<long long> d_steps;
+  HIP_TRY(d_f64.alloc(BT + 2 * (size_t)B + most_steps * 4 + most_pairs * 2 * ((size_t)N + R + 1)));
+  HIP_TRY(d_X.alloc(most_steps * 2 * N + 1));
+  HIP_TRY(d_i32.alloc(2 * BW + R + 4 * most_pairs));
+  HIP_TRY(d_steps.alloc(BW + 1));
+  double* d_scale = d_f64.p + BT;
+  double* d_shift = d_scale + B;
+  double* d_mom = d_shift + B;
+  double* d_exc = d_mom + most_steps * 4;
+  double* d_order = d_exc + most_pairs * 2 * N;
+  double* d_obsexc = d_order + most_pairs * 2 * R;
+  int* d_count = d_i32.p + BW;
+  int* d_ranks = d_count + BW;
+  int* d_at = d_ranks + R;
+  int* d_exceed = d_at + 2 * most_pairs;
+  HIP_TRY(hipMemcpyAsync(d_f64.p, observed, BT * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_i32.p, first, BW * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_count, count, BW * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_ranks, ranks, num_ranks * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_steps.p, steps_before.data(), (BW + 1) * sizeof(long long), hipMemcpyHostToDevice,
+                         stream));
+  std::vector<double> mom;
+  const double nan = std::nan("");
+  for (size_t i = 0; i + 1 < starts.size(); ++i) {
+    const size_t p0 = starts[i], pairs = starts[i + 1] - p0;
+    if (pairs == 0) continue;
+    const size_t steps = (size_t)(steps_before[p0 + pairs] - steps_before[p0]);
+    int max_count = 0;
+    for (size_t p = p0; p < p0 + pairs; ++p) max_count = count[p] > max_count ? count[p] : max_count;
+    HIP_TRY(ci::paths_launch(stream, N, T, W, (int)p0, (int)pairs, max_count, traj, d_f64.p, d_scale, d_shift,
+                             d_i32.p, d_count, d_steps.p, d_X.p, d_mom, d_obsexc, d_at, d_exc, d_exceed));
+    if (excursion_order)
+      HIP_TRY(launch_select(stream, N, 1, (int)(2 * pairs), num_ranks, d_ranks, d_exc, nullptr, d_order,
+                            nullptr));
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+      return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+    };
+    mom.resize(steps * 4);
+    if (center || spread) HIP_TRY(fetch(mom.data(), d_mom, steps * 4 * sizeof(double)));
+    HIP_TRY(fetch(excursion ? excursion + p0 * 2 * N : nullptr, d_exc, pairs * 2 * N * sizeof(double)));
+    HIP_TRY(fetch(excursion_order ? excursion_order + p0 * 2 * num_ranks : nullptr, d_order,
+                  pairs * 2 * num_ranks * sizeof(double)));
+    HIP_TRY(fetch(observed_excursion ? observed_excursion + p0 * 2 : nullptr, d_obsexc, pairs * 2 * sizeof(double)));
+    HIP_TRY(fetch(at ? at + p0 * 2 : nullptr, d_at, pairs * 2 * sizeof(int)));
+    HIP_TRY(fetch(exceed ? exceed + p0 * 2 : nullptr, d_exceed, pairs * 2 * sizeof(int)));
+    HIP_TRY(hipStreamSynchronize(stream));
+    // center, spread [B, W, 2, T]: NaN outside the window and, for the cumulative path, at the steps
+    // without an observation
+    for (size_t p = p0; p < p0 + pairs && (center || spread); ++p) {
+      const int f = first[p], n = count[p];
+      const double* obs = observed + (p / W) * (size_t)T;
+      const double* m = mom.data() + (size_t)(steps_before[p] - steps_before[p0]) * 4;
+      for (int k = 0; k < 2; ++k) {
+        double* rows[2] = {center ? center + (p * 2 + k) * T : nullptr, spread ? spread + (p * 2 + k) * T : nullptr};
+        for (int j = 0; j < 2; ++j) {
+          if (!rows[j]) continue;
+          for (int t = 0; t < T; ++t) rows[j][t] = nan;
+          for (int s = 0; s < n; ++s)
+            if (k == 0 || obs[f + s] == obs[f + s]) rows[j][f + s] = m[((size_t)k * 2 + j) * n + s];
+        }
+      }
+    }
+  }
   return 0;
 }
 
@@ -391,6 +527,45 @@ int ci_ll_session_summarize_windows(ci_ll_session* s, const double* scale, const
   return windows_resident("ci_ll_session_summarize_windows", s->device, s->stream, s->B, s->T,
                           s->h_C * s->h_S, s->h_traj.p, scale, shift, observed, num_windows, first,
                           count, num_ranks, ranks, per_draw, per_draw_order);
+}
+
+int ci_session_summarize_paths(ci_session* s, const double* scale, const double* shift,
+                               const double* observed, int32_t num_windows, const int32_t* first,
+                               const int32_t* count, int32_t num_ranks, const int32_t* ranks,
+                               double* center, double* spread, double* excursion, double* excursion_order,
+                               double* observed_excursion, int32_t* at, int32_t* exceed) {
+  return ci_test_session_summarize_paths(s, scale, shift, observed, num_windows, first, count, num_ranks,
+                                         ranks, center, spread, excursion, excursion_order,
+                                         observed_excursion, at, exceed, CI_PATHS_MAX_BYTES, nullptr);
+}
+
+int ci_test_session_summarize_paths(ci_session* s, const double* scale, const double* shift,
+                                    const double* observed, int32_t num_windows, const int32_t* first,
+                                    const int32_t* count, int32_t num_ranks, const int32_t* ranks,
+                                    double* center, double* spread, double* excursion,
+                                    double* excursion_order, double* observed_excursion, int32_t* at,
+                                    int32_t* exceed, int64_t max_bytes, int32_t* num_chunks) {
+  if (!s || !scale || !shift || !observed || !first || !count || !ranks) return fail("NULL argument");
+  if (!s->ran) return fail("ci_session_summarize_paths needs a finished ci_session_run");
+  const ci_problem& pb = s->pb;
+  return paths_resident("ci_session_summarize_paths", pb.device, s->stream, pb.num_series, pb.T,
+                        pb.num_chains * pb.num_results, s->o_traj.p, scale, shift, observed, num_windows,
+                        first, count, num_ranks, ranks, center, spread, excursion, excursion_order,
+                        observed_excursion, at, exceed, max_bytes, num_chunks);
+}
+
+int ci_ll_session_summarize_paths(ci_ll_session* s, const double* scale, const double* shift,
+                                  const double* observed, int32_t num_windows, const int32_t* first,
+                                  const int32_t* count, int32_t num_ranks, const int32_t* ranks,
+                                  double* center, double* spread, double* excursion,
+                                  double* excursion_order, double* observed_excursion, int32_t* at,
+                                  int32_t* exceed) {
+  if (!s || !scale || !shift || !observed || !first || !count || !ranks) return fail("NULL argument");
+  if (!s->h_ran) return fail("ci_ll_session_summarize_paths needs a finished ci_ll_session_hmc_run");
+  return paths_resident("ci_ll_session_summarize_paths", s->device, s->stream, s->B, s->T, s->h_C * s->h_S,
+                        s->h_traj.p, scale, shift, observed, num_windows, first, count, num_ranks, ranks,
+                        center, spread, excursion, excursion_order, observed_excursion, at, exceed,
+                        CI_PATHS_MAX_BYTES, nullptr);
 }
 
 int ci_session_summarize_components(ci_session* s, const double* scale, const double* shift,
