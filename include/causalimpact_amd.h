@@ -577,6 +577,45 @@ int ci_summarize_draws_f64(int32_t device, int32_t num_draws, int32_t T, const d
                            double scale, double shift, const double* observed, const uint8_t* flags,
                            int32_t num_ranks, const int32_t* ranks, double* value_order,
                            double* cum_order, double* per_draw, double* per_draw_order);
+/* ci_session_summarize_paths for float64 draws that are on the host and belong to no session: the
+ * POOLED draws of groups of series (ci_session_pool_trajectories, ci_session_pool_event_trajectories),
+ * so that a pooled effect gets simultaneous bands and a whole-path test like every series.  Additive:
+ * CI_ABI_VERSION stays 5; look the symbol up (dlsym) where an older library may be met.
+ * draws [num_groups, N = num_draws, T] float64 are uploaded to `device`; group g has the num_windows
+ * windows first[g, w], count[g, w] (steps of its T; windows may overlap, count may be 0).  With
+ *   v[n, t] = draws[g, n, t] * scale[g] + shift[g]             (two roundings, no fused multiply-add)
+ * paths, targets, center, spread, counted steps, excursions, observed_excursion, at, exceed and
+ * excursion_order are those of ci_session_summarize_paths, with g in place of b: the same
+ * expressions in the first pass and the very same kernels after it, hence the same ORDER OF THE
+ * ADDITIONS OVER n and the same roundings.  On draws that are float32 values the results are those of
+ * ci_session_summarize_paths on the float32 trajectories bit for bit; given the returned center and
+ * spread a plain loop on the host reproduces the rest bit for bit.  count = 0: excursions and order
+ * statistics 0.0, observed_excursion NaN, at -1, exceed 0.  scale, shift [num_groups] (pooled draws are
+ * on the data scale already: 1.0 and 0.0); observed [num_groups, T], NaN: no observation; ranks:
+ * num_ranks 0-based order statistics over the N draws.  Outputs (host, caller-allocated; each may be
+ * NULL):
+ *   center, spread [num_groups, num_windows, 2, T] float64: NaN outside the window and, for path 1, at
+ *     the steps without an observation
+ *   excursion [num_groups, num_windows, 2, N]   excursion_order [num_groups, num_windows, 2, num_ranks]
+ *   observed_excursion [num_groups, num_windows, 2] float64   at, exceed [num_groups, num_windows, 2] int32
+ * DEVICE MEMORY: a call takes at most CI_PATHS_MAX_BYTES of its own, given back when it returns: the
+ * tables, N * T doubles per group whose draws are on the device, and per (group, window) the doubles
+ * ci_session_summarize_paths counts.  The (group, window) pairs are taken in order, in as many chunks
+ * as the limit asks for; a chunk holds the draws of the groups its pairs belong to and may end inside
+ * a group, whose draws then travel again.  Every pair is computed alone, so no result depends on the
+ * chunking; a group whose own draws and one of its windows do not fit beside the tables is refused,
+ * naming the group and the window.  No load touches memory outside draws, observed and the tables.
+ * Checked before any device call, the error text naming the offender: no NULL argument but the
+ * outputs, num_groups >= 1, num_draws >= 2, T >= 1, scale and shift finite, num_windows in [1, 64],
+ * first >= 0, count >= 0, first + count <= T, num_ranks in [1, 8], ranks in [0, N). */
+int ci_summarize_draw_paths_f64(int32_t device, int32_t num_groups, int32_t num_draws, int32_t T,
+                                const double* draws, const double* scale, const double* shift,
+                                const double* observed, int32_t num_windows,
+                                const int32_t* first, const int32_t* count,
+                                int32_t num_ranks, const int32_t* ranks,
+                                double* center, double* spread, double* excursion,
+                                double* excursion_order, double* observed_excursion,
+                                int32_t* at, int32_t* exceed);
 
 /* Kalman-filter log-likelihood of the trend + regression model for num_evals parameter sets
  * (the objective an HMC / VI fit would use; the reference never
@@ -775,6 +814,16 @@ int ci_test_session_summarize_paths(ci_session* session, const double* scale, co
                                     double* excursion_order, double* observed_excursion,
                                     int32_t* at, int32_t* exceed, int64_t max_bytes,
                                     int32_t* num_chunks);
+/* ci_summarize_draw_paths_f64 with max_bytes and num_chunks, likewise. */
+int ci_test_summarize_draw_paths_f64(int32_t device, int32_t num_groups, int32_t num_draws, int32_t T,
+                                     const double* draws, const double* scale, const double* shift,
+                                     const double* observed, int32_t num_windows,
+                                     const int32_t* first, const int32_t* count,
+                                     int32_t num_ranks, const int32_t* ranks,
+                                     double* center, double* spread, double* excursion,
+                                     double* excursion_order, double* observed_excursion,
+                                     int32_t* at, int32_t* exceed, int64_t max_bytes,
+                                     int32_t* num_chunks);
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,12 @@ def load():
       getattr(L, name).argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p] + [C.c_void_p] * 7 +
                                    ([C.c_int64, C.c_void_p] if name.startswith("ci_test_") else []))
+  for name in ("ci_summarize_draw_paths_f64", "ci_test_summarize_draw_paths_f64"):
+    if hasattr(L, name):                               # (additive, likewise)
+      getattr(L, name).argtypes = ([C.c_int32] * 4 + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p,
+                                                                         C.c_int32, C.c_void_p] +
+                                   [C.c_void_p] * 7 +
+                                   ([C.c_int64, C.c_void_p] if name.startswith("ci_test_") else []))
   for pool_fn in (L.ci_session_pool_trajectories, L.ci_ll_session_pool_trajectories):
     pool_fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p, C.c_void_p]
@@ -197,6 +203,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_profile", "ci_ll_session_kernel_name",
           "ci_session_summarize", "ci_session_summarize_components",
           "ci_session_summarize_predictions", "ci_session_summarize_placebo", "ci_summarize_draws", "ci_summarize_draws_f64",
+          "ci_summarize_draw_paths_f64",
           "ci_session_summarize_windows", "ci_ll_session_summarize_windows",
           "ci_session_summarize_paths", "ci_ll_session_summarize_paths",
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
@@ -208,7 +215,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_comm_unique_id", "ci_comm_create", "ci_comm_info", "ci_comm_set_timeout", "ci_comm_barrier",
           "ci_comm_all_reduce", "ci_comm_all_gather", "ci_comm_session_all_gather",
           "ci_comm_ll_session_all_gather", "ci_comm_destroy", "ci_test_rng",
-          "ci_test_dk_draw", "ci_test_session_summarize_paths")
+          "ci_test_dk_draw", "ci_test_session_summarize_paths", "ci_test_summarize_draw_paths_f64")
 
 
 def _check(rc: int):
@@ -580,6 +587,9 @@ def path_excursions_host(trajectories, scale, shift, observed, first, count, ran
   return out
 
 
+_NO_SESSION = object()          # `_paths_call`'s handle for an entry that has no session
+
+
 def _paths_call(fn, handle, B: int, N: int, T: int, scale, shift, observed, first, count, ranks,
                 want, extra=()) -> Dict[str, np.ndarray]:
   """The call every session's `summarize_paths` makes; want: the `PATH_OUTPUTS` to return."""
@@ -604,9 +614,37 @@ def _paths_call(fn, handle, B: int, N: int, T: int, scale, shift, observed, firs
                 exceed=(B, W, 2))
   arrs = {k: np.empty(shapes[k], np.int32 if k in ("at", "exceed") else np.float64)
           for k in PATH_OUTPUTS if k in want}
-  _check(fn(handle, sc.ctypes.data, sh.ctypes.data, obs.ctypes.data, W, fi.ctypes.data, co.ctypes.data,
-            int(rk.size), rk.ctypes.data, *[_ptr(arrs.get(k)) for k in PATH_OUTPUTS], *extra))
+  args = (sc.ctypes.data, sh.ctypes.data, obs.ctypes.data, W, fi.ctypes.data, co.ctypes.data,
+          int(rk.size), rk.ctypes.data, *[_ptr(arrs.get(k)) for k in PATH_OUTPUTS], *extra)
+  _check(fn(*args) if handle is _NO_SESSION else fn(handle, *args))
   return arrs
+
+
+def summarize_draw_paths(draws, scale, shift, observed, first, count, ranks, want=PATH_OUTPUTS, device=0,
+                         max_bytes=None) -> Dict[str, np.ndarray]:
+  """`Session.summarize_paths` for float64 draws [G, N, T] that are on the host and belong to no
+  session -- the pooled draws of groups of series -- on device `device`
+  (ci_summarize_draw_paths_f64; first pass: path_values_f64_kernel of csrc/ci_paths.h, the other passes
+  the session route's own).  scale, shift: scalars or [G] (pooled draws are on the data scale: 1.0,
+  0.0); observed [T] or [G, T]; first, count [W] or [G, W]; want: the `PATH_OUTPUTS` to return, the
+  group axis in front.  `path_excursions_host` is the same in numpy.  max_bytes (tests): the limit of
+  the call's device memory in place of the library's (ci_test_summarize_draw_paths_f64); the result
+  then has "num_chunks" too."""
+  name = "ci_summarize_draw_paths_f64" if max_bytes is None else "ci_test_summarize_draw_paths_f64"
+  fn = getattr(load(), name, None)
+  if fn is None:
+    raise NativeError(f"the loaded library has no {name}: rebuild it")
+  dr = np.ascontiguousarray(draws, dtype=np.float64)
+  if dr.ndim != 3:
+    raise ValueError(f"`draws` must be [G, N, T], got shape {dr.shape}")
+  G, N, T = dr.shape
+  chunks = C.c_int32(0)
+  head = lambda *rest: fn(int(device), G, N, T, dr.ctypes.data, *rest)   # pylint: disable=unnecessary-lambda-assignment
+  out = _paths_call(head, _NO_SESSION, G, N, T, scale, shift, observed, first, count, ranks, want,
+                    () if max_bytes is None else (int(max_bytes), C.addressof(chunks)))
+  if max_bytes is not None:
+    out["num_chunks"] = chunks.value
+  return out
 
 
 class _PinnedBlock:

@@ -392,6 +392,11 @@ class CausalImpactBatchAnalysis:
     self._joint: Optional[Dict[str, Any]] = None
     self.joint_summary: Optional[pd.DataFrame] = None
     self.window_joint_summary: Optional[pd.DataFrame] = None
+    # `joint_bands=True` with aggregates: the same two tables of the pooled groups, indexed by
+    # (aggregate, pointwise|cumulative) and (aggregate, window, pointwise|cumulative); every
+    # `aggregates[name]` carries its own slices and its `joint_bands` frame
+    self.aggregate_joint_summary: Optional[pd.DataFrame] = None
+    self.aggregate_window_joint_summary: Optional[pd.DataFrame] = None
 
   def _model_labels(self, b: int) -> pd.Index:
     """The labels of the model steps of series b."""
@@ -592,6 +597,8 @@ class PerSeriesBatchAnalysis(CausalImpactBatchAnalysis):
     self._joint = None
     self.joint_summary = None
     self.window_joint_summary = None
+    self.aggregate_joint_summary = None
+    self.aggregate_window_joint_summary = None
     if all(a.joint_summary is not None for a in analyses):
       self.joint_summary = pd.concat([a.joint_summary for a in analyses], keys=self._names,
                                      names=["series", None])
@@ -1141,8 +1148,37 @@ def scaler_stats(outcome_pre: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
             np.array([np.nanstd(r, axis=0, ddof=1) for r in rows]))
 
 
-def _frame_analyses(rows, alpha: float, ranks, device: int = 0, windows=None):
-  """(`aggregates`, `aggregate_summary`, `aggregate_window_summary`) from one row per group: (name, the `CausalImpactData` of the
+def _aggregate_paths(rows, alpha: float, device: int, windows):
+  """The path arrays of every group's pooled draws in ONE device call (`_native.summarize_draw_paths`,
+  ci_summarize_draw_paths_f64: scale 1, shift 0), as a record keeps them: ({path_*: [G, 1 + W, 2, ...]},
+  the ranks of the excursions' order statistics, the number of draws).  rows, windows: those of
+  `_frame_analyses`.  Window 0 of a group is its post-period (`lib.joint_windows` of its flags), then
+  the effect windows in the order of their names, count 0 for one the group's axis does not cover.
+  Groups of a panel have axes of their own: the draws are padded with 0.0, the observations with NaN,
+  to the widest, and no window reaches the padding."""
+  names = [] if windows is None else list(windows[0])
+  G, N = len(rows), rows[0][5].shape[0]
+  T = max(row[5].shape[1] for row in rows)
+  draws, observed = np.zeros((G, N, T)), np.full((G, T), np.nan)
+  first, count = np.zeros((G, 1 + len(names)), np.int32), np.zeros((G, 1 + len(names)), np.int32)
+  for g, (_, _, obs, flags, _, pooled) in enumerate(rows):
+    width = pooled.shape[1]
+    draws[g, :, :width], observed[g, :width] = pooled, obs
+    covered = {} if windows is None else {w.name: w for w in windows[1][g]}
+    more = None
+    if names:
+      more = lib.Windows(np.array([covered[n].first if n in covered else 0 for n in names], np.int32),
+                         np.array([covered[n].count if n in covered else 0 for n in names], np.int32))
+    first[g], count[g] = lib.joint_windows(np.asarray(flags), more)
+  path_ranks = lib._path_ranks(N, alpha)                        # pylint: disable=protected-access
+  got = _native.summarize_draw_paths(draws, 1.0, 0.0, observed, first, count, path_ranks,
+                                     want=lib._PATH_RECORD, device=device)   # pylint: disable=protected-access
+  return lib._paths_record(got), path_ranks, N                  # pylint: disable=protected-access
+
+
+def _frame_analyses(rows, alpha: float, ranks, device: int = 0, windows=None, joint_bands: bool = False):
+  """(`aggregates`, `aggregate_summary`, `aggregate_window_summary`, `aggregate_joint_summary`,
+  `aggregate_window_joint_summary`) from one row per group: (name, the `CausalImpactData` of the
   pooled outcome -- on the data scale already: standardize_data=False -- the pooled observed outcome
   and the window flags over the model steps, the pooled posterior mean, the pooled draws [N, steps]
   float64).  The order statistics and per-draw totals of the pooled draws come from
@@ -1150,8 +1186,12 @@ def _frame_analyses(rows, alpha: float, ranks, device: int = 0, windows=None):
   built by `_compute_impact_device`.  windows (`effect_windows`): (window names, per group the
   `lib.EffectWindow`s its axis covers); their totals come from `_native.window_totals_host` on the
   same pooled draws (scale 1, shift 0), and the table has NaN rows for a window a group does not
-  cover.  The third result is None without them."""
+  cover.  The third result is None without them.  joint_bands: every group's `joint_bands`,
+  `joint_summary` and `window_joint_summary` (`lib._joint_frames` on the arrays of `_aggregate_paths`,
+  over the index of its `CausalImpactData`) and the last two results, the groups' tables stacked; None
+  without it, the last also without windows."""
   analyses = {}
+  paths = _aggregate_paths(rows, alpha, device, windows) if joint_bands else None
   for g, (name, ci_data, observed, flags, mean, draws) in enumerate(rows):
     dsum = _native.summarize_draws(draws, 1.0, 0.0, observed, flags, ranks, device=device)
     wins, totals = (() if windows is None else windows[1][g]), None
@@ -1160,7 +1200,16 @@ def _frame_analyses(rows, alpha: float, ranks, device: int = 0, windows=None):
           draws[None], 1.0, 0.0, observed, [w.first for w in wins], [w.count for w in wins])[0]
     series, summary, window_summary = lib._compute_impact_device(   # pylint: disable=protected-access
         mean, dsum, observed, flags, ranks, ci_data, alpha, windows=wins, window_totals=totals)
-    analyses[name] = lib.CausalImpactAnalysis(series, summary, None, window_summary=window_summary)
+    joint = (None, None, None)
+    if paths is not None:
+      psum = _cut({k: v[g] for k, v in paths[0].items()}, draws.shape[1], "windows")
+      joint = lib._joint_frames(                                # pylint: disable=protected-access
+          psum, paths[1], paths[2], alpha, np.asarray(observed, np.float64),
+          lib.posterior_processing.model_index(ci_data), ci_data.data.index,
+          None if windows is None else list(windows[0]))
+    analyses[name] = lib.CausalImpactAnalysis(series, summary, None, window_summary=window_summary,
+                                              joint_bands=joint[0], joint_summary=joint[1],
+                                              window_joint_summary=joint[2])
   table = pd.concat([a.summary for a in analyses.values()], keys=list(analyses),
                     names=["aggregate", None])
   window_table_ = None
@@ -1170,13 +1219,26 @@ def _frame_analyses(rows, alpha: float, ranks, device: int = 0, windows=None):
     window_table_ = pd.concat(
         [blank if a.window_summary is None else a.window_summary.reindex(full) for a in analyses.values()],
         keys=list(analyses), names=["aggregate", "window", None])
-  return analyses, table, window_table_
+  joint_table, window_joint_table = None, None
+  if paths is not None:
+    joint_table = pd.concat([a.joint_summary for a in analyses.values()], keys=list(analyses),
+                            names=["aggregate", None])
+    if windows is not None:
+      window_joint_table = pd.concat([a.window_joint_summary for a in analyses.values()],
+                                     keys=list(analyses), names=["aggregate", "window", None])
+  return analyses, table, window_table_, joint_table, window_joint_table
+
+
+def _take_aggregates(res, got):
+  """Hands the five results of `_frame_analyses` to the batch or panel result `res`."""
+  (res.aggregates, res.aggregate_summary, res.aggregate_window_summary, res.aggregate_joint_summary,
+   res.aggregate_window_joint_summary) = got
 
 
 def _aggregate_analyses(agg_names, csr, pooled: np.ndarray, means: np.ndarray, prep: PreparedBatch,
                         outcome_name, alpha: float, ranks, device: int = 0,
-                        windows: Optional[WindowPlan] = None):
-  """(`aggregates`, `aggregate_summary`, `aggregate_window_summary`) of a batch from the pooled draws [G, N, T] (float64, data
+                        windows: Optional[WindowPlan] = None, joint_bands: bool = False):
+  """The results of `_frame_analyses` for a batch from the pooled draws [G, N, T] (float64, data
   scale) and the series' posterior means [B, T] on the data scale.  Per group: the observed outcome
   and the posterior mean are pooled with the same weights (`pool_weighted`; the outcome is NaN
   wherever a member is), the flags are the batch's, and the frames are built by `_frame_analyses` over
@@ -1194,7 +1256,8 @@ def _aggregate_analyses(agg_names, csr, pooled: np.ndarray, means: np.ndarray, p
     rows.append((name, ci_data, observed[g], prep.flags, mean[g], pooled[g]))
   # (the groups share the batch's calendar, hence its windows)
   return _frame_analyses(rows, alpha, ranks, device,
-                         None if windows is None else (windows.names, [windows.windows] * len(rows)))
+                         None if windows is None else (windows.names, [windows.windows] * len(rows)),
+                         joint_bands)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1314,8 +1377,8 @@ def event_plan(agg_names, csr, prep: PreparedPanel, outcome_name) -> EventPlan:
 
 def _event_aggregate_analyses(plan: EventPlan, pooled: np.ndarray, means: Sequence[np.ndarray],
                               alpha: float, ranks, device: int = 0,
-                              windows: Optional[WindowPlan] = None):
-  """(`aggregates`, `aggregate_summary`, `aggregate_window_summary`) of a panel from the pooled draws [G, N, stride] (float64,
+                              windows: Optional[WindowPlan] = None, joint_bands: bool = False):
+  """The results of `_frame_analyses` for a panel from the pooled draws [G, N, stride] (float64,
   data scale; group g owns its first width_g columns) and the series' posterior means over their own
   steps on the data scale.  Per group the posterior mean is pooled over the members' windows like the
   outcome (`pool_event_weighted`, the member order of the draws), the flags are the axis', and the
@@ -1331,7 +1394,8 @@ def _event_aggregate_analyses(plan: EventPlan, pooled: np.ndarray, means: Sequen
              for axis in plan.axes])
   return _frame_analyses(
       [(name, plan.data[g], plan.observed[g], axis.flags, mean[g], pooled[g][:, :axis.width])
-       for g, (name, axis) in enumerate(zip(plan.names, plan.axes))], alpha, ranks, device, wins)
+       for g, (name, axis) in enumerate(zip(plan.names, plan.axes))], alpha, ranks, device, wins,
+      joint_bands)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1446,12 +1510,12 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
     ranks = lib._summary_ranks(host_pool.pooled.shape[1], (alpha / 2.0, 1.0 - alpha / 2.0))   # pylint: disable=protected-access
     devs = list(inference_options.devices) if inference_options.devices else [0]
     if event_aggregates is not None:
-      res.aggregates, res.aggregate_summary, res.aggregate_window_summary = _event_aggregate_analyses(
-          event_aggregates, host_pool.pooled, host_pool.means, alpha, ranks, devs[0], windows)
+      _take_aggregates(res, _event_aggregate_analyses(
+          event_aggregates, host_pool.pooled, host_pool.means, alpha, ranks, devs[0], windows, joint_bands))
     else:
-      res.aggregates, res.aggregate_summary, res.aggregate_window_summary = _aggregate_analyses(
+      _take_aggregates(res, _aggregate_analyses(
           agg_names, csr, host_pool.pooled, np.stack(host_pool.means), prep, outcome_column, alpha,
-          ranks, devs[0], windows)
+          ranks, devs[0], windows, joint_bands))
   return res
 
 
@@ -1796,8 +1860,12 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   `result[b].joint_summary`, `result.joint_summary` as one table indexed by (series,
   pointwise|cumulative) and, with `effect_windows`, `window_joint_summary` indexed by (series, window,
   pointwise|cumulative).  Every draw's largest standardised excursion is taken where the trajectories
-  lie (csrc/ci_paths.h; no draws downloaded), in numpy on the routes fitted series by series.  The
-  pooled `aggregates` get no joint bands.
+  lie (csrc/ci_paths.h; no draws downloaded), in numpy on the routes fitted series by series.  With
+  `aggregates` every pooled group gets the same: `result.aggregates[name]` has `joint_bands`,
+  `joint_summary` and `window_joint_summary` over the batch's calendar, `result.aggregate_joint_summary`
+  is indexed by (aggregate, pointwise|cumulative) and, with `effect_windows`,
+  `result.aggregate_window_joint_summary` by (aggregate, window, pointwise|cumulative) -- one device call
+  on the pooled float64 draws of all groups (ci_summarize_draw_paths_f64), on every route.
   """
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
@@ -1884,9 +1952,9 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   if chain is not None:
     # the posterior means on the data scale with the statistics every series' own frame uses
     mu, sd = scaler_stats(prep.values[:, prep.model_rows[:prep.num_pre], 0])
-    res.aggregates, res.aggregate_summary, res.aggregate_window_summary = _aggregate_analyses(
+    _take_aggregates(res, _aggregate_analyses(
         agg[0], agg[1], chain.result(), means.astype(np.float64) * sd[:, None] + mu[:, None], prep,
-        columns[0], alpha, fit.ranks, launches[0][0], plan)
+        columns[0], alpha, fit.ranks, launches[0][0], plan, joint_bands))
   return res
 
 
@@ -1986,7 +2054,10 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
 
   joint_bands: as in `fit_causalimpact_batch`, every series over its OWN post-period and the
   `effect_windows` in event time; `window_joint_summary` has NaN rows where a series' post-period does
-  not reach a window.  The pooled `event_aggregates` get no joint bands."""
+  not reach a window.  With `event_aggregates` every pooled group gets `joint_bands`, `joint_summary`
+  and `window_joint_summary` on its own `event_time` axis, and the result
+  `aggregate_joint_summary` and `aggregate_window_joint_summary` as in `fit_causalimpact_batch`, with
+  blank rows where a group's axis does not reach a window."""
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
   placebo = lib.resolve_placebo(placebo)
@@ -2062,6 +2133,6 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
     for b, (Tb, nb) in enumerate(zip(prep.lengths, prep.num_pre)):
       mu, sd = scaler_stats(prep.raw[b][prep.model_rows[b][:nb], 0][None])
       data_means.append(means[b, :Tb].astype(np.float64) * sd[0] + mu[0])
-    res.aggregates, res.aggregate_summary, res.aggregate_window_summary = _event_aggregate_analyses(
-        plan, chain.result(), data_means, alpha, fit.ranks, launches[0][0], wplan)
+    _take_aggregates(res, _event_aggregate_analyses(
+        plan, chain.result(), data_means, alpha, fit.ranks, launches[0][0], wplan, joint_bands))
   return res

@@ -150,7 +150,8 @@ class CausalImpactAnalysis:
   # critical_value = some step is outside.  An effect that rises and reverses shows here and not in
   # `summary`.  `window_joint_summary` (with `effect_windows=`): the same table per window, indexed by
   # (window, pointwise|cumulative), critical value and test taken over the window's steps alone.
-  # (Init-only and kept as plain attributes, as those above.)
+  # The analysis of a pooled group (`aggregates`, `event_aggregates`) carries all three as well, from
+  # its pooled draws (`batch._aggregate_paths`).  (Init-only and kept as plain attributes, as those above.)
   joint_bands: dataclasses.InitVar[Optional[pd.DataFrame]] = None
   joint_summary: dataclasses.InitVar[Optional[pd.DataFrame]] = None
   window_joint_summary: dataclasses.InitVar[Optional[pd.DataFrame]] = None

@@ -33,6 +33,9 @@
 // path_observed_kernel (one thread per (window, path)) runs between the last two.
 // No [B, T, N] matrix of the whole series is built; no load reaches outside the trajectories,
 // observed and the tables (the trajectory loads are those of window_totals_kernel).
+// path_values_f64_kernel is the first pass for float64 draws [G, N, T] handed in by the caller
+// (ci_summarize_draw_paths_f64); the other passes, hence the order of the additions and every rounding
+// after the first pass, are shared.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -98,6 +101,68 @@ __global__ __launch_bounds__(64) void path_values_kernel(PathsChunk c, const flo
     if (n < N) {
       for (int t = lo; t < hi; ++t) {
         const double v = __dadd_rn(__dmul_rn((double)tile[lane][t - t0], scale), shift);
+        const double point = -__dsub_rn(v, obs_tile[t - t0]);
+        point_sum = __dadd_rn(point_sum, (point != point) ? 0.0 : point);
+        X0[(size_t)(t - first) * N + n] = v;
+        X1[(size_t)(t - first) * N + n] = point_sum;
+      }
+    }
+    __syncthreads();                                                 // the next tile overwrites both
+  }
+}
+
+// path_values_kernel for float64 draws [groups, N, T] that the caller uploaded
+// (ci_summarize_draw_paths_f64: the pooled draws of a group of series): the same expressions, the same
+// X.  `draws` holds the groups g0, g0 + 1, ... of the chunk only; obs, scales and shifts are indexed by
+// the group itself.  A 64 x 64 float64 tile is 32 KiB; its rows are padded by one access width (65
+// doubles: 33280 bytes, with obs_tile 33792 of static LDS), so that the walk down t -- lane l reads
+// tile[l][j], 8 bytes at dword 130 l + 2 j -- takes each 32-lane half of a ds_read_b64 through 32
+// distinct bank pairs.  A row's 64 steps are 512 contiguous bytes.  ALIGNED (T % 2 == 0 and a 16-byte
+// aligned base): 16 bytes per lane, 32 lanes per row and two rows per load; t is even, so t < T
+// implies t + 1 < T; the two 8-byte LDS stores of a lane are 16 bytes from its neighbour's (two-way on
+// ds_write_b64, behind the global loads they wait for).  Otherwise one lane per step, 8 bytes each,
+// consecutive doubles into LDS.  No load reaches outside draws, observed and the tables.
+template <bool ALIGNED>
+__global__ __launch_bounds__(64) void path_values_f64_kernel(PathsChunk c, int g0,
+                                                             const double* __restrict__ draws,
+                                                             double* __restrict__ X_all) {
+  __shared__ double tile[PATHS_TILE][PATHS_TILE + 1];
+  __shared__ double obs_tile[PATHS_TILE];
+  const int lane = threadIdx.x, p = c.p0 + blockIdx.y, N = c.N, T = c.T;
+  const size_t b = p / c.W;
+  const int n0 = blockIdx.x * PATHS_TILE, n = n0 + lane;
+  const int rows = N - n0 < PATHS_TILE ? N - n0 : PATHS_TILE;
+  const int first = c.first[p], count = c.count[p], end = first + count;
+  const double* traj = draws + ((b - g0) * N + n0) * (size_t)T;
+  const double* obs = c.obs + b * T;
+  const double scale = c.scales[b], shift = c.shifts[b];
+  double* X0 = X_all + (size_t)(c.steps_before[p] - c.steps_before[c.p0]) * 2 * N;
+  double* X1 = X0 + (size_t)count * N;
+  double point_sum = 0.0;
+  for (int t0 = first / PATHS_TILE * PATHS_TILE; t0 < end; t0 += PATHS_TILE) {
+    const int lo = first > t0 ? first : t0;
+    const int hi = end < t0 + PATHS_TILE ? end : t0 + PATHS_TILE;    // (lo < hi <= T)
+    if (ALIGNED) {
+      const int q = 2 * (lane & 31), r0 = lane >> 5, t = t0 + q;     // t % 2 == 0, so t < T => t + 1 < T
+      if (t < hi && t + 1 >= lo) {
+#pragma unroll 8
+        for (int r = r0; r < rows; r += 2) {
+          const double2 f = *reinterpret_cast<const double2*>(traj + (size_t)r * T + t);
+          tile[r][q] = f.x; tile[r][q + 1] = f.y;
+        }
+      }
+    } else {
+      const int t = t0 + lane;
+      if (t >= lo && t < hi) {
+#pragma unroll 16
+        for (int r = 0; r < rows; ++r) tile[r][lane] = traj[(size_t)r * T + t];
+      }
+    }
+    if (t0 + lane >= lo && t0 + lane < hi) obs_tile[lane] = obs[t0 + lane];
+    __syncthreads();
+    if (n < N) {
+      for (int t = lo; t < hi; ++t) {
+        const double v = __dadd_rn(__dmul_rn(tile[lane][t - t0], scale), shift);
         const double point = -__dsub_rn(v, obs_tile[t - t0]);
         point_sum = __dadd_rn(point_sum, (point != point) ? 0.0 : point);
         X0[(size_t)(t - first) * N + n] = v;

@@ -3,8 +3,8 @@
 // ci_session_summarize_predictions, ci_session_summarize_placebo (kernels: ci_placebo.h),
 // ci_session_summarize_windows, ci_ll_session_summarize_windows
 // (kernel: ci_windows.h), ci_session_summarize_paths, ci_ll_session_summarize_paths (kernels: ci_paths.h),
-// ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] on
-// draws the caller hands in; ci_session_pool_trajectories, ci_ll_session_pool_trajectories and
+// ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] and
+// ci_summarize_draw_paths_f64 on draws the caller hands in; ci_session_pool_trajectories, ci_ll_session_pool_trajectories and
 // ci_session_pool_event_trajectories (kernels: ci_pool.h) on the trajectories a session holds.
 #include <cmath>
 #include <vector>
@@ -131,22 +131,29 @@ hipError_t paths_launch(hipStream_t stream, int N, int T, int W, int p0, int pai
                         const float* traj, const double* obs, const double* scales, const double* shifts,
                         const int* first, const int* count, const long long* steps_before, double* X,
                         double* mom, double* observed_excursion, int* at, double* excursion, int* exceed);
+hipError_t paths_launch_f64(hipStream_t stream, int N, int T, int W, int p0, int pairs, int max_count,
+                            const double* draws, int g0, const double* obs, const double* scales,
+                            const double* shifts, const int* first, const int* count,
+                            const long long* steps_before, double* X, double* mom,
+                            double* observed_excursion, int* at, double* excursion, int* exceed);
 }  // namespace ci
 
 // The window tables of ci_session_summarize_windows and ci_session_summarize_paths: first, count
-// [B, W] inside the session's T steps, the error naming the offending window.
+// [B, W] inside the session's T steps, the error naming the offending window.  unit, whose: what the
+// B rows are called and whose steps they are (ci_summarize_draw_paths_f64: groups of draws).
 static int check_window_table(const char* what, int B, int T, int32_t W, int max_windows,
-                              const int32_t* first, const int32_t* count) {
+                              const int32_t* first, const int32_t* count, const char* unit = "series",
+                              const char* whose = "the session's") {
   if (W < 1 || W > max_windows)
     return fail("%s: num_windows must be in [1, %d], got %d", what, max_windows, W);
   for (int b = 0; b < B; ++b)
     for (int w = 0; w < W; ++w) {
       const int f = first[(size_t)b * W + w], c = count[(size_t)b * W + w];
-      if (f < 0) return fail("%s: window %d of series %d: first step %d is negative", what, w, b, f);
-      if (c < 0) return fail("%s: window %d of series %d: count %d is negative", what, w, b, c);
+      if (f < 0) return fail("%s: window %d of %s %d: first step %d is negative", what, w, unit, b, f);
+      if (c < 0) return fail("%s: window %d of %s %d: count %d is negative", what, w, unit, b, c);
       if ((long long)f + c > T)
-        return fail("%s: window %d of series %d: steps %d .. %lld end beyond the session's %d steps",
-                    what, w, b, f, (long long)f + c - 1, T);
+        return fail("%s: window %d of %s %d: steps %d .. %lld end beyond %s %d steps",
+                    what, w, unit, b, f, (long long)f + c - 1, whose, T);
     }
   return 0;
 }
@@ -204,6 +211,10 @@ static int windows_resident(const char* what, int device, hipStream_t stream, in
 // steps the doubles paths_pair_doubles counts -- stays within max_bytes; the results cannot depend on
 // the chunking.  All of it is the call's own and goes back on every return path; the summary's
 // scratch is neither built nor touched.  num_chunks (may be NULL): how many chunks it took.
+// host_draws != NULL (ci_summarize_draw_paths_f64; traj is then NULL): the B rows are groups of float64
+// draws [B, N, T] on the host.  The draws of the groups a chunk's pairs belong to are uploaded for
+// that chunk and count N * T doubles each against max_bytes, so a chunk may end inside a group (whose
+// draws the next chunk uploads again); a pair is still computed alone.
 static size_t paths_pair_doubles(int N, int count) {
   // X [count, 2, N], moments [count, 4], excursion [2, N], order [2, 8], observed_excursion [2],
   // at and exceed [2] int32 each
@@ -215,10 +226,14 @@ static int paths_resident(const char* what, int device, hipStream_t stream, int 
                           const double* observed, int32_t W, const int32_t* first, const int32_t* count,
                           int32_t num_ranks, const int32_t* ranks, double* center, double* spread,
                           double* excursion, double* excursion_order, double* observed_excursion,
-                          int32_t* at, int32_t* exceed, int64_t max_bytes, int32_t* num_chunks) {
-  if (check_window_table(what, B, T, W, 64, first, count)) return 1;
+                          int32_t* at, int32_t* exceed, int64_t max_bytes, int32_t* num_chunks,
+                          const double* host_draws = nullptr) {
+  const char* unit = host_draws ? "group" : "series";
+  if (check_window_table(what, B, T, W, 64, first, count, unit, host_draws ? "the draws'" : "the session's"))
+    return 1;
   if (check_ranks(num_ranks, ranks, N)) return 1;
   const int R = ci::SUMM_MAX_RANKS;
+  const size_t group_doubles = host_draws ? (size_t)N * T : 0;      // the uploaded draws of one group
   const size_t BW = (size_t)B * W, BT = (size_t)B * T;
   const size_t table_bytes = (BT + 2 * (size_t)B) * sizeof(double) + 2 * BW * sizeof(int) +
                              (BW + 1) * sizeof(long long) + R * sizeof(int);
@@ -229,19 +244,25 @@ static int paths_resident(const char* what, int device, hipStream_t stream, int 
   // chunks of consecutive pairs: [starts[i], starts[i + 1])
   std::vector<long long> steps_before(BW + 1, 0);
   std::vector<size_t> starts(1, 0);
-  size_t used = 0, most_steps = 0, most_pairs = 0;
+  size_t used = 0, most_steps = 0, most_pairs = 0, most_groups = 0;
   for (size_t p = 0; p < BW; ++p) {
     steps_before[p + 1] = steps_before[p] + count[p];
-    const size_t need = paths_pair_doubles(N, count[p]);
-    if (need > budget)
-      return fail("%s: window %d of series %d: its %d steps of %d draws take %zu bytes of device memory "
-                  "beside %zu of tables, the limit is %lld", what, (int)(p % W), (int)(p / W), count[p], N,
-                  need * sizeof(double), table_bytes, (long long)max_bytes);
+    size_t need = paths_pair_doubles(N, count[p]);
+    if (need + group_doubles > budget)
+      return fail("%s: window %d of %s %d: its %d steps of %d draws%s take %zu bytes of device memory "
+                  "beside %zu of tables, the limit is %lld", what, (int)(p % W), unit, (int)(p / W), count[p],
+                  N, host_draws ? " and the group's own draws" : "", (need + group_doubles) * sizeof(double),
+                  table_bytes, (long long)max_bytes);
+    if (p > 0 && p / W != (p - 1) / W) need += group_doubles;       // (the first pair of its group in this chunk)
     if (used + need > budget || p - starts.back() == 65535) {
       starts.push_back(p);
       used = 0;
+      need = paths_pair_doubles(N, count[p]);
     }
+    if (used == 0) need += group_doubles;                            // (the first pair of a chunk)
     used += need;
+    const size_t groups = p / W - starts.back() / W + 1;
+    most_groups = groups > most_groups ? groups : most_groups;
     const size_t steps = (size_t)(steps_before[p + 1] - steps_before[starts.back()]);
     most_steps = steps > most_steps ? steps : most_steps;
     most_pairs = p + 1 - starts.back() > most_pairs ? p + 1 - starts.back() : most_pairs;
@@ -252,6 +273,8 @@ static int paths_resident(const char* what, int device, hipStream_t stream, int 
   DevBuf<double> d_f64, d_X;  // observed [B, T], scale, shift [B]; per chunk: moments, excursion, order, observed_excursion
   DevBuf<int> d_i32;          // first, count [B, W], ranks [8]; per chunk: at, exceed [pairs, 2]
   DevBuf<long long> d_steps;
+  DevBuf<double> d_draws;     // (host_draws) per chunk: the draws of its groups [groups, N, T]
+  if (host_draws) HIP_TRY(d_draws.alloc(most_groups * group_doubles));
   HIP_TRY(d_f64.alloc(BT + 2 * (size_t)B + most_steps * 4 + most_pairs * 2 * ((size_t)N + R + 1)));
   HIP_TRY(d_X.alloc(most_steps * 2 * N + 1));
   HIP_TRY(d_i32.alloc(2 * BW + R + 4 * most_pairs));
@@ -282,8 +305,17 @@ static int paths_resident(const char* what, int device, hipStream_t stream, int 
     const size_t steps = (size_t)(steps_before[p0 + pairs] - steps_before[p0]);
     int max_count = 0;
     for (size_t p = p0; p < p0 + pairs; ++p) max_count = count[p] > max_count ? count[p] : max_count;
-    HIP_TRY(ci::paths_launch(stream, N, T, W, (int)p0, (int)pairs, max_count, traj, d_f64.p, d_scale, d_shift,
-                             d_i32.p, d_count, d_steps.p, d_X.p, d_mom, d_obsexc, d_at, d_exc, d_exceed));
+    if (host_draws) {
+      const size_t g0 = p0 / W, groups = (p0 + pairs - 1) / W - g0 + 1;
+      HIP_TRY(hipMemcpyAsync(d_draws.p, host_draws + g0 * group_doubles, groups * group_doubles * sizeof(double),
+                             hipMemcpyHostToDevice, stream));
+      HIP_TRY(ci::paths_launch_f64(stream, N, T, W, (int)p0, (int)pairs, max_count, d_draws.p, (int)g0, d_f64.p,
+                                   d_scale, d_shift, d_i32.p, d_count, d_steps.p, d_X.p, d_mom, d_obsexc, d_at,
+                                   d_exc, d_exceed));
+    } else {
+      HIP_TRY(ci::paths_launch(stream, N, T, W, (int)p0, (int)pairs, max_count, traj, d_f64.p, d_scale, d_shift,
+                               d_i32.p, d_count, d_steps.p, d_X.p, d_mom, d_obsexc, d_at, d_exc, d_exceed));
+    }
     if (excursion_order)
       HIP_TRY(launch_select(stream, N, 1, (int)(2 * pairs), num_ranks, d_ranks, d_exc, nullptr, d_order,
                             nullptr));
@@ -823,6 +855,41 @@ int ci_summarize_draws_f64(int32_t device, int32_t num_draws, int32_t T, const d
                            double* cum_order, double* per_draw, double* per_draw_order) {
   return summarize_draws_impl<double>(device, num_draws, T, trajectories, scale, shift, observed, flags,
                                       num_ranks, ranks, value_order, cum_order, per_draw, per_draw_order);
+}
+
+int ci_summarize_draw_paths_f64(int32_t device, int32_t num_groups, int32_t num_draws, int32_t T,
+                                const double* draws, const double* scale, const double* shift,
+                                const double* observed, int32_t num_windows, const int32_t* first,
+                                const int32_t* count, int32_t num_ranks, const int32_t* ranks,
+                                double* center, double* spread, double* excursion, double* excursion_order,
+                                double* observed_excursion, int32_t* at, int32_t* exceed) {
+  return ci_test_summarize_draw_paths_f64(device, num_groups, num_draws, T, draws, scale, shift, observed,
+                                          num_windows, first, count, num_ranks, ranks, center, spread,
+                                          excursion, excursion_order, observed_excursion, at, exceed,
+                                          CI_PATHS_MAX_BYTES, nullptr);
+}
+
+int ci_test_summarize_draw_paths_f64(int32_t device, int32_t num_groups, int32_t num_draws, int32_t T,
+                                     const double* draws, const double* scale, const double* shift,
+                                     const double* observed, int32_t num_windows, const int32_t* first,
+                                     const int32_t* count, int32_t num_ranks, const int32_t* ranks,
+                                     double* center, double* spread, double* excursion,
+                                     double* excursion_order, double* observed_excursion, int32_t* at,
+                                     int32_t* exceed, int64_t max_bytes, int32_t* num_chunks) {
+  const char* what = "ci_summarize_draw_paths_f64";
+  if (!draws || !scale || !shift || !observed || !first || !count || !ranks)
+    return fail("%s: NULL argument", what);
+  if (num_groups < 1) return fail("%s: num_groups must be >= 1, got %d", what, num_groups);
+  if (num_draws < 2) return fail("%s: num_draws must be >= 2, got %d", what, num_draws);
+  if (T < 1) return fail("%s: T must be >= 1, got %d", what, T);
+  for (int g = 0; g < num_groups; ++g) {
+    if (!std::isfinite(scale[g])) return fail("%s: the scale of group %d is not finite", what, g);
+    if (!std::isfinite(shift[g])) return fail("%s: the shift of group %d is not finite", what, g);
+  }
+  // (the null stream, as ci_summarize_draws: the call has no session)
+  return paths_resident(what, device, nullptr, num_groups, T, num_draws, nullptr, scale, shift, observed,
+                        num_windows, first, count, num_ranks, ranks, center, spread, excursion,
+                        excursion_order, observed_excursion, at, exceed, max_bytes, num_chunks, draws);
 }
 
 int ci_ll_session_hmc_summarize(ci_ll_session* s, const double* scale, const double* shift,
