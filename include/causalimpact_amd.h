@@ -416,6 +416,45 @@ int ci_session_summarize_predictions(ci_session* session, const double* scale, c
 int ci_session_summarize_placebo(ci_session* session, const double* scale, const double* shift,
                                  int32_t max_origins, const int32_t* origins, const int32_t* horizon,
                                  double* predicted_mean, double* spread_mean, double* pit_mean);
+/* PLACEBO FORECASTS OF POOLED SUMS: the forecasts above, added over groups of series draw by draw --
+ * the placebo check of a pooled effect.  Additive: CI_ABI_VERSION stays 5; look the symbol up (dlsym)
+ * where an older library may be met.
+ * The group table is that of ci_session_pool_trajectories: group g has the entries k in offsets[g] ..
+ * offsets[g + 1], entry k the member b_k = members[k] (a position in the session, ascending inside a
+ * group) and the weight w_k.  Entry k has its own origin row origins[k, 0 .. O - 1] (steps, strictly
+ * ascending, -1 = unused, at the end); group g has ONE horizon H_g = horizon[g].  For entry k, slot i
+ * and pooled draw n the filter and the forecast of ci_session_summarize_placebo run for series b_k
+ * from origins[k, i] with horizon H_g: C, V, cnt in the sampler's units.  On the data scale
+ *   s = C * scale[b] + cnt * shift[b]          (separate roundings: SUM above)
+ *   v = (V * scale[b]) * scale[b]              (the variance alone)
+ * both 0 where cnt == 0 or the slot is unused.  Pooled in float64, entries ascending, one rounding
+ * per operation, no fused multiply-add:
+ *   S[g, i, n] = init_S[g, i, n];  for k ascending:  S = S + w_k * s_k
+ *   U[g, i, n] = init_U[g, i, n];  for k ascending:  U = U + (w_k * w_k) * v_k
+ * init and out: host arrays [G, O, 2, N], S then U.  init may be NULL (0.0) and may be `out` itself;
+ * several sessions continue one running sum by handing `out` on as `init`, bit for bit however the
+ * series are cut into sessions.
+ * seen (optional, host, [G, O]): the pooled observed sum on the data scale.  With it the call also
+ * returns predicted_mean, spread_mean, pit_mean [G, O] (each may be NULL), the means over the N draws,
+ * as ci_session_summarize_components takes its means, of
+ *   e = seen[g, i] - S;   SUM = S;   SPREAD = U + e * e;   PIT = 0.5 * erfc(-e / sqrt(2 U))
+ * all 0 where U == 0 (U holds sigma_obs^2 of every counted step: it is 0 exactly when no member
+ * counts a step).  Given draw n of EVERY member the pooled sum of the counted observations is
+ * N(S, U) if the members are independent of each other -- the assumption a pooled band rests on,
+ * and the one this check tests: shocks common to the members show as too many exceedances.
+ * Sessions and models as ci_session_summarize_placebo; a ragged session uses each series' own
+ * length T_b.  At most B entries at a time pass through the scratch of ci_session_summarize, a SUM
+ * pass and a VAR pass each; beyond it the call holds the tables and the [G, O, 2, N] accumulators.
+ * Checked before any device call, with the group, entry or slot named: the arguments but init, seen
+ * and the means are not NULL, the block list, a finished ci_session_run, the group table as for
+ * ci_session_pool_trajectories, max_origins in [1, T], horizon >= 1, every origin row ascending with
+ * -1 only at the end, origin + H_g <= T_b, and no mean output without `seen`. */
+int ci_session_pool_placebo(ci_session* session, const double* scale, const double* shift,
+                            int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                            const double* weights, int32_t max_origins,
+                            const int32_t* origins /* [K, O] */, const int32_t* horizon /* [G] */,
+                            const double* init, double* out, const double* seen,
+                            double* predicted_mean, double* spread_mean, double* pit_mean);
 /* Per-draw totals over SUB-WINDOWS of the session's steps, for all B series at once: how an effect
  * unfolds inside the post-period (week 1 against week 4, a promotion's second phase), whose bands,
  * relative effect and tail-area probability need every draw's total over the window and are not

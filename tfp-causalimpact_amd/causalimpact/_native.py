@@ -8,6 +8,7 @@ by these entry points and by nothing else).
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Dict, Optional, Sequence
 
@@ -123,6 +124,9 @@ def load():
   if hasattr(L, "ci_session_summarize_placebo"):       # (additive, likewise)
     L.ci_session_summarize_placebo.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                C.c_void_p, C.c_void_p] + [C.c_void_p] * 3
+  if hasattr(L, "ci_session_pool_placebo"):            # (additive, likewise)
+    L.ci_session_pool_placebo.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 +
+                                          [C.c_int32] + [C.c_void_p] * 8)
   for name in ("ci_session_summarize_windows", "ci_ll_session_summarize_windows"):
     if hasattr(L, name):                               # (additive: a library built before it lacks it)
       getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
@@ -207,7 +211,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_summarize_windows", "ci_ll_session_summarize_windows",
           "ci_session_summarize_paths", "ci_ll_session_summarize_paths",
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
-          "ci_session_pool_event_trajectories",
+          "ci_session_pool_event_trajectories", "ci_session_pool_placebo",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
           "ci_ll_session_draw_latents", "ci_ll_session_hmc_run", "ci_ll_session_hmc_fetch",
           "ci_ll_session_algorithmic_bytes", "ci_ll_session_destroy", "ci_ll_session_create_batch",
@@ -379,6 +383,70 @@ def pool_host(trajectories, scale, shift, groups, init=None) -> np.ndarray:
       b = members[k]
       out[g] = out[g] + weights[k] * (tr[b].astype(np.float64) * sc[b] + sh[b])
   return out
+
+
+def _entry_csr(groups, num_series: int):
+  """`groups` as (offsets, members, weights): the tables themselves, or what `groups_csr` takes."""
+  if isinstance(groups, tuple) and len(groups) == 3 and isinstance(groups[0], np.ndarray):
+    return groups
+  return groups_csr(groups, num_series)
+
+
+def placebo_terms_host(mean, variance, counted, scale, shift):
+  """What one entry adds to a pooled placebo forecast, on the data scale: (s, v) from the per-draw C,
+  V [O, N] and cnt [O] of `causalimpact_lib._placebo_summary_host(per_draw=True)` --
+  s = C * scale + cnt * shift (separate roundings), v = (V * scale) * scale, both 0 where cnt == 0."""
+  C_, V_ = np.asarray(mean, np.float64), np.asarray(variance, np.float64)
+  cnt = np.asarray(counted, np.float64).reshape(-1, 1)
+  scale, shift = np.float64(scale), np.float64(shift)
+  some = cnt > 0
+  return np.where(some, C_ * scale + cnt * shift, 0.0), np.where(some, (V_ * scale) * scale, 0.0)
+
+
+def pool_placebo_host(sums, variances, groups, init=None) -> np.ndarray:
+  """What `Session.pool_placebo` accumulates, in numpy: sums, variances [K, O, N] -- per entry of the
+  group table, in its order, the s and v of `placebo_terms_host` -- and groups: the (offsets, members,
+  weights) of `groups_csr`, or what it takes (the entries are then the members of non-zero weight,
+  group after group, ascending).  Returns acc [G, O, 2, N] float64:
+    acc[g, :, 0] = init[g, :, 0] + sum over the group's entries k, ascending, of w_k * s_k
+    acc[g, :, 1] = init[g, :, 1] + sum over the same entries of (w_k * w_k) * v_k
+  one rounding per operation -- the loop of include/causalimpact_amd.h.  Given every member's draw the
+  pooled sum is N(S, U) IF the members are independent of each other; that is the assumption the
+  pooled placebo tests."""
+  s_, v_ = np.asarray(sums, np.float64), np.asarray(variances, np.float64)
+  if s_.ndim != 3 or s_.shape != v_.shape:
+    raise ValueError(f"`sums` and `variances` must both be [K, O, N], got {s_.shape} and {v_.shape}")
+  offsets, _, weights = _entry_csr(groups, np.iinfo(np.int32).max)
+  G = len(offsets) - 1
+  if offsets[G] != s_.shape[0]:
+    raise ValueError(f"the groups have {offsets[G]} entries, `sums` has {s_.shape[0]}")
+  shape = (G, s_.shape[1], 2, s_.shape[2])
+  out = np.zeros(shape, np.float64) if init is None else np.array(init, np.float64).reshape(shape)
+  for g in range(G):
+    for k in range(offsets[g], offsets[g + 1]):
+      w = np.float64(weights[k])
+      out[g, :, 0] = out[g, :, 0] + w * s_[k]
+      out[g, :, 1] = out[g, :, 1] + (w * w) * v_[k]
+  return out
+
+
+_erfc = np.vectorize(math.erfc, otypes=[np.float64])
+
+
+def finish_placebo_host(acc, seen) -> Dict[str, np.ndarray]:
+  """The finishing step of `Session.pool_placebo` in numpy: acc [G, O, 2, N] (S, U), seen [G, O] the
+  pooled observed sums -> predicted_mean, spread_mean, pit_mean [G, O], the means over the draws of
+  SUM = S, SPREAD = U + e^2, PIT = 0.5 erfc(-e / sqrt(2 U)) with e = seen - S; 0 where U == 0."""
+  acc = np.asarray(acc, np.float64)
+  S, U = acc[:, :, 0], acc[:, :, 1]
+  some = U != 0.0
+  with np.errstate(invalid="ignore", divide="ignore"):
+    e = np.asarray(seen, np.float64)[:, :, None] - S
+    spread = np.where(some, U + e * e, 0.0)
+    pit = np.where(some, 0.5 * _erfc(np.where(some, -e / np.sqrt(2.0 * np.where(some, U, 1.0)), 0.0)), 0.0)
+  # (draws first: the mean adds them in ascending order, as `_placebo_summary_host` takes its means)
+  mean = lambda x: np.ascontiguousarray(np.moveaxis(x, 2, 0)).mean(axis=0)   # pylint: disable=unnecessary-lambda-assignment
+  return dict(predicted_mean=mean(np.where(some, S, 0.0)), spread_mean=mean(spread), pit_mean=mean(pit))
 
 
 def _pool_call(fn, handle, B: int, N: int, T: int, scale, shift, groups, init, event=False,
@@ -1037,6 +1105,68 @@ class Session:
     pb = self.pb
     return _pool_call(fn, self._h, pb.num_series, pb.num_chains * pb.num_results, pb.T, scale, shift,
                       groups, init, True, out_stride)
+
+  def pool_placebo(self, scale, shift, groups, origins, horizon, init=None, seen=None) -> Dict[str, np.ndarray]:
+    """Placebo forecasts of POOLED sums (ci_session_pool_placebo): `summarize_placebo`'s forecasts of
+    the members of every group, added draw by draw with the group's weights, and the members'
+    predictive variances added with the squared weights -- float64, entries ascending, one rounding
+    per operation (`pool_placebo_host` is the same loop in numpy).  scale, shift: scalars or [B];
+    groups: as for `pool_trajectories` (`groups_csr`: members of zero weight are left out);
+    origins: [B, O] int -- every entry takes the row of its series -- or one mapping {position in the
+    session: row [O]} per group, every row strictly ascending steps with -1 (unused) at the end;
+    horizon: a scalar or [G], ONE horizon per group; init: [G, O, 2, N] float64 -- the `acc` of the
+    part of a batch in front of this session -- or None; seen: [G, O] the pooled observed sums on the
+    data scale, or None.  Returns acc [G, O, 2, N] (S, then U) and, with `seen`, predicted_mean,
+    spread_mean, pit_mean [G, O] (`finish_placebo_host`).  Given every member's draw the pooled sum
+    is N(S, U) IF the members are independent of each other: the assumption this check tests."""
+    fn = getattr(self._lib, "ci_session_pool_placebo", None)
+    if fn is None:
+      raise NativeError("the loaded library has no ci_session_pool_placebo: rebuild it")
+    pb = self.pb
+    B, N = pb.num_series, pb.num_chains * pb.num_results
+    sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
+    for name, a in (("scale", sc), ("shift", sh)):
+      if a.shape not in ((), (B,)):
+        raise ValueError(f"`{name}` must be a scalar or have one entry per series ({B}), got shape {a.shape}")
+    sc = np.ascontiguousarray(np.broadcast_to(sc, (B,)))
+    sh = np.ascontiguousarray(np.broadcast_to(sh, (B,)))
+    offsets, members, weights = _entry_csr(groups, B)
+    G = offsets.size - 1
+    if isinstance(origins, np.ndarray) or not (len(origins) and hasattr(origins[0], "items")):
+      per_series = np.asarray(origins)
+      if per_series.ndim != 2 or per_series.shape[0] != B:
+        raise ValueError(f"`origins` must be [{B}, O] or one mapping per group, got shape {per_series.shape}")
+      org = per_series[members] if members.size else per_series[:0]
+    else:
+      if len(origins) != G:
+        raise ValueError(f"`origins` must have one mapping per group ({G}), got {len(origins)}")
+      rows = [np.asarray(origins[g][int(b)]).reshape(-1) for g in range(G) for b in members[offsets[g]:offsets[g + 1]]]
+      width = max([r.size for r in rows] + [np.asarray(v).size for m in origins for v in m.values()] + [1])
+      org = np.full((len(rows), width), -1, np.int64)
+      for k, r in enumerate(rows):
+        org[k, :r.size] = r
+    org = np.ascontiguousarray(org, dtype=np.int32)
+    O = int(org.shape[1])
+    if members.size == 0:                  # (no entry at all: the tables still want an address)
+      members, weights, org = np.zeros(1, np.int32), np.zeros(1), np.full((1, O), -1, np.int32)
+    hz = np.asarray(horizon)
+    if hz.shape not in ((), (G,)):
+      raise ValueError(f"`horizon` must be a scalar or have one entry per group ({G}), got shape {hz.shape}")
+    hz = np.ascontiguousarray(np.broadcast_to(hz, (G,)), dtype=np.int32)
+    if init is not None:
+      init = np.ascontiguousarray(init, dtype=np.float64)
+      if init.shape != (G, O, 2, N):
+        raise ValueError(f"`init` must be {[G, O, 2, N]}, got {list(init.shape)}")
+    out = {"acc": np.empty((G, O, 2, N), np.float64)}
+    if seen is not None:
+      seen = np.ascontiguousarray(seen, dtype=np.float64)
+      if seen.shape != (G, O):
+        raise ValueError(f"`seen` must be {[G, O]}, got {list(seen.shape)}")
+      out.update({k: np.empty((G, O), np.float64) for k in PLACEBO_OUTPUTS})
+    _check(fn(self._h, sc.ctypes.data, sh.ctypes.data, G, offsets.ctypes.data, members.ctypes.data,
+              weights.ctypes.data, O, org.ctypes.data, hz.ctypes.data, _ptr(init), out["acc"].ctypes.data,
+              _ptr(seen), *[_ptr(out.get(k)) for k in PLACEBO_OUTPUTS]))
+    return out
 
   def close(self):
     if self._h:

@@ -38,6 +38,10 @@ calendar; `prepare_panel`, padded to the longest series):
     aggregates of both -- the group table, the running sums handed from launch to launch, the frames
     of every group.  A calendar aggregate is an event-time aggregate whose members all start at step
     0 with the width T, so one chain and one host pool serve both, given the axes or not;
+  * `PlaceboPoolPlan`, `_PlaceboChain` (`HostPlaceboPool` on the per-series routes),
+    `_take_aggregate_placebo`: the placebo forecasts of the pooled effects (`placebo=` with
+    aggregates) -- per entry of the group table the member's origins, a second chain next to
+    `_PoolChain` for the sums [G, O, 2, N] of csrc/ci_placebo.h, the frames of every group;
   * `pool_weighted` + `_aggregate_analyses` (a batch) and `event_axes` / `event_plan`,
     `pool_event_weighted` + `_event_aggregate_analyses` (a panel): what differs -- every group's axis
     around its members' own treatment starts, the pooled outcome and posterior mean, the rows of
@@ -397,6 +401,9 @@ class CausalImpactBatchAnalysis:
     # `aggregates[name]` carries its own slices and its `joint_bands` frame
     self.aggregate_joint_summary: Optional[pd.DataFrame] = None
     self.aggregate_window_joint_summary: Optional[pd.DataFrame] = None
+    # `placebo=` with aggregates: one row per aggregate with the `lib.PLACEBO_QUALITY_ENTRIES` of its
+    # pooled placebo forecasts; every `aggregates[name]` carries its `placebo` and `placebo_quality`
+    self.aggregate_placebo_quality: Optional[pd.DataFrame] = None
 
   def _model_labels(self, b: int) -> pd.Index:
     """The labels of the model steps of series b."""
@@ -599,6 +606,7 @@ class PerSeriesBatchAnalysis(CausalImpactBatchAnalysis):
     self.window_joint_summary = None
     self.aggregate_joint_summary = None
     self.aggregate_window_joint_summary = None
+    self.aggregate_placebo_quality = None
     if all(a.joint_summary is not None for a in analyses):
       self.joint_summary = pd.concat([a.joint_summary for a in analyses], keys=self._names,
                                      names=["series", None])
@@ -1399,6 +1407,239 @@ def _event_aggregate_analyses(plan: EventPlan, pooled: np.ndarray, means: Sequen
 
 
 # ------------------------------------------------------------------------------------------
+# Placebo forecasts of the pooled effects (`placebo=` with `aggregates=` / `event_aggregates=`)
+# ------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class PlaceboPoolPlan:
+  """What the pooled placebo forecasts of a fit's aggregates are taken over: the group table, per
+  ENTRY of it the member's origins as its own model steps, and per group the same origins as
+  positions on the group's own axis (`labels[g]`), its one horizon and the steps of its post-period.
+  -1: an unused slot, at the end of a row; a group without room for an origin has a row of -1."""
+  csr: Tuple[np.ndarray, np.ndarray, np.ndarray]
+  origins: np.ndarray           # [K, O] int32
+  columns: np.ndarray           # [G, O] int32
+  horizon: np.ndarray           # [G] int32
+  n_post: np.ndarray            # [G]
+  labels: List[pd.Index]
+
+  def entries_of(self, b: int):
+    """[(group, entry)] of the series at position b, groups ascending; groups without an origin left out."""
+    offsets, members, _ = self.csr
+    out = []
+    for g in range(len(offsets) - 1):
+      k = offsets[g] + int(np.searchsorted(members[offsets[g]:offsets[g + 1]], b))
+      if k < offsets[g + 1] and members[k] == b and np.any(self.columns[g] >= 0):
+        out.append((g, int(k)))
+    return out
+
+
+def batch_placebo_pool_plan(csr, origins, horizon, n_post, labels: pd.Index) -> PlaceboPoolPlan:
+  """The plan of a batch: every group has the origins [O] and the horizon every series of the batch
+  has (they share `num_pre` and the post-period), on the batch's model index."""
+  G, K = len(csr[0]) - 1, len(csr[1])
+  origins = np.asarray(origins, np.int32).reshape(-1)
+  return PlaceboPoolPlan(csr, np.tile(origins, (K, 1)), np.tile(origins, (G, 1)), np.full(G, int(horizon), np.int32),
+                         np.full(G, int(n_post)), [labels] * G)
+
+
+def event_placebo_pool_plan(placebo: lib.Placebo, plan: EventPlan, state_dim: int) -> PlaceboPoolPlan:
+  """The plan of a panel's event-time aggregates: group g has `lib.placebo_plan(placebo, L - gap,
+  Hwin, state_dim)` on its `EventAxis` -- the pre-period and the window all its members share -- and
+  member k forecasts from its own step first[k] + column, so every window lies inside every member's
+  own pre-period.  The frames are indexed by `event_time` (column - L)."""
+  offsets = plan.csr[0]
+  plans = [lib.placebo_plan(placebo, axis.L - axis.gap, axis.Hwin, state_dim) for axis in plan.axes]
+  width = max(1, max(len(o) for _, o in plans))
+  columns = np.full((len(plans), width), -1, np.int32)
+  origins = np.full((len(plan.csr[1]), width), -1, np.int32)
+  for g, ((_, cols), axis) in enumerate(zip(plans, plan.axes)):
+    columns[g, :len(cols)] = cols
+    for k, first in zip(range(offsets[g], offsets[g + 1]), axis.first):
+      origins[k, :len(cols)] = np.asarray(cols, np.int64) + int(first)
+  return PlaceboPoolPlan(plan.csr, origins, columns, np.array([h for h, _ in plans], np.int32),
+                         np.array([axis.Hwin for axis in plan.axes]), [axis.index for axis in plan.axes])
+
+
+def _placebo_pool_observed(pp: PlaceboPoolPlan, entry_seen) -> Dict[str, np.ndarray]:
+  """{seen_sum, actual, n_counted: [G, O]} of the pooled sums: seen_sum and actual the weighted sums
+  over a group's entries, ascending, of the members' (`lib._placebo_entry_seen`), n_counted the plain
+  sum -- member-steps.  entry_seen(g, k) -> that dict of entry k, or None before it is known."""
+  offsets, _, weights = pp.csr
+  out = {k: np.zeros(pp.columns.shape) for k in ("seen_sum", "actual", "n_counted")}
+  for g in range(len(offsets) - 1):
+    if not np.any(pp.columns[g] >= 0):
+      continue
+    for k in range(offsets[g], offsets[g + 1]):
+      one = entry_seen(g, k)
+      out["seen_sum"][g] = out["seen_sum"][g] + weights[k] * one["seen_sum"]
+      out["actual"][g] = out["actual"][g] + weights[k] * one["actual"]
+      out["n_counted"][g] = out["n_counted"][g] + one["n_counted"]
+  return out
+
+
+def _fit_placebo_observed(pp: PlaceboPoolPlan, fit: "_Fit") -> Dict[str, np.ndarray]:
+  """`_placebo_pool_observed` of a one-launch fit, from the arrays its launches read: every member
+  as its sampler saw it (float32), on the data scale with its own scaler's statistics."""
+  members = pp.csr[1]
+  known: Dict[Any, Dict] = {}        # (a series of a batch has the same windows in every group)
+
+  def entry_seen(g, k):
+    b = int(members[k])
+    key = (b, int(pp.horizon[g]), pp.origins[k].tobytes())
+    if key not in known:
+      Tb = int(fit.lengths[b])
+      one = lib.SeriesInputs(fit.y[b, :Tb], fit.mask[b, :Tb], None, None, (), False, {})
+      known[key] = lib._placebo_entry_seen(one, fit.own_scale[b], fit.own_shift[b], fit.observed[b, :Tb],   # pylint: disable=protected-access
+                                           pp.origins[k], int(pp.horizon[g]))
+    return known[key]
+  return _placebo_pool_observed(pp, entry_seen)
+
+
+class HostPlaceboPool:
+  """The running sums of the pooled placebo forecasts in numpy, for batches and panels that are fitted
+  series by series: `add(b, forecast)` for b = 0, 1, ... with the `forecast(origins, horizon)` a fit
+  hands to its `_placebo_sink`; every group that has b takes the terms of its own origins and horizon
+  (`_native.pool_placebo_host`'s arithmetic, one entry at a time, entries ascending)."""
+
+  def __init__(self, pp: PlaceboPoolPlan):
+    self.pp = pp
+    self.acc: Optional[np.ndarray] = None
+    self._seen: Dict[int, Dict] = {}
+
+  def add(self, b: int, forecast):
+    pp = self.pp
+    weights = pp.csr[2]
+    for g, k in pp.entries_of(b):
+      one = forecast(pp.origins[k], int(pp.horizon[g]))
+      if self.acc is None:
+        self.acc = np.zeros(pp.columns.shape + (2, one["s"].shape[1]))
+      w = np.float64(weights[k])
+      self.acc[g, :, 0] = self.acc[g, :, 0] + w * one["s"]
+      self.acc[g, :, 1] = self.acc[g, :, 1] + (w * w) * one["v"]
+      self._seen[k] = {name: one[name] for name in ("seen_sum", "actual", "n_counted")}
+
+  def result(self):
+    """(means, observed): `_native.finish_placebo_host` of the sums, and `_placebo_pool_observed`."""
+    observed = _placebo_pool_observed(self.pp, lambda g, k: self._seen[k])
+    if self.acc is None:                       # (no group has room for an origin)
+      return None, observed
+    return _native.finish_placebo_host(self.acc, observed["seen_sum"]), observed
+
+
+class _PlaceboChain(_PoolChain):
+  """The second chain of a fit with aggregates and `placebo=`: the accumulators [G, O, 2, N] of the
+  pooled placebo forecasts (csrc/ci_placebo.h, ci_session_pool_placebo), handed from launch to launch
+  in the order of the trajectories' sum -- list order: class key, then position -- so a group's sums
+  do not depend on how the fit is cut into launches and devices, bit for bit.  The last launch hands
+  the finished sums back with `seen`, the pooled observed sums, and gets the three means."""
+
+  def __init__(self, launches, pp: PlaceboPoolPlan, seen: np.ndarray):
+    super().__init__(launches, pp.csr)
+    self.pp, self.seen = pp, seen
+    self.means: Optional[Dict[str, np.ndarray]] = None
+
+  def groups_of(self, ids: Sequence[int]):
+    """Per group ({place within the launch: weight}, {place: origin row}) over the positions `ids`;
+    both empty for a group without a member there or without an origin."""
+    offsets, members, weights = self.csr
+    place = {int(b): i for i, b in enumerate(ids)}
+    out = []
+    for g in range(len(offsets) - 1):
+      here = [k for k in range(offsets[g], offsets[g + 1])
+              if int(members[k]) in place and np.any(self.pp.columns[g] >= 0)]
+      out.append(({place[int(members[k])]: float(weights[k]) for k in here},
+                  {place[int(members[k])]: self.pp.origins[k] for k in here}))
+    return out
+
+  def session_pool(self, sess, scale, shift, series_inputs=None, observed=None):
+    """(pool, finish) of the open session `sess`: pool(groups, origins, horizon, init) -> acc of the
+    groups handed in, finish(acc, seen) -> the three means.  A session with `pool_placebo` whose model
+    the device filter takes runs both on the device; any other (HMC, several blocks) filters its
+    members in numpy from the parameter draws it holds (`lib._placebo_entry_host`) and pools with the
+    host twin."""
+    on_device = (hasattr(sess, "pool_placebo") and "placebo" in sess.summaries and
+                 lib.device_predictions_supported(series_inputs[0].num_seasons))
+    if on_device:
+      T, B = int(sess.pb.T), int(sess.pb.num_series)
+
+      def pool(groups, origins, horizon, init):
+        return sess.pool_placebo(scale, shift, groups, origins, horizon, init)["acc"]
+
+      def finish(acc, seen):
+        # no slot row is longer than the session's steps: as many slots at a time as it takes
+        out = {k: np.zeros(seen.shape) for k in _native.PLACEBO_OUTPUTS}
+        for j in range(0, acc.shape[1], T):
+          w = min(T, acc.shape[1] - j)
+          got = sess.pool_placebo(scale, shift, [{}] * acc.shape[0], np.full((B, w), -1, np.int32),
+                                  np.ones(acc.shape[0], np.int32), np.ascontiguousarray(acc[:, j:j + w]),
+                                  np.ascontiguousarray(seen[:, j:j + w]))
+          for k in out:
+            out[k][:, j:j + w] = got[k]
+        return out
+      return pool, finish
+    draws = sess.fetch(list(lib._PARAMETER_DRAWS))                 # pylint: disable=protected-access
+
+    def host_pool(groups, origins, horizon, init):
+      csr = _native.groups_csr(groups, len(series_inputs))
+      terms = [lib._placebo_entry_host(                             # pylint: disable=protected-access
+          series_inputs[i], lib._pooled_draws(draws, i), scale[i], shift[i], observed[i],   # pylint: disable=protected-access
+          origins[g][i], int(horizon[g]))
+               for g in range(len(groups)) for i in (int(m) for m in csr[1][csr[0][g]:csr[0][g + 1]])]
+      return _native.pool_placebo_host(np.stack([t["s"] for t in terms]), np.stack([t["v"] for t in terms]),
+                                       csr, init)
+    return host_pool, _native.finish_placebo_host
+
+  def step(self, launch, pool):            # pylint: disable=arguments-renamed
+    """The step of `launch`, its session still open; pool: the pair of `session_pool`.  Only the
+    groups with a member in the launch are added to; the last launch of the list finishes all."""
+    pool, finish = pool
+    k = self._index[int(launch[2][0])]
+    try:
+      acc = self._futures[k - 1].result() if k else None
+      groups = self.groups_of(launch[2])
+      active = [g for g, (members, _) in enumerate(groups) if members]
+      if active:
+        used = self.pp.columns[active] >= 0
+        width = max(1, int(used.sum(axis=1).max()))
+        origins = [{i: row[:width] for i, row in groups[g][1].items()} for g in active]
+        init = None if acc is None else np.ascontiguousarray(acc[active][:, :width])
+        part = pool([groups[g][0] for g in active], origins, np.maximum(self.pp.horizon[active], 1), init)
+        if acc is None:
+          acc = np.zeros(self.pp.columns.shape + part.shape[2:])
+        else:
+          acc = acc.copy()
+        acc[active, :width] = part
+      if k == len(self._futures) - 1 and acc is not None:
+        self.means = finish(acc, self.seen)
+      if self._futures[k].done():            # failed meanwhile by a launch in front that ended in an error
+        self._futures[k].result()
+      self._futures[k].set_result(acc)
+    except BaseException as e:
+      self.fail(launch, e)
+      raise
+
+
+def _take_aggregate_placebo(res, pp: PlaceboPoolPlan, names, means: Optional[Dict[str, np.ndarray]],
+                            observed: Dict[str, np.ndarray], alpha: float):
+  """Gives every `res.aggregates[name]` its `placebo` and `placebo_quality`
+  (`lib._aggregate_placebo_frames`; fit_relative_effect: the aggregate's own cumulative `rel_effect`)
+  and `res` its `aggregate_placebo_quality`, one row per aggregate.  means None: no group has room
+  for an origin."""
+  rows = []
+  for g, name in enumerate(names):
+    one = res.aggregates[name]
+    psum = None
+    if means is not None and np.any(pp.columns[g] >= 0):
+      psum = dict({k: v[g] for k, v in means.items()}, n_counted=observed["n_counted"][g],
+                  seen_sum=np.where(pp.columns[g] >= 0, observed["seen_sum"][g], np.nan))
+    one.placebo, one.placebo_quality = lib._aggregate_placebo_frames(   # pylint: disable=protected-access
+        psum, observed["actual"][g], pp.columns[g], int(pp.horizon[g]), alpha, pp.labels[g], int(pp.n_post[g]),
+        one.summary.loc["cumulative", "rel_effect"])
+    rows.append(one.placebo_quality)
+  res.aggregate_placebo_quality = pd.DataFrame(rows, index=pd.Index(list(names), name="aggregate"))
+
+
+# ------------------------------------------------------------------------------------------
 # The one launch-and-assemble path of batches and panels
 # ------------------------------------------------------------------------------------------
 def _options(alpha, data_options, model_options, inference_options):
@@ -1437,7 +1678,8 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
                     event_aggregates: Optional[EventPlan] = None,
                     windows: Optional[WindowPlan] = None, series_windows=None,
                     placebo=None, placebo_lenient: bool = False,
-                    joint_bands: bool = False) -> PerSeriesBatchAnalysis:
+                    joint_bands: bool = False,
+                    placebo_pool: Optional[PlaceboPoolPlan] = None) -> PerSeriesBatchAnalysis:
   """`fit_causalimpact` on every series in turn: the routes the one-launch path does not have.
   float64 compute (csrc/ci_gibbs64.h) and raw-scale outcomes (their per-series internal
   conditioning, causalimpact_lib._internal_conditioning) exist on the single-series path, and so do
@@ -1462,7 +1704,11 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
   windows a series does not cover.
 
   placebo: the `placebo=` every fit takes; placebo_lenient (panels): a series whose pre-period has
-  no room for an origin gets an empty `placebo` frame and a NaN quality row instead of a ValueError."""
+  no room for an origin gets an empty `placebo` frame and a NaN quality row instead of a ValueError.
+
+  placebo_pool (`placebo` with aggregates): the `PlaceboPoolPlan`.  Every fit hands its
+  `_placebo_sink` the per-draw terms of the origins and the horizon of every group it belongs to, and
+  `HostPlaceboPool` adds them up in position order, as `HostPool` adds the trajectories."""
   opts = dataclasses.replace(data_options, outcome_column=outcome_column)
   base_seed = lib._sanitize_seed(seed)   # pylint: disable=protected-access
   analyses = []
@@ -1472,12 +1718,15 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
     host_pool = HostPool(csr)
   elif event_aggregates is not None:
     host_pool = HostPool(event_aggregates.csr, event_aggregates.axes)
+  host_placebo = None if placebo_pool is None else HostPlaceboPool(placebo_pool)
   for b, frame in enumerate(frames):
     seed_b = base_seed if shared_streams else _native.series_stream_key(base_seed, b)
     if host_pool is not None:
       extra = dict(_trajectory_sink=lambda *a, b=b: host_pool.add(b, *a))
     if placebo is not None:
       extra = dict(extra, placebo=placebo, _placebo_lenient=placebo_lenient)
+    if host_placebo is not None:
+      extra = dict(extra, _placebo_sink=lambda forecast, b=b: host_placebo.add(b, forecast))
     if joint_bands:
       extra = dict(extra, joint_bands=True)
     one = lib.fit_causalimpact(frame, periods[b][0], periods[b][1], alpha=alpha, seed=seed_b,
@@ -1516,6 +1765,8 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
       _take_aggregates(res, _aggregate_analyses(
           agg_names, csr, host_pool.pooled, np.stack(host_pool.means), prep, outcome_column, alpha,
           ranks, devs[0], windows, joint_bands))
+    if host_placebo is not None:
+      _take_aggregate_placebo(res, placebo_pool, list(res.aggregates), *host_placebo.result(), alpha)
   return res
 
 
@@ -1608,7 +1859,8 @@ def placebo_plans(placebo: lib.Placebo, num_pre, num_post, state_dim: int):
   return origins, np.array([h for h, _ in plans], np.int32)
 
 
-def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None):
+def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None,
+                placebo_chain: Optional[_PlaceboChain] = None):
   """One launch of the Gibbs sampler and its summaries on the device.  launch: (device, key,
   positions) as `panel_launches` lists them; kind: the session the positions run in --
     "ordinary"         `_native.Session`: series b of the launch is keyed by positions[0] + b, hence
@@ -1623,7 +1875,8 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
   `lib.SummaryRecord` of `_launch_request` (`lib.take_summaries`).  Every array keeps the series axis,
   and T is the longest series of the launch on every route.
   chain (aggregates of a batch, event-time aggregates of a panel): the launch's pool step runs after
-  the summaries, the session still open."""
+  the summaries, the session still open; placebo_chain (the same with `placebo=`): the step of the
+  pooled placebo forecasts after it."""
   dev, _, ids = launch
   ids = np.asarray(ids, dtype=np.int64)
   mo, io = fit.model_options, fit.inference_options
@@ -1658,10 +1911,14 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
   try:
     sess.run()
     out = sess.fetch(["posterior_means", *_DRAW_SCALARS])
-    record = lib.take_summaries(sess, _launch_request(fit, ids, observed, flags),
-                                _series_inputs(fit, ids, season_change, num_seasons))
+    inputs = _series_inputs(fit, ids, season_change, num_seasons)
+    record = lib.take_summaries(sess, _launch_request(fit, ids, observed, flags), inputs)
     if chain is not None:
       chain.step(launch, chain.session_pool(sess, scale, shift))
+    if placebo_chain is not None:
+      placebo_chain.step(launch, placebo_chain.session_pool(
+          sess, fit.own_scale[ids], fit.own_shift[ids], inputs,
+          [fit.observed[b, :int(fit.lengths[b])] for b in ids]))
   finally:
     sess.close()
   if stride != T:            # (back at the stride of the longest series)
@@ -1695,7 +1952,8 @@ def _series_inputs(fit: _Fit, ids, season_change, num_seasons) -> Optional[List[
                            fit.params[b]) for b, Tb in ((int(b), int(fit.lengths[b])) for b in ids)]
 
 
-def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None):
+def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None,
+                    placebo_chain: Optional[_PlaceboChain] = None):
   """`_run_launch` for the one-launch HMC path (`_hmc.fit_hmc_batch`: B x chains HMC chains, then
   the latent paths and the predictive trajectories on the device): consecutive positions of a batch,
   series b keyed by positions[0] + b.  Its session (`_native.BatchLogLikSession`) has the effect
@@ -1707,11 +1965,13 @@ def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None):
   mo, io = fit.model_options, fit.inference_options
 
   def resident(sess):            # (the session still open: the summaries, then the pool step)
-    record = lib.take_summaries(
-        sess, _launch_request(fit, ids, fit.observed[ids], fit.flags),
-        _series_inputs(fit, ids, np.zeros((0, fit.y.shape[1]), np.uint8), ()))
+    inputs = _series_inputs(fit, ids, np.zeros((0, fit.y.shape[1]), np.uint8), ())
+    record = lib.take_summaries(sess, _launch_request(fit, ids, fit.observed[ids], fit.flags), inputs)
     if chain is not None:
       chain.step(launch, chain.session_pool(sess, fit.scale[ids], fit.shift[ids]))
+    if placebo_chain is not None:          # (no filter on this session: numpy, from its parameter draws)
+      placebo_chain.step(launch, placebo_chain.session_pool(
+          sess, fit.own_scale[ids], fit.own_shift[ids], inputs, list(fit.observed[ids])))
     return record
 
   res = _hmc.fit_hmc_batch(
@@ -1853,7 +2113,18 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   `result[b].placebo_quality`, and `result.placebo_quality` as one table with a row per series, the
   companion of `fit_quality` at the horizon of the post-period.  Forecast on the device that holds
   the draws (csrc/ci_placebo.h) inside every launch; in numpy on the routes `prediction_errors`
-  takes in numpy.  ValueError before any fit when the pre-period has no room for an origin.
+  takes in numpy.  ValueError before any fit when the pre-period has no room for an origin.  With
+  `aggregates` every pooled group gets the same check -- it is where it matters most: a pooled band adds
+  the members' predictive variances as if no shock were common to them, and only a placebo on the
+  pooled sum can show that it is too narrow.  `result.aggregates[name]` then has `placebo` (the
+  `PLACEBO_COLUMNS` on the batch's index: the origins and the horizon every series has) and
+  `placebo_quality`, and `result.aggregate_placebo_quality` has one row per aggregate.  The members'
+  forecasts are added draw by draw with the group's weights, their variances with the squared weights,
+  where the draws lie (csrc/ci_placebo.h, ci_session_pool_placebo), chained from launch to launch like
+  the trajectories' sums; in numpy (`_native.pool_placebo_host`) on the routes that filter there.
+  Given every member's draw the pooled sum is normal with these two moments IF the members are
+  independent of each other: the assumption the check tests.  `actual` and `n_counted` are the
+  weighted sum and the plain sum (member-steps) of the members'.
 
   joint_bands: False (the default: nothing runs, no result differs) or True -- the simultaneous bands
   and the whole-path test of `fit_causalimpact` for every series: `result[b].joint_bands`,
@@ -1907,11 +2178,17 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     if agg is not None:
       agg = (*agg, shared)
     plan = None if effect_windows is None else batch_windows(effect_windows, shared)
+    pool_plan = None
+    if agg is not None and placebo is not None:
+      n_post = int(np.count_nonzero(shared.flags & 2))
+      pl_h, pl_o = lib.placebo_plan(placebo, shared.num_pre, n_post, pl_dim)
+      pool_plan = batch_placebo_pool_plan(agg[1], pl_o if len(pl_o) else [-1], pl_h, n_post,
+                                          shared.index[shared.model_rows])
     return _fit_per_series((pd.DataFrame(values[b], index=index, columns=columns) for b in range(B)),
                            [(pre_period, post_period)] * B, names, columns[0], alpha, seed,
                            data_options, model_options, inference_options, shared_streams, agg,
                            windows=plan, series_windows=None if plan is None else [effect_windows] * B,
-                           placebo=placebo, joint_bands=joint_bands)
+                           placebo=placebo, joint_bands=joint_bands, placebo_pool=pool_plan)
   plan = None if effect_windows is None else batch_windows(effect_windows, prep)
   pl_plan = pl_post = None
   if placebo is not None:
@@ -1936,11 +2213,19 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     launches = [(dev, key, ids[lo:lo + step]) for dev, key, ids in launches
                 for lo in range(0, len(ids), step)]
   chain = None if agg is None else _PoolChain(launches, agg[1])
+  pool_plan = pool_seen = pl_chain = None
+  if agg is not None and placebo is not None:
+    pool_plan = batch_placebo_pool_plan(agg[1], pl_plan[0][0], pl_plan[1][0], pl_post[0],
+                                        prep.index[prep.model_rows])
+    pool_seen = _fit_placebo_observed(pool_plan, fit)
+    pl_chain = _PlaceboChain(launches, pool_plan, pool_seen["seen_sum"])
   if hmc:
-    run = lambda launch: _run_hmc_launch(launch, fit, chain)          # pylint: disable=unnecessary-lambda-assignment
+    run = lambda launch: _run_hmc_launch(launch, fit, chain, pl_chain)          # pylint: disable=unnecessary-lambda-assignment
   else:
-    run = lambda launch: _run_launch(launch, "ordinary", fit, chain)   # pylint: disable=unnecessary-lambda-assignment
-  means, record, diag_draws = _assemble(launches, run if chain is None else chain.guarded(run), B, T)
+    run = lambda launch: _run_launch(launch, "ordinary", fit, chain, pl_chain)   # pylint: disable=unnecessary-lambda-assignment
+  for guard in (chain, pl_chain):
+    run = run if guard is None else guard.guarded(run)
+  means, record, diag_draws = _assemble(launches, run, B, T)
   res = CausalImpactBatchAnalysis(
       prep, names, alpha, means, record.effect, fit.ranks, columns, diag_draws, record,
       _state_dim(model_options, inference_options),
@@ -1955,6 +2240,8 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     _take_aggregates(res, _aggregate_analyses(
         agg[0], agg[1], chain.result(), means.astype(np.float64) * sd[:, None] + mu[:, None], prep,
         columns[0], alpha, fit.ranks, launches[0][0], plan, joint_bands))
+    if pl_chain is not None:
+      _take_aggregate_placebo(res, pool_plan, agg[0], pl_chain.means, pool_seen, alpha)
   return res
 
 
@@ -2050,7 +2337,13 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
 
   placebo: as in `fit_causalimpact_batch`, every series with the horizon and the origins of its OWN
   pre- and post-period.  A series whose pre-period has no room for an origin has an empty
-  `placebo` frame and a NaN row (n_origins 0) in `placebo_quality` -- no error.
+  `placebo` frame and a NaN row (n_origins 0) in `placebo_quality` -- no error.  With
+  `event_aggregates` every pooled group gets the check as in `fit_causalimpact_batch`, in EVENT TIME:
+  group g has the horizon and the origins of `lib.placebo_plan` on the pre-period and the window all
+  its members share (L - gap steps, Hwin), member k forecasts from its own step first_k + column --
+  inside its own pre-period -- and `result.aggregates[name].placebo` is indexed by `event_time`
+  (negative: before the treatment start).  A group without room for an origin has the empty frame and
+  the NaN row; `result.aggregate_placebo_quality` has one row per aggregate.
 
   joint_bands: as in `fit_causalimpact_batch`, every series over its OWN post-period and the
   `effect_windows` in event time; `window_joint_summary` has NaN rows where a series' post-period does
@@ -2096,7 +2389,9 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
     return _fit_per_series(frames, periods, names, columns[0], alpha, seed, data_options,
                            model_options, inference_options, shared_streams, event_aggregates=plan,
                            windows=wplan, series_windows=own, placebo=placebo, placebo_lenient=True,
-                           joint_bands=joint_bands)
+                           joint_bands=joint_bands,
+                           placebo_pool=None if plan is None or placebo is None else
+                           event_placebo_pool_plan(placebo, plan, pl_dim))
   prep = prepare_panel([f[columns] for f in frames], periods, names=names)
   pl_plan = pl_post = None
   if placebo is not None:
@@ -2116,9 +2411,15 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   kind = "ordinary" if route["route"] == "equal_length" else route["route"]
   launches = panel_launches(route, inference_options.devices, shared_streams)
   chain = None if plan is None else _PoolChain(launches, plan.csr, plan.axes)
-  run = lambda launch: _run_launch(launch, kind, fit, chain)   # pylint: disable=unnecessary-lambda-assignment
-  means, record, diag_draws = _assemble(launches, run if chain is None else chain.guarded(run), B,
-                                        prep.y.shape[1])
+  pool_plan = pool_seen = pl_chain = None
+  if plan is not None and placebo is not None:
+    pool_plan = event_placebo_pool_plan(placebo, plan, pl_dim)
+    pool_seen = _fit_placebo_observed(pool_plan, fit)
+    pl_chain = _PlaceboChain(launches, pool_plan, pool_seen["seen_sum"])
+  run = lambda launch: _run_launch(launch, kind, fit, chain, pl_chain)   # pylint: disable=unnecessary-lambda-assignment
+  for guard in (chain, pl_chain):
+    run = run if guard is None else guard.guarded(run)
+  means, record, diag_draws = _assemble(launches, run, B, prep.y.shape[1])
   res = CausalImpactPanelAnalysis(
       prep, names, alpha, means, record.effect, fit.ranks, columns, diag_draws, record,
       _state_dim(model_options, inference_options),
@@ -2135,4 +2436,6 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
       data_means.append(means[b, :Tb].astype(np.float64) * sd[0] + mu[0])
     _take_aggregates(res, _event_aggregate_analyses(
         plan, chain.result(), data_means, alpha, fit.ranks, launches[0][0], wplan, joint_bands))
+    if pl_chain is not None:
+      _take_aggregate_placebo(res, pool_plan, plan.names, pl_chain.means, pool_seen, alpha)
   return res

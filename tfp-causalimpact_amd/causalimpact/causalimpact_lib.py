@@ -287,6 +287,10 @@ def fit_causalimpact(data: pd.DataFrame,
   #  series) called with (posterior_means [T], posterior_trajectories [draws, T], scale, shift):
   #  data-scale value = array * scale + shift
   trajectory_sink = kwargs.pop("_trajectory_sink", None)
+  # (internal, batch.py: the pooled placebo forecasts of the same routes) called with
+  #  forecast(origins [O], horizon) -> `_placebo_entry_host` of this fit's draws: the per-draw terms
+  #  of whatever origins and horizon a group asks of this series, on the data scale
+  placebo_sink = kwargs.pop("_placebo_sink", None)
   # (internal, batch.py: a panel's series without room for a placebo origin gets the NaN row)
   placebo_lenient = kwargs.pop("_placebo_lenient", False)
   if kwargs:
@@ -343,7 +347,7 @@ def fit_causalimpact(data: pd.DataFrame,
       devices=inference_options.devices, local_linear_trend=model_options.local_linear_trend,
       sampler=inference_options.sampler, request=request,
       hmc_init=inference_options.hmc_init, hmc_prior=inference_options.hmc_prior,
-      kernel_flags=inference_options.kernel_flags)
+      kernel_flags=inference_options.kernel_flags, placebo_sink=placebo_sink)
   if trajectory_sink is not None:
     trajectory_sink(posterior_means, posterior_trajectories, base["scale"], base["shift"])
   # (draws pooled on the host -- several devices, float64, HMC -- were summarised inside
@@ -1008,6 +1012,29 @@ def _placebo_frames(psum: Optional[Dict], origins, horizon: int, alpha: float, o
   return frame[list(PLACEBO_COLUMNS)], _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
 
 
+def _aggregate_placebo_frames(psum: Optional[Dict], actual, columns, horizon: int, alpha: float,
+                              labels: pd.Index, n_post: int, fit_relative_effect):
+  """(placebo, placebo_quality) of one POOLED group (`aggregates=` / `event_aggregates=` with
+  `placebo=`): `_placebo_frames` for the group's pooled sums.  psum: predicted_mean, spread_mean,
+  pit_mean [O] of the pooled forecast (`_native.finish_placebo_host`, or the device's), n_counted the
+  member-steps every window counts and seen_sum the weighted sum of the members' `_placebo_seen`;
+  actual [O]: the weighted sum of the members' `actual`; columns [O]: the origins as positions into
+  `labels`, the group's own axis (-1: unused).  The pooled forecast treats the members as independent
+  given their draws: its band adds their predictive variances.  That is the assumption these frames
+  test -- shocks common to the members show as a false-positive rate above alpha."""
+  columns = np.asarray(columns).reshape(-1)
+  used = columns >= 0
+  if psum is None or not np.any(used):
+    frame = pd.DataFrame({k: np.zeros(0) for k in PLACEBO_COLUMNS}, index=labels[:0])
+    return frame, _placebo_quality(None, horizon, alpha, n_post, fit_relative_effect)
+  cols = _placebo_columns(psum, columns, horizon, alpha, np.zeros(len(labels)))
+  cols["actual"] = np.asarray(actual, np.float64)[used] + np.where(cols["n_counted"] > 0, 0.0, np.nan)
+  end = cols.pop("horizon_end_step")
+  frame = pd.DataFrame({"horizon_end": labels[end], **cols}, index=labels[columns[used]])
+  frame.index.name = "origin"
+  return frame[list(PLACEBO_COLUMNS)], _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
+
+
 # --------------------------------------------------------------------------------------
 # Simultaneous bands and the whole-path test (`joint_bands=True`)
 # --------------------------------------------------------------------------------------
@@ -1418,6 +1445,30 @@ def _device_placebo_summaries(sess, part: PlaceboPart):
   return out
 
 
+def _placebo_entry_host(one: "SeriesInputs", draws, scale, shift, observed, origins, horizon) -> Dict:
+  """What one member adds to a pooled placebo forecast, filtered in numpy: for the origins [O] (steps
+  of the series; -1: unused, at the end) and the horizon of the GROUP, s and v [O, N] on the data
+  scale (`_placebo_summary_host(per_draw=True)`, `_native.placebo_terms_host`), n_counted and seen_sum
+  [O] (`_placebo_seen`; 0 in an unused slot) and actual [O], the observed sum of every window
+  (`observed`: the series' outcome on the data scale, NaN: none).  draws: the series' pooled
+  parameter draws."""
+  origins = np.asarray(origins).reshape(-1)
+  got = _placebo_summary_host(*one.filter_inputs(), draws, scale, shift, origins, horizon, per_draw=True)
+  s, v = _native.placebo_terms_host(got["C"], got["V"], got["cnt"], scale, shift)
+  return dict(s=s, v=v, **_placebo_entry_seen(one, scale, shift, observed, origins, horizon))
+
+
+def _placebo_entry_seen(one: "SeriesInputs", scale, shift, observed, origins, horizon) -> Dict:
+  """n_counted, seen_sum and actual [O] of `_placebo_entry_host`: what needs no draws."""
+  origins = np.asarray(origins).reshape(-1)
+  cnt, seen = _placebo_seen(one.outcome(), one.mask, origins, horizon, scale, shift)
+  observed = np.asarray(observed, np.float64)
+  # (every window's own contiguous steps, summed as `_placebo_columns` sums them; 0 in an unused slot)
+  steps = np.maximum(origins, 0).astype(np.int64)[:, None] + np.arange(int(horizon))[None, :]
+  actual = np.where(origins >= 0, np.nansum(observed[np.minimum(steps, observed.shape[0] - 1)], axis=1), 0.0)
+  return dict(n_counted=cnt, seen_sum=np.nan_to_num(seen), actual=actual)
+
+
 def _per_series(part: PlaceboPart, n: int) -> PlaceboPart:
   """`part` with one row per series: scale, shift, horizon [n], origins [n, O]."""
   origins = np.asarray(part.origins)
@@ -1483,7 +1534,7 @@ def _model_mask(ci_data) -> np.ndarray:
 def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps, model=None,
                  dtype=np.float32, seasons=(), num_chains=1, devices=None,
                  local_linear_trend=False, sampler="gibbs", request: Optional[SummaryRequest] = None,
-                 hmc_init="gibbs", hmc_prior="slab", kernel_flags=0):
+                 hmc_init="gibbs", hmc_prior="slab", kernel_flags=0, placebo_sink=None):
   """_train_causalimpact_sts plus the `SummaryRecord` of `request` (on the caller's scale; None: an
   empty record), the record of ONE series (`SummaryRecord.of_series`).  On one device, with the
   float32 Gibbs sampler and unless `request.on_device` is off or it wants the trajectories kept, the
@@ -1608,6 +1659,12 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
       part = _per_series(internal.placebo, 1)
       placebo = _with_placebo_seen(inputs, part, _host_placebo_summaries(inputs, draws, part))
     record = SummaryRecord(effect=effect, predictions=predictions, windows=windows, placebo=placebo)
+  if placebo_sink is not None:
+    # (batch.py, pooled placebo forecasts: the per-draw terms from the parameter draws in the
+    #  sampler's units, mapped to the caller's scale like every other summary)
+    pooled = _pooled_draws({k: out[k][None] for k in _PARAMETER_DRAWS}, 0)
+    placebo_sink(lambda origins, horizon: _placebo_entry_host(
+        inputs[0], pooled, internal.scale, internal.shift, internal.observed, origins, horizon))
   if record.components is not None and cond_s != 1.0:
     # the weights on the caller's model scale, as in `samples`
     record = dataclasses.replace(record, components={

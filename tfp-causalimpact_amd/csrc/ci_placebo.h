@@ -19,23 +19,34 @@
 //   SUM    = C * scale[b] + cnt * shift[b]          (separate roundings)
 //   SPREAD = ((V + (A - C)^2) * scale[b]) * scale[b]
 //   PIT    = 0.5 erfc(-(A - C) / sqrt(2 V))
+//   VAR    = (V * scale[b]) * scale[b]             (the variance alone: what a pooled sum adds up)
 // An origin whose window counts no step, and a slot without origin (-1, at the end of the row),
-// read 0 in all three.  The filter then goes on from the untouched (a, P) and stops after the
+// read 0 in all four.  The filter then goes on from the untouched (a, P) and stops after the
 // series' last origin.  The result is the [B * O, N] matrix `out`, draws contiguous: what the
 // row-statistics kernel reads.  The host checks o + H_b <= T_b for every origin before the launch:
 // no step beyond the series is read.
+//
+// With an ENTRY TABLE (series_of; ci_session_pool_placebo) the grid's rows are entries of a group
+// table instead of series: entry e filters series series_of[e] with the origins' row e and horizon[e],
+// and writes rows e * O .. of `out`.  A series may be the member of several groups, each with origins
+// and a horizon of its own.  placebo_pool_kernel then adds the entries' rows to the groups'
+// accumulators and placebo_finish_kernel turns the accumulators into the three matrices of the
+// pooled sum, N(S, U) given the members' draws:
+//   e = seen - S;  SUM = S;  SPREAD = U + e^2;  PIT = 0.5 erfc(-e / sqrt(2 U));  all 0 where U == 0.
 #pragma once
 #include "ci_predict.h"
 
 namespace ci {
 
-enum PlaceboOut { PLACEBO_SUM = 0, PLACEBO_SPREAD = 1, PLACEBO_PIT = 2 };
+enum PlaceboOut { PLACEBO_SUM = 0, PLACEBO_SPREAD = 1, PLACEBO_PIT = 2, PLACEBO_VAR = 3 };
 
 struct PlaceboArgs {
   PredArgs p;                      // the filter's inputs; p.out [B, O, N], p.ll unused
   int O;                           // origin slots per series
   const int* origins;              // [B, O] strictly ascending, -1: unused (at the end)
   const int* horizon;              // [B]
+  const int* series_of = nullptr;  // the entry table: [E] the series of every entry, origins [E, O],
+                                   // horizon [E], p.out [E, O, N]; nullptr: entry b is series b
 };
 
 // a <- T a, P <- T P T' + Q of step t -> t + 1 (the lines of predict_kernel): the trend's part, then
@@ -61,13 +72,14 @@ __device__ __forceinline__ void placebo_propagate(double (&a)[D], double (&P)[D 
 #undef PM
 }
 
-// grid (ceil(N / 64), B), block 64.
+// grid (ceil(N / 64), B), block 64; with an entry table (ceil(N / 64), E).
 template <int HAS_SLOPE, int NS, int OUT>
 __global__ __launch_bounds__(64) void placebo_kernel(PlaceboArgs k) {
   constexpr int N1 = NS ? NS - 1 : 0, O = 1 + HAS_SLOPE, D = O + N1, NP = D * (D + 1) / 2;
   constexpr int ZS = O < D ? O : 0;              // the block's first effect (NS > 0)
   const int n = blockIdx.x * 64 + threadIdx.x, N = k.p.N, T = k.p.T, NO = k.O;
-  const size_t b = blockIdx.y;
+  const size_t e = blockIdx.y;
+  const size_t b = k.series_of ? (size_t)k.series_of[e] : e;
   if (n >= N) return;
   const int Tb = k.p.series_T ? k.p.series_T[b] : T;
   const size_t bn = b * N + n;
@@ -87,9 +99,9 @@ __global__ __launch_bounds__(64) void placebo_kernel(PlaceboArgs k) {
   const float* y = k.p.y + b * T;
   const uint8_t* mask = k.p.mask + b * T;
   const double* reg = k.p.reg ? k.p.reg + b * T * N + n : nullptr;
-  double* out = k.p.out + b * NO * N + n;
-  const int* org = k.origins + b * NO;
-  const int Hb = k.horizon[b];
+  double* out = k.p.out + e * NO * N + n;
+  const int* org = k.origins + e * NO;
+  const int Hb = k.horizon[e];
 
   double a[D], P[NP];
 #define PM(i, j) P[pred_sym<D>(i, j)]
@@ -148,10 +160,11 @@ __global__ __launch_bounds__(64) void placebo_kernel(PlaceboArgs k) {
       }
       double res = 0.0;
       if (cnt > 0) {
-        const double e = A - C;
+        const double err = A - C;
         if (OUT == PLACEBO_SUM) res = __dadd_rn(__dmul_rn(C, scale), __dmul_rn((double)cnt, shift));
-        else if (OUT == PLACEBO_SPREAD) res = __dmul_rn(__dmul_rn(__dadd_rn(V, __dmul_rn(e, e)), scale), scale);
-        else res = 0.5 * erfc(-e / sqrt(2.0 * V));
+        else if (OUT == PLACEBO_SPREAD) res = __dmul_rn(__dmul_rn(__dadd_rn(V, __dmul_rn(err, err)), scale), scale);
+        else if (OUT == PLACEBO_VAR) res = __dmul_rn(__dmul_rn(V, scale), scale);
+        else res = 0.5 * erfc(-err / sqrt(2.0 * V));
       }
       out[(size_t)slot * N] = res;
       ++slot;
@@ -182,6 +195,59 @@ __global__ __launch_bounds__(64) void placebo_kernel(PlaceboArgs k) {
 #undef PM
 #undef FM
   for (; slot < NO; ++slot) out[(size_t)slot * N] = 0.0;
+}
+
+// The entries c0 .. c1 - 1 of the group table, whose rows [(c1 - c0) * O, N] of one pass lie in M,
+// added to the accumulators acc [G, O, 2, N] (S, then U): one lane per (group, slot, draw), the
+// group's entries of this chunk in ascending order, one rounding per operation --
+//   WHICH == 0 (M holds SUM):  S = S + w_k * s_k;    WHICH == 1 (M holds VAR):  U = U + (w_k * w_k) * v_k
+// so the result depends neither on the launch geometry nor on where the entries are cut.
+// grid (ceil(N / 64), min(G * O, 65535)), block 64.
+template <int WHICH>
+__global__ __launch_bounds__(64) void placebo_pool_kernel(int N, int O, size_t rows, int c0, int c1,
+                                                          const int* __restrict__ offsets,
+                                                          const double* __restrict__ weights,
+                                                          const double* __restrict__ M,
+                                                          double* __restrict__ acc) {
+  const int n = blockIdx.x * 64 + threadIdx.x;
+  if (n >= N) return;
+  for (size_t row = blockIdx.y; row < rows; row += gridDim.y) {
+    const size_t g = row / O, i = row - g * O;
+    const int k0 = offsets[g] > c0 ? offsets[g] : c0;
+    const int k1 = offsets[g + 1] < c1 ? offsets[g + 1] : c1;
+    if (k0 >= k1) continue;
+    double* at = acc + (row * 2 + WHICH) * N + n;
+    double a = *at;
+    for (int k = k0; k < k1; ++k) {
+      const double w = WHICH ? __dmul_rn(weights[k], weights[k]) : weights[k];
+      a = __dadd_rn(a, __dmul_rn(w, M[((size_t)(k - c0) * O + i) * N + n]));
+    }
+    *at = a;
+  }
+}
+
+// The rows r0 .. r0 + rows - 1 of the accumulators acc [G * O, 2, N] against seen [G * O]: the
+// matrix OUT (PLACEBO_SUM, PLACEBO_SPREAD or PLACEBO_PIT of the pooled sum) [rows, N] in `out`.
+// grid (ceil(N / 64), min(rows, 65535)), block 64.
+template <int OUT>
+__global__ __launch_bounds__(64) void placebo_finish_kernel(int N, size_t r0, size_t rows,
+                                                            const double* __restrict__ acc,
+                                                            const double* __restrict__ seen,
+                                                            double* __restrict__ out) {
+  const int n = blockIdx.x * 64 + threadIdx.x;
+  if (n >= N) return;
+  for (size_t r = blockIdx.y; r < rows; r += gridDim.y) {
+    const size_t row = r0 + r;
+    const double S = acc[row * 2 * N + n], U = acc[(row * 2 + 1) * N + n];
+    double res = 0.0;
+    if (U != 0.0) {
+      const double err = seen[row] - S;
+      if (OUT == PLACEBO_SUM) res = S;
+      else if (OUT == PLACEBO_SPREAD) res = __dadd_rn(U, __dmul_rn(err, err));
+      else res = 0.5 * erfc(-err / sqrt(2.0 * U));
+    }
+    out[r * N + n] = res;
+  }
 }
 
 }  // namespace ci

@@ -1,5 +1,5 @@
-// Instantiation unit of the placebo forecasts (ci_placebo.h) and their launch;
-// ci_session_summarize_placebo (ci_summary.hip) calls it.
+// Instantiation unit of the placebo forecasts (ci_placebo.h) and their launches;
+// ci_session_summarize_placebo and ci_session_pool_placebo (ci_summary.hip) call them.
 #include "ci_placebo.h"
 
 namespace ci {
@@ -9,6 +9,7 @@ using PlaceboFn = void (*)(PlaceboArgs);
 template <int HAS_SLOPE, int NS> static PlaceboFn placebo_fn(int out) {
   if (out == PLACEBO_SUM) return placebo_kernel<HAS_SLOPE, NS, PLACEBO_SUM>;
   if (out == PLACEBO_SPREAD) return placebo_kernel<HAS_SLOPE, NS, PLACEBO_SPREAD>;
+  if (out == PLACEBO_VAR) return placebo_kernel<HAS_SLOPE, NS, PLACEBO_VAR>;
   return placebo_kernel<HAS_SLOPE, NS, PLACEBO_PIT>;
 }
 
@@ -25,12 +26,40 @@ template <int HAS_SLOPE> static PlaceboFn placebo_fn(int ns, int out) {
   }
 }
 
-// One pass over B series: `out` one of PlaceboOut, num_seasons 0 (no block) or 2..7.
+// One pass over B series (with args.series_of: B entries): `out` one of PlaceboOut, num_seasons 0
+// (no block) or 2..7.
 hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
                           const PlaceboArgs& args) {
   const PlaceboFn fn = has_slope ? placebo_fn<1>(num_seasons, out) : placebo_fn<0>(num_seasons, out);
   if (!fn) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3((args.p.N + 63) / 64, B), dim3(64), 0, stream, args);
+  return hipGetLastError();
+}
+
+// The rows [(c1 - c0) * O, N] of one pass (which: 0 SUM, 1 VAR) added to acc [G, O, 2, N].
+hipError_t placebo_pool_launch(hipStream_t stream, int N, int O, int G, int which, int c0, int c1,
+                               const int* offsets, const double* weights, const double* M, double* acc) {
+  const size_t rows = (size_t)G * O;
+  const dim3 grid((N + 63) / 64, (unsigned)(rows < 65535 ? rows : 65535)), block(64);
+  if (which)
+    hipLaunchKernelGGL(placebo_pool_kernel<1>, grid, block, 0, stream, N, O, rows, c0, c1, offsets, weights, M, acc);
+  else
+    hipLaunchKernelGGL(placebo_pool_kernel<0>, grid, block, 0, stream, N, O, rows, c0, c1, offsets, weights, M, acc);
+  return hipGetLastError();
+}
+
+// The matrix `out` (PLACEBO_SUM, PLACEBO_SPREAD, PLACEBO_PIT) of the rows r0 .. r0 + rows - 1 of acc.
+hipError_t placebo_finish_launch(hipStream_t stream, int N, size_t r0, size_t rows, int out,
+                                 const double* acc, const double* seen, double* M) {
+  const dim3 grid((N + 63) / 64, (unsigned)(rows < 65535 ? rows : 65535)), block(64);
+  if (out == PLACEBO_SUM)
+    hipLaunchKernelGGL(placebo_finish_kernel<PLACEBO_SUM>, grid, block, 0, stream, N, r0, rows, acc, seen, M);
+  else if (out == PLACEBO_SPREAD)
+    hipLaunchKernelGGL(placebo_finish_kernel<PLACEBO_SPREAD>, grid, block, 0, stream, N, r0, rows, acc, seen, M);
+  else if (out == PLACEBO_PIT)
+    hipLaunchKernelGGL(placebo_finish_kernel<PLACEBO_PIT>, grid, block, 0, stream, N, r0, rows, acc, seen, M);
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

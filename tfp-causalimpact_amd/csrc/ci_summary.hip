@@ -1,6 +1,7 @@
 // ci_summary.hip -- the on-device summaries behind the C-ABI (kernels: ci_summary.h,
 // ci_components.h, ci_predict.h): ci_session_summarize, ci_session_summarize_components,
-// ci_session_summarize_predictions, ci_session_summarize_placebo (kernels: ci_placebo.h),
+// ci_session_summarize_predictions, ci_session_summarize_placebo, ci_session_pool_placebo (kernels:
+// ci_placebo.h),
 // ci_session_summarize_windows, ci_ll_session_summarize_windows
 // (kernel: ci_windows.h), ci_session_summarize_paths, ci_ll_session_summarize_paths (kernels: ci_paths.h),
 // ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] and
@@ -122,6 +123,10 @@ hipError_t predict_launch(hipStream_t stream, int B, int has_slope, int num_seas
 // The launch of ci_placebo.hip (kernels: ci_placebo.h).
 hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
                           const PlaceboArgs& args);
+hipError_t placebo_pool_launch(hipStream_t stream, int N, int O, int G, int which, int c0, int c1,
+                               const int* offsets, const double* weights, const double* M, double* acc);
+hipError_t placebo_finish_launch(hipStream_t stream, int N, size_t r0, size_t rows, int out,
+                                 const double* acc, const double* seen, double* M);
 // The launch of ci_windows.hip (kernel: ci_windows.h).
 hipError_t windows_launch(hipStream_t stream, int B, int N, int T, int W, const float* traj,
                           const double* obs, const double* scales, const double* shifts,
@@ -838,6 +843,123 @@ int ci_session_summarize_placebo(ci_session* s, const double* scale, const doubl
   if (spread_mean && pass(ci::PLACEBO_SPREAD, spread_mean)) return 1;
   if (pit_mean && pass(ci::PLACEBO_PIT, pit_mean)) return 1;
   HIP_TRY(hipStreamSynchronize(stream));   // (the uploads of a call that asks for nothing)
+  return 0;
+}
+
+// The placebo forecasts of POOLED sums: per group, slot and draw the weighted sum S of the members'
+// forecasts and the sum U of their predictive variances (include/causalimpact_amd.h).  The entries
+// of the group table pass through `value` at most B at a time, a SUM pass and its accumulate, then a
+// VAR pass and its accumulate; the accumulators [G, O, 2, N] and the tables are the call's own.
+int ci_session_pool_placebo(ci_session* s, const double* scale, const double* shift,
+                            int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                            const double* weights, int32_t max_origins, const int32_t* origins,
+                            const int32_t* horizon, const double* init, double* out,
+                            const double* seen, double* predicted_mean, double* spread_mean,
+                            double* pit_mean) {
+  if (!s || !scale || !shift || !offsets || !members || !weights || !origins || !horizon || !out)
+    return fail("NULL argument");
+  const ci_problem& pb = s->pb;
+  if (pred_check_session(s, "ci_session_pool_placebo")) return 1;
+  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
+  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins, G = num_groups;
+  if (check_groups(B, G, offsets, members, weights)) return 1;
+  if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
+  if (!seen && (predicted_mean || spread_mean || pit_mean))
+    return fail("predicted_mean, spread_mean and pit_mean need `seen`, the pooled observed sums");
+  const int K = offsets[G];
+  std::vector<int> entry_horizon((size_t)(K ? K : 1));
+  for (int g = 0; g < G; ++g) {
+    const int Hg = horizon[g];
+    if (Hg < 1) return fail("group %d: the horizon must be at least 1, got %d", g, Hg);
+    for (int k = offsets[g]; k < offsets[g + 1]; ++k) {
+      const int b = members[k], Tb = s->ragged ? s->lengths[b] : T;
+      const int32_t* row = origins + (size_t)k * O;
+      entry_horizon[k] = Hg;
+      bool ended = false;
+      for (int i = 0; i < O; ++i) {
+        const int o = row[i];
+        if (o == -1) { ended = true; continue; }
+        if (o < 0)
+          return fail("group %d, entry %d (member %d): slot %d must hold a step or -1 (unused), got %d", g, k, b, i, o);
+        if (ended || (i > 0 && o <= row[i - 1]))
+          return fail("group %d, entry %d (member %d): the origins must be strictly ascending with the unused "
+                      "slots (-1) at the end (slot %d holds %d)", g, k, b, i, o);
+        if ((long long)o + Hg > Tb)
+          return fail("group %d, entry %d (member %d): the origin %d of slot %d with horizon %d reaches beyond "
+                      "the series' %d steps", g, k, b, o, i, Hg, Tb);
+      }
+    }
+  }
+  HIP_TRY(hipSetDevice(pb.device));
+  SummScratch& w = s->summ;
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  hipStream_t stream = s->stream;
+  double* d_scale = w.obs.p + (size_t)B * T;
+  double* d_shift = d_scale + B;
+  if (pred_init_upload(s)) return 1;
+  const size_t rows = (size_t)G * O, acc_n = rows * 2 * N, Ka = K ? K : 1;
+  DevBuf<int> d_int;                     // offsets [G + 1], members [K], horizon [K], origins [K, O]
+  DevBuf<double> d_dbl;                  // acc [G, O, 2, N], seen [G, O], weights [K]
+  HIP_TRY(d_int.alloc((size_t)G + 1 + 2 * Ka + Ka * O));
+  HIP_TRY(d_dbl.alloc(acc_n + rows + Ka));
+  int* d_off = d_int.p;
+  int* d_members = d_off + G + 1;
+  int* d_horizon = d_members + Ka;
+  int* d_origins = d_horizon + Ka;
+  double* d_acc = d_dbl.p;
+  double* d_seen = d_acc + acc_n;
+  double* d_weights = d_seen + rows;
+  HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+  if (K > 0) {
+    HIP_TRY(hipMemcpyAsync(d_members, members, (size_t)K * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_horizon, entry_horizon.data(), (size_t)K * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_origins, origins, (size_t)K * O * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_weights, weights, (size_t)K * sizeof(double), hipMemcpyHostToDevice, stream));
+  }
+  if (init)
+    HIP_TRY(hipMemcpyAsync(d_acc, init, acc_n * sizeof(double), hipMemcpyHostToDevice, stream));
+  else
+    HIP_TRY(hipMemsetAsync(d_acc, 0, acc_n * sizeof(double), stream));
+  if (seen) HIP_TRY(hipMemcpyAsync(d_seen, seen, rows * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
+  if (P > 0 && K > 0)
+    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
+                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
+  ci::PlaceboArgs a;
+  a.p.N = N; a.p.T = T;
+  a.p.y = s->y.p; a.p.mask = s->mask.p; a.p.season_change = s->season_change.p; a.p.series_T = d_series_T;
+  a.p.obs = s->o_obs.p; a.p.lscale = s->o_lscale.p; a.p.sscale = s->o_sscale.p; a.p.drift = s->o_drift.p;
+  a.p.init = s->pred_init.p; a.p.scales = d_scale; a.p.shifts = d_shift;
+  a.p.reg = P > 0 ? w.cum.p : nullptr;
+  a.p.out = w.value.p; a.p.ll = nullptr;
+  a.O = O;
+  // at most B entries at a time: [B * O, N] with O <= T fits `value`
+  for (int c0 = 0; c0 < K; c0 += B) {
+    const int c1 = K - c0 < B ? K : c0 + B;
+    a.series_of = d_members + c0; a.origins = d_origins + (size_t)c0 * O; a.horizon = d_horizon + c0;
+    for (int which = 0; which < 2; ++which) {
+      HIP_TRY(ci::placebo_launch(stream, c1 - c0, pb.has_slope, NS, which ? ci::PLACEBO_VAR : ci::PLACEBO_SUM, a));
+      HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, which, c0, c1, d_off, d_weights, w.value.p, d_acc));
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(out, d_acc, acc_n * sizeof(double), hipMemcpyDeviceToHost, stream));
+  // the means over the draws, one matrix at a time and as many rows as `value` and `obs` hold
+  const size_t per_pass = (size_t)B * T;
+  auto finish = [&](int which, double* mean_dst) -> int {
+    for (size_t r0 = 0; r0 < rows; r0 += per_pass) {
+      const size_t nr = rows - r0 < per_pass ? rows - r0 : per_pass;
+      HIP_TRY(ci::placebo_finish_launch(stream, N, r0, nr, which, d_acc, d_seen, w.value.p));
+      HIP_TRY(ci::comp_launch_row_stats(stream, nr, N, w.value.p, w.obs.p, nullptr));
+      HIP_TRY(hipMemcpyAsync(mean_dst + r0, w.obs.p, nr * sizeof(double), hipMemcpyDeviceToHost, stream));
+    }
+    return 0;
+  };
+  if (predicted_mean && finish(ci::PLACEBO_SUM, predicted_mean)) return 1;
+  if (spread_mean && finish(ci::PLACEBO_SPREAD, spread_mean)) return 1;
+  if (pit_mean && finish(ci::PLACEBO_PIT, pit_mean)) return 1;
+  HIP_TRY(hipStreamSynchronize(stream));
   return 0;
 }
 
