@@ -22,6 +22,8 @@ from causalimpact import _synthetic as syn
 from causalimpact import causalimpact_lib as lib
 from causalimpact import data as cid
 
+import prior_cases
+
 pytestmark = pytest.mark.gpu
 
 SCALE, SHIFT = 3.7, -12.25
@@ -37,7 +39,7 @@ def _origins(Tb, H):
   return [3, 4, 11, 35, Tb - H, -1, -1]
 
 
-def _series(T, P, seed, has_slope, seasons):
+def _series(T, P, seed, has_slope, seasons, distinct=None):
   """Sampler inputs of one series with P design columns (the intercept is the last one); the steps
   11, 12 and 40 are missing; the last 30 % are the masked post-period."""
   y, mask, X, _ = syn.standardize_for_sampler(*syn.make_raw_series(T, max(P - 1, 0), seed), int(0.7 * T))
@@ -49,6 +51,8 @@ def _series(T, P, seed, has_slope, seasons):
   mask[[11, 12, 40]] = True
   spec = _model.series_params(np.where(mask, np.nan, y), mask, X, has_slope=has_slope,
                               num_seasonal_blocks=len(seasons))
+  if distinct is not None:           # record number `distinct` of tests/prior_cases.py: no two fields agree
+    spec = prior_cases.filter_record(spec, P, has_slope, distinct)
   return y, mask, X, spec
 
 
@@ -59,11 +63,12 @@ def _pad(arrs, T, fill):
   return out
 
 
-def _open(lengths, P, has_slope, seasons, ragged=False, only=None, C_=2, S=37, seed=(5, 9)):
+def _open(lengths, P, has_slope, seasons, ragged=False, only=None, C_=2, S=37, seed=(5, 9), distinct=False):
   """(session, inputs): the batch of len(lengths) series, or with `only` = b the session of that
   series alone at series_offset b.  inputs: what the reference needs, as the session holds it."""
   K = len(seasons)
-  series = [_series(T, P, 40 + 7 * b + P, has_slope, seasons) for b, T in enumerate(lengths)]
+  series = [_series(T, P, 40 + 7 * b + P, has_slope, seasons, b if distinct else None)
+            for b, T in enumerate(lengths)]
   T = max(lengths)
   if ragged and K:
     T = (T + 3) & ~3
@@ -166,10 +171,10 @@ def _plan(lengths, H):
 
 
 @functools.lru_cache(maxsize=None)
-def _run(lengths, P, has_slope, seasons, H, ragged=False, only=None, scale=SCALE, shift=SHIFT):
+def _run(lengths, P, has_slope, seasons, H, ragged=False, only=None, scale=SCALE, shift=SHIFT, distinct=False):
   """One session: its parameter draws, its placebo summary (all outputs, then pit_mean alone), its
   prediction summary, the inputs as it holds them and the kernel it ran."""
-  sess, inp = _open(list(lengths), P, has_slope, seasons, ragged, only)
+  sess, inp = _open(list(lengths), P, has_slope, seasons, ragged, only, distinct=distinct)
   try:
     sess.run()
     draws = sess.fetch(PARAM_FIELDS)
@@ -223,6 +228,29 @@ def test_one_seasonal_block_equals_numpy_on_the_fetched_draws(seasons, has_slope
   print("kernel:", name)
   _check(full, inp, draws, has_slope, seasons, [SCALE] * 2, [SHIFT] * 2, H, f"seasons={seasons} slope={has_slope} H={H}")
   np.testing.assert_array_equal(some["pit_mean"], full["pit_mean"])
+
+
+def test_the_forecasts_start_from_every_series_own_distinct_prior_record():
+  """Trend + slope + weekly block, three series fitted with three records in which init_level_loc and
+  the three init_*_scale differ from each other, from the default's and between the series
+  (tests/prior_cases.py).  The same tolerances; the early origins (3 and 4) still feel the initial
+  state, and the reference on a record with one field swapped is far off there."""
+  seasons, lengths, H = ((7, 1),), (133, 133, 133), 9
+  draws, full, _, _, inp, name = _run(lengths, 3, True, seasons, H, distinct=True)
+  print("kernel:", name)
+  _check(full, inp, draws, True, seasons, [SCALE] * 3, [SHIFT] * 3, H, "distinct record")
+  origins, _ = _plan(inp["lengths"], H)
+  for b in range(3):
+    spec = inp["specs"][b]
+    used = [int(o) for o in origins[b] if o >= 0]
+    swaps = dict(init_level_loc=float(inp["y"][b][~inp["mask"][b]][0]), init_level_scale=spec["init_slope_scale"],
+                 init_slope_scale=spec["init_level_scale"], init_seasonal_scale=spec["init_level_scale"],
+                 other_series=None)
+    for f, v in swaps.items():
+      other = dict(inp, specs=[inp["specs"][(b + 1) % 3] if f == "other_series" else dict(spec, **{f: v})] * 3)
+      ref = _reference(other, draws, b, True, seasons, SCALE, SHIFT, used, H)
+      moved = max(float(np.abs(full[k][b, :len(used)] - ref[j].mean(axis=1)).max()) for j, k in enumerate(OUTPUTS))
+      assert moved > 1e-3, (b, f, moved)
 
 
 @pytest.mark.parametrize("seasons", [(), ((7, 1),)])

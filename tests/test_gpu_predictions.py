@@ -23,6 +23,8 @@ from causalimpact import causalimpact_lib as lib
 from causalimpact import data as cid
 from oracle import ci_oracle as orc
 
+import prior_cases
+
 pytestmark = pytest.mark.gpu
 
 SCALE, SHIFT = 3.7, -12.25
@@ -32,7 +34,7 @@ OUTPUTS = ("forecast_mean", "forecast_order", "variance_mean", "pit_mean", "logl
 _erfc = np.vectorize(math.erfc, otypes=[np.float64])
 
 
-def _series(T, P, seed, has_slope, seasons):
+def _series(T, P, seed, has_slope, seasons, distinct=None):
   """Sampler inputs of one series with P design columns (the intercept is the last one); the steps
   11, 12 and 40 are missing inside the pre-period."""
   y, mask, X, _ = syn.standardize_for_sampler(*syn.make_raw_series(T, max(P - 1, 0), seed), int(0.7 * T))
@@ -44,6 +46,8 @@ def _series(T, P, seed, has_slope, seasons):
   mask[[11, 12, 40]] = True
   spec = _model.series_params(np.where(mask, np.nan, y), mask, X, has_slope=has_slope,
                               num_seasonal_blocks=len(seasons))
+  if distinct is not None:           # record number `distinct` of tests/prior_cases.py: no two fields agree
+    spec = prior_cases.filter_record(spec, P, has_slope, distinct)
   return y, mask, X, spec
 
 
@@ -54,11 +58,12 @@ def _pad(arrs, T, fill):
   return out
 
 
-def _open(lengths, P, has_slope, seasons, ragged=False, only=None, C_=2, S=37, seed=(5, 9)):
+def _open(lengths, P, has_slope, seasons, ragged=False, only=None, C_=2, S=37, seed=(5, 9), distinct=False):
   """(session, inputs): the batch of len(lengths) series, or with `only` = b the session of that
   series alone at series_offset b.  inputs: what the reference needs, as the session holds it."""
   K = len(seasons)
-  series = [_series(T, P, 40 + 7 * b + P, has_slope, seasons) for b, T in enumerate(lengths)]
+  series = [_series(T, P, 40 + 7 * b + P, has_slope, seasons, b if distinct else None)
+            for b, T in enumerate(lengths)]
   T = max(lengths)
   if ragged and K:
     T = (T + 3) & ~3
@@ -158,10 +163,10 @@ PARAM_FIELDS = ["observation_noise_scale", "level_scale", "slope_scale", "season
 
 
 @functools.lru_cache(maxsize=None)
-def _run(lengths, P, has_slope, seasons, ragged=False, only=None, scale=SCALE, shift=SHIFT):
+def _run(lengths, P, has_slope, seasons, ragged=False, only=None, scale=SCALE, shift=SHIFT, distinct=False):
   """One session: its parameter draws, its prediction summary (all outputs, then pit_mean alone),
   the inputs as it holds them and the kernel it ran."""
-  sess, inp = _open(list(lengths), P, has_slope, seasons, ragged, only)
+  sess, inp = _open(list(lengths), P, has_slope, seasons, ragged, only, distinct=distinct)
   try:
     sess.run()
     draws = sess.fetch(PARAM_FIELDS)
@@ -218,6 +223,26 @@ def test_one_seasonal_block_equals_numpy_on_the_fetched_draws(seasons, has_slope
   print("kernel:", name)
   _check(full, inp, draws, has_slope, seasons, [SCALE] * 2, [SHIFT] * 2, f"seasons={seasons} slope={has_slope}")
   np.testing.assert_array_equal(some["pit_mean"], full["pit_mean"])
+
+
+def test_the_filter_starts_from_every_series_own_distinct_prior_record():
+  """Trend + slope + weekly block, three series fitted with three records in which init_level_loc and
+  the three init_*_scale differ from each other, from the default's and between the series
+  (tests/prior_cases.py): the filter of series b starts from record b.  The same tolerances; and the
+  reference on a record with one field swapped is far off, so a reader of the wrong field fails."""
+  seasons, lengths = ((7, 1),), (133, 133, 133)
+  draws, full, _, inp, name = _run(lengths, 3, True, seasons, distinct=True)
+  print("kernel:", name)
+  _check(full, inp, draws, True, seasons, [SCALE] * 3, [SHIFT] * 3, "distinct record")
+  for b in range(3):
+    spec = inp["specs"][b]
+    swaps = dict(init_level_loc=float(inp["y"][b][~inp["mask"][b]][0]), init_level_scale=spec["init_slope_scale"],
+                 init_slope_scale=spec["init_level_scale"], init_seasonal_scale=spec["init_level_scale"],
+                 other_series=None)
+    for f, v in swaps.items():
+      other = dict(inp, specs=[inp["specs"][(b + 1) % 3] if f == "other_series" else dict(spec, **{f: v})] * 3)
+      ref = _reference(other, draws, b, True, seasons, SCALE, SHIFT)
+      assert np.abs(full["loglik"][b] - ref["loglik"]).max() > 1e-3, (b, f)
 
 
 @pytest.mark.parametrize("seasons", [(), ((7, 1),)])
