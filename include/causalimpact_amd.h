@@ -603,6 +603,38 @@ int ci_session_pool_event_trajectories(ci_session* session, const double* scale,
                                        int32_t num_groups, const int32_t* offsets, const int32_t* members,
                                        const double* weights, const int32_t* first, const int32_t* width,
                                        int32_t out_stride, const double* init, double* out);
+/* The OUTCOME LINK of a session's summaries: a multiplicative outcome is modelled as log y (or
+ * log1p y), and its effect is wanted on the data scale.  E[exp z] != exp E[z]: the link has to be
+ * applied draw by draw, before any sum or mean.  Additive: CI_ABI_VERSION stays 5; look the symbols
+ * up (dlsym) where an older library may be met.  With
+ *   z = (double)trajectory * scale[b] + shift[b]          two roundings, no FMA, as today
+ * the `value` of the summaries below is z (CI_LINK_IDENTITY, the default: nothing changes, not a
+ * bit), exp(z) (CI_LINK_LOG) or expm1(z) (CI_LINK_LOG1P), the float64 device functions, without a
+ * clamp: an exp that overflows is +inf and propagates as numpy's would.  The link is session state
+ * and may be set any time after create; an unknown link is an error.  It is honoured by
+ *   ci_session_summarize, ci_session_summarize_windows, ci_session_summarize_paths,
+ *   ci_session_pool_trajectories, ci_session_pool_event_trajectories, ci_session_value_mean
+ * wherever they form `value`; point, cum, the totals, moments, excursions and pooled sums keep their
+ * definitions on top of it, so given the device's own values a plain loop on the host still
+ * reproduces them bit for bit, and the element-wise exp / expm1 (within 4 ulp of numpy's) is the only
+ * place where device and host may differ.  ci_session_summarize_components,
+ * ci_session_summarize_predictions, ci_session_summarize_placebo and ci_session_pool_placebo describe
+ * the model, which is Gaussian on the transformed scale: they IGNORE the link.  So do the
+ * ci_ll_session_* calls and ci_summarize_draws* (transform host draws before the upload).  No call
+ * keeps values in the scratch for a later one, so a change of the link finds nothing stale.  In a
+ * ragged session a padded step reads link(shift[b]) and carries no meaning, as before. */
+#define CI_LINK_IDENTITY 0   /* value = z                      (today's behaviour) */
+#define CI_LINK_LOG      1   /* value = exp(z)                                      */
+#define CI_LINK_LOG1P    2   /* value = expm1(z)                                    */
+int ci_session_set_link(ci_session* session, int32_t link);
+/* value_mean [B, T] (host, float64): the mean over the N pooled draws of value[b, n, t] under the
+ * session's link, taken exactly as ci_session_summarize_components takes its means (within
+ * N * 2^-52 * max|x| of any other float64 summation of the row), through the scratch of
+ * ci_session_summarize.  Every link, ordinary and both kinds of ragged sessions.  Under a link the
+ * sampler's posterior_means mapped through (scale, shift) are not the posterior mean of the
+ * prediction; this is.  Checked before any device call: no NULL argument, a finished run. */
+int ci_session_value_mean(ci_session* session, const double* scale, const double* shift,
+                          double* value_mean /* [B, T] */);
 /* The same summary for draws that are on the host (pooled from several devices / processes, or
  * produced by the HMC path): trajectories [num_draws, T] float32 are uploaded to `device`,
  * summarised there and the (one-series) results returned as above. */

@@ -25,6 +25,8 @@ COMPONENT_OUTPUTS = ("trend_mean", "trend_order", "seasonal_mean", "seasonal_ord
 PREDICTION_OUTPUTS = ("forecast_mean", "forecast_order", "variance_mean", "pit_mean", "loglik")
 # the output arrays of ci_session_summarize_placebo, in argument order
 PLACEBO_OUTPUTS = ("predicted_mean", "spread_mean", "pit_mean")
+# the outcome link of a session's summaries (== CI_LINK_*): value = z, exp(z), expm1(z)
+LINK_IDENTITY, LINK_LOG, LINK_LOG1P = 0, 1, 2
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, "lib", "libcausalimpact_amd.so")
 
@@ -127,6 +129,9 @@ def load():
   if hasattr(L, "ci_session_pool_placebo"):            # (additive, likewise)
     L.ci_session_pool_placebo.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 +
                                           [C.c_int32] + [C.c_void_p] * 8)
+  if hasattr(L, "ci_session_set_link"):                # (additive, likewise)
+    L.ci_session_set_link.argtypes = [C.c_void_p, C.c_int32]
+    L.ci_session_value_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
   for name in ("ci_session_summarize_windows", "ci_ll_session_summarize_windows"):
     if hasattr(L, name):                               # (additive: a library built before it lacks it)
       getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
@@ -212,6 +217,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_summarize_paths", "ci_ll_session_summarize_paths",
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
           "ci_session_pool_event_trajectories", "ci_session_pool_placebo",
+          "ci_session_set_link", "ci_session_value_mean",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
           "ci_ll_session_draw_latents", "ci_ll_session_hmc_run", "ci_ll_session_hmc_fetch",
           "ci_ll_session_algorithmic_bytes", "ci_ll_session_destroy", "ci_ll_session_create_batch",
@@ -339,6 +345,19 @@ def summarize_draws(trajectories, scale, shift, observed, flags, ranks, device=0
             obs.ctypes.data, fl.ctypes.data, int(rk.size), rk.ctypes.data,
             vo.ctypes.data, co.ctypes.data, pd_.ctypes.data, do.ctypes.data))
   return dict(value_order=vo, cum_order=co, per_draw=pd_, per_draw_order=do)
+
+
+def link_values_host(z, link) -> np.ndarray:
+  """The outcome link in numpy, float64: z itself (LINK_IDENTITY), np.exp(z) (LINK_LOG) or
+  np.expm1(z) (LINK_LOG1P), z = trajectory * scale + shift in two roundings.  No clamp: an overflow
+  is inf.  The definition the device's `value` under `Session.set_link` is compared with."""
+  z = np.asarray(z, np.float64)
+  if link == LINK_IDENTITY:
+    return z
+  if link not in (LINK_LOG, LINK_LOG1P):
+    raise ValueError(f"unknown link {link!r}: LINK_IDENTITY = 0, LINK_LOG = 1, LINK_LOG1P = 2")
+  with np.errstate(over="ignore"):
+    return np.exp(z) if link == LINK_LOG else np.expm1(z)
 
 
 def groups_csr(groups, num_series: int):
@@ -901,6 +920,32 @@ class Session:
     cyc = np.zeros(32, np.int64)
     _check(self._lib.ci_session_profile(self._h, int(enable), cyc.ctypes.data))
     return cyc
+
+  def set_link(self, link: int):
+    """The outcome link of this session's summaries from now on (ci_session_set_link): LINK_IDENTITY
+    (the default), LINK_LOG or LINK_LOG1P.  `summarize`, `summarize_windows`, `summarize_paths`,
+    `pool_trajectories`, `pool_event_trajectories` and `value_mean` then form value = link(trajectory
+    * scale + shift) (`link_values_host`) draw by draw and keep their definitions on top of it;
+    `summarize_components`, `summarize_predictions`, `summarize_placebo` and `pool_placebo` describe
+    the model and ignore it."""
+    fn = getattr(self._lib, "ci_session_set_link", None)
+    if fn is None:
+      raise NativeError("the loaded library has no ci_session_set_link: rebuild it")
+    _check(fn(self._h, int(link)))
+
+  def value_mean(self, scale, shift) -> np.ndarray:
+    """The mean over the N pooled draws of value[b, n, t] under the session's link
+    (ci_session_value_mean), [B, T] float64 with the series axis kept; scale, shift: scalars or [B].
+    Under a link the sampler's `posterior_means` mapped through (scale, shift) is not this mean."""
+    fn = getattr(self._lib, "ci_session_value_mean", None)
+    if fn is None:
+      raise NativeError("the loaded library has no ci_session_value_mean: rebuild it")
+    B, T = self.pb.num_series, self.pb.T
+    sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (B,)))
+    sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.float64), (B,)))
+    out = np.empty((B, T), np.float64)
+    _check(fn(self._h, sc.ctypes.data, sh.ctypes.data, out.ctypes.data))
+    return out
 
   def summarize(self, scale, shift, observed, flags, ranks) -> Dict[str, np.ndarray]:
     """On-device order statistics / running effect sums of the pooled predictive draws of every

@@ -83,6 +83,10 @@ class PreparedBatch:
   outcome_sd: np.ndarray      # [B] pre-period sd (ddof=1)     (1 if not standardised)
   observed: np.ndarray        # [B, T] data-scale outcome, NaN in gap / tail (predictions only)
   flags: np.ndarray           # [T] uint8: bit 0 = t >= treatment start, bit 1 = in the window
+  # `outcome_link` (`_under_link`): the `_native.LINK_*`, and the prepared batch of the model's copy
+  # (log y); `values` and `observed` here are then the RAW outcome's, everything the sampler reads the model's
+  link: int = 0
+  model: Optional["PreparedBatch"] = None
 
 
 def prepare_batch(values: np.ndarray, index: pd.Index, pre_period, post_period,
@@ -133,6 +137,16 @@ def prepare_batch(values: np.ndarray, index: pd.Index, pre_period, post_period,
                        standardize_data=standardize_data, model_rows=rows, num_pre=n_pre, y=y,
                        mask=mask, design=design, outcome_mean=o_mu, outcome_sd=o_sd,
                        observed=observed, flags=flags)
+
+
+def _under_link(model_prep, raw_prep, link: int):
+  """The prepared batch or panel of a fit under `outcome_link`: what the sampler reads (y, mask, design,
+  the outcome's mean and sd) comes from `model_prep`, prepared from the model's copy (log y, log1p y);
+  what the data-scale frames read -- the raw values and `observed` -- from `raw_prep`, prepared from the
+  input as it came.  `model` keeps `model_prep` for what describes the model (components, prediction
+  errors)."""
+  own = dict(raw=raw_prep.raw) if isinstance(model_prep, PreparedPanel) else dict(values=raw_prep.values)
+  return dataclasses.replace(model_prep, observed=raw_prep.observed, link=link, model=model_prep, **own)
 
 
 def summary_table(names, alpha, ranks, dsum, *, n_win, n_obs, obs_mean, obs_sum, avg_pred,
@@ -409,6 +423,14 @@ class CausalImpactBatchAnalysis:
     """The labels of the model steps of series b."""
     return self._prep.index[self._prep.model_rows]
 
+  def _data_means(self) -> np.ndarray:
+    """The posterior means [B, T] on the data scale: the sampler's through every outcome's (sd, mean),
+    or under `outcome_link` the means of the linked draws as they are (`value_mean`)."""
+    p = self._prep
+    if getattr(p, "link", 0):
+      return np.asarray(self._means, np.float64)
+    return self._means.astype(np.float64) * p.outcome_sd[:, None] + p.outcome_mean[:, None]
+
   def set_joint(self, wsum: Dict[str, np.ndarray], path_ranks, window_names=None):
     """Takes the path arrays of the record's `windows` kind ({path_*: [B, 1 + W, 2, ...]}, window 0
     every series' post-period) and builds `joint_summary` and `window_joint_summary`."""
@@ -480,8 +502,7 @@ class CausalImpactBatchAnalysis:
     p = self._prep
     win = (p.flags & 2) != 0
     obs_w = p.observed[:, win]                                             # [B, T_w]
-    post_mean = (self._means.astype(np.float64) * p.outcome_sd[:, None]
-                 + p.outcome_mean[:, None])[:, win]
+    post_mean = self._data_means()[:, win]
     n_obs = np.sum(~np.isnan(obs_w), axis=1)
     with np.errstate(invalid="ignore", divide="ignore"):
       obs_mean, obs_sum = np.nanmean(obs_w, axis=1), np.nansum(obs_w, axis=1)
@@ -495,22 +516,32 @@ class CausalImpactBatchAnalysis:
     return (pd.DataFrame(p.values[b], index=p.index, columns=self._columns), p.pre_period,
             p.post_period, len(p.model_rows))
 
+  def _model_frame(self, b: int) -> pd.DataFrame:
+    """(`outcome_link`) the frame of series b as its model read it."""
+    p = self._prep.model
+    return pd.DataFrame(p.values[b], index=p.index, columns=self._columns)
+
   def __getitem__(self, b: int) -> lib.CausalImpactAnalysis:
     b = range(len(self))[b]
     if b not in self._cache:
       # (arrays over time are padded to the longest series of a panel: series b owns [0, Tb))
       df, pre, post, Tb = self._series_view(b)
-      ci_data = cid.CausalImpactData(df, pre, post, standardize_data=self._prep.standardize_data)
+      # (`outcome_link`: ci_data of the model's copy; the effect's frames read the raw outcome and
+      #  means that are on the data scale already)
+      linked = bool(getattr(self._prep, "link", 0))
+      ci_data = cid.CausalImpactData(self._model_frame(b) if linked else df, pre, post,
+                                     standardize_data=self._prep.standardize_data)
+      effect_data = lib._data_scale_view(ci_data, df) if linked else ci_data   # pylint: disable=protected-access
       dsum = _cut({k: v[b] for k, v in self._dsum.items()}, Tb, "effect")
-      rq = lib._device_summary_request(ci_data, self.alpha)   # pylint: disable=protected-access
+      rq = lib._device_summary_request(effect_data, self.alpha)   # pylint: disable=protected-access
       series, summary = lib._compute_impact_device(            # pylint: disable=protected-access
-          self._means[b, :Tb], dsum, rq["observed"], rq["flags"], self._ranks, ci_data, self.alpha)
+          self._means[b, :Tb], dsum, rq["observed"], rq["flags"], self._ranks, effect_data, self.alpha)
       self._cache[b] = lib.CausalImpactAnalysis(series, summary, None, self.diagnostics_of(b),
                                                 *self._component_frames(b, ci_data, Tb),
                                                 *self._prediction_frames(b, ci_data, Tb),
                                                 self._window_slice(b),
                                                 *self._placebo_frames(b, ci_data, Tb, summary),
-                                                *self._joint_frames(b, ci_data, Tb))
+                                                *self._joint_frames(b, effect_data, Tb))
     return self._cache[b]
 
   def _placebo_frames(self, b: int, ci_data, num_steps: int, summary: pd.DataFrame):
@@ -545,7 +576,7 @@ class CausalImpactBatchAnalysis:
 
   def _prediction_inputs(self, b: int, num_steps: int):
     """(summary, observed, conditioned) of series b over its `num_steps` steps."""
-    p = self._prep
+    p = getattr(self._prep, "model", None) or self._prep      # (`outcome_link`: the model's own outcome)
     psum = _cut({k: v[b] for k, v in self._psum.items()}, num_steps, "predictions")
     return psum, p.observed[b, :num_steps], ~p.mask[b, :num_steps]
 
@@ -647,13 +678,14 @@ HMC_BATCH_MAX_P = 128
 
 
 def hmc_batch_route(*, float64: bool, standardize_data: bool, num_seasonal_blocks: int, T: int,
-                    P: int, hmc_init: str) -> str:
+                    P: int, hmc_init: str, outcome_link: bool = False) -> str:
   """Where `fit_causalimpact_batch(sampler="hmc")` fits a batch: "one_launch" (all series x chains
   in one kernel launch per device and HBM budget) or "per_series" (`fit_causalimpact` on every
   series in turn, with the series' key: seasonal blocks, T > 4096, P > 128, hmc_init="vi", float64,
-  standardize_data=False -- the refusals of the single-series path stay where they are)."""
+  standardize_data=False -- the refusals of the single-series path stay where they are; and
+  outcome_link, which the one-launch session's summaries do not take)."""
   if (float64 or not standardize_data or num_seasonal_blocks > 0 or T > HMC_BATCH_MAX_T
-      or P > HMC_BATCH_MAX_P or hmc_init != "gibbs"):
+      or P > HMC_BATCH_MAX_P or hmc_init != "gibbs" or outcome_link):
     return "per_series"
   return "one_launch"
 
@@ -775,6 +807,9 @@ class PreparedPanel:
   outcome_sd: np.ndarray        # [B]
   observed: np.ndarray          # [B, T_max] data-scale outcome, NaN in gap / tail / padding
   flags: np.ndarray             # [B, T_max] uint8: bit 0 = t >= treatment start, bit 1 = in the window
+  # `outcome_link` (`_under_link`): as in `PreparedBatch`; `raw` and `observed` are the RAW outcome's
+  link: int = 0
+  model: Optional["PreparedPanel"] = None
 
 
 def prepare_panel(frames_or_values, periods, standardize_data: bool = True,
@@ -923,14 +958,17 @@ class CausalImpactPanelAnalysis(CausalImpactBatchAnalysis):
 
   def _build_summary(self) -> pd.DataFrame:
     p = self._prep
-    post_mean = (self._means.astype(np.float64) * p.outcome_sd[:, None] + p.outcome_mean[:, None])
-    stats = panel_window_stats(p.observed, p.flags, post_mean, p.lengths)
+    stats = panel_window_stats(p.observed, p.flags, self._data_means(), p.lengths)
     return summary_table(self._names, self.alpha, self._ranks, self._dsum, **stats)
 
   def _series_view(self, b: int):
     p = self._prep
     return (pd.DataFrame(p.raw[b], index=p.indices[b], columns=self._columns), *p.periods[b],
             int(p.lengths[b]))
+
+  def _model_frame(self, b: int) -> pd.DataFrame:
+    p = self._prep.model
+    return pd.DataFrame(p.raw[b], index=p.indices[b], columns=self._columns)
 
   def _model_labels(self, b: int) -> pd.Index:
     return self._prep.indices[b][self._prep.model_rows[b]]
@@ -1679,7 +1717,8 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
                     windows: Optional[WindowPlan] = None, series_windows=None,
                     placebo=None, placebo_lenient: bool = False,
                     joint_bands: bool = False,
-                    placebo_pool: Optional[PlaceboPoolPlan] = None) -> PerSeriesBatchAnalysis:
+                    placebo_pool: Optional[PlaceboPoolPlan] = None,
+                    outcome_link=None) -> PerSeriesBatchAnalysis:
   """`fit_causalimpact` on every series in turn: the routes the one-launch path does not have.
   float64 compute (csrc/ci_gibbs64.h) and raw-scale outcomes (their per-series internal
   conditioning, causalimpact_lib._internal_conditioning) exist on the single-series path, and so do
@@ -1708,7 +1747,10 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
 
   placebo_pool (`placebo` with aggregates): the `PlaceboPoolPlan`.  Every fit hands its
   `_placebo_sink` the per-draw terms of the origins and the horizon of every group it belongs to, and
-  `HostPlaceboPool` adds them up in position order, as `HostPool` adds the trajectories."""
+  `HostPlaceboPool` adds them up in position order, as `HostPool` adds the trajectories.
+
+  outcome_link: the `outcome_link=` every fit takes, on the RAW frames; a fit then hands its
+  `_trajectory_sink` the linked draws and their mean, on the data scale already (scale 1, shift 0)."""
   opts = dataclasses.replace(data_options, outcome_column=outcome_column)
   base_seed = lib._sanitize_seed(seed)   # pylint: disable=protected-access
   analyses = []
@@ -1729,6 +1771,8 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
       extra = dict(extra, _placebo_sink=lambda forecast, b=b: host_placebo.add(b, forecast))
     if joint_bands:
       extra = dict(extra, joint_bands=True)
+    if outcome_link is not None:
+      extra = dict(extra, outcome_link=outcome_link)
     one = lib.fit_causalimpact(frame, periods[b][0], periods[b][1], alpha=alpha, seed=seed_b,
                                data_options=opts, model_options=model_options,
                                inference_options=inference_options,
@@ -1804,6 +1848,9 @@ class _Fit:
   # window 0 its post-period) and the order statistics of the excursions
   paths: Optional[lib.Windows] = None
   path_ranks: Sequence[int] = ()
+  # `outcome_link`: the `_native.LINK_*` of the effect summaries and the pooled sums (`observed` is then
+  # the raw outcome, `scale` and `shift` the model's)
+  link: int = 0
 
 
 def _sampler_outcome(prep, data_options) -> np.ndarray:
@@ -1818,12 +1865,13 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
   the sd of every series' own pre-period outcome; placebo: (origins [B, O], horizon [B]) or None."""
   own_shift = own_scale = None
   if inference_options.prediction_errors or placebo is not None:
+    src = prep.model if prep.link else prep          # (the outcome the model read)
     if isinstance(prep, PreparedPanel):
-      stats = [scaler_stats(prep.raw[b][prep.model_rows[b][:nb], 0][None])
+      stats = [scaler_stats(src.raw[b][prep.model_rows[b][:nb], 0][None])
                for b, nb in enumerate(prep.num_pre)]
       own_shift, own_scale = (np.array([st[i][0] for st in stats]) for i in (0, 1))
     else:
-      own_shift, own_scale = scaler_stats(prep.values[:, prep.model_rows[:prep.num_pre], 0])
+      own_shift, own_scale = scaler_stats(src.values[:, prep.model_rows[:prep.num_pre], 0])
   with np.errstate(invalid="ignore"):
     params = [_model.series_params(
         y[b, :Tb], prep.mask[b, :Tb], None if prep.design is None else prep.design[b, :Tb],
@@ -1844,7 +1892,8 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
               own_scale=own_scale, own_shift=own_shift, windows=windows,
               placebo_origins=None if placebo is None else placebo[0],
               placebo_horizon=None if placebo is None else placebo[1], paths=paths,
-              path_ranks=lib._path_ranks(num_draws, alpha) if joint_bands else ())   # pylint: disable=protected-access
+              path_ranks=lib._path_ranks(num_draws, alpha) if joint_bands else (),   # pylint: disable=protected-access
+              link=prep.link)
 
 
 def placebo_plans(placebo: lib.Placebo, num_pre, num_post, state_dim: int):
@@ -1914,6 +1963,7 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
     inputs = _series_inputs(fit, ids, season_change, num_seasons)
     record = lib.take_summaries(sess, _launch_request(fit, ids, observed, flags), inputs)
     if chain is not None:
+      # (`outcome_link`: the session keeps the link `take_summaries` set -- the pool adds linked values)
       chain.step(launch, chain.session_pool(sess, scale, shift))
     if placebo_chain is not None:
       placebo_chain.step(launch, placebo_chain.session_pool(
@@ -1938,7 +1988,7 @@ def _launch_request(fit: _Fit, ids, observed, flags) -> lib.SummaryRequest:
       placebo=None if fit.placebo_origins is None else lib.PlaceboPart(
           *own, fit.placebo_origins[ids], fit.placebo_horizon[ids]),
       paths=None if fit.paths is None else lib.Windows(fit.paths.first[ids], fit.paths.count[ids]),
-      path_ranks=fit.path_ranks)
+      path_ranks=fit.path_ranks, link=fit.link)
 
 
 def _series_inputs(fit: _Fit, ids, season_change, num_seasons) -> Optional[List[lib.SeriesInputs]]:
@@ -2004,7 +2054,8 @@ def _assemble(launches, run, num_series: int, num_steps: int):
   """Runs `launches` [(device, key, positions)] through `run(launch) -> (out, record)`
   (`_run_launch`; the launches of a device in turn, the devices side by side) and puts the series
   axis back together.  Returns what the containers take:
-    means [B, T_max]  the chain mean of posterior_means, 0 beyond a series' length;
+    means [B, T_max]  the chain mean of posterior_means, 0 beyond a series' length (under
+                      `outcome_link` the record's value_mean: data scale, NaN beyond it);
     record            the `lib.SummaryRecord` {name: [B, ...]} per kind (None: a kind the launches
                       did not take); arrays over time are NaN beyond a series' length;
     diag_draws        {name: [B, C, S]} of `_DRAW_SCALARS`, or None for one chain.
@@ -2024,6 +2075,8 @@ def _assemble(launches, run, num_series: int, num_steps: int):
     fetched = gather("fetched", fetched)
     record = results[0][1].map(lambda kind, _: gather(kind, [getattr(rec, kind) for _, rec in results]))
   means = fetched.pop("means")
+  if "value_mean" in record.effect:     # (`outcome_link`: the means of the linked draws, on the data scale)
+    means = record.effect["value_mean"]
   diag_draws = fetched if fetched[_DRAW_SCALARS[0]].shape[1] > 1 else None
   return means, record, diag_draws
 
@@ -2037,7 +2090,8 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
                            names: Optional[Sequence[Any]] = None,
                            shared_streams: bool = False,
                            aggregates=None, effect_windows=None,
-                           placebo=None, joint_bands: bool = False) -> CausalImpactBatchAnalysis:
+                           placebo=None, joint_bands: bool = False,
+                           outcome_link=None) -> CausalImpactBatchAnalysis:
   """`fit_causalimpact` for B series at once.
 
   data: a sequence of DataFrames with identical index and column layout (outcome first, or
@@ -2137,9 +2191,23 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   is indexed by (aggregate, pointwise|cumulative) and, with `effect_windows`,
   `result.aggregate_window_joint_summary` by (aggregate, window, pointwise|cumulative) -- one device call
   on the pooled float64 draws of all groups (ci_summarize_draw_paths_f64), on every route.
+
+  outcome_link: None (the default: nothing runs, no result differs), "log" or "log1p" -- multiplicative
+  outcomes as in `fit_causalimpact`: every series is modelled as log y (log1p y), and `summary`,
+  `result[b]`, `window_summary`, the joint tables and every pooled `aggregates[name]` are on the data
+  scale, from the linked draws.  A pooled draw is the sum over the members of w_b * exp(draw of series
+  b): the link is applied where the draws lie, inside the summary and pool kernels
+  (`_native.Session.set_link`), so a one-launch batch still downloads no draws; the routes fitted
+  series by series apply `_native.link_values_host` in numpy.  A one-launch HMC batch asked for a link
+  takes the per-series route (as with `components=True`).  ValueError before any fit, the series and
+  the label named, for a value outside the link's domain on a row a model conditions on.
+  `components` and `prediction_errors` stay on the transformed scale; `placebo=` is refused.
   """
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
+  link = lib.resolve_outcome_link(outcome_link)
+  if link and placebo is not None and placebo is not False:
+    raise ValueError(lib._LINK_PLACEBO_REFUSAL)                  # pylint: disable=protected-access
   placebo = lib.resolve_placebo(placebo)
   pl_dim = None if placebo is None else lib.placebo_state_dim(model_options.local_linear_trend,
                                                               model_options.seasons)
@@ -2159,6 +2227,14 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   names = list(range(B)) if names is None else list(names)
   agg = None if aggregates is None else _check_aggregates(aggregates, names, shared_streams)
   hmc = inference_options.sampler == "hmc"
+  raw_values = values
+  if link:
+    # the models' copy: log y (log1p y) of the outcome column alone; `raw_values` stays what every
+    # data-scale frame reads.  Refusals first, the series named.
+    pre, _ = indices.parse_and_validate_date_data(
+        data=pd.DataFrame({"y": np.zeros(len(index))}, index=index), pre_period=pre_period, post_period=post_period)
+    values = raw_values.copy()
+    values[:, :, 0] = lib.link_column(raw_values[:, :, 0], index, pre, link, columns[0], names)
   # float64 and raw-scale batches go series by series; every other batch is standardised float32
   per_series = (cid._as_numpy_dtype(data_options.dtype) == np.float64   # pylint: disable=protected-access
                 or not data_options.standardize_data)
@@ -2166,15 +2242,16 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     prep = prepare_batch(values, index, pre_period, post_period)
     T = prep.y.shape[1]
     # the one-launch HMC path keeps no latent draws and has no component summary: asked for
-    # components, an HMC batch takes the per-series route, where `fit_causalimpact` has the draws
+    # components, an HMC batch takes the per-series route, where `fit_causalimpact` has the draws;
+    # its session has no link either: asked for `outcome_link`, the same
     per_series = hmc and (inference_options.components or hmc_batch_route(
         float64=False, standardize_data=True, num_seasonal_blocks=len(model_options.seasons), T=T,
         P=0 if prep.design is None else prep.design.shape[2],
-        hmc_init=inference_options.hmc_init) == "per_series")
+        hmc_init=inference_options.hmc_init, outcome_link=bool(link)) == "per_series")
   if per_series:
     shared = None
     if agg is not None or effect_windows is not None:   # (the shared calendar: pooled outcome, window flags)
-      shared = prepare_batch(values, index, pre_period, post_period, data_options.standardize_data)
+      shared = prepare_batch(raw_values, index, pre_period, post_period, data_options.standardize_data)
     if agg is not None:
       agg = (*agg, shared)
     plan = None if effect_windows is None else batch_windows(effect_windows, shared)
@@ -2184,11 +2261,14 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
       pl_h, pl_o = lib.placebo_plan(placebo, shared.num_pre, n_post, pl_dim)
       pool_plan = batch_placebo_pool_plan(agg[1], pl_o if len(pl_o) else [-1], pl_h, n_post,
                                           shared.index[shared.model_rows])
-    return _fit_per_series((pd.DataFrame(values[b], index=index, columns=columns) for b in range(B)),
+    return _fit_per_series((pd.DataFrame(raw_values[b], index=index, columns=columns) for b in range(B)),
                            [(pre_period, post_period)] * B, names, columns[0], alpha, seed,
                            data_options, model_options, inference_options, shared_streams, agg,
                            windows=plan, series_windows=None if plan is None else [effect_windows] * B,
-                           placebo=placebo, joint_bands=joint_bands, placebo_pool=pool_plan)
+                           placebo=placebo, joint_bands=joint_bands, placebo_pool=pool_plan,
+                           outcome_link=outcome_link)
+  if link:
+    prep = _under_link(prep, prepare_batch(raw_values, index, pre_period, post_period), link)
   plan = None if effect_windows is None else batch_windows(effect_windows, prep)
   pl_plan = pl_post = None
   if placebo is not None:
@@ -2236,9 +2316,14 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     res.set_joint(record.windows, fit.path_ranks, None if plan is None else plan.names)
   if chain is not None:
     # the posterior means on the data scale with the statistics every series' own frame uses
-    mu, sd = scaler_stats(prep.values[:, prep.model_rows[:prep.num_pre], 0])
+    # (`outcome_link`: the means of the linked draws are there already)
+    if link:
+      data_means = np.asarray(means, np.float64)
+    else:
+      mu, sd = scaler_stats(prep.values[:, prep.model_rows[:prep.num_pre], 0])
+      data_means = means.astype(np.float64) * sd[:, None] + mu[:, None]
     _take_aggregates(res, _aggregate_analyses(
-        agg[0], agg[1], chain.result(), means.astype(np.float64) * sd[:, None] + mu[:, None], prep,
+        agg[0], agg[1], chain.result(), data_means, prep,
         columns[0], alpha, fit.ranks, launches[0][0], plan, joint_bands))
     if pl_chain is not None:
       _take_aggregate_placebo(res, pool_plan, agg[0], pl_chain.means, pool_seen, alpha)
@@ -2249,8 +2334,7 @@ def _window_summary(res: CausalImpactBatchAnalysis, plan: WindowPlan, wsum) -> p
   """`window_summary` of a one-launch batch or panel from the assembled window totals: the
   observations and the data-scale posterior mean of `_build_summary`, every window's own steps."""
   p = res._prep                                                  # pylint: disable=protected-access
-  post_mean = (res._means.astype(np.float64) * p.outcome_sd[:, None]   # pylint: disable=protected-access
-               + p.outcome_mean[:, None])
+  post_mean = res._data_means()                                  # pylint: disable=protected-access
   classes = None
   if isinstance(p, PreparedPanel):       # (the groups `panel_window_stats` reduces together)
     groups: Dict[Any, List[int]] = {}
@@ -2268,7 +2352,8 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
                            names: Optional[Sequence[Any]] = None,
                            shared_streams: bool = False,
                            event_aggregates=None, effect_windows=None,
-                           placebo=None, joint_bands: bool = False) -> CausalImpactBatchAnalysis:
+                           placebo=None, joint_bands: bool = False,
+                           outcome_link=None) -> CausalImpactBatchAnalysis:
   """`fit_causalimpact` for a PANEL: B series with the same columns (outcome first, or
   `DataOptions.outcome_column`; the same covariates), each with its own index, its own length and
   its own (pre_period, post_period) -- staggered roll-outs, units that enter the data on different
@@ -2350,9 +2435,19 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   not reach a window.  With `event_aggregates` every pooled group gets `joint_bands`, `joint_summary`
   and `window_joint_summary` on its own `event_time` axis, and the result
   `aggregate_joint_summary` and `aggregate_window_joint_summary` as in `fit_causalimpact_batch`, with
-  blank rows where a group's axis does not reach a window."""
+  blank rows where a group's axis does not reach a window.
+
+  outcome_link: as in `fit_causalimpact_batch` -- every series modelled as log y (log1p y), every
+  table, frame and pooled `aggregates[name]` on the data scale from the linked draws, the link applied
+  by the summary and pool kernels of every ragged launch; panels fitted series by series in numpy.
+  ValueError before any fit, the series and the label named, for a value outside the link's domain on
+  a row its model conditions on.  `components` and `prediction_errors` stay on the transformed scale;
+  `placebo=` is refused."""
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
+  link = lib.resolve_outcome_link(outcome_link)
+  if link and placebo is not None and placebo is not False:
+    raise ValueError(lib._LINK_PLACEBO_REFUSAL)                  # pylint: disable=protected-access
   placebo = lib.resolve_placebo(placebo)
   pl_dim = None if placebo is None else lib.placebo_state_dim(model_options.local_linear_trend,
                                                               model_options.seasons)
@@ -2370,6 +2465,11 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
       raise ValueError(f"series {names[b]!r}: all series of a panel must share the columns")
   float64 = cid._as_numpy_dtype(data_options.dtype) == np.float64  # pylint: disable=protected-access
   num_blocks = len(model_options.seasons)
+  model_frames = None
+  if link:
+    # the models' copies (log y, log1p y of the outcome column alone); refusals first, the series named
+    model_frames = [lib.link_outcome(f[columns], periods[b][0], periods[b][1], columns[0], link, names[b])
+                    for b, f in enumerate(frames)]
   # (which panels go series by series does not depend on the lengths: the frames' bound them here)
   if panel_route(float64=float64, standardize_data=data_options.standardize_data,
                  sampler=inference_options.sampler, num_seasonal_blocks=num_blocks,
@@ -2391,8 +2491,10 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
                            windows=wplan, series_windows=own, placebo=placebo, placebo_lenient=True,
                            joint_bands=joint_bands,
                            placebo_pool=None if plan is None or placebo is None else
-                           event_placebo_pool_plan(placebo, plan, pl_dim))
-  prep = prepare_panel([f[columns] for f in frames], periods, names=names)
+                           event_placebo_pool_plan(placebo, plan, pl_dim), outcome_link=outcome_link)
+  prep = prepare_panel(model_frames or [f[columns] for f in frames], periods, names=names)
+  if link:
+    prep = _under_link(prep, prepare_panel([f[columns] for f in frames], periods, names=names), link)
   pl_plan = pl_post = None
   if placebo is not None:
     pl_post = np.array([np.count_nonzero(prep.flags[b, :Tb] & 2) for b, Tb in enumerate(prep.lengths)])
@@ -2432,6 +2534,9 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
     # the posterior means on the data scale with the statistics every series' own frame uses
     data_means = []
     for b, (Tb, nb) in enumerate(zip(prep.lengths, prep.num_pre)):
+      if link:                 # (the means of the linked draws are on the data scale already)
+        data_means.append(np.asarray(means[b, :Tb], np.float64))
+        continue
       mu, sd = scaler_stats(prep.raw[b][prep.model_rows[b][:nb], 0][None])
       data_means.append(means[b, :Tb].astype(np.float64) * sd[0] + mu[0])
     _take_aggregates(res, _event_aggregate_analyses(

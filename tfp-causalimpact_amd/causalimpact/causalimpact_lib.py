@@ -15,6 +15,7 @@ Host-side post-processing (reference :635-1093) is re-implemented on numpy array
 against the reference's own output by tests/test_golden_postprocessing.py.
 """
 import collections.abc
+import copy
 import dataclasses
 import math
 from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
@@ -242,8 +243,25 @@ def fit_causalimpact(data: pd.DataFrame,
                      effect_windows=None,
                      placebo=None,
                      joint_bands=False,
+                     outcome_link=None,
                      **kwargs) -> CausalImpactAnalysis:
   """Fits the CausalImpact model and summarises the effect (reference :223-339).
+
+  outcome_link (extension): None (the default: nothing runs, no result differs), "log" or "log1p",
+  for outcomes that move multiplicatively (revenue, conversions, counts).  The outcome column alone
+  is transformed (log y, log1p y) before standardisation -- the model, the kernels and the draws are
+  exactly those of fitting the pre-transformed frame, and `posterior_samples` stay on the model's
+  scale -- but `series`, `summary`, `window_summary` and the joint bands are on the DATA scale, from
+  the linked draws: exp (expm1) is applied to every predictive draw before any mean, sum or
+  quantile, because E[exp z] != exp E[z].  The posterior mean is the mean of the linked draws.
+  `observed` is the input column itself.  On the GPU that holds the draws wherever the summaries run
+  there (`_native.Session.set_link`), the same definitions in numpy (`_native.link_values_host`) on
+  the routes that pool the draws on the host.  Every row the model conditions on needs y > 0 (log)
+  or y > -1 (log1p): ValueError before any fit, the first offending label named; a post-period value
+  outside the domain (sales driven to 0) is a missing value to the model's copy alone.
+  `components=True` and `prediction_errors=True` describe the model, which is Gaussian on the
+  TRANSFORMED scale: they are reported there.  `placebo=` with a link is refused (ValueError): a sum
+  of lognormals has no closed-form variance.
 
   effect_windows (extension): {name: (start, end)}, sub-windows of the post-period given as labels
   on the index, both ends inclusive, parsed and aligned exactly as `post_period` is.  The result then
@@ -299,6 +317,12 @@ def fit_causalimpact(data: pd.DataFrame,
     raise NotImplementedError(
         "experimental_model takes a tfp.sts.StructuralTimeSeries; this build has no TFP. Use "
         "ModelOptions(local_linear_trend=..., seasons=...) instead.")
+  link = resolve_outcome_link(outcome_link)
+  if link and placebo is not None and placebo is not False:
+    raise ValueError(_LINK_PLACEBO_REFUSAL)
+  raw_data = None
+  if link:
+    raw_data, data = data, link_outcome(data, pre_period, post_period, data_options.outcome_column, link)
 
   ci_data = cid.CausalImpactData(
       data=data, pre_period=pre_period, post_period=post_period,
@@ -307,6 +331,12 @@ def fit_causalimpact(data: pd.DataFrame,
   if not 0 < alpha < 1:
     raise ValueError("`alpha` must be between 0 and 1.")
   base = _device_summary_request(ci_data, alpha)
+  # under a link: the effect is summarised on the data scale, against the raw outcome; `ci_view` is
+  # `ci_data` as the data-scale frames see it, `model_observed` what the model's own checks compare
+  ci_view, model_observed = ci_data, base["observed"]
+  if link:
+    ci_view = _data_scale_view(ci_data, raw_data)
+    base = dict(base, observed=_device_summary_request(ci_view, alpha)["observed"])
   windows = None
   if effect_windows is not None:
     windows = resolve_windows(effect_windows, ci_data.data.index,
@@ -338,7 +368,7 @@ def fit_causalimpact(data: pd.DataFrame,
       windows=Windows([w.first for w in windows], [w.count for w in windows]) if windows else None,
       placebo=placebo_part, on_device=inference_options.summarize_on_device,
       keep_trajectories=trajectory_sink is not None,
-      paths=path_windows, path_ranks=_path_ranks(num_draws, alpha) if joint_bands else ())
+      paths=path_windows, path_ranks=_path_ranks(num_draws, alpha) if joint_bands else (), link=link)
   samples, posterior_means, posterior_trajectories, record = _run_sampler(
       ci_data=ci_data, prior_level_sd=model_options.prior_level_sd, seed=seed,
       num_results=inference_options.num_results,
@@ -348,19 +378,29 @@ def fit_causalimpact(data: pd.DataFrame,
       sampler=inference_options.sampler, request=request,
       hmc_init=inference_options.hmc_init, hmc_prior=inference_options.hmc_prior,
       kernel_flags=inference_options.kernel_flags, placebo_sink=placebo_sink)
+  if link:
+    # the predictive arrays on the data scale: the linked draws (where the host has them) and the mean
+    # of the linked draws, never the link of the mean
+    if posterior_trajectories is not None:
+      posterior_trajectories = _native.link_values_host(
+          np.asarray(posterior_trajectories, np.float64) * np.float64(base["scale"]) + np.float64(base["shift"]),
+          link)
+    posterior_means = (record.effect["value_mean"] if record.effect is not None
+                       else posterior_trajectories.mean(axis=0))
   if trajectory_sink is not None:
-    trajectory_sink(posterior_means, posterior_trajectories, base["scale"], base["shift"])
+    trajectory_sink(posterior_means, posterior_trajectories, *((1.0, 0.0) if link else
+                                                               (base["scale"], base["shift"])))
   # (draws pooled on the host -- several devices, float64, HMC -- were summarised inside
   #  _run_sampler, in the sampler's internal units)
   if record.effect is not None:
     series, summary, window_summary = _compute_impact_device(
-        posterior_means, record.effect, base["observed"], base["flags"], ranks, ci_data, alpha,
+        posterior_means, record.effect, base["observed"], base["flags"], ranks, ci_view, alpha,
         windows=windows or (),
         window_totals=None if record.windows is None else record.windows.get("per_draw"))
   else:
     series, summary, window_summary = _compute_impact(
         posterior_means=posterior_means, posterior_trajectories=posterior_trajectories,
-        ci_data=ci_data, alpha=alpha, windows=windows or ())
+        ci_data=ci_view, alpha=alpha, windows=windows or ())
   has_weights = samples["weights"].shape[-1] > 0
   has_seasons = samples["seasonal_drift_scales"].shape[-1] > 0
   posterior = CausalImpactPosteriorSamples(
@@ -394,7 +434,7 @@ def fit_causalimpact(data: pd.DataFrame,
   prediction_errors = fit_quality = None
   if record.predictions is not None:
     prediction_errors, fit_quality = _prediction_frames(
-        record.predictions, ranks, alpha, base["observed"], ~_model_mask(ci_data), state_dim,
+        record.predictions, ranks, alpha, model_observed, ~_model_mask(ci_data), state_dim,
         posterior_processing.model_index(ci_data), ci_data.data.index)
   placebo_frame = placebo_quality = None
   if placebo is not None:
@@ -409,6 +449,70 @@ def fit_causalimpact(data: pd.DataFrame,
   return CausalImpactAnalysis(series, summary, posterior, samples.get("diagnostics"), components,
                               coefficients, prediction_errors, fit_quality, window_summary,
                               placebo_frame, placebo_quality, *joint)
+
+
+OUTCOME_LINKS = {None: _native.LINK_IDENTITY, "log": _native.LINK_LOG, "log1p": _native.LINK_LOG1P}
+_LINK_PLACEBO_REFUSAL = ("`placebo=` is not available with `outcome_link`: the placebo forecasts are "
+                         "Gaussian on the transformed scale, and a sum of lognormals has no closed-form "
+                         "variance")
+
+
+def resolve_outcome_link(outcome_link) -> int:
+  """`outcome_link` (None, "log", "log1p") as the `_native.LINK_*` it stands for; ValueError else."""
+  try:
+    return OUTCOME_LINKS[outcome_link]
+  except (KeyError, TypeError):
+    raise ValueError(f"`outcome_link` must be None, 'log' or 'log1p', got {outcome_link!r}") from None
+
+
+def link_outcome(data, pre_period, post_period, outcome_column, link: int, series=None) -> pd.DataFrame:
+  """The model's copy of `data` under an outcome link: the outcome column alone as log y (LINK_LOG)
+  or log1p y (LINK_LOG1P), the covariates untouched.  The rows the model conditions on -- those of the
+  pre-period -- must lie in the domain (y > 0, y > -1; a missing value stays missing): ValueError
+  naming the first offending label, and `series` where given.  A row the model never reads with a
+  value outside the domain becomes NaN, in this copy only.  No device is touched."""
+  frame = pd.DataFrame(data).copy()
+  column = frame.columns[0] if outcome_column is None else outcome_column
+  if column not in frame.columns:
+    raise KeyError(f"Specified `outcome_column` ({column}) not found in data")
+  pre, _ = indices.parse_and_validate_date_data(data=frame, pre_period=pre_period, post_period=post_period)
+  frame[column] = link_column(frame[column].to_numpy(dtype=np.float64), frame.index, pre, link, column, series)
+  return frame
+
+
+def link_column(y: np.ndarray, index: pd.Index, pre_period, link: int, column="y", series=None) -> np.ndarray:
+  """`link_outcome` on the outcome values alone, `pre_period` parsed already: y [T_all], or [B, T_all]
+  for series that share `index`, `series` then their names."""
+  low = 0.0 if link == _native.LINK_LOG else -1.0
+  outside = ~np.isnan(y) & ~(y > low)
+  conditioned = np.asarray((index >= pre_period[0]) & (index <= pre_period[1]))
+  bad = np.argwhere(outside & conditioned)             # (row-major: the first series, its first label)
+  if bad.size:
+    at = tuple(bad[0])
+    name = "log" if link == _native.LINK_LOG else "log1p"
+    who = series if y.ndim == 1 else series[at[0]]
+    where = "" if who is None else f" of series {who!r}"
+    raise ValueError(f"outcome_link={name!r} needs {column!r} > {low:g} on every row the model conditions on: "
+                     f"row {index[at[-1]]}{where} holds {float(y[at])!r}")
+  y = np.where(outside, np.nan, y)
+  with np.errstate(invalid="ignore", divide="ignore"):
+    return np.log(y) if link == _native.LINK_LOG else np.log1p(y)
+
+
+def _data_scale_view(ci_data, raw_data):
+  """`ci_data` (of the model's copy under an outcome link) as the frames of the effect read it: the
+  raw outcome column in `data`, `pre_data` and `after_pre_data`, and nothing left to unstandardise --
+  the linked values are on the data scale already.  The model's own arrays stay where they are."""
+  view = copy.copy(ci_data)
+  raw = pd.DataFrame(raw_data)
+  data = ci_data.data.copy()
+  data[ci_data.outcome_column] = raw[ci_data.outcome_column].reindex(data.index)
+  idx = data.index
+  view.data = data
+  view.pre_data = data.loc[(idx >= ci_data.pre_period[0]) & (idx <= ci_data.pre_period[1])]
+  view.after_pre_data = data.loc[idx > ci_data.pre_period[1]]
+  view.standardize_data = False
+  return view
 
 
 @dataclasses.dataclass(frozen=True)
@@ -1312,12 +1416,17 @@ class SummaryRequest:
   # `_compute_impact`; keep_trajectories: the predictive draws are wanted on the host as well
   on_device: bool = True
   keep_trajectories: bool = False
+  # `outcome_link`: the `_native.LINK_*` under which the effect, its windows and its paths form their
+  # values (`Session.set_link`); the record's effect then has value_mean
+  link: int = 0
 
 
 @dataclasses.dataclass(frozen=True)
 class SummaryRecord:
   """What a fit got: per kind {name: [B, ...]} (`of_series`: one series' own), or None for a kind that
   was not asked for or that this route leaves to the host."""
+  # (under `SummaryRequest.link` the effect has value_mean [B, T] too: the mean over the draws of the
+  #  linked values, which the sampler's posterior_means no longer give)
   effect: Optional[Dict[str, np.ndarray]] = None
   components: Optional[Dict[str, np.ndarray]] = None
   predictions: Optional[Dict[str, np.ndarray]] = None
@@ -1343,7 +1452,7 @@ class SummaryKind(NamedTuple):
 
 
 SUMMARY_KINDS = {
-    "effect": SummaryKind(("per_draw", "per_draw_order"), np.nan),            # [B, 2, draws | R]
+    "effect": SummaryKind(("per_draw", "per_draw_order"), np.nan),            # [B, 2, draws | R]; value_mean [B, T]
     "components": SummaryKind(("inclusion_prob", "weight_mean", "weight_order"), np.nan),   # [B, ..., P]
     "predictions": SummaryKind(("loglik",), np.nan),                          # [B, draws]
     # [B, W, 2, draws | R]; `joint_bands`: path_center, path_spread [B, 1 + W, 2, T] over time, the rest whole
@@ -1495,7 +1604,14 @@ def take_summaries(sess, request: SummaryRequest,
   entries and `device_predictions_supported` takes the model; else in numpy from the parameter draws,
   fetched once for both, over `series_inputs` (one per series of the session; read for these two
   kinds only).  Components a session lacks stay None: the caller's business.  The scales and shifts
-  map the SESSION's units to the data scale (`_request_in_internal_units`)."""
+  map the SESSION's units to the data scale (`_request_in_internal_units`).  With `request.link` the
+  session's link is set first (`set_link`: the effect, its windows and paths then form linked values,
+  and so does a pool step that follows while the session is open) and the effect gets `value_mean`
+  from a last call."""
+  if request.link:
+    # (session state: `summarize`, `summarize_windows`, `summarize_paths` and `value_mean` honour it;
+    #  the components, prediction errors and placebo forecasts describe the model and do not)
+    sess.set_link(request.link)
   effect = sess.summarize(request.scale, request.shift, request.observed, request.flags, request.ranks)
   if effect["value_order"].ndim == 2:      # (`Session.summarize` drops the series axis of one series)
     effect = {k: v[None] for k, v in effect.items()}
@@ -1520,6 +1636,8 @@ def take_summaries(sess, request: SummaryRequest,
     part = _per_series(request.placebo, len(series_inputs))
     placebo = _with_placebo_seen(series_inputs, part, _host_placebo_summaries(series_inputs, draws, part)
                                  if on_host else _device_placebo_summaries(sess, part))
+  if request.link:
+    effect = dict(effect, value_mean=sess.value_mean(request.scale, request.shift))
   return SummaryRecord(effect=effect, components=components, predictions=predictions, windows=windows,
                        placebo=placebo)
 
@@ -1635,22 +1753,27 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
     # on the single-device path.  Summarising the rescaled draws would round the offset back in
     # (8e-6 steps at y ~ 100).
     effect = windows = predictions = placebo = None
+    tr = out["posterior_trajectories"]
+    tr = tr.reshape((1, tr.shape[0] * tr.shape[1]) + tr.shape[2:])
+    own = Affine(internal.scale, internal.shift)
+    if internal.link and (internal.on_device or internal.paths is not None):
+      # under a link: the draws on the data scale, in float64, before anything is summed or uploaded
+      # (`_native.link_values_host`); what follows reads them as they are
+      tr = _native.link_values_host(
+          tr.astype(np.float64) * np.float64(internal.scale) + np.float64(internal.shift), internal.link)
+      own = Affine(1.0, 0.0)
     if internal.on_device:
-      tr = out["posterior_trajectories"]
-      tr = tr.reshape((1, tr.shape[0] * tr.shape[1]) + tr.shape[2:])
       effect = {k: v[None] for k, v in _native.summarize_draws(
-          tr[0], internal.scale, internal.shift, internal.observed, internal.flags, internal.ranks,
-          device=devs[0]).items()}
+          tr[0], *own, internal.observed, internal.flags, internal.ranks, device=devs[0]).items()}
+      if internal.link:
+        effect["value_mean"] = tr.mean(axis=1)
       if internal.windows is not None:
         # ... and the window totals from exactly these trajectories and this (scale, shift)
-        windows = dict(per_draw=_native.window_totals_host(
-            tr, internal.scale, internal.shift, internal.observed, *internal.windows))
+        windows = dict(per_draw=_native.window_totals_host(tr, *own, internal.observed, *internal.windows))
     if internal.paths is not None:
       # ... and the path excursions, also where the effect is left to `_compute_impact`
-      tr = out["posterior_trajectories"]
       windows = dict(windows or {}, **_paths_record(_native.path_excursions_host(
-          tr.reshape((1, tr.shape[0] * tr.shape[1]) + tr.shape[2:]), internal.scale, internal.shift,
-          internal.observed, *internal.paths, ranks=internal.path_ranks)))
+          tr, *own, internal.observed, *internal.paths, ranks=internal.path_ranks)))
     # the same definitions in numpy, from the parameter draws in the sampler's units
     draws = {k: out[k][None] for k in _PARAMETER_DRAWS}
     if internal.predictions is not None:

@@ -40,6 +40,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ci_link.h"
+
 namespace ci {
 
 constexpr int PATHS_TILE = 64;
@@ -61,7 +63,8 @@ struct PathsChunk {
 
 // grid (ceil(N / 64), pairs), one wavefront per workgroup.  X of a pair: [2][count][N].
 // ALIGNED as in window_totals_kernel (T % 4 == 0 and a 16-byte aligned base).
-template <bool ALIGNED>
+// LINK (ci_link.h): v is link(that); the identity is the code without it.
+template <bool ALIGNED, int LINK = LINK_IDENTITY>
 __global__ __launch_bounds__(64) void path_values_kernel(PathsChunk c, const float* __restrict__ traj_all,
                                                          double* __restrict__ X_all) {
   __shared__ float tile[PATHS_TILE][PATHS_TILE + 1];      // 65 columns: lane l reads bank (l + t) % 32
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(64) void path_values_kernel(PathsChunk c, const flo
     __syncthreads();
     if (n < N) {
       for (int t = lo; t < hi; ++t) {
-        const double v = __dadd_rn(__dmul_rn((double)tile[lane][t - t0], scale), shift);
+        const double v = link_value<LINK>(__dadd_rn(__dmul_rn((double)tile[lane][t - t0], scale), shift));
         const double point = -__dsub_rn(v, obs_tile[t - t0]);
         point_sum = __dadd_rn(point_sum, (point != point) ? 0.0 : point);
         X0[(size_t)(t - first) * N + n] = v;

@@ -12,7 +12,19 @@ namespace ci {
 // (0 <= first, 0 <= count, first + count <= T), and 1 <= pairs <= 65535.
 // draws64 != NULL (ci_summarize_draw_paths_f64): the first pass reads these float64 draws
 // [groups of the chunk, N, T] instead, row 0 of them group g0's, and traj is not looked at.
-static hipError_t paths_launch_any(hipStream_t stream, int N, int T, int W, int p0, int pairs, int max_count,
+// link: one of ci::LINK_* (checked by the caller), for the float32 trajectories of a session only.
+template <bool ALIGNED>
+static void path_values_launch(hipStream_t stream, int link, dim3 grid, const PathsChunk& c, const float* traj,
+                               double* X) {
+  if (link == LINK_LOG)
+    hipLaunchKernelGGL((path_values_kernel<ALIGNED, LINK_LOG>), grid, dim3(PATHS_TILE), 0, stream, c, traj, X);
+  else if (link == LINK_LOG1P)
+    hipLaunchKernelGGL((path_values_kernel<ALIGNED, LINK_LOG1P>), grid, dim3(PATHS_TILE), 0, stream, c, traj, X);
+  else
+    hipLaunchKernelGGL((path_values_kernel<ALIGNED, LINK_IDENTITY>), grid, dim3(PATHS_TILE), 0, stream, c, traj, X);
+}
+
+static hipError_t paths_launch_any(hipStream_t stream, int link, int N, int T, int W, int p0, int pairs, int max_count,
                                    const float* traj, const double* draws64, int g0, const double* obs,
                                    const double* scales, const double* shifts, const int* first,
                                    const int* count, const long long* steps_before, double* X, double* mom,
@@ -29,9 +41,9 @@ static hipError_t paths_launch_any(hipStream_t stream, int N, int T, int W, int 
     else if (draws64)
       hipLaunchKernelGGL(path_values_f64_kernel<false>, grid, dim3(PATHS_TILE), 0, stream, c, g0, draws64, X);
     else if (aligned)
-      hipLaunchKernelGGL(path_values_kernel<true>, grid, dim3(PATHS_TILE), 0, stream, c, traj, X);
+      path_values_launch<true>(stream, link, grid, c, traj, X);
     else
-      hipLaunchKernelGGL(path_values_kernel<false>, grid, dim3(PATHS_TILE), 0, stream, c, traj, X);
+      path_values_launch<false>(stream, link, grid, c, traj, X);
     hipLaunchKernelGGL(path_moments_kernel, dim3(2 * max_count, pairs), dim3(PATHS_NT), 0, stream, c, X, mom);
   }
   hipLaunchKernelGGL(path_observed_kernel, dim3((2 * pairs + 63) / 64), dim3(64), 0, stream, c, pairs, mom,
@@ -41,11 +53,11 @@ static hipError_t paths_launch_any(hipStream_t stream, int N, int T, int W, int 
   return hipGetLastError();
 }
 
-hipError_t paths_launch(hipStream_t stream, int N, int T, int W, int p0, int pairs, int max_count,
+hipError_t paths_launch(hipStream_t stream, int link, int N, int T, int W, int p0, int pairs, int max_count,
                         const float* traj, const double* obs, const double* scales, const double* shifts,
                         const int* first, const int* count, const long long* steps_before, double* X,
                         double* mom, double* observed_excursion, int* at, double* excursion, int* exceed) {
-  return paths_launch_any(stream, N, T, W, p0, pairs, max_count, traj, nullptr, 0, obs, scales, shifts, first,
+  return paths_launch_any(stream, link, N, T, W, p0, pairs, max_count, traj, nullptr, 0, obs, scales, shifts, first,
                           count, steps_before, X, mom, observed_excursion, at, excursion, exceed);
 }
 
@@ -56,7 +68,7 @@ hipError_t paths_launch_f64(hipStream_t stream, int N, int T, int W, int p0, int
                             const double* shifts, const int* first, const int* count,
                             const long long* steps_before, double* X, double* mom,
                             double* observed_excursion, int* at, double* excursion, int* exceed) {
-  return paths_launch_any(stream, N, T, W, p0, pairs, max_count, nullptr, draws, g0, obs, scales, shifts, first,
+  return paths_launch_any(stream, LINK_IDENTITY, N, T, W, p0, pairs, max_count, nullptr, draws, g0, obs, scales, shifts, first,
                           count, steps_before, X, mom, observed_excursion, at, excursion, exceed);
 }
 

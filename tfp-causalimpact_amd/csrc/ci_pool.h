@@ -13,7 +13,8 @@
 //
 // Arithmetic is float64 and ordered like the numpy loop it stands for:
 //   acc = init (or 0.0);  for the members b of the group, ascending:
-//     v = traj[b] * scale[b] + shift[b]      the value ci_session_summarize forms (two roundings)
+//     v = traj[b] * scale[b] + shift[b]      the value ci_session_summarize forms (two roundings;
+//                                            under a LINK, ci_link.h, the link of that)
 //     acc = acc + w * v                      (two roundings)
 // so the result does not depend on the launch geometry, and a batch cut into several sessions
 // continues one running sum through `init`, bit for bit.  In event time traj[b] is
@@ -21,6 +22,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "ci_link.h"
 
 namespace ci {
 
@@ -53,7 +56,7 @@ __device__ __forceinline__ void pool_pick(const float4 a, const float4 b, unsign
 // in its row and the rows of a session are T floats apart, so unless ALIGNED (every start and T a
 // multiple of 4 on an aligned base) the offset differs from member to member and from draw to draw:
 // phase is base_m + r, per thread.
-template <bool ALIGNED, int CNT>
+template <bool ALIGNED, int CNT, int LINK>
 __device__ __forceinline__ void pool_chunk(const float* __restrict__ traj,
                                            const PoolEntry* __restrict__ en, long long r,
                                            unsigned phase, unsigned base_m, double acc[4]) {
@@ -80,7 +83,7 @@ __device__ __forceinline__ void pool_chunk(const float* __restrict__ traj,
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const double x = __dadd_rn(__dmul_rn((double)v[j], m.scale), m.shift);
+      const double x = link_value<LINK>(__dadd_rn(__dmul_rn((double)v[j], m.scale), m.shift));
       acc[j] = __dadd_rn(acc[j], __dmul_rn(m.w, x));
     }
   }
@@ -103,7 +106,7 @@ __device__ __forceinline__ void pool_init(const double* out, bool whole, int lef
 // The members k0 .. k1 - 1 of a group added to a thread's accumulators, in order.  vec: the thread's
 // four elements of every member may be read by vector loads (the kernels say when); otherwise its
 // first `left` elements are read one by one.
-template <bool ALIGNED>
+template <bool ALIGNED, int LINK>
 __device__ __forceinline__ void pool_members(const float* __restrict__ traj,
                                              const PoolEntry* __restrict__ entries, int k0, int k1,
                                              long long r, unsigned phase, unsigned base_m, bool vec,
@@ -112,10 +115,10 @@ __device__ __forceinline__ void pool_members(const float* __restrict__ traj,
     // whole chunks of POOL_AHEAD members, then the rest in chunks of 4, 2 and 1: every load is of a
     // member of the group, and the loads of a chunk are issued together, without a branch between
     int k = k0;
-    for (; k + POOL_AHEAD <= k1; k += POOL_AHEAD) pool_chunk<ALIGNED, POOL_AHEAD>(traj, entries + k, r, phase, base_m, acc);
-    if (k + 4 <= k1) { pool_chunk<ALIGNED, 4>(traj, entries + k, r, phase, base_m, acc); k += 4; }
-    if (k + 2 <= k1) { pool_chunk<ALIGNED, 2>(traj, entries + k, r, phase, base_m, acc); k += 2; }
-    if (k < k1) pool_chunk<ALIGNED, 1>(traj, entries + k, r, phase, base_m, acc);
+    for (; k + POOL_AHEAD <= k1; k += POOL_AHEAD) pool_chunk<ALIGNED, POOL_AHEAD, LINK>(traj, entries + k, r, phase, base_m, acc);
+    if (k + 4 <= k1) { pool_chunk<ALIGNED, 4, LINK>(traj, entries + k, r, phase, base_m, acc); k += 4; }
+    if (k + 2 <= k1) { pool_chunk<ALIGNED, 2, LINK>(traj, entries + k, r, phase, base_m, acc); k += 2; }
+    if (k < k1) pool_chunk<ALIGNED, 1, LINK>(traj, entries + k, r, phase, base_m, acc);
   } else {
     for (int k = k0; k < k1; ++k) {
       const PoolEntry en = entries[k];
@@ -123,7 +126,7 @@ __device__ __forceinline__ void pool_members(const float* __restrict__ traj,
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (j < left) {
-          const double x = __dadd_rn(__dmul_rn((double)p[j], en.scale), en.shift);
+          const double x = link_value<LINK>(__dadd_rn(__dmul_rn((double)p[j], en.scale), en.shift));
           acc[j] = __dadd_rn(acc[j], __dmul_rn(en.w, x));
         }
       }
@@ -150,7 +153,7 @@ __device__ __forceinline__ void pool_store(double* out, bool out16, int room, co
 // initial accumulator when has_init, and the result afterwards.
 // ALIGNED: every member block starts 16-byte aligned (N*T a multiple of 4 on an aligned base):
 // one float4 per member and thread.
-template <bool ALIGNED>
+template <bool ALIGNED, int LINK = LINK_IDENTITY>
 __global__ __launch_bounds__(POOL_NT) void pool_kernel(long long NT,
                                                        const float* __restrict__ traj,
                                                        const int* __restrict__ offsets,
@@ -172,7 +175,7 @@ __global__ __launch_bounds__(POOL_NT) void pool_kernel(long long NT,
   // the thread's own, which stay inside the block while e + 8 <= NT.  The last elements of the slice
   // (and the first four on a misaligned base) go element by element.
   const bool vec = ALIGNED ? left == 4 : (e + 8 <= NT && (e >= 4 || base_m == 0u));
-  pool_members<ALIGNED>(traj, entries, k0, k1, e, base_m, base_m, vec, left, acc);
+  pool_members<ALIGNED, LINK>(traj, entries, k0, k1, e, base_m, base_m, vec, left, acc);
   pool_store(out, out16, left, acc);
 }
 
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(POOL_NT) void pool_kernel(long long NT,
 // traj: the session's [B, N, T] trajectories, `total` = B*N*T floats; entries offsets[g] ..
 // offsets[g + 1] are the members of group g; widths[g] <= S; pooled [groups, N, S] float64 holds the
 // initial accumulator when has_init, and the result afterwards.
-template <bool ALIGNED>
+template <bool ALIGNED, int LINK = LINK_IDENTITY>
 __global__ __launch_bounds__(POOL_NT) void pool_event_kernel(int N, int T, long long total,
                                                              const float* __restrict__ traj,
                                                              const int* __restrict__ offsets,
@@ -214,7 +217,7 @@ __global__ __launch_bounds__(POOL_NT) void pool_event_kernel(int N, int T, long 
   bool vec = left == 4 && k0 < k1;
   if (!ALIGNED && vec)
     vec = (entries[k0].start + r >= 4 || base_m == 0u) && entries[k1 - 1].start + r + 8 <= total;
-  pool_members<ALIGNED>(traj, entries, k0, k1, r, base_m + (unsigned)r, base_m, vec, left, acc);
+  pool_members<ALIGNED, LINK>(traj, entries, k0, k1, r, base_m + (unsigned)r, base_m, vec, left, acc);
   pool_store(out, out16, room, acc);
 }
 

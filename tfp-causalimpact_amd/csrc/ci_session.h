@@ -65,6 +65,7 @@ struct ci_session {
   DevBuf<float> cpart, cw;
   DevBuf<double> cv;
   SummScratch summ;          // on-device summarisation (ci_summary.h)
+  int link = 0;              // ci_session_set_link: the outcome link of the summaries (ci_link.h)
   // ci_session_summarize_predictions: the B parameter blocks the session was created with, and on
   // the device (first call) [B, 4] initial moments followed by [B] ones (ci_predict.h)
   std::vector<ci_series_params> params;

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ci_link.h"
+
 namespace ci {
 
 constexpr int SUMM_MAX_RANKS = 8;
@@ -20,7 +22,8 @@ constexpr int SUMM_MAX_RANKS = 8;
 // standardize.py:60-64 `values * stddev + mean` (two roundings, no FMA).
 // grid (ceil(T/64), ceil(N/64), B), block (64, 4); series b uses (scale[b], shift[b]).
 // TIn: float (the sampler's float32 container) or double (float64 fits pooled on the host, round 5).
-template <class TIn>
+// LINK (ci_link.h): the value is link(that); the identity is the code without it.
+template <class TIn, int LINK = LINK_IDENTITY>
 __global__ __launch_bounds__(256) void summ_transpose_kernel(int N, int T,
                                                              const TIn* __restrict__ traj_all,
                                                              const double* __restrict__ scales,
@@ -36,7 +39,7 @@ __global__ __launch_bounds__(256) void summ_transpose_kernel(int N, int T,
   for (int i = 0; i < 16; ++i) {
     const int n = n0 + ty + 4 * i, t = t0 + tx;
     if (n < N && t < T)
-      tile[ty + 4 * i][tx] = __dadd_rn(__dmul_rn((double)traj[(size_t)n * T + t], scale), shift);
+      tile[ty + 4 * i][tx] = link_value<LINK>(__dadd_rn(__dmul_rn((double)traj[(size_t)n * T + t], scale), shift));
   }
   __syncthreads();
 #pragma unroll

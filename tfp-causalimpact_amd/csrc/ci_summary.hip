@@ -4,6 +4,7 @@
 // ci_placebo.h),
 // ci_session_summarize_windows, ci_ll_session_summarize_windows
 // (kernel: ci_windows.h), ci_session_summarize_paths, ci_ll_session_summarize_paths (kernels: ci_paths.h),
+// ci_session_set_link and ci_session_value_mean (the outcome link: ci_link.h),
 // ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] and
 // ci_summarize_draw_paths_f64 on draws the caller hands in; ci_session_pool_trajectories, ci_ll_session_pool_trajectories and
 // ci_session_pool_event_trajectories (kernels: ci_pool.h) on the trajectories a session holds.
@@ -65,11 +66,28 @@ static int summ_scratch_alloc(SummScratch& w, int B, int T, int N) {
   return 0;
 }
 
+// The transpose of one link (ci_link.h) of B series' [B, N, T] trajectories into value [B, T, N].
+template <class TIn>
+static void launch_transpose(hipStream_t stream, int link, int B, int T, int N, const TIn* traj,
+                             const double* d_scale, const double* d_shift, double* value) {
+  const dim3 grid((T + 63) / 64, (N + 63) / 64, B), block(64, 4);
+  if (link == ci::LINK_LOG)
+    hipLaunchKernelGGL((ci::summ_transpose_kernel<TIn, ci::LINK_LOG>), grid, block, 0, stream, N, T, traj,
+                       d_scale, d_shift, value);
+  else if (link == ci::LINK_LOG1P)
+    hipLaunchKernelGGL((ci::summ_transpose_kernel<TIn, ci::LINK_LOG1P>), grid, block, 0, stream, N, T, traj,
+                       d_scale, d_shift, value);
+  else
+    hipLaunchKernelGGL((ci::summ_transpose_kernel<TIn, ci::LINK_IDENTITY>), grid, block, 0, stream, N, T, traj,
+                       d_scale, d_shift, value);
+}
+
 // The summary of B series' [B, N, T] trajectories resident in HBM (ci_session_summarize,
 // ci_ll_session_hmc_summarize; ci_summarize_draws after its upload): transpose with value = trajectory * scale + shift, running sums,
-// order statistics; the scratch is allocated on first use and kept.
+// order statistics; the scratch is allocated on first use and kept.  Nothing in the scratch outlives
+// a call, so a change of the link between two calls finds nothing stale.
 template <class TIn>
-static int summarize_resident(hipStream_t stream, SummScratch& w, int B, int T, int N, const TIn* traj,
+static int summarize_resident(hipStream_t stream, SummScratch& w, int link, int B, int T, int N, const TIn* traj,
                               const double* scale, const double* shift, const double* observed,
                               const uint8_t* flags, int32_t num_ranks, const int32_t* ranks,
                               double* value_order, double* cum_order, double* per_draw,
@@ -83,8 +101,7 @@ static int summarize_resident(hipStream_t stream, SummScratch& w, int B, int T, 
   HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(w.flags.p, flags, (size_t)B * T, hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, num_ranks * sizeof(int), hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(ci::summ_transpose_kernel<TIn>, dim3((T + 63) / 64, (N + 63) / 64, B), dim3(64, 4), 0,
-                     stream, N, T, traj, d_scale, d_shift, w.value.p);
+  launch_transpose<TIn>(stream, link, B, T, N, traj, d_scale, d_shift, w.value.p);
   hipLaunchKernelGGL(ci::summ_cumsum_kernel, dim3((N + 63) / 64, B), dim3(64), 0, stream, N, T,
                      w.value.p, w.obs.p, w.flags.p, w.cum.p, w.draw.p);
   double* ord_value = w.order.p;
@@ -128,11 +145,11 @@ hipError_t placebo_pool_launch(hipStream_t stream, int N, int O, int G, int whic
 hipError_t placebo_finish_launch(hipStream_t stream, int N, size_t r0, size_t rows, int out,
                                  const double* acc, const double* seen, double* M);
 // The launch of ci_windows.hip (kernel: ci_windows.h).
-hipError_t windows_launch(hipStream_t stream, int B, int N, int T, int W, const float* traj,
+hipError_t windows_launch(hipStream_t stream, int link, int B, int N, int T, int W, const float* traj,
                           const double* obs, const double* scales, const double* shifts,
                           const int* first, const int* count, double* out);
 // The launch of ci_paths.hip (kernels: ci_paths.h).
-hipError_t paths_launch(hipStream_t stream, int N, int T, int W, int p0, int pairs, int max_count,
+hipError_t paths_launch(hipStream_t stream, int link, int N, int T, int W, int p0, int pairs, int max_count,
                         const float* traj, const double* obs, const double* scales, const double* shifts,
                         const int* first, const int* count, const long long* steps_before, double* X,
                         double* mom, double* observed_excursion, int* at, double* excursion, int* exceed);
@@ -169,7 +186,7 @@ static int check_window_table(const char* what, int B, int T, int32_t W, int max
 // the 2 * B * W rows of totals.  The call's device memory -- the tables and 2 * (N + 8) doubles per
 // (series, window) -- is its own and goes back on every return path; the summary's scratch is
 // neither built nor touched.
-static int windows_resident(const char* what, int device, hipStream_t stream, int B, int T, int N,
+static int windows_resident(const char* what, int device, hipStream_t stream, int link, int B, int T, int N,
                             const float* traj, const double* scale, const double* shift,
                             const double* observed, int32_t W, const int32_t* first,
                             const int32_t* count, int32_t num_ranks, const int32_t* ranks,
@@ -195,7 +212,7 @@ static int windows_resident(const char* what, int device, hipStream_t stream, in
   HIP_TRY(hipMemcpyAsync(d_i32.p, first, BW * sizeof(int), hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(d_count, count, BW * sizeof(int), hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(d_ranks, ranks, num_ranks * sizeof(int), hipMemcpyHostToDevice, stream));
-  HIP_TRY(ci::windows_launch(stream, B, N, T, W, traj, d_f64.p, d_scale, d_shift, d_i32.p, d_count,
+  HIP_TRY(ci::windows_launch(stream, link, B, N, T, W, traj, d_f64.p, d_scale, d_shift, d_i32.p, d_count,
                              d_draw));
   if (per_draw_order)
     HIP_TRY(launch_select(stream, N, 1, (int)(2 * BW), num_ranks, d_ranks, d_draw, nullptr, d_order,
@@ -226,7 +243,7 @@ static size_t paths_pair_doubles(int N, int count) {
   return (size_t)count * (2 * (size_t)N + 4) + 2 * (size_t)N + 2 * ci::SUMM_MAX_RANKS + 2 + 2;
 }
 
-static int paths_resident(const char* what, int device, hipStream_t stream, int B, int T, int N,
+static int paths_resident(const char* what, int device, hipStream_t stream, int link, int B, int T, int N,
                           const float* traj, const double* scale, const double* shift,
                           const double* observed, int32_t W, const int32_t* first, const int32_t* count,
                           int32_t num_ranks, const int32_t* ranks, double* center, double* spread,
@@ -318,7 +335,7 @@ static int paths_resident(const char* what, int device, hipStream_t stream, int 
                                    d_scale, d_shift, d_i32.p, d_count, d_steps.p, d_X.p, d_mom, d_obsexc, d_at,
                                    d_exc, d_exceed));
     } else {
-      HIP_TRY(ci::paths_launch(stream, N, T, W, (int)p0, (int)pairs, max_count, traj, d_f64.p, d_scale, d_shift,
+      HIP_TRY(ci::paths_launch(stream, link, N, T, W, (int)p0, (int)pairs, max_count, traj, d_f64.p, d_scale, d_shift,
                                d_i32.p, d_count, d_steps.p, d_X.p, d_mom, d_obsexc, d_at, d_exc, d_exceed));
     }
     if (excursion_order)
@@ -372,7 +389,7 @@ static int summarize_draws_impl(int32_t device, int32_t num_draws, int32_t T, co
   SummScratch w;
   HIP_TRY(d_traj.alloc(TN));
   HIP_TRY(hipMemcpy(d_traj.p, trajectories, TN * sizeof(TIn), hipMemcpyHostToDevice));
-  return summarize_resident<TIn>(nullptr, w, 1, T, num_draws, d_traj.p, &scale, &shift, observed, flags,
+  return summarize_resident<TIn>(nullptr, w, ci::LINK_IDENTITY, 1, T, num_draws, d_traj.p, &scale, &shift, observed, flags,
                                  num_ranks, ranks, value_order, cum_order, per_draw, per_draw_order);
 }
 
@@ -426,7 +443,27 @@ static int check_windows(int T, int32_t G, const int32_t* offsets, const int32_t
 // Otherwise (ci_session_pool_event_trajectories): a group is N rows of S = out_stride doubles on the
 // host and of min(S, T) on the device -- no width exceeds T, so min(num_groups, B) groups fit `value`
 // at a time either way -- and the columns of a wider host row are zeroed on the host.
-static int pool_resident(int device, hipStream_t stream, SummScratch& w, int B, int T, int N,
+// link: one of ci::LINK_* (ci_link.h).
+template <int LINK>
+static void pool_launch(hipStream_t stream, bool event, bool aligned, dim3 grid, int N, int T, long long NT,
+                        long long total, const float* traj, const int* d_off, const ci::PoolEntry* d_entries,
+                        const int* d_width, int Sd, int has_init, double* pooled) {
+  const dim3 block(ci::POOL_NT);
+  if (!event && aligned)
+    hipLaunchKernelGGL((ci::pool_kernel<true, LINK>), grid, block, 0, stream, NT, traj, d_off, d_entries,
+                       has_init, pooled);
+  else if (!event)
+    hipLaunchKernelGGL((ci::pool_kernel<false, LINK>), grid, block, 0, stream, NT, traj, d_off, d_entries,
+                       has_init, pooled);
+  else if (aligned)
+    hipLaunchKernelGGL((ci::pool_event_kernel<true, LINK>), grid, block, 0, stream, N, T, total, traj,
+                       d_off, d_entries, d_width, Sd, has_init, pooled);
+  else
+    hipLaunchKernelGGL((ci::pool_event_kernel<false, LINK>), grid, block, 0, stream, N, T, total, traj,
+                       d_off, d_entries, d_width, Sd, has_init, pooled);
+}
+
+static int pool_resident(int device, hipStream_t stream, SummScratch& w, int link, int B, int T, int N,
                          const float* traj, const double* scale, const double* shift, int32_t G,
                          const int32_t* offsets, const int32_t* members, const double* weights,
                          const int32_t* first, const int32_t* width, int32_t S,
@@ -470,22 +507,14 @@ static int pool_resident(int device, hipStream_t stream, SummScratch& w, int B, 
     const int ng = G - g0 < per_pass ? G - g0 : per_pass;
     const size_t rows = (size_t)ng * group_rows, at = (size_t)g0 * group_rows * Sh;
     if (init) HIP_TRY(copy(w.value.p, init + at, rows, true));
-    const dim3 grid(blocks, ng), block(ci::POOL_NT);
+    const dim3 grid(blocks, ng);
     const int* d_off = d_tables.p + g0;
     const int* d_width = d_tables.p + G + 1 + g0;
     const int has_init = init ? 1 : 0;
-    if (!first && aligned)
-      hipLaunchKernelGGL(ci::pool_kernel<true>, grid, block, 0, stream, NT, traj, d_off, d_entries.p,
-                         has_init, w.value.p);
-    else if (!first)
-      hipLaunchKernelGGL(ci::pool_kernel<false>, grid, block, 0, stream, NT, traj, d_off, d_entries.p,
-                         has_init, w.value.p);
-    else if (aligned)
-      hipLaunchKernelGGL(ci::pool_event_kernel<true>, grid, block, 0, stream, N, T, (long long)B * NT, traj,
-                         d_off, d_entries.p, d_width, (int)Sd, has_init, w.value.p);
-    else
-      hipLaunchKernelGGL(ci::pool_event_kernel<false>, grid, block, 0, stream, N, T, (long long)B * NT, traj,
-                         d_off, d_entries.p, d_width, (int)Sd, has_init, w.value.p);
+    const auto launch = link == ci::LINK_LOG ? pool_launch<ci::LINK_LOG>
+                        : link == ci::LINK_LOG1P ? pool_launch<ci::LINK_LOG1P> : pool_launch<ci::LINK_IDENTITY>;
+    launch(stream, first != nullptr, aligned, grid, N, T, NT, (long long)B * NT, traj, d_off, d_entries.p,
+           d_width, (int)Sd, has_init, w.value.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(copy(out + at, w.value.p, rows, false));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -497,6 +526,38 @@ static int pool_resident(int device, hipStream_t stream, SummScratch& w, int B, 
 
 extern "C" {
 
+int ci_session_set_link(ci_session* s, int32_t link) {
+  if (!s) return fail("NULL argument");
+  if (link < 0 || link >= ci::NUM_LINKS)
+    return fail("ci_session_set_link: unknown link %d (CI_LINK_IDENTITY = 0, CI_LINK_LOG = 1, CI_LINK_LOG1P = 2)",
+                link);
+  s->link = link;
+  return 0;
+}
+
+// The means over the draws of value[b, n, t] under the session's link: the transpose into `value`,
+// its row means in `obs` -- the passes of a component of ci_session_summarize_components.
+int ci_session_value_mean(ci_session* s, const double* scale, const double* shift, double* value_mean) {
+  if (!s || !scale || !shift || !value_mean) return fail("NULL argument");
+  if (!s->ran) return fail("ci_session_value_mean needs a finished ci_session_run");
+  const ci_problem& pb = s->pb;
+  const int B = pb.num_series, T = pb.T, N = pb.num_chains * pb.num_results;
+  HIP_TRY(hipSetDevice(pb.device));
+  SummScratch& w = s->summ;
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  hipStream_t stream = s->stream;
+  double* d_scale = w.obs.p + (size_t)B * T;
+  double* d_shift = d_scale + B;
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  launch_transpose<float>(stream, s->link, B, T, N, s->o_traj.p, d_scale, d_shift, w.value.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * T, N, w.value.p, w.obs.p, nullptr));
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipMemcpy(value_mean, w.obs.p, (size_t)B * T * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int ci_session_pool_event_trajectories(ci_session* s, const double* scale, const double* shift,
                                        int32_t num_groups, const int32_t* offsets, const int32_t* members,
                                        const double* weights, const int32_t* first, const int32_t* width,
@@ -505,7 +566,7 @@ int ci_session_pool_event_trajectories(ci_session* s, const double* scale, const
     return fail("NULL argument");
   if (!s->ran) return fail("ci_session_pool_event_trajectories needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
-  return pool_resident(pb.device, s->stream, s->summ, pb.num_series, pb.T, pb.num_chains * pb.num_results,
+  return pool_resident(pb.device, s->stream, s->summ, s->link, pb.num_series, pb.T, pb.num_chains * pb.num_results,
                        s->o_traj.p, scale, shift, num_groups, offsets, members, weights, first, width,
                        out_stride, init, out);
 }
@@ -516,7 +577,7 @@ int ci_session_pool_trajectories(ci_session* s, const double* scale, const doubl
   if (!s || !scale || !shift || !offsets || !members || !weights || !out) return fail("NULL argument");
   if (!s->ran) return fail("ci_session_pool_trajectories needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
-  return pool_resident(pb.device, s->stream, s->summ, pb.num_series, pb.T, pb.num_chains * pb.num_results,
+  return pool_resident(pb.device, s->stream, s->summ, s->link, pb.num_series, pb.T, pb.num_chains * pb.num_results,
                        s->o_traj.p, scale, shift, num_groups, offsets, members, weights, nullptr, nullptr, 0,
                        init, out);
 }
@@ -526,7 +587,7 @@ int ci_ll_session_pool_trajectories(ci_ll_session* s, const double* scale, const
                                     const double* weights, const double* init, double* out) {
   if (!s || !scale || !shift || !offsets || !members || !weights || !out) return fail("NULL argument");
   if (!s->h_ran) return fail("ci_ll_session_pool_trajectories needs a finished ci_ll_session_hmc_run");
-  return pool_resident(s->device, s->stream, s->summ, s->B, s->T, s->h_C * s->h_S, s->h_traj.p, scale,
+  return pool_resident(s->device, s->stream, s->summ, ci::LINK_IDENTITY, s->B, s->T, s->h_C * s->h_S, s->h_traj.p, scale,
                        shift, num_groups, offsets, members, weights, nullptr, nullptr, 0, init, out);
 }
 
@@ -538,7 +599,7 @@ int ci_session_summarize(ci_session* s, const double* scale, const double* shift
   if (!s->ran) return fail("ci_session_summarize needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
   HIP_TRY(hipSetDevice(pb.device));
-  return summarize_resident(s->stream, s->summ, pb.num_series, pb.T, pb.num_chains * pb.num_results,
+  return summarize_resident(s->stream, s->summ, s->link, pb.num_series, pb.T, pb.num_chains * pb.num_results,
                             s->o_traj.p, scale, shift, observed, flags, num_ranks, ranks, value_order,
                             cum_order, per_draw, per_draw_order);
 }
@@ -550,7 +611,7 @@ int ci_session_summarize_windows(ci_session* s, const double* scale, const doubl
   if (!s || !scale || !shift || !observed || !first || !count || !ranks) return fail("NULL argument");
   if (!s->ran) return fail("ci_session_summarize_windows needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
-  return windows_resident("ci_session_summarize_windows", pb.device, s->stream, pb.num_series, pb.T,
+  return windows_resident("ci_session_summarize_windows", pb.device, s->stream, s->link, pb.num_series, pb.T,
                           pb.num_chains * pb.num_results, s->o_traj.p, scale, shift, observed,
                           num_windows, first, count, num_ranks, ranks, per_draw, per_draw_order);
 }
@@ -561,7 +622,7 @@ int ci_ll_session_summarize_windows(ci_ll_session* s, const double* scale, const
                                     double* per_draw, double* per_draw_order) {
   if (!s || !scale || !shift || !observed || !first || !count || !ranks) return fail("NULL argument");
   if (!s->h_ran) return fail("ci_ll_session_summarize_windows needs a finished ci_ll_session_hmc_run");
-  return windows_resident("ci_ll_session_summarize_windows", s->device, s->stream, s->B, s->T,
+  return windows_resident("ci_ll_session_summarize_windows", s->device, s->stream, ci::LINK_IDENTITY, s->B, s->T,
                           s->h_C * s->h_S, s->h_traj.p, scale, shift, observed, num_windows, first,
                           count, num_ranks, ranks, per_draw, per_draw_order);
 }
@@ -585,7 +646,7 @@ int ci_test_session_summarize_paths(ci_session* s, const double* scale, const do
   if (!s || !scale || !shift || !observed || !first || !count || !ranks) return fail("NULL argument");
   if (!s->ran) return fail("ci_session_summarize_paths needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
-  return paths_resident("ci_session_summarize_paths", pb.device, s->stream, pb.num_series, pb.T,
+  return paths_resident("ci_session_summarize_paths", pb.device, s->stream, s->link, pb.num_series, pb.T,
                         pb.num_chains * pb.num_results, s->o_traj.p, scale, shift, observed, num_windows,
                         first, count, num_ranks, ranks, center, spread, excursion, excursion_order,
                         observed_excursion, at, exceed, max_bytes, num_chunks);
@@ -599,7 +660,7 @@ int ci_ll_session_summarize_paths(ci_ll_session* s, const double* scale, const d
                                   int32_t* exceed) {
   if (!s || !scale || !shift || !observed || !first || !count || !ranks) return fail("NULL argument");
   if (!s->h_ran) return fail("ci_ll_session_summarize_paths needs a finished ci_ll_session_hmc_run");
-  return paths_resident("ci_ll_session_summarize_paths", s->device, s->stream, s->B, s->T, s->h_C * s->h_S,
+  return paths_resident("ci_ll_session_summarize_paths", s->device, s->stream, ci::LINK_IDENTITY, s->B, s->T, s->h_C * s->h_S,
                         s->h_traj.p, scale, shift, observed, num_windows, first, count, num_ranks, ranks,
                         center, spread, excursion, excursion_order, observed_excursion, at, exceed,
                         CI_PATHS_MAX_BYTES, nullptr);
@@ -1009,7 +1070,7 @@ int ci_test_summarize_draw_paths_f64(int32_t device, int32_t num_groups, int32_t
     if (!std::isfinite(shift[g])) return fail("%s: the shift of group %d is not finite", what, g);
   }
   // (the null stream, as ci_summarize_draws: the call has no session)
-  return paths_resident(what, device, nullptr, num_groups, T, num_draws, nullptr, scale, shift, observed,
+  return paths_resident(what, device, nullptr, ci::LINK_IDENTITY, num_groups, T, num_draws, nullptr, scale, shift, observed,
                         num_windows, first, count, num_ranks, ranks, center, spread, excursion,
                         excursion_order, observed_excursion, at, exceed, max_bytes, num_chunks, draws);
 }
@@ -1021,7 +1082,7 @@ int ci_ll_session_hmc_summarize(ci_ll_session* s, const double* scale, const dou
   if (!s || !scale || !shift || !observed || !flags || !ranks) return fail("NULL argument");
   if (!s->h_ran) return fail("ci_ll_session_hmc_summarize needs a finished ci_ll_session_hmc_run");
   HIP_TRY(hipSetDevice(s->device));
-  return summarize_resident(s->stream, s->summ, s->B, s->T, s->h_C * s->h_S, s->h_traj.p, scale, shift,
+  return summarize_resident(s->stream, s->summ, ci::LINK_IDENTITY, s->B, s->T, s->h_C * s->h_S, s->h_traj.p, scale, shift,
                             observed, flags, num_ranks, ranks, value_order, cum_order, per_draw,
                             per_draw_order);
 }

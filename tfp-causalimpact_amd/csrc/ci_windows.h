@@ -22,6 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ci_link.h"
+
 namespace ci {
 
 constexpr int WIN_TILE = 64;
@@ -30,7 +32,8 @@ constexpr int WIN_TILE = 64;
 // ALIGNED (T % 4 == 0 and a 16-byte aligned base: every row then starts on a 16-byte boundary):
 // float4 loads, 16 lanes per row and 4 rows per instruction; otherwise one float per lane.
 // first, count [B, W]; out [B, W, 2, N].  Requires 0 <= first, 0 <= count, first + count <= T.
-template <bool ALIGNED>
+// LINK (ci_link.h): v is link(that); the identity is the code without it.
+template <bool ALIGNED, int LINK = LINK_IDENTITY>
 __global__ __launch_bounds__(64) void window_totals_kernel(int N, int T, int W,
                                                            const float* __restrict__ traj_all,
                                                            const double* __restrict__ obs_all,
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(64) void window_totals_kernel(int N, int T, int W,
     __syncthreads();
     if (n < N) {
       for (int t = lo; t < hi; ++t) {
-        const double v = __dadd_rn(__dmul_rn((double)tile[lane][t - t0], scale), shift);
+        const double v = link_value<LINK>(__dadd_rn(__dmul_rn((double)tile[lane][t - t0], scale), shift));
         pred_sum = __dadd_rn(pred_sum, v);
         const double point = -__dsub_rn(v, obs_tile[t - t0]);
         point_sum = __dadd_rn(point_sum, (point != point) ? 0.0 : point);

@@ -10,6 +10,7 @@ pre_period, post_period = ("2022-01-01", "2022-05-20"), ("2022-05-21", "2022-07-
 impact = causalimpact.fit_causalimpact(data, pre_period, post_period)
 print(impact.series.columns.tolist()[:6], impact.summary.shape, type(impact.posterior_samples.level).__name__, impact.posterior_samples.level.numpy().shape)
 print(causalimpact.summary(impact))
+print(causalimpact.fit_causalimpact(data, pre_period, post_period, outcome_link="log").summary["rel_effect"])  # log-scale model, data-scale answers
 impact = causalimpact.fit_causalimpact(
     data, pre_period, post_period,
     inference_options=causalimpact.InferenceOptions(num_results=1000, num_chains=8, devices=[0]),
