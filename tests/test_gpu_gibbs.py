@@ -489,10 +489,10 @@ def test_eight_wave_latency_kernel_equals_the_four_wave_kernel(T, p, has_slope, 
     out[flags] = (sess.kernel_name(), sess.run(), sess.fetch())
     sess.close()
   assert "gibbs_kernel8" in out[0][0] and "gibbs_kernel<" in out[_native.FLAG_FOUR_WAVES][0]
-  five, four = out[0][2], out[_native.FLAG_FOUR_WAVES][2]
+  eight, four = out[0][2], out[_native.FLAG_FOUR_WAVES][2]
   for k, v in four.items():
-    np.testing.assert_array_equal(five[k], v, err_msg=k)
-  w = five["weights"]
+    np.testing.assert_array_equal(eight[k], v, err_msg=k)
+  w = eight["weights"]
   assert np.isfinite(w).all() and (w != 0).any()
   if p >= 5:   # inclusion patterns do change during the run: the fall-back route is exercised
     incl = (w != 0)

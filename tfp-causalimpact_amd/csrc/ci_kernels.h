@@ -703,7 +703,7 @@ __device__ __forceinline__ void dk_normals(const Rng& rng, uint32_t iter, int ow
 
 // Step (1) of dk_draw, the scan of the prior simulation x <- T x + n_t, in two halves around a
 // workgroup barrier: it needs the disturbance scales and the normals only, not the regression
-// draw, so the five-wave kernel runs the first half before its (B3).
+// draw, so the eight-wave kernel runs the first half before its (Bs).
 template <int D, int L>
 __device__ __forceinline__ PElem<D> dk_prior_begin(const Vec<D>& sig, const float (&zl)[L],
                                                    const float (&zs)[L], float* slots, int lane,
@@ -738,7 +738,7 @@ __device__ __forceinline__ PElem<D> dk_prior_finish(const PElem<D>& incl, const 
 //     Mb = N_0 ... N_{L-1},   N_t = (I - Z' k_t') T'   adjoint:  r_{t-1} = N_t r_t + Z' v_t / F_t
 //   DATA phase -- two scans of affine maps of d-vectors (forward: the filtered means, backward:
 //   the smoothing adjoint r) whose matrix parts are Mf / Mb, each followed by a local pass.
-// The five-/eight-wave Gibbs kernels run the matrix phase while the regression wave is still
+// The eight-wave Gibbs kernel runs the matrix phase while the regression wave is still
 // drawing the weights (the data of the filter); every kernel calls the same functions, so all of
 // them produce the same bits (-ffp-contract=on).
 // ------------------------------------------------------------------------------------
@@ -2666,6 +2666,44 @@ static __device__ __forceinline__ void serial_section(SerialCtx* cx, const RegLd
   wave_sync();
 }
 
+// ------------------------------------------------------------------------------------
+// Steps of one Gibbs iteration that gibbs_kernel (below: four waves, stock and ragged, every
+// regression mode) and gibbs_kernel8 (ci_kernels8.h: eight waves) both perform, ONE text each, next
+// to xt_sums_wave, store_targets, the serial section, the sweeps and the Durbin-Koopman draw.  No
+// function here branches on its caller at run time.
+// ------------------------------------------------------------------------------------
+// The model of the Durbin-Koopman draw: observation variance from sigma_obs `so`, disturbance
+// scales, prior moments of x_0.
+template <int D>
+__device__ __forceinline__ DkModel<D> dk_model(float so, const Vec<D>& sig, float init_loc, float init_var,
+                                               float init_svar) {
+  DkModel<D> md;
+  md.H = so * so;
+  md.sig = sig;
+  md.a1 = vzero<D>();
+  md.a1.v[0] = init_loc;
+  md.p1.v[0] = init_var;
+  if constexpr (D == 2) md.p1.v[1] = init_svar;
+  return md;
+}
+
+// Progress of a streamed fit (KArgs::progress): retained draws 0 .. done-1 are published after
+// iteration `it` when `done` is a multiple of progress_every or the last.  The order is: every
+// wave waits for its own rows (progress_rows_sent), a workgroup barrier (the caller's), then ONE
+// thread makes them visible at system scope and stores the count (progress_publish).
+__device__ __forceinline__ bool progress_due(const KArgs& a, int it) {
+  return a.progress != nullptr && it > a.W && ((it - a.W) % a.progress_every == 0 || it - a.W == a.S);
+}
+__device__ __forceinline__ void progress_rows_sent() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows have reached L2
+}
+__device__ __forceinline__ void progress_publish(const KArgs& a, size_t chain_lin, int it) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");          // system scope: write back L2
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __hip_atomic_store(a.progress + chain_lin, (unsigned int)(it - a.W), __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 template <int D, int L, int PM, bool PROF = false, bool RAGGED = false>
 #ifndef CI_MIN_WAVES
 #define CI_MIN_WAVES 2
@@ -2750,6 +2788,12 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
     R.idx = (int*)(smem + lay.off_idx);
     R.w = wls;
   }
+  // (The SerialCtx set-up, the staging of yv / maskbits and of xtx / omega / the design below are also in
+  //  gibbs_kernel8, written out: moved into shared functions each of them costs this kernel registers --
+  //  e.g. the ragged <1,8,3> build 252 -> 280 bytes of scratch with the observations staged by a function,
+  //  <1,8,2> 0 -> 16 spilled VGPRs with xtx / omega / the design, <2,16,2> 252 -> 260 bytes with the context;
+  //  the stream keys above as a function leave this kernel's code as it is but cost gibbs_kernel8<2,8> two
+  //  VGPRs: profiles/trend_kernels_shared_steps_resources.txt.)
   if (tid == 0) {
     cx->sp = a.sp[series];
     cx->obs_scale = cx->sp.obs_scale0;           // causalimpact_lib.py:566-572
@@ -3117,18 +3161,10 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
       else if (wave == 0) emit(so_prev, nz0 + 3 * L * 64);   // waves 1-3 emitted during the serial section
     }
     prof.tick(2);
-    if (a.progress != nullptr && it > a.W) {
-      const int done = it - a.W;                  // retained draws 0 .. done-1 are in HBM
-      if (done % a.progress_every == 0 || done == a.S) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows have reached L2
-        __syncthreads();                          // ... and so have every other wave's
-        if (tid == 0) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");          // system scope: write back L2
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          __hip_atomic_store(a.progress + chain_lin, (unsigned int)done, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
+    if (progress_due(a, it)) {
+      progress_rows_sent();
+      __syncthreads();                            // ... and so have every other wave's
+      if (tid == 0) progress_publish(a, chain_lin, it);
     }
     if (it == n_iter) break;
 
@@ -3224,19 +3260,11 @@ __global__ __launch_bounds__(NT, PM == 2 ? 1 : CI_MIN_WAVES) void gibbs_kernel(K
 #pragma unroll
       for (int l = 0; l < L; ++l) resid[l] = yv[l] - xw[l];
     }
-    DkModel<D> md;
-    {
-      const float so = scal[SC_OBS_DK];
-      md.H = so * so;
-      md.sig.v[0] = scal[SC_LEVEL];
-      md.a1 = vzero<D>();
-      md.a1.v[0] = init_loc;
-      md.p1.v[0] = init_var;
-      if constexpr (D == 2) {
-        md.sig.v[1] = scal[SC_SLOPE];
-        md.p1.v[1] = init_svar;
-      }
-    }
+    const float so = scal[SC_OBS_DK];
+    Vec<D> sig;
+    sig.v[0] = scal[SC_LEVEL];
+    if constexpr (D == 2) sig.v[1] = scal[SC_SLOPE];
+    const DkModel<D> md = dk_model<D>(so, sig, init_loc, init_var, init_svar);
     Vec<D> x[L];
     prof.tick(3);
     if (wave == 0) {

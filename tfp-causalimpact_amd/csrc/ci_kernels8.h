@@ -1184,40 +1184,22 @@ __global__ __launch_bounds__(NT8) void gibbs_kernel8(KArgs a) {
       if constexpr (D == 2) sig.v[1] = (float)slope_scale;
       if (it < n_iter) pincl = dk_prior_begin<D, L>(sig, zl, zs, slots, lane, wave);
     }
-    const bool publish = a.progress != nullptr && it > a.W &&
-                         ((it - a.W) % a.progress_every == 0 || it - a.W == a.S);
-    if (publish) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows are in L2
+    const bool publish = progress_due(a, it);
+    if (publish) progress_rows_sent();
     prof.tick(2);
     aprof.tick(7 + wave);
     __syncthreads();                                       // (Bs) sigma^2_obs(it) in LDS
     prof.tick(1);
-    if (publish) {
-      // the time waves' stores of the first `done` rows were issued before (Bs); make them visible
-      // to the copy engines and publish (the scalars / weights of these draws are copied after
-      // the kernel has ended)
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(a.progress + chain_lin, (unsigned int)(it - a.W), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
+    // (Bs) is the barrier of the publication: the time waves' rows were issued before it (the
+    // scalars / weights of these draws are copied after the kernel has ended)
+    if (publish && tid == 0) progress_publish(a, chain_lin, it);
     if (it == n_iter) {
       __syncthreads();                                     // (B3)
       break;
     }
 
     // ---- matrix phase of the draw of iteration it: needs sigma^2_obs, not the weights
-    DkModel<D> md;
-    {
-      const float so = scal[SC_OBS_DK];
-      md.H = so * so;
-      md.sig = sig;
-      md.a1 = vzero<D>();
-      md.a1.v[0] = init_loc;
-      md.p1.v[0] = init_var;
-      if constexpr (D == 2) md.p1.v[1] = init_svar;
-    }
+    const DkModel<D> md = dk_model<D>(scal[SC_OBS_DK], sig, init_loc, init_var, init_svar);
     Vec<D> q;
 #pragma unroll
     for (int i = 0; i < D; ++i) q.v[i] = md.sig.v[i] * md.sig.v[i];
