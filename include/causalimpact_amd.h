@@ -416,6 +416,36 @@ int ci_session_summarize_predictions(ci_session* session, const double* scale, c
 int ci_session_summarize_placebo(ci_session* session, const double* scale, const double* shift,
                                  int32_t max_origins, const int32_t* origins, const int32_t* horizon,
                                  double* predicted_mean, double* spread_mean, double* pit_mean);
+/* The two summaries above for ANY BLOCK LIST whose state has at most 64 components: weekly plus
+ * monthly blocks, blocks of 12, 24 or 52 seasons, blocks with several steps per season next to
+ * others.  Additive: CI_ABI_VERSION stays 5; look the symbols up (dlsym) where an older library may
+ * be met.  Arguments, outputs, argument checks and their messages are those of
+ * ci_session_summarize_predictions and ci_session_summarize_placebo.  The model generalises theirs to
+ * the K blocks of the session (hs = has_slope):
+ *   block k has n_k = num_seasons[k] seasons and n_k - 1 effects at offset o_k = 1 + hs +
+ *     sum_{j<k} (n_j - 1);  d = 1 + hs + sum_k (n_k - 1) <= 64;  Z has ones at 0 and at every o_k;
+ *   sigma_drift: the draws [B, N, K]; season_change [K, T]; the initial moments of every block are
+ *     init_seasonal_scale^2 * ((i == j) - 1 / n_k), zero across blocks;
+ *   m = a[0] + a[o_0] + a[o_1] + ..;  (P Z')_i = P[i][0] + P[i][o_0] + ..;  F = Z (P Z') + H, summed
+ *     in that order; Z r and Z pz of the placebo likewise;
+ *   transition: level += slope, then for k ascending every block whose season_change[k, t] is set
+ *     rotates, x' = (x_1, .., x_{n_k - 2}, -sum x), its rows, its columns and its covariances with
+ *     every other component, the sums ascending from 0.0, and takes (sigma_drift_k / n_k)^2 on every
+ *     entry of the block; last sigma_level^2 on P[0][0] and sigma_slope^2 on P[1][1].
+ * Every other line is that of the entries above.  A filter is run by a group of 8, 16, 32 or 64
+ * lanes (the smallest that holds d), a row of P per lane; what it computes for a (series, draw)
+ * depends on nothing else in the launch.
+ * Sessions: every finished ci_session of ci_session_create (float32 Gibbs), whatever kernel it runs
+ * on, its state at most 64; a ragged session is refused (its models belong to the entries above).
+ * Checked before any device call: as the entries above, with the state's size in place of their
+ * block list. */
+int ci_session_summarize_predictions_blocks(ci_session* session, const double* scale, const double* shift,
+                                            int32_t num_ranks, const int32_t* ranks,
+                                            double* forecast_mean, double* forecast_order,
+                                            double* variance_mean, double* pit_mean, double* loglik);
+int ci_session_summarize_placebo_blocks(ci_session* session, const double* scale, const double* shift,
+                                        int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                        double* predicted_mean, double* spread_mean, double* pit_mean);
 /* PLACEBO FORECASTS OF POOLED SUMS: the forecasts above, added over groups of series draw by draw --
  * the placebo check of a pooled effect.  Additive: CI_ABI_VERSION stays 5; look the symbol up (dlsym)
  * where an older library may be met.

@@ -126,6 +126,12 @@ def load():
   if hasattr(L, "ci_session_summarize_placebo"):       # (additive, likewise)
     L.ci_session_summarize_placebo.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                C.c_void_p, C.c_void_p] + [C.c_void_p] * 3
+  if hasattr(L, "ci_session_summarize_predictions_blocks"):   # (additive, likewise)
+    L.ci_session_summarize_predictions_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                          C.c_void_p] + [C.c_void_p] * 5
+  if hasattr(L, "ci_session_summarize_placebo_blocks"):       # (additive, likewise)
+    L.ci_session_summarize_placebo_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                      C.c_void_p, C.c_void_p] + [C.c_void_p] * 3
   if hasattr(L, "ci_session_pool_placebo"):            # (additive, likewise)
     L.ci_session_pool_placebo.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 +
                                           [C.c_int32] + [C.c_void_p] * 8)
@@ -211,7 +217,8 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_algorithmic_bytes", "ci_session_kernel_name", "ci_session_destroy",
           "ci_session_profile", "ci_ll_session_kernel_name",
           "ci_session_summarize", "ci_session_summarize_components",
-          "ci_session_summarize_predictions", "ci_session_summarize_placebo", "ci_summarize_draws", "ci_summarize_draws_f64",
+          "ci_session_summarize_predictions", "ci_session_summarize_placebo",
+          "ci_session_summarize_predictions_blocks", "ci_session_summarize_placebo_blocks", "ci_summarize_draws", "ci_summarize_draws_f64",
           "ci_summarize_draw_paths_f64",
           "ci_session_summarize_windows", "ci_ll_session_summarize_windows",
           "ci_session_summarize_paths", "ci_ll_session_summarize_paths",
@@ -1012,7 +1019,8 @@ class Session:
         *[_ptr(arrs.get(k)) for k in COMPONENT_OUTPUTS]))
     return arrs
 
-  def summarize_predictions(self, scale, shift, ranks, want=None) -> Dict[str, np.ndarray]:
+  def summarize_predictions(self, scale, shift, ranks, want=None,
+                            _entry="ci_session_summarize_predictions") -> Dict[str, np.ndarray]:
     """On-device one-step-ahead prediction errors of every fit (ci_session_summarize_predictions):
     for every pooled draw the Kalman filter of that draw's model over the observed series, in
     float64 (`causalimpact_lib._prediction_summary_host` is the same definition in numpy).  scale,
@@ -1020,9 +1028,9 @@ class Session:
     that keep the series axis: forecast_mean [B,T], forecast_order [B,R,T], variance_mean [B,T],
     pit_mean [B,T] (0 at the masked steps), loglik [B,N].  `want`: the names to compute (default:
     all); the others are skipped on the device too."""
-    fn = getattr(self._lib, "ci_session_summarize_predictions", None)
+    fn = getattr(self._lib, _entry, None)
     if fn is None:
-      raise NativeError("the loaded library has no ci_session_summarize_predictions: rebuild it")
+      raise NativeError(f"the loaded library has no {_entry}: rebuild it")
     pb = self.pb
     B, T, N = pb.num_series, pb.T, pb.num_chains * pb.num_results
     rk = np.ascontiguousarray(ranks, dtype=np.int32).reshape(-1)
@@ -1044,7 +1052,15 @@ class Session:
               *[_ptr(arrs.get(k)) for k in PREDICTION_OUTPUTS]))
     return arrs
 
-  def summarize_placebo(self, scale, shift, origins, horizon, want=None) -> Dict[str, np.ndarray]:
+  def summarize_predictions_blocks(self, scale, shift, ranks, want=None) -> Dict[str, np.ndarray]:
+    """`summarize_predictions` for any block list whose state has at most 64 components
+    (ci_session_summarize_predictions_blocks: a group of lanes per filter): same arguments, same
+    outputs, same `want`.  Ragged sessions stay with `summarize_predictions`."""
+    return self.summarize_predictions(scale, shift, ranks, want,
+                                      _entry="ci_session_summarize_predictions_blocks")
+
+  def summarize_placebo(self, scale, shift, origins, horizon, want=None,
+                        _entry="ci_session_summarize_placebo") -> Dict[str, np.ndarray]:
     """On-device placebo forecasts of every fit (ci_session_summarize_placebo): for every pooled draw
     the filter of `summarize_predictions` up to each origin, then the forecast of the sum of the next
     `horizon` observations without any update, in float64 (`causalimpact_lib._placebo_summary_host`
@@ -1053,9 +1069,9 @@ class Session:
     row; horizon: scalar or [B].  Returns float64 arrays [B, O]: predicted_mean, spread_mean,
     pit_mean (0 in the unused slots and where the window counts no observation).  `want`: the names
     to compute (default: all); the others are skipped on the device too."""
-    fn = getattr(self._lib, "ci_session_summarize_placebo", None)
+    fn = getattr(self._lib, _entry, None)
     if fn is None:
-      raise NativeError("the loaded library has no ci_session_summarize_placebo: rebuild it")
+      raise NativeError(f"the loaded library has no {_entry}: rebuild it")
     B = self.pb.num_series
     org = np.asarray(origins)
     if org.ndim == 1 and B == 1:
@@ -1083,6 +1099,13 @@ class Session:
     _check(fn(self._h, sc.ctypes.data, sh.ctypes.data, int(org.shape[1]), org.ctypes.data,
               hz.ctypes.data, *[_ptr(arrs.get(k)) for k in PLACEBO_OUTPUTS]))
     return arrs
+
+  def summarize_placebo_blocks(self, scale, shift, origins, horizon, want=None) -> Dict[str, np.ndarray]:
+    """`summarize_placebo` for any block list whose state has at most 64 components
+    (ci_session_summarize_placebo_blocks): same arguments, same outputs, same `want`.  Ragged
+    sessions stay with `summarize_placebo`."""
+    return self.summarize_placebo(scale, shift, origins, horizon, want,
+                                  _entry="ci_session_summarize_placebo_blocks")
 
   def summarize_windows(self, scale, shift, observed, first, count, ranks,
                         want_draws=True) -> Dict[str, np.ndarray]:

@@ -281,7 +281,8 @@ def fit_causalimpact(data: pd.DataFrame,
   be trusted.  This is the FIXED-PARAMETER placebo: every draw's scales and weights come from the one
   fit of the whole pre-period, nothing is refitted, which makes the check cheap and somewhat
   optimistic; the windows overlap, so the origins are not independent trials.  On the GPU that holds
-  the draws wherever the predictive summary runs there (csrc/ci_placebo.h), in numpy from the
+  the draws wherever the predictive summary runs there (csrc/ci_placebo.h; csrc/ci_placebo_blocks.h for
+  more than one seasonal block or a block of more than 7 seasons), in numpy from the
   parameter draws on the other routes, exactly as `InferenceOptions.prediction_errors`.  ValueError
   before any fit when the pre-period has no room for one origin, or the state has more than
   `PREDICTION_MAX_STATE` components.
@@ -667,6 +668,13 @@ def check_prediction_state(local_linear_trend: bool, seasons: Sequence) -> int:
 def device_predictions_supported(num_seasons: Sequence[int]) -> bool:
   """The block lists ci_session_summarize_predictions takes: none, or one block of 2 to 7 seasons."""
   return len(num_seasons) == 0 or (len(num_seasons) == 1 and 2 <= int(num_seasons[0]) <= 7)
+
+
+def device_block_predictions_supported(has_slope: bool, num_seasons: Sequence[int]) -> bool:
+  """The models ci_session_summarize_predictions_blocks and ci_session_summarize_placebo_blocks take:
+  any block list whose state has at most `PREDICTION_MAX_STATE` components."""
+  return (all(int(n) >= 2 for n in num_seasons)
+          and prediction_state_dim(has_slope, num_seasons) <= PREDICTION_MAX_STATE)
 
 
 def _prediction_summary_host(y, mask, X, season_change, num_seasons, has_slope, params, draws,
@@ -1542,12 +1550,13 @@ def _host_placebo_summaries(inputs: Sequence[SeriesInputs], draws, part: Placebo
   return out
 
 
-def _device_placebo_summaries(sess, part: PlaceboPart):
-  """The placebo summary {name: [n, O]} of an open session (`summarize_placebo`): the launch's own
-  origin slots (never more than its steps), the horizon of a series without origin raised to the 1
-  the entry asks for."""
+def _device_placebo_summaries(sess, part: PlaceboPart, blocks: bool = False):
+  """The placebo summary {name: [n, O]} of an open session (`summarize_placebo`, with `blocks`
+  `summarize_placebo_blocks`): the launch's own origin slots (never more than its steps), the horizon
+  of a series without origin raised to the 1 the entry asks for."""
   width = max(1, int((part.origins >= 0).sum(axis=1).max()))
-  got = sess.summarize_placebo(part.scale, part.shift, part.origins[:, :width], np.maximum(part.horizon, 1))
+  entry = sess.summarize_placebo_blocks if blocks else sess.summarize_placebo
+  got = entry(part.scale, part.shift, part.origins[:, :width], np.maximum(part.horizon, 1))
   out = {k: np.zeros(part.origins.shape) for k in got}
   for k, v in got.items():
     out[k][:, :width] = v
@@ -1601,7 +1610,9 @@ def take_summaries(sess, request: SummaryRequest,
   after it), `summarize_placebo`, in this order for every caller -- every entry uploads its own arguments and leaves nothing behind for the
   next (tests/test_gpu_summaries_together.py).  `sess.summaries` names the kinds a session has.
   Prediction errors and placebo forecasts are filtered on the device where the session has the
-  entries and `device_predictions_supported` takes the model; else in numpy from the parameter draws,
+  entries and `device_predictions_supported` takes the model; else by the block-model entries
+  (`summarize_predictions_blocks`, `summarize_placebo_blocks`) where the session has those and
+  `device_block_predictions_supported` takes it; else in numpy from the parameter draws,
   fetched once for both, over `series_inputs` (one per series of the session; read for these two
   kinds only).  Components a session lacks stay None: the caller's business.  The scales and shifts
   map the SESSION's units to the data scale (`_request_in_internal_units`).  With `request.link` the
@@ -1618,14 +1629,21 @@ def take_summaries(sess, request: SummaryRequest,
   components = predictions = windows = placebo = draws = None
   if request.components and "components" in sess.summaries:
     components = sess.summarize_components(request.scale, request.shift, request.ranks)
-  on_host = (request.predictions is not None or request.placebo is not None) and not (
-      {"predictions", "placebo"} <= set(sess.summaries)
-      and device_predictions_supported(series_inputs[0].num_seasons))
+  filtered = request.predictions is not None or request.placebo is not None
+  has_entries = {"predictions", "placebo"} <= set(sess.summaries)
+  one_lane = filtered and has_entries and device_predictions_supported(series_inputs[0].num_seasons)
+  blocks = (filtered and has_entries and not one_lane and hasattr(sess, "summarize_predictions_blocks")
+            and hasattr(sess, "summarize_placebo_blocks")
+            and device_block_predictions_supported(series_inputs[0].has_slope, series_inputs[0].num_seasons))
+  on_host = filtered and not (one_lane or blocks)
   if on_host:
     draws = sess.fetch(list(_PARAMETER_DRAWS))
   if request.predictions is not None:
-    predictions = (_host_prediction_summaries(series_inputs, draws, request.predictions, request.ranks)
-                   if on_host else sess.summarize_predictions(*request.predictions, request.ranks))
+    if on_host:
+      predictions = _host_prediction_summaries(series_inputs, draws, request.predictions, request.ranks)
+    else:
+      entry = sess.summarize_predictions_blocks if blocks else sess.summarize_predictions
+      predictions = entry(*request.predictions, request.ranks)
   if request.windows is not None:
     windows = sess.summarize_windows(request.scale, request.shift, request.observed, *request.windows,
                                      request.ranks)
@@ -1635,7 +1653,7 @@ def take_summaries(sess, request: SummaryRequest,
   if request.placebo is not None:
     part = _per_series(request.placebo, len(series_inputs))
     placebo = _with_placebo_seen(series_inputs, part, _host_placebo_summaries(series_inputs, draws, part)
-                                 if on_host else _device_placebo_summaries(sess, part))
+                                 if on_host else _device_placebo_summaries(sess, part, blocks))
   if request.link:
     effect = dict(effect, value_mean=sess.value_mean(request.scale, request.shift))
   return SummaryRecord(effect=effect, components=components, predictions=predictions, windows=windows,

@@ -1,0 +1,103 @@
+// ci_placebo_blocks.h -- the placebo forecasts of ci_placebo.h for ANY block list with a state of at
+// most 64 components (ci_session_summarize_placebo_blocks; DESIGN.md "Block-model filters").
+//
+// The model, the layout (a group of G lanes per filter, lane i owns a_i and row i of P in registers)
+// and every step of the filter are those at the top of ci_predict_blocks.h.  When t reaches the
+// series' next origin -- uniform over the wavefront -- the lane copies its share of the predicted
+// moments (a_i, row i of P) and the group forecasts from the copy: the branch of ci_placebo.h, lines
+// 10-27, with Z r and Z pz summed in the order of Z a (0, o_0, o_1, ..) and r, one component per
+// lane, transformed like the mean.  The OUT selectors SUM, SPREAD, PIT and VAR and the zero slots
+// are unchanged.  The group's lane 0 stores: the result is the [B * O, N] matrix, draws contiguous.
+// The host checks o + H_b <= T for every origin before the launch: no step beyond the series is read.
+#pragma once
+#include "ci_placebo.h"
+#include "ci_predict_blocks.h"
+
+namespace ci {
+
+struct PlaceboBlocksArgs {
+  PlaceboArgs q;                   // q.p as PredBlocksArgs::p; q.series_of unused
+  BlockModel m;
+};
+
+// grid (ceil(N / (64 / G)), B), block 64.
+template <int G, int OUT>
+__global__ __launch_bounds__(64) void placebo_blocks_kernel(PlaceboBlocksArgs k) {
+  constexpr int FPW = 64 / G;
+  __shared__ PbShared sh;
+  const PredArgs& p = k.q.p;
+  const int N = p.N, T = p.T, NO = k.q.O;
+  const int n_own = blockIdx.x * FPW + (int)threadIdx.x / G;
+  const bool active = n_own < N;
+  const int n = active ? n_own : N - 1;
+  const size_t b = blockIdx.y, bn = b * N + n;
+  PbCtx c;
+  double H, a, P[G];
+  pb_begin<G>(p, k.m, sh, b, bn, c, H, a, P);
+  const bool writer = active && c.i == 0;
+  const double scale = p.scales[b], shift = p.shifts[b];
+  const float* y = p.y + b * T;
+  const uint8_t* mask = p.mask + b * T;
+  const double* reg = p.reg ? p.reg + b * T * N + n : nullptr;
+  double* out = p.out + b * NO * N + n;
+  const int* org = k.q.origins + b * NO;
+  const int Hb = k.q.horizon[b];
+
+  int slot = 0;
+  int next = org[0];                             // uniform over the wavefront, as everything of the origins
+  double unused = 0.0;
+  for (int t = 0; t < T && next >= 0; ++t) {
+    if (t == next) {
+      // the forecast branch, from a copy of the predicted moments
+      double fa = a, r = 0.0, fP[G];
+#pragma unroll
+      for (int j = 0; j < G; ++j) fP[j] = P[j];
+      double V = 0.0, C = 0.0, A = 0.0;
+      int cnt = 0;
+      for (int h = 0; h < Hb; ++h) {
+        const int u = t + h;
+        double pz, m, zpz;
+        pb_moments<G>(c, fa, fP, pz, m, zpz);
+        if (mask[u] == 0) {
+          c.xc[c.lane] = r;                      // (its last readers passed the barriers of pb_moments)
+          __syncthreads();
+          const double zr = pb_zsum(c, c.xc);
+          C += m + (reg ? reg[(size_t)u * N] : 0.0);
+          A += (double)y[u];
+          cnt += 1;
+          V += (2.0 * zr + zpz) + H;
+          r += pz;
+        }
+        if (h + 1 >= Hb) break;
+        pb_transition<G, true>(c, u, fa, r, fP);
+      }
+      double res = 0.0;
+      if (cnt > 0) {
+        const double err = A - C;
+        if (OUT == PLACEBO_SUM) res = __dadd_rn(__dmul_rn(C, scale), __dmul_rn((double)cnt, shift));
+        else if (OUT == PLACEBO_SPREAD) res = __dmul_rn(__dmul_rn(__dadd_rn(V, __dmul_rn(err, err)), scale), scale);
+        else if (OUT == PLACEBO_VAR) res = __dmul_rn(__dmul_rn(V, scale), scale);
+        else res = 0.5 * erfc(-err / sqrt(2.0 * V));
+      }
+      if (writer) out[(size_t)slot * N] = res;
+      ++slot;
+      next = slot < NO ? org[slot] : -1;
+      if (next < 0) break;
+    }
+    // the filter's step t (predict_blocks_kernel)
+    double pz, m, zpz;
+    pb_moments<G>(c, a, P, pz, m, zpz);
+    if (mask[t] == 0) {
+      const double F = zpz + H;
+      const double f = m + (reg ? reg[(size_t)t * N] : 0.0);
+      const double v = (double)y[t] - f;
+      pb_update<G>(c, a, P, pz, F, v);
+    }
+    if (t + 1 >= T) break;
+    pb_transition<G, false>(c, t, a, unused, P);
+  }
+  if (writer)
+    for (; slot < NO; ++slot) out[(size_t)slot * N] = 0.0;
+}
+
+}  // namespace ci

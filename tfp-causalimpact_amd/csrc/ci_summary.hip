@@ -12,8 +12,10 @@
 #include <vector>
 
 #include "ci_placebo.h"
+#include "ci_placebo_blocks.h"
 #include "ci_pool.h"
 #include "ci_predict.h"
+#include "ci_predict_blocks.h"
 #include "ci_session.h"
 #include "ci_summary.h"
 
@@ -140,6 +142,10 @@ hipError_t predict_launch(hipStream_t stream, int B, int has_slope, int num_seas
 // The launch of ci_placebo.hip (kernels: ci_placebo.h).
 hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
                           const PlaceboArgs& args);
+// The launches of ci_predict_blocks.hip and ci_placebo_blocks.hip (kernels: ci_predict_blocks.h,
+// ci_placebo_blocks.h).
+hipError_t predict_blocks_launch(hipStream_t stream, int B, int out, const PredBlocksArgs& args);
+hipError_t placebo_blocks_launch(hipStream_t stream, int B, int out, const PlaceboBlocksArgs& args);
 hipError_t placebo_pool_launch(hipStream_t stream, int N, int O, int G, int which, int c0, int c1,
                                const int* offsets, const double* weights, const double* M, double* acc);
 hipError_t placebo_finish_launch(hipStream_t stream, int N, size_t r0, size_t rows, int out,
@@ -766,6 +772,41 @@ static int pred_check_session(const ci_session* s, const char* who) {
   return 0;
 }
 
+// What ci_session_summarize_predictions_blocks and ci_session_summarize_placebo_blocks ask of a
+// session: not ragged, a state of at most 64 components, and a finished run.
+static int pred_blocks_check_session(const ci_session* s, const char* who) {
+  const ci_problem& pb = s->pb;
+  if (s->ragged)
+    return fail("%s takes no ragged session: their models (one block of 2 to 7 seasons at most) "
+                "belong to the entry without _blocks", who);
+  int d = 1 + (pb.has_slope ? 1 : 0);
+  for (int k = 0; k < pb.num_blocks; ++k) d += pb.num_seasons[k] - 1;
+  if (d > ci::PB_MAX_STATE) {
+    std::string blocks;
+    for (int k = 0; k < pb.num_blocks; ++k) blocks += (k ? ", " : "") + std::to_string(pb.num_seasons[k]);
+    return fail("%s takes a state of at most %d components, this session has %d with the blocks (%s)",
+                who, ci::PB_MAX_STATE, d, blocks.c_str());
+  }
+  if (!s->ran) return fail("%s needs a finished ci_session_run", who);
+  return 0;
+}
+
+// The block list of a session as the block-model filters read it.
+static ci::BlockModel pred_block_model(const ci_problem& pb) {
+  ci::BlockModel m = {};
+  m.has_slope = pb.has_slope ? 1 : 0;
+  m.K = pb.num_blocks;
+  m.d = 1 + m.has_slope;
+  m.zmask = 1ull;
+  for (int k = 0; k < m.K; ++k) {
+    m.off[k] = m.d;
+    m.ns[k] = pb.num_seasons[k];
+    m.zmask |= 1ull << m.d;
+    m.d += pb.num_seasons[k] - 1;
+  }
+  return m;
+}
+
 // On the device, once per session: per series the initial moments of its ci_series_params [B, 4],
 // then [B] times the 1.0 the regression term is scaled by.
 static int pred_init_upload(ci_session* s) {
@@ -784,13 +825,17 @@ static int pred_init_upload(ci_session* s) {
   return 0;
 }
 
-int ci_session_summarize_predictions(ci_session* s, const double* scale, const double* shift,
-                                     int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
-                                     double* forecast_order, double* variance_mean, double* pit_mean,
-                                     double* loglik) {
+// ci_session_summarize_predictions and, with `blocks`, ci_session_summarize_predictions_blocks: they
+// differ in the sessions they take and in the filter they launch, in nothing else.
+static int summarize_predictions(ci_session* s, bool blocks, const double* scale, const double* shift,
+                                 int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
+                                 double* forecast_order, double* variance_mean, double* pit_mean,
+                                 double* loglik) {
   if (!s || !scale || !shift || !ranks) return fail("NULL argument");
   const ci_problem& pb = s->pb;          // (not kpb: the inert block of a long trend-only series is no part of the model)
-  if (pred_check_session(s, "ci_session_summarize_predictions")) return 1;
+  if (blocks ? pred_blocks_check_session(s, "ci_session_summarize_predictions_blocks")
+             : pred_check_session(s, "ci_session_summarize_predictions"))
+    return 1;
   const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
   const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, R = num_ranks;
   if (check_ranks(R, ranks, N)) return 1;
@@ -818,10 +863,17 @@ int ci_session_summarize_predictions(ci_session* s, const double* scale, const d
   a.init = s->pred_init.p; a.scales = d_scale; a.shifts = d_shift;
   a.reg = P > 0 ? w.cum.p : nullptr;
   a.out = w.value.p;
+  ci::PredBlocksArgs ab;
+  if (blocks) ab.m = pred_block_model(pb);
   bool ll_pending = loglik != nullptr;
   auto pass = [&](int which, double* mean_dst, double* order_dst) -> int {
     a.ll = ll_pending ? w.draw.p : nullptr;
-    HIP_TRY(ci::predict_launch(stream, B, pb.has_slope, NS, which, a));
+    if (blocks) {
+      ab.p = a;
+      HIP_TRY(ci::predict_blocks_launch(stream, B, which, ab));
+    } else {
+      HIP_TRY(ci::predict_launch(stream, B, pb.has_slope, NS, which, a));
+    }
     if (mean_dst) HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * T, N, w.value.p, w.obs.p, nullptr));
     if (order_dst)
       HIP_TRY(launch_select(stream, N, T, B * T, R, w.ranks.p, w.value.p, nullptr, w.order.p, nullptr));
@@ -841,12 +893,31 @@ int ci_session_summarize_predictions(ci_session* s, const double* scale, const d
   return 0;
 }
 
-int ci_session_summarize_placebo(ci_session* s, const double* scale, const double* shift,
-                                 int32_t max_origins, const int32_t* origins, const int32_t* horizon,
-                                 double* predicted_mean, double* spread_mean, double* pit_mean) {
+int ci_session_summarize_predictions(ci_session* s, const double* scale, const double* shift,
+                                     int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
+                                     double* forecast_order, double* variance_mean, double* pit_mean,
+                                     double* loglik) {
+  return summarize_predictions(s, false, scale, shift, num_ranks, ranks, forecast_mean, forecast_order,
+                               variance_mean, pit_mean, loglik);
+}
+
+int ci_session_summarize_predictions_blocks(ci_session* s, const double* scale, const double* shift,
+                                            int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
+                                            double* forecast_order, double* variance_mean, double* pit_mean,
+                                            double* loglik) {
+  return summarize_predictions(s, true, scale, shift, num_ranks, ranks, forecast_mean, forecast_order,
+                               variance_mean, pit_mean, loglik);
+}
+
+// ci_session_summarize_placebo and, with `blocks`, ci_session_summarize_placebo_blocks, likewise.
+static int summarize_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
+                             int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                             double* predicted_mean, double* spread_mean, double* pit_mean) {
   if (!s || !scale || !shift || !origins || !horizon) return fail("NULL argument");
   const ci_problem& pb = s->pb;          // (not kpb: the inert block of a long trend-only series is no part of the model)
-  if (pred_check_session(s, "ci_session_summarize_placebo")) return 1;
+  if (blocks ? pred_blocks_check_session(s, "ci_session_summarize_placebo_blocks")
+             : pred_check_session(s, "ci_session_summarize_placebo"))
+    return 1;
   const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
   const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins;
   if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
@@ -893,8 +964,11 @@ int ci_session_summarize_placebo(ci_session* s, const double* scale, const doubl
   a.p.reg = P > 0 ? w.cum.p : nullptr;
   a.p.out = w.value.p; a.p.ll = nullptr;
   a.O = O; a.origins = d_plan.p; a.horizon = d_plan.p + (size_t)B * O;
+  ci::PlaceboBlocksArgs ab;
+  if (blocks) { ab.q = a; ab.m = pred_block_model(pb); }
   auto pass = [&](int which, double* mean_dst) -> int {
-    HIP_TRY(ci::placebo_launch(stream, B, pb.has_slope, NS, which, a));
+    if (blocks) HIP_TRY(ci::placebo_blocks_launch(stream, B, which, ab));
+    else HIP_TRY(ci::placebo_launch(stream, B, pb.has_slope, NS, which, a));
     HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * O, N, w.value.p, w.obs.p, nullptr));
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(hipMemcpy(mean_dst, w.obs.p, (size_t)B * O * sizeof(double), hipMemcpyDeviceToHost));
@@ -905,6 +979,20 @@ int ci_session_summarize_placebo(ci_session* s, const double* scale, const doubl
   if (pit_mean && pass(ci::PLACEBO_PIT, pit_mean)) return 1;
   HIP_TRY(hipStreamSynchronize(stream));   // (the uploads of a call that asks for nothing)
   return 0;
+}
+
+int ci_session_summarize_placebo(ci_session* s, const double* scale, const double* shift,
+                                 int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                 double* predicted_mean, double* spread_mean, double* pit_mean) {
+  return summarize_placebo(s, false, scale, shift, max_origins, origins, horizon, predicted_mean, spread_mean,
+                           pit_mean);
+}
+
+int ci_session_summarize_placebo_blocks(ci_session* s, const double* scale, const double* shift,
+                                        int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                        double* predicted_mean, double* spread_mean, double* pit_mean) {
+  return summarize_placebo(s, true, scale, shift, max_origins, origins, horizon, predicted_mean, spread_mean,
+                           pit_mean);
 }
 
 // The placebo forecasts of POOLED sums: per group, slot and draw the weighted sum S of the members'
