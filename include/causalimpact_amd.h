@@ -446,6 +446,65 @@ int ci_session_summarize_predictions_blocks(ci_session* session, const double* s
 int ci_session_summarize_placebo_blocks(ci_session* session, const double* scale, const double* shift,
                                         int32_t max_origins, const int32_t* origins, const int32_t* horizon,
                                         double* predicted_mean, double* spread_mean, double* pit_mean);
+/* SIMULATED PLACEBO FORECASTS: the placebo check for fits under an outcome link (CI_LINK_LOG,
+ * CI_LINK_LOG1P), and an independent check of the analytic one under the identity.  Additive:
+ * CI_ABI_VERSION stays 5; look the symbols up (dlsym) where an older library may be met.  Under a
+ * link the window's total is a sum of exp's of jointly Gaussian values and has no closed form, so
+ * for every pooled draw ONE path of the window is drawn from that draw's predictive, linked step by
+ * step and summed: N simulated totals per window.  Fixed parameters, as the analytic placebo.
+ * Series b, pooled draw n = c * S + s (chain c of the session, kept draw s, S = num_results), origin
+ * slot i with origin o, horizon H_b, o + H_b <= T_b.  The model, Z, T_t, Q_t, reg[n, t], the initial
+ * moments and the filter are those of ci_session_summarize_placebo (of .._blocks for the block
+ * models).  By the chain rule y_{o+h} given the simulated y_o .. y_{o+h-1} is N(f_h, F_h) of a
+ * filter that is updated with the simulated values:
+ *   run the filter over t = 0 .. o - 1: (a, P) are the predicted moments of x_o
+ *   copy (a, P);  S = 0.0;  cnt = 0
+ *   for h = 0 .. H_b - 1, u = o + h:
+ *     pz = P Z';  m = Z a;  F = Z pz + sigma_obs^2;  f = m + reg[n, u]     (sums in the filters' order)
+ *     if mask[b, u] == 0:
+ *       z    = normal_d(key_b, chain = chain_offset + c, iter = s, site = SITE_PLACEBO_SIM, sub = i, idx = h)
+ *       v    = sqrt(F) * z;   ysim = f + v                  (one rounding each)
+ *       S   += link(ysim * scale[b] + shift[b])             (two roundings, no FMA, as ci_session_set_link)
+ *       cnt += 1
+ *       a += (pz / F) v;   P -= pz pz' / F                  (the filter's own update, with the simulated innovation)
+ *     if h + 1 < H_b:  a = T_u a;  P = T_u P T_u' + Q_u
+ *   TOTAL[b, i, n] = S   (0.0 where cnt == 0 or the slot is unused)
+ * key_b is the Philox key the fit of series b ran on: ci_series_stream_key of the series' id (its
+ * series_ids entry in a ragged session, else series_offset + b), or the seed itself under
+ * CI_FLAG_SHARED_SERIES_STREAMS.  normal_d is the float64 Box-Muller normal of the specified stream
+ * (Philox4x32-10, counter (idx >> 2, site | sub << 8, iter, chain), component idx & 3);
+ * SITE_PLACEBO_SIM = 18 is a site of its own: the stream of every other site is untouched.  idx is h
+ * whether or not the step is counted -- a masked step leaves its normal unused.  The filter outside
+ * the branch goes on from the untouched (a, P).
+ * link: a CI_LINK_* value, passed explicitly -- ci_session_set_link is neither read nor changed.
+ * seen [B, O] (host, data scale): the observed total of every window; may be NULL when neither
+ * spread_mean nor below is asked for.  ranks: num_ranks (1..8) 0-based order statistics over the N
+ * draws.  Outputs (host, caller-allocated, float64; each may be NULL and is then skipped):
+ *   predicted_mean [B, O]        the mean over n of TOTAL
+ *   spread_mean    [B, O]        the mean over n of (TOTAL - seen)^2, one rounding per operation
+ *   below          [B, O]        #{n : TOTAL <= seen}, the exact integer count as a double
+ *   total_order    [B, num_ranks, O]   the order statistics of TOTAL over n
+ *   totals         [B, O, N]     TOTAL itself (tests, and callers that want the draws)
+ * all 0 where cnt == 0 or the slot is unused.  A mean is that of ci_session_summarize_components:
+ * lane l of 64 adds the values n = l, l + 64, .. ascending from 0.0, the 64 sums are combined by a
+ * butterfly (partners 32, 16, .., 1 apart), and the result is divided by N.
+ * The filter runs once per call: the totals are simulated into the scratch of ci_session_summarize,
+ * reduced, downloaded if wanted, and rewritten in place to the squares.  TOTAL depends on (b, i, n)
+ * alone -- not on the launch geometry, nor on how a batch is cut into sessions as long as the
+ * series keep their ids and the chains their global ids.
+ * Checked before any device call: as ci_session_summarize_placebo (.._blocks), and link in range,
+ * num_ranks in [1, 8], ranks in [0, N), seen not NULL unless only predicted_mean, total_order and
+ * totals are asked for. */
+int ci_session_simulate_placebo(ci_session* session, const double* scale, const double* shift,
+                                int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                int32_t link, const double* seen, int32_t num_ranks, const int32_t* ranks,
+                                double* predicted_mean, double* spread_mean, double* below,
+                                double* total_order, double* totals);
+int ci_session_simulate_placebo_blocks(ci_session* session, const double* scale, const double* shift,
+                                       int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                       int32_t link, const double* seen, int32_t num_ranks,
+                                       const int32_t* ranks, double* predicted_mean, double* spread_mean,
+                                       double* below, double* total_order, double* totals);
 /* PLACEBO FORECASTS OF POOLED SUMS: the forecasts above, added over groups of series draw by draw --
  * the placebo check of a pooled effect.  Additive: CI_ABI_VERSION stays 5; look the symbol up (dlsym)
  * where an older library may be met.
@@ -925,6 +984,15 @@ int ci_test_summarize_draw_paths_f64(int32_t device, int32_t num_groups, int32_t
                                      double* excursion_order, double* observed_excursion,
                                      int32_t* at, int32_t* exceed, int64_t max_bytes,
                                      int32_t* num_chunks);
+/* ci_session_simulate_placebo (blocks == 0) or ci_session_simulate_placebo_blocks (blocks != 0) with
+ * the rows of a chunk handed in (max_rows in place of the scratch's B * T; 0: that default; at least
+ * max_origins) and the number of chunks it took written to num_chunks (may be NULL), likewise. */
+int ci_test_session_simulate_placebo(ci_session* session, int32_t blocks, const double* scale,
+                                     const double* shift, int32_t max_origins, const int32_t* origins,
+                                     const int32_t* horizon, int32_t link, const double* seen,
+                                     int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
+                                     double* spread_mean, double* below, double* total_order,
+                                     double* totals, int64_t max_rows, int32_t* num_chunks);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,9 @@ COMPONENT_OUTPUTS = ("trend_mean", "trend_order", "seasonal_mean", "seasonal_ord
 PREDICTION_OUTPUTS = ("forecast_mean", "forecast_order", "variance_mean", "pit_mean", "loglik")
 # the output arrays of ci_session_summarize_placebo, in argument order
 PLACEBO_OUTPUTS = ("predicted_mean", "spread_mean", "pit_mean")
+# the output arrays of ci_session_simulate_placebo, in argument order
+PLACEBO_SIM_OUTPUTS = ("predicted_mean", "spread_mean", "below", "total_order", "totals")
+SITE_PLACEBO_SIM = 18   # == ci::SITE_PLACEBO_SIM (csrc/ci_rng.h)
 # the outcome link of a session's summaries (== CI_LINK_*): value = z, exp(z), expm1(z)
 LINK_IDENTITY, LINK_LOG, LINK_LOG1P = 0, 1, 2
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -132,6 +135,14 @@ def load():
   if hasattr(L, "ci_session_summarize_placebo_blocks"):       # (additive, likewise)
     L.ci_session_summarize_placebo_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                       C.c_void_p, C.c_void_p] + [C.c_void_p] * 3
+  for name in ("ci_session_simulate_placebo", "ci_session_simulate_placebo_blocks",
+               "ci_test_session_simulate_placebo"):
+    if hasattr(L, name):                               # (additive, likewise)
+      test = name.startswith("ci_test_")
+      getattr(L, name).argtypes = ([C.c_void_p] + ([C.c_int32] if test else []) +
+                                   [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.c_int32, C.c_void_p] + [C.c_void_p] * 5 +
+                                   ([C.c_int64, C.c_void_p] if test else []))
   if hasattr(L, "ci_session_pool_placebo"):            # (additive, likewise)
     L.ci_session_pool_placebo.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 +
                                           [C.c_int32] + [C.c_void_p] * 8)
@@ -224,6 +235,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_summarize_paths", "ci_ll_session_summarize_paths",
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
           "ci_session_pool_event_trajectories", "ci_session_pool_placebo",
+          "ci_session_simulate_placebo", "ci_session_simulate_placebo_blocks",
           "ci_session_set_link", "ci_session_value_mean",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
           "ci_ll_session_draw_latents", "ci_ll_session_hmc_run", "ci_ll_session_hmc_fetch",
@@ -232,7 +244,8 @@ def exported_symbols() -> Sequence[str]:
           "ci_comm_unique_id", "ci_comm_create", "ci_comm_info", "ci_comm_set_timeout", "ci_comm_barrier",
           "ci_comm_all_reduce", "ci_comm_all_gather", "ci_comm_session_all_gather",
           "ci_comm_ll_session_all_gather", "ci_comm_destroy", "ci_test_rng",
-          "ci_test_dk_draw", "ci_test_session_summarize_paths", "ci_test_summarize_draw_paths_f64")
+          "ci_test_dk_draw", "ci_test_session_summarize_paths", "ci_test_summarize_draw_paths_f64",
+          "ci_test_session_simulate_placebo")
 
 
 def _check(rc: int):
@@ -416,6 +429,59 @@ def _entry_csr(groups, num_series: int):
   if isinstance(groups, tuple) and len(groups) == 3 and isinstance(groups[0], np.ndarray):
     return groups
   return groups_csr(groups, num_series)
+
+
+def philox4x32_10_host(counter, key) -> np.ndarray:
+  """Philox4x32-10 of csrc/ci_rng.h in numpy: counter [..., 4] and key [..., 2] (broadcast against
+  each other over the leading axes), unsigned 32-bit words; returns the four output words [..., 4]
+  as uint32."""
+  ctr = np.asarray(counter, np.uint64) & np.uint64(0xFFFFFFFF)
+  k = np.asarray(key, np.uint64) & np.uint64(0xFFFFFFFF)
+  shape = np.broadcast_shapes(ctr.shape[:-1], k.shape[:-1])
+  c0, c1, c2, c3 = (np.broadcast_to(ctr[..., i], shape).copy() for i in range(4))
+  k0, k1 = (np.broadcast_to(k[..., i], shape).copy() for i in range(2))
+  m32, sh32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+  for _ in range(10):
+    p0 = np.uint64(0xD2511F53) * c0
+    p1 = np.uint64(0xCD9E8D57) * c2
+    c0, c1, c2, c3 = (p1 >> sh32) ^ c1 ^ k0, p1 & m32, (p0 >> sh32) ^ c3 ^ k1, p0 & m32
+    k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+  return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def normals_host(key, chain, iteration, site: int, sub, idx) -> np.ndarray:
+  """`normal_d` of csrc/ci_rng.h in vectorised numpy: the float64 Box-Muller normal of element `idx`
+  of (site, sub) in iteration `iteration` of chain `chain` under the Philox key `key` (k0, k1) --
+  counter (idx >> 2, site | sub << 8, iteration, chain), component idx & 3.  chain, iteration, sub
+  and idx broadcast against each other.  The angle is 2 pi rev through cos and sin, as the oracle
+  takes it (the device uses sincospi: the same value to a few ulp)."""
+  chain, iteration, sub, idx = np.broadcast_arrays(*(np.asarray(v, np.uint64) for v in (chain, iteration, sub, idx)))
+  counter = np.stack([idx >> np.uint64(2), np.uint64(int(site)) | (sub << np.uint64(8)), iteration, chain], axis=-1)
+  words = philox4x32_10_host(counter, np.asarray([int(key[0]), int(key[1])], np.uint64)).astype(np.float64)
+  hi = (idx & np.uint64(2)) != 0
+  ra = np.where(hi, words[..., 2], words[..., 0])
+  rb = np.where(hi, words[..., 3], words[..., 1])
+  u1 = (ra + 0.5) * (1.0 / 4294967296.0)
+  rev = rb * (1.0 / 4294967296.0)
+  rad = np.sqrt(-2.0 * np.log(u1))
+  angle = (2.0 * np.pi) * rev
+  return np.where((idx & np.uint64(1)) != 0, rad * np.sin(angle), rad * np.cos(angle))
+
+
+def row_means_host(M) -> np.ndarray:
+  """The mean of every row of M [..., N] as the row-statistics kernel takes it
+  (csrc/ci_components.h): lane l of 64 adds the values l, l + 64, .. ascending from 0.0, the 64 sums
+  are combined by a butterfly (partners 32, 16, .., 1 apart), and the result is divided by N."""
+  M = np.asarray(M, np.float64)
+  N = M.shape[-1]
+  pad = (-N) % 64
+  padded = np.concatenate([M, np.zeros(M.shape[:-1] + (pad,))], axis=-1) if pad else M
+  lanes = np.zeros(M.shape[:-1] + (64,))
+  for chunk in range(padded.shape[-1] // 64):                     # (a padded 0.0 leaves a sum unchanged)
+    lanes = lanes + padded[..., 64 * chunk:64 * chunk + 64]
+  for off in (32, 16, 8, 4, 2, 1):
+    lanes = lanes + lanes[..., np.arange(64) ^ off]
+  return lanes[..., 0] / np.float64(N)
 
 
 def placebo_terms_host(mean, variance, counted, scale, shift):
@@ -1106,6 +1172,80 @@ class Session:
     sessions stay with `summarize_placebo`."""
     return self.summarize_placebo(scale, shift, origins, horizon, want,
                                   _entry="ci_session_summarize_placebo_blocks")
+
+  def simulate_placebo(self, scale, shift, origins, horizon, link, seen, ranks, want=None,
+                       blocks: bool = False, max_rows=None) -> Dict[str, np.ndarray]:
+    """On-device SIMULATED placebo forecasts of every fit (ci_session_simulate_placebo): for every
+    pooled draw the filter of `summarize_placebo` up to each origin, then ONE simulated path of the
+    window -- the filter's own step fed with a draw from its own forecast -- linked step by step and
+    summed (`causalimpact_lib._placebo_simulated_host` is the same definition in numpy).  scale,
+    shift, origins, horizon: as for `summarize_placebo`; link: a `LINK_*`, passed explicitly (the
+    session's `set_link` is neither read nor changed); seen [B, O]: the observed totals on the data
+    scale (None: neither spread_mean nor below can be asked for); ranks: 1 to 8 order statistics.
+    Returns float64 arrays: predicted_mean, spread_mean, below [B, O], total_order [B, R, O], totals
+    [B, O, N] (0 in the unused slots and where the window counts no observation).  `want`: the names
+    to compute (default: all but `totals`, and without `seen` those that need none).  max_rows
+    (tests): the rows of a chunk in place of the scratch's (ci_test_session_simulate_placebo); the
+    result then has "num_chunks" too."""
+    if max_rows is not None:
+      name = "ci_test_session_simulate_placebo"
+    else:
+      name = "ci_session_simulate_placebo_blocks" if blocks else "ci_session_simulate_placebo"
+    fn = getattr(self._lib, name, None)
+    if fn is None:
+      raise NativeError(f"the loaded library has no {name}: rebuild it")
+    pb = self.pb
+    B, N = pb.num_series, pb.num_chains * pb.num_results
+    org = np.asarray(origins)
+    if org.ndim == 1 and B == 1:
+      org = org[None]
+    if org.ndim != 2 or org.shape[0] != B:
+      raise ValueError(f"`origins` must be [{B}, O], got shape {org.shape}")
+    org = np.ascontiguousarray(org, dtype=np.int32)
+    O = int(org.shape[1])
+    hz = np.asarray(horizon)
+    if hz.shape not in ((), (B,)):
+      raise ValueError(f"`horizon` must be a scalar or have one entry per series ({B}), got shape {hz.shape}")
+    hz = np.ascontiguousarray(np.broadcast_to(hz, (B,)), dtype=np.int32)
+    sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
+    for what, a in (("scale", sc), ("shift", sh)):
+      if a.shape not in ((), (B,)):
+        raise ValueError(f"`{what}` must be a scalar or have one entry per series ({B}), got shape {a.shape}")
+    sc = np.ascontiguousarray(np.broadcast_to(sc, (B,)))
+    sh = np.ascontiguousarray(np.broadcast_to(sh, (B,)))
+    rk = np.ascontiguousarray(ranks, dtype=np.int32).reshape(-1)
+    if seen is not None:
+      seen = np.asarray(seen, np.float64)
+      if seen.ndim == 1 and B == 1:
+        seen = seen[None]
+      if seen.shape != org.shape:
+        raise ValueError(f"`seen` must be {list(org.shape)}, got {list(seen.shape)}")
+      seen = np.ascontiguousarray(seen)
+    shapes = dict(predicted_mean=(B, O), spread_mean=(B, O), below=(B, O), total_order=(B, rk.size, O),
+                  totals=(B, O, N))
+    if want is None:
+      want = [k for k in PLACEBO_SIM_OUTPUTS
+              if k != "totals" and (seen is not None or k not in ("spread_mean", "below"))]
+    unknown = [k for k in want if k not in PLACEBO_SIM_OUTPUTS]
+    if unknown:
+      raise ValueError(f"unknown simulated placebo outputs {unknown}: choose from {list(PLACEBO_SIM_OUTPUTS)}")
+    arrs = {k: np.empty(shapes[k], np.float64) for k in PLACEBO_SIM_OUTPUTS if k in want}
+    chunks = C.c_int32(0)
+    _check(fn(self._h, *((int(bool(blocks)),) if max_rows is not None else ()),
+              sc.ctypes.data, sh.ctypes.data, O, org.ctypes.data, hz.ctypes.data, int(link), _ptr(seen),
+              int(rk.size), rk.ctypes.data, *[_ptr(arrs.get(k)) for k in PLACEBO_SIM_OUTPUTS],
+              *((int(max_rows), C.addressof(chunks)) if max_rows is not None else ())))
+    if max_rows is not None:
+      arrs["num_chunks"] = chunks.value
+    return arrs
+
+  def simulate_placebo_blocks(self, scale, shift, origins, horizon, link, seen, ranks, want=None,
+                              max_rows=None) -> Dict[str, np.ndarray]:
+    """`simulate_placebo` for any block list whose state has at most 64 components
+    (ci_session_simulate_placebo_blocks): same arguments, same outputs.  Ragged sessions stay with
+    `simulate_placebo`."""
+    return self.simulate_placebo(scale, shift, origins, horizon, link, seen, ranks, want, blocks=True,
+                                 max_rows=max_rows)
 
   def summarize_windows(self, scale, shift, observed, first, count, ranks,
                         want_draws=True) -> Dict[str, np.ndarray]:

@@ -362,7 +362,8 @@ _KINDS = dict(lib.SUMMARY_KINDS, fetched=lib.SummaryKind(_DRAW_SCALARS, 0))
 
 def _cut(arrays: Dict[str, np.ndarray], num_steps: int, kind: str) -> Dict[str, np.ndarray]:
   """`arrays` of `kind` with the time (last) axis cut to `num_steps`."""
-  return {k: (v if k in _KINDS[kind].whole else v[..., :num_steps]) for k, v in arrays.items()}
+  whole = _KINDS[kind].whole + _KINDS[kind].also
+  return {k: (v if k in whole else v[..., :num_steps]) for k, v in arrays.items()}
 
 
 class CausalImpactBatchAnalysis:
@@ -1844,6 +1845,8 @@ class _Fit:
   # and horizon [B] (`placebo_plans`); the summary is put on the data scale with own_scale / own_shift
   placebo_origins: Optional[np.ndarray] = None
   placebo_horizon: Optional[np.ndarray] = None
+  # `Placebo(simulate=True)` only: the (lower, upper) quantiles of the simulated totals the frames report
+  placebo_quantiles: Optional[Tuple[float, float]] = None
   # `joint_bands=True` only: every series' windows of `summarize_paths` [B, 1 + W] (`lib.joint_windows`:
   # window 0 its post-period) and the order statistics of the excursions
   paths: Optional[lib.Windows] = None
@@ -1860,7 +1863,7 @@ def _sampler_outcome(prep, data_options) -> np.ndarray:
 
 def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_options,
              shared_streams, windows: Optional[WindowPlan] = None, placebo=None,
-             joint_bands: bool = False) -> _Fit:
+             joint_bands: bool = False, placebo_simulate: bool = False) -> _Fit:
   """The `_Fit` of a prepared batch or panel: y = `_sampler_outcome(prep)`, lengths [B], pre_sd [B]
   the sd of every series' own pre-period outcome; placebo: (origins [B, O], horizon [B]) or None."""
   own_shift = own_scale = None
@@ -1891,7 +1894,9 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
               model_options=model_options, inference_options=inference_options,
               own_scale=own_scale, own_shift=own_shift, windows=windows,
               placebo_origins=None if placebo is None else placebo[0],
-              placebo_horizon=None if placebo is None else placebo[1], paths=paths,
+              placebo_horizon=None if placebo is None else placebo[1],
+              placebo_quantiles=(alpha / 2.0, 1.0 - alpha / 2.0) if placebo is not None and placebo_simulate else None,
+              paths=paths,
               path_ranks=lib._path_ranks(num_draws, alpha) if joint_bands else (),   # pylint: disable=protected-access
               link=prep.link)
 
@@ -1981,12 +1986,17 @@ def _launch_request(fit: _Fit, ids, observed, flags) -> lib.SummaryRequest:
   io, own = fit.inference_options, None
   if fit.own_scale is not None:
     own = lib.Affine(fit.own_scale[ids], fit.own_shift[ids])
+  simulated = {}
+  if fit.placebo_quantiles is not None:
+    # (every series on the key its fit runs on, the chains of a launch being all of its chains)
+    simulated = dict(quantiles=fit.placebo_quantiles, link=fit.link, streams=[
+        lib.placebo_stream(fit.seed, None if fit.shared_streams else int(b), range(io.num_chains)) for b in ids])
   return lib.SummaryRequest(
       scale=fit.scale[ids], shift=fit.shift[ids], observed=observed, flags=flags, ranks=fit.ranks,
       components=io.components, predictions=own if io.prediction_errors else None,
       windows=None if fit.windows is None else lib.Windows(fit.windows.first[ids], fit.windows.count[ids]),
       placebo=None if fit.placebo_origins is None else lib.PlaceboPart(
-          *own, fit.placebo_origins[ids], fit.placebo_horizon[ids]),
+          *own, fit.placebo_origins[ids], fit.placebo_horizon[ids], **simulated),
       paths=None if fit.paths is None else lib.Windows(fit.paths.first[ids], fit.paths.count[ids]),
       path_ranks=fit.path_ranks, link=fit.link)
 
@@ -2037,7 +2047,7 @@ def _scatter(parts, num_series: int, num_steps: int, kind: str) -> Dict[str, np.
   """{name: [num_series, ...]} of parts = [(positions, {name: [len(positions), ...]})], arrays of
   `kind`: those over time (last axis) are padded from a launch's stride to `num_steps` with the
   kind's fill."""
-  whole, fill = _KINDS[kind]
+  whole, fill = _KINDS[kind].whole + _KINDS[kind].also, _KINDS[kind].fill
   out = {k: (np.zeros((num_series,) + v.shape[1:], v.dtype) if k in whole else
              np.full((num_series,) + v.shape[1:-1] + (num_steps,), fill, v.dtype))
          for k, v in parts[0][1].items()}
@@ -2201,14 +2211,15 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   series by series apply `_native.link_values_host` in numpy.  A one-launch HMC batch asked for a link
   takes the per-series route (as with `components=True`).  ValueError before any fit, the series and
   the label named, for a value outside the link's domain on a row a model conditions on.
-  `components` and `prediction_errors` stay on the transformed scale; `placebo=` is refused.
+  `components` and `prediction_errors` stay on the transformed scale; the analytic `placebo=` is refused,
+  `placebo=Placebo(simulate=True)` runs the simulated placebo (not together with `aggregates`).
   """
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
   link = lib.resolve_outcome_link(outcome_link)
-  if link and placebo is not None and placebo is not False:
-    raise ValueError(lib._LINK_PLACEBO_REFUSAL)                  # pylint: disable=protected-access
+  lib.check_link_placebo(link, placebo)
   placebo = lib.resolve_placebo(placebo)
+  lib.check_simulated_placebo_pool(placebo, None if aggregates is None else "aggregates")
   pl_dim = None if placebo is None else lib.placebo_state_dim(model_options.local_linear_trend,
                                                               model_options.seasons)
   if isinstance(data, np.ndarray):
@@ -2281,7 +2292,7 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   with np.errstate(invalid="ignore"):
     pre_sd = np.nanstd(y[:, :prep.num_pre], axis=1, ddof=1)
   fit = _new_fit(prep, y, np.full(B, T), pre_sd, alpha, seed, model_options, inference_options,
-                 shared_streams, plan, pl_plan, joint_bands)
+                 shared_streams, plan, pl_plan, joint_bands, placebo is not None and placebo.simulate)
   # a batch is the panel of one group of equal lengths: consecutive positions on every device
   launches = panel_launches(dict(route="equal_length", groups=[(T, list(range(B)))]),
                             inference_options.devices, shared_streams)
@@ -2442,13 +2453,14 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   by the summary and pool kernels of every ragged launch; panels fitted series by series in numpy.
   ValueError before any fit, the series and the label named, for a value outside the link's domain on
   a row its model conditions on.  `components` and `prediction_errors` stay on the transformed scale;
-  `placebo=` is refused."""
+  the analytic `placebo=` is refused; `placebo=Placebo(simulate=True)` runs the simulated placebo (not
+  together with `event_aggregates`)."""
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
   link = lib.resolve_outcome_link(outcome_link)
-  if link and placebo is not None and placebo is not False:
-    raise ValueError(lib._LINK_PLACEBO_REFUSAL)                  # pylint: disable=protected-access
+  lib.check_link_placebo(link, placebo)
   placebo = lib.resolve_placebo(placebo)
+  lib.check_simulated_placebo_pool(placebo, None if event_aggregates is None else "event_aggregates")
   pl_dim = None if placebo is None else lib.placebo_state_dim(model_options.local_linear_trend,
                                                               model_options.seasons)
   frames, columns = _frames_outcome_first(data, data_options)
@@ -2509,7 +2521,7 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   with np.errstate(invalid="ignore"):
     pre_sd = [np.nanstd(y[b, :nb], ddof=1) for b, nb in enumerate(prep.num_pre)]
   fit = _new_fit(prep, y, prep.lengths, pre_sd, alpha, seed, model_options, inference_options,
-                 shared_streams, wplan, pl_plan, joint_bands)
+                 shared_streams, wplan, pl_plan, joint_bands, placebo is not None and placebo.simulate)
   kind = "ordinary" if route["route"] == "equal_length" else route["route"]
   launches = panel_launches(route, inference_options.devices, shared_streams)
   chain = None if plan is None else _PoolChain(launches, plan.csr, plan.axes)

@@ -260,8 +260,9 @@ def fit_causalimpact(data: pd.DataFrame,
   or y > -1 (log1p): ValueError before any fit, the first offending label named; a post-period value
   outside the domain (sales driven to 0) is a missing value to the model's copy alone.
   `components=True` and `prediction_errors=True` describe the model, which is Gaussian on the
-  TRANSFORMED scale: they are reported there.  `placebo=` with a link is refused (ValueError): a sum
-  of lognormals has no closed-form variance.
+  TRANSFORMED scale: they are reported there.  The analytic `placebo=` with a link is refused
+  (ValueError): a sum of lognormals has no closed-form variance; `placebo=Placebo(simulate=True)` runs
+  the simulated placebo instead (see `Placebo`).
 
   effect_windows (extension): {name: (start, end)}, sub-windows of the post-period given as labels
   on the index, both ends inclusive, parsed and aligned exactly as `post_period` is.  The result then
@@ -285,7 +286,10 @@ def fit_causalimpact(data: pd.DataFrame,
   more than one seasonal block or a block of more than 7 seasons), in numpy from the
   parameter draws on the other routes, exactly as `InferenceOptions.prediction_errors`.  ValueError
   before any fit when the pre-period has no room for one origin, or the state has more than
-  `PREDICTION_MAX_STATE` components.
+  `PREDICTION_MAX_STATE` components.  `Placebo(simulate=True)`: the simulated placebo -- one path of
+  every window per draw, the link applied step by step, band and `p` from the N totals
+  (csrc/ci_placebo.h `placebo_sim_kernel`; `_placebo_simulated_host` on the other routes); the frame
+  gains `predicted_lower` and `predicted_upper`.
 
   joint_bands (extension): False (the default: nothing runs, no result differs) or True.  The bands
   of `series` are pointwise: over a long post-period the observed series leaves them at several steps
@@ -319,8 +323,7 @@ def fit_causalimpact(data: pd.DataFrame,
         "experimental_model takes a tfp.sts.StructuralTimeSeries; this build has no TFP. Use "
         "ModelOptions(local_linear_trend=..., seasons=...) instead.")
   link = resolve_outcome_link(outcome_link)
-  if link and placebo is not None and placebo is not False:
-    raise ValueError(_LINK_PLACEBO_REFUSAL)
+  check_link_placebo(link, placebo)
   raw_data = None
   if link:
     raw_data, data = data, link_outcome(data, pre_period, post_period, data_options.outcome_column, link)
@@ -356,6 +359,13 @@ def fit_causalimpact(data: pd.DataFrame,
                        f"horizon {horizon} and the history it needs")
     if origins.size:
       placebo_part = PlaceboPart(base["scale"], base["shift"], origins, horizon)
+      if placebo.simulate:
+        # (the simulation draws from the fit's own streams: a seed of None is settled here, once;
+        #  one device or several, the chains are pooled in the order of their global ids)
+        seed = _sanitize_seed(seed)
+        placebo_part = placebo_part._replace(
+            quantiles=base["quantiles"], link=link,
+            streams=placebo_stream(seed, None, range(inference_options.num_chains)))
   num_draws = inference_options.num_chains * inference_options.num_results
   ranks = _summary_ranks(num_draws, base["quantiles"])
   path_windows = None
@@ -455,7 +465,8 @@ def fit_causalimpact(data: pd.DataFrame,
 OUTCOME_LINKS = {None: _native.LINK_IDENTITY, "log": _native.LINK_LOG, "log1p": _native.LINK_LOG1P}
 _LINK_PLACEBO_REFUSAL = ("`placebo=` is not available with `outcome_link`: the placebo forecasts are "
                          "Gaussian on the transformed scale, and a sum of lognormals has no closed-form "
-                         "variance")
+                         "variance; `placebo=Placebo(simulate=True)` runs the simulated placebo instead, "
+                         "whose band and p-value come from one simulated path of every window per draw")
 
 
 def resolve_outcome_link(outcome_link) -> int:
@@ -836,15 +847,25 @@ class Placebo:
                  (the post-period's own length wherever the pre-period is three times as long);
     max_origins  the most origins per series, spread evenly over the admissible ones;
     min_history  the first admissible origin (steps of history before it); None: max(horizon,
-                 state dimension + 1).
+                 state dimension + 1);
+    simulate     False (the default): the exact Gaussian moments of every window's sum.  True: the
+                 SIMULATED placebo -- for every posterior draw one path of the window is drawn from
+                 that draw's predictive, the outcome link applied step by step and the values summed;
+                 band, `p` and `significant` come from the N simulated totals, and the frame gains
+                 `predicted_lower` / `predicted_upper`.  The only placebo under `outcome_link`, where
+                 a window's total has no closed-form distribution; under the identity an independent
+                 check of the analytic one.  The Monte-Carlo floor of `p` is 1 / (N + 1).
   Fixed-parameter: every draw's scales and weights are those of the one fit of the whole pre-period,
   so the check is cheap and somewhat optimistic; the windows overlap, so the origins are not
   independent trials."""
   horizon: Optional[int] = None
   max_origins: int = 32
   min_history: Optional[int] = None
+  simulate: bool = False
 
   def __post_init__(self):
+    if not isinstance(self.simulate, (bool, np.bool_)):
+      raise TypeError(f"Placebo.simulate must be True or False, got {self.simulate!r}")
     if self.horizon is not None and int(self.horizon) < 1:
       raise ValueError(f"Placebo.horizon must be at least 1, got {self.horizon}")
     if int(self.max_origins) < 1:
@@ -862,6 +883,23 @@ def resolve_placebo(placebo) -> Optional[Placebo]:
   if isinstance(placebo, Placebo):
     return placebo
   raise TypeError(f"`placebo` must be None, True or a Placebo, got {placebo!r}")
+
+
+def check_link_placebo(link: int, placebo) -> None:
+  """`placebo=` under an outcome link runs only as the simulated placebo: ValueError
+  (`_LINK_PLACEBO_REFUSAL`) for True or a `Placebo` without `simulate`, before anything is fitted."""
+  if link and placebo is not None and placebo is not False and not (
+      isinstance(placebo, Placebo) and placebo.simulate):
+    raise ValueError(_LINK_PLACEBO_REFUSAL)
+
+
+def check_simulated_placebo_pool(placebo: Optional[Placebo], argument: Optional[str]) -> None:
+  """The simulated placebo has no pooled form: ValueError naming `argument` ("aggregates",
+  "event_aggregates"; None: no pooled effects were asked for), before anything is fitted."""
+  if placebo is not None and placebo.simulate and argument is not None:
+    raise ValueError(f"`{argument}` cannot be combined with `Placebo(simulate=True)`: the pooled placebo "
+                     "forecasts add the members' exact Gaussian moments, and a simulated pooled placebo is "
+                     "not available; use `Placebo()` (without `outcome_link`) for the pooled check")
 
 
 def placebo_horizon(placebo: Placebo, n_pre: int, n_post: int) -> int:
@@ -906,125 +944,216 @@ def placebo_state_dim(local_linear_trend: bool, seasons: Sequence) -> int:
   return d
 
 
+class _PlaceboFilter:
+  """The filter the placebo forecasts of one series start from, in numpy, from the pooled PARAMETER
+  draws alone: that of `_prediction_summary_host` (whose arguments the first eight are), for any
+  block list of up to `PREDICTION_MAX_STATE` state components.  origins [O]: steps, strictly ascending
+  (-1: an unused slot, at the end); horizon: steps per window, origin + horizon <= T.  `at_origins`
+  runs it and yields, at every used origin, (slot, t, a [N, d], P [N, d, d]): the predicted moments of
+  x_t given y[0 .. t - 1], which the caller forecasts from and must not modify.  Z [d], H [N], reg
+  [N, T], y, mask [T], `transition(t)` -> (T_t [d, d], Q_t [N, d, d]) of step t -> t + 1."""
+
+  def __init__(self, y, mask, X, season_change, num_seasons, has_slope, params, draws, origins, horizon):
+    self.y = y = np.asarray(y, np.float64)
+    self.mask = np.asarray(mask, bool)
+    self.T = T = y.shape[0]
+    self.origins = origins = [int(o) for o in np.asarray(origins).reshape(-1)]
+    self.Hn = Hn = int(horizon)
+    self.used = used = [o for o in origins if o >= 0]
+    if Hn < 1:
+      raise ValueError(f"the placebo horizon must be at least 1, got {Hn}")
+    if any(o < -1 for o in origins) or used != origins[:len(used)] or any(b <= a for a, b in zip(used, used[1:])):
+      raise ValueError("placebo origins must be strictly ascending steps with the unused slots (-1) at the end")
+    if used and used[-1] + Hn > T:
+      raise ValueError(f"placebo origin {used[-1]} with horizon {Hn} reaches beyond the series' {T} steps")
+    self.num_seasons = num_seasons = [int(n) for n in num_seasons]
+    K, hs = len(num_seasons), int(bool(has_slope))
+    self.hs = hs
+    self.d = d = prediction_state_dim(hs, num_seasons)
+    if d > PREDICTION_MAX_STATE:
+      raise ValueError(f"placebo forecasts take a state of at most {PREDICTION_MAX_STATE} components, "
+                       f"this model has {d}")
+    self.sc = np.asarray(season_change, np.uint8).reshape(K, -1)[:, :T] if K else np.zeros((0, T), np.uint8)
+    so = np.asarray(draws["observation_noise_scale"], np.float64).reshape(-1)
+    self.N = N = so.shape[0]
+    self.H = so * so
+    self.sl = np.asarray(draws["level_scale"], np.float64).reshape(N)
+    self.ss = np.asarray(draws["slope_scale"], np.float64).reshape(N) if hs else None
+    self.sd = np.asarray(draws["seasonal_drift_scales"], np.float64).reshape(N, -1) if K else None
+    self.reg = reg = np.zeros((N, T))
+    w = draws.get("weights")
+    if X is not None and w is not None and np.shape(w)[-1] > 0:
+      w, X = np.asarray(w, np.float64).reshape(N, -1), np.asarray(X, np.float64)
+      for j in range(w.shape[1]):
+        reg += w[:, j, None] * X[None, :, j]
+    self.offsets = offsets = np.cumsum([1 + hs] + [n - 1 for n in num_seasons])[:-1] if K else []
+    self.Z = Z = np.zeros(d)
+    Z[0] = 1.0
+    for o in offsets:
+      Z[o] = 1.0
+    self.a0 = a = np.zeros((N, d))
+    a[:, 0] = float(params["init_level_loc"])
+    self.P0 = P = np.zeros((N, d, d))
+    P[:, 0, 0] = float(params["init_level_scale"]) ** 2
+    if hs:
+      P[:, 1, 1] = float(params["init_slope_scale"]) ** 2
+    for o, n in zip(offsets, num_seasons):
+      P[:, o:o + n - 1, o:o + n - 1] = float(params["init_seasonal_scale"]) ** 2 * (np.eye(n - 1) - 1.0 / n)
+
+  def transition(self, t):            # (T_t [d, d], Q_t [N, d, d]) of step t -> t + 1
+    d, N, hs = self.d, self.N, self.hs
+    Tm = np.eye(d)
+    if hs:
+      Tm[0, 1] = 1.0
+    Q = np.zeros((N, d, d))
+    Q[:, 0, 0] = self.sl * self.sl
+    if hs:
+      Q[:, 1, 1] = self.ss * self.ss
+    for k, (o, n) in enumerate(zip(self.offsets, self.num_seasons)):
+      if self.sc[k, t]:
+        blk = np.zeros((n - 1, n - 1))
+        blk[:-1, 1:] = np.eye(n - 2)
+        blk[-1, :] = -1.0
+        Tm[o:o + n - 1, o:o + n - 1] = blk
+        q = self.sd[:, k] / n
+        Q[:, o:o + n - 1, o:o + n - 1] = (q * q)[:, None, None]
+    return Tm, Q
+
+  def at_origins(self):
+    a, P, Z, H, used = self.a0, self.P0, self.Z, self.H, self.used
+    slot = 0
+    for t in range(self.T):
+      if slot >= len(used):
+        break
+      if t == used[slot]:
+        yield slot, t, a, P
+        slot += 1
+        if slot >= len(used):
+          break
+      pz = P @ Z
+      if not self.mask[t]:
+        F = pz @ Z + H
+        v = self.y[t] - (a @ Z + self.reg[:, t])
+        a = a + (pz / F[:, None]) * v[:, None]
+        P = P - pz[:, :, None] * pz[:, None, :] / F[:, None, None]
+      if t + 1 < self.T:
+        Tm, Q = self.transition(t)
+        a = a @ Tm.T
+        P = Tm @ P @ Tm.T + Q
+
+
 def _placebo_summary_host(y, mask, X, season_change, num_seasons, has_slope, params, draws,
                           scale, shift, origins, horizon, per_draw: bool = False) -> Dict:
   """The placebo summary of one series in numpy, from the pooled PARAMETER draws alone: the
   definitions of ci_session_summarize_placebo (include/causalimpact_amd.h) in float64, for any block
   list of up to `PREDICTION_MAX_STATE` state components.  The arguments but the last three are those
-  of `_prediction_summary_host`, whose filter this runs; origins [O]: steps, strictly ascending
-  (-1: an unused slot, at the end); horizon: steps per window, origin + horizon <= T.
+  of `_prediction_summary_host`, whose filter this runs (`_PlaceboFilter`); origins [O]: steps,
+  strictly ascending (-1: an unused slot, at the end); horizon: steps per window, origin + horizon <= T.
   Returns predicted_mean, spread_mean, pit_mean [O] (0 in an unused slot and where the window counts
   no observation), as the device returns them for one series; with `per_draw` also C, V [O, N] (the
   conditional mean and predictive variance of the counted sum, in the sampler's units), A and cnt [O]."""
-  y = np.asarray(y, np.float64)
-  mask = np.asarray(mask, bool)
-  T = y.shape[0]
+  flt = _PlaceboFilter(y, mask, X, season_change, num_seasons, has_slope, params, draws, origins, horizon)
+  y, mask, reg, Z, H, N, d, Hn, transition = flt.y, flt.mask, flt.reg, flt.Z, flt.H, flt.N, flt.d, flt.Hn, flt.transition
   scale, shift = np.float64(scale), np.float64(shift)
-  origins = [int(o) for o in np.asarray(origins).reshape(-1)]
-  Hn = int(horizon)
-  used = [o for o in origins if o >= 0]
-  if Hn < 1:
-    raise ValueError(f"the placebo horizon must be at least 1, got {Hn}")
-  if any(o < -1 for o in origins) or used != origins[:len(used)] or any(b <= a for a, b in zip(used, used[1:])):
-    raise ValueError("placebo origins must be strictly ascending steps with the unused slots (-1) at the end")
-  if used and used[-1] + Hn > T:
-    raise ValueError(f"placebo origin {used[-1]} with horizon {Hn} reaches beyond the series' {T} steps")
-  num_seasons = [int(n) for n in num_seasons]
-  K, hs = len(num_seasons), int(bool(has_slope))
-  d = prediction_state_dim(hs, num_seasons)
-  if d > PREDICTION_MAX_STATE:
-    raise ValueError(f"placebo forecasts take a state of at most {PREDICTION_MAX_STATE} components, "
-                     f"this model has {d}")
-  sc = np.asarray(season_change, np.uint8).reshape(K, -1)[:, :T] if K else np.zeros((0, T), np.uint8)
-  so = np.asarray(draws["observation_noise_scale"], np.float64).reshape(-1)
-  N = so.shape[0]
-  H = so * so
-  sl = np.asarray(draws["level_scale"], np.float64).reshape(N)
-  ss = np.asarray(draws["slope_scale"], np.float64).reshape(N) if hs else None
-  sd = np.asarray(draws["seasonal_drift_scales"], np.float64).reshape(N, -1) if K else None
-  reg = np.zeros((N, T))
-  w = draws.get("weights")
-  if X is not None and w is not None and np.shape(w)[-1] > 0:
-    w, X = np.asarray(w, np.float64).reshape(N, -1), np.asarray(X, np.float64)
-    for j in range(w.shape[1]):
-      reg += w[:, j, None] * X[None, :, j]
-  offsets = np.cumsum([1 + hs] + [n - 1 for n in num_seasons])[:-1] if K else []
-  Z = np.zeros(d)
-  Z[0] = 1.0
-  for o in offsets:
-    Z[o] = 1.0
-  a = np.zeros((N, d))
-  a[:, 0] = float(params["init_level_loc"])
-  P = np.zeros((N, d, d))
-  P[:, 0, 0] = float(params["init_level_scale"]) ** 2
-  if hs:
-    P[:, 1, 1] = float(params["init_slope_scale"]) ** 2
-  for o, n in zip(offsets, num_seasons):
-    P[:, o:o + n - 1, o:o + n - 1] = float(params["init_seasonal_scale"]) ** 2 * (np.eye(n - 1) - 1.0 / n)
-
-  def transition(t):                  # (T_t [d, d], Q_t [N, d, d]) of step t -> t + 1
-    Tm = np.eye(d)
-    if hs:
-      Tm[0, 1] = 1.0
-    Q = np.zeros((N, d, d))
-    Q[:, 0, 0] = sl * sl
-    if hs:
-      Q[:, 1, 1] = ss * ss
-    for k, (o, n) in enumerate(zip(offsets, num_seasons)):
-      if sc[k, t]:
-        blk = np.zeros((n - 1, n - 1))
-        blk[:-1, 1:] = np.eye(n - 2)
-        blk[-1, :] = -1.0
-        Tm[o:o + n - 1, o:o + n - 1] = blk
-        q = sd[:, k] / n
-        Q[:, o:o + n - 1, o:o + n - 1] = (q * q)[:, None, None]
-    return Tm, Q
-
-  O = len(origins)
+  O = len(flt.origins)
   Cs, Vs, As, cnts = np.zeros((N, O)), np.zeros((N, O)), np.zeros(O), np.zeros(O)
   sums, spreads, pits = np.zeros((N, O)), np.zeros((N, O)), np.zeros((N, O))
-  slot = 0
-  for t in range(T):
-    if slot >= len(used):
-      break
-    if t == used[slot]:
-      fa, fP, r = a, P, np.zeros((N, d))
-      V, C, A, cnt = np.zeros(N), np.zeros(N), np.float64(0.0), 0
-      for h in range(Hn):
-        u = t + h
-        pz = fP @ Z
-        if not mask[u]:
-          C = C + (fa @ Z + reg[:, u])
-          A = A + y[u]
-          cnt += 1
-          V = V + ((2.0 * (r @ Z) + pz @ Z) + H)
-          r = r + pz
-        if h + 1 < Hn:
-          Tm, Q = transition(u)
-          fa, r = fa @ Tm.T, r @ Tm.T
-          fP = Tm @ fP @ Tm.T + Q
-      Cs[:, slot], Vs[:, slot], As[slot], cnts[slot] = C, V, A, cnt
-      if cnt:
-        e = A - C
-        sums[:, slot] = C * scale + np.float64(cnt) * shift
-        spreads[:, slot] = ((V + e * e) * scale) * scale
-        pits[:, slot] = 0.5 * _erfc(-e / np.sqrt(2.0 * V))
-      slot += 1
-      if slot >= len(used):
-        break
-    pz = P @ Z
-    if not mask[t]:
-      F = pz @ Z + H
-      v = y[t] - (a @ Z + reg[:, t])
-      a = a + (pz / F[:, None]) * v[:, None]
-      P = P - pz[:, :, None] * pz[:, None, :] / F[:, None, None]
-    if t + 1 < T:
-      Tm, Q = transition(t)
-      a = a @ Tm.T
-      P = Tm @ P @ Tm.T + Q
+  for slot, t, a, P in flt.at_origins():
+    # the forecast branch, from the predicted moments
+    fa, fP, r = a, P, np.zeros((N, d))
+    V, C, A, cnt = np.zeros(N), np.zeros(N), np.float64(0.0), 0
+    for h in range(Hn):
+      u = t + h
+      pz = fP @ Z
+      if not mask[u]:
+        C = C + (fa @ Z + reg[:, u])
+        A = A + y[u]
+        cnt += 1
+        V = V + ((2.0 * (r @ Z) + pz @ Z) + H)
+        r = r + pz
+      if h + 1 < Hn:
+        Tm, Q = transition(u)
+        fa, r = fa @ Tm.T, r @ Tm.T
+        fP = Tm @ fP @ Tm.T + Q
+    Cs[:, slot], Vs[:, slot], As[slot], cnts[slot] = C, V, A, cnt
+    if cnt:
+      e = A - C
+      sums[:, slot] = C * scale + np.float64(cnt) * shift
+      spreads[:, slot] = ((V + e * e) * scale) * scale
+      pits[:, slot] = 0.5 * _erfc(-e / np.sqrt(2.0 * V))
   out = dict(predicted_mean=sums.mean(axis=0), spread_mean=spreads.mean(axis=0), pit_mean=pits.mean(axis=0))
   if per_draw:
     out.update(C=Cs.T.copy(), V=Vs.T.copy(), A=As, cnt=cnts)
+  return out
+
+
+def placebo_stream(seed, series_id=None, chains=(0,)):
+  """What addresses the random stream of a fit's simulated placebo forecasts: (key, chains) -- the
+  Philox key the fit ran on (`_native.series_stream_key(seed, series_id)`; the seed itself for
+  series_id None: a single fit, or shared streams) and the GLOBAL ids of the chains whose draws are
+  pooled, in pooling order."""
+  pair = tuple(int(v) & 0xFFFFFFFF for v in _native.seed_pair(seed))
+  key = pair if series_id is None else _native.series_stream_key(pair, int(series_id))
+  return key, tuple(int(c) for c in chains)
+
+
+def _placebo_simulated_host(y, mask, X, season_change, num_seasons, has_slope, params, draws,
+                            scale, shift, origins, horizon, link, stream, seen=None, ranks=()) -> Dict:
+  """The SIMULATED placebo forecasts of one series in numpy, from the pooled PARAMETER draws alone:
+  the definitions of ci_session_simulate_placebo (include/causalimpact_amd.h) in float64, for any block
+  list of up to `PREDICTION_MAX_STATE` state components.  The arguments up to `horizon` are those of
+  `_placebo_summary_host`, whose filter this runs (`_PlaceboFilter`); link: a `_native.LINK_*`;
+  stream: (key, chains) of `placebo_stream` -- pooled draw n = c * S + s is kept draw s of chain
+  chains[c], S = N / len(chains), so the result does not depend on how the chains were spread over
+  devices; seen [O]: the observed totals on the data scale (None: no spread_mean, no below); ranks:
+  the order statistics of total_order.  For every draw ONE path of the window: the filter's own step
+  fed with v = sqrt(F) z, z = `_native.normals_host`(key, chain, s, SITE_PLACEBO_SIM, slot, h), the
+  link applied step by step, the values summed.  Returns what the device returns for one series --
+  predicted_mean, spread_mean, below [O], total_order [R, O], means as `_native.row_means_host` -- and
+  totals [O, N], cnt [O]; everything 0 in an unused slot and where the window counts no observation."""
+  flt = _PlaceboFilter(y, mask, X, season_change, num_seasons, has_slope, params, draws, origins, horizon)
+  mask, reg, Z, H, N, Hn = flt.mask, flt.reg, flt.Z, flt.H, flt.N, flt.Hn
+  scale, shift = np.float64(scale), np.float64(shift)
+  key, chains = stream
+  if not chains or N % len(chains):
+    raise ValueError(f"{N} pooled draws are not a whole number of draws for each of {len(chains)} chains")
+  kept = N // len(chains)
+  chain_of = np.repeat(np.asarray(chains, np.uint64), kept)
+  iter_of = np.tile(np.arange(kept, dtype=np.uint64), len(chains))
+  O = len(flt.origins)
+  totals, cnts = np.zeros((O, N)), np.zeros(O)
+  for slot, t, a, P in flt.at_origins():
+    z = _native.normals_host(key, chain_of[:, None], iter_of[:, None], _native.SITE_PLACEBO_SIM, slot,
+                             np.arange(Hn, dtype=np.uint64)[None, :])                     # [N, H]
+    fa, fP, S, cnt = a, P, np.zeros(N), 0
+    for h in range(Hn):
+      u = t + h
+      pz = fP @ Z
+      if not mask[u]:
+        F = pz @ Z + H
+        f = fa @ Z + reg[:, u]
+        v = np.sqrt(F) * z[:, h]
+        ysim = f + v
+        with np.errstate(over="ignore"):
+          S = S + _native.link_values_host(ysim * scale + shift, link)
+        cnt += 1
+        fa = fa + (pz / F[:, None]) * v[:, None]
+        fP = fP - pz[:, :, None] * pz[:, None, :] / F[:, None, None]
+      if h + 1 < Hn:
+        Tm, Q = flt.transition(u)
+        fa = fa @ Tm.T
+        fP = Tm @ fP @ Tm.T + Q
+    cnts[slot] = cnt
+    if cnt:
+      totals[slot] = S
+  some = cnts > 0
+  out = dict(predicted_mean=_native.row_means_host(totals), totals=totals, cnt=cnts,
+             total_order=np.sort(totals, axis=1)[:, list(ranks)].T.copy())
+  if seen is not None:
+    seen = np.where(some, np.nan_to_num(np.asarray(seen, np.float64).reshape(O)), 0.0)
+    out["below"] = np.where(some, np.count_nonzero(totals <= seen[:, None], axis=1), 0).astype(np.float64)
+    dev = totals - seen[:, None]
+    out["spread_mean"] = np.where(some, _native.row_means_host(dev * dev), 0.0)
   return out
 
 
@@ -1050,6 +1179,8 @@ def _placebo_seen(y_seen, mask, origins, horizon: int, scale, shift):
 
 PLACEBO_COLUMNS = ("horizon_end", "n_counted", "actual", "predicted", "predicted_sd", "effect",
                    "relative_effect", "pit", "p", "significant")
+# `Placebo(simulate=True)`: the alpha / 2 and 1 - alpha / 2 quantiles of the simulated totals, after them
+PLACEBO_SIMULATED_COLUMNS = ("predicted_lower", "predicted_upper")
 PLACEBO_QUALITY_ENTRIES = ("n_origins", "horizon", "false_positive_rate", "mean_relative_effect",
                            "mde_relative", "empirical_p")
 
@@ -1106,7 +1237,9 @@ def _placebo_columns(psum: Dict, origins, horizon: int, alpha: float, observed) 
         "relative_effect": effect / predicted,
         "pit": pit,
         "p": 2.0 * np.minimum(pit, 1.0 - pit),
-        "significant": some & ((pit < alpha / 2.0) | (pit > 1.0 - alpha / 2.0))}
+        "significant": some & ((pit < alpha / 2.0) | (pit > 1.0 - alpha / 2.0)),
+        # (the simulated route only: the quantiles of the totals)
+        **{k: np.asarray(psum[k], np.float64)[used] + nan for k in PLACEBO_SIMULATED_COLUMNS if k in psum}}
 
 
 def _placebo_frames(psum: Optional[Dict], origins, horizon: int, alpha: float, observed,
@@ -1121,7 +1254,8 @@ def _placebo_frames(psum: Optional[Dict], origins, horizon: int, alpha: float, o
   end = cols.pop("horizon_end_step")
   frame = pd.DataFrame({"horizon_end": model_idx[end], **cols}, index=model_idx[origins[origins >= 0]])
   frame.index.name = "origin"
-  return frame[list(PLACEBO_COLUMNS)], _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
+  shown = list(PLACEBO_COLUMNS) + [k for k in PLACEBO_SIMULATED_COLUMNS if k in cols]
+  return frame[shown], _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
 
 
 def _aggregate_placebo_frames(psum: Optional[Dict], actual, columns, horizon: int, alpha: float,
@@ -1399,6 +1533,13 @@ class PlaceboPart(NamedTuple):
   shift: Any
   origins: Any
   horizon: Any
+  # `Placebo(simulate=True)` only: the (lower, upper) quantiles of the totals the frame reports -- None:
+  # the analytic placebo --, the `_native.LINK_*` the simulated values are formed under, and per series
+  # the `placebo_stream` (key, chains) its fit's random numbers are addressed by (one pair for all:
+  # a single fit).  The observed totals are taken from the request's `observed` under a link.
+  quantiles: Optional[Tuple[float, float]] = None
+  link: int = 0
+  streams: Any = None
 
 
 @dataclasses.dataclass(frozen=True)
@@ -1457,6 +1598,7 @@ class SummaryKind(NamedTuple):
   last -- cut to a series' length, and padded with `fill` beyond it when launches are put together."""
   whole: Tuple[str, ...]
   fill: float
+  also: Tuple[str, ...] = ()    # names only some routes return, laid out like those in `whole`
 
 
 SUMMARY_KINDS = {
@@ -1466,8 +1608,9 @@ SUMMARY_KINDS = {
     # [B, W, 2, draws | R]; `joint_bands`: path_center, path_spread [B, 1 + W, 2, T] over time, the rest whole
     "windows": SummaryKind(("per_draw", "per_draw_order", "path_excursion_order", "path_observed_excursion",
                             "path_at", "path_exceed"), np.nan),
+    # [B, O]; predicted_lower, predicted_upper on the simulated route (`Placebo(simulate=True)`) only
     "placebo": SummaryKind(("predicted_mean", "spread_mean", "pit_mean", "n_counted", "seen_sum"),
-                           np.nan)}                                           # [B, O]
+                           np.nan, ("predicted_lower", "predicted_upper"))}
 # the parameter draws the prediction errors and the placebo forecasts are filtered from on the host
 _PARAMETER_DRAWS = ("observation_noise_scale", "level_scale", "slope_scale", "seasonal_drift_scales",
                     "weights")
@@ -1588,12 +1731,106 @@ def _placebo_entry_seen(one: "SeriesInputs", scale, shift, observed, origins, ho
 
 
 def _per_series(part: PlaceboPart, n: int) -> PlaceboPart:
-  """`part` with one row per series: scale, shift, horizon [n], origins [n, O]."""
+  """`part` with one row per series: scale, shift, horizon [n], origins [n, O], streams n pairs."""
   origins = np.asarray(part.origins)
-  return PlaceboPart(np.broadcast_to(np.asarray(part.scale, np.float64), (n,)),
-                     np.broadcast_to(np.asarray(part.shift, np.float64), (n,)),
-                     np.broadcast_to(origins, (n, origins.shape[-1])),
-                     np.broadcast_to(np.asarray(part.horizon), (n,)))
+  streams = part.streams
+  if streams is not None and len(streams) == 2 and not isinstance(streams[0][0], (tuple, list)):
+    streams = [streams] * n              # (one (key, chains) pair for all)
+  return part._replace(scale=np.broadcast_to(np.asarray(part.scale, np.float64), (n,)),
+                       shift=np.broadcast_to(np.asarray(part.shift, np.float64), (n,)),
+                       origins=np.broadcast_to(origins, (n, origins.shape[-1])),
+                       horizon=np.broadcast_to(np.asarray(part.horizon), (n,)), streams=streams)
+
+
+def _placebo_seen_linked(observed, mask, origins, horizon: int, link: int):
+  """`_placebo_seen` under an outcome link: (n_counted [O], seen_sum [O]) with seen_sum the sum of the
+  RAW outcome (`observed`, data scale) over the counted steps of every window, ascending in float64.
+  Those steps are rows the model conditions on; ValueError if one lies outside the link's domain."""
+  observed = np.asarray(observed, np.float64)
+  mask = np.asarray(mask, bool)
+  origins = np.asarray(origins).reshape(-1)
+  n_counted, seen_sum = np.zeros(origins.size), np.full(origins.size, np.nan)
+  used = origins >= 0
+  if used.any():
+    steps = origins[used].astype(np.int64)[:, None] + np.arange(int(horizon))[None, :]     # [O, H]
+    seen = ~mask[steps]
+    values = observed[steps]
+    with np.errstate(invalid="ignore"):
+      inside = values > (0.0 if link == _native.LINK_LOG else -1.0)
+    if np.any(seen & ~inside):
+      o, h = np.argwhere(seen & ~inside)[0]
+      raise ValueError(f"placebo: the outcome {values[o, h]!r} at model step {int(steps[o, h])} lies outside the "
+                       "domain of `outcome_link`")
+    n_counted[used] = seen.sum(axis=1).astype(np.float64)
+    seen_sum[used] = np.cumsum(np.where(seen, values, 0.0), axis=1)[:, -1]
+  return n_counted, seen_sum
+
+
+def _placebo_sim_ranks(num_draws: int, quantiles) -> List[int]:
+  """The order statistics of the simulated totals the two quantiles of the frame need."""
+  return sorted({r for lo, hi, _ in _quantile_ranks(num_draws, quantiles) for r in (lo, hi)})
+
+
+def _simulated_placebo_summaries(inputs: Sequence[SeriesInputs], part: PlaceboPart, observed, num_draws: int,
+                                 simulate) -> Dict[str, np.ndarray]:
+  """The placebo kind of a record on the simulated route, {name: [n, O]}: n_counted and seen_sum of
+  every series (`_placebo_seen_linked` on `observed` [T] or [n, T] under a link, `_placebo_seen`
+  under the identity), then simulate(seen [n, O] with 0 in the unused slots, ranks) -> predicted_mean,
+  spread_mean, below [n, O], total_order [n, R, O] of the device or the numpy twin, and from them
+    pit_mean = (below + 0.5) / (N + 1)
+    predicted_lower, predicted_upper: the part's quantiles of the totals, interpolated from the order
+    statistics as `series` interpolates its bands."""
+  n = len(inputs)
+  seen = []
+  for i, one in enumerate(inputs):
+    if part.link:
+      obs = np.broadcast_to(np.asarray(observed, np.float64), (n, np.shape(observed)[-1]))[i]
+      seen.append(_placebo_seen_linked(obs, one.mask, part.origins[i], part.horizon[i], part.link))
+    else:
+      seen.append(_placebo_seen(one.outcome(), one.mask, part.origins[i], part.horizon[i],
+                                part.scale[i], part.shift[i]))
+  n_counted, seen_sum = np.stack([c for c, _ in seen]), np.stack([a for _, a in seen])
+  ranks = _placebo_sim_ranks(num_draws, part.quantiles)
+  got = simulate(np.nan_to_num(seen_sum), ranks)
+  pos = {r: i for i, r in enumerate(ranks)}
+  (lo_a, hi_a, g_a), (lo_b, hi_b, g_b) = _quantile_ranks(num_draws, part.quantiles)
+  by_rank = {r: got["total_order"][:, pos[r]] for r in (lo_a, hi_a, lo_b, hi_b)}
+  return dict(predicted_mean=got["predicted_mean"], spread_mean=got["spread_mean"],
+              pit_mean=(got["below"] + 0.5) / (num_draws + 1.0), n_counted=n_counted, seen_sum=seen_sum,
+              predicted_lower=_lerp_order_stats(by_rank, lo_a, hi_a, g_a),
+              predicted_upper=_lerp_order_stats(by_rank, lo_b, hi_b, g_b))
+
+
+def _host_placebo_simulations(inputs: Sequence[SeriesInputs], draws, part: PlaceboPart):
+  """simulate(seen, ranks) of `_simulated_placebo_summaries` in numpy (`_placebo_simulated_host`) from
+  the parameter draws {name: [n, C, S, ...]}; a series without an origin stays at zero."""
+  def simulate(seen, ranks):
+    shape = part.origins.shape
+    out = dict(predicted_mean=np.zeros(shape), spread_mean=np.zeros(shape), below=np.zeros(shape),
+               total_order=np.zeros((shape[0], len(ranks), shape[1])))
+    for i, one in enumerate(inputs):
+      if np.any(part.origins[i] >= 0):
+        got = _placebo_simulated_host(*one.filter_inputs(), _pooled_draws(draws, i), part.scale[i], part.shift[i],
+                                      part.origins[i], part.horizon[i], part.link, part.streams[i], seen=seen[i],
+                                      ranks=ranks)
+        for k in out:
+          out[k][i] = got[k]
+    return out
+  return simulate
+
+
+def _device_placebo_simulations(sess, part: PlaceboPart, blocks: bool = False):
+  """simulate(seen, ranks) of `_simulated_placebo_summaries` on an open session (`simulate_placebo`,
+  with `blocks` `simulate_placebo_blocks`): the launch's own origin slots, as `_device_placebo_summaries`."""
+  def simulate(seen, ranks):
+    width = max(1, int((part.origins >= 0).sum(axis=1).max()))
+    got = sess.simulate_placebo(part.scale, part.shift, part.origins[:, :width], np.maximum(part.horizon, 1),
+                                part.link, seen[:, :width], ranks, blocks=blocks)
+    out = {k: np.zeros(v.shape[:-1] + (part.origins.shape[1],)) for k, v in got.items()}
+    for k, v in got.items():
+      out[k][..., :width] = v
+    return out
+  return simulate
 
 
 def _with_placebo_seen(inputs: Sequence[SeriesInputs], part: PlaceboPart, plsum):
@@ -1614,7 +1851,9 @@ def take_summaries(sess, request: SummaryRequest,
   (`summarize_predictions_blocks`, `summarize_placebo_blocks`) where the session has those and
   `device_block_predictions_supported` takes it; else in numpy from the parameter draws,
   fetched once for both, over `series_inputs` (one per series of the session; read for these two
-  kinds only).  Components a session lacks stay None: the caller's business.  The scales and shifts
+  kinds only).  A placebo part with `quantiles` is the SIMULATED placebo (`simulate_placebo`,
+  `simulate_placebo_blocks`, `_placebo_simulated_host`, chosen the same way; a session without the
+  entry filters on the host).  Components a session lacks stay None: the caller's business.  The scales and shifts
   map the SESSION's units to the data scale (`_request_in_internal_units`).  With `request.link` the
   session's link is set first (`set_link`: the effect, its windows and paths then form linked values,
   and so does a pool step that follows while the session is open) and the effect gets `value_mean`
@@ -1631,6 +1870,9 @@ def take_summaries(sess, request: SummaryRequest,
     components = sess.summarize_components(request.scale, request.shift, request.ranks)
   filtered = request.predictions is not None or request.placebo is not None
   has_entries = {"predictions", "placebo"} <= set(sess.summaries)
+  simulated = request.placebo is not None and request.placebo.quantiles is not None
+  if simulated and not hasattr(sess, "simulate_placebo"):
+    has_entries = False
   one_lane = filtered and has_entries and device_predictions_supported(series_inputs[0].num_seasons)
   blocks = (filtered and has_entries and not one_lane and hasattr(sess, "summarize_predictions_blocks")
             and hasattr(sess, "summarize_placebo_blocks")
@@ -1650,7 +1892,15 @@ def take_summaries(sess, request: SummaryRequest,
   if request.paths is not None:
     windows = dict(windows or {}, **_paths_record(sess.summarize_paths(
         request.scale, request.shift, request.observed, *request.paths, request.path_ranks, want=_PATH_RECORD)))
-  if request.placebo is not None:
+  if simulated:
+    part = _per_series(request.placebo, len(series_inputs))
+    num_draws = (int(np.prod(draws["observation_noise_scale"].shape[1:3])) if on_host else
+                 sess.pb.num_chains * sess.pb.num_results)
+    placebo = _simulated_placebo_summaries(
+        series_inputs, part, request.observed, num_draws,
+        _host_placebo_simulations(series_inputs, draws, part) if on_host else
+        _device_placebo_simulations(sess, part, blocks))
+  elif request.placebo is not None:
     part = _per_series(request.placebo, len(series_inputs))
     placebo = _with_placebo_seen(series_inputs, part, _host_placebo_summaries(series_inputs, draws, part)
                                  if on_host else _device_placebo_summaries(sess, part, blocks))
@@ -1796,7 +2046,12 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
     draws = {k: out[k][None] for k in _PARAMETER_DRAWS}
     if internal.predictions is not None:
       predictions = _host_prediction_summaries(inputs, draws, internal.predictions, internal.ranks)
-    if internal.placebo is not None:
+    if internal.placebo is not None and internal.placebo.quantiles is not None:
+      part = _per_series(internal.placebo, 1)
+      placebo = _simulated_placebo_summaries(
+          inputs, part, internal.observed, int(np.prod(draws["observation_noise_scale"].shape[1:3])),
+          _host_placebo_simulations(inputs, draws, part))
+    elif internal.placebo is not None:
       part = _per_series(internal.placebo, 1)
       placebo = _with_placebo_seen(inputs, part, _host_placebo_summaries(inputs, draws, part))
     record = SummaryRecord(effect=effect, predictions=predictions, windows=windows, placebo=placebo)

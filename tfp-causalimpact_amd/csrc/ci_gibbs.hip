@@ -453,6 +453,7 @@ static int session_create_impl(const ci_problem* pb, const int32_t* series_lengt
   s->pb = *pb;
   s->ragged = series_lengths != nullptr;
   if (s->ragged) s->lengths.assign(series_lengths, series_lengths + B);
+  if (series_ids) s->ids.assign(series_ids, series_ids + B);
   s->params.assign(params, params + B);
   if (plan_route(s, device_cu_count(pb->device))) return 1;
   // one LDS limit per function, after the route is complete

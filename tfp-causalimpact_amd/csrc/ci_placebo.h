@@ -34,7 +34,9 @@
 // pooled sum, N(S, U) given the members' draws:
 //   e = seen - S;  SUM = S;  SPREAD = U + e^2;  PIT = 0.5 erfc(-e / sqrt(2 U));  all 0 where U == 0.
 #pragma once
+#include "ci_link.h"
 #include "ci_predict.h"
+#include "ci_rng.h"
 
 namespace ci {
 
@@ -195,6 +197,206 @@ __global__ __launch_bounds__(64) void placebo_kernel(PlaceboArgs k) {
 #undef PM
 #undef FM
   for (; slot < NO; ++slot) out[(size_t)slot * N] = 0.0;
+}
+
+// ---- SIMULATED placebo forecasts (ci_session_simulate_placebo; DESIGN.md "Simulated placebo
+// forecasts").  Under an outcome link the window's total is a sum of exp's of jointly Gaussian values
+// and has no closed form, so one path of the window is drawn per posterior draw instead: by the chain
+// rule y_{o+h} given the simulated y_o .. y_{o+h-1} is N(f_h, F_h) of a filter that is updated with
+// the simulated values, so the forecast branch is the filter's own step fed with a draw from its own
+// forecast -- no r, V, C, A, and no factor of P.  From the copy (a, P) of the predicted moments:
+//   S = 0.0, cnt = 0
+//   for h = 0 .. H_b - 1, u = o + h:
+//     pz = P Z';  m = Z a;  F = Z pz + sigma_obs^2;  f = m + reg[n, u]
+//     mask[u] == 0:  z = normal_d(key_b, chain_offset + n / S_kept, n % S_kept, SITE_PLACEBO_SIM, slot, h)
+//                    v = sqrt(F) * z;  ysim = f + v                    (separate roundings)
+//                    S += link(ysim * scale[b] + shift[b]);  cnt += 1  (two roundings, as ci_link.h)
+//                    a += (pz / F) v;  P -= pz pz' / F                 (the filter's update)
+//     h + 1 < H_b:   a <- T_u a;  P <- T_u P T_u' + Q_u
+// TOTAL[b, slot, n] = S, 0.0 where cnt == 0 and in the unused slots.  idx of the normal is h whether
+// or not the step is counted: one Philox call serves four consecutive h, its two Box-Muller pairs
+// are formed when h reaches them.  Lane 0 of the grid's first column also stores cnt per (b, slot):
+// the rows the statistics below leave at 0.
+struct PlaceboSimArgs {
+  PlaceboArgs q;                   // q.p.out [rows of this launch, N]; q.series_of unused
+  int b0;                          // the first series of this launch: grid row r is series b0 + r
+  int kept;                        // S: kept draws per chain, n = c * S + s
+  uint32_t chain_offset;           // the global id of the session's chain 0
+  const uint32_t* keys;            // [B, 2]: the Philox key every series' fit ran on
+  int* counted;                    // [rows of this launch]: cnt of (series, slot)
+};
+
+// The normal of step h of a window: the Philox call of h >> 2 and the Box-Muller pair of h >> 1 are
+// formed when h enters them and carried in (r, z0, z1) -- normal_d(g, iter, SITE_PLACEBO_SIM, sub, h).
+__device__ __forceinline__ double placebo_sim_normal(const Rng& g, uint32_t iter, uint32_t sub, int h, U4& r,
+                                                     double& z0, double& z1) {
+  if ((h & 3) == 0) r = site_call(g, iter, SITE_PLACEBO_SIM, sub, (uint32_t)h >> 2);
+  if ((h & 1) == 0) {
+    const bool hi = (h & 2) != 0;
+    box_muller_d(hi ? r.z : r.x, hi ? r.w : r.y, z0, z1);
+  }
+  return (h & 1) ? z1 : z0;
+}
+
+// grid (ceil(N / 64), series of the launch), block 64.
+template <int HAS_SLOPE, int NS, int LINK>
+__global__ __launch_bounds__(64) void placebo_sim_kernel(PlaceboSimArgs k) {
+  constexpr int N1 = NS ? NS - 1 : 0, O = 1 + HAS_SLOPE, D = O + N1, NP = D * (D + 1) / 2;
+  constexpr int ZS = O < D ? O : 0;              // the block's first effect (NS > 0)
+  const PredArgs& p = k.q.p;
+  const int n = blockIdx.x * 64 + threadIdx.x, N = p.N, T = p.T, NO = k.q.O;
+  const size_t e = blockIdx.y, b = (size_t)k.b0 + e;
+  if (n >= N) return;
+  const int Tb = p.series_T ? p.series_T[b] : T;
+  const size_t bn = b * N + n;
+  const double so = (double)p.obs[bn], H = so * so;
+  const double sl = (double)p.lscale[bn], q_level = sl * sl;
+  double q_slope = 0.0, q_drift = 0.0;
+  if (HAS_SLOPE) {
+    const double ss = (double)p.sscale[bn];
+    q_slope = ss * ss;
+  }
+  if (NS) {
+    const double q = (double)p.drift[bn] / (double)NS;
+    q_drift = q * q;
+  }
+  const double scale = p.scales[b], shift = p.shifts[b];
+  const double* init = p.init + 4 * b;
+  const float* y = p.y + b * T;
+  const uint8_t* mask = p.mask + b * T;
+  const double* reg = p.reg ? p.reg + b * T * N + n : nullptr;
+  double* out = p.out + e * NO * N + n;
+  int* counted = n == 0 ? k.counted + e * NO : nullptr;
+  const int* org = k.q.origins + b * NO;
+  const int Hb = k.q.horizon[b];
+  Rng rng;
+  rng.k0 = k.keys[2 * b];
+  rng.k1 = k.keys[2 * b + 1];
+  rng.chain = k.chain_offset + (uint32_t)(n / k.kept);
+  const uint32_t iter = (uint32_t)(n % k.kept);
+
+  double a[D], P[NP];
+#define PM(i, j) P[pred_sym<D>(i, j)]
+#define FM(i, j) fP[pred_sym<D>(i, j)]
+#pragma unroll
+  for (int i = 0; i < D; ++i) a[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) P[i] = 0.0;
+  a[0] = init[0];
+  PM(0, 0) = init[1];
+  if (HAS_SLOPE) PM(1, 1) = init[2];
+  if (NS) {
+    const double v = init[3];
+#pragma unroll
+    for (int i = 0; i < N1; ++i)
+#pragma unroll
+      for (int j = i; j < N1; ++j) PM(O + i, O + j) = v * ((i == j ? 1.0 : 0.0) - 1.0 / (double)NS);
+  }
+
+  int slot = 0;
+  int next = org[0];                             // uniform over the wavefront, as everything of the origins
+  for (int t = 0; t < Tb && next >= 0; ++t) {
+    if (t == next) {
+      // the simulated branch, from a copy of the predicted moments
+      double fa[D], fP[NP];
+#pragma unroll
+      for (int i = 0; i < D; ++i) fa[i] = a[i];
+#pragma unroll
+      for (int i = 0; i < NP; ++i) fP[i] = P[i];
+      double S = 0.0, z0 = 0.0, z1 = 0.0;
+      U4 r4 = {0u, 0u, 0u, 0u};
+      int cnt = 0;
+      for (int h = 0; h < Hb; ++h) {
+        const int u = t + h;
+        const double z = placebo_sim_normal(rng, iter, (uint32_t)slot, h, r4, z0, z1);
+        double pz[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) pz[i] = NS ? FM(i, 0) + FM(i, ZS) : FM(i, 0);
+        if (mask[u] == 0) {
+          const double m = NS ? fa[0] + fa[ZS] : fa[0];
+          const double F = (NS ? pz[0] + pz[ZS] : pz[0]) + H;
+          const double f = m + (reg ? reg[(size_t)u * N] : 0.0);
+          const double v = __dmul_rn(sqrt(F), z);
+          const double ysim = __dadd_rn(f, v);
+          S += link_value<LINK>(__dadd_rn(__dmul_rn(ysim, scale), shift));
+          cnt += 1;
+#pragma unroll
+          for (int i = 0; i < D; ++i) fa[i] += (pz[i] / F) * v;
+#pragma unroll
+          for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = i; j < D; ++j) FM(i, j) -= pz[i] * pz[j] / F;
+        }
+        if (h + 1 >= Hb) break;
+        bool change = false;
+        if constexpr (NS > 0) change = p.season_change[u] != 0;
+        placebo_propagate<HAS_SLOPE, NS, D>(fa, fP, change, q_level, q_slope, q_drift);
+      }
+      out[(size_t)slot * N] = cnt > 0 ? S : 0.0;
+      if (counted) counted[slot] = cnt;
+      ++slot;
+      next = slot < NO ? org[slot] : -1;
+      if (next < 0) break;
+    }
+    // the filter's step t (predict_kernel)
+    double pz[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) pz[i] = NS ? PM(i, 0) + PM(i, ZS) : PM(i, 0);
+    if (mask[t] == 0) {
+      const double m = NS ? a[0] + a[ZS] : a[0];
+      const double F = (NS ? pz[0] + pz[ZS] : pz[0]) + H;
+      const double f = m + (reg ? reg[(size_t)t * N] : 0.0);
+      const double v = (double)y[t] - f;
+#pragma unroll
+      for (int i = 0; i < D; ++i) a[i] += (pz[i] / F) * v;
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) PM(i, j) -= pz[i] * pz[j] / F;
+    }
+    if (t + 1 >= Tb) break;
+    bool change = false;
+    if constexpr (NS > 0) change = p.season_change[t] != 0;
+    placebo_propagate<HAS_SLOPE, NS, D>(a, P, change, q_level, q_slope, q_drift);
+  }
+#undef PM
+#undef FM
+  for (; slot < NO; ++slot) {
+    out[(size_t)slot * N] = 0.0;
+    if (counted) counted[slot] = 0;
+  }
+}
+
+// The statistics of the rows of TOTAL [rows, N] that need `seen` [rows]: one wavefront per row, four
+// rows per workgroup (comp_row_stats_kernel's layout).
+//   below[row] = #{n : TOTAL <= seen}, an integer count (exact in any order), stored as a double;
+//   with REWRITE the row becomes (TOTAL - seen)^2 in place, one rounding per operation -- its row
+//   mean is spread_mean.
+// A row with counted == 0 (no step counted, or an unused slot) reads 0 in both and is left at 0.
+template <int REWRITE>
+__global__ __launch_bounds__(256) void placebo_sim_seen_kernel(size_t rows, int N, double* __restrict__ M,
+                                                               const double* __restrict__ seen,
+                                                               const int* __restrict__ counted,
+                                                               double* __restrict__ below) {
+  const int lane = threadIdx.x & 63;
+  const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  double* x = M + row * N;
+  int c = 0;
+  if (counted[row] > 0) {                        // uniform over the wavefront
+    const double s = seen[row];
+    for (int i = lane; i < N; i += 64) {
+      const double v = x[i];
+      c += v <= s ? 1 : 0;
+      if (REWRITE) {
+        const double d = __dsub_rn(v, s);
+        x[i] = __dmul_rn(d, d);
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+  if (lane == 0 && below) below[row] = (double)c;
 }
 
 // The entries c0 .. c1 - 1 of the group table, whose rows [(c1 - c0) * O, N] of one pass lie in M,

@@ -1,5 +1,6 @@
 // Instantiation unit of the placebo forecasts (ci_placebo.h) and their launches;
-// ci_session_summarize_placebo and ci_session_pool_placebo (ci_summary.hip) call them.
+// ci_session_summarize_placebo, ci_session_pool_placebo and ci_session_simulate_placebo
+// (ci_summary.hip) call them.
 #include "ci_placebo.h"
 
 namespace ci {
@@ -33,6 +34,46 @@ hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seas
   const PlaceboFn fn = has_slope ? placebo_fn<1>(num_seasons, out) : placebo_fn<0>(num_seasons, out);
   if (!fn) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3((args.p.N + 63) / 64, B), dim3(64), 0, stream, args);
+  return hipGetLastError();
+}
+
+using PlaceboSimFn = void (*)(PlaceboSimArgs);
+
+template <int HAS_SLOPE, int NS> static PlaceboSimFn placebo_sim_fn(int link) {
+  if (link == LINK_LOG) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG>;
+  if (link == LINK_LOG1P) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG1P>;
+  return placebo_sim_kernel<HAS_SLOPE, NS, LINK_IDENTITY>;
+}
+
+template <int HAS_SLOPE> static PlaceboSimFn placebo_sim_fn(int ns, int link) {
+  switch (ns) {
+    case 0: return placebo_sim_fn<HAS_SLOPE, 0>(link);
+    case 2: return placebo_sim_fn<HAS_SLOPE, 2>(link);
+    case 3: return placebo_sim_fn<HAS_SLOPE, 3>(link);
+    case 4: return placebo_sim_fn<HAS_SLOPE, 4>(link);
+    case 5: return placebo_sim_fn<HAS_SLOPE, 5>(link);
+    case 6: return placebo_sim_fn<HAS_SLOPE, 6>(link);
+    case 7: return placebo_sim_fn<HAS_SLOPE, 7>(link);
+    default: return nullptr;
+  }
+}
+
+// The simulated totals of `nb` series from args.b0 on: rows [nb * O, N] in args.q.p.out, cnt per row
+// in args.counted; link one of ci_link.h, num_seasons 0 (no block) or 2..7.
+hipError_t placebo_sim_launch(hipStream_t stream, int nb, int has_slope, int num_seasons, int link,
+                              const PlaceboSimArgs& args) {
+  const PlaceboSimFn fn = has_slope ? placebo_sim_fn<1>(num_seasons, link) : placebo_sim_fn<0>(num_seasons, link);
+  if (!fn || link < 0 || link >= NUM_LINKS) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fn, dim3((args.q.p.N + 63) / 64, nb), dim3(64), 0, stream, args);
+  return hipGetLastError();
+}
+
+// below[row] and, with `rewrite`, the rows of M [rows, N] as (x - seen)^2 in place.
+hipError_t placebo_sim_seen_launch(hipStream_t stream, size_t rows, int N, double* M, const double* seen,
+                                   const int* counted, double* below, int rewrite) {
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  if (rewrite) hipLaunchKernelGGL(placebo_sim_seen_kernel<1>, grid, block, 0, stream, rows, N, M, seen, counted, below);
+  else hipLaunchKernelGGL(placebo_sim_seen_kernel<0>, grid, block, 0, stream, rows, N, M, seen, counted, below);
   return hipGetLastError();
 }
 

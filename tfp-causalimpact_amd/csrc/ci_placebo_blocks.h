@@ -100,4 +100,95 @@ __global__ __launch_bounds__(64) void placebo_blocks_kernel(PlaceboBlocksArgs k)
     for (; slot < NO; ++slot) out[(size_t)slot * N] = 0.0;
 }
 
+// The SIMULATED placebo forecasts of ci_placebo.h (placebo_sim_kernel: its definition, line by line)
+// for the block models: the branch is the filter's own step -- pb_moments, pb_update,
+// pb_transition<G, false> -- on the copy, fed with v = sqrt(F) z.  Every lane of a group forms the
+// same normal from the group's (chain, draw): nothing crosses lanes for it.  Lane 0 stores.
+struct PlaceboBlocksSimArgs {
+  PlaceboSimArgs s;                // s.q.p as PredBlocksArgs::p
+  BlockModel m;
+};
+
+// grid (ceil(N / (64 / G)), series of the launch), block 64.
+template <int G, int LINK>
+__global__ __launch_bounds__(64) void placebo_blocks_sim_kernel(PlaceboBlocksSimArgs k) {
+  constexpr int FPW = 64 / G;
+  __shared__ PbShared sh;
+  const PredArgs& p = k.s.q.p;
+  const int N = p.N, T = p.T, NO = k.s.q.O;
+  const int n_own = blockIdx.x * FPW + (int)threadIdx.x / G;
+  const bool active = n_own < N;
+  const int n = active ? n_own : N - 1;
+  const size_t e = blockIdx.y, b = (size_t)k.s.b0 + e, bn = b * N + n;
+  PbCtx c;
+  double H, a, P[G];
+  pb_begin<G>(p, k.m, sh, b, bn, c, H, a, P);
+  const bool writer = active && c.i == 0;
+  const double scale = p.scales[b], shift = p.shifts[b];
+  const float* y = p.y + b * T;
+  const uint8_t* mask = p.mask + b * T;
+  const double* reg = p.reg ? p.reg + b * T * N + n : nullptr;
+  double* out = p.out + e * NO * N + n;
+  int* counted = writer && n == 0 ? k.s.counted + e * NO : nullptr;
+  const int* org = k.s.q.origins + b * NO;
+  const int Hb = k.s.q.horizon[b];
+  Rng rng;
+  rng.k0 = k.s.keys[2 * b];
+  rng.k1 = k.s.keys[2 * b + 1];
+  rng.chain = k.s.chain_offset + (uint32_t)(n / k.s.kept);
+  const uint32_t iter = (uint32_t)(n % k.s.kept);
+
+  int slot = 0;
+  int next = org[0];                             // uniform over the wavefront, as everything of the origins
+  double unused = 0.0;
+  for (int t = 0; t < T && next >= 0; ++t) {
+    if (t == next) {
+      // the simulated branch, from a copy of the predicted moments
+      double fa = a, fP[G];
+#pragma unroll
+      for (int j = 0; j < G; ++j) fP[j] = P[j];
+      double S = 0.0, z0 = 0.0, z1 = 0.0;
+      U4 r4 = {0u, 0u, 0u, 0u};
+      int cnt = 0;
+      for (int h = 0; h < Hb; ++h) {
+        const int u = t + h;
+        const double z = placebo_sim_normal(rng, iter, (uint32_t)slot, h, r4, z0, z1);
+        double pz, m, zpz;
+        pb_moments<G>(c, fa, fP, pz, m, zpz);
+        if (mask[u] == 0) {
+          const double F = zpz + H;
+          const double f = m + (reg ? reg[(size_t)u * N] : 0.0);
+          const double v = __dmul_rn(sqrt(F), z);
+          const double ysim = __dadd_rn(f, v);
+          S += link_value<LINK>(__dadd_rn(__dmul_rn(ysim, scale), shift));
+          cnt += 1;
+          pb_update<G>(c, fa, fP, pz, F, v);
+        }
+        if (h + 1 >= Hb) break;
+        pb_transition<G, false>(c, u, fa, unused, fP);
+      }
+      if (writer) out[(size_t)slot * N] = cnt > 0 ? S : 0.0;
+      if (counted) counted[slot] = cnt;
+      ++slot;
+      next = slot < NO ? org[slot] : -1;
+      if (next < 0) break;
+    }
+    // the filter's step t (predict_blocks_kernel)
+    double pz, m, zpz;
+    pb_moments<G>(c, a, P, pz, m, zpz);
+    if (mask[t] == 0) {
+      const double F = zpz + H;
+      const double f = m + (reg ? reg[(size_t)t * N] : 0.0);
+      const double v = (double)y[t] - f;
+      pb_update<G>(c, a, P, pz, F, v);
+    }
+    if (t + 1 >= T) break;
+    pb_transition<G, false>(c, t, a, unused, P);
+  }
+  for (; slot < NO; ++slot) {
+    if (writer) out[(size_t)slot * N] = 0.0;
+    if (counted) counted[slot] = 0;
+  }
+}
+
 }  // namespace ci

@@ -1,5 +1,5 @@
 // Instantiation unit of the block-model placebo forecasts (ci_placebo_blocks.h) and their launch;
-// ci_session_summarize_placebo_blocks (ci_summary.hip) calls it.
+// ci_session_summarize_placebo_blocks and ci_session_simulate_placebo_blocks (ci_summary.hip) call them.
 #include "ci_placebo_blocks.h"
 
 namespace ci {
@@ -23,6 +23,25 @@ hipError_t placebo_blocks_launch(hipStream_t stream, int B, int out, const Place
                            : G == 32 ? placebo_blocks_fn<32>(out) : placebo_blocks_fn<64>(out);
   const int fpw = 64 / G;
   hipLaunchKernelGGL(fn, dim3((args.q.p.N + fpw - 1) / fpw, B), dim3(64), 0, stream, args);
+  return hipGetLastError();
+}
+
+using PlaceboBlocksSimFn = void (*)(PlaceboBlocksSimArgs);
+
+template <int G> static PlaceboBlocksSimFn placebo_blocks_sim_fn(int link) {
+  if (link == LINK_LOG) return placebo_blocks_sim_kernel<G, LINK_LOG>;
+  if (link == LINK_LOG1P) return placebo_blocks_sim_kernel<G, LINK_LOG1P>;
+  return placebo_blocks_sim_kernel<G, LINK_IDENTITY>;
+}
+
+// The simulated totals of `nb` series from args.s.b0 on (placebo_sim_launch's for the block models).
+hipError_t placebo_blocks_sim_launch(hipStream_t stream, int nb, int link, const PlaceboBlocksSimArgs& args) {
+  if (args.m.d < 1 || args.m.d > PB_MAX_STATE || link < 0 || link >= NUM_LINKS) return hipErrorInvalidValue;
+  const int G = blocks_group_size(args.m.d);
+  const PlaceboBlocksSimFn fn = G == 8 ? placebo_blocks_sim_fn<8>(link) : G == 16 ? placebo_blocks_sim_fn<16>(link)
+                              : G == 32 ? placebo_blocks_sim_fn<32>(link) : placebo_blocks_sim_fn<64>(link);
+  const int fpw = 64 / G;
+  hipLaunchKernelGGL(fn, dim3((args.s.q.p.N + fpw - 1) / fpw, nb), dim3(64), 0, stream, args);
   return hipGetLastError();
 }
 

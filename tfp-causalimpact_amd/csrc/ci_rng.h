@@ -18,7 +18,9 @@ enum Site : uint32_t {
   SITE_LEVEL_SCALE = 10, SITE_SLOPE_SCALE = 11, SITE_DRIFT_SCALE = 12, SITE_OBS_SCALE = 13,
   SITE_PRED = 14,
   // HMC extension (ci_hmc.h): momentum, accept uniform, initial jitter
-  SITE_HMC_MOMENTUM = 15, SITE_HMC_ACCEPT = 16, SITE_HMC_INIT = 17
+  SITE_HMC_MOMENTUM = 15, SITE_HMC_ACCEPT = 16, SITE_HMC_INIT = 17,
+  // simulated placebo forecasts (ci_placebo.h): sub = the origin slot, idx = the step of the window
+  SITE_PLACEBO_SIM = 18
 };
 
 struct U4 { uint32_t x, y, z, w; };

@@ -44,6 +44,7 @@ struct ci_session {
   // stride, series b has lengths[b] steps
   bool ragged = false;
   std::vector<int> lengths;
+  std::vector<int> ids;          // the series ids handed to a ragged session (empty: none were)
   DevBuf<int> series_T, series_ids;
   // seasonal models
   int D_full = 0, dred = 0;

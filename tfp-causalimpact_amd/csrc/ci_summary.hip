@@ -1,7 +1,7 @@
 // ci_summary.hip -- the on-device summaries behind the C-ABI (kernels: ci_summary.h,
 // ci_components.h, ci_predict.h): ci_session_summarize, ci_session_summarize_components,
-// ci_session_summarize_predictions, ci_session_summarize_placebo, ci_session_pool_placebo (kernels:
-// ci_placebo.h),
+// ci_session_summarize_predictions, ci_session_summarize_placebo, ci_session_pool_placebo,
+// ci_session_simulate_placebo[_blocks] (kernels: ci_placebo.h, ci_placebo_blocks.h),
 // ci_session_summarize_windows, ci_ll_session_summarize_windows
 // (kernel: ci_windows.h), ci_session_summarize_paths, ci_ll_session_summarize_paths (kernels: ci_paths.h),
 // ci_session_set_link and ci_session_value_mean (the outcome link: ci_link.h),
@@ -146,6 +146,11 @@ hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seas
 // ci_placebo_blocks.h).
 hipError_t predict_blocks_launch(hipStream_t stream, int B, int out, const PredBlocksArgs& args);
 hipError_t placebo_blocks_launch(hipStream_t stream, int B, int out, const PlaceboBlocksArgs& args);
+hipError_t placebo_sim_launch(hipStream_t stream, int nb, int has_slope, int num_seasons, int link,
+                              const PlaceboSimArgs& args);
+hipError_t placebo_blocks_sim_launch(hipStream_t stream, int nb, int link, const PlaceboBlocksSimArgs& args);
+hipError_t placebo_sim_seen_launch(hipStream_t stream, size_t rows, int N, double* M, const double* seen,
+                                   const int* counted, double* below, int rewrite);
 hipError_t placebo_pool_launch(hipStream_t stream, int N, int O, int G, int which, int c0, int c1,
                                const int* offsets, const double* weights, const double* M, double* acc);
 hipError_t placebo_finish_launch(hipStream_t stream, int N, size_t r0, size_t rows, int out,
@@ -909,17 +914,10 @@ int ci_session_summarize_predictions_blocks(ci_session* s, const double* scale, 
                                variance_mean, pit_mean, loglik);
 }
 
-// ci_session_summarize_placebo and, with `blocks`, ci_session_summarize_placebo_blocks, likewise.
-static int summarize_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
-                             int32_t max_origins, const int32_t* origins, const int32_t* horizon,
-                             double* predicted_mean, double* spread_mean, double* pit_mean) {
-  if (!s || !scale || !shift || !origins || !horizon) return fail("NULL argument");
-  const ci_problem& pb = s->pb;          // (not kpb: the inert block of a long trend-only series is no part of the model)
-  if (blocks ? pred_blocks_check_session(s, "ci_session_summarize_placebo_blocks")
-             : pred_check_session(s, "ci_session_summarize_placebo"))
-    return 1;
-  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
-  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins;
+// The origin table of ci_session_summarize_placebo and ci_session_simulate_placebo: max_origins in
+// [1, T], horizon >= 1, every row ascending with -1 only at the end, o + H_b <= T_b.
+static int check_placebo_plan(const ci_session* s, int O, const int32_t* origins, const int32_t* horizon) {
+  const int B = s->pb.num_series, T = s->pb.T;
   if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
   for (int b = 0; b < B; ++b) {
     const int Tb = s->ragged ? s->lengths[b] : T, Hb = horizon[b];
@@ -937,6 +935,21 @@ static int summarize_placebo(ci_session* s, bool blocks, const double* scale, co
         return fail("origins[%d, %d] = %d with horizon %d reaches beyond the series' %d steps", b, i, o, Hb, Tb);
     }
   }
+  return 0;
+}
+
+// ci_session_summarize_placebo and, with `blocks`, ci_session_summarize_placebo_blocks, likewise.
+static int summarize_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
+                             int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                             double* predicted_mean, double* spread_mean, double* pit_mean) {
+  if (!s || !scale || !shift || !origins || !horizon) return fail("NULL argument");
+  const ci_problem& pb = s->pb;          // (not kpb: the inert block of a long trend-only series is no part of the model)
+  if (blocks ? pred_blocks_check_session(s, "ci_session_summarize_placebo_blocks")
+             : pred_check_session(s, "ci_session_summarize_placebo"))
+    return 1;
+  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
+  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins;
+  if (check_placebo_plan(s, O, origins, horizon)) return 1;
   HIP_TRY(hipSetDevice(pb.device));
   SummScratch& w = s->summ;
   if (summ_scratch_alloc(w, B, T, N)) return 1;
@@ -993,6 +1006,136 @@ int ci_session_summarize_placebo_blocks(ci_session* s, const double* scale, cons
                                         double* predicted_mean, double* spread_mean, double* pit_mean) {
   return summarize_placebo(s, true, scale, shift, max_origins, origins, horizon, predicted_mean, spread_mean,
                            pit_mean);
+}
+
+// ci_session_simulate_placebo and, with `blocks`, ci_session_simulate_placebo_blocks: the filter runs
+// ONCE per chunk of series whose rows [nb * O, N] fit the scratch -- simulate into `value`, its row
+// means and order statistics, the rows' download when `totals` is wanted, the count below `seen`,
+// the rewrite to (x - seen)^2 in place and its row means.  TOTAL is a function of (b, slot, n) alone
+// and every statistic one of its row, so nothing depends on where the chunks are cut.  max_rows
+// (tests; 0: the scratch's B * T rows, which hold every call's B * O): the rows of a chunk;
+// num_chunks (may be NULL): how many it took.
+static int simulate_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
+                            int32_t max_origins, const int32_t* origins, const int32_t* horizon, int32_t link,
+                            const double* seen, int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
+                            double* spread_mean, double* below, double* total_order, double* totals,
+                            int64_t max_rows, int32_t* num_chunks) {
+  if (!s || !scale || !shift || !origins || !horizon || !ranks) return fail("NULL argument");
+  const ci_problem& pb = s->pb;          // (not kpb: the inert block of a long trend-only series is no part of the model)
+  const char* who = blocks ? "ci_session_simulate_placebo_blocks" : "ci_session_simulate_placebo";
+  if (blocks ? pred_blocks_check_session(s, who) : pred_check_session(s, who)) return 1;
+  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
+  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins, R = num_ranks;
+  if (check_placebo_plan(s, O, origins, horizon)) return 1;
+  if (link < 0 || link >= ci::NUM_LINKS)
+    return fail("link must be CI_LINK_IDENTITY, CI_LINK_LOG or CI_LINK_LOG1P (0 to %d), got %d", ci::NUM_LINKS - 1, link);
+  if (check_ranks(R, ranks, N)) return 1;
+  if (!seen && (spread_mean || below)) return fail("spread_mean and below need `seen`, which is NULL");
+  const size_t BO = (size_t)B * O;
+  if (max_rows < 0 || (max_rows > 0 && max_rows < O))
+    return fail("max_rows must hold the %d rows of one series, got %lld", O, (long long)max_rows);
+  const size_t cap = max_rows > 0 && (size_t)max_rows < (size_t)B * T ? (size_t)max_rows : (size_t)B * T;
+  const int nb_max = (int)(cap / O);     // (O <= T: at least one series)
+  if (num_chunks) *num_chunks = (B + nb_max - 1) / nb_max;
+  // the Philox key every series' fit ran on (ci_series_stream_key of its id, or the seed itself)
+  std::vector<uint32_t> keys((size_t)2 * B);
+  const int shared = (pb.flags & CI_FLAG_SHARED_SERIES_STREAMS) ? -1 : 0;
+  for (int b = 0; b < B; ++b) {
+    const int sid = s->ids.empty() ? pb.series_offset + b : s->ids[b];
+    keys[2 * b] = ci::stream_key0(pb.seed[0], shared, sid);
+    keys[2 * b + 1] = ci::stream_key1(pb.seed[1], shared, sid);
+  }
+  HIP_TRY(hipSetDevice(pb.device));
+  SummScratch& w = s->summ;
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  hipStream_t stream = s->stream;
+  double* d_scale = w.obs.p + (size_t)B * T;
+  double* d_shift = d_scale + B;
+  if (pred_init_upload(s)) return 1;
+  DevBuf<int> d_plan;                    // origins [B, O], horizon [B], counted [B, O]
+  DevBuf<uint32_t> d_keys;               // [B, 2]
+  DevBuf<double> d_stat;                 // seen, mean, spread, below: [B, O] each
+  HIP_TRY(d_plan.alloc(2 * BO + B));
+  HIP_TRY(d_keys.alloc((size_t)2 * B));
+  HIP_TRY(d_stat.alloc(4 * BO));
+  int* d_counted = d_plan.p + BO + B;
+  double *d_seen = d_stat.p, *d_mean = d_stat.p + BO, *d_spread = d_stat.p + 2 * BO, *d_below = d_stat.p + 3 * BO;
+  HIP_TRY(hipMemcpyAsync(d_plan.p, origins, BO * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_plan.p + BO, horizon, B * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_keys.p, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  if (seen) HIP_TRY(hipMemcpyAsync(d_seen, seen, BO * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
+  const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
+  if (P > 0)
+    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
+                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
+  ci::PlaceboBlocksSimArgs ab;
+  ci::PlaceboSimArgs& a = ab.s;
+  a.q.p.N = N; a.q.p.T = T;
+  a.q.p.y = s->y.p; a.q.p.mask = s->mask.p; a.q.p.season_change = s->season_change.p; a.q.p.series_T = d_series_T;
+  a.q.p.obs = s->o_obs.p; a.q.p.lscale = s->o_lscale.p; a.q.p.sscale = s->o_sscale.p; a.q.p.drift = s->o_drift.p;
+  a.q.p.init = s->pred_init.p; a.q.p.scales = d_scale; a.q.p.shifts = d_shift;
+  a.q.p.reg = P > 0 ? w.cum.p : nullptr;
+  a.q.p.out = w.value.p; a.q.p.ll = nullptr;
+  a.q.O = O; a.q.origins = d_plan.p; a.q.horizon = d_plan.p + BO;
+  a.kept = pb.num_results; a.chain_offset = (uint32_t)pb.chain_offset; a.keys = d_keys.p;
+  if (blocks) ab.m = pred_block_model(pb);
+  for (int b0 = 0; b0 < B; b0 += nb_max) {
+    const int nb = B - b0 < nb_max ? B - b0 : nb_max;
+    const size_t rows = (size_t)nb * O, off = (size_t)b0 * O;
+    a.b0 = b0;
+    a.counted = d_counted + off;
+    if (blocks) HIP_TRY(ci::placebo_blocks_sim_launch(stream, nb, link, ab));
+    else HIP_TRY(ci::placebo_sim_launch(stream, nb, pb.has_slope, NS, link, a));
+    if (predicted_mean) HIP_TRY(ci::comp_launch_row_stats(stream, rows, N, w.value.p, d_mean + off, nullptr));
+    if (total_order)
+      HIP_TRY(launch_select(stream, N, O, (int)rows, R, w.ranks.p, w.value.p, nullptr,
+                            w.order.p + (size_t)b0 * R * O, nullptr));
+    if (totals) {
+      HIP_TRY(hipStreamSynchronize(stream));
+      HIP_TRY(hipMemcpy(totals + off * N, w.value.p, rows * N * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (spread_mean || below) {
+      HIP_TRY(ci::placebo_sim_seen_launch(stream, rows, N, w.value.p, d_seen + off, d_counted + off,
+                                          below ? d_below + off : nullptr, spread_mean != nullptr));
+      if (spread_mean) HIP_TRY(ci::comp_launch_row_stats(stream, rows, N, w.value.p, d_spread + off, nullptr));
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (predicted_mean) HIP_TRY(hipMemcpy(predicted_mean, d_mean, BO * sizeof(double), hipMemcpyDeviceToHost));
+  if (spread_mean) HIP_TRY(hipMemcpy(spread_mean, d_spread, BO * sizeof(double), hipMemcpyDeviceToHost));
+  if (below) HIP_TRY(hipMemcpy(below, d_below, BO * sizeof(double), hipMemcpyDeviceToHost));
+  if (total_order)
+    HIP_TRY(hipMemcpy(total_order, w.order.p, BO * R * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int ci_session_simulate_placebo(ci_session* s, const double* scale, const double* shift, int32_t max_origins,
+                                const int32_t* origins, const int32_t* horizon, int32_t link, const double* seen,
+                                int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
+                                double* spread_mean, double* below, double* total_order, double* totals) {
+  return simulate_placebo(s, false, scale, shift, max_origins, origins, horizon, link, seen, num_ranks, ranks,
+                          predicted_mean, spread_mean, below, total_order, totals, 0, nullptr);
+}
+
+int ci_session_simulate_placebo_blocks(ci_session* s, const double* scale, const double* shift,
+                                       int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                       int32_t link, const double* seen, int32_t num_ranks, const int32_t* ranks,
+                                       double* predicted_mean, double* spread_mean, double* below,
+                                       double* total_order, double* totals) {
+  return simulate_placebo(s, true, scale, shift, max_origins, origins, horizon, link, seen, num_ranks, ranks,
+                          predicted_mean, spread_mean, below, total_order, totals, 0, nullptr);
+}
+
+int ci_test_session_simulate_placebo(ci_session* s, int32_t blocks, const double* scale, const double* shift,
+                                     int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                     int32_t link, const double* seen, int32_t num_ranks, const int32_t* ranks,
+                                     double* predicted_mean, double* spread_mean, double* below,
+                                     double* total_order, double* totals, int64_t max_rows, int32_t* num_chunks) {
+  return simulate_placebo(s, blocks != 0, scale, shift, max_origins, origins, horizon, link, seen, num_ranks, ranks,
+                          predicted_mean, spread_mean, below, total_order, totals, max_rows, num_chunks);
 }
 
 // The placebo forecasts of POOLED sums: per group, slot and draw the weighted sum S of the members'
