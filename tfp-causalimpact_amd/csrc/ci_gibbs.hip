@@ -41,6 +41,46 @@ static __global__ void test_rng_kernel(uint32_t k0, uint32_t k1, uint32_t chain,
   }
 }
 
+// ------------------------------------------------------------------------------------
+// the tail of a streamed fit (ci_session_run_streamed): what is left when the sampler ends
+// ------------------------------------------------------------------------------------
+// One result array's share of the tail: nseg runs of seg_len floats, seg_stride floats apart, at
+// the same offsets in source (HBM) and destination (the device address of pinned host memory).
+struct TailSeg {
+  float* dst;
+  const float* src;
+  unsigned long long seg_len, seg_stride;
+  unsigned int nseg;
+};
+constexpr int TAIL_MAX = 10;        // the members of ci_outputs
+constexpr int TAIL_PART = 1024;     // floats per work item: one float4 per thread
+constexpr int TAIL_BLOCKS = 64;     // workgroups per array
+struct TailArgs { TailSeg e[TAIL_MAX]; };
+
+// Launched with grid (TAIL_BLOCKS, arrays) behind the sampler on its stream: writes the rows of the
+// last chunk and the arrays without a time axis straight into the caller's pinned buffers, with
+// 16-byte stores wherever source and destination are aligned alike.
+static __global__ __launch_bounds__(256) void tail_gather_kernel(TailArgs a) {
+  const TailSeg e = a.e[blockIdx.y];
+  const size_t parts = (e.seg_len + TAIL_PART - 1) / TAIL_PART;
+  const size_t items = parts * e.nseg;
+  const size_t tid = threadIdx.x;
+  for (size_t it = blockIdx.x; it < items; it += gridDim.x) {
+    const size_t seg = it / parts, lo = (it % parts) * TAIL_PART;
+    const size_t n = e.seg_len - lo < (size_t)TAIL_PART ? e.seg_len - lo : (size_t)TAIL_PART;
+    float* d = e.dst + seg * e.seg_stride + lo;
+    const float* s = e.src + seg * e.seg_stride + lo;
+    size_t head = (4 - (((uintptr_t)d >> 2) & 3)) & 3;      // floats up to d's 16-byte boundary
+    if (head > n || (((uintptr_t)(s + head)) & 15) != 0) head = n;   // (s not aligned like d: all scalar)
+    for (size_t i = tid; i < head; i += blockDim.x) d[i] = s[i];
+    const size_t nv = (n - head) / 4;
+    const float4* s4 = reinterpret_cast<const float4*>(s + head);
+    float4* d4 = reinterpret_cast<float4*>(d + head);
+    for (size_t i = tid; i < nv; i += blockDim.x) d4[i] = s4[i];
+    for (size_t i = head + nv * 4 + tid; i < n; i += blockDim.x) d[i] = s[i];
+  }
+}
+
 }  // namespace ci
 
 extern "C" {
@@ -579,6 +619,46 @@ int ci_session_run(ci_session* s, float* kernel_ms) {
 
 // The [B*C, S, T] arrays of a session, paired with the caller's buffers.
 struct BigPair { float* dst; const float* src; size_t row; };
+// An array without a time axis per draw: complete, like the last chunk, when the sampler ends.
+struct SmallPair { float* dst; const float* src; size_t n; };
+
+// Tails of up to this many bytes go through tail_gather_kernel, larger ones to the copy engines
+// (with chunk_draws >= S the whole result is "the last chunk").  -DCI_TAIL_GATHER_MAX_BYTES=0
+// builds the library without the kernel's use: every tail through copies behind the wait on ev1.
+// Measured at cfg2's shape (T = 1000, P = 11, 8 chains, three [S, T] arrays to pinned memory;
+// profiles/streamed_tail_parent_vs_branch.jsonl, "kind": "tail_sweep"), step time minus kernel
+// time in us, copies -> kernel: 1.25 MB 168 -> 73, 2.0 MB 147 -> 65, 3.1 MB 146 -> 83, 6.3 MB
+// 202 -> 140, 12.5 MB 311 -> 257, 25 MB 542 -> 481, 50 MB 982 -> 936, 96 MB (chunk_draws = S)
+// 1798 -> 1775.  Both move the bytes at the link's rate (~55 GB/s); what the kernel saves is a
+// constant 50-95 us of command latency.  Up to 12.5 MB that is 17 % of the tail or more; beyond
+// 16 MiB it is a tenth or less, paid for with up to 640 workgroups held for the length of a PCIe
+// transfer on a device other sessions may be sampling on -- there the copy engines keep the work.
+#ifndef CI_TAIL_GATHER_MAX_BYTES
+#define CI_TAIL_GATHER_MAX_BYTES (16u << 20)
+#endif
+
+// The device's address of `p` if `p` is the start of a block of pinned host memory that kernels
+// can write; NULL for pageable (or unknown) memory, which only a staged copy reaches.
+static float* pinned_device_address(float* p) {
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof(at));
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();        // an unregistered pointer is no error of this fit
+    return nullptr;
+  }
+  if (at.type != hipMemoryTypeHost || at.hostPointer != (void*)p) return nullptr;
+  return (float*)at.devicePointer;
+}
+
+// Leaves both streams of a streamed run idle when the run is left early.
+struct StreamsIdle {
+  ci_session* s;
+  ~StreamsIdle() {
+    if (!s) return;
+    (void)hipStreamSynchronize(s->copy_stream);
+    (void)hipStreamSynchronize(s->stream);
+  }
+};
 
 int ci_session_run_streamed(ci_session* s, ci_outputs* o, int32_t chunk_draws, float* kernel_ms) {
   if (!s || !o) return fail("NULL argument");
@@ -607,10 +687,51 @@ int ci_session_run_streamed(ci_session* s, ci_outputs* o, int32_t chunk_draws, f
   if (o->slope && pb.has_slope) big.push_back({o->slope, s->o_slope.p, (size_t)T});
   if (o->posterior_trajectories) big.push_back({o->posterior_trajectories, s->o_traj.p, (size_t)T});
   if (o->seasonal_levels && s->o_seasonal.n) big.push_back({o->seasonal_levels, s->o_seasonal.p, (size_t)T * K});
+  const SmallPair small[] = {
+      {o->observation_noise_scale, s->o_obs.p, s->o_obs.n}, {o->level_scale, s->o_lscale.p, s->o_lscale.n},
+      {o->slope_scale, s->o_sscale.p, s->o_sscale.n},       {o->weights, s->o_w.p, s->o_w.n},
+      {o->posterior_means, s->o_pm.p, s->o_pm.n},           {o->seasonal_drift_scales, s->o_drift.p, s->o_drift.n}};
+  // From here on copies and kernels that write the caller's buffers are in flight: whatever the
+  // way out, both streams are idle before the caller gets its buffers (and the pool its streams) back.
+  StreamsIdle idle{s};
+  // The tail -- the last chunk's rows and the arrays without a time axis -- is known now, and so is
+  // when it is ready: at ev1.  It is queued while the sampler runs, so that nothing is left for the
+  // host to submit once the GPU has gone idle.  Arrays the device can write itself (pinned
+  // destinations) go through ONE gather kernel behind ev1 on the sampler's stream; the others
+  // through copies behind a wait on ev1.
+  const int tail_next = (S - 1) / chunk_draws * chunk_draws;      // first draw of the last chunk
+  size_t tail_bytes = 0;
+  for (const BigPair& b : big) tail_bytes += BC * (size_t)(S - tail_next) * b.row * sizeof(float);
+  for (const SmallPair& m : small) tail_bytes += m.dst ? m.n * sizeof(float) : 0;
+  bool big_gathered[4] = {false, false, false, false}, small_gathered[6] = {false, false, false, false, false, false};
+  ci::TailArgs ta;
+  int ng = 0;
+  if (tail_bytes <= (size_t)CI_TAIL_GATHER_MAX_BYTES) {
+    for (size_t i = 0; i < big.size(); ++i)
+      if (float* d = pinned_device_address(big[i].dst)) {
+        const size_t off = (size_t)tail_next * big[i].row;
+        ta.e[ng++] = {d + off, big[i].src + off, (size_t)(S - tail_next) * big[i].row, (size_t)S * big[i].row,
+                      (unsigned int)BC};
+        big_gathered[i] = true;
+      }
+    for (int i = 0; i < 6; ++i)
+      if (small[i].dst && small[i].n)
+        if (float* d = pinned_device_address(small[i].dst)) {
+          ta.e[ng++] = {d, small[i].src, small[i].n, 0, 1u};
+          small_gathered[i] = true;
+        }
+    if (ng) {
+      hipLaunchKernelGGL(ci::tail_gather_kernel, dim3(ci::TAIL_BLOCKS, ng), dim3(256), 0, s->stream, ta);
+      HIP_TRY(hipGetLastError());
+    }
+  }
   int next = 0;
   while (next < S) {
     const int target = std::min(S, next + chunk_draws);
-    if (live) {
+    if (live && target == S) {
+      // the last chunk: no waiting for its progress value, the copies wait for the kernel's end
+      HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev1, 0));
+    } else if (live) {
       // wait until every chain has published `target` complete draws
       for (;;) {
         unsigned int lo = 0xFFFFFFFFu;
@@ -625,7 +746,9 @@ int ci_session_run_streamed(ci_session* s, ci_outputs* o, int32_t chunk_draws, f
     } else if (next == 0) {
       HIP_TRY(hipStreamSynchronize(s->stream));
     }
-    for (const BigPair& b : big) {
+    for (size_t i = 0; i < big.size(); ++i) {
+      if (target == S && big_gathered[i]) continue;
+      const BigPair& b = big[i];
       const size_t pitch = (size_t)S * b.row * sizeof(float);
       HIP_TRY(hipMemcpy2DAsync(b.dst + (size_t)next * b.row, pitch, b.src + (size_t)next * b.row, pitch,
                                (size_t)(target - next) * b.row * sizeof(float), BC,
@@ -633,10 +756,22 @@ int ci_session_run_streamed(ci_session* s, ci_outputs* o, int32_t chunk_draws, f
     }
     next = target;
   }
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  for (int i = 0; i < 6; ++i)
+    if (small[i].dst && small[i].n && !small_gathered[i])
+      HIP_TRY(hipMemcpyAsync(small[i].dst, small[i].src, small[i].n * sizeof(float), hipMemcpyDeviceToHost,
+                             s->copy_stream));
+  // ONE wait for the copies (they end after the sampler: gated on ev1, or queued after it had
+  // ended); the sampler's stream, with the gather kernel, is then idle or about to be.  A failed
+  // kernel is reported from its own stream first.
+  const hipError_t copied = hipStreamSynchronize(s->copy_stream);
+  const hipError_t sampled = hipStreamSynchronize(s->stream);
+  if (sampled != hipSuccess) return fail("Gibbs kernel failed: %s", hipGetErrorString(sampled));
+  if (copied != hipSuccess) return fail("copying the results failed: %s", hipGetErrorString(copied));
+  idle.s = nullptr;
   if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, s->ev0, s->ev1));
   s->ran = true;
-  return copy_outputs(o, s->outputs(), s->copy_stream);
+  if (o->slope && !pb.has_slope) memset(o->slope, 0, s->o_level.n * sizeof(float));
+  return 0;
 }
 
 

@@ -64,10 +64,9 @@ template <class T> struct DevBuf {
 };
 
 // Copies a device array into the caller's buffer when the caller wants it (dst non-null) and the
-// fit has it: synchronously, or queued on `stream` when one is given.
-template <class T> hipError_t copy_out(T* dst, const DevBuf<T>& src, hipStream_t stream = nullptr) {
+// fit has it.
+template <class T> hipError_t copy_out(T* dst, const DevBuf<T>& src) {
   if (!dst || src.n == 0) return hipSuccess;
-  if (stream) return hipMemcpyAsync(dst, src.p, src.n * sizeof(T), hipMemcpyDeviceToHost, stream);
   return hipMemcpy(dst, src.p, src.n * sizeof(T), hipMemcpyDeviceToHost);
 }
 
@@ -76,24 +75,19 @@ template <class T> struct OutBufs {
   const DevBuf<T> &obs, &lscale, &sscale, &w, &level, &slope, &pm, &traj, &drift, &seasonal;
   bool has_slope;
 };
-// Copies out every array the caller asked for; `slope` of a model without one reads 0.  With a
-// stream: the arrays without a time axis per draw only, queued on it and waited for (a streamed
-// run has copied the others in chunks already).
-template <class O, class T> int copy_outputs(O* o, const OutBufs<T>& b, hipStream_t stream = nullptr) {
-  HIP_TRY(copy_out(o->observation_noise_scale, b.obs, stream));
-  HIP_TRY(copy_out(o->level_scale, b.lscale, stream));
-  HIP_TRY(copy_out(o->slope_scale, b.sscale, stream));
-  HIP_TRY(copy_out(o->weights, b.w, stream));
-  HIP_TRY(copy_out(o->posterior_means, b.pm, stream));
-  HIP_TRY(copy_out(o->seasonal_drift_scales, b.drift, stream));
-  if (stream) {
-    HIP_TRY(hipStreamSynchronize(stream));
-  } else {
-    HIP_TRY(copy_out(o->level, b.level));
-    HIP_TRY(copy_out(o->posterior_trajectories, b.traj));
-    HIP_TRY(copy_out(o->seasonal_levels, b.seasonal));
-    if (o->slope && b.has_slope) HIP_TRY(copy_out(o->slope, b.slope));
-  }
+// Copies out every array the caller asked for; `slope` of a model without one reads 0.  (A streamed
+// run delivers its results itself: ci_session_run_streamed.)
+template <class O, class T> int copy_outputs(O* o, const OutBufs<T>& b) {
+  HIP_TRY(copy_out(o->observation_noise_scale, b.obs));
+  HIP_TRY(copy_out(o->level_scale, b.lscale));
+  HIP_TRY(copy_out(o->slope_scale, b.sscale));
+  HIP_TRY(copy_out(o->weights, b.w));
+  HIP_TRY(copy_out(o->posterior_means, b.pm));
+  HIP_TRY(copy_out(o->seasonal_drift_scales, b.drift));
+  HIP_TRY(copy_out(o->level, b.level));
+  HIP_TRY(copy_out(o->posterior_trajectories, b.traj));
+  HIP_TRY(copy_out(o->seasonal_levels, b.seasonal));
+  if (o->slope && b.has_slope) HIP_TRY(copy_out(o->slope, b.slope));
   if (o->slope && !b.has_slope) memset(o->slope, 0, b.level.n * sizeof(T));
   return 0;
 }
