@@ -544,6 +544,28 @@ int ci_session_pool_placebo(ci_session* session, const double* scale, const doub
                             const int32_t* origins /* [K, O] */, const int32_t* horizon /* [G] */,
                             const double* init, double* out, const double* seen,
                             double* predicted_mean, double* spread_mean, double* pit_mean);
+/* ci_session_pool_placebo with the filter of ci_session_summarize_placebo_blocks: the pooled placebo
+ * forecasts of ANY block list whose state has at most 64 components.  Additive: CI_ABI_VERSION stays
+ * 5; look the symbol up (dlsym) where an older library may be met.  The arguments, the group table,
+ * s and v, the order of addition, init / out [G, O, 2, N] and their aliasing, seen and the three means
+ * are those of ci_session_pool_placebo; only this differs:
+ *   the model, Z, the transition and the filter of entry k are those of .._summarize_placebo_blocks
+ *     (a group of 8, 16, 32 or 64 lanes per (entry, draw)), so C, V and cnt are its values;
+ *   the filter runs ONCE per chunk of at most B entries: one forecast branch stores s into the
+ *     scratch of ci_session_summarize and v into a buffer of the call's own, [chunk, O, N]; the two
+ *     accumulates and the finishing step are the kernels of ci_session_pool_placebo.  Where the two
+ *     filters agree bit for bit (the models both take) so do the accumulators and the means.
+ * Sessions: those of ci_session_summarize_placebo_blocks -- a finished ci_session of
+ * ci_session_create, its state at most 64; a ragged session is refused (its models belong to
+ * ci_session_pool_placebo).
+ * Checked before any device call: as ci_session_pool_placebo, with the state's size in place of its
+ * block list. */
+int ci_session_pool_placebo_blocks(ci_session* session, const double* scale, const double* shift,
+                                   int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                   const double* weights, int32_t max_origins,
+                                   const int32_t* origins /* [K, O] */, const int32_t* horizon /* [G] */,
+                                   const double* init, double* out, const double* seen,
+                                   double* predicted_mean, double* spread_mean, double* pit_mean);
 /* Per-draw totals over SUB-WINDOWS of the session's steps, for all B series at once: how an effect
  * unfolds inside the post-period (week 1 against week 4, a promotion's second phase), whose bands,
  * relative effect and tail-area probability need every draw's total over the window and are not
@@ -993,6 +1015,15 @@ int ci_test_session_simulate_placebo(ci_session* session, int32_t blocks, const 
                                      int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
                                      double* spread_mean, double* below, double* total_order,
                                      double* totals, int64_t max_rows, int32_t* num_chunks);
+/* ci_session_pool_placebo_blocks with the entries of a chunk handed in (chunk_entries in [1, B] in
+ * place of B), likewise: the result does not depend on where the entries are cut. */
+int ci_test_session_pool_placebo_blocks(ci_session* session, const double* scale, const double* shift,
+                                        int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                        const double* weights, int32_t max_origins,
+                                        const int32_t* origins /* [K, O] */, const int32_t* horizon /* [G] */,
+                                        const double* init, double* out, const double* seen,
+                                        double* predicted_mean, double* spread_mean, double* pit_mean,
+                                        int32_t chunk_entries);
 
 #ifdef __cplusplus
 }

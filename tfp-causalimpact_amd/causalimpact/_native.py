@@ -146,6 +146,11 @@ def load():
   if hasattr(L, "ci_session_pool_placebo"):            # (additive, likewise)
     L.ci_session_pool_placebo.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 +
                                           [C.c_int32] + [C.c_void_p] * 8)
+  for name in ("ci_session_pool_placebo_blocks", "ci_test_session_pool_placebo_blocks"):
+    if hasattr(L, name):                               # (additive, likewise)
+      getattr(L, name).argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 +
+                                   [C.c_int32] + [C.c_void_p] * 8 +
+                                   ([C.c_int32] if name.startswith("ci_test_") else []))
   if hasattr(L, "ci_session_set_link"):                # (additive, likewise)
     L.ci_session_set_link.argtypes = [C.c_void_p, C.c_int32]
     L.ci_session_value_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -235,6 +240,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_summarize_paths", "ci_ll_session_summarize_paths",
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
           "ci_session_pool_event_trajectories", "ci_session_pool_placebo",
+          "ci_session_pool_placebo_blocks",
           "ci_session_simulate_placebo", "ci_session_simulate_placebo_blocks",
           "ci_session_set_link", "ci_session_value_mean",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
@@ -245,7 +251,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_comm_all_reduce", "ci_comm_all_gather", "ci_comm_session_all_gather",
           "ci_comm_ll_session_all_gather", "ci_comm_destroy", "ci_test_rng",
           "ci_test_dk_draw", "ci_test_session_summarize_paths", "ci_test_summarize_draw_paths_f64",
-          "ci_test_session_simulate_placebo")
+          "ci_test_session_simulate_placebo", "ci_test_session_pool_placebo_blocks")
 
 
 def _check(rc: int):
@@ -1314,7 +1320,8 @@ class Session:
     return _pool_call(fn, self._h, pb.num_series, pb.num_chains * pb.num_results, pb.T, scale, shift,
                       groups, init, True, out_stride)
 
-  def pool_placebo(self, scale, shift, groups, origins, horizon, init=None, seen=None) -> Dict[str, np.ndarray]:
+  def pool_placebo(self, scale, shift, groups, origins, horizon, init=None, seen=None, *,
+                   _entry="ci_session_pool_placebo", _tail=()) -> Dict[str, np.ndarray]:
     """Placebo forecasts of POOLED sums (ci_session_pool_placebo): `summarize_placebo`'s forecasts of
     the members of every group, added draw by draw with the group's weights, and the members'
     predictive variances added with the squared weights -- float64, entries ascending, one rounding
@@ -1327,9 +1334,9 @@ class Session:
     data scale, or None.  Returns acc [G, O, 2, N] (S, then U) and, with `seen`, predicted_mean,
     spread_mean, pit_mean [G, O] (`finish_placebo_host`).  Given every member's draw the pooled sum
     is N(S, U) IF the members are independent of each other: the assumption this check tests."""
-    fn = getattr(self._lib, "ci_session_pool_placebo", None)
+    fn = getattr(self._lib, _entry, None)
     if fn is None:
-      raise NativeError("the loaded library has no ci_session_pool_placebo: rebuild it")
+      raise NativeError(f"the loaded library has no {_entry}: rebuild it")
     pb = self.pb
     B, N = pb.num_series, pb.num_chains * pb.num_results
     sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
@@ -1373,8 +1380,21 @@ class Session:
       out.update({k: np.empty((G, O), np.float64) for k in PLACEBO_OUTPUTS})
     _check(fn(self._h, sc.ctypes.data, sh.ctypes.data, G, offsets.ctypes.data, members.ctypes.data,
               weights.ctypes.data, O, org.ctypes.data, hz.ctypes.data, _ptr(init), out["acc"].ctypes.data,
-              _ptr(seen), *[_ptr(out.get(k)) for k in PLACEBO_OUTPUTS]))
+              _ptr(seen), *[_ptr(out.get(k)) for k in PLACEBO_OUTPUTS], *_tail))
     return out
+
+  def pool_placebo_blocks(self, scale, shift, groups, origins, horizon, init=None, seen=None,
+                          chunk_entries=None) -> Dict[str, np.ndarray]:
+    """`pool_placebo` for any block list whose state has at most 64 components
+    (ci_session_pool_placebo_blocks): same arguments, same outputs; the filter of
+    `summarize_placebo_blocks` runs once per chunk of entries for both pooled terms.  Ragged sessions
+    stay with `pool_placebo`.  chunk_entries (tests): the entries of a chunk, in [1, B], in place of B
+    (ci_test_session_pool_placebo_blocks); the result does not depend on it."""
+    if chunk_entries is None:
+      return self.pool_placebo(scale, shift, groups, origins, horizon, init, seen,
+                               _entry="ci_session_pool_placebo_blocks")
+    return self.pool_placebo(scale, shift, groups, origins, horizon, init, seen,
+                             _entry="ci_test_session_pool_placebo_blocks", _tail=(int(chunk_entries),))
 
   def close(self):
     if self._h:

@@ -1565,6 +1565,20 @@ class HostPlaceboPool:
     return _native.finish_placebo_host(self.acc, observed["seen_sum"]), observed
 
 
+def placebo_pool_route(sess, has_slope: bool, num_seasons: Sequence[int]) -> str:
+  """Where the pooled placebo forecasts of the open session `sess` are filtered: "one_lane"
+  (`pool_placebo`: a trend with at most one block of 2 to 7 seasons), "blocks" (`pool_placebo_blocks`:
+  any other block list whose state the block-model filter takes) or "host" (numpy, from the
+  parameter draws: HMC and float64 sessions, a library without the entry, a wider state)."""
+  if "placebo" not in getattr(sess, "summaries", ()):
+    return "host"
+  if hasattr(sess, "pool_placebo") and lib.device_predictions_supported(num_seasons):
+    return "one_lane"
+  if hasattr(sess, "pool_placebo_blocks") and lib.device_block_predictions_supported(has_slope, num_seasons):
+    return "blocks"
+  return "host"
+
+
 class _PlaceboChain(_PoolChain):
   """The second chain of a fit with aggregates and `placebo=`: the accumulators [G, O, 2, N] of the
   pooled placebo forecasts (csrc/ci_placebo.h, ci_session_pool_placebo), handed from launch to launch
@@ -1592,26 +1606,27 @@ class _PlaceboChain(_PoolChain):
 
   def session_pool(self, sess, scale, shift, series_inputs=None, observed=None):
     """(pool, finish) of the open session `sess`: pool(groups, origins, horizon, init) -> acc of the
-    groups handed in, finish(acc, seen) -> the three means.  A session with `pool_placebo` whose model
-    the device filter takes runs both on the device; any other (HMC, several blocks) filters its
-    members in numpy from the parameter draws it holds (`lib._placebo_entry_host`) and pools with the
-    host twin."""
-    on_device = (hasattr(sess, "pool_placebo") and "placebo" in sess.summaries and
-                 lib.device_predictions_supported(series_inputs[0].num_seasons))
-    if on_device:
+    groups handed in, finish(acc, seen) -> the three means.  `placebo_pool_route` chooses: a session
+    whose model the one-lane filter takes runs both through `pool_placebo`, one whose model the
+    block-model filter takes through `pool_placebo_blocks`; any other (HMC, a state beyond 64) filters
+    its members in numpy from the parameter draws it holds (`lib._placebo_entry_host`) and pools with
+    the host twin."""
+    route = placebo_pool_route(sess, series_inputs[0].has_slope, series_inputs[0].num_seasons)
+    if route != "host":
       T, B = int(sess.pb.T), int(sess.pb.num_series)
+      entry = sess.pool_placebo if route == "one_lane" else sess.pool_placebo_blocks
 
       def pool(groups, origins, horizon, init):
-        return sess.pool_placebo(scale, shift, groups, origins, horizon, init)["acc"]
+        return entry(scale, shift, groups, origins, horizon, init)["acc"]
 
       def finish(acc, seen):
         # no slot row is longer than the session's steps: as many slots at a time as it takes
         out = {k: np.zeros(seen.shape) for k in _native.PLACEBO_OUTPUTS}
         for j in range(0, acc.shape[1], T):
           w = min(T, acc.shape[1] - j)
-          got = sess.pool_placebo(scale, shift, [{}] * acc.shape[0], np.full((B, w), -1, np.int32),
-                                  np.ones(acc.shape[0], np.int32), np.ascontiguousarray(acc[:, j:j + w]),
-                                  np.ascontiguousarray(seen[:, j:j + w]))
+          got = entry(scale, shift, [{}] * acc.shape[0], np.full((B, w), -1, np.int32),
+                      np.ones(acc.shape[0], np.int32), np.ascontiguousarray(acc[:, j:j + w]),
+                      np.ascontiguousarray(seen[:, j:j + w]))
           for k in out:
             out[k][:, j:j + w] = got[k]
         return out
@@ -2184,8 +2199,9 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   `PLACEBO_COLUMNS` on the batch's index: the origins and the horizon every series has) and
   `placebo_quality`, and `result.aggregate_placebo_quality` has one row per aggregate.  The members'
   forecasts are added draw by draw with the group's weights, their variances with the squared weights,
-  where the draws lie (csrc/ci_placebo.h, ci_session_pool_placebo), chained from launch to launch like
-  the trajectories' sums; in numpy (`_native.pool_placebo_host`) on the routes that filter there.
+  where the draws lie (csrc/ci_placebo.h, ci_session_pool_placebo; for any other block list up to 64
+  state components csrc/ci_placebo_blocks.h, ci_session_pool_placebo_blocks), chained from launch to
+  launch like the trajectories' sums; in numpy (`_native.pool_placebo_host`) on the routes that filter there.
   Given every member's draw the pooled sum is normal with these two moments IF the members are
   independent of each other: the assumption the check tests.  `actual` and `n_counted` are the
   weighted sum and the plain sum (member-steps) of the members'.

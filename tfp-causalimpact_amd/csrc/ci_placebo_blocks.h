@@ -9,20 +9,45 @@
 // lane, transformed like the mean.  The OUT selectors SUM, SPREAD, PIT and VAR and the zero slots
 // are unchanged.  The group's lane 0 stores: the result is the [B * O, N] matrix, draws contiguous.
 // The host checks o + H_b <= T for every origin before the launch: no step beyond the series is read.
+//
+// With an ENTRY TABLE (q.series_of; ci_session_pool_placebo_blocks) the grid's rows are entries as in
+// ci_placebo.h: entry e filters series series_of[e] with the origins' row e and horizon[e] and writes
+// rows e * O .. of its outputs.  That build has the selector SUM_VAR: from ONE forecast branch lane 0
+// stores SUM into `out` and VAR into `var`, the expressions of the two selectors, both 0 where
+// cnt == 0 and in the unused slots -- the filter runs once for both terms of a pooled sum.  The entry
+// is uniform over the workgroup: every barrier is met by all 64 lanes as before.
 #pragma once
+#include <type_traits>
+
 #include "ci_placebo.h"
 #include "ci_predict_blocks.h"
 
 namespace ci {
 
+constexpr int PLACEBO_SUM_VAR = 4;  // (entry-table build only) SUM into `out` and VAR into `var`
+
 struct PlaceboBlocksArgs {
-  PlaceboArgs q;                   // q.p as PredBlocksArgs::p; q.series_of unused
+  PlaceboArgs q;                   // q.p as PredBlocksArgs::p; q.series_of read by the entry-table build only
   BlockModel m;
 };
 
-// grid (ceil(N / (64 / G)), B), block 64.
-template <int G, int OUT>
-__global__ __launch_bounds__(64) void placebo_blocks_kernel(PlaceboBlocksArgs k) {
+struct PlaceboBlocksPoolArgs : PlaceboBlocksArgs {   // q.series_of [E], q.origins [E, O], q.horizon [E], q.p.out [E, O, N]: SUM
+  double* var;                     // [E, O, N]: VAR
+};
+
+// The series of grid row e: with an entry table that of entry e, else e itself.
+template <bool ENTRIES>
+__device__ __forceinline__ size_t pb_series_of(const PlaceboArgs& q, size_t e) {
+  if constexpr (ENTRIES) return (size_t)q.series_of[e];
+  else return e;
+}
+
+// grid (ceil(N / (64 / G)), B), block 64; as placebo_blocks_kernel<G, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs>
+// (the entry-table build) (ceil(N / (64 / G)), E).
+template <int G, int OUT, class ARGS = PlaceboBlocksArgs>
+__global__ __launch_bounds__(64) void placebo_blocks_kernel(ARGS k) {
+  constexpr bool ENTRIES = OUT == PLACEBO_SUM_VAR;
+  static_assert(ENTRIES == std::is_same<ARGS, PlaceboBlocksPoolArgs>::value, "SUM_VAR is the entry-table build's selector");
   constexpr int FPW = 64 / G;
   __shared__ PbShared sh;
   const PredArgs& p = k.q.p;
@@ -30,7 +55,8 @@ __global__ __launch_bounds__(64) void placebo_blocks_kernel(PlaceboBlocksArgs k)
   const int n_own = blockIdx.x * FPW + (int)threadIdx.x / G;
   const bool active = n_own < N;
   const int n = active ? n_own : N - 1;
-  const size_t b = blockIdx.y, bn = b * N + n;
+  const size_t e = blockIdx.y;                   // the grid's row, uniform over the workgroup
+  const size_t b = pb_series_of<ENTRIES>(k.q, e), bn = b * N + n;
   PbCtx c;
   double H, a, P[G];
   pb_begin<G>(p, k.m, sh, b, bn, c, H, a, P);
@@ -39,9 +65,11 @@ __global__ __launch_bounds__(64) void placebo_blocks_kernel(PlaceboBlocksArgs k)
   const float* y = p.y + b * T;
   const uint8_t* mask = p.mask + b * T;
   const double* reg = p.reg ? p.reg + b * T * N + n : nullptr;
-  double* out = p.out + b * NO * N + n;
-  const int* org = k.q.origins + b * NO;
-  const int Hb = k.q.horizon[b];
+  double* out = p.out + e * NO * N + n;
+  double* var = nullptr;
+  if constexpr (ENTRIES) var = k.var + e * NO * N + n;
+  const int* org = k.q.origins + e * NO;
+  const int Hb = k.q.horizon[e];
 
   int slot = 0;
   int next = org[0];                             // uniform over the wavefront, as everything of the origins
@@ -74,12 +102,15 @@ __global__ __launch_bounds__(64) void placebo_blocks_kernel(PlaceboBlocksArgs k)
       double res = 0.0;
       if (cnt > 0) {
         const double err = A - C;
-        if (OUT == PLACEBO_SUM) res = __dadd_rn(__dmul_rn(C, scale), __dmul_rn((double)cnt, shift));
+        if (OUT == PLACEBO_SUM || OUT == PLACEBO_SUM_VAR) res = __dadd_rn(__dmul_rn(C, scale), __dmul_rn((double)cnt, shift));
         else if (OUT == PLACEBO_SPREAD) res = __dmul_rn(__dmul_rn(__dadd_rn(V, __dmul_rn(err, err)), scale), scale);
         else if (OUT == PLACEBO_VAR) res = __dmul_rn(__dmul_rn(V, scale), scale);
         else res = 0.5 * erfc(-err / sqrt(2.0 * V));
       }
       if (writer) out[(size_t)slot * N] = res;
+      if constexpr (ENTRIES) {
+        if (writer) var[(size_t)slot * N] = cnt > 0 ? __dmul_rn(__dmul_rn(V, scale), scale) : 0.0;
+      }
       ++slot;
       next = slot < NO ? org[slot] : -1;
       if (next < 0) break;
@@ -95,6 +126,10 @@ __global__ __launch_bounds__(64) void placebo_blocks_kernel(PlaceboBlocksArgs k)
     }
     if (t + 1 >= T) break;
     pb_transition<G, false>(c, t, a, unused, P);
+  }
+  if constexpr (ENTRIES) {
+    if (writer)
+      for (int i = slot; i < NO; ++i) var[(size_t)i * N] = 0.0;
   }
   if (writer)
     for (; slot < NO; ++slot) out[(size_t)slot * N] = 0.0;

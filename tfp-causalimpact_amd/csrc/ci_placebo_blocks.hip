@@ -1,5 +1,6 @@
 // Instantiation unit of the block-model placebo forecasts (ci_placebo_blocks.h) and their launch;
-// ci_session_summarize_placebo_blocks and ci_session_simulate_placebo_blocks (ci_summary.hip) call them.
+// ci_session_summarize_placebo_blocks, ci_session_pool_placebo_blocks and ci_session_simulate_placebo_blocks
+// (ci_summary.hip) call them.
 #include "ci_placebo_blocks.h"
 
 namespace ci {
@@ -23,6 +24,19 @@ hipError_t placebo_blocks_launch(hipStream_t stream, int B, int out, const Place
                            : G == 32 ? placebo_blocks_fn<32>(out) : placebo_blocks_fn<64>(out);
   const int fpw = 64 / G;
   hipLaunchKernelGGL(fn, dim3((args.q.p.N + fpw - 1) / fpw, B), dim3(64), 0, stream, args);
+  return hipGetLastError();
+}
+
+// One pass over E entries of a group table: SUM into args.q.p.out, VAR into args.var, args.m.d <= 64.
+hipError_t placebo_blocks_pool_launch(hipStream_t stream, int E, const PlaceboBlocksPoolArgs& args) {
+  if (args.m.d < 1 || args.m.d > PB_MAX_STATE || !args.q.series_of || !args.var) return hipErrorInvalidValue;
+  const int G = blocks_group_size(args.m.d);
+  void (*fn)(PlaceboBlocksPoolArgs) = G == 8 ? placebo_blocks_kernel<8, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs>
+                                    : G == 16 ? placebo_blocks_kernel<16, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs>
+                                    : G == 32 ? placebo_blocks_kernel<32, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs>
+                                    : placebo_blocks_kernel<64, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs>;
+  const int fpw = 64 / G;
+  hipLaunchKernelGGL(fn, dim3((args.q.p.N + fpw - 1) / fpw, E), dim3(64), 0, stream, args);
   return hipGetLastError();
 }
 

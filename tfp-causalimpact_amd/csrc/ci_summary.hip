@@ -1,7 +1,7 @@
 // ci_summary.hip -- the on-device summaries behind the C-ABI (kernels: ci_summary.h,
 // ci_components.h, ci_predict.h): ci_session_summarize, ci_session_summarize_components,
 // ci_session_summarize_predictions, ci_session_summarize_placebo, ci_session_pool_placebo,
-// ci_session_simulate_placebo[_blocks] (kernels: ci_placebo.h, ci_placebo_blocks.h),
+// ci_session_pool_placebo_blocks, ci_session_simulate_placebo[_blocks] (kernels: ci_placebo.h, ci_placebo_blocks.h),
 // ci_session_summarize_windows, ci_ll_session_summarize_windows
 // (kernel: ci_windows.h), ci_session_summarize_paths, ci_ll_session_summarize_paths (kernels: ci_paths.h),
 // ci_session_set_link and ci_session_value_mean (the outcome link: ci_link.h),
@@ -146,6 +146,7 @@ hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seas
 // ci_placebo_blocks.h).
 hipError_t predict_blocks_launch(hipStream_t stream, int B, int out, const PredBlocksArgs& args);
 hipError_t placebo_blocks_launch(hipStream_t stream, int B, int out, const PlaceboBlocksArgs& args);
+hipError_t placebo_blocks_pool_launch(hipStream_t stream, int E, const PlaceboBlocksPoolArgs& args);
 hipError_t placebo_sim_launch(hipStream_t stream, int nb, int has_slope, int num_seasons, int link,
                               const PlaceboSimArgs& args);
 hipError_t placebo_blocks_sim_launch(hipStream_t stream, int nb, int link, const PlaceboBlocksSimArgs& args);
@@ -781,9 +782,13 @@ static int pred_check_session(const ci_session* s, const char* who) {
 // session: not ragged, a state of at most 64 components, and a finished run.
 static int pred_blocks_check_session(const ci_session* s, const char* who) {
   const ci_problem& pb = s->pb;
-  if (s->ragged)
+  if (s->ragged) {
+    const std::string name(who), tail("_blocks");
+    const bool cut = name.size() > tail.size() && name.compare(name.size() - tail.size(), tail.size(), tail) == 0;
     return fail("%s takes no ragged session: their models (one block of 2 to 7 seasons at most) "
-                "belong to the entry without _blocks", who);
+                "belong to the entry without _blocks, %s", who,
+                (cut ? name.substr(0, name.size() - tail.size()) : name).c_str());
+  }
   int d = 1 + (pb.has_slope ? 1 : 0);
   for (int k = 0; k < pb.num_blocks; ++k) d += pb.num_seasons[k] - 1;
   if (d > ci::PB_MAX_STATE) {
@@ -1142,18 +1147,26 @@ int ci_test_session_simulate_placebo(ci_session* s, int32_t blocks, const double
 // forecasts and the sum U of their predictive variances (include/causalimpact_amd.h).  The entries
 // of the group table pass through `value` at most B at a time, a SUM pass and its accumulate, then a
 // VAR pass and its accumulate; the accumulators [G, O, 2, N] and the tables are the call's own.
-int ci_session_pool_placebo(ci_session* s, const double* scale, const double* shift,
-                            int32_t num_groups, const int32_t* offsets, const int32_t* members,
-                            const double* weights, int32_t max_origins, const int32_t* origins,
-                            const int32_t* horizon, const double* init, double* out,
-                            const double* seen, double* predicted_mean, double* spread_mean,
-                            double* pit_mean) {
+// With `blocks` ci_session_pool_placebo_blocks: the sessions and the filter of the block models, ONE
+// pass per chunk that stores SUM into `value` and VAR into a buffer of the call's own, then the same
+// two accumulates.  chunk_entries (tests; 0: B): the entries of a chunk, in [1, B].
+static int pool_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
+                        int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                        const double* weights, int32_t max_origins, const int32_t* origins,
+                        const int32_t* horizon, const double* init, double* out,
+                        const double* seen, double* predicted_mean, double* spread_mean,
+                        double* pit_mean, int32_t chunk_entries) {
   if (!s || !scale || !shift || !offsets || !members || !weights || !origins || !horizon || !out)
     return fail("NULL argument");
   const ci_problem& pb = s->pb;
-  if (pred_check_session(s, "ci_session_pool_placebo")) return 1;
+  if (blocks ? pred_blocks_check_session(s, "ci_session_pool_placebo_blocks")
+             : pred_check_session(s, "ci_session_pool_placebo"))
+    return 1;
   const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
   const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins, G = num_groups;
+  if (chunk_entries < 0 || chunk_entries > B)
+    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", B, chunk_entries);
+  const int chunk = chunk_entries ? chunk_entries : B;
   if (check_groups(B, G, offsets, members, weights)) return 1;
   if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
   if (!seen && (predicted_mean || spread_mean || pit_mean))
@@ -1192,8 +1205,10 @@ int ci_session_pool_placebo(ci_session* s, const double* scale, const double* sh
   const size_t rows = (size_t)G * O, acc_n = rows * 2 * N, Ka = K ? K : 1;
   DevBuf<int> d_int;                     // offsets [G + 1], members [K], horizon [K], origins [K, O]
   DevBuf<double> d_dbl;                  // acc [G, O, 2, N], seen [G, O], weights [K]
+  DevBuf<double> d_var;                  // (blocks) VAR of a chunk [chunk, O, N]
   HIP_TRY(d_int.alloc((size_t)G + 1 + 2 * Ka + Ka * O));
   HIP_TRY(d_dbl.alloc(acc_n + rows + Ka));
+  if (blocks && K > 0) HIP_TRY(d_var.alloc((size_t)(K < chunk ? K : chunk) * O * N));
   int* d_off = d_int.p;
   int* d_members = d_off + G + 1;
   int* d_horizon = d_members + Ka;
@@ -1227,10 +1242,19 @@ int ci_session_pool_placebo(ci_session* s, const double* scale, const double* sh
   a.p.reg = P > 0 ? w.cum.p : nullptr;
   a.p.out = w.value.p; a.p.ll = nullptr;
   a.O = O;
+  ci::PlaceboBlocksPoolArgs ab;
+  if (blocks) { ab.m = pred_block_model(pb); ab.var = d_var.p; }
   // at most B entries at a time: [B * O, N] with O <= T fits `value`
-  for (int c0 = 0; c0 < K; c0 += B) {
-    const int c1 = K - c0 < B ? K : c0 + B;
+  for (int c0 = 0; c0 < K; c0 += chunk) {
+    const int c1 = K - c0 < chunk ? K : c0 + chunk;
     a.series_of = d_members + c0; a.origins = d_origins + (size_t)c0 * O; a.horizon = d_horizon + c0;
+    if (blocks) {
+      ab.q = a;
+      HIP_TRY(ci::placebo_blocks_pool_launch(stream, c1 - c0, ab));
+      HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, 0, c0, c1, d_off, d_weights, w.value.p, d_acc));
+      HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, 1, c0, c1, d_off, d_weights, d_var.p, d_acc));
+      continue;
+    }
     for (int which = 0; which < 2; ++which) {
       HIP_TRY(ci::placebo_launch(stream, c1 - c0, pb.has_slope, NS, which ? ci::PLACEBO_VAR : ci::PLACEBO_SUM, a));
       HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, which, c0, c1, d_off, d_weights, w.value.p, d_acc));
@@ -1253,6 +1277,39 @@ int ci_session_pool_placebo(ci_session* s, const double* scale, const double* sh
   if (pit_mean && finish(ci::PLACEBO_PIT, pit_mean)) return 1;
   HIP_TRY(hipStreamSynchronize(stream));
   return 0;
+}
+
+int ci_session_pool_placebo(ci_session* s, const double* scale, const double* shift,
+                            int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                            const double* weights, int32_t max_origins, const int32_t* origins,
+                            const int32_t* horizon, const double* init, double* out,
+                            const double* seen, double* predicted_mean, double* spread_mean,
+                            double* pit_mean) {
+  return pool_placebo(s, false, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
+                      horizon, init, out, seen, predicted_mean, spread_mean, pit_mean, 0);
+}
+
+int ci_session_pool_placebo_blocks(ci_session* s, const double* scale, const double* shift,
+                                   int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                   const double* weights, int32_t max_origins, const int32_t* origins,
+                                   const int32_t* horizon, const double* init, double* out,
+                                   const double* seen, double* predicted_mean, double* spread_mean,
+                                   double* pit_mean) {
+  return pool_placebo(s, true, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
+                      horizon, init, out, seen, predicted_mean, spread_mean, pit_mean, 0);
+}
+
+int ci_test_session_pool_placebo_blocks(ci_session* s, const double* scale, const double* shift,
+                                        int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                        const double* weights, int32_t max_origins, const int32_t* origins,
+                                        const int32_t* horizon, const double* init, double* out,
+                                        const double* seen, double* predicted_mean, double* spread_mean,
+                                        double* pit_mean, int32_t chunk_entries) {
+  if (!s) return fail("NULL argument");
+  if (chunk_entries < 1)
+    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", s->pb.num_series, chunk_entries);
+  return pool_placebo(s, true, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
+                      horizon, init, out, seen, predicted_mean, spread_mean, pit_mean, chunk_entries);
 }
 
 int ci_summarize_draws(int32_t device, int32_t num_draws, int32_t T, const float* trajectories,
