@@ -566,6 +566,62 @@ int ci_session_pool_placebo_blocks(ci_session* session, const double* scale, con
                                    const int32_t* origins /* [K, O] */, const int32_t* horizon /* [G] */,
                                    const double* init, double* out, const double* seen,
                                    double* predicted_mean, double* spread_mean, double* pit_mean);
+/* SIMULATED PLACEBO FORECASTS OF POOLED SUMS: the placebo check of a pooled effect under an outcome
+ * link, where the pooled total is a weighted sum of sums of exp's and N(S, U) above does not exist.
+ * Additive: CI_ABI_VERSION stays 5; look the symbols up (dlsym) where an older library may be met.
+ * The group table, the entries, the weights, the origin rows origins[k, 0 .. O - 1] per entry and ONE
+ * horizon H_g per group are those of ci_session_pool_placebo.  For entry k (member b_k), slot i and
+ * pooled draw n
+ *   TOTAL_k[i, n] = TOTAL of ci_session_simulate_placebo for series b_k from origins[k, i] with
+ *                   horizon H_g
+ * exactly: the same filter (of .._simulate_placebo_blocks in the _blocks entry), the same explicit
+ * `link`, the same two-rounding linked value and the same Philox address -- key of series b_k, chain
+ * chain_offset + c, iter s, SITE_PLACEBO_SIM, sub = i, idx = h -- and 0.0 where the entry counts no
+ * step or the slot is unused.  No random site is added: different members have different keys, so
+ * their paths are independent of each other, the assumption the pooled check tests
+ * (CI_FLAG_SHARED_SERIES_STREAMS would give all members one world and is not meant for this call); a
+ * series has the same simulated world in every group it belongs to.  Pooled in float64, entries
+ * ascending, one rounding per operation, no fused multiply-add:
+ *   POOL[g, i, n] = init[g, i, n];  for k ascending:  POOL = POOL + w_k * TOTAL_k[i, n]
+ * init and out: host arrays [G, O, N] (one plane).  init may be NULL (0.0) and may be `out` itself;
+ * several sessions continue one running sum by handing `out` on as `init`, bit for bit however the
+ * series are cut into sessions as long as the series keep their ids and the chains their global ids.
+ * seen [G, O] (host, the pooled observed total on the data scale) and counted [G, O] (host, int32, the
+ * member-steps the window counts over all members) are optional, but wanted TOGETHER by every
+ * statistic.  With them the call returns the statistics of ci_session_simulate_placebo over the row
+ * POOL[g, i, :] (each output may be NULL and is then skipped):
+ *   predicted_mean [G, O]        the mean over n of POOL
+ *   spread_mean    [G, O]        the mean over n of (POOL - seen)^2, subtraction and product rounded separately
+ *   below          [G, O]        #{n : POOL <= seen}, the exact integer count as a double
+ *   total_order    [G, num_ranks, O]   the order statistics of POOL over n
+ * the means as ci_session_summarize_components takes its means; spread_mean and below are 0 where
+ * counted == 0, and so are the others, POOL being 0.0 there.  A call with empty groups (offsets all
+ * 0) and init = the finished sums only takes the statistics.
+ * Sessions and models as ci_session_simulate_placebo (.._blocks: a ragged session is refused).  At most
+ * B entries at a time pass through the scratch of ci_session_summarize, ONE simulation pass each;
+ * beyond it the call holds the tables and the [G, O, N] accumulators, whose rows then pass through
+ * the scratch, whole groups at a time, for the statistics -- `out` is downloaded before.  Nothing
+ * depends on where the entries or the rows are cut.
+ * Checked before any device call, with the group, entry or slot named: as ci_session_pool_placebo,
+ * and link in range, num_ranks in [1, 8], ranks (not NULL) in [0, N), no statistic without both
+ * `seen` and `counted`. */
+int ci_session_pool_simulated_placebo(ci_session* session, const double* scale, const double* shift,
+                                      int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                      const double* weights, int32_t max_origins,
+                                      const int32_t* origins /* [K, O] */, const int32_t* horizon /* [G] */,
+                                      int32_t link, const double* init, double* out /* [G, O, N] */,
+                                      const double* seen /* [G, O] */, const int32_t* counted /* [G, O] */,
+                                      int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
+                                      double* spread_mean, double* below, double* total_order /* [G, R, O] */);
+int ci_session_pool_simulated_placebo_blocks(ci_session* session, const double* scale, const double* shift,
+                                             int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                             const double* weights, int32_t max_origins,
+                                             const int32_t* origins /* [K, O] */, const int32_t* horizon /* [G] */,
+                                             int32_t link, const double* init, double* out /* [G, O, N] */,
+                                             const double* seen /* [G, O] */, const int32_t* counted /* [G, O] */,
+                                             int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
+                                             double* spread_mean, double* below,
+                                             double* total_order /* [G, R, O] */);
 /* Per-draw totals over SUB-WINDOWS of the session's steps, for all B series at once: how an effect
  * unfolds inside the post-period (week 1 against week 4, a promotion's second phase), whose bands,
  * relative effect and tail-area probability need every draw's total over the window and are not
@@ -1024,6 +1080,17 @@ int ci_test_session_pool_placebo_blocks(ci_session* session, const double* scale
                                         const double* init, double* out, const double* seen,
                                         double* predicted_mean, double* spread_mean, double* pit_mean,
                                         int32_t chunk_entries);
+/* ci_session_pool_simulated_placebo (blocks == 0) or .._blocks (blocks != 0) with the entries of a
+ * chunk handed in (chunk_entries in [1, B] in place of B), likewise. */
+int ci_test_session_pool_simulated_placebo(ci_session* session, int32_t blocks, const double* scale,
+                                           const double* shift, int32_t num_groups, const int32_t* offsets,
+                                           const int32_t* members, const double* weights, int32_t max_origins,
+                                           const int32_t* origins /* [K, O] */, const int32_t* horizon /* [G] */,
+                                           int32_t link, const double* init, double* out /* [G, O, N] */,
+                                           const double* seen /* [G, O] */, const int32_t* counted /* [G, O] */,
+                                           int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
+                                           double* spread_mean, double* below,
+                                           double* total_order /* [G, R, O] */, int32_t chunk_entries);
 
 #ifdef __cplusplus
 }

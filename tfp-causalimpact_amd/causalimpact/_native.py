@@ -151,6 +151,14 @@ def load():
       getattr(L, name).argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 +
                                    [C.c_int32] + [C.c_void_p] * 8 +
                                    ([C.c_int32] if name.startswith("ci_test_") else []))
+  for name in ("ci_session_pool_simulated_placebo", "ci_session_pool_simulated_placebo_blocks",
+               "ci_test_session_pool_simulated_placebo"):
+    if hasattr(L, name):                               # (additive, likewise)
+      test = name.startswith("ci_test_")
+      getattr(L, name).argtypes = ([C.c_void_p] + ([C.c_int32] if test else []) +
+                                   [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] +
+                                   [C.c_void_p] * 2 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] +
+                                   [C.c_void_p] * 5 + ([C.c_int32] if test else []))
   if hasattr(L, "ci_session_set_link"):                # (additive, likewise)
     L.ci_session_set_link.argtypes = [C.c_void_p, C.c_int32]
     L.ci_session_value_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -241,6 +249,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
           "ci_session_pool_event_trajectories", "ci_session_pool_placebo",
           "ci_session_pool_placebo_blocks",
+          "ci_session_pool_simulated_placebo", "ci_session_pool_simulated_placebo_blocks",
           "ci_session_simulate_placebo", "ci_session_simulate_placebo_blocks",
           "ci_session_set_link", "ci_session_value_mean",
           "ci_kalman_loglik", "ci_ll_session_create", "ci_ll_session_create2", "ci_ll_session_eval",
@@ -251,7 +260,8 @@ def exported_symbols() -> Sequence[str]:
           "ci_comm_all_reduce", "ci_comm_all_gather", "ci_comm_session_all_gather",
           "ci_comm_ll_session_all_gather", "ci_comm_destroy", "ci_test_rng",
           "ci_test_dk_draw", "ci_test_session_summarize_paths", "ci_test_summarize_draw_paths_f64",
-          "ci_test_session_simulate_placebo", "ci_test_session_pool_placebo_blocks")
+          "ci_test_session_simulate_placebo", "ci_test_session_pool_placebo_blocks",
+          "ci_test_session_pool_simulated_placebo")
 
 
 def _check(rc: int):
@@ -545,6 +555,44 @@ def finish_placebo_host(acc, seen) -> Dict[str, np.ndarray]:
   # (draws first: the mean adds them in ascending order, as `_placebo_summary_host` takes its means)
   mean = lambda x: np.ascontiguousarray(np.moveaxis(x, 2, 0)).mean(axis=0)   # pylint: disable=unnecessary-lambda-assignment
   return dict(predicted_mean=mean(np.where(some, S, 0.0)), spread_mean=mean(spread), pit_mean=mean(pit))
+
+
+def pool_simulated_placebo_host(totals, groups, init=None) -> np.ndarray:
+  """What `Session.pool_simulated_placebo` accumulates, in numpy: totals [K, O, N] -- per entry of the
+  group table, in its order, the simulated totals of its member at the entry's origins and the
+  group's horizon (0 where nothing is counted) -- and groups as for `pool_placebo_host`.  Returns acc
+  [G, O, N] float64:
+    acc[g] = init[g] + sum over the group's entries k, ascending, of w_k * totals[k]
+  one rounding per operation -- the loop of include/causalimpact_amd.h."""
+  t_ = np.asarray(totals, np.float64)
+  if t_.ndim != 3:
+    raise ValueError(f"`totals` must be [K, O, N], got {t_.shape}")
+  offsets, _, weights = _entry_csr(groups, np.iinfo(np.int32).max)
+  G = len(offsets) - 1
+  if offsets[G] != t_.shape[0]:
+    raise ValueError(f"the groups have {offsets[G]} entries, `totals` has {t_.shape[0]}")
+  shape = (G,) + t_.shape[1:]
+  out = np.zeros(shape, np.float64) if init is None else np.array(init, np.float64).reshape(shape)
+  for g in range(G):
+    for k in range(offsets[g], offsets[g + 1]):
+      out[g] = out[g] + np.float64(weights[k]) * t_[k]
+  return out
+
+
+def finish_simulated_placebo_host(acc, seen, counted, ranks=()) -> Dict[str, np.ndarray]:
+  """The finishing step of `Session.pool_simulated_placebo` in numpy: acc [G, O, N] the pooled
+  simulated totals, seen [G, O] the pooled observed totals, counted [G, O] the member-steps every
+  window counts -> the statistics of `simulate_placebo` over the rows of acc: predicted_mean (as
+  `row_means_host`), spread_mean (the mean of (acc - seen)^2), below (#{n: acc <= seen}) [G, O] and
+  total_order [G, R, O]; spread_mean and below 0 where counted == 0 (acc is 0.0 there)."""
+  acc = np.asarray(acc, np.float64)
+  some = np.asarray(counted) > 0
+  seen = np.where(some, np.nan_to_num(np.asarray(seen, np.float64)), 0.0)
+  dev = acc - seen[..., None]
+  return dict(predicted_mean=row_means_host(acc),
+              spread_mean=np.where(some, row_means_host(dev * dev), 0.0),
+              below=np.where(some, np.count_nonzero(acc <= seen[..., None], axis=-1), 0).astype(np.float64),
+              total_order=np.ascontiguousarray(np.moveaxis(np.sort(acc, axis=-1)[..., list(ranks)], -1, -2)))
 
 
 def _pool_call(fn, handle, B: int, N: int, T: int, scale, shift, groups, init, event=False,
@@ -1320,25 +1368,10 @@ class Session:
     return _pool_call(fn, self._h, pb.num_series, pb.num_chains * pb.num_results, pb.T, scale, shift,
                       groups, init, True, out_stride)
 
-  def pool_placebo(self, scale, shift, groups, origins, horizon, init=None, seen=None, *,
-                   _entry="ci_session_pool_placebo", _tail=()) -> Dict[str, np.ndarray]:
-    """Placebo forecasts of POOLED sums (ci_session_pool_placebo): `summarize_placebo`'s forecasts of
-    the members of every group, added draw by draw with the group's weights, and the members'
-    predictive variances added with the squared weights -- float64, entries ascending, one rounding
-    per operation (`pool_placebo_host` is the same loop in numpy).  scale, shift: scalars or [B];
-    groups: as for `pool_trajectories` (`groups_csr`: members of zero weight are left out);
-    origins: [B, O] int -- every entry takes the row of its series -- or one mapping {position in the
-    session: row [O]} per group, every row strictly ascending steps with -1 (unused) at the end;
-    horizon: a scalar or [G], ONE horizon per group; init: [G, O, 2, N] float64 -- the `acc` of the
-    part of a batch in front of this session -- or None; seen: [G, O] the pooled observed sums on the
-    data scale, or None.  Returns acc [G, O, 2, N] (S, then U) and, with `seen`, predicted_mean,
-    spread_mean, pit_mean [G, O] (`finish_placebo_host`).  Given every member's draw the pooled sum
-    is N(S, U) IF the members are independent of each other: the assumption this check tests."""
-    fn = getattr(self._lib, _entry, None)
-    if fn is None:
-      raise NativeError(f"the loaded library has no {_entry}: rebuild it")
-    pb = self.pb
-    B, N = pb.num_series, pb.num_chains * pb.num_results
+  def _pool_placebo_tables(self, scale, shift, groups, origins, horizon):
+    """(scale [B], shift [B], offsets, members, weights, origins [K, O] int32, horizon [G] int32): the
+    arguments of `pool_placebo` and `pool_simulated_placebo` as the C entries take them."""
+    B = self.pb.num_series
     sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
     for name, a in (("scale", sc), ("shift", sh)):
       if a.shape not in ((), (B,)):
@@ -1368,6 +1401,27 @@ class Session:
     if hz.shape not in ((), (G,)):
       raise ValueError(f"`horizon` must be a scalar or have one entry per group ({G}), got shape {hz.shape}")
     hz = np.ascontiguousarray(np.broadcast_to(hz, (G,)), dtype=np.int32)
+    return sc, sh, offsets, members, weights, org, hz
+
+  def pool_placebo(self, scale, shift, groups, origins, horizon, init=None, seen=None, *,
+                   _entry="ci_session_pool_placebo", _tail=()) -> Dict[str, np.ndarray]:
+    """Placebo forecasts of POOLED sums (ci_session_pool_placebo): `summarize_placebo`'s forecasts of
+    the members of every group, added draw by draw with the group's weights, and the members'
+    predictive variances added with the squared weights -- float64, entries ascending, one rounding
+    per operation (`pool_placebo_host` is the same loop in numpy).  scale, shift: scalars or [B];
+    groups: as for `pool_trajectories` (`groups_csr`: members of zero weight are left out);
+    origins: [B, O] int -- every entry takes the row of its series -- or one mapping {position in the
+    session: row [O]} per group, every row strictly ascending steps with -1 (unused) at the end;
+    horizon: a scalar or [G], ONE horizon per group; init: [G, O, 2, N] float64 -- the `acc` of the
+    part of a batch in front of this session -- or None; seen: [G, O] the pooled observed sums on the
+    data scale, or None.  Returns acc [G, O, 2, N] (S, then U) and, with `seen`, predicted_mean,
+    spread_mean, pit_mean [G, O] (`finish_placebo_host`).  Given every member's draw the pooled sum
+    is N(S, U) IF the members are independent of each other: the assumption this check tests."""
+    fn = getattr(self._lib, _entry, None)
+    if fn is None:
+      raise NativeError(f"the loaded library has no {_entry}: rebuild it")
+    sc, sh, offsets, members, weights, org, hz = self._pool_placebo_tables(scale, shift, groups, origins, horizon)
+    G, O, N = offsets.size - 1, int(org.shape[1]), self.pb.num_chains * self.pb.num_results
     if init is not None:
       init = np.ascontiguousarray(init, dtype=np.float64)
       if init.shape != (G, O, 2, N):
@@ -1395,6 +1449,69 @@ class Session:
                                _entry="ci_session_pool_placebo_blocks")
     return self.pool_placebo(scale, shift, groups, origins, horizon, init, seen,
                              _entry="ci_test_session_pool_placebo_blocks", _tail=(int(chunk_entries),))
+
+  def pool_simulated_placebo(self, scale, shift, groups, origins, horizon, link, init=None, seen=None,
+                             counted=None, ranks=None, want=None, *, blocks: bool = False,
+                             chunk_entries=None) -> Dict[str, np.ndarray]:
+    """SIMULATED placebo forecasts of POOLED sums (ci_session_pool_simulated_placebo): the totals of
+    `simulate_placebo` of the members of every group -- the same filter, link and random stream, every
+    entry from its own origin row with the group's horizon -- added draw by draw with the group's
+    weights, float64, entries ascending, one rounding per operation (`pool_simulated_placebo_host` is
+    the same loop in numpy).  scale, shift, groups, origins, horizon: as for `pool_placebo`; link: a
+    `LINK_*`, passed explicitly; init: [G, O, N] float64 -- the `acc` of the part of a batch in front
+    of this session -- or None; seen [G, O]: the pooled observed totals on the data scale, counted
+    [G, O]: the member-steps every window counts -- both or neither; ranks: 1 to 8 order statistics
+    (default with `seen`: none asked for).  Returns acc [G, O, N] and, with `seen` and `counted`, the
+    statistics of `simulate_placebo` over the rows of acc (`finish_simulated_placebo_host`):
+    predicted_mean, spread_mean, below [G, O] and, with `ranks`, total_order [G, R, O]; `want` names
+    those to compute.  The members' paths are independent of each other (every series has its own
+    Philox key): the assumption this check tests.  chunk_entries (tests): the entries of a chunk, in
+    [1, B], in place of B (ci_test_session_pool_simulated_placebo); the result does not depend on it."""
+    if chunk_entries is not None:
+      name = "ci_test_session_pool_simulated_placebo"
+    else:
+      name = "ci_session_pool_simulated_placebo_blocks" if blocks else "ci_session_pool_simulated_placebo"
+    fn = getattr(self._lib, name, None)
+    if fn is None:
+      raise NativeError(f"the loaded library has no {name}: rebuild it")
+    sc, sh, offsets, members, weights, org, hz = self._pool_placebo_tables(scale, shift, groups, origins, horizon)
+    G, O, N = offsets.size - 1, int(org.shape[1]), self.pb.num_chains * self.pb.num_results
+    if init is not None:
+      init = np.ascontiguousarray(init, dtype=np.float64)
+      if init.shape != (G, O, N):
+        raise ValueError(f"`init` must be {[G, O, N]}, got {list(init.shape)}")
+    if (seen is None) != (counted is None):
+      raise ValueError("`seen` and `counted` go together: the statistics need both")
+    rk = np.ascontiguousarray([0] if ranks is None else ranks, dtype=np.int32).reshape(-1)
+    shapes = dict(predicted_mean=(G, O), spread_mean=(G, O), below=(G, O), total_order=(G, rk.size, O))
+    if want is None:
+      want = [] if seen is None else [k for k in shapes if k != "total_order" or ranks is not None]
+    unknown = [k for k in want if k not in shapes]
+    if unknown:
+      raise ValueError(f"unknown pooled simulated placebo outputs {unknown}: choose from {list(shapes)}")
+    if seen is not None:
+      seen = np.ascontiguousarray(seen, dtype=np.float64)
+      counted = np.ascontiguousarray(counted, dtype=np.int32)
+      for what, a in (("seen", seen), ("counted", counted)):
+        if a.shape != (G, O):
+          raise ValueError(f"`{what}` must be {[G, O]}, got {list(a.shape)}")
+    out = {"acc": np.empty((G, O, N), np.float64)}
+    out.update({k: np.empty(shapes[k], np.float64) for k in shapes if k in want})
+    _check(fn(self._h, *((int(bool(blocks)),) if chunk_entries is not None else ()),
+              sc.ctypes.data, sh.ctypes.data, G, offsets.ctypes.data, members.ctypes.data, weights.ctypes.data,
+              O, org.ctypes.data, hz.ctypes.data, int(link), _ptr(init), out["acc"].ctypes.data, _ptr(seen),
+              _ptr(counted), int(rk.size), rk.ctypes.data, *[_ptr(out.get(k)) for k in shapes],
+              *((int(chunk_entries),) if chunk_entries is not None else ())))
+    return out
+
+  def pool_simulated_placebo_blocks(self, scale, shift, groups, origins, horizon, link, init=None, seen=None,
+                                    counted=None, ranks=None, want=None,
+                                    chunk_entries=None) -> Dict[str, np.ndarray]:
+    """`pool_simulated_placebo` for any block list whose state has at most 64 components
+    (ci_session_pool_simulated_placebo_blocks): same arguments, same outputs, the filter of
+    `simulate_placebo_blocks`.  Ragged sessions stay with `pool_simulated_placebo`."""
+    return self.pool_simulated_placebo(scale, shift, groups, origins, horizon, link, init, seen, counted, ranks,
+                                       want, blocks=True, chunk_entries=chunk_entries)
 
   def close(self):
     if self._h:

@@ -41,7 +41,9 @@ calendar; `prepare_panel`, padded to the longest series):
   * `PlaceboPoolPlan`, `_PlaceboChain` (`HostPlaceboPool` on the per-series routes),
     `_take_aggregate_placebo`: the placebo forecasts of the pooled effects (`placebo=` with
     aggregates) -- per entry of the group table the member's origins, a second chain next to
-    `_PoolChain` for the sums [G, O, 2, N] of csrc/ci_placebo.h, the frames of every group;
+    `_PoolChain` for the sums [G, O, 2, N] of csrc/ci_placebo.h, the frames of every group; with a
+    `SimulatedPool` (`Placebo(simulate=True, pool=True)`) the same chain for the sums [G, O, N] of the
+    members' simulated totals;
   * `pool_weighted` + `_aggregate_analyses` (a batch) and `event_axes` / `event_plan`,
     `pool_event_weighted` + `_event_aggregate_analyses` (a panel): what differs -- every group's axis
     around its members' own treatment starts, the pooled outcome and posterior mean, the rows of
@@ -53,7 +55,7 @@ from __future__ import annotations
 
 import concurrent.futures
 import dataclasses
-from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import pandas as pd
@@ -1518,7 +1520,8 @@ def _placebo_pool_observed(pp: PlaceboPoolPlan, entry_seen) -> Dict[str, np.ndar
 
 def _fit_placebo_observed(pp: PlaceboPoolPlan, fit: "_Fit") -> Dict[str, np.ndarray]:
   """`_placebo_pool_observed` of a one-launch fit, from the arrays its launches read: every member
-  as its sampler saw it (float32), on the data scale with its own scaler's statistics."""
+  as its sampler saw it (float32), on the data scale with its own scaler's statistics; under the
+  fit's outcome link the members' raw outcomes (`lib._placebo_entry_seen`)."""
   members = pp.csr[1]
   known: Dict[Any, Dict] = {}        # (a series of a batch has the same windows in every group)
 
@@ -1529,19 +1532,41 @@ def _fit_placebo_observed(pp: PlaceboPoolPlan, fit: "_Fit") -> Dict[str, np.ndar
       Tb = int(fit.lengths[b])
       one = lib.SeriesInputs(fit.y[b, :Tb], fit.mask[b, :Tb], None, None, (), False, {})
       known[key] = lib._placebo_entry_seen(one, fit.own_scale[b], fit.own_shift[b], fit.observed[b, :Tb],   # pylint: disable=protected-access
-                                           pp.origins[k], int(pp.horizon[g]))
+                                           pp.origins[k], int(pp.horizon[g]), fit.link)
     return known[key]
   return _placebo_pool_observed(pp, entry_seen)
+
+
+class SimulatedPool(NamedTuple):
+  """`Placebo(simulate=True, pool=True)`: what the SIMULATED pooled placebo forecasts need beyond the
+  plan -- the `_native.LINK_*` the totals are formed under and the (lower, upper) quantiles the frames
+  report."""
+  link: int
+  quantiles: Tuple[float, float]
+
+  def means(self, stats: Dict[str, np.ndarray], ranks, num_draws: int) -> Dict[str, np.ndarray]:
+    """The summary the frames read (`lib._simulated_placebo_means`) from the statistics [G, O] of the
+    pooled totals."""
+    return lib._simulated_placebo_means(stats, ranks, num_draws, self.quantiles)   # pylint: disable=protected-access
+
+  def finish_host(self, acc: np.ndarray, seen, counted) -> Dict[str, np.ndarray]:
+    """`_native.finish_simulated_placebo_host` of the sums [G, O, N], as that summary."""
+    num_draws = acc.shape[-1]
+    ranks = lib._placebo_sim_ranks(num_draws, self.quantiles)   # pylint: disable=protected-access
+    return self.means(_native.finish_simulated_placebo_host(acc, seen, counted, ranks), ranks, num_draws)
 
 
 class HostPlaceboPool:
   """The running sums of the pooled placebo forecasts in numpy, for batches and panels that are fitted
   series by series: `add(b, forecast)` for b = 0, 1, ... with the `forecast(origins, horizon)` a fit
   hands to its `_placebo_sink`; every group that has b takes the terms of its own origins and horizon
-  (`_native.pool_placebo_host`'s arithmetic, one entry at a time, entries ascending)."""
+  (`_native.pool_placebo_host`'s arithmetic, one entry at a time, entries ascending).  simulated (a
+  `SimulatedPool`): the forecast hands the member's simulated totals (`lib._placebo_entry_simulated_host`)
+  and the sums are those of `_native.pool_simulated_placebo_host`, [G, O, N]."""
 
-  def __init__(self, pp: PlaceboPoolPlan):
+  def __init__(self, pp: PlaceboPoolPlan, simulated: Optional[SimulatedPool] = None):
     self.pp = pp
+    self.simulated = simulated
     self.acc: Optional[np.ndarray] = None
     self._seen: Dict[int, Dict] = {}
 
@@ -1550,31 +1575,63 @@ class HostPlaceboPool:
     weights = pp.csr[2]
     for g, k in pp.entries_of(b):
       one = forecast(pp.origins[k], int(pp.horizon[g]))
-      if self.acc is None:
-        self.acc = np.zeros(pp.columns.shape + (2, one["s"].shape[1]))
       w = np.float64(weights[k])
-      self.acc[g, :, 0] = self.acc[g, :, 0] + w * one["s"]
-      self.acc[g, :, 1] = self.acc[g, :, 1] + (w * w) * one["v"]
+      if self.simulated is not None:
+        if self.acc is None:
+          self.acc = np.zeros(pp.columns.shape + (one["totals"].shape[1],))
+        self.acc[g] = self.acc[g] + w * one["totals"]
+      else:
+        if self.acc is None:
+          self.acc = np.zeros(pp.columns.shape + (2, one["s"].shape[1]))
+        self.acc[g, :, 0] = self.acc[g, :, 0] + w * one["s"]
+        self.acc[g, :, 1] = self.acc[g, :, 1] + (w * w) * one["v"]
       self._seen[k] = {name: one[name] for name in ("seen_sum", "actual", "n_counted")}
 
   def result(self):
-    """(means, observed): `_native.finish_placebo_host` of the sums, and `_placebo_pool_observed`."""
+    """(means, observed): `_native.finish_placebo_host` of the sums (simulated: `SimulatedPool.finish_host`),
+    and `_placebo_pool_observed`."""
     observed = _placebo_pool_observed(self.pp, lambda g, k: self._seen[k])
     if self.acc is None:                       # (no group has room for an origin)
       return None, observed
+    if self.simulated is not None:
+      return self.simulated.finish_host(self.acc, observed["seen_sum"], observed["n_counted"]), observed
     return _native.finish_placebo_host(self.acc, observed["seen_sum"]), observed
 
 
-def placebo_pool_route(sess, has_slope: bool, num_seasons: Sequence[int]) -> str:
+def _simulated_pool(placebo: Optional[lib.Placebo], link: int, alpha: float) -> Optional[SimulatedPool]:
+  """The `SimulatedPool` of `Placebo(simulate=True, pool=True)` under the `_native.LINK_*` link, else
+  None: the analytic pooled placebo."""
+  if placebo is None or not placebo.pool:
+    return None
+  return SimulatedPool(int(link), (alpha / 2.0, 1.0 - alpha / 2.0))
+
+
+def _new_placebo_chain(launches, pp: PlaceboPoolPlan, observed: Dict[str, np.ndarray], fit: "_Fit",
+                       placebo: lib.Placebo, alpha: float) -> "_PlaceboChain":
+  """The `_PlaceboChain` of a one-launch fit: analytic, or with `Placebo(pool=True)` simulated -- every
+  series on the stream its fit runs on (`_launch_request`'s)."""
+  sim = _simulated_pool(placebo, fit.link, alpha)
+  if sim is None:
+    return _PlaceboChain(launches, pp, observed["seen_sum"])
+  num_chains = fit.inference_options.num_chains
+  streams = lambda ids: [lib.placebo_stream(fit.seed, None if fit.shared_streams else int(b), range(num_chains))   # pylint: disable=unnecessary-lambda-assignment
+                         for b in ids]
+  return _PlaceboChain(launches, pp, observed["seen_sum"], sim, observed["n_counted"].astype(np.int32), streams)
+
+
+def placebo_pool_route(sess, has_slope: bool, num_seasons: Sequence[int], simulated: bool = False) -> str:
   """Where the pooled placebo forecasts of the open session `sess` are filtered: "one_lane"
   (`pool_placebo`: a trend with at most one block of 2 to 7 seasons), "blocks" (`pool_placebo_blocks`:
   any other block list whose state the block-model filter takes) or "host" (numpy, from the
-  parameter draws: HMC and float64 sessions, a library without the entry, a wider state)."""
+  parameter draws: HMC and float64 sessions, a library without the entry, a wider state).  simulated:
+  the same choice between `pool_simulated_placebo` and `pool_simulated_placebo_blocks`."""
+  one_lane, blocks = (("pool_simulated_placebo", "pool_simulated_placebo_blocks") if simulated else
+                      ("pool_placebo", "pool_placebo_blocks"))
   if "placebo" not in getattr(sess, "summaries", ()):
     return "host"
-  if hasattr(sess, "pool_placebo") and lib.device_predictions_supported(num_seasons):
+  if hasattr(sess, one_lane) and lib.device_predictions_supported(num_seasons):
     return "one_lane"
-  if hasattr(sess, "pool_placebo_blocks") and lib.device_block_predictions_supported(has_slope, num_seasons):
+  if hasattr(sess, blocks) and lib.device_block_predictions_supported(has_slope, num_seasons):
     return "blocks"
   return "host"
 
@@ -1584,11 +1641,22 @@ class _PlaceboChain(_PoolChain):
   pooled placebo forecasts (csrc/ci_placebo.h, ci_session_pool_placebo), handed from launch to launch
   in the order of the trajectories' sum -- list order: class key, then position -- so a group's sums
   do not depend on how the fit is cut into launches and devices, bit for bit.  The last launch hands
-  the finished sums back with `seen`, the pooled observed sums, and gets the three means."""
+  the finished sums back with `seen`, the pooled observed sums, and gets the three means.
+  simulated (a `SimulatedPool`; counted [G, O]: the member-steps every window counts, `streams(ids)`:
+  the `lib.placebo_stream` of the positions `ids`): the same chain for the accumulators [G, O, N] of the
+  SIMULATED pooled placebo forecasts (ci_session_pool_simulated_placebo) -- the same launch order, the
+  same hand-on, the same choice of route; the last launch finishes with `seen`, `counted` and the
+  ranks of `lib._placebo_sim_ranks`, and `means` is the summary `SimulatedPool.means` makes of it."""
 
-  def __init__(self, launches, pp: PlaceboPoolPlan, seen: np.ndarray):
+  simulated: Optional[SimulatedPool] = None      # (the analytic chain, unless `__init__` says otherwise)
+  counted: Optional[np.ndarray] = None
+  streams = None
+
+  def __init__(self, launches, pp: PlaceboPoolPlan, seen: np.ndarray, simulated: Optional[SimulatedPool] = None,
+               counted: Optional[np.ndarray] = None, streams=None):
     super().__init__(launches, pp.csr)
     self.pp, self.seen = pp, seen
+    self.simulated, self.counted, self.streams = simulated, counted, streams
     self.means: Optional[Dict[str, np.ndarray]] = None
 
   def groups_of(self, ids: Sequence[int]):
@@ -1604,13 +1672,15 @@ class _PlaceboChain(_PoolChain):
                   {place[int(members[k])]: self.pp.origins[k] for k in here}))
     return out
 
-  def session_pool(self, sess, scale, shift, series_inputs=None, observed=None):
+  def session_pool(self, sess, scale, shift, series_inputs=None, observed=None, ids=None):
     """(pool, finish) of the open session `sess`: pool(groups, origins, horizon, init) -> acc of the
     groups handed in, finish(acc, seen) -> the three means.  `placebo_pool_route` chooses: a session
     whose model the one-lane filter takes runs both through `pool_placebo`, one whose model the
     block-model filter takes through `pool_placebo_blocks`; any other (HMC, a state beyond 64) filters
     its members in numpy from the parameter draws it holds (`lib._placebo_entry_host`) and pools with
     the host twin."""
+    if self.simulated is not None:
+      return self._simulated_session_pool(sess, scale, shift, series_inputs, ids)
     route = placebo_pool_route(sess, series_inputs[0].has_slope, series_inputs[0].num_seasons)
     if route != "host":
       T, B = int(sess.pb.T), int(sess.pb.num_series)
@@ -1642,6 +1712,48 @@ class _PlaceboChain(_PoolChain):
       return _native.pool_placebo_host(np.stack([t["s"] for t in terms]), np.stack([t["v"] for t in terms]),
                                        csr, init)
     return host_pool, _native.finish_placebo_host
+
+  def _simulated_session_pool(self, sess, scale, shift, series_inputs, ids):
+    """`session_pool` of the simulated mode: (pool, finish) through `pool_simulated_placebo`
+    (`.._blocks`) where `placebo_pool_route` finds the entry and the model, else in numpy from the
+    session's parameter draws (`lib._placebo_simulated_host` on every member's own stream,
+    `_native.pool_simulated_placebo_host`, `SimulatedPool.finish_host`).  ids: the launch's positions."""
+    sim, counted = self.simulated, self.counted
+    route = placebo_pool_route(sess, series_inputs[0].has_slope, series_inputs[0].num_seasons, simulated=True)
+    if route != "host":
+      T, B = int(sess.pb.T), int(sess.pb.num_series)
+      num_draws = int(sess.pb.num_chains * sess.pb.num_results)
+      ranks = lib._placebo_sim_ranks(num_draws, sim.quantiles)    # pylint: disable=protected-access
+      entry = sess.pool_simulated_placebo if route == "one_lane" else sess.pool_simulated_placebo_blocks
+
+      def pool(groups, origins, horizon, init):
+        return entry(scale, shift, groups, origins, horizon, sim.link, init)["acc"]
+
+      def finish(acc, seen):
+        # no slot row is longer than the session's steps: as many slots at a time as it takes
+        G, R = acc.shape[0], len(ranks)
+        out = dict(predicted_mean=np.zeros(seen.shape), spread_mean=np.zeros(seen.shape),
+                   below=np.zeros(seen.shape), total_order=np.zeros((G, R, seen.shape[1])))
+        for j in range(0, acc.shape[1], T):
+          w = min(T, acc.shape[1] - j)
+          got = entry(scale, shift, [{}] * G, np.full((B, w), -1, np.int32), np.ones(G, np.int32), sim.link,
+                      np.ascontiguousarray(acc[:, j:j + w]), np.ascontiguousarray(seen[:, j:j + w]),
+                      np.ascontiguousarray(counted[:, j:j + w]), ranks)
+          for k in out:
+            out[k][..., j:j + w] = got[k]
+        return sim.means(out, ranks, num_draws)
+      return pool, finish
+    draws = sess.fetch(list(lib._PARAMETER_DRAWS))                 # pylint: disable=protected-access
+    streams = self.streams(ids)
+
+    def host_pool(groups, origins, horizon, init):
+      csr = _native.groups_csr(groups, len(series_inputs))
+      totals = [lib._placebo_simulated_host(                        # pylint: disable=protected-access
+          *series_inputs[i].filter_inputs(), lib._pooled_draws(draws, i), scale[i], shift[i],   # pylint: disable=protected-access
+          np.asarray(origins[g][i]).reshape(-1), int(horizon[g]), sim.link, streams[i])["totals"]
+                for g in range(len(groups)) for i in (int(m) for m in csr[1][csr[0][g]:csr[0][g + 1]])]
+      return _native.pool_simulated_placebo_host(np.stack(totals), csr, init)
+    return host_pool, lambda acc, seen: sim.finish_host(acc, seen, counted)
 
   def step(self, launch, pool):            # pylint: disable=arguments-renamed
     """The step of `launch`, its session still open; pool: the pair of `session_pool`.  Only the
@@ -1776,7 +1888,9 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
     host_pool = HostPool(csr)
   elif event_aggregates is not None:
     host_pool = HostPool(event_aggregates.csr, event_aggregates.axes)
-  host_placebo = None if placebo_pool is None else HostPlaceboPool(placebo_pool)
+  host_placebo = None
+  if placebo_pool is not None:
+    host_placebo = HostPlaceboPool(placebo_pool, _simulated_pool(placebo, lib.resolve_outcome_link(outcome_link), alpha))
   for b, frame in enumerate(frames):
     seed_b = base_seed if shared_streams else _native.series_stream_key(base_seed, b)
     if host_pool is not None:
@@ -1988,7 +2102,7 @@ def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None
     if placebo_chain is not None:
       placebo_chain.step(launch, placebo_chain.session_pool(
           sess, fit.own_scale[ids], fit.own_shift[ids], inputs,
-          [fit.observed[b, :int(fit.lengths[b])] for b in ids]))
+          [fit.observed[b, :int(fit.lengths[b])] for b in ids], ids))
   finally:
     sess.close()
   if stride != T:            # (back at the stride of the longest series)
@@ -2046,7 +2160,7 @@ def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None,
       chain.step(launch, chain.session_pool(sess, fit.scale[ids], fit.shift[ids]))
     if placebo_chain is not None:          # (no filter on this session: numpy, from its parameter draws)
       placebo_chain.step(launch, placebo_chain.session_pool(
-          sess, fit.own_scale[ids], fit.own_shift[ids], inputs, list(fit.observed[ids])))
+          sess, fit.own_scale[ids], fit.own_shift[ids], inputs, list(fit.observed[ids]), ids))
     return record
 
   res = _hmc.fit_hmc_batch(
@@ -2228,7 +2342,11 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   takes the per-series route (as with `components=True`).  ValueError before any fit, the series and
   the label named, for a value outside the link's domain on a row a model conditions on.
   `components` and `prediction_errors` stay on the transformed scale; the analytic `placebo=` is refused,
-  `placebo=Placebo(simulate=True)` runs the simulated placebo (not together with `aggregates`).
+  `placebo=Placebo(simulate=True)` runs the simulated placebo; together with `aggregates` as
+  `Placebo(simulate=True, pool=True)`, which adds the SIMULATED pooled placebo: every member's simulated
+  totals at the group's origins and horizon, added draw by draw with the group's weights
+  (ci_session_pool_simulated_placebo; `_native.pool_simulated_placebo_host` on the routes that filter in
+  numpy), `result.aggregates[name].placebo` with the columns of the per-series simulated frame.
   """
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
@@ -2325,7 +2443,7 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     pool_plan = batch_placebo_pool_plan(agg[1], pl_plan[0][0], pl_plan[1][0], pl_post[0],
                                         prep.index[prep.model_rows])
     pool_seen = _fit_placebo_observed(pool_plan, fit)
-    pl_chain = _PlaceboChain(launches, pool_plan, pool_seen["seen_sum"])
+    pl_chain = _new_placebo_chain(launches, pool_plan, pool_seen, fit, placebo, alpha)
   if hmc:
     run = lambda launch: _run_hmc_launch(launch, fit, chain, pl_chain)          # pylint: disable=unnecessary-lambda-assignment
   else:
@@ -2469,14 +2587,16 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   by the summary and pool kernels of every ragged launch; panels fitted series by series in numpy.
   ValueError before any fit, the series and the label named, for a value outside the link's domain on
   a row its model conditions on.  `components` and `prediction_errors` stay on the transformed scale;
-  the analytic `placebo=` is refused; `placebo=Placebo(simulate=True)` runs the simulated placebo (not
-  together with `event_aggregates`)."""
+  the analytic `placebo=` is refused; `placebo=Placebo(simulate=True)` runs the simulated placebo, together
+  with `event_aggregates` as `Placebo(simulate=True, pool=True)`: the simulated pooled placebo in event
+  time, as in `fit_causalimpact_batch`."""
   data_options, model_options, inference_options = _options(alpha, data_options, model_options,
                                                              inference_options)
   link = lib.resolve_outcome_link(outcome_link)
   lib.check_link_placebo(link, placebo)
   placebo = lib.resolve_placebo(placebo)
-  lib.check_simulated_placebo_pool(placebo, None if event_aggregates is None else "event_aggregates")
+  lib.check_simulated_placebo_pool(placebo, None if event_aggregates is None else "event_aggregates",
+                                   "event_aggregates")
   pl_dim = None if placebo is None else lib.placebo_state_dim(model_options.local_linear_trend,
                                                               model_options.seasons)
   frames, columns = _frames_outcome_first(data, data_options)
@@ -2545,7 +2665,7 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   if plan is not None and placebo is not None:
     pool_plan = event_placebo_pool_plan(placebo, plan, pl_dim)
     pool_seen = _fit_placebo_observed(pool_plan, fit)
-    pl_chain = _PlaceboChain(launches, pool_plan, pool_seen["seen_sum"])
+    pl_chain = _new_placebo_chain(launches, pool_plan, pool_seen, fit, placebo, alpha)
   run = lambda launch: _run_launch(launch, kind, fit, chain, pl_chain)   # pylint: disable=unnecessary-lambda-assignment
   for guard in (chain, pl_chain):
     run = run if guard is None else guard.guarded(run)

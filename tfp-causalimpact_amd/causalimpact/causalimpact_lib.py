@@ -324,6 +324,8 @@ def fit_causalimpact(data: pd.DataFrame,
         "ModelOptions(local_linear_trend=..., seasons=...) instead.")
   link = resolve_outcome_link(outcome_link)
   check_link_placebo(link, placebo)
+  if placebo_sink is None:
+    check_single_fit_placebo(placebo)
   raw_data = None
   if link:
     raw_data, data = data, link_outcome(data, pre_period, post_period, data_options.outcome_column, link)
@@ -349,6 +351,11 @@ def fit_causalimpact(data: pd.DataFrame,
     state_dim = check_prediction_state(model_options.local_linear_trend, model_options.seasons)
   placebo_part = None
   placebo = resolve_placebo(placebo)
+  sink_simulated = None
+  if placebo is not None and placebo.pool and placebo_sink is not None:
+    # (batch.py, the simulated pooled placebo: the sink's totals are drawn from this fit's own stream)
+    seed = _sanitize_seed(seed)
+    sink_simulated = (link, placebo_stream(seed, None, range(inference_options.num_chains)))
   if placebo is not None:
     n_post = int(np.count_nonzero(base["flags"] & 2))
     n_pre = base["flags"].shape[0] - ci_data.model_after_pre_data.shape[0]
@@ -388,7 +395,7 @@ def fit_causalimpact(data: pd.DataFrame,
       devices=inference_options.devices, local_linear_trend=model_options.local_linear_trend,
       sampler=inference_options.sampler, request=request,
       hmc_init=inference_options.hmc_init, hmc_prior=inference_options.hmc_prior,
-      kernel_flags=inference_options.kernel_flags, placebo_sink=placebo_sink)
+      kernel_flags=inference_options.kernel_flags, placebo_sink=placebo_sink, sink_simulated=sink_simulated)
   if link:
     # the predictive arrays on the data scale: the linked draws (where the host has them) and the mean
     # of the linked draws, never the link of the mean
@@ -855,6 +862,13 @@ class Placebo:
                  `predicted_lower` / `predicted_upper`.  The only placebo under `outcome_link`, where
                  a window's total has no closed-form distribution; under the identity an independent
                  check of the analytic one.  The Monte-Carlo floor of `p` is 1 / (N + 1).
+    pool         False (the default).  True, with `simulate=True` and `aggregates=` /
+                 `event_aggregates=` of the batch and panel fits only: the SIMULATED POOLED placebo
+                 next to the per-series one -- every member's simulated totals at the group's origins
+                 and horizon, added draw by draw with the group's weights; `result.aggregates[name]`
+                 gets `placebo` and `placebo_quality` from the N pooled totals.  The members' paths are
+                 drawn independently of each other: the assumption a pooled band rests on, and the one
+                 this check tests.  The only pooled placebo under `outcome_link`.
   Fixed-parameter: every draw's scales and weights are those of the one fit of the whole pre-period,
   so the check is cheap and somewhat optimistic; the windows overlap, so the origins are not
   independent trials."""
@@ -862,10 +876,16 @@ class Placebo:
   max_origins: int = 32
   min_history: Optional[int] = None
   simulate: bool = False
+  pool: bool = False
 
   def __post_init__(self):
     if not isinstance(self.simulate, (bool, np.bool_)):
       raise TypeError(f"Placebo.simulate must be True or False, got {self.simulate!r}")
+    if not isinstance(self.pool, (bool, np.bool_)):
+      raise TypeError(f"Placebo.pool must be True or False, got {self.pool!r}")
+    if self.pool and not self.simulate:
+      raise ValueError("Placebo(pool=True) is the SIMULATED pooled placebo and needs `simulate=True`; the analytic "
+                       "pooled placebo runs with `Placebo()` wherever aggregates are asked for")
     if self.horizon is not None and int(self.horizon) < 1:
       raise ValueError(f"Placebo.horizon must be at least 1, got {self.horizon}")
     if int(self.max_origins) < 1:
@@ -893,13 +913,30 @@ def check_link_placebo(link: int, placebo) -> None:
     raise ValueError(_LINK_PLACEBO_REFUSAL)
 
 
-def check_simulated_placebo_pool(placebo: Optional[Placebo], argument: Optional[str]) -> None:
-  """The simulated placebo has no pooled form: ValueError naming `argument` ("aggregates",
-  "event_aggregates"; None: no pooled effects were asked for), before anything is fitted."""
-  if placebo is not None and placebo.simulate and argument is not None:
+def check_simulated_placebo_pool(placebo: Optional[Placebo], argument: Optional[str],
+                                 wanted: str = "aggregates") -> None:
+  """The simulated placebo pools only where it is asked to: ValueError naming `argument` ("aggregates",
+  "event_aggregates"; None: no pooled effects were asked for) for `Placebo(simulate=True)` without
+  `pool=True` together with pooled effects, and naming `wanted` for `pool=True` without any, before
+  anything is fitted."""
+  if placebo is None:
+    return
+  if placebo.pool and argument is None:
+    raise ValueError(f"`Placebo(pool=True)` pools the simulated placebo forecasts over `{wanted}`, and none "
+                     "were asked for")
+  if placebo.simulate and not placebo.pool and argument is not None:
     raise ValueError(f"`{argument}` cannot be combined with `Placebo(simulate=True)`: the pooled placebo "
                      "forecasts add the members' exact Gaussian moments, and a simulated pooled placebo is "
-                     "not available; use `Placebo()` (without `outcome_link`) for the pooled check")
+                     "asked for with `Placebo(simulate=True, pool=True)`; use that, or `Placebo()` (without "
+                     "`outcome_link`) for the analytic pooled check")
+
+
+def check_single_fit_placebo(placebo) -> None:
+  """`fit_causalimpact` has no pooled effects: ValueError for `Placebo(pool=True)`, before anything is
+  fitted."""
+  if isinstance(placebo, Placebo) and placebo.pool:
+    raise ValueError("`Placebo(pool=True)` is not available on `fit_causalimpact`: it pools over the `aggregates` "
+                     "of `fit_causalimpact_batch` or the `event_aggregates` of `fit_causalimpact_panel`")
 
 
 def placebo_horizon(placebo: Placebo, n_pre: int, n_post: int) -> int:
@@ -1265,7 +1302,9 @@ def _aggregate_placebo_frames(psum: Optional[Dict], actual, columns, horizon: in
   pit_mean [O] of the pooled forecast (`_native.finish_placebo_host`, or the device's), n_counted the
   member-steps every window counts and seen_sum the weighted sum of the members' `_placebo_seen`;
   actual [O]: the weighted sum of the members' `actual`; columns [O]: the origins as positions into
-  `labels`, the group's own axis (-1: unused).  The pooled forecast treats the members as independent
+  `labels`, the group's own axis (-1: unused).  A simulated summary (`_simulated_placebo_means` of the
+  pooled totals: pit_mean from `below`, and predicted_lower, predicted_upper) gives the columns and the
+  formulas of the per-series simulated frame.  The pooled forecast treats the members as independent
   given their draws: its band adds their predictive variances.  That is the assumption these frames
   test -- shocks common to the members show as a false-positive rate above alpha."""
   columns = np.asarray(columns).reshape(-1)
@@ -1278,7 +1317,8 @@ def _aggregate_placebo_frames(psum: Optional[Dict], actual, columns, horizon: in
   end = cols.pop("horizon_end_step")
   frame = pd.DataFrame({"horizon_end": labels[end], **cols}, index=labels[columns[used]])
   frame.index.name = "origin"
-  return frame[list(PLACEBO_COLUMNS)], _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
+  shown = list(PLACEBO_COLUMNS) + [k for k in PLACEBO_SIMULATED_COLUMNS if k in cols]
+  return frame[shown], _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
 
 
 # --------------------------------------------------------------------------------------
@@ -1719,11 +1759,16 @@ def _placebo_entry_host(one: "SeriesInputs", draws, scale, shift, observed, orig
   return dict(s=s, v=v, **_placebo_entry_seen(one, scale, shift, observed, origins, horizon))
 
 
-def _placebo_entry_seen(one: "SeriesInputs", scale, shift, observed, origins, horizon) -> Dict:
-  """n_counted, seen_sum and actual [O] of `_placebo_entry_host`: what needs no draws."""
+def _placebo_entry_seen(one: "SeriesInputs", scale, shift, observed, origins, horizon, link: int = 0) -> Dict:
+  """n_counted, seen_sum and actual [O] of `_placebo_entry_host`: what needs no draws.  Under an
+  outcome link (the simulated pooled placebo) seen_sum is the sum of the RAW outcome `observed` over
+  the counted steps (`_placebo_seen_linked`)."""
   origins = np.asarray(origins).reshape(-1)
-  cnt, seen = _placebo_seen(one.outcome(), one.mask, origins, horizon, scale, shift)
   observed = np.asarray(observed, np.float64)
+  if link:
+    cnt, seen = _placebo_seen_linked(observed, one.mask, origins, horizon, link)
+  else:
+    cnt, seen = _placebo_seen(one.outcome(), one.mask, origins, horizon, scale, shift)
   # (every window's own contiguous steps, summed as `_placebo_columns` sums them; 0 in an unused slot)
   steps = np.maximum(origins, 0).astype(np.int64)[:, None] + np.arange(int(horizon))[None, :]
   actual = np.where(origins >= 0, np.nansum(observed[np.minimum(steps, observed.shape[0] - 1)], axis=1), 0.0)
@@ -1792,13 +1837,33 @@ def _simulated_placebo_summaries(inputs: Sequence[SeriesInputs], part: PlaceboPa
   n_counted, seen_sum = np.stack([c for c, _ in seen]), np.stack([a for _, a in seen])
   ranks = _placebo_sim_ranks(num_draws, part.quantiles)
   got = simulate(np.nan_to_num(seen_sum), ranks)
+  return dict(_simulated_placebo_means(got, ranks, num_draws, part.quantiles), n_counted=n_counted,
+              seen_sum=seen_sum)
+
+
+def _simulated_placebo_means(got: Dict[str, np.ndarray], ranks, num_draws: int, quantiles) -> Dict[str, np.ndarray]:
+  """What the frames of a simulated placebo read, from the statistics of `simulate_placebo` or
+  `pool_simulated_placebo` (predicted_mean, spread_mean, below [n, O], total_order [n, R, O] at
+  `ranks` = `_placebo_sim_ranks`): predicted_mean, spread_mean, pit_mean = (below + 0.5) / (N + 1) and
+  predicted_lower, predicted_upper, the two quantiles interpolated from the order statistics."""
   pos = {r: i for i, r in enumerate(ranks)}
-  (lo_a, hi_a, g_a), (lo_b, hi_b, g_b) = _quantile_ranks(num_draws, part.quantiles)
+  (lo_a, hi_a, g_a), (lo_b, hi_b, g_b) = _quantile_ranks(num_draws, quantiles)
   by_rank = {r: got["total_order"][:, pos[r]] for r in (lo_a, hi_a, lo_b, hi_b)}
   return dict(predicted_mean=got["predicted_mean"], spread_mean=got["spread_mean"],
-              pit_mean=(got["below"] + 0.5) / (num_draws + 1.0), n_counted=n_counted, seen_sum=seen_sum,
+              pit_mean=(got["below"] + 0.5) / (num_draws + 1.0),
               predicted_lower=_lerp_order_stats(by_rank, lo_a, hi_a, g_a),
               predicted_upper=_lerp_order_stats(by_rank, lo_b, hi_b, g_b))
+
+
+def _placebo_entry_simulated_host(one: "SeriesInputs", draws, scale, shift, observed, origins, horizon,
+                                  link: int, stream) -> Dict:
+  """What one member adds to a SIMULATED pooled placebo forecast, in numpy: totals [O, N], the
+  simulated totals of `_placebo_simulated_host` at the origins [O] and the horizon of the GROUP on
+  the member's own stream (`placebo_stream` of its series), and n_counted, seen_sum, actual [O] of
+  `_placebo_entry_seen` under `link`."""
+  origins = np.asarray(origins).reshape(-1)
+  got = _placebo_simulated_host(*one.filter_inputs(), draws, scale, shift, origins, horizon, link, stream)
+  return dict(totals=got["totals"], **_placebo_entry_seen(one, scale, shift, observed, origins, horizon, link))
 
 
 def _host_placebo_simulations(inputs: Sequence[SeriesInputs], draws, part: PlaceboPart):
@@ -1920,7 +1985,7 @@ def _model_mask(ci_data) -> np.ndarray:
 def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps, model=None,
                  dtype=np.float32, seasons=(), num_chains=1, devices=None,
                  local_linear_trend=False, sampler="gibbs", request: Optional[SummaryRequest] = None,
-                 hmc_init="gibbs", hmc_prior="slab", kernel_flags=0, placebo_sink=None):
+                 hmc_init="gibbs", hmc_prior="slab", kernel_flags=0, placebo_sink=None, sink_simulated=None):
   """_train_causalimpact_sts plus the `SummaryRecord` of `request` (on the caller's scale; None: an
   empty record), the record of ONE series (`SummaryRecord.of_series`).  On one device, with the
   float32 Gibbs sampler and unless `request.on_device` is off or it wants the trajectories kept, the
@@ -2059,8 +2124,12 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
     # (batch.py, pooled placebo forecasts: the per-draw terms from the parameter draws in the
     #  sampler's units, mapped to the caller's scale like every other summary)
     pooled = _pooled_draws({k: out[k][None] for k in _PARAMETER_DRAWS}, 0)
-    placebo_sink(lambda origins, horizon: _placebo_entry_host(
-        inputs[0], pooled, internal.scale, internal.shift, internal.observed, origins, horizon))
+    if sink_simulated is not None:       # (link, stream): the simulated totals in place of the moments
+      placebo_sink(lambda origins, horizon: _placebo_entry_simulated_host(
+          inputs[0], pooled, internal.scale, internal.shift, internal.observed, origins, horizon, *sink_simulated))
+    else:
+      placebo_sink(lambda origins, horizon: _placebo_entry_host(
+          inputs[0], pooled, internal.scale, internal.shift, internal.observed, origins, horizon))
   if record.components is not None and cond_s != 1.0:
     # the weights on the caller's model scale, as in `samples`
     record = dataclasses.replace(record, components={

@@ -33,6 +33,9 @@
 // accumulators and placebo_finish_kernel turns the accumulators into the three matrices of the
 // pooled sum, N(S, U) given the members' draws:
 //   e = seen - S;  SUM = S;  SPREAD = U + e^2;  PIT = 0.5 erfc(-e / sqrt(2 U));  all 0 where U == 0.
+// The SIMULATED totals (below) pool over the same table (ci_session_pool_simulated_placebo): the
+// ENTRIES build of placebo_sim_kernel simulates the entries' rows, placebo_pool_kernel<0, 1> adds them
+// to one-plane accumulators, and the row statistics of the simulated placebo are taken over those.
 #pragma once
 #include "ci_link.h"
 #include "ci_predict.h"
@@ -218,8 +221,8 @@ __global__ __launch_bounds__(64) void placebo_kernel(PlaceboArgs k) {
 // are formed when h reaches them.  Lane 0 of the grid's first column also stores cnt per (b, slot):
 // the rows the statistics below leave at 0.
 struct PlaceboSimArgs {
-  PlaceboArgs q;                   // q.p.out [rows of this launch, N]; q.series_of unused
-  int b0;                          // the first series of this launch: grid row r is series b0 + r
+  PlaceboArgs q;                   // q.p.out [rows of this launch, N]; q.series_of read by the entry-table build only
+  int b0;                          // the first series of this launch: grid row r is series b0 + r (no entry table)
   int kept;                        // S: kept draws per chain, n = c * S + s
   uint32_t chain_offset;           // the global id of the session's chain 0
   const uint32_t* keys;            // [B, 2]: the Philox key every series' fit ran on
@@ -238,14 +241,19 @@ __device__ __forceinline__ double placebo_sim_normal(const Rng& g, uint32_t iter
   return (h & 1) ? z1 : z0;
 }
 
-// grid (ceil(N / 64), series of the launch), block 64.
-template <int HAS_SLOPE, int NS, int LINK>
+// grid (ceil(N / 64), series of the launch), block 64.  The entry-table build (ENTRIES) has the grid
+// (ceil(N / 64), entries of the launch): row e simulates series q.series_of[e] from the origins' row e
+// with q.horizon[e] and writes rows e * O .. of `out` and `counted` -- the tables of
+// ci_session_pool_placebo, whose pointers the host sets to the launch's first entry; b0 is not
+// read.  Everything else of the row, the Philox key included, is the series'.
+template <int HAS_SLOPE, int NS, int LINK, bool ENTRIES = false>
 __global__ __launch_bounds__(64) void placebo_sim_kernel(PlaceboSimArgs k) {
   constexpr int N1 = NS ? NS - 1 : 0, O = 1 + HAS_SLOPE, D = O + N1, NP = D * (D + 1) / 2;
   constexpr int ZS = O < D ? O : 0;              // the block's first effect (NS > 0)
   const PredArgs& p = k.q.p;
   const int n = blockIdx.x * 64 + threadIdx.x, N = p.N, T = p.T, NO = k.q.O;
-  const size_t e = blockIdx.y, b = (size_t)k.b0 + e;
+  const size_t e = blockIdx.y, b = ENTRIES ? (size_t)k.q.series_of[e] : (size_t)k.b0 + e;
+  const size_t plan = ENTRIES ? e : b;           // the row of the plan: origins [., O], horizon [.]
   if (n >= N) return;
   const int Tb = p.series_T ? p.series_T[b] : T;
   const size_t bn = b * N + n;
@@ -267,8 +275,8 @@ __global__ __launch_bounds__(64) void placebo_sim_kernel(PlaceboSimArgs k) {
   const double* reg = p.reg ? p.reg + b * T * N + n : nullptr;
   double* out = p.out + e * NO * N + n;
   int* counted = n == 0 ? k.counted + e * NO : nullptr;
-  const int* org = k.q.origins + b * NO;
-  const int Hb = k.q.horizon[b];
+  const int* org = k.q.origins + plan * NO;
+  const int Hb = k.q.horizon[plan];
   Rng rng;
   rng.k0 = k.keys[2 * b];
   rng.k1 = k.keys[2 * b + 1];
@@ -405,12 +413,16 @@ __global__ __launch_bounds__(256) void placebo_sim_seen_kernel(size_t rows, int 
 //   WHICH == 0 (M holds SUM):  S = S + w_k * s_k;    WHICH == 1 (M holds VAR):  U = U + (w_k * w_k) * v_k
 // so the result depends neither on the launch geometry nor on where the entries are cut.
 // grid (ceil(N / 64), min(G * O, 65535)), block 64.
-template <int WHICH>
+// PLANES: the planes of a row of acc.  placebo_pool_kernel<0, 1> is the ONE-PLANE accumulate of
+// ci_session_pool_simulated_placebo: M holds the entries' simulated totals, acc is [G, O, N] and
+// POOL = POOL + w_k * TOTAL_k -- the arithmetic of WHICH == 0 on accumulators of stride N.
+template <int WHICH, int PLANES = 2>
 __global__ __launch_bounds__(64) void placebo_pool_kernel(int N, int O, size_t rows, int c0, int c1,
                                                           const int* __restrict__ offsets,
                                                           const double* __restrict__ weights,
                                                           const double* __restrict__ M,
                                                           double* __restrict__ acc) {
+  static_assert(WHICH < PLANES, "the plane of this pass");
   const int n = blockIdx.x * 64 + threadIdx.x;
   if (n >= N) return;
   for (size_t row = blockIdx.y; row < rows; row += gridDim.y) {
@@ -418,7 +430,7 @@ __global__ __launch_bounds__(64) void placebo_pool_kernel(int N, int O, size_t r
     const int k0 = offsets[g] > c0 ? offsets[g] : c0;
     const int k1 = offsets[g + 1] < c1 ? offsets[g + 1] : c1;
     if (k0 >= k1) continue;
-    double* at = acc + (row * 2 + WHICH) * N + n;
+    double* at = acc + (row * PLANES + WHICH) * N + n;
     double a = *at;
     for (int k = k0; k < k1; ++k) {
       const double w = WHICH ? __dmul_rn(weights[k], weights[k]) : weights[k];

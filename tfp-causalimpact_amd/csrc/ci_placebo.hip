@@ -1,6 +1,6 @@
 // Instantiation unit of the placebo forecasts (ci_placebo.h) and their launches;
-// ci_session_summarize_placebo, ci_session_pool_placebo and ci_session_simulate_placebo
-// (ci_summary.hip) call them.
+// ci_session_summarize_placebo, ci_session_pool_placebo, ci_session_simulate_placebo and
+// ci_session_pool_simulated_placebo (ci_summary.hip) call them.
 #include "ci_placebo.h"
 
 namespace ci {
@@ -65,6 +65,45 @@ hipError_t placebo_sim_launch(hipStream_t stream, int nb, int has_slope, int num
   const PlaceboSimFn fn = has_slope ? placebo_sim_fn<1>(num_seasons, link) : placebo_sim_fn<0>(num_seasons, link);
   if (!fn || link < 0 || link >= NUM_LINKS) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3((args.q.p.N + 63) / 64, nb), dim3(64), 0, stream, args);
+  return hipGetLastError();
+}
+
+template <int HAS_SLOPE, int NS> static PlaceboSimFn placebo_sim_entries_fn(int link) {
+  if (link == LINK_LOG) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG, true>;
+  if (link == LINK_LOG1P) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG1P, true>;
+  return placebo_sim_kernel<HAS_SLOPE, NS, LINK_IDENTITY, true>;
+}
+
+template <int HAS_SLOPE> static PlaceboSimFn placebo_sim_entries_fn(int ns, int link) {
+  switch (ns) {
+    case 0: return placebo_sim_entries_fn<HAS_SLOPE, 0>(link);
+    case 2: return placebo_sim_entries_fn<HAS_SLOPE, 2>(link);
+    case 3: return placebo_sim_entries_fn<HAS_SLOPE, 3>(link);
+    case 4: return placebo_sim_entries_fn<HAS_SLOPE, 4>(link);
+    case 5: return placebo_sim_entries_fn<HAS_SLOPE, 5>(link);
+    case 6: return placebo_sim_entries_fn<HAS_SLOPE, 6>(link);
+    case 7: return placebo_sim_entries_fn<HAS_SLOPE, 7>(link);
+    default: return nullptr;
+  }
+}
+
+// The simulated totals of E entries of a group table (args.q.series_of, origins and horizon from the
+// launch's first entry on): rows [E * O, N] in args.q.p.out, cnt per row in args.counted.
+hipError_t placebo_sim_entries_launch(hipStream_t stream, int E, int has_slope, int num_seasons, int link,
+                                      const PlaceboSimArgs& args) {
+  const PlaceboSimFn fn = has_slope ? placebo_sim_entries_fn<1>(num_seasons, link)
+                                    : placebo_sim_entries_fn<0>(num_seasons, link);
+  if (!fn || link < 0 || link >= NUM_LINKS || !args.q.series_of) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fn, dim3((args.q.p.N + 63) / 64, E), dim3(64), 0, stream, args);
+  return hipGetLastError();
+}
+
+// The rows [(c1 - c0) * O, N] of one pass of simulated totals added to acc [G, O, N].
+hipError_t placebo_pool_totals_launch(hipStream_t stream, int N, int O, int G, int c0, int c1,
+                                      const int* offsets, const double* weights, const double* M, double* acc) {
+  const size_t rows = (size_t)G * O;
+  const dim3 grid((N + 63) / 64, (unsigned)(rows < 65535 ? rows : 65535)), block(64);
+  hipLaunchKernelGGL((placebo_pool_kernel<0, 1>), grid, block, 0, stream, N, O, rows, c0, c1, offsets, weights, M, acc);
   return hipGetLastError();
 }
 

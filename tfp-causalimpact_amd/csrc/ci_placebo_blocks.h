@@ -144,8 +144,11 @@ struct PlaceboBlocksSimArgs {
   BlockModel m;
 };
 
-// grid (ceil(N / (64 / G)), series of the launch), block 64.
-template <int G, int LINK>
+// grid (ceil(N / (64 / G)), series of the launch), block 64.  The entry-table build (ENTRIES;
+// ci_session_pool_simulated_placebo_blocks) has the grid (ceil(N / (64 / G)), entries of the launch)
+// and rows as placebo_sim_kernel's; the entry is uniform over the workgroup, so every barrier is met
+// by all 64 lanes as before.
+template <int G, int LINK, bool ENTRIES = false>
 __global__ __launch_bounds__(64) void placebo_blocks_sim_kernel(PlaceboBlocksSimArgs k) {
   constexpr int FPW = 64 / G;
   __shared__ PbShared sh;
@@ -154,7 +157,8 @@ __global__ __launch_bounds__(64) void placebo_blocks_sim_kernel(PlaceboBlocksSim
   const int n_own = blockIdx.x * FPW + (int)threadIdx.x / G;
   const bool active = n_own < N;
   const int n = active ? n_own : N - 1;
-  const size_t e = blockIdx.y, b = (size_t)k.s.b0 + e, bn = b * N + n;
+  const size_t e = blockIdx.y, b = ENTRIES ? (size_t)k.s.q.series_of[e] : (size_t)k.s.b0 + e, bn = b * N + n;
+  const size_t plan = ENTRIES ? e : b;           // the row of the plan: origins [., O], horizon [.]
   PbCtx c;
   double H, a, P[G];
   pb_begin<G>(p, k.m, sh, b, bn, c, H, a, P);
@@ -165,8 +169,8 @@ __global__ __launch_bounds__(64) void placebo_blocks_sim_kernel(PlaceboBlocksSim
   const double* reg = p.reg ? p.reg + b * T * N + n : nullptr;
   double* out = p.out + e * NO * N + n;
   int* counted = writer && n == 0 ? k.s.counted + e * NO : nullptr;
-  const int* org = k.s.q.origins + b * NO;
-  const int Hb = k.s.q.horizon[b];
+  const int* org = k.s.q.origins + plan * NO;
+  const int Hb = k.s.q.horizon[plan];
   Rng rng;
   rng.k0 = k.s.keys[2 * b];
   rng.k1 = k.s.keys[2 * b + 1];

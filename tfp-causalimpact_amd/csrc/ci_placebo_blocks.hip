@@ -1,6 +1,6 @@
 // Instantiation unit of the block-model placebo forecasts (ci_placebo_blocks.h) and their launch;
-// ci_session_summarize_placebo_blocks, ci_session_pool_placebo_blocks and ci_session_simulate_placebo_blocks
-// (ci_summary.hip) call them.
+// ci_session_summarize_placebo_blocks, ci_session_pool_placebo_blocks, ci_session_simulate_placebo_blocks and
+// ci_session_pool_simulated_placebo_blocks (ci_summary.hip) call them.
 #include "ci_placebo_blocks.h"
 
 namespace ci {
@@ -56,6 +56,26 @@ hipError_t placebo_blocks_sim_launch(hipStream_t stream, int nb, int link, const
                               : G == 32 ? placebo_blocks_sim_fn<32>(link) : placebo_blocks_sim_fn<64>(link);
   const int fpw = 64 / G;
   hipLaunchKernelGGL(fn, dim3((args.s.q.p.N + fpw - 1) / fpw, nb), dim3(64), 0, stream, args);
+  return hipGetLastError();
+}
+
+template <int G> static PlaceboBlocksSimFn placebo_blocks_sim_entries_fn(int link) {
+  if (link == LINK_LOG) return placebo_blocks_sim_kernel<G, LINK_LOG, true>;
+  if (link == LINK_LOG1P) return placebo_blocks_sim_kernel<G, LINK_LOG1P, true>;
+  return placebo_blocks_sim_kernel<G, LINK_IDENTITY, true>;
+}
+
+// The simulated totals of E entries of a group table (placebo_sim_entries_launch's for the block models).
+hipError_t placebo_blocks_sim_entries_launch(hipStream_t stream, int E, int link, const PlaceboBlocksSimArgs& args) {
+  if (args.m.d < 1 || args.m.d > PB_MAX_STATE || link < 0 || link >= NUM_LINKS || !args.s.q.series_of)
+    return hipErrorInvalidValue;
+  const int G = blocks_group_size(args.m.d);
+  const PlaceboBlocksSimFn fn = G == 8 ? placebo_blocks_sim_entries_fn<8>(link)
+                              : G == 16 ? placebo_blocks_sim_entries_fn<16>(link)
+                              : G == 32 ? placebo_blocks_sim_entries_fn<32>(link)
+                                        : placebo_blocks_sim_entries_fn<64>(link);
+  const int fpw = 64 / G;
+  hipLaunchKernelGGL(fn, dim3((args.s.q.p.N + fpw - 1) / fpw, E), dim3(64), 0, stream, args);
   return hipGetLastError();
 }
 

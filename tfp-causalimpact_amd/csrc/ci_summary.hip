@@ -1,7 +1,8 @@
 // ci_summary.hip -- the on-device summaries behind the C-ABI (kernels: ci_summary.h,
 // ci_components.h, ci_predict.h): ci_session_summarize, ci_session_summarize_components,
 // ci_session_summarize_predictions, ci_session_summarize_placebo, ci_session_pool_placebo,
-// ci_session_pool_placebo_blocks, ci_session_simulate_placebo[_blocks] (kernels: ci_placebo.h, ci_placebo_blocks.h),
+// ci_session_pool_placebo_blocks, ci_session_simulate_placebo[_blocks], ci_session_pool_simulated_placebo[_blocks]
+// (kernels: ci_placebo.h, ci_placebo_blocks.h),
 // ci_session_summarize_windows, ci_ll_session_summarize_windows
 // (kernel: ci_windows.h), ci_session_summarize_paths, ci_ll_session_summarize_paths (kernels: ci_paths.h),
 // ci_session_set_link and ci_session_value_mean (the outcome link: ci_link.h),
@@ -150,6 +151,11 @@ hipError_t placebo_blocks_pool_launch(hipStream_t stream, int E, const PlaceboBl
 hipError_t placebo_sim_launch(hipStream_t stream, int nb, int has_slope, int num_seasons, int link,
                               const PlaceboSimArgs& args);
 hipError_t placebo_blocks_sim_launch(hipStream_t stream, int nb, int link, const PlaceboBlocksSimArgs& args);
+hipError_t placebo_sim_entries_launch(hipStream_t stream, int E, int has_slope, int num_seasons, int link,
+                                      const PlaceboSimArgs& args);
+hipError_t placebo_blocks_sim_entries_launch(hipStream_t stream, int E, int link, const PlaceboBlocksSimArgs& args);
+hipError_t placebo_pool_totals_launch(hipStream_t stream, int N, int O, int G, int c0, int c1,
+                                      const int* offsets, const double* weights, const double* M, double* acc);
 hipError_t placebo_sim_seen_launch(hipStream_t stream, size_t rows, int N, double* M, const double* seen,
                                    const int* counted, double* below, int rewrite);
 hipError_t placebo_pool_launch(hipStream_t stream, int N, int O, int G, int which, int c0, int c1,
@@ -1143,6 +1149,38 @@ int ci_test_session_simulate_placebo(ci_session* s, int32_t blocks, const double
                           predicted_mean, spread_mean, below, total_order, totals, max_rows, num_chunks);
 }
 
+// The plan of a pooled placebo call (ci_session_pool_placebo, ci_session_pool_simulated_placebo):
+// one horizon >= 1 per group, every entry's origin row ascending with -1 only at the end and
+// o + H_g <= T_b of its member; entry_horizon [K] is the group's horizon per entry.
+static int check_pool_plan(const ci_session* s, int G, const int32_t* offsets, const int32_t* members, int O,
+                           const int32_t* origins, const int32_t* horizon, std::vector<int>& entry_horizon) {
+  const int T = s->pb.T, K = offsets[G];
+  entry_horizon.assign((size_t)(K ? K : 1), 0);
+  for (int g = 0; g < G; ++g) {
+    const int Hg = horizon[g];
+    if (Hg < 1) return fail("group %d: the horizon must be at least 1, got %d", g, Hg);
+    for (int k = offsets[g]; k < offsets[g + 1]; ++k) {
+      const int b = members[k], Tb = s->ragged ? s->lengths[b] : T;
+      const int32_t* row = origins + (size_t)k * O;
+      entry_horizon[k] = Hg;
+      bool ended = false;
+      for (int i = 0; i < O; ++i) {
+        const int o = row[i];
+        if (o == -1) { ended = true; continue; }
+        if (o < 0)
+          return fail("group %d, entry %d (member %d): slot %d must hold a step or -1 (unused), got %d", g, k, b, i, o);
+        if (ended || (i > 0 && o <= row[i - 1]))
+          return fail("group %d, entry %d (member %d): the origins must be strictly ascending with the unused "
+                      "slots (-1) at the end (slot %d holds %d)", g, k, b, i, o);
+        if ((long long)o + Hg > Tb)
+          return fail("group %d, entry %d (member %d): the origin %d of slot %d with horizon %d reaches beyond "
+                      "the series' %d steps", g, k, b, o, i, Hg, Tb);
+      }
+    }
+  }
+  return 0;
+}
+
 // The placebo forecasts of POOLED sums: per group, slot and draw the weighted sum S of the members'
 // forecasts and the sum U of their predictive variances (include/causalimpact_amd.h).  The entries
 // of the group table pass through `value` at most B at a time, a SUM pass and its accumulate, then a
@@ -1172,29 +1210,8 @@ static int pool_placebo(ci_session* s, bool blocks, const double* scale, const d
   if (!seen && (predicted_mean || spread_mean || pit_mean))
     return fail("predicted_mean, spread_mean and pit_mean need `seen`, the pooled observed sums");
   const int K = offsets[G];
-  std::vector<int> entry_horizon((size_t)(K ? K : 1));
-  for (int g = 0; g < G; ++g) {
-    const int Hg = horizon[g];
-    if (Hg < 1) return fail("group %d: the horizon must be at least 1, got %d", g, Hg);
-    for (int k = offsets[g]; k < offsets[g + 1]; ++k) {
-      const int b = members[k], Tb = s->ragged ? s->lengths[b] : T;
-      const int32_t* row = origins + (size_t)k * O;
-      entry_horizon[k] = Hg;
-      bool ended = false;
-      for (int i = 0; i < O; ++i) {
-        const int o = row[i];
-        if (o == -1) { ended = true; continue; }
-        if (o < 0)
-          return fail("group %d, entry %d (member %d): slot %d must hold a step or -1 (unused), got %d", g, k, b, i, o);
-        if (ended || (i > 0 && o <= row[i - 1]))
-          return fail("group %d, entry %d (member %d): the origins must be strictly ascending with the unused "
-                      "slots (-1) at the end (slot %d holds %d)", g, k, b, i, o);
-        if ((long long)o + Hg > Tb)
-          return fail("group %d, entry %d (member %d): the origin %d of slot %d with horizon %d reaches beyond "
-                      "the series' %d steps", g, k, b, o, i, Hg, Tb);
-      }
-    }
-  }
+  std::vector<int> entry_horizon;
+  if (check_pool_plan(s, G, offsets, members, O, origins, horizon, entry_horizon)) return 1;
   HIP_TRY(hipSetDevice(pb.device));
   SummScratch& w = s->summ;
   if (summ_scratch_alloc(w, B, T, N)) return 1;
@@ -1310,6 +1327,185 @@ int ci_test_session_pool_placebo_blocks(ci_session* s, const double* scale, cons
     return fail("chunk_entries must be in [1, %d] (the session's series), got %d", s->pb.num_series, chunk_entries);
   return pool_placebo(s, true, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
                       horizon, init, out, seen, predicted_mean, spread_mean, pit_mean, chunk_entries);
+}
+
+// The SIMULATED placebo forecasts of pooled sums (include/causalimpact_amd.h): the entries of the group
+// table pass through `value` at most `chunk` at a time -- ONE simulation pass (the entry-table build
+// of simulate_placebo's kernel; TOTAL is a function of (series, origin, slot, horizon, n) alone) and
+// its accumulate into POOL [G, O, N], the call's own.  `out` is downloaded, then the statistics of
+// simulate_placebo are taken over the accumulators' rows, copied through `value` at most B * T rows
+// at a time (whole groups, so that the selection's [G, R, O] layout holds per chunk): row means,
+// order statistics, the count below `seen`, the rewrite to squares and its row means.  Nothing
+// depends on where either kind of chunk is cut.  chunk_entries (tests; 0: B): in [1, B].
+static int pool_simulated_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
+                                  int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                  const double* weights, int32_t max_origins, const int32_t* origins,
+                                  const int32_t* horizon, int32_t link, const double* init, double* out,
+                                  const double* seen, const int32_t* counted, int32_t num_ranks,
+                                  const int32_t* ranks, double* predicted_mean, double* spread_mean,
+                                  double* below, double* total_order, int32_t chunk_entries) {
+  if (!s || !scale || !shift || !offsets || !members || !weights || !origins || !horizon || !out || !ranks)
+    return fail("NULL argument");
+  const ci_problem& pb = s->pb;
+  const char* who = blocks ? "ci_session_pool_simulated_placebo_blocks" : "ci_session_pool_simulated_placebo";
+  if (blocks ? pred_blocks_check_session(s, who) : pred_check_session(s, who)) return 1;
+  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
+  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins, G = num_groups, R = num_ranks;
+  if (chunk_entries < 0 || chunk_entries > B)
+    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", B, chunk_entries);
+  const int chunk = chunk_entries ? chunk_entries : B;
+  if (check_groups(B, G, offsets, members, weights)) return 1;
+  if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
+  if (link < 0 || link >= ci::NUM_LINKS)
+    return fail("link must be CI_LINK_IDENTITY, CI_LINK_LOG or CI_LINK_LOG1P (0 to %d), got %d", ci::NUM_LINKS - 1, link);
+  if (check_ranks(R, ranks, N)) return 1;
+  const bool stats = predicted_mean || spread_mean || below || total_order;
+  if (stats && (!seen || !counted))
+    return fail("predicted_mean, spread_mean, below and total_order need `seen` and `counted`, the pooled "
+                "observed totals and the member-steps they count");
+  const int K = offsets[G];
+  std::vector<int> entry_horizon;
+  if (check_pool_plan(s, G, offsets, members, O, origins, horizon, entry_horizon)) return 1;
+  // the Philox key every series' fit ran on (simulate_placebo's)
+  std::vector<uint32_t> keys((size_t)2 * B);
+  const int shared = (pb.flags & CI_FLAG_SHARED_SERIES_STREAMS) ? -1 : 0;
+  for (int b = 0; b < B; ++b) {
+    const int sid = s->ids.empty() ? pb.series_offset + b : s->ids[b];
+    keys[2 * b] = ci::stream_key0(pb.seed[0], shared, sid);
+    keys[2 * b + 1] = ci::stream_key1(pb.seed[1], shared, sid);
+  }
+  HIP_TRY(hipSetDevice(pb.device));
+  SummScratch& w = s->summ;
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  hipStream_t stream = s->stream;
+  double* d_scale = w.obs.p + (size_t)B * T;
+  double* d_shift = d_scale + B;
+  if (pred_init_upload(s)) return 1;
+  const size_t rows = (size_t)G * O, acc_n = rows * N, Ka = K ? K : 1;
+  const size_t chunk_rows = (size_t)(K < chunk ? (K ? K : 1) : chunk) * O;
+  DevBuf<int> d_int;                     // offsets [G + 1], members [K], horizon [K], origins [K, O],
+                                         // cnt of a chunk's rows [chunk, O], counted [G, O]
+  DevBuf<double> d_dbl;                  // acc [G, O, N], seen, mean, spread, below [G, O] each, order [G, R, O], weights [K]
+  DevBuf<uint32_t> d_keys;               // [B, 2]
+  HIP_TRY(d_int.alloc((size_t)G + 1 + 2 * Ka + Ka * O + chunk_rows + rows));
+  HIP_TRY(d_dbl.alloc(acc_n + 4 * rows + rows * R + Ka));
+  HIP_TRY(d_keys.alloc((size_t)2 * B));
+  int* d_off = d_int.p;
+  int* d_members = d_off + G + 1;
+  int* d_horizon = d_members + Ka;
+  int* d_origins = d_horizon + Ka;
+  int* d_cnt = d_origins + Ka * O;
+  int* d_counted = d_cnt + chunk_rows;
+  double* d_acc = d_dbl.p;
+  double* d_seen = d_acc + acc_n;
+  double *d_mean = d_seen + rows, *d_spread = d_mean + rows, *d_below = d_spread + rows;
+  double* d_order = d_below + rows;
+  double* d_weights = d_order + rows * R;
+  HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+  if (K > 0) {
+    HIP_TRY(hipMemcpyAsync(d_members, members, (size_t)K * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_horizon, entry_horizon.data(), (size_t)K * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_origins, origins, (size_t)K * O * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_weights, weights, (size_t)K * sizeof(double), hipMemcpyHostToDevice, stream));
+  }
+  if (init)
+    HIP_TRY(hipMemcpyAsync(d_acc, init, acc_n * sizeof(double), hipMemcpyHostToDevice, stream));
+  else
+    HIP_TRY(hipMemsetAsync(d_acc, 0, acc_n * sizeof(double), stream));
+  if (stats) {
+    HIP_TRY(hipMemcpyAsync(d_seen, seen, rows * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_counted, counted, rows * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
+  }
+  HIP_TRY(hipMemcpyAsync(d_keys.p, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
+  const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
+  if (P > 0 && K > 0)
+    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
+                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
+  ci::PlaceboBlocksSimArgs ab;
+  ci::PlaceboSimArgs& a = ab.s;
+  a.q.p.N = N; a.q.p.T = T;
+  a.q.p.y = s->y.p; a.q.p.mask = s->mask.p; a.q.p.season_change = s->season_change.p; a.q.p.series_T = d_series_T;
+  a.q.p.obs = s->o_obs.p; a.q.p.lscale = s->o_lscale.p; a.q.p.sscale = s->o_sscale.p; a.q.p.drift = s->o_drift.p;
+  a.q.p.init = s->pred_init.p; a.q.p.scales = d_scale; a.q.p.shifts = d_shift;
+  a.q.p.reg = P > 0 ? w.cum.p : nullptr;
+  a.q.p.out = w.value.p; a.q.p.ll = nullptr;
+  a.q.O = O;
+  a.b0 = 0; a.kept = pb.num_results; a.chain_offset = (uint32_t)pb.chain_offset; a.keys = d_keys.p;
+  a.counted = d_cnt;
+  if (blocks) ab.m = pred_block_model(pb);
+  // at most B entries at a time: [B * O, N] with O <= T fits `value`
+  for (int c0 = 0; c0 < K; c0 += chunk) {
+    const int c1 = K - c0 < chunk ? K : c0 + chunk;
+    a.q.series_of = d_members + c0; a.q.origins = d_origins + (size_t)c0 * O; a.q.horizon = d_horizon + c0;
+    if (blocks) HIP_TRY(ci::placebo_blocks_sim_entries_launch(stream, c1 - c0, link, ab));
+    else HIP_TRY(ci::placebo_sim_entries_launch(stream, c1 - c0, pb.has_slope, NS, link, a));
+    HIP_TRY(ci::placebo_pool_totals_launch(stream, N, O, G, c0, c1, d_off, d_weights, w.value.p, d_acc));
+  }
+  HIP_TRY(hipMemcpyAsync(out, d_acc, acc_n * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (stats) {
+    // whole groups, as many as `value` holds: (B * T / O) * O rows, at least O
+    const size_t per_pass = ((size_t)B * T / O) * O;
+    for (size_t r0 = 0; r0 < rows; r0 += per_pass) {
+      const size_t nr = rows - r0 < per_pass ? rows - r0 : per_pass;
+      HIP_TRY(hipMemcpyAsync(w.value.p, d_acc + r0 * N, nr * N * sizeof(double), hipMemcpyDeviceToDevice, stream));
+      if (predicted_mean) HIP_TRY(ci::comp_launch_row_stats(stream, nr, N, w.value.p, d_mean + r0, nullptr));
+      if (total_order)
+        HIP_TRY(launch_select(stream, N, O, (int)nr, R, w.ranks.p, w.value.p, nullptr, d_order + r0 * R, nullptr));
+      if (spread_mean || below) {
+        HIP_TRY(ci::placebo_sim_seen_launch(stream, nr, N, w.value.p, d_seen + r0, d_counted + r0,
+                                            below ? d_below + r0 : nullptr, spread_mean != nullptr));
+        if (spread_mean) HIP_TRY(ci::comp_launch_row_stats(stream, nr, N, w.value.p, d_spread + r0, nullptr));
+      }
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (predicted_mean) HIP_TRY(hipMemcpy(predicted_mean, d_mean, rows * sizeof(double), hipMemcpyDeviceToHost));
+  if (spread_mean) HIP_TRY(hipMemcpy(spread_mean, d_spread, rows * sizeof(double), hipMemcpyDeviceToHost));
+  if (below) HIP_TRY(hipMemcpy(below, d_below, rows * sizeof(double), hipMemcpyDeviceToHost));
+  if (total_order) HIP_TRY(hipMemcpy(total_order, d_order, rows * R * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int ci_session_pool_simulated_placebo(ci_session* s, const double* scale, const double* shift,
+                                      int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                      const double* weights, int32_t max_origins, const int32_t* origins,
+                                      const int32_t* horizon, int32_t link, const double* init, double* out,
+                                      const double* seen, const int32_t* counted, int32_t num_ranks,
+                                      const int32_t* ranks, double* predicted_mean, double* spread_mean,
+                                      double* below, double* total_order) {
+  return pool_simulated_placebo(s, false, scale, shift, num_groups, offsets, members, weights, max_origins,
+                                origins, horizon, link, init, out, seen, counted, num_ranks, ranks,
+                                predicted_mean, spread_mean, below, total_order, 0);
+}
+
+int ci_session_pool_simulated_placebo_blocks(ci_session* s, const double* scale, const double* shift,
+                                             int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                             const double* weights, int32_t max_origins, const int32_t* origins,
+                                             const int32_t* horizon, int32_t link, const double* init, double* out,
+                                             const double* seen, const int32_t* counted, int32_t num_ranks,
+                                             const int32_t* ranks, double* predicted_mean, double* spread_mean,
+                                             double* below, double* total_order) {
+  return pool_simulated_placebo(s, true, scale, shift, num_groups, offsets, members, weights, max_origins,
+                                origins, horizon, link, init, out, seen, counted, num_ranks, ranks,
+                                predicted_mean, spread_mean, below, total_order, 0);
+}
+
+int ci_test_session_pool_simulated_placebo(ci_session* s, int32_t blocks, const double* scale, const double* shift,
+                                           int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                           const double* weights, int32_t max_origins, const int32_t* origins,
+                                           const int32_t* horizon, int32_t link, const double* init, double* out,
+                                           const double* seen, const int32_t* counted, int32_t num_ranks,
+                                           const int32_t* ranks, double* predicted_mean, double* spread_mean,
+                                           double* below, double* total_order, int32_t chunk_entries) {
+  if (!s) return fail("NULL argument");
+  if (chunk_entries < 1)
+    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", s->pb.num_series, chunk_entries);
+  return pool_simulated_placebo(s, blocks != 0, scale, shift, num_groups, offsets, members, weights, max_origins,
+                                origins, horizon, link, init, out, seen, counted, num_ranks, ranks,
+                                predicted_mean, spread_mean, below, total_order, chunk_entries);
 }
 
 int ci_summarize_draws(int32_t device, int32_t num_draws, int32_t T, const float* trajectories,
