@@ -269,6 +269,33 @@ def _check(rc: int):
     raise NativeError(load().ci_last_error().decode("utf-8", "replace"))
 
 
+def _symbol(lib, name: str):
+  """The entry point `name` of the loaded library."""
+  fn = getattr(lib, name, None)
+  if fn is None:
+    raise NativeError(f"the loaded library has no {name}: rebuild it")
+  return fn
+
+
+def _per_series(name: str, value, B: int, dtype=np.float64) -> np.ndarray:
+  """`value`, a scalar or one entry per series, as a contiguous [B] array of `dtype`."""
+  a = np.asarray(value)
+  if a.shape not in ((), (B,)):
+    raise ValueError(f"`{name}` must be a scalar or have one entry per series ({B}), got shape {a.shape}")
+  return np.ascontiguousarray(np.broadcast_to(a, (B,)), dtype=dtype)
+
+
+def _origin_plan(origins, horizon, B: int):
+  """(origins [B, O] int32, horizon [B] int32) of `Session.summarize_placebo` and `simulate_placebo`:
+  origins [B, O], or [O] for one series; horizon a scalar or [B]."""
+  org = np.asarray(origins)
+  if org.ndim == 1 and B == 1:
+    org = org[None]
+  if org.ndim != 2 or org.shape[0] != B:
+    raise ValueError(f"`origins` must be [{B}, O], got shape {org.shape}")
+  return np.ascontiguousarray(org, dtype=np.int32), _per_series("horizon", horizon, B, np.int32)
+
+
 def series_stream_key(seed, series_id: int):
   """(k0, k1): the Philox key of series `series_id` of a batch fitted with `seed` -- a
   single-series fit (device or oracle) with seed = this key reproduces that series' draws."""
@@ -845,9 +872,7 @@ def summarize_draw_paths(draws, scale, shift, observed, first, count, ranks, wan
   the call's device memory in place of the library's (ci_test_summarize_draw_paths_f64); the result
   then has "num_chunks" too."""
   name = "ci_summarize_draw_paths_f64" if max_bytes is None else "ci_test_summarize_draw_paths_f64"
-  fn = getattr(load(), name, None)
-  if fn is None:
-    raise NativeError(f"the loaded library has no {name}: rebuild it")
+  fn = _symbol(load(), name)
   dr = np.ascontiguousarray(draws, dtype=np.float64)
   if dr.ndim != 3:
     raise ValueError(f"`draws` must be [G, N, T], got shape {dr.shape}")
@@ -1055,18 +1080,13 @@ class Session:
     * scale + shift) (`link_values_host`) draw by draw and keep their definitions on top of it;
     `summarize_components`, `summarize_predictions`, `summarize_placebo` and `pool_placebo` describe
     the model and ignore it."""
-    fn = getattr(self._lib, "ci_session_set_link", None)
-    if fn is None:
-      raise NativeError("the loaded library has no ci_session_set_link: rebuild it")
-    _check(fn(self._h, int(link)))
+    _check(_symbol(self._lib, "ci_session_set_link")(self._h, int(link)))
 
   def value_mean(self, scale, shift) -> np.ndarray:
     """The mean over the N pooled draws of value[b, n, t] under the session's link
     (ci_session_value_mean), [B, T] float64 with the series axis kept; scale, shift: scalars or [B].
     Under a link the sampler's `posterior_means` mapped through (scale, shift) is not this mean."""
-    fn = getattr(self._lib, "ci_session_value_mean", None)
-    if fn is None:
-      raise NativeError("the loaded library has no ci_session_value_mean: rebuild it")
+    fn = _symbol(self._lib, "ci_session_value_mean")
     B, T = self.pb.num_series, self.pb.T
     sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (B,)))
     sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.float64), (B,)))
@@ -1115,12 +1135,7 @@ class Session:
     rk = np.ascontiguousarray(ranks, dtype=np.int32).reshape(-1)
     if not 1 <= rk.size <= MAX_SUMMARY_RANKS:
       raise ValueError(f"`ranks` must hold 1 to {MAX_SUMMARY_RANKS} order statistics, got {rk.size}")
-    sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
-    for name, a in (("scale", sc), ("shift", sh)):
-      if a.shape not in ((), (B,)):
-        raise ValueError(f"`{name}` must be a scalar or have one entry per series ({B}), got shape {a.shape}")
-    sc = np.ascontiguousarray(np.broadcast_to(sc, (B,)))
-    sh = np.ascontiguousarray(np.broadcast_to(sh, (B,)))
+    sc, sh = _per_series("scale", scale, B), _per_series("shift", shift, B)
     R = rk.size
     shapes = dict(trend_mean=(B, T), trend_order=(B, R, T))
     if K > 0:
@@ -1148,18 +1163,11 @@ class Session:
     that keep the series axis: forecast_mean [B,T], forecast_order [B,R,T], variance_mean [B,T],
     pit_mean [B,T] (0 at the masked steps), loglik [B,N].  `want`: the names to compute (default:
     all); the others are skipped on the device too."""
-    fn = getattr(self._lib, _entry, None)
-    if fn is None:
-      raise NativeError(f"the loaded library has no {_entry}: rebuild it")
+    fn = _symbol(self._lib, _entry)
     pb = self.pb
     B, T, N = pb.num_series, pb.T, pb.num_chains * pb.num_results
     rk = np.ascontiguousarray(ranks, dtype=np.int32).reshape(-1)
-    sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
-    for name, a in (("scale", sc), ("shift", sh)):
-      if a.shape not in ((), (B,)):
-        raise ValueError(f"`{name}` must be a scalar or have one entry per series ({B}), got shape {a.shape}")
-    sc = np.ascontiguousarray(np.broadcast_to(sc, (B,)))
-    sh = np.ascontiguousarray(np.broadcast_to(sh, (B,)))
+    sc, sh = _per_series("scale", scale, B), _per_series("shift", shift, B)
     shapes = dict(forecast_mean=(B, T), forecast_order=(B, rk.size, T), variance_mean=(B, T),
                   pit_mean=(B, T), loglik=(B, N))
     if want is not None:
@@ -1189,26 +1197,10 @@ class Session:
     row; horizon: scalar or [B].  Returns float64 arrays [B, O]: predicted_mean, spread_mean,
     pit_mean (0 in the unused slots and where the window counts no observation).  `want`: the names
     to compute (default: all); the others are skipped on the device too."""
-    fn = getattr(self._lib, _entry, None)
-    if fn is None:
-      raise NativeError(f"the loaded library has no {_entry}: rebuild it")
+    fn = _symbol(self._lib, _entry)
     B = self.pb.num_series
-    org = np.asarray(origins)
-    if org.ndim == 1 and B == 1:
-      org = org[None]
-    if org.ndim != 2 or org.shape[0] != B:
-      raise ValueError(f"`origins` must be [{B}, O], got shape {org.shape}")
-    org = np.ascontiguousarray(org, dtype=np.int32)
-    hz = np.asarray(horizon)
-    if hz.shape not in ((), (B,)):
-      raise ValueError(f"`horizon` must be a scalar or have one entry per series ({B}), got shape {hz.shape}")
-    hz = np.ascontiguousarray(np.broadcast_to(hz, (B,)), dtype=np.int32)
-    sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
-    for name, a in (("scale", sc), ("shift", sh)):
-      if a.shape not in ((), (B,)):
-        raise ValueError(f"`{name}` must be a scalar or have one entry per series ({B}), got shape {a.shape}")
-    sc = np.ascontiguousarray(np.broadcast_to(sc, (B,)))
-    sh = np.ascontiguousarray(np.broadcast_to(sh, (B,)))
+    org, hz = _origin_plan(origins, horizon, B)
+    sc, sh = _per_series("scale", scale, B), _per_series("shift", shift, B)
     names = PLACEBO_OUTPUTS
     if want is not None:
       unknown = [k for k in want if k not in PLACEBO_OUTPUTS]
@@ -1245,28 +1237,12 @@ class Session:
       name = "ci_test_session_simulate_placebo"
     else:
       name = "ci_session_simulate_placebo_blocks" if blocks else "ci_session_simulate_placebo"
-    fn = getattr(self._lib, name, None)
-    if fn is None:
-      raise NativeError(f"the loaded library has no {name}: rebuild it")
+    fn = _symbol(self._lib, name)
     pb = self.pb
     B, N = pb.num_series, pb.num_chains * pb.num_results
-    org = np.asarray(origins)
-    if org.ndim == 1 and B == 1:
-      org = org[None]
-    if org.ndim != 2 or org.shape[0] != B:
-      raise ValueError(f"`origins` must be [{B}, O], got shape {org.shape}")
-    org = np.ascontiguousarray(org, dtype=np.int32)
+    org, hz = _origin_plan(origins, horizon, B)
     O = int(org.shape[1])
-    hz = np.asarray(horizon)
-    if hz.shape not in ((), (B,)):
-      raise ValueError(f"`horizon` must be a scalar or have one entry per series ({B}), got shape {hz.shape}")
-    hz = np.ascontiguousarray(np.broadcast_to(hz, (B,)), dtype=np.int32)
-    sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
-    for what, a in (("scale", sc), ("shift", sh)):
-      if a.shape not in ((), (B,)):
-        raise ValueError(f"`{what}` must be a scalar or have one entry per series ({B}), got shape {a.shape}")
-    sc = np.ascontiguousarray(np.broadcast_to(sc, (B,)))
-    sh = np.ascontiguousarray(np.broadcast_to(sh, (B,)))
+    sc, sh = _per_series("scale", scale, B), _per_series("shift", shift, B)
     rk = np.ascontiguousarray(ranks, dtype=np.int32).reshape(-1)
     if seen is not None:
       seen = np.asarray(seen, np.float64)
@@ -1311,9 +1287,7 @@ class Session:
     point effects with the unobserved steps skipped; left out unless want_draws) and per_draw_order
     [B, W, 2, R]; the series axis is kept.  `window_totals_host` is the same loop on the host; a
     window equal to the post-period gives `summarize`'s per_draw and per_draw_order bit for bit."""
-    fn = getattr(self._lib, "ci_session_summarize_windows", None)
-    if fn is None:
-      raise NativeError("the loaded library has no ci_session_summarize_windows: rebuild it")
+    fn = _symbol(self._lib, "ci_session_summarize_windows")
     pb = self.pb
     return _windows_call(fn, self._h, pb.num_series, pb.num_chains * pb.num_results, pb.T, scale, shift,
                          observed, first, count, ranks, want_draws)
@@ -1329,9 +1303,7 @@ class Session:
     max_bytes (tests): the limit of the call's device memory in place of the library's
     (ci_test_session_summarize_paths); the result then has "num_chunks" too."""
     name = "ci_session_summarize_paths" if max_bytes is None else "ci_test_session_summarize_paths"
-    fn = getattr(self._lib, name, None)
-    if fn is None:
-      raise NativeError(f"the loaded library has no {name}: rebuild it")
+    fn = _symbol(self._lib, name)
     pb, chunks = self.pb, C.c_int32(0)
     out = _paths_call(fn, self._h, pb.num_series, pb.num_chains * pb.num_results, pb.T, scale, shift,
                       observed, first, count, ranks, want,
@@ -1361,9 +1333,7 @@ class Session:
     float64, one rounding per operation (`pool_event_host` is the same loop in numpy); the columns
     from a group's width to out_stride (default: the widest group) are 0.0.  init: [G, N, out_stride]
     float64 or None.  Returns [G, N, out_stride] float64."""
-    fn = getattr(self._lib, "ci_session_pool_event_trajectories", None)
-    if fn is None:
-      raise NativeError("the loaded library has no ci_session_pool_event_trajectories: rebuild it")
+    fn = _symbol(self._lib, "ci_session_pool_event_trajectories")
     pb = self.pb
     return _pool_call(fn, self._h, pb.num_series, pb.num_chains * pb.num_results, pb.T, scale, shift,
                       groups, init, True, out_stride)
@@ -1372,12 +1342,7 @@ class Session:
     """(scale [B], shift [B], offsets, members, weights, origins [K, O] int32, horizon [G] int32): the
     arguments of `pool_placebo` and `pool_simulated_placebo` as the C entries take them."""
     B = self.pb.num_series
-    sc, sh = np.asarray(scale, np.float64), np.asarray(shift, np.float64)
-    for name, a in (("scale", sc), ("shift", sh)):
-      if a.shape not in ((), (B,)):
-        raise ValueError(f"`{name}` must be a scalar or have one entry per series ({B}), got shape {a.shape}")
-    sc = np.ascontiguousarray(np.broadcast_to(sc, (B,)))
-    sh = np.ascontiguousarray(np.broadcast_to(sh, (B,)))
+    sc, sh = _per_series("scale", scale, B), _per_series("shift", shift, B)
     offsets, members, weights = _entry_csr(groups, B)
     G = offsets.size - 1
     if isinstance(origins, np.ndarray) or not (len(origins) and hasattr(origins[0], "items")):
@@ -1417,9 +1382,7 @@ class Session:
     data scale, or None.  Returns acc [G, O, 2, N] (S, then U) and, with `seen`, predicted_mean,
     spread_mean, pit_mean [G, O] (`finish_placebo_host`).  Given every member's draw the pooled sum
     is N(S, U) IF the members are independent of each other: the assumption this check tests."""
-    fn = getattr(self._lib, _entry, None)
-    if fn is None:
-      raise NativeError(f"the loaded library has no {_entry}: rebuild it")
+    fn = _symbol(self._lib, _entry)
     sc, sh, offsets, members, weights, org, hz = self._pool_placebo_tables(scale, shift, groups, origins, horizon)
     G, O, N = offsets.size - 1, int(org.shape[1]), self.pb.num_chains * self.pb.num_results
     if init is not None:
@@ -1471,9 +1434,7 @@ class Session:
       name = "ci_test_session_pool_simulated_placebo"
     else:
       name = "ci_session_pool_simulated_placebo_blocks" if blocks else "ci_session_pool_simulated_placebo"
-    fn = getattr(self._lib, name, None)
-    if fn is None:
-      raise NativeError(f"the loaded library has no {name}: rebuild it")
+    fn = _symbol(self._lib, name)
     sc, sh, offsets, members, weights, org, hz = self._pool_placebo_tables(scale, shift, groups, origins, horizon)
     G, O, N = offsets.size - 1, int(org.shape[1]), self.pb.num_chains * self.pb.num_results
     if init is not None:
@@ -1747,9 +1708,7 @@ class BatchLogLikSession(LogLikSession):
                         want_draws=True) -> Dict[str, np.ndarray]:
     """`Session.summarize_windows` of the fit's resident predictive trajectories
     (ci_ll_session_summarize_windows): per_draw [B, W, 2, N], per_draw_order [B, W, 2, R], N = C x S."""
-    fn = getattr(self._lib, "ci_ll_session_summarize_windows", None)
-    if fn is None:
-      raise NativeError("the loaded library has no ci_ll_session_summarize_windows: rebuild it")
+    fn = _symbol(self._lib, "ci_ll_session_summarize_windows")
     Cn, S = self._hmc_shape
     return _windows_call(fn, self._h, self.B, Cn * S, self.T, scale, shift, observed, first, count,
                          ranks, want_draws)
@@ -1758,9 +1717,7 @@ class BatchLogLikSession(LogLikSession):
                       want=PATH_OUTPUTS) -> Dict[str, np.ndarray]:
     """`Session.summarize_paths` of the fit's resident predictive trajectories
     (ci_ll_session_summarize_paths), N = C x S."""
-    fn = getattr(self._lib, "ci_ll_session_summarize_paths", None)
-    if fn is None:
-      raise NativeError("the loaded library has no ci_ll_session_summarize_paths: rebuild it")
+    fn = _symbol(self._lib, "ci_ll_session_summarize_paths")
     Cn, S = getattr(self, "_hmc_shape", (0, 0))           # (before a run: the entry refuses the call)
     return _paths_call(fn, self._h, self.B, Cn * S, self.T, scale, shift, observed, first, count, ranks,
                        want)

@@ -22,6 +22,20 @@
 
 namespace ci {
 
+// The launches (ci_components.hip) of the three kernels below: block k of K of `in` for B series
+// (scales, shifts == nullptr: none), their regression terms, the row statistics of M [rows, N].
+hipError_t comp_launch_gather(hipStream_t stream, int B, int N, int T, int K, int k, const float* in,
+                              const double* scales, const double* shifts, double* out);
+hipError_t comp_launch_regression(hipStream_t stream, int B, int N, int T, int P, const float* Xt,
+                                  const float* w, const int* series_T, const double* scales,
+                                  double* out);
+hipError_t comp_launch_row_stats(hipStream_t stream, size_t rows, int N, const double* M,
+                                 double* mean, int* nonzero);
+
+// Two of the kernels are no templates: a unit that includes them emits them.  The host units
+// (ci_session.h) take the declarations above alone.
+#ifndef CI_SEASONAL_DECL_ONLY
+
 // [N, T, K] float32 (one series: draws x steps x interleaved blocks) -> [T, N] float64 of block k.
 // K = 1 is the plain transpose (level; the weights with T = P).  A draw's 64 steps of all K blocks
 // are 64 K contiguous floats: the lanes sweep them in order (every cache line is used whole) and
@@ -147,5 +161,7 @@ __global__ __launch_bounds__(256) void comp_row_stats_kernel(size_t rows, int N,
     if (nonzero) nonzero[row] = c;
   }
 }
+
+#endif  // CI_SEASONAL_DECL_ONLY
 
 }  // namespace ci

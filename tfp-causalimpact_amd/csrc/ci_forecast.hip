@@ -1,0 +1,724 @@
+// ci_forecast.hip -- the Kalman-filter entries of a finished session behind the C-ABI:
+// ci_session_summarize_predictions[_blocks] (kernels: ci_predict.h, ci_predict_blocks.h),
+// ci_session_summarize_placebo[_blocks], ci_session_simulate_placebo[_blocks],
+// ci_session_pool_placebo[_blocks], ci_session_pool_simulated_placebo[_blocks] (kernels: ci_placebo.h,
+// ci_placebo_blocks.h) and their ci_test_ entries.  A host unit: it instantiates no kernel -- the
+// filters are launched through their units' launch functions, the order statistics through
+// launch_select of ci_summary.hip (ci_summary_host.h).
+//
+// Every routine has the same shape: NULL pointers, the session (pred_check_session), the routine's own
+// arguments, all before the first device call; then forecast_call, the set-up they share; then the
+// routine's own tables, its filter passes through the summary's scratch, and the downloads.
+#include <vector>
+
+#include "ci_session.h"
+#include "ci_components.h"
+#include "ci_placebo.h"
+#include "ci_placebo_blocks.h"
+#include "ci_predict.h"
+#include "ci_predict_blocks.h"
+#include "ci_summary_host.h"
+
+// What an entry asks of a session, and a finished run.  `entry`: its public name without _blocks.
+// Without `blocks`: a trend with at most one block of 2 to 7 seasons.  With it: not ragged, and a
+// state of at most 64 components.
+static int pred_check_session(const ci_session* s, bool blocks, const char* entry) {
+  const ci_problem& pb = s->pb;
+  const std::string name = std::string(entry) + (blocks ? "_blocks" : "");
+  const char* who = name.c_str();
+  std::string list;
+  for (int k = 0; k < pb.num_blocks; ++k) list += (k ? ", " : "") + std::to_string(pb.num_seasons[k]);
+  if (!blocks) {
+    if (pb.num_blocks > 1 || (pb.num_blocks == 1 && (pb.num_seasons[0] < 2 || pb.num_seasons[0] > 7)))
+      return fail("%s takes a trend with at most one block of 2 to 7 seasons, "
+                  "this session has the blocks (%s)", who, list.c_str());
+  } else {
+    if (s->ragged)
+      return fail("%s takes no ragged session: their models (one block of 2 to 7 seasons at most) "
+                  "belong to the entry without _blocks, %s", who, entry);
+    int d = 1 + (pb.has_slope ? 1 : 0);
+    for (int k = 0; k < pb.num_blocks; ++k) d += pb.num_seasons[k] - 1;
+    if (d > ci::PB_MAX_STATE)
+      return fail("%s takes a state of at most %d components, this session has %d with the blocks (%s)",
+                  who, ci::PB_MAX_STATE, d, list.c_str());
+  }
+  if (!s->ran) return fail("%s needs a finished ci_session_run", who);
+  return 0;
+}
+
+// The block list of a session as the block-model filters read it.
+static ci::BlockModel pred_block_model(const ci_problem& pb) {
+  ci::BlockModel m = {};
+  m.has_slope = pb.has_slope ? 1 : 0;
+  m.K = pb.num_blocks;
+  m.d = 1 + m.has_slope;
+  m.zmask = 1ull;
+  for (int k = 0; k < m.K; ++k) {
+    m.off[k] = m.d;
+    m.ns[k] = pb.num_seasons[k];
+    m.zmask |= 1ull << m.d;
+    m.d += pb.num_seasons[k] - 1;
+  }
+  return m;
+}
+
+// On the device, once per session: per series the initial moments of its ci_series_params [B, 4],
+// then [B] times the 1.0 the regression term is scaled by.
+static int pred_init_upload(ci_session* s) {
+  if (s->pred_init.p) return 0;
+  const int B = s->pb.num_series;
+  std::vector<double> init((size_t)5 * B, 1.0);
+  for (int b = 0; b < B; ++b) {
+    const ci_series_params& q = s->params[b];
+    init[4 * b + 0] = q.init_level_loc;
+    init[4 * b + 1] = q.init_level_scale * q.init_level_scale;
+    init[4 * b + 2] = q.init_slope_scale * q.init_slope_scale;
+    init[4 * b + 3] = q.init_seasonal_scale * q.init_seasonal_scale;
+  }
+  HIP_TRY(s->pred_init.alloc(init.size()));
+  HIP_TRY(hipMemcpy(s->pred_init.p, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
+static int check_link(int32_t link) {
+  if (link < 0 || link >= ci::NUM_LINKS)
+    return fail("link must be CI_LINK_IDENTITY, CI_LINK_LOG or CI_LINK_LOG1P (0 to %d), got %d", ci::NUM_LINKS - 1, link);
+  return 0;
+}
+
+// What the routines below share once their arguments are checked: the session's geometry (not kpb:
+// the inert block of a long trend-only series is no part of the model), its stream and scratch, and
+// the filter's inputs.  The routine copies `p` into the argument struct of whichever filter it
+// launches (PredArgs, PlaceboArgs::p, PlaceboSimArgs::q.p, or the _blocks structs with `m`).
+namespace {
+struct ForecastCall {
+  int B, T, N, has_slope, NS;      // NS: the seasons of the one-lane build's block (0: none)
+  hipStream_t stream;
+  SummScratch* w;                  // value: p.out; cum: p.reg; obs [B * T], then scale [B], shift [B]
+  ci::PredArgs p;                  // out = `value`, ll = nullptr
+  ci::BlockModel m;                // (blocks)
+};
+}  // namespace
+
+// The set-up of a call, the first device work of every routine: the device, the scratch and the
+// initial moments (both on first use), scale and shift next to `obs`, and -- `filters`: the call has
+// a row to filter -- the regression term of every draw and step in `cum`, once for all its passes.
+static int forecast_call(ForecastCall& c, ci_session* s, bool blocks, const double* scale, const double* shift,
+                         bool filters = true) {
+  const ci_problem& pb = s->pb;
+  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
+  HIP_TRY(hipSetDevice(pb.device));
+  SummScratch& w = s->summ;
+  if (summ_scratch_alloc(w, B, T, N)) return 1;
+  if (pred_init_upload(s)) return 1;
+  double* d_scale = w.obs.p + (size_t)B * T;
+  double* d_shift = d_scale + B;
+  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
+  if (P > 0 && filters)
+    HIP_TRY(ci::comp_launch_regression(s->stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
+                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
+  c.B = B; c.T = T; c.N = N; c.has_slope = pb.has_slope; c.NS = pb.num_blocks ? pb.num_seasons[0] : 0;
+  c.stream = s->stream;
+  c.w = &w;
+  ci::PredArgs& a = c.p;
+  a.N = N; a.T = T;
+  a.y = s->y.p; a.mask = s->mask.p; a.season_change = s->season_change.p; a.series_T = d_series_T;
+  a.obs = s->o_obs.p; a.lscale = s->o_lscale.p; a.sscale = s->o_sscale.p; a.drift = s->o_drift.p;
+  a.init = s->pred_init.p; a.scales = d_scale; a.shifts = d_shift;
+  a.reg = P > 0 ? w.cum.p : nullptr;
+  a.out = w.value.p; a.ll = nullptr;
+  c.m = blocks ? pred_block_model(pb) : ci::BlockModel{};
+  return 0;
+}
+
+// ci_session_summarize_predictions and, with `blocks`, ci_session_summarize_predictions_blocks: they
+// differ in the sessions they take and in the filter they launch, in nothing else.
+static int summarize_predictions(ci_session* s, bool blocks, const double* scale, const double* shift,
+                                 int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
+                                 double* forecast_order, double* variance_mean, double* pit_mean,
+                                 double* loglik) {
+  if (!s || !scale || !shift || !ranks) return fail("NULL argument");
+  if (pred_check_session(s, blocks, "ci_session_summarize_predictions")) return 1;
+  const int R = num_ranks;
+  if (check_ranks(R, ranks, s->pb.num_chains * s->pb.num_results)) return 1;
+  ForecastCall c;
+  if (forecast_call(c, s, blocks, scale, shift)) return 1;
+  const int B = c.B, T = c.T, N = c.N;
+  hipStream_t stream = c.stream;
+  SummScratch& w = *c.w;
+  HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
+  // One filter pass per requested matrix through `value`, its row means in `obs`, its order
+  // statistics in `order`, the per-draw log-likelihoods (with the first pass) in `draw`.
+  ci::PredBlocksArgs ab;
+  ab.p = c.p; ab.m = c.m;
+  bool ll_pending = loglik != nullptr;
+  auto pass = [&](int which, double* mean_dst, double* order_dst) -> int {
+    ab.p.ll = ll_pending ? w.draw.p : nullptr;
+    if (blocks) HIP_TRY(ci::predict_blocks_launch(stream, B, which, ab));
+    else HIP_TRY(ci::predict_launch(stream, B, c.has_slope, c.NS, which, ab.p));
+    if (mean_dst) HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * T, N, w.value.p, w.obs.p, nullptr));
+    if (order_dst)
+      HIP_TRY(launch_select(stream, N, T, B * T, R, w.ranks.p, w.value.p, nullptr, w.order.p, nullptr));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (mean_dst)
+      HIP_TRY(hipMemcpy(mean_dst, w.obs.p, (size_t)B * T * sizeof(double), hipMemcpyDeviceToHost));
+    if (order_dst)
+      HIP_TRY(hipMemcpy(order_dst, w.order.p, (size_t)B * R * T * sizeof(double), hipMemcpyDeviceToHost));
+    if (ll_pending)
+      HIP_TRY(hipMemcpy(loglik, w.draw.p, (size_t)B * N * sizeof(double), hipMemcpyDeviceToHost));
+    ll_pending = false;
+    return 0;
+  };
+  if ((forecast_mean || forecast_order) && pass(ci::PRED_FORECAST, forecast_mean, forecast_order)) return 1;
+  if (variance_mean && pass(ci::PRED_VARIANCE, variance_mean, nullptr)) return 1;
+  if ((pit_mean || ll_pending) && pass(ci::PRED_PIT, pit_mean, nullptr)) return 1;
+  return 0;
+}
+
+// The origin table of ci_session_summarize_placebo and ci_session_simulate_placebo: max_origins in
+// [1, T], horizon >= 1, every row ascending with -1 only at the end, o + H_b <= T_b.
+static int check_placebo_plan(const ci_session* s, int O, const int32_t* origins, const int32_t* horizon) {
+  const int B = s->pb.num_series, T = s->pb.T;
+  if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
+  for (int b = 0; b < B; ++b) {
+    const int Tb = s->ragged ? s->lengths[b] : T, Hb = horizon[b];
+    if (Hb < 1) return fail("horizon[%d] must be at least 1, got %d", b, Hb);
+    const int32_t* row = origins + (size_t)b * O;
+    bool ended = false;
+    for (int i = 0; i < O; ++i) {
+      const int o = row[i];
+      if (o == -1) { ended = true; continue; }
+      if (o < 0) return fail("origins[%d, %d] must be a step or -1 (unused), got %d", b, i, o);
+      if (ended || (i > 0 && o <= row[i - 1]))
+        return fail("origins[%d] must be strictly ascending with the unused slots (-1) at the end "
+                    "(slot %d holds %d)", b, i, o);
+      if ((long long)o + Hb > Tb)
+        return fail("origins[%d, %d] = %d with horizon %d reaches beyond the series' %d steps", b, i, o, Hb, Tb);
+    }
+  }
+  return 0;
+}
+
+// ci_session_summarize_placebo and, with `blocks`, ci_session_summarize_placebo_blocks, likewise.
+static int summarize_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
+                             int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                             double* predicted_mean, double* spread_mean, double* pit_mean) {
+  if (!s || !scale || !shift || !origins || !horizon) return fail("NULL argument");
+  if (pred_check_session(s, blocks, "ci_session_summarize_placebo")) return 1;
+  const int O = max_origins;
+  if (check_placebo_plan(s, O, origins, horizon)) return 1;
+  ForecastCall c;
+  if (forecast_call(c, s, blocks, scale, shift)) return 1;
+  const int B = c.B, N = c.N;
+  hipStream_t stream = c.stream;
+  SummScratch& w = *c.w;
+  DevBuf<int> d_plan;                    // origins [B, O], then horizon [B]
+  HIP_TRY(d_plan.alloc((size_t)B * O + B));
+  HIP_TRY(hipMemcpyAsync(d_plan.p, origins, (size_t)B * O * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_plan.p + (size_t)B * O, horizon, B * sizeof(int), hipMemcpyHostToDevice, stream));
+  // One pass per requested matrix [B * O, N] through `value` (O <= T: it fits), its row means in `obs`.
+  ci::PlaceboBlocksArgs ab;
+  ci::PlaceboArgs& a = ab.q;
+  a.p = c.p; ab.m = c.m;
+  a.O = O; a.origins = d_plan.p; a.horizon = d_plan.p + (size_t)B * O;
+  auto pass = [&](int which, double* mean_dst) -> int {
+    if (blocks) HIP_TRY(ci::placebo_blocks_launch(stream, B, which, ab));
+    else HIP_TRY(ci::placebo_launch(stream, B, c.has_slope, c.NS, which, a));
+    HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * O, N, w.value.p, w.obs.p, nullptr));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy(mean_dst, w.obs.p, (size_t)B * O * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+  };
+  if (predicted_mean && pass(ci::PLACEBO_SUM, predicted_mean)) return 1;
+  if (spread_mean && pass(ci::PLACEBO_SPREAD, spread_mean)) return 1;
+  if (pit_mean && pass(ci::PLACEBO_PIT, pit_mean)) return 1;
+  HIP_TRY(hipStreamSynchronize(stream));   // (the uploads of a call that asks for nothing)
+  return 0;
+}
+
+// The Philox key every series' fit ran on (ci_series_stream_key of its id, or the seed itself), [B, 2]:
+// what the simulated routines draw their normals from.  `keys` is the caller's: it outlives the copy.
+static int stream_keys_upload(const ci_session* s, std::vector<uint32_t>& keys, DevBuf<uint32_t>& d_keys) {
+  const ci_problem& pb = s->pb;
+  const int B = pb.num_series;
+  keys.resize((size_t)2 * B);
+  const int shared = (pb.flags & CI_FLAG_SHARED_SERIES_STREAMS) ? -1 : 0;
+  for (int b = 0; b < B; ++b) {
+    const int sid = s->ids.empty() ? pb.series_offset + b : s->ids[b];
+    keys[2 * b] = ci::stream_key0(pb.seed[0], shared, sid);
+    keys[2 * b + 1] = ci::stream_key1(pb.seed[1], shared, sid);
+  }
+  HIP_TRY(d_keys.alloc(keys.size()));
+  HIP_TRY(hipMemcpyAsync(d_keys.p, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+  return 0;
+}
+
+// The statistics of `rows` rows of simulated totals in `value`, O rows per series or group; every
+// destination is on the device and may be NULL (not asked for): the row means, the order statistics
+// [rows / O, R, O], the rows' download when `totals` (host) is wanted, the count below `seen`, the
+// rewrite to (x - seen)^2 in place and its row means.  `value` holds the squares afterwards.
+static int sim_total_stats(hipStream_t stream, SummScratch& w, size_t rows, int N, int O, int R,
+                           const double* d_seen, const int* d_counted, double* d_mean, double* d_order,
+                           double* d_below, double* d_spread, double* totals = nullptr) {
+  if (d_mean) HIP_TRY(ci::comp_launch_row_stats(stream, rows, N, w.value.p, d_mean, nullptr));
+  if (d_order)
+    HIP_TRY(launch_select(stream, N, O, (int)rows, R, w.ranks.p, w.value.p, nullptr, d_order, nullptr));
+  if (totals) {
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy(totals, w.value.p, rows * N * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  if (d_spread || d_below) {
+    HIP_TRY(ci::placebo_sim_seen_launch(stream, rows, N, w.value.p, d_seen, d_counted, d_below, d_spread != nullptr));
+    if (d_spread) HIP_TRY(ci::comp_launch_row_stats(stream, rows, N, w.value.p, d_spread, nullptr));
+  }
+  return 0;
+}
+
+// ci_session_simulate_placebo and, with `blocks`, ci_session_simulate_placebo_blocks: the filter runs
+// ONCE per chunk of series whose rows [nb * O, N] fit the scratch -- simulate into `value`, then
+// sim_total_stats.  TOTAL is a function of (b, slot, n) alone and every statistic one of its row, so
+// nothing depends on where the chunks are cut.  max_rows (tests; 0: the scratch's B * T rows, which
+// hold every call's B * O): the rows of a chunk; num_chunks (may be NULL): how many it took.
+static int simulate_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
+                            int32_t max_origins, const int32_t* origins, const int32_t* horizon, int32_t link,
+                            const double* seen, int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
+                            double* spread_mean, double* below, double* total_order, double* totals,
+                            int64_t max_rows, int32_t* num_chunks) {
+  if (!s || !scale || !shift || !origins || !horizon || !ranks) return fail("NULL argument");
+  if (pred_check_session(s, blocks, "ci_session_simulate_placebo")) return 1;
+  const ci_problem& pb = s->pb;
+  const int B = pb.num_series, T = pb.T, N = pb.num_chains * pb.num_results;
+  const int O = max_origins, R = num_ranks;
+  if (check_placebo_plan(s, O, origins, horizon)) return 1;
+  if (check_link(link)) return 1;
+  if (check_ranks(R, ranks, N)) return 1;
+  if (!seen && (spread_mean || below)) return fail("spread_mean and below need `seen`, which is NULL");
+  const size_t BO = (size_t)B * O;
+  if (max_rows < 0 || (max_rows > 0 && max_rows < O))
+    return fail("max_rows must hold the %d rows of one series, got %lld", O, (long long)max_rows);
+  const size_t cap = max_rows > 0 && (size_t)max_rows < (size_t)B * T ? (size_t)max_rows : (size_t)B * T;
+  const int nb_max = (int)(cap / O);     // (O <= T: at least one series)
+  if (num_chunks) *num_chunks = (B + nb_max - 1) / nb_max;
+  ForecastCall c;
+  if (forecast_call(c, s, blocks, scale, shift)) return 1;
+  hipStream_t stream = c.stream;
+  SummScratch& w = *c.w;
+  std::vector<uint32_t> keys;
+  DevBuf<int> d_plan;                    // origins [B, O], horizon [B], counted [B, O]
+  DevBuf<uint32_t> d_keys;               // [B, 2]
+  DevBuf<double> d_stat;                 // seen, mean, spread, below: [B, O] each
+  HIP_TRY(d_plan.alloc(2 * BO + B));
+  HIP_TRY(d_stat.alloc(4 * BO));
+  int* d_counted = d_plan.p + BO + B;
+  double *d_seen = d_stat.p, *d_mean = d_stat.p + BO, *d_spread = d_stat.p + 2 * BO, *d_below = d_stat.p + 3 * BO;
+  HIP_TRY(hipMemcpyAsync(d_plan.p, origins, BO * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_plan.p + BO, horizon, B * sizeof(int), hipMemcpyHostToDevice, stream));
+  if (stream_keys_upload(s, keys, d_keys)) return 1;
+  if (seen) HIP_TRY(hipMemcpyAsync(d_seen, seen, BO * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
+  ci::PlaceboBlocksSimArgs ab;
+  ci::PlaceboSimArgs& a = ab.s;
+  a.q.p = c.p; ab.m = c.m;
+  a.q.O = O; a.q.origins = d_plan.p; a.q.horizon = d_plan.p + BO;
+  a.kept = pb.num_results; a.chain_offset = (uint32_t)pb.chain_offset; a.keys = d_keys.p;
+  for (int b0 = 0; b0 < B; b0 += nb_max) {
+    const int nb = B - b0 < nb_max ? B - b0 : nb_max;
+    const size_t rows = (size_t)nb * O, off = (size_t)b0 * O;
+    a.b0 = b0;
+    a.counted = d_counted + off;
+    if (blocks) HIP_TRY(ci::placebo_blocks_sim_launch(stream, nb, link, ab));
+    else HIP_TRY(ci::placebo_sim_launch(stream, nb, c.has_slope, c.NS, link, a));
+    if (sim_total_stats(stream, w, rows, N, O, R, d_seen + off, d_counted + off,
+                        predicted_mean ? d_mean + off : nullptr,
+                        total_order ? w.order.p + (size_t)b0 * R * O : nullptr, below ? d_below + off : nullptr,
+                        spread_mean ? d_spread + off : nullptr, totals ? totals + off * N : nullptr))
+      return 1;
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (predicted_mean) HIP_TRY(hipMemcpy(predicted_mean, d_mean, BO * sizeof(double), hipMemcpyDeviceToHost));
+  if (spread_mean) HIP_TRY(hipMemcpy(spread_mean, d_spread, BO * sizeof(double), hipMemcpyDeviceToHost));
+  if (below) HIP_TRY(hipMemcpy(below, d_below, BO * sizeof(double), hipMemcpyDeviceToHost));
+  if (total_order)
+    HIP_TRY(hipMemcpy(total_order, w.order.p, BO * R * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The plan of a pooled placebo call (ci_session_pool_placebo, ci_session_pool_simulated_placebo):
+// one horizon >= 1 per group, every entry's origin row ascending with -1 only at the end and
+// o + H_g <= T_b of its member; entry_horizon [K] is the group's horizon per entry.
+static int check_pool_plan(const ci_session* s, int G, const int32_t* offsets, const int32_t* members, int O,
+                           const int32_t* origins, const int32_t* horizon, std::vector<int>& entry_horizon) {
+  const int T = s->pb.T, K = offsets[G];
+  entry_horizon.assign((size_t)(K ? K : 1), 0);
+  for (int g = 0; g < G; ++g) {
+    const int Hg = horizon[g];
+    if (Hg < 1) return fail("group %d: the horizon must be at least 1, got %d", g, Hg);
+    for (int k = offsets[g]; k < offsets[g + 1]; ++k) {
+      const int b = members[k], Tb = s->ragged ? s->lengths[b] : T;
+      const int32_t* row = origins + (size_t)k * O;
+      entry_horizon[k] = Hg;
+      bool ended = false;
+      for (int i = 0; i < O; ++i) {
+        const int o = row[i];
+        if (o == -1) { ended = true; continue; }
+        if (o < 0)
+          return fail("group %d, entry %d (member %d): slot %d must hold a step or -1 (unused), got %d", g, k, b, i, o);
+        if (ended || (i > 0 && o <= row[i - 1]))
+          return fail("group %d, entry %d (member %d): the origins must be strictly ascending with the unused "
+                      "slots (-1) at the end (slot %d holds %d)", g, k, b, i, o);
+        if ((long long)o + Hg > Tb)
+          return fail("group %d, entry %d (member %d): the origin %d of slot %d with horizon %d reaches beyond "
+                      "the series' %d steps", g, k, b, o, i, Hg, Tb);
+      }
+    }
+  }
+  return 0;
+}
+
+// The device copy of a pooled call's group table, the call's own: the K entries (an empty table
+// keeps one slot: Ka = 1) and the groups' accumulators [G, O, planes, N] holding `init` or zeros.
+// tail_ints, tail_doubles: room behind them for what the routine keeps per row besides.
+namespace {
+struct PoolTables {
+  DevBuf<int> ints;                // offsets [G + 1], members [Ka], horizon [Ka], origins [Ka, O], tail
+  DevBuf<double> doubles;          // acc, weights [Ka], tail
+  int *offsets, *members, *horizon, *origins, *tail_ints;
+  double *acc, *weights, *tail_doubles;
+  size_t acc_n;
+};
+}  // namespace
+
+static int pool_tables_upload(PoolTables& t, hipStream_t stream, int G, int O, int N, int planes,
+                              const int32_t* offsets, const int32_t* members, const double* weights,
+                              const int32_t* origins, const std::vector<int>& entry_horizon, const double* init,
+                              size_t tail_ints, size_t tail_doubles) {
+  const size_t K = (size_t)offsets[G], Ka = K ? K : 1;
+  t.acc_n = (size_t)G * O * planes * N;
+  HIP_TRY(t.ints.alloc((size_t)G + 1 + 2 * Ka + Ka * O + tail_ints));
+  HIP_TRY(t.doubles.alloc(t.acc_n + Ka + tail_doubles));
+  t.offsets = t.ints.p;
+  t.members = t.offsets + G + 1;
+  t.horizon = t.members + Ka;
+  t.origins = t.horizon + Ka;
+  t.tail_ints = t.origins + Ka * O;
+  t.acc = t.doubles.p;
+  t.weights = t.acc + t.acc_n;
+  t.tail_doubles = t.weights + Ka;
+  HIP_TRY(hipMemcpyAsync(t.offsets, offsets, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
+  if (K > 0) {
+    HIP_TRY(hipMemcpyAsync(t.members, members, K * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(t.horizon, entry_horizon.data(), K * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(t.origins, origins, K * O * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(t.weights, weights, K * sizeof(double), hipMemcpyHostToDevice, stream));
+  }
+  if (init)
+    HIP_TRY(hipMemcpyAsync(t.acc, init, t.acc_n * sizeof(double), hipMemcpyHostToDevice, stream));
+  else
+    HIP_TRY(hipMemsetAsync(t.acc, 0, t.acc_n * sizeof(double), stream));
+  return 0;
+}
+
+// The placebo forecasts of POOLED sums: per group, slot and draw the weighted sum S of the members'
+// forecasts and the sum U of their predictive variances (include/causalimpact_amd.h).  The entries
+// of the group table pass through `value` at most B at a time, a SUM pass and its accumulate, then a
+// VAR pass and its accumulate; the accumulators [G, O, 2, N] and the tables are the call's own.
+// With `blocks` ci_session_pool_placebo_blocks: the sessions and the filter of the block models, ONE
+// pass per chunk that stores SUM into `value` and VAR into a buffer of the call's own, then the same
+// two accumulates.  chunk_entries (tests; 0: B): the entries of a chunk, in [1, B].
+static int pool_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
+                        int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                        const double* weights, int32_t max_origins, const int32_t* origins,
+                        const int32_t* horizon, const double* init, double* out,
+                        const double* seen, double* predicted_mean, double* spread_mean,
+                        double* pit_mean, int32_t chunk_entries) {
+  if (!s || !scale || !shift || !offsets || !members || !weights || !origins || !horizon || !out)
+    return fail("NULL argument");
+  if (pred_check_session(s, blocks, "ci_session_pool_placebo")) return 1;
+  const int B = s->pb.num_series, T = s->pb.T, O = max_origins, G = num_groups;
+  if (chunk_entries < 0 || chunk_entries > B)
+    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", B, chunk_entries);
+  const int chunk = chunk_entries ? chunk_entries : B;
+  if (check_groups(B, G, offsets, members, weights)) return 1;
+  if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
+  if (!seen && (predicted_mean || spread_mean || pit_mean))
+    return fail("predicted_mean, spread_mean and pit_mean need `seen`, the pooled observed sums");
+  const int K = offsets[G];
+  std::vector<int> entry_horizon;
+  if (check_pool_plan(s, G, offsets, members, O, origins, horizon, entry_horizon)) return 1;
+  ForecastCall c;
+  if (forecast_call(c, s, blocks, scale, shift, K > 0)) return 1;
+  const int N = c.N;
+  hipStream_t stream = c.stream;
+  SummScratch& w = *c.w;
+  const size_t rows = (size_t)G * O;
+  PoolTables t;                          // tail: seen [G, O]
+  DevBuf<double> d_var;                  // (blocks) VAR of a chunk [chunk, O, N]
+  if (pool_tables_upload(t, stream, G, O, N, 2, offsets, members, weights, origins, entry_horizon, init, 0, rows))
+    return 1;
+  if (blocks && K > 0) HIP_TRY(d_var.alloc((size_t)(K < chunk ? K : chunk) * O * N));
+  double* d_seen = t.tail_doubles;
+  if (seen) HIP_TRY(hipMemcpyAsync(d_seen, seen, rows * sizeof(double), hipMemcpyHostToDevice, stream));
+  ci::PlaceboBlocksPoolArgs ab;
+  ci::PlaceboArgs& a = ab.q;
+  a.p = c.p; ab.m = c.m; ab.var = d_var.p;
+  a.O = O;
+  // at most B entries at a time: [B * O, N] with O <= T fits `value`
+  for (int c0 = 0; c0 < K; c0 += chunk) {
+    const int c1 = K - c0 < chunk ? K : c0 + chunk;
+    a.series_of = t.members + c0; a.origins = t.origins + (size_t)c0 * O; a.horizon = t.horizon + c0;
+    if (blocks) {
+      HIP_TRY(ci::placebo_blocks_pool_launch(stream, c1 - c0, ab));
+      HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, 0, c0, c1, t.offsets, t.weights, w.value.p, t.acc));
+      HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, 1, c0, c1, t.offsets, t.weights, d_var.p, t.acc));
+      continue;
+    }
+    for (int which = 0; which < 2; ++which) {
+      HIP_TRY(ci::placebo_launch(stream, c1 - c0, c.has_slope, c.NS, which ? ci::PLACEBO_VAR : ci::PLACEBO_SUM, a));
+      HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, which, c0, c1, t.offsets, t.weights, w.value.p, t.acc));
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(out, t.acc, t.acc_n * sizeof(double), hipMemcpyDeviceToHost, stream));
+  // the means over the draws, one matrix at a time and as many rows as `value` and `obs` hold
+  const size_t per_pass = (size_t)B * T;
+  auto finish = [&](int which, double* mean_dst) -> int {
+    for (size_t r0 = 0; r0 < rows; r0 += per_pass) {
+      const size_t nr = rows - r0 < per_pass ? rows - r0 : per_pass;
+      HIP_TRY(ci::placebo_finish_launch(stream, N, r0, nr, which, t.acc, d_seen, w.value.p));
+      HIP_TRY(ci::comp_launch_row_stats(stream, nr, N, w.value.p, w.obs.p, nullptr));
+      HIP_TRY(hipMemcpyAsync(mean_dst + r0, w.obs.p, nr * sizeof(double), hipMemcpyDeviceToHost, stream));
+    }
+    return 0;
+  };
+  if (predicted_mean && finish(ci::PLACEBO_SUM, predicted_mean)) return 1;
+  if (spread_mean && finish(ci::PLACEBO_SPREAD, spread_mean)) return 1;
+  if (pit_mean && finish(ci::PLACEBO_PIT, pit_mean)) return 1;
+  HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
+
+// The SIMULATED placebo forecasts of pooled sums (include/causalimpact_amd.h): the entries of the group
+// table pass through `value` at most `chunk` at a time -- ONE simulation pass (the entry-table build
+// of simulate_placebo's kernel; TOTAL is a function of (series, origin, slot, horizon, n) alone) and
+// its accumulate into POOL [G, O, N], the call's own.  `out` is downloaded, then sim_total_stats is
+// taken over the accumulators' rows, copied through `value` at most B * T rows at a time (whole
+// groups, so that the selection's [G, R, O] layout holds per chunk).  Nothing depends on where either
+// kind of chunk is cut.  chunk_entries (tests; 0: B): in [1, B].
+static int pool_simulated_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
+                                  int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                  const double* weights, int32_t max_origins, const int32_t* origins,
+                                  const int32_t* horizon, int32_t link, const double* init, double* out,
+                                  const double* seen, const int32_t* counted, int32_t num_ranks,
+                                  const int32_t* ranks, double* predicted_mean, double* spread_mean,
+                                  double* below, double* total_order, int32_t chunk_entries) {
+  if (!s || !scale || !shift || !offsets || !members || !weights || !origins || !horizon || !out || !ranks)
+    return fail("NULL argument");
+  if (pred_check_session(s, blocks, "ci_session_pool_simulated_placebo")) return 1;
+  const ci_problem& pb = s->pb;
+  const int B = pb.num_series, T = pb.T, N = pb.num_chains * pb.num_results;
+  const int O = max_origins, G = num_groups, R = num_ranks;
+  if (chunk_entries < 0 || chunk_entries > B)
+    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", B, chunk_entries);
+  const int chunk = chunk_entries ? chunk_entries : B;
+  if (check_groups(B, G, offsets, members, weights)) return 1;
+  if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
+  if (check_link(link)) return 1;
+  if (check_ranks(R, ranks, N)) return 1;
+  const bool stats = predicted_mean || spread_mean || below || total_order;
+  if (stats && (!seen || !counted))
+    return fail("predicted_mean, spread_mean, below and total_order need `seen` and `counted`, the pooled "
+                "observed totals and the member-steps they count");
+  const int K = offsets[G];
+  std::vector<int> entry_horizon;
+  if (check_pool_plan(s, G, offsets, members, O, origins, horizon, entry_horizon)) return 1;
+  ForecastCall c;
+  if (forecast_call(c, s, blocks, scale, shift, K > 0)) return 1;
+  hipStream_t stream = c.stream;
+  SummScratch& w = *c.w;
+  const size_t rows = (size_t)G * O;
+  const size_t chunk_rows = (size_t)(K < chunk ? (K ? K : 1) : chunk) * O;
+  std::vector<uint32_t> keys;
+  PoolTables t;                          // tails: cnt of a chunk's rows [chunk, O], counted [G, O];
+                                         // seen, mean, spread, below [G, O] each, order [G, R, O]
+  DevBuf<uint32_t> d_keys;               // [B, 2]
+  if (pool_tables_upload(t, stream, G, O, N, 1, offsets, members, weights, origins, entry_horizon, init,
+                         chunk_rows + rows, 4 * rows + rows * R))
+    return 1;
+  int* d_cnt = t.tail_ints;
+  int* d_counted = d_cnt + chunk_rows;
+  double* d_seen = t.tail_doubles;
+  double *d_mean = d_seen + rows, *d_spread = d_mean + rows, *d_below = d_spread + rows;
+  double* d_order = d_below + rows;
+  if (stats) {
+    HIP_TRY(hipMemcpyAsync(d_seen, seen, rows * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_counted, counted, rows * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
+  }
+  if (stream_keys_upload(s, keys, d_keys)) return 1;
+  ci::PlaceboBlocksSimArgs ab;
+  ci::PlaceboSimArgs& a = ab.s;
+  a.q.p = c.p; ab.m = c.m;
+  a.q.O = O;
+  a.b0 = 0; a.kept = pb.num_results; a.chain_offset = (uint32_t)pb.chain_offset; a.keys = d_keys.p;
+  a.counted = d_cnt;
+  // at most B entries at a time: [B * O, N] with O <= T fits `value`
+  for (int c0 = 0; c0 < K; c0 += chunk) {
+    const int c1 = K - c0 < chunk ? K : c0 + chunk;
+    a.q.series_of = t.members + c0; a.q.origins = t.origins + (size_t)c0 * O; a.q.horizon = t.horizon + c0;
+    if (blocks) HIP_TRY(ci::placebo_blocks_sim_entries_launch(stream, c1 - c0, link, ab));
+    else HIP_TRY(ci::placebo_sim_entries_launch(stream, c1 - c0, c.has_slope, c.NS, link, a));
+    HIP_TRY(ci::placebo_pool_totals_launch(stream, N, O, G, c0, c1, t.offsets, t.weights, w.value.p, t.acc));
+  }
+  HIP_TRY(hipMemcpyAsync(out, t.acc, t.acc_n * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (stats) {
+    // whole groups, as many as `value` holds: (B * T / O) * O rows, at least O
+    const size_t per_pass = ((size_t)B * T / O) * O;
+    for (size_t r0 = 0; r0 < rows; r0 += per_pass) {
+      const size_t nr = rows - r0 < per_pass ? rows - r0 : per_pass;
+      HIP_TRY(hipMemcpyAsync(w.value.p, t.acc + r0 * N, nr * N * sizeof(double), hipMemcpyDeviceToDevice, stream));
+      if (sim_total_stats(stream, w, nr, N, O, R, d_seen + r0, d_counted + r0, predicted_mean ? d_mean + r0 : nullptr,
+                          total_order ? d_order + r0 * R : nullptr, below ? d_below + r0 : nullptr,
+                          spread_mean ? d_spread + r0 : nullptr))
+        return 1;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (predicted_mean) HIP_TRY(hipMemcpy(predicted_mean, d_mean, rows * sizeof(double), hipMemcpyDeviceToHost));
+  if (spread_mean) HIP_TRY(hipMemcpy(spread_mean, d_spread, rows * sizeof(double), hipMemcpyDeviceToHost));
+  if (below) HIP_TRY(hipMemcpy(below, d_below, rows * sizeof(double), hipMemcpyDeviceToHost));
+  if (total_order) HIP_TRY(hipMemcpy(total_order, d_order, rows * R * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+extern "C" {
+
+int ci_session_summarize_predictions(ci_session* s, const double* scale, const double* shift,
+                                     int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
+                                     double* forecast_order, double* variance_mean, double* pit_mean,
+                                     double* loglik) {
+  return summarize_predictions(s, false, scale, shift, num_ranks, ranks, forecast_mean, forecast_order,
+                               variance_mean, pit_mean, loglik);
+}
+
+int ci_session_summarize_predictions_blocks(ci_session* s, const double* scale, const double* shift,
+                                            int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
+                                            double* forecast_order, double* variance_mean, double* pit_mean,
+                                            double* loglik) {
+  return summarize_predictions(s, true, scale, shift, num_ranks, ranks, forecast_mean, forecast_order,
+                               variance_mean, pit_mean, loglik);
+}
+
+int ci_session_summarize_placebo(ci_session* s, const double* scale, const double* shift,
+                                 int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                 double* predicted_mean, double* spread_mean, double* pit_mean) {
+  return summarize_placebo(s, false, scale, shift, max_origins, origins, horizon, predicted_mean, spread_mean,
+                           pit_mean);
+}
+
+int ci_session_summarize_placebo_blocks(ci_session* s, const double* scale, const double* shift,
+                                        int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                        double* predicted_mean, double* spread_mean, double* pit_mean) {
+  return summarize_placebo(s, true, scale, shift, max_origins, origins, horizon, predicted_mean, spread_mean,
+                           pit_mean);
+}
+
+int ci_session_simulate_placebo(ci_session* s, const double* scale, const double* shift, int32_t max_origins,
+                                const int32_t* origins, const int32_t* horizon, int32_t link, const double* seen,
+                                int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
+                                double* spread_mean, double* below, double* total_order, double* totals) {
+  return simulate_placebo(s, false, scale, shift, max_origins, origins, horizon, link, seen, num_ranks, ranks,
+                          predicted_mean, spread_mean, below, total_order, totals, 0, nullptr);
+}
+
+int ci_session_simulate_placebo_blocks(ci_session* s, const double* scale, const double* shift,
+                                       int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                       int32_t link, const double* seen, int32_t num_ranks, const int32_t* ranks,
+                                       double* predicted_mean, double* spread_mean, double* below,
+                                       double* total_order, double* totals) {
+  return simulate_placebo(s, true, scale, shift, max_origins, origins, horizon, link, seen, num_ranks, ranks,
+                          predicted_mean, spread_mean, below, total_order, totals, 0, nullptr);
+}
+
+int ci_test_session_simulate_placebo(ci_session* s, int32_t blocks, const double* scale, const double* shift,
+                                     int32_t max_origins, const int32_t* origins, const int32_t* horizon,
+                                     int32_t link, const double* seen, int32_t num_ranks, const int32_t* ranks,
+                                     double* predicted_mean, double* spread_mean, double* below,
+                                     double* total_order, double* totals, int64_t max_rows, int32_t* num_chunks) {
+  return simulate_placebo(s, blocks != 0, scale, shift, max_origins, origins, horizon, link, seen, num_ranks, ranks,
+                          predicted_mean, spread_mean, below, total_order, totals, max_rows, num_chunks);
+}
+
+int ci_session_pool_placebo(ci_session* s, const double* scale, const double* shift,
+                            int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                            const double* weights, int32_t max_origins, const int32_t* origins,
+                            const int32_t* horizon, const double* init, double* out,
+                            const double* seen, double* predicted_mean, double* spread_mean,
+                            double* pit_mean) {
+  return pool_placebo(s, false, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
+                      horizon, init, out, seen, predicted_mean, spread_mean, pit_mean, 0);
+}
+
+int ci_session_pool_placebo_blocks(ci_session* s, const double* scale, const double* shift,
+                                   int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                   const double* weights, int32_t max_origins, const int32_t* origins,
+                                   const int32_t* horizon, const double* init, double* out,
+                                   const double* seen, double* predicted_mean, double* spread_mean,
+                                   double* pit_mean) {
+  return pool_placebo(s, true, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
+                      horizon, init, out, seen, predicted_mean, spread_mean, pit_mean, 0);
+}
+
+int ci_test_session_pool_placebo_blocks(ci_session* s, const double* scale, const double* shift,
+                                        int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                        const double* weights, int32_t max_origins, const int32_t* origins,
+                                        const int32_t* horizon, const double* init, double* out,
+                                        const double* seen, double* predicted_mean, double* spread_mean,
+                                        double* pit_mean, int32_t chunk_entries) {
+  if (!s) return fail("NULL argument");
+  if (chunk_entries < 1)
+    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", s->pb.num_series, chunk_entries);
+  return pool_placebo(s, true, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
+                      horizon, init, out, seen, predicted_mean, spread_mean, pit_mean, chunk_entries);
+}
+
+int ci_session_pool_simulated_placebo(ci_session* s, const double* scale, const double* shift,
+                                      int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                      const double* weights, int32_t max_origins, const int32_t* origins,
+                                      const int32_t* horizon, int32_t link, const double* init, double* out,
+                                      const double* seen, const int32_t* counted, int32_t num_ranks,
+                                      const int32_t* ranks, double* predicted_mean, double* spread_mean,
+                                      double* below, double* total_order) {
+  return pool_simulated_placebo(s, false, scale, shift, num_groups, offsets, members, weights, max_origins,
+                                origins, horizon, link, init, out, seen, counted, num_ranks, ranks,
+                                predicted_mean, spread_mean, below, total_order, 0);
+}
+
+int ci_session_pool_simulated_placebo_blocks(ci_session* s, const double* scale, const double* shift,
+                                             int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                             const double* weights, int32_t max_origins, const int32_t* origins,
+                                             const int32_t* horizon, int32_t link, const double* init, double* out,
+                                             const double* seen, const int32_t* counted, int32_t num_ranks,
+                                             const int32_t* ranks, double* predicted_mean, double* spread_mean,
+                                             double* below, double* total_order) {
+  return pool_simulated_placebo(s, true, scale, shift, num_groups, offsets, members, weights, max_origins,
+                                origins, horizon, link, init, out, seen, counted, num_ranks, ranks,
+                                predicted_mean, spread_mean, below, total_order, 0);
+}
+
+int ci_test_session_pool_simulated_placebo(ci_session* s, int32_t blocks, const double* scale, const double* shift,
+                                           int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                           const double* weights, int32_t max_origins, const int32_t* origins,
+                                           const int32_t* horizon, int32_t link, const double* init, double* out,
+                                           const double* seen, const int32_t* counted, int32_t num_ranks,
+                                           const int32_t* ranks, double* predicted_mean, double* spread_mean,
+                                           double* below, double* total_order, int32_t chunk_entries) {
+  if (!s) return fail("NULL argument");
+  if (chunk_entries < 1)
+    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", s->pb.num_series, chunk_entries);
+  return pool_simulated_placebo(s, blocks != 0, scale, shift, num_groups, offsets, members, weights, max_origins,
+                                origins, horizon, link, init, out, seen, counted, num_ranks, ranks,
+                                predicted_mean, spread_mean, below, total_order, chunk_entries);
+}
+
+}  // extern "C"

@@ -61,6 +61,19 @@ struct PathsChunk {
   const double* shifts;
 };
 
+// The launches (ci_paths.hip) of one chunk's four passes -- `pairs` pairs from p0, max_count the
+// longest window among them -- from the resident float32 trajectories under `link`, and from float64
+// draws [groups, N, T] whose first group is g0.
+hipError_t paths_launch(hipStream_t stream, int link, int N, int T, int W, int p0, int pairs, int max_count,
+                        const float* traj, const double* obs, const double* scales, const double* shifts,
+                        const int* first, const int* count, const long long* steps_before, double* X,
+                        double* mom, double* observed_excursion, int* at, double* excursion, int* exceed);
+hipError_t paths_launch_f64(hipStream_t stream, int N, int T, int W, int p0, int pairs, int max_count,
+                            const double* draws, int g0, const double* obs, const double* scales,
+                            const double* shifts, const int* first, const int* count,
+                            const long long* steps_before, double* X, double* mom,
+                            double* observed_excursion, int* at, double* excursion, int* exceed);
+
 // grid (ceil(N / 64), pairs), one wavefront per workgroup.  X of a pair: [2][count][N].
 // ALIGNED as in window_totals_kernel (T % 4 == 0 and a 16-byte aligned base).
 // LINK (ci_link.h): v is link(that); the identity is the code without it.
@@ -187,6 +200,10 @@ __device__ inline double paths_block_sum(double a, double* part) {
   return __dadd_rn(__dadd_rn(__dadd_rn(part[0], part[1]), part[2]), part[3]);
 }
 
+// The three kernels from here on are no templates: a unit that includes them emits them.  The host
+// units (ci_session.h) take the declarations alone.
+#ifndef CI_SEASONAL_DECL_ONLY
+
 // grid (2 * the longest window of the chunk, pairs), PATHS_NT threads: blockIdx.x = 2 * step + path.
 // mom of a pair: [path][center | spread][count].
 __global__ __launch_bounds__(PATHS_NT) void path_moments_kernel(PathsChunk c, const double* __restrict__ X_all,
@@ -265,5 +282,7 @@ __global__ __launch_bounds__(PATHS_NT) void path_excursion_kernel(PathsChunk c, 
   excursion[((size_t)q * 2 + k) * N + n] = best;
   if (best >= observed_excursion[2 * q + k]) atomicAdd(exceed + 2 * q + k, 1);
 }
+
+#endif  // CI_SEASONAL_DECL_ONLY
 
 }  // namespace ci

@@ -54,6 +54,16 @@ struct PlaceboArgs {
                                    // horizon [E], p.out [E, O, N]; nullptr: entry b is series b
 };
 
+// The launches (ci_placebo.hip): placebo_kernel<has_slope, num_seasons, out> over B series or
+// entries; placebo_pool_kernel<which> adding the rows of the entries c0 .. c1 - 1 in M to the groups'
+// accumulators; placebo_finish_kernel<out> over the accumulators' rows r0 .. r0 + rows - 1 into M.
+hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
+                          const PlaceboArgs& args);
+hipError_t placebo_pool_launch(hipStream_t stream, int N, int O, int G, int which, int c0, int c1,
+                               const int* offsets, const double* weights, const double* M, double* acc);
+hipError_t placebo_finish_launch(hipStream_t stream, int N, size_t r0, size_t rows, int out,
+                                 const double* acc, const double* seen, double* M);
+
 // a <- T a, P <- T P T' + Q of step t -> t + 1 (the lines of predict_kernel): the trend's part, then
 // the block's where `change` is set.
 template <int HAS_SLOPE, int NS, int D>
@@ -228,6 +238,18 @@ struct PlaceboSimArgs {
   const uint32_t* keys;            // [B, 2]: the Philox key every series' fit ran on
   int* counted;                    // [rows of this launch]: cnt of (series, slot)
 };
+
+// The launches (ci_placebo.hip): placebo_sim_kernel<has_slope, num_seasons, link> over nb series from
+// args.b0, its ENTRIES build over E entries; placebo_pool_kernel<0, 1> adding the entries' totals to
+// one-plane accumulators; placebo_sim_seen_kernel<rewrite> over the rows of M.
+hipError_t placebo_sim_launch(hipStream_t stream, int nb, int has_slope, int num_seasons, int link,
+                              const PlaceboSimArgs& args);
+hipError_t placebo_sim_entries_launch(hipStream_t stream, int E, int has_slope, int num_seasons, int link,
+                                      const PlaceboSimArgs& args);
+hipError_t placebo_pool_totals_launch(hipStream_t stream, int N, int O, int G, int c0, int c1,
+                                      const int* offsets, const double* weights, const double* M, double* acc);
+hipError_t placebo_sim_seen_launch(hipStream_t stream, size_t rows, int N, double* M, const double* seen,
+                                   const int* counted, double* below, int rewrite);
 
 // The normal of step h of a window: the Philox call of h >> 2 and the Box-Muller pair of h >> 1 are
 // formed when h enters them and carried in (r, z0, z1) -- normal_d(g, iter, SITE_PLACEBO_SIM, sub, h).

@@ -35,6 +35,11 @@ struct PlaceboBlocksPoolArgs : PlaceboBlocksArgs {   // q.series_of [E], q.origi
   double* var;                     // [E, O, N]: VAR
 };
 
+// The launches (ci_placebo_blocks.hip): placebo_blocks_kernel<G, out> over B series; its entry-table
+// build <G, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs> over E entries.
+hipError_t placebo_blocks_launch(hipStream_t stream, int B, int out, const PlaceboBlocksArgs& args);
+hipError_t placebo_blocks_pool_launch(hipStream_t stream, int E, const PlaceboBlocksPoolArgs& args);
+
 // The series of grid row e: with an entry table that of entry e, else e itself.
 template <bool ENTRIES>
 __device__ __forceinline__ size_t pb_series_of(const PlaceboArgs& q, size_t e) {
@@ -143,6 +148,11 @@ struct PlaceboBlocksSimArgs {
   PlaceboSimArgs s;                // s.q.p as PredBlocksArgs::p
   BlockModel m;
 };
+
+// The launches (ci_placebo_blocks.hip): placebo_blocks_sim_kernel<G, link> over nb series from
+// args.s.b0, its ENTRIES build over E entries.
+hipError_t placebo_blocks_sim_launch(hipStream_t stream, int nb, int link, const PlaceboBlocksSimArgs& args);
+hipError_t placebo_blocks_sim_entries_launch(hipStream_t stream, int E, int link, const PlaceboBlocksSimArgs& args);
 
 // grid (ceil(N / (64 / G)), series of the launch), block 64.  The entry-table build (ENTRIES;
 // ci_session_pool_simulated_placebo_blocks) has the grid (ceil(N / (64 / G)), entries of the launch)

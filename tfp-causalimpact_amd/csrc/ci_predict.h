@@ -55,6 +55,10 @@ struct PredArgs {
   double* ll;                      // [B, N] or nullptr
 };
 
+// The launch (ci_predict.hip): predict_kernel<has_slope, num_seasons, out> over B series.
+hipError_t predict_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
+                          const PredArgs& args);
+
 // Position of (i, j) in the row-major upper triangle of a symmetric D x D matrix.
 template <int D> __host__ __device__ constexpr int pred_sym(int i, int j) {
   return i <= j ? i * D - i * (i - 1) / 2 + (j - i) : j * D - j * (j - 1) / 2 + (i - j);

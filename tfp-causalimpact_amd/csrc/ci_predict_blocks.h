@@ -69,6 +69,9 @@ struct PredBlocksArgs {
   BlockModel m;
 };
 
+// The launch (ci_predict_blocks.hip): predict_blocks_kernel<G, out> over B series, G from m.d.
+hipError_t predict_blocks_launch(hipStream_t stream, int B, int out, const PredBlocksArgs& args);
+
 // What a group's lanes share: the model in LDS, the exchange vectors, the lane's place.
 struct PbCtx {
   int lane, i, gb, g;              // lane of the wavefront, row, the group's first lane, group

@@ -1,26 +1,26 @@
-// ci_summary.hip -- the on-device summaries behind the C-ABI (kernels: ci_summary.h,
-// ci_components.h, ci_predict.h): ci_session_summarize, ci_session_summarize_components,
-// ci_session_summarize_predictions, ci_session_summarize_placebo, ci_session_pool_placebo,
-// ci_session_pool_placebo_blocks, ci_session_simulate_placebo[_blocks], ci_session_pool_simulated_placebo[_blocks]
-// (kernels: ci_placebo.h, ci_placebo_blocks.h),
+// ci_summary.hip -- the on-device summaries of trajectories behind the C-ABI (kernels: ci_summary.h,
+// ci_components.h): ci_session_summarize, ci_session_summarize_components,
 // ci_session_summarize_windows, ci_ll_session_summarize_windows
 // (kernel: ci_windows.h), ci_session_summarize_paths, ci_ll_session_summarize_paths (kernels: ci_paths.h),
 // ci_session_set_link and ci_session_value_mean (the outcome link: ci_link.h),
 // ci_ll_session_hmc_summarize on the trajectories a session holds, ci_summarize_draws[_f64] and
 // ci_summarize_draw_paths_f64 on draws the caller hands in; ci_session_pool_trajectories, ci_ll_session_pool_trajectories and
 // ci_session_pool_event_trajectories (kernels: ci_pool.h) on the trajectories a session holds.
+// The Kalman-filter entries (prediction errors, placebo forecasts) are ci_forecast.hip's; the helpers
+// it takes from here -- and with launch_select the select kernels, instantiated in this unit alone --
+// are declared in ci_summary_host.h.
 #include <cmath>
 #include <vector>
 
-#include "ci_placebo.h"
-#include "ci_placebo_blocks.h"
-#include "ci_pool.h"
-#include "ci_predict.h"
-#include "ci_predict_blocks.h"
 #include "ci_session.h"
+#include "ci_components.h"
+#include "ci_paths.h"
+#include "ci_pool.h"
 #include "ci_summary.h"
+#include "ci_summary_host.h"
+#include "ci_windows.h"
 
-static int check_ranks(int32_t num_ranks, const int32_t* ranks, int N) {
+int check_ranks(int32_t num_ranks, const int32_t* ranks, int N) {
   if (num_ranks < 1 || num_ranks > ci::SUMM_MAX_RANKS)
     return fail("num_ranks must be in [1, %d], got %d", ci::SUMM_MAX_RANKS, num_ranks);
   for (int r = 0; r < num_ranks; ++r)
@@ -35,8 +35,8 @@ static int check_ranks(int32_t num_ranks, const int32_t* ranks, int N) {
 #ifndef CI_SEL_NT
 #define CI_SEL_NT 256
 #endif
-static hipError_t launch_select(hipStream_t stream, int N, int T, int rows, int R, const int* d_ranks,
-                                const double* M0, const double* M1, double* out0, double* out1) {
+hipError_t launch_select(hipStream_t stream, int N, int T, int rows, int R, const int* d_ranks,
+                         const double* M0, const double* M1, double* out0, double* out1) {
   const int grid = M1 ? 2 * rows : rows;
   if (N <= 8192) {
     hipLaunchKernelGGL((ci::summ_select_reg_kernel<CI_SEL_NT, 8192 / CI_SEL_NT>), dim3(grid),
@@ -56,7 +56,7 @@ static hipError_t launch_select(hipStream_t stream, int N, int T, int rows, int 
 
 // The scratch of a summary of B series of N draws over T steps: allocated on first use and kept
 // (ci_session_summarize and ci_session_summarize_components share it).
-static int summ_scratch_alloc(SummScratch& w, int B, int T, int N) {
+int summ_scratch_alloc(SummScratch& w, int B, int T, int N) {
   if (w.value.p) return 0;
   const size_t BTN = (size_t)B * T * N;
   HIP_TRY(w.value.alloc(BTN));
@@ -127,56 +127,6 @@ static int summarize_resident(hipStream_t stream, SummScratch& w, int link, int 
                       hipMemcpyDeviceToHost));
   return 0;
 }
-
-// The launches of ci_components.hip (kernels: ci_components.h).
-namespace ci {
-hipError_t comp_launch_gather(hipStream_t stream, int B, int N, int T, int K, int k, const float* in,
-                              const double* scales, const double* shifts, double* out);
-hipError_t comp_launch_regression(hipStream_t stream, int B, int N, int T, int P, const float* Xt,
-                                  const float* w, const int* series_T, const double* scales,
-                                  double* out);
-hipError_t comp_launch_row_stats(hipStream_t stream, size_t rows, int N, const double* M,
-                                 double* mean, int* nonzero);
-// The launch of ci_predict.hip (kernels: ci_predict.h).
-hipError_t predict_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
-                          const PredArgs& args);
-// The launch of ci_placebo.hip (kernels: ci_placebo.h).
-hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
-                          const PlaceboArgs& args);
-// The launches of ci_predict_blocks.hip and ci_placebo_blocks.hip (kernels: ci_predict_blocks.h,
-// ci_placebo_blocks.h).
-hipError_t predict_blocks_launch(hipStream_t stream, int B, int out, const PredBlocksArgs& args);
-hipError_t placebo_blocks_launch(hipStream_t stream, int B, int out, const PlaceboBlocksArgs& args);
-hipError_t placebo_blocks_pool_launch(hipStream_t stream, int E, const PlaceboBlocksPoolArgs& args);
-hipError_t placebo_sim_launch(hipStream_t stream, int nb, int has_slope, int num_seasons, int link,
-                              const PlaceboSimArgs& args);
-hipError_t placebo_blocks_sim_launch(hipStream_t stream, int nb, int link, const PlaceboBlocksSimArgs& args);
-hipError_t placebo_sim_entries_launch(hipStream_t stream, int E, int has_slope, int num_seasons, int link,
-                                      const PlaceboSimArgs& args);
-hipError_t placebo_blocks_sim_entries_launch(hipStream_t stream, int E, int link, const PlaceboBlocksSimArgs& args);
-hipError_t placebo_pool_totals_launch(hipStream_t stream, int N, int O, int G, int c0, int c1,
-                                      const int* offsets, const double* weights, const double* M, double* acc);
-hipError_t placebo_sim_seen_launch(hipStream_t stream, size_t rows, int N, double* M, const double* seen,
-                                   const int* counted, double* below, int rewrite);
-hipError_t placebo_pool_launch(hipStream_t stream, int N, int O, int G, int which, int c0, int c1,
-                               const int* offsets, const double* weights, const double* M, double* acc);
-hipError_t placebo_finish_launch(hipStream_t stream, int N, size_t r0, size_t rows, int out,
-                                 const double* acc, const double* seen, double* M);
-// The launch of ci_windows.hip (kernel: ci_windows.h).
-hipError_t windows_launch(hipStream_t stream, int link, int B, int N, int T, int W, const float* traj,
-                          const double* obs, const double* scales, const double* shifts,
-                          const int* first, const int* count, double* out);
-// The launch of ci_paths.hip (kernels: ci_paths.h).
-hipError_t paths_launch(hipStream_t stream, int link, int N, int T, int W, int p0, int pairs, int max_count,
-                        const float* traj, const double* obs, const double* scales, const double* shifts,
-                        const int* first, const int* count, const long long* steps_before, double* X,
-                        double* mom, double* observed_excursion, int* at, double* excursion, int* exceed);
-hipError_t paths_launch_f64(hipStream_t stream, int N, int T, int W, int p0, int pairs, int max_count,
-                            const double* draws, int g0, const double* obs, const double* scales,
-                            const double* shifts, const int* first, const int* count,
-                            const long long* steps_before, double* X, double* mom,
-                            double* observed_excursion, int* at, double* excursion, int* exceed);
-}  // namespace ci
 
 // The window tables of ci_session_summarize_windows and ci_session_summarize_paths: first, count
 // [B, W] inside the session's T steps, the error naming the offending window.  unit, whose: what the
@@ -412,8 +362,7 @@ static int summarize_draws_impl(int32_t device, int32_t num_draws, int32_t T, co
 }
 
 // The group table of the pool entry points (CSR over the positions of the session's B series).
-static int check_groups(int B, int32_t G, const int32_t* offsets, const int32_t* members,
-                        const double* weights) {
+int check_groups(int B, int32_t G, const int32_t* offsets, const int32_t* members, const double* weights) {
   if (G < 1) return fail("num_groups must be >= 1, got %d", G);
   if (offsets[0] != 0) return fail("offsets[0] must be 0, got %d", offsets[0]);
   for (int g = 0; g < G; ++g) {
@@ -768,744 +717,6 @@ int ci_session_summarize_components(ci_session* s, const double* scale, const do
       for (size_t e = 0; e < BP; ++e) inclusion_prob[e] = (double)count[e] / (double)N;
   }
   return 0;
-}
-
-// What ci_session_summarize_predictions and ci_session_summarize_placebo ask of a session: a trend
-// with at most one block of 2 to 7 seasons, and a finished run.
-static int pred_check_session(const ci_session* s, const char* who) {
-  const ci_problem& pb = s->pb;
-  if (pb.num_blocks > 1 || (pb.num_blocks == 1 && (pb.num_seasons[0] < 2 || pb.num_seasons[0] > 7))) {
-    std::string blocks;
-    for (int k = 0; k < pb.num_blocks; ++k) blocks += (k ? ", " : "") + std::to_string(pb.num_seasons[k]);
-    return fail("%s takes a trend with at most one block of 2 to 7 seasons, "
-                "this session has the blocks (%s)", who, blocks.c_str());
-  }
-  if (!s->ran) return fail("%s needs a finished ci_session_run", who);
-  return 0;
-}
-
-// What ci_session_summarize_predictions_blocks and ci_session_summarize_placebo_blocks ask of a
-// session: not ragged, a state of at most 64 components, and a finished run.
-static int pred_blocks_check_session(const ci_session* s, const char* who) {
-  const ci_problem& pb = s->pb;
-  if (s->ragged) {
-    const std::string name(who), tail("_blocks");
-    const bool cut = name.size() > tail.size() && name.compare(name.size() - tail.size(), tail.size(), tail) == 0;
-    return fail("%s takes no ragged session: their models (one block of 2 to 7 seasons at most) "
-                "belong to the entry without _blocks, %s", who,
-                (cut ? name.substr(0, name.size() - tail.size()) : name).c_str());
-  }
-  int d = 1 + (pb.has_slope ? 1 : 0);
-  for (int k = 0; k < pb.num_blocks; ++k) d += pb.num_seasons[k] - 1;
-  if (d > ci::PB_MAX_STATE) {
-    std::string blocks;
-    for (int k = 0; k < pb.num_blocks; ++k) blocks += (k ? ", " : "") + std::to_string(pb.num_seasons[k]);
-    return fail("%s takes a state of at most %d components, this session has %d with the blocks (%s)",
-                who, ci::PB_MAX_STATE, d, blocks.c_str());
-  }
-  if (!s->ran) return fail("%s needs a finished ci_session_run", who);
-  return 0;
-}
-
-// The block list of a session as the block-model filters read it.
-static ci::BlockModel pred_block_model(const ci_problem& pb) {
-  ci::BlockModel m = {};
-  m.has_slope = pb.has_slope ? 1 : 0;
-  m.K = pb.num_blocks;
-  m.d = 1 + m.has_slope;
-  m.zmask = 1ull;
-  for (int k = 0; k < m.K; ++k) {
-    m.off[k] = m.d;
-    m.ns[k] = pb.num_seasons[k];
-    m.zmask |= 1ull << m.d;
-    m.d += pb.num_seasons[k] - 1;
-  }
-  return m;
-}
-
-// On the device, once per session: per series the initial moments of its ci_series_params [B, 4],
-// then [B] times the 1.0 the regression term is scaled by.
-static int pred_init_upload(ci_session* s) {
-  if (s->pred_init.p) return 0;
-  const int B = s->pb.num_series;
-  std::vector<double> init((size_t)5 * B, 1.0);
-  for (int b = 0; b < B; ++b) {
-    const ci_series_params& q = s->params[b];
-    init[4 * b + 0] = q.init_level_loc;
-    init[4 * b + 1] = q.init_level_scale * q.init_level_scale;
-    init[4 * b + 2] = q.init_slope_scale * q.init_slope_scale;
-    init[4 * b + 3] = q.init_seasonal_scale * q.init_seasonal_scale;
-  }
-  HIP_TRY(s->pred_init.alloc(init.size()));
-  HIP_TRY(hipMemcpy(s->pred_init.p, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
-  return 0;
-}
-
-// ci_session_summarize_predictions and, with `blocks`, ci_session_summarize_predictions_blocks: they
-// differ in the sessions they take and in the filter they launch, in nothing else.
-static int summarize_predictions(ci_session* s, bool blocks, const double* scale, const double* shift,
-                                 int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
-                                 double* forecast_order, double* variance_mean, double* pit_mean,
-                                 double* loglik) {
-  if (!s || !scale || !shift || !ranks) return fail("NULL argument");
-  const ci_problem& pb = s->pb;          // (not kpb: the inert block of a long trend-only series is no part of the model)
-  if (blocks ? pred_blocks_check_session(s, "ci_session_summarize_predictions_blocks")
-             : pred_check_session(s, "ci_session_summarize_predictions"))
-    return 1;
-  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
-  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, R = num_ranks;
-  if (check_ranks(R, ranks, N)) return 1;
-  HIP_TRY(hipSetDevice(pb.device));
-  SummScratch& w = s->summ;
-  if (summ_scratch_alloc(w, B, T, N)) return 1;
-  hipStream_t stream = s->stream;
-  double* d_scale = w.obs.p + (size_t)B * T;
-  double* d_shift = d_scale + B;
-  if (pred_init_upload(s)) return 1;
-  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
-  // The regression term of every draw and step in `cum`, once; then one filter pass per requested
-  // matrix through `value`, its row means in `obs`, its order statistics in `order`, the per-draw
-  // log-likelihoods (with the first pass) in `draw`.
-  const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
-  if (P > 0)
-    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
-                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
-  ci::PredArgs a;
-  a.N = N; a.T = T;
-  a.y = s->y.p; a.mask = s->mask.p; a.season_change = s->season_change.p; a.series_T = d_series_T;
-  a.obs = s->o_obs.p; a.lscale = s->o_lscale.p; a.sscale = s->o_sscale.p; a.drift = s->o_drift.p;
-  a.init = s->pred_init.p; a.scales = d_scale; a.shifts = d_shift;
-  a.reg = P > 0 ? w.cum.p : nullptr;
-  a.out = w.value.p;
-  ci::PredBlocksArgs ab;
-  if (blocks) ab.m = pred_block_model(pb);
-  bool ll_pending = loglik != nullptr;
-  auto pass = [&](int which, double* mean_dst, double* order_dst) -> int {
-    a.ll = ll_pending ? w.draw.p : nullptr;
-    if (blocks) {
-      ab.p = a;
-      HIP_TRY(ci::predict_blocks_launch(stream, B, which, ab));
-    } else {
-      HIP_TRY(ci::predict_launch(stream, B, pb.has_slope, NS, which, a));
-    }
-    if (mean_dst) HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * T, N, w.value.p, w.obs.p, nullptr));
-    if (order_dst)
-      HIP_TRY(launch_select(stream, N, T, B * T, R, w.ranks.p, w.value.p, nullptr, w.order.p, nullptr));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (mean_dst)
-      HIP_TRY(hipMemcpy(mean_dst, w.obs.p, (size_t)B * T * sizeof(double), hipMemcpyDeviceToHost));
-    if (order_dst)
-      HIP_TRY(hipMemcpy(order_dst, w.order.p, (size_t)B * R * T * sizeof(double), hipMemcpyDeviceToHost));
-    if (ll_pending)
-      HIP_TRY(hipMemcpy(loglik, w.draw.p, (size_t)B * N * sizeof(double), hipMemcpyDeviceToHost));
-    ll_pending = false;
-    return 0;
-  };
-  if ((forecast_mean || forecast_order) && pass(ci::PRED_FORECAST, forecast_mean, forecast_order)) return 1;
-  if (variance_mean && pass(ci::PRED_VARIANCE, variance_mean, nullptr)) return 1;
-  if ((pit_mean || ll_pending) && pass(ci::PRED_PIT, pit_mean, nullptr)) return 1;
-  return 0;
-}
-
-int ci_session_summarize_predictions(ci_session* s, const double* scale, const double* shift,
-                                     int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
-                                     double* forecast_order, double* variance_mean, double* pit_mean,
-                                     double* loglik) {
-  return summarize_predictions(s, false, scale, shift, num_ranks, ranks, forecast_mean, forecast_order,
-                               variance_mean, pit_mean, loglik);
-}
-
-int ci_session_summarize_predictions_blocks(ci_session* s, const double* scale, const double* shift,
-                                            int32_t num_ranks, const int32_t* ranks, double* forecast_mean,
-                                            double* forecast_order, double* variance_mean, double* pit_mean,
-                                            double* loglik) {
-  return summarize_predictions(s, true, scale, shift, num_ranks, ranks, forecast_mean, forecast_order,
-                               variance_mean, pit_mean, loglik);
-}
-
-// The origin table of ci_session_summarize_placebo and ci_session_simulate_placebo: max_origins in
-// [1, T], horizon >= 1, every row ascending with -1 only at the end, o + H_b <= T_b.
-static int check_placebo_plan(const ci_session* s, int O, const int32_t* origins, const int32_t* horizon) {
-  const int B = s->pb.num_series, T = s->pb.T;
-  if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
-  for (int b = 0; b < B; ++b) {
-    const int Tb = s->ragged ? s->lengths[b] : T, Hb = horizon[b];
-    if (Hb < 1) return fail("horizon[%d] must be at least 1, got %d", b, Hb);
-    const int32_t* row = origins + (size_t)b * O;
-    bool ended = false;
-    for (int i = 0; i < O; ++i) {
-      const int o = row[i];
-      if (o == -1) { ended = true; continue; }
-      if (o < 0) return fail("origins[%d, %d] must be a step or -1 (unused), got %d", b, i, o);
-      if (ended || (i > 0 && o <= row[i - 1]))
-        return fail("origins[%d] must be strictly ascending with the unused slots (-1) at the end "
-                    "(slot %d holds %d)", b, i, o);
-      if ((long long)o + Hb > Tb)
-        return fail("origins[%d, %d] = %d with horizon %d reaches beyond the series' %d steps", b, i, o, Hb, Tb);
-    }
-  }
-  return 0;
-}
-
-// ci_session_summarize_placebo and, with `blocks`, ci_session_summarize_placebo_blocks, likewise.
-static int summarize_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
-                             int32_t max_origins, const int32_t* origins, const int32_t* horizon,
-                             double* predicted_mean, double* spread_mean, double* pit_mean) {
-  if (!s || !scale || !shift || !origins || !horizon) return fail("NULL argument");
-  const ci_problem& pb = s->pb;          // (not kpb: the inert block of a long trend-only series is no part of the model)
-  if (blocks ? pred_blocks_check_session(s, "ci_session_summarize_placebo_blocks")
-             : pred_check_session(s, "ci_session_summarize_placebo"))
-    return 1;
-  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
-  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins;
-  if (check_placebo_plan(s, O, origins, horizon)) return 1;
-  HIP_TRY(hipSetDevice(pb.device));
-  SummScratch& w = s->summ;
-  if (summ_scratch_alloc(w, B, T, N)) return 1;
-  hipStream_t stream = s->stream;
-  double* d_scale = w.obs.p + (size_t)B * T;
-  double* d_shift = d_scale + B;
-  if (pred_init_upload(s)) return 1;
-  DevBuf<int> d_plan;                    // origins [B, O], then horizon [B]
-  HIP_TRY(d_plan.alloc((size_t)B * O + B));
-  HIP_TRY(hipMemcpyAsync(d_plan.p, origins, (size_t)B * O * sizeof(int), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_plan.p + (size_t)B * O, horizon, B * sizeof(int), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
-  // The regression term of every draw and step in `cum`, once; then one pass per requested matrix
-  // [B * O, N] through `value` (O <= T: it fits), its row means in `obs`.
-  const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
-  if (P > 0)
-    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
-                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
-  ci::PlaceboArgs a;
-  a.p.N = N; a.p.T = T;
-  a.p.y = s->y.p; a.p.mask = s->mask.p; a.p.season_change = s->season_change.p; a.p.series_T = d_series_T;
-  a.p.obs = s->o_obs.p; a.p.lscale = s->o_lscale.p; a.p.sscale = s->o_sscale.p; a.p.drift = s->o_drift.p;
-  a.p.init = s->pred_init.p; a.p.scales = d_scale; a.p.shifts = d_shift;
-  a.p.reg = P > 0 ? w.cum.p : nullptr;
-  a.p.out = w.value.p; a.p.ll = nullptr;
-  a.O = O; a.origins = d_plan.p; a.horizon = d_plan.p + (size_t)B * O;
-  ci::PlaceboBlocksArgs ab;
-  if (blocks) { ab.q = a; ab.m = pred_block_model(pb); }
-  auto pass = [&](int which, double* mean_dst) -> int {
-    if (blocks) HIP_TRY(ci::placebo_blocks_launch(stream, B, which, ab));
-    else HIP_TRY(ci::placebo_launch(stream, B, pb.has_slope, NS, which, a));
-    HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * O, N, w.value.p, w.obs.p, nullptr));
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipMemcpy(mean_dst, w.obs.p, (size_t)B * O * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-  };
-  if (predicted_mean && pass(ci::PLACEBO_SUM, predicted_mean)) return 1;
-  if (spread_mean && pass(ci::PLACEBO_SPREAD, spread_mean)) return 1;
-  if (pit_mean && pass(ci::PLACEBO_PIT, pit_mean)) return 1;
-  HIP_TRY(hipStreamSynchronize(stream));   // (the uploads of a call that asks for nothing)
-  return 0;
-}
-
-int ci_session_summarize_placebo(ci_session* s, const double* scale, const double* shift,
-                                 int32_t max_origins, const int32_t* origins, const int32_t* horizon,
-                                 double* predicted_mean, double* spread_mean, double* pit_mean) {
-  return summarize_placebo(s, false, scale, shift, max_origins, origins, horizon, predicted_mean, spread_mean,
-                           pit_mean);
-}
-
-int ci_session_summarize_placebo_blocks(ci_session* s, const double* scale, const double* shift,
-                                        int32_t max_origins, const int32_t* origins, const int32_t* horizon,
-                                        double* predicted_mean, double* spread_mean, double* pit_mean) {
-  return summarize_placebo(s, true, scale, shift, max_origins, origins, horizon, predicted_mean, spread_mean,
-                           pit_mean);
-}
-
-// ci_session_simulate_placebo and, with `blocks`, ci_session_simulate_placebo_blocks: the filter runs
-// ONCE per chunk of series whose rows [nb * O, N] fit the scratch -- simulate into `value`, its row
-// means and order statistics, the rows' download when `totals` is wanted, the count below `seen`,
-// the rewrite to (x - seen)^2 in place and its row means.  TOTAL is a function of (b, slot, n) alone
-// and every statistic one of its row, so nothing depends on where the chunks are cut.  max_rows
-// (tests; 0: the scratch's B * T rows, which hold every call's B * O): the rows of a chunk;
-// num_chunks (may be NULL): how many it took.
-static int simulate_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
-                            int32_t max_origins, const int32_t* origins, const int32_t* horizon, int32_t link,
-                            const double* seen, int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
-                            double* spread_mean, double* below, double* total_order, double* totals,
-                            int64_t max_rows, int32_t* num_chunks) {
-  if (!s || !scale || !shift || !origins || !horizon || !ranks) return fail("NULL argument");
-  const ci_problem& pb = s->pb;          // (not kpb: the inert block of a long trend-only series is no part of the model)
-  const char* who = blocks ? "ci_session_simulate_placebo_blocks" : "ci_session_simulate_placebo";
-  if (blocks ? pred_blocks_check_session(s, who) : pred_check_session(s, who)) return 1;
-  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
-  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins, R = num_ranks;
-  if (check_placebo_plan(s, O, origins, horizon)) return 1;
-  if (link < 0 || link >= ci::NUM_LINKS)
-    return fail("link must be CI_LINK_IDENTITY, CI_LINK_LOG or CI_LINK_LOG1P (0 to %d), got %d", ci::NUM_LINKS - 1, link);
-  if (check_ranks(R, ranks, N)) return 1;
-  if (!seen && (spread_mean || below)) return fail("spread_mean and below need `seen`, which is NULL");
-  const size_t BO = (size_t)B * O;
-  if (max_rows < 0 || (max_rows > 0 && max_rows < O))
-    return fail("max_rows must hold the %d rows of one series, got %lld", O, (long long)max_rows);
-  const size_t cap = max_rows > 0 && (size_t)max_rows < (size_t)B * T ? (size_t)max_rows : (size_t)B * T;
-  const int nb_max = (int)(cap / O);     // (O <= T: at least one series)
-  if (num_chunks) *num_chunks = (B + nb_max - 1) / nb_max;
-  // the Philox key every series' fit ran on (ci_series_stream_key of its id, or the seed itself)
-  std::vector<uint32_t> keys((size_t)2 * B);
-  const int shared = (pb.flags & CI_FLAG_SHARED_SERIES_STREAMS) ? -1 : 0;
-  for (int b = 0; b < B; ++b) {
-    const int sid = s->ids.empty() ? pb.series_offset + b : s->ids[b];
-    keys[2 * b] = ci::stream_key0(pb.seed[0], shared, sid);
-    keys[2 * b + 1] = ci::stream_key1(pb.seed[1], shared, sid);
-  }
-  HIP_TRY(hipSetDevice(pb.device));
-  SummScratch& w = s->summ;
-  if (summ_scratch_alloc(w, B, T, N)) return 1;
-  hipStream_t stream = s->stream;
-  double* d_scale = w.obs.p + (size_t)B * T;
-  double* d_shift = d_scale + B;
-  if (pred_init_upload(s)) return 1;
-  DevBuf<int> d_plan;                    // origins [B, O], horizon [B], counted [B, O]
-  DevBuf<uint32_t> d_keys;               // [B, 2]
-  DevBuf<double> d_stat;                 // seen, mean, spread, below: [B, O] each
-  HIP_TRY(d_plan.alloc(2 * BO + B));
-  HIP_TRY(d_keys.alloc((size_t)2 * B));
-  HIP_TRY(d_stat.alloc(4 * BO));
-  int* d_counted = d_plan.p + BO + B;
-  double *d_seen = d_stat.p, *d_mean = d_stat.p + BO, *d_spread = d_stat.p + 2 * BO, *d_below = d_stat.p + 3 * BO;
-  HIP_TRY(hipMemcpyAsync(d_plan.p, origins, BO * sizeof(int), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_plan.p + BO, horizon, B * sizeof(int), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_keys.p, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-  if (seen) HIP_TRY(hipMemcpyAsync(d_seen, seen, BO * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
-  const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
-  if (P > 0)
-    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
-                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
-  ci::PlaceboBlocksSimArgs ab;
-  ci::PlaceboSimArgs& a = ab.s;
-  a.q.p.N = N; a.q.p.T = T;
-  a.q.p.y = s->y.p; a.q.p.mask = s->mask.p; a.q.p.season_change = s->season_change.p; a.q.p.series_T = d_series_T;
-  a.q.p.obs = s->o_obs.p; a.q.p.lscale = s->o_lscale.p; a.q.p.sscale = s->o_sscale.p; a.q.p.drift = s->o_drift.p;
-  a.q.p.init = s->pred_init.p; a.q.p.scales = d_scale; a.q.p.shifts = d_shift;
-  a.q.p.reg = P > 0 ? w.cum.p : nullptr;
-  a.q.p.out = w.value.p; a.q.p.ll = nullptr;
-  a.q.O = O; a.q.origins = d_plan.p; a.q.horizon = d_plan.p + BO;
-  a.kept = pb.num_results; a.chain_offset = (uint32_t)pb.chain_offset; a.keys = d_keys.p;
-  if (blocks) ab.m = pred_block_model(pb);
-  for (int b0 = 0; b0 < B; b0 += nb_max) {
-    const int nb = B - b0 < nb_max ? B - b0 : nb_max;
-    const size_t rows = (size_t)nb * O, off = (size_t)b0 * O;
-    a.b0 = b0;
-    a.counted = d_counted + off;
-    if (blocks) HIP_TRY(ci::placebo_blocks_sim_launch(stream, nb, link, ab));
-    else HIP_TRY(ci::placebo_sim_launch(stream, nb, pb.has_slope, NS, link, a));
-    if (predicted_mean) HIP_TRY(ci::comp_launch_row_stats(stream, rows, N, w.value.p, d_mean + off, nullptr));
-    if (total_order)
-      HIP_TRY(launch_select(stream, N, O, (int)rows, R, w.ranks.p, w.value.p, nullptr,
-                            w.order.p + (size_t)b0 * R * O, nullptr));
-    if (totals) {
-      HIP_TRY(hipStreamSynchronize(stream));
-      HIP_TRY(hipMemcpy(totals + off * N, w.value.p, rows * N * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    if (spread_mean || below) {
-      HIP_TRY(ci::placebo_sim_seen_launch(stream, rows, N, w.value.p, d_seen + off, d_counted + off,
-                                          below ? d_below + off : nullptr, spread_mean != nullptr));
-      if (spread_mean) HIP_TRY(ci::comp_launch_row_stats(stream, rows, N, w.value.p, d_spread + off, nullptr));
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (predicted_mean) HIP_TRY(hipMemcpy(predicted_mean, d_mean, BO * sizeof(double), hipMemcpyDeviceToHost));
-  if (spread_mean) HIP_TRY(hipMemcpy(spread_mean, d_spread, BO * sizeof(double), hipMemcpyDeviceToHost));
-  if (below) HIP_TRY(hipMemcpy(below, d_below, BO * sizeof(double), hipMemcpyDeviceToHost));
-  if (total_order)
-    HIP_TRY(hipMemcpy(total_order, w.order.p, BO * R * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int ci_session_simulate_placebo(ci_session* s, const double* scale, const double* shift, int32_t max_origins,
-                                const int32_t* origins, const int32_t* horizon, int32_t link, const double* seen,
-                                int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
-                                double* spread_mean, double* below, double* total_order, double* totals) {
-  return simulate_placebo(s, false, scale, shift, max_origins, origins, horizon, link, seen, num_ranks, ranks,
-                          predicted_mean, spread_mean, below, total_order, totals, 0, nullptr);
-}
-
-int ci_session_simulate_placebo_blocks(ci_session* s, const double* scale, const double* shift,
-                                       int32_t max_origins, const int32_t* origins, const int32_t* horizon,
-                                       int32_t link, const double* seen, int32_t num_ranks, const int32_t* ranks,
-                                       double* predicted_mean, double* spread_mean, double* below,
-                                       double* total_order, double* totals) {
-  return simulate_placebo(s, true, scale, shift, max_origins, origins, horizon, link, seen, num_ranks, ranks,
-                          predicted_mean, spread_mean, below, total_order, totals, 0, nullptr);
-}
-
-int ci_test_session_simulate_placebo(ci_session* s, int32_t blocks, const double* scale, const double* shift,
-                                     int32_t max_origins, const int32_t* origins, const int32_t* horizon,
-                                     int32_t link, const double* seen, int32_t num_ranks, const int32_t* ranks,
-                                     double* predicted_mean, double* spread_mean, double* below,
-                                     double* total_order, double* totals, int64_t max_rows, int32_t* num_chunks) {
-  return simulate_placebo(s, blocks != 0, scale, shift, max_origins, origins, horizon, link, seen, num_ranks, ranks,
-                          predicted_mean, spread_mean, below, total_order, totals, max_rows, num_chunks);
-}
-
-// The plan of a pooled placebo call (ci_session_pool_placebo, ci_session_pool_simulated_placebo):
-// one horizon >= 1 per group, every entry's origin row ascending with -1 only at the end and
-// o + H_g <= T_b of its member; entry_horizon [K] is the group's horizon per entry.
-static int check_pool_plan(const ci_session* s, int G, const int32_t* offsets, const int32_t* members, int O,
-                           const int32_t* origins, const int32_t* horizon, std::vector<int>& entry_horizon) {
-  const int T = s->pb.T, K = offsets[G];
-  entry_horizon.assign((size_t)(K ? K : 1), 0);
-  for (int g = 0; g < G; ++g) {
-    const int Hg = horizon[g];
-    if (Hg < 1) return fail("group %d: the horizon must be at least 1, got %d", g, Hg);
-    for (int k = offsets[g]; k < offsets[g + 1]; ++k) {
-      const int b = members[k], Tb = s->ragged ? s->lengths[b] : T;
-      const int32_t* row = origins + (size_t)k * O;
-      entry_horizon[k] = Hg;
-      bool ended = false;
-      for (int i = 0; i < O; ++i) {
-        const int o = row[i];
-        if (o == -1) { ended = true; continue; }
-        if (o < 0)
-          return fail("group %d, entry %d (member %d): slot %d must hold a step or -1 (unused), got %d", g, k, b, i, o);
-        if (ended || (i > 0 && o <= row[i - 1]))
-          return fail("group %d, entry %d (member %d): the origins must be strictly ascending with the unused "
-                      "slots (-1) at the end (slot %d holds %d)", g, k, b, i, o);
-        if ((long long)o + Hg > Tb)
-          return fail("group %d, entry %d (member %d): the origin %d of slot %d with horizon %d reaches beyond "
-                      "the series' %d steps", g, k, b, o, i, Hg, Tb);
-      }
-    }
-  }
-  return 0;
-}
-
-// The placebo forecasts of POOLED sums: per group, slot and draw the weighted sum S of the members'
-// forecasts and the sum U of their predictive variances (include/causalimpact_amd.h).  The entries
-// of the group table pass through `value` at most B at a time, a SUM pass and its accumulate, then a
-// VAR pass and its accumulate; the accumulators [G, O, 2, N] and the tables are the call's own.
-// With `blocks` ci_session_pool_placebo_blocks: the sessions and the filter of the block models, ONE
-// pass per chunk that stores SUM into `value` and VAR into a buffer of the call's own, then the same
-// two accumulates.  chunk_entries (tests; 0: B): the entries of a chunk, in [1, B].
-static int pool_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
-                        int32_t num_groups, const int32_t* offsets, const int32_t* members,
-                        const double* weights, int32_t max_origins, const int32_t* origins,
-                        const int32_t* horizon, const double* init, double* out,
-                        const double* seen, double* predicted_mean, double* spread_mean,
-                        double* pit_mean, int32_t chunk_entries) {
-  if (!s || !scale || !shift || !offsets || !members || !weights || !origins || !horizon || !out)
-    return fail("NULL argument");
-  const ci_problem& pb = s->pb;
-  if (blocks ? pred_blocks_check_session(s, "ci_session_pool_placebo_blocks")
-             : pred_check_session(s, "ci_session_pool_placebo"))
-    return 1;
-  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
-  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins, G = num_groups;
-  if (chunk_entries < 0 || chunk_entries > B)
-    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", B, chunk_entries);
-  const int chunk = chunk_entries ? chunk_entries : B;
-  if (check_groups(B, G, offsets, members, weights)) return 1;
-  if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
-  if (!seen && (predicted_mean || spread_mean || pit_mean))
-    return fail("predicted_mean, spread_mean and pit_mean need `seen`, the pooled observed sums");
-  const int K = offsets[G];
-  std::vector<int> entry_horizon;
-  if (check_pool_plan(s, G, offsets, members, O, origins, horizon, entry_horizon)) return 1;
-  HIP_TRY(hipSetDevice(pb.device));
-  SummScratch& w = s->summ;
-  if (summ_scratch_alloc(w, B, T, N)) return 1;
-  hipStream_t stream = s->stream;
-  double* d_scale = w.obs.p + (size_t)B * T;
-  double* d_shift = d_scale + B;
-  if (pred_init_upload(s)) return 1;
-  const size_t rows = (size_t)G * O, acc_n = rows * 2 * N, Ka = K ? K : 1;
-  DevBuf<int> d_int;                     // offsets [G + 1], members [K], horizon [K], origins [K, O]
-  DevBuf<double> d_dbl;                  // acc [G, O, 2, N], seen [G, O], weights [K]
-  DevBuf<double> d_var;                  // (blocks) VAR of a chunk [chunk, O, N]
-  HIP_TRY(d_int.alloc((size_t)G + 1 + 2 * Ka + Ka * O));
-  HIP_TRY(d_dbl.alloc(acc_n + rows + Ka));
-  if (blocks && K > 0) HIP_TRY(d_var.alloc((size_t)(K < chunk ? K : chunk) * O * N));
-  int* d_off = d_int.p;
-  int* d_members = d_off + G + 1;
-  int* d_horizon = d_members + Ka;
-  int* d_origins = d_horizon + Ka;
-  double* d_acc = d_dbl.p;
-  double* d_seen = d_acc + acc_n;
-  double* d_weights = d_seen + rows;
-  HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-  if (K > 0) {
-    HIP_TRY(hipMemcpyAsync(d_members, members, (size_t)K * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_horizon, entry_horizon.data(), (size_t)K * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_origins, origins, (size_t)K * O * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_weights, weights, (size_t)K * sizeof(double), hipMemcpyHostToDevice, stream));
-  }
-  if (init)
-    HIP_TRY(hipMemcpyAsync(d_acc, init, acc_n * sizeof(double), hipMemcpyHostToDevice, stream));
-  else
-    HIP_TRY(hipMemsetAsync(d_acc, 0, acc_n * sizeof(double), stream));
-  if (seen) HIP_TRY(hipMemcpyAsync(d_seen, seen, rows * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
-  const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
-  if (P > 0 && K > 0)
-    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
-                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
-  ci::PlaceboArgs a;
-  a.p.N = N; a.p.T = T;
-  a.p.y = s->y.p; a.p.mask = s->mask.p; a.p.season_change = s->season_change.p; a.p.series_T = d_series_T;
-  a.p.obs = s->o_obs.p; a.p.lscale = s->o_lscale.p; a.p.sscale = s->o_sscale.p; a.p.drift = s->o_drift.p;
-  a.p.init = s->pred_init.p; a.p.scales = d_scale; a.p.shifts = d_shift;
-  a.p.reg = P > 0 ? w.cum.p : nullptr;
-  a.p.out = w.value.p; a.p.ll = nullptr;
-  a.O = O;
-  ci::PlaceboBlocksPoolArgs ab;
-  if (blocks) { ab.m = pred_block_model(pb); ab.var = d_var.p; }
-  // at most B entries at a time: [B * O, N] with O <= T fits `value`
-  for (int c0 = 0; c0 < K; c0 += chunk) {
-    const int c1 = K - c0 < chunk ? K : c0 + chunk;
-    a.series_of = d_members + c0; a.origins = d_origins + (size_t)c0 * O; a.horizon = d_horizon + c0;
-    if (blocks) {
-      ab.q = a;
-      HIP_TRY(ci::placebo_blocks_pool_launch(stream, c1 - c0, ab));
-      HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, 0, c0, c1, d_off, d_weights, w.value.p, d_acc));
-      HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, 1, c0, c1, d_off, d_weights, d_var.p, d_acc));
-      continue;
-    }
-    for (int which = 0; which < 2; ++which) {
-      HIP_TRY(ci::placebo_launch(stream, c1 - c0, pb.has_slope, NS, which ? ci::PLACEBO_VAR : ci::PLACEBO_SUM, a));
-      HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, which, c0, c1, d_off, d_weights, w.value.p, d_acc));
-    }
-  }
-  HIP_TRY(hipMemcpyAsync(out, d_acc, acc_n * sizeof(double), hipMemcpyDeviceToHost, stream));
-  // the means over the draws, one matrix at a time and as many rows as `value` and `obs` hold
-  const size_t per_pass = (size_t)B * T;
-  auto finish = [&](int which, double* mean_dst) -> int {
-    for (size_t r0 = 0; r0 < rows; r0 += per_pass) {
-      const size_t nr = rows - r0 < per_pass ? rows - r0 : per_pass;
-      HIP_TRY(ci::placebo_finish_launch(stream, N, r0, nr, which, d_acc, d_seen, w.value.p));
-      HIP_TRY(ci::comp_launch_row_stats(stream, nr, N, w.value.p, w.obs.p, nullptr));
-      HIP_TRY(hipMemcpyAsync(mean_dst + r0, w.obs.p, nr * sizeof(double), hipMemcpyDeviceToHost, stream));
-    }
-    return 0;
-  };
-  if (predicted_mean && finish(ci::PLACEBO_SUM, predicted_mean)) return 1;
-  if (spread_mean && finish(ci::PLACEBO_SPREAD, spread_mean)) return 1;
-  if (pit_mean && finish(ci::PLACEBO_PIT, pit_mean)) return 1;
-  HIP_TRY(hipStreamSynchronize(stream));
-  return 0;
-}
-
-int ci_session_pool_placebo(ci_session* s, const double* scale, const double* shift,
-                            int32_t num_groups, const int32_t* offsets, const int32_t* members,
-                            const double* weights, int32_t max_origins, const int32_t* origins,
-                            const int32_t* horizon, const double* init, double* out,
-                            const double* seen, double* predicted_mean, double* spread_mean,
-                            double* pit_mean) {
-  return pool_placebo(s, false, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
-                      horizon, init, out, seen, predicted_mean, spread_mean, pit_mean, 0);
-}
-
-int ci_session_pool_placebo_blocks(ci_session* s, const double* scale, const double* shift,
-                                   int32_t num_groups, const int32_t* offsets, const int32_t* members,
-                                   const double* weights, int32_t max_origins, const int32_t* origins,
-                                   const int32_t* horizon, const double* init, double* out,
-                                   const double* seen, double* predicted_mean, double* spread_mean,
-                                   double* pit_mean) {
-  return pool_placebo(s, true, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
-                      horizon, init, out, seen, predicted_mean, spread_mean, pit_mean, 0);
-}
-
-int ci_test_session_pool_placebo_blocks(ci_session* s, const double* scale, const double* shift,
-                                        int32_t num_groups, const int32_t* offsets, const int32_t* members,
-                                        const double* weights, int32_t max_origins, const int32_t* origins,
-                                        const int32_t* horizon, const double* init, double* out,
-                                        const double* seen, double* predicted_mean, double* spread_mean,
-                                        double* pit_mean, int32_t chunk_entries) {
-  if (!s) return fail("NULL argument");
-  if (chunk_entries < 1)
-    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", s->pb.num_series, chunk_entries);
-  return pool_placebo(s, true, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
-                      horizon, init, out, seen, predicted_mean, spread_mean, pit_mean, chunk_entries);
-}
-
-// The SIMULATED placebo forecasts of pooled sums (include/causalimpact_amd.h): the entries of the group
-// table pass through `value` at most `chunk` at a time -- ONE simulation pass (the entry-table build
-// of simulate_placebo's kernel; TOTAL is a function of (series, origin, slot, horizon, n) alone) and
-// its accumulate into POOL [G, O, N], the call's own.  `out` is downloaded, then the statistics of
-// simulate_placebo are taken over the accumulators' rows, copied through `value` at most B * T rows
-// at a time (whole groups, so that the selection's [G, R, O] layout holds per chunk): row means,
-// order statistics, the count below `seen`, the rewrite to squares and its row means.  Nothing
-// depends on where either kind of chunk is cut.  chunk_entries (tests; 0: B): in [1, B].
-static int pool_simulated_placebo(ci_session* s, bool blocks, const double* scale, const double* shift,
-                                  int32_t num_groups, const int32_t* offsets, const int32_t* members,
-                                  const double* weights, int32_t max_origins, const int32_t* origins,
-                                  const int32_t* horizon, int32_t link, const double* init, double* out,
-                                  const double* seen, const int32_t* counted, int32_t num_ranks,
-                                  const int32_t* ranks, double* predicted_mean, double* spread_mean,
-                                  double* below, double* total_order, int32_t chunk_entries) {
-  if (!s || !scale || !shift || !offsets || !members || !weights || !origins || !horizon || !out || !ranks)
-    return fail("NULL argument");
-  const ci_problem& pb = s->pb;
-  const char* who = blocks ? "ci_session_pool_simulated_placebo_blocks" : "ci_session_pool_simulated_placebo";
-  if (blocks ? pred_blocks_check_session(s, who) : pred_check_session(s, who)) return 1;
-  const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
-  const int NS = pb.num_blocks ? pb.num_seasons[0] : 0, O = max_origins, G = num_groups, R = num_ranks;
-  if (chunk_entries < 0 || chunk_entries > B)
-    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", B, chunk_entries);
-  const int chunk = chunk_entries ? chunk_entries : B;
-  if (check_groups(B, G, offsets, members, weights)) return 1;
-  if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
-  if (link < 0 || link >= ci::NUM_LINKS)
-    return fail("link must be CI_LINK_IDENTITY, CI_LINK_LOG or CI_LINK_LOG1P (0 to %d), got %d", ci::NUM_LINKS - 1, link);
-  if (check_ranks(R, ranks, N)) return 1;
-  const bool stats = predicted_mean || spread_mean || below || total_order;
-  if (stats && (!seen || !counted))
-    return fail("predicted_mean, spread_mean, below and total_order need `seen` and `counted`, the pooled "
-                "observed totals and the member-steps they count");
-  const int K = offsets[G];
-  std::vector<int> entry_horizon;
-  if (check_pool_plan(s, G, offsets, members, O, origins, horizon, entry_horizon)) return 1;
-  // the Philox key every series' fit ran on (simulate_placebo's)
-  std::vector<uint32_t> keys((size_t)2 * B);
-  const int shared = (pb.flags & CI_FLAG_SHARED_SERIES_STREAMS) ? -1 : 0;
-  for (int b = 0; b < B; ++b) {
-    const int sid = s->ids.empty() ? pb.series_offset + b : s->ids[b];
-    keys[2 * b] = ci::stream_key0(pb.seed[0], shared, sid);
-    keys[2 * b + 1] = ci::stream_key1(pb.seed[1], shared, sid);
-  }
-  HIP_TRY(hipSetDevice(pb.device));
-  SummScratch& w = s->summ;
-  if (summ_scratch_alloc(w, B, T, N)) return 1;
-  hipStream_t stream = s->stream;
-  double* d_scale = w.obs.p + (size_t)B * T;
-  double* d_shift = d_scale + B;
-  if (pred_init_upload(s)) return 1;
-  const size_t rows = (size_t)G * O, acc_n = rows * N, Ka = K ? K : 1;
-  const size_t chunk_rows = (size_t)(K < chunk ? (K ? K : 1) : chunk) * O;
-  DevBuf<int> d_int;                     // offsets [G + 1], members [K], horizon [K], origins [K, O],
-                                         // cnt of a chunk's rows [chunk, O], counted [G, O]
-  DevBuf<double> d_dbl;                  // acc [G, O, N], seen, mean, spread, below [G, O] each, order [G, R, O], weights [K]
-  DevBuf<uint32_t> d_keys;               // [B, 2]
-  HIP_TRY(d_int.alloc((size_t)G + 1 + 2 * Ka + Ka * O + chunk_rows + rows));
-  HIP_TRY(d_dbl.alloc(acc_n + 4 * rows + rows * R + Ka));
-  HIP_TRY(d_keys.alloc((size_t)2 * B));
-  int* d_off = d_int.p;
-  int* d_members = d_off + G + 1;
-  int* d_horizon = d_members + Ka;
-  int* d_origins = d_horizon + Ka;
-  int* d_cnt = d_origins + Ka * O;
-  int* d_counted = d_cnt + chunk_rows;
-  double* d_acc = d_dbl.p;
-  double* d_seen = d_acc + acc_n;
-  double *d_mean = d_seen + rows, *d_spread = d_mean + rows, *d_below = d_spread + rows;
-  double* d_order = d_below + rows;
-  double* d_weights = d_order + rows * R;
-  HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-  if (K > 0) {
-    HIP_TRY(hipMemcpyAsync(d_members, members, (size_t)K * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_horizon, entry_horizon.data(), (size_t)K * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_origins, origins, (size_t)K * O * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_weights, weights, (size_t)K * sizeof(double), hipMemcpyHostToDevice, stream));
-  }
-  if (init)
-    HIP_TRY(hipMemcpyAsync(d_acc, init, acc_n * sizeof(double), hipMemcpyHostToDevice, stream));
-  else
-    HIP_TRY(hipMemsetAsync(d_acc, 0, acc_n * sizeof(double), stream));
-  if (stats) {
-    HIP_TRY(hipMemcpyAsync(d_seen, seen, rows * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_counted, counted, rows * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(w.ranks.p, ranks, R * sizeof(int), hipMemcpyHostToDevice, stream));
-  }
-  HIP_TRY(hipMemcpyAsync(d_keys.p, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, stream));
-  const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
-  if (P > 0 && K > 0)
-    HIP_TRY(ci::comp_launch_regression(stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
-                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
-  ci::PlaceboBlocksSimArgs ab;
-  ci::PlaceboSimArgs& a = ab.s;
-  a.q.p.N = N; a.q.p.T = T;
-  a.q.p.y = s->y.p; a.q.p.mask = s->mask.p; a.q.p.season_change = s->season_change.p; a.q.p.series_T = d_series_T;
-  a.q.p.obs = s->o_obs.p; a.q.p.lscale = s->o_lscale.p; a.q.p.sscale = s->o_sscale.p; a.q.p.drift = s->o_drift.p;
-  a.q.p.init = s->pred_init.p; a.q.p.scales = d_scale; a.q.p.shifts = d_shift;
-  a.q.p.reg = P > 0 ? w.cum.p : nullptr;
-  a.q.p.out = w.value.p; a.q.p.ll = nullptr;
-  a.q.O = O;
-  a.b0 = 0; a.kept = pb.num_results; a.chain_offset = (uint32_t)pb.chain_offset; a.keys = d_keys.p;
-  a.counted = d_cnt;
-  if (blocks) ab.m = pred_block_model(pb);
-  // at most B entries at a time: [B * O, N] with O <= T fits `value`
-  for (int c0 = 0; c0 < K; c0 += chunk) {
-    const int c1 = K - c0 < chunk ? K : c0 + chunk;
-    a.q.series_of = d_members + c0; a.q.origins = d_origins + (size_t)c0 * O; a.q.horizon = d_horizon + c0;
-    if (blocks) HIP_TRY(ci::placebo_blocks_sim_entries_launch(stream, c1 - c0, link, ab));
-    else HIP_TRY(ci::placebo_sim_entries_launch(stream, c1 - c0, pb.has_slope, NS, link, a));
-    HIP_TRY(ci::placebo_pool_totals_launch(stream, N, O, G, c0, c1, d_off, d_weights, w.value.p, d_acc));
-  }
-  HIP_TRY(hipMemcpyAsync(out, d_acc, acc_n * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (stats) {
-    // whole groups, as many as `value` holds: (B * T / O) * O rows, at least O
-    const size_t per_pass = ((size_t)B * T / O) * O;
-    for (size_t r0 = 0; r0 < rows; r0 += per_pass) {
-      const size_t nr = rows - r0 < per_pass ? rows - r0 : per_pass;
-      HIP_TRY(hipMemcpyAsync(w.value.p, d_acc + r0 * N, nr * N * sizeof(double), hipMemcpyDeviceToDevice, stream));
-      if (predicted_mean) HIP_TRY(ci::comp_launch_row_stats(stream, nr, N, w.value.p, d_mean + r0, nullptr));
-      if (total_order)
-        HIP_TRY(launch_select(stream, N, O, (int)nr, R, w.ranks.p, w.value.p, nullptr, d_order + r0 * R, nullptr));
-      if (spread_mean || below) {
-        HIP_TRY(ci::placebo_sim_seen_launch(stream, nr, N, w.value.p, d_seen + r0, d_counted + r0,
-                                            below ? d_below + r0 : nullptr, spread_mean != nullptr));
-        if (spread_mean) HIP_TRY(ci::comp_launch_row_stats(stream, nr, N, w.value.p, d_spread + r0, nullptr));
-      }
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (predicted_mean) HIP_TRY(hipMemcpy(predicted_mean, d_mean, rows * sizeof(double), hipMemcpyDeviceToHost));
-  if (spread_mean) HIP_TRY(hipMemcpy(spread_mean, d_spread, rows * sizeof(double), hipMemcpyDeviceToHost));
-  if (below) HIP_TRY(hipMemcpy(below, d_below, rows * sizeof(double), hipMemcpyDeviceToHost));
-  if (total_order) HIP_TRY(hipMemcpy(total_order, d_order, rows * R * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int ci_session_pool_simulated_placebo(ci_session* s, const double* scale, const double* shift,
-                                      int32_t num_groups, const int32_t* offsets, const int32_t* members,
-                                      const double* weights, int32_t max_origins, const int32_t* origins,
-                                      const int32_t* horizon, int32_t link, const double* init, double* out,
-                                      const double* seen, const int32_t* counted, int32_t num_ranks,
-                                      const int32_t* ranks, double* predicted_mean, double* spread_mean,
-                                      double* below, double* total_order) {
-  return pool_simulated_placebo(s, false, scale, shift, num_groups, offsets, members, weights, max_origins,
-                                origins, horizon, link, init, out, seen, counted, num_ranks, ranks,
-                                predicted_mean, spread_mean, below, total_order, 0);
-}
-
-int ci_session_pool_simulated_placebo_blocks(ci_session* s, const double* scale, const double* shift,
-                                             int32_t num_groups, const int32_t* offsets, const int32_t* members,
-                                             const double* weights, int32_t max_origins, const int32_t* origins,
-                                             const int32_t* horizon, int32_t link, const double* init, double* out,
-                                             const double* seen, const int32_t* counted, int32_t num_ranks,
-                                             const int32_t* ranks, double* predicted_mean, double* spread_mean,
-                                             double* below, double* total_order) {
-  return pool_simulated_placebo(s, true, scale, shift, num_groups, offsets, members, weights, max_origins,
-                                origins, horizon, link, init, out, seen, counted, num_ranks, ranks,
-                                predicted_mean, spread_mean, below, total_order, 0);
-}
-
-int ci_test_session_pool_simulated_placebo(ci_session* s, int32_t blocks, const double* scale, const double* shift,
-                                           int32_t num_groups, const int32_t* offsets, const int32_t* members,
-                                           const double* weights, int32_t max_origins, const int32_t* origins,
-                                           const int32_t* horizon, int32_t link, const double* init, double* out,
-                                           const double* seen, const int32_t* counted, int32_t num_ranks,
-                                           const int32_t* ranks, double* predicted_mean, double* spread_mean,
-                                           double* below, double* total_order, int32_t chunk_entries) {
-  if (!s) return fail("NULL argument");
-  if (chunk_entries < 1)
-    return fail("chunk_entries must be in [1, %d] (the session's series), got %d", s->pb.num_series, chunk_entries);
-  return pool_simulated_placebo(s, blocks != 0, scale, shift, num_groups, offsets, members, weights, max_origins,
-                                origins, horizon, link, init, out, seen, counted, num_ranks, ranks,
-                                predicted_mean, spread_mean, below, total_order, chunk_entries);
 }
 
 int ci_summarize_draws(int32_t device, int32_t num_draws, int32_t T, const float* trajectories,

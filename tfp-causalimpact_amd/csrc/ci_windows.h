@@ -28,6 +28,11 @@ namespace ci {
 
 constexpr int WIN_TILE = 64;
 
+// The launch (ci_windows.hip): window_totals_kernel over W windows of B series under `link`.
+hipError_t windows_launch(hipStream_t stream, int link, int B, int N, int T, int W, const float* traj,
+                          const double* obs, const double* scales, const double* shifts,
+                          const int* first, const int* count, double* out);
+
 // grid (ceil(N/64), W, B), one wavefront per workgroup: (draw tile, window, series).
 // ALIGNED (T % 4 == 0 and a 16-byte aligned base: every row then starts on a 16-byte boundary):
 // float4 loads, 16 lanes per row and 4 rows per instruction; otherwise one float per lane.

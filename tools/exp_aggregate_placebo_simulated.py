@@ -15,10 +15,11 @@ With `--seasons MODEL` the same for a model the one-lane filter does not take
 (`Session.pool_simulated_placebo_blocks` next to `Session.simulate_placebo_blocks`): 64 series by
 default, the host twin on `--share` series with `--twin-origins` origins each.
 
-With `--baseline-root DIR` (a built checkout of the parent commit) the stock paths
-`Session.simulate_placebo`, `Session.simulate_placebo_blocks` and `Session.pool_placebo`, parent and
-branch alternating, one child process per run, five runs each, with the checksum of their outputs;
-written to `--stock-out`.
+With `--baseline-root DIR` (a built checkout of the parent commit) the stock paths -- the device calls
+of `Session.summarize_predictions`, `summarize_placebo`, `simulate_placebo`, `pool_placebo` and
+`pool_simulated_placebo` on the 512 series, and of their _blocks builds on 64 series of the
+weekly+monthly model -- parent and branch alternating, one child process per session and run, five
+runs each, with the checksum of their outputs; written to `--stock-out`.
 
 Prints one JSON line per leg: wall-clock ms of every run, their median and their spread (max - min).
 
@@ -133,52 +134,65 @@ def checksum(got):
 
 
 def stock_child(a, values, index, pre, post):
-  """One run of a stock path, `--runs` times after a warm-up, and the checksum of its outputs."""
-  blocks = a.child == "simulate_placebo_blocks"
+  """One run of the stock paths of one session -- `--child one_lane`: the five Kalman-filter entries;
+  `--child blocks`: their _blocks builds on the weekly+monthly model -- each `--runs` times after a
+  warm-up, and the checksum of its outputs: one JSON line per entry."""
+  blocks = a.child == "blocks"
   sess, w = open_session("weekly+monthly" if blocks else None, values, index, pre, post, a.draws, a.series)
+  sfx = "_blocks" if blocks else ""
   try:
     sess.run()
     prep = w["prep"]
-    sc, sh = prep.outcome_sd, prep.outcome_mean
-    if a.child == "pool_placebo":
-      call = lambda: sess.pool_placebo(sc, sh, w["groups"], w["origins"], int(w["horizon"][0]), seen=w["seen"])   # pylint: disable=unnecessary-lambda-assignment
-    else:
-      call = lambda: sess.simulate_placebo(sc, sh, w["origins"], w["horizon"], _native.LINK_LOG, w["series_seen"],   # pylint: disable=unnecessary-lambda-assignment
-                                           w["ranks"], blocks=blocks)
-    got = call()                                              # warm-up: the scratch
-    times = []
-    for _ in range(a.runs):
-      t0 = time.perf_counter()
-      got = call()
-      times.append((time.perf_counter() - t0) * 1e3)
-    print(json.dumps(dict(median_ms=statistics.median(times), all_ms=[round(t, 3) for t in times],
-                          checksum=checksum(got))), flush=True)
+    sc, sh, H = prep.outcome_sd, prep.outcome_mean, int(w["horizon"][0])
+    calls = {
+        "summarize_predictions" + sfx: lambda: getattr(sess, "summarize_predictions" + sfx)(sc, sh, w["ranks"]),
+        "summarize_placebo" + sfx: lambda: getattr(sess, "summarize_placebo" + sfx)(sc, sh, w["origins"], w["horizon"]),
+        "simulate_placebo" + sfx: lambda: sess.simulate_placebo(sc, sh, w["origins"], w["horizon"], _native.LINK_LOG,
+                                                                w["series_seen"], w["ranks"], blocks=blocks),
+        "pool_placebo" + sfx: lambda: getattr(sess, "pool_placebo" + sfx)(sc, sh, w["groups"], w["origins"], H,
+                                                                          seen=w["seen"]),
+        "pool_simulated_placebo" + sfx: lambda: sess.pool_simulated_placebo(
+            sc, sh, w["groups"], w["origins"], H, _native.LINK_LOG, None, w["seen"], w["counted"], w["ranks"],
+            blocks=blocks),
+    }
+    for name, call in calls.items():
+      got = call()                                            # warm-up: the scratch
+      times = []
+      for _ in range(a.runs):
+        t0 = time.perf_counter()
+        got = call()
+        times.append((time.perf_counter() - t0) * 1e3)
+      print(json.dumps(dict(entry=name, median_ms=statistics.median(times), all_ms=[round(t, 3) for t in times],
+                            checksum=checksum(got))), flush=True)
   finally:
     sess.close()
 
 
-STOCK = (("simulate_placebo", 512), ("simulate_placebo_blocks", 64), ("pool_placebo", 512))
+STOCK = (("one_lane", 512), ("blocks", 64))
 
 
 def stock_main(a):
   """Parent and branch alternating, the parent first in each round; one child process per run."""
-  lines = []
+  lines, got = [], {}
   for child, series in STOCK:
-    got = []
     for run in range(1, 6):
       for tree, root in (("parent", a.baseline_root), ("branch", ROOT)):
         cmd = [sys.executable, os.path.abspath(__file__), "--root", root, "--child", child, "--series", str(series),
                "--steps", str(a.steps), "--covariates", str(a.covariates), "--draws", str(a.draws), "--runs", str(a.runs)]
-        one = json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True).stdout.strip().splitlines()[-1])
-        got.append((tree, one))
-        lines.append(json.dumps(dict(tree=tree, run=run, leg=f"Session.{child}, {series} series, stock path", **one)))
-        print(lines[-1], flush=True)
-    parent = [g["median_ms"] for t, g in got if t == "parent"]
-    branch = [g["median_ms"] for t, g in got if t == "branch"]
+        out = subprocess.run(cmd, check=True, capture_output=True, text=True).stdout.strip().splitlines()
+        for one in (json.loads(l) for l in out if l.startswith("{")):
+          entry = one.pop("entry")
+          got.setdefault((entry, series), []).append((tree, one))
+          lines.append(json.dumps(dict(tree=tree, run=run, leg=f"Session.{entry}, {series} series, stock path", **one)))
+          print(lines[-1], flush=True)
+  for (entry, series), runs in got.items():
+    parent = [g["median_ms"] for t, g in runs if t == "parent"]
+    branch = [g["median_ms"] for t, g in runs if t == "branch"]
     lines.append(json.dumps(dict(
-        leg=f"Session.{child}", series=series, parent_median_ms=statistics.median(parent), parent_min_ms=min(parent),
+        leg=f"Session.{entry}", series=series, parent_median_ms=statistics.median(parent), parent_min_ms=min(parent),
         parent_max_ms=max(parent), branch_median_ms=statistics.median(branch), branch_min_ms=min(branch),
-        branch_max_ms=max(branch), checksums_equal=len({g["checksum"] for _, g in got}) == 1,
+        branch_max_ms=max(branch), checksums_equal=len({g["checksum"] for _, g in runs}) == 1,
+        ranges_overlap=min(branch) <= max(parent) and min(parent) <= max(branch),
         branch_median_inside_parent_range=min(parent) <= statistics.median(branch) <= max(parent))))
     print(lines[-1], flush=True)
   with open(a.stock_out, "w", encoding="utf-8") as f:
