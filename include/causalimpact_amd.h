@@ -278,6 +278,49 @@ int ci_session_kernel_name(const ci_session* session, char* buf, int32_t buflen)
 int ci_session_profile(ci_session* session, int enable, int64_t* cycles16);
 int ci_session_destroy(ci_session* session);
 
+/* A session MADE FROM DRAWS: what the prediction-error and placebo entries read -- the data and the
+ * pooled parameter draws of B fits -- uploaded from the host, so that every route that holds its draws
+ * there (float64 fits, HMC fits, fits pooled over devices, batches fitted series by series) runs the
+ * filters of a fit's own session.  The filters never read the fit itself.
+ *   problem   geometry (T, P, has_slope, the blocks), num_chains C, num_results S, seed, chain_offset,
+ *             series_offset, flags (CI_FLAG_SHARED_SERIES_STREAMS), device, as of the fit; num_warmup is
+ *             not read.  Chains pooled from several devices are ONE session with chain_offset 0.
+ *   y, mask, X, season_change, params[B]   as ci_session_create takes them
+ *   observation_noise_scale, level_scale, slope_scale [B,C,S], seasonal_drift_scales [B,C,S,K],
+ *   weights [B,C,S,P]   the draws, chain-major, in the layout ci_session_fetch delivers; slope_scale
+ *             is read only with has_slope, seasonal_drift_scales with K > 0, X and weights with P > 0
+ *             (each may be NULL otherwise)
+ * ci_session_create_from_draws takes float32 arrays: given the draws ci_session_fetch delivered and
+ * the fit's problem record, every entry below returns the bits of the fit's own session.
+ * ci_session_create_from_draws_f64 takes float64 arrays and filters them as they are, through the
+ * float64-input builds of the same kernels (every value is widened to double once, where it is
+ * loaded, so float32 values passed as float64 give the float32 entry's bits).
+ * Checked on the host before the first device call: NULL pointers, the problem record, an unmasked y
+ * that is not finite ("y[b, t] is not finite but unmasked"), and every scale draw, which must be
+ * finite and not negative (the message names the array, the series and the pooled draw n = c * S + s).
+ * The session is not ragged.  It holds no fit workspace, no trajectories and no latent draws.
+ * It is accepted by ci_session_summarize_predictions[_blocks], ci_session_summarize_placebo[_blocks],
+ * ci_session_simulate_placebo[_blocks], ci_session_pool_placebo[_blocks],
+ * ci_session_pool_simulated_placebo[_blocks] (unchanged signatures and checks; the simulated entries
+ * address Philox as on a fit's session: series key, chain_offset + c, draw, slot, step), their ci_test_
+ * entries and ci_session_destroy.  Every entry that needs a fit -- ci_session_run, _run_streamed,
+ * _fetch, _summarize, _summarize_components, _summarize_windows, _summarize_paths, _pool_trajectories,
+ * _pool_event_trajectories, _value_mean, _profile, _kernel_name, _algorithmic_bytes and
+ * ci_comm_session_all_gather -- refuses it before any device call: ci_last_error names the entry and
+ * says that the session was made from draws. */
+int ci_session_create_from_draws(const ci_problem* problem, const float* y, const uint8_t* mask,
+                                 const float* X, const uint8_t* season_change,
+                                 const ci_series_params* params, const float* observation_noise_scale,
+                                 const float* level_scale, const float* slope_scale,
+                                 const float* seasonal_drift_scales, const float* weights,
+                                 ci_session** session);
+int ci_session_create_from_draws_f64(const ci_problem* problem, const double* y, const uint8_t* mask,
+                                     const double* X, const uint8_t* season_change,
+                                     const ci_series_params* params,
+                                     const double* observation_noise_scale, const double* level_scale,
+                                     const double* slope_scale, const double* seasonal_drift_scales,
+                                     const double* weights, ci_session** session);
+
 /* On-device summarisation of the pooled posterior-predictive draws of a finished run, for all
  * B series of the session at once: replaces the T x (C*S) pandas/numpy work of _compute_impact
  * (causalimpact_lib.py:793-837 effect trajectories, posterior_processing.py:25-60 quantiles,

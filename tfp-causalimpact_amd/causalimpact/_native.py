@@ -113,6 +113,10 @@ def load():
   L.ci_session_create_ragged_seasonal.argtypes = [C.POINTER(Problem), C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.POINTER(SeriesParams), C.POINTER(C.c_void_p)]
+  for name in ("ci_session_create_from_draws", "ci_session_create_from_draws_f64"):
+    if hasattr(L, name):                               # (additive: a library built before it lacks it)
+      getattr(L, name).argtypes = ([C.POINTER(Problem)] + [C.c_void_p] * 4 + [C.POINTER(SeriesParams)] +
+                                   [C.c_void_p] * 5 + [C.POINTER(C.c_void_p)])
   L.ci_session_run.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
   L.ci_session_fetch.argtypes = [C.c_void_p, C.POINTER(Outputs)]
   L.ci_session_algorithmic_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -237,7 +241,8 @@ def exported_symbols() -> Sequence[str]:
   return ("ci_last_error", "ci_abi_version", "ci_device_count", "ci_series_stream_key", "ci_device_synchronize", "ci_pool_trim", "ci_host_alloc",
           "ci_host_free", "ci_fit_gibbs", "ci_fit_gibbs_f64", "ci_fit_gibbs_f64_kernel_ms",
           "ci_fit_gibbs_f64_route",
-          "ci_session_create", "ci_session_create_ragged", "ci_session_create_ragged_seasonal", "ci_session_run", "ci_session_run_streamed", "ci_session_fetch",
+          "ci_session_create", "ci_session_create_ragged", "ci_session_create_ragged_seasonal",
+          "ci_session_create_from_draws", "ci_session_create_from_draws_f64", "ci_session_run", "ci_session_run_streamed", "ci_session_fetch",
           "ci_session_algorithmic_bytes", "ci_session_kernel_name", "ci_session_destroy",
           "ci_session_profile", "ci_ll_session_kernel_name",
           "ci_session_summarize", "ci_session_summarize_components",
@@ -1486,6 +1491,63 @@ class Session:
       pass
 
 
+DRAW_FIELDS = ("observation_noise_scale", "level_scale", "slope_scale", "seasonal_drift_scales", "weights")
+
+
+class DrawsSession(Session):
+  """A session made from draws (ci_session_create_from_draws[_f64]): the data and the pooled
+  parameter draws of B fits, uploaded from the host, for the prediction-error and placebo entries
+  alone -- `summarize_predictions`, `summarize_placebo`, `simulate_placebo`, `pool_placebo`,
+  `pool_simulated_placebo` and their `_blocks` forms, with the signatures and results they have on a
+  fit's `Session`.  Every method that needs a fit (`run`, `fetch`, `summarize`, ..) raises NativeError.
+
+  pb: the fit's problem record (geometry, chains, kept draws, seed, chain_offset, series_offset,
+  flags, device); chains pooled from several devices are one session with chain_offset 0.  y, mask
+  [B, T], X [B, T, P], season_change [K, T], params: as `Session` takes them.  draws: a dict with
+  `DRAW_FIELDS` as `Session.fetch` returns them -- [B, C, S], seasonal_drift_scales [B, C, S, K],
+  weights [B, C, S, P]; slope_scale, seasonal_drift_scales and weights may be missing where the model
+  has no slope, block or design.  dtype float32: the filters of a fit's session on these values, bit
+  for bit; float64: y, X and the draws are filtered as float64."""
+
+  summaries = ("predictions", "placebo")
+
+  def __init__(self, pb: Problem, y, mask, X, season_change, params, draws, dtype=np.float32):  # pylint: disable=super-init-not-called
+    self._lib = load()
+    self.pb = pb
+    self._h = C.c_void_p()
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+      raise ValueError(f"`dtype` must be float32 or float64, got {dt}")
+    self.dtype = dt
+    B, T, P, K = pb.num_series, pb.T, pb.P, pb.num_blocks
+    CS = (pb.num_chains, pb.num_results)
+    shapes = dict(observation_noise_scale=(B,) + CS, level_scale=(B,) + CS, slope_scale=(B,) + CS,
+                  seasonal_drift_scales=(B,) + CS + (K,), weights=(B,) + CS + (P,))
+    needed = dict(observation_noise_scale=True, level_scale=True, slope_scale=bool(pb.has_slope),
+                  seasonal_drift_scales=K > 0, weights=P > 0)
+    arrs = []
+    for k in DRAW_FIELDS:
+      a = draws.get(k)
+      if a is None or not needed[k]:
+        if needed[k]:
+          raise ValueError(f"`draws` lacks {k!r}, which this model reads")
+        arrs.append(None)
+        continue
+      a = np.asarray(a)
+      if a.shape != shapes[k]:
+        raise ValueError(f"draws[{k!r}] must be {list(shapes[k])}, got {list(a.shape)}")
+      arrs.append(np.ascontiguousarray(a, dtype=dt))
+    mask8 = np.ascontiguousarray(np.asarray(mask, dtype=bool).reshape(B, T).astype(np.uint8))
+    yd = np.ascontiguousarray(np.asarray(y, dtype=dt).reshape(B, T))
+    Xd = np.ascontiguousarray(np.asarray(X, dtype=dt).reshape(B, T, P)) if P > 0 else None
+    sc = None
+    if K > 0 and season_change is not None:
+      sc = np.ascontiguousarray(np.asarray(season_change, dtype=np.uint8).reshape(K, T))
+    name = "ci_session_create_from_draws_f64" if dt == np.dtype(np.float64) else "ci_session_create_from_draws"
+    _check(_symbol(self._lib, name)(C.byref(pb), _ptr(yd), _ptr(mask8), _ptr(Xd), _ptr(sc), params,
+                                    *[_ptr(a) for a in arrs], C.byref(self._h)))
+
+
 def kalman_loglik(pb: Problem, params, y, mask, X, theta) -> np.ndarray:
   """Log-likelihood l(theta_e) for every row theta_e = (sigma_obs, sigma_level, sigma_slope,
   weights...) of `theta` (row H of SURVEY.md section 8)."""
@@ -1650,6 +1712,7 @@ class BatchLogLikSession(LogLikSession):
 
   def __init__(self, pb: Problem, params, y, mask, X, max_evals: int = 1):   # pylint: disable=super-init-not-called
     self._lib = load()
+    self.problem = pb      # (seed, series_offset, flags, device: what keys the series' streams)
     self.B, self.T, self.P, self.D, self.K = pb.num_series, pb.T, pb.P, 2 if pb.has_slope else 1, 0
     self.num_seasons = []
     self.max_evals = int(max_evals)

@@ -1611,12 +1611,14 @@ def _new_placebo_chain(launches, pp: PlaceboPoolPlan, observed: Dict[str, np.nda
   """The `_PlaceboChain` of a one-launch fit: analytic, or with `Placebo(pool=True)` simulated -- every
   series on the stream its fit runs on (`_launch_request`'s)."""
   sim = _simulated_pool(placebo, fit.link, alpha)
+  on_device = bool(getattr(fit.inference_options, "summarize_on_device", True))
   if sim is None:
-    return _PlaceboChain(launches, pp, observed["seen_sum"])
+    return _PlaceboChain(launches, pp, observed["seen_sum"], on_device=on_device)
   num_chains = fit.inference_options.num_chains
   streams = lambda ids: [lib.placebo_stream(fit.seed, None if fit.shared_streams else int(b), range(num_chains))   # pylint: disable=unnecessary-lambda-assignment
                          for b in ids]
-  return _PlaceboChain(launches, pp, observed["seen_sum"], sim, observed["n_counted"].astype(np.int32), streams)
+  return _PlaceboChain(launches, pp, observed["seen_sum"], sim, observed["n_counted"].astype(np.int32), streams,
+                       on_device=on_device)
 
 
 def placebo_pool_route(sess, has_slope: bool, num_seasons: Sequence[int], simulated: bool = False) -> str:
@@ -1651,12 +1653,14 @@ class _PlaceboChain(_PoolChain):
   simulated: Optional[SimulatedPool] = None      # (the analytic chain, unless `__init__` says otherwise)
   counted: Optional[np.ndarray] = None
   streams = None
+  on_device = True
 
   def __init__(self, launches, pp: PlaceboPoolPlan, seen: np.ndarray, simulated: Optional[SimulatedPool] = None,
-               counted: Optional[np.ndarray] = None, streams=None):
+               counted: Optional[np.ndarray] = None, streams=None, on_device: bool = True):
     super().__init__(launches, pp.csr)
     self.pp, self.seen = pp, seen
     self.simulated, self.counted, self.streams = simulated, counted, streams
+    self.on_device = on_device     # `InferenceOptions.summarize_on_device`: off, a session without entries filters in numpy
     self.means: Optional[Dict[str, np.ndarray]] = None
 
   def groups_of(self, ids: Sequence[int]):
@@ -1676,12 +1680,20 @@ class _PlaceboChain(_PoolChain):
     """(pool, finish) of the open session `sess`: pool(groups, origins, horizon, init) -> acc of the
     groups handed in, finish(acc, seen) -> the three means.  `placebo_pool_route` chooses: a session
     whose model the one-lane filter takes runs both through `pool_placebo`, one whose model the
-    block-model filter takes through `pool_placebo_blocks`; any other (HMC, a state beyond 64) filters
-    its members in numpy from the parameter draws it holds (`lib._placebo_entry_host`) and pools with
-    the host twin."""
+    block-model filter takes through `pool_placebo_blocks`; a session without the entries (HMC) through
+    those of a `_native.DrawsSession` made from its parameter draws, which the pair then holds for
+    `step` to close; any other (a state beyond 64, `summarize_on_device=False`) filters its members in
+    numpy from the parameter draws (`lib._placebo_entry_host`) and pools with the host twin."""
     if self.simulated is not None:
       return self._simulated_session_pool(sess, scale, shift, series_inputs, ids)
     route = placebo_pool_route(sess, series_inputs[0].has_slope, series_inputs[0].num_seasons)
+    draws, held = None, ()
+    if route == "host":
+      # a session without the entries (HMC): a session made from its parameter draws has them
+      draws = sess.fetch(list(lib._PARAMETER_DRAWS))               # pylint: disable=protected-access
+      drawn, blocks = lib._draws_session_beside(sess, series_inputs, draws, self.on_device)   # pylint: disable=protected-access
+      if drawn is not None:
+        sess, held, route = drawn, (drawn,), "blocks" if blocks else "one_lane"
     if route != "host":
       T, B = int(sess.pb.T), int(sess.pb.num_series)
       entry = sess.pool_placebo if route == "one_lane" else sess.pool_placebo_blocks
@@ -1700,8 +1712,7 @@ class _PlaceboChain(_PoolChain):
           for k in out:
             out[k][:, j:j + w] = got[k]
         return out
-      return pool, finish
-    draws = sess.fetch(list(lib._PARAMETER_DRAWS))                 # pylint: disable=protected-access
+      return (pool, finish) + held
 
     def host_pool(groups, origins, horizon, init):
       csr = _native.groups_csr(groups, len(series_inputs))
@@ -1720,6 +1731,12 @@ class _PlaceboChain(_PoolChain):
     `_native.pool_simulated_placebo_host`, `SimulatedPool.finish_host`).  ids: the launch's positions."""
     sim, counted = self.simulated, self.counted
     route = placebo_pool_route(sess, series_inputs[0].has_slope, series_inputs[0].num_seasons, simulated=True)
+    draws, held = None, ()
+    if route == "host":
+      draws = sess.fetch(list(lib._PARAMETER_DRAWS))               # pylint: disable=protected-access
+      drawn, blocks = lib._draws_session_beside(sess, series_inputs, draws, self.on_device)   # pylint: disable=protected-access
+      if drawn is not None:
+        sess, held, route = drawn, (drawn,), "blocks" if blocks else "one_lane"
     if route != "host":
       T, B = int(sess.pb.T), int(sess.pb.num_series)
       num_draws = int(sess.pb.num_chains * sess.pb.num_results)
@@ -1742,8 +1759,7 @@ class _PlaceboChain(_PoolChain):
           for k in out:
             out[k][..., j:j + w] = got[k]
         return sim.means(out, ranks, num_draws)
-      return pool, finish
-    draws = sess.fetch(list(lib._PARAMETER_DRAWS))                 # pylint: disable=protected-access
+      return (pool, finish) + held
     streams = self.streams(ids)
 
     def host_pool(groups, origins, horizon, init):
@@ -1758,7 +1774,7 @@ class _PlaceboChain(_PoolChain):
   def step(self, launch, pool):            # pylint: disable=arguments-renamed
     """The step of `launch`, its session still open; pool: the pair of `session_pool`.  Only the
     groups with a member in the launch are added to; the last launch of the list finishes all."""
-    pool, finish = pool
+    pool, finish, *held = pool             # held: a draws session `session_pool` opened for the pair
     k = self._index[int(launch[2][0])]
     try:
       acc = self._futures[k - 1].result() if k else None
@@ -1783,6 +1799,9 @@ class _PlaceboChain(_PoolChain):
     except BaseException as e:
       self.fail(launch, e)
       raise
+    finally:
+      for one in held:
+        one.close()
 
 
 def _take_aggregate_placebo(res, pp: PlaceboPoolPlan, names, means: Optional[Dict[str, np.ndarray]],
@@ -2127,7 +2146,7 @@ def _launch_request(fit: _Fit, ids, observed, flags) -> lib.SummaryRequest:
       placebo=None if fit.placebo_origins is None else lib.PlaceboPart(
           *own, fit.placebo_origins[ids], fit.placebo_horizon[ids], **simulated),
       paths=None if fit.paths is None else lib.Windows(fit.paths.first[ids], fit.paths.count[ids]),
-      path_ranks=fit.path_ranks, link=fit.link)
+      path_ranks=fit.path_ranks, link=fit.link, on_device=bool(getattr(io, "summarize_on_device", True)))
 
 
 def _series_inputs(fit: _Fit, ids, season_change, num_seasons) -> Optional[List[lib.SeriesInputs]]:
@@ -2147,7 +2166,9 @@ def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None,
   the latent paths and the predictive trajectories on the device): consecutive positions of a batch,
   series b keyed by positions[0] + b.  Its session (`_native.BatchLogLikSession`) has the effect
   summary and the window totals; it keeps no latent draws, hence no component summary, and prediction
-  errors and placebo forecasts are filtered in numpy from the parameter draws."""
+  errors and placebo forecasts are filtered from its parameter draws: by one `_native.DrawsSession`
+  over the launch's series (`lib.take_summaries`, `_PlaceboChain.session_pool`), in numpy with
+  `InferenceOptions(summarize_on_device=False)`."""
   from causalimpact import _hmc  # pylint: disable=import-outside-toplevel
   dev, _, ids = launch
   ids = np.asarray(ids, dtype=np.int64)
@@ -2158,7 +2179,7 @@ def _run_hmc_launch(launch, fit: _Fit, chain: Optional[_PoolChain] = None,
     record = lib.take_summaries(sess, _launch_request(fit, ids, fit.observed[ids], fit.flags), inputs)
     if chain is not None:
       chain.step(launch, chain.session_pool(sess, fit.scale[ids], fit.shift[ids]))
-    if placebo_chain is not None:          # (no filter on this session: numpy, from its parameter draws)
+    if placebo_chain is not None:          # (no filter on this session: a session made from its parameter draws)
       placebo_chain.step(launch, placebo_chain.session_pool(
           sess, fit.own_scale[ids], fit.own_shift[ids], inputs, list(fit.observed[ids]), ids))
     return record

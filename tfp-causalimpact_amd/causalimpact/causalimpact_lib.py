@@ -1733,6 +1733,94 @@ def _host_placebo_summaries(inputs: Sequence[SeriesInputs], draws, part: Placebo
   return out
 
 
+def draws_filter_route(has_slope: bool, num_seasons: Sequence[int], on_device: bool = True) -> str:
+  """Where prediction errors and placebo forecasts are filtered from parameter draws that lie on the
+  host (float64 fits, HMC fits, chains pooled from several devices, the one-launch HMC batch):
+  "one_lane" -- a `_native.DrawsSession` and the entries of `device_predictions_supported` --, "blocks"
+  -- the same session and the `_blocks` entries (`device_block_predictions_supported`: a state of at
+  most `PREDICTION_MAX_STATE` components) --, or "host": the numpy twins, with
+  `InferenceOptions(summarize_on_device=False)` and for any wider state."""
+  if not on_device:
+    return "host"
+  if device_predictions_supported(num_seasons):
+    return "one_lane"
+  if device_block_predictions_supported(has_slope, num_seasons):
+    return "blocks"
+  return "host"
+
+
+def open_draws_session(inputs: Sequence[SeriesInputs], draws, *, seed, device: int = 0, series_offset: int = 0,
+                       shared_streams: bool = True):
+  """The `_native.DrawsSession` of the n series `inputs` -- one model, one length -- and their
+  parameter draws {name: [n, C, S, ...]} (`_PARAMETER_DRAWS`; a name the model lacks may be missing)
+  on `device`.  Float64 where the sampler read float64 (`SeriesInputs.seen`) or handed float64 draws,
+  else float32: the values the numpy twins read, as they read them.  seed, series_offset,
+  shared_streams: what keys the series' random streams (`placebo_stream`: series i of the session is
+  series id series_offset + i, or the seed itself with shared_streams); the chains are the global
+  chains 0 .. C - 1 in pooling order.  None where the series do not share a length."""
+  one = inputs[0]
+  num_steps = one.y.shape[0]
+  if any(i.y.shape[0] != num_steps for i in inputs):
+    return None
+  used = {k: np.asarray(draws[k]) for k in _PARAMETER_DRAWS if draws.get(k) is not None}
+  wide = one.seen == np.float64 or any(v.dtype == np.float64 for v in used.values())
+  num_chains, num_results = used["observation_noise_scale"].shape[1:3]
+  P = 0 if one.design is None else one.design.shape[1]
+  if P == 0:
+    used.pop("weights", None)
+  if not one.num_seasons:
+    used.pop("seasonal_drift_scales", None)
+  pb = _native.make_problem(
+      T=num_steps, P=P, has_slope=one.has_slope, num_seasons=one.num_seasons, num_warmup=0,
+      num_results=num_results, num_chains=num_chains, num_series=len(inputs), seed=seed, device=device,
+      flags=_native.FLAG_SHARED_SERIES_STREAMS if shared_streams else 0, series_offset=series_offset)
+  return _native.DrawsSession(
+      pb, np.stack([i.y.astype(i.seen) for i in inputs]), np.stack([i.mask for i in inputs]),
+      None if P == 0 else np.stack([i.design.astype(i.seen) for i in inputs]), one.season_change,
+      _native.make_params([i.params for i in inputs]), used, dtype=np.float64 if wide else np.float32)
+
+
+def _draws_session_beside(sess, inputs: Sequence[SeriesInputs], draws, on_device: bool):
+  """(`open_draws_session`, blocks) for the series of the open session `sess`, which has no filter
+  entries of its own (the one-launch HMC batch), keyed as `sess` keys its series; (None, False): the
+  numpy twins (`draws_filter_route`; a session that has the entries and came here all the same has
+  a model they do not take, or a library without one of them)."""
+  origin = getattr(sess, "problem", None) or getattr(sess, "pb", None)
+  route = draws_filter_route(inputs[0].has_slope, inputs[0].num_seasons, on_device)
+  if origin is None or route == "host" or {"predictions", "placebo"} <= set(getattr(sess, "summaries", ())):
+    return None, False
+  drawn = open_draws_session(
+      inputs, draws, seed=(int(origin.seed[0]), int(origin.seed[1])), device=int(origin.device),
+      series_offset=int(origin.series_offset),
+      shared_streams=bool(origin.flags & _native.FLAG_SHARED_SERIES_STREAMS))
+  return drawn, route == "blocks"
+
+
+def _placebo_entry_device(drawn, blocks: bool, one: "SeriesInputs", scale, shift, observed, origins, horizon,
+                          simulated=None) -> Dict:
+  """`_placebo_entry_host` -- with simulated = (link, stream) `_placebo_entry_simulated_host` -- through
+  the one-series draws session `drawn`: the group table of one group with this member at weight 1,
+  whose accumulators are 0 + 1 * term, the member's own terms."""
+  origins = np.asarray(origins).reshape(-1)
+  link = simulated[0] if simulated is not None else 0
+  seen = _placebo_entry_seen(one, scale, shift, observed, origins, horizon, link)
+  num_draws = drawn.pb.num_chains * drawn.pb.num_results
+  width = int((origins >= 0).sum())
+  planes = 1 if simulated is not None else 2
+  acc = np.zeros((origins.size, planes, num_draws))
+  if width:
+    if simulated is not None:
+      entry = drawn.pool_simulated_placebo_blocks if blocks else drawn.pool_simulated_placebo
+      got = entry(scale, shift, [{0: 1.0}], [{0: origins[:width]}], [int(horizon)], link)["acc"]
+      acc[:width, 0] = got[0]
+    else:
+      entry = drawn.pool_placebo_blocks if blocks else drawn.pool_placebo
+      acc[:width] = entry(scale, shift, [{0: 1.0}], [{0: origins[:width]}], [int(horizon)])["acc"][0]
+  if simulated is not None:
+    return dict(totals=acc[:, 0], **seen)
+  return dict(s=acc[:, 0], v=acc[:, 1], **seen)
+
+
 def _device_placebo_summaries(sess, part: PlaceboPart, blocks: bool = False):
   """The placebo summary {name: [n, O]} of an open session (`summarize_placebo`, with `blocks`
   `summarize_placebo_blocks`): the launch's own origin slots (never more than its steps), the horizon
@@ -1914,9 +2002,11 @@ def take_summaries(sess, request: SummaryRequest,
   Prediction errors and placebo forecasts are filtered on the device where the session has the
   entries and `device_predictions_supported` takes the model; else by the block-model entries
   (`summarize_predictions_blocks`, `summarize_placebo_blocks`) where the session has those and
-  `device_block_predictions_supported` takes it; else in numpy from the parameter draws,
-  fetched once for both, over `series_inputs` (one per series of the session; read for these two
-  kinds only).  A placebo part with `quantiles` is the SIMULATED placebo (`simulate_placebo`,
+  `device_block_predictions_supported` takes it; else from the parameter draws, fetched once for
+  both, over `series_inputs` (one per series of the session; read for these two kinds only): a
+  session without filter entries (the one-launch HMC batch) through ONE `_native.DrawsSession` over
+  its series (`_draws_session_beside`), in numpy with `request.on_device` off, for a wider state and
+  for a session whose library lacks an entry.  A placebo part with `quantiles` is the SIMULATED placebo (`simulate_placebo`,
   `simulate_placebo_blocks`, `_placebo_simulated_host`, chosen the same way; a session without the
   entry filters on the host).  Components a session lacks stay None: the caller's business.  The scales and shifts
   map the SESSION's units to the data scale (`_request_in_internal_units`).  With `request.link` the
@@ -1943,36 +2033,43 @@ def take_summaries(sess, request: SummaryRequest,
             and hasattr(sess, "summarize_placebo_blocks")
             and device_block_predictions_supported(series_inputs[0].has_slope, series_inputs[0].num_seasons))
   on_host = filtered and not (one_lane or blocks)
+  flt = sess                               # the session that filters: this one, or one made from its draws
   if on_host:
     draws = sess.fetch(list(_PARAMETER_DRAWS))
-  if request.predictions is not None:
-    if on_host:
-      predictions = _host_prediction_summaries(series_inputs, draws, request.predictions, request.ranks)
-    else:
-      entry = sess.summarize_predictions_blocks if blocks else sess.summarize_predictions
-      predictions = entry(*request.predictions, request.ranks)
-  if request.windows is not None:
-    windows = sess.summarize_windows(request.scale, request.shift, request.observed, *request.windows,
-                                     request.ranks)
-  if request.paths is not None:
-    windows = dict(windows or {}, **_paths_record(sess.summarize_paths(
-        request.scale, request.shift, request.observed, *request.paths, request.path_ranks, want=_PATH_RECORD)))
-  if simulated:
-    part = _per_series(request.placebo, len(series_inputs))
-    num_draws = (int(np.prod(draws["observation_noise_scale"].shape[1:3])) if on_host else
-                 sess.pb.num_chains * sess.pb.num_results)
-    placebo = _simulated_placebo_summaries(
-        series_inputs, part, request.observed, num_draws,
-        _host_placebo_simulations(series_inputs, draws, part) if on_host else
-        _device_placebo_simulations(sess, part, blocks))
-  elif request.placebo is not None:
-    part = _per_series(request.placebo, len(series_inputs))
-    placebo = _with_placebo_seen(series_inputs, part, _host_placebo_summaries(series_inputs, draws, part)
-                                 if on_host else _device_placebo_summaries(sess, part, blocks))
-  if request.link:
-    effect = dict(effect, value_mean=sess.value_mean(request.scale, request.shift))
-  return SummaryRecord(effect=effect, components=components, predictions=predictions, windows=windows,
-                       placebo=placebo)
+    flt, blocks = _draws_session_beside(sess, series_inputs, draws, request.on_device)
+    on_host = flt is None
+  try:
+    if request.predictions is not None:
+      if on_host:
+        predictions = _host_prediction_summaries(series_inputs, draws, request.predictions, request.ranks)
+      else:
+        entry = flt.summarize_predictions_blocks if blocks else flt.summarize_predictions
+        predictions = entry(*request.predictions, request.ranks)
+    if request.windows is not None:
+      windows = sess.summarize_windows(request.scale, request.shift, request.observed, *request.windows,
+                                       request.ranks)
+    if request.paths is not None:
+      windows = dict(windows or {}, **_paths_record(sess.summarize_paths(
+          request.scale, request.shift, request.observed, *request.paths, request.path_ranks, want=_PATH_RECORD)))
+    if simulated:
+      part = _per_series(request.placebo, len(series_inputs))
+      num_draws = (int(np.prod(draws["observation_noise_scale"].shape[1:3])) if on_host else
+                   flt.pb.num_chains * flt.pb.num_results)
+      placebo = _simulated_placebo_summaries(
+          series_inputs, part, request.observed, num_draws,
+          _host_placebo_simulations(series_inputs, draws, part) if on_host else
+          _device_placebo_simulations(flt, part, blocks))
+    elif request.placebo is not None:
+      part = _per_series(request.placebo, len(series_inputs))
+      placebo = _with_placebo_seen(series_inputs, part, _host_placebo_summaries(series_inputs, draws, part)
+                                   if on_host else _device_placebo_summaries(flt, part, blocks))
+    if request.link:
+      effect = dict(effect, value_mean=sess.value_mean(request.scale, request.shift))
+    return SummaryRecord(effect=effect, components=components, predictions=predictions, windows=windows,
+                         placebo=placebo)
+  finally:
+    if flt is not None and flt is not sess:
+      flt.close()
 
 
 def _model_mask(ci_data) -> np.ndarray:
@@ -1993,7 +2090,9 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
   returned as None.  On every other route the draws are pooled on the host: the effect and its
   windows run the same kernels on the same values (`_native.summarize_draws`,
   `_native.window_totals_host`; left out with `request.on_device` off), prediction errors and placebo
-  forecasts are filtered in numpy, and the components stay None for the caller's pooled draws."""
+  forecasts are filtered by a session made from the pooled parameter draws (`open_draws_session` on
+  the first device; in numpy with `request.on_device` off and for a state `draws_filter_route` does
+  not take), and the components stay None for the caller's pooled draws."""
   if model is not None:
     raise NotImplementedError("custom tfp.sts models are not supported by the HIP path")
   seed_pair = _sanitize_seed(seed)
@@ -2107,29 +2206,56 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
       # ... and the path excursions, also where the effect is left to `_compute_impact`
       windows = dict(windows or {}, **_paths_record(_native.path_excursions_host(
           tr, *own, internal.observed, *internal.paths, ranks=internal.path_ranks)))
-    # the same definitions in numpy, from the parameter draws in the sampler's units
+    # the same definitions from the parameter draws in the sampler's units: filtered by the kernels of a
+    # fit's session through a session made from the draws (`draws_filter_route`), else in numpy
     draws = {k: out[k][None] for k in _PARAMETER_DRAWS}
-    if internal.predictions is not None:
-      predictions = _host_prediction_summaries(inputs, draws, internal.predictions, internal.ranks)
-    if internal.placebo is not None and internal.placebo.quantiles is not None:
-      part = _per_series(internal.placebo, 1)
-      placebo = _simulated_placebo_summaries(
-          inputs, part, internal.observed, int(np.prod(draws["observation_noise_scale"].shape[1:3])),
-          _host_placebo_simulations(inputs, draws, part))
-    elif internal.placebo is not None:
-      part = _per_series(internal.placebo, 1)
-      placebo = _with_placebo_seen(inputs, part, _host_placebo_summaries(inputs, draws, part))
+    route = "host"
+    if internal.predictions is not None or internal.placebo is not None:
+      route = draws_filter_route(local_linear_trend, num_seasons, internal.on_device)
+    drawn = None if route == "host" else open_draws_session(inputs, draws, seed=seed_pair, device=devs[0])
+    try:
+      blocks = route == "blocks"
+      if internal.predictions is not None:
+        if drawn is None:
+          predictions = _host_prediction_summaries(inputs, draws, internal.predictions, internal.ranks)
+        else:
+          entry = drawn.summarize_predictions_blocks if blocks else drawn.summarize_predictions
+          predictions = entry(*internal.predictions, internal.ranks)
+      if internal.placebo is not None and internal.placebo.quantiles is not None:
+        part = _per_series(internal.placebo, 1)
+        placebo = _simulated_placebo_summaries(
+            inputs, part, internal.observed, int(np.prod(draws["observation_noise_scale"].shape[1:3])),
+            _host_placebo_simulations(inputs, draws, part) if drawn is None else
+            _device_placebo_simulations(drawn, part, blocks))
+      elif internal.placebo is not None:
+        part = _per_series(internal.placebo, 1)
+        placebo = _with_placebo_seen(inputs, part, _host_placebo_summaries(inputs, draws, part)
+                                     if drawn is None else _device_placebo_summaries(drawn, part, blocks))
+    finally:
+      if drawn is not None:
+        drawn.close()
     record = SummaryRecord(effect=effect, predictions=predictions, windows=windows, placebo=placebo)
   if placebo_sink is not None:
     # (batch.py, pooled placebo forecasts: the per-draw terms from the parameter draws in the
     #  sampler's units, mapped to the caller's scale like every other summary)
-    pooled = _pooled_draws({k: out[k][None] for k in _PARAMETER_DRAWS}, 0)
-    if sink_simulated is not None:       # (link, stream): the simulated totals in place of the moments
-      placebo_sink(lambda origins, horizon: _placebo_entry_simulated_host(
-          inputs[0], pooled, internal.scale, internal.shift, internal.observed, origins, horizon, *sink_simulated))
-    else:
-      placebo_sink(lambda origins, horizon: _placebo_entry_host(
-          inputs[0], pooled, internal.scale, internal.shift, internal.observed, origins, horizon))
+    draws = {k: out[k][None] for k in _PARAMETER_DRAWS}
+    pooled = _pooled_draws(draws, 0)
+    route = draws_filter_route(local_linear_trend, num_seasons, internal.on_device)
+    drawn = None if route == "host" else open_draws_session(inputs, draws, seed=seed_pair, device=devs[0])
+    try:
+      if drawn is not None:                # (the same terms through the kernels of a fit's session)
+        placebo_sink(lambda origins, horizon: _placebo_entry_device(
+            drawn, route == "blocks", inputs[0], internal.scale, internal.shift, internal.observed, origins,
+            horizon, sink_simulated))
+      elif sink_simulated is not None:     # (link, stream): the simulated totals in place of the moments
+        placebo_sink(lambda origins, horizon: _placebo_entry_simulated_host(
+            inputs[0], pooled, internal.scale, internal.shift, internal.observed, origins, horizon, *sink_simulated))
+      else:
+        placebo_sink(lambda origins, horizon: _placebo_entry_host(
+            inputs[0], pooled, internal.scale, internal.shift, internal.observed, origins, horizon))
+    finally:
+      if drawn is not None:
+        drawn.close()
   if record.components is not None and cond_s != 1.0:
     # the weights on the caller's model scale, as in `samples`
     record = dataclasses.replace(record, components={

@@ -478,6 +478,7 @@ static const DevBuf<float>* field_of(const OutBufs<float>& o, int32_t field) {
 
 int ci_comm_session_all_gather(ci_comm* c, ci_session* s, int32_t field, float* recv) {
   if (!c || !s) return fail("NULL argument");
+  if (refuse_draws_session(s, "ci_comm_session_all_gather")) return 1;
   if (!s->ran) return fail("ci_comm_session_all_gather needs a finished ci_session_run");
   const DevBuf<float>* b = field_of(s->outputs(), field);
   if (!b) return fail("unknown field %d", field);

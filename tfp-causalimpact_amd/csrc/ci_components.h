@@ -29,10 +29,14 @@ hipError_t comp_launch_gather(hipStream_t stream, int B, int N, int T, int K, in
 hipError_t comp_launch_regression(hipStream_t stream, int B, int N, int T, int P, const float* Xt,
                                   const float* w, const int* series_T, const double* scales,
                                   double* out);
+// ... of float64 designs and weights (a session made from float64 draws): the F = double build.
+hipError_t comp_launch_regression_f64(hipStream_t stream, int B, int N, int T, int P, const double* Xt,
+                                      const double* w, const int* series_T, const double* scales,
+                                      double* out);
 hipError_t comp_launch_row_stats(hipStream_t stream, size_t rows, int N, const double* M,
                                  double* mean, int* nonzero);
 
-// Two of the kernels are no templates: a unit that includes them emits them.  The host units
+// One of the kernels is no template: a unit that includes it emits it.  The host units
 // (ci_session.h) take the declarations above alone.
 #ifndef CI_SEASONAL_DECL_ONLY
 
@@ -78,7 +82,8 @@ __global__ __launch_bounds__(256) void comp_gather_kernel(int N, int T, int K, i
 }
 
 // The regression term: per series a [N, P] x [P, T] product, Xt [P, T] feature-major (rows
-// contiguous over time) and w [N, P] (a tile's 64 draws are 64 P contiguous floats).  The design
+// contiguous over time) and w [N, P] (a tile's 64 draws are 64 P contiguous values), both of the
+// input type F, widened to double where they are multiplied.  The design
 // columns pass through LDS in chunks of COMP_PC: per chunk both sides are read from HBM once per
 // tile, the 16 accumulators of a thread (one draw, 16 steps) stay in registers across the chunks, so
 // every sum runs over j = 0..P-1 in ascending order.  In the inner loop a wavefront reads one X
@@ -88,17 +93,18 @@ __global__ __launch_bounds__(256) void comp_gather_kernel(int N, int T, int K, i
 // grid (ceil(T/64), ceil(N/64), B), block (64, 4).
 constexpr int COMP_PC = 32;
 
+template <class F = float>
 __global__ __launch_bounds__(256) void comp_regression_kernel(int N, int T, int P,
-                                                              const float* __restrict__ Xt_all,
-                                                              const float* __restrict__ w_all,
+                                                              const F* __restrict__ Xt_all,
+                                                              const F* __restrict__ w_all,
                                                               const int* __restrict__ series_T,
                                                               const double* __restrict__ scales,
                                                               double* __restrict__ out_all) {
-  __shared__ float Xs[COMP_PC][64];
-  __shared__ float Ws[64][COMP_PC + 1];
+  __shared__ F Xs[COMP_PC][64];
+  __shared__ F Ws[64][COMP_PC + 1];
   const size_t b = blockIdx.z;
-  const float* Xt = Xt_all + b * (size_t)P * T;
-  const float* w = w_all + b * (size_t)N * P;
+  const F* Xt = Xt_all + b * (size_t)P * T;
+  const F* w = w_all + b * (size_t)N * P;
   double* out = out_all + b * (size_t)N * T;
   const int Tb = series_T ? series_T[b] : T;
   const double scale = scales[b];
@@ -111,11 +117,11 @@ __global__ __launch_bounds__(256) void comp_regression_kernel(int N, int T, int 
     const int pc = P - j0 < COMP_PC ? P - j0 : COMP_PC;
     for (int e = tid; e < pc * 64; e += 256) {
       const int jj = e >> 6, t = t0 + (e & 63);
-      Xs[jj][e & 63] = t < Tb ? Xt[(size_t)(j0 + jj) * T + t] : 0.f;
+      Xs[jj][e & 63] = t < Tb ? Xt[(size_t)(j0 + jj) * T + t] : (F)0;
     }
     for (int e = tid; e < pc * 64; e += 256) {
       const int n = e / pc, jj = e - n * pc;
-      Ws[n][jj] = n0 + n < N ? w[(size_t)(n0 + n) * P + j0 + jj] : 0.f;
+      Ws[n][jj] = n0 + n < N ? w[(size_t)(n0 + n) * P + j0 + jj] : (F)0;
     }
     __syncthreads();
     for (int jj = 0; jj < pc; ++jj) {

@@ -17,7 +17,15 @@ hipError_t comp_launch_gather(hipStream_t stream, int B, int N, int T, int K, in
 hipError_t comp_launch_regression(hipStream_t stream, int B, int N, int T, int P, const float* Xt,
                                   const float* w, const int* series_T, const double* scales,
                                   double* out) {
-  hipLaunchKernelGGL(comp_regression_kernel, dim3((T + 63) / 64, (N + 63) / 64, B), dim3(64, 4), 0,
+  hipLaunchKernelGGL(comp_regression_kernel<float>, dim3((T + 63) / 64, (N + 63) / 64, B), dim3(64, 4), 0,
+                     stream, N, T, P, Xt, w, series_T, scales, out);
+  return hipGetLastError();
+}
+
+hipError_t comp_launch_regression_f64(hipStream_t stream, int B, int N, int T, int P, const double* Xt,
+                                      const double* w, const int* series_T, const double* scales,
+                                      double* out) {
+  hipLaunchKernelGGL(comp_regression_kernel<double>, dim3((T + 63) / 64, (N + 63) / 64, B), dim3(64, 4), 0,
                      stream, N, T, P, Xt, w, series_T, scales, out);
   return hipGetLastError();
 }

@@ -2,7 +2,8 @@
 // ci_session_summarize_predictions[_blocks] (kernels: ci_predict.h, ci_predict_blocks.h),
 // ci_session_summarize_placebo[_blocks], ci_session_simulate_placebo[_blocks],
 // ci_session_pool_placebo[_blocks], ci_session_pool_simulated_placebo[_blocks] (kernels: ci_placebo.h,
-// ci_placebo_blocks.h) and their ci_test_ entries.  A host unit: it instantiates no kernel -- the
+// ci_placebo_blocks.h) and their ci_test_ entries; and ci_session_create_from_draws[_f64], the session
+// that holds what these entries read and nothing else.  A host unit: it instantiates no kernel -- the
 // filters are launched through their units' launch functions, the order statistics through
 // launch_select of ci_summary.hip (ci_summary_host.h).
 //
@@ -93,6 +94,7 @@ static int check_link(int32_t link) {
 namespace {
 struct ForecastCall {
   int B, T, N, has_slope, NS;      // NS: the seasons of the one-lane build's block (0: none)
+  bool f64;                        // the inputs are float64 (a session made from float64 draws): the _f64 launches
   hipStream_t stream;
   SummScratch* w;                  // value: p.out; cum: p.reg; obs [B * T], then scale [B], shift [B]
   ci::PredArgs p;                  // out = `value`, ll = nullptr
@@ -116,16 +118,28 @@ static int forecast_call(ForecastCall& c, ci_session* s, bool blocks, const doub
   HIP_TRY(hipMemcpyAsync(d_scale, scale, B * sizeof(double), hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, s->stream));
   const int* d_series_T = s->ragged ? s->series_T.p : nullptr;
-  if (P > 0 && filters)
-    HIP_TRY(ci::comp_launch_regression(s->stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
-                                       s->pred_init.p + (size_t)4 * B, w.cum.p));
+  if (P > 0 && filters) {
+    if (s->f64)
+      HIP_TRY(ci::comp_launch_regression_f64(s->stream, B, N, T, P, s->Xt64.p, s->d_w64.p, d_series_T,
+                                             s->pred_init.p + (size_t)4 * B, w.cum.p));
+    else
+      HIP_TRY(ci::comp_launch_regression(s->stream, B, N, T, P, s->Xt.p, s->o_w.p, d_series_T,
+                                         s->pred_init.p + (size_t)4 * B, w.cum.p));
+  }
   c.B = B; c.T = T; c.N = N; c.has_slope = pb.has_slope; c.NS = pb.num_blocks ? pb.num_seasons[0] : 0;
   c.stream = s->stream;
   c.w = &w;
+  c.f64 = s->f64;
   ci::PredArgs& a = c.p;
   a.N = N; a.T = T;
-  a.y = s->y.p; a.mask = s->mask.p; a.season_change = s->season_change.p; a.series_T = d_series_T;
-  a.obs = s->o_obs.p; a.lscale = s->o_lscale.p; a.sscale = s->o_sscale.p; a.drift = s->o_drift.p;
+  a.mask = s->mask.p; a.season_change = s->season_change.p; a.series_T = d_series_T;
+  if (s->f64) {
+    a.y = s->y64.p;
+    a.obs = s->d_obs64.p; a.lscale = s->d_lscale64.p; a.sscale = s->d_sscale64.p; a.drift = s->d_drift64.p;
+  } else {
+    a.y = s->y.p;
+    a.obs = s->o_obs.p; a.lscale = s->o_lscale.p; a.sscale = s->o_sscale.p; a.drift = s->o_drift.p;
+  }
   a.init = s->pred_init.p; a.scales = d_scale; a.shifts = d_shift;
   a.reg = P > 0 ? w.cum.p : nullptr;
   a.out = w.value.p; a.ll = nullptr;
@@ -156,8 +170,8 @@ static int summarize_predictions(ci_session* s, bool blocks, const double* scale
   bool ll_pending = loglik != nullptr;
   auto pass = [&](int which, double* mean_dst, double* order_dst) -> int {
     ab.p.ll = ll_pending ? w.draw.p : nullptr;
-    if (blocks) HIP_TRY(ci::predict_blocks_launch(stream, B, which, ab));
-    else HIP_TRY(ci::predict_launch(stream, B, c.has_slope, c.NS, which, ab.p));
+    if (blocks) HIP_TRY((c.f64 ? ci::predict_blocks_launch_f64 : ci::predict_blocks_launch)(stream, B, which, ab));
+    else HIP_TRY((c.f64 ? ci::predict_launch_f64 : ci::predict_launch)(stream, B, c.has_slope, c.NS, which, ab.p));
     if (mean_dst) HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * T, N, w.value.p, w.obs.p, nullptr));
     if (order_dst)
       HIP_TRY(launch_select(stream, N, T, B * T, R, w.ranks.p, w.value.p, nullptr, w.order.p, nullptr));
@@ -224,8 +238,8 @@ static int summarize_placebo(ci_session* s, bool blocks, const double* scale, co
   a.p = c.p; ab.m = c.m;
   a.O = O; a.origins = d_plan.p; a.horizon = d_plan.p + (size_t)B * O;
   auto pass = [&](int which, double* mean_dst) -> int {
-    if (blocks) HIP_TRY(ci::placebo_blocks_launch(stream, B, which, ab));
-    else HIP_TRY(ci::placebo_launch(stream, B, c.has_slope, c.NS, which, a));
+    if (blocks) HIP_TRY((c.f64 ? ci::placebo_blocks_launch_f64 : ci::placebo_blocks_launch)(stream, B, which, ab));
+    else HIP_TRY((c.f64 ? ci::placebo_launch_f64 : ci::placebo_launch)(stream, B, c.has_slope, c.NS, which, a));
     HIP_TRY(ci::comp_launch_row_stats(stream, (size_t)B * O, N, w.value.p, w.obs.p, nullptr));
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(hipMemcpy(mean_dst, w.obs.p, (size_t)B * O * sizeof(double), hipMemcpyDeviceToHost));
@@ -328,8 +342,8 @@ static int simulate_placebo(ci_session* s, bool blocks, const double* scale, con
     const size_t rows = (size_t)nb * O, off = (size_t)b0 * O;
     a.b0 = b0;
     a.counted = d_counted + off;
-    if (blocks) HIP_TRY(ci::placebo_blocks_sim_launch(stream, nb, link, ab));
-    else HIP_TRY(ci::placebo_sim_launch(stream, nb, c.has_slope, c.NS, link, a));
+    if (blocks) HIP_TRY((c.f64 ? ci::placebo_blocks_sim_launch_f64 : ci::placebo_blocks_sim_launch)(stream, nb, link, ab));
+    else HIP_TRY((c.f64 ? ci::placebo_sim_launch_f64 : ci::placebo_sim_launch)(stream, nb, c.has_slope, c.NS, link, a));
     if (sim_total_stats(stream, w, rows, N, O, R, d_seen + off, d_counted + off,
                         predicted_mean ? d_mean + off : nullptr,
                         total_order ? w.order.p + (size_t)b0 * R * O : nullptr, below ? d_below + off : nullptr,
@@ -469,13 +483,14 @@ static int pool_placebo(ci_session* s, bool blocks, const double* scale, const d
     const int c1 = K - c0 < chunk ? K : c0 + chunk;
     a.series_of = t.members + c0; a.origins = t.origins + (size_t)c0 * O; a.horizon = t.horizon + c0;
     if (blocks) {
-      HIP_TRY(ci::placebo_blocks_pool_launch(stream, c1 - c0, ab));
+      HIP_TRY((c.f64 ? ci::placebo_blocks_pool_launch_f64 : ci::placebo_blocks_pool_launch)(stream, c1 - c0, ab));
       HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, 0, c0, c1, t.offsets, t.weights, w.value.p, t.acc));
       HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, 1, c0, c1, t.offsets, t.weights, d_var.p, t.acc));
       continue;
     }
     for (int which = 0; which < 2; ++which) {
-      HIP_TRY(ci::placebo_launch(stream, c1 - c0, c.has_slope, c.NS, which ? ci::PLACEBO_VAR : ci::PLACEBO_SUM, a));
+      HIP_TRY((c.f64 ? ci::placebo_launch_f64 : ci::placebo_launch)(stream, c1 - c0, c.has_slope, c.NS,
+                                                                    which ? ci::PLACEBO_VAR : ci::PLACEBO_SUM, a));
       HIP_TRY(ci::placebo_pool_launch(stream, N, O, G, which, c0, c1, t.offsets, t.weights, w.value.p, t.acc));
     }
   }
@@ -566,8 +581,11 @@ static int pool_simulated_placebo(ci_session* s, bool blocks, const double* scal
   for (int c0 = 0; c0 < K; c0 += chunk) {
     const int c1 = K - c0 < chunk ? K : c0 + chunk;
     a.q.series_of = t.members + c0; a.q.origins = t.origins + (size_t)c0 * O; a.q.horizon = t.horizon + c0;
-    if (blocks) HIP_TRY(ci::placebo_blocks_sim_entries_launch(stream, c1 - c0, link, ab));
-    else HIP_TRY(ci::placebo_sim_entries_launch(stream, c1 - c0, c.has_slope, c.NS, link, a));
+    if (blocks)
+      HIP_TRY((c.f64 ? ci::placebo_blocks_sim_entries_launch_f64 : ci::placebo_blocks_sim_entries_launch)(stream, c1 - c0, link, ab));
+    else
+      HIP_TRY((c.f64 ? ci::placebo_sim_entries_launch_f64 : ci::placebo_sim_entries_launch)(stream, c1 - c0, c.has_slope, c.NS,
+                                                                                            link, a));
     HIP_TRY(ci::placebo_pool_totals_launch(stream, N, O, G, c0, c1, t.offsets, t.weights, w.value.p, t.acc));
   }
   HIP_TRY(hipMemcpyAsync(out, t.acc, t.acc_n * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -591,7 +609,118 @@ static int pool_simulated_placebo(ci_session* s, bool blocks, const double* scal
   return 0;
 }
 
+// ---- A session made from draws (include/causalimpact_amd.h) --------------------------------------
+// The filters read the data and the parameter draws, never the fit: this session holds y (masked
+// steps zeroed, as a fit's), mask, the design feature-major, season_change, the parameter blocks
+// (pred_init_upload) and the five draw arrays -- where a fit leaves them (F = float) or, float64, in
+// the session's *64 buffers, which the float64-input builds of the filters read.  No workspace, no
+// trajectories, no latents, no kernel pointer, no copy stream.
+namespace {
+struct DrawsSessionGuard {
+  ci_session* s;
+  ~DrawsSessionGuard() { if (s) ci_session_destroy(s); }
+};
+
+// A scale draw must be finite and not negative: array [B, N], or with `per_block` [B, N, width].
+template <class F>
+int check_scale_draws(const char* name, const F* x, int B, int N, int width = 1, bool per_block = false) {
+  for (int b = 0; b < B; ++b)
+    for (int n = 0; n < N; ++n)
+      for (int k = 0; k < width; ++k) {
+        const double v = (double)x[((size_t)b * N + n) * width + k];
+        if (std::isfinite(v) && v >= 0.0) continue;
+        if (per_block)
+          return fail("%s of series %d, draw %d, block %d must be finite and not negative, got %g", name, b, n, k, v);
+        return fail("%s of series %d, draw %d must be finite and not negative, got %g", name, b, n, v);
+      }
+  return 0;
+}
+
+template <class F> int upload(DevBuf<F>& dst, const F* src, size_t n) {
+  HIP_TRY(dst.alloc(n));
+  if (n) HIP_TRY(hipMemcpy(dst.p, src, n * sizeof(F), hipMemcpyHostToDevice));
+  return 0;
+}
+}  // namespace
+
+template <class F>
+static int session_from_draws(const ci_problem* pb, const F* y, const uint8_t* mask, const F* X,
+                              const uint8_t* season_change, const ci_series_params* params, const F* obs,
+                              const F* lscale, const F* sscale, const F* drift, const F* weights,
+                              ci_session** out) {
+  constexpr bool F64 = sizeof(F) == sizeof(double);
+  if (validate(pb)) return 1;
+  if (!y || !mask || !params || !obs || !lscale || !out) return fail("NULL argument");
+  if (pb->has_slope && !sscale) return fail("slope_scale is NULL but has_slope is set");
+  if (pb->num_blocks > 0 && !season_change) return fail("season_change is NULL but num_blocks > 0");
+  if (pb->num_blocks > 0 && !drift) return fail("seasonal_drift_scales is NULL but num_blocks > 0");
+  if (pb->P > 0 && !X) return fail("X is NULL but P=%d", pb->P);
+  if (pb->P > 0 && !weights) return fail("weights is NULL but P=%d", pb->P);
+  const int B = pb->num_series, T = pb->T, P = pb->P, K = pb->num_blocks;
+  const int N = pb->num_chains * pb->num_results;
+  std::vector<F> yh;
+  std::vector<double> n_obs;
+  if (stage_outcomes<F>(B, T, nullptr, y, mask, yh, n_obs)) return 1;
+  if (check_scale_draws("observation_noise_scale", obs, B, N)) return 1;
+  if (check_scale_draws("level_scale", lscale, B, N)) return 1;
+  if (pb->has_slope && check_scale_draws("slope_scale", sscale, B, N)) return 1;
+  if (K > 0 && check_scale_draws("seasonal_drift_scales", drift, B, N, K, true)) return 1;
+  HIP_TRY(hipSetDevice(pb->device));
+  ci_session* s = new ci_session();
+  DrawsSessionGuard guard{s};
+  s->pb = *pb;
+  s->kpb = *pb;
+  s->from_draws = true;
+  s->f64 = F64;
+  s->ran = true;
+  s->kernel_name = "(made from draws)";
+  s->params.assign(params, params + B);
+  HIP_TRY(pool_stream_get(&s->stream));
+  const size_t BN = (size_t)B * N;
+  HIP_TRY(s->mask.alloc((size_t)B * T));
+  HIP_TRY(hipMemcpy(s->mask.p, mask, (size_t)B * T, hipMemcpyHostToDevice));
+  if (K > 0) {
+    HIP_TRY(s->season_change.alloc((size_t)K * T));
+    HIP_TRY(hipMemcpy(s->season_change.p, season_change, (size_t)K * T, hipMemcpyHostToDevice));
+  }
+  const std::vector<F> xt = P > 0 ? transpose_design<F>(B, T, P, X) : std::vector<F>();
+  // (no slope: the filters never read sscale; no block: never drift; no design: never Xt and w)
+  const size_t n_ss = pb->has_slope ? BN : 0, n_dr = K > 0 ? BN * K : 0, n_w = P > 0 ? BN * P : 0;
+  if constexpr (F64) {
+    if (upload(s->y64, yh.data(), yh.size()) || upload(s->Xt64, xt.data(), xt.size()) ||
+        upload(s->d_obs64, obs, BN) || upload(s->d_lscale64, lscale, BN) || upload(s->d_sscale64, sscale, n_ss) ||
+        upload(s->d_drift64, drift, n_dr) || upload(s->d_w64, weights, n_w))
+      return 1;
+  } else {
+    if (upload(s->y, yh.data(), yh.size()) || upload(s->Xt, xt.data(), xt.size()) ||
+        upload(s->o_obs, obs, BN) || upload(s->o_lscale, lscale, BN) || upload(s->o_sscale, sscale, n_ss) ||
+        upload(s->o_drift, drift, n_dr) || upload(s->o_w, weights, n_w))
+      return 1;
+  }
+  guard.s = nullptr;
+  *out = s;
+  return 0;
+}
+
 extern "C" {
+
+int ci_session_create_from_draws(const ci_problem* pb, const float* y, const uint8_t* mask, const float* X,
+                                 const uint8_t* season_change, const ci_series_params* params,
+                                 const float* observation_noise_scale, const float* level_scale,
+                                 const float* slope_scale, const float* seasonal_drift_scales,
+                                 const float* weights, ci_session** out) {
+  return session_from_draws<float>(pb, y, mask, X, season_change, params, observation_noise_scale, level_scale,
+                                   slope_scale, seasonal_drift_scales, weights, out);
+}
+
+int ci_session_create_from_draws_f64(const ci_problem* pb, const double* y, const uint8_t* mask, const double* X,
+                                     const uint8_t* season_change, const ci_series_params* params,
+                                     const double* observation_noise_scale, const double* level_scale,
+                                     const double* slope_scale, const double* seasonal_drift_scales,
+                                     const double* weights, ci_session** out) {
+  return session_from_draws<double>(pb, y, mask, X, season_change, params, observation_noise_scale, level_scale,
+                                    slope_scale, seasonal_drift_scales, weights, out);
+}
 
 int ci_session_summarize_predictions(ci_session* s, const double* scale, const double* shift,
                                      int32_t num_ranks, const int32_t* ranks, double* forecast_mean,

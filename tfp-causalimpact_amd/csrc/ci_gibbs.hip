@@ -609,6 +609,7 @@ static int session_launch(ci_session* s) {
 
 int ci_session_run(ci_session* s, float* kernel_ms) {
   if (!s) return fail("session is NULL");
+  if (refuse_draws_session(s, "ci_session_run")) return 1;
   s->progress_every = 0;
   if (session_launch(s)) return 1;
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -662,6 +663,7 @@ struct StreamsIdle {
 
 int ci_session_run_streamed(ci_session* s, ci_outputs* o, int32_t chunk_draws, float* kernel_ms) {
   if (!s || !o) return fail("NULL argument");
+  if (refuse_draws_session(s, "ci_session_run_streamed")) return 1;
   if (chunk_draws < 1) return fail("chunk_draws must be >= 1, got %d", chunk_draws);
   if (s->ragged) return fail("ci_session_run_streamed does not take ragged sessions: use ci_session_run and ci_session_fetch");
   const ci_problem& pb = s->pb;
@@ -777,12 +779,14 @@ int ci_session_run_streamed(ci_session* s, ci_outputs* o, int32_t chunk_draws, f
 
 int ci_session_fetch(ci_session* s, ci_outputs* o) {
   if (!s || !o) return fail("NULL argument");
+  if (refuse_draws_session(s, "ci_session_fetch")) return 1;
   HIP_TRY(hipSetDevice(s->pb.device));
   return copy_outputs(o, s->outputs());
 }
 
 int ci_session_algorithmic_bytes(const ci_session* s, double* bytes) {
   if (!s || !bytes) return fail("NULL argument");
+  if (refuse_draws_session(s, "ci_session_algorithmic_bytes")) return 1;
   const ci_problem& pb = s->pb;
   const double P = pb.P, S = pb.num_results;
   if (s->ragged) {
@@ -809,11 +813,13 @@ int ci_session_algorithmic_bytes(const ci_session* s, double* bytes) {
 
 int ci_session_kernel_name(const ci_session* s, char* buf, int32_t buflen) {
   if (!s) return fail("session is NULL");
+  if (refuse_draws_session(s, "ci_session_kernel_name")) return 1;
   return copy_name(s->kernel_name, buf, buflen);
 }
 
 int ci_session_profile(ci_session* s, int enable, int64_t* cycles16) {
   if (!s) return fail("session is NULL");
+  if (refuse_draws_session(s, "ci_session_profile")) return 1;
   if (s->ragged && enable) return fail("ci_session_profile does not take ragged sessions (no instrumented ragged build)");
   s->profile = enable != 0;
   if (cycles16) {

@@ -59,6 +59,8 @@ struct PlaceboArgs {
 // accumulators; placebo_finish_kernel<out> over the accumulators' rows r0 .. r0 + rows - 1 into M.
 hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
                           const PlaceboArgs& args);
+hipError_t placebo_launch_f64(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
+                              const PlaceboArgs& args);
 hipError_t placebo_pool_launch(hipStream_t stream, int N, int O, int G, int which, int c0, int c1,
                                const int* offsets, const double* weights, const double* M, double* acc);
 hipError_t placebo_finish_launch(hipStream_t stream, int N, size_t r0, size_t rows, int out,
@@ -88,7 +90,7 @@ __device__ __forceinline__ void placebo_propagate(double (&a)[D], double (&P)[D 
 }
 
 // grid (ceil(N / 64), B), block 64; with an entry table (ceil(N / 64), E).
-template <int HAS_SLOPE, int NS, int OUT>
+template <int HAS_SLOPE, int NS, int OUT, class IN = float>
 __global__ __launch_bounds__(64) void placebo_kernel(PlaceboArgs k) {
   constexpr int N1 = NS ? NS - 1 : 0, O = 1 + HAS_SLOPE, D = O + N1, NP = D * (D + 1) / 2;
   constexpr int ZS = O < D ? O : 0;              // the block's first effect (NS > 0)
@@ -98,20 +100,20 @@ __global__ __launch_bounds__(64) void placebo_kernel(PlaceboArgs k) {
   if (n >= N) return;
   const int Tb = k.p.series_T ? k.p.series_T[b] : T;
   const size_t bn = b * N + n;
-  const double so = (double)k.p.obs[bn], H = so * so;
-  const double sl = (double)k.p.lscale[bn], q_level = sl * sl;
+  const double so = (double)((const IN*)k.p.obs)[bn], H = so * so;
+  const double sl = (double)((const IN*)k.p.lscale)[bn], q_level = sl * sl;
   double q_slope = 0.0, q_drift = 0.0;
   if (HAS_SLOPE) {
-    const double ss = (double)k.p.sscale[bn];
+    const double ss = (double)((const IN*)k.p.sscale)[bn];
     q_slope = ss * ss;
   }
   if (NS) {
-    const double q = (double)k.p.drift[bn] / (double)NS;
+    const double q = (double)((const IN*)k.p.drift)[bn] / (double)NS;
     q_drift = q * q;
   }
   const double scale = k.p.scales[b], shift = k.p.shifts[b];
   const double* init = k.p.init + 4 * b;
-  const float* y = k.p.y + b * T;
+  const IN* y = (const IN*)k.p.y + b * T;
   const uint8_t* mask = k.p.mask + b * T;
   const double* reg = k.p.reg ? k.p.reg + b * T * N + n : nullptr;
   double* out = k.p.out + e * NO * N + n;
@@ -246,6 +248,10 @@ hipError_t placebo_sim_launch(hipStream_t stream, int nb, int has_slope, int num
                               const PlaceboSimArgs& args);
 hipError_t placebo_sim_entries_launch(hipStream_t stream, int E, int has_slope, int num_seasons, int link,
                                       const PlaceboSimArgs& args);
+hipError_t placebo_sim_launch_f64(hipStream_t stream, int nb, int has_slope, int num_seasons, int link,
+                                  const PlaceboSimArgs& args);
+hipError_t placebo_sim_entries_launch_f64(hipStream_t stream, int E, int has_slope, int num_seasons, int link,
+                                          const PlaceboSimArgs& args);
 hipError_t placebo_pool_totals_launch(hipStream_t stream, int N, int O, int G, int c0, int c1,
                                       const int* offsets, const double* weights, const double* M, double* acc);
 hipError_t placebo_sim_seen_launch(hipStream_t stream, size_t rows, int N, double* M, const double* seen,
@@ -268,7 +274,7 @@ __device__ __forceinline__ double placebo_sim_normal(const Rng& g, uint32_t iter
 // with q.horizon[e] and writes rows e * O .. of `out` and `counted` -- the tables of
 // ci_session_pool_placebo, whose pointers the host sets to the launch's first entry; b0 is not
 // read.  Everything else of the row, the Philox key included, is the series'.
-template <int HAS_SLOPE, int NS, int LINK, bool ENTRIES = false>
+template <int HAS_SLOPE, int NS, int LINK, bool ENTRIES = false, class IN = float>
 __global__ __launch_bounds__(64) void placebo_sim_kernel(PlaceboSimArgs k) {
   constexpr int N1 = NS ? NS - 1 : 0, O = 1 + HAS_SLOPE, D = O + N1, NP = D * (D + 1) / 2;
   constexpr int ZS = O < D ? O : 0;              // the block's first effect (NS > 0)
@@ -279,20 +285,20 @@ __global__ __launch_bounds__(64) void placebo_sim_kernel(PlaceboSimArgs k) {
   if (n >= N) return;
   const int Tb = p.series_T ? p.series_T[b] : T;
   const size_t bn = b * N + n;
-  const double so = (double)p.obs[bn], H = so * so;
-  const double sl = (double)p.lscale[bn], q_level = sl * sl;
+  const double so = (double)((const IN*)p.obs)[bn], H = so * so;
+  const double sl = (double)((const IN*)p.lscale)[bn], q_level = sl * sl;
   double q_slope = 0.0, q_drift = 0.0;
   if (HAS_SLOPE) {
-    const double ss = (double)p.sscale[bn];
+    const double ss = (double)((const IN*)p.sscale)[bn];
     q_slope = ss * ss;
   }
   if (NS) {
-    const double q = (double)p.drift[bn] / (double)NS;
+    const double q = (double)((const IN*)p.drift)[bn] / (double)NS;
     q_drift = q * q;
   }
   const double scale = p.scales[b], shift = p.shifts[b];
   const double* init = p.init + 4 * b;
-  const float* y = p.y + b * T;
+  const IN* y = (const IN*)p.y + b * T;
   const uint8_t* mask = p.mask + b * T;
   const double* reg = p.reg ? p.reg + b * T * N + n : nullptr;
   double* out = p.out + e * NO * N + n;

@@ -1,6 +1,8 @@
 // Instantiation unit of the placebo forecasts (ci_placebo.h) and their launches;
 // ci_session_summarize_placebo, ci_session_pool_placebo, ci_session_simulate_placebo and
-// ci_session_pool_simulated_placebo (ci_summary.hip) call them.
+// ci_session_pool_simulated_placebo (ci_forecast.hip) call them.  With -DCI_FILTER_F64: the float64-input
+// builds of the two filters and their launches with the suffix _f64; the kernels over accumulators and
+// totals read no input of a session and belong to the float32 build alone.
 #include "ci_placebo.h"
 
 namespace ci {
@@ -8,10 +10,10 @@ namespace ci {
 using PlaceboFn = void (*)(PlaceboArgs);
 
 template <int HAS_SLOPE, int NS> static PlaceboFn placebo_fn(int out) {
-  if (out == PLACEBO_SUM) return placebo_kernel<HAS_SLOPE, NS, PLACEBO_SUM>;
-  if (out == PLACEBO_SPREAD) return placebo_kernel<HAS_SLOPE, NS, PLACEBO_SPREAD>;
-  if (out == PLACEBO_VAR) return placebo_kernel<HAS_SLOPE, NS, PLACEBO_VAR>;
-  return placebo_kernel<HAS_SLOPE, NS, PLACEBO_PIT>;
+  if (out == PLACEBO_SUM) return placebo_kernel<HAS_SLOPE, NS, PLACEBO_SUM, CI_FILTER_F>;
+  if (out == PLACEBO_SPREAD) return placebo_kernel<HAS_SLOPE, NS, PLACEBO_SPREAD, CI_FILTER_F>;
+  if (out == PLACEBO_VAR) return placebo_kernel<HAS_SLOPE, NS, PLACEBO_VAR, CI_FILTER_F>;
+  return placebo_kernel<HAS_SLOPE, NS, PLACEBO_PIT, CI_FILTER_F>;
 }
 
 template <int HAS_SLOPE> static PlaceboFn placebo_fn(int ns, int out) {
@@ -29,7 +31,7 @@ template <int HAS_SLOPE> static PlaceboFn placebo_fn(int ns, int out) {
 
 // One pass over B series (with args.series_of: B entries): `out` one of PlaceboOut, num_seasons 0
 // (no block) or 2..7.
-hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
+hipError_t CI_FILTER_NAME(placebo_launch)(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
                           const PlaceboArgs& args) {
   const PlaceboFn fn = has_slope ? placebo_fn<1>(num_seasons, out) : placebo_fn<0>(num_seasons, out);
   if (!fn) return hipErrorInvalidValue;
@@ -40,9 +42,9 @@ hipError_t placebo_launch(hipStream_t stream, int B, int has_slope, int num_seas
 using PlaceboSimFn = void (*)(PlaceboSimArgs);
 
 template <int HAS_SLOPE, int NS> static PlaceboSimFn placebo_sim_fn(int link) {
-  if (link == LINK_LOG) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG>;
-  if (link == LINK_LOG1P) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG1P>;
-  return placebo_sim_kernel<HAS_SLOPE, NS, LINK_IDENTITY>;
+  if (link == LINK_LOG) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG, false, CI_FILTER_F>;
+  if (link == LINK_LOG1P) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG1P, false, CI_FILTER_F>;
+  return placebo_sim_kernel<HAS_SLOPE, NS, LINK_IDENTITY, false, CI_FILTER_F>;
 }
 
 template <int HAS_SLOPE> static PlaceboSimFn placebo_sim_fn(int ns, int link) {
@@ -60,7 +62,7 @@ template <int HAS_SLOPE> static PlaceboSimFn placebo_sim_fn(int ns, int link) {
 
 // The simulated totals of `nb` series from args.b0 on: rows [nb * O, N] in args.q.p.out, cnt per row
 // in args.counted; link one of ci_link.h, num_seasons 0 (no block) or 2..7.
-hipError_t placebo_sim_launch(hipStream_t stream, int nb, int has_slope, int num_seasons, int link,
+hipError_t CI_FILTER_NAME(placebo_sim_launch)(hipStream_t stream, int nb, int has_slope, int num_seasons, int link,
                               const PlaceboSimArgs& args) {
   const PlaceboSimFn fn = has_slope ? placebo_sim_fn<1>(num_seasons, link) : placebo_sim_fn<0>(num_seasons, link);
   if (!fn || link < 0 || link >= NUM_LINKS) return hipErrorInvalidValue;
@@ -69,9 +71,9 @@ hipError_t placebo_sim_launch(hipStream_t stream, int nb, int has_slope, int num
 }
 
 template <int HAS_SLOPE, int NS> static PlaceboSimFn placebo_sim_entries_fn(int link) {
-  if (link == LINK_LOG) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG, true>;
-  if (link == LINK_LOG1P) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG1P, true>;
-  return placebo_sim_kernel<HAS_SLOPE, NS, LINK_IDENTITY, true>;
+  if (link == LINK_LOG) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG, true, CI_FILTER_F>;
+  if (link == LINK_LOG1P) return placebo_sim_kernel<HAS_SLOPE, NS, LINK_LOG1P, true, CI_FILTER_F>;
+  return placebo_sim_kernel<HAS_SLOPE, NS, LINK_IDENTITY, true, CI_FILTER_F>;
 }
 
 template <int HAS_SLOPE> static PlaceboSimFn placebo_sim_entries_fn(int ns, int link) {
@@ -89,7 +91,7 @@ template <int HAS_SLOPE> static PlaceboSimFn placebo_sim_entries_fn(int ns, int 
 
 // The simulated totals of E entries of a group table (args.q.series_of, origins and horizon from the
 // launch's first entry on): rows [E * O, N] in args.q.p.out, cnt per row in args.counted.
-hipError_t placebo_sim_entries_launch(hipStream_t stream, int E, int has_slope, int num_seasons, int link,
+hipError_t CI_FILTER_NAME(placebo_sim_entries_launch)(hipStream_t stream, int E, int has_slope, int num_seasons, int link,
                                       const PlaceboSimArgs& args) {
   const PlaceboSimFn fn = has_slope ? placebo_sim_entries_fn<1>(num_seasons, link)
                                     : placebo_sim_entries_fn<0>(num_seasons, link);
@@ -98,6 +100,7 @@ hipError_t placebo_sim_entries_launch(hipStream_t stream, int E, int has_slope, 
   return hipGetLastError();
 }
 
+#ifndef CI_FILTER_F64
 // The rows [(c1 - c0) * O, N] of one pass of simulated totals added to acc [G, O, N].
 hipError_t placebo_pool_totals_launch(hipStream_t stream, int N, int O, int G, int c0, int c1,
                                       const int* offsets, const double* weights, const double* M, double* acc) {
@@ -142,5 +145,6 @@ hipError_t placebo_finish_launch(hipStream_t stream, int N, size_t r0, size_t ro
     return hipErrorInvalidValue;
   return hipGetLastError();
 }
+#endif  // CI_FILTER_F64
 
 }  // namespace ci

@@ -39,6 +39,8 @@ struct PlaceboBlocksPoolArgs : PlaceboBlocksArgs {   // q.series_of [E], q.origi
 // build <G, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs> over E entries.
 hipError_t placebo_blocks_launch(hipStream_t stream, int B, int out, const PlaceboBlocksArgs& args);
 hipError_t placebo_blocks_pool_launch(hipStream_t stream, int E, const PlaceboBlocksPoolArgs& args);
+hipError_t placebo_blocks_launch_f64(hipStream_t stream, int B, int out, const PlaceboBlocksArgs& args);
+hipError_t placebo_blocks_pool_launch_f64(hipStream_t stream, int E, const PlaceboBlocksPoolArgs& args);
 
 // The series of grid row e: with an entry table that of entry e, else e itself.
 template <bool ENTRIES>
@@ -49,7 +51,7 @@ __device__ __forceinline__ size_t pb_series_of(const PlaceboArgs& q, size_t e) {
 
 // grid (ceil(N / (64 / G)), B), block 64; as placebo_blocks_kernel<G, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs>
 // (the entry-table build) (ceil(N / (64 / G)), E).
-template <int G, int OUT, class ARGS = PlaceboBlocksArgs>
+template <int G, int OUT, class ARGS = PlaceboBlocksArgs, class IN = float>
 __global__ __launch_bounds__(64) void placebo_blocks_kernel(ARGS k) {
   constexpr bool ENTRIES = OUT == PLACEBO_SUM_VAR;
   static_assert(ENTRIES == std::is_same<ARGS, PlaceboBlocksPoolArgs>::value, "SUM_VAR is the entry-table build's selector");
@@ -64,10 +66,10 @@ __global__ __launch_bounds__(64) void placebo_blocks_kernel(ARGS k) {
   const size_t b = pb_series_of<ENTRIES>(k.q, e), bn = b * N + n;
   PbCtx c;
   double H, a, P[G];
-  pb_begin<G>(p, k.m, sh, b, bn, c, H, a, P);
+  pb_begin<G, IN>(p, k.m, sh, b, bn, c, H, a, P);
   const bool writer = active && c.i == 0;
   const double scale = p.scales[b], shift = p.shifts[b];
-  const float* y = p.y + b * T;
+  const IN* y = (const IN*)p.y + b * T;
   const uint8_t* mask = p.mask + b * T;
   const double* reg = p.reg ? p.reg + b * T * N + n : nullptr;
   double* out = p.out + e * NO * N + n;
@@ -153,12 +155,14 @@ struct PlaceboBlocksSimArgs {
 // args.s.b0, its ENTRIES build over E entries.
 hipError_t placebo_blocks_sim_launch(hipStream_t stream, int nb, int link, const PlaceboBlocksSimArgs& args);
 hipError_t placebo_blocks_sim_entries_launch(hipStream_t stream, int E, int link, const PlaceboBlocksSimArgs& args);
+hipError_t placebo_blocks_sim_launch_f64(hipStream_t stream, int nb, int link, const PlaceboBlocksSimArgs& args);
+hipError_t placebo_blocks_sim_entries_launch_f64(hipStream_t stream, int E, int link, const PlaceboBlocksSimArgs& args);
 
 // grid (ceil(N / (64 / G)), series of the launch), block 64.  The entry-table build (ENTRIES;
 // ci_session_pool_simulated_placebo_blocks) has the grid (ceil(N / (64 / G)), entries of the launch)
 // and rows as placebo_sim_kernel's; the entry is uniform over the workgroup, so every barrier is met
 // by all 64 lanes as before.
-template <int G, int LINK, bool ENTRIES = false>
+template <int G, int LINK, bool ENTRIES = false, class IN = float>
 __global__ __launch_bounds__(64) void placebo_blocks_sim_kernel(PlaceboBlocksSimArgs k) {
   constexpr int FPW = 64 / G;
   __shared__ PbShared sh;
@@ -171,10 +175,10 @@ __global__ __launch_bounds__(64) void placebo_blocks_sim_kernel(PlaceboBlocksSim
   const size_t plan = ENTRIES ? e : b;           // the row of the plan: origins [., O], horizon [.]
   PbCtx c;
   double H, a, P[G];
-  pb_begin<G>(p, k.m, sh, b, bn, c, H, a, P);
+  pb_begin<G, IN>(p, k.m, sh, b, bn, c, H, a, P);
   const bool writer = active && c.i == 0;
   const double scale = p.scales[b], shift = p.shifts[b];
-  const float* y = p.y + b * T;
+  const IN* y = (const IN*)p.y + b * T;
   const uint8_t* mask = p.mask + b * T;
   const double* reg = p.reg ? p.reg + b * T * N + n : nullptr;
   double* out = p.out + e * NO * N + n;

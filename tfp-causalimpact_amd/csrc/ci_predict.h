@@ -10,7 +10,9 @@
 // unrolled register arrays; no array is indexed at run time (that would go to scratch).
 //
 // The model of series b, draw n (the state space of oracle/ci_oracle.c):
-//   sigma_obs, sigma_level, sigma_slope, sigma_drift: the session's float32 draws widened to double;
+//   sigma_obs, sigma_level, sigma_slope, sigma_drift: the session's draws widened to double, once, where
+//     they are loaded -- float32 (IN = float: a fit's session, or one made from float32 draws) or float64
+//     (IN = double: ci_session_create_from_draws_f64); y likewise; everything downstream is float64;
 //     H = sigma_obs^2, Q_level = sigma_level^2, Q_slope = sigma_slope^2, q = (sigma_drift / NS)^2
 //   a_0 = (init_level_loc, 0, ..), P_0 = diag(init_level_scale^2, init_slope_scale^2) and, in the
 //     NS - 1 effect coordinates, init_seasonal_scale^2 (I - 1/NS)        (init [B, 4] holds them)
@@ -43,11 +45,11 @@ enum PredOut { PRED_FORECAST = 0, PRED_VARIANCE = 1, PRED_PIT = 2 };
 
 struct PredArgs {
   int N, T;                        // pooled draws; steps (the row stride of a ragged session)
-  const float* y;                  // [B, T]
+  const void* y;                   // [B, T] of IN, the input type (float or double) the kernel is built for
   const uint8_t* mask;             // [B, T]
   const uint8_t* season_change;    // [T] (NS > 0)
   const int* series_T;             // [B] or nullptr
-  const float *obs, *lscale, *sscale, *drift;   // [B, N]
+  const void *obs, *lscale, *sscale, *drift;   // [B, N] of IN
   const double* init;              // [B, 4]: level loc, level var, slope var, seasonal var
   const double *scales, *shifts;   // [B]
   const double* reg;               // [B, T, N] or nullptr
@@ -55,9 +57,21 @@ struct PredArgs {
   double* ll;                      // [B, N] or nullptr
 };
 
-// The launch (ci_predict.hip): predict_kernel<has_slope, num_seasons, out> over B series.
+// The launch (ci_predict.hip): predict_kernel<has_slope, num_seasons, out> over B series.  The filter
+// units are built twice: as they stand for F = float, the inputs of a fit's session, and with
+// -DCI_FILTER_F64 for F = double, the inputs of a float64 session made from draws
+// (ci_session_create_from_draws_f64); the launches of that build carry the suffix _f64.
 hipError_t predict_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
                           const PredArgs& args);
+hipError_t predict_launch_f64(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
+                              const PredArgs& args);
+#ifdef CI_FILTER_F64
+#define CI_FILTER_F double
+#define CI_FILTER_NAME(name) name##_f64
+#else
+#define CI_FILTER_F float
+#define CI_FILTER_NAME(name) name
+#endif
 
 // Position of (i, j) in the row-major upper triangle of a symmetric D x D matrix.
 template <int D> __host__ __device__ constexpr int pred_sym(int i, int j) {
@@ -120,7 +134,7 @@ __device__ __forceinline__ void pred_season_step(double (&a)[D], double (&P)[D *
 }
 
 // grid (ceil(N / 64), B), block 64.
-template <int HAS_SLOPE, int NS, int OUT>
+template <int HAS_SLOPE, int NS, int OUT, class IN = float>
 __global__ __launch_bounds__(64) void predict_kernel(PredArgs k) {
   constexpr int N1 = NS ? NS - 1 : 0, O = 1 + HAS_SLOPE, D = O + N1, NP = D * (D + 1) / 2;
   constexpr double LOG_2PI = 1.8378770664093454835606594728112;
@@ -129,20 +143,20 @@ __global__ __launch_bounds__(64) void predict_kernel(PredArgs k) {
   if (n >= N) return;
   const int Tb = k.series_T ? k.series_T[b] : T;
   const size_t bn = b * N + n;
-  const double so = (double)k.obs[bn], H = so * so;
-  const double sl = (double)k.lscale[bn], q_level = sl * sl;
+  const double so = (double)((const IN*)k.obs)[bn], H = so * so;
+  const double sl = (double)((const IN*)k.lscale)[bn], q_level = sl * sl;
   double q_slope = 0.0, q_drift = 0.0;
   if (HAS_SLOPE) {
-    const double ss = (double)k.sscale[bn];
+    const double ss = (double)((const IN*)k.sscale)[bn];
     q_slope = ss * ss;
   }
   if (NS) {
-    const double q = (double)k.drift[bn] / (double)NS;
+    const double q = (double)((const IN*)k.drift)[bn] / (double)NS;
     q_drift = q * q;
   }
   const double scale = k.scales[b], shift = k.shifts[b];
   const double* init = k.init + 4 * b;
-  const float* y = k.y + b * T;
+  const IN* y = (const IN*)k.y + b * T;
   const uint8_t* mask = k.mask + b * T;
   const double* reg = k.reg ? k.reg + b * T * N + n : nullptr;
   double* out = k.out + b * T * N + n;

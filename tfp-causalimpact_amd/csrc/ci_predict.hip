@@ -1,5 +1,6 @@
 // Instantiation unit of the prediction-error filter (ci_predict.h) and its launch;
-// ci_session_summarize_predictions (ci_summary.hip) calls it.
+// ci_session_summarize_predictions (ci_forecast.hip) calls it.  With -DCI_FILTER_F64: the float64-input
+// build and predict_launch_f64.
 #include "ci_predict.h"
 
 namespace ci {
@@ -7,9 +8,9 @@ namespace ci {
 using PredictFn = void (*)(PredArgs);
 
 template <int HAS_SLOPE, int NS> static PredictFn predict_fn(int out) {
-  if (out == PRED_FORECAST) return predict_kernel<HAS_SLOPE, NS, PRED_FORECAST>;
-  if (out == PRED_VARIANCE) return predict_kernel<HAS_SLOPE, NS, PRED_VARIANCE>;
-  return predict_kernel<HAS_SLOPE, NS, PRED_PIT>;
+  if (out == PRED_FORECAST) return predict_kernel<HAS_SLOPE, NS, PRED_FORECAST, CI_FILTER_F>;
+  if (out == PRED_VARIANCE) return predict_kernel<HAS_SLOPE, NS, PRED_VARIANCE, CI_FILTER_F>;
+  return predict_kernel<HAS_SLOPE, NS, PRED_PIT, CI_FILTER_F>;
 }
 
 template <int HAS_SLOPE> static PredictFn predict_fn(int ns, int out) {
@@ -26,7 +27,7 @@ template <int HAS_SLOPE> static PredictFn predict_fn(int ns, int out) {
 }
 
 // One filter pass over B series: `out` one of PredOut, num_seasons 0 (no block) or 2..7.
-hipError_t predict_launch(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
+hipError_t CI_FILTER_NAME(predict_launch)(hipStream_t stream, int B, int has_slope, int num_seasons, int out,
                           const PredArgs& args) {
   const PredictFn fn = has_slope ? predict_fn<1>(num_seasons, out) : predict_fn<0>(num_seasons, out);
   if (!fn) return hipErrorInvalidValue;

@@ -5,8 +5,8 @@
 // THE MODEL is that of ci_predict.h, generalised to K blocks.  Let hs = has_slope.
 //   Block k has n_k seasons and n_k - 1 effect coordinates at offset o_k = 1 + hs + sum_{j<k} (n_j - 1);
 //   d = 1 + hs + sum_k (n_k - 1) <= 64.  Z has ones at 0 and at every o_k.
-//   sigma_obs, sigma_level, sigma_slope as there; sigma_drift: the session's draws [B, N, K], float32
-//   widened to double; season_change [K, T].  a_0 = (init_level_loc, 0, ..), P_0 = diag(init_level_scale^2,
+//   sigma_obs, sigma_level, sigma_slope as there; sigma_drift: the session's draws [B, N, K], of the
+//   input type IN (float or double, as there) widened to double; season_change [K, T].  a_0 = (init_level_loc, 0, ..), P_0 = diag(init_level_scale^2,
 //   init_slope_scale^2) and init_seasonal_scale^2 (I - 1/n_k) in every block, zero across blocks.
 // Per step t = 0 .. T - 1:
 //   m = a[0] + a[o_0] + a[o_1] + ..        (added in that order)
@@ -71,6 +71,7 @@ struct PredBlocksArgs {
 
 // The launch (ci_predict_blocks.hip): predict_blocks_kernel<G, out> over B series, G from m.d.
 hipError_t predict_blocks_launch(hipStream_t stream, int B, int out, const PredBlocksArgs& args);
+hipError_t predict_blocks_launch_f64(hipStream_t stream, int B, int out, const PredBlocksArgs& args);
 
 // What a group's lanes share: the model in LDS, the exchange vectors, the lane's place.
 struct PbCtx {
@@ -198,7 +199,7 @@ struct PbShared {
 
 // Sets the context up, loads the draw's scales and the initial moments (a, P) of the lane's row.
 // n: the group's draw (clamped to N - 1), bn = b * N + n.
-template <int G>
+template <int G, class IN>
 __device__ __forceinline__ void pb_begin(const PredArgs& p, const BlockModel& m, PbShared& sh, size_t b, size_t bn,
                                          PbCtx& c, double& H, double& a, double (&P)[G]) {
   c.lane = threadIdx.x; c.i = c.lane % G; c.g = c.lane / G; c.gb = c.g * G;
@@ -214,16 +215,16 @@ __device__ __forceinline__ void pb_begin(const PredArgs& p, const BlockModel& m,
     }
   __syncthreads();
   if (c.i < m.K) {
-    const double q = (double)p.drift[bn * m.K + c.i] / (double)(sh.n1[c.i] + 1);
+    const double q = (double)((const IN*)p.drift)[bn * m.K + c.i] / (double)(sh.n1[c.i] + 1);
     sh.q[c.g][c.i] = q * q;
   }
-  const double so = (double)p.obs[bn];
+  const double so = (double)((const IN*)p.obs)[bn];
   H = so * so;
-  const double sl = (double)p.lscale[bn];
+  const double sl = (double)((const IN*)p.lscale)[bn];
   c.q_level = sl * sl;
   c.q_slope = 0.0;
   if (m.has_slope) {
-    const double ss = (double)p.sscale[bn];
+    const double ss = (double)((const IN*)p.sscale)[bn];
     c.q_slope = ss * ss;
   }
   __syncthreads();
@@ -259,7 +260,7 @@ __device__ __forceinline__ void pb_moments(const PbCtx& c, double a, const doubl
 }
 
 // grid (ceil(N / (64 / G)), B), block 64.
-template <int G, int OUT>
+template <int G, int OUT, class IN = float>
 __global__ __launch_bounds__(64) void predict_blocks_kernel(PredBlocksArgs k) {
   constexpr double LOG_2PI = 1.8378770664093454835606594728112;
   constexpr int FPW = 64 / G;
@@ -271,10 +272,10 @@ __global__ __launch_bounds__(64) void predict_blocks_kernel(PredBlocksArgs k) {
   const size_t b = blockIdx.y, bn = b * N + n;
   PbCtx c;
   double H, a, P[G];
-  pb_begin<G>(k.p, k.m, sh, b, bn, c, H, a, P);
+  pb_begin<G, IN>(k.p, k.m, sh, b, bn, c, H, a, P);
   const bool writer = active && c.i == 0;
   const double scale = k.p.scales[b], shift = k.p.shifts[b];
-  const float* y = k.p.y + b * T;
+  const IN* y = (const IN*)k.p.y + b * T;
   const uint8_t* mask = k.p.mask + b * T;
   const double* reg = k.p.reg ? k.p.reg + b * T * N + n : nullptr;
   double* out = k.p.out + b * T * N + n;

@@ -72,6 +72,13 @@ struct ci_session {
   std::vector<ci_series_params> params;
   DevBuf<double> pred_init;
   bool ran = false;
+  // A session MADE FROM DRAWS (ci_session_create_from_draws[_f64], ci_forecast.hip): the inputs and the
+  // pooled parameter draws the forecast entries read, no fit -- `ran` is true from the start.  Float32
+  // draws lie where a fit leaves them (y, Xt, o_obs, o_lscale, o_sscale, o_drift, o_w); with `f64`
+  // the inputs and the draws are float64, in the buffers below, and the float64-input builds of the
+  // filters read them.
+  bool from_draws = false, f64 = false;
+  DevBuf<double> y64, Xt64, d_obs64, d_lscale64, d_sscale64, d_drift64, d_w64;
   ci_problem kpb;          // what the kernel runs (== pb except for long trend-only series)
   bool inert_block = false;
   std::string kernel_name; // the Gibbs kernel this session dispatches to (as rocprofv3 names it)
@@ -128,6 +135,13 @@ struct ci_ll_session {
     return {h_obs, h_lscale, h_sscale, h_w, h_level, h_slope, h_pm, h_traj, h_drift, h_seasonal, D == 2};
   }
 };
+
+// The entries that need a fit refuse a session made from draws, before any device call.
+inline int refuse_draws_session(const ci_session* s, const char* entry) {
+  if (s->from_draws)
+    return fail("%s: the session was made from draws (ci_session_create_from_draws) and holds no fit", entry);
+  return 0;
+}
 
 // ---- ci_stage.hip: what is checked and staged on the host, before any device call ---------------
 int validate(const ci_problem* pb);

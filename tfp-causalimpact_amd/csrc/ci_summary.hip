@@ -506,6 +506,7 @@ int ci_session_set_link(ci_session* s, int32_t link) {
 // its row means in `obs` -- the passes of a component of ci_session_summarize_components.
 int ci_session_value_mean(ci_session* s, const double* scale, const double* shift, double* value_mean) {
   if (!s || !scale || !shift || !value_mean) return fail("NULL argument");
+  if (refuse_draws_session(s, "ci_session_value_mean")) return 1;
   if (!s->ran) return fail("ci_session_value_mean needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
   const int B = pb.num_series, T = pb.T, N = pb.num_chains * pb.num_results;
@@ -531,6 +532,7 @@ int ci_session_pool_event_trajectories(ci_session* s, const double* scale, const
                                        int32_t out_stride, const double* init, double* out) {
   if (!s || !scale || !shift || !offsets || !members || !weights || !first || !width || !out)
     return fail("NULL argument");
+  if (refuse_draws_session(s, "ci_session_pool_event_trajectories")) return 1;
   if (!s->ran) return fail("ci_session_pool_event_trajectories needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
   return pool_resident(pb.device, s->stream, s->summ, s->link, pb.num_series, pb.T, pb.num_chains * pb.num_results,
@@ -542,6 +544,7 @@ int ci_session_pool_trajectories(ci_session* s, const double* scale, const doubl
                                  int32_t num_groups, const int32_t* offsets, const int32_t* members,
                                  const double* weights, const double* init, double* out) {
   if (!s || !scale || !shift || !offsets || !members || !weights || !out) return fail("NULL argument");
+  if (refuse_draws_session(s, "ci_session_pool_trajectories")) return 1;
   if (!s->ran) return fail("ci_session_pool_trajectories needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
   return pool_resident(pb.device, s->stream, s->summ, s->link, pb.num_series, pb.T, pb.num_chains * pb.num_results,
@@ -563,6 +566,7 @@ int ci_session_summarize(ci_session* s, const double* scale, const double* shift
                          const int32_t* ranks, double* value_order, double* cum_order,
                          double* per_draw, double* per_draw_order) {
   if (!s || !scale || !shift || !observed || !flags || !ranks) return fail("NULL argument");
+  if (refuse_draws_session(s, "ci_session_summarize")) return 1;
   if (!s->ran) return fail("ci_session_summarize needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
   HIP_TRY(hipSetDevice(pb.device));
@@ -576,6 +580,7 @@ int ci_session_summarize_windows(ci_session* s, const double* scale, const doubl
                                  const int32_t* count, int32_t num_ranks, const int32_t* ranks,
                                  double* per_draw, double* per_draw_order) {
   if (!s || !scale || !shift || !observed || !first || !count || !ranks) return fail("NULL argument");
+  if (refuse_draws_session(s, "ci_session_summarize_windows")) return 1;
   if (!s->ran) return fail("ci_session_summarize_windows needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
   return windows_resident("ci_session_summarize_windows", pb.device, s->stream, s->link, pb.num_series, pb.T,
@@ -611,6 +616,7 @@ int ci_test_session_summarize_paths(ci_session* s, const double* scale, const do
                                     double* excursion_order, double* observed_excursion, int32_t* at,
                                     int32_t* exceed, int64_t max_bytes, int32_t* num_chunks) {
   if (!s || !scale || !shift || !observed || !first || !count || !ranks) return fail("NULL argument");
+  if (refuse_draws_session(s, "ci_session_summarize_paths")) return 1;
   if (!s->ran) return fail("ci_session_summarize_paths needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
   return paths_resident("ci_session_summarize_paths", pb.device, s->stream, s->link, pb.num_series, pb.T,
@@ -639,6 +645,7 @@ int ci_session_summarize_components(ci_session* s, const double* scale, const do
                                     double* regression_mean, double* regression_order,
                                     double* inclusion_prob, double* weight_mean, double* weight_order) {
   if (!s || !scale || !shift || !ranks) return fail("NULL argument");
+  if (refuse_draws_session(s, "ci_session_summarize_components")) return 1;
   if (!s->ran) return fail("ci_session_summarize_components needs a finished ci_session_run");
   const ci_problem& pb = s->pb;
   const int B = pb.num_series, T = pb.T, P = pb.P, N = pb.num_chains * pb.num_results;
