@@ -459,7 +459,36 @@ int ci_session_summarize_predictions(ci_session* session, const double* scale, c
 int ci_session_summarize_placebo(ci_session* session, const double* scale, const double* shift,
                                  int32_t max_origins, const int32_t* origins, const int32_t* horizon,
                                  double* predicted_mean, double* spread_mean, double* pit_mean);
-/* The two summaries above for ANY BLOCK LIST whose state has at most 64 components: weekly plus
+/* PLACEBO FORECASTS AT SEVERAL HORIZONS from one filter pass: ci_session_summarize_placebo's three
+ * outputs for K horizons per series, every horizon looking from the SAME origins, so that the rows
+ * are comparable (how does the check behave after 1, 2, 4 weeks; from which horizon on does the model
+ * drift).  Additive: CI_ABI_VERSION stays 5; look the symbol up (dlsym) where an older library may be
+ * met.  The running C, V, A and cnt of the loop above after h steps are what a window of horizon h
+ * returns, so the forecast of an origin runs to the row's last horizon and SUM, SPREAD and PIT are
+ * formed -- with the expressions above -- at every h == horizons[b, k]:
+ *   out[b, i, k] == what ci_session_summarize_placebo returns at [b, i] with horizon[b] = horizons[b, k],
+ * bit for bit, for every output.
+ * max_origins, origins [B, O]: as above, with o + (the row's largest horizon) <= T_b; max_horizons: K,
+ * the slots per series, in [1, 64]; horizons [B, K]: >= 1, strictly ascending, -1 = unused, the unused
+ * slots at the end of the row, at least one horizon per row.  Outputs (host, caller-allocated,
+ * float64, each [B, O, K]; each may be NULL): predicted_mean, spread_mean, pit_mean; 0 in the unused
+ * origin and horizon slots and where the window counts no observation.
+ * Sessions and models as ci_session_summarize_placebo (a trend with at most one block of 2 to 7
+ * seasons; a ragged session uses each series' own length; a session made from draws in float32 or
+ * float64).  The filter runs ONCE per chunk of whole series: a chunk's 3 * nb * O * K rows of N doubles
+ * lie in the scratch of ci_session_summarize where one series' rows fit its B * T, else in a buffer of
+ * the call's own of at most CI_PATHS_MAX_BYTES, given back when it returns; one series that does not
+ * fit that is refused.  No value depends on where the chunks are cut.  Checked before any device call:
+ * the arguments but the outputs are not NULL, the block list, a finished ci_session_run, max_horizons,
+ * the horizon rows, then the origins as above with every row's largest horizon. */
+int ci_session_summarize_placebo_horizons(ci_session* session, const double* scale, const double* shift,
+                                          int32_t max_origins, const int32_t* origins /* [B, O] */,
+                                          int32_t max_horizons, const int32_t* horizons /* [B, K] */,
+                                          double* predicted_mean, double* spread_mean,
+                                          double* pit_mean /* each [B, O, K], may be NULL */);
+/* ci_session_summarize_predictions and ci_session_summarize_placebo for ANY BLOCK LIST whose state
+ * has at most 64 components (the several-horizons entry has no such twin: K calls of
+ * ci_session_summarize_placebo_blocks with the same origins return the same table): weekly plus
  * monthly blocks, blocks of 12, 24 or 52 seasons, blocks with several steps per season next to
  * others.  Additive: CI_ABI_VERSION stays 5; look the symbols up (dlsym) where an older library may
  * be met.  Arguments, outputs, argument checks and their messages are those of
@@ -1114,6 +1143,14 @@ int ci_test_session_simulate_placebo(ci_session* session, int32_t blocks, const 
                                      int32_t num_ranks, const int32_t* ranks, double* predicted_mean,
                                      double* spread_mean, double* below, double* total_order,
                                      double* totals, int64_t max_rows, int32_t* num_chunks);
+/* ci_session_summarize_placebo_horizons with the rows of a chunk handed in (max_rows in place of its
+ * own capacity; 0: that default; at least the 3 * max_origins * max_horizons rows of one series) and
+ * the number of chunks it took written to num_chunks (may be NULL), likewise. */
+int ci_test_session_summarize_placebo_horizons(ci_session* session, const double* scale, const double* shift,
+                                               int32_t max_origins, const int32_t* origins,
+                                               int32_t max_horizons, const int32_t* horizons,
+                                               double* predicted_mean, double* spread_mean, double* pit_mean,
+                                               int64_t max_rows, int32_t* num_chunks);
 /* ci_session_pool_placebo_blocks with the entries of a chunk handed in (chunk_entries in [1, B] in
  * place of B), likewise: the result does not depend on where the entries are cut. */
 int ci_test_session_pool_placebo_blocks(ci_session* session, const double* scale, const double* shift,

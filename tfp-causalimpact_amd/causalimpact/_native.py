@@ -139,6 +139,11 @@ def load():
   if hasattr(L, "ci_session_summarize_placebo_blocks"):       # (additive, likewise)
     L.ci_session_summarize_placebo_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                       C.c_void_p, C.c_void_p] + [C.c_void_p] * 3
+  for name in ("ci_session_summarize_placebo_horizons", "ci_test_session_summarize_placebo_horizons"):
+    if hasattr(L, name):                               # (additive, likewise)
+      getattr(L, name).argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                    C.c_void_p] + [C.c_void_p] * 3 +
+                                   ([C.c_int64, C.c_void_p] if name.startswith("ci_test_") else []))
   for name in ("ci_session_simulate_placebo", "ci_session_simulate_placebo_blocks",
                "ci_test_session_simulate_placebo"):
     if hasattr(L, name):                               # (additive, likewise)
@@ -247,6 +252,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_profile", "ci_ll_session_kernel_name",
           "ci_session_summarize", "ci_session_summarize_components",
           "ci_session_summarize_predictions", "ci_session_summarize_placebo",
+          "ci_session_summarize_placebo_horizons", "ci_test_session_summarize_placebo_horizons",
           "ci_session_summarize_predictions_blocks", "ci_session_summarize_placebo_blocks", "ci_summarize_draws", "ci_summarize_draws_f64",
           "ci_summarize_draw_paths_f64",
           "ci_session_summarize_windows", "ci_ll_session_summarize_windows",
@@ -299,6 +305,43 @@ def _origin_plan(origins, horizon, B: int):
   if org.ndim != 2 or org.shape[0] != B:
     raise ValueError(f"`origins` must be [{B}, O], got shape {org.shape}")
   return np.ascontiguousarray(org, dtype=np.int32), _per_series("horizon", horizon, B, np.int32)
+
+
+MAX_PLACEBO_HORIZONS = 64   # max_horizons of ci_session_summarize_placebo_horizons
+
+
+def horizon_table(horizons, B: int) -> np.ndarray:
+  """horizons [B, K] int32 of `Session.summarize_placebo_horizons`, from [B, K] or -- the same row for
+  every series -- [K].  The rules the C entry checks, checked here first (ValueError, series and slot
+  named): 1 <= K <= 64, every row with at least one horizon, each >= 1, strictly ascending, -1
+  (unused) only at the end of the row."""
+  hz = np.asarray(horizons)
+  if hz.ndim == 1:
+    hz = np.broadcast_to(hz, (B,) + hz.shape)
+  if hz.ndim != 2 or hz.shape[0] != B:
+    raise ValueError(f"`horizons` must be [{B}, K] or [K], got shape {np.shape(horizons)}")
+  if not np.issubdtype(hz.dtype, np.integer):
+    if not (np.issubdtype(hz.dtype, np.floating) and np.all(hz == np.floor(hz))):
+      raise ValueError(f"`horizons` must hold integers, got dtype {hz.dtype}")
+  K = hz.shape[1]
+  if not 1 <= K <= MAX_PLACEBO_HORIZONS:
+    raise ValueError(f"`horizons` must have 1 to {MAX_PLACEBO_HORIZONS} slots per series, got {K}")
+  hz = np.ascontiguousarray(hz, dtype=np.int32)
+  for b in range(B):
+    row = hz[b]
+    used = int(np.count_nonzero(row != -1))
+    if used == 0:
+      raise ValueError(f"horizons[{b}] holds no horizon: every series needs at least one")
+    for i in range(K):
+      h = int(row[i])
+      if h == -1:
+        continue
+      if h < 1:
+        raise ValueError(f"horizons[{b}, {i}] must be at least 1, or -1 (unused), got {h}")
+      if i >= used or (i > 0 and h <= int(row[i - 1])):
+        raise ValueError(f"horizons[{b}] must be strictly ascending with the unused slots (-1) at the end "
+                         f"(slot {i} holds {h})")
+  return hz
 
 
 def series_stream_key(seed, series_id: int):
@@ -1224,6 +1267,45 @@ class Session:
     return self.summarize_placebo(scale, shift, origins, horizon, want,
                                   _entry="ci_session_summarize_placebo_blocks")
 
+  def summarize_placebo_horizons(self, scale, shift, origins, horizons, want=None,
+                                 max_rows=None) -> Dict[str, np.ndarray]:
+    """`summarize_placebo` at SEVERAL horizons from one filter pass
+    (ci_session_summarize_placebo_horizons): result[name][:, :, k] is, bit for bit, what
+    `summarize_placebo(scale, shift, origins, horizons[:, k])` returns -- every horizon looks from the
+    same origins.  scale, shift, origins: as there, with origin + the row's largest horizon within the
+    series; horizons [B, K] (or [K]: the same for every series) int, K <= 64: >= 1, strictly ascending,
+    -1 = unused, at the end of the row (`horizon_table`).  Returns float64 arrays [B, O, K] under the
+    names of `PLACEBO_OUTPUTS` (0 in the unused slots and where the window counts no observation);
+    `want`: the names to compute (default: all).  Models: a trend with at most one block of 2 to 7
+    seasons (for the others call `summarize_placebo_blocks` once per horizon).  max_rows (tests): the
+    rows of a chunk in place of the call's own capacity (ci_test_session_summarize_placebo_horizons);
+    the result then has "num_chunks" too."""
+    fn = _symbol(self._lib, "ci_session_summarize_placebo_horizons" if max_rows is None
+                 else "ci_test_session_summarize_placebo_horizons")
+    B = self.pb.num_series
+    org = np.asarray(origins)
+    if org.ndim == 1 and B == 1:
+      org = org[None]
+    if org.ndim != 2 or org.shape[0] != B:
+      raise ValueError(f"`origins` must be [{B}, O], got shape {org.shape}")
+    org = np.ascontiguousarray(org, dtype=np.int32)
+    hz = horizon_table(horizons, B)
+    sc, sh = _per_series("scale", scale, B), _per_series("shift", shift, B)
+    names = PLACEBO_OUTPUTS
+    if want is not None:
+      unknown = [k for k in want if k not in PLACEBO_OUTPUTS]
+      if unknown:
+        raise ValueError(f"unknown placebo outputs {unknown}: choose from {list(PLACEBO_OUTPUTS)}")
+      names = [k for k in PLACEBO_OUTPUTS if k in want]
+    arrs = {k: np.empty(org.shape + (hz.shape[1],), np.float64) for k in names}
+    chunks = C.c_int32(0)
+    _check(fn(self._h, sc.ctypes.data, sh.ctypes.data, int(org.shape[1]), org.ctypes.data, int(hz.shape[1]),
+              hz.ctypes.data, *[_ptr(arrs.get(k)) for k in PLACEBO_OUTPUTS],
+              *((int(max_rows), C.addressof(chunks)) if max_rows is not None else ())))
+    if max_rows is not None:
+      arrs["num_chunks"] = chunks.value
+    return arrs
+
   def simulate_placebo(self, scale, shift, origins, horizon, link, seen, ranks, want=None,
                        blocks: bool = False, max_rows=None) -> Dict[str, np.ndarray]:
     """On-device SIMULATED placebo forecasts of every fit (ci_session_simulate_placebo): for every
@@ -1497,7 +1579,7 @@ DRAW_FIELDS = ("observation_noise_scale", "level_scale", "slope_scale", "seasona
 class DrawsSession(Session):
   """A session made from draws (ci_session_create_from_draws[_f64]): the data and the pooled
   parameter draws of B fits, uploaded from the host, for the prediction-error and placebo entries
-  alone -- `summarize_predictions`, `summarize_placebo`, `simulate_placebo`, `pool_placebo`,
+  alone -- `summarize_predictions`, `summarize_placebo`, `summarize_placebo_horizons`, `simulate_placebo`, `pool_placebo`,
   `pool_simulated_placebo` and their `_blocks` forms, with the signatures and results they have on a
   fit's `Session`.  Every method that needs a fit (`run`, `fetch`, `summarize`, ..) raises NativeError.
 

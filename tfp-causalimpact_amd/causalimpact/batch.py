@@ -383,6 +383,7 @@ class CausalImpactBatchAnalysis:
     # record's placebo summary {name: [B, O]} as "summary", or None
     self._placebo = None if placebo_plan is None else dict(placebo_plan, summary=record.placebo)
     self._placebo_quality: Optional[pd.DataFrame] = None
+    self._placebo_profile: Optional[pd.DataFrame] = None
     # {name: [B, ...]} of ci_session_summarize_components (InferenceOptions.components), or None
     self._csum = record.components
     # {name: [B, ...]} of ci_session_summarize_predictions (InferenceOptions.prediction_errors), or
@@ -544,8 +545,42 @@ class CausalImpactBatchAnalysis:
                                                 *self._prediction_frames(b, ci_data, Tb),
                                                 self._window_slice(b),
                                                 *self._placebo_frames(b, ci_data, Tb, summary),
-                                                *self._joint_frames(b, effect_data, Tb))
+                                                *self._joint_frames(b, effect_data, Tb),
+                                                *self._placebo_horizon_frames(b, ci_data, Tb, summary))
     return self._cache[b]
+
+  def _placebo_horizon_frames(self, b: int, ci_data, num_steps: int, summary: pd.DataFrame):
+    """(placebo_by_horizon, placebo_profile) of series b, or (None, None) without `Placebo(horizons=...)`."""
+    pl = self._placebo
+    if pl is None or pl.get("horizons") is None:
+      return None, None
+    return lib._placebo_horizon_frames(                         # pylint: disable=protected-access
+        {k: v[b] for k, v in pl["summary"].items()}, pl["origins"][b], pl["horizons"][b], self.alpha,
+        self._prep.observed[b, :num_steps], lib.posterior_processing.model_index(ci_data),
+        int(pl["n_post"][b]), summary.loc["cumulative", "rel_effect"])
+
+  @property
+  def placebo_profile(self) -> Optional[pd.DataFrame]:
+    """`CausalImpactAnalysis.placebo_profile` of every series as one table indexed by (series, horizon)
+    (None without `Placebo(horizons=...)`): every series over the union of the horizons, NaN rows for
+    the horizons a series lacks (a panel's series keeps the listed horizons <= its own H)."""
+    pl = self._placebo
+    if pl is None or pl.get("horizons") is None:
+      return None
+    if self._placebo_profile is None:
+      rel = self.summary["rel_effect"].to_numpy()[1::2]          # (the cumulative rows)
+      tables = []
+      for b in range(len(self)):
+        per = []
+        if np.any(pl["origins"][b] >= 0):
+          per = lib._placebo_horizon_columns(                   # pylint: disable=protected-access
+              {k: v[b] for k, v in pl["summary"].items()}, pl["origins"][b], pl["horizons"][b], self.alpha,
+              self._prep.observed[b, :self._series_view(b)[3]])
+        rows = [lib._placebo_profile_row(cols, h, self.alpha, int(pl["n_post"][b]), rel[b]) for h, cols in per]   # pylint: disable=protected-access
+        tables.append(pd.DataFrame(rows, index=pd.Index([h for h, _ in per], dtype=np.int64, name="horizon"),
+                                   columns=list(lib.PLACEBO_PROFILE_COLUMNS)))
+      self._placebo_profile = _stack_profiles(tables, self._names)
+    return self._placebo_profile
 
   def _placebo_frames(self, b: int, ci_data, num_steps: int, summary: pd.DataFrame):
     """(placebo, placebo_quality) of series b, or (None, None) when they were not asked for."""
@@ -622,6 +657,16 @@ class CausalImpactBatchAnalysis:
     return (self[b] for b in range(len(self)))
 
 
+def _stack_profiles(tables: Sequence[pd.DataFrame], names) -> pd.DataFrame:
+  """The per-series `placebo_profile` tables as one, indexed by (series, horizon): every series over
+  the sorted union of the horizons, NaN rows where it lacks one."""
+  horizons = pd.Index(sorted({int(h) for t in tables for h in t.index}), dtype=np.int64, name="horizon")
+  columns = list(lib.PLACEBO_PROFILE_COLUMNS)
+  values = [t.reindex(horizons)[columns].to_numpy(np.float64) for t in tables]
+  index = pd.MultiIndex.from_product([list(names), horizons], names=["series", "horizon"])
+  return pd.DataFrame(np.concatenate(values) if values else np.zeros((0, len(columns))), index=index, columns=columns)
+
+
 class PerSeriesBatchAnalysis(CausalImpactBatchAnalysis):
   """The same container over analyses that were fitted one series at a time (the routes the
   one-launch path does not have: float64 compute, raw-scale outcomes)."""
@@ -658,6 +703,12 @@ class PerSeriesBatchAnalysis(CausalImpactBatchAnalysis):
       return None
     return pd.DataFrame([self._cache[b].placebo_quality for b in range(len(self))],
                         index=pd.Index(self._names, name="series"))
+
+  @property
+  def placebo_profile(self) -> Optional[pd.DataFrame]:
+    if any(a.placebo_profile is None for a in self._cache.values()):
+      return None
+    return _stack_profiles([self._cache[b].placebo_profile for b in range(len(self))], self._names)
 
   def diagnostics_of(self, b: int):
     return self._cache[range(len(self))[b]].diagnostics
@@ -1931,7 +1982,9 @@ def _fit_per_series(frames, periods, names, outcome_column, alpha, seed, data_op
                                         window_summary=one.window_summary, placebo=one.placebo,
                                         placebo_quality=one.placebo_quality, joint_bands=one.joint_bands,
                                         joint_summary=one.joint_summary,
-                                        window_joint_summary=one.window_joint_summary))
+                                        window_joint_summary=one.window_joint_summary,
+                                        placebo_by_horizon=one.placebo_by_horizon,
+                                        placebo_profile=one.placebo_profile))
   res = PerSeriesBatchAnalysis(names, alpha, analyses)
   if windows is not None:
     full = pd.MultiIndex.from_product([windows.names, ["average", "cumulative"]], names=["window", None])
@@ -1993,6 +2046,8 @@ class _Fit:
   # and horizon [B] (`placebo_plans`); the summary is put on the data scale with own_scale / own_shift
   placebo_origins: Optional[np.ndarray] = None
   placebo_horizon: Optional[np.ndarray] = None
+  # `Placebo(horizons=...)` only: every series' horizons [B, K] (`placebo_horizon_tables`)
+  placebo_horizons: Optional[np.ndarray] = None
   # `Placebo(simulate=True)` only: the (lower, upper) quantiles of the simulated totals the frames report
   placebo_quantiles: Optional[Tuple[float, float]] = None
   # `joint_bands=True` only: every series' windows of `summarize_paths` [B, 1 + W] (`lib.joint_windows`:
@@ -2011,7 +2066,7 @@ def _sampler_outcome(prep, data_options) -> np.ndarray:
 
 def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_options,
              shared_streams, windows: Optional[WindowPlan] = None, placebo=None,
-             joint_bands: bool = False, placebo_simulate: bool = False) -> _Fit:
+             joint_bands: bool = False, placebo_simulate: bool = False, placebo_horizons=None) -> _Fit:
   """The `_Fit` of a prepared batch or panel: y = `_sampler_outcome(prep)`, lengths [B], pre_sd [B]
   the sd of every series' own pre-period outcome; placebo: (origins [B, O], horizon [B]) or None."""
   own_shift = own_scale = None
@@ -2043,6 +2098,7 @@ def _new_fit(prep, y, lengths, pre_sd, alpha, seed, model_options, inference_opt
               own_scale=own_scale, own_shift=own_shift, windows=windows,
               placebo_origins=None if placebo is None else placebo[0],
               placebo_horizon=None if placebo is None else placebo[1],
+              placebo_horizons=None if placebo is None else placebo_horizons,
               placebo_quantiles=(alpha / 2.0, 1.0 - alpha / 2.0) if placebo is not None and placebo_simulate else None,
               paths=paths,
               path_ranks=lib._path_ranks(num_draws, alpha) if joint_bands else (),   # pylint: disable=protected-access
@@ -2059,6 +2115,21 @@ def placebo_plans(placebo: lib.Placebo, num_pre, num_post, state_dim: int):
   for b, (_, o) in enumerate(plans):
     origins[b, :len(o)] = o
   return origins, np.array([h for h, _ in plans], np.int32)
+
+
+def placebo_horizon_tables(placebo: Optional[lib.Placebo], horizon, strict: bool = True) -> Optional[np.ndarray]:
+  """horizons [B, K] int32 (-1: unused, at the end of a row) of B series from their plans' horizons
+  [B] -- `lib.placebo_horizon_list` of every series -- or None without `Placebo(horizons=...)`.  strict
+  (batches): a listed horizon beyond a series' H is a ValueError; off (panels): the series keeps the
+  listed horizons <= its own H.  A series whose H is below 1 has a row of -1."""
+  if placebo is None or placebo.horizons is None:
+    return None
+  rows = [lib.placebo_horizon_list(placebo, int(h), strict) for h in horizon]
+  table = np.full((len(rows), max(1, max(0 if r is None else len(r) for r in rows))), -1, np.int32)
+  for b, r in enumerate(rows):
+    if r is not None:
+      table[b, :len(r)] = r
+  return table
 
 
 def _run_launch(launch, kind: str, fit: _Fit, chain: Optional[_PoolChain] = None,
@@ -2144,7 +2215,8 @@ def _launch_request(fit: _Fit, ids, observed, flags) -> lib.SummaryRequest:
       components=io.components, predictions=own if io.prediction_errors else None,
       windows=None if fit.windows is None else lib.Windows(fit.windows.first[ids], fit.windows.count[ids]),
       placebo=None if fit.placebo_origins is None else lib.PlaceboPart(
-          *own, fit.placebo_origins[ids], fit.placebo_horizon[ids], **simulated),
+          *own, fit.placebo_origins[ids], fit.placebo_horizon[ids], **simulated,
+          horizons=None if fit.placebo_horizons is None else fit.placebo_horizons[ids]),
       paths=None if fit.paths is None else lib.Windows(fit.paths.first[ids], fit.paths.count[ids]),
       path_ranks=fit.path_ranks, link=fit.link, on_device=bool(getattr(io, "summarize_on_device", True)))
 
@@ -2341,6 +2413,11 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   independent of each other: the assumption the check tests.  `actual` and `n_counted` are the
   weighted sum and the plain sum (member-steps) of the members'.
 
+  `Placebo(horizons=...)` (see `lib.Placebo`): every `result[b]` gains `placebo_by_horizon` and
+  `placebo_profile`, and `result.placebo_profile` is one table indexed by (series, horizon) -- one
+  filter pass of the launch for all horizons (ci_session_summarize_placebo_horizons).  ValueError before
+  any fit for a listed horizon beyond H; the pooled placebo of `aggregates` stays at H.
+
   joint_bands: False (the default: nothing runs, no result differs) or True -- the simultaneous bands
   and the whole-path test of `fit_causalimpact` for every series: `result[b].joint_bands`,
   `result[b].joint_summary`, `result.joint_summary` as one table indexed by (series,
@@ -2443,11 +2520,12 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
     if not np.any(pl_plan[0] >= 0):
       raise ValueError(f"placebo: a pre-period of {prep.num_pre} steps has no room for an origin with "
                        f"horizon {int(pl_plan[1][0])} and the history it needs")
+  pl_hz = None if pl_plan is None else placebo_horizon_tables(placebo, pl_plan[1])
   y = _sampler_outcome(prep, data_options)
   with np.errstate(invalid="ignore"):
     pre_sd = np.nanstd(y[:, :prep.num_pre], axis=1, ddof=1)
   fit = _new_fit(prep, y, np.full(B, T), pre_sd, alpha, seed, model_options, inference_options,
-                 shared_streams, plan, pl_plan, joint_bands, placebo is not None and placebo.simulate)
+                 shared_streams, plan, pl_plan, joint_bands, placebo is not None and placebo.simulate, pl_hz)
   # a batch is the panel of one group of equal lengths: consecutive positions on every device
   launches = panel_launches(dict(route="equal_length", groups=[(T, list(range(B)))]),
                             inference_options.devices, shared_streams)
@@ -2475,7 +2553,7 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   res = CausalImpactBatchAnalysis(
       prep, names, alpha, means, record.effect, fit.ranks, columns, diag_draws, record,
       _state_dim(model_options, inference_options),
-      None if placebo is None else dict(origins=pl_plan[0], horizon=pl_plan[1], n_post=pl_post))
+      None if placebo is None else dict(origins=pl_plan[0], horizon=pl_plan[1], n_post=pl_post, horizons=pl_hz))
   if plan is not None:
     res.window_summary = _window_summary(res, plan, record.windows)
   if joint_bands:
@@ -2594,7 +2672,10 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   its members share (L - gap steps, Hwin), member k forecasts from its own step first_k + column --
   inside its own pre-period -- and `result.aggregates[name].placebo` is indexed by `event_time`
   (negative: before the treatment start).  A group without room for an origin has the empty frame and
-  the NaN row; `result.aggregate_placebo_quality` has one row per aggregate.
+  the NaN row; `result.aggregate_placebo_quality` has one row per aggregate.  With
+  `Placebo(horizons=...)` every series keeps the listed horizons <= its own H (none is refused) and
+  `result.placebo_profile`, indexed by (series, horizon), has NaN rows for the horizons a series lacks;
+  the pooled placebo of `event_aggregates` stays at its group's H.
 
   joint_bands: as in `fit_causalimpact_batch`, every series over its OWN post-period and the
   `effect_windows` in event time; `window_joint_summary` has NaN rows where a series' post-period does
@@ -2668,6 +2749,7 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   if placebo is not None:
     pl_post = np.array([np.count_nonzero(prep.flags[b, :Tb] & 2) for b, Tb in enumerate(prep.lengths)])
     pl_plan = placebo_plans(placebo, prep.num_pre, pl_post, pl_dim)
+  pl_hz = None if pl_plan is None else placebo_horizon_tables(placebo, pl_plan[1], strict=False)
   plan = None if agg is None else event_plan(*agg, prep, columns[0])
   wplan = None if effect_windows is None else panel_windows(effect_windows, prep)
   route = panel_route(float64=False, standardize_data=True, sampler="gibbs",
@@ -2678,7 +2760,7 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   with np.errstate(invalid="ignore"):
     pre_sd = [np.nanstd(y[b, :nb], ddof=1) for b, nb in enumerate(prep.num_pre)]
   fit = _new_fit(prep, y, prep.lengths, pre_sd, alpha, seed, model_options, inference_options,
-                 shared_streams, wplan, pl_plan, joint_bands, placebo is not None and placebo.simulate)
+                 shared_streams, wplan, pl_plan, joint_bands, placebo is not None and placebo.simulate, pl_hz)
   kind = "ordinary" if route["route"] == "equal_length" else route["route"]
   launches = panel_launches(route, inference_options.devices, shared_streams)
   chain = None if plan is None else _PoolChain(launches, plan.csr, plan.axes)
@@ -2694,7 +2776,7 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   res = CausalImpactPanelAnalysis(
       prep, names, alpha, means, record.effect, fit.ranks, columns, diag_draws, record,
       _state_dim(model_options, inference_options),
-      None if placebo is None else dict(origins=pl_plan[0], horizon=pl_plan[1], n_post=pl_post))
+      None if placebo is None else dict(origins=pl_plan[0], horizon=pl_plan[1], n_post=pl_post, horizons=pl_hz))
   if wplan is not None:
     res.window_summary = _window_summary(res, wplan, record.windows)
   if joint_bands:

@@ -156,9 +156,21 @@ class CausalImpactAnalysis:
   joint_bands: dataclasses.InitVar[Optional[pd.DataFrame]] = None
   joint_summary: dataclasses.InitVar[Optional[pd.DataFrame]] = None
   window_joint_summary: dataclasses.InitVar[Optional[pd.DataFrame]] = None
+  # `placebo=Placebo(horizons=...)` only: the placebo check at several horizons h <= H from the SAME
+  # origins (those of the plan at H).  `placebo_by_horizon`: the `PLACEBO_COLUMNS` indexed by (origin,
+  # horizon), horizon_end, n_counted, actual and the rest taken per horizon; `.xs(H, level="horizon")`
+  # is `placebo`.  `placebo_profile`: indexed by horizon, the `PLACEBO_PROFILE_COLUMNS` -- the entries
+  # of `placebo_quality` at that horizon (its last row is `placebo_quality`; empirical_p only on the row
+  # h == n_post) and relative_sd, the median over the counted origins of predicted_sd / |predicted|:
+  # how mde_relative and the false-positive rate move with the window's length, and from which horizon
+  # on the model drifts.  (Init-only and kept as plain attributes, as those above.)
+  placebo_by_horizon: dataclasses.InitVar[Optional[pd.DataFrame]] = None
+  placebo_profile: dataclasses.InitVar[Optional[pd.DataFrame]] = None
 
   def __post_init__(self, prediction_errors, fit_quality, window_summary=None, placebo=None,
-                    placebo_quality=None, joint_bands=None, joint_summary=None, window_joint_summary=None):
+                    placebo_quality=None, joint_bands=None, joint_summary=None, window_joint_summary=None,
+                    placebo_by_horizon=None, placebo_profile=None):
+    self.placebo_by_horizon, self.placebo_profile = placebo_by_horizon, placebo_profile
     self.prediction_errors, self.fit_quality = prediction_errors, fit_quality
     self.window_summary = window_summary
     self.placebo, self.placebo_quality = placebo, placebo_quality
@@ -289,7 +301,12 @@ def fit_causalimpact(data: pd.DataFrame,
   `PREDICTION_MAX_STATE` components.  `Placebo(simulate=True)`: the simulated placebo -- one path of
   every window per draw, the link applied step by step, band and `p` from the N totals
   (csrc/ci_placebo.h `placebo_sim_kernel`; `_placebo_simulated_host` on the other routes); the frame
-  gains `predicted_lower` and `predicted_upper`.
+  gains `predicted_lower` and `predicted_upper`.  `Placebo(horizons=...)`: the same check at several
+  horizons h <= H from the origins of the plan at H, in one pass of the filter
+  (ci_session_summarize_placebo_horizons; one call of the block-model entry per horizon for the
+  other block lists, `_placebo_summary_host(horizons=...)` in numpy): the result gains
+  `placebo_by_horizon` and `placebo_profile`; ValueError before any fit for a listed horizon beyond
+  H, for more than `MAX_PLACEBO_HORIZONS` and together with `simulate=True`.
 
   joint_bands (extension): False (the default: nothing runs, no result differs) or True.  The bands
   of `series` are pointwise: over a long post-period the observed series leaves them at several steps
@@ -364,8 +381,10 @@ def fit_causalimpact(data: pd.DataFrame,
     if origins.size == 0 and not placebo_lenient:
       raise ValueError(f"placebo: a pre-period of {n_pre} steps has no room for an origin with "
                        f"horizon {horizon} and the history it needs")
+    # (`Placebo(horizons=...)`: refused here, before the fit, where a listed horizon is beyond H)
+    placebo_horizons = placebo_horizon_list(placebo, horizon, strict=not placebo_lenient)
     if origins.size:
-      placebo_part = PlaceboPart(base["scale"], base["shift"], origins, horizon)
+      placebo_part = PlaceboPart(base["scale"], base["shift"], origins, horizon, horizons=placebo_horizons)
       if placebo.simulate:
         # (the simulation draws from the fit's own streams: a seed of None is settled here, once;
         #  one device or several, the chains are pooled in the order of their global ids)
@@ -459,6 +478,11 @@ def fit_causalimpact(data: pd.DataFrame,
     placebo_frame, placebo_quality = _placebo_frames(
         record.placebo, origins, horizon, alpha, base["observed"],
         posterior_processing.model_index(ci_data), n_post, summary.loc["cumulative", "rel_effect"])
+  by_horizon = (None, None)
+  if placebo is not None and placebo.horizons is not None:
+    by_horizon = _placebo_horizon_frames(
+        record.placebo, origins, placebo_horizons, alpha, base["observed"],
+        posterior_processing.model_index(ci_data), n_post, summary.loc["cumulative", "rel_effect"])
   joint = (None, None, None)
   if joint_bands:
     joint = _joint_frames(record.windows, request.path_ranks, num_draws, alpha, base["observed"],
@@ -466,7 +490,7 @@ def fit_causalimpact(data: pd.DataFrame,
                           [w.name for w in windows] if windows else None)
   return CausalImpactAnalysis(series, summary, posterior, samples.get("diagnostics"), components,
                               coefficients, prediction_errors, fit_quality, window_summary,
-                              placebo_frame, placebo_quality, *joint)
+                              placebo_frame, placebo_quality, *joint, *by_horizon)
 
 
 OUTCOME_LINKS = {None: _native.LINK_IDENTITY, "log": _native.LINK_LOG, "log1p": _native.LINK_LOG1P}
@@ -869,6 +893,17 @@ class Placebo:
                  gets `placebo` and `placebo_quality` from the N pooled totals.  The members' paths are
                  drawn independently of each other: the assumption a pooled band rests on, and the one
                  this check tests.  The only pooled placebo under `outcome_link`.
+    horizons     None (the default: nothing more runs, no result or bit differs).  Else the check at
+                 SEVERAL horizons h <= H (H: the horizon above) from the SAME origins -- those of the plan
+                 at H, so that the rows are comparable -- in one pass of the filter
+                 (ci_session_summarize_placebo_horizons): the result gains `placebo_by_horizon` and
+                 `placebo_profile`, the batch and panel results `placebo_profile`.  An int k >= 2: k
+                 horizons spread over 1..H, unique(max(1, (H i) // k)), i = 1..k; a sequence of ints:
+                 these horizons, each >= 1 and <= H (sorted, duplicates dropped; a panel's series keeps
+                 those <= its own H).  H is always the last one; at most `MAX_PLACEBO_HORIZONS` (64)
+                 remain.  Not with `simulate=True` (hence not under `outcome_link`).  With
+                 `aggregates=` / `event_aggregates=` the per-series tables are built and the POOLED
+                 placebo stays at H.
   Fixed-parameter: every draw's scales and weights are those of the one fit of the whole pre-period,
   so the check is cheap and somewhat optimistic; the windows overlap, so the origins are not
   independent trials."""
@@ -877,8 +912,36 @@ class Placebo:
   min_history: Optional[int] = None
   simulate: bool = False
   pool: bool = False
+  horizons: Any = None
 
   def __post_init__(self):
+    if self.horizons is not None:
+      hs = self.horizons
+      if isinstance(hs, (bool, np.bool_)):
+        raise TypeError(f"Placebo.horizons must be None, an int >= 2 or a sequence of ints, got {hs!r}")
+      if isinstance(hs, (int, np.integer)):
+        if int(hs) < 2:
+          raise ValueError(f"Placebo.horizons as a number of horizons must be at least 2, got {hs}")
+        if int(hs) > MAX_PLACEBO_HORIZONS:
+          raise ValueError(f"Placebo.horizons: at most {MAX_PLACEBO_HORIZONS} horizons, got {hs}")
+        object.__setattr__(self, "horizons", int(hs))
+      else:
+        try:
+          listed = [h for h in hs]
+        except TypeError:
+          raise TypeError(f"Placebo.horizons must be None, an int >= 2 or a sequence of ints, got {hs!r}") from None
+        if not listed or any(isinstance(h, (bool, np.bool_)) or not isinstance(h, (int, np.integer)) for h in listed):
+          raise TypeError(f"Placebo.horizons must list ints (at least one), got {hs!r}")
+        if min(listed) < 1:
+          raise ValueError(f"Placebo.horizons must be at least 1 each, got {min(listed)}")
+        listed = tuple(sorted({int(h) for h in listed}))
+        if len(listed) > MAX_PLACEBO_HORIZONS:
+          raise ValueError(f"Placebo.horizons: at most {MAX_PLACEBO_HORIZONS} horizons, got {len(listed)}")
+        object.__setattr__(self, "horizons", listed)
+      if self.simulate:
+        raise ValueError("Placebo.horizons is not available with `simulate=True` (hence not under `outcome_link`): "
+                         "the several-horizons table reads the analytic forecast's running moments, and a "
+                         "simulated path is drawn for one horizon")
     if not isinstance(self.simulate, (bool, np.bool_)):
       raise TypeError(f"Placebo.simulate must be True or False, got {self.simulate!r}")
     if not isinstance(self.pool, (bool, np.bool_)):
@@ -968,6 +1031,30 @@ def placebo_plan(placebo: Placebo, n_pre: int, n_post: int, state_dim: int):
   horizon = placebo_horizon(placebo, n_pre, n_post)
   return horizon, placebo_origins(n_pre, horizon, placebo_min_history(placebo, horizon, state_dim),
                                   placebo.max_origins)
+
+
+MAX_PLACEBO_HORIZONS = _native.MAX_PLACEBO_HORIZONS
+
+
+def placebo_horizon_list(placebo: Placebo, horizon: int, strict: bool = True) -> Optional[np.ndarray]:
+  """The horizons [K] (ascending, int32, the last one `horizon` = H) of `Placebo.horizons` for a series
+  whose plan has the horizon H; None when the option is off or H < 1.  An int k: unique(max(1, (H i) //
+  k)), i = 1..k.  A sequence: its entries (sorted, unique) -- one above H is a ValueError naming the
+  option, or with strict off (a panel's series) dropped -- and H.  More than `MAX_PLACEBO_HORIZONS`:
+  ValueError."""
+  if placebo is None or placebo.horizons is None or int(horizon) < 1:
+    return None
+  H, hs = int(horizon), placebo.horizons
+  if isinstance(hs, int):
+    out = sorted({max(1, (H * i) // hs) for i in range(1, hs + 1)})
+  else:
+    if strict and hs[-1] > H:
+      raise ValueError(f"Placebo.horizons: the horizon {hs[-1]} is beyond the placebo horizon {H} "
+                       "(Placebo.horizon, else min(n_post, n_pre // 3)): every listed horizon must be <= it")
+    out = sorted({h for h in hs if h <= H} | {H})
+  if len(out) > MAX_PLACEBO_HORIZONS:
+    raise ValueError(f"Placebo.horizons: at most {MAX_PLACEBO_HORIZONS} horizons, got {len(out)} with H = {H}")
+  return np.array(out, np.int32)
 
 
 def placebo_state_dim(local_linear_trend: bool, seasons: Sequence) -> int:
@@ -1080,7 +1167,7 @@ class _PlaceboFilter:
 
 
 def _placebo_summary_host(y, mask, X, season_change, num_seasons, has_slope, params, draws,
-                          scale, shift, origins, horizon, per_draw: bool = False) -> Dict:
+                          scale, shift, origins, horizon=None, per_draw: bool = False, horizons=None) -> Dict:
   """The placebo summary of one series in numpy, from the pooled PARAMETER draws alone: the
   definitions of ci_session_summarize_placebo (include/causalimpact_amd.h) in float64, for any block
   list of up to `PREDICTION_MAX_STATE` state components.  The arguments but the last three are those
@@ -1088,13 +1175,27 @@ def _placebo_summary_host(y, mask, X, season_change, num_seasons, has_slope, par
   strictly ascending (-1: an unused slot, at the end); horizon: steps per window, origin + horizon <= T.
   Returns predicted_mean, spread_mean, pit_mean [O] (0 in an unused slot and where the window counts
   no observation), as the device returns them for one series; with `per_draw` also C, V [O, N] (the
-  conditional mean and predictive variance of the counted sum, in the sampler's units), A and cnt [O]."""
+  conditional mean and predictive variance of the counted sum, in the sampler's units), A and cnt [O].
+  horizons [K] (ascending, -1: unused, at the end; `horizon` is then their last one, whatever is passed):
+  the one forecast loop records its running values at the checkpoints h == horizons[k] and the three
+  outputs are [O, K] -- column k what `horizon=horizons[k]` returns, bit for bit (0 in an unused slot);
+  not with `per_draw`."""
+  if horizons is not None:
+    hz = [int(h) for h in np.asarray(horizons).reshape(-1)]
+    marks = [h for h in hz if h != -1]
+    if (per_draw or not marks or min(marks) < 1 or marks != hz[:len(marks)]
+        or any(b <= a for a, b in zip(marks, marks[1:]))):
+      raise ValueError("placebo horizons must be at least 1 and strictly ascending with the unused slots (-1) at "
+                       "the end, at least one of them (and not with per_draw)")
+    horizon = marks[-1]
   flt = _PlaceboFilter(y, mask, X, season_change, num_seasons, has_slope, params, draws, origins, horizon)
   y, mask, reg, Z, H, N, d, Hn, transition = flt.y, flt.mask, flt.reg, flt.Z, flt.H, flt.N, flt.d, flt.Hn, flt.transition
   scale, shift = np.float64(scale), np.float64(shift)
   O = len(flt.origins)
   Cs, Vs, As, cnts = np.zeros((N, O)), np.zeros((N, O)), np.zeros(O), np.zeros(O)
-  sums, spreads, pits = np.zeros((N, O)), np.zeros((N, O)), np.zeros((N, O))
+  marks = [Hn] if horizons is None else marks
+  # (one [N, O] matrix per checkpoint and output: the means below are taken as those of one horizon)
+  sums, spreads, pits = ([np.zeros((N, O)) for _ in marks] for _ in range(3))
   for slot, t, a, P in flt.at_origins():
     # the forecast branch, from the predicted moments
     fa, fP, r = a, P, np.zeros((N, d))
@@ -1108,17 +1209,20 @@ def _placebo_summary_host(y, mask, X, season_change, num_seasons, has_slope, par
         cnt += 1
         V = V + ((2.0 * (r @ Z) + pz @ Z) + H)
         r = r + pz
+      if h + 1 in marks and cnt:
+        k, e = marks.index(h + 1), A - C
+        sums[k][:, slot] = C * scale + np.float64(cnt) * shift
+        spreads[k][:, slot] = ((V + e * e) * scale) * scale
+        pits[k][:, slot] = 0.5 * _erfc(-e / np.sqrt(2.0 * V))
       if h + 1 < Hn:
         Tm, Q = transition(u)
         fa, r = fa @ Tm.T, r @ Tm.T
         fP = Tm @ fP @ Tm.T + Q
     Cs[:, slot], Vs[:, slot], As[slot], cnts[slot] = C, V, A, cnt
-    if cnt:
-      e = A - C
-      sums[:, slot] = C * scale + np.float64(cnt) * shift
-      spreads[:, slot] = ((V + e * e) * scale) * scale
-      pits[:, slot] = 0.5 * _erfc(-e / np.sqrt(2.0 * V))
-  out = dict(predicted_mean=sums.mean(axis=0), spread_mean=spreads.mean(axis=0), pit_mean=pits.mean(axis=0))
+  if horizons is not None:
+    table = lambda mats: np.stack([m.mean(axis=0) for m in mats] + [np.zeros(O)] * (len(hz) - len(marks)), axis=1)   # pylint: disable=unnecessary-lambda-assignment
+    return dict(predicted_mean=table(sums), spread_mean=table(spreads), pit_mean=table(pits))
+  out = dict(predicted_mean=sums[0].mean(axis=0), spread_mean=spreads[0].mean(axis=0), pit_mean=pits[0].mean(axis=0))
   if per_draw:
     out.update(C=Cs.T.copy(), V=Vs.T.copy(), A=As, cnt=cnts)
   return out
@@ -1194,21 +1298,32 @@ def _placebo_simulated_host(y, mask, X, season_change, num_seasons, has_slope, p
   return out
 
 
-def _placebo_seen(y_seen, mask, origins, horizon: int, scale, shift):
+def _placebo_seen(y_seen, mask, origins, horizon: int, scale, shift, horizons=None):
   """(n_counted [O], seen_sum [O]) of a series' placebo windows: the observed steps of every window
   and the sum over them of the outcome AS THE SAMPLER SAW IT (y_seen, in its number format and
   units), accumulated ascending in float64 and mapped to the data scale: A * scale + cnt * shift --
-  the value every route's pit and spread are taken at.  0 and NaN for an unused slot (-1)."""
+  the value every route's pit and spread are taken at.  0 and NaN for an unused slot (-1).
+  horizons [K] (ascending, -1: unused, at the end; `horizon` at least their last one): both [O, K],
+  the PREFIXES of the same running sums -- column k what `horizon=horizons[k]` returns, bit for bit;
+  0 and NaN in an unused horizon slot."""
   y_seen = np.asarray(y_seen, np.float64)
   mask = np.asarray(mask, bool)
   origins = np.asarray(origins).reshape(-1)
-  n_counted, seen_sum = np.zeros(origins.size), np.full(origins.size, np.nan)
+  shape = (origins.size,) if horizons is None else (origins.size, np.size(horizons))
+  n_counted, seen_sum = np.zeros(shape), np.full(shape, np.nan)
   used = origins >= 0
   if used.any():
     steps = origins[used].astype(np.int64)[:, None] + np.arange(int(horizon))[None, :]     # [O, H]
     seen = ~mask[steps]
     # (a masked step adds 0.0; cumsum adds left to right: the ascending sum)
-    A = np.cumsum(np.where(seen, y_seen[steps], 0.0), axis=1)[:, -1]
+    sums = np.cumsum(np.where(seen, y_seen[steps], 0.0), axis=1)
+    if horizons is not None:
+      for k, h in enumerate(int(h) for h in np.asarray(horizons).reshape(-1)):
+        if h >= 1:
+          cnt = seen[:, :h].sum(axis=1).astype(np.float64)
+          n_counted[used, k], seen_sum[used, k] = cnt, sums[:, h - 1] * np.float64(scale) + cnt * np.float64(shift)
+      return n_counted, seen_sum
+    A = sums[:, -1]
     cnt = seen.sum(axis=1).astype(np.float64)
     n_counted[used], seen_sum[used] = cnt, A * np.float64(scale) + cnt * np.float64(shift)
   return n_counted, seen_sum
@@ -1293,6 +1408,67 @@ def _placebo_frames(psum: Optional[Dict], origins, horizon: int, alpha: float, o
   frame.index.name = "origin"
   shown = list(PLACEBO_COLUMNS) + [k for k in PLACEBO_SIMULATED_COLUMNS if k in cols]
   return frame[shown], _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
+
+
+# `placebo_profile`: the quality entries but the horizon (the index), and the model's own statement of
+# the noise at that horizon
+PLACEBO_PROFILE_COLUMNS = tuple(k for k in PLACEBO_QUALITY_ENTRIES if k != "horizon") + ("relative_sd",)
+
+
+def _placebo_profile_row(cols: Optional[Dict[str, np.ndarray]], horizon: int, alpha: float, n_post: int,
+                         fit_relative_effect) -> Dict[str, float]:
+  """One row of `placebo_profile`: `_placebo_quality` on the columns of that horizon without its
+  `horizon` entry (empirical_p hence on the row horizon == n_post alone), and relative_sd, the median
+  over the counted origins of predicted_sd / |predicted|."""
+  quality = _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
+  row = {k: float(quality[k]) for k in PLACEBO_PROFILE_COLUMNS[:-1]}
+  row["relative_sd"] = float("nan")
+  if cols is not None:
+    ok = np.asarray(cols["n_counted"]) > 0
+    if ok.any():
+      with np.errstate(invalid="ignore", divide="ignore"):
+        row["relative_sd"] = float(np.median(np.asarray(cols["predicted_sd"])[ok] / np.abs(np.asarray(cols["predicted"])[ok])))
+  return row
+
+
+def _placebo_horizon_columns(psum: Dict, origins, horizons, alpha: float, observed):
+  """[(h, `_placebo_columns` at h)] for the used horizons of one series, from the
+  `PLACEBO_HORIZON_ARRAYS` [O, K] of its placebo summary: column k read as the summary of horizon
+  horizons[k]."""
+  out = []
+  for k, h in enumerate(int(h) for h in np.asarray(horizons).reshape(-1)):
+    if h >= 1:
+      at = {name: np.asarray(psum["horizons_" + name])[:, k]
+            for name in ("predicted_mean", "spread_mean", "pit_mean", "n_counted", "seen_sum")}
+      out.append((h, _placebo_columns(at, origins, h, alpha, observed)))
+  return out
+
+
+def _placebo_horizon_frames(psum: Optional[Dict], origins, horizons, alpha: float, observed,
+                            model_idx: pd.Index, n_post: int, fit_relative_effect):
+  """(placebo_by_horizon, placebo_profile) of one series with `Placebo(horizons=...)`: the
+  `PLACEBO_COLUMNS` indexed by (origin, horizon) -- the slice at a horizon is the `placebo` frame that
+  horizon alone would give, from the same origins -- and the `PLACEBO_PROFILE_COLUMNS` indexed by
+  horizon.  psum None, no origin or no horizon: empty frames."""
+  origins = np.asarray(origins).reshape(-1)
+  per = []
+  if psum is not None and horizons is not None and np.any(origins >= 0):
+    per = _placebo_horizon_columns(psum, origins, horizons, alpha, observed)
+  if not per:
+    index = pd.MultiIndex.from_arrays([model_idx[:0], np.zeros(0, np.int64)], names=["origin", "horizon"])
+    return (pd.DataFrame({k: np.zeros(0) for k in PLACEBO_COLUMNS}, index=index),
+            pd.DataFrame({k: np.zeros(0) for k in PLACEBO_PROFILE_COLUMNS}, index=pd.Index([], dtype=np.int64, name="horizon")))
+  frames, rows = [], []
+  for h, cols in per:
+    rows.append(_placebo_profile_row(cols, h, alpha, n_post, fit_relative_effect))
+    end = cols.pop("horizon_end_step")
+    frame = pd.DataFrame({"horizon_end": model_idx[end], **cols}, index=model_idx[origins[origins >= 0]])
+    frame.index.name = "origin"
+    frames.append(frame[list(PLACEBO_COLUMNS)])
+  by_horizon = pd.concat(frames, keys=[h for h, _ in per], names=["horizon", "origin"]).swaplevel().sort_index()
+  profile = pd.DataFrame(rows, index=pd.Index([h for h, _ in per], dtype=np.int64, name="horizon"),
+                         columns=list(PLACEBO_PROFILE_COLUMNS))
+  return by_horizon, profile
 
 
 def _aggregate_placebo_frames(psum: Optional[Dict], actual, columns, horizon: int, alpha: float,
@@ -1580,6 +1756,10 @@ class PlaceboPart(NamedTuple):
   quantiles: Optional[Tuple[float, float]] = None
   link: int = 0
   streams: Any = None
+  # `Placebo(horizons=...)` only: the horizons [K] or [B, K] (ascending, -1: unused, at the end of a row;
+  # the last used one is `horizon`) the same origins are also looked from -- the placebo kind then has
+  # the `PLACEBO_HORIZON_ARRAYS` [B, O, K] too
+  horizons: Any = None
 
 
 @dataclasses.dataclass(frozen=True)
@@ -1633,6 +1813,11 @@ class SummaryRecord:
     return self.map(lambda _, arrays: {k: v[b] for k, v in arrays.items()})
 
 
+# `Placebo(horizons=...)`: the five arrays of the placebo kind at every horizon, [B, O, K]
+PLACEBO_HORIZON_ARRAYS = ("horizons_predicted_mean", "horizons_spread_mean", "horizons_pit_mean",
+                          "horizons_n_counted", "horizons_seen_sum")
+
+
 class SummaryKind(NamedTuple):
   """How the arrays of one kind are laid out: series first and, but for the names in `whole`, time
   last -- cut to a series' length, and padded with `fill` beyond it when launches are put together."""
@@ -1650,7 +1835,7 @@ SUMMARY_KINDS = {
                             "path_at", "path_exceed"), np.nan),
     # [B, O]; predicted_lower, predicted_upper on the simulated route (`Placebo(simulate=True)`) only
     "placebo": SummaryKind(("predicted_mean", "spread_mean", "pit_mean", "n_counted", "seen_sum"),
-                           np.nan, ("predicted_lower", "predicted_upper"))}
+                           np.nan, ("predicted_lower", "predicted_upper") + PLACEBO_HORIZON_ARRAYS)}
 # the parameter draws the prediction errors and the placebo forecasts are filtered from on the host
 _PARAMETER_DRAWS = ("observation_noise_scale", "level_scale", "slope_scale", "seasonal_drift_scales",
                     "weights")
@@ -1724,12 +1909,32 @@ def _host_placebo_summaries(inputs: Sequence[SeriesInputs], draws, part: Placebo
   """The same for the placebo summary (`_placebo_summary_host`; `part` per series: `_per_series`); a
   series without an origin stays at zero."""
   out = {k: np.zeros(part.origins.shape) for k in SUMMARY_KINDS["placebo"].whole[:3]}
+  if part.horizons is not None:
+    # (`Placebo(horizons=...)`: the one loop records the checkpoints; the columns at H are the summary at H)
+    table = {k: np.zeros(part.origins.shape + (part.horizons.shape[1],)) for k in out}
+    for i, one in enumerate(inputs):
+      if np.any(part.origins[i] >= 0):
+        got = _placebo_summary_host(*one.filter_inputs(), _pooled_draws(draws, i), part.scale[i],
+                                    part.shift[i], part.origins[i], horizons=part.horizons[i])
+        for k, v in got.items():
+          table[k][i] = v
+    return _placebo_with_horizons(table, part)
   for i, one in enumerate(inputs):
     if np.any(part.origins[i] >= 0):
       got = _placebo_summary_host(*one.filter_inputs(), _pooled_draws(draws, i), part.scale[i],
                                   part.shift[i], part.origins[i], part.horizon[i])
       for k, v in got.items():
         out[k][i] = v
+  return out
+
+
+def _placebo_with_horizons(table: Dict[str, np.ndarray], part: PlaceboPart) -> Dict[str, np.ndarray]:
+  """The placebo summary {name: [n, O]} at H -- every series' LAST used column of `table` {name:
+  [n, O, K]}: the checkpoint at H is the forecast at H -- and the table itself under the
+  `PLACEBO_HORIZON_ARRAYS` names."""
+  last = np.maximum((np.asarray(part.horizons) > 0).sum(axis=1) - 1, 0)
+  out = {k: np.take_along_axis(v, last[:, None, None], axis=2)[:, :, 0] for k, v in table.items()}
+  out.update({"horizons_" + k: v for k, v in table.items()})
   return out
 
 
@@ -1827,6 +2032,25 @@ def _device_placebo_summaries(sess, part: PlaceboPart, blocks: bool = False):
   of a series without origin raised to the 1 the entry asks for."""
   width = max(1, int((part.origins >= 0).sum(axis=1).max()))
   entry = sess.summarize_placebo_blocks if blocks else sess.summarize_placebo
+  if part.horizons is not None:
+    # `Placebo(horizons=...)`: ONE filter pass for all horizons (`summarize_placebo_horizons`); for the
+    # block models one call of `summarize_placebo_blocks` per horizon slot, the same origins -- the same
+    # definitions, a series without that slot at its own H (not read)
+    hz = np.asarray(part.horizons)
+    table = {k: np.zeros(part.origins.shape + (hz.shape[1],)) for k in _native.PLACEBO_OUTPUTS}
+    if blocks:
+      for k in range(hz.shape[1]):
+        used = hz[:, k] > 0
+        if used.any():
+          got = entry(part.scale, part.shift, part.origins[:, :width],
+                      np.where(used, hz[:, k], np.maximum(part.horizon, 1)))
+          for name, v in got.items():
+            table[name][used, :width, k] = v[used]
+    else:
+      rows = np.where((hz > 0).any(axis=1)[:, None], hz, np.array([1] + [-1] * (hz.shape[1] - 1))[None, :])
+      for name, v in sess.summarize_placebo_horizons(part.scale, part.shift, part.origins[:, :width], rows).items():
+        table[name][:, :width] = v
+    return _placebo_with_horizons(table, part)
   got = entry(part.scale, part.shift, part.origins[:, :width], np.maximum(part.horizon, 1))
   out = {k: np.zeros(part.origins.shape) for k in got}
   for k, v in got.items():
@@ -1872,7 +2096,9 @@ def _per_series(part: PlaceboPart, n: int) -> PlaceboPart:
   return part._replace(scale=np.broadcast_to(np.asarray(part.scale, np.float64), (n,)),
                        shift=np.broadcast_to(np.asarray(part.shift, np.float64), (n,)),
                        origins=np.broadcast_to(origins, (n, origins.shape[-1])),
-                       horizon=np.broadcast_to(np.asarray(part.horizon), (n,)), streams=streams)
+                       horizon=np.broadcast_to(np.asarray(part.horizon), (n,)), streams=streams,
+                       horizons=None if part.horizons is None else
+                       np.broadcast_to(np.asarray(part.horizons), (n, np.shape(part.horizons)[-1])))
 
 
 def _placebo_seen_linked(observed, mask, origins, horizon: int, link: int):
@@ -1990,7 +2216,12 @@ def _with_placebo_seen(inputs: Sequence[SeriesInputs], part: PlaceboPart, plsum)
   """`plsum` {name: [n, O]} with `_placebo_seen`'s n_counted and seen_sum of every series."""
   seen = [_placebo_seen(one.outcome(), one.mask, part.origins[i], part.horizon[i],
                         part.scale[i], part.shift[i]) for i, one in enumerate(inputs)]
-  return dict(plsum, n_counted=np.stack([c for c, _ in seen]), seen_sum=np.stack([a for _, a in seen]))
+  out = dict(plsum, n_counted=np.stack([c for c, _ in seen]), seen_sum=np.stack([a for _, a in seen]))
+  if part.horizons is not None:        # (`Placebo(horizons=...)`: the prefixes of the same sums)
+    seen = [_placebo_seen(one.outcome(), one.mask, part.origins[i], max(int(part.horizon[i]), 1),
+                          part.scale[i], part.shift[i], horizons=part.horizons[i]) for i, one in enumerate(inputs)]
+    out.update(horizons_n_counted=np.stack([c for c, _ in seen]), horizons_seen_sum=np.stack([a for _, a in seen]))
+  return out
 
 
 def take_summaries(sess, request: SummaryRequest,

@@ -1,6 +1,6 @@
 // ci_forecast.hip -- the Kalman-filter entries of a finished session behind the C-ABI:
 // ci_session_summarize_predictions[_blocks] (kernels: ci_predict.h, ci_predict_blocks.h),
-// ci_session_summarize_placebo[_blocks], ci_session_simulate_placebo[_blocks],
+// ci_session_summarize_placebo[_blocks], ci_session_summarize_placebo_horizons, ci_session_simulate_placebo[_blocks],
 // ci_session_pool_placebo[_blocks], ci_session_pool_simulated_placebo[_blocks] (kernels: ci_placebo.h,
 // ci_placebo_blocks.h) and their ci_test_ entries; and ci_session_create_from_draws[_f64], the session
 // that holds what these entries read and nothing else.  A host unit: it instantiates no kernel -- the
@@ -249,6 +249,98 @@ static int summarize_placebo(ci_session* s, bool blocks, const double* scale, co
   if (spread_mean && pass(ci::PLACEBO_SPREAD, spread_mean)) return 1;
   if (pit_mean && pass(ci::PLACEBO_PIT, pit_mean)) return 1;
   HIP_TRY(hipStreamSynchronize(stream));   // (the uploads of a call that asks for nothing)
+  return 0;
+}
+
+// The horizon table of ci_session_summarize_placebo_horizons: max_horizons in [1, 64], every row with
+// at least one horizon, >= 1, strictly ascending, -1 only at the end.  last [B]: the row's largest.
+static int check_horizon_table(int B, int K, const int32_t* horizons, std::vector<int32_t>& last) {
+  if (K < 1 || K > 64) return fail("max_horizons must be in [1, 64], got %d", K);
+  last.assign(B, 0);
+  for (int b = 0; b < B; ++b) {
+    const int32_t* row = horizons + (size_t)b * K;
+    bool ended = false;
+    for (int i = 0; i < K; ++i) {
+      const int h = row[i];
+      if (h == -1) { ended = true; continue; }
+      if (h < 1) return fail("horizons[%d, %d] must be at least 1, or -1 (unused), got %d", b, i, h);
+      if (ended || (i > 0 && h <= row[i - 1]))
+        return fail("horizons[%d] must be strictly ascending with the unused slots (-1) at the end "
+                    "(slot %d holds %d)", b, i, h);
+      last[b] = h;
+    }
+    if (last[b] < 1) return fail("horizons[%d] holds no horizon: every series needs at least one", b);
+  }
+  return 0;
+}
+
+// ci_session_summarize_placebo_horizons: summarize_placebo's three outputs at K horizons per series
+// from ONE filter pass per chunk of whole series.  The chunk's three planes [nb * O * K, N] lie in
+// `value` where one series' 3 * O * K rows fit the scratch's B * T, else in a buffer of the call's own
+// of at most CI_PATHS_MAX_BYTES; comp_launch_row_stats then takes the wanted planes' row means.  Every
+// value is a function of (b, slot, k, n) alone and every mean one of its row, so nothing depends on
+// where the chunks are cut.  max_rows (tests; 0: the capacity above): the rows of a chunk; num_chunks
+// (may be NULL): how many it took.
+static int summarize_placebo_horizons(ci_session* s, const double* scale, const double* shift,
+                                      int32_t max_origins, const int32_t* origins, int32_t max_horizons,
+                                      const int32_t* horizons, double* predicted_mean, double* spread_mean,
+                                      double* pit_mean, int64_t max_rows, int32_t* num_chunks) {
+  if (!s || !scale || !shift || !origins || !horizons) return fail("NULL argument");
+  if (pred_check_session(s, false, "ci_session_summarize_placebo_horizons")) return 1;
+  const ci_problem& pb = s->pb;
+  const int B = pb.num_series, T = pb.T, N = pb.num_chains * pb.num_results;
+  const int O = max_origins, K = max_horizons;
+  std::vector<int32_t> last;
+  if (check_horizon_table(B, K, horizons, last)) return 1;
+  if (check_placebo_plan(s, O, origins, last.data())) return 1;
+  const size_t per = (size_t)3 * O * K;          // the rows of one series, all planes
+  const size_t scratch_rows = (size_t)B * T;
+  const size_t own_rows = (size_t)CI_PATHS_MAX_BYTES / sizeof(double) / N;
+  const bool in_scratch = per <= scratch_rows;
+  if (!in_scratch && per > own_rows)
+    return fail("ci_session_summarize_placebo_horizons: the %d origins x %d horizons of one series (series 0) "
+                "take %zu bytes of device memory for %d draws, the limit is %lld", O, K,
+                per * N * sizeof(double), N, (long long)CI_PATHS_MAX_BYTES);
+  if (max_rows < 0 || (max_rows > 0 && (size_t)max_rows < per))
+    return fail("max_rows must hold the %zu rows of one series (3 x %d origins x %d horizons), got %lld", per, O,
+                K, (long long)max_rows);
+  size_t cap = in_scratch ? scratch_rows : own_rows;
+  if (max_rows > 0 && (size_t)max_rows < cap) cap = (size_t)max_rows;
+  size_t fit = cap / per;
+  fit = fit > 65535 ? 65535 : fit;               // (grid.y)
+  const int nb_max = fit < (size_t)B ? (int)fit : B;
+  if (num_chunks) *num_chunks = (B + nb_max - 1) / nb_max;
+  ForecastCall c;
+  if (forecast_call(c, s, false, scale, shift)) return 1;
+  hipStream_t stream = c.stream;
+  SummScratch& w = *c.w;
+  const size_t BO = (size_t)B * O, BK = (size_t)B * K, BOK = BO * K;
+  DevBuf<int> d_plan;                    // origins [B, O], then horizons [B, K]
+  DevBuf<double> d_mean, d_own;          // the three outputs [3, B, O, K]; the planes of a chunk (not in_scratch)
+  HIP_TRY(d_plan.alloc(BO + BK));
+  HIP_TRY(d_mean.alloc(3 * BOK));
+  if (!in_scratch) HIP_TRY(d_own.alloc((size_t)nb_max * per * N));
+  HIP_TRY(hipMemcpyAsync(d_plan.p, origins, BO * sizeof(int), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_plan.p + BO, horizons, BK * sizeof(int), hipMemcpyHostToDevice, stream));
+  double* const dst[3] = {predicted_mean, spread_mean, pit_mean};
+  ci::PlaceboHorizonsArgs a;
+  a.p = c.p;
+  a.p.out = in_scratch ? w.value.p : d_own.p;
+  a.O = O; a.origins = d_plan.p; a.K = K; a.horizons = d_plan.p + BO;
+  for (int b0 = 0; b0 < B; b0 += nb_max) {
+    const int nb = B - b0 < nb_max ? B - b0 : nb_max;
+    a.b0 = b0;
+    a.rows = (size_t)nb * O * K;
+    HIP_TRY((c.f64 ? ci::placebo_horizons_launch_f64 : ci::placebo_horizons_launch)(stream, nb, c.has_slope, c.NS, a));
+    for (int plane = 0; plane < 3; ++plane)
+      if (dst[plane])
+        HIP_TRY(ci::comp_launch_row_stats(stream, a.rows, N, a.p.out + (size_t)plane * a.rows * N,
+                                          d_mean.p + (size_t)plane * BOK + (size_t)b0 * O * K, nullptr));
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (int plane = 0; plane < 3; ++plane)
+    if (dst[plane])
+      HIP_TRY(hipMemcpy(dst[plane], d_mean.p + (size_t)plane * BOK, BOK * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -750,6 +842,23 @@ int ci_session_summarize_placebo_blocks(ci_session* s, const double* scale, cons
                                         double* predicted_mean, double* spread_mean, double* pit_mean) {
   return summarize_placebo(s, true, scale, shift, max_origins, origins, horizon, predicted_mean, spread_mean,
                            pit_mean);
+}
+
+int ci_session_summarize_placebo_horizons(ci_session* s, const double* scale, const double* shift,
+                                          int32_t max_origins, const int32_t* origins, int32_t max_horizons,
+                                          const int32_t* horizons, double* predicted_mean, double* spread_mean,
+                                          double* pit_mean) {
+  return summarize_placebo_horizons(s, scale, shift, max_origins, origins, max_horizons, horizons, predicted_mean,
+                                    spread_mean, pit_mean, 0, nullptr);
+}
+
+int ci_test_session_summarize_placebo_horizons(ci_session* s, const double* scale, const double* shift,
+                                               int32_t max_origins, const int32_t* origins, int32_t max_horizons,
+                                               const int32_t* horizons, double* predicted_mean,
+                                               double* spread_mean, double* pit_mean, int64_t max_rows,
+                                               int32_t* num_chunks) {
+  return summarize_placebo_horizons(s, scale, shift, max_origins, origins, max_horizons, horizons, predicted_mean,
+                                    spread_mean, pit_mean, max_rows, num_chunks);
 }
 
 int ci_session_simulate_placebo(ci_session* s, const double* scale, const double* shift, int32_t max_origins,

@@ -100,6 +100,32 @@ hipError_t CI_FILTER_NAME(placebo_sim_entries_launch)(hipStream_t stream, int E,
   return hipGetLastError();
 }
 
+using PlaceboHorizonsFn = void (*)(PlaceboHorizonsArgs);
+
+template <int HAS_SLOPE> static PlaceboHorizonsFn placebo_horizons_fn(int ns) {
+  switch (ns) {
+    case 0: return placebo_horizons_kernel<HAS_SLOPE, 0, CI_FILTER_F>;
+    case 2: return placebo_horizons_kernel<HAS_SLOPE, 2, CI_FILTER_F>;
+    case 3: return placebo_horizons_kernel<HAS_SLOPE, 3, CI_FILTER_F>;
+    case 4: return placebo_horizons_kernel<HAS_SLOPE, 4, CI_FILTER_F>;
+    case 5: return placebo_horizons_kernel<HAS_SLOPE, 5, CI_FILTER_F>;
+    case 6: return placebo_horizons_kernel<HAS_SLOPE, 6, CI_FILTER_F>;
+    case 7: return placebo_horizons_kernel<HAS_SLOPE, 7, CI_FILTER_F>;
+    default: return nullptr;
+  }
+}
+
+// The three planes [nb * O * K, N] each of `nb` series from args.b0 on in args.p.out, one filter pass;
+// num_seasons 0 (no block) or 2..7.
+hipError_t CI_FILTER_NAME(placebo_horizons_launch)(hipStream_t stream, int nb, int has_slope, int num_seasons,
+                                   const PlaceboHorizonsArgs& args) {
+  const PlaceboHorizonsFn fn = has_slope ? placebo_horizons_fn<1>(num_seasons) : placebo_horizons_fn<0>(num_seasons);
+  if (!fn || nb < 1 || nb > 65535 || args.O < 1 || args.K < 1 || args.rows != (size_t)nb * args.O * args.K)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fn, dim3((args.p.N + 63) / 64, nb), dim3(64), 0, stream, args);
+  return hipGetLastError();
+}
+
 #ifndef CI_FILTER_F64
 // The rows [(c1 - c0) * O, N] of one pass of simulated totals added to acc [G, O, N].
 hipError_t placebo_pool_totals_launch(hipStream_t stream, int N, int O, int G, int c0, int c1,
