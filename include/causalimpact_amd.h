@@ -638,6 +638,51 @@ int ci_session_pool_placebo_blocks(ci_session* session, const double* scale, con
                                    const int32_t* origins /* [K, O] */, const int32_t* horizon /* [G] */,
                                    const double* init, double* out, const double* seen,
                                    double* predicted_mean, double* spread_mean, double* pit_mean);
+/* PLACEBO FORECASTS OF POOLED SUMS AT SEVERAL HORIZONS from one filter pass: what
+ * ci_session_pool_placebo[_blocks] returns, for K horizons per group, every horizon looking from the
+ * SAME origins -- how the pooled check moves with the window's length.  Additive: CI_ABI_VERSION
+ * stays 5; look the symbols up (dlsym) where an older library may be met.
+ * The group table, the entries' origin rows origins[k, 0 .. O - 1], scale, shift, s, v and the order
+ * of addition are those of ci_session_pool_placebo.  Group g has the horizon row horizons[g, 0 .. K - 1]
+ * (>= 1, strictly ascending, -1 = unused, the unused slots at the end, at least one horizon per row;
+ * max_horizons: K, in [1, 64]).  The running C, V and cnt of the forecast loop after h steps are what a
+ * window of horizon h returns, so the forecast of an entry's origin runs to its group's largest
+ * horizon and s and v are formed at every h == horizons[g, k].
+ *   init, out: host arrays [G, O, K, 2, N], S then U; init may be NULL (0.0) and may be `out` itself
+ *   seen (optional): [G, O, K];  predicted_mean, spread_mean, pit_mean: [G, O, K] each, may be NULL
+ * CONTRACT: for every output, x[g, i, k] is, bit for bit, what ci_session_pool_placebo (for .._blocks:
+ * ci_session_pool_placebo_blocks) returns at [g, i] when called with the same group table and origins,
+ * horizon[g] = horizons[g, k], init[:, :, k] and seen[:, :, k].  An unused horizon slot adds terms of
+ * 0, as an unused origin slot does: its accumulators keep `init` and its means are 0 (where U == 0).
+ * Several sessions continue one running sum by handing `out` on as `init`, as above.
+ * Sessions and models: those of ci_session_pool_placebo (ragged sessions, sessions made from draws in
+ * float32 or float64) and of ci_session_pool_placebo_blocks respectively.  The filter runs ONCE per
+ * chunk of whole entries, storing s and v of every checkpoint as two planes [chunk * O * K, N]; the
+ * accumulate and the finishing step are the kernels of ci_session_pool_placebo with O * K slots.  A
+ * chunk's planes lie in the scratch of ci_session_summarize where one entry's 2 * O * K rows fit its
+ * B * T rows, else in a buffer of the call's own of at most CI_PATHS_MAX_BYTES, given back when it
+ * returns; one entry that does not fit that is refused by name, and so are accumulators [G, O, K, 2, N]
+ * beyond CI_PATHS_MAX_BYTES (pass the horizon slots in several calls: the columns are independent).
+ * Nothing depends on where the chunks are cut.
+ * Checked before any device call, with the group, entry or slot named: as ci_session_pool_placebo
+ * (.._blocks), max_horizons and every group's horizon row, the origins with origin + (the group's
+ * largest horizon) <= T_b, and no mean output without `seen`. */
+int ci_session_pool_placebo_horizons(ci_session* session, const double* scale, const double* shift,
+                                     int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                     const double* weights, int32_t max_origins,
+                                     const int32_t* origins /* [E, O] */, int32_t max_horizons,
+                                     const int32_t* horizons /* [G, K] */, const double* init,
+                                     double* out /* [G, O, K, 2, N] */, const double* seen /* [G, O, K] */,
+                                     double* predicted_mean, double* spread_mean,
+                                     double* pit_mean /* each [G, O, K], may be NULL */);
+int ci_session_pool_placebo_horizons_blocks(ci_session* session, const double* scale, const double* shift,
+                                            int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                            const double* weights, int32_t max_origins,
+                                            const int32_t* origins /* [E, O] */, int32_t max_horizons,
+                                            const int32_t* horizons /* [G, K] */, const double* init,
+                                            double* out /* [G, O, K, 2, N] */, const double* seen /* [G, O, K] */,
+                                            double* predicted_mean, double* spread_mean,
+                                            double* pit_mean /* each [G, O, K], may be NULL */);
 /* SIMULATED PLACEBO FORECASTS OF POOLED SUMS: the placebo check of a pooled effect under an outcome
  * link, where the pooled total is a weighted sum of sums of exp's and N(S, U) above does not exist.
  * Additive: CI_ABI_VERSION stays 5; look the symbols up (dlsym) where an older library may be met.
@@ -1160,6 +1205,17 @@ int ci_test_session_pool_placebo_blocks(ci_session* session, const double* scale
                                         const double* init, double* out, const double* seen,
                                         double* predicted_mean, double* spread_mean, double* pit_mean,
                                         int32_t chunk_entries);
+/* ci_session_pool_placebo_horizons (blocks == 0) or .._blocks (blocks != 0) with the entries of a
+ * chunk handed in (chunk_entries >= 1; the call's own capacity where that is smaller) and the number
+ * of chunks it took written to num_chunks (may be NULL), likewise. */
+int ci_test_session_pool_placebo_horizons(ci_session* session, int32_t blocks, const double* scale,
+                                          const double* shift, int32_t num_groups, const int32_t* offsets,
+                                          const int32_t* members, const double* weights, int32_t max_origins,
+                                          const int32_t* origins /* [E, O] */, int32_t max_horizons,
+                                          const int32_t* horizons /* [G, K] */, const double* init,
+                                          double* out /* [G, O, K, 2, N] */, const double* seen /* [G, O, K] */,
+                                          double* predicted_mean, double* spread_mean, double* pit_mean,
+                                          int32_t chunk_entries, int32_t* num_chunks);
 /* ci_session_pool_simulated_placebo (blocks == 0) or .._blocks (blocks != 0) with the entries of a
  * chunk handed in (chunk_entries in [1, B] in place of B), likewise. */
 int ci_test_session_pool_simulated_placebo(ci_session* session, int32_t blocks, const double* scale,

@@ -160,6 +160,14 @@ def load():
       getattr(L, name).argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 +
                                    [C.c_int32] + [C.c_void_p] * 8 +
                                    ([C.c_int32] if name.startswith("ci_test_") else []))
+  for name in ("ci_session_pool_placebo_horizons", "ci_session_pool_placebo_horizons_blocks",
+               "ci_test_session_pool_placebo_horizons"):
+    if hasattr(L, name):                               # (additive, likewise)
+      test = name.startswith("ci_test_")
+      getattr(L, name).argtypes = ([C.c_void_p] + ([C.c_int32] if test else []) +
+                                   [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p,
+                                    C.c_int32, C.c_void_p] + [C.c_void_p] * 6 +
+                                   ([C.c_int32, C.c_void_p] if test else []))
   for name in ("ci_session_pool_simulated_placebo", "ci_session_pool_simulated_placebo_blocks",
                "ci_test_session_pool_simulated_placebo"):
     if hasattr(L, name):                               # (additive, likewise)
@@ -260,6 +268,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_session_pool_trajectories", "ci_ll_session_pool_trajectories",
           "ci_session_pool_event_trajectories", "ci_session_pool_placebo",
           "ci_session_pool_placebo_blocks",
+          "ci_session_pool_placebo_horizons", "ci_session_pool_placebo_horizons_blocks",
           "ci_session_pool_simulated_placebo", "ci_session_pool_simulated_placebo_blocks",
           "ci_session_simulate_placebo", "ci_session_simulate_placebo_blocks",
           "ci_session_set_link", "ci_session_value_mean",
@@ -272,7 +281,7 @@ def exported_symbols() -> Sequence[str]:
           "ci_comm_ll_session_all_gather", "ci_comm_destroy", "ci_test_rng",
           "ci_test_dk_draw", "ci_test_session_summarize_paths", "ci_test_summarize_draw_paths_f64",
           "ci_test_session_simulate_placebo", "ci_test_session_pool_placebo_blocks",
-          "ci_test_session_pool_simulated_placebo")
+          "ci_test_session_pool_simulated_placebo", "ci_test_session_pool_placebo_horizons")
 
 
 def _check(rc: int):
@@ -310,11 +319,12 @@ def _origin_plan(origins, horizon, B: int):
 MAX_PLACEBO_HORIZONS = 64   # max_horizons of ci_session_summarize_placebo_horizons
 
 
-def horizon_table(horizons, B: int) -> np.ndarray:
+def horizon_table(horizons, B: int, owner: str = "series") -> np.ndarray:
   """horizons [B, K] int32 of `Session.summarize_placebo_horizons`, from [B, K] or -- the same row for
   every series -- [K].  The rules the C entry checks, checked here first (ValueError, series and slot
   named): 1 <= K <= 64, every row with at least one horizon, each >= 1, strictly ascending, -1
-  (unused) only at the end of the row."""
+  (unused) only at the end of the row.  `Session.pool_placebo_horizons` has one row per group
+  (owner="group": what the messages call a row's owner)."""
   hz = np.asarray(horizons)
   if hz.ndim == 1:
     hz = np.broadcast_to(hz, (B,) + hz.shape)
@@ -325,13 +335,13 @@ def horizon_table(horizons, B: int) -> np.ndarray:
       raise ValueError(f"`horizons` must hold integers, got dtype {hz.dtype}")
   K = hz.shape[1]
   if not 1 <= K <= MAX_PLACEBO_HORIZONS:
-    raise ValueError(f"`horizons` must have 1 to {MAX_PLACEBO_HORIZONS} slots per series, got {K}")
+    raise ValueError(f"`horizons` must have 1 to {MAX_PLACEBO_HORIZONS} slots per {owner}, got {K}")
   hz = np.ascontiguousarray(hz, dtype=np.int32)
   for b in range(B):
     row = hz[b]
     used = int(np.count_nonzero(row != -1))
     if used == 0:
-      raise ValueError(f"horizons[{b}] holds no horizon: every series needs at least one")
+      raise ValueError(f"horizons[{b}] holds no horizon: every {owner} needs at least one")
     for i in range(K):
       h = int(row[i])
       if h == -1:
@@ -578,9 +588,10 @@ def row_means_host(M) -> np.ndarray:
 def placebo_terms_host(mean, variance, counted, scale, shift):
   """What one entry adds to a pooled placebo forecast, on the data scale: (s, v) from the per-draw C,
   V [O, N] and cnt [O] of `causalimpact_lib._placebo_summary_host(per_draw=True)` --
-  s = C * scale + cnt * shift (separate roundings), v = (V * scale) * scale, both 0 where cnt == 0."""
+  s = C * scale + cnt * shift (separate roundings), v = (V * scale) * scale, both 0 where cnt == 0.
+  At several horizons (`horizons=`): C, V [O, K, N] and cnt [O, K], likewise."""
   C_, V_ = np.asarray(mean, np.float64), np.asarray(variance, np.float64)
-  cnt = np.asarray(counted, np.float64).reshape(-1, 1)
+  cnt = np.asarray(counted, np.float64).reshape(C_.shape[:-1] + (1,))
   scale, shift = np.float64(scale), np.float64(shift)
   some = cnt > 0
   return np.where(some, C_ * scale + cnt * shift, 0.0), np.where(some, (V_ * scale) * scale, 0.0)
@@ -614,6 +625,31 @@ def pool_placebo_host(sums, variances, groups, init=None) -> np.ndarray:
 
 
 _erfc = np.vectorize(math.erfc, otypes=[np.float64])
+
+
+def pool_placebo_horizons_host(sums, variances, groups, init=None) -> np.ndarray:
+  """What `Session.pool_placebo_horizons` accumulates, in numpy: sums, variances [E, O, K, N] -- per
+  entry of the group table the s and v of `placebo_terms_host` at the K checkpoints of its group's
+  horizon row, 0 in the unused slots -- and groups as for `pool_placebo_host`.  Returns acc
+  [G, O, K, 2, N]: `pool_placebo_host` over the O * K slots, so acc[:, :, k] is its result for column k
+  and `init` [G, O, K, 2, N] continues it bit for bit."""
+  s_, v_ = np.asarray(sums, np.float64), np.asarray(variances, np.float64)
+  if s_.ndim != 4 or s_.shape != v_.shape:
+    raise ValueError(f"`sums` and `variances` must both be [E, O, K, N], got {s_.shape} and {v_.shape}")
+  E, O, K, N = s_.shape
+  if init is not None:
+    init = np.asarray(init, np.float64).reshape(-1, O * K, 2, N)
+  acc = pool_placebo_host(s_.reshape(E, O * K, N), v_.reshape(E, O * K, N), groups, init)
+  return acc.reshape(acc.shape[0], O, K, 2, N)
+
+
+def finish_placebo_horizons_host(acc, seen) -> Dict[str, np.ndarray]:
+  """The finishing step of `Session.pool_placebo_horizons` in numpy: acc [G, O, K, 2, N], seen [G, O, K]
+  -> predicted_mean, spread_mean, pit_mean [G, O, K]: `finish_placebo_host` over the O * K slots."""
+  acc = np.asarray(acc, np.float64)
+  G, O, K, _, N = acc.shape
+  res = finish_placebo_host(acc.reshape(G, O * K, 2, N), np.asarray(seen, np.float64).reshape(G, O * K))
+  return {k: v.reshape(G, O, K) for k, v in res.items()}
 
 
 def finish_placebo_host(acc, seen) -> Dict[str, np.ndarray]:
@@ -1500,6 +1536,47 @@ class Session:
     return self.pool_placebo(scale, shift, groups, origins, horizon, init, seen,
                              _entry="ci_test_session_pool_placebo_blocks", _tail=(int(chunk_entries),))
 
+  def pool_placebo_horizons(self, scale, shift, groups, origins, horizons, init=None, seen=None, *,
+                            blocks: bool = False, chunk_entries=None) -> Dict[str, np.ndarray]:
+    """`pool_placebo` at SEVERAL HORIZONS per group from one filter pass
+    (ci_session_pool_placebo_horizons; blocks=True: .._blocks, the sessions and models of
+    `pool_placebo_blocks`): every x[g, i, k] of the result is, bit for bit, what `pool_placebo`
+    (`pool_placebo_blocks`) returns at [g, i] with horizon[g] = horizons[g, k], init[:, :, k] and
+    seen[:, :, k].  scale, shift, groups, origins: as for `pool_placebo`, the origins checked with the
+    group's largest horizon; horizons: [G, K] int or -- the same row for every group -- [K], every row
+    strictly ascending, >= 1, -1 = unused, at the end of the row (`horizon_table`, checked here before
+    the library is reached); init: [G, O, K, 2, N] or None; seen: [G, O, K] or None.  Returns acc
+    [G, O, K, 2, N] (S, then U) and, with `seen`, predicted_mean, spread_mean, pit_mean [G, O, K]; an
+    unused horizon slot adds nothing to acc and reads 0 in the means.  chunk_entries (tests): the
+    entries of a chunk (ci_test_session_pool_placebo_horizons); the result does not depend on it and
+    `num_chunks` is returned besides."""
+    name = ("ci_test_session_pool_placebo_horizons" if chunk_entries is not None
+            else "ci_session_pool_placebo_horizons" + ("_blocks" if blocks else ""))
+    sc, sh, offsets, members, weights, org, _ = self._pool_placebo_tables(scale, shift, groups, origins, 1)
+    G, O, N = offsets.size - 1, int(org.shape[1]), self.pb.num_chains * self.pb.num_results
+    hz = horizon_table(horizons, G, owner="group")
+    K = int(hz.shape[1])
+    if init is not None:
+      init = np.ascontiguousarray(init, dtype=np.float64)
+      if init.shape != (G, O, K, 2, N):
+        raise ValueError(f"`init` must be {[G, O, K, 2, N]}, got {list(init.shape)}")
+    out = {"acc": np.empty((G, O, K, 2, N), np.float64)}
+    if seen is not None:
+      seen = np.ascontiguousarray(seen, dtype=np.float64)
+      if seen.shape != (G, O, K):
+        raise ValueError(f"`seen` must be {[G, O, K]}, got {list(seen.shape)}")
+      out.update({k: np.empty((G, O, K), np.float64) for k in PLACEBO_OUTPUTS})
+    fn = _symbol(self._lib, name)
+    chunks = C.c_int32(0)
+    head = (self._h,) + ((int(bool(blocks)),) if chunk_entries is not None else ())
+    tail = (int(chunk_entries), C.addressof(chunks)) if chunk_entries is not None else ()
+    _check(fn(*head, sc.ctypes.data, sh.ctypes.data, G, offsets.ctypes.data, members.ctypes.data,
+              weights.ctypes.data, O, org.ctypes.data, K, hz.ctypes.data, _ptr(init), out["acc"].ctypes.data,
+              _ptr(seen), *[_ptr(out.get(k)) for k in PLACEBO_OUTPUTS], *tail))
+    if chunk_entries is not None:
+      out["num_chunks"] = int(chunks.value)
+    return out
+
   def pool_simulated_placebo(self, scale, shift, groups, origins, horizon, link, init=None, seen=None,
                              counted=None, ranks=None, want=None, *, blocks: bool = False,
                              chunk_entries=None) -> Dict[str, np.ndarray]:
@@ -1580,6 +1657,7 @@ class DrawsSession(Session):
   """A session made from draws (ci_session_create_from_draws[_f64]): the data and the pooled
   parameter draws of B fits, uploaded from the host, for the prediction-error and placebo entries
   alone -- `summarize_predictions`, `summarize_placebo`, `summarize_placebo_horizons`, `simulate_placebo`, `pool_placebo`,
+  `pool_placebo_horizons`,
   `pool_simulated_placebo` and their `_blocks` forms, with the signatures and results they have on a
   fit's `Session`.  Every method that needs a fit (`run`, `fetch`, `summarize`, ..) raises NativeError.
 

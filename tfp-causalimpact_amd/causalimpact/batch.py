@@ -422,6 +422,8 @@ class CausalImpactBatchAnalysis:
     # `placebo=` with aggregates: one row per aggregate with the `lib.PLACEBO_QUALITY_ENTRIES` of its
     # pooled placebo forecasts; every `aggregates[name]` carries its `placebo` and `placebo_quality`
     self.aggregate_placebo_quality: Optional[pd.DataFrame] = None
+    # `Placebo(horizons=...)` with aggregates: every aggregate's `placebo_profile`, indexed by (aggregate, horizon)
+    self.aggregate_placebo_profile: Optional[pd.DataFrame] = None
 
   def _model_labels(self, b: int) -> pd.Index:
     """The labels of the model steps of series b."""
@@ -657,13 +659,14 @@ class CausalImpactBatchAnalysis:
     return (self[b] for b in range(len(self)))
 
 
-def _stack_profiles(tables: Sequence[pd.DataFrame], names) -> pd.DataFrame:
+def _stack_profiles(tables: Sequence[pd.DataFrame], names, level: str = "series") -> pd.DataFrame:
   """The per-series `placebo_profile` tables as one, indexed by (series, horizon): every series over
-  the sorted union of the horizons, NaN rows where it lacks one."""
+  the sorted union of the horizons, NaN rows where it lacks one.  level: the name of the first index
+  level ("aggregate" for the pooled effects' profiles)."""
   horizons = pd.Index(sorted({int(h) for t in tables for h in t.index}), dtype=np.int64, name="horizon")
   columns = list(lib.PLACEBO_PROFILE_COLUMNS)
   values = [t.reindex(horizons)[columns].to_numpy(np.float64) for t in tables]
-  index = pd.MultiIndex.from_product([list(names), horizons], names=["series", "horizon"])
+  index = pd.MultiIndex.from_product([list(names), horizons], names=[level, "horizon"])
   return pd.DataFrame(np.concatenate(values) if values else np.zeros((0, len(columns))), index=index, columns=columns)
 
 
@@ -686,6 +689,7 @@ class PerSeriesBatchAnalysis(CausalImpactBatchAnalysis):
     self.aggregate_joint_summary = None
     self.aggregate_window_joint_summary = None
     self.aggregate_placebo_quality = None
+    self.aggregate_placebo_profile = None
     if all(a.joint_summary is not None for a in analyses):
       self.joint_summary = pd.concat([a.joint_summary for a in analyses], keys=self._names,
                                      names=["series", None])
@@ -1506,13 +1510,25 @@ class PlaceboPoolPlan:
   """What the pooled placebo forecasts of a fit's aggregates are taken over: the group table, per
   ENTRY of it the member's origins as its own model steps, and per group the same origins as
   positions on the group's own axis (`labels[g]`), its one horizon and the steps of its post-period.
-  -1: an unused slot, at the end of a row; a group without room for an origin has a row of -1."""
+  -1: an unused slot, at the end of a row; a group without room for an origin has a row of -1.
+  horizons (`Placebo(horizons=...)`, else None): per group the horizons its forecasts are read at,
+  ascending, the last used one its `horizon`; a group whose horizon is below 1 has a row of -1."""
   csr: Tuple[np.ndarray, np.ndarray, np.ndarray]
   origins: np.ndarray           # [K, O] int32
   columns: np.ndarray           # [G, O] int32
   horizon: np.ndarray           # [G] int32
   n_post: np.ndarray            # [G]
   labels: List[pd.Index]
+  horizons: Optional[np.ndarray] = None   # [G, K] int32
+
+  @property
+  def shape(self) -> Tuple[int, ...]:
+    """The slots of the pooled sums: [G, O], with horizons [G, O, K]."""
+    return self.columns.shape if self.horizons is None else self.columns.shape + (self.horizons.shape[1],)
+
+  def last_column(self, g: int) -> int:
+    """The horizon slot of group g that holds its `horizon` (the last used one; 0 without any)."""
+    return max(int(np.count_nonzero(self.horizons[g] >= 1)) - 1, 0)
 
   def entries_of(self, b: int):
     """[(group, entry)] of the series at position b, groups ascending; groups without an origin left out."""
@@ -1525,20 +1541,24 @@ class PlaceboPoolPlan:
     return out
 
 
-def batch_placebo_pool_plan(csr, origins, horizon, n_post, labels: pd.Index) -> PlaceboPoolPlan:
+def batch_placebo_pool_plan(csr, origins, horizon, n_post, labels: pd.Index,
+                            placebo: Optional[lib.Placebo] = None) -> PlaceboPoolPlan:
   """The plan of a batch: every group has the origins [O] and the horizon every series of the batch
-  has (they share `num_pre` and the post-period), on the batch's model index."""
+  has (they share `num_pre` and the post-period), on the batch's model index.  placebo (with
+  `Placebo(horizons=...)`): every group takes `lib.placebo_horizon_list(placebo, horizon)`, strictly."""
   G, K = len(csr[0]) - 1, len(csr[1])
   origins = np.asarray(origins, np.int32).reshape(-1)
   return PlaceboPoolPlan(csr, np.tile(origins, (K, 1)), np.tile(origins, (G, 1)), np.full(G, int(horizon), np.int32),
-                         np.full(G, int(n_post)), [labels] * G)
+                         np.full(G, int(n_post)), [labels] * G,
+                         placebo_horizon_tables(placebo, np.full(G, int(horizon))))
 
 
 def event_placebo_pool_plan(placebo: lib.Placebo, plan: EventPlan, state_dim: int) -> PlaceboPoolPlan:
   """The plan of a panel's event-time aggregates: group g has `lib.placebo_plan(placebo, L - gap,
   Hwin, state_dim)` on its `EventAxis` -- the pre-period and the window all its members share -- and
   member k forecasts from its own step first[k] + column, so every window lies inside every member's
-  own pre-period.  The frames are indexed by `event_time` (column - L)."""
+  own pre-period.  The frames are indexed by `event_time` (column - L).  With `Placebo(horizons=...)`
+  a group keeps the listed horizons <= its own H_g (lenient, as for a panel's series)."""
   offsets = plan.csr[0]
   plans = [lib.placebo_plan(placebo, axis.L - axis.gap, axis.Hwin, state_dim) for axis in plan.axes]
   width = max(1, max(len(o) for _, o in plans))
@@ -1548,16 +1568,19 @@ def event_placebo_pool_plan(placebo: lib.Placebo, plan: EventPlan, state_dim: in
     columns[g, :len(cols)] = cols
     for k, first in zip(range(offsets[g], offsets[g + 1]), axis.first):
       origins[k, :len(cols)] = np.asarray(cols, np.int64) + int(first)
-  return PlaceboPoolPlan(plan.csr, origins, columns, np.array([h for h, _ in plans], np.int32),
-                         np.array([axis.Hwin for axis in plan.axes]), [axis.index for axis in plan.axes])
+  horizon = np.array([h for h, _ in plans], np.int32)
+  return PlaceboPoolPlan(plan.csr, origins, columns, horizon,
+                         np.array([axis.Hwin for axis in plan.axes]), [axis.index for axis in plan.axes],
+                         placebo_horizon_tables(placebo, horizon, strict=False))
 
 
 def _placebo_pool_observed(pp: PlaceboPoolPlan, entry_seen) -> Dict[str, np.ndarray]:
   """{seen_sum, actual, n_counted: [G, O]} of the pooled sums: seen_sum and actual the weighted sums
   over a group's entries, ascending, of the members' (`lib._placebo_entry_seen`), n_counted the plain
-  sum -- member-steps.  entry_seen(g, k) -> that dict of entry k, or None before it is known."""
+  sum -- member-steps.  entry_seen(g, k) -> that dict of entry k, or None before it is known.  With
+  `pp.horizons` every array is [G, O, K]: the same sums per horizon slot."""
   offsets, _, weights = pp.csr
-  out = {k: np.zeros(pp.columns.shape) for k in ("seen_sum", "actual", "n_counted")}
+  out = {k: np.zeros(pp.shape) for k in ("seen_sum", "actual", "n_counted")}
   for g in range(len(offsets) - 1):
     if not np.any(pp.columns[g] >= 0):
       continue
@@ -1578,12 +1601,13 @@ def _fit_placebo_observed(pp: PlaceboPoolPlan, fit: "_Fit") -> Dict[str, np.ndar
 
   def entry_seen(g, k):
     b = int(members[k])
-    key = (b, int(pp.horizon[g]), pp.origins[k].tobytes())
+    hz = None if pp.horizons is None else pp.horizons[g]
+    key = (b, int(pp.horizon[g]), pp.origins[k].tobytes(), None if hz is None else hz.tobytes())
     if key not in known:
       Tb = int(fit.lengths[b])
       one = lib.SeriesInputs(fit.y[b, :Tb], fit.mask[b, :Tb], None, None, (), False, {})
       known[key] = lib._placebo_entry_seen(one, fit.own_scale[b], fit.own_shift[b], fit.observed[b, :Tb],   # pylint: disable=protected-access
-                                           pp.origins[k], int(pp.horizon[g]), fit.link)
+                                           pp.origins[k], int(pp.horizon[g]), fit.link, hz)
     return known[key]
   return _placebo_pool_observed(pp, entry_seen)
 
@@ -1613,7 +1637,9 @@ class HostPlaceboPool:
   hands to its `_placebo_sink`; every group that has b takes the terms of its own origins and horizon
   (`_native.pool_placebo_host`'s arithmetic, one entry at a time, entries ascending).  simulated (a
   `SimulatedPool`): the forecast hands the member's simulated totals (`lib._placebo_entry_simulated_host`)
-  and the sums are those of `_native.pool_simulated_placebo_host`, [G, O, N]."""
+  and the sums are those of `_native.pool_simulated_placebo_host`, [G, O, N].  With `pp.horizons` the
+  forecast is asked for the group's horizon row as well and the sums are [G, O, K, 2, N]
+  (`_native.pool_placebo_horizons_host`'s)."""
 
   def __init__(self, pp: PlaceboPoolPlan, simulated: Optional[SimulatedPool] = None):
     self.pp = pp
@@ -1625,9 +1651,17 @@ class HostPlaceboPool:
     pp = self.pp
     weights = pp.csr[2]
     for g, k in pp.entries_of(b):
-      one = forecast(pp.origins[k], int(pp.horizon[g]))
+      if pp.horizons is not None:
+        one = forecast(pp.origins[k], int(pp.horizon[g]), pp.horizons[g])
+      else:
+        one = forecast(pp.origins[k], int(pp.horizon[g]))
       w = np.float64(weights[k])
-      if self.simulated is not None:
+      if pp.horizons is not None:
+        if self.acc is None:
+          self.acc = np.zeros(pp.shape + (2, one["s"].shape[-1]))
+        self.acc[g, :, :, 0] = self.acc[g, :, :, 0] + w * one["s"]
+        self.acc[g, :, :, 1] = self.acc[g, :, :, 1] + (w * w) * one["v"]
+      elif self.simulated is not None:
         if self.acc is None:
           self.acc = np.zeros(pp.columns.shape + (one["totals"].shape[1],))
         self.acc[g] = self.acc[g] + w * one["totals"]
@@ -1646,6 +1680,8 @@ class HostPlaceboPool:
       return None, observed
     if self.simulated is not None:
       return self.simulated.finish_host(self.acc, observed["seen_sum"], observed["n_counted"]), observed
+    if self.pp.horizons is not None:
+      return _native.finish_placebo_horizons_host(self.acc, observed["seen_sum"]), observed
     return _native.finish_placebo_host(self.acc, observed["seen_sum"]), observed
 
 
@@ -1699,9 +1735,14 @@ class _PlaceboChain(_PoolChain):
   the `lib.placebo_stream` of the positions `ids`): the same chain for the accumulators [G, O, N] of the
   SIMULATED pooled placebo forecasts (ci_session_pool_simulated_placebo) -- the same launch order, the
   same hand-on, the same choice of route; the last launch finishes with `seen`, `counted` and the
-  ranks of `lib._placebo_sim_ranks`, and `means` is the summary `SimulatedPool.means` makes of it."""
+  ranks of `lib._placebo_sim_ranks`, and `means` is the summary `SimulatedPool.means` makes of it.
+  With `pp.horizons` (`Placebo(horizons=...)`) the chain carries [G, O, K, 2, N] in the same order and
+  with the same hand-on: a launch pools through ONE filter pass (`lib.pool_placebo_horizon_columns`:
+  `Session.pool_placebo_horizons`, for a block model its `_blocks` entry, K calls where the library lacks
+  it) and the last launch finishes the O * K slots; `seen` and `means` are [G, O, K]."""
 
   simulated: Optional[SimulatedPool] = None      # (the analytic chain, unless `__init__` says otherwise)
+  pp: Optional[PlaceboPoolPlan] = None
   counted: Optional[np.ndarray] = None
   streams = None
   on_device = True
@@ -1745,15 +1786,35 @@ class _PlaceboChain(_PoolChain):
       drawn, blocks = lib._draws_session_beside(sess, series_inputs, draws, self.on_device)   # pylint: disable=protected-access
       if drawn is not None:
         sess, held, route = drawn, (drawn,), "blocks" if blocks else "one_lane"
+    several = getattr(self.pp, "horizons", None) is not None
     if route != "host":
       T, B = int(sess.pb.T), int(sess.pb.num_series)
       entry = sess.pool_placebo if route == "one_lane" else sess.pool_placebo_blocks
 
       def pool(groups, origins, horizon, init):
+        if several:                  # (`horizon`: the groups' horizon rows)
+          return lib.pool_placebo_horizon_columns(sess, route == "blocks", scale, shift, groups, origins, horizon, init)
         return entry(scale, shift, groups, origins, horizon, init)["acc"]
 
       def finish(acc, seen):
         # no slot row is longer than the session's steps: as many slots at a time as it takes
+        shape = seen.shape
+        if several and lib.pool_placebo_horizons_available(route == "blocks"):
+          # the entry itself with empty groups: no filter pass, the accumulators handed in and finished
+          hz = self.pp.horizons
+          rows = np.where((hz > 0).any(axis=1)[:, None], hz, np.array([1] + [-1] * (hz.shape[1] - 1), np.int32)[None, :])
+          out = {k: np.zeros(shape) for k in _native.PLACEBO_OUTPUTS}
+          room = max(1, (1 << 30) // max(acc[:, :1].nbytes, 1))     # (the accumulators a call may hold)
+          for j in range(0, shape[1], min(T, room)):
+            w = min(T, room, shape[1] - j)
+            got = sess.pool_placebo_horizons(scale, shift, [{}] * shape[0], np.full((B, w), -1, np.int32), rows,
+                                             np.ascontiguousarray(acc[:, j:j + w]), np.ascontiguousarray(seen[:, j:j + w]),
+                                             blocks=route == "blocks")
+            for k in out:
+              out[k][:, j:j + w] = got[k]
+          return out
+        if several:                  # (a library without it: the O * K slots of a group, one after another)
+          acc, seen = acc.reshape((shape[0], -1) + acc.shape[-2:]), seen.reshape(shape[0], -1)
         out = {k: np.zeros(seen.shape) for k in _native.PLACEBO_OUTPUTS}
         for j in range(0, acc.shape[1], T):
           w = min(T, acc.shape[1] - j)
@@ -1762,18 +1823,24 @@ class _PlaceboChain(_PoolChain):
                       np.ascontiguousarray(seen[:, j:j + w]))
           for k in out:
             out[k][:, j:j + w] = got[k]
-        return out
+        return {k: v.reshape(shape) for k, v in out.items()}
       return (pool, finish) + held
 
     def host_pool(groups, origins, horizon, init):
       csr = _native.groups_csr(groups, len(series_inputs))
+      entries = [(g, int(m)) for g in range(len(groups)) for m in csr[1][csr[0][g]:csr[0][g + 1]]]
+      if several:                    # (`horizon`: the groups' horizon rows)
+        terms = [lib._placebo_entry_host(                           # pylint: disable=protected-access
+            series_inputs[i], lib._pooled_draws(draws, i), scale[i], shift[i], observed[i],   # pylint: disable=protected-access
+            origins[g][i], int(np.max(horizon[g])), horizon[g]) for g, i in entries]
+        return _native.pool_placebo_horizons_host(np.stack([t["s"] for t in terms]), np.stack([t["v"] for t in terms]),
+                                                  csr, init)
       terms = [lib._placebo_entry_host(                             # pylint: disable=protected-access
           series_inputs[i], lib._pooled_draws(draws, i), scale[i], shift[i], observed[i],   # pylint: disable=protected-access
-          origins[g][i], int(horizon[g]))
-               for g in range(len(groups)) for i in (int(m) for m in csr[1][csr[0][g]:csr[0][g + 1]])]
+          origins[g][i], int(horizon[g])) for g, i in entries]
       return _native.pool_placebo_host(np.stack([t["s"] for t in terms]), np.stack([t["v"] for t in terms]),
                                        csr, init)
-    return host_pool, _native.finish_placebo_host
+    return host_pool, (_native.finish_placebo_horizons_host if several else _native.finish_placebo_host)
 
   def _simulated_session_pool(self, sess, scale, shift, series_inputs, ids):
     """`session_pool` of the simulated mode: (pool, finish) through `pool_simulated_placebo`
@@ -1836,7 +1903,8 @@ class _PlaceboChain(_PoolChain):
         width = max(1, int(used.sum(axis=1).max()))
         origins = [{i: row[:width] for i, row in groups[g][1].items()} for g in active]
         init = None if acc is None else np.ascontiguousarray(acc[active][:, :width])
-        part = pool([groups[g][0] for g in active], origins, np.maximum(self.pp.horizon[active], 1), init)
+        horizon = np.maximum(self.pp.horizon[active], 1) if self.pp.horizons is None else self.pp.horizons[active]
+        part = pool([groups[g][0] for g in active], origins, horizon, init)
         if acc is None:
           acc = np.zeros(self.pp.columns.shape + part.shape[2:])
         else:
@@ -1860,19 +1928,33 @@ def _take_aggregate_placebo(res, pp: PlaceboPoolPlan, names, means: Optional[Dic
   """Gives every `res.aggregates[name]` its `placebo` and `placebo_quality`
   (`lib._aggregate_placebo_frames`; fit_relative_effect: the aggregate's own cumulative `rel_effect`)
   and `res` its `aggregate_placebo_quality`, one row per aggregate.  means None: no group has room
-  for an origin."""
-  rows = []
+  for an origin.  With `pp.horizons` means and observed are [G, O, K]: `placebo` and `placebo_quality`
+  are read from each group's last used column (its H), every aggregate gains `placebo_by_horizon` and
+  `placebo_profile` (`lib._aggregate_placebo_horizon_frames`) and `res` its `aggregate_placebo_profile`,
+  indexed by (aggregate, horizon) with NaN rows where a group lacks a horizon."""
+  rows, profiles = [], []
   for g, name in enumerate(names):
     one = res.aggregates[name]
-    psum = None
-    if means is not None and np.any(pp.columns[g] >= 0):
+    rel = one.summary.loc["cumulative", "rel_effect"]
+    used = pp.columns[g] >= 0
+    psum, actual = None, observed["actual"][g]
+    if means is not None and np.any(used):
+      seen = observed["seen_sum"][g]
       psum = dict({k: v[g] for k, v in means.items()}, n_counted=observed["n_counted"][g],
-                  seen_sum=np.where(pp.columns[g] >= 0, observed["seen_sum"][g], np.nan))
+                  seen_sum=np.where(used if seen.ndim == 1 else used[:, None], seen, np.nan))
+    if pp.horizons is not None:
+      one.placebo_by_horizon, one.placebo_profile = lib._aggregate_placebo_horizon_frames(   # pylint: disable=protected-access
+          psum, actual, pp.columns[g], pp.horizons[g], alpha, pp.labels[g], int(pp.n_post[g]), rel)
+      profiles.append(one.placebo_profile)
+      # the frames at H: the group's last used column
+      last = pp.last_column(g)
+      psum, actual = None if psum is None else {k: v[:, last] for k, v in psum.items()}, actual[:, last]
     one.placebo, one.placebo_quality = lib._aggregate_placebo_frames(   # pylint: disable=protected-access
-        psum, observed["actual"][g], pp.columns[g], int(pp.horizon[g]), alpha, pp.labels[g], int(pp.n_post[g]),
-        one.summary.loc["cumulative", "rel_effect"])
+        psum, actual, pp.columns[g], int(pp.horizon[g]), alpha, pp.labels[g], int(pp.n_post[g]), rel)
     rows.append(one.placebo_quality)
   res.aggregate_placebo_quality = pd.DataFrame(rows, index=pd.Index(list(names), name="aggregate"))
+  if pp.horizons is not None:
+    res.aggregate_placebo_profile = _stack_profiles(profiles, list(names), "aggregate")
 
 
 # ------------------------------------------------------------------------------------------
@@ -2416,7 +2498,12 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   `Placebo(horizons=...)` (see `lib.Placebo`): every `result[b]` gains `placebo_by_horizon` and
   `placebo_profile`, and `result.placebo_profile` is one table indexed by (series, horizon) -- one
   filter pass of the launch for all horizons (ci_session_summarize_placebo_horizons).  ValueError before
-  any fit for a listed horizon beyond H; the pooled placebo of `aggregates` stays at H.
+  any fit for a listed horizon beyond H.  With `aggregates` every `result.aggregates[name]` gains the same
+  two frames for the pooled effect (`placebo_by_horizon` indexed by (origin, horizon), `placebo_profile`
+  with empirical_p on the row h == n_post against the aggregate's own cumulative rel_effect) and
+  `result.aggregate_placebo_profile` is one table indexed by (aggregate, horizon) -- one filter pass per
+  launch for every horizon of every group (ci_session_pool_placebo_horizons, `_blocks` for the block
+  models), the pooled `placebo` at H read from its last column.
 
   joint_bands: False (the default: nothing runs, no result differs) or True -- the simultaneous bands
   and the whole-path test of `fit_causalimpact` for every series: `result[b].joint_bands`,
@@ -2503,7 +2590,7 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
       n_post = int(np.count_nonzero(shared.flags & 2))
       pl_h, pl_o = lib.placebo_plan(placebo, shared.num_pre, n_post, pl_dim)
       pool_plan = batch_placebo_pool_plan(agg[1], pl_o if len(pl_o) else [-1], pl_h, n_post,
-                                          shared.index[shared.model_rows])
+                                          shared.index[shared.model_rows], placebo)
     return _fit_per_series((pd.DataFrame(raw_values[b], index=index, columns=columns) for b in range(B)),
                            [(pre_period, post_period)] * B, names, columns[0], alpha, seed,
                            data_options, model_options, inference_options, shared_streams, agg,
@@ -2540,7 +2627,7 @@ def fit_causalimpact_batch(data: Union[Sequence[pd.DataFrame], np.ndarray],
   pool_plan = pool_seen = pl_chain = None
   if agg is not None and placebo is not None:
     pool_plan = batch_placebo_pool_plan(agg[1], pl_plan[0][0], pl_plan[1][0], pl_post[0],
-                                        prep.index[prep.model_rows])
+                                        prep.index[prep.model_rows], placebo)
     pool_seen = _fit_placebo_observed(pool_plan, fit)
     pl_chain = _new_placebo_chain(launches, pool_plan, pool_seen, fit, placebo, alpha)
   if hmc:
@@ -2675,7 +2762,10 @@ def fit_causalimpact_panel(data: Sequence[pd.DataFrame], periods, alpha: float =
   the NaN row; `result.aggregate_placebo_quality` has one row per aggregate.  With
   `Placebo(horizons=...)` every series keeps the listed horizons <= its own H (none is refused) and
   `result.placebo_profile`, indexed by (series, horizon), has NaN rows for the horizons a series lacks;
-  the pooled placebo of `event_aggregates` stays at its group's H.
+  with `event_aggregates` every group keeps the listed horizons <= its own H_g likewise:
+  `result.aggregates[name].placebo_by_horizon` / `.placebo_profile` on the group's event-time axis and
+  `result.aggregate_placebo_profile`, indexed by (aggregate, horizon), with NaN rows where a group lacks
+  a horizon.
 
   joint_bands: as in `fit_causalimpact_batch`, every series over its OWN post-period and the
   `effect_windows` in event time; `window_joint_summary` has NaN rows where a series' post-period does

@@ -902,8 +902,9 @@ class Placebo:
                  these horizons, each >= 1 and <= H (sorted, duplicates dropped; a panel's series keeps
                  those <= its own H).  H is always the last one; at most `MAX_PLACEBO_HORIZONS` (64)
                  remain.  Not with `simulate=True` (hence not under `outcome_link`).  With
-                 `aggregates=` / `event_aggregates=` the per-series tables are built and the POOLED
-                 placebo stays at H.
+                 `aggregates=` / `event_aggregates=` the pooled effects get the same two tables
+                 (`result.aggregates[name].placebo_by_horizon`, `.placebo_profile`) and the result
+                 `aggregate_placebo_profile`; a panel's group keeps the listed horizons <= its H_g.
   Fixed-parameter: every draw's scales and weights are those of the one fit of the whole pre-period,
   so the check is cheap and somewhat optimistic; the windows overlap, so the origins are not
   independent trials."""
@@ -1179,14 +1180,15 @@ def _placebo_summary_host(y, mask, X, season_change, num_seasons, has_slope, par
   horizons [K] (ascending, -1: unused, at the end; `horizon` is then their last one, whatever is passed):
   the one forecast loop records its running values at the checkpoints h == horizons[k] and the three
   outputs are [O, K] -- column k what `horizon=horizons[k]` returns, bit for bit (0 in an unused slot);
-  not with `per_draw`."""
+  with `per_draw` also C, V [O, K, N], A and cnt [O, K] at the checkpoints (0 in an unused slot): what
+  `per_draw` returns for `horizon=horizons[k]`."""
   if horizons is not None:
     hz = [int(h) for h in np.asarray(horizons).reshape(-1)]
     marks = [h for h in hz if h != -1]
-    if (per_draw or not marks or min(marks) < 1 or marks != hz[:len(marks)]
+    if (not marks or min(marks) < 1 or marks != hz[:len(marks)]
         or any(b <= a for a, b in zip(marks, marks[1:]))):
       raise ValueError("placebo horizons must be at least 1 and strictly ascending with the unused slots (-1) at "
-                       "the end, at least one of them (and not with per_draw)")
+                       "the end, at least one of them")
     horizon = marks[-1]
   flt = _PlaceboFilter(y, mask, X, season_change, num_seasons, has_slope, params, draws, origins, horizon)
   y, mask, reg, Z, H, N, d, Hn, transition = flt.y, flt.mask, flt.reg, flt.Z, flt.H, flt.N, flt.d, flt.Hn, flt.transition
@@ -1196,6 +1198,8 @@ def _placebo_summary_host(y, mask, X, season_change, num_seasons, has_slope, par
   marks = [Hn] if horizons is None else marks
   # (one [N, O] matrix per checkpoint and output: the means below are taken as those of one horizon)
   sums, spreads, pits = ([np.zeros((N, O)) for _ in marks] for _ in range(3))
+  Ck, Vk = np.zeros((O, len(marks), N)), np.zeros((O, len(marks), N))   # (per_draw with horizons)
+  Ak, cntk = np.zeros((O, len(marks))), np.zeros((O, len(marks)))
   for slot, t, a, P in flt.at_origins():
     # the forecast branch, from the predicted moments
     fa, fP, r = a, P, np.zeros((N, d))
@@ -1209,6 +1213,9 @@ def _placebo_summary_host(y, mask, X, season_change, num_seasons, has_slope, par
         cnt += 1
         V = V + ((2.0 * (r @ Z) + pz @ Z) + H)
         r = r + pz
+      if h + 1 in marks:
+        k = marks.index(h + 1)
+        Ck[slot, k], Vk[slot, k], Ak[slot, k], cntk[slot, k] = C, V, A, cnt
       if h + 1 in marks and cnt:
         k, e = marks.index(h + 1), A - C
         sums[k][:, slot] = C * scale + np.float64(cnt) * shift
@@ -1221,7 +1228,11 @@ def _placebo_summary_host(y, mask, X, season_change, num_seasons, has_slope, par
     Cs[:, slot], Vs[:, slot], As[slot], cnts[slot] = C, V, A, cnt
   if horizons is not None:
     table = lambda mats: np.stack([m.mean(axis=0) for m in mats] + [np.zeros(O)] * (len(hz) - len(marks)), axis=1)   # pylint: disable=unnecessary-lambda-assignment
-    return dict(predicted_mean=table(sums), spread_mean=table(spreads), pit_mean=table(pits))
+    out = dict(predicted_mean=table(sums), spread_mean=table(spreads), pit_mean=table(pits))
+    if per_draw:
+      pad = lambda x: np.concatenate([x, np.zeros((O, len(hz) - len(marks)) + x.shape[2:])], axis=1)   # pylint: disable=unnecessary-lambda-assignment
+      out.update(C=pad(Ck), V=pad(Vk), A=pad(Ak), cnt=pad(cntk))
+    return out
   out = dict(predicted_mean=sums[0].mean(axis=0), spread_mean=spreads[0].mean(axis=0), pit_mean=pits[0].mean(axis=0))
   if per_draw:
     out.update(C=Cs.T.copy(), V=Vs.T.copy(), A=As, cnt=cnts)
@@ -1318,10 +1329,12 @@ def _placebo_seen(y_seen, mask, origins, horizon: int, scale, shift, horizons=No
     # (a masked step adds 0.0; cumsum adds left to right: the ascending sum)
     sums = np.cumsum(np.where(seen, y_seen[steps], 0.0), axis=1)
     if horizons is not None:
-      for k, h in enumerate(int(h) for h in np.asarray(horizons).reshape(-1)):
-        if h >= 1:
-          cnt = seen[:, :h].sum(axis=1).astype(np.float64)
-          n_counted[used, k], seen_sum[used, k] = cnt, sums[:, h - 1] * np.float64(scale) + cnt * np.float64(shift)
+      hz = np.asarray(horizons).reshape(-1).astype(np.int64)
+      at = np.flatnonzero(hz >= 1)                       # (every used slot at once: the counts are exact integers)
+      cnt = np.cumsum(seen, axis=1)[:, hz[at] - 1].astype(np.float64)
+      rows = np.flatnonzero(used)[:, None]
+      n_counted[rows, at[None, :]] = cnt
+      seen_sum[rows, at[None, :]] = sums[:, hz[at] - 1] * np.float64(scale) + cnt * np.float64(shift)
       return n_counted, seen_sum
     A = sums[:, -1]
     cnt = seen.sum(axis=1).astype(np.float64)
@@ -1488,13 +1501,49 @@ def _aggregate_placebo_frames(psum: Optional[Dict], actual, columns, horizon: in
   if psum is None or not np.any(used):
     frame = pd.DataFrame({k: np.zeros(0) for k in PLACEBO_COLUMNS}, index=labels[:0])
     return frame, _placebo_quality(None, horizon, alpha, n_post, fit_relative_effect)
+  frame, cols = _aggregate_placebo_frame(psum, actual, columns, horizon, alpha, labels)
+  return frame, _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
+
+
+def _aggregate_placebo_frame(psum: Dict, actual, columns, horizon: int, alpha: float, labels: pd.Index):
+  """(frame, columns) of `_aggregate_placebo_frames` for a group with an origin: `_placebo_columns` of
+  the pooled sums with the pooled `actual`, indexed by the origins' labels on the group's axis."""
+  used = columns >= 0
   cols = _placebo_columns(psum, columns, horizon, alpha, np.zeros(len(labels)))
   cols["actual"] = np.asarray(actual, np.float64)[used] + np.where(cols["n_counted"] > 0, 0.0, np.nan)
   end = cols.pop("horizon_end_step")
   frame = pd.DataFrame({"horizon_end": labels[end], **cols}, index=labels[columns[used]])
   frame.index.name = "origin"
   shown = list(PLACEBO_COLUMNS) + [k for k in PLACEBO_SIMULATED_COLUMNS if k in cols]
-  return frame[shown], _placebo_quality(cols, horizon, alpha, n_post, fit_relative_effect)
+  return frame[shown], cols
+
+
+def _aggregate_placebo_horizon_frames(psum: Optional[Dict], actual, columns, horizons, alpha: float,
+                                      labels: pd.Index, n_post: int, fit_relative_effect):
+  """(placebo_by_horizon, placebo_profile) of one POOLED group with `Placebo(horizons=...)`:
+  `_placebo_horizon_frames` for the group's pooled sums.  psum: predicted_mean, spread_mean, pit_mean,
+  n_counted and seen_sum, each [O, K] -- column k what `_aggregate_placebo_frames` takes for the horizon
+  horizons[k]; actual [O, K]; horizons [K] (-1: unused, at the end).  The slice of the first frame at a
+  horizon is the `placebo` frame of that horizon alone; the profile's row at h is its quality without
+  `horizon` (empirical_p on the row h == n_post, against the aggregate's own cumulative rel_effect) and
+  relative_sd, the median over the counted origins of predicted_sd / |predicted|.  psum None, no origin
+  or no horizon: empty frames."""
+  columns = np.asarray(columns).reshape(-1)
+  marks = [] if horizons is None else [(k, int(h)) for k, h in enumerate(np.asarray(horizons).reshape(-1)) if h >= 1]
+  if psum is None or not np.any(columns >= 0) or not marks:
+    index = pd.MultiIndex.from_arrays([labels[:0], np.zeros(0, np.int64)], names=["origin", "horizon"])
+    return (pd.DataFrame({k: np.zeros(0) for k in PLACEBO_COLUMNS}, index=index),
+            pd.DataFrame({k: np.zeros(0) for k in PLACEBO_PROFILE_COLUMNS}, index=pd.Index([], dtype=np.int64, name="horizon")))
+  frames, rows = [], []
+  for k, h in marks:
+    frame, cols = _aggregate_placebo_frame({name: np.asarray(v)[:, k] for name, v in psum.items()},
+                                           np.asarray(actual)[:, k], columns, h, alpha, labels)
+    frames.append(frame)
+    rows.append(_placebo_profile_row(cols, h, alpha, n_post, fit_relative_effect))
+  by_horizon = pd.concat(frames, keys=[h for _, h in marks], names=["horizon", "origin"]).swaplevel().sort_index()
+  profile = pd.DataFrame(rows, index=pd.Index([h for _, h in marks], dtype=np.int64, name="horizon"),
+                         columns=list(PLACEBO_PROFILE_COLUMNS))
+  return by_horizon, profile
 
 
 # --------------------------------------------------------------------------------------
@@ -2001,12 +2050,65 @@ def _draws_session_beside(sess, inputs: Sequence[SeriesInputs], draws, on_device
   return drawn, route == "blocks"
 
 
+def pool_placebo_horizons_available(blocks: bool) -> bool:
+  """Whether the loaded library has ci_session_pool_placebo_horizons (blocks: its `_blocks` form)."""
+  return hasattr(_native.load(), "ci_session_pool_placebo_horizons" + ("_blocks" if blocks else ""))
+
+
+def pool_placebo_horizon_columns(sess, blocks: bool, scale, shift, groups, origins, horizons, init=None,
+                                 one_pass: Optional[bool] = None, max_bytes: int = 1 << 30) -> np.ndarray:
+  """acc [G, O, K, 2, N] of `Session.pool_placebo_horizons` on the open session `sess` (blocks: the
+  `_blocks` entry), however the library and the memory allow it: ONE filter pass where the loaded
+  library has the entry (one_pass None: ask it), the horizon slots in ascending column chunks where the
+  accumulators would take more than max_bytes (the limit of the C entry) -- the columns are independent,
+  so no bit depends on that cut -- and K calls of `pool_placebo` (`pool_placebo_blocks`) where it lacks
+  the entry: the definition, and the bit reference.  groups: one mapping per group; origins: one mapping
+  {place: row} per group; horizons [G, K] (-1: unused, at the end); init: [G, O, K, 2, N] or None.  A
+  group without a used slot among the columns of a call takes no part in it."""
+  hz = np.asarray(horizons, np.int32)
+  n_groups, width = hz.shape
+  if one_pass is None:
+    one_pass = pool_placebo_horizons_available(blocks)
+  slots = max([np.asarray(row).size for m in origins for row in m.values()] + [1])
+  num_draws = int(sess.pb.num_chains * sess.pb.num_results)
+  per_column = n_groups * slots * 2 * num_draws * 8
+  step = max(1, min(width, max_bytes // max(per_column, 1))) if one_pass else 1
+  acc = np.zeros((n_groups, slots, width, 2, num_draws)) if init is None else np.array(init, np.float64)
+  single = sess.pool_placebo_blocks if blocks else sess.pool_placebo
+  for j in range(0, width, step):
+    sub = hz[:, j:j + step]
+    used = (sub > 0).any(axis=1)
+    if not used.any():
+      continue
+    here = [groups[g] if used[g] else {} for g in range(n_groups)]
+    rows = [origins[g] if used[g] else {} for g in range(n_groups)]
+    before = np.ascontiguousarray(acc[:, :, j:j + step]) if init is not None else None
+    if one_pass:
+      table = np.where(used[:, None], sub, np.array([1] + [-1] * (sub.shape[1] - 1), np.int32)[None, :])
+      acc[:, :, j:j + step] = sess.pool_placebo_horizons(scale, shift, here, rows, table, before, blocks=blocks)["acc"]
+    else:
+      acc[:, :, j] = single(scale, shift, here, rows, np.where(used, sub[:, 0], 1),
+                            None if before is None else np.ascontiguousarray(before[:, :, 0]))["acc"]
+  return acc
+
+
 def _placebo_entry_device(drawn, blocks: bool, one: "SeriesInputs", scale, shift, observed, origins, horizon,
-                          simulated=None) -> Dict:
+                          simulated=None, horizons=None) -> Dict:
   """`_placebo_entry_host` -- with simulated = (link, stream) `_placebo_entry_simulated_host` -- through
   the one-series draws session `drawn`: the group table of one group with this member at weight 1,
-  whose accumulators are 0 + 1 * term, the member's own terms."""
+  whose accumulators are 0 + 1 * term, the member's own terms.  horizons [K]: the terms [O, K, N] at the
+  group's horizons (`pool_placebo_horizon_columns`)."""
   origins = np.asarray(origins).reshape(-1)
+  if horizons is not None:
+    if simulated is not None:
+      raise ValueError("the simulated pooled placebo has one horizon")
+    hz = np.asarray(horizons, np.int32).reshape(1, -1)
+    seen = _placebo_entry_seen(one, scale, shift, observed, origins, horizon, horizons=hz[0])
+    width = int((origins >= 0).sum())
+    acc = np.zeros((origins.size, hz.shape[1], 2, drawn.pb.num_chains * drawn.pb.num_results))
+    if width:
+      acc[:width] = pool_placebo_horizon_columns(drawn, blocks, scale, shift, [{0: 1.0}], [{0: origins[:width]}], hz)[0]
+    return dict(s=acc[:, :, 0], v=acc[:, :, 1], **seen)
   link = simulated[0] if simulated is not None else 0
   seen = _placebo_entry_seen(one, scale, shift, observed, origins, horizon, link)
   num_draws = drawn.pb.num_chains * drawn.pb.num_results
@@ -2058,25 +2160,48 @@ def _device_placebo_summaries(sess, part: PlaceboPart, blocks: bool = False):
   return out
 
 
-def _placebo_entry_host(one: "SeriesInputs", draws, scale, shift, observed, origins, horizon) -> Dict:
+def _placebo_entry_host(one: "SeriesInputs", draws, scale, shift, observed, origins, horizon, horizons=None) -> Dict:
   """What one member adds to a pooled placebo forecast, filtered in numpy: for the origins [O] (steps
   of the series; -1: unused, at the end) and the horizon of the GROUP, s and v [O, N] on the data
   scale (`_placebo_summary_host(per_draw=True)`, `_native.placebo_terms_host`), n_counted and seen_sum
   [O] (`_placebo_seen`; 0 in an unused slot) and actual [O], the observed sum of every window
   (`observed`: the series' outcome on the data scale, NaN: none).  draws: the series' pooled
-  parameter draws."""
+  parameter draws.  horizons [K] (-1: unused, at the end; `horizon` their last one): s, v [O, K, N] and
+  the rest [O, K] at the group's horizons, column k what `horizon=horizons[k]` gives, 0 in an unused slot."""
   origins = np.asarray(origins).reshape(-1)
+  if horizons is not None:
+    got = _placebo_summary_host(*one.filter_inputs(), draws, scale, shift, origins, horizon, per_draw=True,
+                                horizons=horizons)
+    s, v = _native.placebo_terms_host(got["C"], got["V"], got["cnt"], scale, shift)
+    return dict(s=s, v=v, **_placebo_entry_seen(one, scale, shift, observed, origins, horizon, horizons=horizons))
   got = _placebo_summary_host(*one.filter_inputs(), draws, scale, shift, origins, horizon, per_draw=True)
   s, v = _native.placebo_terms_host(got["C"], got["V"], got["cnt"], scale, shift)
   return dict(s=s, v=v, **_placebo_entry_seen(one, scale, shift, observed, origins, horizon))
 
 
-def _placebo_entry_seen(one: "SeriesInputs", scale, shift, observed, origins, horizon, link: int = 0) -> Dict:
+def _placebo_entry_seen(one: "SeriesInputs", scale, shift, observed, origins, horizon, link: int = 0,
+                        horizons=None) -> Dict:
   """n_counted, seen_sum and actual [O] of `_placebo_entry_host`: what needs no draws.  Under an
   outcome link (the simulated pooled placebo) seen_sum is the sum of the RAW outcome `observed` over
-  the counted steps (`_placebo_seen_linked`)."""
+  the counted steps (`_placebo_seen_linked`).  horizons [K] (identity link): all three [O, K], the
+  prefixes of the same running sums (`_placebo_seen(horizons=...)`), 0 in an unused horizon slot."""
   origins = np.asarray(origins).reshape(-1)
   observed = np.asarray(observed, np.float64)
+  if horizons is not None:
+    if link:
+      raise ValueError("the pooled placebo at several horizons has no outcome link")
+    hz = [int(h) for h in np.asarray(horizons).reshape(-1)]
+    last = max([h for h in hz if h >= 1] + [1])
+    cnt, seen = _placebo_seen(one.outcome(), one.mask, origins, last, scale, shift, horizons=hz)
+    steps = np.maximum(origins, 0).astype(np.int64)[:, None] + np.arange(last)[None, :]
+    values = observed[np.minimum(steps, observed.shape[0] - 1)]
+    values = np.where(np.isnan(values), 0.0, values)      # (what `np.nansum` adds up, replaced once)
+    actual = np.zeros((origins.size, len(hz)))
+    for k, h in enumerate(hz):
+      if h >= 1:                                          # the sum of the window's own h steps, as at one horizon
+        actual[:, k] = np.add.reduce(values[:, :h], axis=1)
+    actual[origins < 0] = 0.0
+    return dict(n_counted=cnt, seen_sum=np.nan_to_num(seen), actual=actual)
   if link:
     cnt, seen = _placebo_seen_linked(observed, one.mask, origins, horizon, link)
   else:
@@ -2475,15 +2600,15 @@ def _run_sampler(*, ci_data, prior_level_sd, seed, num_results, num_warmup_steps
     drawn = None if route == "host" else open_draws_session(inputs, draws, seed=seed_pair, device=devs[0])
     try:
       if drawn is not None:                # (the same terms through the kernels of a fit's session)
-        placebo_sink(lambda origins, horizon: _placebo_entry_device(
+        placebo_sink(lambda origins, horizon, horizons=None: _placebo_entry_device(
             drawn, route == "blocks", inputs[0], internal.scale, internal.shift, internal.observed, origins,
-            horizon, sink_simulated))
+            horizon, sink_simulated, horizons))
       elif sink_simulated is not None:     # (link, stream): the simulated totals in place of the moments
         placebo_sink(lambda origins, horizon: _placebo_entry_simulated_host(
             inputs[0], pooled, internal.scale, internal.shift, internal.observed, origins, horizon, *sink_simulated))
       else:
-        placebo_sink(lambda origins, horizon: _placebo_entry_host(
-            inputs[0], pooled, internal.scale, internal.shift, internal.observed, origins, horizon))
+        placebo_sink(lambda origins, horizon, horizons=None: _placebo_entry_host(
+            inputs[0], pooled, internal.scale, internal.shift, internal.observed, origins, horizon, horizons))
     finally:
       if drawn is not None:
         drawn.close()

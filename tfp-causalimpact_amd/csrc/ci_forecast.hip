@@ -1,7 +1,7 @@
 // ci_forecast.hip -- the Kalman-filter entries of a finished session behind the C-ABI:
 // ci_session_summarize_predictions[_blocks] (kernels: ci_predict.h, ci_predict_blocks.h),
 // ci_session_summarize_placebo[_blocks], ci_session_summarize_placebo_horizons, ci_session_simulate_placebo[_blocks],
-// ci_session_pool_placebo[_blocks], ci_session_pool_simulated_placebo[_blocks] (kernels: ci_placebo.h,
+// ci_session_pool_placebo[_blocks], ci_session_pool_placebo_horizons[_blocks], ci_session_pool_simulated_placebo[_blocks] (kernels: ci_placebo.h,
 // ci_placebo_blocks.h) and their ci_test_ entries; and ci_session_create_from_draws[_f64], the session
 // that holds what these entries read and nothing else.  A host unit: it instantiates no kernel -- the
 // filters are launched through their units' launch functions, the order statistics through
@@ -254,7 +254,9 @@ static int summarize_placebo(ci_session* s, bool blocks, const double* scale, co
 
 // The horizon table of ci_session_summarize_placebo_horizons: max_horizons in [1, 64], every row with
 // at least one horizon, >= 1, strictly ascending, -1 only at the end.  last [B]: the row's largest.
-static int check_horizon_table(int B, int K, const int32_t* horizons, std::vector<int32_t>& last) {
+// ci_session_pool_placebo_horizons has one row per group (`owner`: what a row belongs to).
+static int check_horizon_table(int B, int K, const int32_t* horizons, std::vector<int32_t>& last,
+                               const char* owner = "series") {
   if (K < 1 || K > 64) return fail("max_horizons must be in [1, 64], got %d", K);
   last.assign(B, 0);
   for (int b = 0; b < B; ++b) {
@@ -269,7 +271,7 @@ static int check_horizon_table(int B, int K, const int32_t* horizons, std::vecto
                     "(slot %d holds %d)", b, i, h);
       last[b] = h;
     }
-    if (last[b] < 1) return fail("horizons[%d] holds no horizon: every series needs at least one", b);
+    if (last[b] < 1) return fail("horizons[%d] holds no horizon: every %s needs at least one", b, owner);
   }
   return 0;
 }
@@ -605,6 +607,116 @@ static int pool_placebo(ci_session* s, bool blocks, const double* scale, const d
   return 0;
 }
 
+// ci_session_pool_placebo_horizons and, with `blocks`, .._blocks: pool_placebo's accumulators and means
+// at K horizons per group from ONE filter pass per chunk of whole entries.  A chunk's two planes
+// (SUM, VAR) [ne * O * K, N] lie in `value` where one entry's 2 * O * K rows fit the scratch's B * T,
+// else in a buffer of the call's own of at most CI_PATHS_MAX_BYTES; placebo_pool_kernel then adds them
+// to the accumulators [G, O * K, 2, N] and placebo_finish_kernel finishes them, both with O * K in the
+// place of O.  Every term is a function of (entry, slot, k, n) alone and the accumulate takes a
+// group's entries in ascending order whatever the cut, so nothing depends on where the chunks are
+// cut.  chunk_entries (tests; 0: the capacity above): the entries of a chunk, at most that capacity;
+// num_chunks (may be NULL): how many it took.
+static int pool_placebo_horizons(ci_session* s, bool blocks, const double* scale, const double* shift,
+                                 int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                 const double* weights, int32_t max_origins, const int32_t* origins,
+                                 int32_t max_horizons, const int32_t* horizons, const double* init, double* out,
+                                 const double* seen, double* predicted_mean, double* spread_mean,
+                                 double* pit_mean, int32_t chunk_entries, int32_t* num_chunks) {
+  if (!s || !scale || !shift || !offsets || !members || !weights || !origins || !horizons || !out)
+    return fail("NULL argument");
+  if (pred_check_session(s, blocks, "ci_session_pool_placebo_horizons")) return 1;
+  const char* who = blocks ? "ci_session_pool_placebo_horizons_blocks" : "ci_session_pool_placebo_horizons";
+  const ci_problem& pb = s->pb;
+  const int B = pb.num_series, T = pb.T, N = pb.num_chains * pb.num_results;
+  const int O = max_origins, K = max_horizons, G = num_groups;
+  if (chunk_entries < 0) return fail("chunk_entries must be at least 1, got %d", chunk_entries);
+  if (check_groups(B, G, offsets, members, weights)) return 1;
+  if (O < 1 || O > T) return fail("max_origins must be in [1, %d], got %d", T, O);
+  if (!seen && (predicted_mean || spread_mean || pit_mean))
+    return fail("predicted_mean, spread_mean and pit_mean need `seen`, the pooled observed sums");
+  std::vector<int32_t> last;             // [G] every group's largest horizon
+  if (check_horizon_table(G, K, horizons, last, "group")) return 1;
+  const int E = offsets[G];
+  std::vector<int> entry_horizon;
+  if (check_pool_plan(s, G, offsets, members, O, origins, last.data(), entry_horizon)) return 1;
+  const size_t OK = (size_t)O * K, rows = (size_t)G * OK;
+  const size_t max_doubles = (size_t)CI_PATHS_MAX_BYTES / sizeof(double);
+  if (rows * 2 > max_doubles / N)
+    return fail("%s: the accumulators of %d groups x %d origins x %d horizons take %zu bytes of device memory "
+                "for %d draws, the limit is %lld: pass the horizon slots in several calls", who, G, O, K,
+                rows * 2 * N * sizeof(double), N, (long long)CI_PATHS_MAX_BYTES);
+  const size_t per = 2 * OK;                     // the rows of one entry, both planes
+  const size_t scratch_rows = (size_t)B * T, own_rows = max_doubles / N;
+  const bool in_scratch = per <= scratch_rows;
+  if (!in_scratch && per > own_rows)
+    return fail("%s: the %d origins x %d horizons of one entry (entry 0) take %zu bytes of device memory for "
+                "%d draws, the limit is %lld", who, O, K, per * N * sizeof(double), N, (long long)CI_PATHS_MAX_BYTES);
+  size_t fit = (in_scratch ? scratch_rows : own_rows) / per;
+  fit = fit > 65535 ? 65535 : fit;               // (grid.y)
+  if (chunk_entries > 0 && (size_t)chunk_entries < fit) fit = (size_t)chunk_entries;
+  const int chunk = (int)fit;
+  if (num_chunks) *num_chunks = (E + chunk - 1) / chunk;
+  ForecastCall c;
+  if (forecast_call(c, s, blocks, scale, shift, E > 0)) return 1;
+  hipStream_t stream = c.stream;
+  SummScratch& w = *c.w;
+  // the horizon row of every entry: its group's
+  const size_t Ea = E ? E : 1;
+  std::vector<int32_t> entry_rows(Ea * K, -1);
+  for (int g = 0; g < G; ++g)
+    for (int k = offsets[g]; k < offsets[g + 1]; ++k)
+      std::copy(horizons + (size_t)g * K, horizons + (size_t)(g + 1) * K, entry_rows.begin() + (size_t)k * K);
+  PoolTables t;                          // acc [G, O, K, 2, N]; tails: the entries' horizon rows [Ea, K]; seen [G, O, K]
+  DevBuf<double> d_own;                  // the planes of a chunk (not in_scratch)
+  if (pool_tables_upload(t, stream, G, O, N, 2 * K, offsets, members, weights, origins, entry_horizon, init,
+                         Ea * K, rows))
+    return 1;
+  int* d_rows = t.tail_ints;
+  HIP_TRY(hipMemcpyAsync(d_rows, entry_rows.data(), Ea * K * sizeof(int), hipMemcpyHostToDevice, stream));
+  const int ne_max = E < chunk ? E : chunk;
+  if (!in_scratch && E > 0) HIP_TRY(d_own.alloc((size_t)ne_max * per * N));
+  double* d_seen = t.tail_doubles;
+  if (seen) HIP_TRY(hipMemcpyAsync(d_seen, seen, rows * sizeof(double), hipMemcpyHostToDevice, stream));
+  double* planes = in_scratch ? w.value.p : d_own.p;
+  ci::PlaceboPoolHorizonsArgs a;
+  a.p = c.p; a.p.out = planes;
+  a.O = O; a.K = K;
+  ci::PlaceboBlocksPoolHorizonsArgs ab;
+  ab.q.p = a.p; ab.m = c.m; ab.q.O = O; ab.K = K; ab.q.horizon = nullptr;
+  for (int c0 = 0; c0 < E; c0 += chunk) {
+    const int c1 = E - c0 < chunk ? E : c0 + chunk;
+    const size_t plane = (size_t)(c1 - c0) * OK * N;   // the doubles of one plane of this chunk
+    if (blocks) {
+      ab.q.series_of = t.members + c0; ab.q.origins = t.origins + (size_t)c0 * O;
+      ab.horizons = d_rows + (size_t)c0 * K; ab.var = planes + plane;
+      HIP_TRY((c.f64 ? ci::placebo_blocks_pool_horizons_launch_f64 : ci::placebo_blocks_pool_horizons_launch)(stream, c1 - c0, ab));
+    } else {
+      a.series_of = t.members + c0; a.origins = t.origins + (size_t)c0 * O;
+      a.horizons = d_rows + (size_t)c0 * K; a.rows = (size_t)(c1 - c0) * OK;
+      HIP_TRY((c.f64 ? ci::placebo_pool_horizons_launch_f64 : ci::placebo_pool_horizons_launch)(stream, c1 - c0, c.has_slope, c.NS, a));
+    }
+    HIP_TRY(ci::placebo_pool_launch(stream, N, (int)OK, G, 0, c0, c1, t.offsets, t.weights, planes, t.acc));
+    HIP_TRY(ci::placebo_pool_launch(stream, N, (int)OK, G, 1, c0, c1, t.offsets, t.weights, planes + plane, t.acc));
+  }
+  HIP_TRY(hipMemcpyAsync(out, t.acc, t.acc_n * sizeof(double), hipMemcpyDeviceToHost, stream));
+  // the means over the draws, one matrix at a time and as many rows as `value` and `obs` hold
+  const size_t per_pass = scratch_rows;
+  auto finish = [&](int which, double* mean_dst) -> int {
+    for (size_t r0 = 0; r0 < rows; r0 += per_pass) {
+      const size_t nr = rows - r0 < per_pass ? rows - r0 : per_pass;
+      HIP_TRY(ci::placebo_finish_launch(stream, N, r0, nr, which, t.acc, d_seen, w.value.p));
+      HIP_TRY(ci::comp_launch_row_stats(stream, nr, N, w.value.p, w.obs.p, nullptr));
+      HIP_TRY(hipMemcpyAsync(mean_dst + r0, w.obs.p, nr * sizeof(double), hipMemcpyDeviceToHost, stream));
+    }
+    return 0;
+  };
+  if (predicted_mean && finish(ci::PLACEBO_SUM, predicted_mean)) return 1;
+  if (spread_mean && finish(ci::PLACEBO_SPREAD, spread_mean)) return 1;
+  if (pit_mean && finish(ci::PLACEBO_PIT, pit_mean)) return 1;
+  HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
+
 // The SIMULATED placebo forecasts of pooled sums (include/causalimpact_amd.h): the entries of the group
 // table pass through `value` at most `chunk` at a time -- ONE simulation pass (the entry-table build
 // of simulate_placebo's kernel; TOTAL is a function of (series, origin, slot, horizon, n) alone) and
@@ -918,6 +1030,41 @@ int ci_test_session_pool_placebo_blocks(ci_session* s, const double* scale, cons
     return fail("chunk_entries must be in [1, %d] (the session's series), got %d", s->pb.num_series, chunk_entries);
   return pool_placebo(s, true, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
                       horizon, init, out, seen, predicted_mean, spread_mean, pit_mean, chunk_entries);
+}
+
+int ci_session_pool_placebo_horizons(ci_session* s, const double* scale, const double* shift,
+                                     int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                     const double* weights, int32_t max_origins, const int32_t* origins,
+                                     int32_t max_horizons, const int32_t* horizons, const double* init,
+                                     double* out, const double* seen, double* predicted_mean,
+                                     double* spread_mean, double* pit_mean) {
+  return pool_placebo_horizons(s, false, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
+                               max_horizons, horizons, init, out, seen, predicted_mean, spread_mean, pit_mean, 0,
+                               nullptr);
+}
+
+int ci_session_pool_placebo_horizons_blocks(ci_session* s, const double* scale, const double* shift,
+                                            int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                            const double* weights, int32_t max_origins, const int32_t* origins,
+                                            int32_t max_horizons, const int32_t* horizons, const double* init,
+                                            double* out, const double* seen, double* predicted_mean,
+                                            double* spread_mean, double* pit_mean) {
+  return pool_placebo_horizons(s, true, scale, shift, num_groups, offsets, members, weights, max_origins, origins,
+                               max_horizons, horizons, init, out, seen, predicted_mean, spread_mean, pit_mean, 0,
+                               nullptr);
+}
+
+int ci_test_session_pool_placebo_horizons(ci_session* s, int32_t blocks, const double* scale, const double* shift,
+                                          int32_t num_groups, const int32_t* offsets, const int32_t* members,
+                                          const double* weights, int32_t max_origins, const int32_t* origins,
+                                          int32_t max_horizons, const int32_t* horizons, const double* init,
+                                          double* out, const double* seen, double* predicted_mean,
+                                          double* spread_mean, double* pit_mean, int32_t chunk_entries,
+                                          int32_t* num_chunks) {
+  if (chunk_entries < 1) return fail("chunk_entries must be at least 1, got %d", chunk_entries);
+  return pool_placebo_horizons(s, blocks != 0, scale, shift, num_groups, offsets, members, weights, max_origins,
+                               origins, max_horizons, horizons, init, out, seen, predicted_mean, spread_mean,
+                               pit_mean, chunk_entries, num_chunks);
 }
 
 int ci_session_pool_simulated_placebo(ci_session* s, const double* scale, const double* shift,

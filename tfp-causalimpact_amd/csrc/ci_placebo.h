@@ -669,4 +669,173 @@ __global__ __launch_bounds__(64) void placebo_horizons_kernel(PlaceboHorizonsArg
   }
 }
 
+// ---- The POOLED terms at several horizons in one filter pass (ci_session_pool_placebo_horizons;
+// DESIGN.md "Pooled placebo forecasts at several horizons").  The entry-table build of the kernel
+// above: grid row e filters series series_of[e] from the origins' row e and runs the forecast branch
+// to the last used horizon of horizons[e, .] -- the row of the entry's group, handed in per entry as
+// PlaceboArgs::horizon is.  At every checkpoint h == horizons[e, k] the lane stores the two terms a
+// pooled sum adds up, with placebo_kernel's expressions and roundings:
+//   SUM = C * scale[b] + cnt * shift[b] (separate roundings);  VAR = (V * scale[b]) * scale[b]
+// both 0 where cnt == 0, in the unused origin slots and in the unused horizon slots.  No A, no erfc:
+// the observed sums enter at placebo_finish_kernel.  Two planes of `rows` = E * O * K rows each,
+//   out[(plane * rows + (e * O + slot) * K + k) * N + n],  plane 0 SUM, 1 VAR
+// so that placebo_pool_kernel and placebo_finish_kernel read them with O * K in the place of O.
+struct PlaceboPoolHorizonsArgs {
+  PredArgs p;                      // the filter's inputs; p.out [2, rows, N], p.ll unused
+  int O;                           // origin slots per entry
+  const int* origins;              // [E, O] strictly ascending, -1: unused (at the end)
+  int K;                           // horizon slots per entry
+  const int* horizons;             // [E, K] strictly ascending, -1: unused (at the end)
+  const int* series_of;            // [E] the series of every entry
+  size_t rows;                     // E * O * K: the rows of one plane
+};
+
+// The launch (ci_placebo.hip): placebo_pool_horizons_kernel<has_slope, num_seasons> over E entries;
+// num_seasons 0 (no block) or 2..7.
+hipError_t placebo_pool_horizons_launch(hipStream_t stream, int E, int has_slope, int num_seasons,
+                                        const PlaceboPoolHorizonsArgs& args);
+hipError_t placebo_pool_horizons_launch_f64(hipStream_t stream, int E, int has_slope, int num_seasons,
+                                            const PlaceboPoolHorizonsArgs& args);
+
+// grid (ceil(N / 64), entries of the launch), block 64.
+template <int HAS_SLOPE, int NS, class IN = float>
+__global__ __launch_bounds__(64) void placebo_pool_horizons_kernel(PlaceboPoolHorizonsArgs k) {
+  constexpr int N1 = NS ? NS - 1 : 0, O = 1 + HAS_SLOPE, D = O + N1, NP = D * (D + 1) / 2;
+  constexpr int ZS = O < D ? O : 0;              // the block's first effect (NS > 0)
+  const int n = blockIdx.x * 64 + threadIdx.x, N = k.p.N, T = k.p.T, NO = k.O, K = k.K;
+  const size_t e = blockIdx.y, b = (size_t)k.series_of[e];
+  if (n >= N) return;
+  const int Tb = k.p.series_T ? k.p.series_T[b] : T;
+  const size_t bn = b * N + n;
+  const double so = (double)((const IN*)k.p.obs)[bn], H = so * so;
+  const double sl = (double)((const IN*)k.p.lscale)[bn], q_level = sl * sl;
+  double q_slope = 0.0, q_drift = 0.0;
+  if (HAS_SLOPE) {
+    const double ss = (double)((const IN*)k.p.sscale)[bn];
+    q_slope = ss * ss;
+  }
+  if (NS) {
+    const double q = (double)((const IN*)k.p.drift)[bn] / (double)NS;
+    q_drift = q * q;
+  }
+  const double scale = k.p.scales[b], shift = k.p.shifts[b];
+  const double* init = k.p.init + 4 * b;
+  const IN* y = (const IN*)k.p.y + b * T;
+  const uint8_t* mask = k.p.mask + b * T;
+  const double* reg = k.p.reg ? k.p.reg + b * T * N + n : nullptr;
+  const size_t plane = k.rows * N;               // the doubles of one plane
+  double* out = k.p.out + e * NO * K * N + n;    // row (slot * K + kc) of the entry, plane SUM
+  const int* org = k.origins + e * NO;
+  const int* hz = k.horizons + e * K;
+  int Hb = 0;                                    // the row's last used horizon
+  for (int i = 0; i < K; ++i) Hb = hz[i] > 0 ? hz[i] : Hb;
+
+  double a[D], P[NP];
+#define PM(i, j) P[pred_sym<D>(i, j)]
+#define FM(i, j) fP[pred_sym<D>(i, j)]
+#pragma unroll
+  for (int i = 0; i < D; ++i) a[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) P[i] = 0.0;
+  a[0] = init[0];
+  PM(0, 0) = init[1];
+  if (HAS_SLOPE) PM(1, 1) = init[2];
+  if (NS) {
+    const double v = init[3];
+#pragma unroll
+    for (int i = 0; i < N1; ++i)
+#pragma unroll
+      for (int j = i; j < N1; ++j) PM(O + i, O + j) = v * ((i == j ? 1.0 : 0.0) - 1.0 / (double)NS);
+  }
+
+  int slot = 0;
+  int next = org[0];                             // uniform over the wavefront, as everything of the entry
+  for (int t = 0; t < Tb && next >= 0; ++t) {
+    if (t == next) {
+      // the forecast branch, from a copy of the predicted moments (placebo_kernel's, with checkpoints)
+      double fa[D], fP[NP], r[D];
+#pragma unroll
+      for (int i = 0; i < D; ++i) fa[i] = a[i], r[i] = 0.0;
+#pragma unroll
+      for (int i = 0; i < NP; ++i) fP[i] = P[i];
+      double V = 0.0, C = 0.0;
+      int cnt = 0;
+      double* row = out + (size_t)slot * K * N;
+      int kc = 0;
+      int check = hz[0];                         // the next checkpoint: uniform, as the horizons
+      for (int h = 0; h < Hb; ++h) {
+        const int u = t + h;
+        double pz[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) pz[i] = NS ? FM(i, 0) + FM(i, ZS) : FM(i, 0);
+        if (mask[u] == 0) {
+          const double m = NS ? fa[0] + fa[ZS] : fa[0];
+          const double zr = NS ? r[0] + r[ZS] : r[0];
+          const double zpz = NS ? pz[0] + pz[ZS] : pz[0];
+          C += m + (reg ? reg[(size_t)u * N] : 0.0);
+          cnt += 1;
+          V += (2.0 * zr + zpz) + H;
+#pragma unroll
+          for (int i = 0; i < D; ++i) r[i] += pz[i];
+        }
+        if (h + 1 == check) {
+          double sum = 0.0, var = 0.0;
+          if (cnt > 0) {
+            sum = __dadd_rn(__dmul_rn(C, scale), __dmul_rn((double)cnt, shift));
+            var = __dmul_rn(__dmul_rn(V, scale), scale);
+          }
+          double* at = row + (size_t)kc * N;
+          at[0] = sum;
+          at[plane] = var;
+          ++kc;
+          check = kc < K ? hz[kc] : -1;
+        }
+        if (h + 1 >= Hb) break;
+        if (HAS_SLOPE) r[0] += r[1];
+        bool change = false;
+        if constexpr (NS > 0) {
+          change = k.p.season_change[u] != 0;
+          if (change) pred_season_rotate<O, N1, D>(r);
+        }
+        placebo_propagate<HAS_SLOPE, NS, D>(fa, fP, change, q_level, q_slope, q_drift);
+      }
+      for (; kc < K; ++kc) {                     // the unused horizon slots
+        double* at = row + (size_t)kc * N;
+        at[0] = 0.0;
+        at[plane] = 0.0;
+      }
+      ++slot;
+      next = slot < NO ? org[slot] : -1;
+      if (next < 0) break;
+    }
+    // the filter's step t (predict_kernel)
+    double pz[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) pz[i] = NS ? PM(i, 0) + PM(i, ZS) : PM(i, 0);
+    if (mask[t] == 0) {
+      const double m = NS ? a[0] + a[ZS] : a[0];
+      const double F = (NS ? pz[0] + pz[ZS] : pz[0]) + H;
+      const double f = m + (reg ? reg[(size_t)t * N] : 0.0);
+      const double v = (double)y[t] - f;
+#pragma unroll
+      for (int i = 0; i < D; ++i) a[i] += (pz[i] / F) * v;
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) PM(i, j) -= pz[i] * pz[j] / F;
+    }
+    if (t + 1 >= Tb) break;
+    bool change = false;
+    if constexpr (NS > 0) change = k.p.season_change[t] != 0;
+    placebo_propagate<HAS_SLOPE, NS, D>(a, P, change, q_level, q_slope, q_drift);
+  }
+#undef PM
+#undef FM
+  for (size_t i = (size_t)slot * K; i < (size_t)NO * K; ++i) {   // the unused origin slots
+    double* at = out + i * N;
+    at[0] = 0.0;
+    at[plane] = 0.0;
+  }
+}
+
 }  // namespace ci

@@ -1,5 +1,5 @@
 // Instantiation unit of the placebo forecasts (ci_placebo.h) and their launches;
-// ci_session_summarize_placebo, ci_session_pool_placebo, ci_session_simulate_placebo and
+// ci_session_summarize_placebo[_horizons], ci_session_pool_placebo[_horizons], ci_session_simulate_placebo and
 // ci_session_pool_simulated_placebo (ci_forecast.hip) call them.  With -DCI_FILTER_F64: the float64-input
 // builds of the two filters and their launches with the suffix _f64; the kernels over accumulators and
 // totals read no input of a session and belong to the float32 build alone.
@@ -123,6 +123,34 @@ hipError_t CI_FILTER_NAME(placebo_horizons_launch)(hipStream_t stream, int nb, i
   if (!fn || nb < 1 || nb > 65535 || args.O < 1 || args.K < 1 || args.rows != (size_t)nb * args.O * args.K)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3((args.p.N + 63) / 64, nb), dim3(64), 0, stream, args);
+  return hipGetLastError();
+}
+
+using PlaceboPoolHorizonsFn = void (*)(PlaceboPoolHorizonsArgs);
+
+template <int HAS_SLOPE> static PlaceboPoolHorizonsFn placebo_pool_horizons_fn(int ns) {
+  switch (ns) {
+    case 0: return placebo_pool_horizons_kernel<HAS_SLOPE, 0, CI_FILTER_F>;
+    case 2: return placebo_pool_horizons_kernel<HAS_SLOPE, 2, CI_FILTER_F>;
+    case 3: return placebo_pool_horizons_kernel<HAS_SLOPE, 3, CI_FILTER_F>;
+    case 4: return placebo_pool_horizons_kernel<HAS_SLOPE, 4, CI_FILTER_F>;
+    case 5: return placebo_pool_horizons_kernel<HAS_SLOPE, 5, CI_FILTER_F>;
+    case 6: return placebo_pool_horizons_kernel<HAS_SLOPE, 6, CI_FILTER_F>;
+    case 7: return placebo_pool_horizons_kernel<HAS_SLOPE, 7, CI_FILTER_F>;
+    default: return nullptr;
+  }
+}
+
+// The two planes [E * O * K, N] each of E entries of a group table (args.series_of, origins and
+// horizons from the launch's first entry on) in args.p.out, one filter pass; num_seasons 0 or 2..7.
+hipError_t CI_FILTER_NAME(placebo_pool_horizons_launch)(hipStream_t stream, int E, int has_slope, int num_seasons,
+                                        const PlaceboPoolHorizonsArgs& args) {
+  const PlaceboPoolHorizonsFn fn = has_slope ? placebo_pool_horizons_fn<1>(num_seasons)
+                                             : placebo_pool_horizons_fn<0>(num_seasons);
+  if (!fn || E < 1 || E > 65535 || args.O < 1 || args.K < 1 || !args.series_of ||
+      args.rows != (size_t)E * args.O * args.K)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fn, dim3((args.p.N + 63) / 64, E), dim3(64), 0, stream, args);
   return hipGetLastError();
 }
 

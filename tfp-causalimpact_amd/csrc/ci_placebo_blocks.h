@@ -25,6 +25,7 @@
 namespace ci {
 
 constexpr int PLACEBO_SUM_VAR = 4;  // (entry-table build only) SUM into `out` and VAR into `var`
+constexpr int PLACEBO_SUM_VAR_HORIZONS = 5;  // (entry-table build only) SUM_VAR at every checkpoint of the entry's horizon row
 
 struct PlaceboBlocksArgs {
   PlaceboArgs q;                   // q.p as PredBlocksArgs::p; q.series_of read by the entry-table build only
@@ -35,12 +36,26 @@ struct PlaceboBlocksPoolArgs : PlaceboBlocksArgs {   // q.series_of [E], q.origi
   double* var;                     // [E, O, N]: VAR
 };
 
+// The entry-table build at SEVERAL HORIZONS (ci_session_pool_placebo_horizons_blocks; the block-model
+// twin of placebo_pool_horizons_kernel): the forecast branch runs to the last used horizon of
+// horizons[e, .] and at every checkpoint h == horizons[e, k] lane 0 stores SUM into `out` and VAR into
+// `var`, rows (e * O + slot) * K + k, with the expressions of SUM_VAR; 0 in the unused origin and
+// horizon slots.  q.horizon is not read.  The checkpoint test is uniform over the workgroup -- the
+// horizons belong to the entry -- and no barrier sits inside it.
+struct PlaceboBlocksPoolHorizonsArgs : PlaceboBlocksPoolArgs {   // q.p.out, var: [E, O, K, N]
+  int K;                           // horizon slots per entry
+  const int* horizons;             // [E, K] strictly ascending, -1: unused (at the end)
+};
+
 // The launches (ci_placebo_blocks.hip): placebo_blocks_kernel<G, out> over B series; its entry-table
-// build <G, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs> over E entries.
+// builds <G, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs> and <G, PLACEBO_SUM_VAR_HORIZONS,
+// PlaceboBlocksPoolHorizonsArgs> over E entries.
 hipError_t placebo_blocks_launch(hipStream_t stream, int B, int out, const PlaceboBlocksArgs& args);
 hipError_t placebo_blocks_pool_launch(hipStream_t stream, int E, const PlaceboBlocksPoolArgs& args);
 hipError_t placebo_blocks_launch_f64(hipStream_t stream, int B, int out, const PlaceboBlocksArgs& args);
 hipError_t placebo_blocks_pool_launch_f64(hipStream_t stream, int E, const PlaceboBlocksPoolArgs& args);
+hipError_t placebo_blocks_pool_horizons_launch(hipStream_t stream, int E, const PlaceboBlocksPoolHorizonsArgs& args);
+hipError_t placebo_blocks_pool_horizons_launch_f64(hipStream_t stream, int E, const PlaceboBlocksPoolHorizonsArgs& args);
 
 // The series of grid row e: with an entry table that of entry e, else e itself.
 template <bool ENTRIES>
@@ -53,8 +68,10 @@ __device__ __forceinline__ size_t pb_series_of(const PlaceboArgs& q, size_t e) {
 // (the entry-table build) (ceil(N / (64 / G)), E).
 template <int G, int OUT, class ARGS = PlaceboBlocksArgs, class IN = float>
 __global__ __launch_bounds__(64) void placebo_blocks_kernel(ARGS k) {
-  constexpr bool ENTRIES = OUT == PLACEBO_SUM_VAR;
-  static_assert(ENTRIES == std::is_same<ARGS, PlaceboBlocksPoolArgs>::value, "SUM_VAR is the entry-table build's selector");
+  constexpr bool HORIZONS = OUT == PLACEBO_SUM_VAR_HORIZONS;
+  constexpr bool ENTRIES = OUT == PLACEBO_SUM_VAR || HORIZONS;
+  static_assert((OUT == PLACEBO_SUM_VAR) == std::is_same<ARGS, PlaceboBlocksPoolArgs>::value, "SUM_VAR is the entry-table build's selector");
+  static_assert(HORIZONS == std::is_same<ARGS, PlaceboBlocksPoolHorizonsArgs>::value, "SUM_VAR_HORIZONS is the several-horizons build's selector");
   constexpr int FPW = 64 / G;
   __shared__ PbShared sh;
   const PredArgs& p = k.q.p;
@@ -76,7 +93,17 @@ __global__ __launch_bounds__(64) void placebo_blocks_kernel(ARGS k) {
   double* var = nullptr;
   if constexpr (ENTRIES) var = k.var + e * NO * N + n;
   const int* org = k.q.origins + e * NO;
-  const int Hb = k.q.horizon[e];
+  int Hb = 0, K = 1;                             // (HORIZONS) Hb: the row's last used horizon
+  const int* hz = nullptr;
+  if constexpr (HORIZONS) {
+    K = k.K;
+    hz = k.horizons + e * K;
+    for (int i = 0; i < K; ++i) Hb = hz[i] > 0 ? hz[i] : Hb;
+    out = p.out + e * NO * K * N + n;            // row (slot * K + kc) of the entry
+    var = k.var + e * NO * K * N + n;
+  } else {
+    Hb = k.q.horizon[e];
+  }
 
   int slot = 0;
   int next = org[0];                             // uniform over the wavefront, as everything of the origins
@@ -89,6 +116,8 @@ __global__ __launch_bounds__(64) void placebo_blocks_kernel(ARGS k) {
       for (int j = 0; j < G; ++j) fP[j] = P[j];
       double V = 0.0, C = 0.0, A = 0.0;
       int cnt = 0;
+      int kc = 0, check = -1;                    // (HORIZONS) the next checkpoint: uniform, as the horizons
+      if constexpr (HORIZONS) check = hz[0];
       for (int h = 0; h < Hb; ++h) {
         const int u = t + h;
         double pz, m, zpz;
@@ -98,25 +127,50 @@ __global__ __launch_bounds__(64) void placebo_blocks_kernel(ARGS k) {
           __syncthreads();
           const double zr = pb_zsum(c, c.xc);
           C += m + (reg ? reg[(size_t)u * N] : 0.0);
-          A += (double)y[u];
+          if constexpr (!HORIZONS) A += (double)y[u];   // (the pooled terms hold no A)
           cnt += 1;
           V += (2.0 * zr + zpz) + H;
           r += pz;
         }
+        if constexpr (HORIZONS) {
+          if (h + 1 == check) {                  // no barrier in here
+            double sum = 0.0, vr = 0.0;
+            if (cnt > 0) {
+              sum = __dadd_rn(__dmul_rn(C, scale), __dmul_rn((double)cnt, shift));
+              vr = __dmul_rn(__dmul_rn(V, scale), scale);
+            }
+            if (writer) {
+              const size_t at = ((size_t)slot * K + kc) * N;
+              out[at] = sum;
+              var[at] = vr;
+            }
+            ++kc;
+            check = kc < K ? hz[kc] : -1;
+          }
+        }
         if (h + 1 >= Hb) break;
         pb_transition<G, true>(c, u, fa, r, fP);
       }
-      double res = 0.0;
-      if (cnt > 0) {
-        const double err = A - C;
-        if (OUT == PLACEBO_SUM || OUT == PLACEBO_SUM_VAR) res = __dadd_rn(__dmul_rn(C, scale), __dmul_rn((double)cnt, shift));
-        else if (OUT == PLACEBO_SPREAD) res = __dmul_rn(__dmul_rn(__dadd_rn(V, __dmul_rn(err, err)), scale), scale);
-        else if (OUT == PLACEBO_VAR) res = __dmul_rn(__dmul_rn(V, scale), scale);
-        else res = 0.5 * erfc(-err / sqrt(2.0 * V));
-      }
-      if (writer) out[(size_t)slot * N] = res;
-      if constexpr (ENTRIES) {
-        if (writer) var[(size_t)slot * N] = cnt > 0 ? __dmul_rn(__dmul_rn(V, scale), scale) : 0.0;
+      if constexpr (HORIZONS) {
+        if (writer)
+          for (; kc < K; ++kc) {                 // the unused horizon slots
+            const size_t at = ((size_t)slot * K + kc) * N;
+            out[at] = 0.0;
+            var[at] = 0.0;
+          }
+      } else {
+        double res = 0.0;
+        if (cnt > 0) {
+          const double err = A - C;
+          if (OUT == PLACEBO_SUM || OUT == PLACEBO_SUM_VAR) res = __dadd_rn(__dmul_rn(C, scale), __dmul_rn((double)cnt, shift));
+          else if (OUT == PLACEBO_SPREAD) res = __dmul_rn(__dmul_rn(__dadd_rn(V, __dmul_rn(err, err)), scale), scale);
+          else if (OUT == PLACEBO_VAR) res = __dmul_rn(__dmul_rn(V, scale), scale);
+          else res = 0.5 * erfc(-err / sqrt(2.0 * V));
+        }
+        if (writer) out[(size_t)slot * N] = res;
+        if constexpr (ENTRIES) {
+          if (writer) var[(size_t)slot * N] = cnt > 0 ? __dmul_rn(__dmul_rn(V, scale), scale) : 0.0;
+        }
       }
       ++slot;
       next = slot < NO ? org[slot] : -1;
@@ -134,12 +188,20 @@ __global__ __launch_bounds__(64) void placebo_blocks_kernel(ARGS k) {
     if (t + 1 >= T) break;
     pb_transition<G, false>(c, t, a, unused, P);
   }
-  if constexpr (ENTRIES) {
+  if constexpr (HORIZONS) {
     if (writer)
-      for (int i = slot; i < NO; ++i) var[(size_t)i * N] = 0.0;
+      for (size_t i = (size_t)slot * K; i < (size_t)NO * K; ++i) {   // the unused origin slots
+        out[i * N] = 0.0;
+        var[i * N] = 0.0;
+      }
+  } else {
+    if constexpr (ENTRIES) {
+      if (writer)
+        for (int i = slot; i < NO; ++i) var[(size_t)i * N] = 0.0;
+    }
+    if (writer)
+      for (; slot < NO; ++slot) out[(size_t)slot * N] = 0.0;
   }
-  if (writer)
-    for (; slot < NO; ++slot) out[(size_t)slot * N] = 0.0;
 }
 
 // The SIMULATED placebo forecasts of ci_placebo.h (placebo_sim_kernel: its definition, line by line)

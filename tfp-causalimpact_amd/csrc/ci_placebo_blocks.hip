@@ -1,5 +1,5 @@
 // Instantiation unit of the block-model placebo forecasts (ci_placebo_blocks.h) and their launch;
-// ci_session_summarize_placebo_blocks, ci_session_pool_placebo_blocks, ci_session_simulate_placebo_blocks and
+// ci_session_summarize_placebo_blocks, ci_session_pool_placebo[_horizons]_blocks, ci_session_simulate_placebo_blocks and
 // ci_session_pool_simulated_placebo_blocks (ci_forecast.hip) call them.  With -DCI_FILTER_F64: the
 // float64-input builds and the launches with the suffix _f64.
 #include "ci_placebo_blocks.h"
@@ -36,6 +36,24 @@ hipError_t CI_FILTER_NAME(placebo_blocks_pool_launch)(hipStream_t stream, int E,
                                     : G == 16 ? placebo_blocks_kernel<16, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs, CI_FILTER_F>
                                     : G == 32 ? placebo_blocks_kernel<32, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs, CI_FILTER_F>
                                     : placebo_blocks_kernel<64, PLACEBO_SUM_VAR, PlaceboBlocksPoolArgs, CI_FILTER_F>;
+  const int fpw = 64 / G;
+  hipLaunchKernelGGL(fn, dim3((args.q.p.N + fpw - 1) / fpw, E), dim3(64), 0, stream, args);
+  return hipGetLastError();
+}
+
+// One pass over E entries of a group table at the K checkpoints of every entry's horizon row: SUM into
+// args.q.p.out, VAR into args.var, [E, O, K, N] each; args.m.d <= 64.
+hipError_t CI_FILTER_NAME(placebo_blocks_pool_horizons_launch)(hipStream_t stream, int E,
+                                                               const PlaceboBlocksPoolHorizonsArgs& args) {
+  if (args.m.d < 1 || args.m.d > PB_MAX_STATE || !args.q.series_of || !args.var || !args.horizons || args.K < 1 ||
+      E < 1 || E > 65535)
+    return hipErrorInvalidValue;
+  const int G = blocks_group_size(args.m.d);
+  void (*fn)(PlaceboBlocksPoolHorizonsArgs) =
+      G == 8 ? placebo_blocks_kernel<8, PLACEBO_SUM_VAR_HORIZONS, PlaceboBlocksPoolHorizonsArgs, CI_FILTER_F>
+      : G == 16 ? placebo_blocks_kernel<16, PLACEBO_SUM_VAR_HORIZONS, PlaceboBlocksPoolHorizonsArgs, CI_FILTER_F>
+      : G == 32 ? placebo_blocks_kernel<32, PLACEBO_SUM_VAR_HORIZONS, PlaceboBlocksPoolHorizonsArgs, CI_FILTER_F>
+                : placebo_blocks_kernel<64, PLACEBO_SUM_VAR_HORIZONS, PlaceboBlocksPoolHorizonsArgs, CI_FILTER_F>;
   const int fpw = 64 / G;
   hipLaunchKernelGGL(fn, dim3((args.q.p.N + fpw - 1) / fpw, E), dim3(64), 0, stream, args);
   return hipGetLastError();
